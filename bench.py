@@ -26,6 +26,13 @@ and relays rank 0's line; under torch.distributed.run it uses the ranks it is gi
 Rank 0 prints ONE JSON line.  `value` = exact (line, grid-point) contributions of the
 reference's scatter loop (pyradClasses.py:392-400) summed over all ranks and steps / the
 max-over-ranks wall time.
+
+A plain run sets up, warms up, times the --steps steps and prints the line (headline, config,
+pairs).  `--full` adds everything else after the timed region: HIP events in every
+--profile-every-th timed step, the steady state in --blocks blocks, the per-kernel pass, the
+all-direct kernel, the budget and per-list legs, the sharded-step breakdown, the batched-gather
+check, the CPU baseline, the API-path and in-flight legs and the other workloads' legs.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64).
 """
 from __future__ import annotations
 
@@ -720,6 +727,48 @@ def run_ranks(plan, timeout_s: float = 3000.0) -> int:
     return rc
 
 
+def step_outputs(L, is_column, layer_arrays, gathered, gather):
+    """name -> float64 array(s): what a caller of the timed step receives from resident set ``L``, as
+    ResidentLayer.results / ResidentColumn.results name them.  A cell: absorption coefficient, transmittance and
+    outgoing radiance over the grid; a column: the outgoing spectrum (+ every layer's transmittance, one array per
+    layer, when the step writes them).  Sharded: the arrays the all-gather assembled over the whole grid, the others
+    over this rank's own points."""
+    own = slice(0, L.n) if L.plan is None else slice(L.first, L.first + L.count)
+    if is_column:
+        if L.plan is not None and not L.plan.in_place and gathered:
+            toa = L.plan.assemble(L.I_gathered.download(L.S * L.world))
+        else:
+            toa = L.I_toa.download(L.n)
+        out = {"toa": toa if gathered else toa[own]}
+        if layer_arrays:
+            out["transmittance"] = [c.trans.download(L.n)[own] for c in L.layers]
+        return out
+    full = {"abs_coef": gathered and gather in ("abs_coef", "all"), "transmittance": gathered and gather == "all",
+            "transmission": gathered and gather == "all"}
+    bufs = {"abs_coef": L.abs_coef, "transmittance": L.trans, "transmission": L.I_out}
+    return {k: (L.spectrum_host(b) if full[k] else L.spectrum_host(b)[own]) for k, b in bufs.items()}
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=64_000_000):
+    """Write every array (or list of equal-length rows) as out_dir/<name>.npy in float64.  Above ``limit_bytes`` in
+    all, every array keeps the same fixed, seeded sample of its points (last axis), sized so that the files fit."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = {k: (v if isinstance(v, list) else [v]) for k, v in arrays.items()}
+    total = sum(8 * r.size for v in rows.values() for r in v)
+    budget = limit_bytes - 4096 * len(rows)                     # (room for the .npy headers)
+    info = {}
+    for name, v in rows.items():
+        n = v[0].size
+        pick = None
+        if total > budget:
+            pick = np.sort(np.random.default_rng(0).choice(n, size=int(n * budget // total), replace=False))
+        a = np.stack([np.asarray(r if pick is None else r[pick], dtype=np.float64) for r in v])
+        a = a if isinstance(arrays[name], list) else a[0]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(a.shape), "sampled_from_points": None if pick is None else n}
+    return {"dir": out_dir, "arrays": info}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -735,7 +784,7 @@ def main():
     ap.add_argument("--precondition-seconds", type=float, default=0.3,
                     help="setup runs the step for this long before the warm-up steps so that the GPU is at its sustained clocks")
     ap.add_argument("--profile-every", type=int, default=4,
-                    help="HIP events around the dominant kernel in every n-th timed step only (default 4; 1 = every step)")
+                    help="--full: HIP events around the dominant kernel in every n-th timed step only (default 4; 1 = every step)")
     ap.add_argument("--column-layer-arrays", type=int, default=0,
                     help="C5: 1 also writes every layer's absorption coefficient and transmittance arrays (default 0: "
                          "the column step keeps them in registers and writes the outgoing spectrum only)")
@@ -768,8 +817,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--legs", default="auto",
                     help="other BASELINE configurations timed after the line's own and reported as workload_legs (untimed-region style, "
-                         "not the value): a comma list of C1,C2,C3,C5 | none | auto = C1,C2,C5 beside the default workload on one GPU, "
-                         "and C5 sharded N-way with its single all-gather under --gpus N")
+                         "not the value): a comma list of C1,C2,C3,C5 | none | auto = with --full, C1,C2,C5 beside the default workload "
+                         "on one GPU, and C5 sharded N-way with its single all-gather under --gpus N; none in a plain run")
     ap.add_argument("--no-direct-pass", action="store_true",
                     help="skip the extra untimed pass of the all-direct kernel (profiles/collect.sh: keeps the PMC passes "
                          "to the kernels of the timed path)")
@@ -790,11 +839,18 @@ def main():
                          "absorption coefficient (north_star asks 1e-6), still fp64 (lbl_set_option accuracy).  The exact line "
                          "carries the budget mode's step as an extra untimed leg, `budget_leg`")
     ap.add_argument("--blocks", type=int, default=5,
-                    help="the steady state is timed in this many blocks of --steps steps: block 0 is the timed region "
+                    help="--full: the steady state is timed in this many blocks of --steps steps: block 0 is the timed region "
                          "(ms_per_step, value); the others only feed ms_per_step_blocks (median, spread)")
     ap.add_argument("--check", action="store_true", help="also compare one shard against the oracle (slow)")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="experiment: lbl_set_option(KEY, VALUE) on every context (e.g. accum_skew=0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every untimed pass and leg after the timed region (see the module docstring); a plain run "
+                         "only sets up, warms up, times --steps steps and prints the headline line.  --profile-every, --blocks, "
+                         "--no-direct-pass, --no-api-path, --no-cpu-baseline, --cpu-seconds and --legs auto shape those passes")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all: "
+                         "a fixed, seeded sample of the grid points beyond that)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -969,19 +1025,21 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    # HIP events bracket only the dominant kernel inside the timed region, and only in every
+    # --full: HIP events bracket only the dominant kernel inside the timed region, and only in every
     # --profile-every-th step: a pair of event records costs the stream ~5 us, 12 % of a C2 step if
     # every launch carries one.  The other kernel classes are timed in a short untimed pass afterwards.
+    # A plain run carries no events.
     ctx.profile_enable(False)
     ctx.profile_reset()
-    ctx.profile_reserve(2 * 8 * (args.steps // max(1, args.profile_every) + 1))      # no event creation in the timed region
+    if args.full:
+        ctx.profile_reserve(2 * 8 * (args.steps // max(1, args.profile_every) + 1))      # no event creation in the timed region
     every = max(1, args.profile_every)
     n_sampled = 0
     barrier()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        sampled = k % every == 0
-        if sampled or (k % every == 1):
+        sampled = args.full and k % every == 0
+        if args.full and (sampled or (k % every == 1)):
             ctx.profile_enable(["xsec_accumulate"] if sampled else False)
         n_sampled += sampled
         step(timed_kernels=sampled)
@@ -989,30 +1047,37 @@ def main():
     elapsed = time.perf_counter() - t0
     ctx.profile_enable(False)
     prof = ctx.profile_read()
-    # Steady state once more in blocks of `steps` (no timing events inside, barrier on both sides of each): the timed
-    # region above is the driver-checked figure, these say how much a block of that length scatters on this box
+    outputs_dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any untimed pass touches the buffers: the arrays of the last timed step's resident set
+        outputs_dumped = dump_outputs(args.dump_outputs, step_outputs(layers[(step_no[0] - 1) % n_sets], is_column,
+                                                                      bool(args.column_layer_arrays),
+                                                                      comm is not None and not batches, args.gather))
+    # --full: steady state once more in blocks of `steps` (no timing events inside, barrier on both sides of each): the
+    # timed region above is the driver-checked figure, these say how much a block of that length scatters on this box
     block_ms = [elapsed / args.steps * 1e3]
-    for _ in range(max(0, args.blocks - 1)):
+    for _ in range(max(0, args.blocks - 1) if args.full else 0):
         barrier()
         t_b0 = time.perf_counter()
         for k in range(args.steps):
             step()
         barrier()
         block_ms.append((time.perf_counter() - t_b0) / args.steps * 1e3)
-    ctx.profile_enable(["line_prep", "regrid", "layer_sweep", "column_sweep"] + ([] if overlap_gather else ["allgather"]))
-    ctx.profile_reset()
     n_extra = max(2, min(5, args.steps))
-    for _ in range(n_extra):
-        step(timed_kernels=True)
-    barrier()
-    extra = ctx.profile_read()
-    for name in ("line_prep", "regrid", "layer_sweep", "column_sweep", "allgather"):
-        n_, ms_ = extra[name]
-        prof[name] = (n_ * args.steps // n_extra, ms_ * args.steps / n_extra)      # scaled to the timed step count
+    if args.full:
+        ctx.profile_enable(["line_prep", "regrid", "layer_sweep", "column_sweep"] + ([] if overlap_gather else ["allgather"]))
+        ctx.profile_reset()
+        for _ in range(n_extra):
+            step(timed_kernels=True)
+        barrier()
+        extra = ctx.profile_read()
+        for name in ("line_prep", "regrid", "layer_sweep", "column_sweep", "allgather"):
+            n_, ms_ = extra[name]
+            prof[name] = (n_ * args.steps // n_extra, ms_ * args.steps / n_extra)      # scaled to the timed step count
     # the all-direct kernel (variant 3: every (line, grid point) pair evaluated, no series) on the
     # same resident inputs, untimed, so that the line carries both numbers
     direct_ms = None
-    if args.variant in (None, 5) and not args.no_direct_pass:
+    if args.full and args.variant in (None, 5) and not args.no_direct_pass:
         ctx.set_option("accum_variant", 3)
         for _ in range(2):
             step(timed_kernels=True)
@@ -1029,7 +1094,7 @@ def main():
     # the same step in budget mode (<= 1e-9 relative on the absorption coefficient), untimed legs: wall clock over
     # n_extra x 4 steps between barriers, then every kernel class bracketed by events in a pass of its own
     budget_leg = None
-    if args.accuracy == "exact" and args.variant in (None, 5) and not args.no_direct_pass:
+    if args.full and args.accuracy == "exact" and args.variant in (None, 5) and not args.no_direct_pass:
         ctx.set_option("accuracy", 1)
         for _ in range(3):
             step()
@@ -1061,7 +1126,7 @@ def main():
     # resident inputs, untimed legs like the budget leg's: the line's value is the merged step, this is what it replaced
     per_list_leg = None
     other_ok = merged or (args.step == "auto" and not args.unfused)          # (auto chose per-list: the merged step is the leg)
-    if other_ok and args.variant in (None, 5) and not args.no_direct_pass:
+    if args.full and other_ok and args.variant in (None, 5) and not args.no_direct_pass:
         step_kwargs["merged"] = not merged
         for _ in range(3):
             step()
@@ -1098,7 +1163,7 @@ def main():
     # them in lockstep): the kernels of a step without the all-gather, and the all-gather alone, in stream.
     # The pipelined step of the timed region cannot be faster than the longer of the two.
     breakdown_local = None
-    if comm is not None:
+    if args.full and comm is not None:
         n_b = max(5, min(20, args.steps))
         if batches:
             n_b = max(n_batch, n_b // n_batch * n_batch)       # whole batches
@@ -1163,7 +1228,7 @@ def main():
     # the host - this rank's own slots against its shard bit for bit, every rank's slots finite, positive over
     # the rank's points (non-negative, not all zero) and identical from step to step (the steps repeat the same cell).  A mismatch is fatal.
     gather_verified = None
-    if batches:
+    if args.full and batches:
         def shard_src(L):
             return L.I_toa if is_column else L.abs_coef
         for i, bt in enumerate(batches):
@@ -1201,6 +1266,10 @@ def main():
         evals_all = red.download(world)
         elapsed_max = float(times.max())
         evals_total = float(evals_all.sum())
+    else:
+        elapsed_max, evals_total = elapsed, evals_local
+    breakdown = None
+    if breakdown_local is not None:
         per_rank = []
         for v in breakdown_local:
             red.upload(np.array([v], dtype=np.float64), offset=rank)
@@ -1228,52 +1297,13 @@ def main():
                              "the step's all-gather(s) alone in stream (%s%s); the pipelined step overlaps the two"
                              % (n_flight, "outgoing spectrum" if is_column else args.gather,
                                 "" if not batches else ", one collective per %d steps, per step" % n_batch)}
-    else:
-        elapsed_max, evals_total = elapsed, evals_local
-        breakdown = None
 
     result = None
     if rank == 0:
         world_scale = evals_total / max(evals_local, 1.0)       # (rank 0's pair counts scaled to the job: shards are alike)
         value = evals_total * args.steps / elapsed_max
-        n_acc, ms_acc = prof["xsec_accumulate"]
-        n_sw, ms_sw = prof["layer_sweep"]
-        n_prep, ms_prep = prof["line_prep"]
-        n_ag, ms_ag = prof["allgather"]
         g = layer.layers[0].g if is_column else layer.g
         pts = layer.count if layer.plan is not None else g["n_work"]
-        n_arrays = len(layer.layers[0].jobs) if is_column else len(layer.jobs)     # cross-section arrays per layer
-        # Algorithmic bytes per launch of the dominant kernel: every line's 7 fp64 HITRAN
-        # fields read once (56 B/line) + 8 B per grid point for EVERY array the launch writes: one
-        # cross section per line list, and k, transmittance, outgoing radiance when the sweep is fused in.
-        fused_sweep = (not is_column) and not args.unfused and n_sw == 0
-        t_acc = (ms_acc / max(n_acc, 1)) * 1e-3
-        t_acc_step = (ms_acc / max(n_sampled, 1)) * 1e-3        # all K2 launches of one (sampled) step
-        launches_per_step = max(n_acc // max(n_sampled, 1), 1)   # a column launches K2 once per window group
-        n_xsec_written = (n_arrays * len(layer.layers)) if is_column else n_arrays
-        if merged:          # no per-line-list cross sections: a column writes one absorption coefficient per layer, a cell none beside the sweep's
-            n_xsec_written = len(layer.layers) if is_column else 0
-        balg_acc = (56.0 * layer.n_lines + 8.0 * pts * n_xsec_written + (24.0 * pts if fused_sweep else 0.0)) / launches_per_step
-        achieved = balg_acc / t_acc / 1e9 if t_acc > 0 else 0.0
-        # per sweep launch: M xsec reads + k, T (, I_out) writes; I_in is computed in-kernel
-        balg_sw = 8.0 * pts * (n_arrays + 3)
-        sweep_kernel = "layer_sweep_kernel"
-        if is_column:
-            # one column_step_kernel launch per step: every layer's cross sections read once, the outgoing
-            # spectrum written (+ two arrays per layer when --column-layer-arrays 1)
-            n_sw, ms_sw = prof["column_sweep"]
-            n_layers = len(layer.layers)
-            balg_sw = 8.0 * pts * (n_arrays * n_layers + 1 + (2 * n_layers if args.column_layer_arrays else 0))
-            if merged:      # one absorption coefficient per layer read, the outgoing spectrum written (+ the layers' transmittances)
-                balg_sw = 8.0 * pts * (n_layers + 1 + (n_layers if args.column_layer_arrays else 0))
-            sweep_kernel = "column_step_kernel"
-        t_sw = (ms_sw / max(n_sw, 1)) * 1e-3
-        # committed PMC passes: of the whole cell, or - for a rank of a G-way sharded run - of one shard of G
-        # ("C3s8": shard 4 of 8, profiles/collect.sh r02 C3 8,4): a shard's launch shape, not this rank's exact lines
-        standard = args.scale == 1 and args.lines is None and not args.unfused and (strong or world == 1)
-        pmc_key = args.workload if shard_world == 1 else "%ss%d" % (args.workload, shard_world)
-        pmc = load_pmc(pmc_key if standard else None, nat.source_hash())
-        traffic = pmc["hbm"].get("xsec_accumulate_kernel")
         result = {
             "metric": "line*gridpoint evals/sec (whole job)", "value": value, "unit": "evals/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1314,55 +1344,96 @@ def main():
                         "`value` counts every contribution the reference's loop adds (both kinds); value_direct_kernel is the "
                         "same workload through the all-direct kernel (accum_variant 3), every pair evaluated point by point"}),
             "evals_direct_per_s": float(layer.pairs["evals_direct"]) * world_scale * args.steps / elapsed_max,
-            "value_direct_kernel": None,
-            "direct_frac": None,
-            "roofline": {"bound": "hbm", "kernel": "xsec_accumulate_lds_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_stale": (pmc["stale"] if traffic is not None else None),
-                         "traffic_source": pmc["source"],
-                         "algorithmic_bytes_per_launch": balg_acc, "avg_launch_ms": t_acc * 1e3, "launches": n_acc,
-                         "launches_timed": "every launch of every %d-th timed step (%d of %d steps)" % (every, n_sampled, args.steps),
-                         "sweep_fused_in": bool(fused_sweep),
-                         "launches_overlap": n_flight > 1,
-                         "note": "compulsory traffic only (56 B/line + 8 B/grid point per array written: one cross section "
-                                 "per line list - none in the merged step, one absorption coefficient per layer in a merged column - "
-                                 "+ k, transmittance and radiance when the layer sweep is fused in). This "
-                                 "kernel is fp64-VALU bound by construction (SURVEY.md §8d): valu_f64.busy_frac is its "
-                                 "real utilisation figure"},
-            "valu_f64": valu_block(evals_local, t_acc_step, direct_ms, args.variant, pmc, launches_per_step,
-                                   n_flight, elapsed_max / args.steps),
-            "roofline_sweep": {"fused_into": "xsec_accumulate_lds_kernel (%s)" % ("lbl_layer_merged_step_dev" if merged else "lbl_layer_step_dev")}
-                              if n_sw == 0 and not is_column else
-                              {"bound": "hbm", "kernel": sweep_kernel,
-                               "achieved": balg_sw / t_sw / 1e9 if t_sw > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                               "frac": (balg_sw / t_sw / 1e9 / HBM_PEAK_GBS) if t_sw > 0 else 0.0,
-                               "traffic": pmc["hbm"].get(sweep_kernel),
-                               "traffic_stale": (pmc["stale"] if pmc["hbm"].get(sweep_kernel) is not None else None),
-                               "algorithmic_bytes_per_launch": balg_sw, "avg_launch_ms": t_sw * 1e3, "launches": n_sw,
-                               # a pair of HIP event records costs the stream a few microseconds, which shows on a 25 us
-                               # kernel: the committed rocprofv3 kernel trace of this very command is the cleaner clock
-                               "avg_launch_ms_rocprofv3": (pmc["avg_us"].get(sweep_kernel) or 0.0) / 1e3 or None,
-                               "frac_rocprofv3": (balg_sw / (pmc["avg_us"][sweep_kernel] * 1e-6) / 1e9 / HBM_PEAK_GBS)
-                                                 if pmc["avg_us"].get(sweep_kernel) else None},
-            "kernel_ms_per_step": {"line_prep": ms_prep / args.steps, "xsec_accumulate": ms_acc / max(n_sampled, 1),
-                                   ("column_step" if is_column else "layer_sweep"): ms_sw / args.steps,
-                                   "allgather": ms_ag / args.steps,
-                                   "source": "xsec_accumulate: HIP events around its launches in every %d-th step OF THE TIMED REGION "
-                                             "(%d of %d steps); line_prep, sweep%s: a SEPARATE pass of %d steps after it, every launch "
-                                             "bracketed (a pair of event records costs the stream a few microseconds, so the parts "
-                                             "can sum to more than ms_per_step)" % (every, n_sampled, args.steps,
-                                                                                   "" if overlap_gather else ", allgather", n_extra)},
-            "ms_per_step_blocks": {"blocks": [round(v, 6) for v in block_ms], "median": float(np.median(block_ms)),
-                                   "min": float(np.min(block_ms)), "max": float(np.max(block_ms)),
-                                   "spread_rel": float((np.max(block_ms) - np.min(block_ms)) / np.median(block_ms)),
-                                   "what": "max over ranks is NOT taken here (rank 0's clock between barriers); block 0 is the "
-                                           "timed region that ms_per_step and value come from"},
             "setup_s": t_setup,
         }
-        vb = result["valu_f64"]
-        if vb.get("direct_kernel_evals_per_s"):
-            result["value_direct_kernel"] = vb["direct_kernel_evals_per_s"]
-            result["direct_frac"] = vb.get("direct_frac")
+        if outputs_dumped is not None:
+            result["outputs_dumped"] = outputs_dumped
+        if args.full:
+            n_acc, ms_acc = prof["xsec_accumulate"]
+            n_sw, ms_sw = prof["layer_sweep"]
+            n_prep, ms_prep = prof["line_prep"]
+            n_ag, ms_ag = prof["allgather"]
+            n_arrays = len(layer.layers[0].jobs) if is_column else len(layer.jobs)     # cross-section arrays per layer
+            # Algorithmic bytes per launch of the dominant kernel: every line's 7 fp64 HITRAN
+            # fields read once (56 B/line) + 8 B per grid point for EVERY array the launch writes: one
+            # cross section per line list, and k, transmittance, outgoing radiance when the sweep is fused in.
+            fused_sweep = (not is_column) and not args.unfused and n_sw == 0
+            t_acc = (ms_acc / max(n_acc, 1)) * 1e-3
+            t_acc_step = (ms_acc / max(n_sampled, 1)) * 1e-3        # all K2 launches of one (sampled) step
+            launches_per_step = max(n_acc // max(n_sampled, 1), 1)   # a column launches K2 once per window group
+            n_xsec_written = (n_arrays * len(layer.layers)) if is_column else n_arrays
+            if merged:          # no per-line-list cross sections: a column writes one absorption coefficient per layer, a cell none beside the sweep's
+                n_xsec_written = len(layer.layers) if is_column else 0
+            balg_acc = (56.0 * layer.n_lines + 8.0 * pts * n_xsec_written + (24.0 * pts if fused_sweep else 0.0)) / launches_per_step
+            achieved = balg_acc / t_acc / 1e9 if t_acc > 0 else 0.0
+            # per sweep launch: M xsec reads + k, T (, I_out) writes; I_in is computed in-kernel
+            balg_sw = 8.0 * pts * (n_arrays + 3)
+            sweep_kernel = "layer_sweep_kernel"
+            if is_column:
+                # one column_step_kernel launch per step: every layer's cross sections read once, the outgoing
+                # spectrum written (+ two arrays per layer when --column-layer-arrays 1)
+                n_sw, ms_sw = prof["column_sweep"]
+                n_layers = len(layer.layers)
+                balg_sw = 8.0 * pts * (n_arrays * n_layers + 1 + (2 * n_layers if args.column_layer_arrays else 0))
+                if merged:      # one absorption coefficient per layer read, the outgoing spectrum written (+ the layers' transmittances)
+                    balg_sw = 8.0 * pts * (n_layers + 1 + (n_layers if args.column_layer_arrays else 0))
+                sweep_kernel = "column_step_kernel"
+            t_sw = (ms_sw / max(n_sw, 1)) * 1e-3
+            # committed PMC passes: of the whole cell, or - for a rank of a G-way sharded run - of one shard of G
+            # ("C3s8": shard 4 of 8, profiles/collect.sh r02 C3 8,4): a shard's launch shape, not this rank's exact lines
+            standard = args.scale == 1 and args.lines is None and not args.unfused and (strong or world == 1)
+            pmc_key = args.workload if shard_world == 1 else "%ss%d" % (args.workload, shard_world)
+            pmc = load_pmc(pmc_key if standard else None, nat.source_hash())
+            traffic = pmc["hbm"].get("xsec_accumulate_kernel")
+            result.update({
+                "value_direct_kernel": None,
+                "direct_frac": None,
+                "roofline": {"bound": "hbm", "kernel": "xsec_accumulate_lds_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": traffic, "traffic_stale": (pmc["stale"] if traffic is not None else None),
+                             "traffic_source": pmc["source"],
+                             "algorithmic_bytes_per_launch": balg_acc, "avg_launch_ms": t_acc * 1e3, "launches": n_acc,
+                             "launches_timed": "every launch of every %d-th timed step (%d of %d steps)" % (every, n_sampled, args.steps),
+                             "sweep_fused_in": bool(fused_sweep),
+                             "launches_overlap": n_flight > 1,
+                             "note": "compulsory traffic only (56 B/line + 8 B/grid point per array written: one cross section "
+                                     "per line list - none in the merged step, one absorption coefficient per layer in a merged column - "
+                                     "+ k, transmittance and radiance when the layer sweep is fused in). This "
+                                     "kernel is fp64-VALU bound by construction (SURVEY.md §8d): valu_f64.busy_frac is its "
+                                     "real utilisation figure"},
+                "valu_f64": valu_block(evals_local, t_acc_step, direct_ms, args.variant, pmc, launches_per_step,
+                                       n_flight, elapsed_max / args.steps),
+                "roofline_sweep": {"fused_into": "xsec_accumulate_lds_kernel (%s)" % ("lbl_layer_merged_step_dev" if merged else "lbl_layer_step_dev")}
+                                  if n_sw == 0 and not is_column else
+                                  {"bound": "hbm", "kernel": sweep_kernel,
+                                   "achieved": balg_sw / t_sw / 1e9 if t_sw > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                   "frac": (balg_sw / t_sw / 1e9 / HBM_PEAK_GBS) if t_sw > 0 else 0.0,
+                                   "traffic": pmc["hbm"].get(sweep_kernel),
+                                   "traffic_stale": (pmc["stale"] if pmc["hbm"].get(sweep_kernel) is not None else None),
+                                   "algorithmic_bytes_per_launch": balg_sw, "avg_launch_ms": t_sw * 1e3, "launches": n_sw,
+                                   # a pair of HIP event records costs the stream a few microseconds, which shows on a 25 us
+                                   # kernel: the committed rocprofv3 kernel trace of this very command is the cleaner clock
+                                   "avg_launch_ms_rocprofv3": (pmc["avg_us"].get(sweep_kernel) or 0.0) / 1e3 or None,
+                                   "frac_rocprofv3": (balg_sw / (pmc["avg_us"][sweep_kernel] * 1e-6) / 1e9 / HBM_PEAK_GBS)
+                                                     if pmc["avg_us"].get(sweep_kernel) else None},
+                "kernel_ms_per_step": {"line_prep": ms_prep / args.steps, "xsec_accumulate": ms_acc / max(n_sampled, 1),
+                                       ("column_step" if is_column else "layer_sweep"): ms_sw / args.steps,
+                                       "allgather": ms_ag / args.steps,
+                                       "source": "xsec_accumulate: HIP events around its launches in every %d-th step OF THE TIMED REGION "
+                                                 "(%d of %d steps); line_prep, sweep%s: a SEPARATE pass of %d steps after it, every launch "
+                                                 "bracketed (a pair of event records costs the stream a few microseconds, so the parts "
+                                                 "can sum to more than ms_per_step)" % (every, n_sampled, args.steps,
+                                                                                       "" if overlap_gather else ", allgather", n_extra)},
+                "ms_per_step_blocks": {"blocks": [round(v, 6) for v in block_ms], "median": float(np.median(block_ms)),
+                                       "min": float(np.min(block_ms)), "max": float(np.max(block_ms)),
+                                       "spread_rel": float((np.max(block_ms) - np.min(block_ms)) / np.median(block_ms)),
+                                       "what": "max over ranks is NOT taken here (rank 0's clock between barriers); block 0 is the "
+                                               "timed region that ms_per_step and value come from"},
+            })
+            vb = result["valu_f64"]
+            if vb.get("direct_kernel_evals_per_s"):
+                result["value_direct_kernel"] = vb["direct_kernel_evals_per_s"]
+                result["direct_frac"] = vb.get("direct_frac")
         if budget_leg is not None:
             result["budget_leg"] = budget_leg
         if per_list_leg is not None:
@@ -1376,15 +1447,15 @@ def main():
             result["invalid"] = "a debug_* option was set: parts of the kernels are switched off, results are wrong, timing experiment only"
         if breakdown is not None:
             result["sharded_step_breakdown"] = breakdown
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             raw = cfg["layers"] if is_column else [cfg]
             result["cpu_baseline"] = cpu_baseline([dict(c, raw_molecules=c["molecules"]) for c in raw], args.workload, args.cpu_seconds)
         if args.check:
             result["check"] = oracle_check(layer, cfg)
-    want_api = rank == 0 and world == 1 and not args.no_api_path and not args.shard_of
+    want_api = args.full and rank == 0 and world == 1 and not args.no_api_path and not args.shard_of
     legs = []
     if args.legs == "auto":
-        if args.workload == "C3" and not args.shard_of and args.scale == 1 and strong and args.variant is None and not args.unfused:
+        if args.full and args.workload == "C3" and not args.shard_of and args.scale == 1 and strong and args.variant is None and not args.unfused:
             legs = ["C1", "C2", "C5"] if (world == 1 and comm is None) else ["C5"]
     elif args.legs != "none":
         legs = [w for w in args.legs.split(",") if w]

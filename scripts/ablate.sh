@@ -8,7 +8,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 WL=${1:-C3}
 for bits in ${ABLATE_BITS:-0 8 256 512 1024 1 2 4 16 32}; do
-  PYRAD_HIP_LIB=$R/scripts/bin/libpyrad_hip_diag.so python3 $R/bench.py --workload $WL --steps 20 --warmup 3 --blocks 1 \
+  PYRAD_HIP_LIB=$R/scripts/bin/libpyrad_hip_diag.so python3 $R/bench.py --full --workload $WL --steps 20 --warmup 3 --blocks 1 \
       --no-cpu-baseline --no-api-path --no-direct-pass $ABLATE_ARGS --set debug_ablate=$bits |
     python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('debug_ablate=$bits', 'step %.4f ms' % d['ms_per_step'], {k: round(v, 4) for k, v in d['kernel_ms_per_step'].items() if k != 'source'}, 'ablated' if d.get('ablated') else '')"
 done

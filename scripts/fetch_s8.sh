@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 for rep in 1 2 3; do
 for c in 1 0; do
   OUT=$R/gpurun_out/f8_$c; rm -rf $OUT
-  rocprofv3 --pmc ${CTR:-FETCH_SIZE} --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --steps 20 --warmup 3 --blocks 1 --no-cpu-baseline --no-api-path --no-direct-pass --workload C3 --shard-of 8,4 --set accum_xcd_pack=$c > $OUT.log 2>&1
+  rocprofv3 --pmc ${CTR:-FETCH_SIZE} --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --full --steps 20 --warmup 3 --blocks 1 --no-cpu-baseline --no-api-path --no-direct-pass --workload C3 --shard-of 8,4 --set accum_xcd_pack=$c > $OUT.log 2>&1
   python3 - "$OUT" "$c" <<'PY'
 import csv, glob, sys, collections
 for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):

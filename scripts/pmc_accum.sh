@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc
 mkdir -p $OUT
-ARGS="$R/bench.py --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:---workload C3 --points-per-lane 4 --line-split 1}"
+ARGS="$R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:---workload C3 --points-per-lane 4 --line-split 1}"
 pass() { name=$1; shift; rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -- python3 $ARGS > $OUT/$name.log 2>&1 || tail -5 $OUT/$name.log; }
 pass p1 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD
 pass p2 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 TAG=${1:-m}
 OUT=$R/gpurun_out/pmc_$TAG
 mkdir -p $OUT
-ARGS="$R/bench.py --steps 10 --warmup 2 --blocks 1 --no-cpu-baseline --no-api-path --no-direct-pass ${BENCH_ARGS:---workload C3}"
+ARGS="$R/bench.py --full --steps 10 --warmup 2 --blocks 1 --no-cpu-baseline --no-api-path --no-direct-pass ${BENCH_ARGS:---workload C3}"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ARGS > $OUT/trace.log 2>&1 || tail -5 $OUT/trace.log
 pass() { name=$1; shift; rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -- python3 $ARGS > $OUT/$name.log 2>&1 || tail -5 $OUT/$name.log; }
 pass p1 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc_mix_$W
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="$R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-api-path --no-direct-pass --workload $W"
+CMD="$R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-api-path --no-direct-pass --workload $W"
 i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64" \
            "SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" \

@@ -1,6 +1,6 @@
 #!/bin/bash
 # far-field variant sweep: library build (threshold/terms) x points per lane x line split
-run() { lib=$1; shift; PYRAD_HIP_LIB=$lib python bench.py --steps 30 --warmup 3 --no-cpu-baseline --variant 5 "$@" 2>/dev/null | python -c "
+run() { lib=$1; shift; PYRAD_HIP_LIB=$lib python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --variant 5 "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$(basename $lib)', '$*', 'acc_ms=%.4f'%d['kernel_ms_per_step']['xsec_accumulate'], 'step_ms=%.4f'%d['ms_per_step'], '%.3e'%d['value'])"; }
 D=$PWD/pyrad_amd/lib/libpyrad_hip.so
 for lib in $D $PWD/scripts/bin/libpyrad_hip_ff*.so; do

@@ -5,7 +5,7 @@ for args in "--workload C2" "--workload C3 --shard-of 8,4 --step per-list" "--wo
 for c in 1 0 t-1 t6 t10; do tol=""; case $c in t*) tol="--set accum_xcd_tolerance=${c#t}"; esac; for ch in $(echo 0); do
   bash $R/scripts/quick_bench.sh "[$args] xcd_pack=$c chunks=$ch" $args $( case $c in t*) echo "--set accum_xcd_pack=1";; *) echo "--set accum_xcd_pack=$c";; esac ) $tol
   OUT=$R/gpurun_out/xp_$c; rm -rf $OUT
-  (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --steps 6 --warmup 2 --blocks 1 --no-cpu-baseline --no-api-path --no-direct-pass $args $( case $c in t*) echo "--set accum_xcd_pack=1";; *) echo "--set accum_xcd_pack=$c";; esac ) $tol > $OUT.log 2>&1)
+  (cd /tmp && TMPDIR=/tmp rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py --full --steps 6 --warmup 2 --blocks 1 --no-cpu-baseline --no-api-path --no-direct-pass $args $( case $c in t*) echo "--set accum_xcd_pack=1";; *) echo "--set accum_xcd_pack=$c";; esac ) $tol > $OUT.log 2>&1)
   python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections
 for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):

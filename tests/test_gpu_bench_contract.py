@@ -1,11 +1,13 @@
 """GPU: bench.py honours the driver's contract — one JSON line on stdout with the required
 keys — on the default path, and with the RCCL communicator forced on (one rank, pipelined
-all-gather over two buffer sets)."""
+all-gather over two buffer sets).  The figures beyond the headline come with --full; a plain run
+and its --dump-outputs are checked at the end."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import REPO
@@ -28,7 +30,7 @@ def run_bench(args, env_extra=None):
 
 
 def test_default_contract():
-    d = run_bench(["--steps", "5", "--warmup", "2", "--cpu-seconds", "1"])
+    d = run_bench(["--full", "--steps", "5", "--warmup", "2", "--cpu-seconds", "1"])
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2
@@ -94,7 +96,7 @@ def test_default_contract():
 
 def test_forced_single_rank_communicator_pipeline():
     # the default N > 1 path: one step in flight, one collective per step, overlapped with the next step (two buffer sets)
-    d0 = run_bench(["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--workload", "C1"], {"PYRAD_FORCE_COMM": "1"})
+    d0 = run_bench(["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--workload", "C1"], {"PYRAD_FORCE_COMM": "1"})
     assert d0["config"]["steps_in_flight"] == 1 and d0["config"]["gather_batch"] == 1 and "2 buffer sets" in d0["config"]["allgather"]
     bd = d0["sharded_step_breakdown"]       # what an N > 1 line carries: kernels without the gather, the gather alone, like-for-like legs
     assert bd["kernels_only_ms_per_step"] > 0 and bd["allgather_alone_ms_per_step"] > 0 and len(bd["kernels_only_ms_by_rank"]) == 1
@@ -102,11 +104,11 @@ def test_forced_single_rank_communicator_pipeline():
     ll = bd["like_for_like"]
     assert ll["in_stream_ms_per_step"] > 0 and ll["overlapped_ms_per_step"] > 0 and ll["step_latency_ms"] > 0
     # opt-in: the gathers of 3 steps batched into one collective
-    d = run_bench(["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--workload", "C1", "--gather-batch", "fit"],
+    d = run_bench(["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--workload", "C1", "--gather-batch", "fit"],
                   {"PYRAD_FORCE_COMM": "1"})
     assert d["config"]["allgather"].startswith("one collective per 3 steps") and d["value"] > 0       # 6 steps, two sets
     assert d["config"]["gather_batch"] == 3 and d["config"]["gather_verified"] is True
-    d2 = run_bench(["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--workload", "C1", "--no-overlap"],
+    d2 = run_bench(["--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--workload", "C1", "--no-overlap"],
                    {"PYRAD_FORCE_COMM": "1"})
     assert d2["config"]["allgather"] == "in-stream" and d2["kernel_ms_per_step"]["allgather"] > 0
 
@@ -114,7 +116,7 @@ def test_forced_single_rank_communicator_pipeline():
 def test_sharded_column_leg_through_the_communicator():
     """`bench.py --gpus N` carries BASELINE config 5 beside config 4: the 30-layer column sharded N-way by contiguous grid
     range with its single all-gather per step and a breakdown - here with one rank forced through the RCCL communicator."""
-    d = run_bench(["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-direct-pass"], {"PYRAD_FORCE_COMM": "1"})
+    d = run_bench(["--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-direct-pass"], {"PYRAD_FORCE_COMM": "1"})
     assert "sharded_step_breakdown" in d and sorted(d["workload_legs"]) == ["C5"]
     g = d["workload_legs"]["C5"]
     assert g["n_gpus"] == 1 and g["step"] == "merged" and g["evals_per_step"] > 2.5e10 and g["ms_per_step"] > 1.0
@@ -147,7 +149,7 @@ def test_sharded_step_with_the_communicator_pipeline(shards):
     driven on one GPU: shard 3 of 8 of the C3 cell with the RCCL communicator forced on (one rank, so the
     collective moves this rank's slot only).  Catches host-side mistakes in the N > 1 branch that the
     gloo tests (no HIP) and the --shard-of runs (no communicator) do not reach."""
-    d = run_bench(["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-api-path", "--shard-of", "8,3",
+    d = run_bench(["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-api-path", "--shard-of", "8,3",
                    "--shards", shards, "--in-flight", "2", "--gather-batch", "fit"], {"PYRAD_FORCE_COMM": "1"})
     assert d["config"]["allgather"].startswith("one collective per 3 steps") and d["value"] > 1e12
     assert d["config"]["gather_verified"] is True
@@ -155,25 +157,25 @@ def test_sharded_step_with_the_communicator_pipeline(shards):
     assert len(b) == 8 and sum(c for _, c in b) == 2400000 and d["config"]["grid_points_per_gpu"] == b[3][1]
     bd = d["sharded_step_breakdown"]
     assert 0.03 < bd["kernels_only_ms_per_step"] < 0.2 and 0 < bd["allgather_alone_ms_per_step"] < 0.2
-    d2 = run_bench(["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-api-path", "--shard-of", "8,3",
+    d2 = run_bench(["--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-api-path", "--shard-of", "8,3",
                     "--shards", shards, "--no-overlap", "--gather", "all"], {"PYRAD_FORCE_COMM": "1"})
     assert d2["config"]["allgather"] == "in-stream" and d2["kernel_ms_per_step"]["allgather"] > 0
     assert d["config"]["steps_in_flight"] == 2 and d["config"]["gather_batch"] == 3      # opt-in: two steps in flight, gathers batched
-    d1 = run_bench(["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-api-path", "--shard-of", "8,3",
+    d1 = run_bench(["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-api-path", "--shard-of", "8,3",
                     "--shards", shards], {"PYRAD_FORCE_COMM": "1"})           # the default: one in flight, a collective per step
     assert d1["config"]["steps_in_flight"] == 1 and "2 buffer sets" in d1["config"]["allgather"] and d1["config"]["gather_batch"] == 1
     assert d1["config"]["evals_per_step"] == d["config"]["evals_per_step"]
     ll = d1["sharded_step_breakdown"]["like_for_like"]
     assert 0.03 < ll["in_stream_ms_per_step"] < 0.3 and 0.03 < ll["overlapped_ms_per_step"] < 0.3 and ll["step_latency_ms"] > 0.03
     # the column takes the same route
-    d3 = run_bench(["--steps", "6", "--warmup", "1", "--no-cpu-baseline", "--workload", "C5", "--shard-of", "8,3",
+    d3 = run_bench(["--full", "--steps", "6", "--warmup", "1", "--no-cpu-baseline", "--workload", "C5", "--shard-of", "8,3",
                     "--shards", shards, "--gather-batch", "fit"], {"PYRAD_FORCE_COMM": "1"})
     assert d3["value"] > 1e11 and "column" in d3["config"]["workload"] and d3["config"]["gather_verified"] is True
 
 
 def test_column_line_carries_the_atmosphere_api_leg():
     """C5: the line's api_path is pyrad_amd.model.Atmosphere.transmission on the same 30-layer column."""
-    d = run_bench(["--workload", "C5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-direct-pass"])
+    d = run_bench(["--full", "--workload", "C5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-direct-pass"])
     a = d["api_path"]
     assert a["ms_per_call"] > 0 and a["bytes_downloaded_per_call"] == 8 * 2400000 and "30 layers" in a["what"] and "finite True" in a["what"]
     assert a["evals_per_s"] > 1e11 and d["roofline_sweep"]["kernel"] == "column_step_kernel"
@@ -181,6 +183,48 @@ def test_column_line_carries_the_atmosphere_api_leg():
 
 
 def test_budget_mode_line_says_so():
-    d = run_bench(["--workload", "C2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-api-path", "--accuracy", "budget",
+    d = run_bench(["--full", "--workload", "C2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-api-path", "--accuracy", "budget",
                    "--blocks", "2"])
     assert d["config"]["accuracy"] == "budget" and "budget_leg" not in d and len(d["ms_per_step_blocks"]["blocks"]) == 2
+
+
+FULL_ONLY = ("roofline", "valu_f64", "roofline_sweep", "kernel_ms_per_step", "ms_per_step_blocks", "cpu_baseline", "budget_leg",
+             "per_list_leg", "api_path", "in_flight_leg", "workload_legs", "value_direct_kernel", "sharded_step_breakdown")
+
+
+def test_plain_run_is_the_headline_only(tmp_path):
+    """Without --full the line carries the headline, config and pairs of the timed region and nothing that needs a pass
+    of its own; --steps sets the timed step count; --dump-outputs writes what the last timed step computed (the C3 cell:
+    three float64 spectra of 2.4e6 points, 57.6 MB, under the 64 MB cap)."""
+    out = tmp_path / "out"
+    d = run_bench(["--steps", "7", "--warmup", "2", "--dump-outputs", str(out)])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "pairs"):
+        assert k in d, k
+    assert not [k for k in FULL_ONLY if k in d]
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["higher_is_better"] is True and d["dtype"] == "f64" and d["unit"] == "evals/s"
+    assert d["config"]["evals_per_step"] == 3925123383.0 and d["config"]["grid_points_per_gpu"] == 2400000
+    assert abs(d["value"] - d["config"]["evals_per_step"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    files = sorted(os.listdir(out))
+    assert files == ["abs_coef.npy", "transmission.npy", "transmittance.npy"]
+    assert sum(os.path.getsize(out / f) for f in files) <= 64_000_000
+    for f in files:
+        a = np.load(out / f)
+        assert a.dtype == np.float64 and a.shape == (2400000,) and np.all(np.isfinite(a))
+    assert d["outputs_dumped"]["arrays"]["abs_coef"]["sampled_from_points"] is None
+
+
+def test_dumped_outputs_match_the_oracle(tmp_path):
+    """--dump-outputs of the C1 cell: the arrays the timed step computed, against the CPU oracle on the same seeded lines."""
+    from pyrad_amd import synthetic
+    from oracle import pyrad_oracle as orc
+    from conftest import rel_err
+    out = tmp_path / "out"
+    run_bench(["--workload", "C1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+    cfg = synthetic.config_c1()
+    ref = orc.layer_properties(cfg)
+    xa = orc.x_axis(cfg["range_min"], cfg["range_max"], cfg["base_resolution"])
+    ref_spec = orc.transmission(ref["transmittance"], orc.planckWavenumber(xa, 288), orc.planckWavenumber(xa, cfg["T"]))
+    assert rel_err(np.load(out / "abs_coef.npy"), ref["abs_coef"]) <= 1e-11
+    assert rel_err(np.load(out / "transmittance.npy"), ref["transmittance"]) <= 1e-11
+    assert rel_err(np.load(out / "transmission.npy"), ref_spec) <= 1e-11
