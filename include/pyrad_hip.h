@@ -91,6 +91,7 @@ int lbl_abi_version(void);
  *                           sums however many isotopologues a layer holds, pyradClasses.py:566-571, 707-712; HITRAN has ~160)
  *   "arrays_per_sum"        inputs of lbl_sum_dev: 64 (a longer sum is chained: the partial sum first)
  *   "arrays_per_column"     terms of lbl_column_step_dev: 511      "layers_per_column": 128      "jobs_per_batch": LBL_MAX_JOBS
+ *   "flux_angles"           angles of lbl_column_flux_dev: 8      "flux_bands": bands of lbl_column_flux_dev: 64
  * Unknown name: LBL_ERR_BAD_ARG. */
 int lbl_limit(const char* name, int64_t* value);
 int lbl_device_count(int* count);
@@ -359,6 +360,33 @@ int lbl_column_fold_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
                         const double* depth, double range_min, double range_max, int64_t n,
                         int64_t first, int64_t count, lbl_buffer* I_in, double surface_T,
                         lbl_buffer* const* trans, lbl_buffer* I_out);
+
+/* ---- level fluxes (beyond the reference; ABI 5, backward compatible) -------------------------------------------------
+ * pyrad_amd.model.Atmosphere.fluxes: upward and downward fluxes at every level of a column and, from them, heating rates.
+ * Layers l = 0 .. n_layers-1 bottom to top, levels i = 0 .. n_layers (level i is the lower boundary of layer i, level 0
+ * the surface, level n_layers the top).  At grid point nu_j = linspace(range_min, range_max, n)[j], for every angle k with
+ * cosine mu_k in (0, 1] and weight W_k:
+ *   t_lk  = exp(-k_l(nu_j) depth_l / mu_k)        k_l = abs_coef[l] (the layer's absorption coefficient)
+ *   B_l   = B(nu_j, T_l)                          (pyradPlanck.py:38-44)
+ *   up:    I_up[0]   = I_surface[j] or B(nu_j, surface_T)      I_up[l+1] = t_lk I_up[l] + (1 - t_lk) B_l
+ *   down:  I_down[L] = I_top[j] or 0                          I_down[l] = t_lk I_down[l+1] + (1 - t_lk) B_l
+ *   spectral flux F_up_i(nu_j) = sum_k W_k I_up[i]  (likewise F_down)
+ *   level_flux[b][0][i] = sum over j in band b of nan_to_num(F_up_i(nu_j)), level_flux[b][1][i] likewise for F_down:
+ *   n_bands x 2 x (n_layers + 1) doubles, band b = grid points [band_first[b], band_first[b] + band_count[b]).
+ * The caller multiplies by the grid step to get W m^-2 (integrateSpectrum's convention).  up_top / down_surface (may be
+ * NULL; n points each) receive F_up at the top and F_down at the surface at every point of every band, 0 elsewhere.
+ * The surface is black (emissivity 1); I_surface / I_top are isotropic radiances in the units of lbl_column_fold_dev's I_in.
+ * Arithmetic: lbl_column_fold_dev's (one Planck term per point and layer shared by all angles, exp(-tau / mu_k) as
+ * exp(-tau * (1 / mu_k))), so with the one angle (1, pi) F_up at the top is pi times the fold's I_out, bit for bit wherever
+ * the fold takes its one-exp-per-thread Planck path.  Sums in a fixed order, no atomics: the same inputs give the same bits.
+ * At most lbl_limit("flux_angles") = 8 angles and lbl_limit("flux_bands") = 64 bands; "sweep_ieee_divisions" 1 gives
+ * LBL_ERR_BAD_ARG, as for the fold.  Stream-ordered on the context's stream; nothing is synchronised. */
+int lbl_column_flux_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T, const double* depth,
+                        double range_min, double range_max, int64_t n,
+                        lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                        int n_angles, const double* mu, const double* weight,
+                        int n_bands, const int64_t* band_first, const int64_t* band_count,
+                        lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface);
 
 /* ---- resident column (ABI 5) ---------------------------------------------------------------------------------------
  * The argument blocks of a column's merged accumulate jobs (lbl_layers_merged_accumulate_dev) and of its fold

@@ -100,6 +100,8 @@ SIGNATURES = {
                                                    C.POINTER(_P)]),
     "lbl_column_fold_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, C.c_int64,
                                       C.c_int64, _P, C.c_double, C.POINTER(_P), _P]),
+    "lbl_column_flux_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, _P, C.c_double,
+                                      _P, C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P]),
     "lbl_column_create": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(IsoParams), C.POINTER(Grid),
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, _D, C.POINTER(_P), C.POINTER(_P)]),
     "lbl_column_destroy": (C.c_int, [_P]),
@@ -142,11 +144,11 @@ def build(force: bool = False) -> str:
 
 def source_hash() -> str:
     """sha256 over what decides the kernels and their launch shapes (csrc/lbl_kernels.hip, lbl_api.hip,
-    lbl_device.h, Makefile): profiles/pmc_traffic.json records it so that bench.py can tell when
+    lbl_device.h, lbl_flux.hip, Makefile): profiles/pmc_traffic.json records it so that bench.py can tell when
     committed PMC numbers were measured on other kernels than the ones it is timing."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("Makefile", "lbl_api.hip", "lbl_device.h", "lbl_kernels.hip", "lbl_launch_shapes.h"):
+    for f in ("Makefile", "lbl_api.hip", "lbl_device.h", "lbl_kernels.hip", "lbl_launch_shapes.h", "lbl_flux.hip"):
         h.update(f.encode())
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
@@ -176,7 +178,7 @@ _limits = {}
 
 def limit(name: str) -> int:
     """A fixed size of the library (lbl_limit): "merged_lists_per_job", "arrays_per_layer", "arrays_per_sum",
-    "arrays_per_column", "layers_per_column", "jobs_per_batch"."""
+    "arrays_per_column", "layers_per_column", "jobs_per_batch", "flux_angles", "flux_bands"."""
     if name not in _limits:
         v = C.c_int64()
         rc = load().lbl_limit(name.encode(), C.byref(v))
@@ -494,6 +496,21 @@ class Context:
             self.h, nl, arr(_P, [b.h for b in abs_coef]), arr(C.c_double, [float(t) for t in layer_T]),
             arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), int(first), int(count),
             hb(I_in), float(surface_T), arr(_P, [hb(b) for b in trans]) if trans is not None else None, I_out.h))
+
+    def column_flux_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
+                        level_flux, I_surface=None, surface_T=0.0, I_top=None, up_top=None, down_surface=None):
+        """Level fluxes of a column from the layers' absorption coefficients (lbl_column_flux_dev): ``level_flux`` receives
+        len(band_first) x 2 x (layers + 1) band sums [band][up, down][level]; ``up_top`` / ``down_surface`` (optional, n
+        points) the spectral upward flux at the top and downward flux at the surface."""
+        nl = len(abs_coef)
+        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
+        hb = lambda b: b.h if b is not None else None
+        self.check(self.lib.lbl_column_flux_dev(
+            self.h, nl, arr(_P, [b.h for b in abs_coef]), arr(C.c_double, [float(t) for t in layer_T]),
+            arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), hb(I_surface),
+            float(surface_T), hb(I_top), len(mu), arr(C.c_double, [float(m) for m in mu]),
+            arr(C.c_double, [float(w) for w in weight]), len(band_first), arr(C.c_int64, [int(f) for f in band_first]),
+            arr(C.c_int64, [int(c) for c in band_count]), hb(level_flux), hb(up_top), hb(down_surface)))
 
     def gather_compact_dev(self, gathered, slot, bounds, out):
         """padded all-gather result (slot r = rank r's shard) -> grid order (lbl_gather_compact_dev)."""

@@ -50,7 +50,7 @@ struct lbl_ctx {
     DeviceArena jobs;       // PrepJob[] + AccumJob[] + regime counters (3 x u64 per job)
     DeviceArena counts;     // per-block regime counts of the last batch
     DeviceArena bal;        // balanced variant: span table, counts, prefix, slab
-    DeviceArena red;        // band-integral partials + result
+    DeviceArena red;        // band-integral partials + result; lbl_column_flux_dev's partials
     DeviceArena zeros;      // an array of zeros: the cross section of a column layer without line lists
     size_t zeros_set = 0;
     void* host_stage = nullptr;   // pinned staging ring for job descriptors
@@ -385,6 +385,8 @@ extern "C" int lbl_limit(const char* name, int64_t* value) {
     else if (!strcmp(name, "arrays_per_column")) *value = kMaxColumnIso - 1;   // terms of lbl_column_step_dev
     else if (!strcmp(name, "layers_per_column")) *value = kMaxLayers;
     else if (!strcmp(name, "jobs_per_batch")) *value = LBL_MAX_JOBS;
+    else if (!strcmp(name, "flux_angles")) *value = kMaxFluxAngles;           // angles of lbl_column_flux_dev
+    else if (!strcmp(name, "flux_bands")) *value = kMaxFluxBands;             // bands of lbl_column_flux_dev
     else return LBL_ERR_BAD_ARG;
     return LBL_OK;
 }
@@ -2561,4 +2563,23 @@ int comm_fail(lbl_ctx* ctx, int code, const char* msg) { return fail(ctx, code, 
 int ctx_device(lbl_ctx* ctx) { return ctx->device; }
 bool ctx_capturing(lbl_ctx* ctx) { return ctx->capturing; }
 lbl_ctx* buffer_ctx(lbl_buffer* buf) { return buf->ctx; }
+// ... and for lbl_flux.hip
+hipStream_t ctx_stream(lbl_ctx* ctx) { return ctx->stream; }
+bool ctx_sweep_ieee(lbl_ctx* ctx) { return ctx->sweep_ieee != 0; }
+int ctx_device_args(lbl_ctx* ctx, const void* host, size_t bytes, void** dptr) { return device_args(ctx, host, bytes, dptr); }
+int ctx_reduction_scratch(lbl_ctx* ctx, size_t bytes, void** dptr) {      // the band-integral partials' arena
+    const int rc = arena_reserve(ctx, ctx->red, bytes);
+    if (rc == LBL_OK) *dptr = ctx->red.ptr;
+    return rc;
+}
+int ctx_check_buffer(lbl_ctx* ctx, lbl_buffer* b, int64_t n, const char* what, bool required) {
+    return check_buf(ctx, b, n, what, required);
+}
+double* buffer_data(lbl_buffer* buf) { return buf->d; }
+void planck_budget_constants(double T, double* pa, double* pbkT) {      // the fold's: 2E8 h c^2 and 100 h c / k / T
+    double pb;
+    planck_constants(pa, &pb);
+    *pbkT = budget_pbkT(T);
+}
+double grid_step(double lo, double hi, int64_t n) { return axis_step(lo, hi, n); }
 }  // namespace lbl

@@ -222,6 +222,34 @@ struct ColumnStepArgs {
     long long n;
     long long first, count;
 };
+// Level fluxes of a column (lbl_column_flux_dev, lbl_flux.hip): the fold's arithmetic over the layers' absorption coefficients
+// for several angles, upward from the surface and downward from the top, each level's angle-weighted radiance summed over a
+// band of grid points.  One argument block per call; every band is its own launch over the same partial-sum scratch.
+constexpr int kMaxFluxAngles = 8;
+constexpr int kMaxFluxBands = 64;
+constexpr int kFluxMaxBlocks = 1024;      // workgroups of one band launch (grid-stride beyond): partials stay (1024 + 1) x 2 x 129 doubles
+struct FluxArgs {
+    const double* abs_coef[kMaxLayers];
+    double depth[kMaxLayers];
+    double pbkT[kMaxLayers];            // 100 h c / k / T_l (the budget Planck exponent per wavenumber)
+    double pbkT_min, pbkT_max;          // smallest / largest of them (the fold's test for its one-exp-per-thread Planck path)
+    double pbk_surface;                 // 100 h c / k / surface_T (used when I_surface == nullptr)
+    double rmu[kMaxFluxAngles];         // 1 / mu_k
+    double w[kMaxFluxAngles];           // W_k
+    double start, stop, step, pa;
+    const double* I_surface;            // upward radiance entering at the surface, or nullptr: B(nu, surface_T)
+    const double* I_top;                // downward radiance entering at the top, or nullptr: 0
+    double* up_top;                     // optional: spectral flux F_up at the top
+    double* down_surface;               // optional: spectral flux F_down at the surface
+    long long n;
+    int32_t n_layers, n_angles;
+};
+// one band [first, first + count): partial sums into `partial` (at most column_flux_partials(count) blocks of 2 (n_layers + 1)),
+// then the fixed-order reduction into level_flux[0 .. 2 (n_layers + 1)): [up, down][level]
+int column_flux_partials(long long count);
+void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long long first, long long count, double* partial,
+                        double* level_flux, hipStream_t s);
+
 struct ColumnArgs {
     const double* trans[kMaxLayers];
     double layer_T[kMaxLayers];

@@ -9,6 +9,8 @@
 //   K5 column_sweep_kernel     fold of pyradClasses.py:784-787 over layers
 //   K5b column_step_kernel     K4's arithmetic per layer + that fold, straight from the cross sections
 //   K6 band_integral kernels   pyradClasses.py:26-29
+//   K5c column_flux_kernel     K5b's fold over absorption coefficients for several angles, upward and downward,
+//                              reduced to level fluxes (Atmosphere.fluxes; beyond the reference)
 //   K7 line_survey_kernel      pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -3288,6 +3290,162 @@ __global__ __launch_bounds__(256) void band_final_kernel(const double* __restric
 }
 
 // ----------------------------------------------------------------------------------------
+// K5c: level fluxes of a column (lbl_column_flux_dev; the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// The fold of column_step_kernel<4, true, true> over the layers' absorption coefficients, for NA angles at once and in both
+// directions: every thread owns NP grid points (4 on the aligned quads of a band, 1 on its head and tail points, the way
+// launch_column_step_b treats its tail), walks the layers bottom to top for the upward radiances I_up[k] and then top to
+// bottom for the downward ones, re-reading k_l and recomputing B_l on the way down (the registers cannot hold 128 layers'
+// worth).  Per point and layer: one Planck term shared by all angles (one exp per thread and layer on the wave-uniform fast
+// path, the general expression otherwise - the fold's guard and arithmetic), and one exp_neg_budget(tau_l / mu_k) per angle
+// and direction.  With the angle set {(1, pi)} the upward radiance at the top is the fold's I_out bit for bit wherever both
+// take the same Planck path (every wave fast, or the same general points).
+// Level sums: after every layer step each thread adds its points' angle-weighted radiances sum_k W_k I_k (nan_to_num per
+// point); the wave reduces them (wave_sum), lane 0 adds the result to its wave's slot in LDS; at the end the four waves'
+// slots are added in a fixed order into ONE partial per workgroup and level, and column_flux_final_kernel adds the partials in
+// a fixed order.  No float atomics: the same inputs and launch give the same bits.
+template <int NP, int NA>
+__global__ __launch_bounds__(256) void column_flux_kernel(const FluxArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                          long long lo1, long long n1, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    typedef double vec __attribute__((ext_vector_type(NP)));
+    typedef const vec __attribute__((address_space(1)))* GlobalVec;
+    constexpr int kSlot = 2 * (kMaxLayers + 1);
+    __shared__ double acc[4 * kSlot];            // [wave][up levels 0..L, down levels 0..L]
+    const FluxArgs& A = *Ap;
+    const int L = A.n_layers;
+    const int nv = 2 * (L + 1);
+    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
+    __syncthreads();
+    double* my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    auto load = [&](const double* p, long long j) {
+        vec v;
+        if (NP == 1) v[0] = load_global_f64(p, j);
+        else v = *(GlobalVec)(unsigned long long)(p + j);
+        return v;
+    };
+    const long long total = n0 + n1;
+    const long long stride = (long long)gridDim.x * blockDim.x * NP;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
+    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
+        const long long q = q0 + (long long)threadIdx.x * NP;
+        const bool active = q < total;
+        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        double nu[NP], pa_n[NP], I[NA][NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            nu[p] = linspace_at(j + p, A.n, A.start, A.stop, A.step);
+            pa_n[p] = A.pa * (nu[p] * nu[p] * nu[p]);
+        }
+        // the fold's test for one Planck exp per thread and layer (column_step_kernel), over the active lanes of the wave
+        const double dnu_last = nu[NP - 1] - nu[0];
+        const bool plain = NP > 1 && nu[0] * A.pbkT_min >= 1e-6 && nu[NP - 1] * A.pbkT_max <= 690.0
+                           && dnu_last * A.pbkT_max <= 1e-3 && dnu_last >= 0.0;
+        const bool fast = NP > 1 && __builtin_amdgcn_ballot_w64(active && !plain) == 0ull;
+        // sum_k W_k I_k per point, nan_to_num, summed over the thread's points, the wave, and into the wave's slot
+        auto level = [&](int slot, double* spec) {
+            double s = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double f = A.w[0] * I[0][p];
+#pragma unroll
+                for (int k = 1; k < NA; ++k) f = fma(A.w[k], I[k][p], f);
+                if (spec && active) spec[j + p] = f;
+                s += active ? nan_to_num(f) : 0.0;
+            }
+            s = wave_sum(s);
+            if (lane0) my[slot] += s;
+        };
+        auto layer = [&](auto fast_tag, int l, vec v) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double pbkT = A.pbkT[l], depth = A.depth[l];
+            double E0 = 0.0;
+            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+                double B;
+                if (FAST) {
+                    const double E = p == 0 ? E0 : fma(E0, expm1_tiny((nu[p] - nu[0]) * pbkT), E0);
+                    B = pa_n[p] * rcp_newton(E - 1.0);
+                } else {
+                    const double b = nu[p] * pbkT;
+                    const double e = exp_clamped(fmin(b, 700.0)) - 1.0;
+                    B = (b > 700.0) ? 0.0 : (e > 0.0 ? pa_n[p] * rcp_newton(fmax(e, 1e-300)) : pa_n[p] / e);
+                    B = b != b ? b : B;
+                }
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double tr = exp_neg_budget(tau * A.rmu[k]);
+                    if (FAST) {
+                        I[k][p] = fma(tr, I[k][p], (1.0 - tr) * B);
+                    } else {
+                        const double transmitted = tr * I[k][p];
+                        const double emitted = (1.0 - tr) * B;
+                        I[k][p] = transmitted + emitted;
+                    }
+                }
+            }
+        };
+        auto walk = [&](auto fast_tag) {
+            // upward: I_0 = I_surface or B(nu, surface_T); level l + 1 after layer l
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double Is = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+#pragma unroll
+                for (int k = 0; k < NA; ++k) I[k][p] = Is;
+            }
+            level(0, L == 0 ? A.up_top : nullptr);
+            vec cur = L > 0 ? load(A.abs_coef[0], j) : (vec)(0.0);
+            for (int l = 0; l < L; ++l) {
+                const vec nxt = l + 1 < L ? load(A.abs_coef[l + 1], j) : cur;
+                layer(fast_tag, l, cur);
+                level(l + 1, l + 1 == L ? A.up_top : nullptr);
+                cur = nxt;
+            }
+            // downward: I_L = I_top or 0; level l after layer l
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double It = A.I_top ? A.I_top[j + p] : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) I[k][p] = It;
+            }
+            level(L + 1 + L, L == 0 ? A.down_surface : nullptr);
+            cur = L > 0 ? load(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load(A.abs_coef[l - 1], j) : cur;
+                layer(fast_tag, l, cur);
+                level(L + 1 + l, l == 0 ? A.down_surface : nullptr);
+                cur = nxt;
+            }
+        };
+        if constexpr (NP > 1) {
+            if (fast) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += blockDim.x)
+        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+}
+
+// level_flux[t] = sum over the partials of value t, in the order of band_final_kernel (one workgroup per value)
+__global__ __launch_bounds__(256) void column_flux_final_kernel(const double* __restrict__ partial, int n_partial, int nv,
+                                                                double* __restrict__ level_flux) {
+    __shared__ double sh[4];
+    const int t = blockIdx.x;
+    double s = 0.0;
+    for (int b = threadIdx.x; b < n_partial; b += blockDim.x) s += partial[(long long)b * nv + t];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) level_flux[t] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// ----------------------------------------------------------------------------------------
 // K7: line survey (pyradClasses.py:409-428): S added into the bin of each line, in line order
 // ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void line_survey_kernel(const double* __restrict__ nu, const double* __restrict__ sw,
@@ -3582,6 +3740,55 @@ void launch_band_integral(const double* y, long long n, double* partial, double*
     const int nb = band_partial_count(n);
     hipLaunchKernelGGL(band_partial_kernel, dim3(nb), dim3(256), 0, s, y, n, partial, (long long)16384);
     hipLaunchKernelGGL(band_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, result);
+}
+
+// ---- K5c launch: one band [first, first + count) --------------------------------------------------------------------
+// Quads aligned to 4 on the global grid (first and last points of the whole range: the fold's quads) go to the NP = 4
+// kernel, at most kFluxMaxBlocks workgroups (grid-stride beyond, so the partial scratch is bounded); the band's head and
+// tail points (at most 6) to ONE 64-lane workgroup of the NP = 1 kernel, whose partial follows the others'.
+int column_flux_partials(long long count) {
+    const long long quads = count / 4 + 1;
+    return (int)std::min<long long>((quads + 255) / 256, kFluxMaxBlocks) + 1;
+}
+
+template <int NA>
+static void launch_column_flux_na(const FluxArgs* d_args, int nv, long long first, long long count, double* partial,
+                                  double* level_flux, hipStream_t s) {
+    const long long end = first + count;
+    const long long q0 = (first + 3) & ~3LL;
+    long long q1 = end & ~3LL;
+    if (q1 < q0) q1 = q0;
+    const long long nq = q1 - q0;
+    const long long nh = std::min(q0, end) - first;
+    const long long nt = end > q1 ? end - q1 : 0;
+    int blocks = 0;
+    if (nq > 0) {
+        blocks = (int)std::min<long long>((nq / 4 + 255) / 256, kFluxMaxBlocks);
+        hipLaunchKernelGGL((column_flux_kernel<4, NA>), dim3(blocks), dim3(256), 0, s, d_args, q0, nq, q0, 0LL, partial);
+    }
+    if (nh + nt > 0) {
+        hipLaunchKernelGGL((column_flux_kernel<1, NA>), dim3(1), dim3(64), 0, s, d_args, nh > 0 ? first : q1, nh, q1, nt,
+                           partial + (long long)blocks * nv);
+        ++blocks;
+    }
+    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, blocks, nv, level_flux);
+}
+
+void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long long first, long long count, double* partial,
+                        double* level_flux, hipStream_t s) {
+    if (count <= 0) return;
+    const int nv = 2 * (n_layers + 1);
+    switch (n_angles) {
+        case 1: launch_column_flux_na<1>(d_args, nv, first, count, partial, level_flux, s); break;
+        case 2: launch_column_flux_na<2>(d_args, nv, first, count, partial, level_flux, s); break;
+        case 3: launch_column_flux_na<3>(d_args, nv, first, count, partial, level_flux, s); break;
+        case 4: launch_column_flux_na<4>(d_args, nv, first, count, partial, level_flux, s); break;
+        case 5: launch_column_flux_na<5>(d_args, nv, first, count, partial, level_flux, s); break;
+        case 6: launch_column_flux_na<6>(d_args, nv, first, count, partial, level_flux, s); break;
+        case 7: launch_column_flux_na<7>(d_args, nv, first, count, partial, level_flux, s); break;
+        case 8: launch_column_flux_na<8>(d_args, nv, first, count, partial, level_flux, s); break;
+        default: break;
+    }
 }
 
 void launch_line_survey(const double* nu, const double* sw, int n_lines, double range_min, double resolution,

@@ -35,6 +35,11 @@ t0 = 296
 p0 = 1013.25
 avo = 6.022140857E23
 
+# Atmosphere.fluxes: heat capacity of air at constant pressure and gas constant of dry air (J kg^-1 K^-1), for the heating
+# rate of a layer from its mass per unit area (change them here to use other values)
+CP_AIR = 1004.0
+R_DRY_AIR = 287.05
+
 VERSION = settings.VERSION
 VERBOSE = False           # the reference prints progress bars; set True to see the regime line
 
@@ -1203,6 +1208,107 @@ class Layer(_OpticalMixin, list):
 
 
 # ----------------------------------------------------------------------------------------
+# Level fluxes of a column (Atmosphere.fluxes; beyond the reference)
+# ----------------------------------------------------------------------------------------
+FLUX_DIFFUSIVITY = 1.66       # the "diffusivity" angle set: one angle, mu = 1 / 1.66, weight pi
+
+
+def fluxAngles(angles=3):
+    """The angle set of Atmosphere.fluxes as two float64 arrays (mu, weight), mu in (0, 1].
+    - an integer N in 1..8: Gauss-Legendre on mu in [0, 1]: with x, w = numpy.polynomial.legendre.leggauss(N),
+      mu_k = (x_k + 1) / 2 and W_k = pi w_k mu_k, so that sum W_k = pi and sum_k W_k I(mu_k) = 2 pi int_0^1 I(mu) mu dmu
+      exactly for every polynomial I of degree <= 2N - 2;
+    - "diffusivity": mu = 1 / 1.66, W = pi;
+    - an explicit list of (mu, W) pairs.
+    ValueError for anything else, N outside 1..8, more than 8 pairs or a mu outside (0, 1]."""
+    nmax = 8
+    if isinstance(angles, str):
+        if angles != "diffusivity":
+            raise ValueError("angles: an integer 1..%d, \"diffusivity\" or a list of (mu, weight) pairs, not %r" % (nmax, angles))
+        return np.array([1.0 / FLUX_DIFFUSIVITY]), np.array([pi])
+    if isinstance(angles, (int, np.integer)) and not isinstance(angles, bool):
+        if not 1 <= int(angles) <= nmax:
+            raise ValueError("angles: %d Gauss-Legendre angles, at most %d" % (int(angles), nmax))
+        x, w = np.polynomial.legendre.leggauss(int(angles))
+        mu = (x + 1.0) / 2.0
+        return mu, pi * w * mu
+    try:
+        pairs = [(float(m), float(wt)) for m, wt in angles]
+    except (TypeError, ValueError):
+        raise ValueError("angles: an integer 1..%d, \"diffusivity\" or a list of (mu, weight) pairs, not %r" % (nmax, angles))
+    if not 1 <= len(pairs) <= nmax:
+        raise ValueError("angles: 1..%d (mu, weight) pairs, not %d" % (nmax, len(pairs)))
+    mu = np.array([m for m, _ in pairs])
+    weight = np.array([wt for _, wt in pairs])
+    if not np.all((mu > 0.0) & (mu <= 1.0)):
+        raise ValueError("angles: every mu must lie in (0, 1]")
+    if not np.all(np.isfinite(weight)):
+        raise ValueError("angles: every weight must be finite")
+    return mu, weight
+
+
+def heatingRates(net, P, T, depth):
+    """Heating rate of every layer in K/day from the net flux (W m^-2) at its levels: H_l = -(F_(l+1) - F_l) / (c_p m_l) *
+    86400 with the layer's mass per unit area m_l = (100 P_l / (R_d T_l)) (depth_l / 100) kg m^-2 (P in mbar, depth in cm,
+    c_p = CP_AIR, R_d = R_DRY_AIR).  ``net``: (..., L + 1); P, T, depth: L values each; returns (..., L)."""
+    net = np.asarray(net, dtype=np.float64)
+    P, T, depth = (np.asarray(v, dtype=np.float64) for v in (P, T, depth))
+    mass = (100.0 * P / (R_DRY_AIR * T)) * (depth / 100.0)
+    return -(net[..., 1:] - net[..., :-1]) / (CP_AIR * mass) * 86400.0
+
+
+def _flux_bands(rangeMin, rangeMax, n, bands):
+    """(first, count) grid-index ranges of the bands: band (lo, hi) holds the points of linspace(rangeMin, rangeMax, n) with
+    lo <= nu < hi (hi may lie beyond rangeMax, so that a band can end with the last point)."""
+    if bands is None:
+        if n < 1:
+            raise ValueError("the wavenumber range holds no grid point")
+        return [0], [n]
+    bands = list(bands)
+    nmax = 64
+    if not bands:
+        raise ValueError("bands: give at least one (lo, hi) band, or None for the whole range")
+    if len(bands) > nmax:
+        raise ValueError("bands: at most %d bands, not %d" % (nmax, len(bands)))
+    x = np.linspace(rangeMin, rangeMax, n)
+    first, count = [], []
+    for b, band in enumerate(bands):
+        try:
+            lo, hi = (float(v) for v in band)
+        except (TypeError, ValueError):
+            raise ValueError("bands: band %d is not a (lo, hi) pair: %r" % (b, band))
+        if not (lo >= rangeMin and lo <= rangeMax):
+            raise ValueError("bands: band %d (%g, %g) starts outside the range [%g, %g]" % (b, lo, hi, rangeMin, rangeMax))
+        i0, i1 = int(np.searchsorted(x, lo, "left")), int(np.searchsorted(x, hi, "left"))
+        if i1 <= i0:
+            raise ValueError("bands: band %d (%g, %g) holds no grid point" % (b, lo, hi))
+        first.append(i0)
+        count.append(i1 - i0)
+    return first, count
+
+
+class Fluxes:
+    """What Atmosphere.fluxes returns.  ``up``, ``down``, ``net``: W m^-2 at the levels 0 (surface) .. L (top), shape (L + 1,)
+    or (n_bands, L + 1); ``heatingRate``: K/day per layer, (L,) or (n_bands, L); ``mu``, ``weight``: the angle set used;
+    ``upSpectrum`` / ``downSpectrum``: the spectral upward flux at the top and downward flux at the surface (W m^-2 per
+    cm^-1, n points; 0 at points outside every band) when asked for, else None."""
+
+    def __init__(self, up, down, heatingRate, mu, weight, upSpectrum=None, downSpectrum=None):
+        self.up = up
+        self.down = down
+        self.net = up - down
+        self.heatingRate = heatingRate
+        self.mu = mu
+        self.weight = weight
+        self.upSpectrum = upSpectrum
+        self.downSpectrum = downSpectrum
+
+    def __repr__(self):
+        return "Fluxes(levels=%d, angles=%d, up[top]=%s, down[surface]=%s)" % (
+            self.up.shape[-1], len(self.mu), self.up[..., -1], self.down[..., 0])
+
+
+# ----------------------------------------------------------------------------------------
 # Atmosphere (cls:790-821) + the column fold this build defines on it (SURVEY.md §3.5)
 # ----------------------------------------------------------------------------------------
 class Atmosphere(list):
@@ -1279,6 +1385,76 @@ class Atmosphere(list):
                 b.free()
 
 
+    def fluxes(self, surfaceTemperature=None, surfaceSpectrum=None, topSpectrum=None, angles=3, bands=None, spectra=False):
+        """Upward, downward and net fluxes at every level and the heating rate of every layer (beyond the reference).
+
+        Layers l = 0 .. L-1 in list order, bottom to top, as transmission() takes them; level i is the lower boundary of
+        layer i (level 0 the surface, level L the top).  All layers share one range and grid.  At every grid point nu_j
+        (xAxis) and for every angle k (cosine mu_k in (0, 1], weight W_k; ``angles``: see fluxAngles, default 3 Gauss
+        angles):
+            t_lk = exp(-k_l(nu_j) depth_l / mu_k)      k_l = the layer's absorption coefficient (getAbsCoef)
+            B_l  = planckWavenumber(nu_j, T_l)
+            up:   I_0k = surfaceSpectrum[j] or B(nu_j, surfaceTemperature)    I_(l+1)k = t_lk I_lk + (1 - t_lk) B_l
+            down: I_Lk = topSpectrum[j] or 0                                  I_lk     = t_lk I_(l+1)k + (1 - t_lk) B_l
+            spectral flux F_i(nu_j) = sum_k W_k I_ik(nu_j)   (each direction)
+            band flux     F_i = res * sum over the band's points of nan_to_num(F_i(nu_j)),  res = settings.BASE_RESOLUTION
+            net           F_i = F_up_i - F_down_i;   heating rate: heatingRates(net, P, T, depth), K/day
+        The surface is black (emissivity 1); both boundary sources are isotropic radiances in the units of transmission()'s
+        surfaceSpectrum.  ``bands``: None (the whole range) or a list of (lo, hi) in cm^-1, band = the points lo <= nu_j < hi
+        (at most 64).  ``spectra``: also return F_up at the top and F_down at the surface per grid point.
+        With angles=[(1.0, pi)] the upward spectral flux at the top is pi * transmission(...) bit for bit wherever the fold
+        takes its one-exp-per-thread Planck path (every range and temperature away from nu -> 0).
+        The absorption coefficients come from the machinery transmission() uses and stay resident: after transmission()
+        nothing is accumulated again.  Everything is validated (ValueError) before the device is touched."""
+        layers = list(self)
+        if not layers:
+            raise ValueError("atmosphere has no layers")
+        first = layers[0]
+        for L in layers[1:]:
+            if (L.rangeMin, L.rangeMax) != (first.rangeMin, first.rangeMax):
+                raise ValueError("all layers of a column must share one wavenumber range")
+        if surfaceSpectrum is None and surfaceTemperature is None:
+            raise ValueError("give surfaceSpectrum or surfaceTemperature")
+        if surfaceSpectrum is None and not float(surfaceTemperature) > 0:
+            raise ValueError("surfaceTemperature must be > 0")
+        mu, weight = fluxAngles(angles)
+        n = int((first.rangeMax - first.rangeMin) / utils.BASE_RESOLUTION)
+        band_first, band_count = _flux_bands(first.rangeMin, first.rangeMax, n, bands)
+        sources = []
+        for name, spec in (("surfaceSpectrum", surfaceSpectrum), ("topSpectrum", topSpectrum)):
+            if spec is not None:
+                spec = np.ascontiguousarray(spec, dtype=np.float64)
+                if spec.shape != (n,):
+                    raise ValueError("%s: %d grid points expected, got shape %s" % (name, n, spec.shape))
+            sources.append(spec)
+        res = utils.BASE_RESOLUTION
+        nl, nb = len(layers), len(band_first)
+        ctx = _ctx()
+        if settings.LAYER_STEP == "merged" and not ctx.option("sweep_ieee_divisions"):
+            kbufs = [p[1].bufs["abs_coef"] for p in self._resident_abs_coef(ctx, layers, n)]
+        else:
+            kbufs = [L._ensure_swept()[0].bufs["abs_coef"] for L in layers]
+        fst = self.__dict__.get("_flux_state")
+        if fst is None:
+            fst = self.__dict__["_flux_state"] = _SweepState(self)
+        fst.reserve(ctx, max(n, nb * 2 * (nl + 1)))
+        I_surface = fst.buf(ctx, "I_surface").upload(sources[0]) if sources[0] is not None else None
+        I_top = fst.buf(ctx, "I_top").upload(sources[1]) if sources[1] is not None else None
+        level = fst.buf(ctx, "level")
+        up_top = fst.buf(ctx, "up_top") if spectra else None
+        down_surface = fst.buf(ctx, "down_surface") if spectra else None
+        ctx.column_flux_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
+                            mu, weight, band_first, band_count, level, I_surface=I_surface,
+                            surface_T=float(surfaceTemperature or 0.0), I_top=I_top, up_top=up_top, down_surface=down_surface)
+        sums = level.download(nb * 2 * (nl + 1)).reshape(nb, 2, nl + 1) * res
+        up, down = sums[:, 0, :], sums[:, 1, :]
+        heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], [L.depth for L in layers])
+        if bands is None:
+            up, down, heat = up[0], down[0], heat[0]
+        return Fluxes(up.copy(), down.copy(), heat, mu, weight,
+                      upSpectrum=up_top.download(n) if spectra else None,
+                      downSpectrum=down_surface.download(n) if spectra else None)
+
     def _transmission_merged(self, ctx, layers, n, surfaceSpectrum, surfaceTemperature):
         """settings.LAYER_STEP "merged": every layer whose inputs changed gets ONE accumulate job over its merged,
         factor-weighted line lists, all of them in one launch sequence (lbl_layers_merged_accumulate_dev: the layers'
@@ -1293,6 +1469,45 @@ class Atmosphere(list):
         fast = self._transmission_resident(ctx, layers, n, surfaceSpectrum, surfaceTemperature)
         if fast is not None:
             return fast
+        plan = self._resident_abs_coef(ctx, layers, n)
+        # (the outgoing spectrum's buffer stays with the atmosphere: a hipMalloc + hipFree pair per call is 0.2 ms of a 5 ms call)
+        ast = self.__dict__.get("_toa_state")
+        if ast is None:
+            ast = self.__dict__["_toa_state"] = _SweepState(self)
+        out = ast.reserve(ctx, n).buf(ctx, "toa")
+        I_in = None
+        if surfaceSpectrum is not None:
+            I_in = ast.buf(ctx, "I_in").upload(np.ascontiguousarray(surfaceSpectrum, dtype=np.float64))
+        first = layers[0]
+        # The fold in four pieces of the grid, each piece's part of the outgoing spectrum on its way to the host while the
+        # next piece is folded (19 MB at the link's rate are 0.4 ms of a 5 ms call).  No layer's transmittance is written
+        # (30 x 19 MB for arrays nobody has asked for): a layer's own getter makes it from the resident absorption
+        # coefficient, as after changeDepth (_ensure_swept: key equal up to its last entry).
+        host = ctx.host_array(n)
+        pieces = 4 if n >= (1 << 16) else 1
+        step = max(((n + pieces - 1) // pieces + 3) & ~3, 4)
+        try:
+            for lo in range(0, n, step):
+                cnt = min(step, n - lo)
+                ctx.column_fold_dev([p[1].bufs["abs_coef"] for p in plan], [p[0].T for p in plan], [p[0].depth for p in plan],
+                                    first.rangeMin, first.rangeMax, n, out, I_in=I_in, surface_T=float(surfaceTemperature or 0.0),
+                                    first=lo, count=cnt)
+                out.download_async(host, cnt, lo, lo)
+        finally:
+            # (also when a piece raised: copies into `host` may be in flight, and its page-locked block must not go back to
+            # the pool before they have landed - advisor, round 5)
+            ctx.download_wait()
+        self._column_remember(ctx, layers, n, plan)
+        return host
+
+    def _resident_abs_coef(self, ctx, layers, n):
+        """settings.LAYER_STEP "merged": make every layer's absorption coefficient resident on the device
+        (_SweepState.bufs["abs_coef"]) and return the plan [(layer, state, grid, members, flat, conc, merged key or None)].
+        The layers whose inputs changed get ONE accumulate job each over their merged, factor-weighted line lists, all of
+        them in one launch sequence (lbl_layers_merged_accumulate_dev: cls:707-712); a layer that cannot be a merged job
+        (no line list, a measured cross-section table among its molecules, more line lists than a job takes, an installed
+        cross section) brings its absorption coefficient by its own route (_ensure_swept).  Shared by transmission() and
+        fluxes(): after either, the other enqueues no accumulate job for unchanged layers."""
         plan = []
         for L in layers:
             members, conc = L._sweep_members()
@@ -1317,42 +1532,14 @@ class Atmosphere(list):
             [dict(lines=[i._device_lines(ctx) for i in flat], iso=[_iso_params(i) for i in flat],
                   grid=_engine.native_grid(g), iso_mol=[m for m, isos in enumerate(members) for _ in isos], conc=conc,
                   abs_coef=st.buf(ctx, "abs_coef")) for (L, st, g, members, flat, conc, key) in todo])
-        # (the outgoing spectrum's buffer stays with the atmosphere: a hipMalloc + hipFree pair per call is 0.2 ms of a 5 ms call)
-        ast = self.__dict__.get("_toa_state")
-        if ast is None:
-            ast = self.__dict__["_toa_state"] = _SweepState(self)
-        out = ast.reserve(ctx, n).buf(ctx, "toa")
-        I_in = None
-        if surfaceSpectrum is not None:
-            I_in = ast.buf(ctx, "I_in").upload(np.ascontiguousarray(surfaceSpectrum, dtype=np.float64))
-        first = layers[0]
-        # The fold in four pieces of the grid, each piece's part of the outgoing spectrum on its way to the host while the
-        # next piece is folded (19 MB at the link's rate are 0.4 ms of a 5 ms call).  No layer's transmittance is written
-        # (30 x 19 MB for arrays nobody has asked for): a layer's own getter makes it from the resident absorption
-        # coefficient, as after changeDepth (_ensure_swept: key equal up to its last entry).
-        host = ctx.host_array(n)
-        pieces = 4 if n >= (1 << 16) else 1
-        step = max(((n + pieces - 1) // pieces + 3) & ~3, 4)
-        try:
-            for lo in range(0, n, step):
-                cnt = min(step, n - lo)
-                ctx.column_fold_dev([p[1].bufs["abs_coef"] for p in plan], [p[0].T for p in plan], [p[0].depth for p in plan],
-                                    first.rangeMin, first.rangeMax, n, out, I_in=I_in, surface_T=float(surfaceTemperature or 0.0),
-                                    first=lo, count=cnt)
-                out.download_async(host, cnt, lo, lo)
-            for (L, st, g, members, flat, conc, key) in plan:
-                if key is not None and st.key != key:
-                    st.key = key[:-1] + ("absorption coefficient only",)
-            for (L, st, g, members, flat, conc, key) in todo:
-                for iso in flat:
-                    iso._defer_cross_section()
-                L._members_ready()
-        finally:
-            # (also when a piece raised: copies into `host` may be in flight, and its page-locked block must not go back to
-            # the pool before they have landed - advisor, round 5)
-            ctx.download_wait()
-        self._column_remember(ctx, layers, n, plan)
-        return host
+        for (L, st, g, members, flat, conc, key) in plan:
+            if key is not None and st.key != key:
+                st.key = key[:-1] + ("absorption coefficient only",)
+        for (L, st, g, members, flat, conc, key) in todo:
+            for iso in flat:
+                iso._defer_cross_section()
+            L._members_ready()
+        return plan
 
     # -- the resident column: the next call's argument blocks are already on the C side (lbl_column, ABI 5) --------------
     def _column_drop(self):
