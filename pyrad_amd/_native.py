@@ -102,6 +102,9 @@ SIGNATURES = {
                                       C.c_int64, _P, C.c_double, C.POINTER(_P), _P]),
     "lbl_column_flux_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, _P, C.c_double,
                                       _P, C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P]),
+    "lbl_column_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, _P,
+                                          C.c_double, C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.c_int, C.POINTER(_P), C.POINTER(C.c_int32), _P, _P, _P]),
     "lbl_column_create": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(IsoParams), C.POINTER(Grid),
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, _D, C.POINTER(_P), C.POINTER(_P)]),
     "lbl_column_destroy": (C.c_int, [_P]),
@@ -178,7 +181,7 @@ _limits = {}
 
 def limit(name: str) -> int:
     """A fixed size of the library (lbl_limit): "merged_lists_per_job", "arrays_per_layer", "arrays_per_sum",
-    "arrays_per_column", "layers_per_column", "jobs_per_batch", "flux_angles", "flux_bands"."""
+    "arrays_per_column", "layers_per_column", "jobs_per_batch", "flux_angles", "flux_bands", "jacobian_terms"."""
     if name not in _limits:
         v = C.c_int64()
         rc = load().lbl_limit(name.encode(), C.byref(v))
@@ -511,6 +514,23 @@ class Context:
             float(surface_T), hb(I_top), len(mu), arr(C.c_double, [float(m) for m in mu]),
             arr(C.c_double, [float(w) for w in weight]), len(band_first), arr(C.c_int64, [int(f) for f in band_first]),
             arr(C.c_int64, [int(c) for c in band_count]), hb(level_flux), hb(up_top), hb(down_surface)))
+
+    def column_jacobian_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
+                            jac, I_surface=None, surface_T=0.0, term_abs_coef=(), term_layer=(), ln_tau_spectra=None,
+                            T_spectra=None):
+        """Jacobians of the upward flux at the top (lbl_column_jacobian_dev): ``jac`` receives len(band_first) x (2 + 2 L +
+        len(term_abs_coef)) band sums [band][F, dF/dT_s, L x dF/d ln tau, L x dF/dT, terms x dF/d ln n]; ``term_layer``
+        gives each term's layer; ``ln_tau_spectra`` / ``T_spectra`` (optional, L x n points) the spectral values."""
+        nl = len(abs_coef)
+        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
+        hb = lambda b: b.h if b is not None else None
+        self.check(self.lib.lbl_column_jacobian_dev(
+            self.h, nl, arr(_P, [b.h for b in abs_coef]), arr(C.c_double, [float(t) for t in layer_T]),
+            arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), hb(I_surface),
+            float(surface_T), len(mu), arr(C.c_double, [float(m) for m in mu]),
+            arr(C.c_double, [float(w) for w in weight]), len(band_first), arr(C.c_int64, [int(f) for f in band_first]),
+            arr(C.c_int64, [int(c) for c in band_count]), len(term_abs_coef), arr(_P, [b.h for b in term_abs_coef]),
+            arr(C.c_int32, [int(l) for l in term_layer]), hb(jac), hb(ln_tau_spectra), hb(T_spectra)))
 
     def gather_compact_dev(self, gathered, slot, bounds, out):
         """padded all-gather result (slot r = rank r's shard) -> grid order (lbl_gather_compact_dev)."""

@@ -387,6 +387,7 @@ extern "C" int lbl_limit(const char* name, int64_t* value) {
     else if (!strcmp(name, "jobs_per_batch")) *value = LBL_MAX_JOBS;
     else if (!strcmp(name, "flux_angles")) *value = kMaxFluxAngles;           // angles of lbl_column_flux_dev
     else if (!strcmp(name, "flux_bands")) *value = kMaxFluxBands;             // bands of lbl_column_flux_dev
+    else if (!strcmp(name, "jacobian_terms")) *value = kMaxJacobianTerms;     // molecule terms of lbl_column_jacobian_dev
     else return LBL_ERR_BAD_ARG;
     return LBL_OK;
 }
@@ -2563,7 +2564,7 @@ int comm_fail(lbl_ctx* ctx, int code, const char* msg) { return fail(ctx, code, 
 int ctx_device(lbl_ctx* ctx) { return ctx->device; }
 bool ctx_capturing(lbl_ctx* ctx) { return ctx->capturing; }
 lbl_ctx* buffer_ctx(lbl_buffer* buf) { return buf->ctx; }
-// ... and for lbl_flux.hip
+// ... and for lbl_flux.hip and lbl_jacobian.hip
 hipStream_t ctx_stream(lbl_ctx* ctx) { return ctx->stream; }
 bool ctx_sweep_ieee(lbl_ctx* ctx) { return ctx->sweep_ieee != 0; }
 int ctx_device_args(lbl_ctx* ctx, const void* host, size_t bytes, void** dptr) { return device_args(ctx, host, bytes, dptr); }

@@ -250,6 +250,37 @@ int column_flux_partials(long long count);
 void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long long first, long long count, double* partial,
                         double* level_flux, hipStream_t s);
 
+// Jacobians of the outgoing flux (lbl_column_jacobian_dev, lbl_jacobian.hip): K5c's upward fold, then a downward pass that
+// keeps per angle the transmittance to the top A and D = E - I_top (E: emission of the layers above that reaches the top),
+// so that A_l t_l (B_l - I_l) = A_l B_l + D_l needs no stored radiance.  Values per band: [F_top, dF/dT_s, L x d ln tau,
+// L x dT (Planck part), n_terms x d ln n].
+constexpr int kMaxJacobianTerms = kMaxColumnIso;
+struct JacArgs {
+    const double* abs_coef[kMaxLayers];
+    double depth[kMaxLayers];
+    double pbkT[kMaxLayers];            // 100 h c / k / T_l
+    double rT[kMaxLayers];              // 1 / T_l (dB/dT = B b e^b / ((e^b - 1) T), b = nu pbkT)
+    double pbkT_min, pbkT_max;
+    double pbk_surface, r_surface_T;    // used when I_surface == nullptr
+    double rmu[kMaxFluxAngles];         // 1 / mu_k
+    double w[kMaxFluxAngles];           // W_k
+    double wrmu[kMaxFluxAngles];        // W_k / mu_k
+    double start, stop, step, pa;
+    const double* I_surface;
+    double* ln_tau_spec;                // optional: L x n spectral dF/d ln tau_l
+    double* T_spec;                     // optional: L x n spectral dF/dT_l
+    const double* term_k[kMaxJacobianTerms];   // the molecule terms sorted by layer (stable)
+    int32_t term_slot[kMaxJacobianTerms];      // ... and each one's index in the caller's list
+    int32_t layer_term[kMaxLayers + 1];        // terms of layer l: [layer_term[l], layer_term[l + 1])
+    long long n;
+    int32_t n_layers, n_angles, n_terms, pad;
+};
+// one band [first, first + count): partials (at most column_jacobian_partials(count) blocks of 2 + 2 L + n_terms values),
+// then the fixed-order reduction into jac[0 .. 2 + 2 L + n_terms)
+int column_jacobian_partials(long long count);
+void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first, long long count,
+                            double* partial, double* jac, hipStream_t s);
+
 struct ColumnArgs {
     const double* trans[kMaxLayers];
     double layer_T[kMaxLayers];

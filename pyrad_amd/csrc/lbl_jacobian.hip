@@ -1,0 +1,149 @@
+// Jacobians of the outgoing flux of a column (include/pyrad_hip.h, "Jacobians"): argument checking and the launch sequence
+// of lbl_column_jacobian_dev.  The kernels are K5d of lbl_kernels.hip; the context's internals are reached through the hooks
+// at the end of lbl_api.hip, as lbl_flux.hip does, so that lbl_api.hip builds on its own (tests/host_shim).
+#include "../../include/pyrad_hip.h"
+#include "lbl_device.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <new>
+#include <stdexcept>
+#include <vector>
+
+namespace lbl {
+int comm_fail(lbl_ctx* ctx, int code, const char* msg);
+int ctx_device(lbl_ctx* ctx);
+hipStream_t ctx_stream(lbl_ctx* ctx);
+bool ctx_sweep_ieee(lbl_ctx* ctx);
+int ctx_device_args(lbl_ctx* ctx, const void* host, size_t bytes, void** dptr);
+int ctx_reduction_scratch(lbl_ctx* ctx, size_t bytes, void** dptr);
+int ctx_check_buffer(lbl_ctx* ctx, lbl_buffer* b, int64_t n, const char* what, bool required);
+double* buffer_data(lbl_buffer* buf);
+void planck_budget_constants(double T, double* pa, double* pbkT);
+double grid_step(double lo, double hi, int64_t n);
+}
+
+using namespace lbl;
+
+static int jac_fail(lbl_ctx* ctx, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return comm_fail(ctx, code, buf);
+}
+
+// no C++ exception crosses the C boundary (see lbl_api.hip)
+#define LBL_GUARD_END(ctx_expr)                                                                                   \
+    catch (const std::bad_alloc&) { return comm_fail((ctx_expr), LBL_ERR_OOM, "host allocation failed"); }        \
+    catch (const std::exception& e) { return comm_fail((ctx_expr), LBL_ERR_STATE, e.what()); }                    \
+    catch (...) { return comm_fail((ctx_expr), LBL_ERR_STATE, "unknown C++ exception"); }
+
+#define JAC_HIP_TRY(ctx, expr)                                                                                    \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess)                                                                                     \
+            return jac_fail(ctx, e_ == hipErrorOutOfMemory ? LBL_ERR_OOM : LBL_ERR_HIP, "%s: %s", #expr,          \
+                            hipGetErrorString(e_));                                                               \
+    } while (0)
+
+extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                       const double* depth, double range_min, double range_max, int64_t n,
+                                       lbl_buffer* I_surface, double surface_T, int n_angles, const double* mu,
+                                       const double* weight, int n_bands, const int64_t* band_first,
+                                       const int64_t* band_count, int n_terms, lbl_buffer* const* term_abs_coef,
+                                       const int32_t* term_layer, lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra,
+                                       lbl_buffer* jac_T_spectra) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    if (n_layers < 0 || n_layers > kMaxLayers) return jac_fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
+    if (n < 0) return jac_fail(ctx, LBL_ERR_BAD_ARG, "negative n");
+    if (n_layers > 0 && (!abs_coef || !T || !depth)) return jac_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if (ctx_sweep_ieee(ctx))
+        return jac_fail(ctx, LBL_ERR_BAD_ARG, "Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)");
+    if (n_angles < 1 || n_angles > kMaxFluxAngles) return jac_fail(ctx, LBL_ERR_BAD_ARG, "1..%d angles", kMaxFluxAngles);
+    if (!mu || !weight) return jac_fail(ctx, LBL_ERR_BAD_ARG, "NULL angle set");
+    if (n_bands < 1 || n_bands > kMaxFluxBands) return jac_fail(ctx, LBL_ERR_BAD_ARG, "1..%d bands", kMaxFluxBands);
+    if (!band_first || !band_count) return jac_fail(ctx, LBL_ERR_BAD_ARG, "NULL band list");
+    if (n_terms < 0 || n_terms > kMaxJacobianTerms)
+        return jac_fail(ctx, LBL_ERR_BAD_ARG, "at most %d molecule terms", kMaxJacobianTerms);
+    if (n_terms > 0 && (!term_abs_coef || !term_layer)) return jac_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
+    const int nv = 2 + 2 * n_layers + n_terms;
+    int rc;
+    if ((rc = ctx_check_buffer(ctx, jac, (int64_t)n_bands * nv, "jac", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, I_surface, n, "I_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, jac_ln_tau_spectra, (int64_t)n_layers * n, "jac_ln_tau_spectra", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, jac_T_spectra, (int64_t)n_layers * n, "jac_T_spectra", false))) return rc;
+    if (!I_surface && !(surface_T > 0)) return jac_fail(ctx, LBL_ERR_BAD_ARG, "need I_surface or surface_T > 0");
+    for (int b = 0; b < n_bands; ++b)
+        if (band_first[b] < 0 || band_count[b] < 1 || band_count[b] > n - band_first[b])
+            return jac_fail(ctx, LBL_ERR_BAD_ARG, "band %d: empty or outside [0, n)", b);
+    std::vector<char> blk(sizeof(JacArgs), 0);
+    JacArgs* a = (JacArgs*)blk.data();
+    double pa = 0.0;
+    for (int l = 0; l < n_layers; ++l) {
+        if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
+        if (!(T[l] > 0)) return jac_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
+        if (!(depth[l] >= 0)) return jac_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: depth must be >= 0", l);
+        a->abs_coef[l] = buffer_data(abs_coef[l]);
+        a->depth[l] = depth[l];
+        a->rT[l] = 1.0 / T[l];
+        planck_budget_constants(T[l], &pa, &a->pbkT[l]);
+        a->pbkT_min = l == 0 ? a->pbkT[l] : std::min(a->pbkT_min, a->pbkT[l]);
+        a->pbkT_max = l == 0 ? a->pbkT[l] : std::max(a->pbkT_max, a->pbkT[l]);
+    }
+    // the molecule terms, sorted by layer (stable): layer l reads [layer_term[l], layer_term[l + 1])
+    for (int t = 0; t < n_terms; ++t) {
+        if (term_layer[t] < 0 || term_layer[t] >= n_layers)
+            return jac_fail(ctx, LBL_ERR_BAD_ARG, "term %d: layer %d outside [0, %d)", t, (int)term_layer[t], n_layers);
+        if ((rc = ctx_check_buffer(ctx, term_abs_coef[t], n, "term_abs_coef", true))) return rc;
+        ++a->layer_term[term_layer[t] + 1];
+    }
+    for (int l = 0; l < n_layers; ++l) a->layer_term[l + 1] += a->layer_term[l];
+    {
+        std::vector<int32_t> fill(a->layer_term, a->layer_term + std::max(n_layers, 1));
+        for (int t = 0; t < n_terms; ++t) {
+            const int pos = fill[term_layer[t]]++;
+            a->term_k[pos] = buffer_data(term_abs_coef[t]);
+            a->term_slot[pos] = t;
+        }
+    }
+    for (int k = 0; k < n_angles; ++k) {
+        if (!(mu[k] > 0 && mu[k] <= 1)) return jac_fail(ctx, LBL_ERR_BAD_ARG, "angle %d: mu must lie in (0, 1]", k);
+        if (!std::isfinite(weight[k])) return jac_fail(ctx, LBL_ERR_BAD_ARG, "angle %d: weight must be finite", k);
+        a->rmu[k] = 1.0 / mu[k];
+        a->w[k] = weight[k];
+        a->wrmu[k] = weight[k] * a->rmu[k];
+    }
+    planck_budget_constants(surface_T > 0 ? surface_T : 1.0, &pa, &a->pbk_surface);
+    a->r_surface_T = surface_T > 0 ? 1.0 / surface_T : 0.0;
+    a->pa = pa;
+    a->start = range_min; a->stop = range_max; a->step = grid_step(range_min, range_max, n);
+    a->I_surface = I_surface ? buffer_data(I_surface) : nullptr;
+    a->ln_tau_spec = jac_ln_tau_spectra ? buffer_data(jac_ln_tau_spectra) : nullptr;
+    a->T_spec = jac_T_spectra ? buffer_data(jac_T_spectra) : nullptr;
+    a->n = n;
+    a->n_layers = n_layers; a->n_angles = n_angles; a->n_terms = n_terms;
+    int64_t max_count = 0;
+    for (int b = 0; b < n_bands; ++b) max_count = std::max(max_count, band_count[b]);
+    void* partial = nullptr;
+    if ((rc = ctx_reduction_scratch(ctx, (size_t)column_jacobian_partials(max_count) * nv * sizeof(double), &partial))) return rc;
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, a, sizeof(JacArgs), &d_args))) return rc;
+    const hipStream_t s = ctx_stream(ctx);
+    JAC_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    // (points outside every band keep 0 in the spectra)
+    const size_t spec_bytes = (size_t)n_layers * (size_t)n * sizeof(double);
+    if (a->ln_tau_spec && spec_bytes) JAC_HIP_TRY(ctx, hipMemsetAsync(a->ln_tau_spec, 0, spec_bytes, s));
+    if (a->T_spec && spec_bytes) JAC_HIP_TRY(ctx, hipMemsetAsync(a->T_spec, 0, spec_bytes, s));
+    // the bands one after another over one partial block: stream order keeps a band's final reduction ahead of the next band
+    for (int b = 0; b < n_bands; ++b)
+        launch_column_jacobian((const JacArgs*)d_args, n_layers, n_angles, n_terms, band_first[b], band_count[b],
+                               (double*)partial, buffer_data(jac) + (size_t)b * nv, s);
+    JAC_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+} LBL_GUARD_END(ctx)

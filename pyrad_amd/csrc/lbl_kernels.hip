@@ -11,6 +11,8 @@
 //   K6 band_integral kernels   pyradClasses.py:26-29
 //   K5c column_flux_kernel     K5b's fold over absorption coefficients for several angles, upward and downward,
 //                              reduced to level fluxes (Atmosphere.fluxes; beyond the reference)
+//   K5d column_jacobian_kernel K5c's upward fold + a downward pass: analytic derivatives of the outgoing flux
+//                              (Atmosphere.jacobians; beyond the reference)
 //   K7 line_survey_kernel      pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -3446,6 +3448,213 @@ __global__ __launch_bounds__(256) void column_flux_final_kernel(const double* __
 }
 
 // ----------------------------------------------------------------------------------------
+// K5d: Jacobians of the outgoing flux (lbl_column_jacobian_dev; the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// planck_budget's value, bit for bit, and with it dB/dT = B b e^b / ((e^b - 1) T) from the same exp (rT = 1 / T)
+__device__ __forceinline__ double planck_budget_dT(double n, double pa, double pbkT, double rT, double* dB) {
+    const double b = n * pbkT;
+    const double e = exp_clamped(fmin(b, 700.0)) - 1.0;
+    const double rc = rcp_newton(fmax(e, 1e-300));
+    const double v = (pa * (n * n * n)) * rc;
+    const bool general = b > 700.0 || !(e > 0.0);
+    const double r = general ? ((b > 700.0) ? 0.0 : (pa * (n * n * n)) / e) : v;
+    const double d = general ? ((b > 700.0) ? 0.0 : r * (b * (e + 1.0) / e) * rT) : r * (((e + 1.0) * rc) * b) * rT;
+    *dB = b != b ? b : d;
+    return b != b ? b : r;
+}
+
+// K5c's upward fold (same Planck paths, guard and update), keeping per angle only the radiance I and its running maximum
+// Imax over the levels; then a downward pass that re-reads k_l and recomputes B_l as K5c's does, and keeps per angle the
+// transmittance A to the top and D = E - I_top, E the emission of the layers above that reaches the top.  Then
+//     A_l t_l (B_l - I_l) = A_l B_l + E_l - I_top = A_l B_l + D_l,
+// clamped to [-A_l t_l Imax, A_l t_l B_l] (both bounds exact for non-negative sources): where the path above is opaque the
+// true value underflows to ~0 while E - I_top is rounding noise that tau / mu would amplify.  Per point and layer:
+// G = sum_k (W_k / mu_k) g_k; d ln tau_l = tau_l G, molecule term m of the layer = k_(m,l) depth_l G, dT_l = sum_k W_k A (1 - t) dB_l/dT.
+// Sums: per thread (nan_to_num per point), wave_sum, lane 0 into its wave's LDS slot; the four waves in a fixed order into one
+// partial per workgroup; column_flux_final_kernel adds the partials in a fixed order.  No float atomics.
+template <int NP, int NA>
+__global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                              long long lo1, long long n1, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    typedef double vec __attribute__((ext_vector_type(NP)));
+    typedef const vec __attribute__((address_space(1)))* GlobalVec;
+    constexpr int kSlot = 2 + 2 * kMaxLayers + kMaxJacobianTerms;
+    __shared__ double acc[4 * kSlot];            // [wave][F_top, dT_s, L x ln tau, L x T, terms]
+    const JacArgs& A = *Ap;
+    const int L = A.n_layers;
+    const int nv = 2 + 2 * L + A.n_terms;
+    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
+    __syncthreads();
+    double* my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    auto load = [&](const double* p, long long j) {
+        vec v;
+        if (NP == 1) v[0] = load_global_f64(p, j);
+        else v = *(GlobalVec)(unsigned long long)(p + j);
+        return v;
+    };
+    auto add = [&](int slot, double s) {
+        s = wave_sum(s);
+        if (lane0) my[slot] += s;
+    };
+    const long long total = n0 + n1;
+    const long long stride = (long long)gridDim.x * blockDim.x * NP;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
+    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
+        const long long q = q0 + (long long)threadIdx.x * NP;
+        const bool active = q < total;
+        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        double nu[NP], pa_n[NP], dBs[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            nu[p] = linspace_at(j + p, A.n, A.start, A.stop, A.step);
+            pa_n[p] = A.pa * (nu[p] * nu[p] * nu[p]);
+        }
+        const double dnu_last = nu[NP - 1] - nu[0];
+        const bool plain = NP > 1 && nu[0] * A.pbkT_min >= 1e-6 && nu[NP - 1] * A.pbkT_max <= 690.0
+                           && dnu_last * A.pbkT_max <= 1e-3 && dnu_last >= 0.0;
+        const bool fast = NP > 1 && __builtin_amdgcn_ballot_w64(active && !plain) == 0ull;
+        // B_l and dB_l/dT at point p (K5c's two paths; the fast one from the thread's single exp E0)
+        auto planck = [&](auto fast_tag, int p, double pbkT, double rT, double E0, double& dB) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            double B;
+            if (FAST) {
+                const double E = p == 0 ? E0 : fma(E0, expm1_tiny((nu[p] - nu[0]) * pbkT), E0);
+                const double rc = rcp_newton(E - 1.0);
+                B = pa_n[p] * rc;
+                dB = B * ((E * rc) * (nu[p] * pbkT)) * rT;
+            } else {
+                const double b = nu[p] * pbkT;
+                const double e = exp_clamped(fmin(b, 700.0)) - 1.0;
+                const double rc = rcp_newton(fmax(e, 1e-300));
+                B = (b > 700.0) ? 0.0 : (e > 0.0 ? pa_n[p] * rc : pa_n[p] / e);
+                dB = (b > 700.0) ? 0.0 : (e > 0.0 ? B * (((e + 1.0) * rc) * b) * rT : B * (b * (e + 1.0) / e) * rT);
+                B = b != b ? b : B;
+                dB = b != b ? b : dB;
+            }
+            return B;
+        };
+        auto up = [&](auto fast_tag, int l, vec v) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double pbkT = A.pbkT[l], depth = A.depth[l];
+            double E0 = 0.0;
+            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+                double dB;
+                const double B = planck(fast_tag, p, pbkT, 0.0, E0, dB);
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double tr = exp_neg_budget(tau * A.rmu[k]);
+                    if (FAST) {
+                        I[k][p] = fma(tr, I[k][p], (1.0 - tr) * B);
+                    } else {
+                        const double transmitted = tr * I[k][p];
+                        const double emitted = (1.0 - tr) * B;
+                        I[k][p] = transmitted + emitted;
+                    }
+                    Imax[k][p] = fmax(Imax[k][p], I[k][p]);
+                }
+            }
+        };
+        auto down = [&](auto fast_tag, int l, vec v) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double pbkT = A.pbkT[l], depth = A.depth[l], rT = A.rT[l];
+            double E0 = 0.0;
+            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+            double s_tau = 0.0, s_T = 0.0, Gd[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+                double dB;
+                const double B = planck(fast_tag, p, pbkT, rT, E0, dB);
+                double G = 0.0, gT = 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double tr = exp_neg_budget(tau * A.rmu[k]);
+                    const double At = Ak[k][p] * tr;
+                    const double g = fmin(fmax(Ak[k][p] * B + I[k][p], -(At * Imax[k][p])), At * B);
+                    G = fma(A.wrmu[k], g, G);
+                    const double a1 = Ak[k][p] * (1.0 - tr);
+                    gT = fma(A.w[k], a1 * dB, gT);
+                    I[k][p] = I[k][p] + a1 * B;              // D_(l-1) = D_l + A_l (1 - t_l) B_l
+                    Ak[k][p] = At;                           // A_(l-1) = A_l t_l
+                }
+                const double dtau = tau * G;
+                Gd[p] = depth * G;
+                if (active && A.ln_tau_spec) A.ln_tau_spec[(long long)l * A.n + j + p] = dtau;
+                if (active && A.T_spec) A.T_spec[(long long)l * A.n + j + p] = gT;
+                s_tau += active ? nan_to_num(dtau) : 0.0;
+                s_T += active ? nan_to_num(gT) : 0.0;
+            }
+            add(2 + l, s_tau);
+            add(2 + L + l, s_T);
+            for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
+                const vec km = load(A.term_k[t], j);
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < NP; ++p) s += active ? nan_to_num(km[p] * Gd[p]) : 0.0;
+                add(2 + 2 * L + A.term_slot[t], s);
+            }
+        };
+        auto walk = [&](auto fast_tag) {
+            // upward: I_0 = I_surface or B(nu, surface_T), as K5c
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                dBs[p] = 0.0;
+                const double Is = A.I_surface ? A.I_surface[j + p] : planck_budget_dT(nu[p], A.pa, A.pbk_surface, A.r_surface_T, &dBs[p]);
+#pragma unroll
+                for (int k = 0; k < NA; ++k) { I[k][p] = Is; Imax[k][p] = Is; }
+            }
+            vec cur = L > 0 ? load(A.abs_coef[0], j) : (vec)(0.0);
+            for (int l = 0; l < L; ++l) {
+                const vec nxt = l + 1 < L ? load(A.abs_coef[l + 1], j) : cur;
+                up(fast_tag, l, cur);
+                cur = nxt;
+            }
+            // F_top; then I becomes D = -I_top and A = 1
+            double s = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double f = A.w[0] * I[0][p];
+#pragma unroll
+                for (int k = 1; k < NA; ++k) f = fma(A.w[k], I[k][p], f);
+                s += active ? nan_to_num(f) : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
+            }
+            add(0, s);
+            cur = L > 0 ? load(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load(A.abs_coef[l - 1], j) : cur;
+                down(fast_tag, l, cur);
+                cur = nxt;
+            }
+            // dF/dT_s = sum_k W_k A_(-1)k dB(nu, T_s)/dT (0 when the surface is a given spectrum)
+            s = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double f = A.w[0] * (Ak[0][p] * dBs[p]);
+#pragma unroll
+                for (int k = 1; k < NA; ++k) f = fma(A.w[k], Ak[k][p] * dBs[p], f);
+                s += active ? nan_to_num(f) : 0.0;
+            }
+            add(1, s);
+        };
+        if constexpr (NP > 1) {
+            if (fast) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += blockDim.x)
+        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+}
+
+// ----------------------------------------------------------------------------------------
 // K7: line survey (pyradClasses.py:409-428): S added into the bin of each line, in line order
 // ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void line_survey_kernel(const double* __restrict__ nu, const double* __restrict__ sw,
@@ -3787,6 +3996,58 @@ void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long
         case 6: launch_column_flux_na<6>(d_args, nv, first, count, partial, level_flux, s); break;
         case 7: launch_column_flux_na<7>(d_args, nv, first, count, partial, level_flux, s); break;
         case 8: launch_column_flux_na<8>(d_args, nv, first, count, partial, level_flux, s); break;
+        default: break;
+    }
+}
+
+// ---- K5d launch: one band [first, first + count) --------------------------------------------------------------------
+// As K5c's, with NP points per thread chosen per angle count so that no instantiation spills (DESIGN.md "K5d"): groups of
+// NP aligned to NP on the global grid go to the NP kernel, the band's head and tail points (at most 2 (NP - 1)) to ONE
+// 64-lane workgroup of the NP = 1 kernel, whose partial follows the others'.
+template <int NA> constexpr int jacobian_np() { return NA <= 2 ? 4 : 2; }
+
+int column_jacobian_partials(long long count) {
+    const long long groups = count / 2 + 1;
+    return (int)std::min<long long>((groups + 255) / 256, kFluxMaxBlocks) + 1;
+}
+
+template <int NA>
+static void launch_column_jacobian_na(const JacArgs* d_args, int nv, long long first, long long count, double* partial,
+                                      double* jac, hipStream_t s) {
+    constexpr int NP = jacobian_np<NA>();
+    const long long end = first + count;
+    const long long q0 = (first + NP - 1) & ~(long long)(NP - 1);
+    long long q1 = end & ~(long long)(NP - 1);
+    if (q1 < q0) q1 = q0;
+    const long long nq = q1 - q0;
+    const long long nh = std::min(q0, end) - first;
+    const long long nt = end > q1 ? end - q1 : 0;
+    int blocks = 0;
+    if (nq > 0) {
+        blocks = (int)std::min<long long>((nq / NP + 255) / 256, kFluxMaxBlocks);
+        hipLaunchKernelGGL((column_jacobian_kernel<NP, NA>), dim3(blocks), dim3(256), 0, s, d_args, q0, nq, q0, 0LL, partial);
+    }
+    if (nh + nt > 0) {
+        hipLaunchKernelGGL((column_jacobian_kernel<1, NA>), dim3(1), dim3(64), 0, s, d_args, nh > 0 ? first : q1, nh, q1, nt,
+                           partial + (long long)blocks * nv);
+        ++blocks;
+    }
+    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, blocks, nv, jac);
+}
+
+void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first, long long count,
+                            double* partial, double* jac, hipStream_t s) {
+    if (count <= 0) return;
+    const int nv = 2 + 2 * n_layers + n_terms;
+    switch (n_angles) {
+        case 1: launch_column_jacobian_na<1>(d_args, nv, first, count, partial, jac, s); break;
+        case 2: launch_column_jacobian_na<2>(d_args, nv, first, count, partial, jac, s); break;
+        case 3: launch_column_jacobian_na<3>(d_args, nv, first, count, partial, jac, s); break;
+        case 4: launch_column_jacobian_na<4>(d_args, nv, first, count, partial, jac, s); break;
+        case 5: launch_column_jacobian_na<5>(d_args, nv, first, count, partial, jac, s); break;
+        case 6: launch_column_jacobian_na<6>(d_args, nv, first, count, partial, jac, s); break;
+        case 7: launch_column_jacobian_na<7>(d_args, nv, first, count, partial, jac, s); break;
+        case 8: launch_column_jacobian_na<8>(d_args, nv, first, count, partial, jac, s); break;
         default: break;
     }
 }

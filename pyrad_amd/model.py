@@ -1308,6 +1308,31 @@ class Fluxes:
             self.up.shape[-1], len(self.mu), self.up[..., -1], self.down[..., 0])
 
 
+class Jacobians:
+    """What Atmosphere.jacobians returns (a leading band axis on every band value when ``bands`` was given).
+    ``olr``: upward flux at the top, W m^-2; ``surfaceTemperature``: dF/dT_s in W m^-2 K^-1, None when a surface spectrum was
+    given; ``temperature``: (L,) dF/dT_l, Planck part; ``opticalDepth``: (L,) dF/d ln tau_l; ``molecules``: one array per
+    layer, aligned with list(layer), dF/d ln n of every molecule (None when not asked for); ``moleculeNames``: their names;
+    ``mu``, ``weight``: the angle set; ``temperatureSpectrum`` / ``opticalDepthSpectrum``: (L, n) spectral dF/dT_l and
+    dF/d ln tau_l (W m^-2 per cm^-1, 0 outside every band) when asked for, else None."""
+
+    def __init__(self, olr, surfaceTemperature, temperature, opticalDepth, molecules, moleculeNames, mu, weight,
+                 temperatureSpectrum=None, opticalDepthSpectrum=None):
+        self.olr = olr
+        self.surfaceTemperature = surfaceTemperature
+        self.temperature = temperature
+        self.opticalDepth = opticalDepth
+        self.molecules = molecules
+        self.moleculeNames = moleculeNames
+        self.mu = mu
+        self.weight = weight
+        self.temperatureSpectrum = temperatureSpectrum
+        self.opticalDepthSpectrum = opticalDepthSpectrum
+
+    def __repr__(self):
+        return "Jacobians(layers=%d, angles=%d, olr=%s)" % (self.opticalDepth.shape[-1], len(self.mu), self.olr)
+
+
 # ----------------------------------------------------------------------------------------
 # Atmosphere (cls:790-821) + the column fold this build defines on it (SURVEY.md §3.5)
 # ----------------------------------------------------------------------------------------
@@ -1454,6 +1479,140 @@ class Atmosphere(list):
         return Fluxes(up.copy(), down.copy(), heat, mu, weight,
                       upSpectrum=up_top.download(n) if spectra else None,
                       downSpectrum=down_surface.download(n) if spectra else None)
+
+    def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False):
+        """Analytic sensitivities of the upward flux at the top (beyond the reference), in one pass over the resident
+        absorption coefficients.
+
+        Column, layer order, grid, angle set (fluxAngles), bands (as fluxes()), nan_to_num and res factor of fluxes().  At
+        every grid point nu_j and angle k (mu_k, W_k):
+            tau_l = k_l(nu_j) depth_l      t_lk = exp(-tau_l / mu_k)      B_l = planckWavenumber(nu_j, T_l)
+            I_0k  = surfaceSpectrum[j] or B(nu_j, T_s)      I_(l+1)k = t_lk I_lk + (1 - t_lk) B_l
+            A_lk  = prod_{i>l} t_ik  (A_(L-1)k = 1)          A_(-1)k = prod_i t_ik
+            F(nu_j)             = sum_k W_k I_Lk                                             upward spectral flux at the top
+            dF/d ln tau_l       = sum_k W_k (tau_l / mu_k) A_lk t_lk (B_l - I_lk)            all absorbers of layer l scaled
+            dF/d ln n_(m,l)     = sum_k W_k (k_(m,l) depth_l / mu_k) A_lk t_lk (B_l - I_lk)  molecule m of layer l
+            dF/dT_l  (Planck)   = sum_k W_k A_lk (1 - t_lk) dB_l/dT                          absorption coefficients held fixed
+            dF/dT_s             = sum_k W_k A_(-1)k dB(nu_j, T_s)/dT                         only when the surface is T_s
+            band value          = res * sum over the band's points of nan_to_num(spectral value)
+        k_(m,l) is molecule m's own absorption coefficient in layer l (Molecule.absCoef); their sum over m is k_l up to
+        rounding.  The molecule Jacobian is the sensitivity to absorber amount AT FIXED LINE SHAPES: the self-broadening
+        fraction in the Lorentz width is not differentiated.  The temperature Jacobian is the PLANCK PART ONLY: dk/dT (line
+        intensity, width, number density) is not included.
+        ``molecules``: also the molecule terms (one merged accumulate job per layer and molecule, kept with the atmosphere
+        and re-used while that molecule's inputs stand; False skips them).  ``spectra``: also the spectral dF/dT_l and
+        dF/d ln tau_l, (L, n) each.  Returns a Jacobians.  The layers' absorption coefficients are the ones fluxes() and
+        transmission() keep resident: after either nothing is accumulated again.  No other result of the model changes.
+        Everything is validated (ValueError) before the device is touched."""
+        layers = list(self)
+        if not layers:
+            raise ValueError("atmosphere has no layers")
+        first = layers[0]
+        for L in layers[1:]:
+            if (L.rangeMin, L.rangeMax) != (first.rangeMin, first.rangeMax):
+                raise ValueError("all layers of a column must share one wavenumber range")
+        if surfaceSpectrum is None and surfaceTemperature is None:
+            raise ValueError("give surfaceSpectrum or surfaceTemperature")
+        if surfaceSpectrum is None and not float(surfaceTemperature) > 0:
+            raise ValueError("surfaceTemperature must be > 0")
+        mu, weight = fluxAngles(angles)
+        n = int((first.rangeMax - first.rangeMin) / utils.BASE_RESOLUTION)
+        band_first, band_count = _flux_bands(first.rangeMin, first.rangeMax, n, bands)
+        if surfaceSpectrum is not None:
+            surfaceSpectrum = np.ascontiguousarray(surfaceSpectrum, dtype=np.float64)
+            if surfaceSpectrum.shape != (n,):
+                raise ValueError("surfaceSpectrum: %d grid points expected, got shape %s" % (n, surfaceSpectrum.shape))
+        names = [[m.name for m in L] for L in layers]
+        n_terms = sum(len(L) for L in layers) if molecules else 0
+        if n_terms > nat.limit("jacobian_terms"):
+            raise ValueError("molecules: %d molecule terms, at most %d (molecules=False skips them)"
+                             % (n_terms, nat.limit("jacobian_terms")))
+        res = utils.BASE_RESOLUTION
+        nl, nb = len(layers), len(band_first)
+        ctx = _ctx()
+        if ctx.option("sweep_ieee_divisions"):
+            raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
+        if settings.LAYER_STEP == "merged":
+            plan = self._resident_abs_coef(ctx, layers, n)
+            kbufs = [p[1].bufs["abs_coef"] for p in plan]
+        else:
+            plan = None
+            kbufs = [L._ensure_swept()[0].bufs["abs_coef"] for L in layers]
+        js = self.__dict__.get("_jacobian_state")
+        if js is None:
+            js = self.__dict__["_jacobian_state"] = dict(terms={}, out=_SweepState(self), spec=_SweepState(self))
+        term_bufs, term_layer = self._jacobian_terms(ctx, layers, n, plan, js) if molecules else ([], [])
+        nv = 2 + 2 * nl + len(term_bufs)
+        out = js["out"].reserve(ctx, max(n, nb * nv))
+        I_surface = out.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
+        jac = out.buf(ctx, "jac")
+        ln_tau_spec = T_spec = None
+        if spectra:
+            sp = js["spec"].reserve(ctx, nl * n)
+            ln_tau_spec, T_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T")
+        ctx.column_jacobian_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
+                                mu, weight, band_first, band_count, jac, I_surface=I_surface,
+                                surface_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs, term_layer=term_layer,
+                                ln_tau_spectra=ln_tau_spec, T_spectra=T_spec)
+        v = jac.download(nb * nv).reshape(nb, nv) * res
+        olr, dTs = v[:, 0], v[:, 1]
+        dtau, dT = v[:, 2:2 + nl], v[:, 2 + nl:2 + 2 * nl]
+        mol = None
+        if molecules:
+            mol, o = [], 2 + 2 * nl
+            for L in layers:
+                mol.append(v[:, o:o + len(L)])
+                o += len(L)
+        if bands is None:
+            olr, dTs, dtau, dT = olr[0], dTs[0], dtau[0], dT[0]
+            mol = [m[0] for m in mol] if mol is not None else None
+        else:
+            olr, dTs, dtau, dT = olr.copy(), dTs.copy(), dtau.copy(), dT.copy()
+            mol = [m.copy() for m in mol] if mol is not None else None
+        return Jacobians(olr, dTs if surfaceSpectrum is None else None, dT, dtau, mol, names, mu, weight,
+                         temperatureSpectrum=T_spec.download(nl * n).reshape(nl, n) if spectra else None,
+                         opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None)
+
+    def _jacobian_terms(self, ctx, layers, n, plan, js):
+        """The molecule terms of jacobians(): every molecule's own absorption coefficient k_(m,l), as (buffers, layer index
+        of each).  In a layer that is one merged job (``plan`` of _resident_abs_coef) a molecule gets ONE merged accumulate
+        job over its own line lists (its volume fraction, iso_mol all 0) into a buffer of the atmosphere's Jacobian state,
+        keyed like the layer's (_merged_key): it is recomputed only when that molecule's inputs change, and all due
+        molecules go in one launch sequence.  Exotic molecules, molecules without line lists and layers that are no merged
+        job use the molecule's own route (Molecule._ensure_swept)."""
+        terms = js["terms"]
+        bufs, where, todo, keys, keep = [], [], [], [], set()
+        for l, L in enumerate(layers):
+            members, conc = L._sweep_members()
+            merged = plan is not None and plan[l][6] is not None
+            g = L._grid() if merged else None
+            for mi, m in enumerate(L):
+                isos = members[mi]
+                if not merged or not isos or m.exotic:
+                    bufs.append(m._ensure_swept()[0].bufs["abs_coef"])
+                    where.append(l)
+                    continue
+                tk = (id(L), id(m))
+                keep.add(tk)
+                st = terms.get(tk)
+                if st is None:
+                    st = terms[tk] = _SweepState(self)
+                st.reserve(ctx, n)
+                key = L._merged_key(isos, [conc[mi]], L, g)[:-1]          # (the depth does not enter k)
+                if st.key != key:
+                    todo.append(dict(lines=[i._device_lines(ctx) for i in isos], iso=[_iso_params(i) for i in isos],
+                                     grid=_engine.native_grid(g), iso_mol=[0] * len(isos), conc=[conc[mi]],
+                                     abs_coef=st.buf(ctx, "abs_coef")))
+                    keys.append((st, key))
+                bufs.append(st.buf(ctx, "abs_coef"))
+                where.append(l)
+        for tk in [t for t in terms if t not in keep]:
+            _free_buffers(terms.pop(tk).bufs)
+        if todo:
+            ctx.layers_merged_accumulate_dev(todo)
+            for st, key in keys:
+                st.key = key
+        return bufs, where
 
     def _transmission_merged(self, ctx, layers, n, surfaceSpectrum, surfaceTemperature):
         """settings.LAYER_STEP "merged": every layer whose inputs changed gets ONE accumulate job over its merged,
