@@ -147,11 +147,11 @@ def build(force: bool = False) -> str:
 
 def source_hash() -> str:
     """sha256 over what decides the kernels and their launch shapes (csrc/lbl_kernels.hip, lbl_api.hip,
-    lbl_device.h, lbl_flux.hip, Makefile): profiles/pmc_traffic.json records it so that bench.py can tell when
-    committed PMC numbers were measured on other kernels than the ones it is timing."""
+    lbl_device.h, lbl_column_transport.hip, Makefile): profiles/pmc_traffic.json records it so that bench.py can tell
+    when committed PMC numbers were measured on other kernels than the ones it is timing."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("Makefile", "lbl_api.hip", "lbl_device.h", "lbl_kernels.hip", "lbl_launch_shapes.h", "lbl_flux.hip"):
+    for f in ("Makefile", "lbl_api.hip", "lbl_device.h", "lbl_kernels.hip", "lbl_launch_shapes.h", "lbl_column_transport.hip"):
         h.update(f.encode())
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
@@ -198,6 +198,10 @@ def _as_f64(a):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _hb(b):
+    return None if b is None else b.h
 
 
 class Context:
@@ -500,20 +504,26 @@ class Context:
             arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), int(first), int(count),
             hb(I_in), float(surface_T), arr(_P, [hb(b) for b in trans]) if trans is not None else None, I_out.h))
 
+    def _column_args(self, abs_coef, layer_T, depth, range_min, range_max, n, I_surface, surface_T, after_surface, mu,
+                     weight, band_first, band_count):
+        """The leading arguments lbl_column_flux_dev and lbl_column_jacobian_dev share, from ctx to band_count
+        (``after_surface``: what the entry point takes between surface_T and the angle set)."""
+        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
+        return (self.h, len(abs_coef), arr(_P, [b.h for b in abs_coef]), arr(C.c_double, [float(t) for t in layer_T]),
+                arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), _hb(I_surface),
+                float(surface_T), *after_surface, len(mu), arr(C.c_double, [float(m) for m in mu]),
+                arr(C.c_double, [float(w) for w in weight]), len(band_first), arr(C.c_int64, [int(f) for f in band_first]),
+                arr(C.c_int64, [int(c) for c in band_count]))
+
     def column_flux_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                         level_flux, I_surface=None, surface_T=0.0, I_top=None, up_top=None, down_surface=None):
         """Level fluxes of a column from the layers' absorption coefficients (lbl_column_flux_dev): ``level_flux`` receives
         len(band_first) x 2 x (layers + 1) band sums [band][up, down][level]; ``up_top`` / ``down_surface`` (optional, n
         points) the spectral upward flux at the top and downward flux at the surface."""
-        nl = len(abs_coef)
-        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
-        hb = lambda b: b.h if b is not None else None
         self.check(self.lib.lbl_column_flux_dev(
-            self.h, nl, arr(_P, [b.h for b in abs_coef]), arr(C.c_double, [float(t) for t in layer_T]),
-            arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), hb(I_surface),
-            float(surface_T), hb(I_top), len(mu), arr(C.c_double, [float(m) for m in mu]),
-            arr(C.c_double, [float(w) for w in weight]), len(band_first), arr(C.c_int64, [int(f) for f in band_first]),
-            arr(C.c_int64, [int(c) for c in band_count]), hb(level_flux), hb(up_top), hb(down_surface)))
+            *self._column_args(abs_coef, layer_T, depth, range_min, range_max, n, I_surface, surface_T, (_hb(I_top),), mu,
+                               weight, band_first, band_count),
+            _hb(level_flux), _hb(up_top), _hb(down_surface)))
 
     def column_jacobian_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                             jac, I_surface=None, surface_T=0.0, term_abs_coef=(), term_layer=(), ln_tau_spectra=None,
@@ -521,16 +531,12 @@ class Context:
         """Jacobians of the upward flux at the top (lbl_column_jacobian_dev): ``jac`` receives len(band_first) x (2 + 2 L +
         len(term_abs_coef)) band sums [band][F, dF/dT_s, L x dF/d ln tau, L x dF/dT, terms x dF/d ln n]; ``term_layer``
         gives each term's layer; ``ln_tau_spectra`` / ``T_spectra`` (optional, L x n points) the spectral values."""
-        nl = len(abs_coef)
         arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
-        hb = lambda b: b.h if b is not None else None
         self.check(self.lib.lbl_column_jacobian_dev(
-            self.h, nl, arr(_P, [b.h for b in abs_coef]), arr(C.c_double, [float(t) for t in layer_T]),
-            arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), hb(I_surface),
-            float(surface_T), len(mu), arr(C.c_double, [float(m) for m in mu]),
-            arr(C.c_double, [float(w) for w in weight]), len(band_first), arr(C.c_int64, [int(f) for f in band_first]),
-            arr(C.c_int64, [int(c) for c in band_count]), len(term_abs_coef), arr(_P, [b.h for b in term_abs_coef]),
-            arr(C.c_int32, [int(l) for l in term_layer]), hb(jac), hb(ln_tau_spectra), hb(T_spectra)))
+            *self._column_args(abs_coef, layer_T, depth, range_min, range_max, n, I_surface, surface_T, (), mu, weight,
+                               band_first, band_count),
+            len(term_abs_coef), arr(_P, [b.h for b in term_abs_coef]), arr(C.c_int32, [int(l) for l in term_layer]),
+            _hb(jac), _hb(ln_tau_spectra), _hb(T_spectra)))
 
     def gather_compact_dev(self, gathered, slot, bounds, out):
         """padded all-gather result (slot r = rank r's shard) -> grid order (lbl_gather_compact_dev)."""

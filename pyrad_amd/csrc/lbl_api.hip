@@ -2564,7 +2564,7 @@ int comm_fail(lbl_ctx* ctx, int code, const char* msg) { return fail(ctx, code, 
 int ctx_device(lbl_ctx* ctx) { return ctx->device; }
 bool ctx_capturing(lbl_ctx* ctx) { return ctx->capturing; }
 lbl_ctx* buffer_ctx(lbl_buffer* buf) { return buf->ctx; }
-// ... and for lbl_flux.hip and lbl_jacobian.hip
+// ... and for lbl_column_transport.hip
 hipStream_t ctx_stream(lbl_ctx* ctx) { return ctx->stream; }
 bool ctx_sweep_ieee(lbl_ctx* ctx) { return ctx->sweep_ieee != 0; }
 int ctx_device_args(lbl_ctx* ctx, const void* host, size_t bytes, void** dptr) { return device_args(ctx, host, bytes, dptr); }

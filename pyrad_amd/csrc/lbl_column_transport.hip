@@ -1,0 +1,202 @@
+// Column transport (include/pyrad_hip.h, "level fluxes" and "Jacobians"): argument checking and the launch sequences of
+// lbl_column_flux_dev and lbl_column_jacobian_dev.  The kernels are K5c and K5d of lbl_kernels.hip; the context's internals
+// are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
+// this file's launchers.
+#include "../../include/pyrad_hip.h"
+#include "lbl_device.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <new>
+#include <stdexcept>
+#include <vector>
+
+namespace lbl {
+int comm_fail(lbl_ctx* ctx, int code, const char* msg);
+int ctx_device(lbl_ctx* ctx);
+hipStream_t ctx_stream(lbl_ctx* ctx);
+bool ctx_sweep_ieee(lbl_ctx* ctx);
+int ctx_device_args(lbl_ctx* ctx, const void* host, size_t bytes, void** dptr);
+int ctx_reduction_scratch(lbl_ctx* ctx, size_t bytes, void** dptr);
+int ctx_check_buffer(lbl_ctx* ctx, lbl_buffer* b, int64_t n, const char* what, bool required);
+double* buffer_data(lbl_buffer* buf);
+void planck_budget_constants(double T, double* pa, double* pbkT);
+double grid_step(double lo, double hi, int64_t n);
+}
+
+using namespace lbl;
+
+static int column_fail(lbl_ctx* ctx, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return comm_fail(ctx, code, buf);
+}
+
+// no C++ exception crosses the C boundary (see lbl_api.hip)
+#define LBL_GUARD_END(ctx_expr)                                                                                   \
+    catch (const std::bad_alloc&) { return comm_fail((ctx_expr), LBL_ERR_OOM, "host allocation failed"); }        \
+    catch (const std::exception& e) { return comm_fail((ctx_expr), LBL_ERR_STATE, e.what()); }                    \
+    catch (...) { return comm_fail((ctx_expr), LBL_ERR_STATE, "unknown C++ exception"); }
+
+#define COLUMN_HIP_TRY(ctx, expr)                                                                                 \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess)                                                                                     \
+            return column_fail(ctx, e_ == hipErrorOutOfMemory ? LBL_ERR_OOM : LBL_ERR_HIP, "%s: %s", #expr,       \
+                               hipGetErrorString(e_));                                                            \
+    } while (0)
+
+// The arguments both entry points share (ctx non-NULL): checked in this order, then the ColumnRT part of the argument block
+// filled.  `what` names the feature in the refusal under "sweep_ieee_divisions" 1.
+static int check_column(lbl_ctx* ctx, const char* what, ColumnRT* a, int n_layers, lbl_buffer* const* abs_coef,
+                        const double* T, const double* depth, double range_min, double range_max, int64_t n,
+                        lbl_buffer* I_surface, double surface_T, int n_angles, const double* mu, const double* weight,
+                        int n_bands, const int64_t* band_first, const int64_t* band_count) {
+    if (n_layers < 0 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
+    if (n < 0) return column_fail(ctx, LBL_ERR_BAD_ARG, "negative n");
+    if (n_layers > 0 && (!abs_coef || !T || !depth)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if (ctx_sweep_ieee(ctx))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", what);
+    if (n_angles < 1 || n_angles > kMaxFluxAngles) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d angles", kMaxFluxAngles);
+    if (!mu || !weight) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL angle set");
+    if (n_bands < 1 || n_bands > kMaxFluxBands) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d bands", kMaxFluxBands);
+    if (!band_first || !band_count) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL band list");
+    int rc;
+    if ((rc = ctx_check_buffer(ctx, I_surface, n, "I_surface", false))) return rc;
+    if (!I_surface && !(surface_T > 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "need I_surface or surface_T > 0");
+    for (int b = 0; b < n_bands; ++b)
+        if (band_first[b] < 0 || band_count[b] < 1 || band_count[b] > n - band_first[b])
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "band %d: empty or outside [0, n)", b);
+    double pa = 0.0;
+    for (int l = 0; l < n_layers; ++l) {
+        if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
+        if (!(T[l] > 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
+        if (!(depth[l] >= 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: depth must be >= 0", l);
+        a->abs_coef[l] = buffer_data(abs_coef[l]);
+        a->depth[l] = depth[l];
+        planck_budget_constants(T[l], &pa, &a->pbkT[l]);
+        a->pbkT_min = l == 0 ? a->pbkT[l] : std::min(a->pbkT_min, a->pbkT[l]);
+        a->pbkT_max = l == 0 ? a->pbkT[l] : std::max(a->pbkT_max, a->pbkT[l]);
+    }
+    for (int k = 0; k < n_angles; ++k) {
+        if (!(mu[k] > 0 && mu[k] <= 1)) return column_fail(ctx, LBL_ERR_BAD_ARG, "angle %d: mu must lie in (0, 1]", k);
+        if (!std::isfinite(weight[k])) return column_fail(ctx, LBL_ERR_BAD_ARG, "angle %d: weight must be finite", k);
+        a->rmu[k] = 1.0 / mu[k];
+        a->w[k] = weight[k];
+    }
+    planck_budget_constants(surface_T > 0 ? surface_T : 1.0, &pa, &a->pbk_surface);
+    a->pa = pa;
+    a->start = range_min; a->stop = range_max; a->step = grid_step(range_min, range_max, n);
+    a->I_surface = I_surface ? buffer_data(I_surface) : nullptr;
+    a->n = n;
+    a->n_layers = n_layers; a->n_angles = n_angles;
+    return LBL_OK;
+}
+
+// The launch sequence after every check: the argument block and the partial scratch for the widest band (`np` points per
+// thread, nv values per partial), the optional spectra spec[0..1] (spec_bytes each) zeroed, then the bands one after another
+// over one partial block: stream order keeps a band's final reduction ahead of the next band.  launch_band(d_args, partial,
+// b, s) enqueues band b.
+template <class Args, class LaunchBand>
+static int run_column(lbl_ctx* ctx, const Args* a, int np, int nv, int n_bands, const int64_t* band_count, double* const (&spec)[2],
+                      size_t spec_bytes, LaunchBand launch_band) {
+    int64_t max_count = 0;
+    for (int b = 0; b < n_bands; ++b) max_count = std::max(max_count, band_count[b]);
+    void* partial = nullptr;
+    int rc;
+    if ((rc = ctx_reduction_scratch(ctx, (size_t)column_transport_partials(max_count, np) * nv * sizeof(double), &partial)))
+        return rc;
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, a, sizeof(Args), &d_args))) return rc;
+    const hipStream_t s = ctx_stream(ctx);
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    // (points outside every band keep 0 in the spectra)
+    for (double* p : spec)
+        if (p && spec_bytes) COLUMN_HIP_TRY(ctx, hipMemsetAsync(p, 0, spec_bytes, s));
+    for (int b = 0; b < n_bands; ++b) launch_band((const Args*)d_args, (double*)partial, b, s);
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+}
+
+extern "C" int lbl_column_flux_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                   const double* depth, double range_min, double range_max, int64_t n,
+                                   lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
+                                   const double* mu, const double* weight, int n_bands, const int64_t* band_first,
+                                   const int64_t* band_count, lbl_buffer* level_flux, lbl_buffer* up_top,
+                                   lbl_buffer* down_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(FluxArgs), 0);
+    FluxArgs* a = (FluxArgs*)blk.data();
+    int rc;
+    if ((rc = check_column(ctx, "level fluxes", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
+                           surface_T, n_angles, mu, weight, n_bands, band_first, band_count)))
+        return rc;
+    const int nv = 2 * (n_layers + 1);
+    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    a->I_top = I_top ? buffer_data(I_top) : nullptr;
+    a->up_top = up_top ? buffer_data(up_top) : nullptr;
+    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
+    return run_column(ctx, a, 4, nv, n_bands, band_count, {a->up_top, a->down_surface}, (size_t)n * sizeof(double),
+                      [&](const FluxArgs* d, double* partial, int b, hipStream_t s) {
+        launch_column_flux(d, n_layers, n_angles, band_first[b], band_count[b], partial, buffer_data(level_flux) + (size_t)b * nv, s);
+    });
+} LBL_GUARD_END(ctx)
+
+extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                       const double* depth, double range_min, double range_max, int64_t n,
+                                       lbl_buffer* I_surface, double surface_T, int n_angles, const double* mu,
+                                       const double* weight, int n_bands, const int64_t* band_first,
+                                       const int64_t* band_count, int n_terms, lbl_buffer* const* term_abs_coef,
+                                       const int32_t* term_layer, lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra,
+                                       lbl_buffer* jac_T_spectra) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(JacArgs), 0);
+    JacArgs* a = (JacArgs*)blk.data();
+    int rc;
+    if ((rc = check_column(ctx, "Jacobians", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface, surface_T,
+                           n_angles, mu, weight, n_bands, band_first, band_count)))
+        return rc;
+    if (n_terms < 0 || n_terms > kMaxJacobianTerms)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d molecule terms", kMaxJacobianTerms);
+    if (n_terms > 0 && (!term_abs_coef || !term_layer)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
+    const int nv = 2 + 2 * n_layers + n_terms;
+    if ((rc = ctx_check_buffer(ctx, jac, (int64_t)n_bands * nv, "jac", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, jac_ln_tau_spectra, (int64_t)n_layers * n, "jac_ln_tau_spectra", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, jac_T_spectra, (int64_t)n_layers * n, "jac_T_spectra", false))) return rc;
+    // the molecule terms, sorted by layer (stable): layer l reads [layer_term[l], layer_term[l + 1])
+    for (int t = 0; t < n_terms; ++t) {
+        if (term_layer[t] < 0 || term_layer[t] >= n_layers)
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "term %d: layer %d outside [0, %d)", t, (int)term_layer[t], n_layers);
+        if ((rc = ctx_check_buffer(ctx, term_abs_coef[t], n, "term_abs_coef", true))) return rc;
+        ++a->layer_term[term_layer[t] + 1];
+    }
+    for (int l = 0; l < n_layers; ++l) a->layer_term[l + 1] += a->layer_term[l];
+    {
+        std::vector<int32_t> fill(a->layer_term, a->layer_term + std::max(n_layers, 1));
+        for (int t = 0; t < n_terms; ++t) {
+            const int pos = fill[term_layer[t]]++;
+            a->term_k[pos] = buffer_data(term_abs_coef[t]);
+            a->term_slot[pos] = t;
+        }
+    }
+    for (int l = 0; l < n_layers; ++l) a->rT[l] = 1.0 / T[l];
+    for (int k = 0; k < n_angles; ++k) a->wrmu[k] = weight[k] * a->rmu[k];
+    a->r_surface_T = surface_T > 0 ? 1.0 / surface_T : 0.0;
+    a->ln_tau_spec = jac_ln_tau_spectra ? buffer_data(jac_ln_tau_spectra) : nullptr;
+    a->T_spec = jac_T_spectra ? buffer_data(jac_T_spectra) : nullptr;
+    a->n_terms = n_terms;
+    return run_column(ctx, a, 2, nv, n_bands, band_count, {a->ln_tau_spec, a->T_spec}, (size_t)n_layers * (size_t)n * sizeof(double),
+                      [&](const JacArgs* d, double* partial, int b, hipStream_t s) {
+        launch_column_jacobian(d, n_layers, n_angles, n_terms, band_first[b], band_count[b], partial, buffer_data(jac) + (size_t)b * nv, s);
+    });
+} LBL_GUARD_END(ctx)

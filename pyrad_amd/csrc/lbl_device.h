@@ -222,13 +222,14 @@ struct ColumnStepArgs {
     long long n;
     long long first, count;
 };
-// Level fluxes of a column (lbl_column_flux_dev, lbl_flux.hip): the fold's arithmetic over the layers' absorption coefficients
-// for several angles, upward from the surface and downward from the top, each level's angle-weighted radiance summed over a
-// band of grid points.  One argument block per call; every band is its own launch over the same partial-sum scratch.
+// Column transport (lbl_column_transport.hip: lbl_column_flux_dev, lbl_column_jacobian_dev): the fold's arithmetic over the
+// layers' absorption coefficients for several angles.  One argument block per call; every band is its own launch over the
+// same partial-sum scratch, then column_flux_final_kernel adds the partials in a fixed order.
 constexpr int kMaxFluxAngles = 8;
 constexpr int kMaxFluxBands = 64;
-constexpr int kFluxMaxBlocks = 1024;      // workgroups of one band launch (grid-stride beyond): partials stay (1024 + 1) x 2 x 129 doubles
-struct FluxArgs {
+constexpr int kFluxMaxBlocks = 1024;      // workgroups of one band launch (grid-stride beyond): the partials stay bounded
+// what both kernels read: the column, its grid, the angle set and the surface source
+struct ColumnRT {
     const double* abs_coef[kMaxLayers];
     double depth[kMaxLayers];
     double pbkT[kMaxLayers];            // 100 h c / k / T_l (the budget Planck exponent per wavenumber)
@@ -238,46 +239,37 @@ struct FluxArgs {
     double w[kMaxFluxAngles];           // W_k
     double start, stop, step, pa;
     const double* I_surface;            // upward radiance entering at the surface, or nullptr: B(nu, surface_T)
-    const double* I_top;                // downward radiance entering at the top, or nullptr: 0
-    double* up_top;                     // optional: spectral flux F_up at the top
-    double* down_surface;               // optional: spectral flux F_down at the surface
     long long n;
     int32_t n_layers, n_angles;
 };
-// one band [first, first + count): partial sums into `partial` (at most column_flux_partials(count) blocks of 2 (n_layers + 1)),
-// then the fixed-order reduction into level_flux[0 .. 2 (n_layers + 1)): [up, down][level]
-int column_flux_partials(long long count);
-void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long long first, long long count, double* partial,
-                        double* level_flux, hipStream_t s);
-
-// Jacobians of the outgoing flux (lbl_column_jacobian_dev, lbl_jacobian.hip): K5c's upward fold, then a downward pass that
-// keeps per angle the transmittance to the top A and D = E - I_top (E: emission of the layers above that reaches the top),
-// so that A_l t_l (B_l - I_l) = A_l B_l + D_l needs no stored radiance.  Values per band: [F_top, dF/dT_s, L x d ln tau,
-// L x dT (Planck part), n_terms x d ln n].
+// Level fluxes (K5c): the fold upward from the surface and downward from the top, each level's angle-weighted radiance summed
+// over a band of grid points.  Values per band: [up, down][level 0 .. L].
+struct FluxArgs : ColumnRT {
+    const double* I_top;                // downward radiance entering at the top, or nullptr: 0
+    double* up_top;                     // optional: spectral flux F_up at the top
+    double* down_surface;               // optional: spectral flux F_down at the surface
+};
+// Jacobians of the outgoing flux (K5d): K5c's upward fold, then a downward pass that keeps per angle the transmittance to the
+// top A and D = E - I_top (E: emission of the layers above that reaches the top), so that A_l t_l (B_l - I_l) = A_l B_l + D_l
+// needs no stored radiance.  Values per band: [F_top, dF/dT_s, L x d ln tau, L x dT (Planck part), n_terms x d ln n].
 constexpr int kMaxJacobianTerms = kMaxColumnIso;
-struct JacArgs {
-    const double* abs_coef[kMaxLayers];
-    double depth[kMaxLayers];
-    double pbkT[kMaxLayers];            // 100 h c / k / T_l
+struct JacArgs : ColumnRT {
     double rT[kMaxLayers];              // 1 / T_l (dB/dT = B b e^b / ((e^b - 1) T), b = nu pbkT)
-    double pbkT_min, pbkT_max;
-    double pbk_surface, r_surface_T;    // used when I_surface == nullptr
-    double rmu[kMaxFluxAngles];         // 1 / mu_k
-    double w[kMaxFluxAngles];           // W_k
+    double r_surface_T;                 // 1 / surface_T (used when I_surface == nullptr)
     double wrmu[kMaxFluxAngles];        // W_k / mu_k
-    double start, stop, step, pa;
-    const double* I_surface;
     double* ln_tau_spec;                // optional: L x n spectral dF/d ln tau_l
     double* T_spec;                     // optional: L x n spectral dF/dT_l
     const double* term_k[kMaxJacobianTerms];   // the molecule terms sorted by layer (stable)
     int32_t term_slot[kMaxJacobianTerms];      // ... and each one's index in the caller's list
     int32_t layer_term[kMaxLayers + 1];        // terms of layer l: [layer_term[l], layer_term[l + 1])
-    long long n;
-    int32_t n_layers, n_angles, n_terms, pad;
+    int32_t n_terms, pad;
 };
-// one band [first, first + count): partials (at most column_jacobian_partials(count) blocks of 2 + 2 L + n_terms values),
-// then the fixed-order reduction into jac[0 .. 2 + 2 L + n_terms)
-int column_jacobian_partials(long long count);
+// partial blocks one band of `count` points needs at `np` points per thread (the head and tail workgroup included)
+int column_transport_partials(long long count, int np);
+// one band [first, first + count): partials, then the fixed-order reduction into level_flux[0 .. 2 (n_layers + 1)) /
+// jac[0 .. 2 + 2 L + n_terms)
+void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long long first, long long count, double* partial,
+                        double* level_flux, hipStream_t s);
 void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first, long long count,
                             double* partial, double* jac, hipStream_t s);
 

@@ -3111,6 +3111,75 @@ __device__ __forceinline__ double expm1_tiny(double x) {
     return x * fma(x, fma(x, fma(x, 1.0 / 24.0, 1.0 / 6.0), 0.5), 1.0);
 }
 
+// ---- the fold's budget arithmetic, shared by K5c and K5d --------------------------------------------------------------
+// column_step_kernel (K5b, below) writes the same operations out itself: moved onto these helpers, its gfx950 code is no
+// longer instruction for instruction what it is, and it is the fold that transmission() and the benchmark time.
+// Default arithmetic with several points per thread: ONE exp per thread and layer for the Planck function (round 6).
+// exp(nu_p c) = exp(nu_0 c) exp((nu_p - nu_0) c): the difference of two neighbouring grid wavenumbers is exact in fp64 and
+// (nu_p - nu_0) c <= 1e-3 for every layer (checked here with the column's largest c = 100 h c / k / T_min), so the second
+// factor is a degree-4 polynomial (7 instructions instead of the 17 of exp; 1-2 ulp).  Also only where no active lane of the
+// wave can meet a special case - exponent above 700, exp(b) - 1 not positive (nu = 0), NaN wavenumbers - which keep the
+// general expression with its selects and its IEEE division.  The result is wave-uniform.  (A: any argument block with the
+// column's pbkT_min and pbkT_max, read only as far as the test gets)
+template <int NP, class Args>
+__device__ __forceinline__ bool fold_fast_path(const Args& A, const double (&nu)[NP], bool active) {
+#pragma clang fp contract(off)
+    const double dnu_last = nu[NP - 1] - nu[0];
+    const bool plain = NP > 1 && nu[0] * A.pbkT_min >= 1e-6 && nu[NP - 1] * A.pbkT_max <= 690.0
+                       && dnu_last * A.pbkT_max <= 1e-3 && dnu_last >= 0.0;
+    return NP > 1 && __builtin_amdgcn_ballot_w64(active && !plain) == 0ull;
+}
+
+// B(nu, T) = pa_n / (exp(nu pbkT) - 1) with pa_n = pa nu^3, pbkT = 100 h c / k / T.  FAST: from the thread's single exp
+// E0 = exp_clamped(nu0 pbkT) of its first point (`first`: nu is that point); else the general expression, planck_budget's
+// value bit for bit.  DT: also dB/dT = B b e^b / ((e^b - 1) T) into *dB from the same exp (rT = 1 / T).
+// (a NaN exponent must stay a NaN, as in np.exp(nan): fmin / fmax drop it, so it is put back explicitly)
+template <bool FAST, bool DT = false>
+__device__ __forceinline__ double fold_planck(bool first, double nu, double nu0, double pa_n, double pbkT, double E0,
+                                              double rT = 0.0, double* dB = nullptr) {
+#pragma clang fp contract(off)
+    if (FAST) {
+        const double E = first ? E0 : fma(E0, expm1_tiny((nu - nu0) * pbkT), E0);
+        const double rc = rcp_newton(E - 1.0);
+        const double B = pa_n * rc;
+        if (DT) *dB = B * ((E * rc) * (nu * pbkT)) * rT;
+        return B;
+    }
+    const double b = nu * pbkT;
+    const double e = exp_clamped(fmin(b, 700.0)) - 1.0;
+    if (!DT) {
+        const double B = (b > 700.0) ? 0.0 : (e > 0.0 ? pa_n * rcp_newton(fmax(e, 1e-300)) : pa_n / e);
+        return b != b ? b : B;
+    }
+    const double rc = rcp_newton(fmax(e, 1e-300));
+    const double B = (b > 700.0) ? 0.0 : (e > 0.0 ? pa_n * rc : pa_n / e);
+    *dB = b != b ? b : ((b > 700.0) ? 0.0 : (e > 0.0 ? B * (((e + 1.0) * rc) * b) * rT : B * (b * (e + 1.0) / e) * rT));
+    return b != b ? b : B;
+}
+
+// I <- t I + (1 - t) B.  FAST: the last product and sum as one fma (three instructions instead of four).  (B + t (I - B)
+// would be two, but loses I against B: with I < 1e-16 B behind a layer of optical depth ~1e-16 the result
+// t I + (1 - t) B ~ I + 1e-16 B would come out as 1e-16 B alone.)
+template <bool FAST>
+__device__ __forceinline__ double fold_update(double tr, double I, double B) {
+#pragma clang fp contract(off)
+    if (FAST) return fma(tr, I, (1.0 - tr) * B);
+    const double transmitted = tr * I;
+    const double emitted = (1.0 - tr) * B;
+    return transmitted + emitted;
+}
+
+// NP values of one array from grid point j on (16- / 32-byte loads for NP = 2 / 4; the caller's j is a multiple of NP)
+template <int NP> using f64v = double __attribute__((ext_vector_type(NP)));
+template <int NP>
+__device__ __forceinline__ f64v<NP> load_points(const double* p, long long j) {
+    typedef const f64v<NP> __attribute__((address_space(1)))* GlobalVec;
+    f64v<NP> v;
+    if (NP == 1) v[0] = load_global_f64(p, j);
+    else v = *(GlobalVec)(unsigned long long)(p + j);
+    return v;
+}
+
 // KFOLD (round 6): the fold over absorption coefficients (lbl_column_fold_dev, the column handle) - every term IS a layer, its
 // factor 1: the per-molecule sums are skipped (0 + v = v, v * 1 = v: the same bits) and the flags are never read.
 template <int NP, bool BUDGET = false, bool KFOLD = false>
@@ -3292,26 +3361,47 @@ __global__ __launch_bounds__(256) void band_final_kernel(const double* __restric
 }
 
 // ----------------------------------------------------------------------------------------
-// K5c: level fluxes of a column (lbl_column_flux_dev; the semantics are in include/pyrad_hip.h)
+// K5c / K5d: column transport (lbl_column_flux_dev, lbl_column_jacobian_dev; the semantics are in include/pyrad_hip.h)
 // ----------------------------------------------------------------------------------------
-// The fold of column_step_kernel<4, true, true> over the layers' absorption coefficients, for NA angles at once and in both
-// directions: every thread owns NP grid points (4 on the aligned quads of a band, 1 on its head and tail points, the way
-// launch_column_step_b treats its tail), walks the layers bottom to top for the upward radiances I_up[k] and then top to
-// bottom for the downward ones, re-reading k_l and recomputing B_l on the way down (the registers cannot hold 128 layers'
-// worth).  Per point and layer: one Planck term shared by all angles (one exp per thread and layer on the wave-uniform fast
-// path, the general expression otherwise - the fold's guard and arithmetic), and one exp_neg_budget(tau_l / mu_k) per angle
-// and direction.  With the angle set {(1, pi)} the upward radiance at the top is the fold's I_out bit for bit wherever both
-// take the same Planck path (every wave fast, or the same general points).
-// Level sums: after every layer step each thread adds its points' angle-weighted radiances sum_k W_k I_k (nan_to_num per
-// point); the wave reduces them (wave_sum), lane 0 adds the result to its wave's slot in LDS; at the end the four waves'
-// slots are added in a fixed order into ONE partial per workgroup and level, and column_flux_final_kernel adds the partials in
-// a fixed order.  No float atomics: the same inputs and launch give the same bits.
+// Both walk the fold of column_step_kernel<4, true, true> over the layers' absorption coefficients for NA angles at once:
+// every thread owns NP grid points (NP on the aligned groups of a band, 1 on its head and tail points, the way
+// launch_column_step_b treats its tail).  Per point and layer: one Planck term shared by all angles (fold_planck: one exp per
+// thread and layer on the wave-uniform fast path, the general expression otherwise - the fold's guard and arithmetic), and
+// one exp_neg_budget(tau_l / mu_k) per angle and direction.
+// Sums: per thread (nan_to_num per point), wave_sum, lane 0 adds the result to its wave's slot in LDS; at the end the four
+// waves' slots are added in a fixed order into ONE partial per workgroup and value, and column_flux_final_kernel adds the
+// partials in a fixed order.  No float atomics: the same inputs and launch give the same bits.
+
+// grid point j + p of the thread and the Planck numerator pa nu^3 there
+template <int NP>
+__device__ __forceinline__ void column_points(const ColumnRT& A, long long j, double (&nu)[NP], double (&pa_n)[NP]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        nu[p] = linspace_at(j + p, A.n, A.start, A.stop, A.step);
+        pa_n[p] = A.pa * (nu[p] * nu[p] * nu[p]);
+    }
+}
+
+// sum_k W_k v(k), angle 0 first
+template <int NA, class V>
+__device__ __forceinline__ double angle_sum(const ColumnRT& A, V v) {
+#pragma clang fp contract(off)
+    double f = A.w[0] * v(0);
+#pragma unroll
+    for (int k = 1; k < NA; ++k) f = fma(A.w[k], v(k), f);
+    return f;
+}
+
+// K5c: walks the layers bottom to top for the upward radiances I_up[k] and then top to bottom for the downward ones,
+// re-reading k_l and recomputing B_l on the way down (the registers cannot hold 128 layers' worth).  With the angle set
+// {(1, pi)} the upward radiance at the top is the fold's I_out bit for bit wherever both take the same Planck path (every
+// wave fast, or the same general points).  Level sums: after every layer step each thread adds its points' sum_k W_k I_k.
 template <int NP, int NA>
 __global__ __launch_bounds__(256) void column_flux_kernel(const FluxArgs* __restrict__ Ap, long long lo0, long long n0,
                                                           long long lo1, long long n1, double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    typedef double vec __attribute__((ext_vector_type(NP)));
-    typedef const vec __attribute__((address_space(1)))* GlobalVec;
+    typedef f64v<NP> vec;
     constexpr int kSlot = 2 * (kMaxLayers + 1);
     __shared__ double acc[4 * kSlot];            // [wave][up levels 0..L, down levels 0..L]
     const FluxArgs& A = *Ap;
@@ -3321,12 +3411,6 @@ __global__ __launch_bounds__(256) void column_flux_kernel(const FluxArgs* __rest
     __syncthreads();
     double* my = acc + (threadIdx.x >> 6) * kSlot;
     const bool lane0 = (threadIdx.x & 63) == 0;
-    auto load = [&](const double* p, long long j) {
-        vec v;
-        if (NP == 1) v[0] = load_global_f64(p, j);
-        else v = *(GlobalVec)(unsigned long long)(p + j);
-        return v;
-    };
     const long long total = n0 + n1;
     const long long stride = (long long)gridDim.x * blockDim.x * NP;
     // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
@@ -3335,24 +3419,14 @@ __global__ __launch_bounds__(256) void column_flux_kernel(const FluxArgs* __rest
         const bool active = q < total;
         const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
         double nu[NP], pa_n[NP], I[NA][NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            nu[p] = linspace_at(j + p, A.n, A.start, A.stop, A.step);
-            pa_n[p] = A.pa * (nu[p] * nu[p] * nu[p]);
-        }
-        // the fold's test for one Planck exp per thread and layer (column_step_kernel), over the active lanes of the wave
-        const double dnu_last = nu[NP - 1] - nu[0];
-        const bool plain = NP > 1 && nu[0] * A.pbkT_min >= 1e-6 && nu[NP - 1] * A.pbkT_max <= 690.0
-                           && dnu_last * A.pbkT_max <= 1e-3 && dnu_last >= 0.0;
-        const bool fast = NP > 1 && __builtin_amdgcn_ballot_w64(active && !plain) == 0ull;
+        column_points<NP>(A, j, nu, pa_n);
+        const bool fast = fold_fast_path<NP>(A, nu, active);
         // sum_k W_k I_k per point, nan_to_num, summed over the thread's points, the wave, and into the wave's slot
         auto level = [&](int slot, double* spec) {
             double s = 0.0;
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                double f = A.w[0] * I[0][p];
-#pragma unroll
-                for (int k = 1; k < NA; ++k) f = fma(A.w[k], I[k][p], f);
+                const double f = angle_sum<NA>(A, [&](int k) { return I[k][p]; });
                 if (spec && active) spec[j + p] = f;
                 s += active ? nan_to_num(f) : 0.0;
             }
@@ -3367,27 +3441,9 @@ __global__ __launch_bounds__(256) void column_flux_kernel(const FluxArgs* __rest
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const double tau = v[p] * depth;
-                double B;
-                if (FAST) {
-                    const double E = p == 0 ? E0 : fma(E0, expm1_tiny((nu[p] - nu[0]) * pbkT), E0);
-                    B = pa_n[p] * rcp_newton(E - 1.0);
-                } else {
-                    const double b = nu[p] * pbkT;
-                    const double e = exp_clamped(fmin(b, 700.0)) - 1.0;
-                    B = (b > 700.0) ? 0.0 : (e > 0.0 ? pa_n[p] * rcp_newton(fmax(e, 1e-300)) : pa_n[p] / e);
-                    B = b != b ? b : B;
-                }
+                const double B = fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0);
 #pragma unroll
-                for (int k = 0; k < NA; ++k) {
-                    const double tr = exp_neg_budget(tau * A.rmu[k]);
-                    if (FAST) {
-                        I[k][p] = fma(tr, I[k][p], (1.0 - tr) * B);
-                    } else {
-                        const double transmitted = tr * I[k][p];
-                        const double emitted = (1.0 - tr) * B;
-                        I[k][p] = transmitted + emitted;
-                    }
-                }
+                for (int k = 0; k < NA; ++k) I[k][p] = fold_update<FAST>(exp_neg_budget(tau * A.rmu[k]), I[k][p], B);
             }
         };
         auto walk = [&](auto fast_tag) {
@@ -3399,9 +3455,9 @@ __global__ __launch_bounds__(256) void column_flux_kernel(const FluxArgs* __rest
                 for (int k = 0; k < NA; ++k) I[k][p] = Is;
             }
             level(0, L == 0 ? A.up_top : nullptr);
-            vec cur = L > 0 ? load(A.abs_coef[0], j) : (vec)(0.0);
+            vec cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
             for (int l = 0; l < L; ++l) {
-                const vec nxt = l + 1 < L ? load(A.abs_coef[l + 1], j) : cur;
+                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
                 layer(fast_tag, l, cur);
                 level(l + 1, l + 1 == L ? A.up_top : nullptr);
                 cur = nxt;
@@ -3414,9 +3470,9 @@ __global__ __launch_bounds__(256) void column_flux_kernel(const FluxArgs* __rest
                 for (int k = 0; k < NA; ++k) I[k][p] = It;
             }
             level(L + 1 + L, L == 0 ? A.down_surface : nullptr);
-            cur = L > 0 ? load(A.abs_coef[L - 1], j) : (vec)(0.0);
+            cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
             for (int l = L - 1; l >= 0; --l) {
-                const vec nxt = l > 0 ? load(A.abs_coef[l - 1], j) : cur;
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
                 layer(fast_tag, l, cur);
                 level(L + 1 + l, l == 0 ? A.down_surface : nullptr);
                 cur = nxt;
@@ -3447,37 +3503,18 @@ __global__ __launch_bounds__(256) void column_flux_final_kernel(const double* __
     if (threadIdx.x == 0) level_flux[t] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// ----------------------------------------------------------------------------------------
-// K5d: Jacobians of the outgoing flux (lbl_column_jacobian_dev; the semantics are in include/pyrad_hip.h)
-// ----------------------------------------------------------------------------------------
-// planck_budget's value, bit for bit, and with it dB/dT = B b e^b / ((e^b - 1) T) from the same exp (rT = 1 / T)
-__device__ __forceinline__ double planck_budget_dT(double n, double pa, double pbkT, double rT, double* dB) {
-    const double b = n * pbkT;
-    const double e = exp_clamped(fmin(b, 700.0)) - 1.0;
-    const double rc = rcp_newton(fmax(e, 1e-300));
-    const double v = (pa * (n * n * n)) * rc;
-    const bool general = b > 700.0 || !(e > 0.0);
-    const double r = general ? ((b > 700.0) ? 0.0 : (pa * (n * n * n)) / e) : v;
-    const double d = general ? ((b > 700.0) ? 0.0 : r * (b * (e + 1.0) / e) * rT) : r * (((e + 1.0) * rc) * b) * rT;
-    *dB = b != b ? b : d;
-    return b != b ? b : r;
-}
-
-// K5c's upward fold (same Planck paths, guard and update), keeping per angle only the radiance I and its running maximum
-// Imax over the levels; then a downward pass that re-reads k_l and recomputes B_l as K5c's does, and keeps per angle the
-// transmittance A to the top and D = E - I_top, E the emission of the layers above that reaches the top.  Then
+// K5d: K5c's upward fold, keeping per angle only the radiance I and its running maximum Imax over the levels; then a
+// downward pass that re-reads k_l and recomputes B_l as K5c's does, and keeps per angle the transmittance A to the top and
+// D = E - I_top, E the emission of the layers above that reaches the top.  Then
 //     A_l t_l (B_l - I_l) = A_l B_l + E_l - I_top = A_l B_l + D_l,
 // clamped to [-A_l t_l Imax, A_l t_l B_l] (both bounds exact for non-negative sources): where the path above is opaque the
 // true value underflows to ~0 while E - I_top is rounding noise that tau / mu would amplify.  Per point and layer:
 // G = sum_k (W_k / mu_k) g_k; d ln tau_l = tau_l G, molecule term m of the layer = k_(m,l) depth_l G, dT_l = sum_k W_k A (1 - t) dB_l/dT.
-// Sums: per thread (nan_to_num per point), wave_sum, lane 0 into its wave's LDS slot; the four waves in a fixed order into one
-// partial per workgroup; column_flux_final_kernel adds the partials in a fixed order.  No float atomics.
 template <int NP, int NA>
 __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __restrict__ Ap, long long lo0, long long n0,
                                                               long long lo1, long long n1, double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    typedef double vec __attribute__((ext_vector_type(NP)));
-    typedef const vec __attribute__((address_space(1)))* GlobalVec;
+    typedef f64v<NP> vec;
     constexpr int kSlot = 2 + 2 * kMaxLayers + kMaxJacobianTerms;
     __shared__ double acc[4 * kSlot];            // [wave][F_top, dT_s, L x ln tau, L x T, terms]
     const JacArgs& A = *Ap;
@@ -3487,12 +3524,6 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
     __syncthreads();
     double* my = acc + (threadIdx.x >> 6) * kSlot;
     const bool lane0 = (threadIdx.x & 63) == 0;
-    auto load = [&](const double* p, long long j) {
-        vec v;
-        if (NP == 1) v[0] = load_global_f64(p, j);
-        else v = *(GlobalVec)(unsigned long long)(p + j);
-        return v;
-    };
     auto add = [&](int slot, double s) {
         s = wave_sum(s);
         if (lane0) my[slot] += s;
@@ -3505,35 +3536,8 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
         const bool active = q < total;
         const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
         double nu[NP], pa_n[NP], dBs[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            nu[p] = linspace_at(j + p, A.n, A.start, A.stop, A.step);
-            pa_n[p] = A.pa * (nu[p] * nu[p] * nu[p]);
-        }
-        const double dnu_last = nu[NP - 1] - nu[0];
-        const bool plain = NP > 1 && nu[0] * A.pbkT_min >= 1e-6 && nu[NP - 1] * A.pbkT_max <= 690.0
-                           && dnu_last * A.pbkT_max <= 1e-3 && dnu_last >= 0.0;
-        const bool fast = NP > 1 && __builtin_amdgcn_ballot_w64(active && !plain) == 0ull;
-        // B_l and dB_l/dT at point p (K5c's two paths; the fast one from the thread's single exp E0)
-        auto planck = [&](auto fast_tag, int p, double pbkT, double rT, double E0, double& dB) {
-            constexpr bool FAST = decltype(fast_tag)::value;
-            double B;
-            if (FAST) {
-                const double E = p == 0 ? E0 : fma(E0, expm1_tiny((nu[p] - nu[0]) * pbkT), E0);
-                const double rc = rcp_newton(E - 1.0);
-                B = pa_n[p] * rc;
-                dB = B * ((E * rc) * (nu[p] * pbkT)) * rT;
-            } else {
-                const double b = nu[p] * pbkT;
-                const double e = exp_clamped(fmin(b, 700.0)) - 1.0;
-                const double rc = rcp_newton(fmax(e, 1e-300));
-                B = (b > 700.0) ? 0.0 : (e > 0.0 ? pa_n[p] * rc : pa_n[p] / e);
-                dB = (b > 700.0) ? 0.0 : (e > 0.0 ? B * (((e + 1.0) * rc) * b) * rT : B * (b * (e + 1.0) / e) * rT);
-                B = b != b ? b : B;
-                dB = b != b ? b : dB;
-            }
-            return B;
-        };
+        column_points<NP>(A, j, nu, pa_n);
+        const bool fast = fold_fast_path<NP>(A, nu, active);
         auto up = [&](auto fast_tag, int l, vec v) {
             constexpr bool FAST = decltype(fast_tag)::value;
             const double pbkT = A.pbkT[l], depth = A.depth[l];
@@ -3542,18 +3546,11 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const double tau = v[p] * depth;
-                double dB;
-                const double B = planck(fast_tag, p, pbkT, 0.0, E0, dB);
+                double dB;          // (not used on the way up; the DT form keeps the down pass's instruction sequence for B)
+                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, 0.0, &dB);
 #pragma unroll
                 for (int k = 0; k < NA; ++k) {
-                    const double tr = exp_neg_budget(tau * A.rmu[k]);
-                    if (FAST) {
-                        I[k][p] = fma(tr, I[k][p], (1.0 - tr) * B);
-                    } else {
-                        const double transmitted = tr * I[k][p];
-                        const double emitted = (1.0 - tr) * B;
-                        I[k][p] = transmitted + emitted;
-                    }
+                    I[k][p] = fold_update<FAST>(exp_neg_budget(tau * A.rmu[k]), I[k][p], B);
                     Imax[k][p] = fmax(Imax[k][p], I[k][p]);
                 }
             }
@@ -3568,7 +3565,7 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
             for (int p = 0; p < NP; ++p) {
                 const double tau = v[p] * depth;
                 double dB;
-                const double B = planck(fast_tag, p, pbkT, rT, E0, dB);
+                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
                 double G = 0.0, gT = 0.0;
 #pragma unroll
                 for (int k = 0; k < NA; ++k) {
@@ -3591,7 +3588,7 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
             add(2 + l, s_tau);
             add(2 + L + l, s_T);
             for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load(A.term_k[t], j);
+                const vec km = load_points<NP>(A.term_k[t], j);
                 double s = 0.0;
 #pragma unroll
                 for (int p = 0; p < NP; ++p) s += active ? nan_to_num(km[p] * Gd[p]) : 0.0;
@@ -3603,13 +3600,15 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 dBs[p] = 0.0;
-                const double Is = A.I_surface ? A.I_surface[j + p] : planck_budget_dT(nu[p], A.pa, A.pbk_surface, A.r_surface_T, &dBs[p]);
+                const double Is = A.I_surface ? A.I_surface[j + p]
+                                              : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
+                                                                         A.r_surface_T, &dBs[p]);
 #pragma unroll
                 for (int k = 0; k < NA; ++k) { I[k][p] = Is; Imax[k][p] = Is; }
             }
-            vec cur = L > 0 ? load(A.abs_coef[0], j) : (vec)(0.0);
+            vec cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
             for (int l = 0; l < L; ++l) {
-                const vec nxt = l + 1 < L ? load(A.abs_coef[l + 1], j) : cur;
+                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
                 up(fast_tag, l, cur);
                 cur = nxt;
             }
@@ -3617,29 +3616,22 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
             double s = 0.0;
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                double f = A.w[0] * I[0][p];
-#pragma unroll
-                for (int k = 1; k < NA; ++k) f = fma(A.w[k], I[k][p], f);
-                s += active ? nan_to_num(f) : 0.0;
+                s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
 #pragma unroll
                 for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
             }
             add(0, s);
-            cur = L > 0 ? load(A.abs_coef[L - 1], j) : (vec)(0.0);
+            cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
             for (int l = L - 1; l >= 0; --l) {
-                const vec nxt = l > 0 ? load(A.abs_coef[l - 1], j) : cur;
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
                 down(fast_tag, l, cur);
                 cur = nxt;
             }
             // dF/dT_s = sum_k W_k A_(-1)k dB(nu, T_s)/dT (0 when the surface is a given spectrum)
             s = 0.0;
 #pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                double f = A.w[0] * (Ak[0][p] * dBs[p]);
-#pragma unroll
-                for (int k = 1; k < NA; ++k) f = fma(A.w[k], Ak[k][p] * dBs[p], f);
-                s += active ? nan_to_num(f) : 0.0;
-            }
+            for (int p = 0; p < NP; ++p)
+                s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return Ak[k][p] * dBs[p]; })) : 0.0;
             add(1, s);
         };
         if constexpr (NP > 1) {
@@ -3951,70 +3943,21 @@ void launch_band_integral(const double* y, long long n, double* partial, double*
     hipLaunchKernelGGL(band_final_kernel, dim3(1), dim3(256), 0, s, partial, nb, result);
 }
 
-// ---- K5c launch: one band [first, first + count) --------------------------------------------------------------------
-// Quads aligned to 4 on the global grid (first and last points of the whole range: the fold's quads) go to the NP = 4
-// kernel, at most kFluxMaxBlocks workgroups (grid-stride beyond, so the partial scratch is bounded); the band's head and
-// tail points (at most 6) to ONE 64-lane workgroup of the NP = 1 kernel, whose partial follows the others'.
-int column_flux_partials(long long count) {
-    const long long quads = count / 4 + 1;
-    return (int)std::min<long long>((quads + 255) / 256, kFluxMaxBlocks) + 1;
-}
-
-template <int NA>
-static void launch_column_flux_na(const FluxArgs* d_args, int nv, long long first, long long count, double* partial,
-                                  double* level_flux, hipStream_t s) {
-    const long long end = first + count;
-    const long long q0 = (first + 3) & ~3LL;
-    long long q1 = end & ~3LL;
-    if (q1 < q0) q1 = q0;
-    const long long nq = q1 - q0;
-    const long long nh = std::min(q0, end) - first;
-    const long long nt = end > q1 ? end - q1 : 0;
-    int blocks = 0;
-    if (nq > 0) {
-        blocks = (int)std::min<long long>((nq / 4 + 255) / 256, kFluxMaxBlocks);
-        hipLaunchKernelGGL((column_flux_kernel<4, NA>), dim3(blocks), dim3(256), 0, s, d_args, q0, nq, q0, 0LL, partial);
-    }
-    if (nh + nt > 0) {
-        hipLaunchKernelGGL((column_flux_kernel<1, NA>), dim3(1), dim3(64), 0, s, d_args, nh > 0 ? first : q1, nh, q1, nt,
-                           partial + (long long)blocks * nv);
-        ++blocks;
-    }
-    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, blocks, nv, level_flux);
-}
-
-void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long long first, long long count, double* partial,
-                        double* level_flux, hipStream_t s) {
-    if (count <= 0) return;
-    const int nv = 2 * (n_layers + 1);
-    switch (n_angles) {
-        case 1: launch_column_flux_na<1>(d_args, nv, first, count, partial, level_flux, s); break;
-        case 2: launch_column_flux_na<2>(d_args, nv, first, count, partial, level_flux, s); break;
-        case 3: launch_column_flux_na<3>(d_args, nv, first, count, partial, level_flux, s); break;
-        case 4: launch_column_flux_na<4>(d_args, nv, first, count, partial, level_flux, s); break;
-        case 5: launch_column_flux_na<5>(d_args, nv, first, count, partial, level_flux, s); break;
-        case 6: launch_column_flux_na<6>(d_args, nv, first, count, partial, level_flux, s); break;
-        case 7: launch_column_flux_na<7>(d_args, nv, first, count, partial, level_flux, s); break;
-        case 8: launch_column_flux_na<8>(d_args, nv, first, count, partial, level_flux, s); break;
-        default: break;
-    }
-}
-
-// ---- K5d launch: one band [first, first + count) --------------------------------------------------------------------
-// As K5c's, with NP points per thread chosen per angle count so that no instantiation spills (DESIGN.md "K5d"): groups of
-// NP aligned to NP on the global grid go to the NP kernel, the band's head and tail points (at most 2 (NP - 1)) to ONE
-// 64-lane workgroup of the NP = 1 kernel, whose partial follows the others'.
-template <int NA> constexpr int jacobian_np() { return NA <= 2 ? 4 : 2; }
-
-int column_jacobian_partials(long long count) {
-    const long long groups = count / 2 + 1;
+// ---- K5c / K5d launch: one band [first, first + count) ---------------------------------------------------------------
+// Groups of NP points aligned to NP on the global grid (the fold's quads for NP = 4) go to kernel<NP>, at most kFluxMaxBlocks
+// workgroups (grid-stride beyond, so the partial scratch is bounded); the band's head and tail points (at most 2 (NP - 1))
+// to ONE 64-lane workgroup of kernel<1>, whose partial follows the others'; then the fixed-order reduction into out[0 .. nv).
+int column_transport_partials(long long count, int np) {
+    const long long groups = count / np + 1;
     return (int)std::min<long long>((groups + 255) / 256, kFluxMaxBlocks) + 1;
 }
 
-template <int NA>
-static void launch_column_jacobian_na(const JacArgs* d_args, int nv, long long first, long long count, double* partial,
-                                      double* jac, hipStream_t s) {
-    constexpr int NP = jacobian_np<NA>();
+template <int NP, class Args>
+static void launch_column_band(void (*kernel_np)(const Args*, long long, long long, long long, long long, double*),
+                               void (*kernel_1)(const Args*, long long, long long, long long, long long, double*),
+                               const Args* d_args, int nv, long long first, long long count, double* partial, double* out,
+                               hipStream_t s) {
+    if (count <= 0) return;
     const long long end = first + count;
     const long long q0 = (first + NP - 1) & ~(long long)(NP - 1);
     long long q1 = end & ~(long long)(NP - 1);
@@ -4025,31 +3968,52 @@ static void launch_column_jacobian_na(const JacArgs* d_args, int nv, long long f
     int blocks = 0;
     if (nq > 0) {
         blocks = (int)std::min<long long>((nq / NP + 255) / 256, kFluxMaxBlocks);
-        hipLaunchKernelGGL((column_jacobian_kernel<NP, NA>), dim3(blocks), dim3(256), 0, s, d_args, q0, nq, q0, 0LL, partial);
+        hipLaunchKernelGGL(kernel_np, dim3(blocks), dim3(256), 0, s, d_args, q0, nq, q0, 0LL, partial);
     }
     if (nh + nt > 0) {
-        hipLaunchKernelGGL((column_jacobian_kernel<1, NA>), dim3(1), dim3(64), 0, s, d_args, nh > 0 ? first : q1, nh, q1, nt,
+        hipLaunchKernelGGL(kernel_1, dim3(1), dim3(64), 0, s, d_args, nh > 0 ? first : q1, nh, q1, nt,
                            partial + (long long)blocks * nv);
         ++blocks;
     }
-    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, blocks, nv, jac);
+    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, blocks, nv, out);
 }
+
+// f(std::integral_constant<int, NA>) for n_angles = NA in 1..kMaxFluxAngles
+template <class F>
+static void with_angles(int n_angles, F f) {
+    switch (n_angles) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 5: f(std::integral_constant<int, 5>{}); break;
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 7: f(std::integral_constant<int, 7>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        default: break;
+    }
+}
+
+void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long long first, long long count, double* partial,
+                        double* level_flux, hipStream_t s) {
+    with_angles(n_angles, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        launch_column_band<4>(column_flux_kernel<4, NA>, column_flux_kernel<1, NA>, d_args, 2 * (n_layers + 1), first, count,
+                              partial, level_flux, s);
+    });
+}
+
+// K5d's points per thread, chosen per angle count so that no instantiation spills (DESIGN.md "K5d")
+template <int NA> constexpr int jacobian_np() { return NA <= 2 ? 4 : 2; }
 
 void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first, long long count,
                             double* partial, double* jac, hipStream_t s) {
-    if (count <= 0) return;
-    const int nv = 2 + 2 * n_layers + n_terms;
-    switch (n_angles) {
-        case 1: launch_column_jacobian_na<1>(d_args, nv, first, count, partial, jac, s); break;
-        case 2: launch_column_jacobian_na<2>(d_args, nv, first, count, partial, jac, s); break;
-        case 3: launch_column_jacobian_na<3>(d_args, nv, first, count, partial, jac, s); break;
-        case 4: launch_column_jacobian_na<4>(d_args, nv, first, count, partial, jac, s); break;
-        case 5: launch_column_jacobian_na<5>(d_args, nv, first, count, partial, jac, s); break;
-        case 6: launch_column_jacobian_na<6>(d_args, nv, first, count, partial, jac, s); break;
-        case 7: launch_column_jacobian_na<7>(d_args, nv, first, count, partial, jac, s); break;
-        case 8: launch_column_jacobian_na<8>(d_args, nv, first, count, partial, jac, s); break;
-        default: break;
-    }
+    with_angles(n_angles, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        constexpr int NP = jacobian_np<NA>();
+        launch_column_band<NP>(column_jacobian_kernel<NP, NA>, column_jacobian_kernel<1, NA>, d_args, 2 + 2 * n_layers + n_terms,
+                               first, count, partial, jac, s);
+    });
 }
 
 void launch_line_survey(const double* nu, const double* sw, int n_lines, double range_min, double resolution,

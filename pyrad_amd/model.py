@@ -358,6 +358,14 @@ class _SweepState:
         return b
 
 
+def _kept_state(owner, key):
+    """The _SweepState kept in owner.__dict__[key], made on first use."""
+    st = owner.__dict__.get(key)
+    if st is None:
+        st = owner.__dict__[key] = _SweepState(owner)
+    return st
+
+
 def _iso_params(iso):
     layer = iso.layer
     q_T = iso.q[layer.T]                       # KeyError for a non-integer temperature, as cls:389
@@ -422,9 +430,7 @@ class _OpticalMixin:
         n = g["n_base"]
         members, conc = self._sweep_members()
         flat = [iso for isos in members for iso in isos]
-        st = self.__dict__.get("_sweep_state")
-        if st is None:
-            st = self.__dict__["_sweep_state"] = _SweepState(self)
+        st = _kept_state(self, "_sweep_state")
         st.reserve(ctx, n)
         lbl = [i for i in flat if not i.exotic]
         dirty = [i for i in lbl if not i.progressCrossSection]
@@ -1199,9 +1205,7 @@ class Layer(_OpticalMixin, list):
         """pyradPlanck.planckWavenumber(self.xAxis, temperature) (cls:781-782, pl:38-44), on the device."""
         ctx = _ctx()
         n = int((self.rangeMax - self.rangeMin) / utils.BASE_RESOLUTION)
-        st = self.__dict__.get("_planck_state")
-        if st is None:
-            st = self.__dict__["_planck_state"] = _SweepState(self)
+        st = _kept_state(self, "_planck_state")
         out = st.reserve(ctx, n).buf(ctx, "planck")
         ctx.planck_dev(self.rangeMin, self.rangeMax, n, float(temperature), out)
         return out.download(n, pinned=True)
@@ -1287,6 +1291,21 @@ def _flux_bands(rangeMin, rangeMax, n, bands):
     return first, count
 
 
+def _grid_spectrum(name, spec, n):
+    """``spec`` as n contiguous float64 values (ValueError for another shape), or None."""
+    if spec is None:
+        return None
+    spec = np.ascontiguousarray(spec, dtype=np.float64)
+    if spec.shape != (n,):
+        raise ValueError("%s: %d grid points expected, got shape %s" % (name, n, spec.shape))
+    return spec
+
+
+def _band_values(bands, values):
+    """Copies of per-band results (leading band axis): without ``bands`` each one's single band alone."""
+    return [(v[0] if bands is None else v).copy() for v in values]
+
+
 class Fluxes:
     """What Atmosphere.fluxes returns.  ``up``, ``down``, ``net``: W m^-2 at the levels 0 (surface) .. L (top), shape (L + 1,)
     or (n_bands, L + 1); ``heatingRate``: K/day per layer, (L,) or (n_bands, L); ``mu``, ``weight``: the angle set used;
@@ -1364,11 +1383,8 @@ class Atmosphere(list):
     def returnLayerObjects(self):
         return list(self)
 
-    def transmission(self, surfaceSpectrum=None, surfaceTemperature=None):
-        """Fold Layer.transmission bottom to top over the layers in list order:
-        I <- T_i I + (1 - T_i) B(nu, T_i), I_0 = surfaceSpectrum or B(nu, surfaceTemperature).
-        (The reference announces an atmosphere path but ships no driver; this is the fold of
-        cls:784-787, computed by one column-sweep kernel.)"""
+    def _column_layers(self):
+        """The layers, bottom to top, and the number of grid points of the one range they share."""
         layers = list(self)
         if not layers:
             raise ValueError("atmosphere has no layers")
@@ -1376,8 +1392,36 @@ class Atmosphere(list):
         for L in layers[1:]:
             if (L.rangeMin, L.rangeMax) != (first.rangeMin, first.rangeMax):
                 raise ValueError("all layers of a column must share one wavenumber range")
+        return layers, int((first.rangeMax - first.rangeMin) / utils.BASE_RESOLUTION)
+
+    def _column_checks(self, surfaceSpectrum, surfaceTemperature, angles, bands):
+        """The checks fluxes() and jacobians() share, before the device is touched: (layers, n, mu, weight, band_first,
+        band_count, surfaceSpectrum as n float64 values or None)."""
+        layers, n = self._column_layers()
+        if surfaceSpectrum is None and surfaceTemperature is None:
+            raise ValueError("give surfaceSpectrum or surfaceTemperature")
+        if surfaceSpectrum is None and not float(surfaceTemperature) > 0:
+            raise ValueError("surfaceTemperature must be > 0")
+        mu, weight = fluxAngles(angles)
+        band_first, band_count = _flux_bands(layers[0].rangeMin, layers[0].rangeMax, n, bands)
+        return layers, n, mu, weight, band_first, band_count, _grid_spectrum("surfaceSpectrum", surfaceSpectrum, n)
+
+    def _column_abs_coef(self, ctx, layers, n):
+        """Every layer's resident absorption coefficient buffer and the plan of _resident_abs_coef, which makes them in the
+        merged layer step of the default arithmetic; otherwise every layer's own sweep does, and the plan is None."""
+        if settings.LAYER_STEP == "merged" and not ctx.option("sweep_ieee_divisions"):
+            plan = self._resident_abs_coef(ctx, layers, n)
+            return [p[1].bufs["abs_coef"] for p in plan], plan
+        return [L._ensure_swept()[0].bufs["abs_coef"] for L in layers], None
+
+    def transmission(self, surfaceSpectrum=None, surfaceTemperature=None):
+        """Fold Layer.transmission bottom to top over the layers in list order:
+        I <- T_i I + (1 - T_i) B(nu, T_i), I_0 = surfaceSpectrum or B(nu, surfaceTemperature).
+        (The reference announces an atmosphere path but ships no driver; this is the fold of
+        cls:784-787, computed by one column-sweep kernel.)"""
+        layers, n = self._column_layers()
+        first = layers[0]
         ctx = _ctx()
-        n = int((first.rangeMax - first.rangeMin) / utils.BASE_RESOLUTION)
         if surfaceSpectrum is None and surfaceTemperature is None:
             raise ValueError("give surfaceSpectrum or surfaceTemperature")
         merged = self._transmission_merged(ctx, layers, n, surfaceSpectrum, surfaceTemperature)
@@ -1431,40 +1475,18 @@ class Atmosphere(list):
         takes its one-exp-per-thread Planck path (every range and temperature away from nu -> 0).
         The absorption coefficients come from the machinery transmission() uses and stay resident: after transmission()
         nothing is accumulated again.  Everything is validated (ValueError) before the device is touched."""
-        layers = list(self)
-        if not layers:
-            raise ValueError("atmosphere has no layers")
+        layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
+            surfaceSpectrum, surfaceTemperature, angles, bands)
+        topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
         first = layers[0]
-        for L in layers[1:]:
-            if (L.rangeMin, L.rangeMax) != (first.rangeMin, first.rangeMax):
-                raise ValueError("all layers of a column must share one wavenumber range")
-        if surfaceSpectrum is None and surfaceTemperature is None:
-            raise ValueError("give surfaceSpectrum or surfaceTemperature")
-        if surfaceSpectrum is None and not float(surfaceTemperature) > 0:
-            raise ValueError("surfaceTemperature must be > 0")
-        mu, weight = fluxAngles(angles)
-        n = int((first.rangeMax - first.rangeMin) / utils.BASE_RESOLUTION)
-        band_first, band_count = _flux_bands(first.rangeMin, first.rangeMax, n, bands)
-        sources = []
-        for name, spec in (("surfaceSpectrum", surfaceSpectrum), ("topSpectrum", topSpectrum)):
-            if spec is not None:
-                spec = np.ascontiguousarray(spec, dtype=np.float64)
-                if spec.shape != (n,):
-                    raise ValueError("%s: %d grid points expected, got shape %s" % (name, n, spec.shape))
-            sources.append(spec)
         res = utils.BASE_RESOLUTION
         nl, nb = len(layers), len(band_first)
         ctx = _ctx()
-        if settings.LAYER_STEP == "merged" and not ctx.option("sweep_ieee_divisions"):
-            kbufs = [p[1].bufs["abs_coef"] for p in self._resident_abs_coef(ctx, layers, n)]
-        else:
-            kbufs = [L._ensure_swept()[0].bufs["abs_coef"] for L in layers]
-        fst = self.__dict__.get("_flux_state")
-        if fst is None:
-            fst = self.__dict__["_flux_state"] = _SweepState(self)
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        fst = _kept_state(self, "_flux_state")
         fst.reserve(ctx, max(n, nb * 2 * (nl + 1)))
-        I_surface = fst.buf(ctx, "I_surface").upload(sources[0]) if sources[0] is not None else None
-        I_top = fst.buf(ctx, "I_top").upload(sources[1]) if sources[1] is not None else None
+        I_surface = fst.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
+        I_top = fst.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
         level = fst.buf(ctx, "level")
         up_top = fst.buf(ctx, "up_top") if spectra else None
         down_surface = fst.buf(ctx, "down_surface") if spectra else None
@@ -1474,9 +1496,8 @@ class Atmosphere(list):
         sums = level.download(nb * 2 * (nl + 1)).reshape(nb, 2, nl + 1) * res
         up, down = sums[:, 0, :], sums[:, 1, :]
         heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], [L.depth for L in layers])
-        if bands is None:
-            up, down, heat = up[0], down[0], heat[0]
-        return Fluxes(up.copy(), down.copy(), heat, mu, weight,
+        up, down, heat = _band_values(bands, [up, down, heat])
+        return Fluxes(up, down, heat, mu, weight,
                       upSpectrum=up_top.download(n) if spectra else None,
                       downSpectrum=down_surface.download(n) if spectra else None)
 
@@ -1504,24 +1525,9 @@ class Atmosphere(list):
         dF/d ln tau_l, (L, n) each.  Returns a Jacobians.  The layers' absorption coefficients are the ones fluxes() and
         transmission() keep resident: after either nothing is accumulated again.  No other result of the model changes.
         Everything is validated (ValueError) before the device is touched."""
-        layers = list(self)
-        if not layers:
-            raise ValueError("atmosphere has no layers")
+        layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
+            surfaceSpectrum, surfaceTemperature, angles, bands)
         first = layers[0]
-        for L in layers[1:]:
-            if (L.rangeMin, L.rangeMax) != (first.rangeMin, first.rangeMax):
-                raise ValueError("all layers of a column must share one wavenumber range")
-        if surfaceSpectrum is None and surfaceTemperature is None:
-            raise ValueError("give surfaceSpectrum or surfaceTemperature")
-        if surfaceSpectrum is None and not float(surfaceTemperature) > 0:
-            raise ValueError("surfaceTemperature must be > 0")
-        mu, weight = fluxAngles(angles)
-        n = int((first.rangeMax - first.rangeMin) / utils.BASE_RESOLUTION)
-        band_first, band_count = _flux_bands(first.rangeMin, first.rangeMax, n, bands)
-        if surfaceSpectrum is not None:
-            surfaceSpectrum = np.ascontiguousarray(surfaceSpectrum, dtype=np.float64)
-            if surfaceSpectrum.shape != (n,):
-                raise ValueError("surfaceSpectrum: %d grid points expected, got shape %s" % (n, surfaceSpectrum.shape))
         names = [[m.name for m in L] for L in layers]
         n_terms = sum(len(L) for L in layers) if molecules else 0
         if n_terms > nat.limit("jacobian_terms"):
@@ -1532,23 +1538,15 @@ class Atmosphere(list):
         ctx = _ctx()
         if ctx.option("sweep_ieee_divisions"):
             raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
-        if settings.LAYER_STEP == "merged":
-            plan = self._resident_abs_coef(ctx, layers, n)
-            kbufs = [p[1].bufs["abs_coef"] for p in plan]
-        else:
-            plan = None
-            kbufs = [L._ensure_swept()[0].bufs["abs_coef"] for L in layers]
-        js = self.__dict__.get("_jacobian_state")
-        if js is None:
-            js = self.__dict__["_jacobian_state"] = dict(terms={}, out=_SweepState(self), spec=_SweepState(self))
-        term_bufs, term_layer = self._jacobian_terms(ctx, layers, n, plan, js) if molecules else ([], [])
+        kbufs, plan = self._column_abs_coef(ctx, layers, n)
+        term_bufs, term_layer = self._jacobian_terms(ctx, layers, n, plan) if molecules else ([], [])
         nv = 2 + 2 * nl + len(term_bufs)
-        out = js["out"].reserve(ctx, max(n, nb * nv))
+        out = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, nb * nv))
         I_surface = out.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
         jac = out.buf(ctx, "jac")
         ln_tau_spec = T_spec = None
         if spectra:
-            sp = js["spec"].reserve(ctx, nl * n)
+            sp = _kept_state(self, "_jacobian_spec").reserve(ctx, nl * n)
             ln_tau_spec, T_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T")
         ctx.column_jacobian_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
                                 mu, weight, band_first, band_count, jac, I_surface=I_surface,
@@ -1563,24 +1561,20 @@ class Atmosphere(list):
             for L in layers:
                 mol.append(v[:, o:o + len(L)])
                 o += len(L)
-        if bands is None:
-            olr, dTs, dtau, dT = olr[0], dTs[0], dtau[0], dT[0]
-            mol = [m[0] for m in mol] if mol is not None else None
-        else:
-            olr, dTs, dtau, dT = olr.copy(), dTs.copy(), dtau.copy(), dT.copy()
-            mol = [m.copy() for m in mol] if mol is not None else None
+        olr, dTs, dtau, dT = _band_values(bands, [olr, dTs, dtau, dT])
+        mol = _band_values(bands, mol) if mol is not None else None
         return Jacobians(olr, dTs if surfaceSpectrum is None else None, dT, dtau, mol, names, mu, weight,
                          temperatureSpectrum=T_spec.download(nl * n).reshape(nl, n) if spectra else None,
                          opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None)
 
-    def _jacobian_terms(self, ctx, layers, n, plan, js):
+    def _jacobian_terms(self, ctx, layers, n, plan):
         """The molecule terms of jacobians(): every molecule's own absorption coefficient k_(m,l), as (buffers, layer index
         of each).  In a layer that is one merged job (``plan`` of _resident_abs_coef) a molecule gets ONE merged accumulate
         job over its own line lists (its volume fraction, iso_mol all 0) into a buffer of the atmosphere's Jacobian state,
         keyed like the layer's (_merged_key): it is recomputed only when that molecule's inputs change, and all due
         molecules go in one launch sequence.  Exotic molecules, molecules without line lists and layers that are no merged
         job use the molecule's own route (Molecule._ensure_swept)."""
-        terms = js["terms"]
+        terms = self.__dict__.setdefault("_jacobian_term_states", {})
         bufs, where, todo, keys, keep = [], [], [], [], set()
         for l, L in enumerate(layers):
             members, conc = L._sweep_members()
@@ -1630,9 +1624,7 @@ class Atmosphere(list):
             return fast
         plan = self._resident_abs_coef(ctx, layers, n)
         # (the outgoing spectrum's buffer stays with the atmosphere: a hipMalloc + hipFree pair per call is 0.2 ms of a 5 ms call)
-        ast = self.__dict__.get("_toa_state")
-        if ast is None:
-            ast = self.__dict__["_toa_state"] = _SweepState(self)
+        ast = _kept_state(self, "_toa_state")
         out = ast.reserve(ctx, n).buf(ctx, "toa")
         I_in = None
         if surfaceSpectrum is not None:
@@ -1680,9 +1672,7 @@ class Atmosphere(list):
                 plan.append((L, st, g, members, flat, conc, None))
                 continue
             _check_window(g)
-            st = L.__dict__.get("_sweep_state")
-            if st is None:
-                st = L.__dict__["_sweep_state"] = _SweepState(L)
+            st = _kept_state(L, "_sweep_state")
             st.reserve(ctx, n)
             plan.append((L, st, g, members, flat, conc, L._merged_key(flat, conc, L, g)))
         # (a layer's absorption coefficient stands as long as everything but the depth is what it was computed from)
@@ -1758,9 +1748,7 @@ class Atmosphere(list):
             col.set_layer(l, [i._device_lines(ctx) for i in flat], [_iso_params(i) for i in flat], _engine.native_grid(g), conc,
                           L.depth, fast["kbuf"][l])
             fast["val"][l] = val
-        ast = self.__dict__.get("_toa_state")
-        if ast is None:
-            ast = self.__dict__["_toa_state"] = _SweepState(self)
+        ast = _kept_state(self, "_toa_state")
         out = ast.reserve(ctx, n).buf(ctx, "toa")
         I_in = None
         if surfaceSpectrum is not None:
