@@ -437,7 +437,8 @@ int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_c
  *                            grid, each piece's part of I_out copied to host_out (page-locked, lbl_host_alloc; may be NULL: no
  *                            download) while the next piece is folded.  Returns when everything is ENQUEUED:
  *                            lbl_download_wait(ctx) before host_out is read.  The sweeps' default arithmetic only
- *                            ("sweep_ieee_divisions" 1: LBL_ERR_BAD_ARG). */
+ *                            ("sweep_ieee_divisions" 1: LBL_ERR_BAD_ARG).  Every argument is checked before anything is
+ *                            enqueued: a refused call has not started the due layers' jobs either. */
 typedef struct lbl_column lbl_column;
 int lbl_column_create(lbl_ctx* ctx, int n_layers, const int32_t* n_iso, lbl_lines* const* lines, const lbl_iso_params* iso,
                       const lbl_grid* grid, const int32_t* iso_mol, const int32_t* n_mol, const double* conc,

@@ -204,6 +204,11 @@ def _hb(b):
     return None if b is None else b.h
 
 
+def _arr(typ, vals):
+    """ctypes array of ``vals`` (one element at least: an empty list still gives the C side a pointer)."""
+    return (typ * max(len(vals), 1))(*vals)
+
+
 class Context:
     """One HIP device + one stream (lbl_ctx).  Not thread-safe."""
 
@@ -422,56 +427,44 @@ class Context:
 
     def layer_sweep_dev(self, xsec, iso_mol, conc, P, T, depth, range_min, range_max, n,
                         I_in=None, surface_T=0.0, abs_coef=None, trans=None, I_out=None, first=0, count=0):
-        n_iso = len(xsec)
-        X = (_P * max(n_iso, 1))(*[b.h for b in xsec])
-        M = (C.c_int32 * max(n_iso, 1))(*[int(m) for m in iso_mol])
-        cc = (C.c_double * max(len(conc), 1))(*[float(c) for c in conc])
         self.check(self.lib.lbl_layer_sweep_dev(
-            self.h, n_iso, X, M, len(conc), cc, float(P), float(T), float(depth), float(range_min),
-            float(range_max), int(n), int(first), int(count), I_in.h if I_in is not None else None,
-            float(surface_T), abs_coef.h if abs_coef is not None else None, trans.h if trans is not None else None,
-            I_out.h if I_out is not None else None))
+            self.h, len(xsec), _arr(_P, [b.h for b in xsec]), _arr(C.c_int32, [int(m) for m in iso_mol]), len(conc),
+            _arr(C.c_double, [float(c) for c in conc]), float(P), float(T), float(depth), float(range_min),
+            float(range_max), int(n), int(first), int(count), _hb(I_in), float(surface_T), _hb(abs_coef), _hb(trans),
+            _hb(I_out)))
+
+    @staticmethod
+    def _layer_lists(lines, iso, iso_mol, conc, xsec=None):
+        """The per-line-list arguments of layer_step_dev and layer_merged_step_dev as C arrays: (n, lines, iso, xsec, iso_mol,
+        number of molecules, conc).  A single Lines / IsoParams / Buffer is taken as one line list, a scalar ``conc`` as one
+        molecule, ``iso_mol`` None as one molecule per line list."""
+        if isinstance(lines, Lines):
+            lines, iso, xsec = [lines], [iso], None if xsec is None else [xsec]
+        if np.isscalar(conc):
+            conc = [conc]
+        if iso_mol is None:
+            iso_mol = list(range(len(lines)))
+        n = len(lines)
+        return (n, (_P * n)(*[l.h for l in lines]), (IsoParams * n)(*iso), None if xsec is None else (_P * n)(*[b.h for b in xsec]),
+                (C.c_int32 * n)(*[int(m) for m in iso_mol]), len(conc), _arr(C.c_double, [float(c) for c in conc]))
 
     def layer_step_dev(self, lines, iso, grid: Grid, xsec, iso_mol, conc, depth, I_in=None, surface_T=0.0,
                        abs_coef=None, trans=None, I_out=None):
         """Accumulate + sweep of one layer in one launch sequence (lbl_layer_step_dev): ``lines`` /
         ``iso`` / ``xsec`` are per line list (a single Lines / IsoParams / Buffer is taken as one),
         ``iso_mol`` maps line list -> molecule, ``conc`` is per molecule."""
-        if isinstance(lines, Lines):
-            lines, iso, xsec = [lines], [iso], [xsec]
-        if np.isscalar(conc):
-            conc = [conc]
-        if iso_mol is None:
-            iso_mol = list(range(len(lines)))
-        n = len(lines)
-        L = (_P * n)(*[l.h for l in lines])
-        I = (IsoParams * n)(*iso)
-        X = (_P * n)(*[b.h for b in xsec])
-        M = (C.c_int32 * n)(*[int(m) for m in iso_mol])
-        cc = (C.c_double * max(len(conc), 1))(*[float(c) for c in conc])
-        h = lambda b: b.h if b is not None else None
-        self.check(self.lib.lbl_layer_step_dev(self.h, n, L, I, C.byref(grid), X, M, len(conc), cc, float(depth), h(I_in),
-                                               float(surface_T), h(abs_coef), h(trans), h(I_out)))
+        n, L, I, X, M, n_mol, cc = self._layer_lists(lines, iso, iso_mol, conc, xsec)
+        self.check(self.lib.lbl_layer_step_dev(self.h, n, L, I, C.byref(grid), X, M, n_mol, cc, float(depth), _hb(I_in),
+                                               float(surface_T), _hb(abs_coef), _hb(trans), _hb(I_out)))
 
     def layer_merged_step_dev(self, lines, iso, grid: Grid, iso_mol, conc, depth, I_in=None, surface_T=0.0,
                               abs_coef=None, trans=None, I_out=None):
         """One layer through ONE accumulate job over its merged, factor-weighted line lists with the sweep in the
         output stage (lbl_layer_merged_step_dev): the absorption coefficient is accumulated directly, no
         per-line-list cross section is written.  Arguments as layer_step_dev without ``xsec``."""
-        if isinstance(lines, Lines):
-            lines, iso = [lines], [iso]
-        if np.isscalar(conc):
-            conc = [conc]
-        if iso_mol is None:
-            iso_mol = list(range(len(lines)))
-        n = len(lines)
-        L = (_P * n)(*[l.h for l in lines])
-        I = (IsoParams * n)(*iso)
-        M = (C.c_int32 * n)(*[int(m) for m in iso_mol])
-        cc = (C.c_double * max(len(conc), 1))(*[float(c) for c in conc])
-        h = lambda b: b.h if b is not None else None
-        self.check(self.lib.lbl_layer_merged_step_dev(self.h, n, L, I, C.byref(grid), M, len(conc), cc, float(depth),
-                                                      h(I_in), float(surface_T), h(abs_coef), h(trans), h(I_out)))
+        n, L, I, _, M, n_mol, cc = self._layer_lists(lines, iso, iso_mol, conc)
+        self.check(self.lib.lbl_layer_merged_step_dev(self.h, n, L, I, C.byref(grid), M, n_mol, cc, float(depth),
+                                                      _hb(I_in), float(surface_T), _hb(abs_coef), _hb(trans), _hb(I_out)))
 
     def layers_merged_accumulate_dev(self, layers):
         """layers: list of dict(lines=[Lines], iso=[IsoParams], grid=Grid, iso_mol=[int], conc=[float], abs_coef=Buffer):
@@ -480,13 +473,12 @@ class Context:
         nl = len(layers)
         if nl == 0:
             return
-        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
         ls = [l for L in layers for l in L["lines"]]
         self.check(self.lib.lbl_layers_merged_accumulate_dev(
-            self.h, nl, arr(C.c_int32, [len(L["lines"]) for L in layers]), arr(_P, [l.h for l in ls]),
-            arr(IsoParams, [i for L in layers for i in L["iso"]]), arr(Grid, [L["grid"] for L in layers]),
-            arr(C.c_int32, [int(m) for L in layers for m in L["iso_mol"]]), arr(C.c_int32, [len(L["conc"]) for L in layers]),
-            arr(C.c_double, [float(c) for L in layers for c in L["conc"]]), arr(_P, [L["abs_coef"].h for L in layers])))
+            self.h, nl, _arr(C.c_int32, [len(L["lines"]) for L in layers]), _arr(_P, [l.h for l in ls]),
+            _arr(IsoParams, [i for L in layers for i in L["iso"]]), _arr(Grid, [L["grid"] for L in layers]),
+            _arr(C.c_int32, [int(m) for L in layers for m in L["iso_mol"]]), _arr(C.c_int32, [len(L["conc"]) for L in layers]),
+            _arr(C.c_double, [float(c) for L in layers for c in L["conc"]]), _arr(_P, [L["abs_coef"].h for L in layers])))
 
     def column(self, layers):
         """Resident column (lbl_column_create): ``layers`` as for layers_merged_accumulate_dev, each with ``depth``."""
@@ -497,23 +489,20 @@ class Context:
         """Column step from the layers' absorption coefficients, bottom to top (lbl_column_fold_dev); ``trans``: None or
         a list (entries may be None) of buffers that receive the layers' transmittances."""
         nl = len(abs_coef)
-        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
-        hb = lambda b: b.h if b is not None else None
         self.check(self.lib.lbl_column_fold_dev(
-            self.h, nl, arr(_P, [b.h for b in abs_coef]), arr(C.c_double, [float(t) for t in layer_T]),
-            arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), int(first), int(count),
-            hb(I_in), float(surface_T), arr(_P, [hb(b) for b in trans]) if trans is not None else None, I_out.h))
+            self.h, nl, _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
+            _arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), int(first), int(count),
+            _hb(I_in), float(surface_T), _arr(_P, [_hb(b) for b in trans]) if trans is not None else None, I_out.h))
 
     def _column_args(self, abs_coef, layer_T, depth, range_min, range_max, n, I_surface, surface_T, after_surface, mu,
                      weight, band_first, band_count):
         """The leading arguments lbl_column_flux_dev and lbl_column_jacobian_dev share, from ctx to band_count
         (``after_surface``: what the entry point takes between surface_T and the angle set)."""
-        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
-        return (self.h, len(abs_coef), arr(_P, [b.h for b in abs_coef]), arr(C.c_double, [float(t) for t in layer_T]),
-                arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), _hb(I_surface),
-                float(surface_T), *after_surface, len(mu), arr(C.c_double, [float(m) for m in mu]),
-                arr(C.c_double, [float(w) for w in weight]), len(band_first), arr(C.c_int64, [int(f) for f in band_first]),
-                arr(C.c_int64, [int(c) for c in band_count]))
+        return (self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
+                _arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), _hb(I_surface),
+                float(surface_T), *after_surface, len(mu), _arr(C.c_double, [float(m) for m in mu]),
+                _arr(C.c_double, [float(w) for w in weight]), len(band_first), _arr(C.c_int64, [int(f) for f in band_first]),
+                _arr(C.c_int64, [int(c) for c in band_count]))
 
     def column_flux_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                         level_flux, I_surface=None, surface_T=0.0, I_top=None, up_top=None, down_surface=None):
@@ -531,11 +520,10 @@ class Context:
         """Jacobians of the upward flux at the top (lbl_column_jacobian_dev): ``jac`` receives len(band_first) x (2 + 2 L +
         len(term_abs_coef)) band sums [band][F, dF/dT_s, L x dF/d ln tau, L x dF/dT, terms x dF/d ln n]; ``term_layer``
         gives each term's layer; ``ln_tau_spectra`` / ``T_spectra`` (optional, L x n points) the spectral values."""
-        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
         self.check(self.lib.lbl_column_jacobian_dev(
             *self._column_args(abs_coef, layer_T, depth, range_min, range_max, n, I_surface, surface_T, (), mu, weight,
                                band_first, band_count),
-            len(term_abs_coef), arr(_P, [b.h for b in term_abs_coef]), arr(C.c_int32, [int(l) for l in term_layer]),
+            len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]), _arr(C.c_int32, [int(l) for l in term_layer]),
             _hb(jac), _hb(ln_tau_spectra), _hb(T_spectra)))
 
     def gather_compact_dev(self, gathered, slot, bounds, out):
@@ -552,25 +540,21 @@ class Context:
         xs = [b for L in layers for b in L["xsec"]]
         im = [int(m) for L in layers for m in L["iso_mol"]]
         cc = [float(c) for L in layers for c in L["conc"]]
-        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
-        n_iso = arr(C.c_int32, [len(L["xsec"]) for L in layers])
-        n_mol = arr(C.c_int32, [len(L["conc"]) for L in layers])
-        hb = lambda b: b.h if b is not None else None
+        n_iso = _arr(C.c_int32, [len(L["xsec"]) for L in layers])
+        n_mol = _arr(C.c_int32, [len(L["conc"]) for L in layers])
         self.check(self.lib.lbl_column_step_dev(
-            self.h, nl, n_iso, arr(_P, [b.h for b in xs]), arr(C.c_int32, im), n_mol, arr(C.c_double, cc),
-            arr(C.c_double, [float(L["P"]) for L in layers]), arr(C.c_double, [float(L["T"]) for L in layers]),
-            arr(C.c_double, [float(L["depth"]) for L in layers]), float(range_min), float(range_max), int(n),
-            int(first), int(count), hb(I_in), float(surface_T),
-            arr(_P, [hb(L.get("abs_coef")) for L in layers]), arr(_P, [hb(L.get("trans")) for L in layers]), I_out.h))
+            self.h, nl, n_iso, _arr(_P, [b.h for b in xs]), _arr(C.c_int32, im), n_mol, _arr(C.c_double, cc),
+            _arr(C.c_double, [float(L["P"]) for L in layers]), _arr(C.c_double, [float(L["T"]) for L in layers]),
+            _arr(C.c_double, [float(L["depth"]) for L in layers]), float(range_min), float(range_max), int(n),
+            int(first), int(count), _hb(I_in), float(surface_T),
+            _arr(_P, [_hb(L.get("abs_coef")) for L in layers]), _arr(_P, [_hb(L.get("trans")) for L in layers]), I_out.h))
 
     def column_sweep_dev(self, trans, layer_T, range_min, range_max, n, I_out, I_in=None, surface_T=0.0,
                          first=0, count=0):
-        nl = len(trans)
-        Tb = (_P * max(nl, 1))(*[b.h for b in trans])
-        TT = (C.c_double * max(nl, 1))(*[float(t) for t in layer_T])
-        self.check(self.lib.lbl_column_sweep_dev(self.h, nl, Tb, TT, float(range_min), float(range_max), int(n),
-                                                 int(first), int(count),
-                                                 I_in.h if I_in is not None else None, float(surface_T), I_out.h))
+        self.check(self.lib.lbl_column_sweep_dev(self.h, len(trans), _arr(_P, [b.h for b in trans]),
+                                                 _arr(C.c_double, [float(t) for t in layer_T]), float(range_min),
+                                                 float(range_max), int(n), int(first), int(count), _hb(I_in),
+                                                 float(surface_T), I_out.h))
 
     def sum_dev(self, bufs, n, out):
         """out = zeros + bufs[0] + bufs[1] + ... in list order (pyradClasses.py:566-571, 684-689).  A list longer than the
@@ -609,24 +593,22 @@ class Column:
     def __init__(self, ctx: "Context", layers):
         self.ctx = ctx
         self.n_layers = len(layers)
-        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
         ls = [l for L in layers for l in L["lines"]]
         self._keep = [(list(L["lines"]), L["abs_coef"]) for L in layers]
         h = _P()
         ctx.check(ctx.lib.lbl_column_create(
-            ctx.h, self.n_layers, arr(C.c_int32, [len(L["lines"]) for L in layers]), arr(_P, [l.h for l in ls]),
-            arr(IsoParams, [i for L in layers for i in L["iso"]]), arr(Grid, [L["grid"] for L in layers]),
-            arr(C.c_int32, [int(m) for L in layers for m in L["iso_mol"]]), arr(C.c_int32, [len(L["conc"]) for L in layers]),
-            arr(C.c_double, [float(c) for L in layers for c in L["conc"]]), arr(C.c_double, [float(L["depth"]) for L in layers]),
-            arr(_P, [L["abs_coef"].h for L in layers]), C.byref(h)))
+            ctx.h, self.n_layers, _arr(C.c_int32, [len(L["lines"]) for L in layers]), _arr(_P, [l.h for l in ls]),
+            _arr(IsoParams, [i for L in layers for i in L["iso"]]), _arr(Grid, [L["grid"] for L in layers]),
+            _arr(C.c_int32, [int(m) for L in layers for m in L["iso_mol"]]), _arr(C.c_int32, [len(L["conc"]) for L in layers]),
+            _arr(C.c_double, [float(c) for L in layers for c in L["conc"]]), _arr(C.c_double, [float(L["depth"]) for L in layers]),
+            _arr(_P, [L["abs_coef"].h for L in layers]), C.byref(h)))
         self.h = h
         self._due = (C.c_uint8 * self.n_layers)()
         ctx._children.append(self)
 
     def set_layer(self, l, lines, iso, grid, conc, depth, abs_coef):
-        arr = lambda typ, vals: (typ * max(len(vals), 1))(*vals)
-        self.ctx.check(self.ctx.lib.lbl_column_set_layer(self.h, int(l), arr(_P, [x.h for x in lines]), arr(IsoParams, list(iso)),
-                                                         C.byref(grid), arr(C.c_double, [float(c) for c in conc]), float(depth),
+        self.ctx.check(self.ctx.lib.lbl_column_set_layer(self.h, int(l), _arr(_P, [x.h for x in lines]), _arr(IsoParams, list(iso)),
+                                                         C.byref(grid), _arr(C.c_double, [float(c) for c in conc]), float(depth),
                                                          abs_coef.h))
         self._keep[l] = (list(lines), abs_coef)
 
@@ -643,7 +625,7 @@ class Column:
             if not (host.dtype == np.float64 and host.flags["C_CONTIGUOUS"]):
                 raise ValueError("the host array must be contiguous float64")
             hp = _ptr(host)
-        self.ctx.check(self.ctx.lib.lbl_column_transmission(self.h, flags, I_in.h if I_in is not None else None, float(surface_T),
+        self.ctx.check(self.ctx.lib.lbl_column_transmission(self.h, flags, _hb(I_in), float(surface_T),
                                                             I_out.h, hp, int(pieces)))
 
     def free(self):

@@ -15,6 +15,7 @@
 #include <new>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 
@@ -1770,13 +1771,137 @@ static int check_buf(lbl_ctx* ctx, const lbl_buffer* b, int64_t n, const char* w
     return LBL_OK;
 }
 
-// smallest / largest Planck-exponent factor 100 h c / k / T of a column's terms (ColumnStepArgs.pbkT_min / _max)
-static void column_pbkT_range(ColumnStepArgs* a) {
-    a->pbkT_min = a->pbkT_max = a->n_terms > 0 ? a->term_pbkT[0] : 0.0;
-    for (int t = 1; t < a->n_terms; ++t) {
+static double* buf_data(const lbl_buffer* b) { return b ? b->d : nullptr; }
+
+// ---- what the layer and column entry points share: an entry point checks with these, fills its argument block (SweepArgs,
+// ColumnArgs, ColumnStepArgs, FusedSweep: the four name their common fields alike) with these and launches with these ----
+
+// the swept range [first, first + count) of a grid of n points; a count of 0 means all of it
+static int check_range(lbl_ctx* ctx, int64_t n, int64_t* first, int64_t* count) {
+    if (n < 0) return fail(ctx, LBL_ERR_BAD_ARG, "negative n");
+    if (*first < 0 || *count < 0 || *count > n - *first) return fail(ctx, LBL_ERR_BAD_ARG, "swept range outside [0, n)");
+    if (*count == 0) { *first = 0; *count = n; }
+    return LBL_OK;
+}
+
+// the arrays of a single layer's sweep, each optional; a column's: the outgoing radiance is what the call is for.  A radiance
+// needs a start, the incoming one or the surface's.
+static int check_layer_arrays(lbl_ctx* ctx, int64_t n, const lbl_buffer* I_in, double surface_T, const lbl_buffer* abs_coef,
+                              const lbl_buffer* trans, const lbl_buffer* I_out) {
+    int rc;
+    if ((rc = check_buf(ctx, I_in, n, "I_in", false)) || (rc = check_buf(ctx, abs_coef, n, "abs_coef", false)) ||
+        (rc = check_buf(ctx, trans, n, "trans", false)) || (rc = check_buf(ctx, I_out, n, "I_out", false)))
+        return rc;
+    if (I_out && !I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "I_out needs I_in or surface_T > 0");
+    return LBL_OK;
+}
+static int check_column_arrays(lbl_ctx* ctx, int64_t n, const lbl_buffer* I_in, double surface_T, const lbl_buffer* I_out) {
+    int rc;
+    if ((rc = check_buf(ctx, I_out, n, "I_out", true)) || (rc = check_buf(ctx, I_in, n, "I_in", false))) return rc;
+    if (!I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "I_out needs I_in or surface_T > 0");
+    return LBL_OK;
+}
+
+// the frame of a block: the wavenumber axis, the Planck constants, the surface, the radiance in and out, the swept range
+template <class Block>
+static void fill_frame(Block* a, double range_min, double range_max, int64_t n, int64_t first, int64_t count,
+                       const lbl_buffer* I_in, double surface_T, double* I_out) {
+    a->start = range_min; a->stop = range_max; a->step = axis_step(range_min, range_max, n);
+    planck_constants(&a->pa, &a->pb);
+    a->surface_T = surface_T;
+    a->r_surface_T = uniform_rcp(surface_T);
+    a->pbk_surface = budget_pbkT(surface_T);
+    a->I_in = buf_data(I_in);
+    a->I_out = I_out;
+    a->n = n;
+    if constexpr (!std::is_same_v<Block, FusedSweep>) { a->first = first; a->count = count; }      // (a fused sweep follows its job's shard)
+}
+
+// the one layer of a SweepArgs or a FusedSweep
+template <class Block>
+static void fill_layer(Block* a, double P, double T, double depth, int budget, const lbl_buffer* abs_coef, const lbl_buffer* trans) {
+    a->P = P; a->T = T; a->depth = depth;
+    a->rT = uniform_rcp(T);
+    a->pbkT = budget_pbkT(T);
+    a->budget = budget;
+    a->abs_coef = buf_data(abs_coef);
+    a->trans = buf_data(trans);
+}
+
+// A layer's term list, one term per cross-section array, molecule after molecule: iso_mol (line list -> molecule of the layer)
+// must be non-decreasing and < n_mol.  With a block, the arrays are checked too and the terms written from term `at` on (SweepArgs:
+// 0; ColumnStepArgs: where the layers below ended); without one (a = xsec = conc = NULL) this is the check of iso_mol alone.
+template <class Block>
+static int add_layer_terms(lbl_ctx* ctx, Block* a, int at, int n_iso, lbl_buffer* const* xsec, const int32_t* iso_mol, int n_mol,
+                           const double* conc, double P, double T, int64_t n, int layer) {
+    for (int i = 0; i < n_iso; ++i) {
+        int rc;
+        if (xsec && (rc = check_buf(ctx, xsec[i], n, "xsec", true))) return rc;
+        const int32_t m = iso_mol[i];
+        if (m < 0 || m >= n_mol || (i > 0 && m < iso_mol[i - 1]))
+            return fail(ctx, LBL_ERR_BAD_ARG, "layer %d: iso_mol must be non-decreasing and < n_mol", layer);
+        if (!a) continue;
+        a->xsec[at + i] = xsec[i]->d;
+        a->term_conc[at + i] = conc[m];
+        a->term_factor[at + i] = budget_factor(conc[m], P, T);
+        a->term_flags[at + i] = (i == n_iso - 1 || iso_mol[i + 1] != m) ? TERM_LAST_MOL : 0;
+    }
+    return LBL_OK;
+}
+
+// a layer's scalars, repeated over its terms [t0, t1) of a ColumnStepArgs
+static void set_term_scalars(ColumnStepArgs* a, int t0, int t1, double P, double T, double depth) {
+    for (int t = t0; t < t1; ++t) {
+        a->term_P[t] = P; a->term_T[t] = T; a->term_depth[t] = depth;
+        a->term_rT[t] = uniform_rcp(T);
+        a->term_pbkT[t] = budget_pbkT(T);
+    }
+}
+
+// an optional per-layer output of a ColumnStepArgs (slot: &a->abs_coef[l] or &a->trans[l])
+static int set_layer_array(lbl_ctx* ctx, ColumnStepArgs* a, double** slot, const lbl_buffer* b, const char* what) {
+    if (!b) return LBL_OK;
+    const int rc = check_buf(ctx, b, a->n, what, true);
+    if (rc) return rc;
+    *slot = b->d;
+    a->layer_arrays = 1;
+    return LBL_OK;
+}
+
+// K4, its block by value; K5 / K5b, their blocks uploaded first (launch(d_args) enqueues the kernel): under a profile event of `kind`
+static int launch_sweep(lbl_ctx* ctx, const SweepArgs& a) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipEvent_t ev = prof_begin(ctx, PROF_SWEEP);
+    launch_layer_sweep(a, ctx->stream);
+    prof_end(ctx, PROF_SWEEP, ev);
+    HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+}
+template <class Block, class Launch>
+static int upload_and_launch(lbl_ctx* ctx, int kind, const Block* a, Launch launch) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void* d_args = nullptr;
+    int rc;
+    if ((rc = device_args(ctx, a, sizeof(Block), &d_args))) return rc;
+    hipEvent_t ev = prof_begin(ctx, kind);
+    launch((const Block*)d_args);
+    prof_end(ctx, kind, ev);
+    HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+}
+// K5b over the block's n_terms terms in n_layers layers, its swept range the block's (kfold: see launch_column_step)
+static int launch_column_terms(lbl_ctx* ctx, int kind, ColumnStepArgs* a, int n_terms, int n_layers, int kfold = 0) {
+    a->n_terms = n_terms; a->n_layers = n_layers;
+    a->ablate = ctx->ablate;
+    // smallest / largest Planck-exponent factor 100 h c / k / T of the terms
+    a->pbkT_min = a->pbkT_max = n_terms > 0 ? a->term_pbkT[0] : 0.0;
+    for (int t = 1; t < n_terms; ++t) {
         a->pbkT_min = std::min(a->pbkT_min, a->term_pbkT[t]);
         a->pbkT_max = std::max(a->pbkT_max, a->term_pbkT[t]);
     }
+    return upload_and_launch(ctx, kind, a, [&](const ColumnStepArgs* d) {
+        launch_column_step(d, a->first, a->count, ctx->stream, !ctx->sweep_ieee, kfold);
+    });
 }
 
 // A layer with more cross-section arrays than SweepArgs holds (kMaxIso): the same sums, in the same order, by the column-step
@@ -1787,53 +1912,22 @@ static int layer_sweep_as_column(lbl_ctx* ctx, int n_iso, lbl_buffer* const* xse
                                  int64_t n, int64_t first, int64_t count, lbl_buffer* I_in, double surface_T,
                                  lbl_buffer* abs_coef, lbl_buffer* trans, lbl_buffer* I_out) {
     int rc;
-    if ((rc = check_buf(ctx, I_in, n, "I_in", false))) return rc;
-    if ((rc = check_buf(ctx, abs_coef, n, "abs_coef", false))) return rc;
-    if ((rc = check_buf(ctx, trans, n, "trans", false))) return rc;
-    if ((rc = check_buf(ctx, I_out, n, "I_out", false))) return rc;
-    if (I_out && !I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "I_out needs I_in or surface_T > 0");
+    if ((rc = check_layer_arrays(ctx, n, I_in, surface_T, abs_coef, trans, I_out))) return rc;
     std::vector<char> blk(sizeof(ColumnStepArgs), 0);
     ColumnStepArgs* a = (ColumnStepArgs*)blk.data();
-    for (int i = 0; i < n_iso; ++i) {
-        if ((rc = check_buf(ctx, xsec[i], n, "xsec", true))) return rc;
-        if (iso_mol[i] < 0 || iso_mol[i] >= n_mol || (i > 0 && iso_mol[i] < iso_mol[i - 1]))
-            return fail(ctx, LBL_ERR_BAD_ARG, "iso_mol must be non-decreasing and < n_mol");
-        a->xsec[i] = xsec[i]->d;
-        a->term_conc[i] = conc[iso_mol[i]];
-        a->term_factor[i] = budget_factor(conc[iso_mol[i]], P, T);
-        a->term_flags[i] = (i == n_iso - 1 || iso_mol[i + 1] != iso_mol[i]) ? TERM_LAST_MOL : 0;
-        a->term_P[i] = P; a->term_T[i] = T; a->term_depth[i] = depth;
-        a->term_rT[i] = uniform_rcp(T);
-        a->term_pbkT[i] = budget_pbkT(T);
-    }
+    if ((rc = add_layer_terms(ctx, a, 0, n_iso, xsec, iso_mol, n_mol, conc, P, T, n, 0))) return rc;
     a->term_flags[n_iso - 1] |= TERM_LAST_LAYER;
-    a->n_terms = n_iso; a->n_layers = 1;
-    column_pbkT_range(a);
-    a->ablate = ctx->ablate;
-    if (abs_coef) { a->abs_coef[0] = abs_coef->d; a->layer_arrays = 1; }
-    if (trans) { a->trans[0] = trans->d; a->layer_arrays = 1; }
-    a->start = range_min; a->stop = range_max; a->step = axis_step(range_min, range_max, n);
-    planck_constants(&a->pa, &a->pb);
-    const double ts = (I_in || surface_T > 0) ? surface_T : T;       // (no radiance wanted: any positive temperature will do)
-    a->surface_T = ts;
-    a->r_surface_T = uniform_rcp(ts);
-    a->pbk_surface = budget_pbkT(ts);
-    a->I_in = I_in ? I_in->d : nullptr;
-    if (I_out) {
-        a->I_out = I_out->d;
-    } else {                                                          // the kernel always writes the radiance: into scratch
+    set_term_scalars(a, 0, n_iso, P, T, depth);
+    double* radiance = buf_data(I_out);
+    if (!radiance) {                                                  // the kernel always writes the radiance: into scratch
         if ((rc = arena_reserve(ctx, ctx->ktmp, (size_t)std::max<int64_t>(n, 1) * sizeof(double)))) return rc;
-        a->I_out = (double*)ctx->ktmp.ptr;
+        radiance = (double*)ctx->ktmp.ptr;
     }
-    a->n = n; a->first = first; a->count = count;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* d_args = nullptr;
-    if ((rc = device_args(ctx, a, sizeof(ColumnStepArgs), &d_args))) return rc;
-    hipEvent_t ev = prof_begin(ctx, PROF_SWEEP);
-    launch_column_step((const ColumnStepArgs*)d_args, first, count, ctx->stream, !ctx->sweep_ieee);
-    prof_end(ctx, PROF_SWEEP, ev);
-    HIP_TRY(ctx, hipGetLastError());
-    return LBL_OK;
+    // (no radiance wanted: any positive surface temperature will do)
+    fill_frame(a, range_min, range_max, n, first, count, I_in, (I_in || surface_T > 0) ? surface_T : T, radiance);
+    if ((rc = set_layer_array(ctx, a, &a->abs_coef[0], abs_coef, "abs_coef"))) return rc;
+    if ((rc = set_layer_array(ctx, a, &a->trans[0], trans, "trans"))) return rc;
+    return launch_column_terms(ctx, PROF_SWEEP, a, n_iso, 1);
 }
 
 extern "C" int lbl_layer_sweep_dev(lbl_ctx* ctx, int n_iso, lbl_buffer* const* xsec, const int32_t* iso_mol, int n_mol,
@@ -1842,9 +1936,8 @@ extern "C" int lbl_layer_sweep_dev(lbl_ctx* ctx, int n_iso, lbl_buffer* const* x
                                    double surface_T, lbl_buffer* abs_coef, lbl_buffer* trans, lbl_buffer* I_out) try {
     if (!ctx) return fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     if (n_iso < 0 || n_iso >= kMaxColumnIso || n_mol < 0 || n_mol >= kMaxColumnIso) return fail(ctx, LBL_ERR_BAD_ARG, "at most %d isotopologues per sweep", kMaxColumnIso - 1);
-    if (n < 0) return fail(ctx, LBL_ERR_BAD_ARG, "negative n");
-    if (first < 0 || count < 0 || count > n - first) return fail(ctx, LBL_ERR_BAD_ARG, "swept range outside [0, n)");
-    if (count == 0) { first = 0; count = n; }
+    int rc;
+    if ((rc = check_range(ctx, n, &first, &count))) return rc;
     if (n_iso > 0 && (!xsec || !iso_mol)) return fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
     if (n_mol > 0 && !conc) return fail(ctx, LBL_ERR_BAD_ARG, "conc is NULL");
     if (!(T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "T must be > 0");
@@ -1853,40 +1946,35 @@ extern "C" int lbl_layer_sweep_dev(lbl_ctx* ctx, int n_iso, lbl_buffer* const* x
                                      I_in, surface_T, abs_coef, trans, I_out);
     SweepArgs a;
     memset(&a, 0, sizeof a);
-    int rc;
-    for (int i = 0; i < n_iso; ++i) {
-        if ((rc = check_buf(ctx, xsec[i], n, "xsec", true))) return rc;
-        if (iso_mol[i] < 0 || iso_mol[i] >= n_mol || (i > 0 && iso_mol[i] < iso_mol[i - 1]))
-            return fail(ctx, LBL_ERR_BAD_ARG, "iso_mol must be non-decreasing and < n_mol");
-        a.xsec[i] = xsec[i]->d;
-        a.term_conc[i] = conc[iso_mol[i]];
-        a.term_factor[i] = budget_factor(conc[iso_mol[i]], P, T);
-        a.term_flags[i] = (i == n_iso - 1 || iso_mol[i + 1] != iso_mol[i]) ? TERM_LAST_MOL : 0;
-    }
-    a.budget = !ctx->sweep_ieee; a.pbkT = budget_pbkT(T); a.pbk_surface = budget_pbkT(surface_T);
-    if ((rc = check_buf(ctx, I_in, n, "I_in", false))) return rc;
-    if ((rc = check_buf(ctx, abs_coef, n, "abs_coef", false))) return rc;
-    if ((rc = check_buf(ctx, trans, n, "trans", false))) return rc;
-    if ((rc = check_buf(ctx, I_out, n, "I_out", false))) return rc;
-    if (I_out && !I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "I_out needs I_in or surface_T > 0");
-    a.n_iso = n_iso; a.n_mol = n_mol; a.P = P; a.T = T; a.depth = depth;
+    if ((rc = add_layer_terms(ctx, &a, 0, n_iso, xsec, iso_mol, n_mol, conc, P, T, n, 0))) return rc;
+    if ((rc = check_layer_arrays(ctx, n, I_in, surface_T, abs_coef, trans, I_out))) return rc;
+    a.n_iso = n_iso; a.n_mol = n_mol;
     a.variant = (ctx->ablate & 64) ? 0 : 1;          // streaming loads and stores: every array is touched once (-4 %)
-    a.rT = uniform_rcp(T); a.r_surface_T = uniform_rcp(surface_T);
-    a.start = range_min; a.stop = range_max; a.step = axis_step(range_min, range_max, n);
-    planck_constants(&a.pa, &a.pb);
-    a.surface_T = surface_T;
-    a.I_in = I_in ? I_in->d : nullptr;
-    a.abs_coef = abs_coef ? abs_coef->d : nullptr;
-    a.trans = trans ? trans->d : nullptr;
-    a.I_out = I_out ? I_out->d : nullptr;
-    a.n = n; a.first = first; a.count = count;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipEvent_t ev = prof_begin(ctx, PROF_SWEEP);
-    launch_layer_sweep(a, ctx->stream);
-    prof_end(ctx, PROF_SWEEP, ev);
-    HIP_TRY(ctx, hipGetLastError());
-    return LBL_OK;
+    fill_layer(&a, P, T, depth, !ctx->sweep_ieee, abs_coef, trans);
+    fill_frame(&a, range_min, range_max, n, first, count, I_in, surface_T, buf_data(I_out));
+    return launch_sweep(ctx, a);
 } LBL_GUARD_END(ctx)
+
+// every line list of a layer: iso_mol in order, T and P the layer's (xsec: their cross-section arrays of n points, where they exist)
+static int check_layer_lists(lbl_ctx* ctx, int n_iso, const lbl_iso_params* iso, const int32_t* iso_mol, int n_mol, int layer,
+                             lbl_buffer* const* xsec = nullptr, int64_t n = 0) {
+    int rc;
+    if ((rc = add_layer_terms<SweepArgs>(ctx, nullptr, 0, n_iso, xsec, iso_mol, n_mol, nullptr, 0, 0, n, layer))) return rc;
+    for (int i = 0; i < n_iso; ++i)
+        if (iso[i].T != iso[0].T || iso[i].P != iso[0].P)
+            return fail(ctx, LBL_ERR_BAD_ARG, "layer %d, line list %d: T and P must be the layer's (those of its first line list)", layer, i);
+    return LBL_OK;
+}
+
+// The sweep of a layer in the output stage of its accumulate job.  on 1: the job's sum is a cross section, folded with `factor`
+// (or the IEEE chain) first; on 2: a merged job, whose sum is the absorption coefficient.
+static void fill_fused(FusedSweep* f, const lbl_grid& g, double P, double T, double depth, const lbl_buffer* I_in, double surface_T,
+                       const lbl_buffer* abs_coef, const lbl_buffer* trans, const lbl_buffer* I_out, int on, int budget, double factor) {
+    memset(f, 0, sizeof *f);
+    fill_layer(f, P, T, depth, budget, abs_coef, trans);
+    fill_frame(f, g.range_min, g.range_max, g.n_base, 0, 0, I_in, surface_T, buf_data(I_out));
+    f->on = on; f->factor = factor;
+}
 
 extern "C" int lbl_layer_step_dev(lbl_ctx* ctx, int n_iso, lbl_lines* const* lines, const lbl_iso_params* iso,
                                   const lbl_grid* grid, lbl_buffer* const* xsec, const int32_t* iso_mol, int n_mol,
@@ -1898,40 +1986,19 @@ extern "C" int lbl_layer_step_dev(lbl_ctx* ctx, int n_iso, lbl_lines* const* lin
     int rc;
     if ((rc = check_grid(ctx, grid))) return rc;
     const int64_t n = grid->n_base;
+    if ((rc = check_layer_lists(ctx, n_iso, iso, iso_mol, n_mol, 0, xsec, n))) return rc;
+    if ((rc = check_layer_arrays(ctx, n, I_in, surface_T, abs_coef, trans, I_out))) return rc;
     std::vector<double*> outs((size_t)n_iso);
     std::vector<lbl_grid> grids((size_t)n_iso, *grid);
-    for (int i = 0; i < n_iso; ++i) {
-        if ((rc = check_buf(ctx, xsec[i], n, "xsec", true))) return rc;
-        if (iso_mol[i] < 0 || iso_mol[i] >= n_mol || (i > 0 && iso_mol[i] < iso_mol[i - 1]))
-            return fail(ctx, LBL_ERR_BAD_ARG, "iso_mol must be non-decreasing and < n_mol");
-        if (iso[i].T != iso[0].T || iso[i].P != iso[0].P)
-            return fail(ctx, LBL_ERR_BAD_ARG, "line list %d: T and P must be the layer's (those of line list 0)", i);
-        outs[i] = xsec[i]->d;
-    }
-    if ((rc = check_buf(ctx, I_in, n, "I_in", false))) return rc;
-    if ((rc = check_buf(ctx, abs_coef, n, "abs_coef", false))) return rc;
-    if ((rc = check_buf(ctx, trans, n, "trans", false))) return rc;
-    if ((rc = check_buf(ctx, I_out, n, "I_out", false))) return rc;
-    if (I_out && !I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "I_out needs I_in or surface_T > 0");
+    for (int i = 0; i < n_iso; ++i) outs[(size_t)i] = xsec[i]->d;
     // One line list on the base grid: the sweep of a point runs in the accumulate kernel's output stage.
     // (A molecule without line lists before it adds 0 * conc to k in the sweep kernel: same bits.)
     const bool fusable = n_iso == 1 && (ctx->accum_variant == 3 || ctx->accum_variant == 5) && !needs_regrid(*grid) &&
                          !ctx->no_fuse;
     if (fusable) {
         FusedSweep f;
-        memset(&f, 0, sizeof f);
-        f.P = iso[0].P; f.T = iso[0].T; f.depth = depth;
-        f.rT = uniform_rcp(f.T); f.r_surface_T = uniform_rcp(surface_T);
-        f.start = grid->range_min; f.stop = grid->range_max; f.step = axis_step(grid->range_min, grid->range_max, n);
-        planck_constants(&f.pa, &f.pb);
-        f.surface_T = surface_T;
-        f.I_in = I_in ? I_in->d : nullptr;
-        f.abs_coef = abs_coef ? abs_coef->d : nullptr;
-        f.trans = trans ? trans->d : nullptr;
-        f.I_out = I_out ? I_out->d : nullptr;
-        f.n = n; f.on = 1;
-        f.budget = !ctx->sweep_ieee; f.factor = budget_factor(conc[iso_mol[0]], f.P, f.T);
-        f.pbkT = budget_pbkT(f.T); f.pbk_surface = budget_pbkT(surface_T);
+        fill_fused(&f, *grid, iso[0].P, iso[0].T, depth, I_in, surface_T, abs_coef, trans, I_out, 1, !ctx->sweep_ieee,
+                   budget_factor(conc[iso_mol[0]], iso[0].P, iso[0].T));
         return enqueue_accumulate(ctx, 1, lines, iso, grids.data(), outs.data(), false, &f, conc[iso_mol[0]]);
     }
     // several line lists, a work grid that needs the regrid kernel, or a kernel variant without the fused
@@ -1970,16 +2037,6 @@ static void merged_weights(int n_iso, const int32_t* iso_mol, const double* conc
     for (int i = 0; i < n_iso; ++i) weight[i] = std::ldexp(weight[i], -e);
 }
 
-static int check_layer_lists(lbl_ctx* ctx, int n_iso, const lbl_iso_params* iso, const int32_t* iso_mol, int n_mol, int layer) {
-    for (int i = 0; i < n_iso; ++i) {
-        if (iso_mol[i] < 0 || iso_mol[i] >= n_mol || (i > 0 && iso_mol[i] < iso_mol[i - 1]))
-            return fail(ctx, LBL_ERR_BAD_ARG, "layer %d: iso_mol must be non-decreasing and < n_mol", layer);
-        if (iso[i].T != iso[0].T || iso[i].P != iso[0].P)
-            return fail(ctx, LBL_ERR_BAD_ARG, "layer %d, line list %d: T and P must be the layer's (those of its first line list)", layer, i);
-    }
-    return LBL_OK;
-}
-
 extern "C" int lbl_layer_merged_step_dev(lbl_ctx* ctx, int n_iso, lbl_lines* const* lines, const lbl_iso_params* iso,
                                          const lbl_grid* grid, const int32_t* iso_mol, int n_mol, const double* conc,
                                          double depth, lbl_buffer* I_in, double surface_T, lbl_buffer* abs_coef,
@@ -1992,31 +2049,13 @@ extern "C" int lbl_layer_merged_step_dev(lbl_ctx* ctx, int n_iso, lbl_lines* con
     if ((rc = check_grid(ctx, grid))) return rc;
     if ((rc = check_layer_lists(ctx, n_iso, iso, iso_mol, n_mol, 0))) return rc;
     const int64_t n = grid->n_base;
-    if ((rc = check_buf(ctx, I_in, n, "I_in", false))) return rc;
-    if ((rc = check_buf(ctx, abs_coef, n, "abs_coef", false))) return rc;
-    if ((rc = check_buf(ctx, trans, n, "trans", false))) return rc;
-    if ((rc = check_buf(ctx, I_out, n, "I_out", false))) return rc;
-    if (I_out && !I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "I_out needs I_in or surface_T > 0");
+    if ((rc = check_layer_arrays(ctx, n, I_in, surface_T, abs_coef, trans, I_out))) return rc;
     if (!abs_coef && !trans && !I_out) return fail(ctx, LBL_ERR_BAD_ARG, "no output array");
     std::vector<double> weight((size_t)n_iso);
     double out_scale = 1.0;
     merged_weights(n_iso, iso_mol, conc, iso[0].P, iso[0].T, weight.data(), &out_scale);
     const int first[2] = {0, n_iso};
     MergeSpec ms{first, weight.data(), &out_scale};
-    FusedSweep f;
-    memset(&f, 0, sizeof f);
-    f.P = iso[0].P; f.T = iso[0].T; f.depth = depth;
-    f.rT = uniform_rcp(f.T); f.r_surface_T = uniform_rcp(surface_T);
-    f.start = grid->range_min; f.stop = grid->range_max; f.step = axis_step(grid->range_min, grid->range_max, n);
-    planck_constants(&f.pa, &f.pb);
-    f.surface_T = surface_T;
-    f.I_in = I_in ? I_in->d : nullptr;
-    f.abs_coef = abs_coef ? abs_coef->d : nullptr;
-    f.trans = trans ? trans->d : nullptr;
-    f.I_out = I_out ? I_out->d : nullptr;
-    f.n = n; f.on = 2;
-    f.budget = 1; f.factor = 1.0;                  // (merged jobs exist in the sweeps' default arithmetic only)
-    f.pbkT = budget_pbkT(f.T); f.pbk_surface = budget_pbkT(surface_T);
     if (!needs_regrid(*grid)) {
         double* out = nullptr;
         if (!trans && !I_out) {
@@ -2024,11 +2063,13 @@ extern "C" int lbl_layer_merged_step_dev(lbl_ctx* ctx, int n_iso, lbl_lines* con
             out = abs_coef->d;
             return enqueue_accumulate(ctx, 1, lines, iso, grid, &out, false, nullptr, 0.0, &ms);
         }
+        FusedSweep f;          // (merged jobs exist in the sweeps' default arithmetic only: budget 1, the factor is in the weights)
+        fill_fused(&f, *grid, iso[0].P, iso[0].T, depth, I_in, surface_T, abs_coef, trans, I_out, 2, 1, 1.0);
         return enqueue_accumulate(ctx, 1, lines, iso, grid, &out, false, &f, 0.0, &ms);
     }
     // a coarser work grid (dynamic resolution, pyradClasses.py:659-662, 401-405): k on the work grid, np.interp onto the base
     // grid (linear, like the sum it is applied to), then the sweep of that one array
-    double* kdst = abs_coef ? abs_coef->d : nullptr;
+    double* kdst = buf_data(abs_coef);
     if (!kdst) {
         if ((rc = arena_reserve(ctx, ctx->ktmp, (size_t)std::max<int64_t>(n, 1) * sizeof(double)))) return rc;
         kdst = (double*)ctx->ktmp.ptr;
@@ -2038,19 +2079,11 @@ extern "C" int lbl_layer_merged_step_dev(lbl_ctx* ctx, int n_iso, lbl_lines* con
     SweepArgs a;
     memset(&a, 0, sizeof a);
     a.xsec[0] = kdst; a.term_conc[0] = 1.0; a.term_factor[0] = 1.0; a.term_flags[0] = TERM_LAST_MOL;
-    a.budget = 1; a.pbkT = f.pbkT; a.pbk_surface = f.pbk_surface;
-    a.n_iso = 1; a.n_mol = 1; a.P = f.P; a.T = f.T; a.depth = depth;
+    a.n_iso = 1; a.n_mol = 1;
     a.variant = 0;                                   // (k is read here and again by the caller: no streaming hints)
-    a.rT = f.rT; a.r_surface_T = f.r_surface_T;
-    a.start = f.start; a.stop = f.stop; a.step = f.step; a.pa = f.pa; a.pb = f.pb;
-    a.surface_T = surface_T;
-    a.I_in = f.I_in; a.abs_coef = nullptr; a.trans = f.trans; a.I_out = f.I_out;
-    a.n = n; a.first = 0; a.count = n;
-    hipEvent_t ev = prof_begin(ctx, PROF_SWEEP);
-    launch_layer_sweep(a, ctx->stream);
-    prof_end(ctx, PROF_SWEEP, ev);
-    HIP_TRY(ctx, hipGetLastError());
-    return LBL_OK;
+    fill_layer(&a, iso[0].P, iso[0].T, depth, 1, nullptr, trans);
+    fill_frame(&a, grid->range_min, grid->range_max, n, 0, n, I_in, surface_T, buf_data(I_out));
+    return launch_sweep(ctx, a);
 } LBL_GUARD_END(ctx)
 
 extern "C" int lbl_layers_merged_accumulate_dev(lbl_ctx* ctx, int n_layers, const int32_t* n_iso, lbl_lines* const* lines,
@@ -2086,55 +2119,38 @@ extern "C" int lbl_layers_merged_accumulate_dev(lbl_ctx* ctx, int n_layers, cons
     return enqueue_accumulate(ctx, n_layers, lines, iso, grid, outs.data(), false, nullptr, 0.0, &ms);
 } LBL_GUARD_END(ctx)
 
+// lbl_column_fold_dev's checks and its block: one term per layer, the "cross section" the layer's absorption coefficient, its factor 1
+static int build_fold(lbl_ctx* ctx, ColumnStepArgs* a, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                      const double* depth, double range_min, double range_max, int64_t n, int64_t first, int64_t count,
+                      lbl_buffer* I_in, double surface_T, lbl_buffer* const* trans, lbl_buffer* I_out) {
+    if (n_layers < 0 || n_layers > kMaxLayers) return fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
+    int rc;
+    if ((rc = check_range(ctx, n, &first, &count))) return rc;
+    if (n_layers > 0 && (!abs_coef || !T || !depth)) return fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if (ctx->sweep_ieee) return fail(ctx, LBL_ERR_BAD_ARG, "the fold over absorption coefficients exists in the sweeps' default arithmetic only: with \"sweep_ieee_divisions\" 1 use lbl_column_step_dev on the cross sections");
+    if ((rc = check_column_arrays(ctx, n, I_in, surface_T, I_out))) return rc;
+    fill_frame(a, range_min, range_max, n, first, count, I_in, surface_T, I_out->d);
+    for (int l = 0; l < n_layers; ++l) {
+        if ((rc = check_buf(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
+        if (!(T[l] > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
+        a->xsec[l] = abs_coef[l]->d;
+        a->term_conc[l] = 1.0; a->term_factor[l] = 1.0;
+        a->term_flags[l] = TERM_LAST_MOL | TERM_LAST_LAYER;
+        set_term_scalars(a, l, l + 1, 0.0, T[l], depth[l]);
+        if (trans && (rc = set_layer_array(ctx, a, &a->trans[l], trans[l], "trans"))) return rc;
+    }
+    return LBL_OK;
+}
+
 extern "C" int lbl_column_fold_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
                                    const double* depth, double range_min, double range_max, int64_t n, int64_t first,
                                    int64_t count, lbl_buffer* I_in, double surface_T, lbl_buffer* const* trans,
                                    lbl_buffer* I_out) try {
     if (!ctx) return fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
-    if (n_layers < 0 || n_layers > kMaxLayers) return fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
-    if (n < 0) return fail(ctx, LBL_ERR_BAD_ARG, "negative n");
-    if (first < 0 || count < 0 || count > n - first) return fail(ctx, LBL_ERR_BAD_ARG, "swept range outside [0, n)");
-    if (count == 0) { first = 0; count = n; }
-    if (n_layers > 0 && (!abs_coef || !T || !depth)) return fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
-    if (ctx->sweep_ieee) return fail(ctx, LBL_ERR_BAD_ARG, "the fold over absorption coefficients exists in the sweeps' default arithmetic only: with \"sweep_ieee_divisions\" 1 use lbl_column_step_dev on the cross sections");
-    int rc;
-    if ((rc = check_buf(ctx, I_out, n, "I_out", true))) return rc;
-    if ((rc = check_buf(ctx, I_in, n, "I_in", false))) return rc;
-    if (!I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "need I_in or surface_T > 0");
     std::vector<char> blk(sizeof(ColumnStepArgs), 0);
     ColumnStepArgs* a = (ColumnStepArgs*)blk.data();
-    for (int l = 0; l < n_layers; ++l) {
-        if ((rc = check_buf(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
-        if (!(T[l] > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
-        // one term per layer: the "cross section" is the layer's absorption coefficient, its factor 1
-        a->xsec[l] = abs_coef[l]->d;
-        a->term_conc[l] = 1.0; a->term_factor[l] = 1.0;
-        a->term_flags[l] = TERM_LAST_MOL | TERM_LAST_LAYER;
-        a->term_P[l] = 0.0; a->term_T[l] = T[l]; a->term_depth[l] = depth[l];
-        a->term_rT[l] = uniform_rcp(T[l]);
-        a->term_pbkT[l] = budget_pbkT(T[l]);
-        if (trans && trans[l]) { if ((rc = check_buf(ctx, trans[l], n, "trans", true))) return rc; a->trans[l] = trans[l]->d; a->layer_arrays = 1; }
-    }
-    a->n_terms = n_layers;
-    column_pbkT_range(a);
-    a->ablate = ctx->ablate;
-    a->n_layers = n_layers;
-    a->start = range_min; a->stop = range_max; a->step = axis_step(range_min, range_max, n);
-    planck_constants(&a->pa, &a->pb);
-    a->surface_T = surface_T;
-    a->r_surface_T = uniform_rcp(surface_T);
-    a->pbk_surface = budget_pbkT(surface_T);
-    a->I_in = I_in ? I_in->d : nullptr;
-    a->I_out = I_out->d;
-    a->n = n; a->first = first; a->count = count;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* d_args = nullptr;
-    if ((rc = device_args(ctx, a, sizeof(ColumnStepArgs), &d_args))) return rc;
-    hipEvent_t ev = prof_begin(ctx, PROF_COLUMN);
-    launch_column_step((const ColumnStepArgs*)d_args, first, count, ctx->stream, 1, 1);
-    prof_end(ctx, PROF_COLUMN, ev);
-    HIP_TRY(ctx, hipGetLastError());
-    return LBL_OK;
+    const int rc = build_fold(ctx, a, n_layers, abs_coef, T, depth, range_min, range_max, n, first, count, I_in, surface_T, trans, I_out);
+    return rc ? rc : launch_column_terms(ctx, PROF_COLUMN, a, n_layers, n_layers, 1);
 } LBL_GUARD_END(ctx)
 
 // ---- resident column (ABI 5): the argument blocks of a column's merged accumulate jobs and of its fold, kept on the C side ----
@@ -2229,6 +2245,14 @@ extern "C" int lbl_column_transmission(lbl_column* col, const uint8_t* due, lbl_
     if (pieces < 1 || pieces > 64) return fail(ctx, LBL_ERR_BAD_ARG, "1..64 pieces");
     int rc;
     if ((rc = check_buf(ctx, I_out, n, "I_out", true))) return rc;
+    // the fold's block, and with it every refusal of the fold, before anything is enqueued
+    std::vector<double> T((size_t)nl);
+    for (int l = 0; l < nl; ++l) T[(size_t)l] = col->iso[(size_t)col->iso_first[(size_t)l]].T;
+    std::vector<char> blk(sizeof(ColumnStepArgs), 0);
+    ColumnStepArgs* fold = (ColumnStepArgs*)blk.data();
+    if ((rc = build_fold(ctx, fold, nl, col->abs_coef.data(), T.data(), col->depth.data(), col->grid[0].range_min,
+                         col->grid[0].range_max, n, 0, 0, I_in, surface_T, nullptr, I_out)))
+        return rc;
     // the layers that are due: one merged accumulate job each, all in one launch sequence
     std::vector<int32_t> d_niso, d_nmol, d_isomol;
     std::vector<lbl_lines*> d_lines;
@@ -2252,16 +2276,13 @@ extern "C" int lbl_column_transmission(lbl_column* col, const uint8_t* due, lbl_
         (rc = lbl_layers_merged_accumulate_dev(ctx, (int)d_niso.size(), d_niso.data(), d_lines.data(), d_iso.data(), d_grid.data(),
                                                d_isomol.data(), d_nmol.data(), d_conc.data(), d_k.data())))
         return rc;
-    std::vector<double> T((size_t)nl);
-    for (int l = 0; l < nl; ++l) T[(size_t)l] = col->iso[(size_t)col->iso_first[(size_t)l]].T;
     // the fold in pieces (multiples of four points: the fold kernel's vector width), each piece's outgoing spectrum
     // downloaded beside the next piece
     const int64_t step = std::max<int64_t>((((n + pieces - 1) / pieces) + 3) & ~(int64_t)3, 4);
     for (int64_t lo = 0; lo < n; lo += step) {
         const int64_t cnt = std::min(step, n - lo);
-        if ((rc = lbl_column_fold_dev(ctx, nl, col->abs_coef.data(), T.data(), col->depth.data(), col->grid[0].range_min,
-                                      col->grid[0].range_max, n, lo, cnt, I_in, surface_T, nullptr, I_out)))
-            return rc;
+        fold->first = lo; fold->count = cnt;
+        if ((rc = launch_column_terms(ctx, PROF_COLUMN, fold, nl, nl, 1))) return rc;
         if (host_out && (rc = lbl_buffer_download_async(I_out, host_out + lo, cnt, lo))) return rc;
     }
     return LBL_OK;
@@ -2272,41 +2293,25 @@ extern "C" int lbl_column_sweep_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
                                     lbl_buffer* I_in, double surface_T, lbl_buffer* I_out) try {
     if (!ctx) return fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     if (n_layers < 0 || n_layers > kMaxLayers) return fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
-    if (n < 0) return fail(ctx, LBL_ERR_BAD_ARG, "negative n");
-    if (first < 0 || count < 0 || count > n - first) return fail(ctx, LBL_ERR_BAD_ARG, "swept range outside [0, n)");
-    if (count == 0) { first = 0; count = n; }
-    if (n_layers > 0 && (!trans || !layer_T)) return fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
     int rc;
-    if ((rc = check_buf(ctx, I_out, n, "I_out", true))) return rc;
-    if ((rc = check_buf(ctx, I_in, n, "I_in", false))) return rc;
-    if (!I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "need I_in or surface_T > 0");
+    if ((rc = check_range(ctx, n, &first, &count))) return rc;
+    if (n_layers > 0 && (!trans || !layer_T)) return fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if ((rc = check_column_arrays(ctx, n, I_in, surface_T, I_out))) return rc;
     std::vector<char> blk(sizeof(ColumnArgs), 0);
     ColumnArgs* a = (ColumnArgs*)blk.data();
     for (int l = 0; l < n_layers; ++l) {
         if ((rc = check_buf(ctx, trans[l], n, "trans", true))) return rc;
-        if (!(layer_T[l] > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "layer_T must be > 0");
+        if (!(layer_T[l] > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
         a->trans[l] = trans[l]->d;
         a->layer_T[l] = layer_T[l];
         a->r_layer_T[l] = uniform_rcp(layer_T[l]);
         a->pbkT[l] = budget_pbkT(layer_T[l]);
     }
     a->n_layers = n_layers;
-    a->start = range_min; a->stop = range_max; a->step = axis_step(range_min, range_max, n);
-    planck_constants(&a->pa, &a->pb);
-    a->surface_T = surface_T;
-    a->r_surface_T = uniform_rcp(surface_T);
-    a->pbk_surface = budget_pbkT(surface_T);
-    a->I_in = I_in ? I_in->d : nullptr;
-    a->I_out = I_out->d;
-    a->n = n; a->first = first; a->count = count;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* d_args = nullptr;
-    if ((rc = device_args(ctx, a, sizeof(ColumnArgs), &d_args))) return rc;
-    hipEvent_t ev = prof_begin(ctx, PROF_COLUMN);
-    launch_column_sweep((const ColumnArgs*)d_args, count, ctx->stream, !ctx->sweep_ieee);
-    prof_end(ctx, PROF_COLUMN, ev);
-    HIP_TRY(ctx, hipGetLastError());
-    return LBL_OK;
+    fill_frame(a, range_min, range_max, n, first, count, I_in, surface_T, I_out->d);
+    return upload_and_launch(ctx, PROF_COLUMN, a, [&](const ColumnArgs* d) {
+        launch_column_sweep(d, count, ctx->stream, !ctx->sweep_ieee);
+    });
 } LBL_GUARD_END(ctx)
 
 extern "C" int lbl_column_step_dev(lbl_ctx* ctx, int n_layers, const int32_t* n_iso, lbl_buffer* const* xsec,
@@ -2316,36 +2321,26 @@ extern "C" int lbl_column_step_dev(lbl_ctx* ctx, int n_layers, const int32_t* n_
                                    lbl_buffer* const* abs_coef, lbl_buffer* const* trans, lbl_buffer* I_out) try {
     if (!ctx) return fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     if (n_layers < 0 || n_layers > kMaxLayers) return fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
-    if (n < 0) return fail(ctx, LBL_ERR_BAD_ARG, "negative n");
-    if (first < 0 || count < 0 || count > n - first) return fail(ctx, LBL_ERR_BAD_ARG, "swept range outside [0, n)");
-    if (count == 0) { first = 0; count = n; }
-    if (n_layers > 0 && (!n_iso || !n_mol || !P || !T || !depth)) return fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
     int rc;
-    if ((rc = check_buf(ctx, I_out, n, "I_out", true))) return rc;
-    if ((rc = check_buf(ctx, I_in, n, "I_in", false))) return rc;
-    if (!I_in && !(surface_T > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "need I_in or surface_T > 0");
+    if ((rc = check_range(ctx, n, &first, &count))) return rc;
+    if (n_layers > 0 && (!n_iso || !n_mol || !P || !T || !depth)) return fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if ((rc = check_column_arrays(ctx, n, I_in, surface_T, I_out))) return rc;
     std::vector<char> blk(sizeof(ColumnStepArgs), 0);
     ColumnStepArgs* a = (ColumnStepArgs*)blk.data();
+    fill_frame(a, range_min, range_max, n, first, count, I_in, surface_T, I_out->d);
     int iso0 = 0, mol0 = 0, nt = 0;
     for (int l = 0; l < n_layers; ++l) {
         if (n_iso[l] < 0 || n_mol[l] < 0 || nt + n_iso[l] + 1 > kMaxColumnIso || mol0 + n_mol[l] > kMaxColumnIso)
             return fail(ctx, LBL_ERR_BAD_ARG, "at most %d isotopologues per column", kMaxColumnIso - 1);
         if (!(T[l] > 0)) return fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
         if ((n_iso[l] > 0 && (!xsec || !iso_mol)) || (n_mol[l] > 0 && !conc)) return fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
-        // the layer's terms: one per cross-section array, molecule after molecule (a molecule without line
-        // lists adds 0 to the absorption coefficient: no term; a layer without any gets one empty term)
-        for (int i = 0; i < n_iso[l]; ++i) {
-            if ((rc = check_buf(ctx, xsec[iso0 + i], n, "xsec", true))) return rc;
-            const int32_t m = iso_mol[iso0 + i];
-            if (m < 0 || m >= n_mol[l] || (i > 0 && m < iso_mol[iso0 + i - 1]))
-                return fail(ctx, LBL_ERR_BAD_ARG, "layer %d: iso_mol must be non-decreasing and < n_mol", l);
-            a->xsec[nt] = xsec[iso0 + i]->d;
-            a->term_conc[nt] = conc[mol0 + m];
-            a->term_factor[nt] = budget_factor(conc[mol0 + m], P[l], T[l]);
-            a->term_flags[nt] = (i == n_iso[l] - 1 || iso_mol[iso0 + i + 1] != m) ? TERM_LAST_MOL : 0;
-            ++nt;
-        }
-        if (n_iso[l] == 0) {
+        // the layer's terms (a molecule without line lists adds 0 to the absorption coefficient: no term; a layer
+        // without any gets one empty term)
+        const int t0 = nt;
+        if (n_iso[l] > 0) {
+            if ((rc = add_layer_terms(ctx, a, nt, n_iso[l], xsec + iso0, iso_mol + iso0, n_mol[l], conc + mol0, P[l], T[l], n, l))) return rc;
+            nt += n_iso[l];
+        } else {
             // a layer without line lists: one term that reads zeros (grown on first use; absorbs nothing)
             if ((rc = arena_reserve(ctx, ctx->zeros, (size_t)n * sizeof(double)))) return rc;
             if (ctx->zeros_set < ctx->zeros.cap) {
@@ -2355,35 +2350,12 @@ extern "C" int lbl_column_step_dev(lbl_ctx* ctx, int n_layers, const int32_t* n_
             a->xsec[nt] = (const double*)ctx->zeros.ptr; a->term_conc[nt] = 0.0; a->term_flags[nt] = TERM_LAST_MOL; ++nt;
         }
         a->term_flags[nt - 1] |= TERM_LAST_LAYER;
-        for (int t = nt - std::max(n_iso[l], 1); t < nt; ++t) {
-            a->term_P[t] = P[l]; a->term_T[t] = T[l]; a->term_depth[t] = depth[l];
-            a->term_rT[t] = uniform_rcp(T[l]);
-            a->term_pbkT[t] = budget_pbkT(T[l]);
-        }
-        if (abs_coef && abs_coef[l]) { if ((rc = check_buf(ctx, abs_coef[l], n, "abs_coef", true))) return rc; a->abs_coef[l] = abs_coef[l]->d; a->layer_arrays = 1; }
-        if (trans && trans[l]) { if ((rc = check_buf(ctx, trans[l], n, "trans", true))) return rc; a->trans[l] = trans[l]->d; a->layer_arrays = 1; }
+        set_term_scalars(a, t0, nt, P[l], T[l], depth[l]);
+        if (abs_coef && (rc = set_layer_array(ctx, a, &a->abs_coef[l], abs_coef[l], "abs_coef"))) return rc;
+        if (trans && (rc = set_layer_array(ctx, a, &a->trans[l], trans[l], "trans"))) return rc;
         iso0 += n_iso[l]; mol0 += n_mol[l];
     }
-    a->n_terms = nt;
-    column_pbkT_range(a);
-    a->ablate = ctx->ablate;
-    a->n_layers = n_layers;
-    a->start = range_min; a->stop = range_max; a->step = axis_step(range_min, range_max, n);
-    planck_constants(&a->pa, &a->pb);
-    a->surface_T = surface_T;
-    a->r_surface_T = uniform_rcp(surface_T);
-    a->pbk_surface = budget_pbkT(surface_T);
-    a->I_in = I_in ? I_in->d : nullptr;
-    a->I_out = I_out->d;
-    a->n = n; a->first = first; a->count = count;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* d_args = nullptr;
-    if ((rc = device_args(ctx, a, sizeof(ColumnStepArgs), &d_args))) return rc;
-    hipEvent_t ev = prof_begin(ctx, PROF_COLUMN);
-    launch_column_step((const ColumnStepArgs*)d_args, first, count, ctx->stream, !ctx->sweep_ieee);
-    prof_end(ctx, PROF_COLUMN, ev);
-    HIP_TRY(ctx, hipGetLastError());
-    return LBL_OK;
+    return launch_column_terms(ctx, PROF_COLUMN, a, nt, n_layers);
 } LBL_GUARD_END(ctx)
 
 extern "C" int lbl_sum_dev(lbl_ctx* ctx, int n_in, lbl_buffer* const* in, int64_t n, lbl_buffer* out) try {

@@ -28,6 +28,7 @@ extern int device_count;            // what hipGetDeviceCount reports (the drive
 extern long long fail_malloc_at;    // the n-th hipMalloc from now fails with hipErrorOutOfMemory (-1: never)
 extern long long clock;
 extern long long live_allocs, live_streams, live_events, live_graphs, live_host;
+extern long long launches;          // stand-in launchers entered so far (mock_kernels.cpp)
 }
 
 inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "success" : e == hipErrorOutOfMemory ? "out of memory (mock)" : "error (mock)"; }

@@ -17,6 +17,7 @@ int device_count = 1;
 long long fail_malloc_at = -1;
 long long clock = 0;
 long long live_allocs = 0, live_streams = 0, live_events = 0, live_graphs = 0, live_host = 0;
+long long launches = 0;      // stand-in launchers entered (the driver: a refused call must not have enqueued anything)
 }
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "mock kernel: violated: %s (%s:%d)\n", #cond, __FILE__, __LINE__); abort(); } } while (0)
@@ -48,6 +49,7 @@ static void prep_one(const PrepJob& J, int i, HotRec& r, ColdRec& c, int32_t& ci
 // line_prep_kernel: grid (ceil(max_lines / 256), n_jobs): job j writes hot / cold / cidx [0, n_lines) and block_counts[bx * 3 + k]
 // for EVERY block bx of the grid (blocks beyond its own lines store zeros); a list of a merged job is skipped
 void launch_line_prep(const PrepJob* d_jobs, int n_jobs, int max_lines, hipStream_t) {
+    ++mockhip::launches;
     if (n_jobs <= 0 || max_lines <= 0) return;
     // (self-test of the harness, tests/test_host_shim_asan_cpu.py: with SHIM_INJECT_OVERRUN set the stand-in writes one block
     // of counters more than the kernel does - AddressSanitizer must report it)
@@ -66,6 +68,7 @@ void launch_line_prep(const PrepJob* d_jobs, int n_jobs, int max_lines, hipStrea
 // line_prep_merged_kernel: job m writes its record arrays [0, n_total) from src[0, n_total) and, for its blocks [0, blocks),
 // block_counts[bx * 3 + k] of each of its lists
 void launch_line_prep_merged(const PrepJob* d_lists, const MergedPrep* d_jobs, int n_jobs, int max_total, hipStream_t) {
+    ++mockhip::launches;
     if (n_jobs <= 0 || max_total <= 0) return;
     for (int m = 0; m < n_jobs; ++m) {
         const MergedPrep& M = d_jobs[m];
@@ -88,12 +91,14 @@ void launch_line_prep_merged(const PrepJob* d_lists, const MergedPrep* d_jobs, i
 
 void launch_line_quantities(const PrepJob* d_job, int n_lines, long long* index, double* lhw, double* ghw, double* intensity,
                             int32_t* regime, hipStream_t) {
+    ++mockhip::launches;
     for (int i = 0; i < n_lines; ++i) { index[i] = d_job->cidx[i]; lhw[i] = 0.07; ghw[i] = 7e-4; intensity[i] = d_job->sw[i]; regime[i] = 1; }
 }
 
 // centre_index_kernel + merge_rank_kernel: every list writes tmp_cidx[0, n_lines); every line of a job writes one entry of
 // src_of_job[0, total lines of the job): the inverse of the stable merge, ties by list
 void launch_merge_ranks(const MergeList* d_lists, int n_lists, int max_lines, hipStream_t) {
+    ++mockhip::launches;
     for (int a = 0; a < n_lists; ++a) {
         const MergeList& A = d_lists[a];
         CHECK(A.n_lines <= max_lines && A.job_first >= 0 && A.job_first + A.job_count <= n_lists && a >= A.job_first && a < A.job_first + A.job_count);
@@ -120,6 +125,7 @@ void launch_merge_ranks(const MergeList* d_lists, int n_lists, int max_lines, hi
 void launch_schedule_build(const SchedJob* d_jobs, int n_jobs, int total_spans, int total_tiles, int R, int spans_per_tile,
                            long long, double, double, double, double, int n_cu, int32_t* tabs, void* scratch, int2* worklist,
                            hipStream_t, int, bool xcd_pack, int, int, int) {
+    ++mockhip::launches;
     if (total_spans <= 0 || total_tiles <= 0) return;
     CHECK(sched_device_supported(total_tiles, n_cu));
     memset(scratch, 0, sched_scratch_bytes(total_tiles));
@@ -185,6 +191,7 @@ static void accumulate_common(const AccumJob* d_jobs, int n_jobs, int max_tiles,
 
 void launch_accumulate(const AccumJob* d_jobs, int n_jobs, int max_tiles, int R, int LS, int variant, const int2* worklist,
                        int total_tiles, hipStream_t, int, int gauss_run) {
+    ++mockhip::launches;
     if (n_jobs <= 0 || max_tiles <= 0) return;
     CHECK((R == 1 || R == 2 || R == 4 || R == 8) && (LS == 1 || LS == 2 || LS == 4 || LS == 8) && (gauss_run == 16 || gauss_run == 32));
     CHECK(gauss_run == 16 || (variant >= 5 && R == 4 && LS == 1));
@@ -193,13 +200,14 @@ void launch_accumulate(const AccumJob* d_jobs, int n_jobs, int max_tiles, int R,
 
 void launch_accumulate_skew(const AccumJob* d_jobs, int n_jobs, int max_tiles, int R, const int2* worklist, int total_tiles,
                             hipStream_t, int LS) {
+    ++mockhip::launches;
     if (n_jobs <= 0 || max_tiles <= 0) return;
     CHECK((R == 1 || R == 2 || R == 4 || R == 8) && (LS == 1 || (R == 8 && (LS == 2 || LS == 4))));
     accumulate_common(d_jobs, n_jobs, max_tiles, accumulate_tile_points(R, LS, 3), 64 * R, worklist, total_tiles);
 }
 
 int balanced_workers(int, int) { return 0; }
-void launch_accumulate_balanced(const AccumJob*, int, int, int, int, SpanRec*, unsigned int*, unsigned long long*, double*, hipStream_t) {}
+void launch_accumulate_balanced(const AccumJob*, int, int, int, int, SpanRec*, unsigned int*, unsigned long long*, double*, hipStream_t) { ++mockhip::launches; }
 
 void accumulate_far_field_params(int R, int* far_half_spans, double* far_cost, int) {
     *far_half_spans = 4;
@@ -208,6 +216,7 @@ void accumulate_far_field_params(int R, int* far_half_spans, double* far_cost, i
 
 // regrid_kernel: reads work[0, n_work), writes out[0, n_base)
 void launch_regrid(const double* work, long long n_work, double* out, long long n_base, double, double, hipStream_t) {
+    ++mockhip::launches;
     if (n_base <= 0) return;
     touch(work, 0, n_work);
     for (long long j = 0; j < n_base; ++j) out[j] = 0.0;
@@ -215,6 +224,7 @@ void launch_regrid(const double* work, long long n_work, double* out, long long 
 
 // layer_sweep_kernel: reads xsec[i][first, first + count) of its n_iso terms, writes abs_coef / trans / I_out there
 void launch_layer_sweep(const SweepArgs& a, hipStream_t) {
+    ++mockhip::launches;
     CHECK(a.n_iso >= 0 && a.n_iso <= kMaxIso && a.first >= 0 && a.count >= 0 && a.first + a.count <= a.n);
     for (int i = 0; i < a.n_iso; ++i) touch(a.xsec[i], a.first, a.count);
     if (a.I_in) touch(a.I_in, a.first, a.count);
@@ -227,6 +237,7 @@ void launch_layer_sweep(const SweepArgs& a, hipStream_t) {
 
 // column_step_kernel: reads every term's array over [first, first + count), writes I_out there and the layers' optional arrays
 void launch_column_step(const ColumnStepArgs* d_args, long long first, long long count, hipStream_t, int, int) {
+    ++mockhip::launches;
     if (count <= 0) return;
     const ColumnStepArgs& A = *d_args;
     CHECK(A.n_terms >= 0 && A.n_terms <= kMaxColumnIso && A.n_layers >= 0 && A.n_layers <= kMaxLayers && first >= 0 && first + count <= A.n);
@@ -252,6 +263,7 @@ void launch_column_step(const ColumnStepArgs* d_args, long long first, long long
 }
 
 void launch_column_sweep(const ColumnArgs* d_args, long long count, hipStream_t, int) {
+    ++mockhip::launches;
     if (count <= 0) return;
     const ColumnArgs& A = *d_args;
     CHECK(A.n_layers >= 0 && A.n_layers <= kMaxLayers && A.first >= 0 && A.count == count && A.first + A.count <= A.n);
@@ -260,16 +272,18 @@ void launch_column_sweep(const ColumnArgs* d_args, long long count, hipStream_t,
     for (long long j = A.first; j < A.first + A.count; ++j) A.I_out[j] = 0.0;
 }
 
-void launch_planck(double* out, long long n, double, double, double, double, double, double, hipStream_t) { for (long long j = 0; j < n; ++j) out[j] = 1.0; }
+void launch_planck(double* out, long long n, double, double, double, double, double, double, hipStream_t) { ++mockhip::launches; for (long long j = 0; j < n; ++j) out[j] = 1.0; }
 
 // band_partial_kernel + band_final_kernel: partial[band_partial_count(n)], result[1]
 void launch_band_integral(const double* y, long long n, double* partial, double* result, hipStream_t) {
+    ++mockhip::launches;
     touch(y, 0, n);
     for (int b = 0; b < band_partial_count(n); ++b) partial[b] = 0.0;
     result[0] = 0.0;
 }
 
 void launch_sum(const SumArgs& a, hipStream_t) {
+    ++mockhip::launches;
     CHECK(a.n_in >= 0 && a.n_in <= kMaxIso);
     for (int i = 0; i < a.n_in; ++i) touch(a.in[i], 0, a.n);
     for (long long j = 0; j < a.n; ++j) a.out[j] = 0.0;
@@ -277,6 +291,7 @@ void launch_sum(const SumArgs& a, hipStream_t) {
 
 // gather_compact_kernel: rank r's `count[r]` doubles from gathered[r * slot ...) to out[first[r] ...)
 void launch_gather_compact(const CompactArgs& a, long long max_count, hipStream_t) {
+    ++mockhip::launches;
     CHECK(a.world >= 1 && a.world <= kMaxRanks);
     for (int r = 0; r < a.world; ++r) {
         CHECK(a.count[r] <= max_count && a.count[r] <= a.slot);
@@ -285,6 +300,7 @@ void launch_gather_compact(const CompactArgs& a, long long max_count, hipStream_
 }
 
 void launch_optical(const double* trans, long long n, int kind, double* out, hipStream_t) {
+    ++mockhip::launches;
     CHECK(kind >= 0 && kind <= 2);
     for (long long j = 0; j < n; ++j) out[j] = trans[j];
 }
@@ -292,6 +308,7 @@ void launch_optical(const double* trans, long long n, int kind, double* out, hip
 // line_survey_kernel: reads nu / sw [0, n_lines), adds into out[0, n_base)
 void launch_line_survey(const double* nu, const double* sw, int n_lines, double range_min, double resolution, double* out,
                         long long n_base, hipStream_t) {
+    ++mockhip::launches;
     for (int i = 0; i < n_lines; ++i) {
         const long long c = centre_index(nu[i], range_min, resolution);
         if (c >= 0 && c < n_base) out[c] += sw[i];

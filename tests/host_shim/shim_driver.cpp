@@ -25,6 +25,8 @@ static bool coin(double p = 0.5) { return frand(0, 1) < p; }
 // a call that may be refused (bad argument on purpose, injected allocation failure): any status is fine, a crash or a sanitizer report is not
 static long long g_site_ok[1024], g_site_no[1024];
 #define MAY(call) do { int rc_ = (call); ++n_calls; if (rc_ != LBL_OK) { ++n_refused; ++g_site_no[__LINE__ % 1024]; if (getenv("SHIM_VERBOSE")) fprintf(stderr, "line %d refused %d: %s\n", __LINE__, rc_, lbl_last_error(ctx)); } else ++g_site_ok[__LINE__ % 1024]; } while (0)
+// ... and one that must be refused before it has enqueued anything: no stand-in launcher was entered
+#define REFUSED_UNLAUNCHED(call) do { const long long l0_ = mockhip::launches; REFUSED(call); if (mockhip::launches != l0_) { fprintf(stderr, "%s:%d: %s entered %lld launchers before it refused\n", __FILE__, __LINE__, #call, mockhip::launches - l0_); exit(3); } } while (0)
 #define REFUSED(call) do { int rc_ = (call); ++n_calls; ++n_refused; if (rc_ == LBL_OK) { fprintf(stderr, "%s:%d: %s was accepted\n", __FILE__, __LINE__, #call); exit(3); } } while (0)
 
 struct Cell {
@@ -82,10 +84,13 @@ static const struct { const char* key; std::vector<int> good; int bad; } kOption
     {"layer_step_fused", {0, 1}, 2},
 };
 
+static int g_ieee = 0;      // the context's "sweep_ieee_divisions", for the checks that switch it and put it back
 static void random_options(lbl_ctx* ctx, double p) {
     for (const auto& o : kOptions) {
         if (!coin(p)) continue;
-        MUST(lbl_set_option(ctx, o.key, o.good[(size_t)urand(0, (int)o.good.size() - 1)]));
+        const int value = o.good[(size_t)urand(0, (int)o.good.size() - 1)];
+        MUST(lbl_set_option(ctx, o.key, value));
+        if (!strcmp(o.key, "sweep_ieee_divisions")) g_ieee = value;
         if (coin(0.1)) REFUSED(lbl_set_option(ctx, o.key, o.bad));
     }
     // (the all-direct scalar kernels and positional orders are slow paths on a GPU, not here: everything is fair game)
@@ -96,6 +101,7 @@ static void default_options(lbl_ctx* ctx) {
     const char* keys[] = {"accum_points_per_lane", "accum_line_split", "accum_xcd_chunks", "accum_far_min_window", "accum_gauss_run", "accum_skew_line_split",
                           "accuracy", "sweep_ieee_divisions"};
     for (const char* k : keys) MUST(lbl_set_option(ctx, k, 0));
+    g_ieee = 0;
     MUST(lbl_set_option(ctx, "accum_variant", 5)); MUST(lbl_set_option(ctx, "accum_longest_first", 4)); MUST(lbl_set_option(ctx, "accum_tile_order", 1));
     MUST(lbl_set_option(ctx, "accum_skew", 1)); MUST(lbl_set_option(ctx, "accum_skew_points_per_lane", 8)); MUST(lbl_set_option(ctx, "accum_xcd_tolerance", 3));
     MUST(lbl_set_option(ctx, "accum_xcd_pack", 1)); MUST(lbl_set_option(ctx, "schedule_build", 1)); MUST(lbl_set_option(ctx, "layer_step_fused", 1));
@@ -104,6 +110,7 @@ static void default_options(lbl_ctx* ctx) {
 static void one_round(int round) {
     lbl_ctx* ctx = nullptr;
     MUST(lbl_ctx_create(0, &ctx));
+    g_ieee = 0;
     { lbl_ctx* none = nullptr; int rc = lbl_ctx_create(5, &none); ++n_calls; ++n_refused; if (rc == LBL_OK) exit(3); }
     char name[64]; int n_cu = 0; int64_t hbm = 0;
     MUST(lbl_device_info(ctx, name, sizeof name, &n_cu, &hbm));
@@ -212,6 +219,15 @@ static void one_round(int round) {
                 REFUSED(lbl_column_set_layer(col, nl, c_lines.data(), c_iso.data(), &c_grid[0], c_conc.data(), 55.0, c_k[0]));
                 REFUSED(lbl_column_transmission(col, nullptr, nullptr, 288.0, I, (double*)host, 0));
                 MAY(lbl_column_transmission(col, nullptr, nullptr, 288.0, I, (double*)host, 3));
+                {   // every refusal of the call comes before its first launch, the due layers' accumulate jobs included
+                    lbl_buffer* shorty = buffer(std::max<int64_t>(n - 1, 0));
+                    if (n > 0) REFUSED_UNLAUNCHED(lbl_column_transmission(col, nullptr, shorty, 0.0, I, (double*)host, 2));
+                    if (n > 0) REFUSED_UNLAUNCHED(lbl_column_transmission(col, nullptr, nullptr, 288.0, shorty, (double*)host, 2));
+                    REFUSED_UNLAUNCHED(lbl_column_transmission(col, nullptr, nullptr, 0.0, I, (double*)host, 2));
+                    MUST(lbl_set_option(ctx, "sweep_ieee_divisions", 1));
+                    REFUSED_UNLAUNCHED(lbl_column_transmission(col, nullptr, Iin, 288.0, I, (double*)host, 2));
+                    MUST(lbl_set_option(ctx, "sweep_ieee_divisions", g_ieee));
+                }
                 MUST(lbl_download_wait(ctx));
                 if (coin(0.2)) REFUSED(lbl_ctx_destroy(ctx));                   // live objects: the context stays
                 MUST(lbl_column_destroy(col));
