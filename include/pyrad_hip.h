@@ -93,6 +93,8 @@ int lbl_abi_version(void);
  *   "arrays_per_column"     terms of lbl_column_step_dev: 511      "layers_per_column": 128      "jobs_per_batch": LBL_MAX_JOBS
  *   "flux_angles"           angles of lbl_column_flux_dev: 8      "flux_bands": bands of lbl_column_flux_dev: 64
  *   "jacobian_terms"        molecule terms of lbl_column_jacobian_dev: 512
+ *   "ils_rows"              rows of lbl_ils_convolve_dev: 512      "ils_channels": its channels: 65536
+ *   "ils_table"             values of its tabulated line shape: 4096
  * Unknown name: LBL_ERR_BAD_ARG. */
 int lbl_limit(const char* name, int64_t* value);
 int lbl_device_count(int* count);
@@ -419,6 +421,39 @@ int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_c
                             int n_bands, const int64_t* band_first, const int64_t* band_count,
                             int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
                             lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra);
+
+/* ---- instrument channels (beyond the reference; ABI 5, backward compatible) -------------------------------------------
+ * pyrad_amd.model.convolve / Atmosphere.observe: n_rows device-resident spectra on the base grid linspace(range_min,
+ * range_max, n) convolved with an instrument line shape (ILS) onto n_channels channels, so that channel radiances and channel
+ * weighting functions come down instead of spectra.  Row r is the n doubles at src[r] + src_offset[r] (several rows may
+ * share a buffer).  Channel c has a centre position[c] in grid-index units ((centre - range_min) / step, fractional), a
+ * width[c] in cm^-1 and the support [first[c], first[c] + count[c]) of grid points.  With step = (range_max - range_min) /
+ * (n - 1), the step the other entry points use:
+ *   x_cj = ((double)j - position[c]) * step      t_cj = x_cj / width[c]      w_cj = shape(t_cj)
+ *   out[r * n_channels + c] = (sum_{j in support} w_cj S_r[j]) / (sum_{j in support} w_cj)
+ *   shape 0 gaussian  exp(-4 ln2 t^2)                      width = FWHM
+ *         1 triangle  max(0, 1 - |t|)                      width = FWHM = half the base
+ *         2 boxcar    1 for |t| <= 0.5, else 0             width = full width
+ *         3 sinc      sin(pi t) / (pi t), 1 at t = 0       width = centre to first zero = 1 / (2 OPD)
+ *         4 table     table[0 .. n_table) sampled uniformly over x in [-table_half, +table_half], 0 outside; at x_cj:
+ *                     u = (x + table_half) * ((n_table - 1) / (2 table_half)), i = min(floor(u), n_table - 2),
+ *                     w = table[i] + (u - i) * (table[i + 1] - table[i]); width is ignored (may be NULL)
+ * Nothing is renormalised beyond the division above: a support cut short changes the channel, it is the caller's to choose
+ * (pyrad_amd.model.Instrument.support).  A sum of weights of 0 gives the IEEE result of the division.
+ * Arithmetic: numerators and the normaliser are accumulated as unevaluated fp64 pairs (exact products, two-sum) in one fixed
+ * order - per thread, per wave, the workgroup's four waves - without atomics: the same inputs give the same bits, a row's
+ * result does not depend on the other rows of the call, and a constant row returns its constant bit for bit.
+ * LBL_ERR_BAD_ARG: n_rows outside 1..lbl_limit("ils_rows") = 512; n_channels outside 1..lbl_limit("ils_channels") = 65536;
+ * count[c] < 1, first[c] < 0 or first[c] + count[c] > n; width[c] not > 0 (shapes 0-3); an unknown shape; shape 4 with
+ * n_table outside 2..lbl_limit("ils_table") = 4096 or table_half not > 0; a NULL src[r] or out; a row that does not fit its
+ * buffer; out shorter than n_rows x n_channels.  Everything is checked before anything is enqueued; the host arrays are
+ * copied and not retained.  Stream-ordered; nothing is synchronised. */
+int lbl_ils_convolve_dev(lbl_ctx* ctx, double range_min, double range_max, int64_t n,
+                         int n_rows, lbl_buffer* const* src, const int64_t* src_offset,
+                         int64_t n_channels, const double* position, const double* width,
+                         const int64_t* first, const int64_t* count,
+                         int shape, int n_table, double table_half, const double* table,
+                         lbl_buffer* out);
 
 /* ---- resident column (ABI 5) ---------------------------------------------------------------------------------------
  * The argument blocks of a column's merged accumulate jobs (lbl_layers_merged_accumulate_dev) and of its fold

@@ -105,6 +105,9 @@ SIGNATURES = {
     "lbl_column_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, _P,
                                           C.c_double, C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.c_int, C.POINTER(_P), C.POINTER(C.c_int32), _P, _P, _P]),
+    "lbl_ils_convolve_dev": (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64),
+                                       C.c_int64, _D, _D, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_int,
+                                       C.c_double, _D, _P]),
     "lbl_column_create": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(IsoParams), C.POINTER(Grid),
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, _D, C.POINTER(_P), C.POINTER(_P)]),
     "lbl_column_destroy": (C.c_int, [_P]),
@@ -176,12 +179,17 @@ def load():
     return lib
 
 
+# line shapes of lbl_ils_convolve_dev, and the rows one of its workgroups carries (kIlsRowBlock of csrc/lbl_device.h)
+ILS_SHAPES = {"gaussian": 0, "triangle": 1, "boxcar": 2, "sinc": 3, "table": 4}
+ILS_ROW_BLOCK = 8
+
 _limits = {}
 
 
 def limit(name: str) -> int:
     """A fixed size of the library (lbl_limit): "merged_lists_per_job", "arrays_per_layer", "arrays_per_sum",
-    "arrays_per_column", "layers_per_column", "jobs_per_batch", "flux_angles", "flux_bands", "jacobian_terms"."""
+    "arrays_per_column", "layers_per_column", "jobs_per_batch", "flux_angles", "flux_bands", "jacobian_terms", "ils_rows",
+    "ils_channels", "ils_table"."""
     if name not in _limits:
         v = C.c_int64()
         rc = load().lbl_limit(name.encode(), C.byref(v))
@@ -194,6 +202,10 @@ def limit(name: str) -> int:
 def _as_f64(a):
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a
+
+
+def _as_i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
 
 
 def _ptr(a):
@@ -525,6 +537,23 @@ class Context:
                                band_first, band_count),
             len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]), _arr(C.c_int32, [int(l) for l in term_layer]),
             _hb(jac), _hb(ln_tau_spectra), _hb(T_spectra)))
+
+    def ils_convolve_dev(self, range_min, range_max, n, rows, position, width, first, count, shape, out, table=None,
+                         table_half=0.0):
+        """Rows on the base grid convolved onto instrument channels (lbl_ils_convolve_dev): ``rows`` is a list of (Buffer,
+        offset in doubles); ``position``, ``width``, ``first``, ``count`` hold one value per channel; ``shape`` is an
+        ILS_SHAPES value, ``table`` / ``table_half`` the tabulated line shape of "table"; ``out`` receives len(rows) x
+        channels doubles, row-major."""
+        position, first, count = _as_f64(position), _as_i64(first), _as_i64(count)
+        width = _as_f64(width) if width is not None else None
+        table = _as_f64(table) if table is not None else None
+        self.check(self.lib.lbl_ils_convolve_dev(
+            self.h, float(range_min), float(range_max), int(n), len(rows), _arr(_P, [_hb(b) for b, _ in rows]),
+            _arr(C.c_int64, [int(o) for _, o in rows]), len(position),
+            position.ctypes.data_as(_D), width.ctypes.data_as(_D) if width is not None else None,
+            first.ctypes.data_as(C.POINTER(C.c_int64)), count.ctypes.data_as(C.POINTER(C.c_int64)), int(shape),
+            len(table) if table is not None else 0, float(table_half),
+            table.ctypes.data_as(_D) if table is not None else None, _hb(out)))
 
     def gather_compact_dev(self, gathered, slot, bounds, out):
         """padded all-gather result (slot r = rank r's shard) -> grid order (lbl_gather_compact_dev)."""

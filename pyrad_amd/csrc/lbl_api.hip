@@ -389,6 +389,9 @@ extern "C" int lbl_limit(const char* name, int64_t* value) {
     else if (!strcmp(name, "flux_angles")) *value = kMaxFluxAngles;           // angles of lbl_column_flux_dev
     else if (!strcmp(name, "flux_bands")) *value = kMaxFluxBands;             // bands of lbl_column_flux_dev
     else if (!strcmp(name, "jacobian_terms")) *value = kMaxJacobianTerms;     // molecule terms of lbl_column_jacobian_dev
+    else if (!strcmp(name, "ils_rows")) *value = kMaxIlsRows;                  // rows of lbl_ils_convolve_dev
+    else if (!strcmp(name, "ils_channels")) *value = kMaxIlsChannels;          // ... its channels
+    else if (!strcmp(name, "ils_table")) *value = kMaxIlsTable;                // ... the values of a tabulated line shape
     else return LBL_ERR_BAD_ARG;
     return LBL_OK;
 }
@@ -2536,7 +2539,7 @@ int comm_fail(lbl_ctx* ctx, int code, const char* msg) { return fail(ctx, code, 
 int ctx_device(lbl_ctx* ctx) { return ctx->device; }
 bool ctx_capturing(lbl_ctx* ctx) { return ctx->capturing; }
 lbl_ctx* buffer_ctx(lbl_buffer* buf) { return buf->ctx; }
-// ... and for lbl_column_transport.hip
+// ... and for lbl_column_transport.hip and lbl_instrument.hip
 hipStream_t ctx_stream(lbl_ctx* ctx) { return ctx->stream; }
 bool ctx_sweep_ieee(lbl_ctx* ctx) { return ctx->sweep_ieee != 0; }
 int ctx_device_args(lbl_ctx* ctx, const void* host, size_t bytes, void** dptr) { return device_args(ctx, host, bytes, dptr); }

@@ -273,6 +273,29 @@ void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long
 void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first, long long count,
                             double* partial, double* jac, hipStream_t s);
 
+// Instrument channels (K8, lbl_instrument.hip: lbl_ils_convolve_dev): n_rows spectra on the base grid convolved with an
+// instrument line shape onto n_channels channels.  One argument block per call: this header, then the arrays it names by
+// their byte offset from the block's start (the block's device address is known only after it is uploaded).
+constexpr int kMaxIlsRows = 512;
+constexpr int kMaxIlsChannels = 65536;
+constexpr int kMaxIlsTable = 4096;
+constexpr int kIlsRowBlock = 8;         // rows one workgroup carries in registers beside the normaliser
+enum : int32_t { ILS_GAUSSIAN = 0, ILS_TRIANGLE = 1, ILS_BOXCAR = 2, ILS_SINC = 3, ILS_TABLE = 4, ILS_SHAPES = 5 };
+struct IlsArgs {
+    long long off_rows;                 // n_rows x const double*: the rows
+    long long off_position, off_width;  // n_channels doubles each: centre in grid-index units, width in cm^-1
+    long long off_first, off_count;     // n_channels x long long: the support [first, first + count)
+    long long off_order;                // n_channels x int32: the channels by ascending `first` (the dispatch order)
+    long long off_table;                // n_table doubles (ILS_TABLE)
+    double* out;                        // n_rows x n_channels, row-major
+    double step;                        // the grid step
+    double table_half, table_rdx;       // ILS_TABLE: half extent in cm^-1 and (n_table - 1) / (2 table_half)
+    long long n_channels;
+    int32_t n_rows, n_table;
+    int32_t chunk, pad;                 // channels dealt to one XCD: ceil(n_channels / 8)
+};
+void launch_ils_convolve(const IlsArgs* d_args, int shape, int n_rows, long long n_channels, hipStream_t s);
+
 struct ColumnArgs {
     const double* trans[kMaxLayers];
     double layer_T[kMaxLayers];

@@ -4023,4 +4023,140 @@ void launch_line_survey(const double* nu, const double* sw, int n_lines, double 
                        resolution, out, n_base);
 }
 
+// ----------------------------------------------------------------------------------------
+// K8: instrument channels (lbl_ils_convolve_dev; the definition is in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// out[r][c] = sum_j w_cj S_r[j] / sum_j w_cj over the channel's support, w_cj = shape(((double)j - p_c) * step / width_c).
+// One workgroup per (channel, block of NR rows): a thread evaluates the weight of its point once and uses it for the NR rows
+// and the normaliser, all held in registers.  Every sum is carried as an unevaluated pair (hi, lo): the product w S exactly
+// (fma), the addition by two-sum with the rounding errors collected in lo.  The normaliser goes through the very same steps
+// in the same order, so numerator and normaliser of a constant row S = s are s sum_j w_cj and sum_j w_cj to ~2^-100 of each,
+// and the final division returns s itself; plain fp64 sums do not (fl(s x) is not s fl(x) unless s is a power of two).
+// Order of every sum: thread t takes the points t, t + 256, ...; the wave's 64 pairs are added by a fixed shuffle tree; thread
+// r adds the four waves' pairs of row r in wave order.  No atomics: the same inputs give the same bits, and a row's bits do
+// not depend on the rows beside it.
+// Workgroup ids are dealt round-robin over the eight XCDs; gridDim.x is a multiple of 8, so XCD x gets the ids x, x + 8, ...
+// of every grid row, and slot (id & 7) * chunk + (id >> 3) of the channel list sorted by support start gives each XCD one
+// contiguous run of overlapping supports for its own L2.
+struct dd { double hi, lo; };
+
+__device__ __forceinline__ void dd_add(dd& a, double p, double e) {
+#pragma clang fp contract(off)
+    const double s = a.hi + p;
+    const double bb = s - a.hi;
+    const double err = (a.hi - (s - bb)) + (p - bb);
+    a.hi = s;
+    a.lo += err + e;
+}
+
+__device__ __forceinline__ dd dd_wave_sum(dd a) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double h2 = __shfl_down(a.hi, off, 64), l2 = __shfl_down(a.lo, off, 64);
+        dd_add(a, h2, l2);
+    }
+    return a;
+}
+
+template <int SHAPE>
+__device__ __forceinline__ double ils_weight(double x, double width, const IlsArgs& A, const double* __restrict__ table) {
+#pragma clang fp contract(off)
+    if (SHAPE == ILS_TABLE) {
+        if (!(x >= -A.table_half && x <= A.table_half)) return 0.0;
+        const double u = (x + A.table_half) * A.table_rdx;
+        int i = (int)u;
+        i = i < 0 ? 0 : (i > A.n_table - 2 ? A.n_table - 2 : i);
+        const double f = u - (double)i;
+        const double v0 = table[i], v1 = table[i + 1];
+        return v0 + f * (v1 - v0);
+    }
+    const double t = x / width;
+    if (SHAPE == ILS_GAUSSIAN) return exp(-2.772588722239781 * (t * t));          // -4 ln 2
+    if (SHAPE == ILS_TRIANGLE) return fmax(0.0, 1.0 - fabs(t));
+    if (SHAPE == ILS_BOXCAR) return fabs(t) <= 0.5 ? 1.0 : 0.0;
+    const double pt = kPi * t;                                                     // ILS_SINC
+    return pt == 0.0 ? 1.0 : sin(pt) / pt;
+}
+
+template <int SHAPE, int NR>
+__global__ __launch_bounds__(256) void ils_convolve_kernel(const IlsArgs* __restrict__ Ap) {
+#pragma clang fp contract(off)
+    const IlsArgs& A = *Ap;
+    const char* base = (const char*)Ap;
+    const long long slot = (long long)(blockIdx.x & 7) * A.chunk + (blockIdx.x >> 3);
+    if (slot >= A.n_channels) return;                                               // (workgroup-uniform; gridDim.x = 8 chunk)
+    const int c = ((const int32_t*)(base + A.off_order))[slot];
+    const double p = ((const double*)(base + A.off_position))[c];
+    const double width = ((const double*)(base + A.off_width))[c];
+    const long long first = ((const long long*)(base + A.off_first))[c];
+    const long long count = ((const long long*)(base + A.off_count))[c];
+    const double* table = (const double*)(base + A.off_table);
+    const double* const* rows = (const double* const*)(base + A.off_rows);
+    const int r0 = blockIdx.y * NR;
+    // (the rows past the last one repeat it; their sums are not stored)
+    const double* row[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) row[i] = rows[min(r0 + i, A.n_rows - 1)] + first;
+
+    dd den = {0.0, 0.0}, num[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) num[i] = {0.0, 0.0};
+    for (long long j = threadIdx.x; j < count; j += 256) {
+        double v[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) v[i] = row[i][j];
+        const double x = ((double)(first + j) - p) * A.step;
+        const double w = ils_weight<SHAPE>(x, width, A, table);
+        dd_add(den, w, 0.0);
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const double pr = w * v[i];
+            dd_add(num[i], pr, fma(w, v[i], -pr));
+        }
+    }
+
+    __shared__ dd sh[4][NR + 1];
+    const int wave = threadIdx.x >> 6;
+    den = dd_wave_sum(den);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) num[i] = dd_wave_sum(num[i]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) sh[wave][i] = num[i];
+        sh[wave][NR] = den;
+    }
+    __syncthreads();
+    if (threadIdx.x < NR && r0 + (int)threadIdx.x < A.n_rows) {
+        dd nu = sh[0][threadIdx.x], de = sh[0][NR];
+        for (int k = 1; k < 4; ++k) {
+            dd_add(nu, sh[k][threadIdx.x].hi, sh[k][threadIdx.x].lo);
+            dd_add(de, sh[k][NR].hi, sh[k][NR].lo);
+        }
+        // (nu.hi + nu.lo) / (de.hi + de.lo): the quotient of the leading parts, then its exact remainder and the trailing parts
+        const double q = nu.hi / de.hi;
+        const double rem = fma(-q, de.hi, nu.hi);
+        A.out[(size_t)(r0 + threadIdx.x) * (size_t)A.n_channels + (size_t)c] = q + ((rem + nu.lo) - q * de.lo) / de.hi;
+    }
+}
+
+template <int NR>
+static void launch_ils_shape(const IlsArgs* d_args, int shape, dim3 grid, hipStream_t s) {
+    switch (shape) {
+        case ILS_GAUSSIAN: hipLaunchKernelGGL((ils_convolve_kernel<ILS_GAUSSIAN, NR>), grid, dim3(256), 0, s, d_args); break;
+        case ILS_TRIANGLE: hipLaunchKernelGGL((ils_convolve_kernel<ILS_TRIANGLE, NR>), grid, dim3(256), 0, s, d_args); break;
+        case ILS_BOXCAR: hipLaunchKernelGGL((ils_convolve_kernel<ILS_BOXCAR, NR>), grid, dim3(256), 0, s, d_args); break;
+        case ILS_SINC: hipLaunchKernelGGL((ils_convolve_kernel<ILS_SINC, NR>), grid, dim3(256), 0, s, d_args); break;
+        case ILS_TABLE: hipLaunchKernelGGL((ils_convolve_kernel<ILS_TABLE, NR>), grid, dim3(256), 0, s, d_args); break;
+        default: break;
+    }
+}
+
+// a single row travels alone (NR = 1); more rows in blocks of kIlsRowBlock.  grid.x = 8 * chunk (see above)
+void launch_ils_convolve(const IlsArgs* d_args, int shape, int n_rows, long long n_channels, hipStream_t s) {
+    if (n_rows < 1 || n_channels < 1) return;
+    const unsigned gx = 8u * (unsigned)((n_channels + 7) / 8);
+    if (n_rows == 1) launch_ils_shape<1>(d_args, shape, dim3(gx, 1), s);
+    else launch_ils_shape<kIlsRowBlock>(d_args, shape, dim3(gx, (n_rows + kIlsRowBlock - 1) / kIlsRowBlock), s);
+}
+
 }  // namespace lbl

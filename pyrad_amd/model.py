@@ -1353,6 +1353,222 @@ class Jacobians:
 
 
 # ----------------------------------------------------------------------------------------
+# Instrument channels (Instrument, convolve, Atmosphere.observe; beyond the reference)
+# ----------------------------------------------------------------------------------------
+def planckWavenumber(wavenumber, temp):
+    """pyradPlanck.py:38-44 (wavenumber in cm^-1, Wm-2sr-1(cm-1)-1) in host NumPy, for channel centres; a spectrum on the
+    grid comes from Layer.planck, on the device."""
+    nu = np.asarray(wavenumber, dtype=np.float64)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        a = 2E8 * h * c**2 * nu**3
+        b = 100 * h * c * nu / k / temp
+        return a / (np.exp(b) - 1)
+
+
+def brightnessTemperature(wavenumber, radiance):
+    """The temperature at which planckWavenumber(wavenumber, T) equals ``radiance`` (host NumPy): 100 h c nu / k /
+    log1p(a / R) with a = 2E8 h c^2 nu^3.  NaN where the radiance is not > 0."""
+    nu = np.asarray(wavenumber, dtype=np.float64)
+    R = np.asarray(radiance, dtype=np.float64)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        a = 2E8 * h * c**2 * nu**3
+        T = 100 * h * c * nu / k / np.log1p(a / R)
+    return np.where(R > 0, T, np.nan)
+
+
+def _planck_dT(wavenumber, temp):
+    """dB/dT of planckWavenumber: B b e^b / ((e^b - 1) T), b = 100 h c nu / k / T (the expression jacobians() documents)."""
+    nu = np.asarray(wavenumber, dtype=np.float64)
+    temp = np.asarray(temp, dtype=np.float64)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        b = 100 * h * c * nu / k / temp
+        return planckWavenumber(nu, temp) * b * np.exp(b) / ((np.exp(b) - 1) * temp)
+
+
+class Instrument:
+    """The channels of an instrument: centres in cm^-1 and one instrument line shape (host-only description).
+
+    ``shape`` and the meaning of ``width`` (a scalar or one value per channel, cm^-1), with t = (nu - centre) / width:
+        "gaussian"  exp(-4 ln2 t^2)                     width = FWHM
+        "triangle"  max(0, 1 - |t|)                     width = FWHM, half the base
+        "boxcar"    1 for |t| <= 0.5, else 0            width = full width
+        "sinc"      sin(pi t) / (pi t)                  width = centre to first zero, 1 / (2 OPD)
+        "table"     ``table`` = (offsets, values): values at uniformly spaced offsets (cm^-1) symmetric about 0, linear
+                    in between, 0 outside; no width
+    ``cutoff``: half support in cm^-1 (a scalar or per channel); default 3 width (gaussian), width (triangle), width / 2
+    (boxcar), the table's half extent (table); a sinc needs one.  The centres need not be sorted or uniform.  A channel value
+    is sum_j w_j S_j / sum_j w_j over the grid points within the cutoff: nothing is renormalised at the ends of a range, a
+    channel that hangs over one is refused (support)."""
+
+    def __init__(self, centres, shape="gaussian", width=None, cutoff=None, table=None):
+        if shape not in nat.ILS_SHAPES:
+            raise ValueError("shape: one of %s, not %r" % (", ".join(nat.ILS_SHAPES), shape))
+        try:
+            centres = np.array(centres, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("centres: a 1-D sequence of wavenumbers, not %r" % (centres,))
+        if centres.ndim != 1 or centres.size < 1 or not np.all(np.isfinite(centres)):
+            raise ValueError("centres: a non-empty 1-D sequence of finite wavenumbers")
+        if centres.size > nat.limit("ils_channels"):
+            raise ValueError("centres: %d channels, at most %d" % (centres.size, nat.limit("ils_channels")))
+        self.centres = centres
+        self.shape = shape
+        self.table = None
+        self.tableHalf = 0.0
+        if shape == "table":
+            if table is None:
+                raise ValueError("table: shape \"table\" needs table=(offsets, values)")
+            try:
+                offsets, values = (np.array(v, dtype=np.float64) for v in table)
+            except (TypeError, ValueError):
+                raise ValueError("table: (offsets, values), two sequences of equal length")
+            if offsets.ndim != 1 or offsets.shape != values.shape or offsets.size < 2:
+                raise ValueError("table: (offsets, values), two 1-D sequences of equal length >= 2")
+            if offsets.size > nat.limit("ils_table"):
+                raise ValueError("table: %d values, at most %d" % (offsets.size, nat.limit("ils_table")))
+            if not (np.all(np.isfinite(offsets)) and np.all(np.isfinite(values))):
+                raise ValueError("table: offsets and values must be finite")
+            half = float(offsets[-1])
+            d = np.diff(offsets)
+            tol = 1e-9 * max(half, 0.0)
+            if not (half > 0 and np.all(d > 0) and np.all(np.abs(d - 2.0 * half / (offsets.size - 1)) <= tol)):
+                raise ValueError("table: the offsets must be uniformly spaced and ascending")
+            if abs(offsets[0] + half) > tol:
+                raise ValueError("table: the offsets must be symmetric about 0")
+            self.table = values
+            self.tableHalf = half
+            self.width = None
+            default_cutoff = half
+        else:
+            if table is not None:
+                raise ValueError("table: only shape \"table\" takes one")
+            if width is None:
+                raise ValueError("width: shape %r needs a width" % shape)
+            self.width = self._per_channel("width", width)
+            default_cutoff = {"gaussian": 3.0 * self.width, "triangle": self.width, "boxcar": self.width / 2.0}.get(shape)
+        if cutoff is None:
+            if default_cutoff is None:
+                raise ValueError("cutoff: shape %r has no default cutoff, give one" % shape)
+            cutoff = default_cutoff
+        self.cutoff = self._per_channel("cutoff", cutoff)
+
+    def _per_channel(self, name, value):
+        try:
+            v = np.array(value, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("%s: a number or one per channel, not %r" % (name, value))
+        if v.ndim == 0:
+            v = np.full(self.centres.shape, float(v))
+        if v.shape != self.centres.shape:
+            raise ValueError("%s: a number or one per channel (%d), got shape %s" % (name, self.centres.size, v.shape))
+        if not np.all(np.isfinite(v) & (v > 0)):
+            raise ValueError("%s must be finite and > 0" % name)
+        return v
+
+    def __len__(self):
+        return self.centres.size
+
+    def __repr__(self):
+        return "Instrument(%d channels, %s)" % (self.centres.size, self.shape)
+
+    def support(self, rangeMin, rangeMax, n):
+        """(position, first, count) of every channel on linspace(rangeMin, rangeMax, n): position = (centre - rangeMin) /
+        step in grid-index units, and [first, first + count) the grid points nu_j with |nu_j - centre| <= cutoff (on the
+        axis _flux_bands searches).  ValueError, naming the channel, when [centre - cutoff, centre + cutoff] is not inside
+        [rangeMin, rangeMax] or holds no grid point."""
+        n = int(n)
+        if n < 2 or not rangeMax > rangeMin:
+            raise ValueError("the wavenumber range holds fewer than two grid points")
+        step = (float(rangeMax) - float(rangeMin)) / (n - 1)
+        lo, hi = self.centres - self.cutoff, self.centres + self.cutoff
+        bad = np.flatnonzero(~((lo >= rangeMin) & (hi <= rangeMax)))
+        if bad.size:
+            i = int(bad[0])
+            raise ValueError("channel %d (centre %.10g, cutoff %.10g) is not inside the range [%g, %g]"
+                             % (i, self.centres[i], self.cutoff[i], rangeMin, rangeMax))
+        x = np.linspace(rangeMin, rangeMax, n)
+        inside = lambda j: np.abs(x[np.clip(j, 0, n - 1)] - self.centres) <= self.cutoff
+        first = np.searchsorted(x, lo, "left").astype(np.int64)
+        end = np.searchsorted(x, hi, "right").astype(np.int64)
+        for _ in range(2):       # (the searched bounds are rounded sums: settle the end points on the criterion itself)
+            first -= (first > 0) & inside(first - 1)
+            first += (first < end) & ~inside(first)
+            end += (end < n) & inside(end)
+            end -= (end > first) & ~inside(end - 1)
+        count = end - first
+        bad = np.flatnonzero(count < 1)
+        if bad.size:
+            i = int(bad[0])
+            raise ValueError("channel %d (centre %.10g, cutoff %.10g) holds no grid point" % (i, self.centres[i], self.cutoff[i]))
+        return (self.centres - rangeMin) / step, first, count
+
+
+def _ils_convolve(ctx, instrument, rangeMin, rangeMax, n, support, rows, out):
+    """K8 over ``rows`` = [(Buffer, offset)] into ``out`` (len(rows) x channels), ``support`` from instrument.support."""
+    position, first, count = support
+    ctx.ils_convolve_dev(rangeMin, rangeMax, n, rows, position, instrument.width, first, count,
+                         nat.ILS_SHAPES[instrument.shape], out, table=instrument.table, table_half=instrument.tableHalf)
+
+
+def convolve(instrument, spectra, rangeMin, rangeMax):
+    """Spectra on the base grid linspace(rangeMin, rangeMax, n) convolved onto the channels of ``instrument`` on the device:
+    ``spectra`` of shape (n,) or (M, n) gives (C,) or (M, C).  Channel c of a row S is sum_j w_cj S_j / sum_j w_cj over the
+    channel's support (Instrument.support) with w_cj = shape(((j - position_c) * step) / width_c); the same inputs give the
+    same bits, a row's result does not depend on the rows beside it, and a constant row returns its constant."""
+    if not isinstance(instrument, Instrument):
+        raise ValueError("instrument: an Instrument, not %r" % (instrument,))
+    spectra = np.ascontiguousarray(spectra, dtype=np.float64)
+    if spectra.ndim not in (1, 2) or spectra.shape[-1] < 2:
+        raise ValueError("spectra: shape (n,) or (M, n) on the base grid, got %s" % (spectra.shape,))
+    rows2d = spectra.reshape(-1, spectra.shape[-1])
+    M, n = rows2d.shape
+    support = instrument.support(rangeMin, rangeMax, n)
+    C = len(instrument)
+    result = np.empty((M, C))
+    if M == 0:
+        return result
+    ctx = _ctx()
+    per_call = min(M, nat.limit("ils_rows"))
+    tmp = []
+    try:
+        src = ctx.buffer(per_call * n); tmp.append(src)
+        out = ctx.buffer(per_call * C); tmp.append(out)
+        for r0 in range(0, M, per_call):
+            m = min(per_call, M - r0)
+            src.upload(rows2d[r0:r0 + m].reshape(-1))
+            _ils_convolve(ctx, instrument, rangeMin, rangeMax, n, support, [(src, i * n) for i in range(m)], out)
+            result[r0:r0 + m] = out.download(m * C).reshape(m, C)
+    finally:
+        for b in tmp:
+            b.free()
+    return result[0] if spectra.ndim == 1 else result
+
+
+class Observation:
+    """What Atmosphere.observe returns.  ``wavenumber``: the channel centres, (C,); ``radiance``: channel radiance in the
+    units of transmission(); ``brightnessTemperature``: its inverse Planck at the centre, K; ``mu``: the viewing cosine.
+    With jacobians=True (else None), (L, C) each: ``temperatureJacobian`` dR_c/dT_l (Planck part only, as jacobians()
+    documents), ``opticalDepthJacobian`` dR_c/d ln tau_l and ``brightnessTemperatureJacobian`` = temperatureJacobian /
+    (dB/dT at the centre and the channel's brightness temperature)."""
+
+    def __init__(self, wavenumber, radiance, mu, temperatureJacobian=None, opticalDepthJacobian=None):
+        self.wavenumber = wavenumber
+        self.radiance = radiance
+        self.brightnessTemperature = brightnessTemperature(wavenumber, radiance)
+        self.mu = mu
+        self.temperatureJacobian = temperatureJacobian
+        self.opticalDepthJacobian = opticalDepthJacobian
+        self.brightnessTemperatureJacobian = None
+        if temperatureJacobian is not None:
+            with np.errstate(divide='ignore', invalid='ignore'):
+                self.brightnessTemperatureJacobian = temperatureJacobian / _planck_dT(wavenumber, self.brightnessTemperature)
+
+    def __repr__(self):
+        return "Observation(channels=%d, mu=%g, jacobians=%s)" % (
+            self.wavenumber.size, self.mu, self.temperatureJacobian is not None)
+
+
+# ----------------------------------------------------------------------------------------
 # Atmosphere (cls:790-821) + the column fold this build defines on it (SURVEY.md §3.5)
 # ----------------------------------------------------------------------------------------
 class Atmosphere(list):
@@ -1566,6 +1782,59 @@ class Atmosphere(list):
         return Jacobians(olr, dTs if surfaceSpectrum is None else None, dT, dtau, mol, names, mu, weight,
                          temperatureSpectrum=T_spec.download(nl * n).reshape(nl, n) if spectra else None,
                          opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None)
+
+    def observe(self, instrument, surfaceTemperature=None, surfaceSpectrum=None, mu=1.0, jacobians=False):
+        """What an instrument above the column sees at viewing cosine ``mu`` (beyond the reference): the upward radiance at
+        the top (fluxes() with the angle set [(mu, 1.0)]: column, layer order, grid and surface source as there) convolved
+        onto the channels of ``instrument`` on the device, beside the resident spectrum; only the channel values come down.
+        ``jacobians``: also the channel weighting functions, jacobians() for the same angle (molecules=False, its spectral
+        dI/dT_l and dI/d ln tau_l) convolved in the same call.  Returns an Observation.  With mu = 1 the radiance is
+        convolve(instrument, transmission(...)) bit for bit wherever fluxes() documents that identity.  The absorption
+        coefficients are the resident ones: after transmission() or fluxes() nothing is accumulated again.  Everything is
+        validated (ValueError) before the device is touched."""
+        if not isinstance(instrument, Instrument):
+            raise ValueError("instrument: an Instrument, not %r" % (instrument,))
+        try:
+            angle = [(float(mu), 1.0)]
+        except (TypeError, ValueError):
+            raise ValueError("mu: a viewing cosine in (0, 1], not %r" % (mu,))
+        if not (angle[0][0] > 0.0 and angle[0][0] <= 1.0):
+            raise ValueError("mu: a viewing cosine in (0, 1], not %r" % (mu,))
+        layers, n, mu_k, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
+            surfaceSpectrum, surfaceTemperature, angle, None)
+        first = layers[0]
+        support = instrument.support(first.rangeMin, first.rangeMax, n)
+        nl, C = len(layers), len(instrument)
+        n_rows = 1 + 2 * nl if jacobians else 1
+        if n_rows > nat.limit("ils_rows"):
+            raise ValueError("jacobians: %d layers, at most %d" % (nl, (nat.limit("ils_rows") - 1) // 2))
+        ctx = _ctx()
+        if jacobians and ctx.option("sweep_ieee_divisions"):
+            raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        T, depth = [L.T for L in layers], [L.depth for L in layers]
+        surface_T = float(surfaceTemperature or 0.0)
+        fst = _kept_state(self, "_flux_state")
+        fst.reserve(ctx, max(n, 2 * (nl + 1)))
+        I_surface = fst.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
+        up_top = fst.buf(ctx, "up_top")
+        ctx.column_flux_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first, band_count,
+                            fst.buf(ctx, "level"), I_surface=I_surface, surface_T=surface_T, up_top=up_top)
+        rows = [(up_top, 0)]
+        if jacobians:
+            jst = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, 2 + 2 * nl))
+            sp = _kept_state(self, "_jacobian_spec").reserve(ctx, nl * n)
+            ln_tau_spec, T_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T")
+            ctx.column_jacobian_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first, band_count,
+                                    jst.buf(ctx, "jac"), I_surface=I_surface, surface_T=surface_T,
+                                    ln_tau_spectra=ln_tau_spec, T_spectra=T_spec)
+            rows += [(T_spec, l * n) for l in range(nl)] + [(ln_tau_spec, l * n) for l in range(nl)]
+        out = _kept_state(self, "_observe_out").reserve(ctx, n_rows * C).buf(ctx, "out")
+        _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, rows, out)
+        v = out.download(n_rows * C).reshape(n_rows, C)
+        return Observation(instrument.centres.copy(), v[0].copy(), float(mu_k[0]),
+                           temperatureJacobian=v[1:1 + nl].copy() if jacobians else None,
+                           opticalDepthJacobian=v[1 + nl:].copy() if jacobians else None)
 
     def _jacobian_terms(self, ctx, layers, n, plan):
         """The molecule terms of jacobians(): every molecule's own absorption coefficient k_(m,l), as (buffers, layer index
