@@ -95,6 +95,8 @@ int lbl_abi_version(void);
  *   "jacobian_terms"        molecule terms of lbl_column_jacobian_dev: 512
  *   "ils_rows"              rows of lbl_ils_convolve_dev: 512      "ils_channels": its channels: 65536
  *   "ils_table"             values of its tabulated line shape: 4096
+ *   "kdist_rows"            rows of lbl_rank_order_dev / lbl_ranked_means_dev: 512
+ *   "kdist_intervals"       rank intervals of one band of lbl_ranked_means_dev: 256
  * Unknown name: LBL_ERR_BAD_ARG. */
 int lbl_limit(const char* name, int64_t* value);
 int lbl_device_count(int* count);
@@ -454,6 +456,62 @@ int lbl_ils_convolve_dev(lbl_ctx* ctx, double range_min, double range_max, int64
                          const int64_t* first, const int64_t* count,
                          int shape, int n_table, double table_half, const double* table,
                          lbl_buffer* out);
+
+/* ---- k-distributions (beyond the reference; ABI 5, backward compatible) -------------------------------------------------
+ * pyrad_amd.model.kDistribution / Atmosphere.kDistribution: the points of a band re-ordered by the size of a row (an
+ * absorption coefficient, usually) and rows averaged over intervals of that rank, so that the tables correlated-k schemes are
+ * built from come down instead of spectra.
+ * Rows and bands.  Row r is the n doubles at src[r] + src_offset[r] on the base grid (several rows may share a buffer).
+ * Band b is the index range [band_first[b], band_first[b] + band_count[b]); there are 1..lbl_limit("flux_bands") = 64 of
+ * them, they may overlap, and each holds at most 2^31 - 1 points.  Every per-point output is laid out band after band: band
+ * b occupies [S_b, S_b + band_count[b]) with S_b the sum of the counts of the bands before it; a row's output is S_total =
+ * sum_b band_count[b] long, and row r's starts at r * S_total.
+ * Order.  The order of row x in band b is exactly first_b + numpy.argsort(x[first_b : first_b + count_b], kind="stable"):
+ * ascending; -0.0 and +0.0 tie; every NaN of either sign sorts after +inf; ties keep grid order.  (The pairs (key, index
+ * in the band) are ranked, key = the value's bits in sign-magnitude order after -0 -> +0 and NaN -> all ones: all pairs are
+ * distinct, so the result does not depend on the sorting algorithm.)  order[r * S_total + S_b + j] is the grid index of the
+ * j-th smallest point as a double, as centre indices travel elsewhere in this library; sorted[...] is the row's value there,
+ * bit for bit (payloads and signs of zero included).
+ *
+ * lbl_rank_order_dev ranks all bands of all rows in one call: tiles of 2,048 points are sorted in LDS by one launch, and a
+ * band of more points takes ceil(log2(count / 2048)) merge passes over the work space `work`, which holds
+ * lbl_rank_order_workspace(...) doubles: 0 when no band is longer than 2,048 points (work may then be NULL), else
+ * 3 * n_rows * S_total.  `sorted` may be NULL.  The outputs must not overlap the rows or the work space.
+ * LBL_ERR_BAD_ARG: a NULL argument; n < 1; n_rows outside 1..lbl_limit("kdist_rows") = 512; n_bands outside 1..64; a band
+ * that is empty, longer than 2^31 - 1 or not inside [0, n); a row that does not fit its buffer; order or sorted shorter than
+ * n_rows * S_total; work shorter than the work space.  lbl_rank_order_workspace needs no context and refuses the same row
+ * and band counts. */
+int lbl_rank_order_workspace(int n_rows, int64_t n, int n_bands, const int64_t* band_count, int64_t* doubles);
+int lbl_rank_order_dev(lbl_ctx* ctx, int64_t n, int n_rows, lbl_buffer* const* src, const int64_t* src_offset,
+                       int n_bands, const int64_t* band_first, const int64_t* band_count,
+                       lbl_buffer* work, lbl_buffer* order, lbl_buffer* sorted);
+/* lbl_ranked_means_dev averages n_rows rows over intervals of a rank.  Row r is ranked by the S_total doubles at order[r] +
+ * order_offset[r] - one row of an `order` output of lbl_rank_order_dev for the same bands; several rows may name the same
+ * one.  Band b has G_b = n_intervals[b] intervals, 1..lbl_limit("kdist_intervals") = 256, given by G_b + 1 rank edges
+ * 0 = e_0 < e_1 < ... < e_G = band_count[b]; `edges` holds the bands' edges one band after the other (sum_b (G_b + 1)
+ * values).  With G_total = sum_b G_b and Gs_b the sum of G of the bands before b:
+ *   mean [mean_offset  + r * G_total             + Gs_b     + i] = (sum_{q = e_i}^{e_(i+1) - 1} x_r[order_r[S_b + q]]) / (e_(i+1) - e_i)
+ *   lower[lower_offset + r * (G_total + n_bands) + Gs_b + b + i] = x_r[order_r[S_b + e_i]]            for i < G_b
+ *                                                                  x_r[order_r[S_b + count_b - 1]]    for i = G_b
+ * (lower may be NULL): the order statistics at the edges, bit-exact when the row is ranked by its own order.  An interval of
+ * one rank returns its value bit for bit.  Every sum is taken in one fixed order - 2,048 ranks per workgroup: per thread,
+ * the wave's 64 by a fixed tree, the four waves in order; then the interval's partial sums the same way - without atomics:
+ * two calls give the same bits and a row's result does not depend on the rows beside it.  Inf and NaN pass through as IEEE
+ * arithmetic gives them.  An order value that is no grid index of its band is clamped into the band (NaN: its first point),
+ * so no read leaves the row.  `work` holds lbl_ranked_means_workspace(...) doubles: n_rows * sum over all intervals of
+ * ceil((e_(i+1) - e_i) / 2048).
+ * LBL_ERR_BAD_ARG: a NULL argument other than lower; rows and bands as above; G_b outside 1..256; edges that do not start
+ * at 0, do not end at band_count[b] or are not strictly increasing; a row or an order that does not fit its buffer; a
+ * negative offset; mean, lower or work too short.
+ * Both entry points check everything before anything is enqueued; the host arrays are copied and not retained.
+ * Stream-ordered; nothing is synchronised. */
+int lbl_ranked_means_workspace(int n_rows, int n_bands, const int64_t* band_count, const int32_t* n_intervals,
+                               const int64_t* edges, int64_t* doubles);
+int lbl_ranked_means_dev(lbl_ctx* ctx, int64_t n, int n_rows, lbl_buffer* const* src, const int64_t* src_offset,
+                         lbl_buffer* const* order, const int64_t* order_offset,
+                         int n_bands, const int64_t* band_first, const int64_t* band_count,
+                         const int32_t* n_intervals, const int64_t* edges, lbl_buffer* work,
+                         lbl_buffer* mean, int64_t mean_offset, lbl_buffer* lower, int64_t lower_offset);
 
 /* ---- resident column (ABI 5) ---------------------------------------------------------------------------------------
  * The argument blocks of a column's merged accumulate jobs (lbl_layers_merged_accumulate_dev) and of its fold

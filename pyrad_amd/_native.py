@@ -108,6 +108,14 @@ SIGNATURES = {
     "lbl_ils_convolve_dev": (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64),
                                        C.c_int64, _D, _D, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_int,
                                        C.c_double, _D, _P]),
+    "lbl_rank_order_workspace": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lbl_rank_order_dev": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64), _P, _P, _P]),
+    "lbl_ranked_means_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lbl_ranked_means_dev": (C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(_P),
+                                       C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int64), _P, _P, C.c_int64, _P, C.c_int64]),
     "lbl_column_create": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(IsoParams), C.POINTER(Grid),
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, _D, C.POINTER(_P), C.POINTER(_P)]),
     "lbl_column_destroy": (C.c_int, [_P]),
@@ -182,6 +190,9 @@ def load():
 # line shapes of lbl_ils_convolve_dev, and the rows one of its workgroups carries (kIlsRowBlock of csrc/lbl_device.h)
 ILS_SHAPES = {"gaussian": 0, "triangle": 1, "boxcar": 2, "sinc": 3, "table": 4}
 ILS_ROW_BLOCK = 8
+# points one workgroup of the k-distribution kernels sorts or merges in LDS (kKdistTile of csrc/lbl_device.h): bands up to this
+# long are ranked in one launch without work space
+KDIST_TILE = 2048
 
 _limits = {}
 
@@ -189,7 +200,7 @@ _limits = {}
 def limit(name: str) -> int:
     """A fixed size of the library (lbl_limit): "merged_lists_per_job", "arrays_per_layer", "arrays_per_sum",
     "arrays_per_column", "layers_per_column", "jobs_per_batch", "flux_angles", "flux_bands", "jacobian_terms", "ils_rows",
-    "ils_channels", "ils_table"."""
+    "ils_channels", "ils_table", "kdist_rows", "kdist_intervals"."""
     if name not in _limits:
         v = C.c_int64()
         rc = load().lbl_limit(name.encode(), C.byref(v))
@@ -554,6 +565,58 @@ class Context:
             first.ctypes.data_as(C.POINTER(C.c_int64)), count.ctypes.data_as(C.POINTER(C.c_int64)), int(shape),
             len(table) if table is not None else 0, float(table_half),
             table.ctypes.data_as(_D) if table is not None else None, _hb(out)))
+
+    @staticmethod
+    def _i64p(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+    def rank_order_workspace(self, n_rows, n, band_count) -> int:
+        """Doubles of work space lbl_rank_order_dev needs for ``n_rows`` rows of ``n`` points and these band lengths."""
+        count = _as_i64(band_count)
+        v = C.c_int64()
+        self.check(self.lib.lbl_rank_order_workspace(int(n_rows), int(n), len(count), self._i64p(count), C.byref(v)))
+        return int(v.value)
+
+    def rank_order_dev(self, n, rows, band_first, band_count, order, sorted=None, work=None):
+        """The stable ascending order of every band of every row (lbl_rank_order_dev): ``rows`` is a list of (Buffer, offset in
+        doubles) of ``n`` points each; ``order`` receives len(rows) x sum(band_count) grid indices as doubles, band after band
+        per row, ``sorted`` (optional) the rows' values in that order; ``work`` holds rank_order_workspace(...) doubles (may
+        be None when that is 0)."""
+        first, count = _as_i64(band_first), _as_i64(band_count)
+        if len(first) != len(count):
+            raise ValueError("rank_order_dev: one first per band")
+        self.check(self.lib.lbl_rank_order_dev(
+            self.h, int(n), len(rows), _arr(_P, [_hb(b) for b, _ in rows]), _arr(C.c_int64, [int(o) for _, o in rows]),
+            len(count), self._i64p(first), self._i64p(count), _hb(work), _hb(order), _hb(sorted)))
+
+    def ranked_means_workspace(self, n_rows, band_count, edges) -> int:
+        """Doubles of work space lbl_ranked_means_dev needs; ``edges``: one array of rank edges per band."""
+        count = _as_i64(band_count)
+        if len(edges) != len(count):
+            raise ValueError("ranked_means_workspace: one edge array per band")
+        flat = _as_i64(np.concatenate([_as_i64(e) for e in edges])) if len(edges) else _as_i64([])
+        v = C.c_int64()
+        self.check(self.lib.lbl_ranked_means_workspace(
+            int(n_rows), len(count), self._i64p(count), _arr(C.c_int32, [len(e) - 1 for e in edges]), self._i64p(flat),
+            C.byref(v)))
+        return int(v.value)
+
+    def ranked_means_dev(self, n, rows, orders, band_first, band_count, edges, work, mean, lower=None, mean_offset=0,
+                         lower_offset=0):
+        """Means of every row over intervals of the rank (lbl_ranked_means_dev): ``rows`` and ``orders`` are lists of (Buffer,
+        offset), row r is averaged by the order at orders[r] (an output row of rank_order_dev); ``edges``: per band G_b + 1
+        rank edges 0 .. count_b.  ``mean`` receives, from ``mean_offset``, len(rows) x sum(G_b) values, ``lower`` (optional,
+        from ``lower_offset``) len(rows) x sum(G_b + 1) order statistics at the edges; ``work`` holds
+        ranked_means_workspace(...) doubles."""
+        first, count = _as_i64(band_first), _as_i64(band_count)
+        if len(orders) != len(rows) or len(first) != len(count) or len(edges) != len(count):
+            raise ValueError("ranked_means_dev: one order per row, one first and one edge array per band")
+        flat = _as_i64(np.concatenate([_as_i64(e) for e in edges])) if len(edges) else _as_i64([])
+        self.check(self.lib.lbl_ranked_means_dev(
+            self.h, int(n), len(rows), _arr(_P, [_hb(b) for b, _ in rows]), _arr(C.c_int64, [int(o) for _, o in rows]),
+            _arr(_P, [_hb(b) for b, _ in orders]), _arr(C.c_int64, [int(o) for _, o in orders]),
+            len(count), self._i64p(first), self._i64p(count), _arr(C.c_int32, [len(e) - 1 for e in edges]), self._i64p(flat),
+            _hb(work), _hb(mean), int(mean_offset), _hb(lower), int(lower_offset)))
 
     def gather_compact_dev(self, gathered, slot, bounds, out):
         """padded all-gather result (slot r = rank r's shard) -> grid order (lbl_gather_compact_dev)."""

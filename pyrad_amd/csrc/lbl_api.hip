@@ -392,6 +392,8 @@ extern "C" int lbl_limit(const char* name, int64_t* value) {
     else if (!strcmp(name, "ils_rows")) *value = kMaxIlsRows;                  // rows of lbl_ils_convolve_dev
     else if (!strcmp(name, "ils_channels")) *value = kMaxIlsChannels;          // ... its channels
     else if (!strcmp(name, "ils_table")) *value = kMaxIlsTable;                // ... the values of a tabulated line shape
+    else if (!strcmp(name, "kdist_rows")) *value = kMaxKdistRows;              // rows of lbl_rank_order_dev / lbl_ranked_means_dev
+    else if (!strcmp(name, "kdist_intervals")) *value = kMaxKdistIntervals;    // ... the intervals of one band
     else return LBL_ERR_BAD_ARG;
     return LBL_OK;
 }
@@ -2539,7 +2541,7 @@ int comm_fail(lbl_ctx* ctx, int code, const char* msg) { return fail(ctx, code, 
 int ctx_device(lbl_ctx* ctx) { return ctx->device; }
 bool ctx_capturing(lbl_ctx* ctx) { return ctx->capturing; }
 lbl_ctx* buffer_ctx(lbl_buffer* buf) { return buf->ctx; }
-// ... and for lbl_column_transport.hip and lbl_instrument.hip
+// ... and for lbl_column_transport.hip, lbl_instrument.hip and lbl_kdist.hip
 hipStream_t ctx_stream(lbl_ctx* ctx) { return ctx->stream; }
 bool ctx_sweep_ieee(lbl_ctx* ctx) { return ctx->sweep_ieee != 0; }
 int ctx_device_args(lbl_ctx* ctx, const void* host, size_t bytes, void** dptr) { return device_args(ctx, host, bytes, dptr); }

@@ -296,6 +296,43 @@ struct IlsArgs {
 };
 void launch_ils_convolve(const IlsArgs* d_args, int shape, int n_rows, long long n_channels, hipStream_t s);
 
+// k-distributions (K9, lbl_kdist.hip: lbl_rank_order_dev, lbl_ranked_means_dev): every (row, band) segment of n_rows rows
+// on the base grid ranked by (key, index), then averaged over intervals of the rank.  One argument block per call.
+constexpr int kMaxKdistRows = 512;
+constexpr int kMaxKdistIntervals = 256;  // per band
+constexpr int kMaxKdistBands = kMaxFluxBands;
+constexpr int kKdistTile = 2048;         // pairs one workgroup sorts / merges in LDS (256 threads x 8), and ranks per partial sum
+constexpr int kKdistMaxPasses = 20;      // merge passes of the longest band the 32-bit band-local index allows: 2048 << 20 = 2^31
+struct RankArgs {
+    long long off_rows;                 // n_rows x const double*: the rows (byte offset from the block's start, as IlsArgs)
+    double* order; double* sorted;      // n_rows x s_total each (sorted may be nullptr)
+    unsigned long long* keys[2];        // ping-pong of the merge passes: n_rows x s_total keys ...
+    unsigned int* idx[2];               // ... and band-local indices (nullptr when no band is longer than a tile)
+    long long s_total;
+    long long first[kMaxKdistBands], count[kMaxKdistBands], s_start[kMaxKdistBands];
+    int32_t passes[kMaxKdistBands];     // merge passes of the band: the smallest P with kKdistTile << P >= count
+    // work items of one row per launch, as a prefix over the bands: launch 0 sorts tiles, launch p + 1 is merge pass p (over
+    // the bands with passes > p, one item per kKdistTile outputs)
+    int32_t item_start[kKdistMaxPasses + 1][kMaxKdistBands + 1];
+    int32_t n_rows, n_bands;
+};
+struct MeansInterval {
+    long long lo, len;                  // ranks [lo, lo + len) of a row's band-major order: lo = s_start[band] + e_i
+    int32_t band, chunk_start;          // first partial sum of the interval (one per kKdistTile ranks)
+};
+struct MeansArgs {
+    long long off_rows, off_orders;     // n_rows x const double* each: the rows, and the order every row is averaged by
+    long long off_intervals;            // (g_total + 1) x MeansInterval, band after band; the last one closes chunk_start
+    double* partial;                    // n_rows x n_chunks
+    double* mean;                       // n_rows x g_total
+    double* lower;                      // n_rows x (g_total + n_bands), or nullptr
+    long long first[kMaxKdistBands], count[kMaxKdistBands], s_start[kMaxKdistBands];
+    int32_t g_start[kMaxKdistBands + 1];   // first interval of every band
+    int32_t n_rows, n_bands, g_total, n_chunks;
+};
+void launch_kdist_rank(const RankArgs* d_args, const RankArgs& host, hipStream_t s);
+void launch_kdist_means(const MeansArgs* d_args, const MeansArgs& host, hipStream_t s);
+
 struct ColumnArgs {
     const double* trans[kMaxLayers];
     double layer_T[kMaxLayers];

@@ -4159,4 +4159,245 @@ void launch_ils_convolve(const IlsArgs* d_args, int shape, int n_rows, long long
     else launch_ils_shape<kIlsRowBlock>(d_args, shape, dim3(gx, (n_rows + kIlsRowBlock - 1) / kIlsRowBlock), s);
 }
 
+// ----------------------------------------------------------------------------------------
+// K9: k-distributions (lbl_rank_order_dev, lbl_ranked_means_dev; the definition is in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// Ranking.  A segment is one band of one row.  Point i of it (band-local index) is the pair (key, i): key = the bits of the
+// value in sign-magnitude order after -0 -> +0 and every NaN -> all ones, so that unsigned order of the keys is numpy's
+// ascending order with NaN last, and the index settles every tie in grid order - the stable order.  All pairs of a segment
+// are distinct, so any correct sort gives the same permutation.
+//   kdist_tile_sort_kernel   one workgroup per tile of kKdistTile points: keys built, bitonic network over the next power of
+//                            two of the tile's points in LDS (padded with pairs that sort last);
+//   kdist_merge_kernel       pass p merges runs of kKdistTile << p pairs two by two: one workgroup per kKdistTile outputs finds
+//                            its two input ranges by a merge-path search on the output diagonals, brings them to LDS, every
+//                            thread finds the start of its 8 outputs the same way in LDS and merges them serially.
+// Whichever launch completes a segment (the tile sort for a band of one tile, else the band's last merge pass) writes the
+// results instead of pairs: order = first + index as a double, sorted = the row's value there (gathered, so bit for bit).
+// grid = (work items of one row, rows); the item -> band map is a prefix table of at most 65 entries in the argument block.
+__device__ __forceinline__ unsigned long long kdist_key(double x) {
+    unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    if (x != x) return ~0ull;
+    if (x == 0.0) b = 0ull;
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ bool kdist_less(unsigned long long ka, unsigned int ia, unsigned long long kb, unsigned int ib) {
+    return ka < kb || (ka == kb && ia < ib);
+}
+
+// number of pairs taken from A among the first d outputs of merge(A[0, na), B[0, nb)) (0 <= d <= na + nb)
+template <typename KP, typename IP>
+__device__ __forceinline__ long long kdist_merge_path(KP ak, IP ai, long long na, KP bk, IP bi, long long nb, long long d) {
+    long long lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (kdist_less(ak[mid], ai[mid], bk[d - 1 - mid], bi[d - 1 - mid])) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int kdist_band_of(const int32_t* __restrict__ start, int n_bands, int item) {
+    int b = 0;
+    while (b + 1 < n_bands && item >= start[b + 1]) ++b;
+    return b;
+}
+
+// `total` pairs of LDS (sk, si) leave for the segment's outputs at [at, at + total): pairs, or the results when the segment is complete
+__device__ __forceinline__ void kdist_emit(const RankArgs& A, const unsigned long long* sk, const unsigned int* si, int total,
+                                           bool last, int buf, long long row_at, long long first, const double* __restrict__ x) {
+    if (last) {
+        for (int i = threadIdx.x; i < total; i += 256) {
+            const unsigned int j = si[i];
+            A.order[row_at + i] = (double)(first + (long long)j);
+            if (A.sorted) A.sorted[row_at + i] = x[j];
+        }
+    } else {
+        for (int i = threadIdx.x; i < total; i += 256) {
+            A.keys[buf][row_at + i] = sk[i];
+            A.idx[buf][row_at + i] = si[i];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void kdist_tile_sort_kernel(const RankArgs* __restrict__ Ap) {
+    __shared__ unsigned long long sk[kKdistTile];
+    __shared__ unsigned int si[kKdistTile];
+    const RankArgs& A = *Ap;
+    const int b = kdist_band_of(A.item_start[0], A.n_bands, blockIdx.x);
+    const long long t0 = (long long)((int)blockIdx.x - A.item_start[0][b]) * kKdistTile;
+    const long long count = A.count[b], first = A.first[b];
+    if (t0 >= count) return;                                                        // (workgroup-uniform; never with the host's grid)
+    const int valid = (int)(count - t0 < kKdistTile ? count - t0 : kKdistTile);
+    const double* __restrict__ x = ((const double* const*)((const char*)Ap + A.off_rows))[blockIdx.y] + first;
+    int m = 2;
+    while (m < valid) m <<= 1;
+    for (int i = threadIdx.x; i < m; i += 256) {
+        const bool in = i < valid;
+        sk[i] = in ? kdist_key(x[t0 + i]) : ~0ull;
+        si[i] = in ? (unsigned int)(t0 + i) : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    for (int k = 2; k <= m; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (m >> 1); t += 256) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const unsigned long long ka = sk[lo], kb = sk[hi];
+                const unsigned int ia = si[lo], ib = si[hi];
+                const bool up = (lo & k) == 0;
+                if (up ? kdist_less(kb, ib, ka, ia) : kdist_less(ka, ia, kb, ib)) {
+                    sk[lo] = kb; sk[hi] = ka;
+                    si[lo] = ib; si[hi] = ia;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    kdist_emit(A, sk, si, valid, A.passes[b] == 0, 0, (long long)blockIdx.y * A.s_total + A.s_start[b] + t0, first, x);
+}
+
+__global__ __launch_bounds__(256) void kdist_merge_kernel(const RankArgs* __restrict__ Ap, int p) {
+    __shared__ unsigned long long sk[kKdistTile];
+    __shared__ unsigned int si[kKdistTile];
+    __shared__ long long split[2];
+    const RankArgs& A = *Ap;
+    const int b = kdist_band_of(A.item_start[p + 1], A.n_bands, blockIdx.x);
+    const long long c0 = (long long)((int)blockIdx.x - A.item_start[p + 1][b]) * kKdistTile;
+    const long long count = A.count[b], first = A.first[b];
+    if (c0 >= count) return;                                                        // (workgroup-uniform; never with the host's grid)
+    const long long W = (long long)kKdistTile << p;
+    const long long base = c0 & ~(2 * W - 1);                                       // the pair of runs this tile of outputs lies in
+    const long long lenA = count - base < W ? count - base : W;
+    const long long lenB = count - base - lenA < W ? count - base - lenA : W;
+    const long long d0 = c0 - base, d1 = d0 + kKdistTile < lenA + lenB ? d0 + kKdistTile : lenA + lenB;
+    const long long seg = (long long)blockIdx.y * A.s_total + A.s_start[b];
+    const unsigned long long* __restrict__ ak = A.keys[p & 1] + seg + base;
+    const unsigned int* __restrict__ ai = A.idx[p & 1] + seg + base;
+    if (threadIdx.x == 0 || threadIdx.x == 64)
+        split[threadIdx.x >> 6] = kdist_merge_path(ak, ai, lenA, ak + lenA, ai + lenA, lenB, threadIdx.x ? d1 : d0);
+    __syncthreads();
+    const long long a0 = split[0], b0 = d0 - a0;
+    const int nA = (int)(split[1] - a0), total = (int)(d1 - d0), nB = total - nA;
+    for (int i = threadIdx.x; i < total; i += 256) {
+        const long long src = i < nA ? a0 + i : lenA + b0 + (i - nA);
+        sk[i] = ak[src];
+        si[i] = ai[src];
+    }
+    __syncthreads();
+    // the 8 outputs [8 t, 8 t + 8) of this thread
+    const int d = min((int)threadIdx.x * 8, total);
+    int pa = (int)kdist_merge_path(sk, si, (long long)nA, sk + nA, si + nA, (long long)nB, (long long)d);
+    int pb = nA + (d - pa);
+    const int endB = nA + nB;
+    unsigned long long rk[8];
+    unsigned int ri[8];
+    unsigned long long ka = pa < nA ? sk[pa] : 0ull, kb = pb < endB ? sk[pb] : 0ull;
+    unsigned int ia = pa < nA ? si[pa] : 0u, ib = pb < endB ? si[pb] : 0u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const bool takeA = pb >= endB || (pa < nA && kdist_less(ka, ia, kb, ib));
+        rk[i] = takeA ? ka : kb;
+        ri[i] = takeA ? ia : ib;
+        if (takeA) {
+            ++pa;
+            if (pa < nA) { ka = sk[pa]; ia = si[pa]; }
+        } else {
+            ++pb;
+            if (pb < endB) { kb = sk[pb]; ib = si[pb]; }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (d + i < total) { sk[d + i] = rk[i]; si[d + i] = ri[i]; }
+    }
+    __syncthreads();
+    const double* __restrict__ x = ((const double* const*)((const char*)Ap + A.off_rows))[blockIdx.y] + first;
+    kdist_emit(A, sk, si, total, A.passes[b] == p + 1, (p + 1) & 1, seg + c0, first, x);
+}
+
+void launch_kdist_rank(const RankArgs* d_args, const RankArgs& host, hipStream_t s) {
+    const int nb = host.n_bands;
+    if (host.n_rows < 1 || nb < 1) return;
+    hipLaunchKernelGGL(kdist_tile_sort_kernel, dim3(host.item_start[0][nb], host.n_rows), dim3(256), 0, s, d_args);
+    for (int p = 0; p < kKdistMaxPasses; ++p)
+        if (host.item_start[p + 1][nb] > 0)
+            hipLaunchKernelGGL(kdist_merge_kernel, dim3(host.item_start[p + 1][nb], host.n_rows), dim3(256), 0, s, d_args, p);
+}
+
+// Means over intervals of the rank.  kdist_partial_kernel: one workgroup per kKdistTile ranks of one interval of one row reads
+// the order (coalesced), gathers the row there and adds: thread t the ranks t, t + 256, ... in turn, the wave's 64 sums by a
+// fixed shuffle tree, the four waves' sums in wave order.  kdist_means_kernel: one wave per (row, interval) adds the
+// interval's partial sums - lane l the partials l, l + 64, ... in turn, then the same tree - divides by the number of ranks
+// and fetches the order statistics at the edges.  No atomics, one order of additions whatever else is in the call.  Every sum
+// starts from -0.0, the identity of IEEE addition for every value (0.0 would turn -0.0 into +0.0); an interval of one rank is
+// copied.  An order value outside its band is clamped into it: no read leaves the row.
+__device__ __forceinline__ double kdist_wave_sum(double v) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ long long kdist_point(double o, long long first, long long count) {
+    const double lo = (double)first, hi = (double)(first + count - 1);      // (exact: grid indices are far below 2^53)
+    o = o >= lo ? o : lo;                                                   // (NaN: first)
+    return (long long)(o <= hi ? o : hi);
+}
+
+__global__ __launch_bounds__(256) void kdist_partial_kernel(const MeansArgs* __restrict__ Ap) {
+#pragma clang fp contract(off)
+    __shared__ double sh[4];
+    const MeansArgs& A = *Ap;
+    const MeansInterval* __restrict__ I = (const MeansInterval*)((const char*)Ap + A.off_intervals);
+    int lo = 0, hi = A.g_total - 1;                       // the interval of this chunk: the last one that starts at or before it
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (I[mid].chunk_start <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const MeansInterval iv = I[lo];
+    const long long r0 = (long long)((int)blockIdx.x - iv.chunk_start) * kKdistTile;
+    const int m = (int)(iv.len - r0 < kKdistTile ? iv.len - r0 : kKdistTile);
+    const long long first = A.first[iv.band], count = A.count[iv.band];
+    const double* __restrict__ x = ((const double* const*)((const char*)Ap + A.off_rows))[blockIdx.y];
+    const double* __restrict__ order = ((const double* const*)((const char*)Ap + A.off_orders))[blockIdx.y] + iv.lo + r0;
+    double acc = -0.0;
+    for (int i = threadIdx.x; i < m; i += 256) acc += x[kdist_point(order[i], first, count)];
+    acc = kdist_wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) A.partial[(size_t)blockIdx.y * (size_t)A.n_chunks + blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+__global__ __launch_bounds__(256) void kdist_means_kernel(const MeansArgs* __restrict__ Ap) {
+#pragma clang fp contract(off)
+    const MeansArgs& A = *Ap;
+    const int g = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (g >= A.g_total) return;                           // (wave-uniform; no barrier below)
+    const MeansInterval* __restrict__ I = (const MeansInterval*)((const char*)Ap + A.off_intervals);
+    const MeansInterval iv = I[g];
+    const int c1 = I[g + 1].chunk_start;
+    const double* __restrict__ part = A.partial + (size_t)blockIdx.y * (size_t)A.n_chunks;
+    double acc = -0.0;
+    for (int c = iv.chunk_start + lane; c < c1; c += 64) acc += part[c];
+    acc = kdist_wave_sum(acc);
+    if (lane != 0) return;
+    const long long first = A.first[iv.band], count = A.count[iv.band];
+    const double* __restrict__ x = ((const double* const*)((const char*)Ap + A.off_rows))[blockIdx.y];
+    const double* __restrict__ order = ((const double* const*)((const char*)Ap + A.off_orders))[blockIdx.y];
+    const double at_edge = x[kdist_point(order[iv.lo], first, count)];
+    A.mean[(size_t)blockIdx.y * (size_t)A.g_total + g] = iv.len == 1 ? at_edge : acc / (double)iv.len;
+    if (A.lower) {
+        double* lower = A.lower + (size_t)blockIdx.y * (size_t)(A.g_total + A.n_bands) + g + iv.band;
+        lower[0] = at_edge;
+        if (g + 1 == A.g_start[iv.band + 1]) lower[1] = x[kdist_point(order[A.s_start[iv.band] + count - 1], first, count)];
+    }
+}
+
+void launch_kdist_means(const MeansArgs* d_args, const MeansArgs& host, hipStream_t s) {
+    if (host.n_rows < 1 || host.g_total < 1) return;
+    hipLaunchKernelGGL(kdist_partial_kernel, dim3(host.n_chunks, host.n_rows), dim3(256), 0, s, d_args);
+    hipLaunchKernelGGL(kdist_means_kernel, dim3((host.g_total + 3) / 4, host.n_rows), dim3(256), 0, s, d_args);
+}
+
 }  // namespace lbl

@@ -1544,6 +1544,178 @@ def convolve(instrument, spectra, rangeMin, rangeMax):
     return result[0] if spectra.ndim == 1 else result
 
 
+# ----------------------------------------------------------------------------------------
+# k-distributions (kDistribution, Atmosphere.kDistribution; beyond the reference)
+# ----------------------------------------------------------------------------------------
+def gIntervals(g=16, count=None):
+    """Rank edges e_0 = 0 < e_1 < ... < e_G = count of the g intervals of a band of ``count`` points, int64.
+    - ``g`` an integer G in 1..256: the g edges are the cumulative Gauss-Legendre weights on [0, 1],
+      numpy.r_[0, numpy.cumsum(leggauss(G)[1] / 2)] with the last one set to exactly 1;
+    - ``g`` an explicit increasing sequence of g edges from 0 to 1 (at most 256 intervals).
+    e_i = int(numpy.rint(g_i * count)).  ValueError for anything else, and when an interval comes out empty."""
+    nmax = 256
+    try:
+        count = int(count)
+    except (TypeError, ValueError):
+        raise ValueError("count: the number of points of the band, not %r" % (count,))
+    if count < 1:
+        raise ValueError("count: the band holds no point")
+    if isinstance(g, (int, np.integer)) and not isinstance(g, bool):
+        if not 1 <= int(g) <= nmax:
+            raise ValueError("g: %d intervals, 1..%d are possible" % (int(g), nmax))
+        ge = np.r_[0.0, np.cumsum(np.polynomial.legendre.leggauss(int(g))[1] / 2.0)]
+        ge[-1] = 1.0
+    else:
+        try:
+            ge = np.array(g, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("g: an integer 1..%d or an increasing sequence of g edges from 0 to 1, not %r" % (nmax, g))
+        if ge.ndim != 1 or not 2 <= ge.size <= nmax + 1:
+            raise ValueError("g: 2..%d edges (1..%d intervals), got shape %s" % (nmax + 1, nmax, ge.shape))
+        if not (np.all(np.isfinite(ge)) and ge[0] == 0.0 and ge[-1] == 1.0):
+            raise ValueError("g: the edges must run from 0 to 1")
+        if not np.all(np.diff(ge) > 0.0):
+            raise ValueError("g: the edges must increase")
+    edges = np.rint(ge * count).astype(np.int64)
+    empty = np.flatnonzero(np.diff(edges) < 1)
+    if empty.size:
+        raise ValueError("g: interval %d of %d holds none of the band's %d points" % (int(empty[0]), edges.size - 1, count))
+    return edges
+
+
+class KDistribution:
+    """What kDistribution and Atmosphere.kDistribution return.  Per band (a list with one entry per band, or the single
+    band's arrays alone when ``bands`` was None): ``k`` (rows, G) mean of the row over every g interval; ``kLower`` (rows,
+    G + 1) the row's value at every interval's first rank and, last, at the band's last rank; ``weight`` (G,) the intervals'
+    share of the band's points; ``edges`` (G + 1,) their rank edges (gIntervals); ``planck`` (rows, G) the mean Planck
+    function over the same points, or None.  With spectra=True also ``order`` (int64 grid indices) and ``sorted`` (the
+    values in that order), (rows, count) each for reference=None and (count,) - the reference row's - otherwise; else None.
+    ``reference``: the row whose order was used, or None."""
+
+    def __init__(self, k, kLower, weight, edges, planck=None, order=None, sorted=None, reference=None):
+        self.k = k
+        self.kLower = kLower
+        self.weight = weight
+        self.edges = edges
+        self.planck = planck
+        self.order = order
+        self.sorted = sorted
+        self.reference = reference
+
+    def __repr__(self):
+        one = isinstance(self.k, np.ndarray)
+        return "KDistribution(bands=%s, intervals=%s, reference=%r)" % (
+            "None" if one else len(self.k), self.weight.size if one else [w.size for w in self.weight], self.reference)
+
+
+class _KdistBuffers:
+    """Device buffers of the k-distribution calls by name, each kept while it is large enough."""
+
+    def __init__(self, owner=None):
+        self.bufs = {}
+        if owner is not None:
+            import weakref
+            weakref.finalize(owner, _free_buffers, self.bufs)
+
+    def get(self, ctx, name, n):
+        b = self.bufs.get(name)
+        if b is not None and (b.h is None or b.ctx is not ctx or b.n < n):
+            if b.h is not None and b.ctx.h:
+                b.free()
+            b = None
+        if b is None:
+            b = self.bufs[name] = ctx.buffer(max(int(n), 1))
+        return b
+
+    def free(self):
+        _free_buffers(self.bufs)
+
+
+def _kdist_checks(rangeMin, rangeMax, n, n_rows, bands, g, reference):
+    """What both k-distribution calls check before the device is touched: (band_first, band_count, edges per band)."""
+    if n_rows > nat.limit("kdist_rows"):
+        raise ValueError("%d rows, at most %d" % (n_rows, nat.limit("kdist_rows")))
+    if reference is not None:
+        if isinstance(reference, bool) or not isinstance(reference, (int, np.integer)) or not 0 <= int(reference) < n_rows:
+            raise ValueError("reference: None or the index of one of the %d rows, not %r" % (n_rows, reference))
+    first, count = _flux_bands(rangeMin, rangeMax, n, bands)
+    return first, count, [gIntervals(g, c) for c in count]
+
+
+def _kdist_run(ctx, keep, n, rows, first, count, edges, reference, spectra, bands, planck=None):
+    """K9 over ``rows`` = [(Buffer, offset)]: one ranking (of every row, or of the reference row), the means of all rows and,
+    with ``planck`` = (rangeMin, rangeMax, [T of every row]), of every row's Planck function made into one kept buffer."""
+    M, nb = len(rows), len(count)
+    S, G = int(sum(count)), int(sum(e.size - 1 for e in edges))
+    ranked = list(rows) if reference is None else [rows[int(reference)]]
+    order = keep.get(ctx, "order", len(ranked) * S)
+    srt = keep.get(ctx, "sorted", len(ranked) * S) if spectra else None
+    need = ctx.rank_order_workspace(len(ranked), n, count)
+    ctx.rank_order_dev(n, ranked, first, count, order, sorted=srt, work=keep.get(ctx, "rank_work", need) if need else None)
+    orders = [(order, r * S if reference is None else 0) for r in range(M)]
+    work = keep.get(ctx, "means_work", ctx.ranked_means_workspace(M, count, edges))
+    mean = keep.get(ctx, "mean", (2 if planck else 1) * M * G)
+    lower = keep.get(ctx, "lower", M * (G + nb))
+    ctx.ranked_means_dev(n, rows, orders, first, count, edges, work, mean, lower=lower)
+    if planck:
+        lo, hi, temps = planck
+        row = keep.get(ctx, "planck_row", n)
+        for l, T in enumerate(temps):                     # in stream: the row is overwritten once its means are enqueued
+            ctx.planck_dev(lo, hi, n, float(T), row)
+            ctx.ranked_means_dev(n, [(row, 0)], [orders[l]], first, count, edges, work, mean, mean_offset=(M + l) * G)
+    v = mean.download((2 if planck else 1) * M * G).reshape(-1, M, G)
+    lw = lower.download(M * (G + nb)).reshape(M, G + nb)
+    k, kl, pl, weight, od, sd = [], [], [], [], [], []
+    if spectra:
+        o = order.download(len(ranked) * S).reshape(len(ranked), S).astype(np.int64)
+        sv = srt.download(len(ranked) * S).reshape(len(ranked), S)
+    g0 = s0 = 0
+    for b in range(nb):
+        Gb = edges[b].size - 1
+        k.append(v[0][:, g0:g0 + Gb].copy())
+        kl.append(lw[:, g0 + b:g0 + b + Gb + 1].copy())
+        if planck:
+            pl.append(v[1][:, g0:g0 + Gb].copy())
+        weight.append(np.diff(edges[b]) / float(count[b]))
+        if spectra:
+            sl = (slice(None) if reference is None else 0, slice(s0, s0 + count[b]))
+            od.append(o[sl].copy())
+            sd.append(sv[sl].copy())
+        g0 += Gb
+        s0 += count[b]
+    pick = (lambda v: v[0]) if bands is None else (lambda v: v)
+    return KDistribution(pick(k), pick(kl), pick(weight), pick([e.copy() for e in edges]), pick(pl) if planck else None,
+                         pick(od) if spectra else None, pick(sd) if spectra else None,
+                         None if reference is None else int(reference))
+
+
+def kDistribution(rows, rangeMin, rangeMax, bands=None, g=16, reference=None, spectra=False):
+    """k-distributions of host rows on the base grid linspace(rangeMin, rangeMax, n), ranked and averaged on the device:
+    ``rows`` of shape (n,) or (M, n) - absorption coefficients, usually.  In every band (``bands`` as Atmosphere.fluxes takes
+    them, at most 64; None: the whole range) a row's points are put in ascending order - exactly first +
+    numpy.argsort(row[first:first + count], kind="stable"): -0.0 and 0.0 tie, NaN after +inf, ties in grid order - and the
+    row is averaged over the intervals gIntervals(g, count) of that rank.  reference=None ranks every row by itself (the
+    classical k-distribution); reference=r averages every row over the point sets of row r's order (one sort, M gathers),
+    which keeps the spectral correlation between the rows.  Sums are taken in one fixed order: the same inputs give the same
+    bits, and a row's result does not depend on the rows beside it.  Returns a KDistribution (for a 1-D input every
+    per-row array holds one row); ``spectra``: also the order and the sorted values."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim not in (1, 2) or rows.shape[-1] < 2:
+        raise ValueError("spectra: shape (n,) or (M, n) on the base grid, got %s" % (rows.shape,))
+    rows2d = rows.reshape(-1, rows.shape[-1])
+    M, n = rows2d.shape
+    if M < 1:
+        raise ValueError("spectra: no rows")
+    first, count, edges = _kdist_checks(rangeMin, rangeMax, n, M, bands, g, reference)
+    ctx = _ctx()
+    keep = _KdistBuffers()
+    try:
+        src = keep.get(ctx, "rows", M * n).upload(rows2d.reshape(-1))
+        return _kdist_run(ctx, keep, n, [(src, r * n) for r in range(M)], first, count, edges, reference, spectra, bands)
+    finally:
+        keep.free()
+
+
 class Observation:
     """What Atmosphere.observe returns.  ``wavenumber``: the channel centres, (C,); ``radiance``: channel radiance in the
     units of transmission(); ``brightnessTemperature``: its inverse Planck at the centre, K; ``mu``: the viewing cosine.
@@ -1835,6 +2007,25 @@ class Atmosphere(list):
         return Observation(instrument.centres.copy(), v[0].copy(), float(mu_k[0]),
                            temperatureJacobian=v[1:1 + nl].copy() if jacobians else None,
                            opticalDepthJacobian=v[1 + nl:].copy() if jacobians else None)
+
+    def kDistribution(self, bands=None, g=16, reference=None, planck=False, spectra=False):
+        """k-distributions of the column's bands (beyond the reference): every layer's absorption coefficient (getAbsCoef)
+        ranked in every band and averaged over g intervals on the device, as kDistribution() defines it, with one row per
+        layer in list order.  reference=None ranks every layer by itself; reference=r averages every layer over the point
+        sets of layer r's order (the mapped distribution: one sort and L gathers).  ``planck``: also the mean of
+        planckWavenumber(nu, T_l) over the same point sets, KDistribution.planck.  ``spectra``: also the order and the sorted
+        coefficients.  The absorption coefficients are the resident ones: after transmission() or fluxes() nothing is
+        accumulated again.  Everything is validated (ValueError) before the device is touched."""
+        layers, n = self._column_layers()
+        first_layer = layers[0]
+        first, count, edges = _kdist_checks(first_layer.rangeMin, first_layer.rangeMax, n, len(layers), bands, g, reference)
+        ctx = _ctx()
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        keep = self.__dict__.get("_kdist_state")
+        if keep is None:
+            keep = self.__dict__["_kdist_state"] = _KdistBuffers(self)
+        return _kdist_run(ctx, keep, n, [(b, 0) for b in kbufs], first, count, edges, reference, bool(spectra), bands,
+                          planck=(first_layer.rangeMin, first_layer.rangeMax, [L.T for L in layers]) if planck else None)
 
     def _jacobian_terms(self, ctx, layers, n, plan):
         """The molecule terms of jacobians(): every molecule's own absorption coefficient k_(m,l), as (buffers, layer index
