@@ -97,6 +97,7 @@ int lbl_abi_version(void);
  *   "ils_table"             values of its tabulated line shape: 4096
  *   "kdist_rows"            rows of lbl_rank_order_dev / lbl_ranked_means_dev: 512
  *   "kdist_intervals"       rank intervals of one band of lbl_ranked_means_dev: 256
+ *   "ray_paths"             rays of lbl_ray_radiance_dev: 512      "ray_segments": their segments, all rays together: 65536
  * Unknown name: LBL_ERR_BAD_ARG. */
 int lbl_limit(const char* name, int64_t* value);
 int lbl_device_count(int* count);
@@ -423,6 +424,37 @@ int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_c
                             int n_bands, const int64_t* band_first, const int64_t* band_count,
                             int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
                             lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra);
+
+/* ---- ray paths (beyond the reference; ABI 5, backward compatible) -----------------------------------------------------
+ * pyrad_amd.model.Atmosphere.radiance: the radiance that arrives along arbitrary lines of sight through the column - upward
+ * looking, slant from a level inside it, limb - many rays per call.  Layers, abs_coef, T and the grid as lbl_column_flux_dev
+ * takes them.  Ray r owns the segments s = ray_first[r] .. ray_first[r + 1] - 1 in the order the light travels (the first
+ * segment is the one farthest from the observer); segment s crosses seg_length[s] cm of layer seg_layer[s].  A layer may be
+ * skipped, or crossed more than once.  At grid point nu_j:
+ *   I    = source_kind[r] == 1 ? (I_source[j] or B(nu_j, source_T)) : 0        (0: cold space, 1: the surface source)
+ *   Ttot = 1
+ *   per segment, l = seg_layer[s]:   tau = k_l(nu_j) * seg_length[s]      t = exp(-tau)      B = B(nu_j, T_l)
+ *                                    I <- t I + (1 - t) B                  Ttot <- Ttot t
+ *   radiance[r * n + j] = I          transmittance[r * n + j] = Ttot       (transmittance may be NULL)
+ * A ray without segments returns its source and transmittance 1.
+ * Arithmetic: lbl_column_flux_dev's step (the same Planck term, exp and update), so a ray through the layers 0 .. L-1 once,
+ * bottom to top, with seg_length = depth_l and the surface source gives that call's up_top for the angle set {(1, 1.0)} bit
+ * for bit.  Nothing is summed: no reductions and no atomics, the same inputs give the same bits, and a ray's result does not
+ * depend on the other rays of the call.
+ * LBL_ERR_BAD_ARG: a NULL ctx, list or radiance; n_layers outside 1..lbl_limit("layers_per_column"); n < 1; n_rays outside
+ * 1..lbl_limit("ray_paths") = 512 (= "ils_rows": every ray can be a row of one lbl_ils_convolve_dev call); ray_first[0] != 0
+ * or a ray_first that decreases; more than lbl_limit("ray_segments") = 65536 segments in all; a segment layer outside
+ * [0, n_layers); a length that is negative, NaN or infinite; T[l] not > 0; a source_kind other than 0 or 1; a ray of kind 1
+ * with neither I_source nor source_T > 0; a buffer too short (radiance and transmittance hold n_rays x n);
+ * "sweep_ieee_divisions" 1, as for the fold.  Everything is checked before anything is enqueued; the host arrays are copied
+ * and not retained.  Stream-ordered on the context's stream; nothing is synchronised. */
+int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                         double range_min, double range_max, int64_t n,
+                         int n_rays, const int32_t* ray_first,      /* n_rays + 1, ray_first[0] = 0, non-decreasing */
+                         const int32_t* seg_layer, const double* seg_length,   /* ray_first[n_rays] each; cm */
+                         const int32_t* source_kind,                /* per ray: 0 cold space (I = 0), 1 surface source */
+                         lbl_buffer* I_source, double source_T,
+                         lbl_buffer* radiance, lbl_buffer* transmittance /* may be NULL */);
 
 /* ---- instrument channels (beyond the reference; ABI 5, backward compatible) -------------------------------------------
  * pyrad_amd.model.convolve / Atmosphere.observe: n_rows device-resident spectra on the base grid linspace(range_min,

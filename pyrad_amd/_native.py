@@ -105,6 +105,9 @@ SIGNATURES = {
     "lbl_column_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, _P,
                                           C.c_double, C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                           C.c_int, C.POINTER(_P), C.POINTER(C.c_int32), _P, _P, _P]),
+    "lbl_ray_radiance_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P, C.c_double,
+                                       _P, _P]),
     "lbl_ils_convolve_dev": (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64),
                                        C.c_int64, _D, _D, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_int,
                                        C.c_double, _D, _P]),
@@ -200,7 +203,7 @@ _limits = {}
 def limit(name: str) -> int:
     """A fixed size of the library (lbl_limit): "merged_lists_per_job", "arrays_per_layer", "arrays_per_sum",
     "arrays_per_column", "layers_per_column", "jobs_per_batch", "flux_angles", "flux_bands", "jacobian_terms", "ils_rows",
-    "ils_channels", "ils_table", "kdist_rows", "kdist_intervals"."""
+    "ils_channels", "ils_table", "kdist_rows", "kdist_intervals", "ray_paths", "ray_segments"."""
     if name not in _limits:
         v = C.c_int64()
         rc = load().lbl_limit(name.encode(), C.byref(v))
@@ -548,6 +551,24 @@ class Context:
                                band_first, band_count),
             len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]), _arr(C.c_int32, [int(l) for l in term_layer]),
             _hb(jac), _hb(ln_tau_spectra), _hb(T_spectra)))
+
+    def ray_radiance_dev(self, abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length, source_kind,
+                         radiance, I_source=None, source_T=0.0, transmittance=None):
+        """Radiance along ray paths through a column (lbl_ray_radiance_dev): ray r crosses the segments ray_first[r] ..
+        ray_first[r + 1] - 1 (``seg_layer``, ``seg_length`` in cm) in the order the light travels, from cold space
+        (``source_kind`` 0) or the surface source (1: ``I_source`` or B(nu, ``source_T``)); ``radiance`` and the optional
+        ``transmittance`` receive len(source_kind) x n doubles, row-major."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
+        seg_length = _as_f64(seg_length)
+        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length):
+            raise ValueError("ray_radiance_dev: one ray_first per ray and one more, one length per segment layer")
+        self.check(self.lib.lbl_ray_radiance_dev(
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
+            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
+            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T), _hb(radiance),
+            _hb(transmittance)))
 
     def ils_convolve_dev(self, range_min, range_max, n, rows, position, width, first, count, shape, out, table=None,
                          table_half=0.0):

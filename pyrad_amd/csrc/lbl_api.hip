@@ -394,6 +394,8 @@ extern "C" int lbl_limit(const char* name, int64_t* value) {
     else if (!strcmp(name, "ils_table")) *value = kMaxIlsTable;                // ... the values of a tabulated line shape
     else if (!strcmp(name, "kdist_rows")) *value = kMaxKdistRows;              // rows of lbl_rank_order_dev / lbl_ranked_means_dev
     else if (!strcmp(name, "kdist_intervals")) *value = kMaxKdistIntervals;    // ... the intervals of one band
+    else if (!strcmp(name, "ray_paths")) *value = kMaxRayPaths;                // rays of lbl_ray_radiance_dev
+    else if (!strcmp(name, "ray_segments")) *value = kMaxRaySegments;          // ... the segments of all of them together
     else return LBL_ERR_BAD_ARG;
     return LBL_OK;
 }

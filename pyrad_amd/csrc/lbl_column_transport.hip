@@ -1,5 +1,6 @@
-// Column transport (include/pyrad_hip.h, "level fluxes" and "Jacobians"): argument checking and the launch sequences of
-// lbl_column_flux_dev and lbl_column_jacobian_dev.  The kernels are K5c and K5d of lbl_kernels.hip; the context's internals
+// Column transport (include/pyrad_hip.h, "level fluxes", "Jacobians" and "ray paths"): argument checking and the launch
+// sequences of lbl_column_flux_dev, lbl_column_jacobian_dev and lbl_ray_radiance_dev.  The kernels are K5c, K5d and K5e of
+// lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -11,6 +12,8 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
+#include <map>
 #include <new>
 #include <stdexcept>
 #include <vector>
@@ -199,4 +202,106 @@ extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* c
                       [&](const JacArgs* d, double* partial, int b, hipStream_t s) {
         launch_column_jacobian(d, n_layers, n_angles, n_terms, band_first[b], band_count[b], partial, buffer_data(jac) + (size_t)b * nv, s);
     });
+} LBL_GUARD_END(ctx)
+
+static size_t round8(size_t b) { return (b + 7) & ~(size_t)7; }
+
+extern "C" int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                    double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
+                                    const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
+                                    lbl_buffer* I_source, double source_T, lbl_buffer* radiance,
+                                    lbl_buffer* transmittance) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    if (n_layers < 1 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d layers", kMaxLayers);
+    if (n < 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "n must be >= 1");
+    if (!abs_coef || !T) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if (ctx_sweep_ieee(ctx))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", "ray paths");
+    if (n_rays < 1 || n_rays > kMaxRayPaths) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d rays", kMaxRayPaths);
+    if (!ray_first || !source_kind) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL ray list");
+    if (ray_first[0] != 0) return column_fail(ctx, LBL_ERR_BAD_ARG, "ray_first[0] must be 0");
+    for (int r = 0; r < n_rays; ++r)
+        if (ray_first[r + 1] < ray_first[r]) return column_fail(ctx, LBL_ERR_BAD_ARG, "ray %d: ray_first decreases", r);
+    const int n_seg = ray_first[n_rays];
+    if (n_seg > kMaxRaySegments) return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d segments", kMaxRaySegments);
+    if (n_seg > 0 && (!seg_layer || !seg_length)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL segment list");
+    for (int s = 0; s < n_seg; ++s) {
+        if (seg_layer[s] < 0 || seg_layer[s] >= n_layers)
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: layer %d outside [0, %d)", s, (int)seg_layer[s], n_layers);
+        if (!(seg_length[s] >= 0) || !std::isfinite(seg_length[s]))
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: length must be finite and >= 0", s);
+    }
+    int rc;
+    if ((rc = ctx_check_buffer(ctx, I_source, n, "I_source", false))) return rc;
+    for (int r = 0; r < n_rays; ++r) {
+        if (source_kind[r] != 0 && source_kind[r] != 1)
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "ray %d: source_kind must be 0 (space) or 1 (surface)", r);
+        if (source_kind[r] == 1 && !I_source && !(source_T > 0))
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "ray %d: a surface source needs I_source or source_T > 0", r);
+    }
+    if (n > INT64_MAX / n_rays) return column_fail(ctx, LBL_ERR_BAD_ARG, "n_rays x n overflows");
+    if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_rays * n, "radiance", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, transmittance, (int64_t)n_rays * n, "transmittance", false))) return rc;
+
+    // the argument block: header, ray_first, seg_layer, seg_length, source_kind, order
+    RayArgs a;
+    memset((void*)&a, 0, sizeof a);
+    double pa = 0.0;
+    for (int l = 0; l < n_layers; ++l) {
+        if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
+        if (!(T[l] > 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
+        a.abs_coef[l] = buffer_data(abs_coef[l]);
+        planck_budget_constants(T[l], &pa, &a.pbkT[l]);
+        a.pbkT_min = l == 0 ? a.pbkT[l] : std::min(a.pbkT_min, a.pbkT[l]);
+        a.pbkT_max = l == 0 ? a.pbkT[l] : std::max(a.pbkT_max, a.pbkT[l]);
+    }
+    planck_budget_constants(source_T > 0 ? source_T : 1.0, &pa, &a.pbk_surface);
+    a.pa = pa;
+    a.start = range_min; a.stop = range_max; a.step = grid_step(range_min, range_max, n);
+    a.I_surface = I_source ? buffer_data(I_source) : nullptr;
+    a.n = n;
+    a.n_layers = n_layers;
+    a.radiance = buffer_data(radiance);
+    a.transmittance = transmittance ? buffer_data(transmittance) : nullptr;
+    a.n_rays = n_rays;
+    size_t off = round8(sizeof a);
+    a.off_ray_first = (long long)off;   off += round8((size_t)(n_rays + 1) * sizeof(int32_t));
+    a.off_seg_layer = (long long)off;   off += round8((size_t)n_seg * sizeof(int32_t));
+    a.off_seg_length = (long long)off;  off += (size_t)n_seg * sizeof(double);
+    a.off_source_kind = (long long)off; off += round8((size_t)n_rays * sizeof(int32_t));
+    a.off_order = (long long)off;       off += round8((size_t)n_rays * sizeof(int32_t));
+    // Bundles: rays with one layer sequence (and at least one segment), kRayBundle at a time in the order they come; what
+    // is left of every sequence, and the rays without segments, go one by one.  (A ray's arithmetic is the same either way.)
+    std::vector<int32_t> order, single;
+    {
+        std::map<std::vector<int32_t>, std::vector<int32_t>> open;
+        for (int r = 0; r < n_rays; ++r) {
+            if (ray_first[r + 1] == ray_first[r]) { single.push_back(r); continue; }
+            auto& waiting = open[std::vector<int32_t>(seg_layer + ray_first[r], seg_layer + ray_first[r + 1])];
+            waiting.push_back(r);
+            if ((int)waiting.size() == kRayBundle) {
+                order.insert(order.end(), waiting.begin(), waiting.end());
+                waiting.clear();
+            }
+        }
+        for (auto& kv : open) single.insert(single.end(), kv.second.begin(), kv.second.end());
+    }
+    a.n_bundles = (int32_t)order.size() / kRayBundle;
+    order.insert(order.end(), single.begin(), single.end());
+    std::vector<char> blk(off, 0);
+    memcpy(blk.data(), (const void*)&a, sizeof a);
+    memcpy(blk.data() + a.off_ray_first, ray_first, (size_t)(n_rays + 1) * sizeof(int32_t));
+    if (n_seg > 0) {
+        memcpy(blk.data() + a.off_seg_layer, seg_layer, (size_t)n_seg * sizeof(int32_t));
+        memcpy(blk.data() + a.off_seg_length, seg_length, (size_t)n_seg * sizeof(double));
+    }
+    memcpy(blk.data() + a.off_source_kind, source_kind, (size_t)n_rays * sizeof(int32_t));
+    memcpy(blk.data() + a.off_order, order.data(), (size_t)n_rays * sizeof(int32_t));
+
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    launch_ray_radiance((const RayArgs*)d_args, n, n_rays, a.n_bundles, ctx_stream(ctx));
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
 } LBL_GUARD_END(ctx)

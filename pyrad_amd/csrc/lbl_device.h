@@ -273,10 +273,30 @@ void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long
 void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first, long long count,
                             double* partial, double* jac, hipStream_t s);
 
+// Ray paths (K5e, lbl_column_transport.hip: lbl_ray_radiance_dev): the fold along an ordered list of (layer, path length)
+// segments per ray.  One argument block per call: this header (of ColumnRT the layers' abs_coef and pbkT, the grid and the
+// surface source are used), then the tables it names by their byte offset from the block's start, as IlsArgs does.
+constexpr int kMaxRayPaths = 512;            // = kMaxIlsRows: every ray can be a row of one lbl_ils_convolve_dev call
+constexpr int kMaxRaySegments = 65536;        // of all rays of a call together
+constexpr int kRayBundle = 4;                 // rays with one layer sequence that a workgroup carries in registers
+struct RayArgs : ColumnRT {
+    long long off_ray_first;            // (n_rays + 1) x int32: ray r owns the segments [ray_first[r], ray_first[r + 1])
+    long long off_seg_layer;            // n_segments x int32
+    long long off_seg_length;           // n_segments doubles, cm
+    long long off_source_kind;          // n_rays x int32: 0 cold space, 1 the surface source
+    long long off_order;                // n_rays x int32: the rays in dispatch order - kRayBundle n_bundles rays bundle after
+                                        // bundle (the rays of a bundle cross the same layers in the same order), then the rest
+    double* radiance;                   // n_rays x n, row-major
+    double* transmittance;              // likewise, or nullptr
+    int32_t n_rays, n_bundles;
+};
+void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s);
+
 // Instrument channels (K8, lbl_instrument.hip: lbl_ils_convolve_dev): n_rows spectra on the base grid convolved with an
 // instrument line shape onto n_channels channels.  One argument block per call: this header, then the arrays it names by
 // their byte offset from the block's start (the block's device address is known only after it is uploaded).
 constexpr int kMaxIlsRows = 512;
+static_assert(kMaxRayPaths == kMaxIlsRows, "every ray of a call is a row of one convolve call");
 constexpr int kMaxIlsChannels = 65536;
 constexpr int kMaxIlsTable = 4096;
 constexpr int kIlsRowBlock = 8;         // rows one workgroup carries in registers beside the normaliser

@@ -13,6 +13,8 @@
 //                              reduced to level fluxes (Atmosphere.fluxes; beyond the reference)
 //   K5d column_jacobian_kernel K5c's upward fold + a downward pass: analytic derivatives of the outgoing flux
 //                              (Atmosphere.jacobians; beyond the reference)
+//   K5e ray_radiance_kernel    K5c's step along ordered (layer, path length) segments: limb, slant and zenith rays
+//                              (Atmosphere.radiance; beyond the reference)
 //   K7 line_survey_kernel      pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -3383,6 +3385,19 @@ __device__ __forceinline__ void column_points(const ColumnRT& A, long long j, do
     }
 }
 
+// One step of the fold for the thread's NP points, shared by K5c (a layer) and K5e (a path segment through a layer): the
+// Planck term of every point (fold_planck: from ONE exp per thread on the fast path), then update(p, k_p, B_p), which forms
+// the optical depths from the absorption coefficient k_p = v[p] and folds them into the caller's radiances.
+template <bool FAST, int NP, class Update>
+__device__ __forceinline__ void transport_step(const double (&nu)[NP], const double (&pa_n)[NP], double pbkT, f64v<NP> v,
+                                               Update update) {
+#pragma clang fp contract(off)
+    double E0 = 0.0;
+    if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) update(p, v[p], fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0));
+}
+
 // sum_k W_k v(k), angle 0 first
 template <int NA, class V>
 __device__ __forceinline__ double angle_sum(const ColumnRT& A, V v) {
@@ -3435,16 +3450,12 @@ __global__ __launch_bounds__(256) void column_flux_kernel(const FluxArgs* __rest
         };
         auto layer = [&](auto fast_tag, int l, vec v) {
             constexpr bool FAST = decltype(fast_tag)::value;
-            const double pbkT = A.pbkT[l], depth = A.depth[l];
-            double E0 = 0.0;
-            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double tau = v[p] * depth;
-                const double B = fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0);
+            const double depth = A.depth[l];
+            transport_step<FAST, NP>(nu, pa_n, A.pbkT[l], v, [&](int p, double kp, double B) {
+                const double tau = kp * depth;
 #pragma unroll
                 for (int k = 0; k < NA; ++k) I[k][p] = fold_update<FAST>(exp_neg_budget(tau * A.rmu[k]), I[k][p], B);
-            }
+            });
         };
         auto walk = [&](auto fast_tag) {
             // upward: I_0 = I_surface or B(nu, surface_T); level l + 1 after layer l
@@ -3501,6 +3512,82 @@ __global__ __launch_bounds__(256) void column_flux_final_kernel(const double* __
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) level_flux[t] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// K5e: ray paths (lbl_ray_radiance_dev; the semantics are in include/pyrad_hip.h).  K5c's step along an ordered list of
+// (layer, path length) segments instead of the column bottom to top: no level sums, so no reductions and nothing shared
+// between threads.  One workgroup = 256 NP points x one BUNDLE of RB rays that cross the same layers in the same order
+// (the host finds them, lbl_column_transport.hip): k_l is loaded and B_l formed once per segment for the bundle, and every
+// ray of it pays only its own exp(-k_l length) and update - the way K5c's angles share a layer.  The operations of one ray
+// are the same in every bundle size, so its bits do not depend on the rays it travels with.  Ray, segment and layer
+// indices are uniform over the workgroup: the tables and the layer scalars come through scalar loads.
+template <int NP, int RB>
+__global__ __launch_bounds__(256) void ray_radiance_kernel(const RayArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                           long long lo1, long long n1, int order_first) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    const RayArgs& A = *Ap;
+    const char* blk = (const char*)Ap;
+    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
+    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
+    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
+    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
+    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
+    // (idle lanes of the last workgroup work on a valid point and store nothing)
+    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
+    const bool active = q < n0 + n1;
+    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    double nu[NP], pa_n[NP], Is[NP], I[RB][NP], Tt[RB][NP];
+    column_points<NP>(A, j, nu, pa_n);
+    const bool fast = fold_fast_path<NP>(A, nu, active);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+    int rid[RB], s0[RB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
+        s0[i] = ray_first[rid[i]];
+        const bool surface = source_kind[rid[i]] == 1;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) { I[i][p] = surface ? Is[p] : 0.0; Tt[i][p] = 1.0; }
+    }
+    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers)
+    const int32_t* lay = seg_layer + s0[0];
+    auto walk = [&](auto fast_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        vec cur = ns > 0 ? load_points<NP>(A.abs_coef[lay[0]], j) : (vec)(0.0);
+        for (int s = 0; s < ns; ++s) {
+            const vec nxt = s + 1 < ns ? load_points<NP>(A.abs_coef[lay[s + 1]], j) : cur;
+            double len[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            transport_step<FAST, NP>(nu, pa_n, A.pbkT[lay[s]], cur, [&](int p, double kp, double B) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double tr = exp_neg_budget(kp * len[i]);
+                    I[i][p] = fold_update<FAST>(tr, I[i][p], B);
+                    Tt[i][p] = Tt[i][p] * tr;
+                }
+            });
+            cur = nxt;
+        }
+    };
+    if constexpr (NP > 1) {
+        if (fast) walk(std::true_type{});
+        else walk(std::false_type{});
+    } else {
+        walk(std::false_type{});
+    }
+    if (!active) return;
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        const long long o = (long long)rid[i] * A.n + j;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            A.radiance[o + p] = I[i][p];
+            if (A.transmittance) A.transmittance[o + p] = Tt[i][p];
+        }
+    }
 }
 
 // K5d: K5c's upward fold, keeping per angle only the radiance I and its running maximum Imax over the levels; then a
@@ -4014,6 +4101,28 @@ void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, i
         launch_column_band<NP>(column_jacobian_kernel<NP, NA>, column_jacobian_kernel<1, NA>, d_args, 2 + 2 * n_layers + n_terms,
                                first, count, partial, jac, s);
     });
+}
+
+// K5e: the aligned groups of 4 points for the bundles of kRayBundle rays (order[0 .. kRayBundle n_bundles)) and then for the
+// single rays behind them, the head and tail points (at most 6) for every ray on its own in one 64-lane workgroup each; the
+// split of the points is launch_column_band's.  No grid-stride bound: nothing here is sized by the grid.
+void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s) {
+    constexpr int NP = 4;
+    if (n <= 0 || n_rays <= 0) return;
+    const long long q1 = n & ~(long long)(NP - 1);
+    const long long nt = n - q1;
+    const int n_single = n_rays - kRayBundle * n_bundles;
+    if (q1 > 0) {
+        const unsigned blocks = (unsigned)((q1 / NP + 255) / 256);
+        if (n_bundles > 0)
+            hipLaunchKernelGGL((ray_radiance_kernel<NP, kRayBundle>), dim3(blocks, n_bundles), dim3(256), 0, s, d_args, 0LL, q1,
+                               0LL, 0LL, 0);
+        if (n_single > 0)
+            hipLaunchKernelGGL((ray_radiance_kernel<NP, 1>), dim3(blocks, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL,
+                               kRayBundle * n_bundles);
+    }
+    if (nt > 0)
+        hipLaunchKernelGGL((ray_radiance_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
 }
 
 void launch_line_survey(const double* nu, const double* sw, int n_lines, double range_min, double resolution,

@@ -1716,6 +1716,64 @@ def kDistribution(rows, rangeMin, rangeMax, bands=None, g=16, reference=None, sp
         keep.free()
 
 
+class Path:
+    """One line of sight through a column, for Atmosphere.radiance: the segments the light crosses on its way to the
+    observer, farthest first.  Segment i runs ``lengths[i]`` cm through layer ``layers[i]`` (index in the atmosphere, bottom
+    layer 0); a layer may be missing or come more than once.  ``source``: what enters the first segment - "surface" (the
+    surface source of the radiance() call) or "space" (nothing).  Immutable; len(path) is the number of segments, which
+    may be 0 (the observer then sees the source).  ValueError for anything else.  Atmosphere.nadirPath, zenithPath and
+    limbPath build the usual ones."""
+    __slots__ = ("layers", "lengths", "source", "name")
+    SOURCES = ("space", "surface")          # the C ABI's source_kind is the index
+
+    def __init__(self, layers, lengths, source="surface", name=""):
+        try:
+            layers = list(layers)
+            lay = tuple(int(l) for l in layers)
+            ok = all(a == b for a, b in zip(lay, layers))
+            lens = tuple(float(x) for x in lengths)
+        except (TypeError, ValueError):
+            raise ValueError("Path: layers are integers and lengths numbers, one per segment")
+        if not ok or any(l < 0 for l in lay):
+            raise ValueError("Path: layers are integers >= 0, not %r" % (list(layers),))
+        if len(lay) != len(lens):
+            raise ValueError("Path: %d layers but %d lengths" % (len(lay), len(lens)))
+        if not all(x >= 0.0 and x != float("inf") for x in lens):
+            raise ValueError("Path: lengths must be finite and >= 0")
+        if source not in self.SOURCES:
+            raise ValueError("Path: source is \"surface\" or \"space\", not %r" % (source,))
+        for k, v in zip(self.__slots__, (lay, lens, source, str(name))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, key, value):
+        raise AttributeError("a Path is immutable")
+
+    __delattr__ = __setattr__
+
+    def __len__(self):
+        return len(self.layers)
+
+    def __repr__(self):
+        return "Path(%s%d segments, source=%s)" % (self.name + ": " if self.name else "", len(self), self.source)
+
+
+class PathRadiance:
+    """What Atmosphere.radiance returns.  ``paths``: the paths, in order.  Without an instrument ``wavenumber`` is the grid
+    (n,) and ``radiance`` (R, n) the spectrum arriving along every path, in the units of transmission(); with one they are
+    the channel centres (C,) and the channel radiances (R, C).  ``transmittance``: the path transmittances in the same
+    shape when asked for, else None."""
+
+    def __init__(self, wavenumber, radiance, transmittance, paths):
+        self.wavenumber = wavenumber
+        self.radiance = radiance
+        self.transmittance = transmittance
+        self.paths = paths
+
+    def __repr__(self):
+        return "PathRadiance(paths=%d, points=%d, transmittance=%s)" % (
+            len(self.paths), self.wavenumber.size, self.transmittance is not None)
+
+
 class Observation:
     """What Atmosphere.observe returns.  ``wavenumber``: the channel centres, (C,); ``radiance``: channel radiance in the
     units of transmission(); ``brightnessTemperature``: its inverse Planck at the centre, K; ``mu``: the viewing cosine.
@@ -2007,6 +2065,137 @@ class Atmosphere(list):
         return Observation(instrument.centres.copy(), v[0].copy(), float(mu_k[0]),
                            temperatureJacobian=v[1:1 + nl].copy() if jacobians else None,
                            opticalDepthJacobian=v[1 + nl:].copy() if jacobians else None)
+
+    @staticmethod
+    def _path_mu(mu):
+        try:
+            mu = float(mu)
+        except (TypeError, ValueError):
+            raise ValueError("mu: a cosine in (0, 1], not %r" % (mu,))
+        if not (mu > 0.0 and mu <= 1.0):
+            raise ValueError("mu: a cosine in (0, 1], not %r" % (mu,))
+        return mu
+
+    def _path_level(self, observerLevel, default):
+        nl = len(self._column_layers()[0])
+        if observerLevel is None:
+            observerLevel = default if default is not None else nl
+        if isinstance(observerLevel, bool) or not isinstance(observerLevel, (int, np.integer)) or not 0 <= observerLevel <= nl:
+            raise ValueError("observerLevel: a level 0..%d (0 the surface), not %r" % (nl, observerLevel))
+        return int(observerLevel), nl
+
+    def nadirPath(self, mu=1.0, observerLevel=None):
+        """The Path of an observer at level ``observerLevel`` (None: the top, level L) looking down at cosine ``mu``: the
+        surface source, then the layers 0 .. observerLevel-1 upward, each over depth_l / mu."""
+        mu = self._path_mu(mu)
+        lev, _ = self._path_level(observerLevel, None)
+        return Path(range(lev), [self[l].depth / mu for l in range(lev)], "surface", "nadir mu=%g level=%d" % (mu, lev))
+
+    def zenithPath(self, mu=1.0, observerLevel=0):
+        """The Path of an upward-looking observer at level ``observerLevel`` (0: the surface) at cosine ``mu``: cold space,
+        then the layers L-1 down to observerLevel, each over depth_l / mu - the downwelling radiance an instrument there
+        measures."""
+        mu = self._path_mu(mu)
+        lev, nl = self._path_level(observerLevel, 0)
+        lay = range(nl - 1, lev - 1, -1)
+        return Path(lay, [self[l].depth / mu for l in lay], "space", "zenith mu=%g level=%d" % (mu, lev))
+
+    def limbPath(self, tangentHeight, planetRadius=6.371e8):
+        """The Path of a limb ray through the column taken as spherical shells around a planet of radius ``planetRadius``
+        (cm; level heights z_0 = 0, z_(l+1) = z_l + depth_l): it enters from space, comes down to ``tangentHeight`` (cm above
+        the surface, 0 <= tangentHeight < z_L) and leaves again towards an observer outside the atmosphere.  NO REFRACTION:
+        the ray is a straight line.  With zt the tangent height and m the tangent layer (z_m <= zt < z_(m+1)), the half
+        chord inside layer l >= m is, with lo = max(z_l, zt) and hi = z_(l+1),
+            sqrt((hi - zt) (2 R + hi + zt)) - sqrt((lo - zt) (2 R + lo + zt))
+        (the factored form of sqrt((R + hi)^2 - (R + zt)^2) - ..., which keeps its digits near the top).  Segments: the
+        layers L-1 .. m+1 with their half chords, layer m once with twice its half chord, then m+1 .. L-1."""
+        layers, _ = self._column_layers()
+        try:
+            zt, R = float(tangentHeight), float(planetRadius)
+        except (TypeError, ValueError):
+            raise ValueError("tangentHeight and planetRadius: heights in cm")
+        if not R > 0.0 or R == float("inf"):
+            raise ValueError("planetRadius must be finite and > 0, not %r" % (planetRadius,))
+        z = [0.0]
+        for L in layers:
+            z.append(z[-1] + float(L.depth))
+        if not (zt >= 0.0 and zt < z[-1]):
+            raise ValueError("tangentHeight: %r is outside [0, %r), the column's heights (rays that meet the surface are "
+                             "not limb paths)" % (tangentHeight, z[-1]))
+        nl = len(layers)
+        m = max(l for l in range(nl) if z[l] <= zt)        # (zt < z_L: the layer above level m is not empty)
+        reach = lambda h: math.sqrt((h - zt) * (2.0 * R + h + zt))
+        half = {l: reach(z[l + 1]) - reach(max(z[l], zt)) for l in range(m, nl)}
+        above = list(range(nl - 1, m, -1))
+        lay = above + [m] + above[::-1]
+        return Path(lay, [half[l] for l in above] + [2.0 * half[m]] + [half[l] for l in above[::-1]], "space",
+                    "limb zt=%g" % zt)
+
+    def radiance(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, transmittance=False):
+        """The radiance arriving along ``paths`` - one Path or a list of up to 512 - through this column (beyond the
+        reference).  Layers, grid and units as transmission() has them.  For every path and grid point nu_j:
+            I = surfaceSpectrum[j] or B(nu_j, surfaceTemperature) for source "surface", 0 for "space";  Ttot = 1
+            per segment (layer l, length s), in order:   t = exp(-k_l(nu_j) s)   I <- t I + (1 - t) B(nu_j, T_l)   Ttot <- Ttot t
+        A surface source is needed only if some path starts at the surface.  ``transmittance``: also return Ttot.
+        ``instrument``: an Instrument - the rows are convolved onto its channels on the device, as observe() does, and
+        only channel values come down (with transmittance twice the paths must fit the 512 rows of one convolution).
+        radiance(nadirPath()) is transmission() bit for bit wherever fluxes() documents that identity, and with an
+        instrument observe(instrument).radiance.  One kernel call (lbl_ray_radiance_dev) for all paths; a path's result does
+        not depend on the others.  The absorption coefficients are the resident ones: after transmission() nothing is
+        accumulated again.  Returns a PathRadiance.  Everything is validated (ValueError) before the device is touched."""
+        plist = [paths] if isinstance(paths, Path) else list(paths) if isinstance(paths, (list, tuple)) else None
+        if not plist or not all(isinstance(p, Path) for p in plist):
+            raise ValueError("paths: a Path or a non-empty list of them, not %r" % (paths,))
+        R = len(plist)
+        if R > nat.limit("ray_paths"):
+            raise ValueError("paths: %d paths, at most %d in one call" % (R, nat.limit("ray_paths")))
+        layers, n = self._column_layers()
+        nl = len(layers)
+        for i, p in enumerate(plist):
+            if any(l >= nl for l in p.layers):
+                raise ValueError("paths: path %d names layer %d, the column has %d" % (i, max(p.layers), nl))
+        if sum(len(p) for p in plist) > nat.limit("ray_segments"):
+            raise ValueError("paths: %d segments, at most %d in one call" % (sum(len(p) for p in plist), nat.limit("ray_segments")))
+        if any(p.source == "surface" for p in plist):
+            if surfaceSpectrum is None and surfaceTemperature is None:
+                raise ValueError("a path starts at the surface: give surfaceSpectrum or surfaceTemperature")
+            if surfaceSpectrum is None and not float(surfaceTemperature) > 0:
+                raise ValueError("surfaceTemperature must be > 0")
+        surfaceSpectrum = _grid_spectrum("surfaceSpectrum", surfaceSpectrum, n)
+        first = layers[0]
+        n_rows = 2 * R if transmittance else R
+        support = None
+        if instrument is not None:
+            if not isinstance(instrument, Instrument):
+                raise ValueError("instrument: an Instrument, not %r" % (instrument,))
+            if n_rows > nat.limit("ils_rows"):
+                raise ValueError("instrument: %d paths with transmittance are %d rows, at most %d in one convolution"
+                                 % (R, n_rows, nat.limit("ils_rows")))
+            support = instrument.support(first.rangeMin, first.rangeMax, n)
+        ctx = _ctx()
+        if ctx.option("sweep_ieee_divisions"):
+            raise ValueError("ray paths exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        I_source = None
+        if surfaceSpectrum is not None:
+            I_source = _kept_state(self, "_path_source").reserve(ctx, n).buf(ctx, "I_source").upload(surfaceSpectrum)
+        pst = _kept_state(self, "_path_state").reserve(ctx, R * n)
+        rad = pst.buf(ctx, "radiance")
+        trn = pst.buf(ctx, "transmittance") if transmittance else None
+        ray_first = np.cumsum([0] + [len(p) for p in plist])
+        ctx.ray_radiance_dev(kbufs, [L.T for L in layers], first.rangeMin, first.rangeMax, n, ray_first,
+                             [l for p in plist for l in p.layers], [x for p in plist for x in p.lengths],
+                             [Path.SOURCES.index(p.source) for p in plist], rad, I_source=I_source,
+                             source_T=float(surfaceTemperature or 0.0), transmittance=trn)
+        if instrument is None:
+            return PathRadiance(first.xAxis, rad.download(R * n).reshape(R, n),
+                                trn.download(R * n).reshape(R, n) if transmittance else None, plist)
+        C = len(instrument)
+        out = _kept_state(self, "_path_out").reserve(ctx, n_rows * C).buf(ctx, "out")
+        rows = [(rad, r * n) for r in range(R)] + ([(trn, r * n) for r in range(R)] if transmittance else [])
+        _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, rows, out)
+        v = out.download(n_rows * C).reshape(n_rows, C)
+        return PathRadiance(instrument.centres.copy(), v[:R].copy(), v[R:].copy() if transmittance else None, plist)
 
     def kDistribution(self, bands=None, g=16, reference=None, planck=False, spectra=False):
         """k-distributions of the column's bands (beyond the reference): every layer's absorption coefficient (getAbsCoef)
