@@ -385,13 +385,19 @@ def test_sweeps_propagate_nan_in_both_arithmetics(ctx):
         x.free()
 
 
-def test_fold_with_faint_incoming_radiance_and_nearly_transparent_layers(ctx):
+@pytest.mark.parametrize("n,form", [(4096, "general"), (32001, "one-exp")])
+def test_fold_with_faint_incoming_radiance_and_nearly_transparent_layers(ctx, n, form):
     """Layer.transmission (cls:784-787), T I + (1 - T) B, at its extremes: incoming radiances from 1e-20 B to B behind layers
-    of optical depth 1e-12 .. 1, through the fold's four-points-per-thread path, against the expression in extended
+    of optical depth 1e-12 .. 1, through the fold's four-points-per-thread kernel, against the expression in extended
     precision.  What double precision allows here is set by T itself: exp(-tau) rounds with up to half an ulp of 1, which
-    the factor (I - B) carries into the result - the bound below - and nothing beyond that may be lost (the kernel forms
-    T I + ((1 - T) B) with one fma; B + T (I - B) would be cheaper and, as it happens, no worse than this bound)."""
-    n = 4096
+    the factor (I - B) carries into the result - the bound below - and nothing beyond that may be lost.
+    The kernel has two forms of the update, chosen per wave (tests/test_fold_regimes_cpu.py): on 4,096 points the grid step
+    is too wide for the one-exp form (3 step pbkT = 1.26e-3 > 1e-3), so every wave runs the general form, T I and (1 - T) B
+    as separate product and sum; on 32,001 points every wave runs the one-exp form, which forms T I + ((1 - T) B) with one
+    fma (B + T (I - B) would be cheaper and, as it happens, no worse than this bound)."""
+    from test_fold_regimes_cpu import wave_classes
+    cls = wave_classes(500.0, 800.0, n, 0, 0, (250.0,))
+    assert cls["general" if form == "general" else "plain"] == len(cls["kind"]) > 0, cls
     rng = np.random.default_rng(5)
     nu = np.linspace(500.0, 800.0, n)
     h, c, kB = 6.62607004e-34, 299792458.0, 1.38064852e-23
