@@ -272,6 +272,33 @@ int lbl_xsec_accumulate_dev(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
 /* Regime counters of the most recent lbl_xsec_accumulate_dev (drains the stream):
  * counts[3*j + {0,1,2}] = {gaussian, lorentz, voigt} of job j. */
 int lbl_last_regime_counts(lbl_ctx* ctx, int n_jobs, int64_t* counts);
+/* ---- true Voigt line shape (beyond the reference; ABI 5, backward compatible) ----------------------------------------------
+ * lbl_xsec_accumulate_dev evaluates the reference's profile: a Gaussian below lhw / ghw = 0.01, a Lorentzian above 100, a
+ * pseudo-Voigt between (pyradClasses.py:378-387).  lbl_xsec_voigt_dev takes the same jobs and evaluates for EVERY line
+ *     A * K(|d| * xs, y) / (ghw * sqrt(pi)),   K(x, y) = Re w(x + i y),   xs = resolution / ghw,   y = lhw / ghw,
+ * with w the Faddeeva function, A the corrected intensity (pyradIntensity.py:30-32), lhw / ghw the Lorentz and Doppler half
+ * widths (pyradClasses.py:252-263) and d the integer offset of a work-grid point from the line's centre index
+ * (pyradClasses.py:390).  The geometry is the reference's scatter (pyradClasses.py:390-400): the centre point once, both
+ * wings for |d| = 1 .. window - 2, points outside [0, n_work) dropped; a work grid coarser than the base grid is regridded
+ * as before (pyradClasses.py:401-405).  x is formed as (double)|d| * xs with xs one IEEE division.
+ * K is accurate to 1e-6 relative (measured: 3e-10) for y == 0 or 1e-5 <= y <= 1e4 and never negative; for 0 < y < 1e-5 its
+ * error grows like 1 / y where exp(-x^2) has died (2.5e-9 at 1e-6, 2.5e-7 at 1e-8); y is what the line list and the
+ * conditions make it - nothing is refused or clamped.
+ * Arguments, limits (LBL_MAX_JOBS), sharding (shard_first / shard_count) and conventions are those of
+ * lbl_xsec_accumulate_dev: stream-ordered, all jobs in one launch sequence, everything checked before anything is enqueued
+ * (same status codes; window < 1 is refused), the host arrays are not retained, LBL_ERR_STATE inside a capture if the call
+ * would allocate or upload.  lbl_last_regime_counts afterwards reports the batch's counters with their meaning unchanged:
+ * the lines per regime by the reference's thresholds.  The options "accuracy" and "accum_*" (and the dispatch schedules,
+ * lbl_ctx_chain_accumulate) do not apply to it: there is one kernel and one arithmetic.
+ * Determinism: every point is summed by one thread over the lines in list order, without atomics: two calls give the same
+ * bits, a job's result does not depend on the other jobs of the batch, and a shard equals the same points of the whole. */
+int lbl_xsec_voigt_dev(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines, const lbl_iso_params* iso,
+                       const lbl_grid* grid, lbl_buffer* const* out);
+/* out[i] = K(x[i], y[i]) for i < n, elementwise, by the device function the accumulate kernel inlines (tests).  x >= 0;
+ * y == 0 or y > 0; NaN in, NaN out; where the true value is below 1e-290 the result lies in [0, 1e-290].  Stream-ordered.
+ * LBL_ERR_BAD_ARG: a NULL argument, negative n, a buffer shorter than n; LBL_ERR_STATE: a buffer of another context. */
+int lbl_voigt_function_dev(lbl_ctx* ctx, lbl_buffer* x, lbl_buffer* y, int64_t n, lbl_buffer* out);
+
 /* Introspection for tests: the k-th most recently used dispatch schedule of the context (0 = the last one an
  * accumulate batch used).  list receives 2 ints per workgroup (job of the launch group, tile of the job), tabs 8 ints
  * per span of 64 R points {iA, iB, iC, iD, iF1, iF2, 0, 0} (the lower bounds of the span's edge / interior / far lines

@@ -84,6 +84,8 @@ SIGNATURES = {
                                       C.POINTER(Grid), _P, C.POINTER(C.c_int64)]),
     "lbl_xsec_accumulate_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(IsoParams), C.POINTER(Grid),
                                           C.POINTER(_P)]),
+    "lbl_xsec_voigt_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(IsoParams), C.POINTER(Grid), C.POINTER(_P)]),
+    "lbl_voigt_function_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "lbl_schedule_export": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int32)]),
     "lbl_last_regime_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
@@ -428,6 +430,21 @@ class Context:
         G = (Grid * n)(*[j[2] for j in jobs])
         O = (_P * n)(*[j[3].h for j in jobs])
         self.check(self.lib.lbl_xsec_accumulate_dev(self.h, n, L, I, G, O))
+
+    def xsec_voigt_dev(self, jobs):
+        """xsec_accumulate_dev's jobs with the true Voigt line shape (lbl_xsec_voigt_dev). Asynchronous."""
+        n = len(jobs)
+        if n == 0:
+            return
+        L = (_P * n)(*[j[0].h for j in jobs])
+        I = (IsoParams * n)(*[j[1] for j in jobs])
+        G = (Grid * n)(*[j[2] for j in jobs])
+        O = (_P * n)(*[j[3].h for j in jobs])
+        self.check(self.lib.lbl_xsec_voigt_dev(self.h, n, L, I, G, O))
+
+    def voigt_function_dev(self, x, y, n, out):
+        """out[i] = Re w(x[i] + 1j * y[i]) for i < n, by the device function the Voigt accumulate kernel inlines."""
+        self.check(self.lib.lbl_voigt_function_dev(self.h, x.h, y.h, int(n), out.h))
 
     def schedule_export(self, k: int = 0):
         """(list[n, 2] of (job, tile), tabs[spans, 8], built_on_device) of the k-th most recently used schedule."""

@@ -111,6 +111,7 @@ struct lbl_ctx {
     int sched_build = 1;     // 1 (default): span tables and dispatch order built on the device, in stream; 0: on the host
     DeviceArena sched;       // scratch of the device build
     DeviceArena ktmp;        // lbl_layer_merged_step_dev on a work grid that needs the regrid kernel, without an abs_coef buffer: the regridded k
+    DeviceArena voigt;       // lbl_xsec_voigt_dev (lbl_voigt.hip): VoigtRec and centre index per line, work grids that need a regrid
     DeviceArena merge_tmp;   // merged layer jobs: per-list centre indices + list descriptors while the merged positions are built
     bool sched_refused = false;   // group_schedule: a merged layer job on a launch the device build does not cover
     uint64_t lines_serial = 0;
@@ -447,7 +448,7 @@ extern "C" int lbl_ctx_destroy(lbl_ctx* ctx) try {
     for (auto& sc : ctx->schedules) if (sc->d_block) (void)hipFree(sc->d_block);
     for (auto& e : ctx->desc_cache) if (e.dptr) (void)hipFree(e.dptr);
     for (auto& e : ctx->arg_cache) if (e.dptr) (void)hipFree(e.dptr);
-    DeviceArena* arenas[] = {&ctx->recs, &ctx->cold, &ctx->cidx, &ctx->work, &ctx->jobs, &ctx->counts, &ctx->bal, &ctx->red, &ctx->zeros, &ctx->sched, &ctx->merge_tmp, &ctx->ktmp};
+    DeviceArena* arenas[] = {&ctx->recs, &ctx->cold, &ctx->cidx, &ctx->work, &ctx->jobs, &ctx->counts, &ctx->bal, &ctx->red, &ctx->zeros, &ctx->sched, &ctx->merge_tmp, &ctx->ktmp, &ctx->voigt};
     for (DeviceArena* a : arenas) if (a->ptr) (void)hipFree(a->ptr);
     if (ctx->host_stage) (void)hipHostFree(ctx->host_stage);
     for (int h = 0; h < 2; ++h) if (ctx->stage_ev[h]) (void)hipEventDestroy(ctx->stage_ev[h]);
@@ -1222,6 +1223,19 @@ static lbl_ctx::Schedule* group_schedule(lbl_ctx* ctx, int variant, const std::v
 // Merged layer jobs (lbl_layer_merged_step_dev, lbl_layers_merged_accumulate_dev): accumulate job j takes the line lists
 // [first[j], first[j + 1]) of `lines` / `iso` as ONE record array in centre-index order; list l's amplitudes carry weight[l]
 // and job j's sums leave the kernel multiplied by out_scale[j] (see PrepJob.weight, AccumJob.out_scale).
+// what line_physics() reads of a PrepJob besides the line fields: the job's conditions and the per-job constants of the
+// reference's expressions, evaluated once on the host in the reference's operation order (K1, and K2v's prep kernel)
+static void prep_job_physics(PrepJob& p, const lbl_iso_params& iso, const lbl_grid& grid) {
+    p.T = iso.T; p.P = iso.P; p.q_frac = iso.q_frac; p.molmass = iso.molmass;
+    p.Q_T = iso.Q_T; p.Q_296 = iso.Q_296;
+    p.range_min = grid.range_min; p.resolution = grid.resolution;
+    p.log_t0_over_T = std::log(296.0 / iso.T);
+    p.P_over_p0 = iso.P / p0;
+    { const double m = iso.molmass / 1000.0 / avo; p.ghw_factor = std::sqrt(2.0 * kB * iso.T / m / (cLight * cLight)); }
+    p.q_ratio = iso.Q_296 / iso.Q_T;
+    p.inv_T = 1.0 / iso.T; p.inv_res = 1.0 / grid.resolution; p.inv_res2 = p.inv_res * p.inv_res;
+}
+
 struct MergeSpec {
     const int* first;          // n_jobs + 1 offsets into lines / iso
     const double* weight;      // per line list
@@ -1413,14 +1427,7 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
             p.merged = scattered ? 1 : 0;
             p.weight = merge ? merge->weight[l] : 1.0;
             p.block_counts = d_counts + (size_t)l * blocks_per_job * 3;
-            p.T = iso[l].T; p.P = iso[l].P; p.q_frac = iso[l].q_frac; p.molmass = iso[l].molmass;
-            p.Q_T = iso[l].Q_T; p.Q_296 = iso[l].Q_296;
-            p.range_min = grid[j].range_min; p.resolution = grid[j].resolution;
-            p.log_t0_over_T = std::log(296.0 / iso[l].T);
-            p.P_over_p0 = iso[l].P / p0;
-            { const double m = iso[l].molmass / 1000.0 / avo; p.ghw_factor = std::sqrt(2.0 * kB * iso[l].T / m / (cLight * cLight)); }
-            p.q_ratio = iso[l].Q_296 / iso[l].Q_T;
-            p.inv_T = 1.0 / iso[l].T; p.inv_res = 1.0 / grid[j].resolution; p.inv_res2 = p.inv_res * p.inv_res;
+            prep_job_physics(p, iso[l], grid[j]);
             p.gauss_cut = ctx->accuracy ? 17179869184.0 : 18014398509481984.0;          // 2^34 : 2^54
             p.n_lines = (int32_t)L->n;
             p.pad = ctx->ablate;                 // (LBL_DIAG builds: debug_ablate 1024 drops every Gaussian part; else 0, never read)
@@ -2562,4 +2569,38 @@ void planck_budget_constants(double T, double* pa, double* pbkT) {      // the f
     *pbkT = budget_pbkT(T);
 }
 double grid_step(double lo, double hi, int64_t n) { return axis_step(lo, hi, n); }
+// ... and for lbl_voigt.hip: what lbl_xsec_accumulate_dev checks and fills of a job, for a batch with kernels of its own
+int ctx_check_grid(lbl_ctx* ctx, const lbl_grid* g) { return check_grid(ctx, g); }
+int ctx_check_lines(lbl_ctx* ctx, const lbl_lines* lines, int at) {
+    if (!lines || lines->ctx != ctx) return fail(ctx, LBL_ERR_STATE, "line list %d: missing or from another context", at);
+    if (lines->n > 2000000000LL) return fail(ctx, LBL_ERR_BAD_ARG, "job %d: too many lines for int32 indexing", at);
+    return LBL_OK;
+}
+int64_t lines_count(const lbl_lines* lines) { return lines->n; }
+void prep_job_fill(PrepJob* p, const lbl_lines* L, const lbl_iso_params* iso, const lbl_grid* grid) {   // (p zeroed by the caller)
+    p->nu = L->field(0); p->sw = L->field(1); p->elower = L->field(2); p->gamma_air = L->field(3);
+    p->gamma_self = L->field(4); p->n_air = L->field(5); p->delta_air = L->field(6);
+    prep_job_physics(*p, *iso, *grid);
+    p->n_lines = (int32_t)L->n;
+    p->weight = 1.0;
+}
+int ctx_voigt_scratch(lbl_ctx* ctx, size_t bytes, void** dptr) {
+    const int rc = arena_reserve(ctx, ctx->voigt, bytes);
+    if (rc == LBL_OK) *dptr = ctx->voigt.ptr;
+    return rc;
+}
+// the per-block regime counters of a batch of n_lists line lists (lbl_last_regime_counts reads them): list l owns
+// blocks_per_list x 3 counters from d_counts + l * blocks_per_list * 3, of which ceil(lines / 256) blocks are written
+int ctx_regime_blocks(lbl_ctx* ctx, int n_lists, int blocks_per_list, unsigned int** d_counts) {
+    const int rc = arena_reserve(ctx, ctx->counts, (size_t)n_lists * (size_t)std::max(blocks_per_list, 1) * 3 * sizeof(unsigned int));
+    if (rc == LBL_OK) *d_counts = (unsigned int*)ctx->counts.ptr;
+    return rc;
+}
+void ctx_regime_batch(lbl_ctx* ctx, int n_lists, int blocks_per_list, const int* list_blocks) {      // once the batch is enqueued
+    ctx->last_jobs = n_lists;
+    ctx->last_blocks_per_job = blocks_per_list;
+    ctx->last_list_blocks.assign(list_blocks, list_blocks + n_lists);
+}
+void* ctx_profile_begin(lbl_ctx* ctx, int kind) { return prof_begin(ctx, kind); }
+void ctx_profile_end(lbl_ctx* ctx, int kind, void* start) { prof_end(ctx, kind, (hipEvent_t)start); }
 }  // namespace lbl

@@ -353,6 +353,34 @@ struct MeansArgs {
 void launch_kdist_rank(const RankArgs* d_args, const RankArgs& host, hipStream_t s);
 void launch_kdist_means(const MeansArgs* d_args, const MeansArgs& host, hipStream_t s);
 
+// True Voigt line shape (K2v, lbl_voigt.hip: lbl_xsec_voigt_dev): one prepared line.  Its contribution to the work-grid point
+// at integer offset d from its centre index is  amp * voigt_k(|d| * xs, y)  for |d| <= H = max(window - 2, 0), with
+// voigt_k(x, y) = Re w(x + i y) of lbl_voigt_func.h.
+struct __attribute__((aligned(32))) VoigtRec {
+    double cf;      // centre index (pyradClasses.py:390) as a double, clamped as K1 clamps it
+    double xs;      // resolution / ghw: one IEEE division
+    double y;       // lhw / ghw
+    double amp;     // A * (1 / (ghw * sqrt(pi)))
+};
+static_assert(sizeof(VoigtRec) == 32, "a lane stages one record with two 16-byte loads");
+// One job of a Voigt batch, beside its PrepJob (same index): PrepJob carries the line fields, the job's physical constants
+// and the regime counters' block; its hot / cold / cidx are not used.
+struct VoigtJob {
+    VoigtRec* rec;
+    int32_t* cidx;         // centre indices, non-decreasing
+    double* out;           // work grid, n_work doubles
+    int32_t n_lines;
+    int32_t H;             // wing support in points = max(window - 2, 0)
+    int32_t p_begin;       // shard of the work grid computed by this job: [p_begin, p_end)
+    int32_t p_end;
+};
+constexpr int kVoigtR = 2;                       // consecutive work-grid points a lane owns
+constexpr int kVoigtChunk = 64;                  // records a wave parks in its LDS at a time (2 KB)
+constexpr int kVoigtTile = 256 * kVoigtR;        // points of a workgroup
+void launch_voigt_prep(const PrepJob* d_prep, const VoigtJob* d_jobs, int n_jobs, int max_lines, hipStream_t s);
+void launch_voigt_accumulate(const VoigtJob* d_jobs, int n_jobs, long long max_points, hipStream_t s);
+void launch_voigt_function(const double* x, const double* y, long long n, double* out, hipStream_t s);
+
 struct ColumnArgs {
     const double* trans[kMaxLayers];
     double layer_T[kMaxLayers];

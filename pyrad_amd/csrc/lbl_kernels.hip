@@ -4,6 +4,8 @@
 //                              pyradIntensity.py:16-32
 //   K2 xsec_accumulate_*       pyradLineshape.py:39, 52, 72-74 and the scatter loop
 //                              pyradClasses.py:392-400, restated as an owner-computes gather
+//   K2v voigt_prep_kernel, voigt_accumulate_kernel   the true Voigt profile Re w((x + i lhw) / ghw) / (ghw sqrt(pi)) over the
+//                              same scatter geometry (lbl_xsec_voigt_dev; beyond the reference, see "K2v" below)
 //   K3 regrid_kernel           np.interp of pyradClasses.py:401-405 (only when res != BASE)
 //   K4 layer_sweep_kernel      pyradClasses.py:566-571, 583, 707-716, 784-787; pyradPlanck.py:38-44
 //   K5 column_sweep_kernel     fold of pyradClasses.py:784-787 over layers
@@ -47,6 +49,8 @@
 // point against 5 fp64 instructions per directly evaluated (line, grid point) pair.
 #include "lbl_device.h"
 #include "lbl_launch_shapes.h"
+#include "lbl_voigt_func.h"
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -2945,6 +2949,105 @@ void launch_schedule_build(const SchedJob* d_jobs, int n_jobs, int total_spans, 
 }
 
 // ----------------------------------------------------------------------------------------
+// K2v: the true Voigt line shape (lbl_xsec_voigt_dev; beyond the reference)
+// ----------------------------------------------------------------------------------------
+// The reference's profile is a Gaussian below lhw / ghw = 0.01, a Lorentzian above 100 and a pseudo-Voigt between; K2v
+// evaluates  A Re w((x + i lhw) / ghw) / (ghw sqrt(pi))  for every line instead, over the reference's scatter geometry
+// (pyradClasses.py:390-400: centre point once, both wings for dx = 1 .. W - 2, points outside the grid dropped), as the
+// same owner-computes gather as K2.  None of K2's records or kernels is touched: the prep kernel writes records of its own
+// from line_physics(), the accumulate kernel streams them through wave-private LDS like variant 3 and evaluates every pair
+// with voigt_k (lbl_voigt_func.h).  One fixed summation order per point (line order), no atomics.
+__global__ __launch_bounds__(256) void voigt_prep_kernel(const PrepJob* __restrict__ jobs, const VoigtJob* __restrict__ vjobs) {
+    const PrepJob& J = jobs[blockIdx.y];
+    const VoigtJob& V = vjobs[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int regime = -1;
+    if (i < J.n_lines) {
+        const LinePhysics L = line_physics(J, i);
+        long long idx = (long long)L.fidx;
+        if (idx > 2000000000LL) idx = 2000000000LL;
+        if (idx < -2000000000LL) idx = -2000000000LL;
+        VoigtRec r;
+        r.cf = (double)idx;
+        r.xs = J.resolution / L.ghw;
+        r.y = L.ratio;                                                // lhw / ghw (pyradClasses.py:378)
+        r.amp = L.A * (1.0 / (L.ghw * 1.7724538509055159));           // sqrt(pi)
+        V.rec[i] = r;
+        V.cidx[i] = (int32_t)idx;
+        regime = line_regime(L.ratio);                                // the counters keep the reference's meaning
+    }
+    __shared__ unsigned int s_cnt[4][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = 0; k < 3; ++k) {
+        const unsigned long long m = __ballot(regime == k);
+        if (lane == 0) s_cnt[wave][k] = (unsigned int)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3)
+        J.block_counts[blockIdx.x * 3 + threadIdx.x] =
+            s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+}
+
+// A wave owns 64 kVoigtR consecutive points of its job's shard, finds the lines whose window meets them (wave_line_ranges:
+// [iA, iD)) and walks them in chunks of kVoigtChunk records: lane l fetches record c0 + l with two 16-byte loads, parks it
+// in the wave's 2 KB of LDS, and every record is read back as a broadcast (all lanes, one address).  Waves stay
+// independent: no workgroup barrier.  Per pair: d = p - cf (exact), x = |d| xs, masked by |d| <= H.
+__global__ __launch_bounds__(256) void voigt_accumulate_kernel(const VoigtJob* __restrict__ jobs) {
+    constexpr int R = kVoigtR;
+    const VoigtJob& J = jobs[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    const int wave = uniform_i32(threadIdx.x >> 6);
+    const int n_end = J.p_end;
+    const long long wave_lo_ll = (long long)J.p_begin + ((long long)blockIdx.x * 4 + wave) * (64LL * R);
+    if (wave_lo_ll >= n_end) return;
+    const int wlo = (int)wave_lo_ll;
+    const int whi = min(wlo + 64 * R - 1, n_end - 1);
+    const int H = J.H;
+    int iA, iB, iC, iD;
+    wave_line_ranges(J.cidx, J.n_lines, wlo, whi, H, lane, iA, iB, iC, iD);
+
+    __shared__ double s_rec[4][kVoigtChunk * 4];
+    double* lr = s_rec[wave];
+    const int p0 = wlo + lane * R;
+    const double x0 = (double)p0;
+    const double Hf = (double)H;
+    double acc[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] = 0.0;
+    for (int c0 = iA; c0 < iD; c0 += kVoigtChunk) {
+        const int n = min(kVoigtChunk, iD - c0);
+        __builtin_amdgcn_wave_barrier();                    // (every lane is done with the chunk before)
+        if (lane < n) {
+            const double2* src = reinterpret_cast<const double2*>(J.rec + c0 + lane);
+            double2* dst = reinterpret_cast<double2*>(lr + lane * 4);
+            dst[0] = src[0];
+            dst[1] = src[1];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (int j = 0; j < n; ++j) {
+            const double cf = lr[j * 4], xs = lr[j * 4 + 1], y = lr[j * 4 + 2], amp = lr[j * 4 + 3];
+            const double d0 = x0 - cf;
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                const double ad = fabs(d0 + (double)k);
+                if (ad <= Hf) acc[k] += amp * voigt_k(ad * xs, y);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+        if (p0 + k < n_end) J.out[p0 + k] = acc[k];
+}
+
+// lbl_voigt_function_dev: the device function the accumulate kernel inlines, elementwise (tests)
+__global__ __launch_bounds__(256) void voigt_function_kernel(const double* __restrict__ x, const double* __restrict__ y, long long n,
+                                                             double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = voigt_k(x[i], y[i]);
+}
+
+// ----------------------------------------------------------------------------------------
 // K3: np.interp from linspace(min,max,n_work) onto linspace(min,max,n_base)
 //     (pyradClasses.py:401-405, 159-162)
 // ----------------------------------------------------------------------------------------
@@ -3875,6 +3978,27 @@ void launch_accumulate(const AccumJob* d_jobs, int n_jobs, int max_tiles, int R,
         case 4: launch_accum_scalar<4>(d_jobs, n_jobs, max_tiles, variant, s); break;
         default: launch_accum_scalar<8>(d_jobs, n_jobs, max_tiles, variant, s); break;
     }
+}
+
+void launch_voigt_prep(const PrepJob* d_prep, const VoigtJob* d_jobs, int n_jobs, int max_lines, hipStream_t s) {
+    if (n_jobs <= 0 || max_lines <= 0) return;
+    for (int j0 = 0; j0 < n_jobs; j0 += 65535) {            // (a launch's second dimension holds 65,535 workgroups)
+        dim3 grid((max_lines + 255) / 256, std::min(n_jobs - j0, 65535));
+        hipLaunchKernelGGL(voigt_prep_kernel, grid, dim3(256), 0, s, d_prep + j0, d_jobs + j0);
+    }
+}
+
+void launch_voigt_accumulate(const VoigtJob* d_jobs, int n_jobs, long long max_points, hipStream_t s) {
+    if (n_jobs <= 0 || max_points <= 0) return;
+    for (int j0 = 0; j0 < n_jobs; j0 += 65535) {
+        dim3 grid((unsigned)((max_points + kVoigtTile - 1) / kVoigtTile), std::min(n_jobs - j0, 65535));
+        hipLaunchKernelGGL(voigt_accumulate_kernel, grid, dim3(256), 0, s, d_jobs + j0);
+    }
+}
+
+void launch_voigt_function(const double* x, const double* y, long long n, double* out, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(voigt_function_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, n, out);
 }
 
 void launch_regrid(const double* work, long long n_work, double* out, long long n_base, double start,

@@ -17,6 +17,7 @@ interactive menu.
 from __future__ import annotations
 
 import math
+import weakref
 
 import numpy as np
 
@@ -405,8 +406,31 @@ def _compute_cross_sections(isotopes):
         g = iso.layer._grid()
         _check_window(g)
         jobs.append((iso._device_lines(ctx), _iso_params(iso), _engine.native_grid(g), iso._device_xsec(ctx, g["n_base"])))
-    ctx.xsec_accumulate_dev(jobs)
+    if settings.LINE_SHAPE == "voigt":
+        ctx.xsec_voigt_dev(jobs)                # the true Voigt profile for every line (lbl_xsec_voigt_dev)
+    else:
+        ctx.xsec_accumulate_dev(jobs)
     _mark_computed(ctx, dirty, dirty[0].layer._grid()["n_base"])
+
+
+def _merged_route(ctx):
+    """The merged layer jobs (settings.LAYER_STEP "merged") evaluate the reference's line shape in the default arithmetic:
+    any other setting takes the per-line-list routes."""
+    return settings.LAYER_STEP == "merged" and settings.LINE_SHAPE == "reference" and not ctx.option("sweep_ieee_divisions")
+
+
+_live_layers = []       # weak references to every Layer (settings.set_line_shape marks their cross sections dirty)
+
+
+def _line_shape_changed():
+    """settings.set_line_shape: every line-by-line cross section below every live Layer is of the other shape."""
+    alive = []
+    for ref in _live_layers:
+        layer = ref()
+        if layer is not None:
+            alive.append(ref)
+            resetCrossSection(layer)
+    _live_layers[:] = alive
 
 
 class _OpticalMixin:
@@ -435,7 +459,8 @@ class _OpticalMixin:
         lbl = [i for i in flat if not i.exotic]
         dirty = [i for i in lbl if not i.progressCrossSection]
         fusable = (dirty and len(dirty) == len(flat) and g["resolution"] == g["base_resolution"]
-                   and g["n_work"] == n and len(flat) <= nat.limit("arrays_per_layer"))
+                   and g["n_work"] == n and len(flat) <= nat.limit("arrays_per_layer")
+                   and settings.LINE_SHAPE == "reference")         # (the fused step's accumulate kernels are the reference's shape)
         if self._merged_step_applies(flat, lbl):
             # A LAYER whose line lists are due (any of them dirty): ONE accumulate job over the merged, factor-weighted
             # line lists - the absorption coefficient sum_m f_m sum_iso xs_iso (cls:707-712, 581-583, 566-571) accumulated
@@ -486,12 +511,13 @@ class _OpticalMixin:
     @staticmethod
     def _merged_key(flat, conc, layer, g):
         return ("merged", tuple((id(i), i._inputs_version) for i in flat), tuple(float(c) for c in conc), layer.P, layer.T,
-                layer.rangeMin, layer.rangeMax, g["n_base"], g["resolution"], settings.ACCURACY, layer.depth)     # (depth last)
+                layer.rangeMin, layer.rangeMax, g["n_base"], g["resolution"], settings.ACCURACY, settings.LINE_SHAPE,
+                layer.depth)     # (depth last)
 
     @staticmethod
     def _sweep_key(flat, conc, layer, g):
         return (tuple((id(i), i._xs_version) for i in flat), tuple(float(c) for c in conc), layer.P, layer.T, layer.depth,
-                layer.rangeMin, layer.rangeMax, g["n_base"])
+                layer.rangeMin, layer.rangeMax, g["n_base"], settings.LINE_SHAPE)
 
     def _members_ready(self):
         """hook: a Layer / Molecule marks the molecule sums it stands for as computed (cls:566-571)"""
@@ -1049,6 +1075,7 @@ class Layer(_OpticalMixin, list):
             self.hasAtmosphere = atmosphere
         _zeros_later(Layer.crossSection, self, int((rangeMax - rangeMin) / utils.BASE_RESOLUTION))
         self.progressCrossSection = False
+        _live_layers[:] = [r for r in _live_layers if r() is not None] + [weakref.ref(self)]
         if not name:
             name = 'layer %s' % self.atmosphere.nextLayerName()
         self.name = name
@@ -1113,8 +1140,7 @@ class Layer(_OpticalMixin, list):
         """settings.LAYER_STEP "merged" (default): the layer's property chain comes from one merged accumulate job when
         any of its line lists is due (all of them line-by-line: a measured cross-section table has no lines to merge).
         With every cross section current (somebody asked for each of them) the sweep kernel over those arrays is cheaper."""
-        return (settings.LAYER_STEP == "merged" and bool(lbl) and len(lbl) == len(flat)
-                and not _ctx().option("sweep_ieee_divisions")            # (the reference's rounding chain: per-line-list entry points only)
+        return (_merged_route(_ctx()) and bool(lbl) and len(lbl) == len(flat)      # (the reference's rounding chain, the Voigt shape: per-line-list entry points only)
                 and len(flat) <= nat.limit("merged_lists_per_job")      # (more line lists: the per-line-list step, up to "arrays_per_layer")
                 and not any(i._xs_installed and i.progressCrossSection for i in lbl)     # an installed array is not the lines' (advisor, round 5)
                 and any(not i.progressCrossSection or i._xs_deferred for i in lbl))
@@ -1855,7 +1881,7 @@ class Atmosphere(list):
     def _column_abs_coef(self, ctx, layers, n):
         """Every layer's resident absorption coefficient buffer and the plan of _resident_abs_coef, which makes them in the
         merged layer step of the default arithmetic; otherwise every layer's own sweep does, and the plan is None."""
-        if settings.LAYER_STEP == "merged" and not ctx.option("sweep_ieee_divisions"):
+        if _merged_route(ctx):
             plan = self._resident_abs_coef(ctx, layers, n)
             return [p[1].bufs["abs_coef"] for p in plan], plan
         return [L._ensure_swept()[0].bufs["abs_coef"] for L in layers], None
@@ -2266,7 +2292,7 @@ class Atmosphere(list):
         line lists than a job takes, an installed cross section) brings its absorption coefficient by its own route
         (_ensure_swept) and is folded with the others.  None only when settings.LAYER_STEP is not "merged": the caller then
         goes through the per-line-list cross sections of the whole column (lbl_column_step_dev)."""
-        if settings.LAYER_STEP != "merged" or ctx.option("sweep_ieee_divisions"):
+        if not _merged_route(ctx):
             return None
         fast = self._transmission_resident(ctx, layers, n, surfaceSpectrum, surfaceTemperature)
         if fast is not None:

@@ -47,3 +47,24 @@ def set_layer_step(mode):
     if mode not in ("merged", "per-list"):
         raise ValueError("layer step must be 'merged' or 'per-list'")
     LAYER_STEP = mode
+
+
+LINE_SHAPE = "reference"   # the profile every line is evaluated with:
+                           # "reference" (default): the reference's, bit for bit - a Gaussian below lhw / ghw = 0.01, a Lorentzian
+                           #   above 100, the pseudo-Voigt between (cls:378-387; lbl_xsec_accumulate_dev and the merged / fused steps);
+                           # "voigt": the true Voigt profile Re w((x + i lhw) / ghw) / (ghw sqrt(pi)) for every line
+                           #   (lbl_xsec_voigt_dev): one job per line list, then the sweep over the cross sections - the merged
+                           #   and fused layer steps do not apply.  Measured cross-section tables and regimeCounts are untouched.
+
+
+def set_line_shape(shape):
+    """Line shape for everything computed from now on.  A change marks every line-by-line cross section of every live
+    Layer dirty, as a change of temperature does (resetCrossSection, cls:38-45): nothing of the other shape is served."""
+    global LINE_SHAPE
+    if shape not in ("reference", "voigt"):
+        raise ValueError("line shape must be 'reference' or 'voigt'")
+    changed = shape != LINE_SHAPE
+    LINE_SHAPE = shape
+    if changed:
+        from . import model
+        model._line_shape_changed()
