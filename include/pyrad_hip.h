@@ -298,6 +298,29 @@ int lbl_xsec_voigt_dev(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines, const 
  * y == 0 or y > 0; NaN in, NaN out; where the true value is below 1e-290 the result lies in [0, 1e-290].  Stream-ordered.
  * LBL_ERR_BAD_ARG: a NULL argument, negative n, a buffer shorter than n; LBL_ERR_STATE: a buffer of another context. */
 int lbl_voigt_function_dev(lbl_ctx* ctx, lbl_buffer* x, lbl_buffer* y, int64_t n, lbl_buffer* out);
+/* ---- temperature derivative of the Voigt cross section (ABI 5, additions) ----------------------------------------------------
+ * Under the Voigt shape every line is amp * K(x, y) with amp = A / (ghw sqrt(pi)), x = |d| * resolution / ghw, y = lhw / ghw:
+ * smooth in T, while the centre index, the window and the pressure shift do not depend on T.  lbl_xsec_voigt_dt_dev takes
+ * lbl_xsec_voigt_dev's jobs and writes, over the same geometry and through the same regrid (it is linear),
+ *     d(sigma)/dT = sum over lines and offsets of  amp * (a * K + bx * GX + by * GY),   GX = x dK/dx,  GY = y dK/dy,
+ *     a  = d ln amp / dT = dlnw_dT[job] + c2 E / T^2 - (c2 nu' / T^2) / expm1(c2 nu' / T) - 1 / (2 T),
+ *          nu' = nu + delta_air P / p0 (Boltzmann factor, stimulated emission, the 1 / ghw of amp),
+ *     bx = d ln x / dT = -1 / (2 T),      by = d ln y / dT = -(n_air + 1/2) / T.
+ * dlnw_dT[j] (host array, n_jobs doubles) is the logarithmic T-derivative of everything that multiplies job j's intensities
+ * and is not formed from T by the line preparation: -d ln Q / dT for a cross section (iso.Q_T is a number to the library,
+ * its slope is the caller's), -d ln Q / dT - 1 / T for a result that will be weighted by a number density P / (k T).
+ * K, GX, GY come from one device function (voigt_kgrad of lbl_voigt_func.h): |dK|, |dGX|, |dGY| <= 1e-6 K for y == 0 or
+ * 1e-5 <= y <= 1e4 wherever K >= 1e-290; K is lbl_voigt_function_dev's value bit for bit.  The derivative of the reference's
+ * profile does not exist at its regime switches and is not offered.
+ * out[j]: n_base doubles (cm^2 / molecule / K).  Stream-ordered, nothing is synchronised; everything is checked before
+ * anything is enqueued.  Errors as lbl_xsec_voigt_dev, and LBL_ERR_BAD_ARG for a NULL or non-finite dlnw_dT.  The regime
+ * counters (lbl_last_regime_counts) are not touched; lbl_profile_read counts the kernels as prep, accumulate and regrid.
+ * Determinism as lbl_xsec_voigt_dev: line order per point, no atomics, a shard equals the same points of the whole. */
+int lbl_xsec_voigt_dt_dev(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines, const lbl_iso_params* iso,
+                          const double* dlnw_dT, const lbl_grid* grid, lbl_buffer* const* out);
+/* K[i], GX[i], GY[i] = K, x dK/dx, y dK/dy at (x[i], y[i]) for i < n, by the device function the derivative kernel inlines
+ * (tests).  y == 0: GY = 0; GX <= 0; NaN in, NaN out.  Stream-ordered.  Errors as lbl_voigt_function_dev. */
+int lbl_voigt_gradient_dev(lbl_ctx* ctx, lbl_buffer* x, lbl_buffer* y, int64_t n, lbl_buffer* K, lbl_buffer* GX, lbl_buffer* GY);
 
 /* Introspection for tests: the k-th most recently used dispatch schedule of the context (0 = the last one an
  * accumulate batch used).  list receives 2 ints per workgroup (job of the launch group, tile of the job), tabs 8 ints
@@ -438,7 +461,9 @@ int lbl_column_flux_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
  * nan_to_num: n_bands x (2 + 2 n_layers + n_terms) doubles (the caller multiplies by the grid step).  jac_ln_tau_spectra /
  * jac_T_spectra (may be NULL; n_layers x n doubles, layer-major) receive the spectral dF/d ln tau_l and dF/dT_l at every
  * point of every band, 0 elsewhere.  The molecule terms are sensitivities at fixed line shapes (the self-broadening fraction
- * of the Lorentz width is not differentiated); the temperature terms are the Planck part only (no dk/dT).
+ * of the Lorentz width is not differentiated); the temperature terms are the Planck part only.  The absorption part of
+ * dF/dT_l is a term like any other: pass dk_l/dT (lbl_xsec_voigt_dt_dev, weighted as k_l is) as term_abs_coef[m] with
+ * term_layer[m] = l; the term sums are linear in the term and do not depend on its sign.
  * Arithmetic: the upward pass is lbl_column_flux_dev's; the downward pass keeps A and E_lk = sum_{i>l} A_ik (1 - t_ik) B_i
  * and evaluates A_lk t_lk (B_l - I_lk) as A_lk B_l + E_lk - I_Lk, clamped to [-A_lk t_lk max_i I_ik, A_lk t_lk B_l] (exact
  * bounds for non-negative sources), so that no per-level radiance is stored.  Sums in a fixed order, no atomics: the same

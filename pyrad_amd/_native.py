@@ -86,6 +86,8 @@ SIGNATURES = {
                                           C.POINTER(_P)]),
     "lbl_xsec_voigt_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(IsoParams), C.POINTER(Grid), C.POINTER(_P)]),
     "lbl_voigt_function_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "lbl_xsec_voigt_dt_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(IsoParams), _D, C.POINTER(Grid), C.POINTER(_P)]),
+    "lbl_voigt_gradient_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
     "lbl_schedule_export": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int32)]),
     "lbl_last_regime_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
@@ -445,6 +447,25 @@ class Context:
     def voigt_function_dev(self, x, y, n, out):
         """out[i] = Re w(x[i] + 1j * y[i]) for i < n, by the device function the Voigt accumulate kernel inlines."""
         self.check(self.lib.lbl_voigt_function_dev(self.h, x.h, y.h, int(n), out.h))
+
+    def xsec_voigt_dT_dev(self, jobs, dlnw_dT):
+        """d(cross section)/dT of xsec_voigt_dev's jobs (lbl_xsec_voigt_dt_dev); dlnw_dT[j]: the logarithmic T-derivative of what
+        multiplies job j's intensities beside the line preparation's own factors (-dlnQ/dT for a cross section). Asynchronous."""
+        n = len(jobs)
+        if len(dlnw_dT) != n:
+            raise ValueError("one dlnw_dT per job")
+        if n == 0:
+            return
+        L = (_P * n)(*[j[0].h for j in jobs])
+        I = (IsoParams * n)(*[j[1] for j in jobs])
+        G = (Grid * n)(*[j[2] for j in jobs])
+        O = (_P * n)(*[j[3].h for j in jobs])
+        W = (C.c_double * n)(*[float(v) for v in dlnw_dT])
+        self.check(self.lib.lbl_xsec_voigt_dt_dev(self.h, n, L, I, W, G, O))
+
+    def voigt_gradient_dev(self, x, y, n, K, GX, GY):
+        """K, GX = x dK/dx, GY = y dK/dy of K = Re w(x + 1j * y), elementwise, by the device function the dT kernel inlines."""
+        self.check(self.lib.lbl_voigt_gradient_dev(self.h, x.h, y.h, int(n), K.h, GX.h, GY.h))
 
     def schedule_export(self, k: int = 0):
         """(list[n, 2] of (job, tile), tabs[spans, 8], built_on_device) of the k-th most recently used schedule."""

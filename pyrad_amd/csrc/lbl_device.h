@@ -381,6 +381,27 @@ void launch_voigt_prep(const PrepJob* d_prep, const VoigtJob* d_jobs, int n_jobs
 void launch_voigt_accumulate(const VoigtJob* d_jobs, int n_jobs, long long max_points, hipStream_t s);
 void launch_voigt_function(const double* x, const double* y, long long n, double* out, hipStream_t s);
 
+// Temperature derivative of the Voigt cross section (K2v-T, lbl_voigt.hip: lbl_xsec_voigt_dt_dev): K2v's record and two
+// logarithmic derivatives.  The line's contribution at integer offset d is
+//     amp * (a * K + bx * GX + by * GY),  (K, GX, GY) = voigt_kgrad(|d| * xs, y),  bx = -1 / (2 T) of the job.
+struct __attribute__((aligned(16))) VoigtDTRec {
+    double cf, xs, y, amp;      // as VoigtRec
+    double a;                   // d ln amp / dT
+    double by;                  // d ln y / dT = -(n_air + 1/2) / T
+};
+static_assert(sizeof(VoigtDTRec) == 48, "a lane stages one record with three 16-byte loads");
+struct VoigtDTJob {
+    VoigtDTRec* rec;
+    int32_t* cidx;
+    double* out;           // work grid, n_work doubles
+    double dlnw_dT;        // the caller's part of d ln amp / dT (what multiplies the intensities beside line_physics' factors)
+    double bx;             // d ln x / dT = -1 / (2 T)
+    int32_t n_lines, H, p_begin, p_end;     // as VoigtJob
+};
+void launch_voigt_dT_prep(const PrepJob* d_prep, const VoigtDTJob* d_jobs, int n_jobs, int max_lines, hipStream_t s);
+void launch_voigt_dT_accumulate(const VoigtDTJob* d_jobs, int n_jobs, long long max_points, hipStream_t s);
+void launch_voigt_gradient(const double* x, const double* y, long long n, double* K, double* GX, double* GY, hipStream_t s);
+
 struct ColumnArgs {
     const double* trans[kMaxLayers];
     double layer_T[kMaxLayers];

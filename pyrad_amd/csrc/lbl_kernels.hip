@@ -6,6 +6,7 @@
 //                              pyradClasses.py:392-400, restated as an owner-computes gather
 //   K2v voigt_prep_kernel, voigt_accumulate_kernel   the true Voigt profile Re w((x + i lhw) / ghw) / (ghw sqrt(pi)) over the
 //                              same scatter geometry (lbl_xsec_voigt_dev; beyond the reference, see "K2v" below)
+//   K2v-T voigt_dT_prep_kernel, voigt_dT_accumulate_kernel   its temperature derivative, term by term (lbl_xsec_voigt_dt_dev)
 //   K3 regrid_kernel           np.interp of pyradClasses.py:401-405 (only when res != BASE)
 //   K4 layer_sweep_kernel      pyradClasses.py:566-571, 583, 707-716, 784-787; pyradPlanck.py:38-44
 //   K5 column_sweep_kernel     fold of pyradClasses.py:784-787 over layers
@@ -3048,6 +3049,114 @@ __global__ __launch_bounds__(256) void voigt_function_kernel(const double* __res
 }
 
 // ----------------------------------------------------------------------------------------
+// K2v-T: the temperature derivative of the true Voigt cross section (lbl_xsec_voigt_dt_dev)
+// ----------------------------------------------------------------------------------------
+// Under the Voigt shape a line's contribution  amp K(|d| xs, y)  is smooth in T, and the centre index, the window and the
+// pressure shift do not depend on T, so the per-point sum is differentiated term by term:
+//     d/dT [amp K(x, y)] = amp (a K + bx GX + by GY),   GX = x dK/dx, GY = y dK/dy (voigt_kgrad, lbl_voigt_func.h)
+//     a  = d ln amp / dT = dlnw_dT + c2 E / T^2 - (c2 nu' / T^2) / expm1(c2 nu' / T) - 1 / (2 T)
+//          (the caller's factor, e.g. -d ln Q / dT; Boltzmann; stimulated emission; the 1 / ghw of amp)
+//     bx = d ln x / dT = -1 / (2 T)  (ghw ~ sqrt T),      by = d ln y / dT = -(n_air + 1/2) / T  (lhw ~ T^-n_air)
+// The prep kernel writes K2v's four record fields, from the same expressions, and a, by beside them; it counts no regimes
+// (lbl_last_regime_counts keeps describing the last value batch).
+__global__ __launch_bounds__(256) void voigt_dT_prep_kernel(const PrepJob* __restrict__ jobs, const VoigtDTJob* __restrict__ vjobs) {
+    const PrepJob& J = jobs[blockIdx.y];
+    const VoigtDTJob& V = vjobs[blockIdx.y];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= J.n_lines) return;
+    const LinePhysics L = line_physics(J, i);
+    long long idx = (long long)L.fidx;
+    if (idx > 2000000000LL) idx = 2000000000LL;
+    if (idx < -2000000000LL) idx = -2000000000LL;
+    VoigtDTRec r;
+    r.cf = (double)idx;
+    r.xs = J.resolution / L.ghw;
+    r.y = L.ratio;
+    r.amp = L.A * (1.0 / (L.ghw * 1.7724538509055159));           // sqrt(pi)
+    const double c2 = cLight * hPlanck * 100.0 / kB;
+    const double c2_T2 = c2 * J.inv_T * J.inv_T;
+    const double u = c2 * L.broadened * J.inv_T;
+    r.a = V.dlnw_dT + c2_T2 * J.elower[i] - c2_T2 * L.broadened / expm1(u) - 0.5 * J.inv_T;
+    r.by = -(J.n_air[i] + 0.5) * J.inv_T;
+    V.rec[i] = r;
+    V.cidx[i] = (int32_t)idx;
+}
+
+// One pair added to a point's sum, every operation spelled out: the same inputs give the same bits whichever lane, point
+// slot or shard evaluates them.
+__device__ __forceinline__ double voigt_dT_add(double acc, double x, double y, double amp, double a, double bx, double by) {
+#pragma clang fp contract(off)
+    double K, GX, GY;
+    voigt_kgrad(x, y, &K, &GX, &GY);
+    return acc + amp * fma(a, K, fma(bx, GX, by * GY));
+}
+
+// K2v's geometry exactly (owner-computes, wave_line_ranges, wave-private LDS chunks read back as broadcasts, no workgroup
+// barrier, no atomics, line order, |d| <= H, the centre point once); a record is 48 bytes: three 16-byte loads per lane,
+// 3 KB of LDS per wave.
+__global__ __launch_bounds__(256) void voigt_dT_accumulate_kernel(const VoigtDTJob* __restrict__ jobs) {
+    constexpr int R = kVoigtR;
+    const VoigtDTJob& J = jobs[blockIdx.y];
+    const int lane = threadIdx.x & 63;
+    const int wave = uniform_i32(threadIdx.x >> 6);
+    const int n_end = J.p_end;
+    const long long wave_lo_ll = (long long)J.p_begin + ((long long)blockIdx.x * 4 + wave) * (64LL * R);
+    if (wave_lo_ll >= n_end) return;
+    const int wlo = (int)wave_lo_ll;
+    const int whi = min(wlo + 64 * R - 1, n_end - 1);
+    const int H = J.H;
+    int iA, iB, iC, iD;
+    wave_line_ranges(J.cidx, J.n_lines, wlo, whi, H, lane, iA, iB, iC, iD);
+
+    __shared__ double s_rec[4][kVoigtChunk * 6];
+    double* lr = s_rec[wave];
+    const int p0 = wlo + lane * R;
+    const double x0 = (double)p0;
+    const double Hf = (double)H;
+    const double bx = J.bx;
+    double acc[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) acc[k] = 0.0;
+    for (int c0 = iA; c0 < iD; c0 += kVoigtChunk) {
+        const int n = min(kVoigtChunk, iD - c0);
+        __builtin_amdgcn_wave_barrier();                    // (every lane is done with the chunk before)
+        if (lane < n) {
+            const double2* src = reinterpret_cast<const double2*>(J.rec + c0 + lane);
+            double2* dst = reinterpret_cast<double2*>(lr + lane * 6);
+            dst[0] = src[0];
+            dst[1] = src[1];
+            dst[2] = src[2];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (int j = 0; j < n; ++j) {
+            const double cf = lr[j * 6], xs = lr[j * 6 + 1], y = lr[j * 6 + 2], amp = lr[j * 6 + 3];
+            const double a = lr[j * 6 + 4], by = lr[j * 6 + 5];
+            const double d0 = x0 - cf;
+#pragma unroll
+            for (int k = 0; k < R; ++k) {
+                const double ad = fabs(d0 + (double)k);
+                if (ad <= Hf) acc[k] = voigt_dT_add(acc[k], ad * xs, y, amp, a, bx, by);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k)
+        if (p0 + k < n_end) J.out[p0 + k] = acc[k];
+}
+
+// lbl_voigt_gradient_dev: voigt_kgrad elementwise (tests)
+__global__ __launch_bounds__(256) void voigt_gradient_kernel(const double* __restrict__ x, const double* __restrict__ y, long long n,
+                                                             double* __restrict__ K, double* __restrict__ GX, double* __restrict__ GY) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        double k, gx, gy;
+        voigt_kgrad(x[i], y[i], &k, &gx, &gy);
+        K[i] = k; GX[i] = gx; GY[i] = gy;
+    }
+}
+
+// ----------------------------------------------------------------------------------------
 // K3: np.interp from linspace(min,max,n_work) onto linspace(min,max,n_base)
 //     (pyradClasses.py:401-405, 159-162)
 // ----------------------------------------------------------------------------------------
@@ -3994,6 +4103,27 @@ void launch_voigt_accumulate(const VoigtJob* d_jobs, int n_jobs, long long max_p
         dim3 grid((unsigned)((max_points + kVoigtTile - 1) / kVoigtTile), std::min(n_jobs - j0, 65535));
         hipLaunchKernelGGL(voigt_accumulate_kernel, grid, dim3(256), 0, s, d_jobs + j0);
     }
+}
+
+void launch_voigt_dT_prep(const PrepJob* d_prep, const VoigtDTJob* d_jobs, int n_jobs, int max_lines, hipStream_t s) {
+    if (n_jobs <= 0 || max_lines <= 0) return;
+    for (int j0 = 0; j0 < n_jobs; j0 += 65535) {
+        dim3 grid((unsigned)((max_lines + 255) / 256), std::min(n_jobs - j0, 65535));
+        hipLaunchKernelGGL(voigt_dT_prep_kernel, grid, dim3(256), 0, s, d_prep + j0, d_jobs + j0);
+    }
+}
+
+void launch_voigt_dT_accumulate(const VoigtDTJob* d_jobs, int n_jobs, long long max_points, hipStream_t s) {
+    if (n_jobs <= 0 || max_points <= 0) return;
+    for (int j0 = 0; j0 < n_jobs; j0 += 65535) {
+        dim3 grid((unsigned)((max_points + kVoigtTile - 1) / kVoigtTile), std::min(n_jobs - j0, 65535));
+        hipLaunchKernelGGL(voigt_dT_accumulate_kernel, grid, dim3(256), 0, s, d_jobs + j0);
+    }
+}
+
+void launch_voigt_gradient(const double* x, const double* y, long long n, double* K, double* GX, double* GY, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(voigt_gradient_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, n, K, GX, GY);
 }
 
 void launch_voigt_function(const double* x, const double* y, long long n, double* out, hipStream_t s) {

@@ -131,6 +131,11 @@ def getAbsCoef(obj):
     return obj.absCoef
 
 
+def getAbsCoefDT(layer):
+    """dk/dT of a Layer under the Voigt line shape (Layer.absCoefDT; beyond the reference)."""
+    return layer.absCoefDT
+
+
 def getTransmittance(obj):
     if not obj.progressCrossSection:
         obj.createCrossSection()
@@ -372,6 +377,25 @@ def _iso_params(iso):
     q_T = iso.q[layer.T]                       # KeyError for a non-integer temperature, as cls:389
     return nat.IsoParams(float(layer.T), float(layer.P), float(iso.molecule.concentration), float(iso.molmass),
                          float(q_T), float(iso.q296))
+
+
+def _dlnq_dT(iso):
+    """d ln Q / dT of an isotopologue at its layer's temperature, from the integer-kelvin table: the central difference
+    (Q[T+1] - Q[T-1]) / (2 Q[T]), one-sided at a table end; KeyError when T itself is missing (as _iso_params)."""
+    T = iso.layer.T
+    q_T = iso.q[T]
+    try:
+        below, above = iso.q.get(T - 1), iso.q.get(T + 1)
+    except AttributeError:                      # (a table that is no dict: only item access)
+        below = iso.q[T - 1] if (T - 1) in iso.q else None
+        above = iso.q[T + 1] if (T + 1) in iso.q else None
+    if below is not None and above is not None:
+        return (float(above) - float(below)) / (2.0 * float(q_T))
+    if above is not None:
+        return (float(above) - float(q_T)) / float(q_T)
+    if below is not None:
+        return (float(q_T) - float(below)) / float(q_T)
+    raise KeyError(T + 1)
 
 
 def _check_window(g):
@@ -1145,6 +1169,55 @@ class Layer(_OpticalMixin, list):
                 and not any(i._xs_installed and i.progressCrossSection for i in lbl)     # an installed array is not the lines' (advisor, round 5)
                 and any(not i.progressCrossSection or i._xs_deferred for i in lbl))
 
+    def _check_abs_coef_dT(self):
+        """What Layer.absCoefDT refuses, before the device is touched."""
+        if settings.LINE_SHAPE != "voigt":
+            raise ValueError("dk/dT needs settings.set_line_shape(\"voigt\"): the reference line shape switches between Gaussian, "
+                             "pseudo-Voigt and Lorentzian at lhw / ghw = 0.01 and 100, which makes k discontinuous in T")
+        for m in self:
+            if m.exotic:
+                raise ValueError("dk/dT: %s is a measured cross-section table, which has no temperature model" % m.name)
+
+    def _abs_coef_dT(self):
+        """(device buffer, n) of dk/dT = sum_m f_m sum_iso d(sigma_iso)/dT - k / T, f_m = conc_m P / 1E4 / k_B / T as in absCoef:
+        one lbl_xsec_voigt_dt_dev job per line list with dlnw_dT = -d ln Q / dT - 1 / T (the number density's 1 / T rides on
+        every line), summed by the layer sweep, which is linear in its cross-section inputs.  Kept until an input changes
+        (every mutator and settings.set_line_shape bump the isotopologues' input versions)."""
+        self._check_abs_coef_dT()
+        ctx = _ctx()
+        g = self._grid()
+        n = g["n_base"]
+        members, conc = self._sweep_members()
+        flat = [iso for isos in members for iso in isos]
+        if len(flat) > nat.limit("arrays_per_layer"):
+            raise ValueError("dk/dT: %d line lists in one layer, at most %d" % (len(flat), nat.limit("arrays_per_layer")))
+        st = _kept_state(self, "_dT_state").reserve(ctx, n)
+        key = (tuple((id(i), i._inputs_version) for i in flat), tuple(float(c) for c in conc), self.P, self.T, self.rangeMin,
+               self.rangeMax, n, g["resolution"], settings.LINE_SHAPE)
+        if st.key != key:
+            out = st.buf(ctx, "abs_coef_dT")
+            if not flat:
+                out.fill(0.0)
+            else:
+                _check_window(g)
+                jobs = [(iso._device_lines(ctx), _iso_params(iso), _engine.native_grid(g), st.buf(ctx, "dxs%d" % i))
+                        for i, iso in enumerate(flat)]
+                ctx.xsec_voigt_dT_dev(jobs, [-_dlnq_dT(iso) - 1.0 / float(self.T) for iso in flat])
+                iso_mol = [m for m, isos in enumerate(members) for _ in isos]
+                ctx.layer_sweep_dev([j[3] for j in jobs], iso_mol, conc, self.P, self.T, self.depth, self.rangeMin, self.rangeMax, n,
+                                    abs_coef=out)
+            st.key = key
+        return st.bufs["abs_coef_dT"], n
+
+    @property
+    def absCoefDT(self):
+        """dk/dT (per cm per K) on the layer's grid, analytic, under settings.set_line_shape("voigt") only (beyond the
+        reference): line intensities (partition sum from the table's central difference, Boltzmann factor, stimulated
+        emission), Doppler and Lorentz widths and the number density.  ValueError under the reference line shape (its regime
+        switches make k discontinuous in T) and for a layer holding a measured cross-section table."""
+        buf, n = self._abs_coef_dT()
+        return buf.download(n, pinned=True)
+
     def createCrossSection(self):
         """cls:684-689: sum of the molecule cross sections.  One fused layer step brings every dirty
         line list up to date (and leaves absorption coefficient and transmittance resident for the
@@ -1359,10 +1432,12 @@ class Jacobians:
     given; ``temperature``: (L,) dF/dT_l, Planck part; ``opticalDepth``: (L,) dF/d ln tau_l; ``molecules``: one array per
     layer, aligned with list(layer), dF/d ln n of every molecule (None when not asked for); ``moleculeNames``: their names;
     ``mu``, ``weight``: the angle set; ``temperatureSpectrum`` / ``opticalDepthSpectrum``: (L, n) spectral dF/dT_l and
-    dF/d ln tau_l (W m^-2 per cm^-1, 0 outside every band) when asked for, else None."""
+    dF/d ln tau_l (W m^-2 per cm^-1, 0 outside every band) when asked for, else None (the temperature spectrum is the Planck
+    part whatever ``temperature`` was).  ``temperatureAbsorption``: (L,) the absorption part of dF/dT_l, through dk_l/dT, and
+    ``temperatureFull`` = temperature + temperatureAbsorption: both None unless temperature="full" was asked for."""
 
     def __init__(self, olr, surfaceTemperature, temperature, opticalDepth, molecules, moleculeNames, mu, weight,
-                 temperatureSpectrum=None, opticalDepthSpectrum=None):
+                 temperatureSpectrum=None, opticalDepthSpectrum=None, temperatureAbsorption=None):
         self.olr = olr
         self.surfaceTemperature = surfaceTemperature
         self.temperature = temperature
@@ -1373,6 +1448,8 @@ class Jacobians:
         self.weight = weight
         self.temperatureSpectrum = temperatureSpectrum
         self.opticalDepthSpectrum = opticalDepthSpectrum
+        self.temperatureAbsorption = temperatureAbsorption
+        self.temperatureFull = None if temperatureAbsorption is None else temperature + temperatureAbsorption
 
     def __repr__(self):
         return "Jacobians(layers=%d, angles=%d, olr=%s)" % (self.opticalDepth.shape[-1], len(self.mu), self.olr)
@@ -1973,7 +2050,8 @@ class Atmosphere(list):
                       upSpectrum=up_top.download(n) if spectra else None,
                       downSpectrum=down_surface.download(n) if spectra else None)
 
-    def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False):
+    def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False,
+                  temperature="planck"):
         """Analytic sensitivities of the upward flux at the top (beyond the reference), in one pass over the resident
         absorption coefficients.
 
@@ -1986,25 +2064,35 @@ class Atmosphere(list):
             dF/d ln tau_l       = sum_k W_k (tau_l / mu_k) A_lk t_lk (B_l - I_lk)            all absorbers of layer l scaled
             dF/d ln n_(m,l)     = sum_k W_k (k_(m,l) depth_l / mu_k) A_lk t_lk (B_l - I_lk)  molecule m of layer l
             dF/dT_l  (Planck)   = sum_k W_k A_lk (1 - t_lk) dB_l/dT                          absorption coefficients held fixed
+            dF/dT_l  (absorption) = sum_k W_k (dk_l/dT depth_l / mu_k) A_lk t_lk (B_l - I_lk)  temperature="full" only
             dF/dT_s             = sum_k W_k A_(-1)k dB(nu_j, T_s)/dT                         only when the surface is T_s
             band value          = res * sum over the band's points of nan_to_num(spectral value)
         k_(m,l) is molecule m's own absorption coefficient in layer l (Molecule.absCoef); their sum over m is k_l up to
         rounding.  The molecule Jacobian is the sensitivity to absorber amount AT FIXED LINE SHAPES: the self-broadening
-        fraction in the Lorentz width is not differentiated.  The temperature Jacobian is the PLANCK PART ONLY: dk/dT (line
-        intensity, width, number density) is not included.
+        fraction in the Lorentz width is not differentiated.  ``temperature``: "planck" (default) gives the Planck part only;
+        "full" also the absorption part through dk_l/dT (Layer.absCoefDT: line intensity, widths, number density; the Voigt line
+        shape only), one more term per layer in the same pass: Jacobians.temperatureAbsorption and .temperatureFull.  The
+        spectral temperatureSpectrum stays the Planck part.
         ``molecules``: also the molecule terms (one merged accumulate job per layer and molecule, kept with the atmosphere
         and re-used while that molecule's inputs stand; False skips them).  ``spectra``: also the spectral dF/dT_l and
         dF/d ln tau_l, (L, n) each.  Returns a Jacobians.  The layers' absorption coefficients are the ones fluxes() and
         transmission() keep resident: after either nothing is accumulated again.  No other result of the model changes.
         Everything is validated (ValueError) before the device is touched."""
+        if temperature not in ("planck", "full"):
+            raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
             surfaceSpectrum, surfaceTemperature, angles, bands)
         first = layers[0]
         names = [[m.name for m in L] for L in layers]
-        n_terms = sum(len(L) for L in layers) if molecules else 0
+        full = temperature == "full"
+        n_terms = (sum(len(L) for L in layers) if molecules else 0) + (len(layers) if full else 0)
         if n_terms > nat.limit("jacobian_terms"):
-            raise ValueError("molecules: %d molecule terms, at most %d (molecules=False skips them)"
+            raise ValueError(("molecules: %d molecule and dk/dT terms, at most %d (molecules=False skips the molecule terms)" if full
+                              else "molecules: %d molecule terms, at most %d (molecules=False skips them)")
                              % (n_terms, nat.limit("jacobian_terms")))
+        if full:
+            for L in layers:
+                L._check_abs_coef_dT()
         res = utils.BASE_RESOLUTION
         nl, nb = len(layers), len(band_first)
         ctx = _ctx()
@@ -2012,6 +2100,10 @@ class Atmosphere(list):
             raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
         kbufs, plan = self._column_abs_coef(ctx, layers, n)
         term_bufs, term_layer = self._jacobian_terms(ctx, layers, n, plan) if molecules else ([], [])
+        n_mol_terms = len(term_bufs)
+        if full:                 # dk_l/dT as one more term of layer l: the term sums are linear in the term, whatever its sign
+            term_bufs = term_bufs + [L._abs_coef_dT()[0] for L in layers]
+            term_layer = term_layer + list(range(nl))
         nv = 2 + 2 * nl + len(term_bufs)
         out = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, nb * nv))
         I_surface = out.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
@@ -2035,9 +2127,11 @@ class Atmosphere(list):
                 o += len(L)
         olr, dTs, dtau, dT = _band_values(bands, [olr, dTs, dtau, dT])
         mol = _band_values(bands, mol) if mol is not None else None
+        dT_abs = _band_values(bands, [v[:, 2 + 2 * nl + n_mol_terms:]])[0] if full else None
         return Jacobians(olr, dTs if surfaceSpectrum is None else None, dT, dtau, mol, names, mu, weight,
                          temperatureSpectrum=T_spec.download(nl * n).reshape(nl, n) if spectra else None,
-                         opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None)
+                         opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None,
+                         temperatureAbsorption=dT_abs)
 
     def observe(self, instrument, surfaceTemperature=None, surfaceSpectrum=None, mu=1.0, jacobians=False):
         """What an instrument above the column sees at viewing cosine ``mu`` (beyond the reference): the upward radiance at
