@@ -508,6 +508,47 @@ int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef
                          lbl_buffer* I_source, double source_T,
                          lbl_buffer* radiance, lbl_buffer* transmittance /* may be NULL */);
 
+/* ---- ray-path Jacobians (beyond the reference; ABI 5, backward compatible) --------------------------------------------
+ * pyrad_amd.model.Atmosphere.pathJacobians: the weighting functions of the radiance lbl_ray_radiance_dev computes - its
+ * analytic derivatives to every crossed layer's optical depth and (Planck) temperature, to the source temperature and to any
+ * number of absorber terms - per ray and grid point, in one pass.  Column, grid, rays, segments and sources as
+ * lbl_ray_radiance_dev takes them, and its arithmetic on the way out: radiance (may be NULL; n_rays x n) receives that call's
+ * radiance bit for bit.  For ray r at grid point nu_j, with I_s the radiance entering segment s (I_s0 the source), t_s =
+ * exp(-tau_s), tau_s = k_l(nu_j) seg_length[s], l = seg_layer[s], B_s = B(nu_j, T_l) and A_s = the product of t_i over the
+ * segments i after s (1 for the last):
+ *   dI/d ln tau_l     = sum over the ray's segments s in layer l of tau_s A_s t_s (B_s - I_s)     all absorbers of l scaled
+ *   dI/dT_l (Planck)  = sum over the same segments of A_s (1 - t_s) dB(nu_j, T_l)/dT              k_l held fixed
+ *   term m            = sum over the ray's segments s in layer term_layer[m] of term_abs_coef[m][j] seg_length[s] A_s t_s (B_s - I_s)
+ *   dI/dT_source      = (the product of all t_s) dB(nu_j, source_T)/dT for source_kind 1 without I_source, else 0
+ * The terms are lbl_column_jacobian_dev's: pass a molecule's own absorption coefficient for dI/d ln n_m at fixed line shapes,
+ * dk_l/dT (lbl_xsec_voigt_dt_dev) for the absorption part of dI/dT_l; the sums are linear in the term whatever its sign.
+ * Rows.  Only the layers a ray crosses have rows (the other derivatives are 0).  Ray r crosses c_r distinct layers
+ * l_0 < l_1 < ... and m_r of the terms lie in one of them; it owns the 1 + 2 c_r + m_r consecutive rows from row_first[r]
+ * = the sum of the counts of the rays before it:
+ *   row 0: dI/dT_source;   rows 1 .. c_r: dI/d ln tau of l_0, l_1, ...;   rows c_r + 1 .. 2 c_r: dI/dT of l_0, l_1, ...;
+ *   then its m_r terms in the order of the term list.            jac[row * n + j] is the value at grid point j.
+ * lbl_ray_jacobian_rows returns that layout - row_first (n_rays + 1 values, the last one the total; may be NULL) and the
+ * total *rows - without a context; it refuses (LBL_ERR_BAD_ARG) the ray lists and term layers lbl_ray_jacobian_dev refuses.
+ * Arithmetic: the forward walk keeps the running maximum Imax of I over the source and every segment end; the segments
+ * are then walked last to first with A and D = E - I, E = the emission of the later segments that reaches the observer, and
+ * A_s t_s (B_s - I_s) is evaluated as A_s B_s + D_s clamped to [-A_s t_s Imax, A_s t_s B_s] (lbl_column_jacobian_dev's form:
+ * exact bounds for non-negative sources, no stored radiances).  A layer crossed more than once: its last segment stores the
+ * layer's rows, every earlier one adds to them in that fixed order, the same thread each time.  No atomics and nothing
+ * zeroed beforehand: the same inputs give the same bits, and a ray's rows do not depend on the other rays of the call.
+ * LBL_ERR_BAD_ARG: everything lbl_ray_radiance_dev refuses (radiance may be NULL here); n_terms outside
+ * 0..lbl_limit("jacobian_terms") = 512; a NULL term or term list; a term layer outside [0, n_layers); a term buffer shorter
+ * than n; jac NULL or shorter than rows x n; rows x n beyond int64.  Everything is checked before anything is enqueued; the
+ * host arrays are copied and not retained.  Stream-ordered on the context's stream; nothing is synchronised. */
+int lbl_ray_jacobian_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
+                          int n_terms, const int32_t* term_layer,
+                          int64_t* row_first /* n_rays + 1, may be NULL */, int64_t* rows);
+int lbl_ray_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                         double range_min, double range_max, int64_t n,
+                         int n_rays, const int32_t* ray_first, const int32_t* seg_layer, const double* seg_length,
+                         const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                         int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
+                         lbl_buffer* radiance /* n_rays x n, may be NULL */, lbl_buffer* jac /* rows x n */);
+
 /* ---- instrument channels (beyond the reference; ABI 5, backward compatible) -------------------------------------------
  * pyrad_amd.model.convolve / Atmosphere.observe: n_rows device-resident spectra on the base grid linspace(range_min,
  * range_max, n) convolved with an instrument line shape (ILS) onto n_channels channels, so that channel radiances and channel

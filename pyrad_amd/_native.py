@@ -112,6 +112,11 @@ SIGNATURES = {
     "lbl_ray_radiance_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P, C.c_double,
                                        _P, _P]),
+    "lbl_ray_jacobian_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lbl_ray_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P, C.c_double,
+                                       C.c_int, C.POINTER(_P), C.POINTER(C.c_int32), _P, _P]),
     "lbl_ils_convolve_dev": (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64),
                                        C.c_int64, _D, _D, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_int,
                                        C.c_double, _D, _P]),
@@ -215,6 +220,23 @@ def limit(name: str) -> int:
             raise LblError(rc, "unknown limit %r" % name)
         _limits[name] = int(v.value)
     return _limits[name]
+
+
+def ray_jacobian_rows(n_layers, ray_first, seg_layer, term_layer=()):
+    """The rows of lbl_ray_jacobian_dev's ``jac`` (lbl_ray_jacobian_rows; no context needed): (row_first, rows) with
+    row_first the n_rays + 1 first rows of the rays and rows the total.  Ray r owns [dI/dT_source, c x dI/d ln tau, c x
+    dI/dT, its terms] for the c distinct layers it crosses in ascending order and the terms that lie in one of them."""
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None
+    ray_first, seg_layer, term_layer = i32(ray_first), i32(seg_layer), i32(term_layer)
+    lib = load()
+    first = np.zeros(max(len(ray_first), 1), dtype=np.int64)
+    rows = C.c_int64()
+    rc = lib.lbl_ray_jacobian_rows(int(n_layers), len(ray_first) - 1, i32p(ray_first), i32p(seg_layer), len(term_layer),
+                                   i32p(term_layer), first.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(rows))
+    if rc != LBL_OK:
+        raise LblError(rc, (lib.lbl_last_error(None) or b"").decode())
+    return first, int(rows.value)
 
 
 def _as_f64(a):
@@ -607,6 +629,25 @@ class Context:
             float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
             seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T), _hb(radiance),
             _hb(transmittance)))
+
+    def ray_jacobian_dev(self, abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length, source_kind, jac,
+                         I_source=None, source_T=0.0, term_abs_coef=(), term_layer=(), radiance=None):
+        """Weighting functions of the radiance along ray paths (lbl_ray_jacobian_dev): the rays as ray_radiance_dev takes
+        them; ``jac`` receives ray_jacobian_rows(...) rows of n doubles - per ray [dI/dT_source, dI/d ln tau and dI/dT of
+        every crossed layer, the terms in crossed layers] - and ``radiance`` (optional) len(source_kind) x n doubles;
+        ``term_layer`` gives each term's layer."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
+        seg_length = _as_f64(seg_length)
+        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length) or len(term_abs_coef) != len(term_layer):
+            raise ValueError("ray_jacobian_dev: one ray_first per ray and one more, one length per segment layer, one layer "
+                             "per term")
+        self.check(self.lib.lbl_ray_jacobian_dev(
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
+            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
+            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T), len(term_abs_coef),
+            _arr(_P, [b.h for b in term_abs_coef]), _arr(C.c_int32, [int(l) for l in term_layer]), _hb(radiance), _hb(jac)))
 
     def ils_convolve_dev(self, range_min, range_max, n, rows, position, width, first, count, shape, out, table=None,
                          table_half=0.0):

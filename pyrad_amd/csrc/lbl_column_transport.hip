@@ -1,6 +1,6 @@
 // Column transport (include/pyrad_hip.h, "level fluxes", "Jacobians" and "ray paths"): argument checking and the launch
-// sequences of lbl_column_flux_dev, lbl_column_jacobian_dev and lbl_ray_radiance_dev.  The kernels are K5c, K5d and K5e of
-// lbl_kernels.hip; the context's internals
+// sequences of lbl_column_flux_dev, lbl_column_jacobian_dev, lbl_ray_radiance_dev and lbl_ray_jacobian_dev.  The kernels are
+// K5c, K5d, K5e and K5f of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -206,32 +206,44 @@ extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* c
 
 static size_t round8(size_t b) { return (b + 7) & ~(size_t)7; }
 
-extern "C" int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
-                                    double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
-                                    const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
-                                    lbl_buffer* I_source, double source_T, lbl_buffer* radiance,
-                                    lbl_buffer* transmittance) try {
-    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+// What lbl_ray_radiance_dev, lbl_ray_jacobian_dev and lbl_ray_jacobian_rows (ctx NULL) check of the ray lists themselves.
+static int check_ray_lists(lbl_ctx* ctx, int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer) {
     if (n_layers < 1 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d layers", kMaxLayers);
-    if (n < 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "n must be >= 1");
-    if (!abs_coef || !T) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
-    if (ctx_sweep_ieee(ctx))
-        return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", "ray paths");
     if (n_rays < 1 || n_rays > kMaxRayPaths) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d rays", kMaxRayPaths);
-    if (!ray_first || !source_kind) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL ray list");
+    if (!ray_first) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL ray list");
     if (ray_first[0] != 0) return column_fail(ctx, LBL_ERR_BAD_ARG, "ray_first[0] must be 0");
     for (int r = 0; r < n_rays; ++r)
         if (ray_first[r + 1] < ray_first[r]) return column_fail(ctx, LBL_ERR_BAD_ARG, "ray %d: ray_first decreases", r);
     const int n_seg = ray_first[n_rays];
     if (n_seg > kMaxRaySegments) return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d segments", kMaxRaySegments);
-    if (n_seg > 0 && (!seg_layer || !seg_length)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL segment list");
-    for (int s = 0; s < n_seg; ++s) {
+    if (n_seg > 0 && !seg_layer) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL segment list");
+    for (int s = 0; s < n_seg; ++s)
         if (seg_layer[s] < 0 || seg_layer[s] >= n_layers)
             return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: layer %d outside [0, %d)", s, (int)seg_layer[s], n_layers);
+    return LBL_OK;
+}
+
+// Everything lbl_ray_radiance_dev and lbl_ray_jacobian_dev check of the arguments they share (ctx non-NULL), then the
+// RayArgs part of the argument block filled - the tables start `header` bytes into the block, *bytes is where they end -
+// and the dispatch order found.  `radiance` holds n_rays x n and may be NULL only where it is not `radiance_required`.
+static int check_rays(lbl_ctx* ctx, RayArgs* a, size_t header, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                      double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
+                      const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind, lbl_buffer* I_source,
+                      double source_T, lbl_buffer* radiance, bool radiance_required, lbl_buffer* transmittance,
+                      std::vector<int32_t>* order, size_t* bytes) {
+    if (n_layers < 1 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d layers", kMaxLayers);
+    if (n < 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "n must be >= 1");
+    if (!abs_coef || !T) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if (ctx_sweep_ieee(ctx))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", "ray paths");
+    int rc;
+    if ((rc = check_ray_lists(ctx, n_layers, n_rays, ray_first, seg_layer))) return rc;
+    if (!source_kind) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL ray list");
+    const int n_seg = ray_first[n_rays];
+    if (n_seg > 0 && !seg_length) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL segment list");
+    for (int s = 0; s < n_seg; ++s)
         if (!(seg_length[s] >= 0) || !std::isfinite(seg_length[s]))
             return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: length must be finite and >= 0", s);
-    }
-    int rc;
     if ((rc = ctx_check_buffer(ctx, I_source, n, "I_source", false))) return rc;
     for (int r = 0; r < n_rays; ++r) {
         if (source_kind[r] != 0 && source_kind[r] != 1)
@@ -240,39 +252,39 @@ extern "C" int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
             return column_fail(ctx, LBL_ERR_BAD_ARG, "ray %d: a surface source needs I_source or source_T > 0", r);
     }
     if (n > INT64_MAX / n_rays) return column_fail(ctx, LBL_ERR_BAD_ARG, "n_rays x n overflows");
-    if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_rays * n, "radiance", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_rays * n, "radiance", radiance_required))) return rc;
     if ((rc = ctx_check_buffer(ctx, transmittance, (int64_t)n_rays * n, "transmittance", false))) return rc;
 
-    // the argument block: header, ray_first, seg_layer, seg_length, source_kind, order
-    RayArgs a;
-    memset((void*)&a, 0, sizeof a);
     double pa = 0.0;
     for (int l = 0; l < n_layers; ++l) {
         if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
         if (!(T[l] > 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
-        a.abs_coef[l] = buffer_data(abs_coef[l]);
-        planck_budget_constants(T[l], &pa, &a.pbkT[l]);
-        a.pbkT_min = l == 0 ? a.pbkT[l] : std::min(a.pbkT_min, a.pbkT[l]);
-        a.pbkT_max = l == 0 ? a.pbkT[l] : std::max(a.pbkT_max, a.pbkT[l]);
+        a->abs_coef[l] = buffer_data(abs_coef[l]);
+        planck_budget_constants(T[l], &pa, &a->pbkT[l]);
+        a->pbkT_min = l == 0 ? a->pbkT[l] : std::min(a->pbkT_min, a->pbkT[l]);
+        a->pbkT_max = l == 0 ? a->pbkT[l] : std::max(a->pbkT_max, a->pbkT[l]);
     }
-    planck_budget_constants(source_T > 0 ? source_T : 1.0, &pa, &a.pbk_surface);
-    a.pa = pa;
-    a.start = range_min; a.stop = range_max; a.step = grid_step(range_min, range_max, n);
-    a.I_surface = I_source ? buffer_data(I_source) : nullptr;
-    a.n = n;
-    a.n_layers = n_layers;
-    a.radiance = buffer_data(radiance);
-    a.transmittance = transmittance ? buffer_data(transmittance) : nullptr;
-    a.n_rays = n_rays;
-    size_t off = round8(sizeof a);
-    a.off_ray_first = (long long)off;   off += round8((size_t)(n_rays + 1) * sizeof(int32_t));
-    a.off_seg_layer = (long long)off;   off += round8((size_t)n_seg * sizeof(int32_t));
-    a.off_seg_length = (long long)off;  off += (size_t)n_seg * sizeof(double);
-    a.off_source_kind = (long long)off; off += round8((size_t)n_rays * sizeof(int32_t));
-    a.off_order = (long long)off;       off += round8((size_t)n_rays * sizeof(int32_t));
+    planck_budget_constants(source_T > 0 ? source_T : 1.0, &pa, &a->pbk_surface);
+    a->pa = pa;
+    a->start = range_min; a->stop = range_max; a->step = grid_step(range_min, range_max, n);
+    a->I_surface = I_source ? buffer_data(I_source) : nullptr;
+    a->n = n;
+    a->n_layers = n_layers;
+    a->radiance = radiance ? buffer_data(radiance) : nullptr;
+    a->transmittance = transmittance ? buffer_data(transmittance) : nullptr;
+    a->n_rays = n_rays;
+    // the tables: ray_first, seg_layer, seg_length, source_kind, order
+    size_t off = round8(header);
+    a->off_ray_first = (long long)off;   off += round8((size_t)(n_rays + 1) * sizeof(int32_t));
+    a->off_seg_layer = (long long)off;   off += round8((size_t)n_seg * sizeof(int32_t));
+    a->off_seg_length = (long long)off;  off += (size_t)n_seg * sizeof(double);
+    a->off_source_kind = (long long)off; off += round8((size_t)n_rays * sizeof(int32_t));
+    a->off_order = (long long)off;       off += round8((size_t)n_rays * sizeof(int32_t));
+    *bytes = off;
     // Bundles: rays with one layer sequence (and at least one segment), kRayBundle at a time in the order they come; what
     // is left of every sequence, and the rays without segments, go one by one.  (A ray's arithmetic is the same either way.)
-    std::vector<int32_t> order, single;
+    std::vector<int32_t> single;
+    order->clear();
     {
         std::map<std::vector<int32_t>, std::vector<int32_t>> open;
         for (int r = 0; r < n_rays; ++r) {
@@ -280,28 +292,189 @@ extern "C" int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
             auto& waiting = open[std::vector<int32_t>(seg_layer + ray_first[r], seg_layer + ray_first[r + 1])];
             waiting.push_back(r);
             if ((int)waiting.size() == kRayBundle) {
-                order.insert(order.end(), waiting.begin(), waiting.end());
+                order->insert(order->end(), waiting.begin(), waiting.end());
                 waiting.clear();
             }
         }
         for (auto& kv : open) single.insert(single.end(), kv.second.begin(), kv.second.end());
     }
-    a.n_bundles = (int32_t)order.size() / kRayBundle;
-    order.insert(order.end(), single.begin(), single.end());
-    std::vector<char> blk(off, 0);
-    memcpy(blk.data(), (const void*)&a, sizeof a);
-    memcpy(blk.data() + a.off_ray_first, ray_first, (size_t)(n_rays + 1) * sizeof(int32_t));
+    a->n_bundles = (int32_t)order->size() / kRayBundle;
+    order->insert(order->end(), single.begin(), single.end());
+    return LBL_OK;
+}
+
+// the tables check_rays laid out, copied into the block (whose header the caller copies)
+static void fill_ray_tables(char* blk, const RayArgs& a, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
+                            const double* seg_length, const int32_t* source_kind, const std::vector<int32_t>& order) {
+    const int n_seg = ray_first[n_rays];
+    memcpy(blk + a.off_ray_first, ray_first, (size_t)(n_rays + 1) * sizeof(int32_t));
     if (n_seg > 0) {
-        memcpy(blk.data() + a.off_seg_layer, seg_layer, (size_t)n_seg * sizeof(int32_t));
-        memcpy(blk.data() + a.off_seg_length, seg_length, (size_t)n_seg * sizeof(double));
+        memcpy(blk + a.off_seg_layer, seg_layer, (size_t)n_seg * sizeof(int32_t));
+        memcpy(blk + a.off_seg_length, seg_length, (size_t)n_seg * sizeof(double));
     }
-    memcpy(blk.data() + a.off_source_kind, source_kind, (size_t)n_rays * sizeof(int32_t));
-    memcpy(blk.data() + a.off_order, order.data(), (size_t)n_rays * sizeof(int32_t));
+    memcpy(blk + a.off_source_kind, source_kind, (size_t)n_rays * sizeof(int32_t));
+    memcpy(blk + a.off_order, order.data(), (size_t)n_rays * sizeof(int32_t));
+}
+
+extern "C" int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                    double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
+                                    const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
+                                    lbl_buffer* I_source, double source_T, lbl_buffer* radiance,
+                                    lbl_buffer* transmittance) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    // the argument block: header, ray_first, seg_layer, seg_length, source_kind, order
+    RayArgs a;
+    memset((void*)&a, 0, sizeof a);
+    std::vector<int32_t> order;
+    size_t bytes = 0;
+    int rc;
+    if ((rc = check_rays(ctx, &a, sizeof a, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
+                         seg_length, source_kind, I_source, source_T, radiance, true, transmittance, &order, &bytes)))
+        return rc;
+    std::vector<char> blk(bytes, 0);
+    memcpy(blk.data(), (const void*)&a, sizeof a);
+    fill_ray_tables(blk.data(), a, n_rays, ray_first, seg_layer, seg_length, source_kind, order);
 
     void* d_args = nullptr;
     if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
     COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
     launch_ray_radiance((const RayArgs*)d_args, n, n_rays, a.n_bundles, ctx_stream(ctx));
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+} LBL_GUARD_END(ctx)
+
+// The rows of lbl_ray_jacobian_dev (include/pyrad_hip.h): per ray the distinct layers it crosses in ascending order and
+// the terms whose layer it crosses in term order.  The lists are checked already.
+struct RayRows {
+    std::vector<int64_t> row_first;          // n_rays + 1
+    std::vector<int32_t> crossed;            // per ray: c
+    std::vector<int32_t> seg_slot;           // per segment: the rank of its layer among the ray's | kRayRowStore
+    std::vector<int32_t> ray_terms;          // per ray: start of its table in term_row
+    std::vector<int32_t> term_row;           // per set of crossed layers: the row of original term m, relative (-1: not crossed)
+};
+static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer, int n_terms,
+                     const int32_t* term_layer, RayRows* R) {
+    R->row_first.assign(1, 0);
+    R->crossed.clear(); R->ray_terms.clear(); R->term_row.clear();
+    R->seg_slot.assign((size_t)ray_first[n_rays], 0);
+    std::map<std::vector<int32_t>, int32_t> tables;
+    std::vector<int32_t> rank(n_layers);
+    for (int r = 0; r < n_rays; ++r) {
+        std::fill(rank.begin(), rank.end(), -1);
+        for (int s = ray_first[r]; s < ray_first[r + 1]; ++s) rank[seg_layer[s]] = 0;
+        std::vector<int32_t> set;
+        for (int l = 0; l < n_layers; ++l)
+            if (rank[l] == 0) { rank[l] = (int32_t)set.size(); set.push_back(l); }
+        const int c = (int)set.size();
+        // backward order: the last segment of a layer stores its rows, the earlier ones add
+        std::vector<char> seen(n_layers, 0);
+        for (int s = ray_first[r + 1] - 1; s >= ray_first[r]; --s) {
+            R->seg_slot[s] = rank[seg_layer[s]] | (seen[seg_layer[s]] ? 0 : kRayRowStore);
+            seen[seg_layer[s]] = 1;
+        }
+        int m_r = 0;
+        for (int m = 0; m < n_terms; ++m) m_r += rank[term_layer[m]] >= 0;
+        if (n_terms > 0) {
+            auto it = tables.find(set);
+            if (it == tables.end()) {
+                it = tables.emplace(set, (int32_t)R->term_row.size()).first;
+                int next = 1 + 2 * c;
+                for (int m = 0; m < n_terms; ++m) R->term_row.push_back(rank[term_layer[m]] >= 0 ? next++ : -1);
+            }
+            R->ray_terms.push_back(it->second);
+        } else {
+            R->ray_terms.push_back(0);
+        }
+        R->crossed.push_back(c);
+        R->row_first.push_back(R->row_first.back() + 1 + 2 * c + m_r);
+    }
+}
+
+static int check_ray_terms(lbl_ctx* ctx, int n_layers, int n_terms, const int32_t* term_layer) {
+    if (n_terms < 0 || n_terms > kMaxJacobianTerms)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d terms", kMaxJacobianTerms);
+    if (n_terms > 0 && !term_layer) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
+    for (int t = 0; t < n_terms; ++t)
+        if (term_layer[t] < 0 || term_layer[t] >= n_layers)
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "term %d: layer %d outside [0, %d)", t, (int)term_layer[t], n_layers);
+    return LBL_OK;
+}
+
+extern "C" int lbl_ray_jacobian_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
+                                     int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows) try {
+    int rc;
+    if (!rows) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "rows is NULL");
+    if ((rc = check_ray_lists(nullptr, n_layers, n_rays, ray_first, seg_layer))) return rc;
+    if ((rc = check_ray_terms(nullptr, n_layers, n_terms, term_layer))) return rc;
+    RayRows R;
+    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, &R);
+    if (row_first) memcpy(row_first, R.row_first.data(), (size_t)(n_rays + 1) * sizeof(int64_t));
+    *rows = R.row_first.back();
+    return LBL_OK;
+} LBL_GUARD_END(nullptr)
+
+extern "C" int lbl_ray_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                    double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
+                                    const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
+                                    lbl_buffer* I_source, double source_T, int n_terms, lbl_buffer* const* term_abs_coef,
+                                    const int32_t* term_layer, lbl_buffer* radiance, lbl_buffer* jac) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    // the argument block: header, K5e's tables, row_first, ray_crossed, seg_slot, ray_terms, term_row
+    std::vector<char> head(sizeof(RayJacArgs), 0);
+    RayJacArgs* a = (RayJacArgs*)head.data();
+    std::vector<int32_t> order;
+    size_t off = 0;
+    int rc;
+    if ((rc = check_rays(ctx, a, sizeof(RayJacArgs), n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first,
+                         seg_layer, seg_length, source_kind, I_source, source_T, radiance, false, nullptr, &order, &off)))
+        return rc;
+    if ((rc = check_ray_terms(ctx, n_layers, n_terms, term_layer))) return rc;
+    if (n_terms > 0 && !term_abs_coef) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
+    for (int t = 0; t < n_terms; ++t)
+        if ((rc = ctx_check_buffer(ctx, term_abs_coef[t], n, "term_abs_coef", true))) return rc;
+    RayRows R;
+    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, &R);
+    const int64_t rows = R.row_first.back();
+    if (n > INT64_MAX / rows) return column_fail(ctx, LBL_ERR_BAD_ARG, "rows x n overflows");
+    if ((rc = ctx_check_buffer(ctx, jac, rows * n, "jac", true))) return rc;
+    // the terms sorted by layer (stable), and every table of term rows re-ordered to match
+    std::vector<int32_t> sorted(std::max(n_terms, 1), 0);
+    for (int t = 0; t < n_terms; ++t) ++a->layer_term[term_layer[t] + 1];
+    for (int l = 0; l < n_layers; ++l) a->layer_term[l + 1] += a->layer_term[l];
+    {
+        std::vector<int32_t> fill(a->layer_term, a->layer_term + n_layers);
+        for (int t = 0; t < n_terms; ++t) {
+            const int pos = fill[term_layer[t]]++;
+            a->term_k[pos] = buffer_data(term_abs_coef[t]);
+            sorted[pos] = t;
+        }
+    }
+    std::vector<int32_t> term_row(R.term_row.size());
+    for (size_t base = 0; base < term_row.size(); base += (size_t)n_terms)
+        for (int pos = 0; pos < n_terms; ++pos) term_row[base + pos] = R.term_row[base + sorted[pos]];
+    for (int l = 0; l < n_layers; ++l) a->rT[l] = 1.0 / T[l];
+    a->r_source_T = source_T > 0 ? 1.0 / source_T : 0.0;
+    a->jac = buffer_data(jac);
+    a->n_terms = n_terms;
+    const int n_seg = ray_first[n_rays];
+    a->off_row_first = (long long)off;   off += (size_t)n_rays * sizeof(int64_t);
+    a->off_ray_crossed = (long long)off; off += round8((size_t)n_rays * sizeof(int32_t));
+    a->off_seg_slot = (long long)off;    off += round8((size_t)n_seg * sizeof(int32_t));
+    a->off_ray_terms = (long long)off;   off += round8((size_t)n_rays * sizeof(int32_t));
+    a->off_term_row = (long long)off;    off += round8(term_row.size() * sizeof(int32_t));
+    std::vector<char> blk(off, 0);
+    memcpy(blk.data(), head.data(), head.size());
+    fill_ray_tables(blk.data(), *a, n_rays, ray_first, seg_layer, seg_length, source_kind, order);
+    memcpy(blk.data() + a->off_row_first, R.row_first.data(), (size_t)n_rays * sizeof(int64_t));
+    memcpy(blk.data() + a->off_ray_crossed, R.crossed.data(), (size_t)n_rays * sizeof(int32_t));
+    if (n_seg > 0) memcpy(blk.data() + a->off_seg_slot, R.seg_slot.data(), (size_t)n_seg * sizeof(int32_t));
+    memcpy(blk.data() + a->off_ray_terms, R.ray_terms.data(), (size_t)n_rays * sizeof(int32_t));
+    if (!term_row.empty()) memcpy(blk.data() + a->off_term_row, term_row.data(), term_row.size() * sizeof(int32_t));
+
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    launch_ray_jacobian((const RayJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
 } LBL_GUARD_END(ctx)

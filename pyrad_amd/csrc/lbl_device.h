@@ -292,6 +292,28 @@ struct RayArgs : ColumnRT {
 };
 void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s);
 
+// Ray-path Jacobians (K5f, lbl_column_transport.hip: lbl_ray_jacobian_dev): K5e's walk, then the segments last to first
+// with K5d's transmittance-and-emission recurrence, one output row per ray, kind and crossed layer.  RayArgs' block with
+// more tables behind it; `radiance` may be nullptr here and `transmittance` is not used.  A ray's rows start at row_first[r]:
+// [dT_source, c x d ln tau, c x dT, its terms] with c the number of distinct layers it crosses (include/pyrad_hip.h).
+constexpr int32_t kRayRowStore = 1 << 30;     // flag of a seg_slot entry: the segment is its layer's first in backward order
+struct RayJacArgs : RayArgs {
+    double rT[kMaxLayers];              // 1 / T_l
+    double r_source_T;                  // 1 / source_T (used when I_surface == nullptr)
+    long long off_row_first;            // n_rays x int64: the ray's first row
+    long long off_ray_crossed;          // n_rays x int32: c, the distinct layers the ray crosses
+    long long off_seg_slot;             // n_segments x int32: rank of the segment's layer among the ray's distinct layers,
+                                        // | kRayRowStore where the row is stored, not added to
+    long long off_ray_terms;            // n_rays x int32: where the ray's term rows start in the table at off_term_row
+    long long off_term_row;             // int32 per sorted term: its row relative to the ray's first (rays that cross the
+                                        // same set of layers share one table; entries of layers not crossed are never read)
+    double* jac;                        // rows x n, row-major
+    const double* term_k[kMaxJacobianTerms];   // the terms sorted by layer (stable)
+    int32_t layer_term[kMaxLayers + 1];        // terms of layer l: [layer_term[l], layer_term[l + 1])
+    int32_t n_terms, pad;
+};
+void launch_ray_jacobian(const RayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms, hipStream_t s);
+
 // Instrument channels (K8, lbl_instrument.hip: lbl_ils_convolve_dev): n_rows spectra on the base grid convolved with an
 // instrument line shape onto n_channels channels.  One argument block per call: this header, then the arrays it names by
 // their byte offset from the block's start (the block's device address is known only after it is uploaded).

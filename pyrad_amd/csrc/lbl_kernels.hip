@@ -18,7 +18,9 @@
 //                              (Atmosphere.jacobians; beyond the reference)
 //   K5e ray_radiance_kernel    K5c's step along ordered (layer, path length) segments: limb, slant and zenith rays
 //                              (Atmosphere.radiance; beyond the reference)
-//   K7 line_survey_kernel      pyradClasses.py:409-428
+//   K5f ray_jacobian_kernel    K5e's walk + K5d's downward pass along the segments: weighting functions of the radiance
+//                              along a ray (Atmosphere.pathJacobians; beyond the reference)
+//   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
 // grid index and samples the half-profile at integer multiples of the resolution, so the
@@ -3945,6 +3947,153 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
         partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
 }
 
+// K5f: ray-path Jacobians (lbl_ray_jacobian_dev; the semantics are in include/pyrad_hip.h).  K5e's walk over the bundle's
+// segments (the same transport_step, exp and update, so the radiance is K5e's bit for bit), keeping per ray and point the
+// running maximum Imax of I; then K5d's downward pass along the segments last to first: k_l re-read a segment ahead, B_l
+// and dB_l/dT recomputed, and per ray the transmittance A from the segment's end to the observer and D = E - I_final.
+//     A t (B - I_s) = A B + D, clamped to [-A t Imax, A t B]            (I_s: the radiance entering the segment)
+// One row per ray, kind and crossed layer: the layer's first segment in this backward order stores, every later one adds to
+// what the same thread stored (the host marks the first, kRayRowStore).  No atomics, no memset, no LDS, nothing shared between
+// threads: the same inputs give the same bits, and a ray's rows do not depend on the rays it travels with.
+// TERMS = false leaves the term loop out (a call without terms): the bundle then need not keep g for it and fits two waves
+// per SIMD; the arithmetic of every other row is the same.
+template <int NP, int RB, bool TERMS>
+__global__ __launch_bounds__(256) void ray_jacobian_kernel(const RayJacArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                           long long lo1, long long n1, int order_first) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    const RayJacArgs& A = *Ap;
+    const char* blk = (const char*)Ap;
+    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
+    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
+    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
+    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
+    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
+    const long long* __restrict__ row_first = (const long long*)(blk + A.off_row_first);
+    // (idle lanes of the last workgroup work on a valid point and store nothing)
+    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
+    const bool active = q < n0 + n1;
+    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    double nu[NP], pa_n[NP], Is[NP], I[RB][NP], Imax[RB][NP], Ak[RB][NP];
+    column_points<NP>(A, j, nu, pa_n);
+    const bool fast = fold_fast_path<NP>(A, nu, active);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+    int rid[RB], s0[RB];
+    bool surface[RB];
+    long long row0[RB];                                   // the ray's first row
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
+        s0[i] = ray_first[rid[i]];
+        surface[i] = source_kind[rid[i]] == 1;
+        row0[i] = row_first[rid[i]];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) { I[i][p] = surface[i] ? Is[p] : 0.0; Imax[i][p] = I[i][p]; }
+    }
+    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers and rows)
+    const int32_t* lay = seg_layer + s0[0];
+    const int32_t* slot = (const int32_t*)(blk + A.off_seg_slot) + s0[0];
+    const int32_t* term_row = (const int32_t*)(blk + A.off_term_row) + ((const int32_t*)(blk + A.off_ray_terms))[rid[0]];
+    const int crossed = ((const int32_t*)(blk + A.off_ray_crossed))[rid[0]];
+    // row `row` of ray i: stored by the layer's first segment, added to afterwards (`store` is uniform over the workgroup)
+    auto put = [&](int i, long long row, int p, double v, bool store) {
+        double* o = A.jac + (row0[i] + row) * A.n + (j + p);
+        *o = store ? v : *o + v;
+    };
+    auto walk = [&](auto fast_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        // forward: K5e's walk, and the running maximum
+        vec cur = ns > 0 ? load_points<NP>(A.abs_coef[lay[0]], j) : (vec)(0.0);
+        for (int s = 0; s < ns; ++s) {
+            const vec nxt = s + 1 < ns ? load_points<NP>(A.abs_coef[lay[s + 1]], j) : cur;
+            double len[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            transport_step<FAST, NP>(nu, pa_n, A.pbkT[lay[s]], cur, [&](int p, double kp, double B) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    I[i][p] = fold_update<FAST>(exp_neg_budget(kp * len[i]), I[i][p], B);
+                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
+                }
+            });
+            cur = nxt;
+        }
+        // the radiance; then I becomes D = -I_final and A = 1
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                if (active && A.radiance) A.radiance[(long long)rid[i] * A.n + j + p] = I[i][p];
+                I[i][p] = -I[i][p];
+                Ak[i][p] = 1.0;
+            }
+        }
+        // backward
+        cur = ns > 0 ? load_points<NP>(A.abs_coef[lay[ns - 1]], j) : (vec)(0.0);
+        for (int s = ns - 1; s >= 0; --s) {
+            const vec nxt = s > 0 ? load_points<NP>(A.abs_coef[lay[s - 1]], j) : cur;
+            const int l = lay[s];
+            const bool store = (slot[s] & kRayRowStore) != 0;
+            const long long row_tau = 1 + (slot[s] & (kRayRowStore - 1));
+            const long long row_T = row_tau + crossed;
+            const double pbkT = A.pbkT[l], rT = A.rT[l];
+            double len[RB], g[RB][NP];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            double E0 = 0.0;
+            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double dB;
+                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double tau = cur[p] * len[i];
+                    const double tr = exp_neg_budget(tau);
+                    const double At = Ak[i][p] * tr;
+                    g[i][p] = fmin(fmax(Ak[i][p] * B + I[i][p], -(At * Imax[i][p])), At * B);
+                    const double a1 = Ak[i][p] * (1.0 - tr);
+                    if (active) {
+                        put(i, row_tau, p, tau * g[i][p], store);
+                        put(i, row_T, p, a1 * dB, store);
+                    }
+                    I[i][p] = I[i][p] + a1 * B;              // D_(s-1) = D_s + A_s (1 - t_s) B_s
+                    Ak[i][p] = At;                           // A_(s-1) = A_s t_s
+                }
+            }
+            if constexpr (TERMS) for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
+                const vec km = load_points<NP>(A.term_k[t], j);
+                const long long row = term_row[t];
+                if (active) {
+#pragma unroll
+                    for (int i = 0; i < RB; ++i) {
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) put(i, row, p, (km[p] * len[i]) * g[i][p], store);
+                    }
+                }
+            }
+            cur = nxt;
+        }
+        // dI/dT_source = A dB(nu, source_T)/dT for a ray from the surface at source_T, else 0
+        if (active) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double dBs = 0.0;
+                if (!A.I_surface) fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
+#pragma unroll
+                for (int i = 0; i < RB; ++i) put(i, 0, p, surface[i] && !A.I_surface ? Ak[i][p] * dBs : 0.0, true);
+            }
+        }
+    };
+    if constexpr (NP > 1) {
+        if (fast) walk(std::true_type{});
+        else walk(std::false_type{});
+    } else {
+        walk(std::false_type{});
+    }
+}
+
 // ----------------------------------------------------------------------------------------
 // K7: line survey (pyradClasses.py:409-428): S added into the bin of each line, in line order
 // ----------------------------------------------------------------------------------------
@@ -4377,6 +4526,30 @@ void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_b
     }
     if (nt > 0)
         hipLaunchKernelGGL((ray_radiance_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+}
+
+// K5f: launch_ray_radiance's split of the points and of the rays (the radiance is K5e's bit for bit only on K5e's own groups
+// of 4 points: the one-exp Planck path starts from the thread's first point).  4 points per thread hold 3 doubles per ray
+// and point, 48 for a bundle, without scratch (DESIGN.md "K5f"); a call without terms takes the bundle kernel without the
+// term loop.
+void launch_ray_jacobian(const RayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms, hipStream_t s) {
+    constexpr int NP = 4;
+    if (n <= 0 || n_rays <= 0) return;
+    const long long q1 = n & ~(long long)(NP - 1);
+    const long long nt = n - q1;
+    const int n_single = n_rays - kRayBundle * n_bundles;
+    if (q1 > 0) {
+        const dim3 grid((unsigned)((q1 / NP + 255) / 256), n_bundles);
+        if (n_bundles > 0 && n_terms > 0)
+            hipLaunchKernelGGL((ray_jacobian_kernel<NP, kRayBundle, true>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL, 0);
+        else if (n_bundles > 0)
+            hipLaunchKernelGGL((ray_jacobian_kernel<NP, kRayBundle, false>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL, 0);
+        if (n_single > 0)
+            hipLaunchKernelGGL((ray_jacobian_kernel<NP, 1, true>), dim3(grid.x, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL,
+                               0LL, kRayBundle * n_bundles);
+    }
+    if (nt > 0)
+        hipLaunchKernelGGL((ray_jacobian_kernel<1, 1, true>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
 }
 
 void launch_line_survey(const double* nu, const double* sw, int n_lines, double range_min, double resolution,

@@ -1877,6 +1877,42 @@ class PathRadiance:
             len(self.paths), self.wavenumber.size, self.transmittance is not None)
 
 
+class PathJacobians:
+    """What Atmosphere.pathJacobians returns, for R paths through L layers.  X is the grid (n points) or, with an instrument,
+    its channels (C).  ``wavenumber``: (X,) the grid or the channel centres; ``radiance``: (R, X), Atmosphere.radiance's;
+    ``opticalDepth``: (R, L, X) dI/d ln tau_l; ``temperature``: (R, L, X) dI/dT_l, Planck part; ``surfaceTemperature``: (R, X)
+    dI/dT_s, 0 for paths from space, None when a surface spectrum was given; ``molecules``: one (R, M_l, X) array per layer,
+    aligned with list(layer), dI/d ln n of every molecule at fixed line shapes (None when not asked for); ``moleculeNames``:
+    their names; ``temperatureAbsorption``: (R, L, X) the absorption part of dI/dT_l through dk_l/dT and ``temperatureFull``
+    = temperature + temperatureAbsorption, both None unless temperature="full" was asked for; ``paths``: the paths, in
+    order.  Layers a path does not cross hold exact zeros.  With an instrument also ``brightnessTemperature`` (R, C), the
+    inverse Planck of the channel radiance at the centre, and ``brightnessTemperatureJacobian`` (R, L, C) = temperature /
+    (dB/dT at the centre and the channel's brightness temperature), as Observation forms it; else both None."""
+
+    def __init__(self, wavenumber, radiance, temperature, opticalDepth, surfaceTemperature, molecules, moleculeNames, paths,
+                 temperatureAbsorption=None, channels=False):
+        self.wavenumber = wavenumber
+        self.radiance = radiance
+        self.temperature = temperature
+        self.opticalDepth = opticalDepth
+        self.surfaceTemperature = surfaceTemperature
+        self.molecules = molecules
+        self.moleculeNames = moleculeNames
+        self.temperatureAbsorption = temperatureAbsorption
+        self.temperatureFull = None if temperatureAbsorption is None else temperature + temperatureAbsorption
+        self.paths = paths
+        self.brightnessTemperature = self.brightnessTemperatureJacobian = None
+        if channels:
+            self.brightnessTemperature = brightnessTemperature(wavenumber, radiance)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                self.brightnessTemperatureJacobian = temperature / _planck_dT(wavenumber, self.brightnessTemperature)[:, None, :]
+
+    def __repr__(self):
+        return "PathJacobians(paths=%d, layers=%d, points=%d, molecules=%s, full=%s)" % (
+            len(self.paths), self.temperature.shape[1], self.wavenumber.size, self.molecules is not None,
+            self.temperatureAbsorption is not None)
+
+
 class Observation:
     """What Atmosphere.observe returns.  ``wavenumber``: the channel centres, (C,); ``radiance``: channel radiance in the
     units of transmission(); ``brightnessTemperature``: its inverse Planck at the centre, K; ``mu``: the viewing cosine.
@@ -2251,18 +2287,9 @@ class Atmosphere(list):
         return Path(lay, [half[l] for l in above] + [2.0 * half[m]] + [half[l] for l in above[::-1]], "space",
                     "limb zt=%g" % zt)
 
-    def radiance(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, transmittance=False):
-        """The radiance arriving along ``paths`` - one Path or a list of up to 512 - through this column (beyond the
-        reference).  Layers, grid and units as transmission() has them.  For every path and grid point nu_j:
-            I = surfaceSpectrum[j] or B(nu_j, surfaceTemperature) for source "surface", 0 for "space";  Ttot = 1
-            per segment (layer l, length s), in order:   t = exp(-k_l(nu_j) s)   I <- t I + (1 - t) B(nu_j, T_l)   Ttot <- Ttot t
-        A surface source is needed only if some path starts at the surface.  ``transmittance``: also return Ttot.
-        ``instrument``: an Instrument - the rows are convolved onto its channels on the device, as observe() does, and
-        only channel values come down (with transmittance twice the paths must fit the 512 rows of one convolution).
-        radiance(nadirPath()) is transmission() bit for bit wherever fluxes() documents that identity, and with an
-        instrument observe(instrument).radiance.  One kernel call (lbl_ray_radiance_dev) for all paths; a path's result does
-        not depend on the others.  The absorption coefficients are the resident ones: after transmission() nothing is
-        accumulated again.  Returns a PathRadiance.  Everything is validated (ValueError) before the device is touched."""
+    def _path_checks(self, paths, surfaceTemperature, surfaceSpectrum):
+        """The checks radiance() and pathJacobians() share, before the device is touched: (the paths as a list, layers,
+        n, surfaceSpectrum as n float64 values or None)."""
         plist = [paths] if isinstance(paths, Path) else list(paths) if isinstance(paths, (list, tuple)) else None
         if not plist or not all(isinstance(p, Path) for p in plist):
             raise ValueError("paths: a Path or a non-empty list of them, not %r" % (paths,))
@@ -2281,7 +2308,22 @@ class Atmosphere(list):
                 raise ValueError("a path starts at the surface: give surfaceSpectrum or surfaceTemperature")
             if surfaceSpectrum is None and not float(surfaceTemperature) > 0:
                 raise ValueError("surfaceTemperature must be > 0")
-        surfaceSpectrum = _grid_spectrum("surfaceSpectrum", surfaceSpectrum, n)
+        return plist, layers, n, _grid_spectrum("surfaceSpectrum", surfaceSpectrum, n)
+
+    def radiance(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, transmittance=False):
+        """The radiance arriving along ``paths`` - one Path or a list of up to 512 - through this column (beyond the
+        reference).  Layers, grid and units as transmission() has them.  For every path and grid point nu_j:
+            I = surfaceSpectrum[j] or B(nu_j, surfaceTemperature) for source "surface", 0 for "space";  Ttot = 1
+            per segment (layer l, length s), in order:   t = exp(-k_l(nu_j) s)   I <- t I + (1 - t) B(nu_j, T_l)   Ttot <- Ttot t
+        A surface source is needed only if some path starts at the surface.  ``transmittance``: also return Ttot.
+        ``instrument``: an Instrument - the rows are convolved onto its channels on the device, as observe() does, and
+        only channel values come down (with transmittance twice the paths must fit the 512 rows of one convolution).
+        radiance(nadirPath()) is transmission() bit for bit wherever fluxes() documents that identity, and with an
+        instrument observe(instrument).radiance.  One kernel call (lbl_ray_radiance_dev) for all paths; a path's result does
+        not depend on the others.  The absorption coefficients are the resident ones: after transmission() nothing is
+        accumulated again.  Returns a PathRadiance.  Everything is validated (ValueError) before the device is touched."""
+        plist, layers, n, surfaceSpectrum = self._path_checks(paths, surfaceTemperature, surfaceSpectrum)
+        R, nl = len(plist), len(layers)
         first = layers[0]
         n_rows = 2 * R if transmittance else R
         support = None
@@ -2316,6 +2358,133 @@ class Atmosphere(list):
         _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, rows, out)
         v = out.download(n_rows * C).reshape(n_rows, C)
         return PathRadiance(instrument.centres.copy(), v[:R].copy(), v[R:].copy() if transmittance else None, plist)
+
+    def pathJacobians(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, molecules=False,
+                      temperature="planck"):
+        """The weighting functions of radiance(): analytic derivatives of the radiance arriving along ``paths`` - one Path or
+        a list of up to 512 - per path and grid point (beyond the reference), in one pass over the resident absorption
+        coefficients per chunk of paths.  Paths, sources, layers, grid and units as radiance() has them.  For a path with
+        the segments s (layer l_s, length x_s), I_s the radiance entering segment s, t_s = exp(-k_l(nu_j) x_s) and A_s the
+        product of t_i over the segments after s:
+            dI/d ln tau_l       = sum over the path's segments in layer l of k_l x_s A_s t_s (B_l - I_s)
+            dI/d ln n_(m,l)     = the same sum with k_(m,l), molecule m's own absorption coefficient (fixed line shapes)
+            dI/dT_l (Planck)    = sum over the same segments of A_s (1 - t_s) dB_l/dT
+            dI/dT_l (absorption)= the same sum as dI/d ln tau_l with dk_l/dT for k_l         temperature="full" only
+            dI/dT_s             = (product of all t_s) dB(nu_j, T_s)/dT       paths from a surface at surfaceTemperature
+        as jacobians() defines the same quantities for the flux.  ``molecules``: also the molecule terms (jacobians()'s,
+        kept with the atmosphere).  ``temperature``: "planck" or "full", as in jacobians() (the Voigt line shape only).
+        ``instrument``: an Instrument - every row is convolved onto its channels on the device, as observe() does, and only
+        channel values come down.  Returns a PathJacobians; its radiance is radiance()'s bit for bit.  A path's result does
+        not depend on the others.  Chunks: as many whole paths, in order, as keep the rows of one kernel call
+        (lbl_ray_jacobian_dev: 1 + 2 crossed layers + terms in crossed layers, per path) at or below the 512 rows of one
+        convolution, one path at least, so the device work space never exceeds max(512, one path's rows) x n doubles
+        whatever the number of paths.  The absorption coefficients are the resident ones: after transmission() nothing is
+        accumulated again.  No other result of the model changes.  Everything is validated (ValueError) before the device
+        is touched."""
+        if temperature not in ("planck", "full"):
+            raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
+        plist, layers, n, surfaceSpectrum = self._path_checks(paths, surfaceTemperature, surfaceSpectrum)
+        R, nl = len(plist), len(layers)
+        first = layers[0]
+        full = temperature == "full"
+        names = [[m.name for m in L] for L in layers]
+        n_mol_terms = sum(len(L) for L in layers) if molecules else 0
+        n_terms = n_mol_terms + (nl if full else 0)
+        if n_terms > nat.limit("jacobian_terms"):
+            raise ValueError(("molecules: %d molecule and dk/dT terms, at most %d (molecules=False skips the molecule terms)" if full
+                              else "molecules: %d molecule terms, at most %d (molecules=False skips them)")
+                             % (n_terms, nat.limit("jacobian_terms")))
+        if full:
+            for L in layers:
+                L._check_abs_coef_dT()
+        support = None
+        if instrument is not None:
+            if not isinstance(instrument, Instrument):
+                raise ValueError("instrument: an Instrument, not %r" % (instrument,))
+            support = instrument.support(first.rangeMin, first.rangeMax, n)
+        # the terms' layers (molecules layer by layer as _jacobian_terms lists them, then dk_l/dT), and every path's rows
+        term_layer = ([l for l, L in enumerate(layers) for _ in L] if molecules else []) + (list(range(nl)) if full else [])
+        crossed = [sorted(set(p.layers)) for p in plist]
+        ray_terms = [[t for t, l in enumerate(term_layer) if l in set(c)] for c in crossed]
+        ray_rows = [1 + 2 * len(c) + len(t) for c, t in zip(crossed, ray_terms)]
+        block = nat.limit("ils_rows")
+        chunks, r = [], 0
+        while r < R:
+            e, rows = r + 1, ray_rows[r]
+            while e < R and rows + ray_rows[e] <= block:
+                rows += ray_rows[e]
+                e += 1
+            chunks.append((r, e, rows))
+            r = e
+        ctx = _ctx()
+        if ctx.option("sweep_ieee_divisions"):
+            raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
+        kbufs, plan = self._column_abs_coef(ctx, layers, n)
+        term_bufs = self._jacobian_terms(ctx, layers, n, plan)[0] if molecules else []
+        if full:                 # dk_l/dT as one more term of layer l, as jacobians() passes it
+            term_bufs = term_bufs + [L._abs_coef_dT()[0] for L in layers]
+        I_source = None
+        if surfaceSpectrum is not None:
+            I_source = _kept_state(self, "_path_source").reserve(ctx, n).buf(ctx, "I_source").upload(surfaceSpectrum)
+        jac = _kept_state(self, "_path_jacobian_rows").reserve(ctx, max(c[2] for c in chunks) * n).buf(ctx, "jac")
+        rad = _kept_state(self, "_path_jacobian_radiance").reserve(ctx, max(e - r for r, e, _ in chunks) * n).buf(ctx, "radiance")
+        X = n if instrument is None else len(instrument)
+        total = sum(ray_rows)
+        if instrument is not None:
+            cst = _kept_state(self, "_path_jacobian_block").reserve(ctx, block * X)
+            out = _kept_state(self, "_path_jacobian_out").reserve(ctx, (R + total) * X).buf(ctx, "out")
+        I = np.empty((R, X))
+        J = np.empty((total, X))
+        T, kinds = [L.T for L in layers], [Path.SOURCES.index(p.source) for p in plist]
+        row0 = 0
+        for r, e, rows in chunks:
+            sub = plist[r:e]
+            ctx.ray_jacobian_dev(kbufs, T, first.rangeMin, first.rangeMax, n, np.cumsum([0] + [len(p) for p in sub]),
+                                 [l for p in sub for l in p.layers], [x for p in sub for x in p.lengths], kinds[r:e], jac,
+                                 I_source=I_source, source_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs,
+                                 term_layer=term_layer, radiance=rad)
+            if instrument is None:
+                I[r:e] = rad.download((e - r) * n).reshape(e - r, n)
+                J[row0:row0 + rows] = jac.download(rows * n).reshape(rows, n)
+            else:          # the radiances, then the rows in blocks of one convolution, gathered behind one another in `out`
+                todo = [(rad, i * n, r + i) for i in range(e - r)] + [(jac, i * n, R + row0 + i) for i in range(rows)]
+                for b in range(0, len(todo), block):
+                    part = todo[b:b + block]
+                    _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, [(buf, o) for buf, o, _ in part],
+                                  cst.buf(ctx, "block"))
+                    at = 0
+                    while at < len(part):          # (runs of consecutive output rows: one copy each)
+                        end = at + 1
+                        while end < len(part) and part[end][2] == part[end - 1][2] + 1:
+                            end += 1
+                        out.stage_from_dev(cst.buf(ctx, "block"), at * X, (end - at) * X, dst_offset=part[at][2] * X)
+                        at = end
+            row0 += rows
+        if instrument is not None:
+            v = out.download((R + total) * X).reshape(R + total, X)
+            I, J = v[:R].copy(), v[R:]
+        # rows -> (R, L, X) arrays: zeros where a path does not cross a layer
+        dtau, dT = np.zeros((R, nl, X)), np.zeros((R, nl, X))
+        dTs = np.zeros((R, X))
+        terms = np.zeros((R, n_terms, X))
+        row0 = 0
+        for r in range(R):
+            c = len(crossed[r])
+            dTs[r] = J[row0]
+            dtau[r, crossed[r]] = J[row0 + 1:row0 + 1 + c]
+            dT[r, crossed[r]] = J[row0 + 1 + c:row0 + 1 + 2 * c]
+            terms[r, ray_terms[r]] = J[row0 + 1 + 2 * c:row0 + ray_rows[r]]
+            row0 += ray_rows[r]
+        mol = None
+        if molecules:
+            mol, o = [], 0
+            for L in layers:
+                mol.append(terms[:, o:o + len(L)].copy())
+                o += len(L)
+        return PathJacobians(first.xAxis if instrument is None else instrument.centres.copy(), I, dT, dtau,
+                             dTs if surfaceSpectrum is None else None, mol, names, plist,
+                             temperatureAbsorption=terms[:, n_mol_terms:].copy() if full else None,
+                             channels=instrument is not None)
 
     def kDistribution(self, bands=None, g=16, reference=None, planck=False, spectra=False):
         """k-distributions of the column's bands (beyond the reference): every layer's absorption coefficient (getAbsCoef)
