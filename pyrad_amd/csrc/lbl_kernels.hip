@@ -1206,12 +1206,27 @@ __device__ __forceinline__ void series_terms(double al, double bp, double& qa, d
     }
 }
 
+// A far line's Gaussian part that still reaches the span.  At 1 atm and 0.001 cm^-1 that is no rare case: a pseudo-Voigt
+// profile is a = 50-100 points wide and K1's cut-off dgi 290-580 points, while the far class begins 384 points from the
+// span's edge - a merged 100-2500 cm^-1 span has 20 such records (median 14, at most 78) beside the 136 of its near walk.
+// The four-point pass of chunk_extras costs them 51 wave-instructions each (two exp per four points) where the transposed
+// runs of the near walk cost 142 per eight records.  So on the production shape (GROUTE: unsplit spans, one wave walks all
+// of a span's records) a far record nearer than FF_GAUSS_CAP half-spans is only NOTED here - [g_lo, g_hi) grows to hold
+// it - and the near walk, which forms the same predicate per record, is extended over that range: records are sorted by
+// centre, so the noted ones and everything between them and the near lines are one index interval, and every (record, span)
+// pair is still evaluated exactly once with the same cut-off.  The cap bounds what the near walk may have to stage beyond its
+// own range (2 x 4 half-spans of records); 8 holds the whole class of a 1 atm cell (largest reach 582 + 128 points < 1,024).
+// A record beyond the cap (several atmospheres, finer grids) keeps the four-point pass here.
+constexpr int FF_GAUSS_CAP = 8;
+
 // Series coefficients of the far lines m0, m0+stride*k.. (chunks of 64, one line per lane) below m1.
-template <int R, int NT>
+template <int R, int NT, bool GROUTE = false>
 __device__ __forceinline__ void far_field_lines(const HotRec* hot, const ColdRec* cold, int m0, int m1, int stride,
                                                 double xc, int wlo, int whi, double x0, double Hf, double* lh, double* lc,
-                                                int lane, double (&C)[NT], WaveAcc<R>& S, int gx_lo = 0, int gx_hi = 0) {
-    // records [gx_lo, gx_hi): their Gaussian parts belong to the near walk (lines between FF_MID and FF_FAR half-spans)
+                                                int lane, double (&C)[NT], WaveAcc<R>& S, int& g_lo, int& g_hi) {
+    // (the records of a call are all far lines: with the series from FF_MID on, the lines between FF_MID and FF_FAR
+    // half-spans are among them - inside the cap, so on the only shape that has them their Gaussian parts go to the near walk)
+    static_assert(GROUTE || NT != FF_NT_MID, "the mid class needs the near walk to take its Gaussian parts");
     typedef double v2f64 __attribute__((ext_vector_type(2)));
     typedef const v2f64 __attribute__((address_space(1)))* GlobalF64x2;
     const GlobalF64x2 gh = (GlobalF64x2)(unsigned long long)hot;
@@ -1231,9 +1246,20 @@ __device__ __forceinline__ void far_field_lines(const HotRec* hot, const ColdRec
         }
         const int ci = (int)w0.x;
         const int dgi = __double2loint(w1.y), fl = __double2hiint(w1.y);
-        const bool gauss = valid && max(0, max(ci - whi, wlo - ci)) < dgi && !(c0 + lane >= gx_lo && c0 + lane < gx_hi);
-        const unsigned long long gmask = __ballot(gauss);
-        if (gmask) {                                   // rare: a far line with a Gaussian part that reaches the span
+        bool gauss = valid && max(0, max(ci - whi, wlo - ci)) < dgi;
+        unsigned long long gmask = __ballot(gauss);
+        if (GROUTE && gmask) {                         // (a chunk without such a record - most of them - pays the one ballot)
+            // inside the cap: 2 |c - xc| < 2 * FF_GAUSS_CAP half-spans, in integers as dmin2 below (the left side is odd: no tie)
+            const bool routed = abs(2 * (ci - wlo) - (64 * R - 1)) < 2 * FF_GAUSS_CAP * 32 * R;
+            const unsigned long long rmask = __ballot(gauss && routed);      // wave-uniform, like c0: scalar registers
+            if (rmask) {
+                g_lo = min(g_lo, c0 + (int)__builtin_ctzll(rmask));
+                g_hi = max(g_hi, c0 + 64 - (int)__builtin_clzll(rmask));
+            }
+            gauss = gauss && !routed;
+            gmask &= ~rmask;
+        }
+        if (gmask) {                                   // (GROUTE: beyond the cap only - very wide profiles)
             const unsigned long long emask = __ballot((fl & REC_NO_RECUR) != 0);
             v2f64 c0v = {0, 0}, c1v = {0, 0};
             if (gauss) {
@@ -1778,6 +1804,7 @@ void xsec_accumulate_lds_kernel(const AccumJob* __restrict__ jobs, const int2* _
             if (odd || iB - iA > 64 * 64 || iD - iC > 64 * 64)
                 edge_rounds_masked<R>(J.hot, J.cold, iA, iB, iC, iD, wlo, whi, x0, Hf, lh, lc, lane, S, odd);
         }
+        int iG1 = iF1, iG2 = iF2;                  // the near walk's records (wave-uniform; wider than [iF1, iF2) on EDGE_SKEW only)
         if (any_far) {
             // the running fraction of the edge lines is folded in first: N = 0, D = 1 are then constants through the series
             // phase instead of 16 live registers beside its 60 of coefficients (28 instructions per span)
@@ -1786,9 +1813,11 @@ void xsec_accumulate_lds_kernel(const AccumJob* __restrict__ jobs, const int2* _
             double C[NTC];
 #pragma unroll
             for (int n = 0; n < NTC; ++n) C[n] = 0.0;
-            // (the Gaussian parts of the records [iF1, iF2) belong to the near walk below)
-            far_field_lines<R, NTC>(J.hot, J.cold, iB + ((part + 1) % LS) * 64, iN1, 64 * LS, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, iF1, iF2);
-            far_field_lines<R, NTC>(J.hot, J.cold, iN2 + ((part + 2) % LS) * 64, iC, 64 * LS, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, iF1, iF2);
+            // (EDGE_SKEW: the Gaussian parts of the far records inside FF_GAUSS_CAP half-spans belong to the near walk below;
+            // the two calls widen [iG1, iG2) to hold them.  Line-split shapes keep them here: their waves are dealt whole far
+            // chunks and would have to agree on the range across a workgroup barrier this kernel does not have at this point.)
+            far_field_lines<R, NTC, EDGE_SKEW>(J.hot, J.cold, iB + ((part + 1) % LS) * 64, iN1, 64 * LS, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, iG1, iG2);
+            far_field_lines<R, NTC, EDGE_SKEW>(J.hot, J.cold, iN2 + ((part + 2) % LS) * 64, iC, 64 * LS, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, iG1, iG2);
             wave_sum_rows<NTC>(C, s_stage[wave], lane);
 #pragma unroll
             for (int k = 0; k < R; ++k) {
@@ -1808,7 +1837,8 @@ void xsec_accumulate_lds_kernel(const AccumJob* __restrict__ jobs, const int2* _
         for (int k = 0; k < GRUN; ++k) G[k] = 0.0;
         if (LBL_ABLATE(J, 512)) {                                            // (512: near lines dropped)
         } else if (edges_done) {
-            accumulate_lines<R, 1, GRUN>(J.hot, J.cold, iF1, iF2, iB, iC, wlo, whi, x0, Hf, lh, lc, lane, S, G, 64, LS, part, iN1, iN2);
+            // (Lorentz terms for [iN1, iN2), Gaussian runs for every record of [iG1, iG2) whose part reaches the span)
+            accumulate_lines<R, 1, GRUN>(J.hot, J.cold, iG1, iG2, iB, iC, wlo, whi, x0, Hf, lh, lc, lane, S, G, 64, LS, part, iN1, iN2);
         } else {
             accumulate_lines<R, 1, GRUN>(J.hot, J.cold, iA, any_far ? iB : iD, iB, iC, wlo, whi, x0, Hf, lh, lc, lane, S, G, 64, LS, part);
             if (any_far) {
