@@ -508,6 +508,66 @@ int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef
                          lbl_buffer* I_source, double source_T,
                          lbl_buffer* radiance, lbl_buffer* transmittance /* may be NULL */);
 
+/* ---- reflecting surface (beyond the reference; ABI 5, backward compatible) --------------------------------------------
+ * pyrad_amd.model.Atmosphere.fluxes and radiance with ``emissivity``: the lower boundary is a surface of emissivity e(nu) that
+ * emits e Is and reflects (1 - e) of what comes down, instead of the black surface of lbl_column_flux_dev and
+ * lbl_ray_radiance_dev.  e = emissivity[j] (n points; may be NULL) or emissivity_all at every point.  The values inside an
+ * emissivity buffer are not read on the host: a value outside [0, 1] gives the arithmetic result of the expressions below.
+ *
+ * lbl_column_flux_surface_dev: the arguments, grid, layers, levels, angles, bands, nan_to_num, partial sums and level_flux
+ * layout of lbl_column_flux_dev, and at grid point nu_j, for every angle k:
+ *   down:   exactly lbl_column_flux_dev's downward walk (I_down[L] = I_top[j] or 0), run FIRST
+ *   D_k   = I_down[0] of angle k                     F0 = sum_k W_k D_k   (angle 0 first, as every spectral flux)
+ *   R_k   = reflection == 0 ? F0 / Wsum : D_k        0 Lambertian, 1 specular; Wsum = W_0 + W_1 + ... added in angle order
+ *   Is    = I_surface[j] or B(nu_j, surface_T)
+ *   I_up[0] of angle k = e * Is + (1 - e) * R_k      (every operation rounded: two products, one difference, one sum)
+ *   up:     exactly lbl_column_flux_dev's upward walk from there
+ * up_surface (may be NULL; n points) receives F_up at level 0, in the layout of up_top / down_surface.
+ * Dividing by Wsum - pi for Gauss-Legendre angles on mu in [0, 1], anything for an explicit angle set - makes the reflected
+ * upward flux sum_k W_k (1 - e) R_k = (1 - e) F0 under the quadrature itself: the Lambertian surface conserves energy in the
+ * discrete scheme whatever the angle set.
+ * Identity: with e == 1 at every point and finite downward radiances at the surface, level_flux, up_top and down_surface are
+ * lbl_column_flux_dev's bit for bit (1 * Is + 0 * R == Is, and every level's sum receives the same terms in the same order).
+ * Emissivity 1 is not a special case of the code.
+ * LBL_ERR_BAD_ARG: everything lbl_column_flux_dev refuses; reflection not 0 or 1; emissivity NULL with emissivity_all outside
+ * [0, 1] or NaN; an emissivity or up_surface buffer shorter than n; weights whose sum is not finite and > 0;
+ * "sweep_ieee_divisions" 1.  Everything is checked before anything is enqueued.  Stream-ordered; nothing is synchronised.
+ *
+ * lbl_ray_radiance_surface_dev: the arguments and semantics of lbl_ray_radiance_dev, and two things more:
+ *   - seg_layer[s] == -1 is a surface marker, not a layer: the ray meets the surface there and is reflected specularly.  Its
+ *     seg_length must be 0.  With Is = I_source[j] or B(nu_j, source_T):
+ *         I <- e * Is + (1 - e) * I          Ttot <- Ttot * (1 - e)
+ *     Any number of markers, anywhere: first, last, adjacent.  A ray of one marker alone returns e Is from cold space.
+ *   - a ray that starts at the surface (source_kind 1) starts with I = e * Is + (1 - e) * Rd, Rd = surface_down[j] /
+ *     surface_down_norm where surface_down (may be NULL; n points: a hemispheric downward flux at the surface, for example
+ *     lbl_column_flux_dev's down_surface, and surface_down_norm the Wsum it was formed with) is given, else 0: the diffuse
+ *     (Lambertian) reflection of the downwelling.  Ttot starts at 1 as before.
+ * Identities: rays without markers, with e == 1 and without surface_down, return lbl_ray_radiance_dev's bits.  The ray down
+ * through the layers L-1 .. 0 over depth_l, a marker, and up through 0 .. L-1 returns lbl_column_flux_surface_dev's up_top for
+ * reflection 1 and the angle set {(1, 1.0)}, bit for bit.  A ray's bits do not depend on the other rays of the call.
+ * LBL_ERR_BAD_ARG: everything lbl_ray_radiance_dev refuses except a segment layer of -1; a marker whose length is not 0; a
+ * ray with a marker when neither I_source nor source_T > 0 is given; emissivity NULL with emissivity_all outside [0, 1] or NaN;
+ * an emissivity or surface_down buffer shorter than n; surface_down given with a norm that is not finite and > 0.  Everything
+ * is checked before anything is enqueued; the host arrays are copied and not retained.  Stream-ordered; nothing is
+ * synchronised.  (lbl_ray_radiance_dev and lbl_ray_jacobian_dev go on refusing a segment layer of -1.) */
+int lbl_column_flux_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T, const double* depth,
+                                double range_min, double range_max, int64_t n,
+                                lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                                int n_angles, const double* mu, const double* weight,
+                                int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                int reflection /* 0 Lambertian, 1 specular */,
+                                lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface,
+                                lbl_buffer* up_surface /* may be NULL */);
+int lbl_ray_radiance_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                 double range_min, double range_max, int64_t n,
+                                 int n_rays, const int32_t* ray_first,
+                                 const int32_t* seg_layer /* -1: surface marker */, const double* seg_length,
+                                 const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                                 lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                 lbl_buffer* surface_down /* may be NULL */, double surface_down_norm,
+                                 lbl_buffer* radiance, lbl_buffer* transmittance /* may be NULL */);
+
 /* ---- ray-path Jacobians (beyond the reference; ABI 5, backward compatible) --------------------------------------------
  * pyrad_amd.model.Atmosphere.pathJacobians: the weighting functions of the radiance lbl_ray_radiance_dev computes - its
  * analytic derivatives to every crossed layer's optical depth and (Planck) temperature, to the source temperature and to any

@@ -112,6 +112,12 @@ SIGNATURES = {
     "lbl_ray_radiance_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P, C.c_double,
                                        _P, _P]),
+    "lbl_column_flux_surface_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, _P,
+                                              C.c_double, _P, C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64), _P, C.c_double, C.c_int, _P, _P, _P, _P]),
+    "lbl_ray_radiance_surface_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P,
+                                               C.c_double, _P, C.c_double, _P, C.c_double, _P, _P]),
     "lbl_ray_jacobian_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lbl_ray_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
@@ -600,6 +606,27 @@ class Context:
                                weight, band_first, band_count),
             _hb(level_flux), _hb(up_top), _hb(down_surface)))
 
+    REFLECTIONS = ("lambertian", "specular")        # the C ABI's ``reflection`` is the index
+
+    @staticmethod
+    def _emissivity_args(emissivity):
+        """(buffer handle or None, emissivity_all) from a Buffer or a number"""
+        if isinstance(emissivity, Buffer):
+            return emissivity.h, 1.0
+        return None, float(emissivity)
+
+    def column_flux_surface_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
+                                level_flux, emissivity, reflection=0, I_surface=None, surface_T=0.0, I_top=None, up_top=None,
+                                down_surface=None, up_surface=None):
+        """Level fluxes over a reflecting surface (lbl_column_flux_surface_dev): column_flux_dev's arguments and results,
+        with ``emissivity`` a Buffer of n points or one number in [0, 1], ``reflection`` 0 (Lambertian) or 1 (specular), and
+        ``up_surface`` (optional, n points) the spectral upward flux at the surface."""
+        self.check(self.lib.lbl_column_flux_surface_dev(
+            *self._column_args(abs_coef, layer_T, depth, range_min, range_max, n, I_surface, surface_T, (_hb(I_top),), mu,
+                               weight, band_first, band_count),
+            *self._emissivity_args(emissivity), int(reflection), _hb(level_flux), _hb(up_top), _hb(down_surface),
+            _hb(up_surface)))
+
     def column_jacobian_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                             jac, I_surface=None, surface_T=0.0, term_abs_coef=(), term_layer=(), ln_tau_spectra=None,
                             T_spectra=None):
@@ -628,6 +655,27 @@ class Context:
             self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
             float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
             seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T), _hb(radiance),
+            _hb(transmittance)))
+
+    def ray_radiance_surface_dev(self, abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length,
+                                 source_kind, radiance, emissivity, I_source=None, source_T=0.0, surface_down=None,
+                                 surface_down_norm=0.0, transmittance=None):
+        """Radiance along ray paths that may meet a reflecting surface (lbl_ray_radiance_surface_dev): ray_radiance_dev's
+        arguments and results; a ``seg_layer`` of -1 (length 0) is where a ray is reflected specularly by the surface of
+        ``emissivity`` (a Buffer of n points or one number in [0, 1]); rays that start at the surface also carry the diffuse
+        reflection of ``surface_down`` (optional, n points: a downward flux formed with weights that add up to
+        ``surface_down_norm``)."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
+        seg_length = _as_f64(seg_length)
+        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length):
+            raise ValueError("ray_radiance_surface_dev: one ray_first per ray and one more, one length per segment layer")
+        self.check(self.lib.lbl_ray_radiance_surface_dev(
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
+            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
+            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
+            *self._emissivity_args(emissivity), _hb(surface_down), float(surface_down_norm), _hb(radiance),
             _hb(transmittance)))
 
     def ray_jacobian_dev(self, abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length, source_kind, jac,

@@ -1,6 +1,7 @@
 // Column transport (include/pyrad_hip.h, "level fluxes", "Jacobians" and "ray paths"): argument checking and the launch
-// sequences of lbl_column_flux_dev, lbl_column_jacobian_dev, lbl_ray_radiance_dev and lbl_ray_jacobian_dev.  The kernels are
-// K5c, K5d, K5e and K5f of lbl_kernels.hip; the context's internals
+// sequences of lbl_column_flux_dev, lbl_column_jacobian_dev, lbl_ray_radiance_dev and lbl_ray_jacobian_dev, and of their
+// variants over a reflecting surface, lbl_column_flux_surface_dev and lbl_ray_radiance_surface_dev.  The kernels are
+// K5c, K5d, K5e, K5f and K5g of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -104,11 +105,11 @@ static int check_column(lbl_ctx* ctx, const char* what, ColumnRT* a, int n_layer
 }
 
 // The launch sequence after every check: the argument block and the partial scratch for the widest band (`np` points per
-// thread, nv values per partial), the optional spectra spec[0..1] (spec_bytes each) zeroed, then the bands one after another
+// thread, nv values per partial), the optional spectra spec[0 .. NS) (spec_bytes each) zeroed, then the bands one after another
 // over one partial block: stream order keeps a band's final reduction ahead of the next band.  launch_band(d_args, partial,
 // b, s) enqueues band b.
-template <class Args, class LaunchBand>
-static int run_column(lbl_ctx* ctx, const Args* a, int np, int nv, int n_bands, const int64_t* band_count, double* const (&spec)[2],
+template <class Args, size_t NS, class LaunchBand>
+static int run_column(lbl_ctx* ctx, const Args* a, int np, int nv, int n_bands, const int64_t* band_count, double* const (&spec)[NS],
                       size_t spec_bytes, LaunchBand launch_band) {
     int64_t max_count = 0;
     for (int b = 0; b < n_bands; ++b) max_count = std::max(max_count, band_count[b]);
@@ -152,6 +153,57 @@ extern "C" int lbl_column_flux_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const
     return run_column(ctx, a, 4, nv, n_bands, band_count, {a->up_top, a->down_surface}, (size_t)n * sizeof(double),
                       [&](const FluxArgs* d, double* partial, int b, hipStream_t s) {
         launch_column_flux(d, n_layers, n_angles, band_first[b], band_count[b], partial, buffer_data(level_flux) + (size_t)b * nv, s);
+    });
+} LBL_GUARD_END(ctx)
+
+// The emissivity arguments of both surface entry points: a buffer of n points (its values are not read here) or one value
+// in [0, 1].
+static int check_emissivity(lbl_ctx* ctx, lbl_buffer* emissivity, double emissivity_all, int64_t n) {
+    int rc;
+    if ((rc = ctx_check_buffer(ctx, emissivity, n, "emissivity", false))) return rc;
+    if (!emissivity && !(emissivity_all >= 0.0 && emissivity_all <= 1.0))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "emissivity_all must lie in [0, 1]");
+    return LBL_OK;
+}
+
+extern "C" int lbl_column_flux_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                           const double* depth, double range_min, double range_max, int64_t n,
+                                           lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
+                                           const double* mu, const double* weight, int n_bands, const int64_t* band_first,
+                                           const int64_t* band_count, lbl_buffer* emissivity, double emissivity_all,
+                                           int reflection, lbl_buffer* level_flux, lbl_buffer* up_top,
+                                           lbl_buffer* down_surface, lbl_buffer* up_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(SurfaceFluxArgs), 0);
+    SurfaceFluxArgs* a = (SurfaceFluxArgs*)blk.data();
+    int rc;
+    if ((rc = check_column(ctx, "level fluxes", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
+                           surface_T, n_angles, mu, weight, n_bands, band_first, band_count)))
+        return rc;
+    const int nv = 2 * (n_layers + 1);
+    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
+    if (reflection != 0 && reflection != 1)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "reflection must be 0 (Lambertian) or 1 (specular)");
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    double w_sum = 0.0;
+    for (int k = 0; k < n_angles; ++k) w_sum += weight[k];
+    if (!(w_sum > 0.0) || !std::isfinite(w_sum))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "the weights must add up to a finite sum > 0");
+    a->I_top = I_top ? buffer_data(I_top) : nullptr;
+    a->up_top = up_top ? buffer_data(up_top) : nullptr;
+    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
+    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a->emissivity_all = emissivity_all;
+    a->w_sum = w_sum;
+    a->up_surface = up_surface ? buffer_data(up_surface) : nullptr;
+    a->reflection = reflection;
+    return run_column(ctx, a, 4, nv, n_bands, band_count, {a->up_top, a->down_surface, a->up_surface}, (size_t)n * sizeof(double),
+                      [&](const SurfaceFluxArgs* d, double* partial, int b, hipStream_t s) {
+        launch_surface_flux(d, n_layers, n_angles, band_first[b], band_count[b], partial, buffer_data(level_flux) + (size_t)b * nv, s);
     });
 } LBL_GUARD_END(ctx)
 
@@ -207,7 +259,10 @@ extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* c
 static size_t round8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 // What lbl_ray_radiance_dev, lbl_ray_jacobian_dev and lbl_ray_jacobian_rows (ctx NULL) check of the ray lists themselves.
-static int check_ray_lists(lbl_ctx* ctx, int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer) {
+// `markers`: a segment layer of kRaySurfaceMarker is no layer but the place where the ray meets the surface
+// (lbl_ray_radiance_surface_dev alone).
+static int check_ray_lists(lbl_ctx* ctx, int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
+                           bool markers) {
     if (n_layers < 1 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d layers", kMaxLayers);
     if (n_rays < 1 || n_rays > kMaxRayPaths) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d rays", kMaxRayPaths);
     if (!ray_first) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL ray list");
@@ -218,7 +273,7 @@ static int check_ray_lists(lbl_ctx* ctx, int n_layers, int n_rays, const int32_t
     if (n_seg > kMaxRaySegments) return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d segments", kMaxRaySegments);
     if (n_seg > 0 && !seg_layer) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL segment list");
     for (int s = 0; s < n_seg; ++s)
-        if (seg_layer[s] < 0 || seg_layer[s] >= n_layers)
+        if ((seg_layer[s] < 0 || seg_layer[s] >= n_layers) && !(markers && seg_layer[s] == kRaySurfaceMarker))
             return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: layer %d outside [0, %d)", s, (int)seg_layer[s], n_layers);
     return LBL_OK;
 }
@@ -226,10 +281,12 @@ static int check_ray_lists(lbl_ctx* ctx, int n_layers, int n_rays, const int32_t
 // Everything lbl_ray_radiance_dev and lbl_ray_jacobian_dev check of the arguments they share (ctx non-NULL), then the
 // RayArgs part of the argument block filled - the tables start `header` bytes into the block, *bytes is where they end -
 // and the dispatch order found.  `radiance` holds n_rays x n and may be NULL only where it is not `radiance_required`.
+// `markers`: surface markers are allowed among the segment layers (check_ray_lists); their length must be 0 and a ray with
+// one needs the surface source.
 static int check_rays(lbl_ctx* ctx, RayArgs* a, size_t header, int n_layers, lbl_buffer* const* abs_coef, const double* T,
                       double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
                       const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind, lbl_buffer* I_source,
-                      double source_T, lbl_buffer* radiance, bool radiance_required, lbl_buffer* transmittance,
+                      double source_T, lbl_buffer* radiance, bool radiance_required, lbl_buffer* transmittance, bool markers,
                       std::vector<int32_t>* order, size_t* bytes) {
     if (n_layers < 1 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d layers", kMaxLayers);
     if (n < 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "n must be >= 1");
@@ -237,7 +294,7 @@ static int check_rays(lbl_ctx* ctx, RayArgs* a, size_t header, int n_layers, lbl
     if (ctx_sweep_ieee(ctx))
         return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", "ray paths");
     int rc;
-    if ((rc = check_ray_lists(ctx, n_layers, n_rays, ray_first, seg_layer))) return rc;
+    if ((rc = check_ray_lists(ctx, n_layers, n_rays, ray_first, seg_layer, markers))) return rc;
     if (!source_kind) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL ray list");
     const int n_seg = ray_first[n_rays];
     if (n_seg > 0 && !seg_length) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL segment list");
@@ -245,6 +302,13 @@ static int check_rays(lbl_ctx* ctx, RayArgs* a, size_t header, int n_layers, lbl
         if (!(seg_length[s] >= 0) || !std::isfinite(seg_length[s]))
             return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: length must be finite and >= 0", s);
     if ((rc = ctx_check_buffer(ctx, I_source, n, "I_source", false))) return rc;
+    for (int r = 0; markers && r < n_rays; ++r)
+        for (int s = ray_first[r]; s < ray_first[r + 1]; ++s) {
+            if (seg_layer[s] != kRaySurfaceMarker) continue;
+            if (seg_length[s] != 0.0) return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: a surface marker has length 0", s);
+            if (!I_source && !(source_T > 0))
+                return column_fail(ctx, LBL_ERR_BAD_ARG, "ray %d: a ray that meets the surface needs I_source or source_T > 0", r);
+        }
     for (int r = 0; r < n_rays; ++r) {
         if (source_kind[r] != 0 && source_kind[r] != 1)
             return column_fail(ctx, LBL_ERR_BAD_ARG, "ray %d: source_kind must be 0 (space) or 1 (surface)", r);
@@ -329,7 +393,7 @@ extern "C" int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
     size_t bytes = 0;
     int rc;
     if ((rc = check_rays(ctx, &a, sizeof a, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
-                         seg_length, source_kind, I_source, source_T, radiance, true, transmittance, &order, &bytes)))
+                         seg_length, source_kind, I_source, source_T, radiance, true, transmittance, false, &order, &bytes)))
         return rc;
     std::vector<char> blk(bytes, 0);
     memcpy(blk.data(), (const void*)&a, sizeof a);
@@ -339,6 +403,43 @@ extern "C" int lbl_ray_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
     if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
     COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
     launch_ray_radiance((const RayArgs*)d_args, n, n_rays, a.n_bundles, ctx_stream(ctx));
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+} LBL_GUARD_END(ctx)
+
+extern "C" int lbl_ray_radiance_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                            double range_min, double range_max, int64_t n, int n_rays,
+                                            const int32_t* ray_first, const int32_t* seg_layer, const double* seg_length,
+                                            const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                                            lbl_buffer* emissivity, double emissivity_all, lbl_buffer* surface_down,
+                                            double surface_down_norm, lbl_buffer* radiance,
+                                            lbl_buffer* transmittance) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    // the argument block: header, then K5e's tables
+    RaySurfaceArgs a;
+    memset((void*)&a, 0, sizeof a);
+    std::vector<int32_t> order;
+    size_t bytes = 0;
+    int rc;
+    if ((rc = check_rays(ctx, &a, sizeof a, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
+                         seg_length, source_kind, I_source, source_T, radiance, true, transmittance, true, &order, &bytes)))
+        return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    if ((rc = ctx_check_buffer(ctx, surface_down, n, "surface_down", false))) return rc;
+    if (surface_down && (!(surface_down_norm > 0.0) || !std::isfinite(surface_down_norm)))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "surface_down_norm must be finite and > 0");
+    a.emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a.emissivity_all = emissivity_all;
+    a.surface_down = surface_down ? buffer_data(surface_down) : nullptr;
+    a.surface_down_norm = surface_down ? surface_down_norm : 1.0;
+    std::vector<char> blk(bytes, 0);
+    memcpy(blk.data(), (const void*)&a, sizeof a);
+    fill_ray_tables(blk.data(), a, n_rays, ray_first, seg_layer, seg_length, source_kind, order);
+
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    launch_ray_surface((const RaySurfaceArgs*)d_args, n, n_rays, a.n_bundles, ctx_stream(ctx));
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
 } LBL_GUARD_END(ctx)
@@ -404,7 +505,7 @@ extern "C" int lbl_ray_jacobian_rows(int n_layers, int n_rays, const int32_t* ra
                                      int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows) try {
     int rc;
     if (!rows) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "rows is NULL");
-    if ((rc = check_ray_lists(nullptr, n_layers, n_rays, ray_first, seg_layer))) return rc;
+    if ((rc = check_ray_lists(nullptr, n_layers, n_rays, ray_first, seg_layer, false))) return rc;
     if ((rc = check_ray_terms(nullptr, n_layers, n_terms, term_layer))) return rc;
     RayRows R;
     ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, &R);
@@ -426,7 +527,7 @@ extern "C" int lbl_ray_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
     size_t off = 0;
     int rc;
     if ((rc = check_rays(ctx, a, sizeof(RayJacArgs), n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first,
-                         seg_layer, seg_length, source_kind, I_source, source_T, radiance, false, nullptr, &order, &off)))
+                         seg_layer, seg_length, source_kind, I_source, source_T, radiance, false, nullptr, false, &order, &off)))
         return rc;
     if ((rc = check_ray_terms(ctx, n_layers, n_terms, term_layer))) return rc;
     if (n_terms > 0 && !term_abs_coef) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");

@@ -292,6 +292,28 @@ struct RayArgs : ColumnRT {
 };
 void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s);
 
+// Reflecting surface (K5g, lbl_column_transport.hip: lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev): K5c's two
+// walks in the other order - downward first, then upward from I_up[0] = e Is + (1 - e) R - and K5e's walk with surface
+// markers (a segment layer of kRaySurfaceMarker) and the diffuse term at a path's start at the surface.  The partials,
+// their count and the final reduction are K5c's; the ray tables and the dispatch order K5e's.
+constexpr int32_t kRaySurfaceMarker = -1;
+struct SurfaceFluxArgs : FluxArgs {
+    const double* emissivity;           // n points, or nullptr: emissivity_all
+    double emissivity_all;
+    double w_sum;                       // W_0 + W_1 + ..., added on the host in angle order (> 0 and finite)
+    double* up_surface;                 // optional: spectral flux F_up at the surface
+    int32_t reflection, pad;            // 0 Lambertian: R_k = F_down(0) / w_sum; 1 specular: R_k = I_down_k(0)
+};
+void launch_surface_flux(const SurfaceFluxArgs* d_args, int n_layers, int n_angles, long long first, long long count,
+                         double* partial, double* level_flux, hipStream_t s);
+struct RaySurfaceArgs : RayArgs {
+    const double* emissivity;           // n points, or nullptr: emissivity_all
+    double emissivity_all;
+    const double* surface_down;         // optional: hemispheric downward flux at the surface, n points
+    double surface_down_norm;           // ... and the sum of the weights it was formed with
+};
+void launch_ray_surface(const RaySurfaceArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s);
+
 // Ray-path Jacobians (K5f, lbl_column_transport.hip: lbl_ray_jacobian_dev): K5e's walk, then the segments last to first
 // with K5d's transmittance-and-emission recurrence, one output row per ray, kind and crossed layer.  RayArgs' block with
 // more tables behind it; `radiance` may be nullptr here and `transmittance` is not used.  A ray's rows start at row_first[r]:

@@ -20,6 +20,8 @@
 //                              (Atmosphere.radiance; beyond the reference)
 //   K5f ray_jacobian_kernel    K5e's walk + K5d's downward pass along the segments: weighting functions of the radiance
 //                              along a ray (Atmosphere.pathJacobians; beyond the reference)
+//   K5g surface_flux_kernel, ray_surface_kernel   K5c and K5e over a reflecting surface: emissivity, Lambertian or specular
+//                              reflection, rays that bounce (fluxes() and radiance() with an emissivity; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -3834,6 +3836,227 @@ __global__ __launch_bounds__(256) void ray_radiance_kernel(const RayArgs* __rest
     }
 }
 
+// ----------------------------------------------------------------------------------------
+// K5g: reflecting surface (lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev; the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// What leaves a surface of emissivity e that emits Is and reflects R: e Is + (1 - e) R, every operation rounded.  With
+// e == 1 it is Is bit for bit for every finite R (1 Is + 0 R), which is what makes both kernels below return K5c's and K5e's
+// bits over a black surface without a special case.
+__device__ __forceinline__ double surface_leaving(double e, double Is, double R) {
+#pragma clang fp contract(off)
+    const double emitted = e * Is;
+    const double reflected = (1.0 - e) * R;
+    return emitted + reflected;
+}
+
+// K5c's kernel with the walks in the other order: DOWNWARD first, so that the downward radiances at level 0 are in the
+// registers when the surface is met; they are turned in place into the upward ones - Lambertian: every angle gets
+// F_down(0) / w_sum, so that sum_k W_k (1 - e) R_k = (1 - e) F_down(0) under the quadrature whatever the angle set;
+// specular: each angle its own - and the upward walk starts from them.  The step, the level sums, the slots and the
+// partials are K5c's (each level slot receives the same terms in the same order), column_flux_final_kernel finishes.
+// The surface source Is is formed BEFORE the downward walk, where K5c forms it - with nothing else in the registers - and
+// waits in LDS, one slot per thread and point that only its thread touches: formed at the surface, between the walks with
+// every angle's radiance alive, the general Planck expression costs the seven-angle body 11 spilled registers at K5c's
+// three waves per SIMD.  So the surface adds no register that lives through a walk; e is read where it is used.
+// (the second launch bound: the waves per SIMD of K5c's instantiation for the same NP and NA - 4 with one angle, 3 up to
+// seven, 2 with eight; left to itself the seven-angle body takes 171 registers, 3 more than three waves allow)
+template <int NP, int NA> constexpr int surface_flux_waves() { return NP == 1 ? 1 : NA == 1 ? 4 : NA <= 7 ? 3 : 2; }
+template <int NP, int NA>
+__global__ __launch_bounds__(256, (surface_flux_waves<NP, NA>())) void surface_flux_kernel(const SurfaceFluxArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                           long long lo1, long long n1, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    constexpr int kSlot = 2 * (kMaxLayers + 1);
+    __shared__ double acc[4 * kSlot];            // [wave][up levels 0..L, down levels 0..L]
+    __shared__ double source[NP * 256];          // [point][thread]: Is, from before the downward walk to the surface
+    const SurfaceFluxArgs& A = *Ap;
+    const int L = A.n_layers;
+    const int nv = 2 * (L + 1);
+    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
+    __syncthreads();
+    double* my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const long long total = n0 + n1;
+    const long long stride = (long long)gridDim.x * blockDim.x * NP;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
+    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
+        const long long q = q0 + (long long)threadIdx.x * NP;
+        const bool active = q < total;
+        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        double nu[NP], pa_n[NP], I[NA][NP];
+        column_points<NP>(A, j, nu, pa_n);
+        const bool fast = fold_fast_path<NP>(A, nu, active);
+        // sum_k W_k I_k per point, nan_to_num, summed over the thread's points, the wave, and into the wave's slot
+        auto level = [&](int slot, double* spec, double* spec2 = nullptr) {
+            double s = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double f = angle_sum<NA>(A, [&](int k) { return I[k][p]; });
+                if (spec && active) spec[j + p] = f;
+                if (spec2 && active) spec2[j + p] = f;
+                s += active ? nan_to_num(f) : 0.0;
+            }
+            s = wave_sum(s);
+            if (lane0) my[slot] += s;
+        };
+        auto layer = [&](auto fast_tag, int l, vec v) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double depth = A.depth[l];
+            transport_step<FAST, NP>(nu, pa_n, A.pbkT[l], v, [&](int p, double kp, double B) {
+                const double tau = kp * depth;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) I[k][p] = fold_update<FAST>(exp_neg_budget(tau * A.rmu[k]), I[k][p], B);
+            });
+        };
+        auto walk = [&](auto fast_tag) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                source[p * 256 + threadIdx.x] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+            // downward: I_L = I_top or 0; level l after layer l
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double It = A.I_top ? A.I_top[j + p] : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) I[k][p] = It;
+            }
+            level(L + 1 + L, L == 0 ? A.down_surface : nullptr);
+            vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+                layer(fast_tag, l, cur);
+                level(L + 1 + l, l == 0 ? A.down_surface : nullptr);
+                cur = nxt;
+            }
+            // the surface: I_up[0] = e Is + (1 - e) R, in place
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+                const double Is = source[p * 256 + threadIdx.x];
+                const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : I[k][p]);
+            }
+            // upward: level l + 1 after layer l
+            level(0, A.up_surface, L == 0 ? A.up_top : nullptr);
+            cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+            for (int l = 0; l < L; ++l) {
+                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+                layer(fast_tag, l, cur);
+                level(l + 1, l + 1 == L ? A.up_top : nullptr);
+                cur = nxt;
+            }
+        };
+        if constexpr (NP > 1) {
+            if (fast) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += blockDim.x)
+        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+}
+
+// K5e's kernel with a surface in the path: a segment whose layer is kRaySurfaceMarker is no segment but the place where the
+// ray meets the surface and is reflected specularly (I <- e Is + (1 - e) I, Ttot <- Ttot (1 - e)), and a ray that starts at
+// the surface starts with e Is + (1 - e) Rd, Rd the diffuse reflection of surface_down (0 without it).  The rays of a bundle
+// share their layer sequence, markers included, so the branch on a marker is uniform over the workgroup; the prefetch of
+// k_l runs one real segment ahead, past the markers.  The operations of a real segment are K5e's.
+template <int NP, int RB>
+__global__ __launch_bounds__(256) void ray_surface_kernel(const RaySurfaceArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                          long long lo1, long long n1, int order_first) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    const RaySurfaceArgs& A = *Ap;
+    const char* blk = (const char*)Ap;
+    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
+    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
+    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
+    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
+    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
+    // (idle lanes of the last workgroup work on a valid point and store nothing)
+    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
+    const bool active = q < n0 + n1;
+    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    double nu[NP], pa_n[NP], Is[NP], em[NP], I[RB][NP], Tt[RB][NP];
+    column_points<NP>(A, j, nu, pa_n);
+    const bool fast = fold_fast_path<NP>(A, nu, active);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+        em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+    }
+    int rid[RB], s0[RB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
+        s0[i] = ray_first[rid[i]];
+        const bool surface = source_kind[rid[i]] == 1;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const double Rd = A.surface_down ? A.surface_down[j + p] / A.surface_down_norm : 0.0;
+            I[i][p] = surface ? surface_leaving(em[p], Is[p], Rd) : 0.0;
+            Tt[i][p] = 1.0;
+        }
+    }
+    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers)
+    const int32_t* lay = seg_layer + s0[0];
+    // the first real segment at or after s (ns: none)
+    auto real_from = [&](int s) {
+        while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
+        return s;
+    };
+    auto walk = [&](auto fast_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        int ahead = real_from(0);
+        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
+        for (int s = 0; s < ns; ++s) {
+            if (lay[s] == kRaySurfaceMarker) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        I[i][p] = surface_leaving(em[p], Is[p], I[i][p]);
+                        Tt[i][p] = Tt[i][p] * (1.0 - em[p]);
+                    }
+                }
+                continue;
+            }
+            ahead = real_from(s + 1);
+            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
+            double len[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            transport_step<FAST, NP>(nu, pa_n, A.pbkT[lay[s]], cur, [&](int p, double kp, double B) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double tr = exp_neg_budget(kp * len[i]);
+                    I[i][p] = fold_update<FAST>(tr, I[i][p], B);
+                    Tt[i][p] = Tt[i][p] * tr;
+                }
+            });
+            cur = nxt;
+        }
+    };
+    if constexpr (NP > 1) {
+        if (fast) walk(std::true_type{});
+        else walk(std::false_type{});
+    } else {
+        walk(std::false_type{});
+    }
+    if (!active) return;
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        const long long o = (long long)rid[i] * A.n + j;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            A.radiance[o + p] = I[i][p];
+            if (A.transmittance) A.transmittance[o + p] = Tt[i][p];
+        }
+    }
+}
+
 // K5d: K5c's upward fold, keeping per angle only the radiance I and its running maximum Imax over the levels; then a
 // downward pass that re-reads k_l and recomputes B_l as K5c's does, and keeps per angle the transmittance A to the top and
 // D = E - I_top, E the emission of the layers above that reaches the top.  Then
@@ -4523,6 +4746,16 @@ void launch_column_flux(const FluxArgs* d_args, int n_layers, int n_angles, long
     });
 }
 
+// K5g: K5c's launch for the kernel that meets a reflecting surface between its two walks
+void launch_surface_flux(const SurfaceFluxArgs* d_args, int n_layers, int n_angles, long long first, long long count,
+                         double* partial, double* level_flux, hipStream_t s) {
+    with_angles(n_angles, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        launch_column_band<4>(surface_flux_kernel<4, NA>, surface_flux_kernel<1, NA>, d_args, 2 * (n_layers + 1), first, count,
+                              partial, level_flux, s);
+    });
+}
+
 // K5d's points per thread, chosen per angle count so that no instantiation spills (DESIGN.md "K5d")
 template <int NA> constexpr int jacobian_np() { return NA <= 2 ? 4 : 2; }
 
@@ -4556,6 +4789,26 @@ void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_b
     }
     if (nt > 0)
         hipLaunchKernelGGL((ray_radiance_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+}
+
+// K5g: launch_ray_radiance's split of the points and of the rays for the kernel that knows surface markers
+void launch_ray_surface(const RaySurfaceArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s) {
+    constexpr int NP = 4;
+    if (n <= 0 || n_rays <= 0) return;
+    const long long q1 = n & ~(long long)(NP - 1);
+    const long long nt = n - q1;
+    const int n_single = n_rays - kRayBundle * n_bundles;
+    if (q1 > 0) {
+        const unsigned blocks = (unsigned)((q1 / NP + 255) / 256);
+        if (n_bundles > 0)
+            hipLaunchKernelGGL((ray_surface_kernel<NP, kRayBundle>), dim3(blocks, n_bundles), dim3(256), 0, s, d_args, 0LL, q1,
+                               0LL, 0LL, 0);
+        if (n_single > 0)
+            hipLaunchKernelGGL((ray_surface_kernel<NP, 1>), dim3(blocks, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL,
+                               kRayBundle * n_bundles);
+    }
+    if (nt > 0)
+        hipLaunchKernelGGL((ray_surface_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
 }
 
 // K5f: launch_ray_radiance's split of the points and of the rays (the radiance is K5e's bit for bit only on K5e's own groups

@@ -1400,6 +1400,57 @@ def _grid_spectrum(name, spec, n):
     return spec
 
 
+REFLECTIONS = ("lambertian", "specular")        # the C ABI's ``reflection`` is the index
+
+
+def _surface_emissivity(emissivity, x):
+    """The ``emissivity`` of fluxes() and radiance() on the grid ``x``: a float for a number, else len(x) contiguous float64
+    values - an array of that many values, or a pair (wavenumbers, values) interpolated with np.interp onto x (the end
+    values held beyond the table).  ValueError for anything else, a value outside [0, 1] or a NaN."""
+    n = len(x)
+    bad = "emissivity: a number in [0, 1], %d values on xAxis or a pair (wavenumbers, values), not %r"
+    if isinstance(emissivity, (bool, str)):
+        raise ValueError(bad % (n, emissivity))
+    if isinstance(emissivity, (int, float, np.integer, np.floating)):
+        e = float(emissivity)
+        if not 0.0 <= e <= 1.0:
+            raise ValueError("emissivity: %r is outside [0, 1]" % (emissivity,))
+        return e
+    table = isinstance(emissivity, (tuple, list)) and len(emissivity) == 2 and all(np.ndim(v) == 1 for v in emissivity)
+    try:
+        if table:
+            nu, val = (np.asarray(v, dtype=np.float64) for v in emissivity)
+        else:
+            e = np.ascontiguousarray(emissivity, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(bad % (n, emissivity))
+    if table:
+        if nu.size < 1 or nu.shape != val.shape or not np.all(np.isfinite(nu)) or np.any(np.diff(nu) <= 0):
+            raise ValueError("emissivity: a table needs as many values as wavenumbers, the wavenumbers finite and increasing")
+        e = np.ascontiguousarray(np.interp(x, nu, val))
+    elif e.shape != (n,):
+        raise ValueError("emissivity: %d grid points expected, got shape %s" % (n, e.shape))
+    if not np.all((e >= 0.0) & (e <= 1.0)):             # (a NaN fails both comparisons)
+        raise ValueError("emissivity: every value must lie in [0, 1]")
+    return e
+
+
+def _weight_sum(weight):
+    """W_0 + W_1 + ... added in angle order, as lbl_column_flux_surface_dev adds them; ValueError unless it is > 0"""
+    total = 0.0
+    for w in weight:
+        total += float(w)
+    if not (total > 0.0 and total != float("inf")):
+        raise ValueError("angles: over a reflecting surface the weights must add up to a finite sum > 0, not %r" % (total,))
+    return total
+
+
+def _surface_reflection(reflection):
+    if not isinstance(reflection, str) or reflection not in REFLECTIONS:
+        raise ValueError("reflection: \"lambertian\" or \"specular\", not %r" % (reflection,))
+    return REFLECTIONS.index(reflection)
+
+
 def _band_values(bands, values):
     """Copies of per-band results (leading band axis): without ``bands`` each one's single band alone."""
     return [(v[0] if bands is None else v).copy() for v in values]
@@ -1409,9 +1460,10 @@ class Fluxes:
     """What Atmosphere.fluxes returns.  ``up``, ``down``, ``net``: W m^-2 at the levels 0 (surface) .. L (top), shape (L + 1,)
     or (n_bands, L + 1); ``heatingRate``: K/day per layer, (L,) or (n_bands, L); ``mu``, ``weight``: the angle set used;
     ``upSpectrum`` / ``downSpectrum``: the spectral upward flux at the top and downward flux at the surface (W m^-2 per
-    cm^-1, n points; 0 at points outside every band) when asked for, else None."""
+    cm^-1, n points; 0 at points outside every band) when asked for, else None; ``upSurfaceSpectrum``: likewise the
+    spectral upward flux at the surface, over a surface with an emissivity only."""
 
-    def __init__(self, up, down, heatingRate, mu, weight, upSpectrum=None, downSpectrum=None):
+    def __init__(self, up, down, heatingRate, mu, weight, upSpectrum=None, downSpectrum=None, upSurfaceSpectrum=None):
         self.up = up
         self.down = down
         self.net = up - down
@@ -1420,6 +1472,7 @@ class Fluxes:
         self.weight = weight
         self.upSpectrum = upSpectrum
         self.downSpectrum = downSpectrum
+        self.upSurfaceSpectrum = upSurfaceSpectrum
 
     def __repr__(self):
         return "Fluxes(levels=%d, angles=%d, up[top]=%s, down[surface]=%s)" % (
@@ -1824,12 +1877,15 @@ class Path:
     observer, farthest first.  Segment i runs ``lengths[i]`` cm through layer ``layers[i]`` (index in the atmosphere, bottom
     layer 0); a layer may be missing or come more than once.  ``source``: what enters the first segment - "surface" (the
     surface source of the radiance() call) or "space" (nothing).  Immutable; len(path) is the number of segments, which
-    may be 0 (the observer then sees the source).  ValueError for anything else.  Atmosphere.nadirPath, zenithPath and
+    may be 0 (the observer then sees the source).  ``bounce``: None, or an integer i in 0..len(path) - the light meets the
+    surface after its first i segments and is reflected specularly there (Atmosphere.radiance with an emissivity;
+    Atmosphere.reflectedPath builds the usual one).  ValueError for anything else.  Atmosphere.nadirPath, zenithPath and
     limbPath build the usual ones."""
-    __slots__ = ("layers", "lengths", "source", "name")
+    __slots__ = ("layers", "lengths", "source", "name", "bounce")
     SOURCES = ("space", "surface")          # the C ABI's source_kind is the index
+    SURFACE_MARKER = -1                     # ... and this segment layer (length 0) the place of a bounce
 
-    def __init__(self, layers, lengths, source="surface", name=""):
+    def __init__(self, layers, lengths, source="surface", name="", bounce=None):
         try:
             layers = list(layers)
             lay = tuple(int(l) for l in layers)
@@ -1845,7 +1901,12 @@ class Path:
             raise ValueError("Path: lengths must be finite and >= 0")
         if source not in self.SOURCES:
             raise ValueError("Path: source is \"surface\" or \"space\", not %r" % (source,))
-        for k, v in zip(self.__slots__, (lay, lens, source, str(name))):
+        if bounce is not None:
+            if isinstance(bounce, bool) or not isinstance(bounce, (int, np.integer)) or not 0 <= bounce <= len(lay):
+                raise ValueError("Path: bounce is None or an integer 0..%d (the segments before the surface), not %r"
+                                 % (len(lay), bounce))
+            bounce = int(bounce)
+        for k, v in zip(self.__slots__, (lay, lens, source, str(name), bounce)):
             object.__setattr__(self, k, v)
 
     def __setattr__(self, key, value):
@@ -1857,7 +1918,15 @@ class Path:
         return len(self.layers)
 
     def __repr__(self):
-        return "Path(%s%d segments, source=%s)" % (self.name + ": " if self.name else "", len(self), self.source)
+        return "Path(%s%d segments, source=%s%s)" % (self.name + ": " if self.name else "", len(self), self.source,
+                                                     "" if self.bounce is None else ", bounce=%d" % self.bounce)
+
+    def _segments(self):
+        """(layers, lengths) as the C call takes them: the bounce as a segment of SURFACE_MARKER and length 0"""
+        if self.bounce is None:
+            return self.layers, self.lengths
+        i = self.bounce
+        return self.layers[:i] + (self.SURFACE_MARKER,) + self.layers[i:], self.lengths[:i] + (0.0,) + self.lengths[i:]
 
 
 class PathRadiance:
@@ -2039,7 +2108,8 @@ class Atmosphere(list):
                 b.free()
 
 
-    def fluxes(self, surfaceTemperature=None, surfaceSpectrum=None, topSpectrum=None, angles=3, bands=None, spectra=False):
+    def fluxes(self, surfaceTemperature=None, surfaceSpectrum=None, topSpectrum=None, angles=3, bands=None, spectra=False,
+               emissivity=None, reflection="lambertian"):
         """Upward, downward and net fluxes at every level and the heating rate of every layer (beyond the reference).
 
         Layers l = 0 .. L-1 in list order, bottom to top, as transmission() takes them; level i is the lower boundary of
@@ -2059,11 +2129,25 @@ class Atmosphere(list):
         With angles=[(1.0, pi)] the upward spectral flux at the top is pi * transmission(...) bit for bit wherever the fold
         takes its one-exp-per-thread Planck path (every range and temperature away from nu -> 0).
         The absorption coefficients come from the machinery transmission() uses and stay resident: after transmission()
-        nothing is accumulated again.  Everything is validated (ValueError) before the device is touched."""
+        nothing is accumulated again.  Everything is validated (ValueError) before the device is touched.
+
+        ``emissivity``: None, the black surface above, or the surface's emissivity e - a number in [0, 1], n values on xAxis,
+        or a pair (wavenumbers, values) interpolated onto xAxis with np.interp (the end values held).  The surface then
+        emits e Is (Is the surface source above) and reflects what comes down: the downward walk runs first, and with D_k the
+        downward radiance of angle k at level 0 and F0 = sum_k W_k D_k,
+            I_0k = e Is + (1 - e) R_k      R_k = F0 / sum_k W_k ("lambertian": diffuse)  or  D_k ("specular": a mirror)
+        Dividing by the sum of the weights (pi for the Gauss angles) makes the reflected upward flux (1 - e) F0 under the
+        quadrature itself, so the surface conserves energy whatever the angle set.  With ``spectra`` the result also carries
+        upSurfaceSpectrum, F_up at level 0.  One pass over the absorption coefficients (lbl_column_flux_surface_dev), nothing
+        comes down in between; with emissivity 1 every result is the black surface's bit for bit."""
         layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
             surfaceSpectrum, surfaceTemperature, angles, bands)
         topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
         first = layers[0]
+        refl = _surface_reflection(reflection)
+        if emissivity is not None:
+            emissivity = _surface_emissivity(emissivity, first.xAxis)
+            wsum = _weight_sum(weight)
         res = utils.BASE_RESOLUTION
         nl, nb = len(layers), len(band_first)
         ctx = _ctx()
@@ -2075,16 +2159,27 @@ class Atmosphere(list):
         level = fst.buf(ctx, "level")
         up_top = fst.buf(ctx, "up_top") if spectra else None
         down_surface = fst.buf(ctx, "down_surface") if spectra else None
-        ctx.column_flux_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
-                            mu, weight, band_first, band_count, level, I_surface=I_surface,
-                            surface_T=float(surfaceTemperature or 0.0), I_top=I_top, up_top=up_top, down_surface=down_surface)
+        up_surface = None
+        if emissivity is None:
+            ctx.column_flux_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
+                                mu, weight, band_first, band_count, level, I_surface=I_surface,
+                                surface_T=float(surfaceTemperature or 0.0), I_top=I_top, up_top=up_top, down_surface=down_surface)
+        else:
+            if not isinstance(emissivity, float):
+                emissivity = fst.buf(ctx, "emissivity").upload(emissivity)
+            up_surface = fst.buf(ctx, "up_surface") if spectra else None
+            ctx.column_flux_surface_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax,
+                                        n, mu, weight, band_first, band_count, level, emissivity, reflection=refl,
+                                        I_surface=I_surface, surface_T=float(surfaceTemperature or 0.0), I_top=I_top,
+                                        up_top=up_top, down_surface=down_surface, up_surface=up_surface)
         sums = level.download(nb * 2 * (nl + 1)).reshape(nb, 2, nl + 1) * res
         up, down = sums[:, 0, :], sums[:, 1, :]
         heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], [L.depth for L in layers])
         up, down, heat = _band_values(bands, [up, down, heat])
         return Fluxes(up, down, heat, mu, weight,
                       upSpectrum=up_top.download(n) if spectra else None,
-                      downSpectrum=down_surface.download(n) if spectra else None)
+                      downSpectrum=down_surface.download(n) if spectra else None,
+                      upSurfaceSpectrum=up_surface.download(n) if up_surface is not None else None)
 
     def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False,
                   temperature="planck"):
@@ -2256,6 +2351,15 @@ class Atmosphere(list):
         lay = range(nl - 1, lev - 1, -1)
         return Path(lay, [self[l].depth / mu for l in lay], "space", "zenith mu=%g level=%d" % (mu, lev))
 
+    def reflectedPath(self, mu=1.0, observerLevel=None):
+        """The Path of nadirPath's observer together with its mirror path: cold space, the layers L-1 .. 0 downward, the
+        surface (bounce = L), then the layers 0 .. observerLevel-1 upward, each over depth_l / mu - what a surface that
+        reflects specularly sends to the observer (radiance() with an emissivity)."""
+        mu = self._path_mu(mu)
+        lev, nl = self._path_level(observerLevel, None)
+        lay = list(range(nl - 1, -1, -1)) + list(range(lev))
+        return Path(lay, [self[l].depth / mu for l in lay], "space", "reflected mu=%g level=%d" % (mu, lev), bounce=nl)
+
     def limbPath(self, tangentHeight, planetRadius=6.371e8):
         """The Path of a limb ray through the column taken as spherical shells around a planet of radius ``planetRadius``
         (cm; level heights z_0 = 0, z_(l+1) = z_l + depth_l): it enters from space, comes down to ``tangentHeight`` (cm above
@@ -2303,14 +2407,15 @@ class Atmosphere(list):
                 raise ValueError("paths: path %d names layer %d, the column has %d" % (i, max(p.layers), nl))
         if sum(len(p) for p in plist) > nat.limit("ray_segments"):
             raise ValueError("paths: %d segments, at most %d in one call" % (sum(len(p) for p in plist), nat.limit("ray_segments")))
-        if any(p.source == "surface" for p in plist):
+        if any(p.source == "surface" or p.bounce is not None for p in plist):
             if surfaceSpectrum is None and surfaceTemperature is None:
-                raise ValueError("a path starts at the surface: give surfaceSpectrum or surfaceTemperature")
+                raise ValueError("a path starts at the surface or meets it: give surfaceSpectrum or surfaceTemperature")
             if surfaceSpectrum is None and not float(surfaceTemperature) > 0:
                 raise ValueError("surfaceTemperature must be > 0")
         return plist, layers, n, _grid_spectrum("surfaceSpectrum", surfaceSpectrum, n)
 
-    def radiance(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, transmittance=False):
+    def radiance(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, transmittance=False,
+                 emissivity=None, reflection="lambertian", angles=3):
         """The radiance arriving along ``paths`` - one Path or a list of up to 512 - through this column (beyond the
         reference).  Layers, grid and units as transmission() has them.  For every path and grid point nu_j:
             I = surfaceSpectrum[j] or B(nu_j, surfaceTemperature) for source "surface", 0 for "space";  Ttot = 1
@@ -2321,10 +2426,28 @@ class Atmosphere(list):
         radiance(nadirPath()) is transmission() bit for bit wherever fluxes() documents that identity, and with an
         instrument observe(instrument).radiance.  One kernel call (lbl_ray_radiance_dev) for all paths; a path's result does
         not depend on the others.  The absorption coefficients are the resident ones: after transmission() nothing is
-        accumulated again.  Returns a PathRadiance.  Everything is validated (ValueError) before the device is touched."""
+        accumulated again.  Returns a PathRadiance.  Everything is validated (ValueError) before the device is touched.
+
+        ``emissivity``: None, the black surface above, or the surface's emissivity e as fluxes() takes it; the call then goes
+        through lbl_ray_radiance_surface_dev.  With Is the surface source above:
+          - a path with a bounce (reflectedPath) is reflected specularly where it meets the surface, whatever ``reflection``:
+                I <- e Is + (1 - e) I        Ttot <- Ttot (1 - e)
+          - a path that starts at the surface starts with I = e Is + (1 - e) Rd.  "lambertian": Rd = F_down / sum_k W_k, the
+            diffuse reflection of the downward flux at the surface that one fluxes() pass with ``angles`` (see fluxAngles)
+            and cold space above leaves on the device - nothing comes down in between.  "specular": Rd = 0, the path carries
+            e Is alone and the reflected light belongs to the paths with a bounce.
+        With emissivity 1 every result is the black surface's bit for bit.  A path with a bounce needs an emissivity."""
         plist, layers, n, surfaceSpectrum = self._path_checks(paths, surfaceTemperature, surfaceSpectrum)
         R, nl = len(plist), len(layers)
         first = layers[0]
+        refl = _surface_reflection(reflection)
+        if emissivity is None:
+            if any(p.bounce is not None for p in plist):
+                raise ValueError("a path with a bounce needs a surface that reflects: give emissivity")
+        else:
+            emissivity = _surface_emissivity(emissivity, first.xAxis)
+            mu, weight = fluxAngles(angles)
+            wsum = _weight_sum(weight)
         n_rows = 2 * R if transmittance else R
         support = None
         if instrument is not None:
@@ -2344,11 +2467,29 @@ class Atmosphere(list):
         pst = _kept_state(self, "_path_state").reserve(ctx, R * n)
         rad = pst.buf(ctx, "radiance")
         trn = pst.buf(ctx, "transmittance") if transmittance else None
-        ray_first = np.cumsum([0] + [len(p) for p in plist])
-        ctx.ray_radiance_dev(kbufs, [L.T for L in layers], first.rangeMin, first.rangeMax, n, ray_first,
-                             [l for p in plist for l in p.layers], [x for p in plist for x in p.lengths],
-                             [Path.SOURCES.index(p.source) for p in plist], rad, I_source=I_source,
-                             source_T=float(surfaceTemperature or 0.0), transmittance=trn)
+        if emissivity is None:
+            ray_first = np.cumsum([0] + [len(p) for p in plist])
+            ctx.ray_radiance_dev(kbufs, [L.T for L in layers], first.rangeMin, first.rangeMax, n, ray_first,
+                                 [l for p in plist for l in p.layers], [x for p in plist for x in p.lengths],
+                                 [Path.SOURCES.index(p.source) for p in plist], rad, I_source=I_source,
+                                 source_T=float(surfaceTemperature or 0.0), transmittance=trn)
+        else:
+            sst = _kept_state(self, "_path_surface").reserve(ctx, max(n, 2 * (nl + 1)))
+            if not isinstance(emissivity, float):
+                emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
+            down, norm = None, 0.0
+            if refl == 0 and any(p.source == "surface" for p in plist):
+                # the downward flux at the surface under cold space, left on the device for the ray call behind it
+                down, norm = sst.buf(ctx, "down_surface"), wsum
+                ctx.column_flux_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax,
+                                    n, mu, weight, [0], [n], sst.buf(ctx, "level"), I_surface=I_source,
+                                    surface_T=float(surfaceTemperature or 0.0), down_surface=down)
+            segs = [p._segments() for p in plist]
+            ctx.ray_radiance_surface_dev(kbufs, [L.T for L in layers], first.rangeMin, first.rangeMax, n,
+                                         np.cumsum([0] + [len(lay) for lay, _ in segs]), [l for lay, _ in segs for l in lay],
+                                         [x for _, lens in segs for x in lens], [Path.SOURCES.index(p.source) for p in plist],
+                                         rad, emissivity, I_source=I_source, source_T=float(surfaceTemperature or 0.0),
+                                         surface_down=down, surface_down_norm=norm, transmittance=trn)
         if instrument is None:
             return PathRadiance(first.xAxis, rad.download(R * n).reshape(R, n),
                                 trn.download(R * n).reshape(R, n) if transmittance else None, plist)
@@ -2384,6 +2525,8 @@ class Atmosphere(list):
         if temperature not in ("planck", "full"):
             raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         plist, layers, n, surfaceSpectrum = self._path_checks(paths, surfaceTemperature, surfaceSpectrum)
+        if any(p.bounce is not None for p in plist):
+            raise ValueError("paths: a path with a bounce has no weighting functions (radiance() with an emissivity computes it)")
         R, nl = len(plist), len(layers)
         first = layers[0]
         full = temperature == "full"
