@@ -609,6 +609,77 @@ int lbl_ray_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef
                          int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
                          lbl_buffer* radiance /* n_rays x n, may be NULL */, lbl_buffer* jac /* rows x n */);
 
+/* ---- Jacobians over a reflecting surface (beyond the reference; ABI 5, backward compatible) ----------------------------
+ * pyrad_amd.model.Atmosphere.jacobians, pathJacobians and observe with ``emissivity``: the derivatives of what
+ * lbl_column_flux_surface_dev and lbl_ray_radiance_surface_dev compute, the emissivity among the variables.
+ *
+ * lbl_column_jacobian_surface_dev: the arguments of lbl_column_jacobian_dev, plus I_top (may be NULL: 0), emissivity /
+ * emissivity_all / reflection as lbl_column_flux_surface_dev takes them, and jac_e_spectrum.  Forward, at grid point nu_j,
+ * exactly lbl_column_flux_surface_dev: the downward walk from I_top gives Id_(l+1)k, the radiance entering layer l from
+ * above, and D_k = Id_0k; R_k = F0 / Wsum (Lambertian, F0 = sum_k W_k D_k) or D_k (specular); Iu_0k = e Is + (1 - e) R_k;
+ * the upward walk gives Iu_lk and F = sum_k W_k Iu_Lk.  With A_lk = prod_{i>l} t_ik, C_lk = prod_{i<l} t_ik, Ttot_k =
+ * prod_i t_ik and Q_k = (1 - e) W_k (sum_k' W_k' Ttot_k') / Wsum (Lambertian) or (1 - e) W_k Ttot_k (specular):
+ *   gu_lk = A_lk t_lk (B_l - Iu_lk)                upward leg: lbl_column_jacobian_dev's term, the reflecting boundary in Iu
+ *   gd_lk = C_lk t_lk (B_l - Id_(l+1)k)            downward leg, seen through the surface
+ *   dF/d ln tau_l     = sum_k (tau_l / mu_k) (W_k gu_lk + Q_k gd_lk)
+ *   term m (layer l)  = sum_k (term_abs_coef[m][j] depth_l / mu_k) (W_k gu_lk + Q_k gd_lk)
+ *   dF/dT_l (Planck)  = sum_k (W_k A_lk + Q_k C_lk) (1 - t_lk) dB_l/dT
+ *   dF/dT_s           = e sum_k W_k Ttot_k dB(nu_j, surface_T)/dT                  0 when I_surface is given
+ *   dF/de             = sum_k W_k Ttot_k (Is - R_k)
+ * jac[b] = [F, dF/dT_s, dF/de, dF/d ln tau_0..L-1, dF/dT_0..L-1, terms]: n_bands x (3 + 2 n_layers + n_terms) doubles, band
+ * sums with nan_to_num (of each leg's spectral value), as lbl_column_jacobian_dev.  jac_ln_tau_spectra / jac_T_spectra
+ * (may be NULL; n_layers x n) and jac_e_spectrum (may be NULL; n) receive the spectral values at every point of every band, 0
+ * elsewhere.  The terms are lbl_column_jacobian_dev's (dk_l/dT as a term gives the absorption part of dF/dT_l).
+ * Arithmetic: three walks - down (Id, its running maximum Dmax over the levels, Ttot), up (lbl_column_jacobian_dev's upward
+ * walk, and beside it gd_lk = C_lk B_l + D'_lk clamped to [-C_lk t_lk Dmax, C_lk t_lk B_l], D' = (the emission of the layers
+ * below l that reaches the surface) - D: lbl_column_jacobian_dev's identity upside down), down (lbl_column_jacobian_dev's
+ * downward pass).  No level radiance is stored; sums in a fixed order, no atomics: the same inputs give the same bits.
+ * Identity: with e == 1 everywhere and finite downward radiances, for one and two angles every value other than dF/de is
+ * lbl_column_jacobian_dev's bit for bit (the reflected leg adds zeros); with more angles the two calls group the points of
+ * a thread differently and agree to rounding.
+ * LBL_ERR_BAD_ARG: everything lbl_column_jacobian_dev or lbl_column_flux_surface_dev refuses (with jac holding n_bands x (3 +
+ * 2 n_layers + n_terms)); a jac_e_spectrum shorter than n; "sweep_ieee_divisions" 1.  Everything is checked before anything
+ * is enqueued.  Stream-ordered; nothing is synchronised.
+ *
+ * lbl_ray_jacobian_surface_dev: the arguments of lbl_ray_jacobian_dev with the rays, markers (seg_layer == -1, length 0) and
+ * sources of lbl_ray_radiance_surface_dev without surface_down - a ray that starts at the surface starts with e Is - and that
+ * call's radiance bit for bit.  An element of a ray is a segment or a marker; A is the product, over every element after
+ * one, of t_s for segments and (1 - e) for markers; A_0 the product over every element of the ray:
+ *   dI/d ln tau_l, dI/dT_l, the terms: lbl_ray_jacobian_dev's sums with that A
+ *   dI/dT_source = e dBs/dT (sum over the markers m of A_m + [source_kind 1] A_0)          0 when I_source is given
+ *   dI/de        = sum over the markers m of A_m (Is - I_m) + [source_kind 1] A_0 Is        I_m: what arrives at the marker
+ * Ray r owns 2 + 2 c_r + m_r rows: row 0 dI/dT_source, row 1 dI/de, then lbl_ray_jacobian_dev's order; markers are no
+ * layers and have no rows.  lbl_ray_jacobian_surface_rows returns that layout without a context.
+ * Arithmetic: lbl_ray_jacobian_dev's two walks; dI/de is carried forward (S <- t S per segment, S <- (Is - I) + (1 - e) S at
+ * a marker), Imax includes the markers' results, and on the way back a marker adds A e Is to D and A e dBs/dT to row 0,
+ * then A <- A (1 - e).  Rays without a marker, with e == 1, give lbl_ray_jacobian_dev's rows and radiance bit for bit.
+ * LBL_ERR_BAD_ARG: everything lbl_ray_jacobian_dev refuses except a segment layer of -1, and what
+ * lbl_ray_radiance_surface_dev refuses of markers and emissivity.  Everything is checked before anything is enqueued; the
+ * host arrays are copied and not retained.  Stream-ordered; nothing is synchronised.
+ * (lbl_ray_jacobian_dev and lbl_ray_jacobian_rows go on refusing a segment layer of -1.) */
+int lbl_column_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                    const double* depth, double range_min, double range_max, int64_t n,
+                                    lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top /* may be NULL */,
+                                    int n_angles, const double* mu, const double* weight,
+                                    int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                    lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                    int reflection /* 0 Lambertian, 1 specular */,
+                                    int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
+                                    lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra,
+                                    lbl_buffer* jac_e_spectrum /* n, may be NULL */);
+int lbl_ray_jacobian_surface_rows(int n_layers, int n_rays, const int32_t* ray_first,
+                                  const int32_t* seg_layer /* -1: surface marker */,
+                                  int n_terms, const int32_t* term_layer,
+                                  int64_t* row_first /* n_rays + 1, may be NULL */, int64_t* rows);
+int lbl_ray_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                 double range_min, double range_max, int64_t n,
+                                 int n_rays, const int32_t* ray_first,
+                                 const int32_t* seg_layer /* -1: surface marker */, const double* seg_length,
+                                 const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                                 lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                 int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
+                                 lbl_buffer* radiance /* n_rays x n, may be NULL */, lbl_buffer* jac /* rows x n */);
+
 /* ---- instrument channels (beyond the reference; ABI 5, backward compatible) -------------------------------------------
  * pyrad_amd.model.convolve / Atmosphere.observe: n_rows device-resident spectra on the base grid linspace(range_min,
  * range_max, n) convolved with an instrument line shape (ILS) onto n_channels channels, so that channel radiances and channel

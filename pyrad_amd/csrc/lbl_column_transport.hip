@@ -1,7 +1,7 @@
 // Column transport (include/pyrad_hip.h, "level fluxes", "Jacobians" and "ray paths"): argument checking and the launch
 // sequences of lbl_column_flux_dev, lbl_column_jacobian_dev, lbl_ray_radiance_dev and lbl_ray_jacobian_dev, and of their
-// variants over a reflecting surface, lbl_column_flux_surface_dev and lbl_ray_radiance_surface_dev.  The kernels are
-// K5c, K5d, K5e, K5f and K5g of lbl_kernels.hip; the context's internals
+// variants over a reflecting surface, lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev, lbl_column_jacobian_surface_dev
+// and lbl_ray_jacobian_surface_dev.  The kernels are K5c, K5d, K5e, K5f, K5g and K5h of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -105,12 +105,12 @@ static int check_column(lbl_ctx* ctx, const char* what, ColumnRT* a, int n_layer
 }
 
 // The launch sequence after every check: the argument block and the partial scratch for the widest band (`np` points per
-// thread, nv values per partial), the optional spectra spec[0 .. NS) (spec_bytes each) zeroed, then the bands one after another
-// over one partial block: stream order keeps a band's final reduction ahead of the next band.  launch_band(d_args, partial,
-// b, s) enqueues band b.
+// thread, nv values per partial), the optional spectra spec[0 .. NS) (spec_bytes each) and spec_n (n points) zeroed, then
+// the bands one after another over one partial block: stream order keeps a band's final reduction ahead of the next band.
+// launch_band(d_args, partial, b, s) enqueues band b.
 template <class Args, size_t NS, class LaunchBand>
 static int run_column(lbl_ctx* ctx, const Args* a, int np, int nv, int n_bands, const int64_t* band_count, double* const (&spec)[NS],
-                      size_t spec_bytes, LaunchBand launch_band) {
+                      size_t spec_bytes, LaunchBand launch_band, double* spec_n = nullptr) {
     int64_t max_count = 0;
     for (int b = 0; b < n_bands; ++b) max_count = std::max(max_count, band_count[b]);
     void* partial = nullptr;
@@ -124,6 +124,7 @@ static int run_column(lbl_ctx* ctx, const Args* a, int np, int nv, int n_bands, 
     // (points outside every band keep 0 in the spectra)
     for (double* p : spec)
         if (p && spec_bytes) COLUMN_HIP_TRY(ctx, hipMemsetAsync(p, 0, spec_bytes, s));
+    if (spec_n && a->n > 0) COLUMN_HIP_TRY(ctx, hipMemsetAsync(spec_n, 0, (size_t)a->n * sizeof(double), s));
     for (int b = 0; b < n_bands; ++b) launch_band((const Args*)d_args, (double*)partial, b, s);
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
@@ -207,24 +208,17 @@ extern "C" int lbl_column_flux_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffe
     });
 } LBL_GUARD_END(ctx)
 
-extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
-                                       const double* depth, double range_min, double range_max, int64_t n,
-                                       lbl_buffer* I_surface, double surface_T, int n_angles, const double* mu,
-                                       const double* weight, int n_bands, const int64_t* band_first,
-                                       const int64_t* band_count, int n_terms, lbl_buffer* const* term_abs_coef,
-                                       const int32_t* term_layer, lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra,
-                                       lbl_buffer* jac_T_spectra) try {
-    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
-    std::vector<char> blk(sizeof(JacArgs), 0);
-    JacArgs* a = (JacArgs*)blk.data();
+// What lbl_column_jacobian_dev and lbl_column_jacobian_surface_dev check behind check_column, then the JacArgs part of the
+// argument block filled; `head` values per band come before the layers' (2, or 3 with dF/de).
+static int check_jacobian(lbl_ctx* ctx, JacArgs* a, int head, int n_layers, const double* T, int64_t n, double surface_T,
+                          int n_angles, const double* weight, int n_bands, int n_terms, lbl_buffer* const* term_abs_coef,
+                          const int32_t* term_layer, lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra,
+                          lbl_buffer* jac_T_spectra) {
     int rc;
-    if ((rc = check_column(ctx, "Jacobians", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface, surface_T,
-                           n_angles, mu, weight, n_bands, band_first, band_count)))
-        return rc;
     if (n_terms < 0 || n_terms > kMaxJacobianTerms)
         return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d molecule terms", kMaxJacobianTerms);
     if (n_terms > 0 && (!term_abs_coef || !term_layer)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
-    const int nv = 2 + 2 * n_layers + n_terms;
+    const int nv = head + 2 * n_layers + n_terms;
     if ((rc = ctx_check_buffer(ctx, jac, (int64_t)n_bands * nv, "jac", true))) return rc;
     if ((rc = ctx_check_buffer(ctx, jac_ln_tau_spectra, (int64_t)n_layers * n, "jac_ln_tau_spectra", false))) return rc;
     if ((rc = ctx_check_buffer(ctx, jac_T_spectra, (int64_t)n_layers * n, "jac_T_spectra", false))) return rc;
@@ -250,17 +244,80 @@ extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* c
     a->ln_tau_spec = jac_ln_tau_spectra ? buffer_data(jac_ln_tau_spectra) : nullptr;
     a->T_spec = jac_T_spectra ? buffer_data(jac_T_spectra) : nullptr;
     a->n_terms = n_terms;
+    return LBL_OK;
+}
+
+extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                       const double* depth, double range_min, double range_max, int64_t n,
+                                       lbl_buffer* I_surface, double surface_T, int n_angles, const double* mu,
+                                       const double* weight, int n_bands, const int64_t* band_first,
+                                       const int64_t* band_count, int n_terms, lbl_buffer* const* term_abs_coef,
+                                       const int32_t* term_layer, lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra,
+                                       lbl_buffer* jac_T_spectra) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(JacArgs), 0);
+    JacArgs* a = (JacArgs*)blk.data();
+    int rc;
+    if ((rc = check_column(ctx, "Jacobians", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface, surface_T,
+                           n_angles, mu, weight, n_bands, band_first, band_count)))
+        return rc;
+    if ((rc = check_jacobian(ctx, a, 2, n_layers, T, n, surface_T, n_angles, weight, n_bands, n_terms, term_abs_coef,
+                             term_layer, jac, jac_ln_tau_spectra, jac_T_spectra)))
+        return rc;
+    const int nv = 2 + 2 * n_layers + n_terms;
     return run_column(ctx, a, 2, nv, n_bands, band_count, {a->ln_tau_spec, a->T_spec}, (size_t)n_layers * (size_t)n * sizeof(double),
                       [&](const JacArgs* d, double* partial, int b, hipStream_t s) {
         launch_column_jacobian(d, n_layers, n_angles, n_terms, band_first[b], band_count[b], partial, buffer_data(jac) + (size_t)b * nv, s);
     });
 } LBL_GUARD_END(ctx)
 
+extern "C" int lbl_column_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                               const double* depth, double range_min, double range_max, int64_t n,
+                                               lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
+                                               const double* mu, const double* weight, int n_bands,
+                                               const int64_t* band_first, const int64_t* band_count, lbl_buffer* emissivity,
+                                               double emissivity_all, int reflection, int n_terms,
+                                               lbl_buffer* const* term_abs_coef, const int32_t* term_layer, lbl_buffer* jac,
+                                               lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra,
+                                               lbl_buffer* jac_e_spectrum) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(SurfaceJacArgs), 0);
+    SurfaceJacArgs* a = (SurfaceJacArgs*)blk.data();
+    int rc;
+    if ((rc = check_column(ctx, "Jacobians", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface, surface_T,
+                           n_angles, mu, weight, n_bands, band_first, band_count)))
+        return rc;
+    if ((rc = check_jacobian(ctx, a, 3, n_layers, T, n, surface_T, n_angles, weight, n_bands, n_terms, term_abs_coef,
+                             term_layer, jac, jac_ln_tau_spectra, jac_T_spectra)))
+        return rc;
+    if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, jac_e_spectrum, n, "jac_e_spectrum", false))) return rc;
+    if (reflection != 0 && reflection != 1)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "reflection must be 0 (Lambertian) or 1 (specular)");
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    double w_sum = 0.0;
+    for (int k = 0; k < n_angles; ++k) w_sum += weight[k];
+    if (!(w_sum > 0.0) || !std::isfinite(w_sum))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "the weights must add up to a finite sum > 0");
+    a->I_top = I_top ? buffer_data(I_top) : nullptr;
+    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a->emissivity_all = emissivity_all;
+    a->w_sum = w_sum;
+    a->e_spec = jac_e_spectrum ? buffer_data(jac_e_spectrum) : nullptr;
+    a->reflection = reflection;
+    const int nv = 3 + 2 * n_layers + n_terms;
+    return run_column(ctx, a, surface_jacobian_points(n_angles), nv, n_bands, band_count, {a->ln_tau_spec, a->T_spec},
+                      (size_t)n_layers * (size_t)n * sizeof(double),
+                      [&](const SurfaceJacArgs* d, double* partial, int b, hipStream_t s) {
+        launch_surface_jacobian(d, n_layers, n_angles, n_terms, band_first[b], band_count[b], partial, buffer_data(jac) + (size_t)b * nv, s);
+    }, a->e_spec);
+} LBL_GUARD_END(ctx)
+
 static size_t round8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 // What lbl_ray_radiance_dev, lbl_ray_jacobian_dev and lbl_ray_jacobian_rows (ctx NULL) check of the ray lists themselves.
 // `markers`: a segment layer of kRaySurfaceMarker is no layer but the place where the ray meets the surface
-// (lbl_ray_radiance_surface_dev alone).
+// (lbl_ray_radiance_surface_dev, lbl_ray_jacobian_surface_dev and lbl_ray_jacobian_surface_rows).
 static int check_ray_lists(lbl_ctx* ctx, int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
                            bool markers) {
     if (n_layers < 1 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d layers", kMaxLayers);
@@ -445,7 +502,8 @@ extern "C" int lbl_ray_radiance_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buff
 } LBL_GUARD_END(ctx)
 
 // The rows of lbl_ray_jacobian_dev (include/pyrad_hip.h): per ray the distinct layers it crosses in ascending order and
-// the terms whose layer it crosses in term order.  The lists are checked already.
+// the terms whose layer it crosses in term order; `head` rows come before the layers' (1, or 2 with dI/de: the surface entry
+// points, whose markers are no layers and have no rows).  The lists are checked already.
 struct RayRows {
     std::vector<int64_t> row_first;          // n_rays + 1
     std::vector<int32_t> crossed;            // per ray: c
@@ -454,7 +512,7 @@ struct RayRows {
     std::vector<int32_t> term_row;           // per set of crossed layers: the row of original term m, relative (-1: not crossed)
 };
 static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer, int n_terms,
-                     const int32_t* term_layer, RayRows* R) {
+                     const int32_t* term_layer, int head, RayRows* R) {
     R->row_first.assign(1, 0);
     R->crossed.clear(); R->ray_terms.clear(); R->term_row.clear();
     R->seg_slot.assign((size_t)ray_first[n_rays], 0);
@@ -462,7 +520,8 @@ static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const i
     std::vector<int32_t> rank(n_layers);
     for (int r = 0; r < n_rays; ++r) {
         std::fill(rank.begin(), rank.end(), -1);
-        for (int s = ray_first[r]; s < ray_first[r + 1]; ++s) rank[seg_layer[s]] = 0;
+        for (int s = ray_first[r]; s < ray_first[r + 1]; ++s)
+            if (seg_layer[s] != kRaySurfaceMarker) rank[seg_layer[s]] = 0;
         std::vector<int32_t> set;
         for (int l = 0; l < n_layers; ++l)
             if (rank[l] == 0) { rank[l] = (int32_t)set.size(); set.push_back(l); }
@@ -470,6 +529,7 @@ static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const i
         // backward order: the last segment of a layer stores its rows, the earlier ones add
         std::vector<char> seen(n_layers, 0);
         for (int s = ray_first[r + 1] - 1; s >= ray_first[r]; --s) {
+            if (seg_layer[s] == kRaySurfaceMarker) continue;
             R->seg_slot[s] = rank[seg_layer[s]] | (seen[seg_layer[s]] ? 0 : kRayRowStore);
             seen[seg_layer[s]] = 1;
         }
@@ -479,7 +539,7 @@ static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const i
             auto it = tables.find(set);
             if (it == tables.end()) {
                 it = tables.emplace(set, (int32_t)R->term_row.size()).first;
-                int next = 1 + 2 * c;
+                int next = head + 2 * c;
                 for (int m = 0; m < n_terms; ++m) R->term_row.push_back(rank[term_layer[m]] >= 0 ? next++ : -1);
             }
             R->ray_terms.push_back(it->second);
@@ -487,7 +547,7 @@ static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const i
             R->ray_terms.push_back(0);
         }
         R->crossed.push_back(c);
-        R->row_first.push_back(R->row_first.back() + 1 + 2 * c + m_r);
+        R->row_first.push_back(R->row_first.back() + head + 2 * c + m_r);
     }
 }
 
@@ -501,40 +561,60 @@ static int check_ray_terms(lbl_ctx* ctx, int n_layers, int n_terms, const int32_
     return LBL_OK;
 }
 
-extern "C" int lbl_ray_jacobian_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
-                                     int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows) try {
+static int ray_jacobian_rows(bool surface, int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
+                             int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows) {
     int rc;
     if (!rows) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "rows is NULL");
-    if ((rc = check_ray_lists(nullptr, n_layers, n_rays, ray_first, seg_layer, false))) return rc;
+    if ((rc = check_ray_lists(nullptr, n_layers, n_rays, ray_first, seg_layer, surface))) return rc;
     if ((rc = check_ray_terms(nullptr, n_layers, n_terms, term_layer))) return rc;
     RayRows R;
-    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, &R);
+    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, surface ? 2 : 1, &R);
     if (row_first) memcpy(row_first, R.row_first.data(), (size_t)(n_rays + 1) * sizeof(int64_t));
     *rows = R.row_first.back();
     return LBL_OK;
+}
+
+extern "C" int lbl_ray_jacobian_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
+                                     int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows) try {
+    return ray_jacobian_rows(false, n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, row_first, rows);
 } LBL_GUARD_END(nullptr)
 
-extern "C" int lbl_ray_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
-                                    double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
-                                    const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
-                                    lbl_buffer* I_source, double source_T, int n_terms, lbl_buffer* const* term_abs_coef,
-                                    const int32_t* term_layer, lbl_buffer* radiance, lbl_buffer* jac) try {
+extern "C" int lbl_ray_jacobian_surface_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
+                                             int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows) try {
+    return ray_jacobian_rows(true, n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, row_first, rows);
+} LBL_GUARD_END(nullptr)
+
+// lbl_ray_jacobian_dev, and with `surface` lbl_ray_jacobian_surface_dev: markers among the segment layers, the emissivity
+// behind the header, one more row per ray.
+static int ray_jacobian_call(lbl_ctx* ctx, bool surface, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                             double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
+                             const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
+                             lbl_buffer* I_source, double source_T, lbl_buffer* emissivity, double emissivity_all,
+                             int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer, lbl_buffer* radiance,
+                             lbl_buffer* jac) {
     if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     // the argument block: header, K5e's tables, row_first, ray_crossed, seg_slot, ray_terms, term_row
-    std::vector<char> head(sizeof(RayJacArgs), 0);
+    const size_t header = surface ? sizeof(RaySurfaceJacArgs) : sizeof(RayJacArgs);
+    std::vector<char> head(header, 0);
     RayJacArgs* a = (RayJacArgs*)head.data();
     std::vector<int32_t> order;
     size_t off = 0;
     int rc;
-    if ((rc = check_rays(ctx, a, sizeof(RayJacArgs), n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first,
-                         seg_layer, seg_length, source_kind, I_source, source_T, radiance, false, nullptr, false, &order, &off)))
+    if ((rc = check_rays(ctx, a, header, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first,
+                         seg_layer, seg_length, source_kind, I_source, source_T, radiance, false, nullptr, surface, &order, &off)))
         return rc;
+    if (surface) {
+        if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+        RaySurfaceJacArgs* sa = (RaySurfaceJacArgs*)head.data();
+        sa->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+        sa->emissivity_all = emissivity_all;
+    }
     if ((rc = check_ray_terms(ctx, n_layers, n_terms, term_layer))) return rc;
     if (n_terms > 0 && !term_abs_coef) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
     for (int t = 0; t < n_terms; ++t)
         if ((rc = ctx_check_buffer(ctx, term_abs_coef[t], n, "term_abs_coef", true))) return rc;
     RayRows R;
-    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, &R);
+    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, surface ? 2 : 1, &R);
     const int64_t rows = R.row_first.back();
     if (n > INT64_MAX / rows) return column_fail(ctx, LBL_ERR_BAD_ARG, "rows x n overflows");
     if ((rc = ctx_check_buffer(ctx, jac, rows * n, "jac", true))) return rc;
@@ -575,7 +655,30 @@ extern "C" int lbl_ray_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
     void* d_args = nullptr;
     if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
     COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
-    launch_ray_jacobian((const RayJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
+    if (surface) launch_ray_surface_jacobian((const RaySurfaceJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
+    else launch_ray_jacobian((const RayJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
+}
+
+extern "C" int lbl_ray_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                    double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
+                                    const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
+                                    lbl_buffer* I_source, double source_T, int n_terms, lbl_buffer* const* term_abs_coef,
+                                    const int32_t* term_layer, lbl_buffer* radiance, lbl_buffer* jac) try {
+    return ray_jacobian_call(ctx, false, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
+                             seg_length, source_kind, I_source, source_T, nullptr, 1.0, n_terms, term_abs_coef, term_layer,
+                             radiance, jac);
+} LBL_GUARD_END(ctx)
+
+extern "C" int lbl_ray_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                            double range_min, double range_max, int64_t n, int n_rays,
+                                            const int32_t* ray_first, const int32_t* seg_layer, const double* seg_length,
+                                            const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                                            lbl_buffer* emissivity, double emissivity_all, int n_terms,
+                                            lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
+                                            lbl_buffer* radiance, lbl_buffer* jac) try {
+    return ray_jacobian_call(ctx, true, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
+                             seg_length, source_kind, I_source, source_T, emissivity, emissivity_all, n_terms, term_abs_coef,
+                             term_layer, radiance, jac);
 } LBL_GUARD_END(ctx)

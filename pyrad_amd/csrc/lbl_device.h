@@ -336,6 +336,30 @@ struct RayJacArgs : RayArgs {
 };
 void launch_ray_jacobian(const RayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms, hipStream_t s);
 
+// Jacobians over a reflecting surface (K5h, lbl_column_transport.hip: lbl_column_jacobian_surface_dev,
+// lbl_ray_jacobian_surface_dev): K5d's passes behind K5g's downward walk, with the downward leg's derivative carried up
+// through the surface, and K5f's walks with surface markers.  Values per band: [F_top, dF/dT_s, dF/de, L x d ln tau, L x dT
+// (Planck part), n_terms x term]; a ray's rows: [dT_source, de, c x d ln tau, c x dT, its terms].  Partials, their count and
+// the final reduction are K5c's; the ray tables, the dispatch order and the row tables K5e's and K5f's.
+struct SurfaceJacArgs : JacArgs {
+    const double* I_top;                // downward radiance entering at the top, or nullptr: 0
+    const double* emissivity;           // n points, or nullptr: emissivity_all
+    double emissivity_all;
+    double w_sum;                       // W_0 + W_1 + ..., added on the host in angle order (> 0 and finite)
+    double* e_spec;                     // optional: n spectral dF/de
+    int32_t reflection, pad2;           // 0 Lambertian, 1 specular (SurfaceFluxArgs)
+};
+// the points per thread of surface_jacobian_kernel for n_angles (its partials are sized by it)
+int surface_jacobian_points(int n_angles);
+void launch_surface_jacobian(const SurfaceJacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first,
+                             long long count, double* partial, double* jac, hipStream_t s);
+struct RaySurfaceJacArgs : RayJacArgs {
+    const double* emissivity;           // n points, or nullptr: emissivity_all
+    double emissivity_all;
+};
+void launch_ray_surface_jacobian(const RaySurfaceJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
+                                 hipStream_t s);
+
 // Instrument channels (K8, lbl_instrument.hip: lbl_ils_convolve_dev): n_rows spectra on the base grid convolved with an
 // instrument line shape onto n_channels channels.  One argument block per call: this header, then the arrays it names by
 // their byte offset from the block's start (the block's device address is known only after it is uploaded).

@@ -22,6 +22,8 @@
 //                              along a ray (Atmosphere.pathJacobians; beyond the reference)
 //   K5g surface_flux_kernel, ray_surface_kernel   K5c and K5e over a reflecting surface: emissivity, Lambertian or specular
 //                              reflection, rays that bounce (fluxes() and radiance() with an emissivity; beyond the reference)
+//   K5h surface_jacobian_kernel, ray_surface_jacobian_kernel   K5d and K5f over that surface: the reflected leg's derivatives
+//                              and d/d emissivity (jacobians(), pathJacobians(), observe() with an emissivity; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -4348,6 +4350,439 @@ __global__ __launch_bounds__(256) void ray_jacobian_kernel(const RayJacArgs* __r
 }
 
 // ----------------------------------------------------------------------------------------
+// K5h: Jacobians over a reflecting surface (lbl_column_jacobian_surface_dev, lbl_ray_jacobian_surface_dev; the semantics are
+// in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// Column: three walks.  (1) K5g's downward walk from I_top, keeping per angle the radiance, its running maximum Dmax over
+// the levels and the transmittance Ttot; at the surface dF/de and dF/dT_s are complete (both need only Ttot, Is and what
+// came down), and the state turns in place into that of walk (2): I_up[0] = e Is + (1 - e) R, Imax, and for the light that
+// went DOWN through a layer and is seen through the surface the weight Qf (Q_k = W_k Qf), C = 1 and D' = -D.  (2) K5d's
+// upward walk, and beside it the downward leg mirrored: with C the transmittance from the layer's lower edge to the
+// surface and D' = E' - D, E' the emission of the layers below that reaches the surface,
+//     C_l t_l (B_l - Id_(l+1)) = C_l B_l + D'_l,   clamped to [-C_l t_l Dmax, C_l t_l B_l]
+// - K5d's identity upside down, so no level radiance is stored.  This walk STORES the reflected leg's part of the spectra
+// and adds its sums to the band slots.  (3) K5d's downward pass, which ADDS its part to what the same thread stored.
+// With e == 1: Qf = 0, walk (2) contributes +-0 everywhere, I_up[0] = Is, and walks (2) and (3) are K5d's operations in
+// K5d's order - K5d's bits on its own groups of points (the one-exp Planck path starts from a thread's first point).
+template <int NP, int NA>
+__global__ __launch_bounds__(256) void surface_jacobian_kernel(const SurfaceJacArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                               long long lo1, long long n1, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    constexpr int kSlot = 3 + 2 * kMaxLayers + kMaxJacobianTerms;
+    __shared__ double acc[4 * kSlot];            // [wave][F_top, dT_s, de, L x ln tau, L x T, terms]
+    const SurfaceJacArgs& A = *Ap;
+    const int L = A.n_layers;
+    const int nv = 3 + 2 * L + A.n_terms;
+    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
+    __syncthreads();
+    double* my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    auto add = [&](int slot, double s) {
+        s = wave_sum(s);
+        if (lane0) my[slot] += s;
+    };
+    const long long total = n0 + n1;
+    const long long stride = (long long)gridDim.x * blockDim.x * NP;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
+    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
+        const long long q = q0 + (long long)threadIdx.x * NP;
+        const bool active = q < total;
+        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        // walk 1: I = Id, Dm = Dmax, Ak = Ttot;  walk 2: I = Iu, Imax, Ck = C, Dp = D', Dm, Ak = Qf;  walk 3: I = D, Imax, Ak = A
+        double nu[NP], pa_n[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP], Ck[NA][NP], Dp[NA][NP], Dm[NA][NP];
+        column_points<NP>(A, j, nu, pa_n);
+        const bool fast = fold_fast_path<NP>(A, nu, active);
+        // the layer's terms: term_k depth G per point, into the terms' slots (walks 2 and 3 each add their leg)
+        auto terms = [&](int l, const double (&Gd)[NP]) {
+            for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
+                const vec km = load_points<NP>(A.term_k[t], j);
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < NP; ++p) s += active ? nan_to_num(km[p] * Gd[p]) : 0.0;
+                add(3 + 2 * L + A.term_slot[t], s);
+            }
+        };
+        auto first_down = [&](auto fast_tag, int l, vec v) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double pbkT = A.pbkT[l], depth = A.depth[l];
+            double E0 = 0.0;
+            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+                double dB;
+                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, 0.0, &dB);
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double tr = exp_neg_budget(tau * A.rmu[k]);
+                    I[k][p] = fold_update<FAST>(tr, I[k][p], B);
+                    Dm[k][p] = fmax(Dm[k][p], I[k][p]);
+                    Ak[k][p] = Ak[k][p] * tr;
+                }
+            }
+        };
+        auto up = [&](auto fast_tag, int l, vec v) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double pbkT = A.pbkT[l], depth = A.depth[l], rT = A.rT[l];
+            double E0 = 0.0;
+            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+            double s_tau = 0.0, s_T = 0.0, Gd[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+                double dB;
+                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
+                double G = 0.0, gT = 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double tr = exp_neg_budget(tau * A.rmu[k]);
+                    // the downward leg through this layer, seen through the surface
+                    const double Ct = Ck[k][p] * tr;
+                    const double g = fmin(fmax(Ck[k][p] * B + Dp[k][p], -(Ct * Dm[k][p])), Ct * B);
+                    G = fma(A.wrmu[k], Ak[k][p] * g, G);
+                    const double c1 = Ck[k][p] * (1.0 - tr);
+                    gT = fma(A.w[k], Ak[k][p] * (c1 * dB), gT);
+                    Dp[k][p] = Dp[k][p] + c1 * B;            // D'_(l+1) = D'_l + C_l (1 - t_l) B_l
+                    Ck[k][p] = Ct;                           // C_(l+1) = C_l t_l
+                    // the upward leg: K5d's walk
+                    I[k][p] = fold_update<FAST>(tr, I[k][p], B);
+                    Imax[k][p] = fmax(Imax[k][p], I[k][p]);
+                }
+                const double dtau = tau * G;
+                Gd[p] = depth * G;
+                if (active && A.ln_tau_spec) A.ln_tau_spec[(long long)l * A.n + j + p] = dtau;
+                if (active && A.T_spec) A.T_spec[(long long)l * A.n + j + p] = gT;
+                s_tau += active ? nan_to_num(dtau) : 0.0;
+                s_T += active ? nan_to_num(gT) : 0.0;
+            }
+            add(3 + l, s_tau);
+            add(3 + L + l, s_T);
+            terms(l, Gd);
+        };
+        auto down = [&](auto fast_tag, int l, vec v) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double pbkT = A.pbkT[l], depth = A.depth[l], rT = A.rT[l];
+            double E0 = 0.0;
+            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+            double s_tau = 0.0, s_T = 0.0, Gd[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+                double dB;
+                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
+                double G = 0.0, gT = 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double tr = exp_neg_budget(tau * A.rmu[k]);
+                    const double At = Ak[k][p] * tr;
+                    const double g = fmin(fmax(Ak[k][p] * B + I[k][p], -(At * Imax[k][p])), At * B);
+                    G = fma(A.wrmu[k], g, G);
+                    const double a1 = Ak[k][p] * (1.0 - tr);
+                    gT = fma(A.w[k], a1 * dB, gT);
+                    I[k][p] = I[k][p] + a1 * B;              // D_(l-1) = D_l + A_l (1 - t_l) B_l
+                    Ak[k][p] = At;                           // A_(l-1) = A_l t_l
+                }
+                const double dtau = tau * G;
+                Gd[p] = depth * G;
+                // (what walk 2 stored here, this thread stored)
+                if (active && A.ln_tau_spec) {
+                    double* o = A.ln_tau_spec + (long long)l * A.n + j + p;
+                    *o = *o + dtau;
+                }
+                if (active && A.T_spec) {
+                    double* o = A.T_spec + (long long)l * A.n + j + p;
+                    *o = *o + gT;
+                }
+                s_tau += active ? nan_to_num(dtau) : 0.0;
+                s_T += active ? nan_to_num(gT) : 0.0;
+            }
+            add(3 + l, s_tau);
+            add(3 + L + l, s_T);
+            terms(l, Gd);
+        };
+        auto walk = [&](auto fast_tag) {
+            // walk 1, downward: I_L = I_top or 0
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double It = A.I_top ? A.I_top[j + p] : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
+            }
+            vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+                first_down(fast_tag, l, cur);
+                cur = nxt;
+            }
+            // the surface: dF/dT_s = e sum_k W_k Ttot_k dBs/dT, dF/de = sum_k W_k Ttot_k (Is - R_k); then the state of walk 2
+            double s_Ts = 0.0, s_e = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+                double dBs = 0.0;
+                const double Is = A.I_surface ? A.I_surface[j + p]
+                                              : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
+                                                                         A.r_surface_T, &dBs);
+                const double edBs = e * dBs;
+                const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
+                const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
+                const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
+                const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
+                if (active && A.e_spec) A.e_spec[j + p] = de;
+                s_Ts += active ? nan_to_num(dTs) : 0.0;
+                s_e += active ? nan_to_num(de) : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double D = I[k][p];
+                    I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
+                    Imax[k][p] = I[k][p];
+                    Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
+                    Ck[k][p] = 1.0;
+                    Dp[k][p] = -D;
+                }
+            }
+            add(1, s_Ts);
+            add(2, s_e);
+            // walk 2, upward
+            cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+            for (int l = 0; l < L; ++l) {
+                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+                up(fast_tag, l, cur);
+                cur = nxt;
+            }
+            // F_top; then I becomes D = -I_top and A = 1
+            double s = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
+            }
+            add(0, s);
+            // walk 3, downward: K5d's
+            cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+                down(fast_tag, l, cur);
+                cur = nxt;
+            }
+        };
+        if constexpr (NP > 1) {
+            if (fast) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += blockDim.x)
+        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+}
+
+// Rays: K5f's kernel with K5g's surface in the path.  A marker (layer kRaySurfaceMarker) is part of the bundle's common
+// sequence, so the branch on it is uniform over the workgroup.  Forward: I <- e Is + (1 - e) I at a marker, as
+// ray_surface_kernel, Imax takes the result, and dI/de is carried along: S <- t S per segment, S <- (Is - I) + (1 - e) S at a
+// marker (the backward identity would divide by 1 - e); a ray from the surface starts with I = e Is and S = Is.  Backward: a
+// marker emits, D += A e Is, adds A e dBs/dT to the ray's row 0 (the first marker met stores, as a layer's rows are stored,
+// the source at the very end adds or stores) and then dims what lies before it, A <- A (1 - e).  Rows: [dT_source, de, K5f's].
+// With e == 1 and no marker every operation on I, Imax, D and A is K5f's.
+template <int NP, int RB, bool TERMS>
+__global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurfaceJacArgs* __restrict__ Ap, long long lo0,
+                                                                   long long n0, long long lo1, long long n1, int order_first) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    const RaySurfaceJacArgs& A = *Ap;
+    const char* blk = (const char*)Ap;
+    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
+    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
+    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
+    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
+    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
+    const long long* __restrict__ row_first = (const long long*)(blk + A.off_row_first);
+    // (idle lanes of the last workgroup work on a valid point and store nothing)
+    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
+    const bool active = q < n0 + n1;
+    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    double nu[NP], pa_n[NP], Is[NP], em[NP], I[RB][NP], Imax[RB][NP], Ak[RB][NP];     // (Ak: S = dI/de on the forward walk)
+    column_points<NP>(A, j, nu, pa_n);
+    const bool fast = fold_fast_path<NP>(A, nu, active);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+        em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+    }
+    int rid[RB], s0[RB];
+    bool surface[RB];
+    long long row0[RB];                                   // the ray's first row
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
+        s0[i] = ray_first[rid[i]];
+        surface[i] = source_kind[rid[i]] == 1;
+        row0[i] = row_first[rid[i]];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            I[i][p] = surface[i] ? surface_leaving(em[p], Is[p], 0.0) : 0.0;
+            Imax[i][p] = I[i][p];
+            Ak[i][p] = surface[i] ? Is[p] : 0.0;
+        }
+    }
+    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers and rows)
+    const int32_t* lay = seg_layer + s0[0];
+    const int32_t* slot = (const int32_t*)(blk + A.off_seg_slot) + s0[0];
+    const int32_t* term_row = (const int32_t*)(blk + A.off_term_row) + ((const int32_t*)(blk + A.off_ray_terms))[rid[0]];
+    const int crossed = ((const int32_t*)(blk + A.off_ray_crossed))[rid[0]];
+    auto put = [&](int i, long long row, int p, double v, bool store) {
+        double* o = A.jac + (row0[i] + row) * A.n + (j + p);
+        *o = store ? v : *o + v;
+    };
+    // e dB(nu, source_T)/dT at point p (0 when the source is a given spectrum)
+    auto source_dT = [&](int p) {
+        double dBs = 0.0;
+        if (!A.I_surface) fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
+        return em[p] * dBs;
+    };
+    // the nearest real segment at or after s / at or before s (ns / -1: none)
+    auto real_from = [&](int s) {
+        while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
+        return s;
+    };
+    auto real_back = [&](int s) {
+        while (s >= 0 && lay[s] == kRaySurfaceMarker) --s;
+        return s;
+    };
+    auto walk = [&](auto fast_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        // forward: ray_surface_kernel's walk, the running maximum and dI/de
+        int ahead = real_from(0);
+        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
+        for (int s = 0; s < ns; ++s) {
+            if (lay[s] == kRaySurfaceMarker) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        Ak[i][p] = (Is[p] - I[i][p]) + (1.0 - em[p]) * Ak[i][p];
+                        I[i][p] = surface_leaving(em[p], Is[p], I[i][p]);
+                        Imax[i][p] = fmax(Imax[i][p], I[i][p]);
+                    }
+                }
+                continue;
+            }
+            ahead = real_from(s + 1);
+            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
+            double len[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            transport_step<FAST, NP>(nu, pa_n, A.pbkT[lay[s]], cur, [&](int p, double kp, double B) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double tr = exp_neg_budget(kp * len[i]);
+                    I[i][p] = fold_update<FAST>(tr, I[i][p], B);
+                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
+                    Ak[i][p] = tr * Ak[i][p];
+                }
+            });
+            cur = nxt;
+        }
+        // the radiance and dI/de; then I becomes D = -I_final and A = 1
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                if (active && A.radiance) A.radiance[(long long)rid[i] * A.n + j + p] = I[i][p];
+                if (active) put(i, 1, p, Ak[i][p], true);
+                I[i][p] = -I[i][p];
+                Ak[i][p] = 1.0;
+            }
+        }
+        // backward
+        bool row0_stored = false;
+        int behind = real_back(ns - 1);
+        cur = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : (vec)(0.0);
+        for (int s = ns - 1; s >= 0; --s) {
+            if (lay[s] == kRaySurfaceMarker) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const double edBs = A.I_surface ? 0.0 : source_dT(p);
+                    const double eIs = em[p] * Is[p];
+#pragma unroll
+                    for (int i = 0; i < RB; ++i) {
+                        if (active && !A.I_surface) put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
+                        I[i][p] = I[i][p] + Ak[i][p] * eIs;
+                        Ak[i][p] = Ak[i][p] * (1.0 - em[p]);
+                    }
+                }
+                if (!A.I_surface) row0_stored = true;
+                continue;
+            }
+            behind = real_back(s - 1);
+            const vec nxt = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : cur;
+            const int l = lay[s];
+            const bool store = (slot[s] & kRayRowStore) != 0;
+            const long long row_tau = 2 + (slot[s] & (kRayRowStore - 1));
+            const long long row_T = row_tau + crossed;
+            const double pbkT = A.pbkT[l], rT = A.rT[l];
+            double len[RB], g[RB][NP];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            double E0 = 0.0;
+            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double dB;
+                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double tau = cur[p] * len[i];
+                    const double tr = exp_neg_budget(tau);
+                    const double At = Ak[i][p] * tr;
+                    g[i][p] = fmin(fmax(Ak[i][p] * B + I[i][p], -(At * Imax[i][p])), At * B);
+                    const double a1 = Ak[i][p] * (1.0 - tr);
+                    if (active) {
+                        put(i, row_tau, p, tau * g[i][p], store);
+                        put(i, row_T, p, a1 * dB, store);
+                    }
+                    I[i][p] = I[i][p] + a1 * B;              // D_(s-1) = D_s + A_s (1 - t_s) B_s
+                    Ak[i][p] = At;                           // A_(s-1) = A_s t_s
+                }
+            }
+            if constexpr (TERMS) for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
+                const vec km = load_points<NP>(A.term_k[t], j);
+                const long long row = term_row[t];
+                if (active) {
+#pragma unroll
+                    for (int i = 0; i < RB; ++i) {
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) put(i, row, p, (km[p] * len[i]) * g[i][p], store);
+                    }
+                }
+            }
+            cur = nxt;
+        }
+        // the source's part of dI/dT_source: A_0 e dBs/dT for a ray from the surface at source_T
+        if (active) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double edBs = source_dT(p);
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double v = surface[i] && !A.I_surface ? Ak[i][p] * edBs : 0.0;
+                    if (!row0_stored || surface[i]) put(i, 0, p, v, !row0_stored);
+                }
+            }
+        }
+    };
+    if constexpr (NP > 1) {
+        if (fast) walk(std::true_type{});
+        else walk(std::false_type{});
+    } else {
+        walk(std::false_type{});
+    }
+}
+
+// ----------------------------------------------------------------------------------------
 // K7: line survey (pyradClasses.py:409-428): S added into the bin of each line, in line order
 // ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void line_survey_kernel(const double* __restrict__ nu, const double* __restrict__ sw,
@@ -4833,6 +5268,50 @@ void launch_ray_jacobian(const RayJacArgs* d_args, long long n, int n_rays, int 
     }
     if (nt > 0)
         hipLaunchKernelGGL((ray_jacobian_kernel<1, 1, true>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+}
+
+// K5h: K5d's launch.  Points per thread: K5d's 4 for one and two angles (its groups of points, so that a black surface
+// gives K5d's bits), 2 beyond - walk 2 keeps six values per angle and point alive (DESIGN.md "K5h")
+template <int NA> constexpr int surface_jacobian_np() { return NA <= 2 ? 4 : 2; }
+
+int surface_jacobian_points(int n_angles) {
+    int np = 1;
+    with_angles(n_angles, [&](auto na) { np = surface_jacobian_np<decltype(na)::value>(); });
+    return np;
+}
+
+void launch_surface_jacobian(const SurfaceJacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first,
+                             long long count, double* partial, double* jac, hipStream_t s) {
+    with_angles(n_angles, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        constexpr int NP = surface_jacobian_np<NA>();
+        launch_column_band<NP>(surface_jacobian_kernel<NP, NA>, surface_jacobian_kernel<1, NA>, d_args,
+                               3 + 2 * n_layers + n_terms, first, count, partial, jac, s);
+    });
+}
+
+// K5h: launch_ray_jacobian's split of the points and of the rays for the kernel that knows surface markers
+void launch_ray_surface_jacobian(const RaySurfaceJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
+                                 hipStream_t s) {
+    constexpr int NP = 4;
+    if (n <= 0 || n_rays <= 0) return;
+    const long long q1 = n & ~(long long)(NP - 1);
+    const long long nt = n - q1;
+    const int n_single = n_rays - kRayBundle * n_bundles;
+    if (q1 > 0) {
+        const dim3 grid((unsigned)((q1 / NP + 255) / 256), n_bundles);
+        if (n_bundles > 0 && n_terms > 0)
+            hipLaunchKernelGGL((ray_surface_jacobian_kernel<NP, kRayBundle, true>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL,
+                               0LL, 0);
+        else if (n_bundles > 0)
+            hipLaunchKernelGGL((ray_surface_jacobian_kernel<NP, kRayBundle, false>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL,
+                               0LL, 0);
+        if (n_single > 0)
+            hipLaunchKernelGGL((ray_surface_jacobian_kernel<NP, 1, true>), dim3(grid.x, n_single), dim3(256), 0, s, d_args, 0LL,
+                               q1, 0LL, 0LL, kRayBundle * n_bundles);
+    }
+    if (nt > 0)
+        hipLaunchKernelGGL((ray_surface_jacobian_kernel<1, 1, true>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
 }
 
 void launch_line_survey(const double* nu, const double* sw, int n_lines, double range_min, double resolution,

@@ -1487,10 +1487,13 @@ class Jacobians:
     ``mu``, ``weight``: the angle set; ``temperatureSpectrum`` / ``opticalDepthSpectrum``: (L, n) spectral dF/dT_l and
     dF/d ln tau_l (W m^-2 per cm^-1, 0 outside every band) when asked for, else None (the temperature spectrum is the Planck
     part whatever ``temperature`` was).  ``temperatureAbsorption``: (L,) the absorption part of dF/dT_l, through dk_l/dT, and
-    ``temperatureFull`` = temperature + temperatureAbsorption: both None unless temperature="full" was asked for."""
+    ``temperatureFull`` = temperature + temperatureAbsorption: both None unless temperature="full" was asked for.
+    ``emissivity``: dF/de per band, W m^-2 per unit emissivity, over a surface with an emissivity (None over the black
+    surface); ``emissivitySpectrum``: (n,) the spectral dF/de when spectra were asked for as well, else None."""
 
     def __init__(self, olr, surfaceTemperature, temperature, opticalDepth, molecules, moleculeNames, mu, weight,
-                 temperatureSpectrum=None, opticalDepthSpectrum=None, temperatureAbsorption=None):
+                 temperatureSpectrum=None, opticalDepthSpectrum=None, temperatureAbsorption=None, emissivity=None,
+                 emissivitySpectrum=None):
         self.olr = olr
         self.surfaceTemperature = surfaceTemperature
         self.temperature = temperature
@@ -1503,6 +1506,8 @@ class Jacobians:
         self.opticalDepthSpectrum = opticalDepthSpectrum
         self.temperatureAbsorption = temperatureAbsorption
         self.temperatureFull = None if temperatureAbsorption is None else temperature + temperatureAbsorption
+        self.emissivity = emissivity
+        self.emissivitySpectrum = emissivitySpectrum
 
     def __repr__(self):
         return "Jacobians(layers=%d, angles=%d, olr=%s)" % (self.opticalDepth.shape[-1], len(self.mu), self.olr)
@@ -1956,10 +1961,11 @@ class PathJacobians:
     = temperature + temperatureAbsorption, both None unless temperature="full" was asked for; ``paths``: the paths, in
     order.  Layers a path does not cross hold exact zeros.  With an instrument also ``brightnessTemperature`` (R, C), the
     inverse Planck of the channel radiance at the centre, and ``brightnessTemperatureJacobian`` (R, L, C) = temperature /
-    (dB/dT at the centre and the channel's brightness temperature), as Observation forms it; else both None."""
+    (dB/dT at the centre and the channel's brightness temperature), as Observation forms it; else both None.
+    ``emissivity``: (R, X) dI/de per unit emissivity over a surface with an emissivity, None over the black surface."""
 
     def __init__(self, wavenumber, radiance, temperature, opticalDepth, surfaceTemperature, molecules, moleculeNames, paths,
-                 temperatureAbsorption=None, channels=False):
+                 temperatureAbsorption=None, channels=False, emissivity=None):
         self.wavenumber = wavenumber
         self.radiance = radiance
         self.temperature = temperature
@@ -1970,6 +1976,7 @@ class PathJacobians:
         self.temperatureAbsorption = temperatureAbsorption
         self.temperatureFull = None if temperatureAbsorption is None else temperature + temperatureAbsorption
         self.paths = paths
+        self.emissivity = emissivity
         self.brightnessTemperature = self.brightnessTemperatureJacobian = None
         if channels:
             self.brightnessTemperature = brightnessTemperature(wavenumber, radiance)
@@ -1987,15 +1994,18 @@ class Observation:
     units of transmission(); ``brightnessTemperature``: its inverse Planck at the centre, K; ``mu``: the viewing cosine.
     With jacobians=True (else None), (L, C) each: ``temperatureJacobian`` dR_c/dT_l (Planck part only, as jacobians()
     documents), ``opticalDepthJacobian`` dR_c/d ln tau_l and ``brightnessTemperatureJacobian`` = temperatureJacobian /
-    (dB/dT at the centre and the channel's brightness temperature)."""
+    (dB/dT at the centre and the channel's brightness temperature); over a surface with an emissivity also
+    ``emissivityJacobian`` (C,) dR_c/de, else None."""
 
-    def __init__(self, wavenumber, radiance, mu, temperatureJacobian=None, opticalDepthJacobian=None):
+    def __init__(self, wavenumber, radiance, mu, temperatureJacobian=None, opticalDepthJacobian=None,
+                 emissivityJacobian=None):
         self.wavenumber = wavenumber
         self.radiance = radiance
         self.brightnessTemperature = brightnessTemperature(wavenumber, radiance)
         self.mu = mu
         self.temperatureJacobian = temperatureJacobian
         self.opticalDepthJacobian = opticalDepthJacobian
+        self.emissivityJacobian = emissivityJacobian
         self.brightnessTemperatureJacobian = None
         if temperatureJacobian is not None:
             with np.errstate(divide='ignore', invalid='ignore'):
@@ -2182,7 +2192,7 @@ class Atmosphere(list):
                       upSurfaceSpectrum=up_surface.download(n) if up_surface is not None else None)
 
     def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False,
-                  temperature="planck"):
+                  temperature="planck", emissivity=None, reflection="lambertian", topSpectrum=None):
         """Analytic sensitivities of the upward flux at the top (beyond the reference), in one pass over the resident
         absorption coefficients.
 
@@ -2208,12 +2218,36 @@ class Atmosphere(list):
         and re-used while that molecule's inputs stand; False skips them).  ``spectra``: also the spectral dF/dT_l and
         dF/d ln tau_l, (L, n) each.  Returns a Jacobians.  The layers' absorption coefficients are the ones fluxes() and
         transmission() keep resident: after either nothing is accumulated again.  No other result of the model changes.
-        Everything is validated (ValueError) before the device is touched."""
+        Everything is validated (ValueError) before the device is touched.
+
+        ``emissivity``: None, the black surface above, or the surface's emissivity e as fluxes() takes it, with ``reflection``
+        and ``topSpectrum`` as there: the derivatives of fluxes(emissivity=..., reflection=..., topSpectrum=...).up at the top
+        (lbl_column_jacobian_surface_dev).  With Id_(l+1)k the downward radiance entering layer l from above, D_k = Id_0k,
+        R_k and Iu_0k = e Is + (1 - e) R_k as fluxes() defines them, Iu_lk the upward radiances from there, C_lk =
+        prod_{i<l} t_ik, Ttot_k = prod_i t_ik and Q_k = (1 - e) W_k (sum_k' W_k' Ttot_k') / sum_k W_k ("lambertian") or
+        (1 - e) W_k Ttot_k ("specular"):
+            gu_lk = A_lk t_lk (B_l - Iu_lk)        gd_lk = C_lk t_lk (B_l - Id_(l+1)k)      (the leg seen through the surface)
+            dF/d ln tau_l     = sum_k (tau_l / mu_k) (W_k gu_lk + Q_k gd_lk)                 molecules and dk/dT likewise
+            dF/dT_l  (Planck) = sum_k (W_k A_lk + Q_k C_lk) (1 - t_lk) dB_l/dT
+            dF/dT_s           = e sum_k W_k Ttot_k dB(nu_j, T_s)/dT
+            dF/de             = sum_k W_k Ttot_k (Is - R_k)                                  Jacobians.emissivity
+        (an emissivity given per grid point or as a table moves as a whole: dF/de is the derivative by one number added to
+        it everywhere; Jacobians.emissivitySpectrum has it per grid point).  With emissivity 1 and one or two angles every
+        value but dF/de is the black surface's bit for bit.  ``topSpectrum`` without an emissivity is a ValueError: the
+        black surface's outgoing flux does not depend on it."""
         if temperature not in ("planck", "full"):
             raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
             surfaceSpectrum, surfaceTemperature, angles, bands)
         first = layers[0]
+        refl = _surface_reflection(reflection)
+        if emissivity is None:
+            if topSpectrum is not None:
+                raise ValueError("topSpectrum: the outgoing flux over a black surface does not depend on it (give emissivity)")
+        else:
+            topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
+            emissivity = _surface_emissivity(emissivity, first.xAxis)
+            _weight_sum(weight)
         names = [[m.name for m in L] for L in layers]
         full = temperature == "full"
         n_terms = (sum(len(L) for L in layers) if molecules else 0) + (len(layers) if full else 0)
@@ -2235,36 +2269,51 @@ class Atmosphere(list):
         if full:                 # dk_l/dT as one more term of layer l: the term sums are linear in the term, whatever its sign
             term_bufs = term_bufs + [L._abs_coef_dT()[0] for L in layers]
             term_layer = term_layer + list(range(nl))
-        nv = 2 + 2 * nl + len(term_bufs)
+        h = 2 if emissivity is None else 3           # the values of a band ahead of the layers': F, dF/dT_s and dF/de
+        nv = h + 2 * nl + len(term_bufs)
         out = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, nb * nv))
         I_surface = out.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
         jac = out.buf(ctx, "jac")
-        ln_tau_spec = T_spec = None
+        ln_tau_spec = T_spec = e_spec = None
         if spectra:
             sp = _kept_state(self, "_jacobian_spec").reserve(ctx, nl * n)
             ln_tau_spec, T_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T")
-        ctx.column_jacobian_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
-                                mu, weight, band_first, band_count, jac, I_surface=I_surface,
-                                surface_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs, term_layer=term_layer,
-                                ln_tau_spectra=ln_tau_spec, T_spectra=T_spec)
+        if emissivity is None:
+            ctx.column_jacobian_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
+                                    mu, weight, band_first, band_count, jac, I_surface=I_surface,
+                                    surface_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs, term_layer=term_layer,
+                                    ln_tau_spectra=ln_tau_spec, T_spectra=T_spec)
+        else:
+            sst = _kept_state(self, "_jacobian_surface").reserve(ctx, n)
+            if not isinstance(emissivity, float):
+                emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
+            I_top = sst.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
+            e_spec = sst.buf(ctx, "e_spec") if spectra else None
+            ctx.column_jacobian_surface_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin,
+                                            first.rangeMax, n, mu, weight, band_first, band_count, jac, emissivity,
+                                            reflection=refl, I_surface=I_surface, surface_T=float(surfaceTemperature or 0.0),
+                                            I_top=I_top, term_abs_coef=term_bufs, term_layer=term_layer,
+                                            ln_tau_spectra=ln_tau_spec, T_spectra=T_spec, e_spectrum=e_spec)
         v = jac.download(nb * nv).reshape(nb, nv) * res
         olr, dTs = v[:, 0], v[:, 1]
-        dtau, dT = v[:, 2:2 + nl], v[:, 2 + nl:2 + 2 * nl]
+        dtau, dT = v[:, h:h + nl], v[:, h + nl:h + 2 * nl]
         mol = None
         if molecules:
-            mol, o = [], 2 + 2 * nl
+            mol, o = [], h + 2 * nl
             for L in layers:
                 mol.append(v[:, o:o + len(L)])
                 o += len(L)
         olr, dTs, dtau, dT = _band_values(bands, [olr, dTs, dtau, dT])
         mol = _band_values(bands, mol) if mol is not None else None
-        dT_abs = _band_values(bands, [v[:, 2 + 2 * nl + n_mol_terms:]])[0] if full else None
+        dT_abs = _band_values(bands, [v[:, h + 2 * nl + n_mol_terms:]])[0] if full else None
         return Jacobians(olr, dTs if surfaceSpectrum is None else None, dT, dtau, mol, names, mu, weight,
                          temperatureSpectrum=T_spec.download(nl * n).reshape(nl, n) if spectra else None,
                          opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None,
-                         temperatureAbsorption=dT_abs)
+                         temperatureAbsorption=dT_abs,
+                         emissivity=_band_values(bands, [v[:, 2]])[0] if emissivity is not None else None,
+                         emissivitySpectrum=e_spec.download(n) if e_spec is not None else None)
 
-    def observe(self, instrument, surfaceTemperature=None, surfaceSpectrum=None, mu=1.0, jacobians=False):
+    def observe(self, instrument, surfaceTemperature=None, surfaceSpectrum=None, mu=1.0, jacobians=False, emissivity=None):
         """What an instrument above the column sees at viewing cosine ``mu`` (beyond the reference): the upward radiance at
         the top (fluxes() with the angle set [(mu, 1.0)]: column, layer order, grid and surface source as there) convolved
         onto the channels of ``instrument`` on the device, beside the resident spectrum; only the channel values come down.
@@ -2272,7 +2321,13 @@ class Atmosphere(list):
         dI/dT_l and dI/d ln tau_l) convolved in the same call.  Returns an Observation.  With mu = 1 the radiance is
         convolve(instrument, transmission(...)) bit for bit wherever fluxes() documents that identity.  The absorption
         coefficients are the resident ones: after transmission() or fluxes() nothing is accumulated again.  Everything is
-        validated (ValueError) before the device is touched."""
+        validated (ValueError) before the device is touched.
+
+        ``emissivity``: None, the black surface above, or the surface's emissivity e as fluxes() takes it.  The surface then
+        emits e Is and reflects, specularly at ``mu``, the downward radiance of the column under cold space (with the single
+        viewing angle the Lambertian and the specular reflection of fluxes() are one expression): the radiance is
+        fluxes(emissivity=e, reflection="specular", angles=[(mu, 1.0)])'s upward spectrum at the top, the weighting functions
+        jacobians(emissivity=e, ...)'s for that angle, and Observation.emissivityJacobian their dR_c/de."""
         if not isinstance(instrument, Instrument):
             raise ValueError("instrument: an Instrument, not %r" % (instrument,))
         try:
@@ -2284,11 +2339,13 @@ class Atmosphere(list):
         layers, n, mu_k, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
             surfaceSpectrum, surfaceTemperature, angle, None)
         first = layers[0]
+        if emissivity is not None:
+            emissivity = _surface_emissivity(emissivity, first.xAxis)
         support = instrument.support(first.rangeMin, first.rangeMax, n)
         nl, C = len(layers), len(instrument)
-        n_rows = 1 + 2 * nl if jacobians else 1
+        n_rows = (1 + 2 * nl + (emissivity is not None)) if jacobians else 1
         if n_rows > nat.limit("ils_rows"):
-            raise ValueError("jacobians: %d layers, at most %d" % (nl, (nat.limit("ils_rows") - 1) // 2))
+            raise ValueError("jacobians: %d layers, at most %d" % (nl, (nat.limit("ils_rows") - 1 - (emissivity is not None)) // 2))
         ctx = _ctx()
         if jacobians and ctx.option("sweep_ieee_divisions"):
             raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
@@ -2299,23 +2356,41 @@ class Atmosphere(list):
         fst.reserve(ctx, max(n, 2 * (nl + 1)))
         I_surface = fst.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
         up_top = fst.buf(ctx, "up_top")
-        ctx.column_flux_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first, band_count,
-                            fst.buf(ctx, "level"), I_surface=I_surface, surface_T=surface_T, up_top=up_top)
+        if emissivity is None:
+            ctx.column_flux_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first, band_count,
+                                fst.buf(ctx, "level"), I_surface=I_surface, surface_T=surface_T, up_top=up_top)
+        else:
+            if not isinstance(emissivity, float):
+                emissivity = fst.buf(ctx, "emissivity").upload(emissivity)
+            ctx.column_flux_surface_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
+                                        band_count, fst.buf(ctx, "level"), emissivity, reflection=REFLECTIONS.index("specular"),
+                                        I_surface=I_surface, surface_T=surface_T, up_top=up_top)
         rows = [(up_top, 0)]
         if jacobians:
-            jst = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, 2 + 2 * nl))
+            jst = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, 3 + 2 * nl))
             sp = _kept_state(self, "_jacobian_spec").reserve(ctx, nl * n)
             ln_tau_spec, T_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T")
-            ctx.column_jacobian_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first, band_count,
-                                    jst.buf(ctx, "jac"), I_surface=I_surface, surface_T=surface_T,
-                                    ln_tau_spectra=ln_tau_spec, T_spectra=T_spec)
+            if emissivity is None:
+                ctx.column_jacobian_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
+                                        band_count, jst.buf(ctx, "jac"), I_surface=I_surface, surface_T=surface_T,
+                                        ln_tau_spectra=ln_tau_spec, T_spectra=T_spec)
+            else:
+                e_spec = _kept_state(self, "_jacobian_surface").reserve(ctx, n).buf(ctx, "e_spec")
+                ctx.column_jacobian_surface_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
+                                                band_count, jst.buf(ctx, "jac"), emissivity,
+                                                reflection=REFLECTIONS.index("specular"), I_surface=I_surface,
+                                                surface_T=surface_T, ln_tau_spectra=ln_tau_spec, T_spectra=T_spec,
+                                                e_spectrum=e_spec)
             rows += [(T_spec, l * n) for l in range(nl)] + [(ln_tau_spec, l * n) for l in range(nl)]
+            if emissivity is not None:
+                rows.append((e_spec, 0))
         out = _kept_state(self, "_observe_out").reserve(ctx, n_rows * C).buf(ctx, "out")
         _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, rows, out)
         v = out.download(n_rows * C).reshape(n_rows, C)
         return Observation(instrument.centres.copy(), v[0].copy(), float(mu_k[0]),
                            temperatureJacobian=v[1:1 + nl].copy() if jacobians else None,
-                           opticalDepthJacobian=v[1 + nl:].copy() if jacobians else None)
+                           opticalDepthJacobian=v[1 + nl:1 + 2 * nl].copy() if jacobians else None,
+                           emissivityJacobian=v[1 + 2 * nl].copy() if jacobians and emissivity is not None else None)
 
     @staticmethod
     def _path_mu(mu):
@@ -2501,7 +2576,7 @@ class Atmosphere(list):
         return PathRadiance(instrument.centres.copy(), v[:R].copy(), v[R:].copy() if transmittance else None, plist)
 
     def pathJacobians(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, molecules=False,
-                      temperature="planck"):
+                      temperature="planck", emissivity=None, reflection="lambertian"):
         """The weighting functions of radiance(): analytic derivatives of the radiance arriving along ``paths`` - one Path or
         a list of up to 512 - per path and grid point (beyond the reference), in one pass over the resident absorption
         coefficients per chunk of paths.  Paths, sources, layers, grid and units as radiance() has them.  For a path with
@@ -2521,14 +2596,35 @@ class Atmosphere(list):
         convolution, one path at least, so the device work space never exceeds max(512, one path's rows) x n doubles
         whatever the number of paths.  The absorption coefficients are the resident ones: after transmission() nothing is
         accumulated again.  No other result of the model changes.  Everything is validated (ValueError) before the device
-        is touched."""
+        is touched.
+
+        ``emissivity``: None, the black surface above, or the surface's emissivity e as radiance() takes it: the weighting
+        functions of radiance(paths, emissivity=e, reflection=...), whose radiance comes back bit for bit
+        (lbl_ray_jacobian_surface_dev, one more row per path).  Paths with a bounce are then accepted (without an
+        emissivity they are refused).  With "element" for a segment or the bounce, and A the product over every element
+        after one of t_s for segments and 1 - e for the bounce (A_0: over the whole path):
+            dI/d ln tau_l, dI/dT_l, molecules: the sums above with that A
+            dI/dT_s  = e dB(nu_j, T_s)/dT (A at the bounce + A_0 for a path from the surface)
+            dI/de    = A at the bounce (Is - the radiance arriving there) + A_0 Is for a path from the surface
+        PathJacobians.emissivity holds dI/de.  A path that STARTS at the surface carries, under reflection="lambertian", the
+        diffusely reflected sky, which depends on every layer of the column; that derivative is not built, and holding the
+        sky fixed would disagree with differences of radiance(): such a path is refused (ValueError) with an emissivity
+        and "lambertian" - take reflection="specular", under which it starts with e Is alone."""
         if temperature not in ("planck", "full"):
             raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         plist, layers, n, surfaceSpectrum = self._path_checks(paths, surfaceTemperature, surfaceSpectrum)
-        if any(p.bounce is not None for p in plist):
-            raise ValueError("paths: a path with a bounce has no weighting functions (radiance() with an emissivity computes it)")
         R, nl = len(plist), len(layers)
         first = layers[0]
+        refl = _surface_reflection(reflection)
+        if emissivity is None:
+            if any(p.bounce is not None for p in plist):
+                raise ValueError("paths: a path with a bounce needs a surface that reflects: give emissivity")
+        else:
+            emissivity = _surface_emissivity(emissivity, first.xAxis)
+            if refl == 0 and any(p.source == "surface" for p in plist):
+                raise ValueError("reflection: a path that starts at the surface has no weighting functions under \"lambertian\" "
+                                 "(the diffusely reflected sky is not differentiated); take reflection=\"specular\"")
+        h = 1 if emissivity is None else 2            # a path's rows ahead of its layers': dI/dT_s and dI/de
         full = temperature == "full"
         names = [[m.name for m in L] for L in layers]
         n_mol_terms = sum(len(L) for L in layers) if molecules else 0
@@ -2549,7 +2645,7 @@ class Atmosphere(list):
         term_layer = ([l for l, L in enumerate(layers) for _ in L] if molecules else []) + (list(range(nl)) if full else [])
         crossed = [sorted(set(p.layers)) for p in plist]
         ray_terms = [[t for t, l in enumerate(term_layer) if l in set(c)] for c in crossed]
-        ray_rows = [1 + 2 * len(c) + len(t) for c, t in zip(crossed, ray_terms)]
+        ray_rows = [h + 2 * len(c) + len(t) for c, t in zip(crossed, ray_terms)]
         block = nat.limit("ils_rows")
         chunks, r = [], 0
         while r < R:
@@ -2569,6 +2665,8 @@ class Atmosphere(list):
         I_source = None
         if surfaceSpectrum is not None:
             I_source = _kept_state(self, "_path_source").reserve(ctx, n).buf(ctx, "I_source").upload(surfaceSpectrum)
+        if emissivity is not None and not isinstance(emissivity, float):
+            emissivity = _kept_state(self, "_path_surface").reserve(ctx, max(n, 2 * (nl + 1))).buf(ctx, "emissivity").upload(emissivity)
         jac = _kept_state(self, "_path_jacobian_rows").reserve(ctx, max(c[2] for c in chunks) * n).buf(ctx, "jac")
         rad = _kept_state(self, "_path_jacobian_radiance").reserve(ctx, max(e - r for r, e, _ in chunks) * n).buf(ctx, "radiance")
         X = n if instrument is None else len(instrument)
@@ -2582,10 +2680,18 @@ class Atmosphere(list):
         row0 = 0
         for r, e, rows in chunks:
             sub = plist[r:e]
-            ctx.ray_jacobian_dev(kbufs, T, first.rangeMin, first.rangeMax, n, np.cumsum([0] + [len(p) for p in sub]),
-                                 [l for p in sub for l in p.layers], [x for p in sub for x in p.lengths], kinds[r:e], jac,
-                                 I_source=I_source, source_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs,
-                                 term_layer=term_layer, radiance=rad)
+            if emissivity is None:
+                ctx.ray_jacobian_dev(kbufs, T, first.rangeMin, first.rangeMax, n, np.cumsum([0] + [len(p) for p in sub]),
+                                     [l for p in sub for l in p.layers], [x for p in sub for x in p.lengths], kinds[r:e], jac,
+                                     I_source=I_source, source_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs,
+                                     term_layer=term_layer, radiance=rad)
+            else:
+                segs = [p._segments() for p in sub]
+                ctx.ray_jacobian_surface_dev(kbufs, T, first.rangeMin, first.rangeMax, n,
+                                             np.cumsum([0] + [len(lay) for lay, _ in segs]), [l for lay, _ in segs for l in lay],
+                                             [x for _, lens in segs for x in lens], kinds[r:e], jac, emissivity,
+                                             I_source=I_source, source_T=float(surfaceTemperature or 0.0),
+                                             term_abs_coef=term_bufs, term_layer=term_layer, radiance=rad)
             if instrument is None:
                 I[r:e] = rad.download((e - r) * n).reshape(e - r, n)
                 J[row0:row0 + rows] = jac.download(rows * n).reshape(rows, n)
@@ -2609,14 +2715,17 @@ class Atmosphere(list):
         # rows -> (R, L, X) arrays: zeros where a path does not cross a layer
         dtau, dT = np.zeros((R, nl, X)), np.zeros((R, nl, X))
         dTs = np.zeros((R, X))
+        de = np.zeros((R, X)) if emissivity is not None else None
         terms = np.zeros((R, n_terms, X))
         row0 = 0
         for r in range(R):
             c = len(crossed[r])
             dTs[r] = J[row0]
-            dtau[r, crossed[r]] = J[row0 + 1:row0 + 1 + c]
-            dT[r, crossed[r]] = J[row0 + 1 + c:row0 + 1 + 2 * c]
-            terms[r, ray_terms[r]] = J[row0 + 1 + 2 * c:row0 + ray_rows[r]]
+            if de is not None:
+                de[r] = J[row0 + 1]
+            dtau[r, crossed[r]] = J[row0 + h:row0 + h + c]
+            dT[r, crossed[r]] = J[row0 + h + c:row0 + h + 2 * c]
+            terms[r, ray_terms[r]] = J[row0 + h + 2 * c:row0 + ray_rows[r]]
             row0 += ray_rows[r]
         mol = None
         if molecules:
@@ -2627,7 +2736,7 @@ class Atmosphere(list):
         return PathJacobians(first.xAxis if instrument is None else instrument.centres.copy(), I, dT, dtau,
                              dTs if surfaceSpectrum is None else None, mol, names, plist,
                              temperatureAbsorption=terms[:, n_mol_terms:].copy() if full else None,
-                             channels=instrument is not None)
+                             channels=instrument is not None, emissivity=de)
 
     def kDistribution(self, bands=None, g=16, reference=None, planck=False, spectra=False):
         """k-distributions of the column's bands (beyond the reference): every layer's absorption coefficient (getAbsCoef)
