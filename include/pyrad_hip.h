@@ -568,6 +568,61 @@ int lbl_ray_radiance_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* 
                                  lbl_buffer* surface_down /* may be NULL */, double surface_down_norm,
                                  lbl_buffer* radiance, lbl_buffer* transmittance /* may be NULL */);
 
+/* ---- linear-in-optical-depth Planck source (beyond the reference; ABI 5, backward compatible) ---------------------------
+ * pyrad_amd.model.Atmosphere.fluxes and radiance with planck="linear": the Planck function is not one value per layer but
+ * runs linearly in optical depth between two temperatures, which removes the first-order error of the isothermal layer on a
+ * column with a lapse rate.  A ray crosses a piece of a layer with optical depth tau along the ray; Ta is the temperature
+ * where the light enters the piece and Tb where it leaves, Ba = B(nu, Ta), Bb = B(nu, Tb):
+ *     t = exp(-tau)
+ *     I <- t I + (1 - t) Ba + g(tau) (Bb - Ba)          Ttot <- Ttot t
+ *     g(tau) = 1 - (1 - t) / tau      (-> tau/2 as tau -> 0, -> 1 as tau -> inf)
+ * The first two terms are the isothermal step of lbl_column_flux_dev with its rounding, the third is added afterwards: with
+ * Ta == Tb it is g * 0 and the step returns the isothermal one's bits.  g (pyrad_amd/csrc/lbl_linear_source.h, one text for
+ * the device and the host) is the expression itself for tau >= tau_0 = 0.25 and the Taylor series tau (1/2 - tau (1/6 - tau
+ * (1/24 - ...))) with 11 terms below: truncation below 2^-53 relative, and 2 / tau_0^2 = 32 times a one-ulp error of t above.
+ * g(0) = 0 exactly, g(+inf) = 1, NaN stays NaN.
+ *
+ * lbl_column_flux_linear_dev: lbl_column_flux_surface_dev's arguments and semantics - the downward walk first, the surface
+ * with emissivity and reflection, the upward walk, level_flux, the spectra - with T replaced by T_edge, two temperatures per
+ * layer: T_edge[2 l] at its bottom edge, T_edge[2 l + 1] at its top edge.  Going up Ta is the bottom edge and Tb the top
+ * edge, going down the other way round; tau = k_l depth_l / mu_k.  The surface source stays surface_T or I_surface: a skin
+ * temperature may differ from the lowest edge.  A black surface is emissivity NULL with emissivity_all 1.
+ *
+ * lbl_ray_radiance_linear_dev: lbl_ray_radiance_surface_dev's arguments and semantics - markers, the diffuse start term -
+ * with T replaced by seg_T, two temperatures per segment in the light's direction of travel: seg_T[2 s] where it enters
+ * segment s, seg_T[2 s + 1] where it leaves.  A marker's pair is ignored.  Rays are carried together where they share their
+ * layer sequence AND their segment temperatures (nadir paths at different cosines still do); a ray's bits do not depend on
+ * the other rays of the call.
+ *
+ * The one-exp-per-thread Planck path is chosen as for the fold, with the smallest and largest of ALL edge (segment)
+ * temperatures of the call; each of a step's two Planck values then comes from one exp per thread.
+ * Identities: with both temperatures of every layer or segment equal to the layer's temperature T_l, every result is the
+ * surface variant's bit for bit, and hence the black-surface call's at e == 1.  The ray down through the layers L-1 .. 0 over
+ * depth_l, a marker, and up through 0 .. L-1, each segment with its layer's edge temperatures in the direction of travel,
+ * returns lbl_column_flux_linear_dev's up_top for reflection 1 and the angle set {(1, 1.0)}, bit for bit.
+ * LBL_ERR_BAD_ARG: everything the surface variant refuses; an edge or segment temperature that is not finite and > 0 (a
+ * marker's pair excepted); "sweep_ieee_divisions" 1.  Everything is checked before anything is enqueued; the host arrays are
+ * copied and not retained.  Stream-ordered; nothing is synchronised. */
+int lbl_column_flux_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
+                               const double* T_edge /* 2 n_layers: bottom, top of layer l */, const double* depth,
+                               double range_min, double range_max, int64_t n,
+                               lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                               int n_angles, const double* mu, const double* weight,
+                               int n_bands, const int64_t* band_first, const int64_t* band_count,
+                               lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                               int reflection /* 0 Lambertian, 1 specular */,
+                               lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface,
+                               lbl_buffer* up_surface /* may be NULL */);
+int lbl_ray_radiance_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
+                                const double* seg_T /* 2 per segment: entry, exit; a marker's pair is ignored */,
+                                double range_min, double range_max, int64_t n,
+                                int n_rays, const int32_t* ray_first,
+                                const int32_t* seg_layer /* -1: surface marker */, const double* seg_length,
+                                const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                                lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                lbl_buffer* surface_down /* may be NULL */, double surface_down_norm,
+                                lbl_buffer* radiance, lbl_buffer* transmittance /* may be NULL */);
+
 /* ---- ray-path Jacobians (beyond the reference; ABI 5, backward compatible) --------------------------------------------
  * pyrad_amd.model.Atmosphere.pathJacobians: the weighting functions of the radiance lbl_ray_radiance_dev computes - its
  * analytic derivatives to every crossed layer's optical depth and (Planck) temperature, to the source temperature and to any

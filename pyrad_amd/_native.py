@@ -118,6 +118,12 @@ SIGNATURES = {
     "lbl_ray_radiance_surface_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P,
                                                C.c_double, _P, C.c_double, _P, C.c_double, _P, _P]),
+    "lbl_column_flux_linear_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, _P,
+                                             C.c_double, _P, C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64), _P, C.c_double, C.c_int, _P, _P, _P, _P]),
+    "lbl_ray_radiance_linear_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P,
+                                              C.c_double, _P, C.c_double, _P, C.c_double, _P, _P]),
     "lbl_ray_jacobian_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lbl_ray_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
@@ -639,6 +645,21 @@ class Context:
             *self._emissivity_args(emissivity), int(reflection), _hb(level_flux), _hb(up_top), _hb(down_surface),
             _hb(up_surface)))
 
+    def column_flux_linear_dev(self, abs_coef, edge_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
+                               level_flux, emissivity=1.0, reflection=0, I_surface=None, surface_T=0.0, I_top=None, up_top=None,
+                               down_surface=None, up_surface=None):
+        """Level fluxes with a Planck source linear in optical depth (lbl_column_flux_linear_dev): column_flux_surface_dev's
+        arguments and results with ``edge_T`` in place of the layers' temperatures - per layer (bottom edge, top edge), as L
+        pairs or 2 L numbers.  The default ``emissivity`` 1 is the black surface."""
+        edge_T = _as_f64(edge_T).reshape(-1)
+        if len(edge_T) != 2 * len(abs_coef):
+            raise ValueError("column_flux_linear_dev: two edge temperatures per layer")
+        self.check(self.lib.lbl_column_flux_linear_dev(
+            *self._column_args(abs_coef, edge_T, depth, range_min, range_max, n, I_surface, surface_T, (_hb(I_top),), mu,
+                               weight, band_first, band_count),
+            *self._emissivity_args(emissivity), int(reflection), _hb(level_flux), _hb(up_top), _hb(down_surface),
+            _hb(up_surface)))
+
     def column_jacobian_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                             jac, I_surface=None, surface_T=0.0, term_abs_coef=(), term_layer=(), ln_tau_spectra=None,
                             T_spectra=None):
@@ -698,6 +719,28 @@ class Context:
             raise ValueError("ray_radiance_surface_dev: one ray_first per ray and one more, one length per segment layer")
         self.check(self.lib.lbl_ray_radiance_surface_dev(
             self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
+            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
+            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
+            *self._emissivity_args(emissivity), _hb(surface_down), float(surface_down_norm), _hb(radiance),
+            _hb(transmittance)))
+
+    def ray_radiance_linear_dev(self, abs_coef, seg_T, range_min, range_max, n, ray_first, seg_layer, seg_length,
+                                source_kind, radiance, emissivity=1.0, I_source=None, source_T=0.0, surface_down=None,
+                                surface_down_norm=0.0, transmittance=None):
+        """Radiance along ray paths with a Planck source linear in optical depth (lbl_ray_radiance_linear_dev):
+        ray_radiance_surface_dev's arguments and results with ``seg_T`` in place of the layers' temperatures - per segment
+        (temperature where the light enters, where it leaves), as pairs or 2 numbers per segment; a marker's pair is
+        ignored.  The default ``emissivity`` 1 is the black surface."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
+        seg_length = _as_f64(seg_length)
+        seg_T = _as_f64(seg_T).reshape(-1)
+        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length) or len(seg_T) != 2 * len(seg_layer):
+            raise ValueError("ray_radiance_linear_dev: one ray_first per ray and one more, one length and two temperatures "
+                             "per segment layer")
+        self.check(self.lib.lbl_ray_radiance_linear_dev(
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), seg_T.ctypes.data_as(_D),
             float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
             seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
             *self._emissivity_args(emissivity), _hb(surface_down), float(surface_down_norm), _hb(radiance),

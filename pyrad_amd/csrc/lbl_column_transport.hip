@@ -1,7 +1,8 @@
 // Column transport (include/pyrad_hip.h, "level fluxes", "Jacobians" and "ray paths"): argument checking and the launch
 // sequences of lbl_column_flux_dev, lbl_column_jacobian_dev, lbl_ray_radiance_dev and lbl_ray_jacobian_dev, and of their
 // variants over a reflecting surface, lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev, lbl_column_jacobian_surface_dev
-// and lbl_ray_jacobian_surface_dev.  The kernels are K5c, K5d, K5e, K5f, K5g and K5h of lbl_kernels.hip; the context's internals
+// and lbl_ray_jacobian_surface_dev, and of the linear-source variants lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev.
+// The kernels are K5c, K5d, K5e, K5f, K5g, K5h and K5i of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -58,11 +59,13 @@ static int column_fail(lbl_ctx* ctx, int code, const char* fmt, ...) {
     } while (0)
 
 // The arguments both entry points share (ctx non-NULL): checked in this order, then the ColumnRT part of the argument block
-// filled.  `what` names the feature in the refusal under "sweep_ieee_divisions" 1.
+// filled.  `what` names the feature in the refusal under "sweep_ieee_divisions" 1.  With `pbkT_top` (the linear source) T holds
+// two temperatures per layer, bottom and top edge, finite and > 0: pbkT receives the bottom edges, pbkT_top the top edges,
+// and pbkT_min / pbkT_max cover both.
 static int check_column(lbl_ctx* ctx, const char* what, ColumnRT* a, int n_layers, lbl_buffer* const* abs_coef,
                         const double* T, const double* depth, double range_min, double range_max, int64_t n,
                         lbl_buffer* I_surface, double surface_T, int n_angles, const double* mu, const double* weight,
-                        int n_bands, const int64_t* band_first, const int64_t* band_count) {
+                        int n_bands, const int64_t* band_first, const int64_t* band_count, double* pbkT_top = nullptr) {
     if (n_layers < 0 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
     if (n < 0) return column_fail(ctx, LBL_ERR_BAD_ARG, "negative n");
     if (n_layers > 0 && (!abs_coef || !T || !depth)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
@@ -81,13 +84,21 @@ static int check_column(lbl_ctx* ctx, const char* what, ColumnRT* a, int n_layer
     double pa = 0.0;
     for (int l = 0; l < n_layers; ++l) {
         if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
-        if (!(T[l] > 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
+        const double Tl = pbkT_top ? T[2 * l] : T[l];
+        if (pbkT_top && !(std::isfinite(Tl) && std::isfinite(T[2 * l + 1]) && Tl > 0 && T[2 * l + 1] > 0))
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: both edge temperatures must be finite and > 0", l);
+        if (!(Tl > 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
         if (!(depth[l] >= 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: depth must be >= 0", l);
         a->abs_coef[l] = buffer_data(abs_coef[l]);
         a->depth[l] = depth[l];
-        planck_budget_constants(T[l], &pa, &a->pbkT[l]);
+        planck_budget_constants(Tl, &pa, &a->pbkT[l]);
         a->pbkT_min = l == 0 ? a->pbkT[l] : std::min(a->pbkT_min, a->pbkT[l]);
         a->pbkT_max = l == 0 ? a->pbkT[l] : std::max(a->pbkT_max, a->pbkT[l]);
+        if (pbkT_top) {
+            planck_budget_constants(T[2 * l + 1], &pa, &pbkT_top[l]);
+            a->pbkT_min = std::min(a->pbkT_min, pbkT_top[l]);
+            a->pbkT_max = std::max(a->pbkT_max, pbkT_top[l]);
+        }
     }
     for (int k = 0; k < n_angles; ++k) {
         if (!(mu[k] > 0 && mu[k] <= 1)) return column_fail(ctx, LBL_ERR_BAD_ARG, "angle %d: mu must lie in (0, 1]", k);
@@ -167,19 +178,18 @@ static int check_emissivity(lbl_ctx* ctx, lbl_buffer* emissivity, double emissiv
     return LBL_OK;
 }
 
-extern "C" int lbl_column_flux_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
-                                           const double* depth, double range_min, double range_max, int64_t n,
-                                           lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
-                                           const double* mu, const double* weight, int n_bands, const int64_t* band_first,
-                                           const int64_t* band_count, lbl_buffer* emissivity, double emissivity_all,
-                                           int reflection, lbl_buffer* level_flux, lbl_buffer* up_top,
-                                           lbl_buffer* down_surface, lbl_buffer* up_surface) try {
-    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
-    std::vector<char> blk(sizeof(SurfaceFluxArgs), 0);
-    SurfaceFluxArgs* a = (SurfaceFluxArgs*)blk.data();
+// lbl_column_flux_surface_dev (Args = SurfaceFluxArgs, T per layer) and lbl_column_flux_linear_dev (Args = LinearFluxArgs, T
+// the 2 n_layers edge temperatures): the same checks in the same order and the same launch sequence around launch(...).
+template <class Args, class Launch>
+static int surface_flux_call(lbl_ctx* ctx, double* pbkT_top, Args* a, Launch launch, int n_layers, lbl_buffer* const* abs_coef,
+                             const double* T, const double* depth, double range_min, double range_max, int64_t n,
+                             lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles, const double* mu,
+                             const double* weight, int n_bands, const int64_t* band_first, const int64_t* band_count,
+                             lbl_buffer* emissivity, double emissivity_all, int reflection, lbl_buffer* level_flux,
+                             lbl_buffer* up_top, lbl_buffer* down_surface, lbl_buffer* up_surface) {
     int rc;
     if ((rc = check_column(ctx, "level fluxes", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
-                           surface_T, n_angles, mu, weight, n_bands, band_first, band_count)))
+                           surface_T, n_angles, mu, weight, n_bands, band_first, band_count, pbkT_top)))
         return rc;
     const int nv = 2 * (n_layers + 1);
     if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
@@ -203,9 +213,38 @@ extern "C" int lbl_column_flux_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffe
     a->up_surface = up_surface ? buffer_data(up_surface) : nullptr;
     a->reflection = reflection;
     return run_column(ctx, a, 4, nv, n_bands, band_count, {a->up_top, a->down_surface, a->up_surface}, (size_t)n * sizeof(double),
-                      [&](const SurfaceFluxArgs* d, double* partial, int b, hipStream_t s) {
-        launch_surface_flux(d, n_layers, n_angles, band_first[b], band_count[b], partial, buffer_data(level_flux) + (size_t)b * nv, s);
+                      [&](const Args* d, double* partial, int b, hipStream_t s) {
+        launch(d, n_layers, n_angles, band_first[b], band_count[b], partial, buffer_data(level_flux) + (size_t)b * nv, s);
     });
+}
+
+extern "C" int lbl_column_flux_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                           const double* depth, double range_min, double range_max, int64_t n,
+                                           lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
+                                           const double* mu, const double* weight, int n_bands, const int64_t* band_first,
+                                           const int64_t* band_count, lbl_buffer* emissivity, double emissivity_all,
+                                           int reflection, lbl_buffer* level_flux, lbl_buffer* up_top,
+                                           lbl_buffer* down_surface, lbl_buffer* up_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(SurfaceFluxArgs), 0);
+    return surface_flux_call(ctx, nullptr, (SurfaceFluxArgs*)blk.data(), launch_surface_flux, n_layers, abs_coef, T, depth,
+                             range_min, range_max, n, I_surface, surface_T, I_top, n_angles, mu, weight, n_bands, band_first,
+                             band_count, emissivity, emissivity_all, reflection, level_flux, up_top, down_surface, up_surface);
+} LBL_GUARD_END(ctx)
+
+extern "C" int lbl_column_flux_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T_edge,
+                                          const double* depth, double range_min, double range_max, int64_t n,
+                                          lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
+                                          const double* mu, const double* weight, int n_bands, const int64_t* band_first,
+                                          const int64_t* band_count, lbl_buffer* emissivity, double emissivity_all,
+                                          int reflection, lbl_buffer* level_flux, lbl_buffer* up_top,
+                                          lbl_buffer* down_surface, lbl_buffer* up_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(LinearFluxArgs), 0);
+    LinearFluxArgs* a = (LinearFluxArgs*)blk.data();
+    return surface_flux_call(ctx, a->pbkT_top, a, launch_linear_flux, n_layers, abs_coef, T_edge, depth, range_min, range_max,
+                             n, I_surface, surface_T, I_top, n_angles, mu, weight, n_bands, band_first, band_count, emissivity,
+                             emissivity_all, reflection, level_flux, up_top, down_surface, up_surface);
 } LBL_GUARD_END(ctx)
 
 // What lbl_column_jacobian_dev and lbl_column_jacobian_surface_dev check behind check_column, then the JacArgs part of the
@@ -339,15 +378,19 @@ static int check_ray_lists(lbl_ctx* ctx, int n_layers, int n_rays, const int32_t
 // RayArgs part of the argument block filled - the tables start `header` bytes into the block, *bytes is where they end -
 // and the dispatch order found.  `radiance` holds n_rays x n and may be NULL only where it is not `radiance_required`.
 // `markers`: surface markers are allowed among the segment layers (check_ray_lists); their length must be 0 and a ray with
-// one needs the surface source.
+// one needs the surface source.  `seg_T` (the linear source; T is then not read): two temperatures per segment, entry and
+// exit, finite and > 0 except a marker's pair; pbkT_min / pbkT_max are taken over them, *seg_pbkT receives their Planck
+// exponents (0 for a marker's), and rays bundle only where they also share their segment temperatures.
 static int check_rays(lbl_ctx* ctx, RayArgs* a, size_t header, int n_layers, lbl_buffer* const* abs_coef, const double* T,
                       double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
                       const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind, lbl_buffer* I_source,
                       double source_T, lbl_buffer* radiance, bool radiance_required, lbl_buffer* transmittance, bool markers,
-                      std::vector<int32_t>* order, size_t* bytes) {
+                      std::vector<int32_t>* order, size_t* bytes, const double* seg_T = nullptr,
+                      std::vector<double>* seg_pbkT = nullptr) {
+    const bool linear = seg_pbkT != nullptr;
     if (n_layers < 1 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d layers", kMaxLayers);
     if (n < 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "n must be >= 1");
-    if (!abs_coef || !T) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if (!abs_coef || (!linear && !T)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
     if (ctx_sweep_ieee(ctx))
         return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", "ray paths");
     int rc;
@@ -358,6 +401,13 @@ static int check_rays(lbl_ctx* ctx, RayArgs* a, size_t header, int n_layers, lbl
     for (int s = 0; s < n_seg; ++s)
         if (!(seg_length[s] >= 0) || !std::isfinite(seg_length[s]))
             return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: length must be finite and >= 0", s);
+    if (linear && n_seg > 0 && !seg_T) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL segment list");
+    for (int s = 0; linear && s < n_seg; ++s) {
+        if (seg_layer[s] == kRaySurfaceMarker) continue;
+        for (int e = 0; e < 2; ++e)
+            if (!(std::isfinite(seg_T[2 * s + e]) && seg_T[2 * s + e] > 0))
+                return column_fail(ctx, LBL_ERR_BAD_ARG, "segment %d: both temperatures must be finite and > 0", s);
+    }
     if ((rc = ctx_check_buffer(ctx, I_source, n, "I_source", false))) return rc;
     for (int r = 0; markers && r < n_rays; ++r)
         for (int s = ray_first[r]; s < ray_first[r + 1]; ++s) {
@@ -379,11 +429,27 @@ static int check_rays(lbl_ctx* ctx, RayArgs* a, size_t header, int n_layers, lbl
     double pa = 0.0;
     for (int l = 0; l < n_layers; ++l) {
         if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
-        if (!(T[l] > 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
         a->abs_coef[l] = buffer_data(abs_coef[l]);
+        if (linear) continue;
+        if (!(T[l] > 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be > 0", l);
         planck_budget_constants(T[l], &pa, &a->pbkT[l]);
         a->pbkT_min = l == 0 ? a->pbkT[l] : std::min(a->pbkT_min, a->pbkT[l]);
         a->pbkT_max = l == 0 ? a->pbkT[l] : std::max(a->pbkT_max, a->pbkT[l]);
+    }
+    if (linear) {
+        // (a call without a real segment forms no Planck value in a step: the bounds stay 0 and the general path runs)
+        seg_pbkT->assign(2 * (size_t)n_seg, 0.0);
+        bool any = false;
+        for (int s = 0; s < n_seg; ++s) {
+            if (seg_layer[s] == kRaySurfaceMarker) continue;
+            for (int e = 0; e < 2; ++e) {
+                double& v = (*seg_pbkT)[2 * (size_t)s + e];
+                planck_budget_constants(seg_T[2 * s + e], &pa, &v);
+                a->pbkT_min = any ? std::min(a->pbkT_min, v) : v;
+                a->pbkT_max = any ? std::max(a->pbkT_max, v) : v;
+                any = true;
+            }
+        }
     }
     planck_budget_constants(source_T > 0 ? source_T : 1.0, &pa, &a->pbk_surface);
     a->pa = pa;
@@ -407,10 +473,14 @@ static int check_rays(lbl_ctx* ctx, RayArgs* a, size_t header, int n_layers, lbl
     std::vector<int32_t> single;
     order->clear();
     {
-        std::map<std::vector<int32_t>, std::vector<int32_t>> open;
+        // (the second key: the segments' Planck exponents with the linear source, empty otherwise)
+        std::map<std::pair<std::vector<int32_t>, std::vector<double>>, std::vector<int32_t>> open;
         for (int r = 0; r < n_rays; ++r) {
             if (ray_first[r + 1] == ray_first[r]) { single.push_back(r); continue; }
-            auto& waiting = open[std::vector<int32_t>(seg_layer + ray_first[r], seg_layer + ray_first[r + 1])];
+            std::vector<double> temps;
+            if (linear) temps.assign(seg_pbkT->begin() + 2 * (size_t)ray_first[r], seg_pbkT->begin() + 2 * (size_t)ray_first[r + 1]);
+            auto& waiting = open[std::make_pair(std::vector<int32_t>(seg_layer + ray_first[r], seg_layer + ray_first[r + 1]),
+                                                std::move(temps))];
             waiting.push_back(r);
             if ((int)waiting.size() == kRayBundle) {
                 order->insert(order->end(), waiting.begin(), waiting.end());
@@ -497,6 +567,48 @@ extern "C" int lbl_ray_radiance_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buff
     if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
     COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
     launch_ray_surface((const RaySurfaceArgs*)d_args, n, n_rays, a.n_bundles, ctx_stream(ctx));
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+} LBL_GUARD_END(ctx)
+
+extern "C" int lbl_ray_radiance_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* seg_T,
+                                           double range_min, double range_max, int64_t n, int n_rays,
+                                           const int32_t* ray_first, const int32_t* seg_layer, const double* seg_length,
+                                           const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                                           lbl_buffer* emissivity, double emissivity_all, lbl_buffer* surface_down,
+                                           double surface_down_norm, lbl_buffer* radiance,
+                                           lbl_buffer* transmittance) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    // the argument block: header, K5e's tables, then the segments' Planck exponents
+    LinearRayArgs a;
+    memset((void*)&a, 0, sizeof a);
+    std::vector<int32_t> order;
+    std::vector<double> seg_pbkT;
+    size_t bytes = 0;
+    int rc;
+    if ((rc = check_rays(ctx, &a, sizeof a, n_layers, abs_coef, nullptr, range_min, range_max, n, n_rays, ray_first, seg_layer,
+                         seg_length, source_kind, I_source, source_T, radiance, true, transmittance, true, &order, &bytes,
+                         seg_T, &seg_pbkT)))
+        return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    if ((rc = ctx_check_buffer(ctx, surface_down, n, "surface_down", false))) return rc;
+    if (surface_down && (!(surface_down_norm > 0.0) || !std::isfinite(surface_down_norm)))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "surface_down_norm must be finite and > 0");
+    a.emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a.emissivity_all = emissivity_all;
+    a.surface_down = surface_down ? buffer_data(surface_down) : nullptr;
+    a.surface_down_norm = surface_down ? surface_down_norm : 1.0;
+    a.off_seg_pbkT = (long long)bytes;
+    bytes += seg_pbkT.size() * sizeof(double);
+    std::vector<char> blk(bytes, 0);
+    memcpy(blk.data(), (const void*)&a, sizeof a);
+    fill_ray_tables(blk.data(), a, n_rays, ray_first, seg_layer, seg_length, source_kind, order);
+    if (!seg_pbkT.empty()) memcpy(blk.data() + a.off_seg_pbkT, seg_pbkT.data(), seg_pbkT.size() * sizeof(double));
+
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    launch_linear_ray((const LinearRayArgs*)d_args, n, n_rays, a.n_bundles, ctx_stream(ctx));
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
 } LBL_GUARD_END(ctx)

@@ -314,6 +314,22 @@ struct RaySurfaceArgs : RayArgs {
 };
 void launch_ray_surface(const RaySurfaceArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s);
 
+// Linear-in-optical-depth Planck source (K5i, lbl_column_transport.hip: lbl_column_flux_linear_dev,
+// lbl_ray_radiance_linear_dev): K5g's two kernels with two temperatures per layer or segment, the step
+// I <- t I + (1 - t) Ba + g(tau) (Bb - Ba) (lbl_linear_source.h).  pbkT_min / pbkT_max are taken over every edge or segment
+// temperature of the call.  Partials, ray tables and dispatch order are K5c's and K5e's; the rays of a bundle also share
+// their segment temperatures.
+struct LinearFluxArgs : SurfaceFluxArgs {
+    double pbkT_top[kMaxLayers];        // 100 h c / k / T at the top edge of layer l; ColumnRT's pbkT holds the bottom edge
+};
+void launch_linear_flux(const LinearFluxArgs* d_args, int n_layers, int n_angles, long long first, long long count,
+                        double* partial, double* level_flux, hipStream_t s);
+struct LinearRayArgs : RaySurfaceArgs {
+    long long off_seg_pbkT;             // 2 n_segments doubles: 100 h c / k / T where the light enters and leaves the segment
+                                        // (a marker's pair is 0 and never read); ColumnRT's pbkT is not used
+};
+void launch_linear_ray(const LinearRayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s);
+
 // Ray-path Jacobians (K5f, lbl_column_transport.hip: lbl_ray_jacobian_dev): K5e's walk, then the segments last to first
 // with K5d's transmittance-and-emission recurrence, one output row per ray, kind and crossed layer.  RayArgs' block with
 // more tables behind it; `radiance` may be nullptr here and `transmittance` is not used.  A ray's rows start at row_first[r]:

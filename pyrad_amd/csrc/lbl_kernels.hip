@@ -24,6 +24,8 @@
 //                              reflection, rays that bounce (fluxes() and radiance() with an emissivity; beyond the reference)
 //   K5h surface_jacobian_kernel, ray_surface_jacobian_kernel   K5d and K5f over that surface: the reflected leg's derivatives
 //                              and d/d emissivity (jacobians(), pathJacobians(), observe() with an emissivity; beyond the reference)
+//   K5i linear_flux_kernel, linear_ray_kernel   K5g's two kernels with a Planck source linear in optical depth between two
+//                              temperatures per layer or segment (fluxes() and radiance() with planck="linear"; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -56,6 +58,7 @@
 // point against 5 fp64 instructions per directly evaluated (line, grid point) pair.
 #include "lbl_device.h"
 #include "lbl_launch_shapes.h"
+#include "lbl_linear_source.h"
 #include "lbl_voigt_func.h"
 #include <algorithm>
 #include <cstdlib>
@@ -4059,6 +4062,251 @@ __global__ __launch_bounds__(256) void ray_surface_kernel(const RaySurfaceArgs* 
     }
 }
 
+// ----------------------------------------------------------------------------------------
+// K5i: linear-in-optical-depth Planck source (lbl_column_flux_linear_dev, lbl_ray_radiance_linear_dev; the semantics are in
+// include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// K5g's two kernels with a Planck function that runs linearly in optical depth through a layer or segment, from Ba = B(Ta)
+// where the light enters to Bb = B(Tb) where it leaves:
+//     I <- t I + (1 - t) Ba + g(tau) (Bb - Ba),   g(tau) = 1 - (1 - t) / tau   (linear_source_g, lbl_linear_source.h).
+// The first two terms are fold_update's value and the third is added to it, so with Ta == Tb (Bb - Ba == 0, g finite) a step
+// returns fold_update's bits, and both kernels K5g's.  Per point and step: a second Planck value, from a second exp per
+// thread on the fast path (whose test covers every edge temperature of the call), and per angle or ray one g.
+
+// One step for the thread's NP points: transport_step with two Planck values; update(p, k_p, Ba_p, Bb_p - Ba_p).
+template <bool FAST, int NP, class Update>
+__device__ __forceinline__ void linear_step(const double (&nu)[NP], const double (&pa_n)[NP], double pbkT_a, double pbkT_b,
+                                            f64v<NP> v, Update update) {
+#pragma clang fp contract(off)
+    double Ea0 = 0.0, Eb0 = 0.0;
+    if (FAST) {
+        Ea0 = exp_clamped(nu[0] * pbkT_a);
+        Eb0 = exp_clamped(nu[0] * pbkT_b);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const double Ba = fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT_a, Ea0);
+        const double Bb = fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT_b, Eb0);
+        update(p, v[p], Ba, Bb - Ba);
+    }
+}
+
+// I <- t I + (1 - t) Ba + g(tau) dB, t = tr = exp_neg_budget(tau)
+template <bool FAST>
+__device__ __forceinline__ double linear_update(double tau, double tr, double I, double Ba, double dB) {
+#pragma clang fp contract(off)
+    const double isothermal = fold_update<FAST>(tr, I, Ba);
+    const double slope = linear_source_g(tau, tr) * dB;
+    return isothermal + slope;
+}
+
+// surface_flux_kernel with linear_step: going down the light enters a layer at its top edge and leaves at its bottom edge,
+// going up the other way round.  Everything else - Is in LDS, the surface, the level slots, the partials - is K5g's.
+// (the second launch bound: 4 points per thread take 135-163 registers with one to four angles, three waves per SIMD, and
+// 171-195 with five to eight, two waves; K5g's bounds - 4 waves with one angle, 3 up to seven - leave 5, 4 and 12 spilled
+// registers at one, five and six angles.  g without a branch: linear_source_g)
+template <int NP, int NA> constexpr int linear_flux_waves() { return NP == 1 ? 1 : NA <= 4 ? 3 : 2; }
+template <int NP, int NA>
+__global__ __launch_bounds__(256, (linear_flux_waves<NP, NA>())) void linear_flux_kernel(const LinearFluxArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                          long long lo1, long long n1, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    constexpr int kSlot = 2 * (kMaxLayers + 1);
+    __shared__ double acc[4 * kSlot];            // [wave][up levels 0..L, down levels 0..L]
+    __shared__ double source[NP * 256];          // [point][thread]: Is, from before the downward walk to the surface
+    const LinearFluxArgs& A = *Ap;
+    const int L = A.n_layers;
+    const int nv = 2 * (L + 1);
+    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
+    __syncthreads();
+    double* my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const long long total = n0 + n1;
+    const long long stride = (long long)gridDim.x * blockDim.x * NP;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
+    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
+        const long long q = q0 + (long long)threadIdx.x * NP;
+        const bool active = q < total;
+        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        double nu[NP], pa_n[NP], I[NA][NP];
+        column_points<NP>(A, j, nu, pa_n);
+        const bool fast = fold_fast_path<NP>(A, nu, active);
+        auto level = [&](int slot, double* spec, double* spec2 = nullptr) __attribute__((always_inline)) {
+            double s = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double f = angle_sum<NA>(A, [&](int k) { return I[k][p]; });
+                if (spec && active) spec[j + p] = f;
+                if (spec2 && active) spec2[j + p] = f;
+                s += active ? nan_to_num(f) : 0.0;
+            }
+            s = wave_sum(s);
+            if (lane0) my[slot] += s;
+        };
+        // (entered at pbkT_a, left at pbkT_b)
+        auto layer = [&](auto fast_tag, int l, vec v, double pbkT_a, double pbkT_b) __attribute__((always_inline)) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double depth = A.depth[l];
+            linear_step<FAST, NP>(nu, pa_n, pbkT_a, pbkT_b, v, [&](int p, double kp, double Ba, double dB) __attribute__((always_inline)) {
+                const double tau = kp * depth;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double tk = tau * A.rmu[k];
+                    I[k][p] = linear_update<FAST>(tk, exp_neg_budget(tk), I[k][p], Ba, dB);
+                }
+            });
+        };
+        auto walk = [&](auto fast_tag) __attribute__((always_inline)) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                source[p * 256 + threadIdx.x] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+            // downward: I_L = I_top or 0; level l after layer l
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double It = A.I_top ? A.I_top[j + p] : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) I[k][p] = It;
+            }
+            level(L + 1 + L, L == 0 ? A.down_surface : nullptr);
+            vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+                layer(fast_tag, l, cur, A.pbkT_top[l], A.pbkT[l]);
+                level(L + 1 + l, l == 0 ? A.down_surface : nullptr);
+                cur = nxt;
+            }
+            // the surface: I_up[0] = e Is + (1 - e) R, in place
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+                const double Is = source[p * 256 + threadIdx.x];
+                const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : I[k][p]);
+            }
+            // upward: level l + 1 after layer l
+            level(0, A.up_surface, L == 0 ? A.up_top : nullptr);
+            cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+            for (int l = 0; l < L; ++l) {
+                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+                layer(fast_tag, l, cur, A.pbkT[l], A.pbkT_top[l]);
+                level(l + 1, l + 1 == L ? A.up_top : nullptr);
+                cur = nxt;
+            }
+        };
+        if constexpr (NP > 1) {
+            if (fast) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += blockDim.x)
+        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+}
+
+// ray_surface_kernel with linear_step: every real segment has its own pair of Planck exponents, entry and exit in the light's
+// direction of travel, in a table beside seg_length; the rays of a bundle share the pairs as they share the layers (the host
+// bundles by both), so the pair is read from the bundle's first ray.  Markers, the diffuse start term and the prefetch are
+// K5g's; a ray's operations are the same in every bundle size.
+template <int NP, int RB>
+__global__ __launch_bounds__(256) void linear_ray_kernel(const LinearRayArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                         long long lo1, long long n1, int order_first) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    const LinearRayArgs& A = *Ap;
+    const char* blk = (const char*)Ap;
+    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
+    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
+    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
+    const double* __restrict__ seg_pbkT = (const double*)(blk + A.off_seg_pbkT);
+    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
+    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
+    // (idle lanes of the last workgroup work on a valid point and store nothing)
+    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
+    const bool active = q < n0 + n1;
+    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    double nu[NP], pa_n[NP], Is[NP], em[NP], I[RB][NP], Tt[RB][NP];
+    column_points<NP>(A, j, nu, pa_n);
+    const bool fast = fold_fast_path<NP>(A, nu, active);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+        em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+    }
+    int rid[RB], s0[RB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
+        s0[i] = ray_first[rid[i]];
+        const bool surface = source_kind[rid[i]] == 1;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const double Rd = A.surface_down ? A.surface_down[j + p] / A.surface_down_norm : 0.0;
+            I[i][p] = surface ? surface_leaving(em[p], Is[p], Rd) : 0.0;
+            Tt[i][p] = 1.0;
+        }
+    }
+    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers)
+    const int32_t* lay = seg_layer + s0[0];
+    const double* pbk = seg_pbkT + 2 * (long long)s0[0];
+    // the first real segment at or after s (ns: none)
+    auto real_from = [&](int s) {
+        while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
+        return s;
+    };
+    auto walk = [&](auto fast_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        int ahead = real_from(0);
+        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
+        for (int s = 0; s < ns; ++s) {
+            if (lay[s] == kRaySurfaceMarker) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        I[i][p] = surface_leaving(em[p], Is[p], I[i][p]);
+                        Tt[i][p] = Tt[i][p] * (1.0 - em[p]);
+                    }
+                }
+                continue;
+            }
+            ahead = real_from(s + 1);
+            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
+            double len[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            linear_step<FAST, NP>(nu, pa_n, pbk[2 * s], pbk[2 * s + 1], cur, [&](int p, double kp, double Ba, double dB) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double tau = kp * len[i];
+                    const double tr = exp_neg_budget(tau);
+                    I[i][p] = linear_update<FAST>(tau, tr, I[i][p], Ba, dB);
+                    Tt[i][p] = Tt[i][p] * tr;
+                }
+            });
+            cur = nxt;
+        }
+    };
+    if constexpr (NP > 1) {
+        if (fast) walk(std::true_type{});
+        else walk(std::false_type{});
+    } else {
+        walk(std::false_type{});
+    }
+    if (!active) return;
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        const long long o = (long long)rid[i] * A.n + j;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            A.radiance[o + p] = I[i][p];
+            if (A.transmittance) A.transmittance[o + p] = Tt[i][p];
+        }
+    }
+}
+
 // K5d: K5c's upward fold, keeping per angle only the radiance I and its running maximum Imax over the levels; then a
 // downward pass that re-reads k_l and recomputes B_l as K5c's does, and keeps per angle the transmittance A to the top and
 // D = E - I_top, E the emission of the layers above that reaches the top.  Then
@@ -5244,6 +5492,36 @@ void launch_ray_surface(const RaySurfaceArgs* d_args, long long n, int n_rays, i
     }
     if (nt > 0)
         hipLaunchKernelGGL((ray_surface_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+}
+
+// K5i: K5g's launches - 4 points per thread for every angle count and bundle size, so that with equal edge temperatures the
+// one-exp Planck path starts from the same points and returns K5g's bits
+void launch_linear_flux(const LinearFluxArgs* d_args, int n_layers, int n_angles, long long first, long long count,
+                        double* partial, double* level_flux, hipStream_t s) {
+    with_angles(n_angles, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        launch_column_band<4>(linear_flux_kernel<4, NA>, linear_flux_kernel<1, NA>, d_args, 2 * (n_layers + 1), first, count,
+                              partial, level_flux, s);
+    });
+}
+
+void launch_linear_ray(const LinearRayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s) {
+    constexpr int NP = 4;
+    if (n <= 0 || n_rays <= 0) return;
+    const long long q1 = n & ~(long long)(NP - 1);
+    const long long nt = n - q1;
+    const int n_single = n_rays - kRayBundle * n_bundles;
+    if (q1 > 0) {
+        const unsigned blocks = (unsigned)((q1 / NP + 255) / 256);
+        if (n_bundles > 0)
+            hipLaunchKernelGGL((linear_ray_kernel<NP, kRayBundle>), dim3(blocks, n_bundles), dim3(256), 0, s, d_args, 0LL, q1,
+                               0LL, 0LL, 0);
+        if (n_single > 0)
+            hipLaunchKernelGGL((linear_ray_kernel<NP, 1>), dim3(blocks, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL,
+                               kRayBundle * n_bundles);
+    }
+    if (nt > 0)
+        hipLaunchKernelGGL((linear_ray_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
 }
 
 // K5f: launch_ray_radiance's split of the points and of the rays (the radiance is K5e's bit for bit only on K5e's own groups

@@ -1451,6 +1451,19 @@ def _surface_reflection(reflection):
     return REFLECTIONS.index(reflection)
 
 
+PLANCK_SOURCES = ("layer", "linear")
+
+
+def _planck_source(planck, levelTemperatures):
+    """True for the source linear in optical depth; ValueError for anything but "layer" and "linear", and for level
+    temperatures that the layer source would ignore"""
+    if not isinstance(planck, str) or planck not in PLANCK_SOURCES:
+        raise ValueError("planck is \"layer\" or \"linear\", not %r" % (planck,))
+    if planck == "layer" and levelTemperatures is not None:
+        raise ValueError("levelTemperatures belong to planck=\"linear\"; planck=\"layer\" uses the layers' temperatures")
+    return planck == "linear"
+
+
 def _band_values(bands, values):
     """Copies of per-band results (leading band axis): without ``bands`` each one's single band alone."""
     return [(v[0] if bands is None else v).copy() for v in values]
@@ -1884,13 +1897,15 @@ class Path:
     surface source of the radiance() call) or "space" (nothing).  Immutable; len(path) is the number of segments, which
     may be 0 (the observer then sees the source).  ``bounce``: None, or an integer i in 0..len(path) - the light meets the
     surface after its first i segments and is reflected specularly there (Atmosphere.radiance with an emissivity;
-    Atmosphere.reflectedPath builds the usual one).  ValueError for anything else.  Atmosphere.nadirPath, zenithPath and
-    limbPath build the usual ones."""
-    __slots__ = ("layers", "lengths", "source", "name", "bounce")
+    Atmosphere.reflectedPath builds the usual one).  ``temperatures``: None, or one pair (Ta, Tb) per segment, finite and
+    > 0 - the temperature where the light enters the segment and where it leaves it, for radiance(planck="linear"); kept
+    as a tuple of pairs.  ValueError for anything else.  Atmosphere.nadirPath, zenithPath and limbPath build the usual
+    ones, with ``levelTemperatures`` also the temperatures."""
+    __slots__ = ("layers", "lengths", "source", "name", "bounce", "temperatures")
     SOURCES = ("space", "surface")          # the C ABI's source_kind is the index
     SURFACE_MARKER = -1                     # ... and this segment layer (length 0) the place of a bounce
 
-    def __init__(self, layers, lengths, source="surface", name="", bounce=None):
+    def __init__(self, layers, lengths, source="surface", name="", bounce=None, temperatures=None):
         try:
             layers = list(layers)
             lay = tuple(int(l) for l in layers)
@@ -1911,7 +1926,16 @@ class Path:
                 raise ValueError("Path: bounce is None or an integer 0..%d (the segments before the surface), not %r"
                                  % (len(lay), bounce))
             bounce = int(bounce)
-        for k, v in zip(self.__slots__, (lay, lens, source, str(name), bounce)):
+        if temperatures is not None:
+            try:
+                temperatures = tuple((float(a), float(b)) for a, b in temperatures)
+            except (TypeError, ValueError):
+                raise ValueError("Path: temperatures are pairs (Ta, Tb) of numbers, one per segment")
+            if len(temperatures) != len(lay):
+                raise ValueError("Path: %d layers but %d pairs of temperatures" % (len(lay), len(temperatures)))
+            if not all(math.isfinite(t) and t > 0.0 for pair in temperatures for t in pair):
+                raise ValueError("Path: temperatures must be finite and > 0")
+        for k, v in zip(self.__slots__, (lay, lens, source, str(name), bounce, temperatures)):
             object.__setattr__(self, k, v)
 
     def __setattr__(self, key, value):
@@ -1923,8 +1947,9 @@ class Path:
         return len(self.layers)
 
     def __repr__(self):
-        return "Path(%s%d segments, source=%s%s)" % (self.name + ": " if self.name else "", len(self), self.source,
-                                                     "" if self.bounce is None else ", bounce=%d" % self.bounce)
+        return "Path(%s%d segments, source=%s%s%s)" % (self.name + ": " if self.name else "", len(self), self.source,
+                                                       "" if self.bounce is None else ", bounce=%d" % self.bounce,
+                                                       "" if self.temperatures is None else ", temperatures")
 
     def _segments(self):
         """(layers, lengths) as the C call takes them: the bounce as a segment of SURFACE_MARKER and length 0"""
@@ -1932,6 +1957,13 @@ class Path:
             return self.layers, self.lengths
         i = self.bounce
         return self.layers[:i] + (self.SURFACE_MARKER,) + self.layers[i:], self.lengths[:i] + (0.0,) + self.lengths[i:]
+
+    def _segment_temperatures(self):
+        """the temperatures beside _segments(): a dummy pair at the bounce, which the C call ignores"""
+        if self.bounce is None:
+            return self.temperatures
+        i = self.bounce
+        return self.temperatures[:i] + ((0.0, 0.0),) + self.temperatures[i:]
 
 
 class PathRadiance:
@@ -2082,7 +2114,9 @@ class Atmosphere(list):
         """Fold Layer.transmission bottom to top over the layers in list order:
         I <- T_i I + (1 - T_i) B(nu, T_i), I_0 = surfaceSpectrum or B(nu, surfaceTemperature).
         (The reference announces an atmosphere path but ships no driver; this is the fold of
-        cls:784-787, computed by one column-sweep kernel.)"""
+        cls:784-787, computed by one column-sweep kernel.)
+        The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
+        planck="linear"; its derivatives are not part of this method)."""
         layers, n = self._column_layers()
         first = layers[0]
         ctx = _ctx()
@@ -2119,7 +2153,7 @@ class Atmosphere(list):
 
 
     def fluxes(self, surfaceTemperature=None, surfaceSpectrum=None, topSpectrum=None, angles=3, bands=None, spectra=False,
-               emissivity=None, reflection="lambertian"):
+               emissivity=None, reflection="lambertian", planck="layer", levelTemperatures=None):
         """Upward, downward and net fluxes at every level and the heating rate of every layer (beyond the reference).
 
         Layers l = 0 .. L-1 in list order, bottom to top, as transmission() takes them; level i is the lower boundary of
@@ -2149,12 +2183,27 @@ class Atmosphere(list):
         Dividing by the sum of the weights (pi for the Gauss angles) makes the reflected upward flux (1 - e) F0 under the
         quadrature itself, so the surface conserves energy whatever the angle set.  With ``spectra`` the result also carries
         upSurfaceSpectrum, F_up at level 0.  One pass over the absorption coefficients (lbl_column_flux_surface_dev), nothing
-        comes down in between; with emissivity 1 every result is the black surface's bit for bit."""
+        comes down in between; with emissivity 1 every result is the black surface's bit for bit.
+
+        ``planck``: "layer", the isothermal layers above, or "linear" - the Planck function runs linearly in optical depth
+        through a layer, between the temperatures of its two levels (``levelTemperatures``: L + 1 numbers, level 0 the
+        surface; None: levelTemperatures()).  With tau = k_l depth_l / mu_k, Ba the Planck function at the level where the
+        light enters the layer (the lower one going up, the upper one going down) and Bb where it leaves,
+            I <- t I + (1 - t) Ba + g(tau) (Bb - Ba)        g(tau) = 1 - (1 - t) / tau
+        which removes the isothermal layer's first-order error on a column with a lapse rate.  The surface source stays
+        surfaceTemperature or surfaceSpectrum (a skin temperature may differ from level 0), emissivity, reflection, bands
+        and spectra work as above (lbl_column_flux_linear_dev), and the heating rates are heatingRates() with the layers'
+        own T, P and depth.  With level temperatures equal to the layers' on both sides of every layer, every result is the
+        layer source's bit for bit."""
         layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
             surfaceSpectrum, surfaceTemperature, angles, bands)
         topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
         first = layers[0]
         refl = _surface_reflection(reflection)
+        edges = None
+        if _planck_source(planck, levelTemperatures):
+            lev = self._level_temperatures(levelTemperatures)
+            edges = np.column_stack([lev[:-1], lev[1:]])
         if emissivity is not None:
             emissivity = _surface_emissivity(emissivity, first.xAxis)
             wsum = _weight_sum(weight)
@@ -2170,7 +2219,18 @@ class Atmosphere(list):
         up_top = fst.buf(ctx, "up_top") if spectra else None
         down_surface = fst.buf(ctx, "down_surface") if spectra else None
         up_surface = None
-        if emissivity is None:
+        if edges is not None:
+            if emissivity is None:
+                emissivity = 1.0
+            else:
+                up_surface = fst.buf(ctx, "up_surface") if spectra else None
+                if not isinstance(emissivity, float):
+                    emissivity = fst.buf(ctx, "emissivity").upload(emissivity)
+            ctx.column_flux_linear_dev(kbufs, edges, [L.depth for L in layers], first.rangeMin, first.rangeMax, n, mu, weight,
+                                       band_first, band_count, level, emissivity, reflection=refl, I_surface=I_surface,
+                                       surface_T=float(surfaceTemperature or 0.0), I_top=I_top, up_top=up_top,
+                                       down_surface=down_surface, up_surface=up_surface)
+        elif emissivity is None:
             ctx.column_flux_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
                                 mu, weight, band_first, band_count, level, I_surface=I_surface,
                                 surface_T=float(surfaceTemperature or 0.0), I_top=I_top, up_top=up_top, down_surface=down_surface)
@@ -2234,7 +2294,9 @@ class Atmosphere(list):
         (an emissivity given per grid point or as a table moves as a whole: dF/de is the derivative by one number added to
         it everywhere; Jacobians.emissivitySpectrum has it per grid point).  With emissivity 1 and one or two angles every
         value but dF/de is the black surface's bit for bit.  ``topSpectrum`` without an emissivity is a ValueError: the
-        black surface's outgoing flux does not depend on it."""
+        black surface's outgoing flux does not depend on it.
+        The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
+        planck="linear"; its derivatives are not part of this method)."""
         if temperature not in ("planck", "full"):
             raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
@@ -2327,7 +2389,9 @@ class Atmosphere(list):
         emits e Is and reflects, specularly at ``mu``, the downward radiance of the column under cold space (with the single
         viewing angle the Lambertian and the specular reflection of fluxes() are one expression): the radiance is
         fluxes(emissivity=e, reflection="specular", angles=[(mu, 1.0)])'s upward spectrum at the top, the weighting functions
-        jacobians(emissivity=e, ...)'s for that angle, and Observation.emissivityJacobian their dR_c/de."""
+        jacobians(emissivity=e, ...)'s for that angle, and Observation.emissivityJacobian their dR_c/de.
+        The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
+        planck="linear"; its derivatives are not part of this method)."""
         if not isinstance(instrument, Instrument):
             raise ValueError("instrument: an Instrument, not %r" % (instrument,))
         try:
@@ -2410,32 +2474,85 @@ class Atmosphere(list):
             raise ValueError("observerLevel: a level 0..%d (0 the surface), not %r" % (nl, observerLevel))
         return int(observerLevel), nl
 
-    def nadirPath(self, mu=1.0, observerLevel=None):
+    def levelTemperatures(self):
+        """The default temperatures of the L + 1 levels for planck="linear": linear in height between the layers'
+        midpoints, where a layer has its own temperature,
+            lev_i = T_(i-1) + (T_i - T_(i-1)) depth_(i-1) / (depth_(i-1) + depth_i)        0 < i < L
+        and at both ends such that the layer's temperature is the mean of its two levels: lev_0 = 2 T_0 - lev_1, lev_L =
+        2 T_(L-1) - lev_(L-1).  One layer: both levels are T_0.  ValueError if a level comes out <= 0."""
+        layers, _ = self._column_layers()
+        T = [float(L.T) for L in layers]
+        d = [float(L.depth) for L in layers]
+        nl = len(layers)
+        lev = np.empty(nl + 1)
+        if nl == 1:
+            lev[:] = T[0]
+        else:
+            for i in range(1, nl):
+                lev[i] = T[i - 1] + (T[i] - T[i - 1]) * d[i - 1] / (d[i - 1] + d[i])
+            lev[0] = 2.0 * T[0] - lev[1]
+            lev[nl] = 2.0 * T[nl - 1] - lev[nl - 1]
+        if not np.all(np.isfinite(lev) & (lev > 0.0)):
+            raise ValueError("levelTemperatures: the default level temperatures %r are not all finite and > 0; give "
+                             "levelTemperatures" % (lev.tolist(),))
+        return lev
+
+    def _level_temperatures(self, levelTemperatures):
+        """``levelTemperatures`` as L + 1 float64 values: None or True the default ones, else L + 1 numbers, finite, > 0"""
+        if levelTemperatures is None or levelTemperatures is True:
+            return self.levelTemperatures()
+        nl = len(self._column_layers()[0])
+        try:
+            lev = np.array(levelTemperatures, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("levelTemperatures: %d numbers, one per level" % (nl + 1))
+        if isinstance(levelTemperatures, (bool, str)) or lev.shape != (nl + 1,):
+            raise ValueError("levelTemperatures: %d numbers, one per level (level 0 the surface), not %r"
+                             % (nl + 1, levelTemperatures))
+        if not np.all(np.isfinite(lev) & (lev > 0.0)):
+            raise ValueError("levelTemperatures must be finite and > 0")
+        return lev
+
+    def _path_temperatures(self, levelTemperatures, crossings):
+        """None without level temperatures, else the (Ta, Tb) of every crossing (layer, upward?) of whole layers"""
+        if levelTemperatures is None:
+            return None
+        lev = self._level_temperatures(levelTemperatures)
+        return [(lev[l], lev[l + 1]) if up else (lev[l + 1], lev[l]) for l, up in crossings]
+
+    def nadirPath(self, mu=1.0, observerLevel=None, levelTemperatures=None):
         """The Path of an observer at level ``observerLevel`` (None: the top, level L) looking down at cosine ``mu``: the
-        surface source, then the layers 0 .. observerLevel-1 upward, each over depth_l / mu."""
+        surface source, then the layers 0 .. observerLevel-1 upward, each over depth_l / mu.  ``levelTemperatures``: None,
+        or L + 1 level temperatures (True: levelTemperatures()) - the path then carries every segment's temperatures in the
+        direction of travel, for radiance(planck="linear")."""
         mu = self._path_mu(mu)
         lev, _ = self._path_level(observerLevel, None)
-        return Path(range(lev), [self[l].depth / mu for l in range(lev)], "surface", "nadir mu=%g level=%d" % (mu, lev))
+        return Path(range(lev), [self[l].depth / mu for l in range(lev)], "surface", "nadir mu=%g level=%d" % (mu, lev),
+                    temperatures=self._path_temperatures(levelTemperatures, [(l, True) for l in range(lev)]))
 
-    def zenithPath(self, mu=1.0, observerLevel=0):
+    def zenithPath(self, mu=1.0, observerLevel=0, levelTemperatures=None):
         """The Path of an upward-looking observer at level ``observerLevel`` (0: the surface) at cosine ``mu``: cold space,
         then the layers L-1 down to observerLevel, each over depth_l / mu - the downwelling radiance an instrument there
-        measures."""
+        measures.  ``levelTemperatures``: as nadirPath takes them (every segment enters at its layer's upper level)."""
         mu = self._path_mu(mu)
         lev, nl = self._path_level(observerLevel, 0)
         lay = range(nl - 1, lev - 1, -1)
-        return Path(lay, [self[l].depth / mu for l in lay], "space", "zenith mu=%g level=%d" % (mu, lev))
+        return Path(lay, [self[l].depth / mu for l in lay], "space", "zenith mu=%g level=%d" % (mu, lev),
+                    temperatures=self._path_temperatures(levelTemperatures, [(l, False) for l in lay]))
 
-    def reflectedPath(self, mu=1.0, observerLevel=None):
+    def reflectedPath(self, mu=1.0, observerLevel=None, levelTemperatures=None):
         """The Path of nadirPath's observer together with its mirror path: cold space, the layers L-1 .. 0 downward, the
         surface (bounce = L), then the layers 0 .. observerLevel-1 upward, each over depth_l / mu - what a surface that
-        reflects specularly sends to the observer (radiance() with an emissivity)."""
+        reflects specularly sends to the observer (radiance() with an emissivity).  ``levelTemperatures``: as nadirPath
+        takes them (downward segments enter at the upper level, upward ones at the lower)."""
         mu = self._path_mu(mu)
         lev, nl = self._path_level(observerLevel, None)
         lay = list(range(nl - 1, -1, -1)) + list(range(lev))
-        return Path(lay, [self[l].depth / mu for l in lay], "space", "reflected mu=%g level=%d" % (mu, lev), bounce=nl)
+        return Path(lay, [self[l].depth / mu for l in lay], "space", "reflected mu=%g level=%d" % (mu, lev), bounce=nl,
+                    temperatures=self._path_temperatures(levelTemperatures, [(l, False) for l in range(nl - 1, -1, -1)]
+                                                         + [(l, True) for l in range(lev)]))
 
-    def limbPath(self, tangentHeight, planetRadius=6.371e8):
+    def limbPath(self, tangentHeight, planetRadius=6.371e8, levelTemperatures=None):
         """The Path of a limb ray through the column taken as spherical shells around a planet of radius ``planetRadius``
         (cm; level heights z_0 = 0, z_(l+1) = z_l + depth_l): it enters from space, comes down to ``tangentHeight`` (cm above
         the surface, 0 <= tangentHeight < z_L) and leaves again towards an observer outside the atmosphere.  NO REFRACTION:
@@ -2443,7 +2560,9 @@ class Atmosphere(list):
         chord inside layer l >= m is, with lo = max(z_l, zt) and hi = z_(l+1),
             sqrt((hi - zt) (2 R + hi + zt)) - sqrt((lo - zt) (2 R + lo + zt))
         (the factored form of sqrt((R + hi)^2 - (R + zt)^2) - ..., which keeps its digits near the top).  Segments: the
-        layers L-1 .. m+1 with their half chords, layer m once with twice its half chord, then m+1 .. L-1."""
+        layers L-1 .. m+1 with their half chords, layer m once with twice its half chord, then m+1 .. L-1.
+        ``levelTemperatures``: as nadirPath takes them; the tangent layer is then crossed in two segments of one half chord
+        each, which meet at T(zt) = lev_m + (lev_(m+1) - lev_m) (zt - z_m) / depth_m."""
         layers, _ = self._column_layers()
         try:
             zt, R = float(tangentHeight), float(planetRadius)
@@ -2462,6 +2581,13 @@ class Atmosphere(list):
         reach = lambda h: math.sqrt((h - zt) * (2.0 * R + h + zt))
         half = {l: reach(z[l + 1]) - reach(max(z[l], zt)) for l in range(m, nl)}
         above = list(range(nl - 1, m, -1))
+        if levelTemperatures is not None:
+            lev = self._level_temperatures(levelTemperatures)
+            Tt = lev[m] + (lev[m + 1] - lev[m]) * (zt - z[m]) / float(layers[m].depth)
+            lay = above + [m, m] + above[::-1]
+            return Path(lay, [half[l] for l in lay], "space", "limb zt=%g" % zt,
+                        temperatures=[(lev[l + 1], lev[l]) for l in above] + [(lev[m + 1], Tt), (Tt, lev[m + 1])]
+                                     + [(lev[l], lev[l + 1]) for l in above[::-1]])
         lay = above + [m] + above[::-1]
         return Path(lay, [half[l] for l in above] + [2.0 * half[m]] + [half[l] for l in above[::-1]], "space",
                     "limb zt=%g" % zt)
@@ -2490,7 +2616,7 @@ class Atmosphere(list):
         return plist, layers, n, _grid_spectrum("surfaceSpectrum", surfaceSpectrum, n)
 
     def radiance(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, transmittance=False,
-                 emissivity=None, reflection="lambertian", angles=3):
+                 emissivity=None, reflection="lambertian", angles=3, planck="layer", levelTemperatures=None):
         """The radiance arriving along ``paths`` - one Path or a list of up to 512 - through this column (beyond the
         reference).  Layers, grid and units as transmission() has them.  For every path and grid point nu_j:
             I = surfaceSpectrum[j] or B(nu_j, surfaceTemperature) for source "surface", 0 for "space";  Ttot = 1
@@ -2511,11 +2637,28 @@ class Atmosphere(list):
             diffuse reflection of the downward flux at the surface that one fluxes() pass with ``angles`` (see fluxAngles)
             and cold space above leaves on the device - nothing comes down in between.  "specular": Rd = 0, the path carries
             e Is alone and the reflected light belongs to the paths with a bounce.
-        With emissivity 1 every result is the black surface's bit for bit.  A path with a bounce needs an emissivity."""
+        With emissivity 1 every result is the black surface's bit for bit.  A path with a bounce needs an emissivity.
+
+        ``planck``: "layer", the isothermal segments above, or "linear" - every path must then carry ``temperatures``, one
+        pair (Ta, Tb) per segment (the path builders fill them from ``levelTemperatures``), and per segment
+            I <- t I + (1 - t) B(nu_j, Ta) + g(tau) (B(nu_j, Tb) - B(nu_j, Ta))      tau = k_l s, g(tau) = 1 - (1 - t) / tau
+        as fluxes(planck="linear") steps through a layer (lbl_ray_radiance_linear_dev).  Instrument, transmittance,
+        emissivity and bounces work as above; the Lambertian start term then comes from one linear-source flux pass with
+        ``levelTemperatures`` (L + 1 numbers; None: levelTemperatures()), which stays on the device as well."""
         plist, layers, n, surfaceSpectrum = self._path_checks(paths, surfaceTemperature, surfaceSpectrum)
         R, nl = len(plist), len(layers)
         first = layers[0]
         refl = _surface_reflection(reflection)
+        linear = _planck_source(planck, levelTemperatures)
+        edges = None
+        if linear:
+            for i, p in enumerate(plist):
+                if p.temperatures is None:
+                    raise ValueError("planck=\"linear\": path %d (%r) carries no temperatures" % (i, p))
+            if levelTemperatures is not None or (emissivity is not None and refl == 0
+                                                 and any(p.source == "surface" for p in plist)):
+                lev = self._level_temperatures(levelTemperatures)
+                edges = np.column_stack([lev[:-1], lev[1:]])
         if emissivity is None:
             if any(p.bounce is not None for p in plist):
                 raise ValueError("a path with a bounce needs a surface that reflects: give emissivity")
@@ -2542,7 +2685,28 @@ class Atmosphere(list):
         pst = _kept_state(self, "_path_state").reserve(ctx, R * n)
         rad = pst.buf(ctx, "radiance")
         trn = pst.buf(ctx, "transmittance") if transmittance else None
-        if emissivity is None:
+        if linear:
+            down, norm = None, 0.0
+            if emissivity is None:
+                emissivity = 1.0
+            else:
+                sst = _kept_state(self, "_path_surface").reserve(ctx, max(n, 2 * (nl + 1)))
+                if not isinstance(emissivity, float):
+                    emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
+                if refl == 0 and any(p.source == "surface" for p in plist):
+                    # the downward flux at the surface under cold space, left on the device for the ray call behind it
+                    down, norm = sst.buf(ctx, "down_surface"), wsum
+                    ctx.column_flux_linear_dev(kbufs, edges, [L.depth for L in layers], first.rangeMin, first.rangeMax, n, mu,
+                                               weight, [0], [n], sst.buf(ctx, "level"), I_surface=I_source,
+                                               surface_T=float(surfaceTemperature or 0.0), down_surface=down)
+            segs = [p._segments() for p in plist]
+            ctx.ray_radiance_linear_dev(kbufs, [t for p in plist for t in p._segment_temperatures()], first.rangeMin,
+                                        first.rangeMax, n, np.cumsum([0] + [len(lay) for lay, _ in segs]),
+                                        [l for lay, _ in segs for l in lay], [x for _, lens in segs for x in lens],
+                                        [Path.SOURCES.index(p.source) for p in plist], rad, emissivity, I_source=I_source,
+                                        source_T=float(surfaceTemperature or 0.0), surface_down=down, surface_down_norm=norm,
+                                        transmittance=trn)
+        elif emissivity is None:
             ray_first = np.cumsum([0] + [len(p) for p in plist])
             ctx.ray_radiance_dev(kbufs, [L.T for L in layers], first.rangeMin, first.rangeMax, n, ray_first,
                                  [l for p in plist for l in p.layers], [x for p in plist for x in p.lengths],
@@ -2609,7 +2773,9 @@ class Atmosphere(list):
         PathJacobians.emissivity holds dI/de.  A path that STARTS at the surface carries, under reflection="lambertian", the
         diffusely reflected sky, which depends on every layer of the column; that derivative is not built, and holding the
         sky fixed would disagree with differences of radiance(): such a path is refused (ValueError) with an emissivity
-        and "lambertian" - take reflection="specular", under which it starts with e Is alone."""
+        and "lambertian" - take reflection="specular", under which it starts with e Is alone.
+        The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
+        planck="linear"; its derivatives are not part of this method)."""
         if temperature not in ("planck", "full"):
             raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         plist, layers, n, surfaceSpectrum = self._path_checks(paths, surfaceTemperature, surfaceSpectrum)
