@@ -735,6 +735,87 @@ int lbl_ray_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* 
                                  int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
                                  lbl_buffer* radiance /* n_rays x n, may be NULL */, lbl_buffer* jac /* rows x n */);
 
+/* ---- Jacobians of the linear-in-optical-depth Planck source (beyond the reference; ABI 5, backward compatible) -----------
+ * pyrad_amd.model.Atmosphere.jacobiansLinear, pathJacobiansLinear and observeLinear: the derivatives of what
+ * lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev compute, the temperatures of the layers' edges and of the
+ * segments' ends among the variables.  The step through a piece of optical depth tau, t = exp(-tau), Ba where the light
+ * enters and Bb where it leaves, is I_out = t I_in + (1 - t) Ba + g(tau) (Bb - Ba) = t I_in + h(tau) Ba + g(tau) Bb with
+ *   h(tau) = (1 - t) - g(tau) = tau g'(tau),   g'(tau) = (1 - t (1 + tau)) / tau^2      (-> 1/2 as tau -> 0, -> 0 as tau -> inf)
+ * so that dI_out/d ln tau = tau t (Ba - I_in) + h (Bb - Ba), dI_out/dTa = h dB(Ta)/dT, dI_out/dTb = g dB(Tb)/dT, and for an
+ * absorber term k_m over the length x: dI_out = k_m x [t (Ba - I_in) + g'(tau) (Bb - Ba)] - no division by tau, a point
+ * without absorption stays finite.  g' is lbl::linear_source_dg of pyrad_amd/csrc/lbl_linear_source.h (the closed form from
+ * tau = 3/8 on, its Taylor series below; within 1e-14 relative for a t good to 2 ulp), h is formed as tau g'.
+ *
+ * lbl_column_jacobian_linear_dev: the arguments of lbl_column_jacobian_surface_dev with T replaced by T_edge (2 per layer:
+ * T_edge[2 l] the bottom edge of layer l, T_edge[2 l + 1] its top edge, as lbl_column_flux_linear_dev) and jac_T_spectra by
+ * jac_T_edge_spectra (2 n_layers x n: rows 2 l and 2 l + 1 are the bottom and top edge of layer l).  emissivity NULL with
+ * emissivity_all 1 is the black surface.  Forward, at grid point nu_j, exactly lbl_column_flux_linear_dev; with that call's
+ * Id_(l+1)k, Iu_lk and lbl_column_jacobian_surface_dev's A_lk, C_lk, Ttot_k, Q_k, R_k and Is formed from them, x = k_l
+ * depth_l / mu_k, t = exp(-x), Bbot = B(T_edge[2 l]), Btop = B(T_edge[2 l + 1]):
+ *   gu_lk = A_lk [x t (Bbot - Iu_lk)     + h(x) (Btop - Bbot)]          upward leg
+ *   gd_lk = C_lk [x t (Btop - Id_(l+1)k) + h(x) (Bbot - Btop)]          downward leg, seen through the surface
+ *   dF/d ln tau_l     = sum_k (W_k gu_lk + Q_k gd_lk)
+ *   term m (layer l)  = sum_k (term_abs_coef[m][j] depth_l / mu_k) (W_k A_lk [t (Bbot - Iu_lk) + g'(x) (Btop - Bbot)]
+ *                                                                 + Q_k C_lk [t (Btop - Id_(l+1)k) + g'(x) (Bbot - Btop)])
+ *   dF/dT_bottom(l)   = dB(T_edge[2 l])/dT     sum_k (W_k A_lk h(x) + Q_k C_lk g(x))
+ *   dF/dT_top(l)      = dB(T_edge[2 l + 1])/dT sum_k (W_k A_lk g(x) + Q_k C_lk h(x))
+ *   dF/dT_s, dF/de    : lbl_column_jacobian_surface_dev's expressions
+ * jac[b] = [F, dF/dT_s, dF/de, dF/d ln tau_0..L-1, dF/dT_edge_0..2L-1, terms]: n_bands x (3 + 3 n_layers + n_terms) doubles,
+ * band sums with nan_to_num (of each leg's spectral value), as lbl_column_jacobian_surface_dev; the spectra likewise.  The
+ * derivative with respect to a level temperature that two layers share is the sum of the two edge values.
+ * Arithmetic: lbl_column_jacobian_surface_dev's three walks with lbl_column_flux_linear_dev's step.  With A the
+ * transmittance behind a step and D = (the emission behind it that reaches the end) - I_end,
+ *   A t (Ba - I_in) = A (Ba + g (Bb - Ba)) + D,   clamped to [-A t Imax, A t Ba]
+ * so no level radiance is stored; sums in a fixed order, no atomics: the same inputs give the same bits.  F agrees with
+ * lbl_column_flux_linear_dev's upward flux at the top to rounding, not to the bit: the two calls group the points of a
+ * thread differently (4, or 2 beyond two angles, against 4).
+ * LBL_ERR_BAD_ARG: everything lbl_column_jacobian_surface_dev or lbl_column_flux_linear_dev refuses (an edge temperature
+ * that is not finite and > 0 among it), with jac holding n_bands x (3 + 3 n_layers + n_terms) and jac_T_edge_spectra 2
+ * n_layers x n; "sweep_ieee_divisions" 1.  Everything is checked before anything is enqueued.  Stream-ordered.
+ *
+ * lbl_ray_jacobian_linear_dev: the arguments of lbl_ray_jacobian_surface_dev with T replaced by seg_T (2 per segment:
+ * seg_T[2 s] where the light enters segment s, seg_T[2 s + 1] where it leaves; a marker's pair is ignored), the forward
+ * model of lbl_ray_radiance_linear_dev without surface_down, and that call's radiance bit for bit (the same step on the same
+ * groups of points).  With lbl_ray_jacobian_surface_dev's A_s (the product over the elements after s):
+ *   dI/d ln tau_l = sum over the ray's segments s in l of A_s [tau_s t_s (Ba_s - I_s) + h(tau_s) (Bb_s - Ba_s)]
+ *   term m        = sum over the same segments of term_abs_coef[m][j] seg_length[s] A_s [t_s (Ba_s - I_s) + g'(tau_s) (Bb_s - Ba_s)]
+ *   dI/dTa_s      = A_s h(tau_s) dB(Ta_s)/dT,   dI/dTb_s = A_s g(tau_s) dB(Tb_s)/dT        per segment, not per layer
+ *   dI/dT_source, dI/de: lbl_ray_jacobian_surface_dev's
+ * Ray r, with c_r crossed layers, s_r segments that are not markers and m_r terms, owns 2 + c_r + 2 s_r + m_r rows: row 0
+ * dI/dT_source, row 1 dI/de, the c_r rows d ln tau in ascending layer order, then for each segment that is no marker, in
+ * order of travel, dI/dTa_s and dI/dTb_s, then the terms.  A segment's two rows are stored once and never added to; the
+ * layer rows and the terms keep lbl_ray_jacobian_dev's rule (the last segment stores, the earlier ones add).
+ * lbl_ray_jacobian_linear_rows returns that layout without a context.  A ray's rows and radiance do not depend on the rays
+ * it travels with, and the same inputs give the same bits.
+ * LBL_ERR_BAD_ARG: everything lbl_ray_jacobian_surface_dev or lbl_ray_radiance_linear_dev refuses (a segment temperature
+ * that is not finite and > 0, a marker's pair excepted), with jac holding the rows of this layout; "sweep_ieee_divisions" 1.
+ * Everything is checked before anything is enqueued; the host arrays are copied and not retained.  Stream-ordered. */
+int lbl_column_jacobian_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
+                                   const double* T_edge /* 2 n_layers: bottom, top */,
+                                   const double* depth, double range_min, double range_max, int64_t n,
+                                   lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top /* may be NULL */,
+                                   int n_angles, const double* mu, const double* weight,
+                                   int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                   lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                   int reflection /* 0 Lambertian, 1 specular */,
+                                   int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
+                                   lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra,
+                                   lbl_buffer* jac_T_edge_spectra /* 2 n_layers x n, may be NULL */,
+                                   lbl_buffer* jac_e_spectrum /* n, may be NULL */);
+int lbl_ray_jacobian_linear_rows(int n_layers, int n_rays, const int32_t* ray_first,
+                                 const int32_t* seg_layer /* -1: surface marker */,
+                                 int n_terms, const int32_t* term_layer,
+                                 int64_t* row_first /* n_rays + 1, may be NULL */, int64_t* rows);
+int lbl_ray_jacobian_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
+                                const double* seg_T /* 2 per segment: entry, exit */,
+                                double range_min, double range_max, int64_t n,
+                                int n_rays, const int32_t* ray_first,
+                                const int32_t* seg_layer /* -1: surface marker */, const double* seg_length,
+                                const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                                lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
+                                lbl_buffer* radiance /* n_rays x n, may be NULL */, lbl_buffer* jac /* rows x n */);
+
 /* ---- instrument channels (beyond the reference; ABI 5, backward compatible) -------------------------------------------
  * pyrad_amd.model.convolve / Atmosphere.observe: n_rows device-resident spectra on the base grid linspace(range_min,
  * range_max, n) convolved with an instrument line shape (ILS) onto n_channels channels, so that channel radiances and channel

@@ -139,6 +139,16 @@ SIGNATURES = {
                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P,
                                                C.c_double, _P, C.c_double, C.c_int, C.POINTER(_P), C.POINTER(C.c_int32), _P,
                                                _P]),
+    "lbl_column_jacobian_linear_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, _D, C.c_double, C.c_double, C.c_int64, _P,
+                                                 C.c_double, _P, C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_int64), _P, C.c_double, C.c_int, C.c_int, C.POINTER(_P),
+                                                 C.POINTER(C.c_int32), _P, _P, _P, _P]),
+    "lbl_ray_jacobian_linear_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "lbl_ray_jacobian_linear_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P,
+                                              C.c_double, _P, C.c_double, C.c_int, C.POINTER(_P), C.POINTER(C.c_int32), _P,
+                                              _P]),
     "lbl_ils_convolve_dev": (C.c_int, [_P, C.c_double, C.c_double, C.c_int64, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64),
                                        C.c_int64, _D, _D, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_int,
                                        C.c_double, _D, _P]),
@@ -244,19 +254,22 @@ def limit(name: str) -> int:
     return _limits[name]
 
 
-def ray_jacobian_rows(n_layers, ray_first, seg_layer, term_layer=(), surface=False):
+def ray_jacobian_rows(n_layers, ray_first, seg_layer, term_layer=(), surface=False, linear=False):
     """The rows of lbl_ray_jacobian_dev's ``jac`` (lbl_ray_jacobian_rows; no context needed): (row_first, rows) with
     row_first the n_rays + 1 first rows of the rays and rows the total.  Ray r owns [dI/dT_source, c x dI/d ln tau, c x
     dI/dT, its terms] for the c distinct layers it crosses in ascending order and the terms that lie in one of them.
     ``surface``: the rows of lbl_ray_jacobian_surface_dev (lbl_ray_jacobian_surface_rows) - a segment layer of -1 is a
-    surface marker without rows, and dI/de follows dI/dT_source."""
+    surface marker without rows, and dI/de follows dI/dT_source.  ``linear``: the rows of lbl_ray_jacobian_linear_dev
+    (lbl_ray_jacobian_linear_rows) - markers allowed, and ray r owns [dI/dT_source, dI/de, c x dI/d ln tau, (dI/dTa, dI/dTb)
+    per segment that is no marker in order of travel, its terms]."""
     i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
     i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None
     ray_first, seg_layer, term_layer = i32(ray_first), i32(seg_layer), i32(term_layer)
     lib = load()
     first = np.zeros(max(len(ray_first), 1), dtype=np.int64)
     rows = C.c_int64()
-    rc = (lib.lbl_ray_jacobian_surface_rows if surface else lib.lbl_ray_jacobian_rows)(int(n_layers), len(ray_first) - 1, i32p(ray_first), i32p(seg_layer), len(term_layer),
+    fn = lib.lbl_ray_jacobian_linear_rows if linear else lib.lbl_ray_jacobian_surface_rows if surface else lib.lbl_ray_jacobian_rows
+    rc = fn(int(n_layers), len(ray_first) - 1, i32p(ray_first), i32p(seg_layer), len(term_layer),
         i32p(term_layer), first.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(rows))
     if rc != LBL_OK:
         raise LblError(rc, (lib.lbl_last_error(None) or b"").decode())
@@ -685,6 +698,26 @@ class Context:
             *self._emissivity_args(emissivity), int(reflection), len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]),
             _arr(C.c_int32, [int(l) for l in term_layer]), _hb(jac), _hb(ln_tau_spectra), _hb(T_spectra), _hb(e_spectrum)))
 
+    def column_jacobian_linear_dev(self, abs_coef, edge_T, depth, range_min, range_max, n, mu, weight, band_first,
+                                   band_count, jac, emissivity=1.0, reflection=0, I_surface=None, surface_T=0.0, I_top=None,
+                                   term_abs_coef=(), term_layer=(), ln_tau_spectra=None, T_edge_spectra=None,
+                                   e_spectrum=None):
+        """Jacobians of the upward flux at the top with a Planck source linear in optical depth
+        (lbl_column_jacobian_linear_dev): column_jacobian_surface_dev's arguments with ``edge_T`` in place of the layers'
+        temperatures - per layer (bottom edge, top edge), as L pairs or 2 L numbers; ``jac`` receives len(band_first) x (3 +
+        3 L + len(term_abs_coef)) band sums [band][F, dF/dT_s, dF/de, L x dF/d ln tau, 2 L x dF/dT_edge (bottom, top per
+        layer), terms]; ``T_edge_spectra`` (optional, 2 L x n points) the spectral edge values.  The default ``emissivity`` 1
+        is the black surface."""
+        edge_T = _as_f64(edge_T).reshape(-1)
+        if len(edge_T) != 2 * len(abs_coef):
+            raise ValueError("column_jacobian_linear_dev: two edge temperatures per layer")
+        self.check(self.lib.lbl_column_jacobian_linear_dev(
+            *self._column_args(abs_coef, edge_T, depth, range_min, range_max, n, I_surface, surface_T, (_hb(I_top),), mu,
+                               weight, band_first, band_count),
+            *self._emissivity_args(emissivity), int(reflection), len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]),
+            _arr(C.c_int32, [int(l) for l in term_layer]), _hb(jac), _hb(ln_tau_spectra), _hb(T_edge_spectra),
+            _hb(e_spectrum)))
+
     def ray_radiance_dev(self, abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length, source_kind,
                          radiance, I_source=None, source_T=0.0, transmittance=None):
         """Radiance along ray paths through a column (lbl_ray_radiance_dev): ray r crosses the segments ray_first[r] ..
@@ -781,6 +814,30 @@ class Context:
                              "layer per term")
         self.check(self.lib.lbl_ray_jacobian_surface_dev(
             self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
+            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
+            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
+            *self._emissivity_args(emissivity), len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]),
+            _arr(C.c_int32, [int(l) for l in term_layer]), _hb(radiance), _hb(jac)))
+
+    def ray_jacobian_linear_dev(self, abs_coef, seg_T, range_min, range_max, n, ray_first, seg_layer, seg_length,
+                                source_kind, jac, emissivity=1.0, I_source=None, source_T=0.0, term_abs_coef=(), term_layer=(),
+                                radiance=None):
+        """Weighting functions of the radiance along ray paths with a Planck source linear in optical depth
+        (lbl_ray_jacobian_linear_dev): ray_jacobian_surface_dev's arguments with ``seg_T`` in place of the layers'
+        temperatures, as ray_radiance_linear_dev takes them; ``jac`` receives ray_jacobian_rows(..., linear=True) rows of n
+        doubles - per ray [dI/dT_source, dI/de, dI/d ln tau of every crossed layer, (dI/dTa, dI/dTb) of every segment that
+        is no marker, the terms in crossed layers].  The default ``emissivity`` 1 is the black surface."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
+        seg_length = _as_f64(seg_length)
+        seg_T = _as_f64(seg_T).reshape(-1)
+        if (len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length) or len(seg_T) != 2 * len(seg_layer)
+                or len(term_abs_coef) != len(term_layer)):
+            raise ValueError("ray_jacobian_linear_dev: one ray_first per ray and one more, one length and two temperatures per "
+                             "segment layer, one layer per term")
+        self.check(self.lib.lbl_ray_jacobian_linear_dev(
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), seg_T.ctypes.data_as(_D),
             float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
             seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
             *self._emissivity_args(emissivity), len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]),

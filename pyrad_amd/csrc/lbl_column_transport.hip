@@ -1,8 +1,9 @@
 // Column transport (include/pyrad_hip.h, "level fluxes", "Jacobians" and "ray paths"): argument checking and the launch
 // sequences of lbl_column_flux_dev, lbl_column_jacobian_dev, lbl_ray_radiance_dev and lbl_ray_jacobian_dev, and of their
 // variants over a reflecting surface, lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev, lbl_column_jacobian_surface_dev
-// and lbl_ray_jacobian_surface_dev, and of the linear-source variants lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev.
-// The kernels are K5c, K5d, K5e, K5f, K5g, K5h and K5i of lbl_kernels.hip; the context's internals
+// and lbl_ray_jacobian_surface_dev, of the linear-source variants lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev, and
+// of their Jacobians lbl_column_jacobian_linear_dev and lbl_ray_jacobian_linear_dev.
+// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i and K5j of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -248,19 +249,22 @@ extern "C" int lbl_column_flux_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer
 } LBL_GUARD_END(ctx)
 
 // What lbl_column_jacobian_dev and lbl_column_jacobian_surface_dev check behind check_column, then the JacArgs part of the
-// argument block filled; `head` values per band come before the layers' (2, or 3 with dF/de).
+// argument block filled; `head` values per band come before the layers' (2, or 3 with dF/de).  `edges` temperatures per
+// layer in T, as many temperature values per layer and band and rows per layer in jac_T_spectra: 1, or 2 with the linear
+// source (lbl_column_jacobian_linear_dev), where rT receives the bottom edges'.
 static int check_jacobian(lbl_ctx* ctx, JacArgs* a, int head, int n_layers, const double* T, int64_t n, double surface_T,
                           int n_angles, const double* weight, int n_bands, int n_terms, lbl_buffer* const* term_abs_coef,
                           const int32_t* term_layer, lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra,
-                          lbl_buffer* jac_T_spectra) {
+                          lbl_buffer* jac_T_spectra, int edges = 1) {
     int rc;
     if (n_terms < 0 || n_terms > kMaxJacobianTerms)
         return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d molecule terms", kMaxJacobianTerms);
     if (n_terms > 0 && (!term_abs_coef || !term_layer)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
-    const int nv = head + 2 * n_layers + n_terms;
+    const int nv = head + (1 + edges) * n_layers + n_terms;
     if ((rc = ctx_check_buffer(ctx, jac, (int64_t)n_bands * nv, "jac", true))) return rc;
     if ((rc = ctx_check_buffer(ctx, jac_ln_tau_spectra, (int64_t)n_layers * n, "jac_ln_tau_spectra", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, jac_T_spectra, (int64_t)n_layers * n, "jac_T_spectra", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, jac_T_spectra, (int64_t)edges * n_layers * n, edges == 1 ? "jac_T_spectra" : "jac_T_edge_spectra", false)))
+        return rc;
     // the molecule terms, sorted by layer (stable): layer l reads [layer_term[l], layer_term[l + 1])
     for (int t = 0; t < n_terms; ++t) {
         if (term_layer[t] < 0 || term_layer[t] >= n_layers)
@@ -277,7 +281,7 @@ static int check_jacobian(lbl_ctx* ctx, JacArgs* a, int head, int n_layers, cons
             a->term_slot[pos] = t;
         }
     }
-    for (int l = 0; l < n_layers; ++l) a->rT[l] = 1.0 / T[l];
+    for (int l = 0; l < n_layers; ++l) a->rT[l] = 1.0 / T[edges * l];
     for (int k = 0; k < n_angles; ++k) a->wrmu[k] = weight[k] * a->rmu[k];
     a->r_surface_T = surface_T > 0 ? 1.0 / surface_T : 0.0;
     a->ln_tau_spec = jac_ln_tau_spectra ? buffer_data(jac_ln_tau_spectra) : nullptr;
@@ -310,24 +314,24 @@ extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* c
     });
 } LBL_GUARD_END(ctx)
 
-extern "C" int lbl_column_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
-                                               const double* depth, double range_min, double range_max, int64_t n,
-                                               lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
-                                               const double* mu, const double* weight, int n_bands,
-                                               const int64_t* band_first, const int64_t* band_count, lbl_buffer* emissivity,
-                                               double emissivity_all, int reflection, int n_terms,
-                                               lbl_buffer* const* term_abs_coef, const int32_t* term_layer, lbl_buffer* jac,
-                                               lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra,
-                                               lbl_buffer* jac_e_spectrum) try {
-    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
-    std::vector<char> blk(sizeof(SurfaceJacArgs), 0);
-    SurfaceJacArgs* a = (SurfaceJacArgs*)blk.data();
+// lbl_column_jacobian_surface_dev (Args = SurfaceJacArgs, T per layer, jac_T_spectra L x n) and lbl_column_jacobian_linear_dev
+// (Args = LinearJacArgs, T the 2 n_layers edge temperatures, jac_T_spectra 2 L x n, `linear` its part of the block): the same
+// checks in the same order and the same launch sequence around launch(...) at `np` points per thread.
+template <class Args, class Launch>
+static int surface_jacobian_call(lbl_ctx* ctx, Args* a, LinearJacArgs* linear, int np, Launch launch, int n_layers,
+                                 lbl_buffer* const* abs_coef, const double* T, const double* depth, double range_min,
+                                 double range_max, int64_t n, lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                                 int n_angles, const double* mu, const double* weight, int n_bands, const int64_t* band_first,
+                                 const int64_t* band_count, lbl_buffer* emissivity, double emissivity_all, int reflection,
+                                 int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer, lbl_buffer* jac,
+                                 lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra, lbl_buffer* jac_e_spectrum) {
+    const int edges = linear ? 2 : 1;
     int rc;
     if ((rc = check_column(ctx, "Jacobians", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface, surface_T,
-                           n_angles, mu, weight, n_bands, band_first, band_count)))
+                           n_angles, mu, weight, n_bands, band_first, band_count, linear ? linear->pbkT_top : nullptr)))
         return rc;
     if ((rc = check_jacobian(ctx, a, 3, n_layers, T, n, surface_T, n_angles, weight, n_bands, n_terms, term_abs_coef,
-                             term_layer, jac, jac_ln_tau_spectra, jac_T_spectra)))
+                             term_layer, jac, jac_ln_tau_spectra, jac_T_spectra, edges)))
         return rc;
     if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
     if ((rc = ctx_check_buffer(ctx, jac_e_spectrum, n, "jac_e_spectrum", false))) return rc;
@@ -344,12 +348,55 @@ extern "C" int lbl_column_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_b
     a->w_sum = w_sum;
     a->e_spec = jac_e_spectrum ? buffer_data(jac_e_spectrum) : nullptr;
     a->reflection = reflection;
-    const int nv = 3 + 2 * n_layers + n_terms;
-    return run_column(ctx, a, surface_jacobian_points(n_angles), nv, n_bands, band_count, {a->ln_tau_spec, a->T_spec},
+    double* T_spec_hi = nullptr;
+    if (linear) {
+        // (the edge spectra are one buffer of 2 L rows: zeroed as two halves of L rows; the kernel reads T_edge_spec alone)
+        for (int l = 0; l < n_layers; ++l) linear->rT_top[l] = 1.0 / T[2 * l + 1];
+        linear->T_edge_spec = a->T_spec;
+        T_spec_hi = a->T_spec ? a->T_spec + (size_t)n_layers * (size_t)n : nullptr;
+    }
+    const int nv = 3 + (1 + edges) * n_layers + n_terms;
+    return run_column(ctx, a, np, nv, n_bands, band_count, {a->ln_tau_spec, a->T_spec, T_spec_hi},
                       (size_t)n_layers * (size_t)n * sizeof(double),
-                      [&](const SurfaceJacArgs* d, double* partial, int b, hipStream_t s) {
-        launch_surface_jacobian(d, n_layers, n_angles, n_terms, band_first[b], band_count[b], partial, buffer_data(jac) + (size_t)b * nv, s);
+                      [&](const Args* d, double* partial, int b, hipStream_t s) {
+        launch(d, n_layers, n_angles, n_terms, band_first[b], band_count[b], partial, buffer_data(jac) + (size_t)b * nv, s);
     }, a->e_spec);
+}
+
+extern "C" int lbl_column_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                               const double* depth, double range_min, double range_max, int64_t n,
+                                               lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
+                                               const double* mu, const double* weight, int n_bands,
+                                               const int64_t* band_first, const int64_t* band_count, lbl_buffer* emissivity,
+                                               double emissivity_all, int reflection, int n_terms,
+                                               lbl_buffer* const* term_abs_coef, const int32_t* term_layer, lbl_buffer* jac,
+                                               lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra,
+                                               lbl_buffer* jac_e_spectrum) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(SurfaceJacArgs), 0);
+    return surface_jacobian_call(ctx, (SurfaceJacArgs*)blk.data(), nullptr, surface_jacobian_points(n_angles),
+                                 launch_surface_jacobian, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
+                                 surface_T, I_top, n_angles, mu, weight, n_bands, band_first, band_count, emissivity,
+                                 emissivity_all, reflection, n_terms, term_abs_coef, term_layer, jac, jac_ln_tau_spectra,
+                                 jac_T_spectra, jac_e_spectrum);
+} LBL_GUARD_END(ctx)
+
+extern "C" int lbl_column_jacobian_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T_edge,
+                                              const double* depth, double range_min, double range_max, int64_t n,
+                                              lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_angles,
+                                              const double* mu, const double* weight, int n_bands,
+                                              const int64_t* band_first, const int64_t* band_count, lbl_buffer* emissivity,
+                                              double emissivity_all, int reflection, int n_terms,
+                                              lbl_buffer* const* term_abs_coef, const int32_t* term_layer, lbl_buffer* jac,
+                                              lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_edge_spectra,
+                                              lbl_buffer* jac_e_spectrum) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(LinearJacArgs), 0);
+    LinearJacArgs* a = (LinearJacArgs*)blk.data();
+    return surface_jacobian_call(ctx, a, a, linear_jacobian_points(n_angles), launch_linear_jacobian, n_layers, abs_coef,
+                                 T_edge, depth, range_min, range_max, n, I_surface, surface_T, I_top, n_angles, mu, weight,
+                                 n_bands, band_first, band_count, emissivity, emissivity_all, reflection, n_terms,
+                                 term_abs_coef, term_layer, jac, jac_ln_tau_spectra, jac_T_edge_spectra, jac_e_spectrum);
 } LBL_GUARD_END(ctx)
 
 static size_t round8(size_t b) { return (b + 7) & ~(size_t)7; }
@@ -615,19 +662,23 @@ extern "C" int lbl_ray_radiance_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffe
 
 // The rows of lbl_ray_jacobian_dev (include/pyrad_hip.h): per ray the distinct layers it crosses in ascending order and
 // the terms whose layer it crosses in term order; `head` rows come before the layers' (1, or 2 with dI/de: the surface entry
-// points, whose markers are no layers and have no rows).  The lists are checked already.
+// points, whose markers are no layers and have no rows).  The lists are checked already.  `linear`
+// (lbl_ray_jacobian_linear_dev): the c temperature rows of the layers give way to two rows per real segment in order of
+// travel, seg_Trow names the first of each pair relative to the ray's first row, and the terms follow them.
 struct RayRows {
     std::vector<int64_t> row_first;          // n_rays + 1
     std::vector<int32_t> crossed;            // per ray: c
     std::vector<int32_t> seg_slot;           // per segment: the rank of its layer among the ray's | kRayRowStore
     std::vector<int32_t> ray_terms;          // per ray: start of its table in term_row
     std::vector<int32_t> term_row;           // per set of crossed layers: the row of original term m, relative (-1: not crossed)
+    std::vector<int32_t> seg_Trow;           // per segment (`linear`): the row of its dTa, relative; 0 for a marker
 };
 static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer, int n_terms,
-                     const int32_t* term_layer, int head, RayRows* R) {
+                     const int32_t* term_layer, int head, RayRows* R, bool linear = false) {
     R->row_first.assign(1, 0);
     R->crossed.clear(); R->ray_terms.clear(); R->term_row.clear();
     R->seg_slot.assign((size_t)ray_first[n_rays], 0);
+    R->seg_Trow.assign(linear ? (size_t)ray_first[n_rays] : 0, 0);
     std::map<std::vector<int32_t>, int32_t> tables;
     std::vector<int32_t> rank(n_layers);
     for (int r = 0; r < n_rays; ++r) {
@@ -645,13 +696,24 @@ static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const i
             R->seg_slot[s] = rank[seg_layer[s]] | (seen[seg_layer[s]] ? 0 : kRayRowStore);
             seen[seg_layer[s]] = 1;
         }
+        // the rows between the head and the terms: 2 c, or c and two per real segment
+        int body = 2 * c;
+        if (linear) {
+            body = c;
+            for (int s = ray_first[r]; s < ray_first[r + 1]; ++s) {
+                if (seg_layer[s] == kRaySurfaceMarker) continue;
+                R->seg_Trow[s] = head + body;
+                body += 2;
+            }
+            set.push_back(n_layers + body);          // (the terms' rows depend on the number of segments too)
+        }
         int m_r = 0;
         for (int m = 0; m < n_terms; ++m) m_r += rank[term_layer[m]] >= 0;
         if (n_terms > 0) {
             auto it = tables.find(set);
             if (it == tables.end()) {
                 it = tables.emplace(set, (int32_t)R->term_row.size()).first;
-                int next = head + 2 * c;
+                int next = head + body;
                 for (int m = 0; m < n_terms; ++m) R->term_row.push_back(rank[term_layer[m]] >= 0 ? next++ : -1);
             }
             R->ray_terms.push_back(it->second);
@@ -659,7 +721,7 @@ static void ray_rows(int n_layers, int n_rays, const int32_t* ray_first, const i
             R->ray_terms.push_back(0);
         }
         R->crossed.push_back(c);
-        R->row_first.push_back(R->row_first.back() + head + 2 * c + m_r);
+        R->row_first.push_back(R->row_first.back() + head + body + m_r);
     }
 }
 
@@ -674,13 +736,13 @@ static int check_ray_terms(lbl_ctx* ctx, int n_layers, int n_terms, const int32_
 }
 
 static int ray_jacobian_rows(bool surface, int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
-                             int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows) {
+                             int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows, bool linear = false) {
     int rc;
     if (!rows) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "rows is NULL");
     if ((rc = check_ray_lists(nullptr, n_layers, n_rays, ray_first, seg_layer, surface))) return rc;
     if ((rc = check_ray_terms(nullptr, n_layers, n_terms, term_layer))) return rc;
     RayRows R;
-    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, surface ? 2 : 1, &R);
+    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, surface ? 2 : 1, &R, linear);
     if (row_first) memcpy(row_first, R.row_first.data(), (size_t)(n_rays + 1) * sizeof(int64_t));
     *rows = R.row_first.back();
     return LBL_OK;
@@ -696,9 +758,15 @@ extern "C" int lbl_ray_jacobian_surface_rows(int n_layers, int n_rays, const int
     return ray_jacobian_rows(true, n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, row_first, rows);
 } LBL_GUARD_END(nullptr)
 
+extern "C" int lbl_ray_jacobian_linear_rows(int n_layers, int n_rays, const int32_t* ray_first, const int32_t* seg_layer,
+                                            int n_terms, const int32_t* term_layer, int64_t* row_first, int64_t* rows) try {
+    return ray_jacobian_rows(true, n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, row_first, rows, true);
+} LBL_GUARD_END(nullptr)
+
 // lbl_ray_jacobian_dev, and with `surface` lbl_ray_jacobian_surface_dev: markers among the segment layers, the emissivity
-// behind the header, one more row per ray.
-static int ray_jacobian_call(lbl_ctx* ctx, bool surface, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+// behind the header, one more row per ray.  With `linear` (and `surface`) lbl_ray_jacobian_linear_dev: T holds two
+// temperatures per segment, their Planck exponents, reciprocals and rows follow the other tables.
+static int ray_jacobian_call(lbl_ctx* ctx, bool surface, bool linear, int n_layers, lbl_buffer* const* abs_coef, const double* T,
                              double range_min, double range_max, int64_t n, int n_rays, const int32_t* ray_first,
                              const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
                              lbl_buffer* I_source, double source_T, lbl_buffer* emissivity, double emissivity_all,
@@ -706,14 +774,16 @@ static int ray_jacobian_call(lbl_ctx* ctx, bool surface, int n_layers, lbl_buffe
                              lbl_buffer* jac) {
     if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     // the argument block: header, K5e's tables, row_first, ray_crossed, seg_slot, ray_terms, term_row
-    const size_t header = surface ? sizeof(RaySurfaceJacArgs) : sizeof(RayJacArgs);
+    const size_t header = linear ? sizeof(LinearRayJacArgs) : surface ? sizeof(RaySurfaceJacArgs) : sizeof(RayJacArgs);
     std::vector<char> head(header, 0);
     RayJacArgs* a = (RayJacArgs*)head.data();
     std::vector<int32_t> order;
+    std::vector<double> seg_pbkT;
     size_t off = 0;
     int rc;
-    if ((rc = check_rays(ctx, a, header, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first,
-                         seg_layer, seg_length, source_kind, I_source, source_T, radiance, false, nullptr, surface, &order, &off)))
+    if ((rc = check_rays(ctx, a, header, n_layers, abs_coef, linear ? nullptr : T, range_min, range_max, n, n_rays, ray_first,
+                         seg_layer, seg_length, source_kind, I_source, source_T, radiance, false, nullptr, surface, &order, &off,
+                         linear ? T : nullptr, linear ? &seg_pbkT : nullptr)))
         return rc;
     if (surface) {
         if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
@@ -726,7 +796,7 @@ static int ray_jacobian_call(lbl_ctx* ctx, bool surface, int n_layers, lbl_buffe
     for (int t = 0; t < n_terms; ++t)
         if ((rc = ctx_check_buffer(ctx, term_abs_coef[t], n, "term_abs_coef", true))) return rc;
     RayRows R;
-    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, surface ? 2 : 1, &R);
+    ray_rows(n_layers, n_rays, ray_first, seg_layer, n_terms, term_layer, surface ? 2 : 1, &R, linear);
     const int64_t rows = R.row_first.back();
     if (n > INT64_MAX / rows) return column_fail(ctx, LBL_ERR_BAD_ARG, "rows x n overflows");
     if ((rc = ctx_check_buffer(ctx, jac, rows * n, "jac", true))) return rc;
@@ -745,7 +815,7 @@ static int ray_jacobian_call(lbl_ctx* ctx, bool surface, int n_layers, lbl_buffe
     std::vector<int32_t> term_row(R.term_row.size());
     for (size_t base = 0; base < term_row.size(); base += (size_t)n_terms)
         for (int pos = 0; pos < n_terms; ++pos) term_row[base + pos] = R.term_row[base + sorted[pos]];
-    for (int l = 0; l < n_layers; ++l) a->rT[l] = 1.0 / T[l];
+    for (int l = 0; !linear && l < n_layers; ++l) a->rT[l] = 1.0 / T[l];
     a->r_source_T = source_T > 0 ? 1.0 / source_T : 0.0;
     a->jac = buffer_data(jac);
     a->n_terms = n_terms;
@@ -755,6 +825,12 @@ static int ray_jacobian_call(lbl_ctx* ctx, bool surface, int n_layers, lbl_buffe
     a->off_seg_slot = (long long)off;    off += round8((size_t)n_seg * sizeof(int32_t));
     a->off_ray_terms = (long long)off;   off += round8((size_t)n_rays * sizeof(int32_t));
     a->off_term_row = (long long)off;    off += round8(term_row.size() * sizeof(int32_t));
+    if (linear) {
+        LinearRayJacArgs* la = (LinearRayJacArgs*)head.data();
+        la->off_seg_pbkT = (long long)off; off += 2 * (size_t)n_seg * sizeof(double);
+        la->off_seg_rT = (long long)off;   off += 2 * (size_t)n_seg * sizeof(double);
+        la->off_seg_Trow = (long long)off; off += round8((size_t)n_seg * sizeof(int32_t));
+    }
     std::vector<char> blk(off, 0);
     memcpy(blk.data(), head.data(), head.size());
     fill_ray_tables(blk.data(), *a, n_rays, ray_first, seg_layer, seg_length, source_kind, order);
@@ -763,11 +839,20 @@ static int ray_jacobian_call(lbl_ctx* ctx, bool surface, int n_layers, lbl_buffe
     if (n_seg > 0) memcpy(blk.data() + a->off_seg_slot, R.seg_slot.data(), (size_t)n_seg * sizeof(int32_t));
     memcpy(blk.data() + a->off_ray_terms, R.ray_terms.data(), (size_t)n_rays * sizeof(int32_t));
     if (!term_row.empty()) memcpy(blk.data() + a->off_term_row, term_row.data(), term_row.size() * sizeof(int32_t));
+    if (linear && n_seg > 0) {
+        const LinearRayJacArgs* la = (const LinearRayJacArgs*)head.data();
+        memcpy(blk.data() + la->off_seg_pbkT, seg_pbkT.data(), 2 * (size_t)n_seg * sizeof(double));
+        double* rT = (double*)(blk.data() + la->off_seg_rT);
+        for (int s = 0; s < n_seg; ++s)
+            for (int e = 0; e < 2; ++e) rT[2 * s + e] = seg_layer[s] == kRaySurfaceMarker ? 0.0 : 1.0 / T[2 * s + e];
+        memcpy(blk.data() + la->off_seg_Trow, R.seg_Trow.data(), (size_t)n_seg * sizeof(int32_t));
+    }
 
     void* d_args = nullptr;
     if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
     COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
-    if (surface) launch_ray_surface_jacobian((const RaySurfaceJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
+    if (linear) launch_linear_ray_jacobian((const LinearRayJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
+    else if (surface) launch_ray_surface_jacobian((const RaySurfaceJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
     else launch_ray_jacobian((const RayJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
@@ -778,7 +863,7 @@ extern "C" int lbl_ray_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
                                     const int32_t* seg_layer, const double* seg_length, const int32_t* source_kind,
                                     lbl_buffer* I_source, double source_T, int n_terms, lbl_buffer* const* term_abs_coef,
                                     const int32_t* term_layer, lbl_buffer* radiance, lbl_buffer* jac) try {
-    return ray_jacobian_call(ctx, false, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
+    return ray_jacobian_call(ctx, false, false, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
                              seg_length, source_kind, I_source, source_T, nullptr, 1.0, n_terms, term_abs_coef, term_layer,
                              radiance, jac);
 } LBL_GUARD_END(ctx)
@@ -790,7 +875,19 @@ extern "C" int lbl_ray_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_buff
                                             lbl_buffer* emissivity, double emissivity_all, int n_terms,
                                             lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
                                             lbl_buffer* radiance, lbl_buffer* jac) try {
-    return ray_jacobian_call(ctx, true, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
+    return ray_jacobian_call(ctx, true, false, n_layers, abs_coef, T, range_min, range_max, n, n_rays, ray_first, seg_layer,
+                             seg_length, source_kind, I_source, source_T, emissivity, emissivity_all, n_terms, term_abs_coef,
+                             term_layer, radiance, jac);
+} LBL_GUARD_END(ctx)
+
+extern "C" int lbl_ray_jacobian_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* seg_T,
+                                           double range_min, double range_max, int64_t n, int n_rays,
+                                           const int32_t* ray_first, const int32_t* seg_layer, const double* seg_length,
+                                           const int32_t* source_kind, lbl_buffer* I_source, double source_T,
+                                           lbl_buffer* emissivity, double emissivity_all, int n_terms,
+                                           lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
+                                           lbl_buffer* radiance, lbl_buffer* jac) try {
+    return ray_jacobian_call(ctx, true, true, n_layers, abs_coef, seg_T, range_min, range_max, n, n_rays, ray_first, seg_layer,
                              seg_length, source_kind, I_source, source_T, emissivity, emissivity_all, n_terms, term_abs_coef,
                              term_layer, radiance, jac);
 } LBL_GUARD_END(ctx)

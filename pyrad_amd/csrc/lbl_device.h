@@ -376,6 +376,28 @@ struct RaySurfaceJacArgs : RayJacArgs {
 void launch_ray_surface_jacobian(const RaySurfaceJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
                                  hipStream_t s);
 
+// Jacobians of the linear-in-optical-depth Planck source (K5j, lbl_column_transport.hip: lbl_column_jacobian_linear_dev,
+// lbl_ray_jacobian_linear_dev): K5h's walks with K5i's step, d/d ln tau through g' and one temperature row per layer edge
+// or segment end.  Values per band: [F_top, dF/dT_s, dF/de, L x d ln tau, 2 L x dT_edge (bottom, top per layer), n_terms x
+// term]; a ray's rows: [dT_source, de, c x d ln tau, 2 per real segment in order of travel (dTa, dTb), its terms].  JacArgs'
+// rT holds 1 / T of the bottom edges and T_spec is not used.
+struct LinearJacArgs : SurfaceJacArgs {
+    double pbkT_top[kMaxLayers];        // 100 h c / k / T at the top edge of layer l; ColumnRT's pbkT holds the bottom edge
+    double rT_top[kMaxLayers];          // 1 / T at the top edge
+    double* T_edge_spec;                // optional: 2 L x n spectral dF/dT_edge
+};
+// the points per thread of linear_jacobian_kernel for n_angles (its partials are sized by it)
+int linear_jacobian_points(int n_angles);
+void launch_linear_jacobian(const LinearJacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first,
+                            long long count, double* partial, double* jac, hipStream_t s);
+struct LinearRayJacArgs : RaySurfaceJacArgs {
+    long long off_seg_pbkT;             // 2 n_segments doubles: 100 h c / k / T where the light enters and leaves the segment
+    long long off_seg_rT;               // 2 n_segments doubles: 1 / T likewise (a marker's pairs are 0 and never read)
+    long long off_seg_Trow;             // n_segments x int32: the row of the segment's dTa relative to the ray's first row
+};
+void launch_linear_ray_jacobian(const LinearRayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
+                                hipStream_t s);
+
 // Instrument channels (K8, lbl_instrument.hip: lbl_ils_convolve_dev): n_rows spectra on the base grid convolved with an
 // instrument line shape onto n_channels channels.  One argument block per call: this header, then the arrays it names by
 // their byte offset from the block's start (the block's device address is known only after it is uploaded).

@@ -26,6 +26,9 @@
 //                              and d/d emissivity (jacobians(), pathJacobians(), observe() with an emissivity; beyond the reference)
 //   K5i linear_flux_kernel, linear_ray_kernel   K5g's two kernels with a Planck source linear in optical depth between two
 //                              temperatures per layer or segment (fluxes() and radiance() with planck="linear"; beyond the reference)
+//   K5j linear_jacobian_kernel, ray_linear_jacobian_kernel   K5h's two kernels with K5i's step: d ln tau through g', one
+//                              temperature row per layer edge or segment end (jacobiansLinear(), pathJacobiansLinear(),
+//                              observeLinear(); beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -5031,6 +5034,478 @@ __global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurf
 }
 
 // ----------------------------------------------------------------------------------------
+// K5j: Jacobians of the linear-in-optical-depth Planck source (lbl_column_jacobian_linear_dev, lbl_ray_jacobian_linear_dev;
+// the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// K5h's walks with K5i's step I <- t I + (1 - t) Ba + g (Bb - Ba) = t I + h Ba + g Bb, h = (1 - t) - g = tau g'(tau)
+// (linear_source_g, linear_source_dg of lbl_linear_source.h).  With A the transmittance behind the step and D = E - I_final,
+// E the emission behind the step that reaches the end (K5d's identity with the step's whole emission in it),
+//     A t (Ba - I_in) = A (Ba + g (Bb - Ba)) + D,   clamped to [-A t Imax, A t Ba],        D <- D + A ((1 - t) Ba + g (Bb - Ba)),
+// so no level radiance is stored here either.  Per step G = that + A g' (Bb - Ba): d ln tau = tau G and a term = k_m x G (no
+// division by tau: a point without absorption stays finite), dTa = A h dB(Ta)/dT, dTb = A g dB(Tb)/dT.
+// Per point and step: two Planck values with their temperature derivatives (two exps per thread on the fast path), and per
+// angle or ray one exp, one g and one g'.
+
+// Ba, Bb and their temperature derivatives for the thread's point p (E0: the thread's two exps on the fast path)
+template <bool FAST>
+__device__ __forceinline__ void linear_planck_pair(bool first, double nu, double nu0, double pa_n, double pbkT_a, double pbkT_b,
+                                                   double Ea0, double Eb0, double rT_a, double rT_b, double& Ba, double& Bb,
+                                                   double& dBa, double& dBb) {
+    Ba = fold_planck<FAST, true>(first, nu, nu0, pa_n, pbkT_a, Ea0, rT_a, &dBa);
+    Bb = fold_planck<FAST, true>(first, nu, nu0, pa_n, pbkT_b, Eb0, rT_b, &dBb);
+}
+
+// Column: surface_jacobian_kernel's three walks.  Walk 1 is linear_flux_kernel's downward walk (entered at the top edge,
+// left at the bottom edge) with Dmax and Ttot; the surface is K5h's; walk 2 carries the upward leg (entered at the bottom
+// edge) and the mirrored downward leg, walk 3 the upward leg's derivatives.  Both later walks add to the band slots; of the
+// spectra walk 2 stores and walk 3 adds to what the same thread stored.  Band slots: [F, dT_s, de, L x ln tau, 2 L x T_edge
+// (bottom, top), terms].
+// Points per thread: K5h's - 4 with one and two angles, 2 beyond.  The state is its six values per angle and point, and a
+// step keeps four Planck values, g, g' and h beside them: 256 VGPRs and up to 202 AGPRs at one wave per SIMD, no scratch
+// (DESIGN.md "K5j").
+template <int NA> constexpr int linear_jacobian_np() { return NA <= 2 ? 4 : 2; }
+template <int NP, int NA>
+__global__ __launch_bounds__(256) void linear_jacobian_kernel(const LinearJacArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                              long long lo1, long long n1, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    constexpr int kSlot = 3 + 3 * kMaxLayers + kMaxJacobianTerms;
+    __shared__ double acc[4 * kSlot];            // [wave][F_top, dT_s, de, L x ln tau, 2 L x T_edge, terms]
+    const LinearJacArgs& A = *Ap;
+    const int L = A.n_layers;
+    const int nv = 3 + 3 * L + A.n_terms;
+    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
+    __syncthreads();
+    double* my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    auto add = [&](int slot, double s) {
+        s = wave_sum(s);
+        if (lane0) my[slot] += s;
+    };
+    const long long total = n0 + n1;
+    const long long stride = (long long)gridDim.x * blockDim.x * NP;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
+    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
+        const long long q = q0 + (long long)threadIdx.x * NP;
+        const bool active = q < total;
+        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        // walk 1: I = Id, Dm = Dmax, Ak = Ttot;  walk 2: I = Iu, Imax, Ck = C, Dp = D', Dm, Ak = Qf;  walk 3: I = D, Imax, Ak = A
+        double nu[NP], pa_n[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP], Ck[NA][NP], Dp[NA][NP], Dm[NA][NP];
+        column_points<NP>(A, j, nu, pa_n);
+        const bool fast = fold_fast_path<NP>(A, nu, active);
+        auto terms = [&](int l, const double (&Gd)[NP]) {
+            for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
+                const vec km = load_points<NP>(A.term_k[t], j);
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < NP; ++p) s += active ? nan_to_num(km[p] * Gd[p]) : 0.0;
+                add(3 + 3 * L + A.term_slot[t], s);
+            }
+        };
+        // one point's values of a layer into the spectra (walk 2 stores, walk 3 adds) and the thread's sums
+        auto emit = [&](bool store, int l, int p, double dtau, double gbot, double gtop, double& s_tau, double& s_bot,
+                        double& s_top) __attribute__((always_inline)) {
+            if (active && A.ln_tau_spec) {
+                double* o = A.ln_tau_spec + (long long)l * A.n + j + p;
+                *o = store ? dtau : *o + dtau;
+            }
+            if (active && A.T_edge_spec) {
+                double* o = A.T_edge_spec + (long long)(2 * l) * A.n + j + p;
+                *o = store ? gbot : *o + gbot;
+                o += A.n;
+                *o = store ? gtop : *o + gtop;
+            }
+            s_tau += active ? nan_to_num(dtau) : 0.0;
+            s_bot += active ? nan_to_num(gbot) : 0.0;
+            s_top += active ? nan_to_num(gtop) : 0.0;
+        };
+        auto first_down = [&](auto fast_tag, int l, vec v) __attribute__((always_inline)) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double depth = A.depth[l];
+            linear_step<FAST, NP>(nu, pa_n, A.pbkT_top[l], A.pbkT[l], v, [&](int p, double kp, double Ba, double dB) __attribute__((always_inline)) {
+                const double tau = kp * depth;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double x = tau * A.rmu[k];
+                    const double tr = exp_neg_budget(x);
+                    I[k][p] = linear_update<FAST>(x, tr, I[k][p], Ba, dB);
+                    Dm[k][p] = fmax(Dm[k][p], I[k][p]);
+                    Ak[k][p] = Ak[k][p] * tr;
+                }
+            });
+        };
+        auto up = [&](auto fast_tag, int l, vec v) __attribute__((always_inline)) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double pbkT = A.pbkT[l], pbkT_top = A.pbkT_top[l], depth = A.depth[l], rT = A.rT[l], rT_top = A.rT_top[l];
+            double E0 = 0.0, E0_top = 0.0;
+            if (FAST) {
+                E0 = exp_clamped(nu[0] * pbkT);
+                E0_top = exp_clamped(nu[0] * pbkT_top);
+            }
+            double s_tau = 0.0, s_bot = 0.0, s_top = 0.0, Gd[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+                double Bbot, Btop, dBbot, dBtop;
+                linear_planck_pair<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT, pbkT_top, E0, E0_top, rT, rT_top, Bbot, Btop, dBbot, dBtop);
+                const double dBu = Btop - Bbot, dBd = Bbot - Btop;
+                double G = 0.0, gbot = 0.0, gtop = 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double x = tau * A.rmu[k];
+                    const double tr = exp_neg_budget(x);
+                    const double g = linear_source_g(x, tr);
+                    const double dg = linear_source_dg(x, tr);
+                    const double h = x * dg;
+                    // the downward leg through this layer (top edge to bottom edge), seen through the surface
+                    const double Ct = Ck[k][p] * tr;
+                    const double gd = fmin(fmax(Ck[k][p] * (Btop + g * dBd) + Dp[k][p], -(Ct * Dm[k][p])), Ct * Btop);
+                    G = fma(A.wrmu[k], Ak[k][p] * (gd + Ck[k][p] * (dg * dBd)), G);
+                    gtop = fma(A.w[k], Ak[k][p] * ((Ck[k][p] * h) * dBtop), gtop);
+                    gbot = fma(A.w[k], Ak[k][p] * ((Ck[k][p] * g) * dBbot), gbot);
+                    Dp[k][p] = Dp[k][p] + Ck[k][p] * ((1.0 - tr) * Btop + g * dBd);      // D' <- D' + C (the step's emission)
+                    Ck[k][p] = Ct;
+                    // the upward leg: linear_flux_kernel's step
+                    I[k][p] = linear_update<FAST>(x, tr, I[k][p], Bbot, dBu);
+                    Imax[k][p] = fmax(Imax[k][p], I[k][p]);
+                }
+                Gd[p] = depth * G;
+                emit(true, l, p, tau * G, gbot, gtop, s_tau, s_bot, s_top);
+            }
+            add(3 + l, s_tau);
+            add(3 + L + 2 * l, s_bot);
+            add(3 + L + 2 * l + 1, s_top);
+            terms(l, Gd);
+        };
+        auto down = [&](auto fast_tag, int l, vec v) __attribute__((always_inline)) {
+            constexpr bool FAST = decltype(fast_tag)::value;
+            const double pbkT = A.pbkT[l], pbkT_top = A.pbkT_top[l], depth = A.depth[l], rT = A.rT[l], rT_top = A.rT_top[l];
+            double E0 = 0.0, E0_top = 0.0;
+            if (FAST) {
+                E0 = exp_clamped(nu[0] * pbkT);
+                E0_top = exp_clamped(nu[0] * pbkT_top);
+            }
+            double s_tau = 0.0, s_bot = 0.0, s_top = 0.0, Gd[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+                double Bbot, Btop, dBbot, dBtop;
+                linear_planck_pair<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT, pbkT_top, E0, E0_top, rT, rT_top, Bbot, Btop, dBbot, dBtop);
+                const double dBu = Btop - Bbot;
+                double G = 0.0, gbot = 0.0, gtop = 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double x = tau * A.rmu[k];
+                    const double tr = exp_neg_budget(x);
+                    const double g = linear_source_g(x, tr);
+                    const double dg = linear_source_dg(x, tr);
+                    const double h = x * dg;
+                    const double At = Ak[k][p] * tr;
+                    const double gu = fmin(fmax(Ak[k][p] * (Bbot + g * dBu) + I[k][p], -(At * Imax[k][p])), At * Bbot);
+                    G = fma(A.wrmu[k], gu + Ak[k][p] * (dg * dBu), G);
+                    gbot = fma(A.w[k], (Ak[k][p] * h) * dBbot, gbot);
+                    gtop = fma(A.w[k], (Ak[k][p] * g) * dBtop, gtop);
+                    I[k][p] = I[k][p] + Ak[k][p] * ((1.0 - tr) * Bbot + g * dBu);        // D <- D + A (the step's emission)
+                    Ak[k][p] = At;
+                }
+                Gd[p] = depth * G;
+                emit(false, l, p, tau * G, gbot, gtop, s_tau, s_bot, s_top);
+            }
+            add(3 + l, s_tau);
+            add(3 + L + 2 * l, s_bot);
+            add(3 + L + 2 * l + 1, s_top);
+            terms(l, Gd);
+        };
+        auto walk = [&](auto fast_tag) __attribute__((always_inline)) {
+            // walk 1, downward: I_L = I_top or 0
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double It = A.I_top ? A.I_top[j + p] : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
+            }
+            vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+                first_down(fast_tag, l, cur);
+                cur = nxt;
+            }
+            // the surface: K5h's
+            double s_Ts = 0.0, s_e = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+                double dBs = 0.0;
+                const double Is = A.I_surface ? A.I_surface[j + p]
+                                              : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
+                                                                         A.r_surface_T, &dBs);
+                const double edBs = e * dBs;
+                const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
+                const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
+                const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
+                const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
+                if (active && A.e_spec) A.e_spec[j + p] = de;
+                s_Ts += active ? nan_to_num(dTs) : 0.0;
+                s_e += active ? nan_to_num(de) : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) {
+                    const double D = I[k][p];
+                    I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
+                    Imax[k][p] = I[k][p];
+                    Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
+                    Ck[k][p] = 1.0;
+                    Dp[k][p] = -D;
+                }
+            }
+            add(1, s_Ts);
+            add(2, s_e);
+            // walk 2, upward
+            cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+            for (int l = 0; l < L; ++l) {
+                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+                up(fast_tag, l, cur);
+                cur = nxt;
+            }
+            // F_top; then I becomes D = -I_top and A = 1
+            double s = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
+#pragma unroll
+                for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
+            }
+            add(0, s);
+            // walk 3, downward
+            cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+                down(fast_tag, l, cur);
+                cur = nxt;
+            }
+        };
+        if constexpr (NP > 1) {
+            if (fast) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += blockDim.x)
+        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+}
+
+// Rays: ray_surface_jacobian_kernel's walks with linear_ray_kernel's step.  Forward every operation on I is
+// linear_ray_kernel's, on the same groups of points, so `radiance` is lbl_ray_radiance_linear_dev's bit for bit; Imax and
+// dI/de are carried as K5h carries them.  Backward a real segment stores its own two temperature rows (once, never added
+// to: seg_Trow names them) and stores or adds to its layer's ln tau row and term rows as K5f's do.
+// Rows: [dT_source, de, c x d ln tau, (dTa, dTb) per real segment in order of travel, terms].
+template <int NP, int RB>
+__global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRayJacArgs* __restrict__ Ap, long long lo0,
+                                                                  long long n0, long long lo1, long long n1, int order_first) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    const LinearRayJacArgs& A = *Ap;
+    const char* blk = (const char*)Ap;
+    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
+    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
+    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
+    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
+    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
+    const long long* __restrict__ row_first = (const long long*)(blk + A.off_row_first);
+    // (idle lanes of the last workgroup work on a valid point and store nothing)
+    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
+    const bool active = q < n0 + n1;
+    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    double nu[NP], pa_n[NP], Is[NP], em[NP], I[RB][NP], Imax[RB][NP], Ak[RB][NP];     // (Ak: S = dI/de on the forward walk)
+    column_points<NP>(A, j, nu, pa_n);
+    const bool fast = fold_fast_path<NP>(A, nu, active);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+        em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+    }
+    int rid[RB], s0[RB];
+    bool surface[RB];
+    long long row0[RB];                                   // the ray's first row
+#pragma unroll
+    for (int i = 0; i < RB; ++i) {
+        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
+        s0[i] = ray_first[rid[i]];
+        surface[i] = source_kind[rid[i]] == 1;
+        row0[i] = row_first[rid[i]];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            I[i][p] = surface[i] ? surface_leaving(em[p], Is[p], 0.0) : 0.0;
+            Imax[i][p] = I[i][p];
+            Ak[i][p] = surface[i] ? Is[p] : 0.0;
+        }
+    }
+    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers and rows)
+    const int32_t* lay = seg_layer + s0[0];
+    const double* pbk = (const double*)(blk + A.off_seg_pbkT) + 2 * (long long)s0[0];
+    const double* srT = (const double*)(blk + A.off_seg_rT) + 2 * (long long)s0[0];
+    const int32_t* slot = (const int32_t*)(blk + A.off_seg_slot) + s0[0];
+    const int32_t* Trow = (const int32_t*)(blk + A.off_seg_Trow) + s0[0];
+    const int32_t* term_row = (const int32_t*)(blk + A.off_term_row) + ((const int32_t*)(blk + A.off_ray_terms))[rid[0]];
+    auto put = [&](int i, long long row, int p, double v, bool store) {
+        double* o = A.jac + (row0[i] + row) * A.n + (j + p);
+        *o = store ? v : *o + v;
+    };
+    // e dB(nu, source_T)/dT at point p (0 when the source is a given spectrum)
+    auto source_dT = [&](int p) {
+        double dBs = 0.0;
+        if (!A.I_surface) fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
+        return em[p] * dBs;
+    };
+    // the nearest real segment at or after s / at or before s (ns / -1: none)
+    auto real_from = [&](int s) {
+        while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
+        return s;
+    };
+    auto real_back = [&](int s) {
+        while (s >= 0 && lay[s] == kRaySurfaceMarker) --s;
+        return s;
+    };
+    auto walk = [&](auto fast_tag) {
+        constexpr bool FAST = decltype(fast_tag)::value;
+        // forward: linear_ray_kernel's walk, the running maximum and dI/de
+        int ahead = real_from(0);
+        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
+        for (int s = 0; s < ns; ++s) {
+            if (lay[s] == kRaySurfaceMarker) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        Ak[i][p] = (Is[p] - I[i][p]) + (1.0 - em[p]) * Ak[i][p];
+                        I[i][p] = surface_leaving(em[p], Is[p], I[i][p]);
+                        Imax[i][p] = fmax(Imax[i][p], I[i][p]);
+                    }
+                }
+                continue;
+            }
+            ahead = real_from(s + 1);
+            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
+            double len[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            linear_step<FAST, NP>(nu, pa_n, pbk[2 * s], pbk[2 * s + 1], cur, [&](int p, double kp, double Ba, double dB) {
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double tau = kp * len[i];
+                    const double tr = exp_neg_budget(tau);
+                    I[i][p] = linear_update<FAST>(tau, tr, I[i][p], Ba, dB);
+                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
+                    Ak[i][p] = tr * Ak[i][p];
+                }
+            });
+            cur = nxt;
+        }
+        // the radiance and dI/de; then I becomes D = -I_final and A = 1
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                if (active && A.radiance) A.radiance[(long long)rid[i] * A.n + j + p] = I[i][p];
+                if (active) put(i, 1, p, Ak[i][p], true);
+                I[i][p] = -I[i][p];
+                Ak[i][p] = 1.0;
+            }
+        }
+        // backward
+        bool row0_stored = false;
+        int behind = real_back(ns - 1);
+        cur = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : (vec)(0.0);
+        for (int s = ns - 1; s >= 0; --s) {
+            if (lay[s] == kRaySurfaceMarker) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const double edBs = A.I_surface ? 0.0 : source_dT(p);
+                    const double eIs = em[p] * Is[p];
+#pragma unroll
+                    for (int i = 0; i < RB; ++i) {
+                        if (active && !A.I_surface) put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
+                        I[i][p] = I[i][p] + Ak[i][p] * eIs;
+                        Ak[i][p] = Ak[i][p] * (1.0 - em[p]);
+                    }
+                }
+                if (!A.I_surface) row0_stored = true;
+                continue;
+            }
+            behind = real_back(s - 1);
+            const vec nxt = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : cur;
+            const int l = lay[s];
+            const bool store = (slot[s] & kRayRowStore) != 0;
+            const long long row_tau = 2 + (slot[s] & (kRayRowStore - 1));
+            const long long row_Ta = Trow[s];
+            const double pbkT_a = pbk[2 * s], pbkT_b = pbk[2 * s + 1], rT_a = srT[2 * s], rT_b = srT[2 * s + 1];
+            double len[RB], G[RB][NP];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            double Ea0 = 0.0, Eb0 = 0.0;
+            if (FAST) {
+                Ea0 = exp_clamped(nu[0] * pbkT_a);
+                Eb0 = exp_clamped(nu[0] * pbkT_b);
+            }
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double Ba, Bb, dBa, dBb;
+                linear_planck_pair<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT_a, pbkT_b, Ea0, Eb0, rT_a, rT_b, Ba, Bb, dBa, dBb);
+                const double dB = Bb - Ba;
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double tau = cur[p] * len[i];
+                    const double tr = exp_neg_budget(tau);
+                    const double g = linear_source_g(tau, tr);
+                    const double dg = linear_source_dg(tau, tr);
+                    const double At = Ak[i][p] * tr;
+                    const double gc = fmin(fmax(Ak[i][p] * (Ba + g * dB) + I[i][p], -(At * Imax[i][p])), At * Ba);
+                    G[i][p] = gc + Ak[i][p] * (dg * dB);
+                    if (active) {
+                        put(i, row_tau, p, tau * G[i][p], store);
+                        put(i, row_Ta, p, (Ak[i][p] * (tau * dg)) * dBa, true);
+                        put(i, row_Ta + 1, p, (Ak[i][p] * g) * dBb, true);
+                    }
+                    I[i][p] = I[i][p] + Ak[i][p] * ((1.0 - tr) * Ba + g * dB);           // D <- D + A (the step's emission)
+                    Ak[i][p] = At;
+                }
+            }
+            for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
+                const vec km = load_points<NP>(A.term_k[t], j);
+                const long long row = term_row[t];
+                if (active) {
+#pragma unroll
+                    for (int i = 0; i < RB; ++i) {
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) put(i, row, p, (km[p] * len[i]) * G[i][p], store);
+                    }
+                }
+            }
+            cur = nxt;
+        }
+        // the source's part of dI/dT_source: A_0 e dBs/dT for a ray from the surface at source_T
+        if (active) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double edBs = source_dT(p);
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double v = surface[i] && !A.I_surface ? Ak[i][p] * edBs : 0.0;
+                    if (!row0_stored || surface[i]) put(i, 0, p, v, !row0_stored);
+                }
+            }
+        }
+    };
+    if constexpr (NP > 1) {
+        if (fast) walk(std::true_type{});
+        else walk(std::false_type{});
+    } else {
+        walk(std::false_type{});
+    }
+}
+
+// ----------------------------------------------------------------------------------------
 // K7: line survey (pyradClasses.py:409-428): S added into the bin of each line, in line order
 // ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void line_survey_kernel(const double* __restrict__ nu, const double* __restrict__ sw,
@@ -5590,6 +6065,44 @@ void launch_ray_surface_jacobian(const RaySurfaceJacArgs* d_args, long long n, i
     }
     if (nt > 0)
         hipLaunchKernelGGL((ray_surface_jacobian_kernel<1, 1, true>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+}
+
+// K5j: K5h's launches.  The column's points per thread are linear_jacobian_np's; the rays keep K5i's groups of 4 points,
+// which is what makes `radiance` lbl_ray_radiance_linear_dev's bit for bit.  (One bundle kernel: without the term loop it
+// spills two registers, and it runs at one wave per SIMD either way.)
+int linear_jacobian_points(int n_angles) {
+    int np = 1;
+    with_angles(n_angles, [&](auto na) { np = linear_jacobian_np<decltype(na)::value>(); });
+    return np;
+}
+
+void launch_linear_jacobian(const LinearJacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first,
+                            long long count, double* partial, double* jac, hipStream_t s) {
+    with_angles(n_angles, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        constexpr int NP = linear_jacobian_np<NA>();
+        launch_column_band<NP>(linear_jacobian_kernel<NP, NA>, linear_jacobian_kernel<1, NA>, d_args,
+                               3 + 3 * n_layers + n_terms, first, count, partial, jac, s);
+    });
+}
+
+void launch_linear_ray_jacobian(const LinearRayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
+                                hipStream_t s) {
+    constexpr int NP = 4;
+    if (n <= 0 || n_rays <= 0) return;
+    const long long q1 = n & ~(long long)(NP - 1);
+    const long long nt = n - q1;
+    const int n_single = n_rays - kRayBundle * n_bundles;
+    if (q1 > 0) {
+        const dim3 grid((unsigned)((q1 / NP + 255) / 256), n_bundles);
+        if (n_bundles > 0)
+            hipLaunchKernelGGL((ray_linear_jacobian_kernel<NP, kRayBundle>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL, 0);
+        if (n_single > 0)
+            hipLaunchKernelGGL((ray_linear_jacobian_kernel<NP, 1>), dim3(grid.x, n_single), dim3(256), 0, s, d_args, 0LL,
+                               q1, 0LL, 0LL, kRayBundle * n_bundles);
+    }
+    if (nt > 0)
+        hipLaunchKernelGGL((ray_linear_jacobian_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
 }
 
 void launch_line_survey(const double* nu, const double* sw, int n_lines, double range_min, double resolution,

@@ -1502,11 +1502,15 @@ class Jacobians:
     part whatever ``temperature`` was).  ``temperatureAbsorption``: (L,) the absorption part of dF/dT_l, through dk_l/dT, and
     ``temperatureFull`` = temperature + temperatureAbsorption: both None unless temperature="full" was asked for.
     ``emissivity``: dF/de per band, W m^-2 per unit emissivity, over a surface with an emissivity (None over the black
-    surface); ``emissivitySpectrum``: (n,) the spectral dF/de when spectra were asked for as well, else None."""
+    surface); ``emissivitySpectrum``: (n,) the spectral dF/de when spectra were asked for as well, else None.
+    From Atmosphere.jacobiansLinear only (else None): ``edgeTemperature``: (L, 2) dF/dT of the bottom and the top edge of
+    every layer; ``levelTemperature``: (L + 1,) dF/d(level temperature), level i the top edge of layer i - 1 plus the bottom
+    edge of layer i; ``levelTemperatureSpectrum``: (L + 1, n) with spectra.  ``temperature`` is then the chain through the
+    default level temperatures, or None when level temperatures were given, and temperatureSpectrum is None."""
 
     def __init__(self, olr, surfaceTemperature, temperature, opticalDepth, molecules, moleculeNames, mu, weight,
                  temperatureSpectrum=None, opticalDepthSpectrum=None, temperatureAbsorption=None, emissivity=None,
-                 emissivitySpectrum=None):
+                 emissivitySpectrum=None, edgeTemperature=None, levelTemperature=None, levelTemperatureSpectrum=None):
         self.olr = olr
         self.surfaceTemperature = surfaceTemperature
         self.temperature = temperature
@@ -1518,9 +1522,13 @@ class Jacobians:
         self.temperatureSpectrum = temperatureSpectrum
         self.opticalDepthSpectrum = opticalDepthSpectrum
         self.temperatureAbsorption = temperatureAbsorption
-        self.temperatureFull = None if temperatureAbsorption is None else temperature + temperatureAbsorption
+        self.temperatureFull = (None if temperatureAbsorption is None or temperature is None
+                                else temperature + temperatureAbsorption)
         self.emissivity = emissivity
         self.emissivitySpectrum = emissivitySpectrum
+        self.edgeTemperature = edgeTemperature
+        self.levelTemperature = levelTemperature
+        self.levelTemperatureSpectrum = levelTemperatureSpectrum
 
     def __repr__(self):
         return "Jacobians(layers=%d, angles=%d, olr=%s)" % (self.opticalDepth.shape[-1], len(self.mu), self.olr)
@@ -1994,10 +2002,13 @@ class PathJacobians:
     order.  Layers a path does not cross hold exact zeros.  With an instrument also ``brightnessTemperature`` (R, C), the
     inverse Planck of the channel radiance at the centre, and ``brightnessTemperatureJacobian`` (R, L, C) = temperature /
     (dB/dT at the centre and the channel's brightness temperature), as Observation forms it; else both None.
-    ``emissivity``: (R, X) dI/de per unit emissivity over a surface with an emissivity, None over the black surface."""
+    ``emissivity``: (R, X) dI/de per unit emissivity over a surface with an emissivity, None over the black surface.
+    From Atmosphere.pathJacobiansLinear only (else None): ``segmentTemperature``: per path an (s, 2, X) array, dI/dTa and
+    dI/dTb of each of its s segments in order of travel; ``temperature``, temperatureFull and
+    brightnessTemperatureJacobian are then None."""
 
     def __init__(self, wavenumber, radiance, temperature, opticalDepth, surfaceTemperature, molecules, moleculeNames, paths,
-                 temperatureAbsorption=None, channels=False, emissivity=None):
+                 temperatureAbsorption=None, channels=False, emissivity=None, segmentTemperature=None):
         self.wavenumber = wavenumber
         self.radiance = radiance
         self.temperature = temperature
@@ -2006,18 +2017,21 @@ class PathJacobians:
         self.molecules = molecules
         self.moleculeNames = moleculeNames
         self.temperatureAbsorption = temperatureAbsorption
-        self.temperatureFull = None if temperatureAbsorption is None else temperature + temperatureAbsorption
+        self.temperatureFull = (None if temperatureAbsorption is None or temperature is None
+                                else temperature + temperatureAbsorption)
         self.paths = paths
         self.emissivity = emissivity
+        self.segmentTemperature = segmentTemperature
         self.brightnessTemperature = self.brightnessTemperatureJacobian = None
         if channels:
             self.brightnessTemperature = brightnessTemperature(wavenumber, radiance)
-            with np.errstate(divide='ignore', invalid='ignore'):
-                self.brightnessTemperatureJacobian = temperature / _planck_dT(wavenumber, self.brightnessTemperature)[:, None, :]
+            if temperature is not None:
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    self.brightnessTemperatureJacobian = temperature / _planck_dT(wavenumber, self.brightnessTemperature)[:, None, :]
 
     def __repr__(self):
         return "PathJacobians(paths=%d, layers=%d, points=%d, molecules=%s, full=%s)" % (
-            len(self.paths), self.temperature.shape[1], self.wavenumber.size, self.molecules is not None,
+            len(self.paths), self.opticalDepth.shape[1], self.wavenumber.size, self.molecules is not None,
             self.temperatureAbsorption is not None)
 
 
@@ -2027,10 +2041,11 @@ class Observation:
     With jacobians=True (else None), (L, C) each: ``temperatureJacobian`` dR_c/dT_l (Planck part only, as jacobians()
     documents), ``opticalDepthJacobian`` dR_c/d ln tau_l and ``brightnessTemperatureJacobian`` = temperatureJacobian /
     (dB/dT at the centre and the channel's brightness temperature); over a surface with an emissivity also
-    ``emissivityJacobian`` (C,) dR_c/de, else None."""
+    ``emissivityJacobian`` (C,) dR_c/de, else None.  From Atmosphere.observeLinear with jacobians=True (else None):
+    ``levelTemperatureJacobian`` (L + 1, C) dR_c/d(level temperature); temperatureJacobian is then None."""
 
     def __init__(self, wavenumber, radiance, mu, temperatureJacobian=None, opticalDepthJacobian=None,
-                 emissivityJacobian=None):
+                 emissivityJacobian=None, levelTemperatureJacobian=None):
         self.wavenumber = wavenumber
         self.radiance = radiance
         self.brightnessTemperature = brightnessTemperature(wavenumber, radiance)
@@ -2038,6 +2053,7 @@ class Observation:
         self.temperatureJacobian = temperatureJacobian
         self.opticalDepthJacobian = opticalDepthJacobian
         self.emissivityJacobian = emissivityJacobian
+        self.levelTemperatureJacobian = levelTemperatureJacobian
         self.brightnessTemperatureJacobian = None
         if temperatureJacobian is not None:
             with np.errstate(divide='ignore', invalid='ignore'):
@@ -2045,7 +2061,7 @@ class Observation:
 
     def __repr__(self):
         return "Observation(channels=%d, mu=%g, jacobians=%s)" % (
-            self.wavenumber.size, self.mu, self.temperatureJacobian is not None)
+            self.wavenumber.size, self.mu, self.opticalDepthJacobian is not None)
 
 
 # ----------------------------------------------------------------------------------------
@@ -2296,7 +2312,7 @@ class Atmosphere(list):
         value but dF/de is the black surface's bit for bit.  ``topSpectrum`` without an emissivity is a ValueError: the
         black surface's outgoing flux does not depend on it.
         The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
-        planck="linear"; its derivatives are not part of this method)."""
+        planck="linear"; its derivatives are jacobiansLinear()'s)."""
         if temperature not in ("planck", "full"):
             raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
@@ -2391,7 +2407,7 @@ class Atmosphere(list):
         fluxes(emissivity=e, reflection="specular", angles=[(mu, 1.0)])'s upward spectrum at the top, the weighting functions
         jacobians(emissivity=e, ...)'s for that angle, and Observation.emissivityJacobian their dR_c/de.
         The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
-        planck="linear"; its derivatives are not part of this method)."""
+        planck="linear"; its derivatives are observeLinear()'s)."""
         if not isinstance(instrument, Instrument):
             raise ValueError("instrument: an Instrument, not %r" % (instrument,))
         try:
@@ -2455,6 +2471,210 @@ class Atmosphere(list):
                            temperatureJacobian=v[1:1 + nl].copy() if jacobians else None,
                            opticalDepthJacobian=v[1 + nl:1 + 2 * nl].copy() if jacobians else None,
                            emissivityJacobian=v[1 + 2 * nl].copy() if jacobians and emissivity is not None else None)
+
+    def _level_chain(self):
+        """The (L + 1) x L matrix M of levelTemperatures(): lev = M T for the layers' temperatures T (the map is linear, its
+        coefficients depend on the layers' depths alone)."""
+        layers, _ = self._column_layers()
+        d = [float(L.depth) for L in layers]
+        nl = len(layers)
+        M = np.zeros((nl + 1, nl))
+        if nl == 1:
+            M[:, 0] = 1.0
+            return M
+        for i in range(1, nl):
+            a = d[i - 1] / (d[i - 1] + d[i])
+            M[i, i - 1], M[i, i] = 1.0 - a, a
+        M[0] = -M[1]
+        M[0, 0] += 2.0
+        M[nl] = -M[nl - 1]
+        M[nl, nl - 1] += 2.0
+        return M
+
+    def jacobiansLinear(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True,
+                        spectra=False, temperature="planck", emissivity=None, reflection="lambertian", topSpectrum=None,
+                        levelTemperatures=None):
+        """jacobians() for fluxes(planck="linear"): analytic sensitivities of the upward flux at the top with the Planck
+        function linear in optical depth through every layer, the temperatures of the levels among the variables
+        (lbl_column_jacobian_linear_dev; beyond the reference).  Column, angles, bands, molecules, spectra, emissivity,
+        reflection and topSpectrum as jacobians() takes them (``emissivity`` None is the black surface);
+        ``levelTemperatures`` as fluxes(planck="linear") takes them (None: levelTemperatures()).  With x = k_l depth_l /
+        mu_k, t = exp(-x), g as fluxes() has it, h = (1 - t) - g, g' = h / x, Bbot and Btop the Planck function at the
+        layer's lower and upper level, and A, C, Q, Iu, Id as jacobians() defines them over the linear forward radiances:
+            dF/d ln tau_l   = sum_k W_k A_lk [x t (Bbot - Iu_lk) + h (Btop - Bbot)] + Q_k C_lk [x t (Btop - Id_(l+1)k) + h (Bbot - Btop)]
+            molecules, dk/dT: the same with (k_m depth_l / mu_k) [t (B - I) + g' (B' - B)] per leg
+            dF/dT_bottom(l) = dB(lev_l)/dT     sum_k (W_k A_lk h + Q_k C_lk g)
+            dF/dT_top(l)    = dB(lev_(l+1))/dT sum_k (W_k A_lk g + Q_k C_lk h)
+            dF/dT_s, dF/de  : jacobians()'s
+        Returns a Jacobians with ``edgeTemperature`` (L, 2), ``levelTemperature`` (L + 1,) - level i is the top edge of
+        layer i - 1 plus the bottom edge of layer i - and with ``spectra`` ``levelTemperatureSpectrum`` (L + 1, n) and
+        opticalDepthSpectrum.  ``temperature`` (L,) is the exact chain through levelTemperatures(), which is linear in the
+        layers' temperatures, when the default level temperatures are in use, and None when level temperatures were given;
+        it is the Planck part, the absorption coefficients held fixed.  temperature="full" adds temperatureAbsorption
+        through dk_l/dT as jacobians() does.  olr is fluxes(planck="linear")'s upward flux at the top to rounding.
+        Everything is validated (ValueError) before the device is touched."""
+        if temperature not in ("planck", "full"):
+            raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
+        layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
+            surfaceSpectrum, surfaceTemperature, angles, bands)
+        first = layers[0]
+        refl = _surface_reflection(reflection)
+        lev = self._level_temperatures(levelTemperatures)
+        chain = self._level_chain() if levelTemperatures is None or levelTemperatures is True else None
+        edges = np.column_stack([lev[:-1], lev[1:]])
+        black = emissivity is None
+        if black:
+            if topSpectrum is not None:
+                raise ValueError("topSpectrum: the outgoing flux over a black surface does not depend on it (give emissivity)")
+            emissivity = 1.0
+        else:
+            topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
+            emissivity = _surface_emissivity(emissivity, first.xAxis)
+        _weight_sum(weight)
+        names = [[m.name for m in L] for L in layers]
+        full = temperature == "full"
+        n_terms = (sum(len(L) for L in layers) if molecules else 0) + (len(layers) if full else 0)
+        if n_terms > nat.limit("jacobian_terms"):
+            raise ValueError("molecules: %d molecule and dk/dT terms, at most %d (molecules=False skips the molecule terms)"
+                             % (n_terms, nat.limit("jacobian_terms")))
+        if full:
+            for L in layers:
+                L._check_abs_coef_dT()
+        res = utils.BASE_RESOLUTION
+        nl, nb = len(layers), len(band_first)
+        ctx = _ctx()
+        if ctx.option("sweep_ieee_divisions"):
+            raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
+        kbufs, plan = self._column_abs_coef(ctx, layers, n)
+        term_bufs, term_layer = self._jacobian_terms(ctx, layers, n, plan) if molecules else ([], [])
+        n_mol_terms = len(term_bufs)
+        if full:
+            term_bufs = term_bufs + [L._abs_coef_dT()[0] for L in layers]
+            term_layer = term_layer + list(range(nl))
+        nv = 3 + 3 * nl + len(term_bufs)
+        out = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, nb * nv))
+        I_surface = out.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
+        jac = out.buf(ctx, "jac")
+        ln_tau_spec = T_edge_spec = e_spec = None
+        if spectra:
+            sp = _kept_state(self, "_jacobian_linear_spec").reserve(ctx, 2 * nl * n)
+            ln_tau_spec, T_edge_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T_edge")
+        sst = _kept_state(self, "_jacobian_surface").reserve(ctx, n)
+        if not isinstance(emissivity, float):
+            emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
+        I_top = sst.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
+        if spectra and not black:
+            e_spec = sst.buf(ctx, "e_spec")
+        ctx.column_jacobian_linear_dev(kbufs, edges, [L.depth for L in layers], first.rangeMin, first.rangeMax, n, mu, weight,
+                                       band_first, band_count, jac, emissivity, reflection=refl, I_surface=I_surface,
+                                       surface_T=float(surfaceTemperature or 0.0), I_top=I_top, term_abs_coef=term_bufs,
+                                       term_layer=term_layer, ln_tau_spectra=ln_tau_spec, T_edge_spectra=T_edge_spec,
+                                       e_spectrum=e_spec)
+        v = jac.download(nb * nv).reshape(nb, nv) * res
+        olr, dTs, de = v[:, 0], v[:, 1], v[:, 2]
+        dtau = v[:, 3:3 + nl]
+        edge = v[:, 3 + nl:3 + 3 * nl].reshape(nb, nl, 2)
+        dlev = self._levels_of_edges(edge)
+        dT = dlev @ chain if chain is not None else None
+        mol = None
+        if molecules:
+            mol, o = [], 3 + 3 * nl
+            for L in layers:
+                mol.append(v[:, o:o + len(L)])
+                o += len(L)
+        olr, dTs, de, dtau, edge, dlev = _band_values(bands, [olr, dTs, de, dtau, edge, dlev])
+        dT = _band_values(bands, [dT])[0] if dT is not None else None
+        mol = _band_values(bands, mol) if mol is not None else None
+        dT_abs = _band_values(bands, [v[:, 3 + 3 * nl + n_mol_terms:]])[0] if full else None
+        lev_spec = None
+        if spectra:
+            lev_spec = self._levels_of_edges(T_edge_spec.download(2 * nl * n).reshape(nl, 2, n).transpose(2, 0, 1)).T.copy()
+        return Jacobians(olr, dTs if surfaceSpectrum is None else None, dT, dtau, mol, names, mu, weight,
+                         opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None,
+                         temperatureAbsorption=dT_abs, emissivity=None if black else de,
+                         emissivitySpectrum=e_spec.download(n) if e_spec is not None else None,
+                         edgeTemperature=edge, levelTemperature=dlev, levelTemperatureSpectrum=lev_spec)
+
+    @staticmethod
+    def _levels_of_edges(edge):
+        """(..., L, 2) edge values (bottom, top per layer) -> (..., L + 1) level values: level i is the top edge of layer
+        i - 1 plus the bottom edge of layer i"""
+        lev = np.zeros(edge.shape[:-2] + (edge.shape[-2] + 1,))
+        lev[..., :-1] += edge[..., :, 0]
+        lev[..., 1:] += edge[..., :, 1]
+        return lev
+
+    def observeLinear(self, instrument, surfaceTemperature=None, surfaceSpectrum=None, mu=1.0, jacobians=False,
+                      emissivity=None, levelTemperatures=None):
+        """observe() for fluxes(planck="linear"): what an instrument above the column sees at viewing cosine ``mu`` with the
+        Planck function linear in optical depth through every layer (lbl_column_flux_linear_dev and
+        lbl_column_jacobian_linear_dev at the angle set [(mu, 1.0)]; beyond the reference).  Arguments as observe() takes
+        them (``emissivity`` None is the black surface; with an emissivity the reflection is specular at ``mu``);
+        ``levelTemperatures`` as fluxes(planck="linear") takes them.  The radiance is convolve(instrument,
+        fluxes(planck="linear", angles=[(mu, 1.0)], ...).upSpectrum).  ``jacobians``: also opticalDepthJacobian (L, C) and
+        ``levelTemperatureJacobian`` (L + 1, C), jacobiansLinear()'s spectral dI/d ln tau_l and edge rows for that angle
+        convolved in the same call, the 2 L edge rows summed to levels on the host (the convolution is linear), and over a
+        surface with an emissivity emissivityJacobian.  Returns an Observation whose temperatureJacobian is None.
+        Everything is validated (ValueError) before the device is touched."""
+        if not isinstance(instrument, Instrument):
+            raise ValueError("instrument: an Instrument, not %r" % (instrument,))
+        try:
+            angle = [(float(mu), 1.0)]
+        except (TypeError, ValueError):
+            raise ValueError("mu: a viewing cosine in (0, 1], not %r" % (mu,))
+        if not (angle[0][0] > 0.0 and angle[0][0] <= 1.0):
+            raise ValueError("mu: a viewing cosine in (0, 1], not %r" % (mu,))
+        layers, n, mu_k, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
+            surfaceSpectrum, surfaceTemperature, angle, None)
+        first = layers[0]
+        lev = self._level_temperatures(levelTemperatures)
+        edges = np.column_stack([lev[:-1], lev[1:]])
+        black = emissivity is None
+        emissivity = 1.0 if black else _surface_emissivity(emissivity, first.xAxis)
+        support = instrument.support(first.rangeMin, first.rangeMax, n)
+        nl, C = len(layers), len(instrument)
+        n_rows = (1 + 3 * nl + (not black)) if jacobians else 1
+        if n_rows > nat.limit("ils_rows"):
+            raise ValueError("jacobians: %d layers, at most %d" % (nl, (nat.limit("ils_rows") - 2) // 3))
+        ctx = _ctx()
+        if jacobians and ctx.option("sweep_ieee_divisions"):
+            raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        depth = [L.depth for L in layers]
+        surface_T = float(surfaceTemperature or 0.0)
+        specular = REFLECTIONS.index("specular")
+        fst = _kept_state(self, "_flux_state")
+        fst.reserve(ctx, max(n, 2 * (nl + 1)))
+        I_surface = fst.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
+        up_top = fst.buf(ctx, "up_top")
+        if not isinstance(emissivity, float):
+            emissivity = fst.buf(ctx, "emissivity").upload(emissivity)
+        ctx.column_flux_linear_dev(kbufs, edges, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
+                                   band_count, fst.buf(ctx, "level"), emissivity, reflection=specular, I_surface=I_surface,
+                                   surface_T=surface_T, up_top=up_top)
+        rows = [(up_top, 0)]
+        if jacobians:
+            jst = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, 3 + 3 * nl))
+            sp = _kept_state(self, "_jacobian_linear_spec").reserve(ctx, 2 * nl * n)
+            ln_tau_spec, T_edge_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T_edge")
+            e_spec = None if black else _kept_state(self, "_jacobian_surface").reserve(ctx, n).buf(ctx, "e_spec")
+            ctx.column_jacobian_linear_dev(kbufs, edges, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
+                                           band_count, jst.buf(ctx, "jac"), emissivity, reflection=specular,
+                                           I_surface=I_surface, surface_T=surface_T, ln_tau_spectra=ln_tau_spec,
+                                           T_edge_spectra=T_edge_spec, e_spectrum=e_spec)
+            rows += [(ln_tau_spec, l * n) for l in range(nl)] + [(T_edge_spec, i * n) for i in range(2 * nl)]
+            if e_spec is not None:
+                rows.append((e_spec, 0))
+        out = _kept_state(self, "_observe_out").reserve(ctx, n_rows * C).buf(ctx, "out")
+        _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, rows, out)
+        v = out.download(n_rows * C).reshape(n_rows, C)
+        dlev = None
+        if jacobians:
+            dlev = self._levels_of_edges(v[1 + nl:1 + 3 * nl].reshape(nl, 2, C).transpose(2, 0, 1)).T.copy()
+        return Observation(instrument.centres.copy(), v[0].copy(), float(mu_k[0]),
+                           opticalDepthJacobian=v[1:1 + nl].copy() if jacobians else None,
+                           emissivityJacobian=v[1 + 3 * nl].copy() if jacobians and not black else None,
+                           levelTemperatureJacobian=dlev)
 
     @staticmethod
     def _path_mu(mu):
@@ -2775,7 +2995,35 @@ class Atmosphere(list):
         sky fixed would disagree with differences of radiance(): such a path is refused (ValueError) with an emissivity
         and "lambertian" - take reflection="specular", under which it starts with e Is alone.
         The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
-        planck="linear"; its derivatives are not part of this method)."""
+        planck="linear"; its derivatives are pathJacobiansLinear()'s)."""
+        return self._path_jacobians(False, paths, surfaceTemperature, surfaceSpectrum, instrument, molecules, temperature,
+                                    emissivity, reflection)
+
+    def pathJacobiansLinear(self, paths, surfaceTemperature=None, surfaceSpectrum=None, instrument=None, molecules=False,
+                            temperature="planck", emissivity=None, reflection="lambertian"):
+        """pathJacobians() for radiance(planck="linear"): the weighting functions of the radiance along ``paths`` with the
+        Planck function linear in optical depth through every segment (lbl_ray_jacobian_linear_dev; beyond the reference).
+        Every path must carry ``temperatures`` (the path builders fill them from levelTemperatures=...).  Arguments, chunks,
+        instrument and refusals are pathJacobians()'s; ``emissivity`` None is the black surface.  Per segment s (layer l,
+        length x, tau = k_l x, t = exp(-tau), Ba = B(Ta_s) where the light enters, Bb = B(Tb_s) where it leaves, I_s the
+        radiance entering, A_s the product over every element after s), with g as radiance() has it, h = (1 - t) - g and
+        g' = h / tau:
+            dI/d ln tau_l    = sum over the path's segments in layer l of A_s [tau t (Ba - I_s) + h (Bb - Ba)]
+            molecules, dk/dT = the same sums with k_m x [t (Ba - I_s) + g' (Bb - Ba)]
+            dI/dTa_s = A_s h dB(Ta_s)/dT        dI/dTb_s = A_s g dB(Tb_s)/dT           per segment, not per layer
+            dI/dT_s, dI/de   : pathJacobians()'s
+        Returns a PathJacobians whose ``segmentTemperature`` holds, per path, an (s, 2, X) array of (dI/dTa, dI/dTb) for
+        its s segments in order of travel (the bounce is no segment); a path's rows in one kernel call are 2 + crossed
+        layers + 2 s + terms.  The per-layer ``temperature`` is None: which level a segment end belongs to is known only to
+        whoever built the path (for the built-in builders, a level's derivative is the sum of the rows of the segment ends
+        that lie on it).  temperature="full" fills temperatureAbsorption.  The radiance is radiance(planck="linear")'s
+        bit for bit."""
+        return self._path_jacobians(True, paths, surfaceTemperature, surfaceSpectrum, instrument, molecules, temperature,
+                                    emissivity, reflection)
+
+    def _path_jacobians(self, linear, paths, surfaceTemperature, surfaceSpectrum, instrument, molecules, temperature,
+                        emissivity, reflection):
+        """pathJacobians() and, with ``linear``, pathJacobiansLinear()"""
         if temperature not in ("planck", "full"):
             raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         plist, layers, n, surfaceSpectrum = self._path_checks(paths, surfaceTemperature, surfaceSpectrum)
@@ -2790,6 +3038,14 @@ class Atmosphere(list):
             if refl == 0 and any(p.source == "surface" for p in plist):
                 raise ValueError("reflection: a path that starts at the surface has no weighting functions under \"lambertian\" "
                                  "(the diffusely reflected sky is not differentiated); take reflection=\"specular\"")
+        if linear:
+            for i, p in enumerate(plist):
+                if p.temperatures is None:
+                    raise ValueError("paths: path %d (%r) carries no temperatures (the linear source needs a pair per segment)"
+                                     % (i, p))
+        black = emissivity is None
+        if linear and black:                          # (the linear entry point is a superset of the black surface)
+            emissivity = 1.0
         h = 1 if emissivity is None else 2            # a path's rows ahead of its layers': dI/dT_s and dI/de
         full = temperature == "full"
         names = [[m.name for m in L] for L in layers]
@@ -2811,7 +3067,7 @@ class Atmosphere(list):
         term_layer = ([l for l, L in enumerate(layers) for _ in L] if molecules else []) + (list(range(nl)) if full else [])
         crossed = [sorted(set(p.layers)) for p in plist]
         ray_terms = [[t for t, l in enumerate(term_layer) if l in set(c)] for c in crossed]
-        ray_rows = [h + 2 * len(c) + len(t) for c, t in zip(crossed, ray_terms)]
+        ray_rows = [h + (len(c) + 2 * len(p) if linear else 2 * len(c)) + len(t) for p, c, t in zip(plist, crossed, ray_terms)]
         block = nat.limit("ils_rows")
         chunks, r = [], 0
         while r < R:
@@ -2846,7 +3102,15 @@ class Atmosphere(list):
         row0 = 0
         for r, e, rows in chunks:
             sub = plist[r:e]
-            if emissivity is None:
+            if linear:
+                segs = [p._segments() for p in sub]
+                ctx.ray_jacobian_linear_dev(kbufs, [t for p in sub for t in p._segment_temperatures()], first.rangeMin,
+                                            first.rangeMax, n, np.cumsum([0] + [len(lay) for lay, _ in segs]),
+                                            [l for lay, _ in segs for l in lay], [x for _, lens in segs for x in lens],
+                                            kinds[r:e], jac, emissivity, I_source=I_source,
+                                            source_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs,
+                                            term_layer=term_layer, radiance=rad)
+            elif emissivity is None:
                 ctx.ray_jacobian_dev(kbufs, T, first.rangeMin, first.rangeMax, n, np.cumsum([0] + [len(p) for p in sub]),
                                      [l for p in sub for l in p.layers], [x for p in sub for x in p.lengths], kinds[r:e], jac,
                                      I_source=I_source, source_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs,
@@ -2879,10 +3143,11 @@ class Atmosphere(list):
             v = out.download((R + total) * X).reshape(R + total, X)
             I, J = v[:R].copy(), v[R:]
         # rows -> (R, L, X) arrays: zeros where a path does not cross a layer
-        dtau, dT = np.zeros((R, nl, X)), np.zeros((R, nl, X))
+        dtau, dT = np.zeros((R, nl, X)), None if linear else np.zeros((R, nl, X))
         dTs = np.zeros((R, X))
-        de = np.zeros((R, X)) if emissivity is not None else None
+        de = np.zeros((R, X)) if emissivity is not None and not black else None
         terms = np.zeros((R, n_terms, X))
+        seg_T = [] if linear else None
         row0 = 0
         for r in range(R):
             c = len(crossed[r])
@@ -2890,8 +3155,13 @@ class Atmosphere(list):
             if de is not None:
                 de[r] = J[row0 + 1]
             dtau[r, crossed[r]] = J[row0 + h:row0 + h + c]
-            dT[r, crossed[r]] = J[row0 + h + c:row0 + h + 2 * c]
-            terms[r, ray_terms[r]] = J[row0 + h + 2 * c:row0 + ray_rows[r]]
+            if linear:
+                ns = len(plist[r])
+                seg_T.append(J[row0 + h + c:row0 + h + c + 2 * ns].reshape(ns, 2, X).copy())
+                terms[r, ray_terms[r]] = J[row0 + h + c + 2 * ns:row0 + ray_rows[r]]
+            else:
+                dT[r, crossed[r]] = J[row0 + h + c:row0 + h + 2 * c]
+                terms[r, ray_terms[r]] = J[row0 + h + 2 * c:row0 + ray_rows[r]]
             row0 += ray_rows[r]
         mol = None
         if molecules:
@@ -2902,7 +3172,7 @@ class Atmosphere(list):
         return PathJacobians(first.xAxis if instrument is None else instrument.centres.copy(), I, dT, dtau,
                              dTs if surfaceSpectrum is None else None, mol, names, plist,
                              temperatureAbsorption=terms[:, n_mol_terms:].copy() if full else None,
-                             channels=instrument is not None, emissivity=de)
+                             channels=instrument is not None, emissivity=de, segmentTemperature=seg_T)
 
     def kDistribution(self, bands=None, g=16, reference=None, planck=False, spectra=False):
         """k-distributions of the column's bands (beyond the reference): every layer's absorption coefficient (getAbsCoef)
