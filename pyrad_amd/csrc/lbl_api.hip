@@ -57,6 +57,7 @@ struct lbl_ctx {
     void* host_stage = nullptr;   // pinned staging ring for job descriptors
     size_t host_stage_cap = 0;
     size_t host_stage_head = 0;
+    int host_stage_half = -1;     // the half the last allocation lies in (-1: nothing allocated since the ring was made)
     hipEvent_t stage_ev[2] = {nullptr, nullptr};   // one per half of the ring: "every copy out of this half has been enqueued"
     bool stage_ev_set[2] = {false, false};
     struct DescSlot { std::vector<char> bytes; void* dptr = nullptr; size_t cap = 0; };
@@ -270,8 +271,10 @@ static void prof_end(lbl_ctx* ctx, int kind, hipEvent_t start) {
 // Pinned staging for descriptors that a later hipMemcpyAsync reads: bump-allocated from a ring of two halves.  A half is
 // reused only after the copies that read it have run: leaving a half records an event on the stream (every copy out of that
 // half was enqueued before it), entering a half waits for ITS event - recorded half a ring of descriptors ago, so normally long
-// complete.  (Until round 6 a wrap drained the whole stream: a step with fresh descriptors - a re-windowed column, whose
-// blocks are ~150 KB per call - then stalled for everything it had just enqueued, 7 ms of a 14 ms call every sixth call or so.)
+// complete.  The half of the last allocation is kept on its own: host_stage_head is the END of that allocation, and one that
+// ends exactly on the middle (or on the capacity) still lies in the half it is about to leave.  (Until round 6 a wrap drained
+// the whole stream: a step with fresh descriptors - a re-windowed column, whose blocks are ~150 KB per call - then stalled for
+// everything it had just enqueued, 7 ms of a 14 ms call every sixth call or so.)
 static int stage_alloc(lbl_ctx* ctx, size_t bytes, void** out) {
     bytes = (bytes + 255) & ~(size_t)255;
     if (ctx->capturing) return capture_refuses(ctx, "staging a host-to-device copy");
@@ -279,7 +282,7 @@ static int stage_alloc(lbl_ctx* ctx, size_t bytes, void** out) {
         TraceScope tr("staging ring grow", (long long)bytes);
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->host_stage) HIP_TRY(ctx, hipHostFree(ctx->host_stage));
-        ctx->host_stage = nullptr; ctx->host_stage_cap = 0; ctx->host_stage_head = 0;
+        ctx->host_stage = nullptr; ctx->host_stage_cap = 0; ctx->host_stage_head = 0; ctx->host_stage_half = -1;
         ctx->stage_ev_set[0] = ctx->stage_ev_set[1] = false;
 #ifdef LBL_SANITIZER_BUILD
         size_t want = bytes * 8;                               // (the harness wants the ring to wrap often)
@@ -290,12 +293,12 @@ static int stage_alloc(lbl_ctx* ctx, size_t bytes, void** out) {
         ctx->host_stage_cap = want;
     }
     const size_t half = ctx->host_stage_cap / 2;
-    const int from = ctx->host_stage_head < half ? 0 : 1;
+    const int from = ctx->host_stage_half;
     size_t head = ctx->host_stage_head;
     if (head < half && head + bytes > half) head = half;                    // no allocation straddles the two halves
     if (head + bytes > ctx->host_stage_cap) head = 0;
     const int to = head < half ? 0 : 1;
-    if (to != from) {
+    if (from >= 0 && to != from) {
         for (int h = 0; h < 2; ++h)
             if (!ctx->stage_ev[h]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->stage_ev[h], hipEventDisableTiming));
         HIP_TRY(ctx, hipEventRecord(ctx->stage_ev[from], ctx->stream));
@@ -307,6 +310,7 @@ static int stage_alloc(lbl_ctx* ctx, size_t bytes, void** out) {
     }
     *out = (char*)ctx->host_stage + head;
     ctx->host_stage_head = head + bytes;
+    ctx->host_stage_half = to;
     return LBL_OK;
 }
 

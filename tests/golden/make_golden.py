@@ -21,6 +21,7 @@ The numeric modules pyradLineshape / pyradIntensity / pyradPlanck / pyradClasses
 are then the reference's own files, executed unmodified.
 
 Usage:  python tests/golden/make_golden.py        (rewrites every tests/golden/G*.npz)
+        python tests/golden/make_golden.py g13    (one of them)
 """
 from __future__ import annotations
 
@@ -958,9 +959,320 @@ def g12():
     save("G12_hitran_shaped_rows", **arrays)
 
 
+# ----------------------------------------------------------------------------
+# G13: mutator chains.  G1/G3/G6 pin single mutators; here the reference's own Layer / Molecule / Atmosphere objects
+# are driven through sequences of them and everything the getters return is recorded after EVERY operation, so that state
+# carried from one call to the next (dirty flags, the effective window that only changeRange refreshes, cls:734-752, the
+# layer's own cross section that nothing ever resets, cls:39) is held to the reference and not to a second object of the
+# build.  The file holds the inputs, the operations as JSON and the recorded numbers.  To stay below 1 MB:
+#   * an array equal, bit for bit, to one already stored for the chain is stored as that array's key ("alias_json");
+#   * the absorption coefficient of a one-molecule layer is, bit for bit, its molecule's cross section times
+#     concentration * P / 1E4 / k / T (cls:583 added to zeros, cls:709-711); the generator checks that and stores the key
+#     of the cross section instead ("derived_json").
+# ----------------------------------------------------------------------------
+G13_SCALARS = ("T", "P", "depth", "rangeMin", "rangeMax", "effectiveRangeMin", "effectiveRangeMax", "resolution",
+               "distanceFromCenter")
+G13_SETTERS = ("setPPM", "setPPB", "setPercentage", "setConcentration")
+
+
+def _g13_setter_op(rng, mol):
+    """A concentration between 1e-4 and 2e-2 through one of the four setters (ppb is x 1e-8, cls:554)."""
+    kind = G13_SETTERS[int(rng.integers(0, 4))]
+    conc = float(10.0 ** rng.uniform(-4.0, -1.7))
+    scale = {"setPPM": 1e6, "setPPB": 1e8, "setPercentage": 1e2, "setConcentration": 1.0}[kind]
+    return dict(op=kind, mol=int(mol), args=[float("%.4g" % (conc * scale))])
+
+
+def _g13_seeded_ops(rng, n, n_mol, pressures, ranges):
+    """``n`` draws over the eight mutators; ``pressures`` is what changePressure draws from (whether a chain really goes
+    to both sides of its start is up to the caller: _g13_straddling_ops)."""
+    ops = []
+    for _ in range(n):
+        kind = int(rng.integers(0, 8))
+        if kind == 0:
+            ops.append(dict(op="changeTemperature", args=[int(rng.integers(200, 321))]))
+        elif kind == 1:
+            ops.append(dict(op="changePressure", args=[float(pressures[int(rng.integers(0, len(pressures)))])]))
+        elif kind == 2:
+            ops.append(dict(op="changeDepth", args=[float("%.5g" % rng.uniform(1.0, 5000.0))]))
+        elif kind == 3:
+            ops.append(dict(op="changeRange", args=list(ranges[int(rng.integers(0, len(ranges)))])))
+        else:
+            ops.append(_g13_setter_op(rng, rng.integers(0, n_mol)))
+    return ops
+
+
+def _g13_pressures_straddle(ops, P0, dfc_window=None):
+    """(a rise, a drop): some changePressure goes above the starting pressure while the window is still the one of a lower
+    pressure (made at construction or by the last changeRange, cls:734-752: the stale narrow window), and some goes below it."""
+    P, rise, drop = P0, False, False
+    window = P0 / 1013.25 * 5 if dfc_window is None else dfc_window
+    for op in ops:
+        if op["op"] == "changePressure":
+            P = op["args"][0]
+            rise |= P > P0 and P / 1013.25 * 5 > window
+            drop |= P < P0
+        elif op["op"] == "changeRange":
+            window = P / 1013.25 * 5
+    return rise, drop
+
+
+def _g13_straddling_ops(seed, n, n_mol, P0, pressures, ranges):
+    """Seeded draws in which the pressure goes to both sides of the start: two of the draws, at seeded positions, become a
+    changePressure above and one below ``P0``; the seed moves on until the rise meets a window that is too narrow for it."""
+    above, below = [p for p in pressures if p > P0], [p for p in pressures if p < P0]
+    for attempt in range(64):
+        rng = np.random.default_rng(seed + 1000 * attempt)
+        ops = _g13_seeded_ops(rng, n, n_mol, pressures, ranges)
+        up, down = (int(i) for i in rng.choice(n, 2, replace=False))
+        ops[up] = dict(op="changePressure", args=[float(above[int(rng.integers(0, len(above)))])])
+        ops[down] = dict(op="changePressure", args=[float(below[int(rng.integers(0, len(below)))])])
+        if all(_g13_pressures_straddle(ops, P0)):
+            return ops
+    raise AssertionError("no seeded chain with a rise into a narrow window and a drop")
+
+
+def _g13_apply(layer, op):
+    name = op["op"]
+    if name in G13_SETTERS:
+        getattr(layer[op["mol"]], name)(*op["args"])
+    else:
+        getattr(layer, name)(*op["args"])
+
+
+class _G13Store:
+    """Arrays of one chain: equal arrays are stored once."""
+
+    def __init__(self, arrays, prefix):
+        self.arrays, self.prefix, self.pool, self.alias, self.derived = arrays, prefix, [], {}, {}
+
+    def put(self, key, value):
+        value = np.array(value, dtype=np.float64)
+        for k, v in self.pool:
+            if v.shape == value.shape and np.array_equal(v, value, equal_nan=True):
+                self.alias[key] = k
+                return k
+        self.pool.append((key, value))
+        self.arrays["%s.%s" % (self.prefix, key)] = value
+        return key
+
+    def finish(self):
+        import json
+        self.arrays[self.prefix + ".alias_json"] = np.array(json.dumps(self.alias))
+        self.arrays[self.prefix + ".derived_json"] = np.array(json.dumps(self.derived))
+
+
+def _g13_flags(layer):
+    return [bool(layer.progressCrossSection)] + [bool(m.progressCrossSection) for m in layer] + \
+        [bool(i.progressCrossSection) for m in layer for i in m]
+
+
+def _g13_record(store, tag, layer, rec):
+    """Everything the issue lists, for ``layer`` in its current state, under the keys ``<tag>.*``."""
+    rec["flags_before"].append(_g13_flags(layer))
+    k_abs = np.array(CLS.getAbsCoef(layer))
+    layer_xs = np.array(CLS.getCrossSection(layer))
+    mol_xs = np.array(CLS.getCrossSection(layer[0]))
+    rec["flags_after"].append(_g13_flags(layer))
+    mol_key = store.put(tag + ".mol0_xsec", mol_xs)
+    store.put(tag + ".layer_xsec", layer_xs)
+    m = layer[0]
+    if len(layer) == 1 and np.array_equal(k_abs, mol_xs * m.concentration * layer.P / 1E4 / CLS.k / layer.T):
+        store.derived[tag + ".abs_coef"] = mol_key
+    else:
+        store.put(tag + ".abs_coef", k_abs)
+    rec["lengths"].append([len(i) for m in layer for i in m])
+    rec["scalars"].append([float(getattr(layer, s)) for s in G13_SCALARS])
+    rec["concentration"].append([float(m.concentration) for m in layer])
+
+
+def _g13_new_rec():
+    return dict(flags_before=[], flags_after=[], lengths=[], scalars=[], concentration=[])
+
+
+def _g13_save_rec(arrays, prefix, rec):
+    arrays[prefix + ".flags_before"] = np.array(rec["flags_before"], dtype=np.bool_)
+    arrays[prefix + ".flags_after"] = np.array(rec["flags_after"], dtype=np.bool_)
+    arrays[prefix + ".lengths"] = np.array(rec["lengths"], dtype=np.int64)
+    arrays[prefix + ".scalars"] = np.array(rec["scalars"], dtype=np.float64)
+    arrays[prefix + ".concentration"] = np.array(rec["concentration"], dtype=np.float64)
+
+
+def _g13_register(arrays, prefix, lines):
+    """lines: {species: key of a line list stored once in the file as ``lines.<key>.*``}"""
+    import json
+    for species, key in lines.items():
+        register(species, unpack_stored_lines(arrays, "lines." + key))
+    arrays[prefix + ".lines_json"] = np.array(json.dumps(lines))
+
+
+def unpack_stored_lines(arrays, prefix):
+    return {f: arrays["%s.%s" % (prefix, f)] for f in synthetic.FIELDS}
+
+
+def _g13_add_molecules(layer, molecules):
+    for species, depth, kind, value in molecules:
+        layer.addMolecule(species, isotopeDepth=depth, **{kind: value})
+
+
+def _g13_layer_chain(arrays, name, build, lines, ops, straddle=False):
+    """build: dict(depth, T, P, range_min, range_max, base_resolution, molecules=[[species, isotopeDepth, kind, value]]);
+    straddle: the RECORDED states hold a pressure above the start on a window narrower than its reach, and one below it"""
+    import json
+    assert len(ops) == 12, (name, len(ops))
+    prefix = "layer." + name
+    _reset_reference_state()
+    UT.BASE_RESOLUTION = build["base_resolution"]
+    store = _G13Store(arrays, prefix)
+    rec, copy_rec = _g13_new_rec(), _g13_new_rec()
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            _g13_register(arrays, prefix, lines)
+            layer = CLS.Layer(build["depth"], build["T"], build["P"], build["range_min"], build["range_max"], name=name)
+            _g13_add_molecules(layer, build["molecules"])
+            for s, op in enumerate(ops):
+                if op["op"] == "returnCopy":
+                    # the reference binds the copy's molecules to the OLD layer (cls:539); the chain copies while the old
+                    # layer's window is the fresh one, reads the copy at once and never touches it again
+                    assert (layer.effectiveRangeMin, layer.effectiveRangeMax) == \
+                        (max(layer.rangeMin - layer.distanceFromCenter, 0), layer.rangeMax + layer.distanceFromCenter)
+                    copy = layer.returnCopy()
+                    _g13_record(store, "s%d.copy" % s, copy, copy_rec)
+                else:
+                    _g13_apply(layer, op)
+                _g13_record(store, "s%d" % s, layer, rec)
+            store.put("end.transmission", layer.transmission(layer.planck(288)))
+            store.put("end.transmittance", CLS.getTransmittance(layer))
+    finally:
+        UT.BASE_RESOLUTION = .01
+    if straddle:
+        rows = [dict(zip(G13_SCALARS, r)) for r in rec["scalars"]]
+        assert any(op["op"] == "changePressure" and r["P"] > build["P"] and
+                   r["effectiveRangeMax"] - r["rangeMax"] < r["distanceFromCenter"] for op, r in zip(ops, rows)), name
+        assert any(r["P"] < build["P"] for r in rows), name
+    store.finish()
+    _g13_save_rec(arrays, prefix, rec)
+    if copy_rec["scalars"]:
+        _g13_save_rec(arrays, prefix + ".copy", copy_rec)
+    arrays[prefix + ".build_json"] = np.array(json.dumps(build))
+    # [molecule index, species key] per isotopologue in the layer's order, read off the reference's objects
+    arrays[prefix + ".species_json"] = np.array(json.dumps(
+        [[mi, synthetic.BY_GLOBAL_ISO[iso.globalIsoNumber][0]] for mi, m in enumerate(layer) for iso in m]))
+    arrays[prefix + ".ops_json"] = np.array(json.dumps(ops))
+
+
+def _g13_column_chain(arrays, name, layers, lines, ops):
+    """layers: [dict(depth, T, P, molecules=[...])] on one range; after every operation the top-of-atmosphere spectrum as
+    G7 computes it (the fold of Layer.transmission, cls:784-787, from the 288 K surface)."""
+    import json
+    assert len(ops) == 8, (name, len(ops))
+    prefix = "column." + name
+    _reset_reference_state()
+    store = _G13Store(arrays, prefix)
+    with contextlib.redirect_stdout(io.StringIO()):
+        _g13_register(arrays, prefix, lines)
+        atm = CLS.Atmosphere(name)
+        for L in layers:
+            _g13_add_molecules(atm.addLayer(L["depth"], L["T"], L["P"], L["range_min"], L["range_max"]), L["molecules"])
+        for s, op in enumerate(ops):
+            if op["op"] == "addLayer":
+                _g13_add_molecules(atm.addLayer(*op["args"]), op["molecules"])
+            elif op["layer"] == "all":
+                for layer in atm:
+                    _g13_apply(layer, op)
+            else:
+                _g13_apply(atm[op["layer"]], op)
+            spec = atm[0].planck(288)
+            for layer in atm:
+                spec = layer.transmission(spec)
+            store.put("s%d.spectrum" % s, spec)
+    store.finish()
+    arrays[prefix + ".layers_json"] = np.array(json.dumps(layers))
+    arrays[prefix + ".ops_json"] = np.array(json.dumps(ops))
+
+
+def g13():
+    import json
+    arrays = {"k_boltzmann": np.float64(CLS.k), "scalar_names_json": np.array(json.dumps(G13_SCALARS))}
+    # line lists: one region for the 0.01 chains, a wide one for the chain that starts at 10132.5 mbar (window +-50),
+    # a dense narrow one for the 0.001 chain
+    co2 = synthetic.make_lines(1300, 320, 628.0, 692.0)
+    co2b = synthetic.make_lines(1301, 120, 628.0, 692.0)
+    h2o = synthetic.make_lines(1302, 220, 628.0, 692.0)
+    ch4 = synthetic.make_lines(1303, 160, 628.0, 692.0)
+    wide = synthetic.make_lines(1304, 400, 590.0, 720.0)
+    fine = synthetic.make_lines(1305, 260, 654.0, 670.0)
+    for key, l in (("co2", co2), ("co2_636", co2b), ("h2o", h2o), ("ch4", ch4), ("wide", wide), ("fine", fine)):
+        l["a"] = np.ones(len(l["nu"]))           # (Einstein A: carried, never used, cls:245; ones cost the file nothing)
+        arrays.update(pack_lines("lines." + key, l))
+    # every chain starts on 10 cm^-1 (4 cm^-1 at 0.001); changeRange moves to 6 - 7 cm^-1 (2 at 0.001): what keeps the file small
+    ranges = [(650, 657), (652, 659), (655, 661), (648, 655)]
+
+    # up: built low, raised: the window stays the narrow one of 300 mbar until changeRange
+    rng = np.random.default_rng(13001)
+    ops = [dict(op="changePressure", args=[1013.25]), dict(op="changeTemperature", args=[270]),
+           dict(op="changeRange", args=[652, 659])] + _g13_seeded_ops(rng, 9, 2, [1013.25, 700.0, 300.0, 120.0], ranges)
+    _g13_layer_chain(arrays, "up", dict(depth=100.0, T=296, P=300.0, range_min=650, range_max=660, base_resolution=.01,
+                                        molecules=[["co2", 1, "ppm", 400.0], ["h2o", 1, "percentage", 1.0]]),
+                     dict(co2="co2", h2o="h2o"), ops)
+    # down: built at 10132.5 mbar (resolution 0.1, regrid), lowered to 50 mbar: W = 25 on a window of +-50 cm^-1
+    rng = np.random.default_rng(13002)
+    ops = [dict(op="changePressure", args=[50.0]), dict(op="changeTemperature", args=[230]), dict(op="changeDepth", args=[2500.0]),
+           dict(op="changeRange", args=[652, 659]), dict(op="changePressure", args=[700.0])] + \
+        _g13_seeded_ops(rng, 7, 1, [10132.5, 1013.25, 300.0, 50.0], ranges)
+    _g13_layer_chain(arrays, "down", dict(depth=100.0, T=260, P=10132.5, range_min=650, range_max=660, base_resolution=.01,
+                                          molecules=[["co2", 1, "ppm", 400.0]]), dict(co2="wide"), ops)
+    # fine: BASE_RESOLUTION 0.001; the resolution switches between 0.01 (1013.25) and 0.001 (101.0, 50.0)
+    rng = np.random.default_rng(13003)
+    fine_ranges = [(660, 662), (661, 663), (659.5, 661.5)]
+    ops = [dict(op="changePressure", args=[101.0]), dict(op="changeRange", args=[661, 663]), dict(op="changePressure", args=[50.0]),
+           dict(op="changeTemperature", args=[250]), dict(op="changePressure", args=[1013.25])] + \
+        _g13_seeded_ops(rng, 7, 1, [1013.25, 101.0, 50.0], fine_ranges)
+    _g13_layer_chain(arrays, "fine", dict(depth=1000.0, T=296, P=1013.25, range_min=660, range_max=664, base_resolution=.001,
+                                          molecules=[["co2", 1, "ppm", 400.0]]), dict(co2="fine"), ops)
+    # mix: three molecules, two isotopologues in the first, the four setters, a copy read at once
+    rng = np.random.default_rng(13004)
+    ops = [dict(op="setPPM", mol=0, args=[420.0]), dict(op="setPPB", mol=2, args=[1900.0]), dict(op="setPercentage", mol=1, args=[0.8]),
+           dict(op="setConcentration", mol=1, args=[0.004]), dict(op="returnCopy")] + \
+        _g13_seeded_ops(rng, 7, 3, [1013.25, 800.0, 500.0, 200.0], ranges)
+    _g13_layer_chain(arrays, "mix", dict(depth=250.0, T=275, P=800.0, range_min=650, range_max=660, base_resolution=.01,
+                                         molecules=[["co2", 2, "ppm", 400.0], ["h2o", 1, "%", 1.5], ["ch4", 1, "ppb", 1800.0]]),
+                     dict(co2="co2", co2_636="co2_636", h2o="h2o", ch4="ch4"), ops)
+    # seeded chains: the pressure goes to both sides of the start, the rise into a window still made for a lower pressure
+    for name, seed, P0, mols, lines in (("r0", 13005, 500.0, [["co2", 1, "ppm", 400.0]], dict(co2="co2")),
+                                        ("r1", 13006, 700.0, [["h2o", 1, "percentage", 1.0], ["co2", 1, "ppm", 400.0]],
+                                         dict(co2="co2", h2o="h2o"))):
+        ops = _g13_straddling_ops(seed, 12, len(mols), P0, [1013.25, 900.0, P0, 250.0, 90.0], ranges)
+        _g13_layer_chain(arrays, name, dict(depth=50.0, T=280, P=P0, range_min=650, range_max=660, base_resolution=.01,
+                                            molecules=mols), lines, ops, straddle=True)
+    arrays["layer_chains_json"] = np.array(json.dumps(["up", "down", "fine", "mix", "r0", "r1"]))
+
+    # columns: three layers, one live Atmosphere
+    mol2 = lambda perc: [["co2", 1, "ppm", 400.0], ["h2o", 1, "percentage", perc]]
+    layers = [dict(depth=2e4, T=288, P=1013.25, range_min=650, range_max=660, molecules=mol2(1.0)),
+              dict(depth=5e4, T=262, P=600.0, range_min=650, range_max=660, molecules=mol2(0.2)),
+              dict(depth=1.2e5, T=231, P=150.0, range_min=650, range_max=660, molecules=mol2(0.01))]
+    for name, seed in (("a", 13011), ("b", 13012)):
+        rng = np.random.default_rng(seed)
+        new_range = [(652, 659), (648, 655)][seed % 2]
+        ops = [dict(op="changePressure", layer=1, args=[950.0]),                       # raised: stale narrow window
+               dict(op="changePressure", layer=0, args=[400.0]),                       # lowered: stale wide window
+               dict(_g13_setter_op(rng, rng.integers(0, 2)), layer=int(rng.integers(0, 3))),
+               dict(op="changeRange", layer="all", args=list(new_range)),
+               dict(op="addLayer", args=[8e4, 220, 80.0, new_range[0], new_range[1]], molecules=mol2(0.005))]
+        for op in _g13_seeded_ops(rng, 3, 2, [1013.25, 500.0, 100.0], [new_range]):
+            ops.append(dict(op, layer="all" if op["op"] == "changeRange" else int(rng.integers(0, 4))))
+        if name == "b":      # another order: the new range and the fourth layer first (later operations name them), the rest shuffled
+            order = rng.permutation(8)
+            ops = [ops[3], ops[4]] + [ops[i] for i in order if i not in (3, 4)]
+        _g13_column_chain(arrays, name, layers, dict(co2="co2", h2o="h2o"), ops)
+    arrays["column_chains_json"] = np.array(json.dumps(["a", "b"]))
+    save("G13_mutator_chains", **arrays)
+
+
 if __name__ == "__main__":
     if not os.path.isdir(REFERENCE):
         sys.exit("needs /root/reference (build container only)")
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13"]
     for name in which:
         globals()[name]()

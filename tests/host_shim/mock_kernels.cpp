@@ -18,6 +18,57 @@ long long fail_malloc_at = -1;
 long long clock = 0;
 long long live_allocs = 0, live_streams = 0, live_events = 0, live_graphs = 0, live_host = 0;
 long long launches = 0;      // stand-in launchers entered (the driver: a refused call must not have enqueued anything)
+long long staged_copies = 0, staged_on_middle = 0, staged_rewrites = 0, stream_syncs = 0;
+
+// page-locked blocks, the ranges copies were staged out of, and those among them that nothing the host waited for covers yet
+struct HostBlock { char* p; size_t bytes; };
+struct Range { char* p; size_t n; mock_stream* stream; long long seq; };
+static std::vector<HostBlock> host_blocks;
+static std::vector<Range> copied, pending;
+static bool overlap(const char* a, size_t na, const char* b, size_t nb) { return a < b + nb && b < a + na; }
+
+void host_block_made(void* p, size_t bytes) { host_blocks.push_back(HostBlock{(char*)p, bytes}); }
+void host_block_freed(void* p) {
+    for (size_t i = 0; i < host_blocks.size(); ++i) {
+        if (host_blocks[i].p != (char*)p) continue;
+        const HostBlock b = host_blocks[i];
+        auto inside = [&](const Range& r) { return overlap(r.p, r.n, b.p, b.bytes); };
+        copied.erase(std::remove_if(copied.begin(), copied.end(), inside), copied.end());
+        pending.erase(std::remove_if(pending.begin(), pending.end(), inside), pending.end());
+        ASAN_UNPOISON_MEMORY_REGION(b.p, b.bytes);
+        host_blocks.erase(host_blocks.begin() + (long)i);
+        return;
+    }
+}
+void before_read(const void* src, size_t n) {
+    for (const Range& r : pending)
+        if (overlap(r.p, r.n, (const char*)src, n)) ASAN_UNPOISON_MEMORY_REGION(r.p, r.n);     // (poisoned again below or by retire)
+}
+void after_read() { for (const Range& r : pending) ASAN_POISON_MEMORY_REGION(r.p, r.n); }
+void staged_copy(const void* src, size_t n, mock_stream* stream) {
+    const char* s = (const char*)src;
+    for (const HostBlock& b : host_blocks) {
+        if (!n || s < b.p || s + n > b.p + b.bytes) continue;
+        ++staged_copies;
+        const size_t end = ((size_t)(s - b.p) + n + 255) & ~(size_t)255;
+        if (b.bytes >= 512 && end == b.bytes / 2) ++staged_on_middle;
+        bool again = false;
+        for (size_t i = 0; i < copied.size();)
+            if (overlap(copied[i].p, copied[i].n, s, n)) { again = true; copied[i] = copied.back(); copied.pop_back(); } else ++i;
+        if (again) ++staged_rewrites;
+        copied.push_back(Range{(char*)src, n, stream, staged_copies});
+        pending.push_back(copied.back());
+        break;
+    }
+}
+void retire(mock_stream* stream, long long up_to) {
+    for (size_t i = 0; i < pending.size();)
+        if ((!stream || pending[i].stream == stream) && pending[i].seq <= up_to) {
+            ASAN_UNPOISON_MEMORY_REGION(pending[i].p, pending[i].n);
+            pending[i] = pending.back(); pending.pop_back();
+        } else ++i;
+    after_read();          // (a retired range may have overlapped one that is still pending)
+}
 }
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "mock kernel: violated: %s (%s:%d)\n", #cond, __FILE__, __LINE__); abort(); } } while (0)

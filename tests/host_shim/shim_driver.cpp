@@ -322,6 +322,34 @@ static void one_round(int round) {
     (void)round;
 }
 
+// The pinned staging ring (stage_alloc in lbl_api.hip) under a host that runs ahead of the stream: column sweeps whose argument
+// blocks differ (another layer temperature each) stage one block of one rounded size per call, and nothing in between
+// synchronises the stream.  Under LBL_SANITIZER_BUILD the ring holds exactly 8 such blocks, so every fourth block ends on the
+// middle or on the capacity, and the third lap writes blocks whose copies only the ring's own events can have covered: the
+// stand-in runtime keeps the source of a staged copy poisoned until the host has waited for something that covers it.
+static void staging_ring_run() {
+    lbl_ctx* ctx = nullptr;
+    MUST(lbl_ctx_create(0, &ctx));
+    const int64_t n = 64;
+    lbl_buffer* trans = nullptr, *out = nullptr;
+    MUST(lbl_buffer_create(ctx, n, &trans)); MUST(lbl_buffer_create(ctx, n, &out));
+    MUST(lbl_buffer_fill(trans, 0.5));
+    double T = 200.0;
+    auto sweep = [&]() { T += 1.0; MUST(lbl_column_sweep_dev(ctx, 1, &trans, &T, 600.0, 600.64, n, 0, 0, nullptr, 288.0, out)); };
+    for (int i = 0; i < 8; ++i) sweep();                    // the 8 argument slots are made (each one drains the stream)
+    const long long syncs = mockhip::stream_syncs, copies = mockhip::staged_copies;
+    const int laps = 4;
+    for (int i = 0; i < 8 * laps; ++i) sweep();
+    if (mockhip::stream_syncs != syncs || mockhip::staged_copies != copies + 8 * laps) {
+        fprintf(stderr, "staging ring run: %lld stream synchronisations and %lld staged copies in %d sweeps\n", mockhip::stream_syncs - syncs,
+                mockhip::staged_copies - copies, 8 * laps);
+        exit(7);
+    }
+    MUST(lbl_sync(ctx));
+    MUST(lbl_buffer_destroy(trans)); MUST(lbl_buffer_destroy(out));
+    MUST(lbl_ctx_destroy(ctx));
+}
+
 int main(int argc, char** argv) {
     const unsigned long long seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int rounds = argc > 2 ? atoi(argv[2]) : 20;
@@ -332,6 +360,10 @@ int main(int argc, char** argv) {
     mockhip::device_count = 0;
     { lbl_ctx* c = nullptr; if (lbl_ctx_create(0, &c) != LBL_ERR_NO_DEVICE) return 5; }      // no device: loud, nothing half-made
     mockhip::device_count = 1;
+    const long long c0 = mockhip::staged_copies, m0 = mockhip::staged_on_middle, w0 = mockhip::staged_rewrites;
+    staging_ring_run();
+    printf("staging ring run: %lld staged copies, %lld ended on the middle of their pinned block, %lld out of a range written again\n",
+           mockhip::staged_copies - c0, mockhip::staged_on_middle - m0, mockhip::staged_rewrites - w0);
     for (int r = 0; r < rounds; ++r) one_round(r);
     if (mockhip::live_allocs || mockhip::live_streams || mockhip::live_events || mockhip::live_graphs || mockhip::live_host) {
         fprintf(stderr, "leaked: %lld device blocks, %lld streams, %lld events, %lld graphs, %lld page-locked blocks\n", mockhip::live_allocs,

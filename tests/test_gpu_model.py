@@ -272,7 +272,11 @@ def test_g8_xsc_molecules(pyrad, tmp_path):
 def test_lazy_protocol_random_sequences(pyrad, seed):
     """The dirty-flag protocol (cls:32-88, 543-560, 734-755) under random sequences of the mutators the
     interactive menu offers: after every operation the layer's absorption coefficient and transmittance
-    equal those of a layer built from scratch in the current state."""
+    equal those of a layer of THIS BUILD made from scratch in the current state.  A self-check: both sides are
+    pyrad_amd.model, so an invalidation that is wrong on both routes passes, and it holds for the reference
+    only because the chain starts at the highest pressure it draws (after a pressure rise the reference keeps
+    the narrow window and differs from a fresh layer).  The reference itself is the yardstick in
+    tests/test_gpu_mutator_chains.py."""
     rng = np.random.default_rng(4000 + seed)
     lines = dict(co2=synthetic.make_lines(41, 500, 580, 720), h2o=synthetic.make_lines(42, 300, 580, 720))
     source(**lines)
@@ -704,8 +708,10 @@ def test_the_reference_rounding_chain_takes_the_per_list_route(pyrad):
 
 
 def test_resident_column_follows_every_kind_of_change(pyrad):
-    """Atmosphere.transmission through the resident column handle (lbl_column, round 6) against a freshly built atmosphere
-    through the general route, after each kind of change between calls: temperature, pressure (new windows), range, depth,
+    """Atmosphere.transmission through the resident column handle (lbl_column, round 6) against a second atmosphere of THIS
+    BUILD, built from scratch with the same changes applied and sent through the general route (a self-check of one route
+    against the other; the reference's own numbers for such chains are in tests/test_gpu_mutator_chains.py), after each kind of
+    change between calls: temperature, pressure (new windows), range, depth,
     concentration, a molecule swapped for another one, a layer added, the surface given as a spectrum - and unchanged calls."""
     lines = dict(co2=synthetic.make_lines(71, 900, 580, 720), h2o=synthetic.make_lines(72, 600, 580, 720), ch4=synthetic.make_lines(73, 300, 580, 720))
     source(**lines)

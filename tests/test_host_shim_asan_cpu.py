@@ -8,9 +8,17 @@ kernels read and write (mock_kernels.cpp, sharing the launch-shape arithmetic of
 real launchers), with -fsanitize=address,undefined and scratch blocks without slack (-DLBL_SANITIZER_BUILD).  shim_driver
 then goes through the PUBLIC C ABI with seeded random cells, shards, columns, 70-line-list layers, views, option
 settings, graph captures, bad arguments, injected allocation failures and random destruction orders; every object the
-stand-in runtime handed out must have come back at the end.  CPU only: nothing of this is ever linked into
+stand-in runtime handed out must have come back at the end.
+
+The stand-in runtime copies synchronously, so by itself it cannot see a page-locked staging block that the host rewrites before
+a queued hipMemcpyAsync has read it.  It therefore keeps the source range of every staged host-to-device copy poisoned until the
+host has waited for something that covers the copy (mock/hip/hip_runtime.h), and the driver opens with a run of column sweeps that
+stages four laps of the 8-block staging ring without a stream synchronisation in between (stage_alloc once took the half it was
+leaving from the END of the last allocation: a block ending exactly on the middle of the ring recorded no event, and nothing was
+ever waited for).  CPU only: nothing of this is ever linked into
 libpyrad_hip.so or run on the GPU box."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -48,3 +56,22 @@ def test_the_harness_sees_a_block_sized_too_small(driver):
     """self-test: the line-prep stand-in made to write counters past what the shim reserved for them is reported"""
     p = run(driver, 1, 3, {"SHIM_INJECT_OVERRUN": "1"})
     assert p.returncode != 0 and "AddressSanitizer" in p.stderr and "buffer-overflow" in p.stderr
+
+
+def test_the_staging_ring_run_reaches_the_boundary_and_is_clean(driver):
+    """the run of column sweeps stages 8 + 32 blocks of one size: blocks end on the middle of the pinned ring and ranges are written
+    again after a copy out of them (so it cannot pass by never getting there), and no block is written while a copy is pending"""
+    p = run(driver, 1, 1)
+    assert p.returncode == 0, (p.stdout[-500:], p.stderr[-6000:])
+    m = re.search(r"staging ring run: (\d+) staged copies, (\d+) ended on the middle of their pinned block, (\d+) out of a range written again", p.stdout)
+    assert m, p.stdout[-500:]
+    copies, on_middle, rewrites = (int(x) for x in m.groups())
+    assert copies >= 8 + 17 and on_middle >= 2 and rewrites >= 2, m.group(0)
+
+
+def test_the_harness_sees_a_pinned_block_written_before_its_copy_was_waited_for(driver):
+    """self-test: with the stand-in's hipEventSynchronize covering nothing (as if the ring had not waited for the half it enters)
+    the same run is reported as a write into a poisoned range"""
+    p = run(driver, 1, 1, {"SHIM_INJECT_NO_EVENT_WAIT": "1"})
+    assert p.returncode != 0 and "AddressSanitizer" in p.stderr and "use-after-poison" in p.stderr
+    assert re.search(r"^\s*#\d+ 0x[0-9a-f]+ in (device_args|stage_alloc)\b", p.stderr, re.M), p.stderr[:3000]      # a frame of the report's stack
