@@ -623,6 +623,49 @@ int lbl_ray_radiance_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* a
                                 lbl_buffer* surface_down /* may be NULL */, double surface_down_norm,
                                 lbl_buffer* radiance, lbl_buffer* transmittance /* may be NULL */);
 
+/* ---- direct solar beam (beyond the reference; ABI 5, backward compatible) ------------------------------------------------
+ * pyrad_amd.model.Atmosphere.solarFluxes: collimated beams (suns) that enter at the top, are attenuated along their slant
+ * paths, and are reflected by the surface; the gas absorbs and nothing emits.  Without scattering the problem is linear: a
+ * sunlit column's fluxes are lbl_column_flux_dev's (or a variant's) plus these, level by level.
+ * Column, layer order, levels, grid, bands, nan_to_num, partial sums and the level_flux layout are lbl_column_flux_dev's
+ * (range_min / range_max are taken for symmetry: no wavenumber enters).  At grid point nu_j, for beams s = 0 .. n_beams-1 and
+ * diffuse angles k = 0 .. n_angles-1 with (mu_k, W_k):
+ *   tau_l  = k_l(nu_j) * depth_l
+ *   d_sl   = exp(-tau_l * slant[s * n_layers + l])       slant >= 0: path length through layer l per unit depth
+ *   down:   S_s[L] = S0[j]                               S_s[l]   = d_sl * S_s[l+1]
+ *           F_down_i(nu_j) = sum_s beam_weight[s] * S_s[i]          (beam 0 first: w_0 S_0, then fma(w_s, S_s, .) in order)
+ *   surface (e = emissivity[j] or emissivity_all, as lbl_column_flux_surface_dev takes it; albedo 1 - e), F0 = F_down_0(nu_j):
+ *     reflection 0 (Lambertian): I_k[0] = ((1 - e) * F0) / Wsum     I_k[l+1] = exp(-tau_l * (1 / mu_k)) * I_k[l]
+ *                                F_up_i = sum_k W_k I_k[i]          Wsum = W_0 + W_1 + ... added in angle order
+ *     reflection 1 (specular):   U_s[0] = (1 - e) * S_s[0]          U_s[l+1] = d_sl * U_s[l]
+ *                                F_up_i = sum_s beam_weight[s] * U_s[i]
+ *   level_flux[b][0][i] = sum over j in band b of nan_to_num(F_up_i(nu_j)), level_flux[b][1][i] likewise for F_down_i.
+ * No thermal emission enters anywhere and no temperature is an argument.  S0 (n points) is the beams' irradiance on a plane
+ * normal to them, W m^-2 per cm^-1; beam_weight[s] is what the host makes of weight_s * mu0_s (the projection onto the
+ * horizontal).  up_top, down_surface and up_surface (may be NULL; n points each) receive F_up at the top, F_down at the
+ * surface and F_up at the surface at every point of every band, 0 elsewhere.  exp is the flux kernels' (x > 800 gives
+ * exp(-800) = 0, a NaN stays a NaN), every operation is rounded on its own (no contraction beside the fma chain named
+ * above), sums run in a fixed order without atomics: the same inputs and launch give the same bits.  A beam's operations do
+ * not depend on the other beams of the call.
+ * At most lbl_limit("flux_angles") = 8 beams and 8 angles, lbl_limit("flux_bands") bands and lbl_limit("layers_per_column")
+ * layers; n_angles may be 0 (mu and weight are then not read) when reflection == 1.
+ * LBL_ERR_BAD_ARG, all before anything is enqueued: a NULL array or a negative count; a count beyond its limit; S0,
+ * level_flux (n_bands x 2 x (n_layers + 1)), an abs_coef, emissivity or a spectrum shorter than n; an empty band or one outside
+ * [0, n); a depth that is negative or NaN; a slant that is negative or not finite; a beam weight that is not finite; a mu
+ * outside (0, 1] or an angle weight that is not finite; reflection not 0 or 1; emissivity NULL with emissivity_all outside
+ * [0, 1] or NaN; reflection 0 with no angle or with weights whose sum is not finite and > 0; "sweep_ieee_divisions" 1, as
+ * for lbl_column_flux_dev.  The host arrays are copied and not retained.  Stream-ordered; nothing is synchronised. */
+int lbl_column_solar_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                         double range_min, double range_max, int64_t n,
+                         lbl_buffer* S0, int n_beams, const double* beam_weight,
+                         const double* slant /* n_beams x n_layers */,
+                         int n_angles, const double* mu, const double* weight,
+                         int n_bands, const int64_t* band_first, const int64_t* band_count,
+                         lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                         int reflection /* 0 Lambertian, 1 specular */,
+                         lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface,
+                         lbl_buffer* up_surface /* may be NULL */);
+
 /* ---- ray-path Jacobians (beyond the reference; ABI 5, backward compatible) --------------------------------------------
  * pyrad_amd.model.Atmosphere.pathJacobians: the weighting functions of the radiance lbl_ray_radiance_dev computes - its
  * analytic derivatives to every crossed layer's optical depth and (Planck) temperature, to the source temperature and to any

@@ -124,6 +124,9 @@ SIGNATURES = {
     "lbl_ray_radiance_linear_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), _D, C.POINTER(C.c_int32), _P,
                                               C.c_double, _P, C.c_double, _P, C.c_double, _P, _P]),
+    "lbl_column_solar_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, _P, C.c_int, _D, _D,
+                                       C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, C.c_double,
+                                       C.c_int, _P, _P, _P, _P]),
     "lbl_ray_jacobian_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lbl_ray_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
@@ -672,6 +675,25 @@ class Context:
                                weight, band_first, band_count),
             *self._emissivity_args(emissivity), int(reflection), _hb(level_flux), _hb(up_top), _hb(down_surface),
             _hb(up_surface)))
+
+    def column_solar_dev(self, abs_coef, depth, range_min, range_max, n, S0, beam_weight, slant, mu, weight, band_first,
+                         band_count, level_flux, emissivity=1.0, reflection=0, up_top=None, down_surface=None, up_surface=None):
+        """The direct solar beam (lbl_column_solar_dev): ``S0`` a Buffer of n points, the beams' irradiance at the top;
+        ``beam_weight`` one number per beam; ``slant`` beams x layers path lengths per unit depth; ``mu`` / ``weight`` the
+        diffuse angles of a Lambertian surface (may be empty for ``reflection`` 1); ``emissivity`` and ``reflection`` as
+        column_flux_surface_dev takes them.  ``level_flux`` receives len(band_first) x 2 x (layers + 1) band sums [band][up,
+        down][level]; ``up_top`` / ``down_surface`` / ``up_surface`` (optional, n points) the spectral fluxes."""
+        nl, ns = len(abs_coef), len(beam_weight)
+        slant = _as_f64(slant).reshape(-1)
+        if len(slant) != ns * nl:
+            raise ValueError("column_solar_dev: one slant per beam and layer")
+        self.check(self.lib.lbl_column_solar_dev(
+            self.h, nl, _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(d) for d in depth]), float(range_min),
+            float(range_max), int(n), _hb(S0), ns, _arr(C.c_double, [float(w) for w in beam_weight]),
+            _arr(C.c_double, [float(v) for v in slant]), len(mu), _arr(C.c_double, [float(m) for m in mu]),
+            _arr(C.c_double, [float(w) for w in weight]), len(band_first), _arr(C.c_int64, [int(f) for f in band_first]),
+            _arr(C.c_int64, [int(c) for c in band_count]), *self._emissivity_args(emissivity), int(reflection),
+            _hb(level_flux), _hb(up_top), _hb(down_surface), _hb(up_surface)))
 
     def column_jacobian_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                             jac, I_surface=None, surface_T=0.0, term_abs_coef=(), term_layer=(), ln_tau_spectra=None,

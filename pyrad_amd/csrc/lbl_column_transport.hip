@@ -2,8 +2,9 @@
 // sequences of lbl_column_flux_dev, lbl_column_jacobian_dev, lbl_ray_radiance_dev and lbl_ray_jacobian_dev, and of their
 // variants over a reflecting surface, lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev, lbl_column_jacobian_surface_dev
 // and lbl_ray_jacobian_surface_dev, of the linear-source variants lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev, and
-// of their Jacobians lbl_column_jacobian_linear_dev and lbl_ray_jacobian_linear_dev.
-// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i and K5j of lbl_kernels.hip; the context's internals
+// of their Jacobians lbl_column_jacobian_linear_dev and lbl_ray_jacobian_linear_dev, and of the direct solar beam,
+// lbl_column_solar_dev.
+// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j and K5k of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -246,6 +247,104 @@ extern "C" int lbl_column_flux_linear_dev(lbl_ctx* ctx, int n_layers, lbl_buffer
     return surface_flux_call(ctx, a->pbkT_top, a, launch_linear_flux, n_layers, abs_coef, T_edge, depth, range_min, range_max,
                              n, I_surface, surface_T, I_top, n_angles, mu, weight, n_bands, band_first, band_count, emissivity,
                              emissivity_all, reflection, level_flux, up_top, down_surface, up_surface);
+} LBL_GUARD_END(ctx)
+
+// K5k: no temperatures and no surface source, so check_column does not fit; the checks follow its order.  The scratch is one
+// reservation: F_down at the surface between the two walks (Lambertian, unless the caller's down_surface serves) and behind
+// it the partials of the widest band.
+extern "C" int lbl_column_solar_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                                    double range_min, double range_max, int64_t n, lbl_buffer* S0, int n_beams,
+                                    const double* beam_weight, const double* slant, int n_angles, const double* mu,
+                                    const double* weight, int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                    lbl_buffer* emissivity, double emissivity_all, int reflection, lbl_buffer* level_flux,
+                                    lbl_buffer* up_top, lbl_buffer* down_surface, lbl_buffer* up_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    (void)range_min; (void)range_max;       // (the grid of the other column calls: nothing here depends on a wavenumber)
+    std::vector<char> blk(sizeof(SolarArgs), 0);
+    SolarArgs* a = (SolarArgs*)blk.data();
+    if (n_layers < 0 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
+    if (n < 0) return column_fail(ctx, LBL_ERR_BAD_ARG, "negative n");
+    if (n_layers > 0 && (!abs_coef || !depth || !slant)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if (ctx_sweep_ieee(ctx))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", "solar fluxes");
+    if (n_beams < 1 || n_beams > kMaxFluxAngles) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d beams", kMaxFluxAngles);
+    if (!beam_weight) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL beam set");
+    if (reflection != 0 && reflection != 1)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "reflection must be 0 (Lambertian) or 1 (specular)");
+    if (n_angles < (reflection == 0 ? 1 : 0) || n_angles > kMaxFluxAngles)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "%d..%d angles", reflection == 0 ? 1 : 0, kMaxFluxAngles);
+    if (n_angles > 0 && (!mu || !weight)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL angle set");
+    if (n_bands < 1 || n_bands > kMaxFluxBands) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d bands", kMaxFluxBands);
+    if (!band_first || !band_count) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL band list");
+    const int nv = 2 * (n_layers + 1);
+    int rc;
+    if ((rc = ctx_check_buffer(ctx, S0, n, "S0", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    int64_t max_count = 0;
+    for (int b = 0; b < n_bands; ++b) {
+        if (band_first[b] < 0 || band_count[b] < 1 || band_count[b] > n - band_first[b])
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "band %d: empty or outside [0, n)", b);
+        max_count = std::max(max_count, band_count[b]);
+    }
+    for (int l = 0; l < n_layers; ++l) {
+        if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
+        if (!(depth[l] >= 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: depth must be >= 0", l);
+        a->abs_coef[l] = buffer_data(abs_coef[l]);
+        a->depth[l] = depth[l];
+    }
+    for (int s = 0; s < n_beams; ++s) {
+        if (!std::isfinite(beam_weight[s])) return column_fail(ctx, LBL_ERR_BAD_ARG, "beam %d: weight must be finite", s);
+        a->beam_w[s] = beam_weight[s];
+        for (int l = 0; l < n_layers; ++l) {
+            const double v = slant[(size_t)s * n_layers + l];
+            if (!(v >= 0) || !std::isfinite(v))
+                return column_fail(ctx, LBL_ERR_BAD_ARG, "beam %d, layer %d: slant must be finite and >= 0", s, l);
+            a->slant[s][l] = v;
+        }
+    }
+    double w_sum = 0.0;
+    for (int k = 0; k < n_angles; ++k) {
+        if (!(mu[k] > 0 && mu[k] <= 1)) return column_fail(ctx, LBL_ERR_BAD_ARG, "angle %d: mu must lie in (0, 1]", k);
+        if (!std::isfinite(weight[k])) return column_fail(ctx, LBL_ERR_BAD_ARG, "angle %d: weight must be finite", k);
+        a->rmu[k] = 1.0 / mu[k];
+        a->w[k] = weight[k];
+        w_sum += weight[k];
+    }
+    if (reflection == 0 && (!(w_sum > 0.0) || !std::isfinite(w_sum)))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "the weights must add up to a finite sum > 0");
+    a->w_sum = w_sum;
+    a->S0 = buffer_data(S0);
+    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a->emissivity_all = emissivity_all;
+    a->up_top = up_top ? buffer_data(up_top) : nullptr;
+    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
+    a->up_surface = up_surface ? buffer_data(up_surface) : nullptr;
+    a->n = n;
+    a->n_layers = n_layers; a->n_beams = n_beams; a->n_angles = n_angles; a->reflection = reflection;
+
+    // (f0 is read with the vector loads of the coefficients: it starts the reservation and the partials follow 32-byte aligned)
+    const size_t f0_bytes = reflection == 0 && !down_surface ? ((size_t)n * sizeof(double) + 31) & ~(size_t)31 : 0;
+    void* scratch = nullptr;
+    if ((rc = ctx_reduction_scratch(ctx, f0_bytes + (size_t)column_transport_partials(max_count, 4) * nv * sizeof(double), &scratch)))
+        return rc;
+    a->f0 = reflection == 1 ? nullptr : down_surface ? a->down_surface : (double*)scratch;
+    double* partial = (double*)((char*)scratch + f0_bytes);
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, a, sizeof(SolarArgs), &d_args))) return rc;
+    const hipStream_t s = ctx_stream(ctx);
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    // (points outside every band keep 0 in the spectra)
+    for (double* p : {a->up_top, a->down_surface, a->up_surface})
+        if (p && n > 0) COLUMN_HIP_TRY(ctx, hipMemsetAsync(p, 0, (size_t)n * sizeof(double), s));
+    for (int b = 0; b < n_bands; ++b)
+        launch_solar((const SolarArgs*)d_args, n_layers, n_beams, n_angles, reflection, band_first[b], band_count[b], partial,
+                     buffer_data(level_flux) + (size_t)b * nv, s);
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
 } LBL_GUARD_END(ctx)
 
 // What lbl_column_jacobian_dev and lbl_column_jacobian_surface_dev check behind check_column, then the JacArgs part of the

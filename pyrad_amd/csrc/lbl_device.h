@@ -330,6 +330,34 @@ struct LinearRayArgs : RaySurfaceArgs {
 };
 void launch_linear_ray(const LinearRayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s);
 
+// Direct solar beam (K5k, lbl_column_transport.hip: lbl_column_solar_dev): collimated beams attenuated down the column along
+// their slant paths, reflected by the surface, and the reflected light attenuated on its way up.  No emission anywhere, so
+// no temperatures and no grid (a point's wavenumber is never formed).  A block of its own: the beams' slants per layer are
+// workgroup-uniform tables.  Values per band as K5c's: [up, down][level 0 .. L]; partials and final reduction are K5c's.
+struct SolarArgs {
+    const double* abs_coef[kMaxLayers];
+    double depth[kMaxLayers];
+    double slant[kMaxFluxAngles][kMaxLayers];   // beam s, layer l: path length through the layer per unit depth
+    double beam_w[kMaxFluxAngles];      // what multiplies beam s in a level's flux (weight_s mu0_s)
+    double rmu[kMaxFluxAngles];         // 1 / mu_k of the diffuse angles (Lambertian reflection)
+    double w[kMaxFluxAngles];           // W_k
+    double w_sum;                       // W_0 + W_1 + ..., added on the host in angle order (Lambertian: > 0 and finite)
+    const double* S0;                   // the beams' irradiance at the top, n points
+    const double* emissivity;           // n points, or nullptr: emissivity_all
+    double emissivity_all;
+    double* f0;                         // Lambertian: F_down at the surface between the two walks, n points - down_surface
+                                        // itself where the caller asked for it, else scratch; specular: nullptr
+    double* up_top;                     // optional spectra, as SurfaceFluxArgs'
+    double* down_surface;
+    double* up_surface;
+    long long n;
+    int32_t n_layers, n_beams, n_angles, reflection;
+};
+// one band [first, first + count): the downward walk (with the upward one behind it where the reflection is specular), the
+// Lambertian upward walk from f0, and the fixed-order reductions into level_flux[0 .. 2 (n_layers + 1))
+void launch_solar(const SolarArgs* d_args, int n_layers, int n_beams, int n_angles, int reflection, long long first,
+                  long long count, double* partial, double* level_flux, hipStream_t s);
+
 // Ray-path Jacobians (K5f, lbl_column_transport.hip: lbl_ray_jacobian_dev): K5e's walk, then the segments last to first
 // with K5d's transmittance-and-emission recurrence, one output row per ray, kind and crossed layer.  RayArgs' block with
 // more tables behind it; `radiance` may be nullptr here and `transmittance` is not used.  A ray's rows start at row_first[r]:

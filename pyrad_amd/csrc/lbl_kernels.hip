@@ -29,6 +29,8 @@
 //   K5j linear_jacobian_kernel, ray_linear_jacobian_kernel   K5h's two kernels with K5i's step: d ln tau through g', one
 //                              temperature row per layer edge or segment end (jacobiansLinear(), pathJacobiansLinear(),
 //                              observeLinear(); beyond the reference)
+//   K5k solar_beam_kernel, solar_diffuse_kernel   K5c's walks without emission: collimated beams attenuated along their slant
+//                              paths, reflected by the surface (Atmosphere.solarFluxes; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -4066,6 +4068,135 @@ __global__ __launch_bounds__(256) void ray_surface_kernel(const RaySurfaceArgs* 
 }
 
 // ----------------------------------------------------------------------------------------
+// K5k: direct solar beam (lbl_column_solar_dev; the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// K5c's walks without a source term: a value is only ever attenuated, S <- exp_neg_budget(k_l depth_l rate) S, so there is no
+// Planck term, no wavenumber and no fast / general split.  Two kernels over one body, each carrying NB values per point in
+// registers the way K5c carries its angles:
+//   solar_beam_kernel<NP, NB>     NB beams, rate = slant[s][l], weight = beam_w[s].  Down from S0 at the top; the spectral
+//                                 F_down(0) goes to f0 (Lambertian).  Specular: the surface turns every beam in place,
+//                                 U_s = (1 - e) S_s, and the upward walk follows in the same kernel (K5g's order of walks),
+//                                 so that no beam's S_s[0] has to be kept or formed twice.
+//   solar_diffuse_kernel<NP, NA>  Lambertian: NA angles, rate = 1 / mu_k, weight = W_k.  Up from (1 - e) f0 / w_sum.
+// A beam's operations are the same whatever the other beams of the call are (one exp and one product per layer, its own
+// table row), so its bits do not depend on them; a level's flux is the fma chain of angle_sum over the beams, beam 0 first.
+// Rates, weights and depths are workgroup-uniform and come through scalar loads.  Level sums, slots, partials and the final
+// reduction are K5c's; the beam kernel's partial holds [down 0..L] (Lambertian) or [up 0..L, down 0..L] (specular), the
+// diffuse kernel's [up 0..L].
+template <int NP, int NB, bool DIFFUSE>
+__device__ __forceinline__ void solar_walks(const SolarArgs& A, long long lo0, long long n0, long long lo1, long long n1,
+                                            double* __restrict__ partial, double* acc) {
+#pragma clang fp contract(off)
+    typedef f64v<NP> vec;
+    constexpr int kSlot = 2 * (kMaxLayers + 1);
+    const int L = A.n_layers;
+    const bool specular = !DIFFUSE && A.reflection == 1;
+    const int nv = specular ? 2 * (L + 1) : L + 1;
+    const int down0 = specular ? L + 1 : 0;
+    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
+    __syncthreads();
+    double* my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const long long total = n0 + n1;
+    const long long stride = (long long)gridDim.x * blockDim.x * NP;
+    auto rate = [&](int s, int l) { return DIFFUSE ? A.rmu[s] : A.slant[s][l]; };
+    auto wt = [&](int s) { return DIFFUSE ? A.w[s] : A.beam_w[s]; };
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
+    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
+        const long long q = q0 + (long long)threadIdx.x * NP;
+        const bool active = q < total;
+        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        double S[NB][NP];
+        // sum_s w_s S_s per point (beam 0 first), nan_to_num, summed over the thread's points, the wave, into the wave's slot
+        auto level = [&](int slot, double* spec, double* spec2 = nullptr) {
+            double sum = 0.0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                double f = wt(0) * S[0][p];
+#pragma unroll
+                for (int s = 1; s < NB; ++s) f = fma(wt(s), S[s][p], f);
+                if (spec && active) spec[j + p] = f;
+                if (spec2 && active) spec2[j + p] = f;
+                sum += active ? nan_to_num(f) : 0.0;
+            }
+            sum = wave_sum(sum);
+            if (lane0) my[slot] += sum;
+        };
+        auto layer = [&](int l, vec v) {
+            const double depth = A.depth[l];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double tau = v[p] * depth;
+#pragma unroll
+                for (int s = 0; s < NB; ++s) S[s][p] = exp_neg_budget(tau * rate(s, l)) * S[s][p];
+            }
+        };
+        vec cur;
+        if constexpr (!DIFFUSE) {
+            // downward: S_s[L] = S0; level l after layer l
+            const vec top = load_points<NP>(A.S0, j);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+#pragma unroll
+                for (int s = 0; s < NB; ++s) S[s][p] = top[p];
+            }
+            double* const surface2 = A.down_surface != A.f0 ? A.down_surface : nullptr;
+            level(down0 + L, L == 0 ? A.f0 : nullptr, L == 0 ? surface2 : nullptr);
+            cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+            for (int l = L - 1; l >= 0; --l) {
+                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+                layer(l, cur);
+                level(down0 + l, l == 0 ? A.f0 : nullptr, l == 0 ? surface2 : nullptr);
+                cur = nxt;
+            }
+        }
+        if (DIFFUSE || specular) {
+            // the surface: nothing is emitted, (1 - e) of what came down leaves again
+            vec f0;
+            if constexpr (DIFFUSE) f0 = load_points<NP>(A.f0, j);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+                if constexpr (DIFFUSE) {
+                    const double leaving = ((1.0 - e) * f0[p]) / A.w_sum;
+#pragma unroll
+                    for (int s = 0; s < NB; ++s) S[s][p] = leaving;
+                } else {
+#pragma unroll
+                    for (int s = 0; s < NB; ++s) S[s][p] = (1.0 - e) * S[s][p];
+                }
+            }
+            // upward: level l + 1 after layer l
+            level(0, A.up_surface, L == 0 ? A.up_top : nullptr);
+            cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+            for (int l = 0; l < L; ++l) {
+                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+                layer(l, cur);
+                level(l + 1, l + 1 == L ? A.up_top : nullptr);
+                cur = nxt;
+            }
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += blockDim.x)
+        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+}
+
+template <int NP, int NB>
+__global__ __launch_bounds__(256) void solar_beam_kernel(const SolarArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                         long long lo1, long long n1, double* __restrict__ partial) {
+    __shared__ double acc[4 * 2 * (kMaxLayers + 1)];     // [wave][up levels 0..L, down levels 0..L]
+    solar_walks<NP, NB, false>(*Ap, lo0, n0, lo1, n1, partial, acc);
+}
+
+template <int NP, int NA>
+__global__ __launch_bounds__(256) void solar_diffuse_kernel(const SolarArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                            long long lo1, long long n1, double* __restrict__ partial) {
+    __shared__ double acc[4 * 2 * (kMaxLayers + 1)];
+    solar_walks<NP, NA, true>(*Ap, lo0, n0, lo1, n1, partial, acc);
+}
+
+// ----------------------------------------------------------------------------------------
 // K5i: linear-in-optical-depth Planck source (lbl_column_flux_linear_dev, lbl_ray_radiance_linear_dev; the semantics are in
 // include/pyrad_hip.h)
 // ----------------------------------------------------------------------------------------
@@ -5911,6 +6042,29 @@ void launch_surface_flux(const SurfaceFluxArgs* d_args, int n_layers, int n_angl
         constexpr int NA = decltype(na)::value;
         launch_column_band<4>(surface_flux_kernel<4, NA>, surface_flux_kernel<1, NA>, d_args, 2 * (n_layers + 1), first, count,
                               partial, level_flux, s);
+    });
+}
+
+// K5k: K5c's launch twice over one partial block (stream order keeps the first reduction ahead of the second kernel): the
+// beams' downward walk into the down half of level_flux, then the Lambertian upward walk into the up half; with a specular
+// surface the beam kernel does both walks and fills both halves.
+void launch_solar(const SolarArgs* d_args, int n_layers, int n_beams, int n_angles, int reflection, long long first,
+                  long long count, double* partial, double* level_flux, hipStream_t s) {
+    const int levels = n_layers + 1;
+    with_angles(n_beams, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        if (reflection == 1)
+            launch_column_band<4>(solar_beam_kernel<4, NB>, solar_beam_kernel<1, NB>, d_args, 2 * levels, first, count, partial,
+                                  level_flux, s);
+        else
+            launch_column_band<4>(solar_beam_kernel<4, NB>, solar_beam_kernel<1, NB>, d_args, levels, first, count, partial,
+                                  level_flux + levels, s);
+    });
+    if (reflection == 1) return;
+    with_angles(n_angles, [&](auto na) {
+        constexpr int NA = decltype(na)::value;
+        launch_column_band<4>(solar_diffuse_kernel<4, NA>, solar_diffuse_kernel<1, NA>, d_args, levels, first, count, partial,
+                              level_flux, s);
     });
 }
 

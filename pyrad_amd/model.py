@@ -1492,6 +1492,177 @@ class Fluxes:
             self.up.shape[-1], len(self.mu), self.up[..., -1], self.down[..., 0])
 
 
+# ----------------------------------------------------------------------------------------
+# The direct solar beam (Atmosphere.solarFluxes; beyond the reference)
+# ----------------------------------------------------------------------------------------
+R_SUN = 6.957e8               # m, the nominal solar radius
+AU = 1.495978707e11           # m
+SOLAR_GEOMETRIES = ("plane", "spherical")
+
+
+def solarIrradiance(xAxis, temperature=5772.0, distanceAU=1.0):
+    """The irradiance of a black-body sun on a plane normal to its beam, W m^-2 per cm^-1 at the wavenumbers ``xAxis``:
+    planckWavenumber(x, temperature) * pi * (R_SUN / (AU * distanceAU))**2 (0 at a wavenumber of 0).  Summed over all
+    wavenumbers at 5772 K and 1 AU it is sigma T^4 (R_SUN / AU)^2 = 1361 W m^-2.  ValueError unless temperature and
+    distanceAU are finite and > 0."""
+    try:
+        T, d = float(temperature), float(distanceAU)
+    except (TypeError, ValueError):
+        raise ValueError("solarTemperature and distanceAU: two numbers > 0, not %r and %r" % (temperature, distanceAU))
+    if not (T > 0.0 and math.isfinite(T)):
+        raise ValueError("solarTemperature must be finite and > 0, not %r" % (temperature,))
+    if not (d > 0.0 and math.isfinite(d)):
+        raise ValueError("distanceAU must be finite and > 0, not %r" % (distanceAU,))
+    x = np.asarray(xAxis, dtype=np.float64)
+    return np.where(x > 0.0, planckWavenumber(x, T), 0.0) * pi * (R_SUN / (AU * d)) ** 2
+
+
+def _solar_beams(mu0):
+    """``mu0`` of solarFluxes as two float64 arrays (cosine, weight): a number (weight 1) or a list of up to 8 (mu0, weight)
+    pairs; every cosine in (0, 1], every weight finite and >= 0."""
+    nmax = 8
+    bad = "mu0: a cosine in (0, 1] or a list of up to %d (mu0, weight) pairs, not %r"
+    if isinstance(mu0, (bool, str)):
+        raise ValueError(bad % (nmax, mu0))
+    if isinstance(mu0, (int, float, np.integer, np.floating)):
+        pairs = [(float(mu0), 1.0)]
+    else:
+        try:
+            pairs = [(float(m), float(wt)) for m, wt in mu0]
+        except (TypeError, ValueError):
+            raise ValueError(bad % (nmax, mu0))
+    if not 1 <= len(pairs) <= nmax:
+        raise ValueError("mu0: 1..%d beams, not %d" % (nmax, len(pairs)))
+    mu = np.array([m for m, _ in pairs])
+    weight = np.array([wt for _, wt in pairs])
+    if not np.all((mu > 0.0) & (mu <= 1.0)):                # (a NaN fails both comparisons)
+        raise ValueError("mu0: every cosine must lie in (0, 1]")
+    if not np.all(np.isfinite(weight) & (weight >= 0.0)):
+        raise ValueError("mu0: every weight must be finite and >= 0")
+    return mu, weight
+
+
+def solarSlants(depths, mu0, geometry="plane", planetRadius=6.371e8):
+    """The path length of a solar beam through every layer per unit depth: (L,) for a number ``mu0``, (beams, L) for a list
+    of (mu0, weight) pairs.  ``depths``: the layers' depths bottom to top, cm, each > 0.
+    - "plane": 1 / mu0 in every layer.
+    - "spherical": the straight ray, WITHOUT REFRACTION, that meets the surface at zenith cosine mu0, through the shells of
+      Atmosphere.limbPath around a planet of radius ``planetRadius`` (cm).  With z_l the level heights (z_0 = 0) and
+      q(z) = sqrt(z (2 R + z) + R^2 mu0^2), the distance along the ray from its point nearest the planet's centre,
+          slant_l = (q(z_(l+1)) - q(z_l)) / depth_l
+      evaluated in the factored form (a_(l+1) + a_l) / (q(z_(l+1)) + q(z_l)) with a = R + z, q = sqrt((a - b) (a + b)) and
+      b = R sqrt((1 - mu0) (1 + mu0)), which keeps its digits (no difference of two long distances) and is exactly 1 for
+      mu0 = 1.  Every slant is <= 1 / mu0 and tends to it as the radius grows.
+    Only the path length is spherical: the projection of the beam's irradiance onto the horizontal stays mu0 at every
+    level (solarFluxes' beam weight), as in the plane-parallel case.
+    ValueError for another geometry, a radius that is not finite and > 0, or a depth that is not finite and > 0."""
+    if not isinstance(geometry, str) or geometry not in SOLAR_GEOMETRIES:
+        raise ValueError("geometry: \"plane\" or \"spherical\", not %r" % (geometry,))
+    try:
+        R = float(planetRadius)
+    except (TypeError, ValueError):
+        raise ValueError("planetRadius must be finite and > 0, not %r" % (planetRadius,))
+    if not (R > 0.0 and math.isfinite(R)):
+        raise ValueError("planetRadius must be finite and > 0, not %r" % (planetRadius,))
+    single = isinstance(mu0, (int, float, np.integer, np.floating)) and not isinstance(mu0, bool)
+    mu, _ = _solar_beams(mu0)
+    try:
+        depth = np.asarray([float(d) for d in depths], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("depths: the layers' depths in cm, not %r" % (depths,))
+    if not np.all(np.isfinite(depth) & (depth > 0.0)):
+        raise ValueError("depths: every depth must be finite and > 0")
+    table = np.empty((len(mu), len(depth)))
+    if geometry == "plane":
+        table[:] = (1.0 / mu)[:, None]
+    else:
+        a = R + np.concatenate([[0.0], np.cumsum(depth)])
+        for s, m in enumerate(mu):
+            b = R * math.sqrt((1.0 - m) * (1.0 + m))
+            q = np.sqrt((a - b) * (a + b))
+            table[s] = (a[1:] + a[:-1]) / (q[1:] + q[:-1])
+    return table[0] if single else table
+
+
+def _solar_spectrum(solarSpectrum, solarTemperature, distanceAU, x):
+    """The beam's irradiance at the top on the grid ``x`` as len(x) contiguous float64 values, finite and >= 0: from exactly
+    one of ``solarSpectrum`` (a number, len(x) values, or a pair (wavenumbers, values) interpolated as _surface_emissivity
+    does) and ``solarTemperature`` (solarIrradiance)."""
+    n = len(x)
+    if (solarSpectrum is None) == (solarTemperature is None):
+        raise ValueError("give exactly one of solarSpectrum and solarTemperature")
+    if solarSpectrum is None:
+        S = solarIrradiance(x, solarTemperature, distanceAU)
+    else:
+        bad = "solarSpectrum: a number >= 0, %d values on xAxis or a pair (wavenumbers, values), not %r"
+        if isinstance(solarSpectrum, (bool, str)):
+            raise ValueError(bad % (n, solarSpectrum))
+        table = (isinstance(solarSpectrum, (tuple, list)) and len(solarSpectrum) == 2
+                 and all(np.ndim(v) == 1 for v in solarSpectrum))
+        try:
+            if isinstance(solarSpectrum, (int, float, np.integer, np.floating)):
+                S = np.full(n, float(solarSpectrum))
+            elif table:
+                nu, val = (np.asarray(v, dtype=np.float64) for v in solarSpectrum)
+            else:
+                S = np.asarray(solarSpectrum, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(bad % (n, solarSpectrum))
+        if table:
+            if nu.size < 1 or nu.shape != val.shape or not np.all(np.isfinite(nu)) or np.any(np.diff(nu) <= 0):
+                raise ValueError("solarSpectrum: a table needs as many values as wavenumbers, the wavenumbers finite and increasing")
+            S = np.interp(x, nu, val)
+        elif S.shape != (n,):
+            raise ValueError("solarSpectrum: %d grid points expected, got shape %s" % (n, S.shape))
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if not np.all(np.isfinite(S) & (S >= 0.0)):
+        raise ValueError("solarSpectrum: every value must be finite and >= 0")
+    return S
+
+
+def _solar_source_key(solarSpectrum, solarTemperature, distanceAU):
+    """What names a source that is made from numbers alone - a black body or one value at every point - else None (also
+    for numbers that _solar_spectrum will refuse)"""
+    try:
+        if solarSpectrum is None and solarTemperature is not None:
+            return ("black body", float(solarTemperature), float(distanceAU))
+        if isinstance(solarSpectrum, (int, float, np.integer, np.floating)) and not isinstance(solarSpectrum, bool):
+            return ("constant", float(solarSpectrum)) if solarTemperature is None else None
+    except (TypeError, ValueError):
+        pass
+    return None
+
+
+class SolarFluxes:
+    """What Atmosphere.solarFluxes returns.  ``up``, ``down``, ``net`` (= up - down, Fluxes' sign): W m^-2 at the levels 0
+    (surface) .. L (top), shape (L + 1,) or (n_bands, L + 1); ``heatingRate``: K/day per layer, (L,) or (n_bands, L);
+    ``absorbedSurface`` = down[0] - up[0], what the surface takes up, per band; ``mu0``, ``beamWeight`` (= weight mu0, what
+    multiplies a beam in a level's flux) and ``slant`` (beams, L): the beams used; ``mu``, ``weight``: the diffuse angles
+    of a Lambertian surface; ``upSpectrum`` / ``downSpectrum`` / ``upSurfaceSpectrum``: the spectral upward flux at the top,
+    downward flux at the surface and upward flux at the surface (W m^-2 per cm^-1, n points; 0 outside every band) when
+    asked for, else None."""
+
+    def __init__(self, up, down, heatingRate, mu0, beamWeight, slant, mu, weight, upSpectrum=None, downSpectrum=None,
+                 upSurfaceSpectrum=None):
+        self.up = up
+        self.down = down
+        self.net = up - down
+        self.heatingRate = heatingRate
+        self.absorbedSurface = down[..., 0] - up[..., 0]
+        self.mu0 = mu0
+        self.beamWeight = beamWeight
+        self.slant = slant
+        self.mu = mu
+        self.weight = weight
+        self.upSpectrum = upSpectrum
+        self.downSpectrum = downSpectrum
+        self.upSurfaceSpectrum = upSurfaceSpectrum
+
+    def __repr__(self):
+        return "SolarFluxes(levels=%d, beams=%d, down[top]=%s, down[surface]=%s, up[top]=%s)" % (
+            self.up.shape[-1], len(self.mu0), self.down[..., -1], self.down[..., 0], self.up[..., -1])
+
+
 class Jacobians:
     """What Atmosphere.jacobians returns (a leading band axis on every band value when ``bands`` was given).
     ``olr``: upward flux at the top, W m^-2; ``surfaceTemperature``: dF/dT_s in W m^-2 K^-1, None when a surface spectrum was
@@ -2266,6 +2437,91 @@ class Atmosphere(list):
                       upSpectrum=up_top.download(n) if spectra else None,
                       downSpectrum=down_surface.download(n) if spectra else None,
                       upSurfaceSpectrum=up_surface.download(n) if up_surface is not None else None)
+
+    def solarFluxes(self, solarSpectrum=None, solarTemperature=None, distanceAU=1.0, mu0=1.0, geometry="plane",
+                    planetRadius=6.371e8, emissivity=1.0, reflection="lambertian", angles=3, bands=None, spectra=False):
+        """The direct solar beam through the column and its heating: gas absorption of sunlight, without scattering and
+        without thermal emission (beyond the reference).
+
+        SUPERPOSITION: without scattering the transfer is linear, so the fluxes of a sunlit column are
+        fluxes(...) (thermal, reflected thermal included) plus solarFluxes(...) (solar, reflected solar included), level by
+        level; likewise the net fluxes and the heating rates.
+
+        Layers, levels, grid, bands and band sums as in fluxes().  ``solarSpectrum``: the beam's irradiance S0 at the top on
+        a plane normal to it, W m^-2 per cm^-1, finite and >= 0 - a number, n values on xAxis or a pair (wavenumbers,
+        values) interpolated onto xAxis with np.interp (the end values held); or ``solarTemperature``: a black-body sun,
+        solarIrradiance(xAxis, solarTemperature, distanceAU).  Exactly one of the two.
+        ``mu0``: the cosine of the solar zenith angle in (0, 1], or a list of up to 8 (mu0, weight) pairs - several suns,
+        for example a day's mean; a plain number means weight 1.  ``geometry``: "plane" or "spherical" with
+        ``planetRadius`` in cm, see solarSlants for the path of a beam through a layer; the projection onto the horizontal
+        stays mu0 at every level in both.  At every grid point nu_j, for every beam s:
+            tau_l = k_l(nu_j) depth_l                      k_l = the layer's absorption coefficient (getAbsCoef)
+            down: S_sL = S0[j]                             S_sl = exp(-tau_l slant_sl) S_s(l+1)
+                  F_down_i = sum_s weight_s mu0_s S_si
+        The surface (``emissivity`` e as fluxes() takes it - here 1 - e is its albedo - and ``reflection``) emits nothing:
+            "lambertian": I_0k = (1 - e) F_down_0 / sum_k W_k    I_(l+1)k = exp(-tau_l / mu_k) I_lk    F_up_i = sum_k W_k I_ik
+                          over the diffuse angles (mu_k, W_k) of ``angles`` (see fluxAngles)
+            "specular":   U_s0 = (1 - e) S_s0                    U_s(l+1) = exp(-tau_l slant_sl) U_sl
+                          F_up_i = sum_s weight_s mu0_s U_si       (the mirrored beam leaves along its own slant path)
+        Band fluxes, net = up - down and heatingRates(net, P, T, depth) as in fluxes(); ``spectra``: also F_up at the top,
+        F_down at the surface and F_up at the surface per grid point.  Returns a SolarFluxes.
+        The absorption coefficients come from the machinery transmission() and fluxes() use and stay resident: after either
+        nothing is accumulated again (lbl_column_solar_dev walks them).  A source made from numbers alone (solarTemperature,
+        or one value) stays on the device while those numbers and the grid stay the same.  Everything is validated
+        (ValueError) before the device is touched."""
+        layers, n = self._column_layers()
+        first = layers[0]
+        x = first.xAxis
+        # (a source made from numbers alone stays on the device from call to call: neither formed nor uploaded again)
+        key = _solar_source_key(solarSpectrum, solarTemperature, distanceAU)
+        if key is not None:
+            _solar_spectrum(solarSpectrum, solarTemperature, distanceAU, x[:1])
+            key += (first.rangeMin, first.rangeMax, n)
+        kept = self.__dict__.get("_solar_state")
+        S0 = None
+        if key is None or kept is None or kept.key != key:
+            S0 = _solar_spectrum(solarSpectrum, solarTemperature, distanceAU, x)
+        mu_s, weight_s = _solar_beams(mu0)
+        depth = [L.depth for L in layers]
+        slant = solarSlants(depth, list(zip(mu_s, weight_s)), geometry, planetRadius)
+        beam_weight = weight_s * mu_s
+        emissivity = _surface_emissivity(emissivity, x)
+        refl = _surface_reflection(reflection)
+        mu, weight = fluxAngles(angles)
+        if refl == 0:
+            _weight_sum(weight)
+        band_first, band_count = _flux_bands(first.rangeMin, first.rangeMax, n, bands)
+        res = utils.BASE_RESOLUTION
+        nl, nb = len(layers), len(band_first)
+        ctx = _ctx()
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        sst = _kept_state(self, "_solar_state")
+        sst.reserve(ctx, max(n, nb * 2 * (nl + 1)))
+        if S0 is None and sst.key != key:                   # (the buffers were given up in between)
+            S0 = _solar_spectrum(solarSpectrum, solarTemperature, distanceAU, x)
+        source = sst.buf(ctx, "S0")
+        if S0 is not None:
+            sst.key = None
+            source.upload(S0)
+            sst.key = key
+        level = sst.buf(ctx, "level")
+        up_top = sst.buf(ctx, "up_top") if spectra else None
+        down_surface = sst.buf(ctx, "down_surface") if spectra else None
+        up_surface = sst.buf(ctx, "up_surface") if spectra else None
+        if not isinstance(emissivity, float):
+            emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
+        ctx.column_solar_dev(kbufs, depth, first.rangeMin, first.rangeMax, n, source, beam_weight, slant,
+                             mu if refl == 0 else (), weight if refl == 0 else (), band_first, band_count, level,
+                             emissivity=emissivity, reflection=refl, up_top=up_top, down_surface=down_surface,
+                             up_surface=up_surface)
+        sums = level.download(nb * 2 * (nl + 1)).reshape(nb, 2, nl + 1) * res
+        up, down = sums[:, 0, :], sums[:, 1, :]
+        heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], depth)
+        up, down, heat = _band_values(bands, [up, down, heat])
+        return SolarFluxes(up, down, heat, mu_s, beam_weight, slant, mu, weight,
+                           upSpectrum=up_top.download(n) if spectra else None,
+                           downSpectrum=down_surface.download(n) if spectra else None,
+                           upSurfaceSpectrum=up_surface.download(n) if spectra else None)
 
     def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False,
                   temperature="planck", emissivity=None, reflection="lambertian", topSpectrum=None):
