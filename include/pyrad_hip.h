@@ -666,6 +666,73 @@ int lbl_column_solar_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef
                          lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface,
                          lbl_buffer* up_surface /* may be NULL */);
 
+/* ---- two-stream multiple scattering of the solar beam (beyond the reference; ABI 5, backward compatible) ----------------
+ * pyrad_amd.model.Atmosphere.solarFluxesTwoStream: lbl_column_solar_dev's beams through a column whose layers also scatter -
+ * a delta-two-stream (quadrature) solution per layer and grid point, the layers joined by the adding method, the surface
+ * Lambertian.  Nothing emits.  Column, layer order, levels, bands, nan_to_num and S0 / beam_weight / slant are
+ * lbl_column_solar_dev's, except that every slant must be > 0.  Scatterer c < n_scat has one amount per layer,
+ * scat_amount[c * n_layers + l], and three numbers per grid point, each from scat_X[c][j] or, where scat_X or scat_X[c] is NULL,
+ * from scat_X_all[c]: extinction ext_c (per unit amount), single-scattering albedo ssa_c and asymmetry g_c.
+ * Per point, with f_c = g_c^2 if delta_scaling else 0:
+ *   alpha_c = ext_c (1 - ssa_c)      sigma_c = (ext_c ssa_c) (1 - f_c)      eta_c = (ext_c ssa_c) (g_c - f_c)
+ * Layer l (sums in scatterer order, every operation rounded on its own):
+ *   ta = k_l depth_l + sum_c amount_cl alpha_c     ts = sum_c amount_cl sigma_c     tsg = sum_c amount_cl eta_c     t = ta + ts
+ *   t == 0: R = 0, T = 1, Td_s = 1, Rb_s = Tb_s = 0.  Otherwise, with D = sqrt(3):
+ *   a = ta / t    b = (t - tsg) / t    w = ts / t    g = tsg / ts (0 when ts == 0)
+ *   g1 = (D b + D a) / 2    g2 = (D b - D a) / 2    lam = sqrt((D a) (D b))
+ *   diffuse:  E = exp(-lam t)    Gam = g2 / (g1 + lam)    oG = (D a + lam) (D b + lam) / (g1 + lam)^2    oE = -expm1(-2 lam t)
+ *             den = oG + Gam^2 oE    R = Gam oE / den    T = E oG / den
+ *             den == 0 (exactly conservative): R = g1 t / (1 + g1 t), T = 1 / (1 + g1 t)
+ *             Ab = (-expm1(-lam t) ((D a + lam) / (g1 + lam))) (1 - Gam E) / den, 0 when den == 0: the layer's diffuse absorptance
+ *             1 - R - T, without cancellation
+ *   beam s, per unit flux through the horizontal at the layer's top:
+ *             m = 1 / slant_sl    Td = exp(-t slant_sl)    g3 = (1 - D g m) / 2    g4 = 1 - g3
+ *             a2 = g1 g3 + g2 g4    Tdm = Td
+ *             if |1 - lam m| < 1e-6 (the particular solution's pole): m = (1 - 1e-6) / lam and Tdm = exp(-t / m) from here on
+ *             Cp = w (g3 - a2 m) / ((1 - lam m) (1 + lam m))     u = w (1 + (D a) (g4 - g3) m) / ((1 - lam m) (1 + lam m))
+ *             Y = (Cp T) (1 - Tdm)     Rb = Y + (R u + Cp Ab)     Tb = (u (T - Tdm) + (Cp Tdm) Ab) - Y
+ *             This is the particular solution Cp, Cm = Cp - u (= -w (g4 + a1 m) / ..., a1 = g1 g4 + g2 g3) with the homogeneous
+ *             one subtracted, Rb = Cp - R Cm - T Cp Tdm, Tb = Cm Tdm - T Cm - R Cp Tdm, regrouped with 1 - R - T = Ab so that
+ *             without absorption (Ab = 0, u = 1) Y cancels and Rb + Tb + Td = R + T to rounding.
+ * Column: S_s[L] = S0[j], S_s[l] = Td_sl S_s[l+1], Fd_s[i] = beam_weight[s] S_s[i]; direct_i = sum_s beam_weight[s] S_s[i]
+ * (beam 0 first, then fma in order, as lbl_column_solar_dev sums); P_l = sum_s Rb_sl Fd_s[l+1], Q_l = sum_s Tb_sl Fd_s[l+1]
+ * likewise.  The layer relations
+ *   up_(l+1) = T_l up_l + R_l dn_(l+1) + P_l      dn_l = T_l dn_(l+1) + R_l up_l + Q_l      dn_L = 0
+ *   up_0 = (1 - e) (dn_0 + direct_0)              e = emissivity[j] or emissivity_all
+ * are solved by adding from the top, dn_i = Rs_i up_i + Ds_i with Rs_L = Ds_L = 0 and, c = 1 - R_l Rs_(l+1):
+ *   U1 = T_l / c    U0 = (R_l Ds_(l+1) + P_l) / c    Rs_l = R_l + (T_l U1) Rs_(l+1)    Ds_l = Q_l + T_l ((Ds_(l+1) + Rs_(l+1) P_l) / c)
+ * then from the surface: up_0 = ((1 - e) (Ds_0 + direct_0)) / (1 - (1 - e) Rs_0), up_(l+1) = U1 up_l + U0, dn_i = Rs_i up_i + Ds_i.
+ * level_flux is n_bands x 3 x (n_layers + 1): [band][up, diffuse down, direct][level], band sums of nan_to_num.  up_top,
+ * down_surface (diffuse), direct_surface and up_surface (may be NULL; n points each) receive the spectral values at every
+ * point of every band, 0 elsewhere.  A point where some layer's t is not finite has NaN in all four and counts as 0 in
+ * every band sum; every other point keeps its bits.  exp is the flux kernels'; no contraction beside the fma chains named;
+ * sums run in a fixed order without atomics.
+ * The first of two kernels writes 5 numbers per level and point into `workspace` (laid out [number][level][point]), the
+ * second reads them.  The call works through each band in passes of as many points as the workspace holds: a whole number
+ * of tiles of 256 points, at least one; lbl_column_twostream_workspace gives the doubles that hold `points` points in one
+ * pass.  The partial sums are laid out by tile of the band, not of the pass: the bits do not depend on the workspace's size.
+ * At most lbl_limit("scatterers") = 4 scatterers, lbl_limit("flux_angles") = 8 beams; the other limits are
+ * lbl_column_solar_dev's.
+ * LBL_ERR_BAD_ARG, all before anything is enqueued: what lbl_column_solar_dev refuses of these arguments (level_flux is
+ * n_bands x 3 x (n_layers + 1)); n_scat outside 0 .. 4 or scat_amount NULL with n_scat and n_layers > 0; an amount that is
+ * negative or not finite; a scat_X[c] shorter than n; with no buffer, an ext_all that is negative or not finite, an ssa_all
+ * outside [0, 1] or an asym_all outside (-1, 1); a slant that is not finite and > 0; delta_scaling not 0 or 1; a
+ * workspace of fewer than lbl_column_twostream_workspace(n_layers, 1) doubles.  Stream-ordered; nothing is synchronised. */
+int lbl_column_twostream_workspace(int n_layers, int64_t points, int64_t* doubles);
+int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                             double range_min, double range_max, int64_t n,
+                             lbl_buffer* S0, int n_beams, const double* beam_weight,
+                             const double* slant /* n_beams x n_layers */,
+                             int n_scat, const double* scat_amount /* n_scat x n_layers */,
+                             lbl_buffer* const* scat_ext /* may be NULL, and every entry */, const double* scat_ext_all,
+                             lbl_buffer* const* scat_ssa, const double* scat_ssa_all,
+                             lbl_buffer* const* scat_asym, const double* scat_asym_all, int delta_scaling,
+                             int n_bands, const int64_t* band_first, const int64_t* band_count,
+                             lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                             lbl_buffer* workspace, lbl_buffer* level_flux, lbl_buffer* up_top,
+                             lbl_buffer* down_surface, lbl_buffer* direct_surface,
+                             lbl_buffer* up_surface /* may be NULL */);
+
 /* ---- ray-path Jacobians (beyond the reference; ABI 5, backward compatible) --------------------------------------------
  * pyrad_amd.model.Atmosphere.pathJacobians: the weighting functions of the radiance lbl_ray_radiance_dev computes - its
  * analytic derivatives to every crossed layer's optical depth and (Planck) temperature, to the source temperature and to any

@@ -127,6 +127,11 @@ SIGNATURES = {
     "lbl_column_solar_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, _P, C.c_int, _D, _D,
                                        C.c_int, _D, _D, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, C.c_double,
                                        C.c_int, _P, _P, _P, _P]),
+    "lbl_column_twostream_workspace": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int64)]),
+    "lbl_column_twostream_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, _P, C.c_int, _D,
+                                           _D, C.c_int, _D, C.POINTER(_P), _D, C.POINTER(_P), _D, C.POINTER(_P), _D, C.c_int,
+                                           C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, C.c_double, _P, _P, _P, _P,
+                                           _P, _P]),
     "lbl_ray_jacobian_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lbl_ray_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
@@ -694,6 +699,42 @@ class Context:
             _arr(C.c_double, [float(w) for w in weight]), len(band_first), _arr(C.c_int64, [int(f) for f in band_first]),
             _arr(C.c_int64, [int(c) for c in band_count]), *self._emissivity_args(emissivity), int(reflection),
             _hb(level_flux), _hb(up_top), _hb(down_surface), _hb(up_surface)))
+
+    def column_twostream_workspace(self, n_layers, points):
+        """The doubles of a workspace with which column_twostream_dev does ``points`` points in one pass
+        (lbl_column_twostream_workspace: whole tiles, at least one)."""
+        out = C.c_int64()
+        self.check(self.lib.lbl_column_twostream_workspace(int(n_layers), int(points), C.byref(out)))
+        return out.value
+
+    def column_twostream_dev(self, abs_coef, depth, range_min, range_max, n, S0, beam_weight, slant, scat_amount, scat_ext,
+                             scat_ssa, scat_asym, delta_scaling, band_first, band_count, workspace, level_flux, emissivity=1.0,
+                             up_top=None, down_surface=None, direct_surface=None, up_surface=None):
+        """Two-stream multiple scattering of the solar beams (lbl_column_twostream_dev): ``S0``, ``beam_weight`` and ``slant``
+        as column_solar_dev takes them (every slant > 0); ``scat_amount`` scatterers x layers; ``scat_ext`` / ``scat_ssa`` /
+        ``scat_asym`` one entry per scatterer, a Buffer of n points or a number; ``workspace`` a Buffer of at least
+        column_twostream_workspace(layers, 1) doubles.  ``level_flux`` receives len(band_first) x 3 x (layers + 1) band sums
+        [band][up, diffuse down, direct][level]; ``up_top`` / ``down_surface`` (diffuse) / ``direct_surface`` / ``up_surface``
+        (optional, n points) the spectral fluxes."""
+        nl, ns, nc = len(abs_coef), len(beam_weight), len(scat_ext)
+        slant = _as_f64(slant).reshape(-1)
+        if len(slant) != ns * nl:
+            raise ValueError("column_twostream_dev: one slant per beam and layer")
+        amount = _as_f64(scat_amount).reshape(-1)
+        if len(amount) != nc * nl or len(scat_ssa) != nc or len(scat_asym) != nc:
+            raise ValueError("column_twostream_dev: one amount per scatterer and layer, one of each number per scatterer")
+
+        def numbers(vals):
+            return (_arr(_P, [v.h if isinstance(v, Buffer) else None for v in vals]),
+                    _arr(C.c_double, [0.0 if isinstance(v, Buffer) else float(v) for v in vals]))
+        self.check(self.lib.lbl_column_twostream_dev(
+            self.h, nl, _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(d) for d in depth]), float(range_min),
+            float(range_max), int(n), _hb(S0), ns, _arr(C.c_double, [float(w) for w in beam_weight]),
+            _arr(C.c_double, [float(v) for v in slant]), nc, _arr(C.c_double, [float(v) for v in amount]),
+            *numbers(scat_ext), *numbers(scat_ssa), *numbers(scat_asym), int(delta_scaling), len(band_first),
+            _arr(C.c_int64, [int(f) for f in band_first]), _arr(C.c_int64, [int(c) for c in band_count]),
+            *self._emissivity_args(emissivity), _hb(workspace), _hb(level_flux), _hb(up_top), _hb(down_surface),
+            _hb(direct_surface), _hb(up_surface)))
 
     def column_jacobian_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                             jac, I_surface=None, surface_T=0.0, term_abs_coef=(), term_layer=(), ln_tau_spectra=None,

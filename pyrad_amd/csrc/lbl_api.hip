@@ -393,6 +393,7 @@ extern "C" int lbl_limit(const char* name, int64_t* value) {
     else if (!strcmp(name, "jobs_per_batch")) *value = LBL_MAX_JOBS;
     else if (!strcmp(name, "flux_angles")) *value = kMaxFluxAngles;           // angles of lbl_column_flux_dev
     else if (!strcmp(name, "flux_bands")) *value = kMaxFluxBands;             // bands of lbl_column_flux_dev
+    else if (!strcmp(name, "scatterers")) *value = kMaxScatterers;            // scatterers of lbl_column_twostream_dev
     else if (!strcmp(name, "jacobian_terms")) *value = kMaxJacobianTerms;     // molecule terms of lbl_column_jacobian_dev
     else if (!strcmp(name, "ils_rows")) *value = kMaxIlsRows;                  // rows of lbl_ils_convolve_dev
     else if (!strcmp(name, "ils_channels")) *value = kMaxIlsChannels;          // ... its channels

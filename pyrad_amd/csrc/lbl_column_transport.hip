@@ -2,9 +2,9 @@
 // sequences of lbl_column_flux_dev, lbl_column_jacobian_dev, lbl_ray_radiance_dev and lbl_ray_jacobian_dev, and of their
 // variants over a reflecting surface, lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev, lbl_column_jacobian_surface_dev
 // and lbl_ray_jacobian_surface_dev, of the linear-source variants lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev, and
-// of their Jacobians lbl_column_jacobian_linear_dev and lbl_ray_jacobian_linear_dev, and of the direct solar beam,
-// lbl_column_solar_dev.
-// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j and K5k of lbl_kernels.hip; the context's internals
+// of their Jacobians lbl_column_jacobian_linear_dev and lbl_ray_jacobian_linear_dev, of the direct solar beam,
+// lbl_column_solar_dev, and of its two-stream multiple scattering, lbl_column_twostream_dev.
+// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j, K5k and K5l of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -343,6 +343,140 @@ extern "C" int lbl_column_solar_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
     for (int b = 0; b < n_bands; ++b)
         launch_solar((const SolarArgs*)d_args, n_layers, n_beams, n_angles, reflection, band_first[b], band_count[b], partial,
                      buffer_data(level_flux) + (size_t)b * nv, s);
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+} LBL_GUARD_END(ctx)
+
+// K5l: the doubles of a workspace that holds `points` points (rounded up to whole tiles, at least one) in one pass
+extern "C" int lbl_column_twostream_workspace(int n_layers, int64_t points, int64_t* doubles) {
+    if (!doubles || n_layers < 0 || n_layers > kMaxLayers || points < 0 || points > (int64_t)1 << 40) return LBL_ERR_BAD_ARG;
+    const int64_t tiles = std::max<int64_t>((points + kTwoStreamTile - 1) / kTwoStreamTile, 1);
+    *doubles = (int64_t)kTwoStreamQuantities * (n_layers + 1) * tiles * kTwoStreamTile;
+    return LBL_OK;
+}
+
+// one of the three spectral numbers of the scatterers: a buffer of n points per scatterer, or the number beside it within
+// [lo, hi] (the ends excluded where `open`)
+static int check_scat_numbers(lbl_ctx* ctx, const char* what, int n_scat, int64_t n, lbl_buffer* const* bufs, const double* all,
+                              double lo, double hi, bool open, const double** ptr, double* value) {
+    for (int c = 0; c < n_scat; ++c) {
+        lbl_buffer* b = bufs ? bufs[c] : nullptr;
+        int rc;
+        if ((rc = ctx_check_buffer(ctx, b, n, what, false))) return rc;
+        if (b) { ptr[c] = buffer_data(b); continue; }
+        if (!all) return column_fail(ctx, LBL_ERR_BAD_ARG, "scatterer %d: %s needs a buffer or a number", c, what);
+        const double v = all[c];
+        if (!(open ? v > lo && v < hi : v >= lo && v <= hi) || !std::isfinite(v))
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "scatterer %d: %s outside its range", c, what);
+        value[c] = v;
+    }
+    return LBL_OK;
+}
+
+// K5l: lbl_column_solar_dev's checks in its order, the scatterers' and the workspace's behind them; then every band in passes
+// of as many points as the workspace holds, the band's partial slots zeroed first and reduced after its last pass.
+extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                                        double range_min, double range_max, int64_t n, lbl_buffer* S0, int n_beams,
+                                        const double* beam_weight, const double* slant, int n_scat, const double* scat_amount,
+                                        lbl_buffer* const* scat_ext, const double* scat_ext_all, lbl_buffer* const* scat_ssa,
+                                        const double* scat_ssa_all, lbl_buffer* const* scat_asym, const double* scat_asym_all,
+                                        int delta_scaling, int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                        lbl_buffer* emissivity, double emissivity_all, lbl_buffer* workspace,
+                                        lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface,
+                                        lbl_buffer* direct_surface, lbl_buffer* up_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    (void)range_min; (void)range_max;       // (the grid of the other column calls: nothing here depends on a wavenumber)
+    std::vector<char> blk(sizeof(TwoStreamArgs), 0);
+    TwoStreamArgs* a = (TwoStreamArgs*)blk.data();
+    if (n_layers < 0 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
+    if (n < 0) return column_fail(ctx, LBL_ERR_BAD_ARG, "negative n");
+    if (n_layers > 0 && (!abs_coef || !depth || !slant)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
+    if (ctx_sweep_ieee(ctx))
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", "two-stream fluxes");
+    if (n_beams < 1 || n_beams > kMaxFluxAngles) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d beams", kMaxFluxAngles);
+    if (!beam_weight) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL beam set");
+    if (n_scat < 0 || n_scat > kMaxScatterers) return column_fail(ctx, LBL_ERR_BAD_ARG, "0..%d scatterers", kMaxScatterers);
+    if (n_scat > 0 && n_layers > 0 && !scat_amount) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL scatterer amounts");
+    if (delta_scaling != 0 && delta_scaling != 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "delta_scaling must be 0 or 1");
+    if (n_bands < 1 || n_bands > kMaxFluxBands) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d bands", kMaxFluxBands);
+    if (!band_first || !band_count) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL band list");
+    const int nv = 3 * (n_layers + 1);
+    int rc;
+    if ((rc = ctx_check_buffer(ctx, S0, n, "S0", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, direct_surface, n, "direct_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    int64_t max_count = 0;
+    for (int b = 0; b < n_bands; ++b) {
+        if (band_first[b] < 0 || band_count[b] < 1 || band_count[b] > n - band_first[b])
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "band %d: empty or outside [0, n)", b);
+        max_count = std::max(max_count, band_count[b]);
+    }
+    for (int l = 0; l < n_layers; ++l) {
+        if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
+        if (!(depth[l] >= 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: depth must be >= 0", l);
+        a->abs_coef[l] = buffer_data(abs_coef[l]);
+        a->depth[l] = depth[l];
+    }
+    for (int s = 0; s < n_beams; ++s) {
+        if (!std::isfinite(beam_weight[s])) return column_fail(ctx, LBL_ERR_BAD_ARG, "beam %d: weight must be finite", s);
+        a->beam_w[s] = beam_weight[s];
+        for (int l = 0; l < n_layers; ++l) {
+            const double v = slant[(size_t)s * n_layers + l];
+            if (!(v > 0) || !std::isfinite(v))
+                return column_fail(ctx, LBL_ERR_BAD_ARG, "beam %d, layer %d: slant must be finite and > 0", s, l);
+            a->slant[s][l] = v;
+            a->m[s][l] = 1.0 / v;
+        }
+    }
+    for (int c = 0; c < n_scat; ++c)
+        for (int l = 0; l < n_layers; ++l) {
+            const double v = scat_amount[(size_t)c * n_layers + l];
+            if (!(v >= 0) || !std::isfinite(v))
+                return column_fail(ctx, LBL_ERR_BAD_ARG, "scatterer %d, layer %d: amount must be finite and >= 0", c, l);
+            a->amount[c][l] = v;
+        }
+    if ((rc = check_scat_numbers(ctx, "extinction", n_scat, n, scat_ext, scat_ext_all, 0.0, HUGE_VAL, false, a->ext, a->ext_all))) return rc;
+    if ((rc = check_scat_numbers(ctx, "single-scattering albedo", n_scat, n, scat_ssa, scat_ssa_all, 0.0, 1.0, false, a->ssa, a->ssa_all))) return rc;
+    if ((rc = check_scat_numbers(ctx, "asymmetry", n_scat, n, scat_asym, scat_asym_all, -1.0, 1.0, true, a->asym, a->asym_all))) return rc;
+    if ((rc = ctx_check_buffer(ctx, workspace, 0, "workspace", true))) return rc;
+    int64_t ws_len = 0, tile_doubles = 0;
+    lbl_buffer_size(workspace, &ws_len);
+    lbl_column_twostream_workspace(n_layers, 1, &tile_doubles);
+    if (ws_len < tile_doubles)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "workspace: at least %lld doubles (one tile of %d points)", (long long)tile_doubles, kTwoStreamTile);
+    const int64_t ws_points = ws_len / tile_doubles * kTwoStreamTile;
+    a->S0 = buffer_data(S0);
+    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a->emissivity_all = emissivity_all;
+    a->workspace = buffer_data(workspace);
+    a->ws_points = ws_points;
+    a->up_top = up_top ? buffer_data(up_top) : nullptr;
+    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
+    a->direct_surface = direct_surface ? buffer_data(direct_surface) : nullptr;
+    a->up_surface = up_surface ? buffer_data(up_surface) : nullptr;
+    a->n_layers = n_layers; a->delta_scaling = delta_scaling;
+
+    void* partial = nullptr;
+    if ((rc = ctx_reduction_scratch(ctx, (size_t)twostream_partials(max_count) * nv * sizeof(double), &partial))) return rc;
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, a, sizeof(TwoStreamArgs), &d_args))) return rc;
+    const hipStream_t s = ctx_stream(ctx);
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    // (points outside every band keep 0 in the spectra)
+    for (double* p : {a->up_top, a->down_surface, a->direct_surface, a->up_surface})
+        if (p && n > 0) COLUMN_HIP_TRY(ctx, hipMemsetAsync(p, 0, (size_t)n * sizeof(double), s));
+    for (int b = 0; b < n_bands; ++b) {
+        const int slots = twostream_partials(band_count[b]);
+        COLUMN_HIP_TRY(ctx, hipMemsetAsync(partial, 0, (size_t)slots * nv * sizeof(double), s));
+        for (int64_t done = 0; done < band_count[b]; done += ws_points)
+            launch_twostream_pass((const TwoStreamArgs*)d_args, n_beams, band_first[b], band_first[b] + done,
+                                  std::min<int64_t>(ws_points, band_count[b] - done), slots, (double*)partial, s);
+        launch_twostream_final(n_layers, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
+    }
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
 } LBL_GUARD_END(ctx)

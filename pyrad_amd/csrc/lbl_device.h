@@ -358,6 +358,46 @@ struct SolarArgs {
 void launch_solar(const SolarArgs* d_args, int n_layers, int n_beams, int n_angles, int reflection, long long first,
                   long long count, double* partial, double* level_flux, hipStream_t s);
 
+// Two-stream multiple scattering for collimated beams (K5l, lbl_column_transport.hip: lbl_column_twostream_dev): a
+// delta-two-stream layer solution per grid point, the layers joined by adding from the top.  Two kernels: the first walks
+// down from the top with the direct beams at hand and writes five numbers per level and point into the caller's workspace,
+// the second walks up from the surface through those numbers alone and forms every sum.  One point per thread; a tile is the
+// kTwoStreamTile points of one workgroup.
+constexpr int kMaxScatterers = 4;
+constexpr int kTwoStreamTile = 256;
+constexpr int kTwoStreamQuantities = 5;    // workspace[q][level][point]: R*, D*, U1, U0 (levels 1 .. L), direct flux
+struct TwoStreamArgs {
+    const double* abs_coef[kMaxLayers];
+    double depth[kMaxLayers];
+    double slant[kMaxFluxAngles][kMaxLayers];   // beam s, layer l: path length through the layer per unit depth, > 0
+    double m[kMaxFluxAngles][kMaxLayers];       // 1 / slant, from the host
+    double amount[kMaxScatterers][kMaxLayers];  // scatterer c, layer l; 0 for c >= n_scat
+    double beam_w[kMaxFluxAngles];
+    const double* ext[kMaxScatterers];          // n points each, or nullptr: the number beside it (0 for c >= n_scat)
+    const double* ssa[kMaxScatterers];
+    const double* asym[kMaxScatterers];
+    double ext_all[kMaxScatterers], ssa_all[kMaxScatterers], asym_all[kMaxScatterers];
+    const double* S0;                   // the beams' irradiance at the top, n points
+    const double* emissivity;           // n points, or nullptr: emissivity_all
+    double emissivity_all;
+    double* workspace;                  // kTwoStreamQuantities x (n_layers + 1) x ws_points
+    long long ws_points;                // points of one pass: a whole number of tiles
+    double* up_top;                     // optional spectra
+    double* down_surface;
+    double* direct_surface;
+    double* up_surface;
+    int32_t n_layers, delta_scaling;
+};
+// partial-sum slots of a band of `count` points: one per tile up to kFluxMaxBlocks, tile t adds into slot t % slots
+int twostream_partials(long long count);
+// one pass over the points [first, first + count) of the band that starts at band_first: first - band_first is a multiple of
+// the tile and count <= ws_points; the second kernel adds the pass's tiles into their slots of `partial` (zeroed by the
+// caller before the band's first pass)
+void launch_twostream_pass(const TwoStreamArgs* d_args, int n_beams, long long band_first, long long first, long long count,
+                           int slots, double* partial, hipStream_t s);
+// the fixed-order reduction of a band's slots into level_flux[0 .. 3 (n_layers + 1))
+void launch_twostream_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s);
+
 // Ray-path Jacobians (K5f, lbl_column_transport.hip: lbl_ray_jacobian_dev): K5e's walk, then the segments last to first
 // with K5d's transmittance-and-emission recurrence, one output row per ray, kind and crossed layer.  RayArgs' block with
 // more tables behind it; `radiance` may be nullptr here and `transmittance` is not used.  A ray's rows start at row_first[r]:

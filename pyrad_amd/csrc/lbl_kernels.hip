@@ -31,6 +31,8 @@
 //                              observeLinear(); beyond the reference)
 //   K5k solar_beam_kernel, solar_diffuse_kernel   K5c's walks without emission: collimated beams attenuated along their slant
 //                              paths, reflected by the surface (Atmosphere.solarFluxes; beyond the reference)
+//   K5l twostream_down_kernel, twostream_up_kernel   the beams through scattering layers: a delta-two-stream solution per
+//                              layer, joined by adding through a workspace (Atmosphere.solarFluxesTwoStream; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -4197,6 +4199,182 @@ __global__ __launch_bounds__(256) void solar_diffuse_kernel(const SolarArgs* __r
 }
 
 // ----------------------------------------------------------------------------------------
+// K5l: two-stream multiple scattering of the beams (lbl_column_twostream_dev; the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// A scattering layer couples the levels both ways, so one walk does not do: the column is solved by adding, in two kernels.
+//   twostream_down_kernel<NB>  top to bottom, where the direct beams are at hand: per layer the two-stream solution (R, T and
+//                              per beam Td, Rb, Tb), the beams' sources P and Q, and the composition of the stack above the
+//                              level: dn_i = Rs_i up_i + Ds_i.  It writes Rs, Ds, the two numbers U1, U0 of the upward step
+//                              up_(l+1) = U1 up_l + U0, and the direct flux, per level, into the workspace.
+//   twostream_up_kernel        bottom to top through those five numbers alone (no coefficient, no beam and no scatterer is
+//                              read again, so it has one instantiation): the surface, then up and dn per level, the spectra
+//                              and every level sum.
+// Up to 129 levels of five numbers cannot live in registers, hence the workspace, [number][level][point of the pass]: a
+// wave's accesses are 512 contiguous bytes.  One point per thread: a point carries 12 scatterer numbers and NB beam values
+// besides the layer's temporaries, and four points would spill.  The scatterers are always kMaxScatterers: those beyond n_scat
+// have amount, extinction and albedo 0 from the host and add exact zeros.  Slants, 1 / slant, amounts, depths and beam weights
+// are workgroup-uniform and come through scalar loads.
+// Sums (second kernel): nan_to_num per point, wave_sum, the four waves added in a fixed order, and the tile's value added to
+// slot (tile of the band) % slots of the partials by the one workgroup that owns the slot, tiles ascending; the passes of a
+// band follow each other in stream order, so a slot's additions are the same whatever the pass size; column_flux_final_kernel
+// finishes.  No float atomics.
+template <int NB>
+__global__ __launch_bounds__(256) void twostream_down_kernel(const TwoStreamArgs* __restrict__ Ap, long long first,
+                                                             long long count) {
+#pragma clang fp contract(off)
+    const TwoStreamArgs& A = *Ap;
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= count) return;
+    const long long j = first + q;
+    const int L = A.n_layers;
+    const long long row = A.ws_points;
+    double* const W = A.workspace + q;
+    auto ws = [&](int v, int i) -> double& { return W[((long long)v * (L + 1) + i) * row]; };
+    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+    double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
+#pragma unroll
+    for (int c = 0; c < kMaxScatterers; ++c) {
+        const double ext = A.ext[c] ? load_global_f64(A.ext[c], j) : A.ext_all[c];
+        const double ssa = A.ssa[c] ? load_global_f64(A.ssa[c], j) : A.ssa_all[c];
+        const double gc = A.asym[c] ? load_global_f64(A.asym[c], j) : A.asym_all[c];
+        const double f = A.delta_scaling ? gc * gc : 0.0;
+        al[c] = ext * (1.0 - ssa);
+        si[c] = (ext * ssa) * (1.0 - f);
+        et[c] = (ext * ssa) * (gc - f);
+    }
+    double S[NB];
+    const double top = load_global_f64(A.S0, j);
+#pragma unroll
+    for (int s = 0; s < NB; ++s) S[s] = top;
+    auto direct = [&]() {
+        double f = A.beam_w[0] * S[0];
+#pragma unroll
+        for (int s = 1; s < NB; ++s) f = fma(A.beam_w[s], S[s], f);
+        return f;
+    };
+    double Rs = 0.0, Ds = 0.0;
+    bool bad = false;
+    ws(0, L) = Rs; ws(1, L) = Ds; ws(4, L) = direct();
+    double k = L > 0 ? load_global_f64(A.abs_coef[L - 1], j) : 0.0;
+    for (int l = L - 1; l >= 0; --l) {
+        const double k_next = l > 0 ? load_global_f64(A.abs_coef[l - 1], j) : k;
+        double ta = k * A.depth[l], ts = 0.0, tsg = 0.0;
+#pragma unroll
+        for (int c = 0; c < kMaxScatterers; ++c) {
+            const double am = A.amount[c][l];
+            ta = ta + am * al[c];
+            ts = ts + am * si[c];
+            tsg = tsg + am * et[c];
+        }
+        const double t = ta + ts;
+        bad = bad || !isfinite(t);
+        const bool empty = t == 0.0;
+        const double a = ta / t, b = (t - tsg) / t, w = ts / t, g = ts == 0.0 ? 0.0 : tsg / ts;
+        const double Da = D * a, Db = D * b;
+        const double g1 = 0.5 * (Db + Da), g2 = 0.5 * (Db - Da);
+        const double lam = sqrt(Da * Db);
+        const double lt = lam * t;
+        const double E = exp_neg_budget(lt);
+        const double g1l = g1 + lam;
+        const double Gam = g2 / g1l;
+        const double oG = ((Da + lam) * (Db + lam)) / (g1l * g1l);
+        const double oE = -expm1(-2.0 * lt);
+        const double den = oG + (Gam * Gam) * oE;
+        const double g1t = g1 * t;
+        double R = den == 0.0 ? g1t / (1.0 + g1t) : (Gam * oE) / den;
+        double T = den == 0.0 ? 1.0 / (1.0 + g1t) : (E * oG) / den;
+        if (empty) { R = 0.0; T = 1.0; }
+        const double Ab = den == 0.0 ? 0.0 : ((-expm1(-lt) * ((Da + lam) / g1l)) * (1.0 - Gam * E)) / den;
+        double P = 0.0, Q = 0.0;
+#pragma unroll
+        for (int s = 0; s < NB; ++s) {
+            const double Td = exp_neg_budget(t * A.slant[s][l]);       // (exactly 1 at t = 0)
+            double m = A.m[s][l];
+            const double g3 = 0.5 * (1.0 - (D * g) * m), g4 = 1.0 - g3;
+            const double a2 = g1 * g3 + g2 * g4;
+            double Tdm = Td;
+            if (fabs(1.0 - lam * m) < 1e-6) {
+                m = (1.0 - 1e-6) / lam;
+                Tdm = exp_neg_budget(t / m);
+            }
+            const double pole = (1.0 - lam * m) * (1.0 + lam * m);
+            const double Cp = (w * (g3 - a2 * m)) / pole;
+            const double u = (w * (1.0 + (Da * (g4 - g3)) * m)) / pole;
+            const double Y = (Cp * T) * (1.0 - Tdm);
+            const double Rb = empty ? 0.0 : Y + (R * u + Cp * Ab);
+            const double Tb = empty ? 0.0 : (u * (T - Tdm) + (Cp * Tdm) * Ab) - Y;
+            const double Fd = A.beam_w[s] * S[s];
+            P = s == 0 ? Rb * Fd : fma(Rb, Fd, P);
+            Q = s == 0 ? Tb * Fd : fma(Tb, Fd, Q);
+            S[s] = Td * S[s];
+        }
+        const double c = 1.0 - R * Rs;
+        const double U1 = T / c;
+        const double U0 = (R * Ds + P) / c;
+        const double Dn = Q + T * ((Ds + Rs * P) / c);
+        Rs = R + (T * U1) * Rs;
+        Ds = Dn;
+        if (bad) Rs = Ds = __builtin_nan("");
+        ws(2, l + 1) = U1; ws(3, l + 1) = U0;
+        ws(0, l) = Rs; ws(1, l) = Ds; ws(4, l) = direct();
+        k = k_next;
+    }
+}
+
+__global__ __launch_bounds__(256) void twostream_up_kernel(const TwoStreamArgs* __restrict__ Ap, long long tile0, long long first,
+                                                           long long count, int slots, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    constexpr int kSlot = 3 * (kMaxLayers + 1);
+    __shared__ double acc[4 * kSlot];                // [wave][up levels 0..L, diffuse down levels 0..L, direct levels 0..L]
+    const TwoStreamArgs& A = *Ap;
+    const int L = A.n_layers;
+    const int levels = L + 1, nv = 3 * levels;
+    const long long row = A.ws_points;
+    double* const my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions)
+    for (long long tile = blockIdx.x; tile < tiles; tile += slots) {
+        const long long q = tile * kTwoStreamTile + threadIdx.x;
+        const bool active = q < count;
+        const long long j = first + q;
+        const double* const W = A.workspace + q;
+        auto ws = [&](int v, int i) { return active ? W[((long long)v * levels + i) * row] : 0.0; };
+        double Rs = ws(0, 0), Ds = ws(1, 0), F = ws(4, 0);
+        const bool bad = isnan(Rs) || isnan(Ds);
+        const double nan = __builtin_nan("");
+        const double e = !active ? 1.0 : A.emissivity ? A.emissivity[j] : A.emissivity_all;
+        const double albedo = 1.0 - e;
+        double up = (albedo * (Ds + F)) / (1.0 - albedo * Rs);
+        for (int i = 0; i <= L; ++i) {
+            if (i > 0) {
+                up = ws(2, i) * up + ws(3, i);
+                Rs = ws(0, i); Ds = ws(1, i); F = ws(4, i);
+            }
+            double dn = Rs * up + Ds;
+            if (bad) up = dn = F = nan;
+            if (active) {
+                if (i == 0) {
+                    if (A.up_surface) A.up_surface[j] = up;
+                    if (A.down_surface) A.down_surface[j] = dn;
+                    if (A.direct_surface) A.direct_surface[j] = F;
+                }
+                if (i == L && A.up_top) A.up_top[j] = up;
+            }
+            const double s_up = wave_sum(active ? nan_to_num(up) : 0.0);
+            const double s_dn = wave_sum(active ? nan_to_num(dn) : 0.0);
+            const double s_F = wave_sum(active ? nan_to_num(F) : 0.0);
+            if (lane0) { my[i] = s_up; my[levels + i] = s_dn; my[2 * levels + i] = s_F; }
+        }
+        __syncthreads();
+        double* const slot = partial + ((tile0 + tile) % slots) * nv;
+        for (int t = threadIdx.x; t < nv; t += blockDim.x)
+            slot[t] = slot[t] + ((acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]));
+        __syncthreads();
+    }
+}
+
+// ----------------------------------------------------------------------------------------
 // K5i: linear-in-optical-depth Planck source (lbl_column_flux_linear_dev, lbl_ray_radiance_linear_dev; the semantics are in
 // include/pyrad_hip.h)
 // ----------------------------------------------------------------------------------------
@@ -6066,6 +6244,29 @@ void launch_solar(const SolarArgs* d_args, int n_layers, int n_beams, int n_angl
         launch_column_band<4>(solar_diffuse_kernel<4, NA>, solar_diffuse_kernel<1, NA>, d_args, levels, first, count, partial,
                               level_flux, s);
     });
+}
+
+// K5l: one pass of a band - the downward kernel over the pass's points, one per thread, then the upward kernel with one
+// workgroup per partial slot that the pass's tiles reach (a workgroup takes the tiles of its slot in ascending order).
+int twostream_partials(long long count) {
+    return (int)std::min<long long>(std::max<long long>((count + kTwoStreamTile - 1) / kTwoStreamTile, 1), kFluxMaxBlocks);
+}
+
+void launch_twostream_pass(const TwoStreamArgs* d_args, int n_beams, long long band_first, long long first, long long count,
+                           int slots, double* partial, hipStream_t s) {
+    if (count <= 0) return;
+    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
+    with_angles(n_beams, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        hipLaunchKernelGGL(twostream_down_kernel<NB>, dim3((unsigned)tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+    });
+    hipLaunchKernelGGL(twostream_up_kernel, dim3((unsigned)std::min<long long>(tiles, slots)), dim3(kTwoStreamTile), 0, s, d_args,
+                       (first - band_first) / kTwoStreamTile, first, count, slots, partial);
+}
+
+void launch_twostream_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s) {
+    const int nv = 3 * (n_layers + 1);
+    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, slots, nv, level_flux);
 }
 
 // K5d's points per thread, chosen per angle count so that no instantiation spills (DESIGN.md "K5d")

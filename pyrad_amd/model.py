@@ -1663,6 +1663,142 @@ class SolarFluxes:
             self.up.shape[-1], len(self.mu0), self.down[..., -1], self.down[..., 0], self.up[..., -1])
 
 
+# ----------------------------------------------------------------------------------------
+# Two-stream multiple scattering of the solar beam (Atmosphere.solarFluxesTwoStream; beyond the reference)
+# ----------------------------------------------------------------------------------------
+MAX_SCATTERERS = 4
+TWOSTREAM_WORKSPACE_BYTES = 256 << 20      # the most solarFluxesTwoStream keeps for its workspace
+
+
+def _spectral_quantity(name, value, x, lo, hi, open_ends=False):
+    """A scatterer's ``name`` on the grid ``x``: a float for a number, else len(x) contiguous float64 values - that many
+    values, or a pair (wavenumbers, values) interpolated with np.interp as _surface_emissivity does.  ValueError (it names
+    ``name``) for anything else and for a value that is not finite or lies outside [lo, hi] ((lo, hi) with open_ends)."""
+    n = len(x)
+    bad = name + ": a number, %d values on xAxis or a pair (wavenumbers, values), not %r"
+    if isinstance(value, (bool, str)) or value is None:
+        raise ValueError(bad % (n, value))
+    table = isinstance(value, (tuple, list)) and len(value) == 2 and all(np.ndim(v) == 1 for v in value)
+    try:
+        if isinstance(value, (int, float, np.integer, np.floating)):
+            v = np.float64(value)
+        elif table:
+            nu, val = (np.asarray(t, dtype=np.float64) for t in value)
+        else:
+            v = np.ascontiguousarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(bad % (n, value))
+    if table:
+        if nu.size < 1 or nu.shape != val.shape or not np.all(np.isfinite(nu)) or np.any(np.diff(nu) <= 0):
+            raise ValueError(name + ": a table needs as many values as wavenumbers, the wavenumbers finite and increasing")
+        v = np.ascontiguousarray(np.interp(x, nu, val))
+    elif v.ndim and v.shape != (n,):
+        raise ValueError("%s: %d grid points expected, got shape %s" % (name, n, v.shape))
+    inside = (v > lo) & (v < hi) if open_ends else (v >= lo) & (v <= hi)
+    if not np.all(inside & np.isfinite(v)):
+        raise ValueError("%s: every value must be finite and lie in %s%g, %g%s" % (name, "([" [not open_ends], lo, hi,
+                                                                                   ")]"[not open_ends]))
+    return v if v.ndim else float(v)
+
+
+class Scatterer:
+    """Something that scatters sunlight in Atmosphere.solarFluxesTwoStream: ``amounts``, one per layer bottom to top, finite
+    and >= 0, in the unit the extinction is per (molecules cm^-2 for a cross section in cm^2; 1 where ``extinction`` is the
+    layer's optical depth itself); ``extinction`` >= 0, ``singleScatteringAlbedo`` in [0, 1] and ``asymmetry`` in (-1, 1),
+    each a number, n values on the column's xAxis or a pair (wavenumbers, values) interpolated onto it.  The spectral
+    quantities are checked against the grid by the call that uses them."""
+
+    def __init__(self, amounts, extinction=1.0, singleScatteringAlbedo=1.0, asymmetry=0.0, name=None):
+        try:
+            self.amounts = np.array([float(a) for a in amounts], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("amounts: one number per layer, not %r" % (amounts,))
+        if not np.all(np.isfinite(self.amounts) & (self.amounts >= 0.0)):
+            raise ValueError("amounts: every amount must be finite and >= 0")
+        self.extinction = extinction
+        self.singleScatteringAlbedo = singleScatteringAlbedo
+        self.asymmetry = asymmetry
+        self.name = name
+
+    def _on_grid(self, x):
+        """(extinction, albedo, asymmetry) on the grid x, each a float or len(x) values"""
+        return (_spectral_quantity("extinction", self.extinction, x, 0.0, float("inf")),
+                _spectral_quantity("singleScatteringAlbedo", self.singleScatteringAlbedo, x, 0.0, 1.0),
+                _spectral_quantity("asymmetry", self.asymmetry, x, -1.0, 1.0, open_ends=True))
+
+    def __repr__(self):
+        return "Scatterer(%s%d layers)" % ("%r, " % self.name if self.name else "", len(self.amounts))
+
+
+def rayleighCrossSection(xAxis):
+    """The Rayleigh scattering cross section of air, cm^2 per molecule, at the wavenumbers ``xAxis`` (cm^-1): Bucholtz
+    (1995), sigma = A lam^-(B + C lam + D / lam) with lam = 1e4 / nu in micrometres and (A, B, C, D) =
+    (4.01061e-28, 3.99668, 1.10298e-3, 2.71393e-2) for lam > 0.5, (3.01577e-28, 3.55212, 1.35579, 0.11563) for lam <= 0.5;
+    0 at a wavenumber of 0."""
+    nu = np.asarray(xAxis, dtype=np.float64)
+    lam = 1e4 / np.where(nu > 0.0, nu, 1.0)
+    long_ = lam > 0.5
+    A = np.where(long_, 4.01061e-28, 3.01577e-28)
+    B = np.where(long_, 3.99668, 3.55212)
+    C = np.where(long_, 1.10298e-3, 1.35579)
+    D = np.where(long_, 2.71393e-2, 0.11563)
+    return np.where(nu > 0.0, A * lam ** -(B + C * lam + D / lam), 0.0)
+
+
+def rayleighScatterer(atmosphere):
+    """The air of ``atmosphere`` as a Scatterer: per layer 100 P / (k T) * 1e-6 * depth molecules cm^-2 (P in mbar, depth in
+    cm), rayleighCrossSection on the layers' xAxis, albedo 1, asymmetry 0."""
+    layers, _ = atmosphere._column_layers()
+    amounts = [100.0 * L.P / (k * L.T) * 1e-6 * L.depth for L in layers]
+    return Scatterer(amounts, rayleighCrossSection(layers[0].xAxis), 1.0, 0.0, name="rayleigh")
+
+
+def _scatterers(scatterers, n_layers):
+    """``scatterers`` of solarFluxesTwoStream as a list of at most MAX_SCATTERERS Scatterers with n_layers amounts each"""
+    if isinstance(scatterers, Scatterer):
+        scatterers = [scatterers]
+    try:
+        scatterers = list(scatterers)
+    except TypeError:
+        raise ValueError("scatterers: a list of Scatterer objects, not %r" % (scatterers,))
+    if len(scatterers) > MAX_SCATTERERS:
+        raise ValueError("scatterers: at most %d, not %d" % (MAX_SCATTERERS, len(scatterers)))
+    for c, sc in enumerate(scatterers):
+        if not isinstance(sc, Scatterer):
+            raise ValueError("scatterers: entry %d is not a Scatterer: %r" % (c, sc))
+        if len(sc.amounts) != n_layers:
+            raise ValueError("scatterers: entry %d has %d amounts for %d layers" % (c, len(sc.amounts), n_layers))
+    return scatterers
+
+
+class TwoStreamFluxes:
+    """What Atmosphere.solarFluxesTwoStream returns.  ``up``, ``down`` (diffuse plus direct), ``direct`` and ``net``
+    (= up - down): W m^-2 at the levels 0 (surface) .. L (top), shape (L + 1,) or (n_bands, L + 1); ``heatingRate``: K/day per
+    layer; ``absorbedSurface`` = down[0] - up[0]; ``mu0``, ``beamWeight``, ``slant``: the beams used; ``upSpectrum`` (top),
+    ``downSpectrum`` (surface, diffuse plus direct), ``directSpectrum`` (surface) and ``upSurfaceSpectrum``: W m^-2 per cm^-1,
+    n points, 0 outside every band, when asked for, else None."""
+
+    def __init__(self, up, down, direct, heatingRate, mu0, beamWeight, slant, upSpectrum=None, downSpectrum=None,
+                 directSpectrum=None, upSurfaceSpectrum=None):
+        self.up = up
+        self.down = down
+        self.direct = direct
+        self.net = up - down
+        self.heatingRate = heatingRate
+        self.absorbedSurface = down[..., 0] - up[..., 0]
+        self.mu0 = mu0
+        self.beamWeight = beamWeight
+        self.slant = slant
+        self.upSpectrum = upSpectrum
+        self.downSpectrum = downSpectrum
+        self.directSpectrum = directSpectrum
+        self.upSurfaceSpectrum = upSurfaceSpectrum
+
+    def __repr__(self):
+        return "TwoStreamFluxes(levels=%d, beams=%d, down[top]=%s, down[surface]=%s, direct[surface]=%s, up[top]=%s)" % (
+            self.up.shape[-1], len(self.mu0), self.down[..., -1], self.down[..., 0], self.direct[..., 0], self.up[..., -1])
+
+
 class Jacobians:
     """What Atmosphere.jacobians returns (a leading band axis on every band value when ``bands`` was given).
     ``olr``: upward flux at the top, W m^-2; ``surfaceTemperature``: dF/dT_s in W m^-2 K^-1, None when a surface spectrum was
@@ -2522,6 +2658,78 @@ class Atmosphere(list):
                            upSpectrum=up_top.download(n) if spectra else None,
                            downSpectrum=down_surface.download(n) if spectra else None,
                            upSurfaceSpectrum=up_surface.download(n) if spectra else None)
+
+    def solarFluxesTwoStream(self, scatterers=(), deltaScaling=True, solarSpectrum=None, solarTemperature=None, distanceAU=1.0,
+                             mu0=1.0, geometry="plane", planetRadius=6.371e8, emissivity=1.0, bands=None, spectra=False):
+        """solarFluxes() through a column that also scatters: Rayleigh air, clouds, aerosol (beyond the reference).  A
+        delta-two-stream (quadrature) solution per layer and grid point, the layers joined by the adding method, over a
+        Lambertian surface of albedo 1 - ``emissivity``; the gas absorbs with the layers' absorption coefficients and
+        nothing emits.  With scattering the superposition of solarFluxes() ends for the scattered light only: thermal
+        fluxes() still add to these level by level.
+
+        ``scatterers``: up to 4 Scatterer objects (see there and rayleighScatterer), each with one amount per layer and an
+        extinction, a single-scattering albedo and an asymmetry per grid point; ``deltaScaling``: scale the forward peak
+        f = g^2 out of every scatterer (delta-Eddington's scaling; recommended for clouds).  Source, ``mu0``, ``geometry``,
+        ``planetRadius``, ``emissivity``, ``bands`` and ``spectra`` as solarFluxes() takes them.  The formulas are those of
+        lbl_column_twostream_dev (include/pyrad_hip.h): per layer t = k depth + sum_c amount_c ext_c (scaled), the
+        two-stream reflectance and transmittance R, T of the layer to diffuse light and Rb, Tb, Td to each beam, and the
+        level relations up_(l+1) = T up_l + R dn_(l+1) + P, dn_l = T dn_(l+1) + R up_l + Q solved exactly.
+        Returns a TwoStreamFluxes: ``up``, ``down`` (diffuse plus direct), ``direct``, ``net``, ``heatingRate``,
+        ``absorbedSurface``.  Without scatterers it is solarFluxes() over a Lambertian surface with the one diffuse angle
+        mu = 1 / sqrt(3).
+        The absorption coefficients are the resident ones of transmission() and fluxes(): nothing is accumulated again.
+        The kernels keep five numbers per level and point in a workspace that stays with the atmosphere: sized for the
+        widest band, but never above 256 MiB - a longer band is done in several passes, with the same bits.  Everything
+        is validated (ValueError) before the device is touched."""
+        layers, n = self._column_layers()
+        first = layers[0]
+        x = first.xAxis
+        nl = len(layers)
+        scat = _scatterers(scatterers, nl)
+        numbers = [sc._on_grid(x) for sc in scat]
+        if not isinstance(deltaScaling, (bool, np.bool_)):
+            raise ValueError("deltaScaling: True or False, not %r" % (deltaScaling,))
+        S0 = _solar_spectrum(solarSpectrum, solarTemperature, distanceAU, x)
+        mu_s, weight_s = _solar_beams(mu0)
+        depth = [L.depth for L in layers]
+        slant = solarSlants(depth, list(zip(mu_s, weight_s)), geometry, planetRadius)
+        beam_weight = weight_s * mu_s
+        emissivity = _surface_emissivity(emissivity, x)
+        band_first, band_count = _flux_bands(first.rangeMin, first.rangeMax, n, bands)
+        res = utils.BASE_RESOLUTION
+        nb = len(band_first)
+        ctx = _ctx()
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        st = _kept_state(self, "_twostream_state")
+        st.reserve(ctx, max(n, nb * 3 * (nl + 1)))
+        source = st.buf(ctx, "S0").upload(S0)
+        if not isinstance(emissivity, float):
+            emissivity = st.buf(ctx, "emissivity").upload(emissivity)
+        columns = []
+        for c, triple in enumerate(numbers):
+            columns.append([v if isinstance(v, float) else st.buf(ctx, "scat%d_%d" % (c, q)).upload(v)
+                            for q, v in enumerate(triple)])
+        # the workspace: the widest band in one pass where 256 MiB hold it, else as many whole tiles as they hold
+        tile = ctx.column_twostream_workspace(nl, 1)
+        want = ctx.column_twostream_workspace(nl, max(band_count))
+        wst = _kept_state(self, "_twostream_workspace")
+        wst.reserve(ctx, min(want, max(TWOSTREAM_WORKSPACE_BYTES // 8 // tile, 1) * tile))
+        level = st.buf(ctx, "level")
+        names = ("up_top", "down_surface", "direct_surface", "up_surface")
+        spec = {name: st.buf(ctx, name) if spectra else None for name in names}
+        ctx.column_twostream_dev(kbufs, depth, first.rangeMin, first.rangeMax, n, source, beam_weight, slant,
+                                 [sc.amounts for sc in scat], [t[0] for t in columns], [t[1] for t in columns],
+                                 [t[2] for t in columns], int(bool(deltaScaling)), band_first, band_count,
+                                 wst.buf(ctx, "workspace"), level, emissivity=emissivity, **spec)
+        sums = level.download(nb * 3 * (nl + 1)).reshape(nb, 3, nl + 1) * res
+        up, direct = sums[:, 0, :], sums[:, 2, :]
+        down = sums[:, 1, :] + direct
+        heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], depth)
+        up, down, direct, heat = _band_values(bands, [up, down, direct, heat])
+        got = {name: spec[name].download(n) if spectra else None for name in names}
+        return TwoStreamFluxes(up, down, direct, heat, mu_s, beam_weight, slant, upSpectrum=got["up_top"],
+                               downSpectrum=got["down_surface"] + got["direct_surface"] if spectra else None,
+                               directSpectrum=got["direct_surface"], upSurfaceSpectrum=got["up_surface"])
 
     def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False,
                   temperature="planck", emissivity=None, reflection="lambertian", topSpectrum=None):
