@@ -3666,6 +3666,86 @@ __device__ __forceinline__ double angle_sum(const ColumnRT& A, V v) {
     return f;
 }
 
+// One step of K5i's linear source for the thread's NP points: transport_step with two Planck values, Ba where the light
+// enters (pbkT_a) and Bb where it leaves (pbkT_b); update(p, k_p, Ba_p, Bb_p - Ba_p).
+template <bool FAST, int NP, class Update>
+__device__ __forceinline__ void linear_step(const double (&nu)[NP], const double (&pa_n)[NP], double pbkT_a, double pbkT_b,
+                                            f64v<NP> v, Update update) {
+#pragma clang fp contract(off)
+    double Ea0 = 0.0, Eb0 = 0.0;
+    if (FAST) {
+        Ea0 = exp_clamped(nu[0] * pbkT_a);
+        Eb0 = exp_clamped(nu[0] * pbkT_b);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const double Ba = fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT_a, Ea0);
+        const double Bb = fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT_b, Eb0);
+        update(p, v[p], Ba, Bb - Ba);
+    }
+}
+
+// K5i: I <- t I + (1 - t) Ba + g(tau) dB, t = tr = exp_neg_budget(tau)
+template <bool FAST>
+__device__ __forceinline__ double linear_update(double tau, double tr, double I, double Ba, double dB) {
+#pragma clang fp contract(off)
+    const double isothermal = fold_update<FAST>(tr, I, Ba);
+    const double slope = linear_source_g(tau, tr) * dB;
+    return isothermal + slope;
+}
+
+// The band frame: what the kernels that sum a band into Jacobian or level slots share (K5d, K5h, K5j, K5k).  The
+// [wave][slot] block `acc` in LDS (declared by the kernel, kSlot doubles per wave) is zeroed; a grid-stride loop hands every
+// thread NP points j .. j + NP - 1 of the two runs [lo0, lo0 + n0) and [lo1, lo1 + n1) and calls walk(fast_tag, j, active, nu,
+// pa_n, add) for them; at the end the four waves' slots are added in a fixed order into the workgroup's partial of nv values.
+// What makes the kernels on it right is stated here, once:
+//   - the loop bound is uniform over the workgroup, and an idle lane (active == false) works on a valid point, lo0, so that
+//     every lane takes part in the wave reductions; a walk adds 0 for it and stores nothing;
+//   - add(slot, s) is wave_sum and then lane 0 adding to its wave's slot: no atomics, one order, the same bits every run;
+//   - the one-exp Planck path (fast_tag = std::true_type) is taken by a whole wave or not at all (fold_fast_path) and only
+//     with several points per thread: a band's head and tail points go to the <1, ...> instantiation, general expression.
+// The flux kernels of K5c, K5g and K5i keep this loop in their own bodies: registers ("Two frames carry ...").
+// PLANCK = false (K5k, which has no source term) leaves out the wavenumbers, the Planck numerators and the dispatch: nu and
+// pa_n are then not set, and the walk gets std::false_type.
+// (threads: blockDim.x, read by the __global__ kernel itself.  Read in a device function it is not folded to the launch's
+// uniform workgroup size: it stays a load and a select on the workgroup's index, in a vector register.)
+template <int NP, int kSlot, bool PLANCK = true, class Args, class Walk>
+__device__ __forceinline__ void band_frame(const Args& A, unsigned threads, long long lo0, long long n0, long long lo1,
+                                           long long n1, double* __restrict__ partial, double* acc, int nv, Walk walk) {
+#pragma clang fp contract(off)
+    for (int t = threadIdx.x; t < 4 * kSlot; t += threads) acc[t] = 0.0;
+    __syncthreads();
+    double* my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    auto add = [&](int slot, double s) {
+        s = wave_sum(s);
+        if (lane0) my[slot] += s;
+    };
+    const long long total = n0 + n1;
+    const long long stride = (long long)gridDim.x * threads * NP;
+    for (long long q0 = (long long)blockIdx.x * threads * NP; q0 < total; q0 += stride) {
+        const long long q = q0 + (long long)threadIdx.x * NP;
+        const bool active = q < total;
+        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        double nu[NP], pa_n[NP];
+        if constexpr (PLANCK) {
+            column_points<NP>(A, j, nu, pa_n);
+            const bool fast = fold_fast_path<NP>(A, nu, active);
+            if constexpr (NP > 1) {
+                if (fast) walk(std::true_type{}, j, active, nu, pa_n, add);
+                else walk(std::false_type{}, j, active, nu, pa_n, add);
+            } else {
+                walk(std::false_type{}, j, active, nu, pa_n, add);
+            }
+        } else {
+            walk(std::false_type{}, j, active, nu, pa_n, add);
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += threads)
+        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+}
+
 // K5c: walks the layers bottom to top for the upward radiances I_up[k] and then top to bottom for the downward ones,
 // re-reading k_l and recomputing B_l on the way down (the registers cannot hold 128 layers' worth).  With the angle set
 // {(1, pi)} the upward radiance at the top is the fold's I_out bit for bit wherever both take the same Planck path (every
@@ -3772,6 +3852,140 @@ __global__ __launch_bounds__(256) void column_flux_final_kernel(const double* __
     if (threadIdx.x == 0) level_flux[t] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+// The ray frame: what five of the six ray kernels (K5e - K5j) share; K5f's ray_jacobian_kernel keeps the same set-up and loops
+// in its own body (it measures slower on the frame: DESIGN.md, "Two frames carry ...").
+// A thread owns NP grid points from j on and a workgroup one bundle of RB rays with one layer sequence; the frame finds
+// both, forms what every ray kernel needs per point and per ray, and walks the bundle's segments for the kernel, which supplies only its start values, what happens at a surface marker and
+// its step through a real segment.  Stated here, once:
+//   - the idle lanes of the last workgroup (active == false) work on a valid point, lo0, and store nothing: the Planck path
+//     is chosen per wave (fold_fast_path), so every lane has to have a point;
+//   - ray, segment and layer indices are uniform over the workgroup, so the tables behind the argument block and the layer
+//     scalars come through scalar loads, and the branch on a marker is uniform too (the rays of a bundle share their layer
+//     sequence, markers included);
+//   - k_l is loaded one REAL segment ahead of its use, past the markers;
+//   - head and tail points go to the <1, 1, ...> instantiation and its general Planck expression (dispatch).
+// MARKERS = false (K5e: no surface in the path) leaves out the emissivity, the marker branch and the search for the
+// next real segment.
+template <int NP, int RB, bool MARKERS, class Args>
+struct RayFrame {
+    typedef f64v<NP> vec;
+    const Args& A;
+    const char* blk;                    // the argument block: A, and behind it the tables at A.off_*
+    long long j;                        // the thread's first grid point
+    bool active, fast;
+    double nu[NP], pa_n[NP], Is[NP];    // per point: column_points and the surface's source
+    double em[NP];                      //   and the surface's emissivity: set only with MARKERS, not to be read without
+    int rid[RB], s0[RB];                // per ray of the bundle: its index and its first segment
+    bool surface[RB];                   //   and whether it starts at the surface (source kind 1)
+    int ns;                             // segments, markers included (the same for every ray of the bundle, as are its
+    const int32_t* __restrict__ lay;    //   layers, lay[0 .. ns), and its rows)
+    const double* __restrict__ seg_length;
+
+    // (threads: blockDim.x, read by the __global__ kernel itself, as for band_frame)
+    __device__ __forceinline__ RayFrame(const Args* Ap, unsigned threads, long long lo0, long long n0, long long lo1,
+                                        long long n1, int order_first) : A(*Ap), blk((const char*)Ap) {
+#pragma clang fp contract(off)
+        const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
+        const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
+        const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
+        seg_length = (const double*)(blk + A.off_seg_length);
+        const long long q = ((long long)blockIdx.x * threads + threadIdx.x) * NP;
+        active = q < n0 + n1;
+        j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+        column_points<NP>(A, j, nu, pa_n);
+        fast = fold_fast_path<NP>(A, nu, active);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
+            if constexpr (MARKERS) em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+        }
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            rid[i] = order[order_first + (int)blockIdx.y * RB + i];
+            s0[i] = ray_first[rid[i]];
+            surface[i] = source_kind[rid[i]] == 1;
+        }
+        ns = ray_first[rid[0] + 1] - s0[0];
+        lay = (const int32_t*)(blk + A.off_seg_layer) + s0[0];
+    }
+
+    // walk(fast_tag): the one-exp Planck path for a wave that may take it, the general expression otherwise
+    template <class Walk>
+    __device__ __forceinline__ void dispatch(Walk walk) const {
+        if constexpr (NP > 1) {
+            if (fast) walk(std::true_type{});
+            else walk(std::false_type{});
+        } else {
+            walk(std::false_type{});
+        }
+    }
+
+    // the nearest real segment at or after s / at or before s (ns / -1: none)
+    __device__ __forceinline__ int real_from(int s) const {
+        if constexpr (MARKERS) while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
+        return s;
+    }
+    __device__ __forceinline__ int real_back(int s) const {
+        if constexpr (MARKERS) while (s >= 0 && lay[s] == kRaySurfaceMarker) --s;
+        return s;
+    }
+
+    // The segments in order of travel: marker() at a surface marker, step(s, k, len) for a real segment s with the points'
+    // absorption coefficients k of its layer and every ray's path length len[i] through it.
+    template <class Marker, class Step>
+    __device__ __forceinline__ void forward(Marker marker, Step step) const {
+        int ahead = real_from(0);
+        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
+        for (int s = 0; s < ns; ++s) {
+            if (MARKERS && lay[s] == kRaySurfaceMarker) {
+                marker();
+                continue;
+            }
+            ahead = real_from(s + 1);
+            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
+            double len[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            step(s, cur, len);
+            cur = nxt;
+        }
+    }
+
+    // The same last to first (the Jacobian kernels' second pass)
+    template <class Marker, class Step>
+    __device__ __forceinline__ void backward(Marker marker, Step step) const {
+        int behind = real_back(ns - 1);
+        vec cur = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : (vec)(0.0);
+        for (int s = ns - 1; s >= 0; --s) {
+            if (MARKERS && lay[s] == kRaySurfaceMarker) {
+                marker();
+                continue;
+            }
+            behind = real_back(s - 1);
+            const vec nxt = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : cur;
+            double len[RB];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            step(s, cur, len);
+            cur = nxt;
+        }
+    }
+
+    // every ray's radiance and, where asked for, total transmittance at the thread's points
+    __device__ __forceinline__ void store(const double (&I)[RB][NP], const double (&Tt)[RB][NP]) const {
+        if (!active) return;
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            const long long o = (long long)rid[i] * A.n + j;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                A.radiance[o + p] = I[i][p];
+                if (A.transmittance) A.transmittance[o + p] = Tt[i][p];
+            }
+        }
+    }
+};
+
 // K5e: ray paths (lbl_ray_radiance_dev; the semantics are in include/pyrad_hip.h).  K5c's step along an ordered list of
 // (layer, path length) segments instead of the column bottom to top: no level sums, so no reductions and nothing shared
 // between threads.  One workgroup = 256 NP points x one BUNDLE of RB rays that cross the same layers in the same order
@@ -3785,41 +3999,17 @@ __global__ __launch_bounds__(256) void ray_radiance_kernel(const RayArgs* __rest
 #pragma clang fp contract(off)
     typedef f64v<NP> vec;
     const RayArgs& A = *Ap;
-    const char* blk = (const char*)Ap;
-    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
-    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
-    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
-    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
-    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
-    // (idle lanes of the last workgroup work on a valid point and store nothing)
-    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
-    const bool active = q < n0 + n1;
-    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
-    double nu[NP], pa_n[NP], Is[NP], I[RB][NP], Tt[RB][NP];
-    column_points<NP>(A, j, nu, pa_n);
-    const bool fast = fold_fast_path<NP>(A, nu, active);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
-    int rid[RB], s0[RB];
+    const RayFrame<NP, RB, false, RayArgs> F(Ap, blockDim.x, lo0, n0, lo1, n1, order_first);
+    double I[RB][NP], Tt[RB][NP];
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
-        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
-        s0[i] = ray_first[rid[i]];
-        const bool surface = source_kind[rid[i]] == 1;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) { I[i][p] = surface ? Is[p] : 0.0; Tt[i][p] = 1.0; }
+        for (int p = 0; p < NP; ++p) { I[i][p] = F.surface[i] ? F.Is[p] : 0.0; Tt[i][p] = 1.0; }
     }
-    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers)
-    const int32_t* lay = seg_layer + s0[0];
-    auto walk = [&](auto fast_tag) {
+    F.dispatch([&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
-        vec cur = ns > 0 ? load_points<NP>(A.abs_coef[lay[0]], j) : (vec)(0.0);
-        for (int s = 0; s < ns; ++s) {
-            const vec nxt = s + 1 < ns ? load_points<NP>(A.abs_coef[lay[s + 1]], j) : cur;
-            double len[RB];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
-            transport_step<FAST, NP>(nu, pa_n, A.pbkT[lay[s]], cur, [&](int p, double kp, double B) {
+        F.forward([] {}, [&](int s, vec cur, const double (&len)[RB]) {
+            transport_step<FAST, NP>(F.nu, F.pa_n, A.pbkT[F.lay[s]], cur, [&](int p, double kp, double B) {
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
                     const double tr = exp_neg_budget(kp * len[i]);
@@ -3827,25 +4017,9 @@ __global__ __launch_bounds__(256) void ray_radiance_kernel(const RayArgs* __rest
                     Tt[i][p] = Tt[i][p] * tr;
                 }
             });
-            cur = nxt;
-        }
-    };
-    if constexpr (NP > 1) {
-        if (fast) walk(std::true_type{});
-        else walk(std::false_type{});
-    } else {
-        walk(std::false_type{});
-    }
-    if (!active) return;
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        const long long o = (long long)rid[i] * A.n + j;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            A.radiance[o + p] = I[i][p];
-            if (A.transmittance) A.transmittance[o + p] = Tt[i][p];
-        }
-    }
+        });
+    });
+    F.store(I, Tt);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -3975,98 +4149,69 @@ __global__ __launch_bounds__(256, (surface_flux_waves<NP, NA>())) void surface_f
 // the surface starts with e Is + (1 - e) Rd, Rd the diffuse reflection of surface_down (0 without it).  The rays of a bundle
 // share their layer sequence, markers included, so the branch on a marker is uniform over the workgroup; the prefetch of
 // k_l runs one real segment ahead, past the markers.  The operations of a real segment are K5e's.
-template <int NP, int RB>
-__global__ __launch_bounds__(256) void ray_surface_kernel(const RaySurfaceArgs* __restrict__ Ap, long long lo0, long long n0,
-                                                          long long lo1, long long n1, int order_first) {
+// One body for this kernel and K5i's (LINEAR: linear_step and linear_update with the segment's own pair of Planck exponents,
+// entry and exit in the light's direction of travel, from the table beside seg_length - the rays of a bundle share the
+// pairs as they share the layers, the host bundles by both, so the pair is read from the bundle's first ray).
+template <int NP, int RB, bool LINEAR, class Args>
+__device__ __forceinline__ void ray_surface_walks(const Args* Ap, unsigned threads, long long lo0, long long n0, long long lo1,
+                                                  long long n1, int order_first) {
 #pragma clang fp contract(off)
     typedef f64v<NP> vec;
-    const RaySurfaceArgs& A = *Ap;
-    const char* blk = (const char*)Ap;
-    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
-    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
-    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
-    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
-    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
-    // (idle lanes of the last workgroup work on a valid point and store nothing)
-    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
-    const bool active = q < n0 + n1;
-    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
-    double nu[NP], pa_n[NP], Is[NP], em[NP], I[RB][NP], Tt[RB][NP];
-    column_points<NP>(A, j, nu, pa_n);
-    const bool fast = fold_fast_path<NP>(A, nu, active);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
-        em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
-    }
-    int rid[RB], s0[RB];
+    const Args& A = *Ap;
+    const RayFrame<NP, RB, true, Args> F(Ap, threads, lo0, n0, lo1, n1, order_first);
+    double I[RB][NP], Tt[RB][NP];
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
-        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
-        s0[i] = ray_first[rid[i]];
-        const bool surface = source_kind[rid[i]] == 1;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            const double Rd = A.surface_down ? A.surface_down[j + p] / A.surface_down_norm : 0.0;
-            I[i][p] = surface ? surface_leaving(em[p], Is[p], Rd) : 0.0;
+            const double Rd = A.surface_down ? A.surface_down[F.j + p] / A.surface_down_norm : 0.0;
+            I[i][p] = F.surface[i] ? surface_leaving(F.em[p], F.Is[p], Rd) : 0.0;
             Tt[i][p] = 1.0;
         }
     }
-    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers)
-    const int32_t* lay = seg_layer + s0[0];
-    // the first real segment at or after s (ns: none)
-    auto real_from = [&](int s) {
-        while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
-        return s;
-    };
-    auto walk = [&](auto fast_tag) {
+    const double* pbk = nullptr;        // (LINEAR) the bundle's exponent pairs, formed once, outside the segment loop
+    if constexpr (LINEAR) pbk = (const double*)(F.blk + A.off_seg_pbkT) + 2 * (long long)F.s0[0];
+    F.dispatch([&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
-        int ahead = real_from(0);
-        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
-        for (int s = 0; s < ns; ++s) {
-            if (lay[s] == kRaySurfaceMarker) {
+        F.forward([&] {
 #pragma unroll
-                for (int i = 0; i < RB; ++i) {
+            for (int i = 0; i < RB; ++i) {
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        I[i][p] = surface_leaving(em[p], Is[p], I[i][p]);
-                        Tt[i][p] = Tt[i][p] * (1.0 - em[p]);
-                    }
+                for (int p = 0; p < NP; ++p) {
+                    I[i][p] = surface_leaving(F.em[p], F.Is[p], I[i][p]);
+                    Tt[i][p] = Tt[i][p] * (1.0 - F.em[p]);
                 }
-                continue;
             }
-            ahead = real_from(s + 1);
-            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
-            double len[RB];
+        }, [&](int s, vec cur, const double (&len)[RB]) {
+            if constexpr (LINEAR) {
+                linear_step<FAST, NP>(F.nu, F.pa_n, pbk[2 * s], pbk[2 * s + 1], cur, [&](int p, double kp, double Ba, double dB) {
 #pragma unroll
-            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
-            transport_step<FAST, NP>(nu, pa_n, A.pbkT[lay[s]], cur, [&](int p, double kp, double B) {
+                    for (int i = 0; i < RB; ++i) {
+                        const double tau = kp * len[i];
+                        const double tr = exp_neg_budget(tau);
+                        I[i][p] = linear_update<FAST>(tau, tr, I[i][p], Ba, dB);
+                        Tt[i][p] = Tt[i][p] * tr;
+                    }
+                });
+            } else {
+                transport_step<FAST, NP>(F.nu, F.pa_n, A.pbkT[F.lay[s]], cur, [&](int p, double kp, double B) {
 #pragma unroll
-                for (int i = 0; i < RB; ++i) {
-                    const double tr = exp_neg_budget(kp * len[i]);
-                    I[i][p] = fold_update<FAST>(tr, I[i][p], B);
-                    Tt[i][p] = Tt[i][p] * tr;
-                }
-            });
-            cur = nxt;
-        }
-    };
-    if constexpr (NP > 1) {
-        if (fast) walk(std::true_type{});
-        else walk(std::false_type{});
-    } else {
-        walk(std::false_type{});
-    }
-    if (!active) return;
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        const long long o = (long long)rid[i] * A.n + j;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            A.radiance[o + p] = I[i][p];
-            if (A.transmittance) A.transmittance[o + p] = Tt[i][p];
-        }
-    }
+                    for (int i = 0; i < RB; ++i) {
+                        const double tr = exp_neg_budget(kp * len[i]);
+                        I[i][p] = fold_update<FAST>(tr, I[i][p], B);
+                        Tt[i][p] = Tt[i][p] * tr;
+                    }
+                });
+            }
+        });
+    });
+    F.store(I, Tt);
+}
+
+template <int NP, int RB>
+__global__ __launch_bounds__(256) void ray_surface_kernel(const RaySurfaceArgs* __restrict__ Ap, long long lo0, long long n0,
+                                                          long long lo1, long long n1, int order_first) {
+    ray_surface_walks<NP, RB, false>(Ap, blockDim.x, lo0, n0, lo1, n1, order_first);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -4086,8 +4231,8 @@ __global__ __launch_bounds__(256) void ray_surface_kernel(const RaySurfaceArgs* 
 // reduction are K5c's; the beam kernel's partial holds [down 0..L] (Lambertian) or [up 0..L, down 0..L] (specular), the
 // diffuse kernel's [up 0..L].
 template <int NP, int NB, bool DIFFUSE>
-__device__ __forceinline__ void solar_walks(const SolarArgs& A, long long lo0, long long n0, long long lo1, long long n1,
-                                            double* __restrict__ partial, double* acc) {
+__device__ __forceinline__ void solar_walks(const SolarArgs& A, unsigned threads, long long lo0, long long n0, long long lo1,
+                                            long long n1, double* __restrict__ partial, double* acc) {
 #pragma clang fp contract(off)
     typedef f64v<NP> vec;
     constexpr int kSlot = 2 * (kMaxLayers + 1);
@@ -4095,19 +4240,10 @@ __device__ __forceinline__ void solar_walks(const SolarArgs& A, long long lo0, l
     const bool specular = !DIFFUSE && A.reflection == 1;
     const int nv = specular ? 2 * (L + 1) : L + 1;
     const int down0 = specular ? L + 1 : 0;
-    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
-    __syncthreads();
-    double* my = acc + (threadIdx.x >> 6) * kSlot;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    const long long total = n0 + n1;
-    const long long stride = (long long)gridDim.x * blockDim.x * NP;
     auto rate = [&](int s, int l) { return DIFFUSE ? A.rmu[s] : A.slant[s][l]; };
     auto wt = [&](int s) { return DIFFUSE ? A.w[s] : A.beam_w[s]; };
-    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
-    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
-        const long long q = q0 + (long long)threadIdx.x * NP;
-        const bool active = q < total;
-        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    band_frame<NP, kSlot, false>(A, threads, lo0, n0, lo1, n1, partial, acc, nv, [&](auto, long long j, bool active,
+                                 const double (&)[NP], const double (&)[NP], auto add) {
         double S[NB][NP];
         // sum_s w_s S_s per point (beam 0 first), nan_to_num, summed over the thread's points, the wave, into the wave's slot
         auto level = [&](int slot, double* spec, double* spec2 = nullptr) {
@@ -4121,8 +4257,7 @@ __device__ __forceinline__ void solar_walks(const SolarArgs& A, long long lo0, l
                 if (spec2 && active) spec2[j + p] = f;
                 sum += active ? nan_to_num(f) : 0.0;
             }
-            sum = wave_sum(sum);
-            if (lane0) my[slot] += sum;
+            add(slot, sum);
         };
         auto layer = [&](int l, vec v) {
             const double depth = A.depth[l];
@@ -4178,24 +4313,21 @@ __device__ __forceinline__ void solar_walks(const SolarArgs& A, long long lo0, l
                 cur = nxt;
             }
         }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < nv; t += blockDim.x)
-        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+    });
 }
 
 template <int NP, int NB>
 __global__ __launch_bounds__(256) void solar_beam_kernel(const SolarArgs* __restrict__ Ap, long long lo0, long long n0,
                                                          long long lo1, long long n1, double* __restrict__ partial) {
     __shared__ double acc[4 * 2 * (kMaxLayers + 1)];     // [wave][up levels 0..L, down levels 0..L]
-    solar_walks<NP, NB, false>(*Ap, lo0, n0, lo1, n1, partial, acc);
+    solar_walks<NP, NB, false>(*Ap, blockDim.x, lo0, n0, lo1, n1, partial, acc);
 }
 
 template <int NP, int NA>
 __global__ __launch_bounds__(256) void solar_diffuse_kernel(const SolarArgs* __restrict__ Ap, long long lo0, long long n0,
                                                             long long lo1, long long n1, double* __restrict__ partial) {
     __shared__ double acc[4 * 2 * (kMaxLayers + 1)];
-    solar_walks<NP, NA, true>(*Ap, lo0, n0, lo1, n1, partial, acc);
+    solar_walks<NP, NA, true>(*Ap, blockDim.x, lo0, n0, lo1, n1, partial, acc);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -4385,33 +4517,6 @@ __global__ __launch_bounds__(256) void twostream_up_kernel(const TwoStreamArgs* 
 // returns fold_update's bits, and both kernels K5g's.  Per point and step: a second Planck value, from a second exp per
 // thread on the fast path (whose test covers every edge temperature of the call), and per angle or ray one g.
 
-// One step for the thread's NP points: transport_step with two Planck values; update(p, k_p, Ba_p, Bb_p - Ba_p).
-template <bool FAST, int NP, class Update>
-__device__ __forceinline__ void linear_step(const double (&nu)[NP], const double (&pa_n)[NP], double pbkT_a, double pbkT_b,
-                                            f64v<NP> v, Update update) {
-#pragma clang fp contract(off)
-    double Ea0 = 0.0, Eb0 = 0.0;
-    if (FAST) {
-        Ea0 = exp_clamped(nu[0] * pbkT_a);
-        Eb0 = exp_clamped(nu[0] * pbkT_b);
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const double Ba = fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT_a, Ea0);
-        const double Bb = fold_planck<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT_b, Eb0);
-        update(p, v[p], Ba, Bb - Ba);
-    }
-}
-
-// I <- t I + (1 - t) Ba + g(tau) dB, t = tr = exp_neg_budget(tau)
-template <bool FAST>
-__device__ __forceinline__ double linear_update(double tau, double tr, double I, double Ba, double dB) {
-#pragma clang fp contract(off)
-    const double isothermal = fold_update<FAST>(tr, I, Ba);
-    const double slope = linear_source_g(tau, tr) * dB;
-    return isothermal + slope;
-}
-
 // surface_flux_kernel with linear_step: going down the light enters a layer at its top edge and leaves at its bottom edge,
 // going up the other way round.  Everything else - Is in LDS, the surface, the level slots, the partials - is K5g's.
 // (the second launch bound: 4 points per thread take 135-163 registers with one to four angles, three waves per SIMD, and
@@ -4518,104 +4623,26 @@ __global__ __launch_bounds__(256, (linear_flux_waves<NP, NA>())) void linear_flu
         partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
 }
 
-// ray_surface_kernel with linear_step: every real segment has its own pair of Planck exponents, entry and exit in the light's
-// direction of travel, in a table beside seg_length; the rays of a bundle share the pairs as they share the layers (the host
-// bundles by both), so the pair is read from the bundle's first ray.  Markers, the diffuse start term and the prefetch are
-// K5g's; a ray's operations are the same in every bundle size.
+// ray_surface_walks with LINEAR: markers, the diffuse start term and the prefetch are K5g's; a ray's operations are the
+// same in every bundle size.
 template <int NP, int RB>
 __global__ __launch_bounds__(256) void linear_ray_kernel(const LinearRayArgs* __restrict__ Ap, long long lo0, long long n0,
                                                          long long lo1, long long n1, int order_first) {
+    ray_surface_walks<NP, RB, true>(Ap, blockDim.x, lo0, n0, lo1, n1, order_first);
+}
+
+// A layer's terms for the column Jacobians (K5d, K5h, K5j): term_k Gd per point, Gd = depth G, summed into the terms' slots,
+// which begin at slot0 (in K5h and K5j walks 2 and 3 each add their leg)
+template <int NP, class Add>
+__device__ __forceinline__ void jacobian_terms(const JacArgs& A, int l, long long j, bool active, const double (&Gd)[NP],
+                                               int slot0, Add add) {
 #pragma clang fp contract(off)
-    typedef f64v<NP> vec;
-    const LinearRayArgs& A = *Ap;
-    const char* blk = (const char*)Ap;
-    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
-    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
-    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
-    const double* __restrict__ seg_pbkT = (const double*)(blk + A.off_seg_pbkT);
-    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
-    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
-    // (idle lanes of the last workgroup work on a valid point and store nothing)
-    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
-    const bool active = q < n0 + n1;
-    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
-    double nu[NP], pa_n[NP], Is[NP], em[NP], I[RB][NP], Tt[RB][NP];
-    column_points<NP>(A, j, nu, pa_n);
-    const bool fast = fold_fast_path<NP>(A, nu, active);
+    for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
+        const f64v<NP> km = load_points<NP>(A.term_k[t], j);
+        double s = 0.0;
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
-        em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
-    }
-    int rid[RB], s0[RB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
-        s0[i] = ray_first[rid[i]];
-        const bool surface = source_kind[rid[i]] == 1;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const double Rd = A.surface_down ? A.surface_down[j + p] / A.surface_down_norm : 0.0;
-            I[i][p] = surface ? surface_leaving(em[p], Is[p], Rd) : 0.0;
-            Tt[i][p] = 1.0;
-        }
-    }
-    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers)
-    const int32_t* lay = seg_layer + s0[0];
-    const double* pbk = seg_pbkT + 2 * (long long)s0[0];
-    // the first real segment at or after s (ns: none)
-    auto real_from = [&](int s) {
-        while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
-        return s;
-    };
-    auto walk = [&](auto fast_tag) {
-        constexpr bool FAST = decltype(fast_tag)::value;
-        int ahead = real_from(0);
-        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
-        for (int s = 0; s < ns; ++s) {
-            if (lay[s] == kRaySurfaceMarker) {
-#pragma unroll
-                for (int i = 0; i < RB; ++i) {
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        I[i][p] = surface_leaving(em[p], Is[p], I[i][p]);
-                        Tt[i][p] = Tt[i][p] * (1.0 - em[p]);
-                    }
-                }
-                continue;
-            }
-            ahead = real_from(s + 1);
-            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
-            double len[RB];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
-            linear_step<FAST, NP>(nu, pa_n, pbk[2 * s], pbk[2 * s + 1], cur, [&](int p, double kp, double Ba, double dB) {
-#pragma unroll
-                for (int i = 0; i < RB; ++i) {
-                    const double tau = kp * len[i];
-                    const double tr = exp_neg_budget(tau);
-                    I[i][p] = linear_update<FAST>(tau, tr, I[i][p], Ba, dB);
-                    Tt[i][p] = Tt[i][p] * tr;
-                }
-            });
-            cur = nxt;
-        }
-    };
-    if constexpr (NP > 1) {
-        if (fast) walk(std::true_type{});
-        else walk(std::false_type{});
-    } else {
-        walk(std::false_type{});
-    }
-    if (!active) return;
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        const long long o = (long long)rid[i] * A.n + j;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            A.radiance[o + p] = I[i][p];
-            if (A.transmittance) A.transmittance[o + p] = Tt[i][p];
-        }
+        for (int p = 0; p < NP; ++p) s += active ? nan_to_num(km[p] * Gd[p]) : 0.0;
+        add(slot0 + A.term_slot[t], s);
     }
 }
 
@@ -4636,24 +4663,9 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
     const JacArgs& A = *Ap;
     const int L = A.n_layers;
     const int nv = 2 + 2 * L + A.n_terms;
-    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
-    __syncthreads();
-    double* my = acc + (threadIdx.x >> 6) * kSlot;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    auto add = [&](int slot, double s) {
-        s = wave_sum(s);
-        if (lane0) my[slot] += s;
-    };
-    const long long total = n0 + n1;
-    const long long stride = (long long)gridDim.x * blockDim.x * NP;
-    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
-    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
-        const long long q = q0 + (long long)threadIdx.x * NP;
-        const bool active = q < total;
-        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
-        double nu[NP], pa_n[NP], dBs[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP];
-        column_points<NP>(A, j, nu, pa_n);
-        const bool fast = fold_fast_path<NP>(A, nu, active);
+    band_frame<NP, kSlot>(A, blockDim.x, lo0, n0, lo1, n1, partial, acc, nv, [&](auto fast_tag, long long j, bool active,
+                          const double (&nu)[NP], const double (&pa_n)[NP], auto add) {
+        double dBs[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP];
         auto up = [&](auto fast_tag, int l, vec v) {
             constexpr bool FAST = decltype(fast_tag)::value;
             const double pbkT = A.pbkT[l], depth = A.depth[l];
@@ -4703,63 +4715,46 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
             }
             add(2 + l, s_tau);
             add(2 + L + l, s_T);
-            for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load_points<NP>(A.term_k[t], j);
-                double s = 0.0;
-#pragma unroll
-                for (int p = 0; p < NP; ++p) s += active ? nan_to_num(km[p] * Gd[p]) : 0.0;
-                add(2 + 2 * L + A.term_slot[t], s);
-            }
+            jacobian_terms<NP>(A, l, j, active, Gd, 2 + 2 * L, add);
         };
-        auto walk = [&](auto fast_tag) {
-            // upward: I_0 = I_surface or B(nu, surface_T), as K5c
+        // upward: I_0 = I_surface or B(nu, surface_T), as K5c
 #pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                dBs[p] = 0.0;
-                const double Is = A.I_surface ? A.I_surface[j + p]
-                                              : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
-                                                                         A.r_surface_T, &dBs[p]);
+        for (int p = 0; p < NP; ++p) {
+            dBs[p] = 0.0;
+            const double Is = A.I_surface ? A.I_surface[j + p]
+                                          : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
+                                                                     A.r_surface_T, &dBs[p]);
 #pragma unroll
-                for (int k = 0; k < NA; ++k) { I[k][p] = Is; Imax[k][p] = Is; }
-            }
-            vec cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
-            for (int l = 0; l < L; ++l) {
-                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
-                up(fast_tag, l, cur);
-                cur = nxt;
-            }
-            // F_top; then I becomes D = -I_top and A = 1
-            double s = 0.0;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
-#pragma unroll
-                for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
-            }
-            add(0, s);
-            cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-            for (int l = L - 1; l >= 0; --l) {
-                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-                down(fast_tag, l, cur);
-                cur = nxt;
-            }
-            // dF/dT_s = sum_k W_k A_(-1)k dB(nu, T_s)/dT (0 when the surface is a given spectrum)
-            s = 0.0;
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-                s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return Ak[k][p] * dBs[p]; })) : 0.0;
-            add(1, s);
-        };
-        if constexpr (NP > 1) {
-            if (fast) walk(std::true_type{});
-            else walk(std::false_type{});
-        } else {
-            walk(std::false_type{});
+            for (int k = 0; k < NA; ++k) { I[k][p] = Is; Imax[k][p] = Is; }
         }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < nv; t += blockDim.x)
-        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+        vec cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+        for (int l = 0; l < L; ++l) {
+            const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+            up(fast_tag, l, cur);
+            cur = nxt;
+        }
+        // F_top; then I becomes D = -I_top and A = 1
+        double s = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
+        }
+        add(0, s);
+        cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+        for (int l = L - 1; l >= 0; --l) {
+            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+            down(fast_tag, l, cur);
+            cur = nxt;
+        }
+        // dF/dT_s = sum_k W_k A_(-1)k dB(nu, T_s)/dT (0 when the surface is a given spectrum)
+        s = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+            s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return Ak[k][p] * dBs[p]; })) : 0.0;
+        add(1, s);
+    });
 }
 
 // K5f: ray-path Jacobians (lbl_ray_jacobian_dev; the semantics are in include/pyrad_hip.h).  K5e's walk over the bundle's
@@ -4934,35 +4929,10 @@ __global__ __launch_bounds__(256) void surface_jacobian_kernel(const SurfaceJacA
     const SurfaceJacArgs& A = *Ap;
     const int L = A.n_layers;
     const int nv = 3 + 2 * L + A.n_terms;
-    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
-    __syncthreads();
-    double* my = acc + (threadIdx.x >> 6) * kSlot;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    auto add = [&](int slot, double s) {
-        s = wave_sum(s);
-        if (lane0) my[slot] += s;
-    };
-    const long long total = n0 + n1;
-    const long long stride = (long long)gridDim.x * blockDim.x * NP;
-    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
-    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
-        const long long q = q0 + (long long)threadIdx.x * NP;
-        const bool active = q < total;
-        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    band_frame<NP, kSlot>(A, blockDim.x, lo0, n0, lo1, n1, partial, acc, nv, [&](auto fast_tag, long long j, bool active,
+                          const double (&nu)[NP], const double (&pa_n)[NP], auto add) {
         // walk 1: I = Id, Dm = Dmax, Ak = Ttot;  walk 2: I = Iu, Imax, Ck = C, Dp = D', Dm, Ak = Qf;  walk 3: I = D, Imax, Ak = A
-        double nu[NP], pa_n[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP], Ck[NA][NP], Dp[NA][NP], Dm[NA][NP];
-        column_points<NP>(A, j, nu, pa_n);
-        const bool fast = fold_fast_path<NP>(A, nu, active);
-        // the layer's terms: term_k depth G per point, into the terms' slots (walks 2 and 3 each add their leg)
-        auto terms = [&](int l, const double (&Gd)[NP]) {
-            for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load_points<NP>(A.term_k[t], j);
-                double s = 0.0;
-#pragma unroll
-                for (int p = 0; p < NP; ++p) s += active ? nan_to_num(km[p] * Gd[p]) : 0.0;
-                add(3 + 2 * L + A.term_slot[t], s);
-            }
-        };
+        double I[NA][NP], Imax[NA][NP], Ak[NA][NP], Ck[NA][NP], Dp[NA][NP], Dm[NA][NP];
         auto first_down = [&](auto fast_tag, int l, vec v) {
             constexpr bool FAST = decltype(fast_tag)::value;
             const double pbkT = A.pbkT[l], depth = A.depth[l];
@@ -5018,7 +4988,7 @@ __global__ __launch_bounds__(256) void surface_jacobian_kernel(const SurfaceJacA
             }
             add(3 + l, s_tau);
             add(3 + L + l, s_T);
-            terms(l, Gd);
+            jacobian_terms<NP>(A, l, j, active, Gd, 3 + 2 * L, add);
         };
         auto down = [&](auto fast_tag, int l, vec v) {
             constexpr bool FAST = decltype(fast_tag)::value;
@@ -5059,85 +5029,74 @@ __global__ __launch_bounds__(256) void surface_jacobian_kernel(const SurfaceJacA
             }
             add(3 + l, s_tau);
             add(3 + L + l, s_T);
-            terms(l, Gd);
+            jacobian_terms<NP>(A, l, j, active, Gd, 3 + 2 * L, add);
         };
-        auto walk = [&](auto fast_tag) {
-            // walk 1, downward: I_L = I_top or 0
+        // walk 1, downward: I_L = I_top or 0
 #pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double It = A.I_top ? A.I_top[j + p] : 0.0;
+        for (int p = 0; p < NP; ++p) {
+            const double It = A.I_top ? A.I_top[j + p] : 0.0;
 #pragma unroll
-                for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
-            }
-            vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-            for (int l = L - 1; l >= 0; --l) {
-                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-                first_down(fast_tag, l, cur);
-                cur = nxt;
-            }
-            // the surface: dF/dT_s = e sum_k W_k Ttot_k dBs/dT, dF/de = sum_k W_k Ttot_k (Is - R_k); then the state of walk 2
-            double s_Ts = 0.0, s_e = 0.0;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
-                double dBs = 0.0;
-                const double Is = A.I_surface ? A.I_surface[j + p]
-                                              : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
-                                                                         A.r_surface_T, &dBs);
-                const double edBs = e * dBs;
-                const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
-                const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
-                const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
-                const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
-                if (active && A.e_spec) A.e_spec[j + p] = de;
-                s_Ts += active ? nan_to_num(dTs) : 0.0;
-                s_e += active ? nan_to_num(de) : 0.0;
-#pragma unroll
-                for (int k = 0; k < NA; ++k) {
-                    const double D = I[k][p];
-                    I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
-                    Imax[k][p] = I[k][p];
-                    Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
-                    Ck[k][p] = 1.0;
-                    Dp[k][p] = -D;
-                }
-            }
-            add(1, s_Ts);
-            add(2, s_e);
-            // walk 2, upward
-            cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
-            for (int l = 0; l < L; ++l) {
-                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
-                up(fast_tag, l, cur);
-                cur = nxt;
-            }
-            // F_top; then I becomes D = -I_top and A = 1
-            double s = 0.0;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
-#pragma unroll
-                for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
-            }
-            add(0, s);
-            // walk 3, downward: K5d's
-            cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-            for (int l = L - 1; l >= 0; --l) {
-                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-                down(fast_tag, l, cur);
-                cur = nxt;
-            }
-        };
-        if constexpr (NP > 1) {
-            if (fast) walk(std::true_type{});
-            else walk(std::false_type{});
-        } else {
-            walk(std::false_type{});
+            for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
         }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < nv; t += blockDim.x)
-        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+        vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+        for (int l = L - 1; l >= 0; --l) {
+            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+            first_down(fast_tag, l, cur);
+            cur = nxt;
+        }
+        // the surface: dF/dT_s = e sum_k W_k Ttot_k dBs/dT, dF/de = sum_k W_k Ttot_k (Is - R_k); then the state of walk 2
+        double s_Ts = 0.0, s_e = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+            double dBs = 0.0;
+            const double Is = A.I_surface ? A.I_surface[j + p]
+                                          : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
+                                                                     A.r_surface_T, &dBs);
+            const double edBs = e * dBs;
+            const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
+            const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
+            const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
+            const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
+            if (active && A.e_spec) A.e_spec[j + p] = de;
+            s_Ts += active ? nan_to_num(dTs) : 0.0;
+            s_e += active ? nan_to_num(de) : 0.0;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) {
+                const double D = I[k][p];
+                I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
+                Imax[k][p] = I[k][p];
+                Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
+                Ck[k][p] = 1.0;
+                Dp[k][p] = -D;
+            }
+        }
+        add(1, s_Ts);
+        add(2, s_e);
+        // walk 2, upward
+        cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+        for (int l = 0; l < L; ++l) {
+            const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+            up(fast_tag, l, cur);
+            cur = nxt;
+        }
+        // F_top; then I becomes D = -I_top and A = 1
+        double s = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
+        }
+        add(0, s);
+        // walk 3, downward: K5d's
+        cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+        for (int l = L - 1; l >= 0; --l) {
+            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+            down(fast_tag, l, cur);
+            cur = nxt;
+        }
+    });
 }
 
 // Rays: K5f's kernel with K5g's surface in the path.  A marker (layer kRaySurfaceMarker) is part of the bundle's common
@@ -5153,89 +5112,48 @@ __global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurf
 #pragma clang fp contract(off)
     typedef f64v<NP> vec;
     const RaySurfaceJacArgs& A = *Ap;
-    const char* blk = (const char*)Ap;
-    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
-    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
-    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
-    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
-    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
-    const long long* __restrict__ row_first = (const long long*)(blk + A.off_row_first);
-    // (idle lanes of the last workgroup work on a valid point and store nothing)
-    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
-    const bool active = q < n0 + n1;
-    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
-    double nu[NP], pa_n[NP], Is[NP], em[NP], I[RB][NP], Imax[RB][NP], Ak[RB][NP];     // (Ak: S = dI/de on the forward walk)
-    column_points<NP>(A, j, nu, pa_n);
-    const bool fast = fold_fast_path<NP>(A, nu, active);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
-        em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
-    }
-    int rid[RB], s0[RB];
-    bool surface[RB];
+    const RayFrame<NP, RB, true, RaySurfaceJacArgs> F(Ap, blockDim.x, lo0, n0, lo1, n1, order_first);
+    const long long* row_first = (const long long*)(F.blk + A.off_row_first);
+    double I[RB][NP], Imax[RB][NP], Ak[RB][NP];          // (Ak: S = dI/de on the forward walk)
     long long row0[RB];                                   // the ray's first row
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
-        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
-        s0[i] = ray_first[rid[i]];
-        surface[i] = source_kind[rid[i]] == 1;
-        row0[i] = row_first[rid[i]];
+        row0[i] = row_first[F.rid[i]];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            I[i][p] = surface[i] ? surface_leaving(em[p], Is[p], 0.0) : 0.0;
+            I[i][p] = F.surface[i] ? surface_leaving(F.em[p], F.Is[p], 0.0) : 0.0;
             Imax[i][p] = I[i][p];
-            Ak[i][p] = surface[i] ? Is[p] : 0.0;
+            Ak[i][p] = F.surface[i] ? F.Is[p] : 0.0;
         }
     }
-    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers and rows)
-    const int32_t* lay = seg_layer + s0[0];
-    const int32_t* slot = (const int32_t*)(blk + A.off_seg_slot) + s0[0];
-    const int32_t* term_row = (const int32_t*)(blk + A.off_term_row) + ((const int32_t*)(blk + A.off_ray_terms))[rid[0]];
-    const int crossed = ((const int32_t*)(blk + A.off_ray_crossed))[rid[0]];
+    const int32_t* slot = (const int32_t*)(F.blk + A.off_seg_slot) + F.s0[0];
+    const int32_t* term_row = (const int32_t*)(F.blk + A.off_term_row) + ((const int32_t*)(F.blk + A.off_ray_terms))[F.rid[0]];
+    const int crossed = ((const int32_t*)(F.blk + A.off_ray_crossed))[F.rid[0]];
     auto put = [&](int i, long long row, int p, double v, bool store) {
-        double* o = A.jac + (row0[i] + row) * A.n + (j + p);
+        double* o = A.jac + (row0[i] + row) * A.n + (F.j + p);
         *o = store ? v : *o + v;
     };
     // e dB(nu, source_T)/dT at point p (0 when the source is a given spectrum)
     auto source_dT = [&](int p) {
         double dBs = 0.0;
-        if (!A.I_surface) fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
-        return em[p] * dBs;
+        if (!A.I_surface) fold_planck<false, true>(false, F.nu[p], F.nu[p], F.pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
+        return F.em[p] * dBs;
     };
-    // the nearest real segment at or after s / at or before s (ns / -1: none)
-    auto real_from = [&](int s) {
-        while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
-        return s;
-    };
-    auto real_back = [&](int s) {
-        while (s >= 0 && lay[s] == kRaySurfaceMarker) --s;
-        return s;
-    };
-    auto walk = [&](auto fast_tag) {
+    F.dispatch([&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
         // forward: ray_surface_kernel's walk, the running maximum and dI/de
-        int ahead = real_from(0);
-        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
-        for (int s = 0; s < ns; ++s) {
-            if (lay[s] == kRaySurfaceMarker) {
+        F.forward([&] {
 #pragma unroll
-                for (int i = 0; i < RB; ++i) {
+            for (int i = 0; i < RB; ++i) {
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        Ak[i][p] = (Is[p] - I[i][p]) + (1.0 - em[p]) * Ak[i][p];
-                        I[i][p] = surface_leaving(em[p], Is[p], I[i][p]);
-                        Imax[i][p] = fmax(Imax[i][p], I[i][p]);
-                    }
+                for (int p = 0; p < NP; ++p) {
+                    Ak[i][p] = (F.Is[p] - I[i][p]) + (1.0 - F.em[p]) * Ak[i][p];
+                    I[i][p] = surface_leaving(F.em[p], F.Is[p], I[i][p]);
+                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
                 }
-                continue;
             }
-            ahead = real_from(s + 1);
-            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
-            double len[RB];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
-            transport_step<FAST, NP>(nu, pa_n, A.pbkT[lay[s]], cur, [&](int p, double kp, double B) {
+        }, [&](int s, vec cur, const double (&len)[RB]) {
+            transport_step<FAST, NP>(F.nu, F.pa_n, A.pbkT[F.lay[s]], cur, [&](int p, double kp, double B) {
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
                     const double tr = exp_neg_budget(kp * len[i]);
@@ -5244,55 +5162,46 @@ __global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurf
                     Ak[i][p] = tr * Ak[i][p];
                 }
             });
-            cur = nxt;
-        }
+        });
         // the radiance and dI/de; then I becomes D = -I_final and A = 1
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                if (active && A.radiance) A.radiance[(long long)rid[i] * A.n + j + p] = I[i][p];
-                if (active) put(i, 1, p, Ak[i][p], true);
+                if (F.active && A.radiance) A.radiance[(long long)F.rid[i] * A.n + F.j + p] = I[i][p];
+                if (F.active) put(i, 1, p, Ak[i][p], true);
                 I[i][p] = -I[i][p];
                 Ak[i][p] = 1.0;
             }
         }
         // backward
         bool row0_stored = false;
-        int behind = real_back(ns - 1);
-        cur = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : (vec)(0.0);
-        for (int s = ns - 1; s >= 0; --s) {
-            if (lay[s] == kRaySurfaceMarker) {
+        F.backward([&] {
 #pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    const double edBs = A.I_surface ? 0.0 : source_dT(p);
-                    const double eIs = em[p] * Is[p];
+            for (int p = 0; p < NP; ++p) {
+                const double edBs = A.I_surface ? 0.0 : source_dT(p);
+                const double eIs = F.em[p] * F.Is[p];
 #pragma unroll
-                    for (int i = 0; i < RB; ++i) {
-                        if (active && !A.I_surface) put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
-                        I[i][p] = I[i][p] + Ak[i][p] * eIs;
-                        Ak[i][p] = Ak[i][p] * (1.0 - em[p]);
-                    }
+                for (int i = 0; i < RB; ++i) {
+                    if (F.active && !A.I_surface) put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
+                    I[i][p] = I[i][p] + Ak[i][p] * eIs;
+                    Ak[i][p] = Ak[i][p] * (1.0 - F.em[p]);
                 }
-                if (!A.I_surface) row0_stored = true;
-                continue;
             }
-            behind = real_back(s - 1);
-            const vec nxt = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : cur;
-            const int l = lay[s];
+            if (!A.I_surface) row0_stored = true;
+        }, [&](int s, vec cur, const double (&len)[RB]) {
+            const int l = F.lay[s];
             const bool store = (slot[s] & kRayRowStore) != 0;
             const long long row_tau = 2 + (slot[s] & (kRayRowStore - 1));
             const long long row_T = row_tau + crossed;
             const double pbkT = A.pbkT[l], rT = A.rT[l];
-            double len[RB], g[RB][NP];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            double g[RB][NP];
             double E0 = 0.0;
-            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+            if (FAST) E0 = exp_clamped(F.nu[0] * pbkT);
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 double dB;
-                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
+                const double B = fold_planck<FAST, true>(p == 0, F.nu[p], F.nu[0], F.pa_n[p], pbkT, E0, rT, &dB);
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
                     const double tau = cur[p] * len[i];
@@ -5300,7 +5209,7 @@ __global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurf
                     const double At = Ak[i][p] * tr;
                     g[i][p] = fmin(fmax(Ak[i][p] * B + I[i][p], -(At * Imax[i][p])), At * B);
                     const double a1 = Ak[i][p] * (1.0 - tr);
-                    if (active) {
+                    if (F.active) {
                         put(i, row_tau, p, tau * g[i][p], store);
                         put(i, row_T, p, a1 * dB, store);
                     }
@@ -5309,9 +5218,9 @@ __global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurf
                 }
             }
             if constexpr (TERMS) for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load_points<NP>(A.term_k[t], j);
+                const vec km = load_points<NP>(A.term_k[t], F.j);
                 const long long row = term_row[t];
-                if (active) {
+                if (F.active) {
 #pragma unroll
                     for (int i = 0; i < RB; ++i) {
 #pragma unroll
@@ -5319,27 +5228,20 @@ __global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurf
                     }
                 }
             }
-            cur = nxt;
-        }
+        });
         // the source's part of dI/dT_source: A_0 e dBs/dT for a ray from the surface at source_T
-        if (active) {
+        if (F.active) {
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const double edBs = source_dT(p);
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
-                    const double v = surface[i] && !A.I_surface ? Ak[i][p] * edBs : 0.0;
-                    if (!row0_stored || surface[i]) put(i, 0, p, v, !row0_stored);
+                    const double v = F.surface[i] && !A.I_surface ? Ak[i][p] * edBs : 0.0;
+                    if (!row0_stored || F.surface[i]) put(i, 0, p, v, !row0_stored);
                 }
             }
         }
-    };
-    if constexpr (NP > 1) {
-        if (fast) walk(std::true_type{});
-        else walk(std::false_type{});
-    } else {
-        walk(std::false_type{});
-    }
+    });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -5383,34 +5285,10 @@ __global__ __launch_bounds__(256) void linear_jacobian_kernel(const LinearJacArg
     const LinearJacArgs& A = *Ap;
     const int L = A.n_layers;
     const int nv = 3 + 3 * L + A.n_terms;
-    for (int t = threadIdx.x; t < 4 * kSlot; t += blockDim.x) acc[t] = 0.0;
-    __syncthreads();
-    double* my = acc + (threadIdx.x >> 6) * kSlot;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    auto add = [&](int slot, double s) {
-        s = wave_sum(s);
-        if (lane0) my[slot] += s;
-    };
-    const long long total = n0 + n1;
-    const long long stride = (long long)gridDim.x * blockDim.x * NP;
-    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions, idle lanes on a valid point)
-    for (long long q0 = (long long)blockIdx.x * blockDim.x * NP; q0 < total; q0 += stride) {
-        const long long q = q0 + (long long)threadIdx.x * NP;
-        const bool active = q < total;
-        const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
+    band_frame<NP, kSlot>(A, blockDim.x, lo0, n0, lo1, n1, partial, acc, nv, [&](auto fast_tag, long long j, bool active,
+                          const double (&nu)[NP], const double (&pa_n)[NP], auto add) __attribute__((always_inline)) {
         // walk 1: I = Id, Dm = Dmax, Ak = Ttot;  walk 2: I = Iu, Imax, Ck = C, Dp = D', Dm, Ak = Qf;  walk 3: I = D, Imax, Ak = A
-        double nu[NP], pa_n[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP], Ck[NA][NP], Dp[NA][NP], Dm[NA][NP];
-        column_points<NP>(A, j, nu, pa_n);
-        const bool fast = fold_fast_path<NP>(A, nu, active);
-        auto terms = [&](int l, const double (&Gd)[NP]) {
-            for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load_points<NP>(A.term_k[t], j);
-                double s = 0.0;
-#pragma unroll
-                for (int p = 0; p < NP; ++p) s += active ? nan_to_num(km[p] * Gd[p]) : 0.0;
-                add(3 + 3 * L + A.term_slot[t], s);
-            }
-        };
+        double I[NA][NP], Imax[NA][NP], Ak[NA][NP], Ck[NA][NP], Dp[NA][NP], Dm[NA][NP];
         // one point's values of a layer into the spectra (walk 2 stores, walk 3 adds) and the thread's sums
         auto emit = [&](bool store, int l, int p, double dtau, double gbot, double gtop, double& s_tau, double& s_bot,
                         double& s_top) __attribute__((always_inline)) {
@@ -5484,7 +5362,7 @@ __global__ __launch_bounds__(256) void linear_jacobian_kernel(const LinearJacArg
             add(3 + l, s_tau);
             add(3 + L + 2 * l, s_bot);
             add(3 + L + 2 * l + 1, s_top);
-            terms(l, Gd);
+            jacobian_terms<NP>(A, l, j, active, Gd, 3 + 3 * L, add);
         };
         auto down = [&](auto fast_tag, int l, vec v) __attribute__((always_inline)) {
             constexpr bool FAST = decltype(fast_tag)::value;
@@ -5523,85 +5401,74 @@ __global__ __launch_bounds__(256) void linear_jacobian_kernel(const LinearJacArg
             add(3 + l, s_tau);
             add(3 + L + 2 * l, s_bot);
             add(3 + L + 2 * l + 1, s_top);
-            terms(l, Gd);
+            jacobian_terms<NP>(A, l, j, active, Gd, 3 + 3 * L, add);
         };
-        auto walk = [&](auto fast_tag) __attribute__((always_inline)) {
-            // walk 1, downward: I_L = I_top or 0
+        // walk 1, downward: I_L = I_top or 0
 #pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double It = A.I_top ? A.I_top[j + p] : 0.0;
+        for (int p = 0; p < NP; ++p) {
+            const double It = A.I_top ? A.I_top[j + p] : 0.0;
 #pragma unroll
-                for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
-            }
-            vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-            for (int l = L - 1; l >= 0; --l) {
-                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-                first_down(fast_tag, l, cur);
-                cur = nxt;
-            }
-            // the surface: K5h's
-            double s_Ts = 0.0, s_e = 0.0;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
-                double dBs = 0.0;
-                const double Is = A.I_surface ? A.I_surface[j + p]
-                                              : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
-                                                                         A.r_surface_T, &dBs);
-                const double edBs = e * dBs;
-                const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
-                const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
-                const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
-                const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
-                if (active && A.e_spec) A.e_spec[j + p] = de;
-                s_Ts += active ? nan_to_num(dTs) : 0.0;
-                s_e += active ? nan_to_num(de) : 0.0;
-#pragma unroll
-                for (int k = 0; k < NA; ++k) {
-                    const double D = I[k][p];
-                    I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
-                    Imax[k][p] = I[k][p];
-                    Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
-                    Ck[k][p] = 1.0;
-                    Dp[k][p] = -D;
-                }
-            }
-            add(1, s_Ts);
-            add(2, s_e);
-            // walk 2, upward
-            cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
-            for (int l = 0; l < L; ++l) {
-                const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
-                up(fast_tag, l, cur);
-                cur = nxt;
-            }
-            // F_top; then I becomes D = -I_top and A = 1
-            double s = 0.0;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
-#pragma unroll
-                for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
-            }
-            add(0, s);
-            // walk 3, downward
-            cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-            for (int l = L - 1; l >= 0; --l) {
-                const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-                down(fast_tag, l, cur);
-                cur = nxt;
-            }
-        };
-        if constexpr (NP > 1) {
-            if (fast) walk(std::true_type{});
-            else walk(std::false_type{});
-        } else {
-            walk(std::false_type{});
+            for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
         }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < nv; t += blockDim.x)
-        partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
+        vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+        for (int l = L - 1; l >= 0; --l) {
+            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+            first_down(fast_tag, l, cur);
+            cur = nxt;
+        }
+        // the surface: K5h's
+        double s_Ts = 0.0, s_e = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+            double dBs = 0.0;
+            const double Is = A.I_surface ? A.I_surface[j + p]
+                                          : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
+                                                                     A.r_surface_T, &dBs);
+            const double edBs = e * dBs;
+            const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
+            const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
+            const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
+            const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
+            if (active && A.e_spec) A.e_spec[j + p] = de;
+            s_Ts += active ? nan_to_num(dTs) : 0.0;
+            s_e += active ? nan_to_num(de) : 0.0;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) {
+                const double D = I[k][p];
+                I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
+                Imax[k][p] = I[k][p];
+                Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
+                Ck[k][p] = 1.0;
+                Dp[k][p] = -D;
+            }
+        }
+        add(1, s_Ts);
+        add(2, s_e);
+        // walk 2, upward
+        cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+        for (int l = 0; l < L; ++l) {
+            const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+            up(fast_tag, l, cur);
+            cur = nxt;
+        }
+        // F_top; then I becomes D = -I_top and A = 1
+        double s = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
+        }
+        add(0, s);
+        // walk 3, downward
+        cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+        for (int l = L - 1; l >= 0; --l) {
+            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+            down(fast_tag, l, cur);
+            cur = nxt;
+        }
+    });
 }
 
 // Rays: ray_surface_jacobian_kernel's walks with linear_ray_kernel's step.  Forward every operation on I is
@@ -5615,91 +5482,50 @@ __global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRa
 #pragma clang fp contract(off)
     typedef f64v<NP> vec;
     const LinearRayJacArgs& A = *Ap;
-    const char* blk = (const char*)Ap;
-    const int32_t* __restrict__ ray_first = (const int32_t*)(blk + A.off_ray_first);
-    const int32_t* __restrict__ seg_layer = (const int32_t*)(blk + A.off_seg_layer);
-    const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
-    const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
-    const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
-    const long long* __restrict__ row_first = (const long long*)(blk + A.off_row_first);
-    // (idle lanes of the last workgroup work on a valid point and store nothing)
-    const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
-    const bool active = q < n0 + n1;
-    const long long j = !active ? lo0 : (q < n0 ? lo0 + q : lo1 + (q - n0));
-    double nu[NP], pa_n[NP], Is[NP], em[NP], I[RB][NP], Imax[RB][NP], Ak[RB][NP];     // (Ak: S = dI/de on the forward walk)
-    column_points<NP>(A, j, nu, pa_n);
-    const bool fast = fold_fast_path<NP>(A, nu, active);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
-        em[p] = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
-    }
-    int rid[RB], s0[RB];
-    bool surface[RB];
+    const RayFrame<NP, RB, true, LinearRayJacArgs> F(Ap, blockDim.x, lo0, n0, lo1, n1, order_first);
+    const long long* row_first = (const long long*)(F.blk + A.off_row_first);
+    double I[RB][NP], Imax[RB][NP], Ak[RB][NP];          // (Ak: S = dI/de on the forward walk)
     long long row0[RB];                                   // the ray's first row
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
-        rid[i] = order[order_first + (int)blockIdx.y * RB + i];
-        s0[i] = ray_first[rid[i]];
-        surface[i] = source_kind[rid[i]] == 1;
-        row0[i] = row_first[rid[i]];
+        row0[i] = row_first[F.rid[i]];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            I[i][p] = surface[i] ? surface_leaving(em[p], Is[p], 0.0) : 0.0;
+            I[i][p] = F.surface[i] ? surface_leaving(F.em[p], F.Is[p], 0.0) : 0.0;
             Imax[i][p] = I[i][p];
-            Ak[i][p] = surface[i] ? Is[p] : 0.0;
+            Ak[i][p] = F.surface[i] ? F.Is[p] : 0.0;
         }
     }
-    const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers and rows)
-    const int32_t* lay = seg_layer + s0[0];
-    const double* pbk = (const double*)(blk + A.off_seg_pbkT) + 2 * (long long)s0[0];
-    const double* srT = (const double*)(blk + A.off_seg_rT) + 2 * (long long)s0[0];
-    const int32_t* slot = (const int32_t*)(blk + A.off_seg_slot) + s0[0];
-    const int32_t* Trow = (const int32_t*)(blk + A.off_seg_Trow) + s0[0];
-    const int32_t* term_row = (const int32_t*)(blk + A.off_term_row) + ((const int32_t*)(blk + A.off_ray_terms))[rid[0]];
+    const double* pbk = (const double*)(F.blk + A.off_seg_pbkT) + 2 * (long long)F.s0[0];
+    const double* srT = (const double*)(F.blk + A.off_seg_rT) + 2 * (long long)F.s0[0];
+    const int32_t* slot = (const int32_t*)(F.blk + A.off_seg_slot) + F.s0[0];
+    const int32_t* Trow = (const int32_t*)(F.blk + A.off_seg_Trow) + F.s0[0];
+    const int32_t* term_row = (const int32_t*)(F.blk + A.off_term_row) + ((const int32_t*)(F.blk + A.off_ray_terms))[F.rid[0]];
     auto put = [&](int i, long long row, int p, double v, bool store) {
-        double* o = A.jac + (row0[i] + row) * A.n + (j + p);
+        double* o = A.jac + (row0[i] + row) * A.n + (F.j + p);
         *o = store ? v : *o + v;
     };
     // e dB(nu, source_T)/dT at point p (0 when the source is a given spectrum)
     auto source_dT = [&](int p) {
         double dBs = 0.0;
-        if (!A.I_surface) fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
-        return em[p] * dBs;
+        if (!A.I_surface) fold_planck<false, true>(false, F.nu[p], F.nu[p], F.pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
+        return F.em[p] * dBs;
     };
-    // the nearest real segment at or after s / at or before s (ns / -1: none)
-    auto real_from = [&](int s) {
-        while (s < ns && lay[s] == kRaySurfaceMarker) ++s;
-        return s;
-    };
-    auto real_back = [&](int s) {
-        while (s >= 0 && lay[s] == kRaySurfaceMarker) --s;
-        return s;
-    };
-    auto walk = [&](auto fast_tag) {
+    F.dispatch([&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
         // forward: linear_ray_kernel's walk, the running maximum and dI/de
-        int ahead = real_from(0);
-        vec cur = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : (vec)(0.0);
-        for (int s = 0; s < ns; ++s) {
-            if (lay[s] == kRaySurfaceMarker) {
+        F.forward([&] {
 #pragma unroll
-                for (int i = 0; i < RB; ++i) {
+            for (int i = 0; i < RB; ++i) {
 #pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        Ak[i][p] = (Is[p] - I[i][p]) + (1.0 - em[p]) * Ak[i][p];
-                        I[i][p] = surface_leaving(em[p], Is[p], I[i][p]);
-                        Imax[i][p] = fmax(Imax[i][p], I[i][p]);
-                    }
+                for (int p = 0; p < NP; ++p) {
+                    Ak[i][p] = (F.Is[p] - I[i][p]) + (1.0 - F.em[p]) * Ak[i][p];
+                    I[i][p] = surface_leaving(F.em[p], F.Is[p], I[i][p]);
+                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
                 }
-                continue;
             }
-            ahead = real_from(s + 1);
-            const vec nxt = ahead < ns ? load_points<NP>(A.abs_coef[lay[ahead]], j) : cur;
-            double len[RB];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
-            linear_step<FAST, NP>(nu, pa_n, pbk[2 * s], pbk[2 * s + 1], cur, [&](int p, double kp, double Ba, double dB) {
+        }, [&](int s, vec cur, const double (&len)[RB]) {
+            linear_step<FAST, NP>(F.nu, F.pa_n, pbk[2 * s], pbk[2 * s + 1], cur, [&](int p, double kp, double Ba, double dB) {
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
                     const double tau = kp * len[i];
@@ -5709,58 +5535,49 @@ __global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRa
                     Ak[i][p] = tr * Ak[i][p];
                 }
             });
-            cur = nxt;
-        }
+        });
         // the radiance and dI/de; then I becomes D = -I_final and A = 1
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                if (active && A.radiance) A.radiance[(long long)rid[i] * A.n + j + p] = I[i][p];
-                if (active) put(i, 1, p, Ak[i][p], true);
+                if (F.active && A.radiance) A.radiance[(long long)F.rid[i] * A.n + F.j + p] = I[i][p];
+                if (F.active) put(i, 1, p, Ak[i][p], true);
                 I[i][p] = -I[i][p];
                 Ak[i][p] = 1.0;
             }
         }
         // backward
         bool row0_stored = false;
-        int behind = real_back(ns - 1);
-        cur = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : (vec)(0.0);
-        for (int s = ns - 1; s >= 0; --s) {
-            if (lay[s] == kRaySurfaceMarker) {
+        F.backward([&] {
 #pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    const double edBs = A.I_surface ? 0.0 : source_dT(p);
-                    const double eIs = em[p] * Is[p];
+            for (int p = 0; p < NP; ++p) {
+                const double edBs = A.I_surface ? 0.0 : source_dT(p);
+                const double eIs = F.em[p] * F.Is[p];
 #pragma unroll
-                    for (int i = 0; i < RB; ++i) {
-                        if (active && !A.I_surface) put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
-                        I[i][p] = I[i][p] + Ak[i][p] * eIs;
-                        Ak[i][p] = Ak[i][p] * (1.0 - em[p]);
-                    }
+                for (int i = 0; i < RB; ++i) {
+                    if (F.active && !A.I_surface) put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
+                    I[i][p] = I[i][p] + Ak[i][p] * eIs;
+                    Ak[i][p] = Ak[i][p] * (1.0 - F.em[p]);
                 }
-                if (!A.I_surface) row0_stored = true;
-                continue;
             }
-            behind = real_back(s - 1);
-            const vec nxt = behind >= 0 ? load_points<NP>(A.abs_coef[lay[behind]], j) : cur;
-            const int l = lay[s];
+            if (!A.I_surface) row0_stored = true;
+        }, [&](int s, vec cur, const double (&len)[RB]) {
+            const int l = F.lay[s];
             const bool store = (slot[s] & kRayRowStore) != 0;
             const long long row_tau = 2 + (slot[s] & (kRayRowStore - 1));
             const long long row_Ta = Trow[s];
             const double pbkT_a = pbk[2 * s], pbkT_b = pbk[2 * s + 1], rT_a = srT[2 * s], rT_b = srT[2 * s + 1];
-            double len[RB], G[RB][NP];
-#pragma unroll
-            for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
+            double G[RB][NP];
             double Ea0 = 0.0, Eb0 = 0.0;
             if (FAST) {
-                Ea0 = exp_clamped(nu[0] * pbkT_a);
-                Eb0 = exp_clamped(nu[0] * pbkT_b);
+                Ea0 = exp_clamped(F.nu[0] * pbkT_a);
+                Eb0 = exp_clamped(F.nu[0] * pbkT_b);
             }
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 double Ba, Bb, dBa, dBb;
-                linear_planck_pair<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT_a, pbkT_b, Ea0, Eb0, rT_a, rT_b, Ba, Bb, dBa, dBb);
+                linear_planck_pair<FAST>(p == 0, F.nu[p], F.nu[0], F.pa_n[p], pbkT_a, pbkT_b, Ea0, Eb0, rT_a, rT_b, Ba, Bb, dBa, dBb);
                 const double dB = Bb - Ba;
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
@@ -5771,7 +5588,7 @@ __global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRa
                     const double At = Ak[i][p] * tr;
                     const double gc = fmin(fmax(Ak[i][p] * (Ba + g * dB) + I[i][p], -(At * Imax[i][p])), At * Ba);
                     G[i][p] = gc + Ak[i][p] * (dg * dB);
-                    if (active) {
+                    if (F.active) {
                         put(i, row_tau, p, tau * G[i][p], store);
                         put(i, row_Ta, p, (Ak[i][p] * (tau * dg)) * dBa, true);
                         put(i, row_Ta + 1, p, (Ak[i][p] * g) * dBb, true);
@@ -5781,9 +5598,9 @@ __global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRa
                 }
             }
             for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load_points<NP>(A.term_k[t], j);
+                const vec km = load_points<NP>(A.term_k[t], F.j);
                 const long long row = term_row[t];
-                if (active) {
+                if (F.active) {
 #pragma unroll
                     for (int i = 0; i < RB; ++i) {
 #pragma unroll
@@ -5791,27 +5608,20 @@ __global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRa
                     }
                 }
             }
-            cur = nxt;
-        }
+        });
         // the source's part of dI/dT_source: A_0 e dBs/dT for a ray from the surface at source_T
-        if (active) {
+        if (F.active) {
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const double edBs = source_dT(p);
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
-                    const double v = surface[i] && !A.I_surface ? Ak[i][p] * edBs : 0.0;
-                    if (!row0_stored || surface[i]) put(i, 0, p, v, !row0_stored);
+                    const double v = F.surface[i] && !A.I_surface ? Ak[i][p] * edBs : 0.0;
+                    if (!row0_stored || F.surface[i]) put(i, 0, p, v, !row0_stored);
                 }
             }
         }
-    };
-    if constexpr (NP > 1) {
-        if (fast) walk(std::true_type{});
-        else walk(std::false_type{});
-    } else {
-        walk(std::false_type{});
-    }
+    });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -6284,8 +6094,14 @@ void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, i
 
 // K5e: the aligned groups of 4 points for the bundles of kRayBundle rays (order[0 .. kRayBundle n_bundles)) and then for the
 // single rays behind them, the head and tail points (at most 6) for every ray on its own in one 64-lane workgroup each; the
-// split of the points is launch_column_band's.  No grid-stride bound: nothing here is sized by the grid.
-void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s) {
+// split of the points is launch_column_band's.  No grid-stride bound: nothing here is sized by the grid.  One split for
+// every ray kernel (K5e - K5j): `bundle` is its <4, kRayBundle>, `single` its <4, 1> and `tail` its <1, 1> instantiation.
+template <class Args>
+using RayKernel = void (*)(const Args*, long long, long long, long long, long long, int);
+
+template <class Args>
+static void launch_ray_split(RayKernel<Args> bundle, RayKernel<Args> single, RayKernel<Args> tail, const Args* d_args,
+                             long long n, int n_rays, int n_bundles, hipStream_t s) {
     constexpr int NP = 4;
     if (n <= 0 || n_rays <= 0) return;
     const long long q1 = n & ~(long long)(NP - 1);
@@ -6294,34 +6110,22 @@ void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_b
     if (q1 > 0) {
         const unsigned blocks = (unsigned)((q1 / NP + 255) / 256);
         if (n_bundles > 0)
-            hipLaunchKernelGGL((ray_radiance_kernel<NP, kRayBundle>), dim3(blocks, n_bundles), dim3(256), 0, s, d_args, 0LL, q1,
-                               0LL, 0LL, 0);
+            hipLaunchKernelGGL(bundle, dim3(blocks, n_bundles), dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL, 0);
         if (n_single > 0)
-            hipLaunchKernelGGL((ray_radiance_kernel<NP, 1>), dim3(blocks, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL,
-                               kRayBundle * n_bundles);
+            hipLaunchKernelGGL(single, dim3(blocks, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL, kRayBundle * n_bundles);
     }
-    if (nt > 0)
-        hipLaunchKernelGGL((ray_radiance_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+    if (nt > 0) hipLaunchKernelGGL(tail, dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+}
+
+void launch_ray_radiance(const RayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s) {
+    launch_ray_split<RayArgs>(ray_radiance_kernel<4, kRayBundle>, ray_radiance_kernel<4, 1>, ray_radiance_kernel<1, 1>, d_args, n,
+                              n_rays, n_bundles, s);
 }
 
 // K5g: launch_ray_radiance's split of the points and of the rays for the kernel that knows surface markers
 void launch_ray_surface(const RaySurfaceArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s) {
-    constexpr int NP = 4;
-    if (n <= 0 || n_rays <= 0) return;
-    const long long q1 = n & ~(long long)(NP - 1);
-    const long long nt = n - q1;
-    const int n_single = n_rays - kRayBundle * n_bundles;
-    if (q1 > 0) {
-        const unsigned blocks = (unsigned)((q1 / NP + 255) / 256);
-        if (n_bundles > 0)
-            hipLaunchKernelGGL((ray_surface_kernel<NP, kRayBundle>), dim3(blocks, n_bundles), dim3(256), 0, s, d_args, 0LL, q1,
-                               0LL, 0LL, 0);
-        if (n_single > 0)
-            hipLaunchKernelGGL((ray_surface_kernel<NP, 1>), dim3(blocks, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL,
-                               kRayBundle * n_bundles);
-    }
-    if (nt > 0)
-        hipLaunchKernelGGL((ray_surface_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+    launch_ray_split<RaySurfaceArgs>(ray_surface_kernel<4, kRayBundle>, ray_surface_kernel<4, 1>, ray_surface_kernel<1, 1>, d_args,
+                                     n, n_rays, n_bundles, s);
 }
 
 // K5i: K5g's launches - 4 points per thread for every angle count and bundle size, so that with equal edge temperatures the
@@ -6336,22 +6140,8 @@ void launch_linear_flux(const LinearFluxArgs* d_args, int n_layers, int n_angles
 }
 
 void launch_linear_ray(const LinearRayArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s) {
-    constexpr int NP = 4;
-    if (n <= 0 || n_rays <= 0) return;
-    const long long q1 = n & ~(long long)(NP - 1);
-    const long long nt = n - q1;
-    const int n_single = n_rays - kRayBundle * n_bundles;
-    if (q1 > 0) {
-        const unsigned blocks = (unsigned)((q1 / NP + 255) / 256);
-        if (n_bundles > 0)
-            hipLaunchKernelGGL((linear_ray_kernel<NP, kRayBundle>), dim3(blocks, n_bundles), dim3(256), 0, s, d_args, 0LL, q1,
-                               0LL, 0LL, 0);
-        if (n_single > 0)
-            hipLaunchKernelGGL((linear_ray_kernel<NP, 1>), dim3(blocks, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL,
-                               kRayBundle * n_bundles);
-    }
-    if (nt > 0)
-        hipLaunchKernelGGL((linear_ray_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+    launch_ray_split<LinearRayArgs>(linear_ray_kernel<4, kRayBundle>, linear_ray_kernel<4, 1>, linear_ray_kernel<1, 1>, d_args, n,
+                                    n_rays, n_bundles, s);
 }
 
 // K5f: launch_ray_radiance's split of the points and of the rays (the radiance is K5e's bit for bit only on K5e's own groups
@@ -6359,23 +6149,8 @@ void launch_linear_ray(const LinearRayArgs* d_args, long long n, int n_rays, int
 // and point, 48 for a bundle, without scratch (DESIGN.md "K5f"); a call without terms takes the bundle kernel without the
 // term loop.
 void launch_ray_jacobian(const RayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms, hipStream_t s) {
-    constexpr int NP = 4;
-    if (n <= 0 || n_rays <= 0) return;
-    const long long q1 = n & ~(long long)(NP - 1);
-    const long long nt = n - q1;
-    const int n_single = n_rays - kRayBundle * n_bundles;
-    if (q1 > 0) {
-        const dim3 grid((unsigned)((q1 / NP + 255) / 256), n_bundles);
-        if (n_bundles > 0 && n_terms > 0)
-            hipLaunchKernelGGL((ray_jacobian_kernel<NP, kRayBundle, true>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL, 0);
-        else if (n_bundles > 0)
-            hipLaunchKernelGGL((ray_jacobian_kernel<NP, kRayBundle, false>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL, 0);
-        if (n_single > 0)
-            hipLaunchKernelGGL((ray_jacobian_kernel<NP, 1, true>), dim3(grid.x, n_single), dim3(256), 0, s, d_args, 0LL, q1, 0LL,
-                               0LL, kRayBundle * n_bundles);
-    }
-    if (nt > 0)
-        hipLaunchKernelGGL((ray_jacobian_kernel<1, 1, true>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+    launch_ray_split<RayJacArgs>(n_terms > 0 ? ray_jacobian_kernel<4, kRayBundle, true> : ray_jacobian_kernel<4, kRayBundle, false>,
+                                 ray_jacobian_kernel<4, 1, true>, ray_jacobian_kernel<1, 1, true>, d_args, n, n_rays, n_bundles, s);
 }
 
 // K5h: K5d's launch.  Points per thread: K5d's 4 for one and two angles (its groups of points, so that a black surface
@@ -6401,25 +6176,10 @@ void launch_surface_jacobian(const SurfaceJacArgs* d_args, int n_layers, int n_a
 // K5h: launch_ray_jacobian's split of the points and of the rays for the kernel that knows surface markers
 void launch_ray_surface_jacobian(const RaySurfaceJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
                                  hipStream_t s) {
-    constexpr int NP = 4;
-    if (n <= 0 || n_rays <= 0) return;
-    const long long q1 = n & ~(long long)(NP - 1);
-    const long long nt = n - q1;
-    const int n_single = n_rays - kRayBundle * n_bundles;
-    if (q1 > 0) {
-        const dim3 grid((unsigned)((q1 / NP + 255) / 256), n_bundles);
-        if (n_bundles > 0 && n_terms > 0)
-            hipLaunchKernelGGL((ray_surface_jacobian_kernel<NP, kRayBundle, true>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL,
-                               0LL, 0);
-        else if (n_bundles > 0)
-            hipLaunchKernelGGL((ray_surface_jacobian_kernel<NP, kRayBundle, false>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL,
-                               0LL, 0);
-        if (n_single > 0)
-            hipLaunchKernelGGL((ray_surface_jacobian_kernel<NP, 1, true>), dim3(grid.x, n_single), dim3(256), 0, s, d_args, 0LL,
-                               q1, 0LL, 0LL, kRayBundle * n_bundles);
-    }
-    if (nt > 0)
-        hipLaunchKernelGGL((ray_surface_jacobian_kernel<1, 1, true>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+    launch_ray_split<RaySurfaceJacArgs>(n_terms > 0 ? ray_surface_jacobian_kernel<4, kRayBundle, true>
+                                                    : ray_surface_jacobian_kernel<4, kRayBundle, false>,
+                                        ray_surface_jacobian_kernel<4, 1, true>, ray_surface_jacobian_kernel<1, 1, true>, d_args, n,
+                                        n_rays, n_bundles, s);
 }
 
 // K5j: K5h's launches.  The column's points per thread are linear_jacobian_np's; the rays keep K5i's groups of 4 points,
@@ -6443,21 +6203,8 @@ void launch_linear_jacobian(const LinearJacArgs* d_args, int n_layers, int n_ang
 
 void launch_linear_ray_jacobian(const LinearRayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
                                 hipStream_t s) {
-    constexpr int NP = 4;
-    if (n <= 0 || n_rays <= 0) return;
-    const long long q1 = n & ~(long long)(NP - 1);
-    const long long nt = n - q1;
-    const int n_single = n_rays - kRayBundle * n_bundles;
-    if (q1 > 0) {
-        const dim3 grid((unsigned)((q1 / NP + 255) / 256), n_bundles);
-        if (n_bundles > 0)
-            hipLaunchKernelGGL((ray_linear_jacobian_kernel<NP, kRayBundle>), grid, dim3(256), 0, s, d_args, 0LL, q1, 0LL, 0LL, 0);
-        if (n_single > 0)
-            hipLaunchKernelGGL((ray_linear_jacobian_kernel<NP, 1>), dim3(grid.x, n_single), dim3(256), 0, s, d_args, 0LL,
-                               q1, 0LL, 0LL, kRayBundle * n_bundles);
-    }
-    if (nt > 0)
-        hipLaunchKernelGGL((ray_linear_jacobian_kernel<1, 1>), dim3(1, n_rays), dim3(64), 0, s, d_args, q1, 0LL, q1, nt, 0);
+    launch_ray_split<LinearRayJacArgs>(ray_linear_jacobian_kernel<4, kRayBundle>, ray_linear_jacobian_kernel<4, 1>,
+                                       ray_linear_jacobian_kernel<1, 1>, d_args, n, n_rays, n_bundles, s);
 }
 
 void launch_line_survey(const double* nu, const double* sw, int n_lines, double range_min, double resolution,

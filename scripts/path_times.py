@@ -24,22 +24,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
 
-def event_ms(ctx, fn, reps, warmup=2):
-    """[ms] of fn() between two events recorded on the context's stream, `reps` times after `warmup` untimed calls"""
-    import torch
-    stream = torch.cuda.ExternalStream(ctx.stream())
-    for _ in range(warmup):
-        fn()
-    ctx.sync()
-    out = []
-    for _ in range(reps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record(stream)
-        fn()
-        t1.record(stream)
-        t1.synchronize()
-        out.append(t0.elapsed_time(t1))
-    return out
+from path_jacobian_times import event_ms  # noqa: E402  (HIP events on the context's stream, through ctypes)
 
 
 def leg(which, reps):
