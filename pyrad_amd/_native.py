@@ -654,6 +654,39 @@ class Context:
             return emissivity.h, 1.0
         return None, float(emissivity)
 
+    @staticmethod
+    def _edge_T(name, edge_T, abs_coef):
+        """``edge_T`` of the column_*_linear_dev wrapper ``name`` as 2 L numbers"""
+        edge_T = _as_f64(edge_T).reshape(-1)
+        if len(edge_T) != 2 * len(abs_coef):
+            raise ValueError("%s: two edge temperatures per layer" % name)
+        return edge_T
+
+    @staticmethod
+    def _term_args(term_abs_coef, term_layer):
+        """(count, buffers, layers) of the terms the column_jacobian_* and ray_jacobian_* entry points take"""
+        return len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]), _arr(C.c_int32, [int(l) for l in term_layer])
+
+    def _ray_args(self, name, abs_coef, T, range_min, range_max, n, ray_first, seg_layer, seg_length, source_kind, I_source,
+                  source_T, seg_T=False, terms=None):
+        """The leading arguments the lbl_ray_* entry points share, from ctx to source_T, behind the length checks of the
+        wrapper ``name``.  ``T``: the layers' temperatures or, with ``seg_T``, two per segment; ``terms``: None or a
+        Jacobian's (term_abs_coef, term_layer)."""
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
+        seg_length = _as_f64(seg_length)
+        if seg_T:
+            T = _as_f64(T).reshape(-1)
+        if (len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length)
+                or (seg_T and len(T) != 2 * len(seg_layer)) or (terms is not None and len(terms[0]) != len(terms[1]))):
+            raise ValueError("%s: one ray_first per ray and one more, one length%s per segment layer%s"
+                             % (name, " and two temperatures" if seg_T else "", "" if terms is None else ", one layer per term"))
+        return (self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]),
+                T.ctypes.data_as(_D) if seg_T else _arr(C.c_double, [float(t) for t in T]), float(range_min),
+                float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer), seg_length.ctypes.data_as(_D),
+                i32p(source_kind), _hb(I_source), float(source_T))
+
     def column_flux_surface_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                                 level_flux, emissivity, reflection=0, I_surface=None, surface_T=0.0, I_top=None, up_top=None,
                                 down_surface=None, up_surface=None):
@@ -672,12 +705,9 @@ class Context:
         """Level fluxes with a Planck source linear in optical depth (lbl_column_flux_linear_dev): column_flux_surface_dev's
         arguments and results with ``edge_T`` in place of the layers' temperatures - per layer (bottom edge, top edge), as L
         pairs or 2 L numbers.  The default ``emissivity`` 1 is the black surface."""
-        edge_T = _as_f64(edge_T).reshape(-1)
-        if len(edge_T) != 2 * len(abs_coef):
-            raise ValueError("column_flux_linear_dev: two edge temperatures per layer")
         self.check(self.lib.lbl_column_flux_linear_dev(
-            *self._column_args(abs_coef, edge_T, depth, range_min, range_max, n, I_surface, surface_T, (_hb(I_top),), mu,
-                               weight, band_first, band_count),
+            *self._column_args(abs_coef, self._edge_T("column_flux_linear_dev", edge_T, abs_coef), depth, range_min, range_max,
+                               n, I_surface, surface_T, (_hb(I_top),), mu, weight, band_first, band_count),
             *self._emissivity_args(emissivity), int(reflection), _hb(level_flux), _hb(up_top), _hb(down_surface),
             _hb(up_surface)))
 
@@ -745,8 +775,7 @@ class Context:
         self.check(self.lib.lbl_column_jacobian_dev(
             *self._column_args(abs_coef, layer_T, depth, range_min, range_max, n, I_surface, surface_T, (), mu, weight,
                                band_first, band_count),
-            len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]), _arr(C.c_int32, [int(l) for l in term_layer]),
-            _hb(jac), _hb(ln_tau_spectra), _hb(T_spectra)))
+            *self._term_args(term_abs_coef, term_layer), _hb(jac), _hb(ln_tau_spectra), _hb(T_spectra)))
 
     def column_jacobian_surface_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first,
                                     band_count, jac, emissivity, reflection=0, I_surface=None, surface_T=0.0, I_top=None,
@@ -758,8 +787,8 @@ class Context:
         self.check(self.lib.lbl_column_jacobian_surface_dev(
             *self._column_args(abs_coef, layer_T, depth, range_min, range_max, n, I_surface, surface_T, (_hb(I_top),), mu,
                                weight, band_first, band_count),
-            *self._emissivity_args(emissivity), int(reflection), len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]),
-            _arr(C.c_int32, [int(l) for l in term_layer]), _hb(jac), _hb(ln_tau_spectra), _hb(T_spectra), _hb(e_spectrum)))
+            *self._emissivity_args(emissivity), int(reflection), *self._term_args(term_abs_coef, term_layer), _hb(jac),
+            _hb(ln_tau_spectra), _hb(T_spectra), _hb(e_spectrum)))
 
     def column_jacobian_linear_dev(self, abs_coef, edge_T, depth, range_min, range_max, n, mu, weight, band_first,
                                    band_count, jac, emissivity=1.0, reflection=0, I_surface=None, surface_T=0.0, I_top=None,
@@ -771,15 +800,11 @@ class Context:
         3 L + len(term_abs_coef)) band sums [band][F, dF/dT_s, dF/de, L x dF/d ln tau, 2 L x dF/dT_edge (bottom, top per
         layer), terms]; ``T_edge_spectra`` (optional, 2 L x n points) the spectral edge values.  The default ``emissivity`` 1
         is the black surface."""
-        edge_T = _as_f64(edge_T).reshape(-1)
-        if len(edge_T) != 2 * len(abs_coef):
-            raise ValueError("column_jacobian_linear_dev: two edge temperatures per layer")
         self.check(self.lib.lbl_column_jacobian_linear_dev(
-            *self._column_args(abs_coef, edge_T, depth, range_min, range_max, n, I_surface, surface_T, (_hb(I_top),), mu,
-                               weight, band_first, band_count),
-            *self._emissivity_args(emissivity), int(reflection), len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]),
-            _arr(C.c_int32, [int(l) for l in term_layer]), _hb(jac), _hb(ln_tau_spectra), _hb(T_edge_spectra),
-            _hb(e_spectrum)))
+            *self._column_args(abs_coef, self._edge_T("column_jacobian_linear_dev", edge_T, abs_coef), depth, range_min,
+                               range_max, n, I_surface, surface_T, (_hb(I_top),), mu, weight, band_first, band_count),
+            *self._emissivity_args(emissivity), int(reflection), *self._term_args(term_abs_coef, term_layer), _hb(jac),
+            _hb(ln_tau_spectra), _hb(T_edge_spectra), _hb(e_spectrum)))
 
     def ray_radiance_dev(self, abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length, source_kind,
                          radiance, I_source=None, source_T=0.0, transmittance=None):
@@ -787,17 +812,10 @@ class Context:
         ray_first[r + 1] - 1 (``seg_layer``, ``seg_length`` in cm) in the order the light travels, from cold space
         (``source_kind`` 0) or the surface source (1: ``I_source`` or B(nu, ``source_T``)); ``radiance`` and the optional
         ``transmittance`` receive len(source_kind) x n doubles, row-major."""
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
-        seg_length = _as_f64(seg_length)
-        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length):
-            raise ValueError("ray_radiance_dev: one ray_first per ray and one more, one length per segment layer")
         self.check(self.lib.lbl_ray_radiance_dev(
-            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
-            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
-            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T), _hb(radiance),
-            _hb(transmittance)))
+            *self._ray_args("ray_radiance_dev", abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length,
+                            source_kind, I_source, source_T),
+            _hb(radiance), _hb(transmittance)))
 
     def ray_radiance_surface_dev(self, abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length,
                                  source_kind, radiance, emissivity, I_source=None, source_T=0.0, surface_down=None,
@@ -807,16 +825,9 @@ class Context:
         ``emissivity`` (a Buffer of n points or one number in [0, 1]); rays that start at the surface also carry the diffuse
         reflection of ``surface_down`` (optional, n points: a downward flux formed with weights that add up to
         ``surface_down_norm``)."""
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
-        seg_length = _as_f64(seg_length)
-        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length):
-            raise ValueError("ray_radiance_surface_dev: one ray_first per ray and one more, one length per segment layer")
         self.check(self.lib.lbl_ray_radiance_surface_dev(
-            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
-            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
-            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
+            *self._ray_args("ray_radiance_surface_dev", abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer,
+                            seg_length, source_kind, I_source, source_T),
             *self._emissivity_args(emissivity), _hb(surface_down), float(surface_down_norm), _hb(radiance),
             _hb(transmittance)))
 
@@ -827,18 +838,9 @@ class Context:
         ray_radiance_surface_dev's arguments and results with ``seg_T`` in place of the layers' temperatures - per segment
         (temperature where the light enters, where it leaves), as pairs or 2 numbers per segment; a marker's pair is
         ignored.  The default ``emissivity`` 1 is the black surface."""
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
-        seg_length = _as_f64(seg_length)
-        seg_T = _as_f64(seg_T).reshape(-1)
-        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length) or len(seg_T) != 2 * len(seg_layer):
-            raise ValueError("ray_radiance_linear_dev: one ray_first per ray and one more, one length and two temperatures "
-                             "per segment layer")
         self.check(self.lib.lbl_ray_radiance_linear_dev(
-            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), seg_T.ctypes.data_as(_D),
-            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
-            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
+            *self._ray_args("ray_radiance_linear_dev", abs_coef, seg_T, range_min, range_max, n, ray_first, seg_layer,
+                            seg_length, source_kind, I_source, source_T, seg_T=True),
             *self._emissivity_args(emissivity), _hb(surface_down), float(surface_down_norm), _hb(radiance),
             _hb(transmittance)))
 
@@ -848,18 +850,10 @@ class Context:
         them; ``jac`` receives ray_jacobian_rows(...) rows of n doubles - per ray [dI/dT_source, dI/d ln tau and dI/dT of
         every crossed layer, the terms in crossed layers] - and ``radiance`` (optional) len(source_kind) x n doubles;
         ``term_layer`` gives each term's layer."""
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
-        seg_length = _as_f64(seg_length)
-        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length) or len(term_abs_coef) != len(term_layer):
-            raise ValueError("ray_jacobian_dev: one ray_first per ray and one more, one length per segment layer, one layer "
-                             "per term")
         self.check(self.lib.lbl_ray_jacobian_dev(
-            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
-            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
-            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T), len(term_abs_coef),
-            _arr(_P, [b.h for b in term_abs_coef]), _arr(C.c_int32, [int(l) for l in term_layer]), _hb(radiance), _hb(jac)))
+            *self._ray_args("ray_jacobian_dev", abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length,
+                            source_kind, I_source, source_T, terms=(term_abs_coef, term_layer)),
+            *self._term_args(term_abs_coef, term_layer), _hb(radiance), _hb(jac)))
 
     def ray_jacobian_surface_dev(self, abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer, seg_length,
                                  source_kind, jac, emissivity, I_source=None, source_T=0.0, term_abs_coef=(), term_layer=(),
@@ -868,19 +862,10 @@ class Context:
         (lbl_ray_jacobian_surface_dev): ray_jacobian_dev's arguments with the markers and the ``emissivity`` of
         ray_radiance_surface_dev; ``jac`` receives ray_jacobian_rows(..., surface=True) rows of n doubles - per ray
         [dI/dT_source, dI/de, dI/d ln tau and dI/dT of every crossed layer, the terms in crossed layers]."""
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
-        seg_length = _as_f64(seg_length)
-        if len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length) or len(term_abs_coef) != len(term_layer):
-            raise ValueError("ray_jacobian_surface_dev: one ray_first per ray and one more, one length per segment layer, one "
-                             "layer per term")
         self.check(self.lib.lbl_ray_jacobian_surface_dev(
-            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in layer_T]),
-            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
-            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
-            *self._emissivity_args(emissivity), len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]),
-            _arr(C.c_int32, [int(l) for l in term_layer]), _hb(radiance), _hb(jac)))
+            *self._ray_args("ray_jacobian_surface_dev", abs_coef, layer_T, range_min, range_max, n, ray_first, seg_layer,
+                            seg_length, source_kind, I_source, source_T, terms=(term_abs_coef, term_layer)),
+            *self._emissivity_args(emissivity), *self._term_args(term_abs_coef, term_layer), _hb(radiance), _hb(jac)))
 
     def ray_jacobian_linear_dev(self, abs_coef, seg_T, range_min, range_max, n, ray_first, seg_layer, seg_length,
                                 source_kind, jac, emissivity=1.0, I_source=None, source_T=0.0, term_abs_coef=(), term_layer=(),
@@ -890,21 +875,10 @@ class Context:
         temperatures, as ray_radiance_linear_dev takes them; ``jac`` receives ray_jacobian_rows(..., linear=True) rows of n
         doubles - per ray [dI/dT_source, dI/de, dI/d ln tau of every crossed layer, (dI/dTa, dI/dTb) of every segment that
         is no marker, the terms in crossed layers].  The default ``emissivity`` 1 is the black surface."""
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        i32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        ray_first, seg_layer, source_kind = i32(ray_first), i32(seg_layer), i32(source_kind)
-        seg_length = _as_f64(seg_length)
-        seg_T = _as_f64(seg_T).reshape(-1)
-        if (len(ray_first) != len(source_kind) + 1 or len(seg_layer) != len(seg_length) or len(seg_T) != 2 * len(seg_layer)
-                or len(term_abs_coef) != len(term_layer)):
-            raise ValueError("ray_jacobian_linear_dev: one ray_first per ray and one more, one length and two temperatures per "
-                             "segment layer, one layer per term")
         self.check(self.lib.lbl_ray_jacobian_linear_dev(
-            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), seg_T.ctypes.data_as(_D),
-            float(range_min), float(range_max), int(n), len(source_kind), i32p(ray_first), i32p(seg_layer),
-            seg_length.ctypes.data_as(_D), i32p(source_kind), _hb(I_source), float(source_T),
-            *self._emissivity_args(emissivity), len(term_abs_coef), _arr(_P, [b.h for b in term_abs_coef]),
-            _arr(C.c_int32, [int(l) for l in term_layer]), _hb(radiance), _hb(jac)))
+            *self._ray_args("ray_jacobian_linear_dev", abs_coef, seg_T, range_min, range_max, n, ray_first, seg_layer,
+                            seg_length, source_kind, I_source, source_T, seg_T=True, terms=(term_abs_coef, term_layer)),
+            *self._emissivity_args(emissivity), *self._term_args(term_abs_coef, term_layer), _hb(radiance), _hb(jac)))
 
     def ils_convolve_dev(self, range_min, range_max, n, rows, position, width, first, count, shape, out, table=None,
                          table_half=0.0):

@@ -2433,6 +2433,116 @@ class Atmosphere(list):
             return [p[1].bufs["abs_coef"] for p in plan], plan
         return [L._ensure_swept()[0].bufs["abs_coef"] for L in layers], None
 
+    # The four call helpers below hold the one rule that picks a transport entry point: ``edges`` (or ``linear``: the paths'
+    # segment temperatures) given - the linear one, with emissivity None passed as 1.0; otherwise emissivity None - the black
+    # one; otherwise the surface one.  ``emissivity`` is None, a float or a Buffer.  A new source or surface variant goes here.
+
+    @staticmethod
+    def _flux_call(ctx, layers, n, kbufs, edges, emissivity, reflection, mu, weight, band_first, band_count, level,
+                   up_surface=None, **kw):
+        """lbl_column_flux_dev, _surface_dev or _linear_dev; ``kw``: I_surface, surface_T, I_top, up_top, down_surface"""
+        first = layers[0]
+        args = ([L.depth for L in layers], first.rangeMin, first.rangeMax, n, mu, weight, band_first, band_count, level)
+        if edges is not None:
+            ctx.column_flux_linear_dev(kbufs, edges, *args, 1.0 if emissivity is None else emissivity, reflection=reflection,
+                                       up_surface=up_surface, **kw)
+        elif emissivity is None:
+            ctx.column_flux_dev(kbufs, [L.T for L in layers], *args, **kw)
+        else:
+            ctx.column_flux_surface_dev(kbufs, [L.T for L in layers], *args, emissivity, reflection=reflection,
+                                        up_surface=up_surface, **kw)
+
+    @staticmethod
+    def _jacobian_call(ctx, layers, n, kbufs, edges, emissivity, reflection, mu, weight, band_first, band_count, jac,
+                       T_spectra=None, I_top=None, e_spectrum=None, **kw):
+        """lbl_column_jacobian_dev, _surface_dev or _linear_dev (``T_spectra`` is then the edges'); ``kw``: I_surface,
+        surface_T, term_abs_coef, term_layer, ln_tau_spectra"""
+        first = layers[0]
+        args = ([L.depth for L in layers], first.rangeMin, first.rangeMax, n, mu, weight, band_first, band_count, jac)
+        if edges is not None:
+            ctx.column_jacobian_linear_dev(kbufs, edges, *args, 1.0 if emissivity is None else emissivity,
+                                           reflection=reflection, I_top=I_top, T_edge_spectra=T_spectra, e_spectrum=e_spectrum,
+                                           **kw)
+        elif emissivity is None:
+            ctx.column_jacobian_dev(kbufs, [L.T for L in layers], *args, T_spectra=T_spectra, **kw)
+        else:
+            ctx.column_jacobian_surface_dev(kbufs, [L.T for L in layers], *args, emissivity, reflection=reflection, I_top=I_top,
+                                            T_spectra=T_spectra, e_spectrum=e_spectrum, **kw)
+
+    @staticmethod
+    def _flat_paths(layers, n, paths, linear, emissivity):
+        """What the ray entry points take between the absorption coefficients and their output: the temperatures, the range
+        and the paths flattened into ray_first, seg_layer, seg_length and source_kind.  The black entry point knows no
+        bounce marker and gets the paths' own segments, the other two Path._segments()."""
+        first = layers[0]
+        segs = [(p.layers, p.lengths) if emissivity is None and not linear else p._segments() for p in paths]
+        return ([t for p in paths for t in p._segment_temperatures()] if linear else [L.T for L in layers],
+                first.rangeMin, first.rangeMax, n, np.cumsum([0] + [len(lay) for lay, _ in segs]),
+                [l for lay, _ in segs for l in lay], [x for _, lens in segs for x in lens],
+                [Path.SOURCES.index(p.source) for p in paths])
+
+    @staticmethod
+    def _ray_radiance_call(ctx, layers, n, kbufs, paths, linear, emissivity, radiance, surface_down=None,
+                           surface_down_norm=0.0, **kw):
+        """lbl_ray_radiance_dev, _surface_dev or _linear_dev; ``kw``: I_source, source_T, transmittance"""
+        args = Atmosphere._flat_paths(layers, n, paths, linear, emissivity)
+        if linear:
+            ctx.ray_radiance_linear_dev(kbufs, *args, radiance, 1.0 if emissivity is None else emissivity,
+                                        surface_down=surface_down, surface_down_norm=surface_down_norm, **kw)
+        elif emissivity is None:
+            ctx.ray_radiance_dev(kbufs, *args, radiance, **kw)
+        else:
+            ctx.ray_radiance_surface_dev(kbufs, *args, radiance, emissivity, surface_down=surface_down,
+                                         surface_down_norm=surface_down_norm, **kw)
+
+    @staticmethod
+    def _ray_jacobian_call(ctx, layers, n, kbufs, paths, linear, emissivity, jac, **kw):
+        """lbl_ray_jacobian_dev, _surface_dev or _linear_dev; ``kw``: I_source, source_T, term_abs_coef, term_layer, radiance"""
+        args = Atmosphere._flat_paths(layers, n, paths, linear, emissivity)
+        if linear:
+            ctx.ray_jacobian_linear_dev(kbufs, *args, jac, 1.0 if emissivity is None else emissivity, **kw)
+        elif emissivity is None:
+            ctx.ray_jacobian_dev(kbufs, *args, jac, **kw)
+        else:
+            ctx.ray_jacobian_surface_dev(kbufs, *args, jac, emissivity, **kw)
+
+    @staticmethod
+    def _device_emissivity(ctx, state, emissivity):
+        """None or a number as it is, n values as ``state``'s "emissivity" buffer"""
+        if emissivity is None or isinstance(emissivity, float):
+            return emissivity
+        return state.buf(ctx, "emissivity").upload(emissivity)
+
+    @staticmethod
+    def _term_count(layers, molecules, full, name_dT):
+        """The number of terms of a Jacobian call - the molecules' and, with ``full``, dk_l/dT per layer - checked against
+        the limit (``name_dT``: the wording that names dk/dT) and, with ``full``, against what dk/dT needs"""
+        n_terms = (sum(len(L) for L in layers) if molecules else 0) + (len(layers) if full else 0)
+        if n_terms > nat.limit("jacobian_terms"):
+            raise ValueError(("molecules: %d molecule and dk/dT terms, at most %d (molecules=False skips the molecule terms)"
+                              if name_dT else "molecules: %d molecule terms, at most %d (molecules=False skips them)")
+                             % (n_terms, nat.limit("jacobian_terms")))
+        if full:
+            for L in layers:
+                L._check_abs_coef_dT()
+        return n_terms
+
+    def _term_buffers(self, ctx, layers, n, plan, molecules, full):
+        """(the terms' buffers, the layer of each, the number of molecule terms): _jacobian_terms' with ``molecules``, then
+        with ``full`` dk_l/dT as one more term of layer l - the term sums are linear in the term, whatever its sign"""
+        bufs, where = self._jacobian_terms(ctx, layers, n, plan) if molecules else ([], [])
+        n_mol_terms = len(bufs)
+        if full:
+            bufs = bufs + [L._abs_coef_dT()[0] for L in layers]
+            where = where + list(range(len(layers)))
+        return bufs, where, n_mol_terms
+
+    def _jacobian_spectra(self, ctx, linear, nl, n):
+        """The kept buffers of the spectral (dF/d ln tau, dF/dT) rows, L x n and L x n or, ``linear``, 2 L x n edge rows"""
+        # behaviour, kept: each source keeps its own state, sized for its own rows (the buffers stand between calls)
+        sp = _kept_state(self, "_jacobian_linear_spec" if linear else "_jacobian_spec").reserve(ctx, (2 if linear else 1) * nl * n)
+        return sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T_edge" if linear else "T")
+
     def transmission(self, surfaceSpectrum=None, surfaceTemperature=None):
         """Fold Layer.transmission bottom to top over the layers in list order:
         I <- T_i I + (1 - T_i) B(nu, T_i), I_0 = surfaceSpectrum or B(nu, surfaceTemperature).
@@ -2541,30 +2651,11 @@ class Atmosphere(list):
         level = fst.buf(ctx, "level")
         up_top = fst.buf(ctx, "up_top") if spectra else None
         down_surface = fst.buf(ctx, "down_surface") if spectra else None
-        up_surface = None
-        if edges is not None:
-            if emissivity is None:
-                emissivity = 1.0
-            else:
-                up_surface = fst.buf(ctx, "up_surface") if spectra else None
-                if not isinstance(emissivity, float):
-                    emissivity = fst.buf(ctx, "emissivity").upload(emissivity)
-            ctx.column_flux_linear_dev(kbufs, edges, [L.depth for L in layers], first.rangeMin, first.rangeMax, n, mu, weight,
-                                       band_first, band_count, level, emissivity, reflection=refl, I_surface=I_surface,
-                                       surface_T=float(surfaceTemperature or 0.0), I_top=I_top, up_top=up_top,
-                                       down_surface=down_surface, up_surface=up_surface)
-        elif emissivity is None:
-            ctx.column_flux_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
-                                mu, weight, band_first, band_count, level, I_surface=I_surface,
-                                surface_T=float(surfaceTemperature or 0.0), I_top=I_top, up_top=up_top, down_surface=down_surface)
-        else:
-            if not isinstance(emissivity, float):
-                emissivity = fst.buf(ctx, "emissivity").upload(emissivity)
-            up_surface = fst.buf(ctx, "up_surface") if spectra else None
-            ctx.column_flux_surface_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax,
-                                        n, mu, weight, band_first, band_count, level, emissivity, reflection=refl,
-                                        I_surface=I_surface, surface_T=float(surfaceTemperature or 0.0), I_top=I_top,
-                                        up_top=up_top, down_surface=down_surface, up_surface=up_surface)
+        emissivity = self._device_emissivity(ctx, fst, emissivity)
+        up_surface = fst.buf(ctx, "up_surface") if spectra and emissivity is not None else None
+        self._flux_call(ctx, layers, n, kbufs, edges, emissivity, refl, mu, weight, band_first, band_count, level,
+                        up_surface=up_surface, I_surface=I_surface, surface_T=float(surfaceTemperature or 0.0), I_top=I_top,
+                        up_top=up_top, down_surface=down_surface)
         sums = level.download(nb * 2 * (nl + 1)).reshape(nb, 2, nl + 1) * res
         up, down = sums[:, 0, :], sums[:, 1, :]
         heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], [L.depth for L in layers])
@@ -2777,83 +2868,8 @@ class Atmosphere(list):
         black surface's outgoing flux does not depend on it.
         The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
         planck="linear"; its derivatives are jacobiansLinear()'s)."""
-        if temperature not in ("planck", "full"):
-            raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
-        layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
-            surfaceSpectrum, surfaceTemperature, angles, bands)
-        first = layers[0]
-        refl = _surface_reflection(reflection)
-        if emissivity is None:
-            if topSpectrum is not None:
-                raise ValueError("topSpectrum: the outgoing flux over a black surface does not depend on it (give emissivity)")
-        else:
-            topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
-            emissivity = _surface_emissivity(emissivity, first.xAxis)
-            _weight_sum(weight)
-        names = [[m.name for m in L] for L in layers]
-        full = temperature == "full"
-        n_terms = (sum(len(L) for L in layers) if molecules else 0) + (len(layers) if full else 0)
-        if n_terms > nat.limit("jacobian_terms"):
-            raise ValueError(("molecules: %d molecule and dk/dT terms, at most %d (molecules=False skips the molecule terms)" if full
-                              else "molecules: %d molecule terms, at most %d (molecules=False skips them)")
-                             % (n_terms, nat.limit("jacobian_terms")))
-        if full:
-            for L in layers:
-                L._check_abs_coef_dT()
-        res = utils.BASE_RESOLUTION
-        nl, nb = len(layers), len(band_first)
-        ctx = _ctx()
-        if ctx.option("sweep_ieee_divisions"):
-            raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
-        kbufs, plan = self._column_abs_coef(ctx, layers, n)
-        term_bufs, term_layer = self._jacobian_terms(ctx, layers, n, plan) if molecules else ([], [])
-        n_mol_terms = len(term_bufs)
-        if full:                 # dk_l/dT as one more term of layer l: the term sums are linear in the term, whatever its sign
-            term_bufs = term_bufs + [L._abs_coef_dT()[0] for L in layers]
-            term_layer = term_layer + list(range(nl))
-        h = 2 if emissivity is None else 3           # the values of a band ahead of the layers': F, dF/dT_s and dF/de
-        nv = h + 2 * nl + len(term_bufs)
-        out = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, nb * nv))
-        I_surface = out.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
-        jac = out.buf(ctx, "jac")
-        ln_tau_spec = T_spec = e_spec = None
-        if spectra:
-            sp = _kept_state(self, "_jacobian_spec").reserve(ctx, nl * n)
-            ln_tau_spec, T_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T")
-        if emissivity is None:
-            ctx.column_jacobian_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax, n,
-                                    mu, weight, band_first, band_count, jac, I_surface=I_surface,
-                                    surface_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs, term_layer=term_layer,
-                                    ln_tau_spectra=ln_tau_spec, T_spectra=T_spec)
-        else:
-            sst = _kept_state(self, "_jacobian_surface").reserve(ctx, n)
-            if not isinstance(emissivity, float):
-                emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
-            I_top = sst.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
-            e_spec = sst.buf(ctx, "e_spec") if spectra else None
-            ctx.column_jacobian_surface_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin,
-                                            first.rangeMax, n, mu, weight, band_first, band_count, jac, emissivity,
-                                            reflection=refl, I_surface=I_surface, surface_T=float(surfaceTemperature or 0.0),
-                                            I_top=I_top, term_abs_coef=term_bufs, term_layer=term_layer,
-                                            ln_tau_spectra=ln_tau_spec, T_spectra=T_spec, e_spectrum=e_spec)
-        v = jac.download(nb * nv).reshape(nb, nv) * res
-        olr, dTs = v[:, 0], v[:, 1]
-        dtau, dT = v[:, h:h + nl], v[:, h + nl:h + 2 * nl]
-        mol = None
-        if molecules:
-            mol, o = [], h + 2 * nl
-            for L in layers:
-                mol.append(v[:, o:o + len(L)])
-                o += len(L)
-        olr, dTs, dtau, dT = _band_values(bands, [olr, dTs, dtau, dT])
-        mol = _band_values(bands, mol) if mol is not None else None
-        dT_abs = _band_values(bands, [v[:, h + 2 * nl + n_mol_terms:]])[0] if full else None
-        return Jacobians(olr, dTs if surfaceSpectrum is None else None, dT, dtau, mol, names, mu, weight,
-                         temperatureSpectrum=T_spec.download(nl * n).reshape(nl, n) if spectra else None,
-                         opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None,
-                         temperatureAbsorption=dT_abs,
-                         emissivity=_band_values(bands, [v[:, 2]])[0] if emissivity is not None else None,
-                         emissivitySpectrum=e_spec.download(n) if e_spec is not None else None)
+        return self._column_jacobians(False, surfaceTemperature, surfaceSpectrum, angles, bands, molecules, spectra, temperature,
+                                      emissivity, reflection, topSpectrum)
 
     def observe(self, instrument, surfaceTemperature=None, surfaceSpectrum=None, mu=1.0, jacobians=False, emissivity=None):
         """What an instrument above the column sees at viewing cosine ``mu`` (beyond the reference): the upward radiance at
@@ -2872,69 +2888,7 @@ class Atmosphere(list):
         jacobians(emissivity=e, ...)'s for that angle, and Observation.emissivityJacobian their dR_c/de.
         The Planck source is the layer source: one temperature per layer (fluxes() and radiance() also take
         planck="linear"; its derivatives are observeLinear()'s)."""
-        if not isinstance(instrument, Instrument):
-            raise ValueError("instrument: an Instrument, not %r" % (instrument,))
-        try:
-            angle = [(float(mu), 1.0)]
-        except (TypeError, ValueError):
-            raise ValueError("mu: a viewing cosine in (0, 1], not %r" % (mu,))
-        if not (angle[0][0] > 0.0 and angle[0][0] <= 1.0):
-            raise ValueError("mu: a viewing cosine in (0, 1], not %r" % (mu,))
-        layers, n, mu_k, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
-            surfaceSpectrum, surfaceTemperature, angle, None)
-        first = layers[0]
-        if emissivity is not None:
-            emissivity = _surface_emissivity(emissivity, first.xAxis)
-        support = instrument.support(first.rangeMin, first.rangeMax, n)
-        nl, C = len(layers), len(instrument)
-        n_rows = (1 + 2 * nl + (emissivity is not None)) if jacobians else 1
-        if n_rows > nat.limit("ils_rows"):
-            raise ValueError("jacobians: %d layers, at most %d" % (nl, (nat.limit("ils_rows") - 1 - (emissivity is not None)) // 2))
-        ctx = _ctx()
-        if jacobians and ctx.option("sweep_ieee_divisions"):
-            raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
-        kbufs, _ = self._column_abs_coef(ctx, layers, n)
-        T, depth = [L.T for L in layers], [L.depth for L in layers]
-        surface_T = float(surfaceTemperature or 0.0)
-        fst = _kept_state(self, "_flux_state")
-        fst.reserve(ctx, max(n, 2 * (nl + 1)))
-        I_surface = fst.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
-        up_top = fst.buf(ctx, "up_top")
-        if emissivity is None:
-            ctx.column_flux_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first, band_count,
-                                fst.buf(ctx, "level"), I_surface=I_surface, surface_T=surface_T, up_top=up_top)
-        else:
-            if not isinstance(emissivity, float):
-                emissivity = fst.buf(ctx, "emissivity").upload(emissivity)
-            ctx.column_flux_surface_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
-                                        band_count, fst.buf(ctx, "level"), emissivity, reflection=REFLECTIONS.index("specular"),
-                                        I_surface=I_surface, surface_T=surface_T, up_top=up_top)
-        rows = [(up_top, 0)]
-        if jacobians:
-            jst = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, 3 + 2 * nl))
-            sp = _kept_state(self, "_jacobian_spec").reserve(ctx, nl * n)
-            ln_tau_spec, T_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T")
-            if emissivity is None:
-                ctx.column_jacobian_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
-                                        band_count, jst.buf(ctx, "jac"), I_surface=I_surface, surface_T=surface_T,
-                                        ln_tau_spectra=ln_tau_spec, T_spectra=T_spec)
-            else:
-                e_spec = _kept_state(self, "_jacobian_surface").reserve(ctx, n).buf(ctx, "e_spec")
-                ctx.column_jacobian_surface_dev(kbufs, T, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
-                                                band_count, jst.buf(ctx, "jac"), emissivity,
-                                                reflection=REFLECTIONS.index("specular"), I_surface=I_surface,
-                                                surface_T=surface_T, ln_tau_spectra=ln_tau_spec, T_spectra=T_spec,
-                                                e_spectrum=e_spec)
-            rows += [(T_spec, l * n) for l in range(nl)] + [(ln_tau_spec, l * n) for l in range(nl)]
-            if emissivity is not None:
-                rows.append((e_spec, 0))
-        out = _kept_state(self, "_observe_out").reserve(ctx, n_rows * C).buf(ctx, "out")
-        _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, rows, out)
-        v = out.download(n_rows * C).reshape(n_rows, C)
-        return Observation(instrument.centres.copy(), v[0].copy(), float(mu_k[0]),
-                           temperatureJacobian=v[1:1 + nl].copy() if jacobians else None,
-                           opticalDepthJacobian=v[1 + nl:1 + 2 * nl].copy() if jacobians else None,
-                           emissivityJacobian=v[1 + 2 * nl].copy() if jacobians and emissivity is not None else None)
+        return self._observe(False, instrument, surfaceTemperature, surfaceSpectrum, mu, jacobians, emissivity)
 
     def _level_chain(self):
         """The (L + 1) x L matrix M of levelTemperatures(): lev = M T for the layers' temperatures T (the map is linear, its
@@ -2977,87 +2931,92 @@ class Atmosphere(list):
         it is the Planck part, the absorption coefficients held fixed.  temperature="full" adds temperatureAbsorption
         through dk_l/dT as jacobians() does.  olr is fluxes(planck="linear")'s upward flux at the top to rounding.
         Everything is validated (ValueError) before the device is touched."""
+        return self._column_jacobians(True, surfaceTemperature, surfaceSpectrum, angles, bands, molecules, spectra, temperature,
+                                      emissivity, reflection, topSpectrum, levelTemperatures)
+
+    def _column_jacobians(self, linear, surfaceTemperature, surfaceSpectrum, angles, bands, molecules, spectra, temperature,
+                          emissivity, reflection, topSpectrum, levelTemperatures=None):
+        """jacobians() and, with ``linear``, jacobiansLinear()"""
         if temperature not in ("planck", "full"):
             raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
         layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
             surfaceSpectrum, surfaceTemperature, angles, bands)
         first = layers[0]
         refl = _surface_reflection(reflection)
-        lev = self._level_temperatures(levelTemperatures)
-        chain = self._level_chain() if levelTemperatures is None or levelTemperatures is True else None
-        edges = np.column_stack([lev[:-1], lev[1:]])
+        edges = chain = None
+        if linear:
+            lev = self._level_temperatures(levelTemperatures)
+            chain = self._level_chain() if levelTemperatures is None or levelTemperatures is True else None
+            edges = np.column_stack([lev[:-1], lev[1:]])
         black = emissivity is None
         if black:
             if topSpectrum is not None:
                 raise ValueError("topSpectrum: the outgoing flux over a black surface does not depend on it (give emissivity)")
-            emissivity = 1.0
         else:
             topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
             emissivity = _surface_emissivity(emissivity, first.xAxis)
-        _weight_sum(weight)
+        if linear or not black:  # behaviour, kept: jacobians() looks at the weights' sum over a reflecting surface only
+            _weight_sum(weight)
         names = [[m.name for m in L] for L in layers]
         full = temperature == "full"
-        n_terms = (sum(len(L) for L in layers) if molecules else 0) + (len(layers) if full else 0)
-        if n_terms > nat.limit("jacobian_terms"):
-            raise ValueError("molecules: %d molecule and dk/dT terms, at most %d (molecules=False skips the molecule terms)"
-                             % (n_terms, nat.limit("jacobian_terms")))
-        if full:
-            for L in layers:
-                L._check_abs_coef_dT()
+        # behaviour, kept: jacobiansLinear() words the limit with dk/dT whatever ``temperature`` is
+        self._term_count(layers, molecules, full, linear or full)
         res = utils.BASE_RESOLUTION
         nl, nb = len(layers), len(band_first)
         ctx = _ctx()
         if ctx.option("sweep_ieee_divisions"):
             raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
         kbufs, plan = self._column_abs_coef(ctx, layers, n)
-        term_bufs, term_layer = self._jacobian_terms(ctx, layers, n, plan) if molecules else ([], [])
-        n_mol_terms = len(term_bufs)
-        if full:
-            term_bufs = term_bufs + [L._abs_coef_dT()[0] for L in layers]
-            term_layer = term_layer + list(range(nl))
-        nv = 3 + 3 * nl + len(term_bufs)
+        term_bufs, term_layer, n_mol_terms = self._term_buffers(ctx, layers, n, plan, molecules, full)
+        h = 2 if black and not linear else 3         # the values of a band ahead of the layers': F, dF/dT_s and dF/de
+        w = 3 if linear else 2                       # ... and per layer: d ln tau and T, or d ln tau and the two edges' T
+        nv = h + w * nl + len(term_bufs)
         out = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, nb * nv))
         I_surface = out.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
         jac = out.buf(ctx, "jac")
-        ln_tau_spec = T_edge_spec = e_spec = None
+        ln_tau_spec = T_spec = e_spec = I_top = None
         if spectra:
-            sp = _kept_state(self, "_jacobian_linear_spec").reserve(ctx, 2 * nl * n)
-            ln_tau_spec, T_edge_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T_edge")
-        sst = _kept_state(self, "_jacobian_surface").reserve(ctx, n)
-        if not isinstance(emissivity, float):
-            emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
-        I_top = sst.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
-        if spectra and not black:
-            e_spec = sst.buf(ctx, "e_spec")
-        ctx.column_jacobian_linear_dev(kbufs, edges, [L.depth for L in layers], first.rangeMin, first.rangeMax, n, mu, weight,
-                                       band_first, band_count, jac, emissivity, reflection=refl, I_surface=I_surface,
-                                       surface_T=float(surfaceTemperature or 0.0), I_top=I_top, term_abs_coef=term_bufs,
-                                       term_layer=term_layer, ln_tau_spectra=ln_tau_spec, T_edge_spectra=T_edge_spec,
-                                       e_spectrum=e_spec)
+            ln_tau_spec, T_spec = self._jacobian_spectra(ctx, linear, nl, n)
+        if linear or not black:  # behaviour, kept: jacobiansLinear() reserves the surface's state over the black surface too
+            sst = _kept_state(self, "_jacobian_surface").reserve(ctx, n)
+            emissivity = self._device_emissivity(ctx, sst, emissivity)
+            I_top = sst.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
+            e_spec = sst.buf(ctx, "e_spec") if spectra and not black else None
+        self._jacobian_call(ctx, layers, n, kbufs, edges, emissivity, refl, mu, weight, band_first, band_count, jac,
+                            T_spectra=T_spec, I_top=I_top, e_spectrum=e_spec, I_surface=I_surface,
+                            surface_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs, term_layer=term_layer,
+                            ln_tau_spectra=ln_tau_spec)
         v = jac.download(nb * nv).reshape(nb, nv) * res
-        olr, dTs, de = v[:, 0], v[:, 1], v[:, 2]
-        dtau = v[:, 3:3 + nl]
-        edge = v[:, 3 + nl:3 + 3 * nl].reshape(nb, nl, 2)
-        dlev = self._levels_of_edges(edge)
-        dT = dlev @ chain if chain is not None else None
-        mol = None
+        mol, o = None, h + w * nl                    # (where the terms begin: the molecules' layer by layer, then dk/dT)
         if molecules:
-            mol, o = [], 3 + 3 * nl
+            mol, at = [], o
             for L in layers:
-                mol.append(v[:, o:o + len(L)])
-                o += len(L)
-        olr, dTs, de, dtau, edge, dlev = _band_values(bands, [olr, dTs, de, dtau, edge, dlev])
-        dT = _band_values(bands, [dT])[0] if dT is not None else None
-        mol = _band_values(bands, mol) if mol is not None else None
-        dT_abs = _band_values(bands, [v[:, 3 + 3 * nl + n_mol_terms:]])[0] if full else None
-        lev_spec = None
-        if spectra:
-            lev_spec = self._levels_of_edges(T_edge_spec.download(2 * nl * n).reshape(nl, 2, n).transpose(2, 0, 1)).T.copy()
-        return Jacobians(olr, dTs if surfaceSpectrum is None else None, dT, dtau, mol, names, mu, weight,
-                         opticalDepthSpectrum=ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None,
-                         temperatureAbsorption=dT_abs, emissivity=None if black else de,
-                         emissivitySpectrum=e_spec.download(n) if e_spec is not None else None,
-                         edgeTemperature=edge, levelTemperature=dlev, levelTemperatureSpectrum=lev_spec)
+                mol.append(v[:, at:at + len(L)])
+                at += len(L)
+            mol = _band_values(bands, mol)
+        rows = [v[:, 0], v[:, 1], v[:, h:h + nl]]
+        if linear:
+            edge = v[:, 3 + nl:3 + 3 * nl].reshape(nb, nl, 2)
+            dlev = self._levels_of_edges(edge)
+            rows += [edge, dlev] + ([dlev @ chain] if chain is not None else [])
+        else:
+            rows.append(v[:, h + nl:h + 2 * nl])
+        olr, dTs, dtau, *own = _band_values(bands, rows)
+        if surfaceSpectrum is not None:
+            dTs = None
+        T_rows = T_spec.download((w - 1) * nl * n) if spectra else None          # (the downloads in this order: T, ln tau, e)
+        tau_rows = ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None
+        dT_abs = _band_values(bands, [v[:, o + n_mol_terms:]])[0] if full else None
+        de = None if black else _band_values(bands, [v[:, 2]])[0]
+        e_row = e_spec.download(n) if e_spec is not None else None
+        if not linear:
+            return Jacobians(olr, dTs, own[0], dtau, mol, names, mu, weight,
+                             temperatureSpectrum=T_rows.reshape(nl, n) if spectra else None, opticalDepthSpectrum=tau_rows,
+                             temperatureAbsorption=dT_abs, emissivity=de, emissivitySpectrum=e_row)
+        lev_spec = self._levels_of_edges(T_rows.reshape(nl, 2, n).transpose(2, 0, 1)).T.copy() if spectra else None
+        return Jacobians(olr, dTs, own[2] if chain is not None else None, dtau, mol, names, mu, weight,
+                         opticalDepthSpectrum=tau_rows, temperatureAbsorption=dT_abs, emissivity=de, emissivitySpectrum=e_row,
+                         edgeTemperature=own[0], levelTemperature=own[1], levelTemperatureSpectrum=lev_spec)
 
     @staticmethod
     def _levels_of_edges(edge):
@@ -3080,64 +3039,74 @@ class Atmosphere(list):
         convolved in the same call, the 2 L edge rows summed to levels on the host (the convolution is linear), and over a
         surface with an emissivity emissivityJacobian.  Returns an Observation whose temperatureJacobian is None.
         Everything is validated (ValueError) before the device is touched."""
+        return self._observe(True, instrument, surfaceTemperature, surfaceSpectrum, mu, jacobians, emissivity, levelTemperatures)
+
+    def _observe(self, linear, instrument, surfaceTemperature, surfaceSpectrum, mu, jacobians, emissivity,
+                 levelTemperatures=None):
+        """observe() and, with ``linear``, observeLinear()"""
         if not isinstance(instrument, Instrument):
             raise ValueError("instrument: an Instrument, not %r" % (instrument,))
         try:
             angle = [(float(mu), 1.0)]
         except (TypeError, ValueError):
-            raise ValueError("mu: a viewing cosine in (0, 1], not %r" % (mu,))
-        if not (angle[0][0] > 0.0 and angle[0][0] <= 1.0):
+            angle = None
+        if angle is None or not (angle[0][0] > 0.0 and angle[0][0] <= 1.0):
             raise ValueError("mu: a viewing cosine in (0, 1], not %r" % (mu,))
         layers, n, mu_k, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
             surfaceSpectrum, surfaceTemperature, angle, None)
         first = layers[0]
-        lev = self._level_temperatures(levelTemperatures)
-        edges = np.column_stack([lev[:-1], lev[1:]])
+        edges = None
+        if linear:
+            lev = self._level_temperatures(levelTemperatures)
+            edges = np.column_stack([lev[:-1], lev[1:]])
         black = emissivity is None
-        emissivity = 1.0 if black else _surface_emissivity(emissivity, first.xAxis)
+        if not black:
+            emissivity = _surface_emissivity(emissivity, first.xAxis)
         support = instrument.support(first.rangeMin, first.rangeMax, n)
         nl, C = len(layers), len(instrument)
-        n_rows = (1 + 3 * nl + (not black)) if jacobians else 1
-        if n_rows > nat.limit("ils_rows"):
-            raise ValueError("jacobians: %d layers, at most %d" % (nl, (nat.limit("ils_rows") - 2) // 3))
+        w = 3 if linear else 2                       # a layer's rows: d ln tau and T, or d ln tau and the two edges' T
+        n_rows = (1 + w * nl + (not black)) if jacobians else 1
+        if n_rows > nat.limit("ils_rows"):           # behaviour, kept: the two methods work out "at most" differently
+            most = (nat.limit("ils_rows") - 2) // 3 if linear else (nat.limit("ils_rows") - 1 - (not black)) // 2
+            raise ValueError("jacobians: %d layers, at most %d" % (nl, most))
         ctx = _ctx()
         if jacobians and ctx.option("sweep_ieee_divisions"):
             raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
         kbufs, _ = self._column_abs_coef(ctx, layers, n)
-        depth = [L.depth for L in layers]
-        surface_T = float(surfaceTemperature or 0.0)
         specular = REFLECTIONS.index("specular")
-        fst = _kept_state(self, "_flux_state")
+        src = dict(surface_T=float(surfaceTemperature or 0.0))
+        fst = _kept_state(self, "_flux_state")       # behaviour, kept: the emissivity stands in fluxes()'s state
         fst.reserve(ctx, max(n, 2 * (nl + 1)))
-        I_surface = fst.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
+        src["I_surface"] = fst.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
         up_top = fst.buf(ctx, "up_top")
-        if not isinstance(emissivity, float):
-            emissivity = fst.buf(ctx, "emissivity").upload(emissivity)
-        ctx.column_flux_linear_dev(kbufs, edges, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
-                                   band_count, fst.buf(ctx, "level"), emissivity, reflection=specular, I_surface=I_surface,
-                                   surface_T=surface_T, up_top=up_top)
+        emissivity = self._device_emissivity(ctx, fst, emissivity)
+        self._flux_call(ctx, layers, n, kbufs, edges, emissivity, specular, mu_k, weight, band_first, band_count,
+                        fst.buf(ctx, "level"), up_top=up_top, **src)
         rows = [(up_top, 0)]
         if jacobians:
-            jst = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, 3 + 3 * nl))
-            sp = _kept_state(self, "_jacobian_linear_spec").reserve(ctx, 2 * nl * n)
-            ln_tau_spec, T_edge_spec = sp.buf(ctx, "ln_tau"), sp.buf(ctx, "T_edge")
+            jst = _kept_state(self, "_jacobian_out").reserve(ctx, max(n, 3 + w * nl))
+            ln_tau_spec, T_spec = self._jacobian_spectra(ctx, linear, nl, n)
             e_spec = None if black else _kept_state(self, "_jacobian_surface").reserve(ctx, n).buf(ctx, "e_spec")
-            ctx.column_jacobian_linear_dev(kbufs, edges, depth, first.rangeMin, first.rangeMax, n, mu_k, weight, band_first,
-                                           band_count, jst.buf(ctx, "jac"), emissivity, reflection=specular,
-                                           I_surface=I_surface, surface_T=surface_T, ln_tau_spectra=ln_tau_spec,
-                                           T_edge_spectra=T_edge_spec, e_spectrum=e_spec)
-            rows += [(ln_tau_spec, l * n) for l in range(nl)] + [(T_edge_spec, i * n) for i in range(2 * nl)]
+            self._jacobian_call(ctx, layers, n, kbufs, edges, emissivity, specular, mu_k, weight, band_first, band_count,
+                                jst.buf(ctx, "jac"), T_spectra=T_spec, e_spectrum=e_spec, ln_tau_spectra=ln_tau_spec, **src)
+            tau_rows, T_rows = [(ln_tau_spec, l * n) for l in range(nl)], [(T_spec, i * n) for i in range((w - 1) * nl)]
+            # behaviour, kept: observe() hands the temperature rows to the convolution first, observeLinear() the edge rows last
+            rows += tau_rows + T_rows if linear else T_rows + tau_rows
             if e_spec is not None:
                 rows.append((e_spec, 0))
         out = _kept_state(self, "_observe_out").reserve(ctx, n_rows * C).buf(ctx, "out")
         _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, rows, out)
         v = out.download(n_rows * C).reshape(n_rows, C)
+        e_row = v[1 + w * nl].copy() if jacobians and not black else None
+        if not linear:
+            return Observation(instrument.centres.copy(), v[0].copy(), float(mu_k[0]),
+                               temperatureJacobian=v[1:1 + nl].copy() if jacobians else None,
+                               opticalDepthJacobian=v[1 + nl:1 + 2 * nl].copy() if jacobians else None, emissivityJacobian=e_row)
         dlev = None
         if jacobians:
             dlev = self._levels_of_edges(v[1 + nl:1 + 3 * nl].reshape(nl, 2, C).transpose(2, 0, 1)).T.copy()
         return Observation(instrument.centres.copy(), v[0].copy(), float(mu_k[0]),
-                           opticalDepthJacobian=v[1:1 + nl].copy() if jacobians else None,
-                           emissivityJacobian=v[1 + 3 * nl].copy() if jacobians and not black else None,
+                           opticalDepthJacobian=v[1:1 + nl].copy() if jacobians else None, emissivityJacobian=e_row,
                            levelTemperatureJacobian=dlev)
 
     @staticmethod
@@ -3369,50 +3338,17 @@ class Atmosphere(list):
         pst = _kept_state(self, "_path_state").reserve(ctx, R * n)
         rad = pst.buf(ctx, "radiance")
         trn = pst.buf(ctx, "transmittance") if transmittance else None
-        if linear:
-            down, norm = None, 0.0
-            if emissivity is None:
-                emissivity = 1.0
-            else:
-                sst = _kept_state(self, "_path_surface").reserve(ctx, max(n, 2 * (nl + 1)))
-                if not isinstance(emissivity, float):
-                    emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
-                if refl == 0 and any(p.source == "surface" for p in plist):
-                    # the downward flux at the surface under cold space, left on the device for the ray call behind it
-                    down, norm = sst.buf(ctx, "down_surface"), wsum
-                    ctx.column_flux_linear_dev(kbufs, edges, [L.depth for L in layers], first.rangeMin, first.rangeMax, n, mu,
-                                               weight, [0], [n], sst.buf(ctx, "level"), I_surface=I_source,
-                                               surface_T=float(surfaceTemperature or 0.0), down_surface=down)
-            segs = [p._segments() for p in plist]
-            ctx.ray_radiance_linear_dev(kbufs, [t for p in plist for t in p._segment_temperatures()], first.rangeMin,
-                                        first.rangeMax, n, np.cumsum([0] + [len(lay) for lay, _ in segs]),
-                                        [l for lay, _ in segs for l in lay], [x for _, lens in segs for x in lens],
-                                        [Path.SOURCES.index(p.source) for p in plist], rad, emissivity, I_source=I_source,
-                                        source_T=float(surfaceTemperature or 0.0), surface_down=down, surface_down_norm=norm,
-                                        transmittance=trn)
-        elif emissivity is None:
-            ray_first = np.cumsum([0] + [len(p) for p in plist])
-            ctx.ray_radiance_dev(kbufs, [L.T for L in layers], first.rangeMin, first.rangeMax, n, ray_first,
-                                 [l for p in plist for l in p.layers], [x for p in plist for x in p.lengths],
-                                 [Path.SOURCES.index(p.source) for p in plist], rad, I_source=I_source,
-                                 source_T=float(surfaceTemperature or 0.0), transmittance=trn)
-        else:
+        down, norm = None, 0.0
+        if emissivity is not None:
             sst = _kept_state(self, "_path_surface").reserve(ctx, max(n, 2 * (nl + 1)))
-            if not isinstance(emissivity, float):
-                emissivity = sst.buf(ctx, "emissivity").upload(emissivity)
-            down, norm = None, 0.0
+            emissivity = self._device_emissivity(ctx, sst, emissivity)
             if refl == 0 and any(p.source == "surface" for p in plist):
                 # the downward flux at the surface under cold space, left on the device for the ray call behind it
                 down, norm = sst.buf(ctx, "down_surface"), wsum
-                ctx.column_flux_dev(kbufs, [L.T for L in layers], [L.depth for L in layers], first.rangeMin, first.rangeMax,
-                                    n, mu, weight, [0], [n], sst.buf(ctx, "level"), I_surface=I_source,
-                                    surface_T=float(surfaceTemperature or 0.0), down_surface=down)
-            segs = [p._segments() for p in plist]
-            ctx.ray_radiance_surface_dev(kbufs, [L.T for L in layers], first.rangeMin, first.rangeMax, n,
-                                         np.cumsum([0] + [len(lay) for lay, _ in segs]), [l for lay, _ in segs for l in lay],
-                                         [x for _, lens in segs for x in lens], [Path.SOURCES.index(p.source) for p in plist],
-                                         rad, emissivity, I_source=I_source, source_T=float(surfaceTemperature or 0.0),
-                                         surface_down=down, surface_down_norm=norm, transmittance=trn)
+                self._flux_call(ctx, layers, n, kbufs, edges, None, 0, mu, weight, [0], [n], sst.buf(ctx, "level"),
+                                I_surface=I_source, surface_T=float(surfaceTemperature or 0.0), down_surface=down)
+        self._ray_radiance_call(ctx, layers, n, kbufs, plist, linear, emissivity, rad, surface_down=down, surface_down_norm=norm,
+                                I_source=I_source, source_T=float(surfaceTemperature or 0.0), transmittance=trn)
         if instrument is None:
             return PathRadiance(first.xAxis, rad.download(R * n).reshape(R, n),
                                 trn.download(R * n).reshape(R, n) if transmittance else None, plist)
@@ -3508,20 +3444,11 @@ class Atmosphere(list):
                     raise ValueError("paths: path %d (%r) carries no temperatures (the linear source needs a pair per segment)"
                                      % (i, p))
         black = emissivity is None
-        if linear and black:                          # (the linear entry point is a superset of the black surface)
-            emissivity = 1.0
-        h = 1 if emissivity is None else 2            # a path's rows ahead of its layers': dI/dT_s and dI/de
+        h = 1 if black and not linear else 2          # a path's rows ahead of its layers': dI/dT_s and (not the black call's) dI/de
         full = temperature == "full"
         names = [[m.name for m in L] for L in layers]
-        n_mol_terms = sum(len(L) for L in layers) if molecules else 0
-        n_terms = n_mol_terms + (nl if full else 0)
-        if n_terms > nat.limit("jacobian_terms"):
-            raise ValueError(("molecules: %d molecule and dk/dT terms, at most %d (molecules=False skips the molecule terms)" if full
-                              else "molecules: %d molecule terms, at most %d (molecules=False skips them)")
-                             % (n_terms, nat.limit("jacobian_terms")))
-        if full:
-            for L in layers:
-                L._check_abs_coef_dT()
+        n_terms = self._term_count(layers, molecules, full, full)
+        n_mol_terms = n_terms - (nl if full else 0)
         support = None
         if instrument is not None:
             if not isinstance(instrument, Instrument):
@@ -3545,9 +3472,7 @@ class Atmosphere(list):
         if ctx.option("sweep_ieee_divisions"):
             raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
         kbufs, plan = self._column_abs_coef(ctx, layers, n)
-        term_bufs = self._jacobian_terms(ctx, layers, n, plan)[0] if molecules else []
-        if full:                 # dk_l/dT as one more term of layer l, as jacobians() passes it
-            term_bufs = term_bufs + [L._abs_coef_dT()[0] for L in layers]
+        term_bufs = self._term_buffers(ctx, layers, n, plan, molecules, full)[0]
         I_source = None
         if surfaceSpectrum is not None:
             I_source = _kept_state(self, "_path_source").reserve(ctx, n).buf(ctx, "I_source").upload(surfaceSpectrum)
@@ -3562,30 +3487,11 @@ class Atmosphere(list):
             out = _kept_state(self, "_path_jacobian_out").reserve(ctx, (R + total) * X).buf(ctx, "out")
         I = np.empty((R, X))
         J = np.empty((total, X))
-        T, kinds = [L.T for L in layers], [Path.SOURCES.index(p.source) for p in plist]
         row0 = 0
         for r, e, rows in chunks:
-            sub = plist[r:e]
-            if linear:
-                segs = [p._segments() for p in sub]
-                ctx.ray_jacobian_linear_dev(kbufs, [t for p in sub for t in p._segment_temperatures()], first.rangeMin,
-                                            first.rangeMax, n, np.cumsum([0] + [len(lay) for lay, _ in segs]),
-                                            [l for lay, _ in segs for l in lay], [x for _, lens in segs for x in lens],
-                                            kinds[r:e], jac, emissivity, I_source=I_source,
-                                            source_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs,
-                                            term_layer=term_layer, radiance=rad)
-            elif emissivity is None:
-                ctx.ray_jacobian_dev(kbufs, T, first.rangeMin, first.rangeMax, n, np.cumsum([0] + [len(p) for p in sub]),
-                                     [l for p in sub for l in p.layers], [x for p in sub for x in p.lengths], kinds[r:e], jac,
-                                     I_source=I_source, source_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs,
-                                     term_layer=term_layer, radiance=rad)
-            else:
-                segs = [p._segments() for p in sub]
-                ctx.ray_jacobian_surface_dev(kbufs, T, first.rangeMin, first.rangeMax, n,
-                                             np.cumsum([0] + [len(lay) for lay, _ in segs]), [l for lay, _ in segs for l in lay],
-                                             [x for _, lens in segs for x in lens], kinds[r:e], jac, emissivity,
-                                             I_source=I_source, source_T=float(surfaceTemperature or 0.0),
-                                             term_abs_coef=term_bufs, term_layer=term_layer, radiance=rad)
+            self._ray_jacobian_call(ctx, layers, n, kbufs, plist[r:e], linear, emissivity, jac, I_source=I_source,
+                                    source_T=float(surfaceTemperature or 0.0), term_abs_coef=term_bufs, term_layer=term_layer,
+                                    radiance=rad)
             if instrument is None:
                 I[r:e] = rad.download((e - r) * n).reshape(e - r, n)
                 J[row0:row0 + rows] = jac.download(rows * n).reshape(rows, n)
@@ -3609,7 +3515,7 @@ class Atmosphere(list):
         # rows -> (R, L, X) arrays: zeros where a path does not cross a layer
         dtau, dT = np.zeros((R, nl, X)), None if linear else np.zeros((R, nl, X))
         dTs = np.zeros((R, X))
-        de = np.zeros((R, X)) if emissivity is not None and not black else None
+        de = None if black else np.zeros((R, X))
         terms = np.zeros((R, n_terms, X))
         seg_T = [] if linear else None
         row0 = 0
