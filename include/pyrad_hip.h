@@ -733,6 +733,56 @@ int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_
                              lbl_buffer* down_surface, lbl_buffer* direct_surface,
                              lbl_buffer* up_surface /* may be NULL */);
 
+/* ---- thermal fluxes through scattering layers (beyond the reference; ABI 5, backward compatible) --------------------------
+ * pyrad_amd.model.Atmosphere.fluxesTwoStream: lbl_column_flux_surface_dev's (or _linear_dev's) thermal fluxes through a column
+ * whose layers also scatter.  The layer solution - scatterers, delta scaling, ta, ts, tsg, t, a, b, g1, g2, lam, R, T, Ab, the
+ * den == 0 and t == 0 branches - and the adding recurrences are lbl_column_twostream_dev's, unchanged; there are no beams.
+ * Fluxes are hemispheric: an isotropic radiance I is the flux pi I, and the result corresponds to the angle set
+ * {(1 / sqrt(3), pi)} of the other flux calls.  B is the fold's general Planck expression, pa nu^3 / (exp(nu pbkT) - 1).
+ * Layer l at nu_j, with Bt = pi B(nu_j, T at the layer's top edge), Bb likewise at its bottom edge, d = Bb - Bt, D = sqrt(3):
+ * the two-stream equations with the source (g1 - g2) pi B(tau), B linear in optical depth, have the particular solution
+ * F+- = pi B(tau) +- c, c = d / ((g1 + g2) t) = d / (D (t - tsg)) (Toon et al. 1989); with the homogeneous response
+ * subtracted the layer emits upward at its top P = (Bt + c) - R (Bt - c) - T (Bb + c) and downward at its bottom
+ * Q = (Bb - c) - R (Bb + c) - T (Bt - c), evaluated with 1 - R - T = Ab and 1 + R - T = Ab + 2 R as
+ *   h = (Ab + 2 R) / (D (t - tsg)) - T
+ *   P = Bt Ab + d h          Q = Bb Ab - d h
+ *   t == 0: P = Q = 0;  ta == 0 or den == 0 (nothing absorbs): P = Q = 0 exactly.
+ * planck_linear 0: T holds n_layers layer temperatures, Bt = Bb = pi B(nu_j, T_l), so P = Q = Bb Ab and no h is formed.
+ * planck_linear 1: T holds 2 n_layers edge temperatures in lbl_column_flux_linear_dev's order, T[2 l] at the bottom edge and
+ * T[2 l + 1] at the top edge of layer l; with both equal to T_l every result is planck_linear 0's bit for bit.
+ * Column, with lbl_column_twostream_dev's relations and recurrences (Rs, Ds, U1, U0, c = 1 - R Rs):
+ *   top:      Rs_L = 0,  Ds_L = pi I_top[j]  or 0 (I_top NULL)
+ *   surface:  Es = pi (I_surface[j] or B(nu_j, surface_T)),  e = emissivity[j] or emissivity_all, Lambertian
+ *             up_0 = (e Es + (1 - e) Ds_0) / (1 - (1 - e) Rs_0)
+ *   then      up_(l+1) = U1 up_l + U0,   dn_i = Rs_i up_i + Ds_i
+ * level_flux is n_bands x 2 x (n_layers + 1): [band][up, down][level], band sums of nan_to_num.  up_top, down_surface and
+ * up_surface (may be NULL; n points each) receive the spectral values at every point of every band, 0 elsewhere.  A point
+ * where some layer's t is not finite has NaN in all three and counts as 0 in every band sum; every other point keeps its bits.
+ * The first of two kernels writes 4 numbers per level and point into `workspace` ([number][level][point]), the second reads
+ * them; passes, tiles of 256 points and the partial sums by tile of the band are lbl_column_twostream_dev's, so the bits do not
+ * depend on the workspace's size.  lbl_column_flux_scatter_workspace gives the doubles that hold `points` points in one pass:
+ * 4 (n_layers + 1) per point, whole tiles, at least one.  Every operation is rounded on its own; no atomics.
+ * Without scatterers R = 0, T = exp(-D ta), and the result is lbl_column_flux_surface_dev's (_linear_dev's) with the angle
+ * set {(1 / sqrt(3), pi)} and Lambertian reflection to rounding: P is (1 - t) Ba + g(tau) (Bb - Ba) at tau = D ta.
+ * LBL_ERR_BAD_ARG, all before anything is enqueued: what lbl_column_flux_surface_dev (planck_linear 1: _linear_dev) refuses of
+ * the column, the surface source, I_top, the bands, the emissivity and the outputs; what lbl_column_twostream_dev refuses of
+ * the scatterers, delta_scaling and the workspace (here lbl_column_flux_scatter_workspace(n_layers, 1) doubles); a
+ * temperature that is not finite and > 0; planck_linear not 0 or 1.  The host arrays are copied and not retained.
+ * Stream-ordered; nothing is synchronised. */
+int lbl_column_flux_scatter_workspace(int n_layers, int64_t points, int64_t* doubles);
+int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
+                                const double* T /* n_layers, or 2 n_layers: bottom, top of layer l */, int planck_linear,
+                                const double* depth, double range_min, double range_max, int64_t n,
+                                lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                                int n_scat, const double* scat_amount /* n_scat x n_layers */,
+                                lbl_buffer* const* scat_ext /* may be NULL, and every entry */, const double* scat_ext_all,
+                                lbl_buffer* const* scat_ssa, const double* scat_ssa_all,
+                                lbl_buffer* const* scat_asym, const double* scat_asym_all, int delta_scaling,
+                                int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                lbl_buffer* workspace, lbl_buffer* level_flux, lbl_buffer* up_top,
+                                lbl_buffer* down_surface, lbl_buffer* up_surface /* may be NULL */);
+
 /* ---- ray-path Jacobians (beyond the reference; ABI 5, backward compatible) --------------------------------------------
  * pyrad_amd.model.Atmosphere.pathJacobians: the weighting functions of the radiance lbl_ray_radiance_dev computes - its
  * analytic derivatives to every crossed layer's optical depth and (Planck) temperature, to the source temperature and to any

@@ -3,8 +3,9 @@
 // variants over a reflecting surface, lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev, lbl_column_jacobian_surface_dev
 // and lbl_ray_jacobian_surface_dev, of the linear-source variants lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev, and
 // of their Jacobians lbl_column_jacobian_linear_dev and lbl_ray_jacobian_linear_dev, of the direct solar beam,
-// lbl_column_solar_dev, and of its two-stream multiple scattering, lbl_column_twostream_dev.
-// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j, K5k and K5l of lbl_kernels.hip; the context's internals
+// lbl_column_solar_dev, of its two-stream multiple scattering, lbl_column_twostream_dev, and of the thermal fluxes through
+// scattering layers, lbl_column_flux_scatter_dev.
+// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j, K5k, K5l and K5m of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -373,6 +374,39 @@ static int check_scat_numbers(lbl_ctx* ctx, const char* what, int n_scat, int64_
     return LBL_OK;
 }
 
+// the scatterers of K5l and K5m (n_scat within its limit, scat_amount there): every amount, then the three numbers of each,
+// into the fields both argument blocks name alike
+template <class Args>
+static int check_scatterers(lbl_ctx* ctx, Args* a, int n_layers, int64_t n, int n_scat, const double* scat_amount,
+                            lbl_buffer* const* scat_ext, const double* scat_ext_all, lbl_buffer* const* scat_ssa,
+                            const double* scat_ssa_all, lbl_buffer* const* scat_asym, const double* scat_asym_all) {
+    int rc;
+    for (int c = 0; c < n_scat; ++c)
+        for (int l = 0; l < n_layers; ++l) {
+            const double v = scat_amount[(size_t)c * n_layers + l];
+            if (!(v >= 0) || !std::isfinite(v))
+                return column_fail(ctx, LBL_ERR_BAD_ARG, "scatterer %d, layer %d: amount must be finite and >= 0", c, l);
+            a->amount[c][l] = v;
+        }
+    if ((rc = check_scat_numbers(ctx, "extinction", n_scat, n, scat_ext, scat_ext_all, 0.0, HUGE_VAL, false, a->ext, a->ext_all))) return rc;
+    if ((rc = check_scat_numbers(ctx, "single-scattering albedo", n_scat, n, scat_ssa, scat_ssa_all, 0.0, 1.0, false, a->ssa, a->ssa_all))) return rc;
+    return check_scat_numbers(ctx, "asymmetry", n_scat, n, scat_asym, scat_asym_all, -1.0, 1.0, true, a->asym, a->asym_all);
+}
+
+// the caller's workspace of K5l and K5m, `quantities` numbers per level and point: at least one tile; *ws_points receives the
+// points of one pass, a whole number of tiles
+static int check_workspace(lbl_ctx* ctx, lbl_buffer* workspace, int quantities, int n_layers, int64_t* ws_points) {
+    int rc;
+    if ((rc = ctx_check_buffer(ctx, workspace, 0, "workspace", true))) return rc;
+    int64_t ws_len = 0;
+    lbl_buffer_size(workspace, &ws_len);
+    const int64_t tile_doubles = (int64_t)quantities * (n_layers + 1) * kTwoStreamTile;
+    if (ws_len < tile_doubles)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "workspace: at least %lld doubles (one tile of %d points)", (long long)tile_doubles, kTwoStreamTile);
+    *ws_points = ws_len / tile_doubles * kTwoStreamTile;
+    return LBL_OK;
+}
+
 // K5l: lbl_column_solar_dev's checks in its order, the scatterers' and the workspace's behind them; then every band in passes
 // of as many points as the workspace holds, the band's partial slots zeroed first and reduced after its last pass.
 extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
@@ -432,23 +466,11 @@ extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* 
             a->m[s][l] = 1.0 / v;
         }
     }
-    for (int c = 0; c < n_scat; ++c)
-        for (int l = 0; l < n_layers; ++l) {
-            const double v = scat_amount[(size_t)c * n_layers + l];
-            if (!(v >= 0) || !std::isfinite(v))
-                return column_fail(ctx, LBL_ERR_BAD_ARG, "scatterer %d, layer %d: amount must be finite and >= 0", c, l);
-            a->amount[c][l] = v;
-        }
-    if ((rc = check_scat_numbers(ctx, "extinction", n_scat, n, scat_ext, scat_ext_all, 0.0, HUGE_VAL, false, a->ext, a->ext_all))) return rc;
-    if ((rc = check_scat_numbers(ctx, "single-scattering albedo", n_scat, n, scat_ssa, scat_ssa_all, 0.0, 1.0, false, a->ssa, a->ssa_all))) return rc;
-    if ((rc = check_scat_numbers(ctx, "asymmetry", n_scat, n, scat_asym, scat_asym_all, -1.0, 1.0, true, a->asym, a->asym_all))) return rc;
-    if ((rc = ctx_check_buffer(ctx, workspace, 0, "workspace", true))) return rc;
-    int64_t ws_len = 0, tile_doubles = 0;
-    lbl_buffer_size(workspace, &ws_len);
-    lbl_column_twostream_workspace(n_layers, 1, &tile_doubles);
-    if (ws_len < tile_doubles)
-        return column_fail(ctx, LBL_ERR_BAD_ARG, "workspace: at least %lld doubles (one tile of %d points)", (long long)tile_doubles, kTwoStreamTile);
-    const int64_t ws_points = ws_len / tile_doubles * kTwoStreamTile;
+    if ((rc = check_scatterers(ctx, a, n_layers, n, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa, scat_ssa_all,
+                               scat_asym, scat_asym_all)))
+        return rc;
+    int64_t ws_points = 0;
+    if ((rc = check_workspace(ctx, workspace, kTwoStreamQuantities, n_layers, &ws_points))) return rc;
     a->S0 = buffer_data(S0);
     a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
     a->emissivity_all = emissivity_all;
@@ -476,6 +498,86 @@ extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* 
             launch_twostream_pass((const TwoStreamArgs*)d_args, n_beams, band_first[b], band_first[b] + done,
                                   std::min<int64_t>(ws_points, band_count[b] - done), slots, (double*)partial, s);
         launch_twostream_final(n_layers, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
+    }
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+} LBL_GUARD_END(ctx)
+
+// K5m: the doubles of a workspace that holds `points` points (rounded up to whole tiles, at least one) in one pass
+extern "C" int lbl_column_flux_scatter_workspace(int n_layers, int64_t points, int64_t* doubles) {
+    if (!doubles || n_layers < 0 || n_layers > kMaxLayers || points < 0 || points > (int64_t)1 << 40) return LBL_ERR_BAD_ARG;
+    const int64_t tiles = std::max<int64_t>((points + kTwoStreamTile - 1) / kTwoStreamTile, 1);
+    *doubles = (int64_t)kScatterFluxQuantities * (n_layers + 1) * tiles * kTwoStreamTile;
+    return LBL_OK;
+}
+
+// K5m: check_column with the two-stream angle in place of an angle set (column, temperatures, surface source, bands), what
+// lbl_column_flux_surface_dev checks behind it, then K5l's scatterers and workspace; the launch sequence is K5l's.
+extern "C" int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                           int planck_linear, const double* depth, double range_min, double range_max,
+                                           int64_t n, lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_scat,
+                                           const double* scat_amount, lbl_buffer* const* scat_ext, const double* scat_ext_all,
+                                           lbl_buffer* const* scat_ssa, const double* scat_ssa_all,
+                                           lbl_buffer* const* scat_asym, const double* scat_asym_all, int delta_scaling,
+                                           int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                           lbl_buffer* emissivity, double emissivity_all, lbl_buffer* workspace,
+                                           lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface,
+                                           lbl_buffer* up_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(ScatterFluxArgs), 0);
+    ScatterFluxArgs* a = (ScatterFluxArgs*)blk.data();
+    if (planck_linear != 0 && planck_linear != 1)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "planck_linear must be 0 (layer temperatures) or 1 (edge temperatures)");
+    const double mu = 0.5773502691896258, weight = kPi;      // 1 / sqrt(3) and pi: what the result corresponds to
+    int rc;
+    if ((rc = check_column(ctx, "scattering level fluxes", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
+                           surface_T, 1, &mu, &weight, n_bands, band_first, band_count, planck_linear ? a->pbkT_top : nullptr)))
+        return rc;
+    for (int l = 0; l < n_layers && !planck_linear; ++l)
+        if (!std::isfinite(T[l])) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be finite and > 0", l);
+    if (n_scat < 0 || n_scat > kMaxScatterers) return column_fail(ctx, LBL_ERR_BAD_ARG, "0..%d scatterers", kMaxScatterers);
+    if (n_scat > 0 && n_layers > 0 && !scat_amount) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL scatterer amounts");
+    if (delta_scaling != 0 && delta_scaling != 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "delta_scaling must be 0 or 1");
+    const int nv = 2 * (n_layers + 1);
+    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    if ((rc = check_scatterers(ctx, a, n_layers, n, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa, scat_ssa_all,
+                               scat_asym, scat_asym_all)))
+        return rc;
+    int64_t ws_points = 0;
+    if ((rc = check_workspace(ctx, workspace, kScatterFluxQuantities, n_layers, &ws_points))) return rc;
+    int64_t max_count = 0;
+    for (int b = 0; b < n_bands; ++b) max_count = std::max(max_count, band_count[b]);
+    a->I_top = I_top ? buffer_data(I_top) : nullptr;
+    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a->emissivity_all = emissivity_all;
+    a->workspace = buffer_data(workspace);
+    a->ws_points = ws_points;
+    a->up_top = up_top ? buffer_data(up_top) : nullptr;
+    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
+    a->up_surface = up_surface ? buffer_data(up_surface) : nullptr;
+    a->delta_scaling = delta_scaling;
+
+    void* partial = nullptr;
+    if ((rc = ctx_reduction_scratch(ctx, (size_t)twostream_partials(max_count) * nv * sizeof(double), &partial))) return rc;
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, a, sizeof(ScatterFluxArgs), &d_args))) return rc;
+    const hipStream_t s = ctx_stream(ctx);
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    // (points outside every band keep 0 in the spectra)
+    for (double* p : {a->up_top, a->down_surface, a->up_surface})
+        if (p && n > 0) COLUMN_HIP_TRY(ctx, hipMemsetAsync(p, 0, (size_t)n * sizeof(double), s));
+    for (int b = 0; b < n_bands; ++b) {
+        const int slots = twostream_partials(band_count[b]);
+        COLUMN_HIP_TRY(ctx, hipMemsetAsync(partial, 0, (size_t)slots * nv * sizeof(double), s));
+        for (int64_t done = 0; done < band_count[b]; done += ws_points)
+            launch_scatter_flux_pass((const ScatterFluxArgs*)d_args, planck_linear != 0, band_first[b], band_first[b] + done,
+                                     std::min<int64_t>(ws_points, band_count[b] - done), slots, (double*)partial, s);
+        launch_scatter_flux_final(n_layers, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
     }
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;

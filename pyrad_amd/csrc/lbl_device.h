@@ -398,6 +398,34 @@ void launch_twostream_pass(const TwoStreamArgs* d_args, int n_beams, long long b
 // the fixed-order reduction of a band's slots into level_flux[0 .. 3 (n_layers + 1))
 void launch_twostream_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s);
 
+// Thermal fluxes through scattering layers (K5m, lbl_column_transport.hip: lbl_column_flux_scatter_dev): K5l's layer solution,
+// adding, workspace, tiles and partial slots, with the layers' Planck emission as the source, an emitting Lambertian surface
+// and a downward flux at the top.  Of ColumnRT the angle set is not used (the two-stream angle is built in); the scatterer
+// fields carry TwoStreamArgs' names, so that the kernels share K5l's device functions.  Values per band as K5c's.
+constexpr int kScatterFluxQuantities = 4;  // workspace[q][level][point]: R*, D*, U1, U0 (levels 1 .. L)
+struct ScatterFluxArgs : ColumnRT {
+    double pbkT_top[kMaxLayers];        // planck_linear: 100 h c / k / T at the top edge of layer l; pbkT holds the bottom edge
+    double amount[kMaxScatterers][kMaxLayers];  // scatterer c, layer l; 0 for c >= n_scat
+    const double* ext[kMaxScatterers];          // n points each, or nullptr: the number beside it (0 for c >= n_scat)
+    const double* ssa[kMaxScatterers];
+    const double* asym[kMaxScatterers];
+    double ext_all[kMaxScatterers], ssa_all[kMaxScatterers], asym_all[kMaxScatterers];
+    const double* I_top;                // downward radiance entering at the top, or nullptr: 0
+    const double* emissivity;           // n points, or nullptr: emissivity_all
+    double emissivity_all;
+    double* workspace;                  // kScatterFluxQuantities x (n_layers + 1) x ws_points
+    long long ws_points;                // points of one pass: a whole number of tiles
+    double* up_top;                     // optional spectra
+    double* down_surface;
+    double* up_surface;
+    int32_t delta_scaling, pad;
+};
+// launch_twostream_pass and launch_twostream_final for K5m (`linear`: two edge temperatures per layer); the slots are
+// twostream_partials'
+void launch_scatter_flux_pass(const ScatterFluxArgs* d_args, bool linear, long long band_first, long long first, long long count,
+                              int slots, double* partial, hipStream_t s);
+void launch_scatter_flux_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s);
+
 // Ray-path Jacobians (K5f, lbl_column_transport.hip: lbl_ray_jacobian_dev): K5e's walk, then the segments last to first
 // with K5d's transmittance-and-emission recurrence, one output row per ray, kind and crossed layer.  RayArgs' block with
 // more tables behind it; `radiance` may be nullptr here and `transmittance` is not used.  A ray's rows start at row_first[r]:

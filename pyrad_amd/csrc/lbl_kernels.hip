@@ -33,6 +33,8 @@
 //                              paths, reflected by the surface (Atmosphere.solarFluxes; beyond the reference)
 //   K5l twostream_down_kernel, twostream_up_kernel   the beams through scattering layers: a delta-two-stream solution per
 //                              layer, joined by adding through a workspace (Atmosphere.solarFluxesTwoStream; beyond the reference)
+//   K5m scatter_flux_down_kernel, scatter_flux_up_kernel   K5l with the layers' thermal emission as the source and an emitting
+//                              surface (Atmosphere.fluxesTwoStream; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -4350,6 +4352,84 @@ __global__ __launch_bounds__(256) void solar_diffuse_kernel(const SolarArgs* __r
 // slot (tile of the band) % slots of the partials by the one workgroup that owns the slot, tiles ascending; the passes of a
 // band follow each other in stream order, so a slot's additions are the same whatever the pass size; column_flux_final_kernel
 // finishes.  No float atomics.
+// What the two downward kernels (K5l here, K5m below) share.  Args: TwoStreamArgs or ScatterFluxArgs.
+// a point's scatterers, per unit amount: what each adds to a layer's absorption, scattering and asymmetry-weighted depths
+template <class Args>
+__device__ __forceinline__ void scatterer_numbers(const Args& A, long long j, double (&al)[kMaxScatterers],
+                                                  double (&si)[kMaxScatterers], double (&et)[kMaxScatterers]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < kMaxScatterers; ++c) {
+        const double ext = A.ext[c] ? load_global_f64(A.ext[c], j) : A.ext_all[c];
+        const double ssa = A.ssa[c] ? load_global_f64(A.ssa[c], j) : A.ssa_all[c];
+        const double gc = A.asym[c] ? load_global_f64(A.asym[c], j) : A.asym_all[c];
+        const double f = A.delta_scaling ? gc * gc : 0.0;
+        al[c] = ext * (1.0 - ssa);
+        si[c] = (ext * ssa) * (1.0 - f);
+        et[c] = (ext * ssa) * (gc - f);
+    }
+}
+
+// layer l at a point with absorption coefficient k: its depths and the two-stream solution for diffuse light.  At t == 0
+// (`empty`) R = 0 and T = 1, and nothing else is to be used; `conservative` is den == 0, where Ab = 0.
+struct TwoStreamLayer {
+    double ta, ts, tsg, t, w, g, Da, g1, g2, lam, R, T, Ab;
+    bool empty, conservative;
+};
+template <class Args>
+__device__ __forceinline__ TwoStreamLayer twostream_layer(const Args& A, int l, double k, const double (&al)[kMaxScatterers],
+                                                          const double (&si)[kMaxScatterers],
+                                                          const double (&et)[kMaxScatterers]) {
+#pragma clang fp contract(off)
+    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+    TwoStreamLayer Y;
+    double ta = k * A.depth[l], ts = 0.0, tsg = 0.0;
+#pragma unroll
+    for (int c = 0; c < kMaxScatterers; ++c) {
+        const double am = A.amount[c][l];
+        ta = ta + am * al[c];
+        ts = ts + am * si[c];
+        tsg = tsg + am * et[c];
+    }
+    const double t = ta + ts;
+    const double a = ta / t, b = (t - tsg) / t;
+    const double Da = D * a, Db = D * b;
+    const double g1 = 0.5 * (Db + Da), g2 = 0.5 * (Db - Da);
+    const double lam = sqrt(Da * Db);
+    const double lt = lam * t;
+    const double E = exp_neg_budget(lt);
+    const double g1l = g1 + lam;
+    const double Gam = g2 / g1l;
+    const double oG = ((Da + lam) * (Db + lam)) / (g1l * g1l);
+    const double oE = -expm1(-2.0 * lt);
+    const double den = oG + (Gam * Gam) * oE;
+    const double g1t = g1 * t;
+    Y.ta = ta; Y.ts = ts; Y.tsg = tsg; Y.t = t;
+    Y.w = ts / t; Y.g = ts == 0.0 ? 0.0 : tsg / ts;
+    Y.Da = Da; Y.g1 = g1; Y.g2 = g2; Y.lam = lam;
+    Y.empty = t == 0.0;
+    Y.conservative = den == 0.0;
+    Y.R = den == 0.0 ? g1t / (1.0 + g1t) : (Gam * oE) / den;
+    Y.T = den == 0.0 ? 1.0 / (1.0 + g1t) : (E * oG) / den;
+    if (Y.empty) { Y.R = 0.0; Y.T = 1.0; }
+    Y.Ab = den == 0.0 ? 0.0 : ((-expm1(-lt) * ((Da + lam) / g1l)) * (1.0 - Gam * E)) / den;
+    return Y;
+}
+
+// the layer (R, T, its sources P up and Q down) joined to the stack above it, dn = Rs up + Ds: the stack from the layer's
+// bottom in Rs, Ds (NaN once some layer's t was not finite) and the upward step up_(l+1) = U1 up_l + U0
+__device__ __forceinline__ void twostream_add(double R, double T, double P, double Q, bool bad, double& Rs, double& Ds,
+                                              double& U1, double& U0) {
+#pragma clang fp contract(off)
+    const double c = 1.0 - R * Rs;
+    U1 = T / c;
+    U0 = (R * Ds + P) / c;
+    const double Dn = Q + T * ((Ds + Rs * P) / c);
+    Rs = R + (T * U1) * Rs;
+    Ds = Dn;
+    if (bad) Rs = Ds = __builtin_nan("");
+}
+
 template <int NB>
 __global__ __launch_bounds__(256) void twostream_down_kernel(const TwoStreamArgs* __restrict__ Ap, long long first,
                                                              long long count) {
@@ -4364,16 +4444,7 @@ __global__ __launch_bounds__(256) void twostream_down_kernel(const TwoStreamArgs
     auto ws = [&](int v, int i) -> double& { return W[((long long)v * (L + 1) + i) * row]; };
     constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
     double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
-#pragma unroll
-    for (int c = 0; c < kMaxScatterers; ++c) {
-        const double ext = A.ext[c] ? load_global_f64(A.ext[c], j) : A.ext_all[c];
-        const double ssa = A.ssa[c] ? load_global_f64(A.ssa[c], j) : A.ssa_all[c];
-        const double gc = A.asym[c] ? load_global_f64(A.asym[c], j) : A.asym_all[c];
-        const double f = A.delta_scaling ? gc * gc : 0.0;
-        al[c] = ext * (1.0 - ssa);
-        si[c] = (ext * ssa) * (1.0 - f);
-        et[c] = (ext * ssa) * (gc - f);
-    }
+    scatterer_numbers(A, j, al, si, et);
     double S[NB];
     const double top = load_global_f64(A.S0, j);
 #pragma unroll
@@ -4390,33 +4461,11 @@ __global__ __launch_bounds__(256) void twostream_down_kernel(const TwoStreamArgs
     double k = L > 0 ? load_global_f64(A.abs_coef[L - 1], j) : 0.0;
     for (int l = L - 1; l >= 0; --l) {
         const double k_next = l > 0 ? load_global_f64(A.abs_coef[l - 1], j) : k;
-        double ta = k * A.depth[l], ts = 0.0, tsg = 0.0;
-#pragma unroll
-        for (int c = 0; c < kMaxScatterers; ++c) {
-            const double am = A.amount[c][l];
-            ta = ta + am * al[c];
-            ts = ts + am * si[c];
-            tsg = tsg + am * et[c];
-        }
-        const double t = ta + ts;
+        const TwoStreamLayer lay = twostream_layer(A, l, k, al, si, et);
+        const double t = lay.t, w = lay.w, g = lay.g, Da = lay.Da, g1 = lay.g1, g2 = lay.g2, lam = lay.lam;
+        const double R = lay.R, T = lay.T, Ab = lay.Ab;
+        const bool empty = lay.empty;
         bad = bad || !isfinite(t);
-        const bool empty = t == 0.0;
-        const double a = ta / t, b = (t - tsg) / t, w = ts / t, g = ts == 0.0 ? 0.0 : tsg / ts;
-        const double Da = D * a, Db = D * b;
-        const double g1 = 0.5 * (Db + Da), g2 = 0.5 * (Db - Da);
-        const double lam = sqrt(Da * Db);
-        const double lt = lam * t;
-        const double E = exp_neg_budget(lt);
-        const double g1l = g1 + lam;
-        const double Gam = g2 / g1l;
-        const double oG = ((Da + lam) * (Db + lam)) / (g1l * g1l);
-        const double oE = -expm1(-2.0 * lt);
-        const double den = oG + (Gam * Gam) * oE;
-        const double g1t = g1 * t;
-        double R = den == 0.0 ? g1t / (1.0 + g1t) : (Gam * oE) / den;
-        double T = den == 0.0 ? 1.0 / (1.0 + g1t) : (E * oG) / den;
-        if (empty) { R = 0.0; T = 1.0; }
-        const double Ab = den == 0.0 ? 0.0 : ((-expm1(-lt) * ((Da + lam) / g1l)) * (1.0 - Gam * E)) / den;
         double P = 0.0, Q = 0.0;
 #pragma unroll
         for (int s = 0; s < NB; ++s) {
@@ -4440,13 +4489,8 @@ __global__ __launch_bounds__(256) void twostream_down_kernel(const TwoStreamArgs
             Q = s == 0 ? Tb * Fd : fma(Tb, Fd, Q);
             S[s] = Td * S[s];
         }
-        const double c = 1.0 - R * Rs;
-        const double U1 = T / c;
-        const double U0 = (R * Ds + P) / c;
-        const double Dn = Q + T * ((Ds + Rs * P) / c);
-        Rs = R + (T * U1) * Rs;
-        Ds = Dn;
-        if (bad) Rs = Ds = __builtin_nan("");
+        double U1, U0;
+        twostream_add(R, T, P, Q, bad, Rs, Ds, U1, U0);
         ws(2, l + 1) = U1; ws(3, l + 1) = U0;
         ws(0, l) = Rs; ws(1, l) = Ds; ws(4, l) = direct();
         k = k_next;
@@ -4497,6 +4541,120 @@ __global__ __launch_bounds__(256) void twostream_up_kernel(const TwoStreamArgs* 
             const double s_dn = wave_sum(active ? nan_to_num(dn) : 0.0);
             const double s_F = wave_sum(active ? nan_to_num(F) : 0.0);
             if (lane0) { my[i] = s_up; my[levels + i] = s_dn; my[2 * levels + i] = s_F; }
+        }
+        __syncthreads();
+        double* const slot = partial + ((tile0 + tile) % slots) * nv;
+        for (int t = threadIdx.x; t < nv; t += blockDim.x)
+            slot[t] = slot[t] + ((acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]));
+        __syncthreads();
+    }
+}
+
+// ----------------------------------------------------------------------------------------
+// K5m: thermal fluxes through scattering layers (lbl_column_flux_scatter_dev; the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// K5l's two kernels with the layers' own emission in place of the beams: the layer solution (twostream_layer) and the adding
+// step (twostream_add) are K5l's, the sources are P = Bt Ab + d h up at the layer's top and Q = Bb Ab - d h down at its
+// bottom, with Bt, Bb = pi B at the top and bottom edge, d = Bb - Bt and h = (Ab + 2 R) / (D (t - tsg)) - T: the particular
+// solution pi B(tau) +- d / ((g1 + g2) t) of a Planck function linear in optical depth, with the homogeneous response
+// subtracted and 1 + R - T = Ab + 2 R.  Ab comes without cancellation, so a thin layer emits Ab pi B and not a rounding error.
+//   scatter_flux_down_kernel<LINEAR>  top to bottom from Ds_L = pi I_top; LINEAR = false: one Planck value per layer (d = 0,
+//                                     no h); LINEAR = true: two, the top edge's carried over from the layer above where the
+//                                     two temperatures are equal (a workgroup-uniform test).  Four numbers per level.
+//   scatter_flux_up_kernel            the emitting Lambertian surface, then K5l's upward walk and sums over two rows.
+// A thread holds one point, so the fold's one-exp-per-thread Planck path (successive points of a thread) has nothing to run
+// along: every Planck value is the fold's general expression (planck_budget; the calls exist in the default arithmetic only).
+// Workspace layout, tiles, scalar loads, the partial slots by tile of the band and the absence of atomics are K5l's.
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void scatter_flux_down_kernel(const ScatterFluxArgs* __restrict__ Ap, long long first,
+                                                                long long count) {
+#pragma clang fp contract(off)
+    const ScatterFluxArgs& A = *Ap;
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= count) return;
+    const long long j = first + q;
+    const int L = A.n_layers;
+    const long long row = A.ws_points;
+    double* const W = A.workspace + q;
+    auto ws = [&](int v, int i) -> double& { return W[((long long)v * (L + 1) + i) * row]; };
+    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+    double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
+    scatterer_numbers(A, j, al, si, et);
+    const double nu = linspace_at(j, A.n, A.start, A.stop, A.step);
+    double Rs = 0.0, Ds = A.I_top ? kPi * load_global_f64(A.I_top, j) : 0.0;
+    bool bad = false;
+    ws(0, L) = Rs; ws(1, L) = Ds;
+    double k = L > 0 ? load_global_f64(A.abs_coef[L - 1], j) : 0.0;
+    double B_above = 0.0;                           // LINEAR: pi B at the bottom edge of the layer above
+    for (int l = L - 1; l >= 0; --l) {
+        const double k_next = l > 0 ? load_global_f64(A.abs_coef[l - 1], j) : k;
+        const TwoStreamLayer lay = twostream_layer(A, l, k, al, si, et);
+        bad = bad || !isfinite(lay.t);
+        const double Bb = kPi * planck_budget(nu, A.pa, A.pbkT[l]);
+        double P = Bb * lay.Ab, Q = P;
+        if (LINEAR) {
+            const bool shared_edge = l < L - 1 && A.pbkT_top[l] == A.pbkT[l + 1];
+            const double Bt = shared_edge ? B_above : kPi * planck_budget(nu, A.pa, A.pbkT_top[l]);
+            const double d = Bb - Bt;
+            const double h = (lay.Ab + 2.0 * lay.R) / (D * (lay.t - lay.tsg)) - lay.T;
+            P = Bt * lay.Ab + d * h;
+            Q = Bb * lay.Ab - d * h;
+            B_above = Bb;
+        }
+        if (lay.empty || lay.conservative || lay.ta == 0.0) P = Q = 0.0;       // (nothing absorbs: nothing emits)
+        double U1, U0;
+        twostream_add(lay.R, lay.T, P, Q, bad, Rs, Ds, U1, U0);
+        ws(2, l + 1) = U1; ws(3, l + 1) = U0;
+        ws(0, l) = Rs; ws(1, l) = Ds;
+        k = k_next;
+    }
+}
+
+__global__ __launch_bounds__(256) void scatter_flux_up_kernel(const ScatterFluxArgs* __restrict__ Ap, long long tile0,
+                                                              long long first, long long count, int slots,
+                                                              double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    constexpr int kSlot = 2 * (kMaxLayers + 1);
+    __shared__ double acc[4 * kSlot];                // [wave][up levels 0..L, down levels 0..L]
+    const ScatterFluxArgs& A = *Ap;
+    const int L = A.n_layers;
+    const int levels = L + 1, nv = 2 * levels;
+    const long long row = A.ws_points;
+    double* const my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions)
+    for (long long tile = blockIdx.x; tile < tiles; tile += slots) {
+        const long long q = tile * kTwoStreamTile + threadIdx.x;
+        const bool active = q < count;
+        const long long j = first + q;
+        const double* const W = A.workspace + q;
+        auto ws = [&](int v, int i) { return active ? W[((long long)v * levels + i) * row] : 0.0; };
+        double Rs = ws(0, 0), Ds = ws(1, 0);
+        const bool bad = isnan(Rs) || isnan(Ds);
+        const double nan = __builtin_nan("");
+        const double e = !active ? 1.0 : A.emissivity ? A.emissivity[j] : A.emissivity_all;
+        const double Is = !active ? 0.0 : A.I_surface ? A.I_surface[j]
+                                        : planck_budget(linspace_at(j, A.n, A.start, A.stop, A.step), A.pa, A.pbk_surface);
+        const double albedo = 1.0 - e;
+        double up = (e * (kPi * Is) + albedo * Ds) / (1.0 - albedo * Rs);
+        for (int i = 0; i <= L; ++i) {
+            if (i > 0) {
+                up = ws(2, i) * up + ws(3, i);
+                Rs = ws(0, i); Ds = ws(1, i);
+            }
+            double dn = Rs * up + Ds;
+            if (bad) up = dn = nan;
+            if (active) {
+                if (i == 0) {
+                    if (A.up_surface) A.up_surface[j] = up;
+                    if (A.down_surface) A.down_surface[j] = dn;
+                }
+                if (i == L && A.up_top) A.up_top[j] = up;
+            }
+            const double s_up = wave_sum(active ? nan_to_num(up) : 0.0);
+            const double s_dn = wave_sum(active ? nan_to_num(dn) : 0.0);
+            if (lane0) { my[i] = s_up; my[levels + i] = s_dn; }
         }
         __syncthreads();
         double* const slot = partial + ((tile0 + tile) % slots) * nv;
@@ -6076,6 +6234,24 @@ void launch_twostream_pass(const TwoStreamArgs* d_args, int n_beams, long long b
 
 void launch_twostream_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s) {
     const int nv = 3 * (n_layers + 1);
+    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, slots, nv, level_flux);
+}
+
+// K5m: K5l's pass and final reduction with the thermal kernels and two rows of level sums
+void launch_scatter_flux_pass(const ScatterFluxArgs* d_args, bool linear, long long band_first, long long first, long long count,
+                              int slots, double* partial, hipStream_t s) {
+    if (count <= 0) return;
+    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
+    if (linear)
+        hipLaunchKernelGGL(scatter_flux_down_kernel<true>, dim3((unsigned)tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+    else
+        hipLaunchKernelGGL(scatter_flux_down_kernel<false>, dim3((unsigned)tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+    hipLaunchKernelGGL(scatter_flux_up_kernel, dim3((unsigned)std::min<long long>(tiles, slots)), dim3(kTwoStreamTile), 0, s, d_args,
+                       (first - band_first) / kTwoStreamTile, first, count, slots, partial);
+}
+
+void launch_scatter_flux_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s) {
+    const int nv = 2 * (n_layers + 1);
     hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, slots, nv, level_flux);
 }
 

@@ -1706,7 +1706,8 @@ class Scatterer:
     and >= 0, in the unit the extinction is per (molecules cm^-2 for a cross section in cm^2; 1 where ``extinction`` is the
     layer's optical depth itself); ``extinction`` >= 0, ``singleScatteringAlbedo`` in [0, 1] and ``asymmetry`` in (-1, 1),
     each a number, n values on the column's xAxis or a pair (wavenumbers, values) interpolated onto it.  The spectral
-    quantities are checked against the grid by the call that uses them."""
+    quantities are checked against the grid by the call that uses them.  Atmosphere.fluxesTwoStream takes the same objects
+    for the thermal fluxes."""
 
     def __init__(self, amounts, extinction=1.0, singleScatteringAlbedo=1.0, asymmetry=0.0, name=None):
         try:
@@ -2756,7 +2757,7 @@ class Atmosphere(list):
         delta-two-stream (quadrature) solution per layer and grid point, the layers joined by the adding method, over a
         Lambertian surface of albedo 1 - ``emissivity``; the gas absorbs with the layers' absorption coefficients and
         nothing emits.  With scattering the superposition of solarFluxes() ends for the scattered light only: thermal
-        fluxes() still add to these level by level.
+        fluxes still add to these level by level - fluxesTwoStream()'s, which sees the same scatterers.
 
         ``scatterers``: up to 4 Scatterer objects (see there and rayleighScatterer), each with one amount per layer and an
         extinction, a single-scattering albedo and an asymmetry per grid point; ``deltaScaling``: scale the forward peak
@@ -2821,6 +2822,78 @@ class Atmosphere(list):
         return TwoStreamFluxes(up, down, direct, heat, mu_s, beam_weight, slant, upSpectrum=got["up_top"],
                                downSpectrum=got["down_surface"] + got["direct_surface"] if spectra else None,
                                directSpectrum=got["direct_surface"], upSurfaceSpectrum=got["up_surface"])
+
+    def fluxesTwoStream(self, scatterers=(), deltaScaling=True, surfaceTemperature=None, surfaceSpectrum=None, topSpectrum=None,
+                        emissivity=1.0, planck="layer", levelTemperatures=None, bands=None, spectra=False):
+        """fluxes() through a column that also scatters: the thermal fluxes under clouds and aerosol (beyond the
+        reference).  solarFluxesTwoStream()'s layer solution and adding, with the layers' own emission as the source
+        instead of a beam, over an emitting Lambertian surface; the sum of the two calls is a cloudy column's flux.
+
+        ``scatterers`` and ``deltaScaling`` as solarFluxesTwoStream() takes them; ``surfaceTemperature`` /
+        ``surfaceSpectrum``, ``topSpectrum``, ``emissivity`` (a number in [0, 1], n values or a table; 1: the black
+        surface), ``planck``, ``levelTemperatures``, ``bands`` and ``spectra`` as fluxes() takes them.  Fluxes are
+        hemispheric - an isotropic radiance I is the flux pi I - and the result corresponds to fluxes(angles=[(1 / sqrt(3),
+        pi)]), which it equals to rounding without scatterers.  The formulas are those of lbl_column_flux_scatter_dev
+        (include/pyrad_hip.h): with Bt = pi B at a layer's top level, Bb at its bottom level (both pi B(T_l) for
+        planck="layer"), d = Bb - Bt, R, T the layer's two-stream reflectance and transmittance and Ab = 1 - R - T,
+            h = (Ab + 2 R) / (sqrt(3) (t - tsg)) - T        P = Bt Ab + d h        Q = Bb Ab - d h
+        are what the layer emits upward at its top and downward at its bottom - the source linear in optical depth of
+        planck="linear", through a scattering layer - and the level relations up_(l+1) = T up_l + R dn_(l+1) + P,
+        dn_l = T dn_(l+1) + R up_l + Q are solved exactly between dn_L = pi topSpectrum (or 0) and
+        up_0 = e pi Is + (1 - e) dn_0.
+        Returns a Fluxes with mu = [1 / sqrt(3)] and weight = [pi].  The absorption coefficients are the resident ones;
+        the workspace (four numbers per level and point) stays with the atmosphere, at most 256 MiB - a longer band is
+        done in several passes, with the same bits.  Everything is validated (ValueError) before the device is touched."""
+        layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
+            surfaceSpectrum, surfaceTemperature, [(1.0 / math.sqrt(3.0), pi)], bands)
+        topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
+        first = layers[0]
+        nl, nb = len(layers), len(band_first)
+        scat = _scatterers(scatterers, nl)
+        numbers = [sc._on_grid(first.xAxis) for sc in scat]
+        if not isinstance(deltaScaling, (bool, np.bool_)):
+            raise ValueError("deltaScaling: True or False, not %r" % (deltaScaling,))
+        linear = _planck_source(planck, levelTemperatures)
+        if linear:
+            lev = self._level_temperatures(levelTemperatures)
+            T = np.column_stack([lev[:-1], lev[1:]])
+        else:
+            T = [L.T for L in layers]
+        emissivity = _surface_emissivity(emissivity, first.xAxis)
+        depth = [L.depth for L in layers]
+        res = utils.BASE_RESOLUTION
+        ctx = _ctx()
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        st = _kept_state(self, "_scatter_flux_state")
+        st.reserve(ctx, max(n, nb * 2 * (nl + 1)))
+        I_surface = st.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
+        I_top = st.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
+        emissivity = self._device_emissivity(ctx, st, emissivity)
+        columns = []
+        for c, triple in enumerate(numbers):
+            columns.append([v if isinstance(v, float) else st.buf(ctx, "scat%d_%d" % (c, q)).upload(v)
+                            for q, v in enumerate(triple)])
+        # the workspace: the widest band in one pass where 256 MiB hold it, else as many whole tiles as they hold
+        tile = ctx.column_flux_scatter_workspace(nl, 1)
+        want = ctx.column_flux_scatter_workspace(nl, max(band_count))
+        wst = _kept_state(self, "_scatter_flux_workspace")
+        wst.reserve(ctx, min(want, max(TWOSTREAM_WORKSPACE_BYTES // 8 // tile, 1) * tile))
+        level = st.buf(ctx, "level")
+        names = ("up_top", "down_surface", "up_surface")
+        spec = {name: st.buf(ctx, name) if spectra else None for name in names}
+        ctx.column_flux_scatter_dev(kbufs, T, int(linear), depth, first.rangeMin, first.rangeMax, n,
+                                    [sc.amounts for sc in scat], [t[0] for t in columns], [t[1] for t in columns],
+                                    [t[2] for t in columns], int(bool(deltaScaling)), band_first, band_count,
+                                    wst.buf(ctx, "workspace"), level, emissivity=emissivity, I_surface=I_surface,
+                                    surface_T=float(surfaceTemperature or 0.0), I_top=I_top, **spec)
+        sums = level.download(nb * 2 * (nl + 1)).reshape(nb, 2, nl + 1) * res
+        up, down = sums[:, 0, :], sums[:, 1, :]
+        heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], depth)
+        up, down, heat = _band_values(bands, [up, down, heat])
+        return Fluxes(up, down, heat, mu, weight,
+                      upSpectrum=spec["up_top"].download(n) if spectra else None,
+                      downSpectrum=spec["down_surface"].download(n) if spectra else None,
+                      upSurfaceSpectrum=spec["up_surface"].download(n) if spectra else None)
 
     def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False,
                   temperature="planck", emissivity=None, reflection="lambertian", topSpectrum=None):
