@@ -172,7 +172,11 @@ int lbl_device_info(lbl_ctx* ctx, char* name, int name_len, int* n_cu, int64_t* 
  *                            per SIMD, else 16; exact mode - 32 except for launches of 12-16 waves per SIMD (one round of the
  *                            chip's wave slots at four per SIMD, two at three).  Results of the two builds agree to ~1e-15
  *                            (different summation orders), each is reproducible bit for bit.
- *   "accum_far_min_window"   windows below this many points take the skewed-range kernel even where the far-field
+ *   "accum_reach_skip"       1 (default): the line prep keeps the largest Gaussian cut-off of every block of 256 records, and a
+ *                            chunk of far lines that lies beyond the largest cut-off of its span's blocks skips the
+ *                            per-record test "does the Gaussian part still reach the span" | 0: every chunk forms the test.
+ *                            The results are the same bit for bit; the switch exists for A/B runs and the tests
+ *   "accum_far_min_window"  windows below this many points take the skewed-range kernel even where the far-field
  *                            kernel could run them (0, the default: its own limit, 640; measured flat up to 1000)
  *   "debug_ablate"           ONLY in diagnostic builds of the library (make EXTRA=-DLBL_DIAG): timing experiments,
  *                            bits switch off parts of kernels, results are wrong.  The production library has no

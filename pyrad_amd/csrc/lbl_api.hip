@@ -77,6 +77,7 @@ struct lbl_ctx {
     int accum_R = 0;         // points per lane, 0 = choose per launch
     int accum_LS = 0;        // waves sharing one span of points (line split), 0 = choose per launch
     int gauss_run = 0;       // points per lane of a Gaussian run in the far-field kernel's production shape: 0 = by the launch's wave count, 16, 32
+    int reach_skip = 1;      // the far loop skips the Gaussian-reach test of chunks beyond the largest cut-off of the span's record blocks (0: never, for A/B)
     int bal_workers[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // resident wavefronts of the balanced kernel per R (cached)
     // schedule cache: (job, tile) lists sorted longest first, per launch group
     struct Schedule {
@@ -555,7 +556,7 @@ void comm_prof_end(lbl_ctx* ctx, void* start) { prof_end(ctx, PROF_GATHER, (hipE
 // before (lbl_capture_end) would go on replaying the old ones.  A change of any option therefore bumps the context's epoch:
 // lbl_graph_launch reports the graph stale (LBL_ERR_STATE) and the caller captures again (engine.StepGraph does by itself).
 static uint64_t option_state(const lbl_ctx* c) {
-    const long long v[] = {c->accum_variant, c->accum_R, c->accum_LS, c->gauss_run, c->lpt, c->tile_order, c->skew, c->skew_R, c->skew_LS, c->xcd_chunks, c->xcd_pack, c->xcd_tol, c->far_min_H,
+    const long long v[] = {c->accum_variant, c->accum_R, c->accum_LS, c->gauss_run, c->reach_skip, c->lpt, c->tile_order, c->skew, c->skew_R, c->skew_LS, c->xcd_chunks, c->xcd_pack, c->xcd_tol, c->far_min_H,
                            c->ablate, c->accuracy, c->sweep_ieee, c->sched_build, c->no_fuse ? 1 : 0,
                            c->bal_workers[1], c->bal_workers[2], c->bal_workers[4], c->bal_workers[8]};
     uint64_t h = 1469598103934665603ull;
@@ -621,6 +622,9 @@ static int set_option_value(lbl_ctx* ctx, const char* key, int value) {
     } else if (!strcmp(key, "accum_gauss_run")) {
         if (value != 0 && value != 16 && value != 32) return fail(ctx, LBL_ERR_BAD_ARG, "accum_gauss_run must be 0 (auto), 16 or 32");
         ctx->gauss_run = value;
+    } else if (!strcmp(key, "accum_reach_skip")) {
+        if (value < 0 || value > 1) return fail(ctx, LBL_ERR_BAD_ARG, "accum_reach_skip must be 0 or 1");
+        ctx->reach_skip = value;
     } else if (!strcmp(key, "accum_far_min_window")) {
         if (value < 0) return fail(ctx, LBL_ERR_BAD_ARG, "accum_far_min_window must be >= 0");
         ctx->far_min_H = value;
@@ -1301,12 +1305,17 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
     const size_t prep_bytes = (((size_t)n_lists * sizeof(PrepJob) + (size_t)n_merged_jobs * sizeof(MergedPrep)) + 15) & ~(size_t)15;
     const size_t acc_bytes = (size_t)n_jobs * sizeof(AccumJob);
     const size_t cnt_bytes = (size_t)n_lists * std::max(blocks_per_job, 1) * 3 * sizeof(unsigned int);
-    if ((rc = arena_reserve(ctx, ctx->counts, cnt_bytes))) return rc;
+    // behind them: the largest Gaussian cut-off per block of 256 records (one int32 per block; a merged job's array, in
+    // merged order, takes the slot of its first list)
+    const size_t reach_bytes = (size_t)n_lists * std::max(blocks_per_job, 1) * sizeof(int32_t);
+    if ((rc = arena_reserve(ctx, ctx->counts, cnt_bytes + reach_bytes))) return rc;
     // descriptors are built in pageable host memory first: a batch that repeats (the usual case:
     // same layer, step after step) finds its descriptor block already on the device and skips the copy
     ctx->desc_build.assign(prep_bytes + acc_bytes, 0);
     void* stage = ctx->desc_build.data();
     unsigned int* d_counts = (unsigned int*)ctx->counts.ptr;
+    int32_t* d_reach = (int32_t*)((char*)ctx->counts.ptr + cnt_bytes);
+    auto job_reach = [&](int j) { return d_reach + (size_t)l0(j) * std::max(blocks_per_job, 1); };
 
     // Jobs of one batch can have very different windows (a column: W = 5000 at the surface,
     // 50 at 10 mbar).  A wave must not own more points than a line's support is wide, so jobs are
@@ -1416,6 +1425,7 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
             m.hot = (HotRec*)ctx->recs.ptr + base; m.cold = (ColdRec*)ctx->cold.ptr + base; m.cidx = (int32_t*)ctx->cidx.ptr + base;
             m.first_list = l0(j); m.n_lists = l1(j) - l0(j);
             m.n_total = (int32_t)job_lines[j]; m.blocks = (int32_t)((job_lines[j] + 255) / 256);
+            m.block_reach = job_reach(j);
         }
         for (int l = l0(j); l < l1(j); ++l) {
             ctx->last_list_blocks[l] = job_src[j] ? (int)((job_lines[j] + 255) / 256) : (int)((lines[l]->n + 255) / 256);
@@ -1432,6 +1442,7 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
             p.merged = scattered ? 1 : 0;
             p.weight = merge ? merge->weight[l] : 1.0;
             p.block_counts = d_counts + (size_t)l * blocks_per_job * 3;
+            p.block_reach = scattered ? nullptr : d_reach + (size_t)l * std::max(blocks_per_job, 1);
             prep_job_physics(p, iso[l], grid[j]);
             p.gauss_cut = ctx->accuracy ? 17179869184.0 : 18014398509481984.0;          // 2^34 : 2^54
             p.n_lines = (int32_t)L->n;
@@ -1465,6 +1476,8 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
             a.ablate = ctx->ablate;
             a.span_tab = g.tabs ? g.tabs + g.tab_off[(size_t)(k - g.first)] : nullptr;
             a.out_scale = merge ? merge->out_scale[j] : 1.0;
+            // (one list, or several prepared in merged order: the blocks of the line prep are the blocks of this job's records)
+            if (ctx->reach_skip && (l1(j) - l0(j) == 1 || job_src[j])) a.block_reach = job_reach(j);
             if (fuse && n_jobs == 1) {
                 a.chain_flags = CHAIN_MOL_FIRST | CHAIN_MOL_LAST;
                 a.conc = fuse_conc;

@@ -93,6 +93,10 @@ struct AccumJob {
     // Every sum leaves the kernel multiplied by out_scale: 1.0 for a line list's cross section (x * 1.0 is exact), and the
     // power of two 2^e that a merged layer job's record weights were divided by (exact as well), see PrepJob.weight.
     double out_scale;
+    // The largest Gaussian cut-off (HotRec.dgi) of every block of 256 records of this job, written by the line prep of the
+    // same batch: the far loop skips the per-record reach test of chunks that lie beyond the largest cut-off of the span's
+    // blocks.  NULL (lbl_set_option "accum_reach_skip" 0, or records not prepared in this form): every chunk forms the test.
+    const int32_t* block_reach;
     FusedSweep fuse;       // fuse.on: sweep every point right after its sum is final
 };
 enum : int32_t { CHAIN_MOL_FIRST = 1, CHAIN_MOL_LAST = 2 };
@@ -129,6 +133,9 @@ struct PrepJob {
     int32_t merged;
     int32_t pad2;
     double weight;
+    // [blocks of 256 lines]: the largest HotRec.dgi of every block, one plain store per block (a list of a merged job: not
+    // used, its job's MergedPrep carries the array in merged order); NULL: not written
+    int32_t* block_reach;
 };
 
 static_assert(sizeof(PrepJob) % 8 == 0, "line_prep_merged_kernel copies PrepJob blocks to LDS in 8-byte words");
@@ -139,6 +146,7 @@ struct MergedPrep {
     HotRec* hot; ColdRec* cold; int32_t* cidx;       // the job's record arrays
     int32_t first_list, n_lists;                     // the job's lists in the PrepJob array
     int32_t n_total, blocks;                         // lines of all its lists; ceil(n_total / 256)
+    int32_t* block_reach;                            // [blocks]: the largest HotRec.dgi of every 256 merged positions; NULL: not written
 };
 void launch_line_prep_merged(const PrepJob* d_lists, const MergedPrep* d_jobs, int n_jobs, int max_total, hipStream_t s);
 

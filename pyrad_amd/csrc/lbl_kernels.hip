@@ -359,11 +359,25 @@ __device__ __forceinline__ void prep_one_line(const PrepJob& J, int i, HotRec& r
     rc.KLd = r.KL;
 }
 
+__device__ __forceinline__ int wave_max_i32(int v);
+
+// The largest Gaussian cut-off dgi of a block of 256 prepared positions, for the far loop of the accumulate kernel: a far
+// chunk farther from its span than the largest cut-off of the span's blocks cannot hold a record whose Gaussian part
+// reaches the span, and skips the per-record test (far_field_lines).  A wave maximum, the block's LDS and one plain store
+// per block, like the regime counters; called by every thread of the block between two barriers of its caller's.
+__device__ __forceinline__ void block_reach_stage(int dgi, int* s_reach) {
+    const int m = wave_max_i32(dgi);
+    if ((threadIdx.x & 63) == 0) s_reach[threadIdx.x >> 6] = m;
+}
+__device__ __forceinline__ int block_reach_value(const int* s_reach) {
+    return max(max(s_reach[0], s_reach[1]), max(s_reach[2], s_reach[3]));
+}
+
 __global__ __launch_bounds__(256) void line_prep_kernel(const PrepJob* __restrict__ jobs) {
     const PrepJob& J = jobs[blockIdx.y];
     if (J.merged) return;                       // (its job's merged-order launch prepares this list)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    int regime = -1;
+    int regime = -1, dgi = 0;
     if (i < J.n_lines) {
         HotRec r;
         ColdRec rc;
@@ -372,7 +386,10 @@ __global__ __launch_bounds__(256) void line_prep_kernel(const PrepJob* __restric
         J.hot[i] = r;
         J.cold[i] = rc;
         J.cidx[i] = (int32_t)idx;
+        dgi = r.dgi;
     }
+    __shared__ int s_reach[4];
+    block_reach_stage(dgi, s_reach);
     // regime counters (pyradClasses.py:368-370, 406).  One plain store per block: thousands of
     // atomics on one cache line cost ~12 ns each and made this kernel 3x longer than its arithmetic.
     __shared__ unsigned int s_cnt[4][3];
@@ -385,6 +402,7 @@ __global__ __launch_bounds__(256) void line_prep_kernel(const PrepJob* __restric
     if (threadIdx.x < 3)
         J.block_counts[blockIdx.x * 3 + threadIdx.x] =
             s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x] + s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x];
+    if (threadIdx.x == 64 && J.block_reach) J.block_reach[blockIdx.x] = block_reach_value(s_reach);
 }
 
 // K1 of a merged layer job, in MERGED order: thread t prepares the line that belongs at position t of the layer's record
@@ -406,7 +424,7 @@ __global__ __launch_bounds__(256) void line_prep_merged_kernel(const PrepJob* __
         for (int w = threadIdx.x; w < words; w += blockDim.x) dst[w] = src[w];
         __syncthreads();
     }
-    int regime = -1, list = -1;
+    int regime = -1, list = -1, dgi = 0;
     if (t < M.n_total) {
         const int s = M.src[t];
         list = (int)((unsigned int)s >> 26);
@@ -418,7 +436,11 @@ __global__ __launch_bounds__(256) void line_prep_merged_kernel(const PrepJob* __
         M.hot[t] = r;
         M.cold[t] = rc;
         M.cidx[t] = (int32_t)idx;
+        dgi = r.dgi;
     }
+    // the largest Gaussian cut-off of the block's 256 merged positions
+    __shared__ int s_reach[4];
+    block_reach_stage(dgi, s_reach);
     // regime counters per list and block of 256 merged positions
     __shared__ unsigned int s_cnt[4][kMaxIso][3];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -432,6 +454,7 @@ __global__ __launch_bounds__(256) void line_prep_merged_kernel(const PrepJob* __
         const int l = q / 3, k = q % 3;
         lists[M.first_list + l].block_counts[blockIdx.x * 3 + k] = s_cnt[0][l][k] + s_cnt[1][l][k] + s_cnt[2][l][k] + s_cnt[3][l][k];
     }
+    if (threadIdx.x == 64 && M.block_reach) M.block_reach[blockIdx.x] = block_reach_value(s_reach);
 }
 
 // lbl_line_quantities: the per-line numbers of the reference (Line.lorentzHW / gaussianHW, the corrected intensity,
@@ -1200,12 +1223,20 @@ __device__ __forceinline__ void wave_sum_rows(double (&C)[NT], double* scratch, 
 // the line's own smallest term on the span): d >= 8: 20 terms (2.7e-17), d >= 16: 15 (1.7e-17), d >= 32: 12 (1.2e-17).
 // Budget mode (NT = 18, 5.9e-10): d >= 8: 12 (2.8e-10), d >= 16: 9 (1.8e-10), d >= 32: 7 (2.6e-10).  With a window of
 // +-39 half-spans two thirds of the far lines are beyond 16 half-spans: 17 terms on average instead of 30.
+// The classes as {d, terms} pairs, nearest first (tests/test_far_terms_cpu.py reads these two lines and holds every pair
+// to the remainder bound of its mode):
+constexpr int kFarClassExact[5][2] = {{3, 38}, {4, 30}, {8, 20}, {16, 15}, {32, 12}};
+constexpr int kFarClassBudget[4][2] = {{4, 18}, {8, 12}, {16, 9}, {32, 7}};
+static_assert(kFarClassExact[0][0] == FF_MID && kFarClassExact[0][1] == FF_NT_MID && kFarClassExact[1][0] == FF_FAR && kFarClassExact[1][1] == FF_NT &&
+              kFarClassBudget[0][0] == FF_FAR_BUDGET && kFarClassBudget[0][1] == FF_NT_BUDGET, "the nearest classes are the builds' own thresholds and term counts");
+static_assert(kFarClassExact[2][0] == 8 && kFarClassExact[3][0] == 16 && kFarClassExact[4][0] == 32 && kFarClassBudget[1][0] == 8 &&
+              kFarClassBudget[2][0] == 16 && kFarClassBudget[3][0] == 32, "far_chunk and the edge series branch at 8, 16 and 32 half-spans");
 template <int NT> struct FarTerms {
     static constexpr bool exact = NT == FF_NT || NT == FF_NT_MID, budget = NT == FF_NT_BUDGET;
-    static constexpr int t4 = budget ? 18 : (NT == FF_NT_MID ? FF_NT : NT);     // (from 4 half-spans on: 30 terms; nearer, NT = 38: the build whose series starts at 3)
-    static constexpr int t8 = exact ? 20 : (budget ? 12 : NT);
-    static constexpr int t16 = exact ? 15 : (budget ? 9 : NT);
-    static constexpr int t32 = exact ? 12 : (budget ? 7 : NT);
+    static constexpr int t4 = budget ? kFarClassBudget[0][1] : (NT == FF_NT_MID ? kFarClassExact[1][1] : NT);     // (from 4 half-spans on: 30 terms; nearer, NT = 38: the build whose series starts at 3)
+    static constexpr int t8 = exact ? kFarClassExact[2][1] : (budget ? kFarClassBudget[1][1] : NT);
+    static constexpr int t16 = exact ? kFarClassExact[3][1] : (budget ? kFarClassBudget[2][1] : NT);
+    static constexpr int t32 = exact ? kFarClassExact[4][1] : (budget ? kFarClassBudget[3][1] : NT);
 };
 
 // q_N0 .. q_{N1-1} of one line per lane added to the per-lane sums (qa, qb: q_{N0-2}, q_{N0-1}; carried on)
@@ -1235,37 +1266,36 @@ __device__ __forceinline__ void series_terms(double al, double bp, double& qa, d
 // A record beyond the cap (several atmospheres, finer grids) keeps the four-point pass here.
 constexpr int FF_GAUSS_CAP = 8;
 
-// Series coefficients of the far lines m0, m0+stride*k.. (chunks of 64, one line per lane) below m1.
-template <int R, int NT, bool GROUTE = false>
-__device__ __forceinline__ void far_field_lines(const HotRec* hot, const ColdRec* cold, int m0, int m1, int stride,
-                                                double xc, int wlo, int whi, double x0, double Hf, double* lh, double* lc,
-                                                int lane, double (&C)[NT], WaveAcc<R>& S, int& g_lo, int& g_hi) {
-    // (the records of a call are all far lines: with the series from FF_MID on, the lines between FF_MID and FF_FAR
-    // half-spans are among them - inside the cap, so on the only shape that has them their Gaussian parts go to the near walk)
-    static_assert(GROUTE || NT != FF_NT_MID, "the mid class needs the near walk to take its Gaussian parts");
+// One chunk of far_field_lines: 64 records (PARTIAL: the nv = m1 - c0 < 64 first lanes; the others hold a copy of the call's
+// last record and count for nothing), one per lane, in w0, w1.
+template <int R, int NT, bool GROUTE, bool PARTIAL>
+__device__ __forceinline__ void far_chunk(const double __attribute__((ext_vector_type(2))) w0, const double __attribute__((ext_vector_type(2))) w1,
+                                          const ColdRec* cold, int c0, int m1, int reach_lim, double xc, int wlo, int whi,
+                                          double x0, double Hf, double* lh, double* lc, int lane, double (&C)[NT], WaveAcc<R>& S,
+                                          int& g_lo, int& g_hi) {
+    // (every fused multiply-add of the series is spelled fma(); the products and sums beside them stay two roundings in
+    // both copies of this body, whatever the compiler would make of each: the copies must agree to the last bit)
+#pragma clang fp contract(off)
     typedef double v2f64 __attribute__((ext_vector_type(2)));
     typedef const v2f64 __attribute__((address_space(1)))* GlobalF64x2;
-    const GlobalF64x2 gh = (GlobalF64x2)(unsigned long long)hot;
-    const GlobalF64x2 gc = (GlobalF64x2)(unsigned long long)cold;
     const double hh = 32.0 * R;
-    v2f64 h0 = {0, 1}, h1 = {0, 0};
-    if (m0 + lane < m1) {
-        const long long r = (long long)(m0 + lane) * 2;
-        h0 = gh[r]; h1 = gh[r + 1];
-    }
-    for (int c0 = m0; c0 < m1; c0 += stride) {
-        const bool valid = c0 + lane < m1;
-        const v2f64 w0 = h0, w1 = h1;
-        if (c0 + stride + lane < m1) {
-            const long long r = (long long)(c0 + stride + lane) * 2;
-            h0 = gh[r]; h1 = gh[r + 1];
-        }
-        const int ci = (int)w0.x;
+    const int ci = (int)w0.x;
+    // the chunk's nearest line (centres are sorted and a call stays on one side of the span: the first or the last
+    // valid lane) decides how many terms the whole chunk takes; wave-uniform branches.  In integers (a centre is an
+    // integer, xc = wlo + 32 R - 1/2): dmin2 = 2 |c - xc| from two v_readlane and scalar arithmetic instead of four
+    // v_readlane and six fp64 vector instructions; the class limits are d half-spans = 32 R d points.
+    const int nv = PARTIAL ? m1 - c0 : 64;
+    const int ca = __builtin_amdgcn_readlane(ci, 0), cb = __builtin_amdgcn_readlane(ci, nv - 1);
+    const int dmin2 = min(abs(2 * (ca - wlo) - (64 * R - 1)), abs(2 * (cb - wlo) - (64 * R - 1)));
+    // Gaussian parts that still reach the span.  A record reaches it only if its distance from the span's nearest point,
+    // at least dmin2 / 2 - 32 R + 1/2 for every record of the chunk, is below its cut-off dgi <= reach: a chunk with
+    // dmin2 >= reach_lim = 2 (reach + 32 R) + 1 has none and forms neither the per-lane test nor its ballot.
+    if (dmin2 < reach_lim) {
         const int dgi = __double2loint(w1.y), fl = __double2hiint(w1.y);
-        bool gauss = valid && max(0, max(ci - whi, wlo - ci)) < dgi;
+        bool gauss = (!PARTIAL || lane < nv) && max(0, max(ci - whi, wlo - ci)) < dgi;
         unsigned long long gmask = __ballot(gauss);
         if (GROUTE && gmask) {                         // (a chunk without such a record - most of them - pays the one ballot)
-            // inside the cap: 2 |c - xc| < 2 * FF_GAUSS_CAP half-spans, in integers as dmin2 below (the left side is odd: no tie)
+            // inside the cap: 2 |c - xc| < 2 * FF_GAUSS_CAP half-spans, in integers as dmin2 above (the left side is odd: no tie)
             const bool routed = abs(2 * (ci - wlo) - (64 * R - 1)) < 2 * FF_GAUSS_CAP * 32 * R;
             const unsigned long long rmask = __ballot(gauss && routed);      // wave-uniform, like c0: scalar registers
             if (rmask) {
@@ -1277,6 +1307,7 @@ __device__ __forceinline__ void far_field_lines(const HotRec* hot, const ColdRec
         }
         if (gmask) {                                   // (GROUTE: beyond the cap only - very wide profiles)
             const unsigned long long emask = __ballot((fl & REC_NO_RECUR) != 0);
+            const GlobalF64x2 gc = (GlobalF64x2)(unsigned long long)cold;
             v2f64 c0v = {0, 0}, c1v = {0, 0};
             if (gauss) {
                 const long long r = (long long)(c0 + lane) * 2;
@@ -1293,36 +1324,72 @@ __device__ __forceinline__ void far_field_lines(const HotRec* hot, const ColdRec
             chunk_extras<R, 0>(lh, lc, gmask, emask, 0ull, ~0ull, x0, Hf, S, 0ull, 0.0, lane, unused);
             __builtin_amdgcn_wave_barrier();
         }
-        const double dl = w0.x - xc;
-        const double sq = fma(dl, dl, w0.y);
-        double be = __builtin_amdgcn_rcp(sq);
-        be = fma(fma(-sq, be, 1.0), be, be);
-        be = fma(fma(-sq, be, 1.0), be, be);
-        const double al = (dl * (2.0 * hh)) * be;
-        const double bp = (hh * hh) * be;
-        double qa = (valid ? w1.x : 0.0) * be;
-        C[0] += qa;
-        double qb = al * qa;
-        C[1] += qb;
-        // the chunk's nearest line (centres are sorted and a call stays on one side of the span: the first or the last
-        // valid lane) decides how many terms the whole chunk takes; wave-uniform branches.  In integers (a centre is an
-        // integer, xc = wlo + 32 R - 1/2): dmin2 = 2 |c - xc| from two v_readlane and scalar arithmetic instead of four
-        // v_readlane and six fp64 vector instructions; the class limits are d half-spans = 32 R d points.
-        const int nv = min(64, m1 - c0);
-        const int ca = __builtin_amdgcn_readlane(ci, 0), cb = __builtin_amdgcn_readlane(ci, nv - 1);
-        const int dmin2 = min(abs(2 * (ca - wlo) - (64 * R - 1)), abs(2 * (cb - wlo) - (64 * R - 1)));
-        typedef FarTerms<NT> FT;
-        series_terms<2, FT::t32, NT>(al, bp, qa, qb, C);
-        if (dmin2 < 2 * 32 * 32 * R) {
-            series_terms<FT::t32, FT::t16, NT>(al, bp, qa, qb, C);
-            if (dmin2 < 2 * 16 * 32 * R) {
-                series_terms<FT::t16, FT::t8, NT>(al, bp, qa, qb, C);
-                if (dmin2 < 2 * 8 * 32 * R) {
-                    series_terms<FT::t8, FT::t4, NT>(al, bp, qa, qb, C);
-                    if (FT::t4 < NT && dmin2 < 2 * 4 * 32 * R) series_terms<FT::t4, NT, NT>(al, bp, qa, qb, C);
-                }
+    }
+    const double dl = w0.x - xc;
+    const double sq = fma(dl, dl, w0.y);
+    double be = __builtin_amdgcn_rcp(sq);
+    be = fma(fma(-sq, be, 1.0), be, be);
+    be = fma(fma(-sq, be, 1.0), be, be);
+    const double al = (dl * (2.0 * hh)) * be;
+    const double bp = (hh * hh) * be;
+    double qa = (PARTIAL ? (lane < nv ? w1.x : 0.0) : w1.x) * be;       // (only a call's last chunk can have lanes without a record)
+    C[0] += qa;
+    double qb = al * qa;
+    C[1] += qb;
+    typedef FarTerms<NT> FT;
+    series_terms<2, FT::t32, NT>(al, bp, qa, qb, C);
+    if (dmin2 < 2 * 32 * 32 * R) {
+        series_terms<FT::t32, FT::t16, NT>(al, bp, qa, qb, C);
+        if (dmin2 < 2 * 16 * 32 * R) {
+            series_terms<FT::t16, FT::t8, NT>(al, bp, qa, qb, C);
+            if (dmin2 < 2 * 8 * 32 * R) {
+                series_terms<FT::t8, FT::t4, NT>(al, bp, qa, qb, C);
+                if (FT::t4 < NT && dmin2 < 2 * 4 * 32 * R) series_terms<FT::t4, NT, NT>(al, bp, qa, qb, C);
             }
         }
+    }
+}
+
+// Series coefficients of the far lines m0, m0+stride*k.. (chunks of 64, one line per lane) below m1.  stride: 64 LS, LS a
+// power of two up to 8.  reach_lim: see far_chunk (INT_MAX: no bound on the records' cut-offs is known).
+// The full chunks run without a validity mask; the call's last chunk, if partial, is a copy of the loop body of its own.
+// A lane's record address is a scalar base plus a 32-bit byte offset that advances by 32 stride per chunk, clamped to the
+// call's last record (so that every lane of every load is in bounds without a per-lane branch); the offsets of a call
+// stay below 2^32 because a call of more than 2^26 records is walked in pieces of 2^26 (a whole number of strides).
+template <int R, int NT, bool GROUTE = false>
+__device__ __forceinline__ void far_field_lines(const HotRec* hot, const ColdRec* cold, int m0, int m1, int stride, int reach_lim,
+                                                double xc, int wlo, int whi, double x0, double Hf, double* lh, double* lc,
+                                                int lane, double (&C)[NT], WaveAcc<R>& S, int& g_lo, int& g_hi) {
+    // (the records of a call are all far lines: with the series from FF_MID on, the lines between FF_MID and FF_FAR
+    // half-spans are among them - inside the cap, so on the only shape that has them their Gaussian parts go to the near walk)
+    static_assert(GROUTE || NT != FF_NT_MID, "the mid class needs the near walk to take its Gaussian parts");
+    typedef double v2f64 __attribute__((ext_vector_type(2)));
+    typedef const char __attribute__((address_space(1)))* GlobalBytes;
+    typedef const v2f64 __attribute__((address_space(1)))* GlobalF64x2;
+    constexpr int PIECE = 1 << 26;
+    for (int p0 = m0; p0 < m1;) {
+        const int p1 = m1 - p0 > PIECE ? p0 + PIECE : m1;
+        const GlobalBytes base = (GlobalBytes)(unsigned long long)(hot + p0);
+        const unsigned int last = (unsigned int)(p1 - 1 - p0) * 32u;
+        unsigned int off = (unsigned int)lane * 32u;
+        v2f64 h0, h1;
+        auto fetch = [&](v2f64& h0, v2f64& h1) {
+            const GlobalF64x2 r = (GlobalF64x2)(base + min(off, last));
+            h0 = r[0]; h1 = r[1];
+            off += (unsigned int)stride * 32u;
+        };
+        fetch(h0, h1);
+        int c0 = p0;
+        // (the chunk loop unrolled by two, with two register sets swapping roles instead of one rotating into the other,
+        // was built and measured: 0.07e6 fewer vector and 0.42e6 more scalar instructions per merged C3 launch on the
+        // three-waves-per-SIMD build, 20-52 bytes of scratch per lane on the builds held to 128 registers - not kept)
+        for (; c0 + 64 <= p1; c0 += stride) {
+            const v2f64 w0 = h0, w1 = h1;
+            if (c0 + stride < p1) fetch(h0, h1);
+            far_chunk<R, NT, GROUTE, false>(w0, w1, cold, c0, p1, reach_lim, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, g_lo, g_hi);
+        }
+        if (c0 < p1) far_chunk<R, NT, GROUTE, true>(h0, h1, cold, c0, p1, reach_lim, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, g_lo, g_hi);
+        p0 = p1;
     }
 }
 
@@ -1832,8 +1899,19 @@ void xsec_accumulate_lds_kernel(const AccumJob* __restrict__ jobs, const int2* _
             // (EDGE_SKEW: the Gaussian parts of the far records inside FF_GAUSS_CAP half-spans belong to the near walk below;
             // the two calls widen [iG1, iG2) to hold them.  Line-split shapes keep them here: their waves are dealt whole far
             // chunks and would have to agree on the range across a workgroup barrier this kernel does not have at this point.)
-            far_field_lines<R, NTC, EDGE_SKEW>(J.hot, J.cold, iB + ((part + 1) % LS) * 64, iN1, 64 * LS, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, iG1, iG2);
-            far_field_lines<R, NTC, EDGE_SKEW>(J.hot, J.cold, iN2 + ((part + 2) % LS) * 64, iC, 64 * LS, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, iG1, iG2);
+            // the largest Gaussian cut-off of the record blocks that meet [iB, iC), once per span (one block per lane, a wave
+            // maximum), as the distance in dmin2's units from which a far chunk skips its reach test (far_chunk)
+            int reach_lim = INT_MAX;
+            if (J.block_reach) {
+                int r = 0;
+                const int b1 = (iC - 1) >> 8;
+                for (int b = iB >> 8; b <= b1; b += 64)
+                    if (b + lane <= b1) r = max(r, J.block_reach[b + lane]);
+                const int reach = wave_max_i32(r);
+                if (reach < (1 << 29)) reach_lim = 2 * (reach + 32 * R) + 1;
+            }
+            far_field_lines<R, NTC, EDGE_SKEW>(J.hot, J.cold, iB + ((part + 1) % LS) * 64, iN1, 64 * LS, reach_lim, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, iG1, iG2);
+            far_field_lines<R, NTC, EDGE_SKEW>(J.hot, J.cold, iN2 + ((part + 2) % LS) * 64, iC, 64 * LS, reach_lim, xc, wlo, whi, x0, Hf, lh, lc, lane, C, S, iG1, iG2);
             wave_sum_rows<NTC>(C, s_stage[wave], lane);
 #pragma unroll
             for (int k = 0; k < R; ++k) {
