@@ -787,6 +787,70 @@ int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* a
                                 lbl_buffer* workspace, lbl_buffer* level_flux, lbl_buffer* up_top,
                                 lbl_buffer* down_surface, lbl_buffer* up_surface /* may be NULL */);
 
+/* ---- radiances through scattering layers (beyond the reference; ABI 5, backward compatible) -------------------------------
+ * pyrad_amd.model.Atmosphere.radianceTwoStream: what an instrument sees of lbl_column_flux_scatter_dev's column, by the
+ * two-stream source function technique (Toon et al. 1989).  Everything about the column is that call's, unchanged: layers,
+ * scatterers and delta scaling, ta, ts, tsg, t, a, b, g1, g2, lam, R, T, Ab, the t == 0 and den == 0 branches, the sources P
+ * and Q, the adding recurrences, the surface and I_top; they define the hemispheric fluxes up_i and dn_i at every level over
+ * the whole grid [0, n) (there are no bands).  Up to lbl_limit("scatter_views") = 16 views: view v is a cosine view_mu[v] in
+ * (0, 1] and a direction, view_down[v] 0: the radiance leaving the top of the column upward; 1: the radiance arriving at the
+ * surface downward.
+ * Within layer l let s in [0, t] be the scaled optical depth from the layer's top, w = ts / t, g = tsg / ts (0 when ts == 0),
+ * a = ta / t, D = sqrt(3), Bs(s) = Bt + (Bb - Bt) s / t (Bt, Bb = pi B at the top and bottom edge as in
+ * lbl_column_flux_scatter_dev; equal for planck_linear 0).  F+(s), F-(s) are the two-stream fluxes inside the layer:
+ *   dF+/ds =  g1 F+ - g2 F- - (g1 - g2) Bs(s)        F-(0) = dn_(l+1)
+ *   dF-/ds =  g2 F+ - g1 F- + (g1 - g2) Bs(s)        F+(t) = up_l           (so F+(0) = up_(l+1), F-(t) = dn_l)
+ * The source function in direction +-mu is
+ *   S+-(s, mu) = ( a Bs(s) + (w / 2) [ (1 +- D g mu) F+(s) + (1 -+ D g mu) F-(s) ] ) / pi
+ * and the radiances are
+ *   up view:    Iu_0 = up_0 / pi   (the Lambertian surface: e Es + (1 - e) dn_0 = up_0)
+ *               Iu_(l+1) = Iu_l exp(-t / mu) + integral_0^t S+(s, mu) exp(-s / mu) ds / mu            result Iu_L
+ *   down view:  Id_L = I_top[j] or 0
+ *               Id_l = Id_(l+1) exp(-t / mu) + integral_0^t S-(s, mu) exp(-(t - s) / mu) ds / mu      result Id_0
+ *   t == 0:     the layer changes nothing.
+ * Evaluation (every operation rounded on its own, exp the flux kernels').  With sigma = F+ + F- - 2 Bs, Delta = F+ - F-,
+ * c = (Bb - Bt) / (D (t - tsg)) (0 where ta == 0) and a + w = 1:  pi S+- = Bs + (w / 2) sigma +- (w D g mu / 2) Delta, and
+ * sigma and Delta - 2 c solve y'' = lam^2 y, so each is y(0) r0(s) + y(t) r1(s) with r1 = sinh(lam s) / sinh(lam t),
+ * r0 = sinh(lam (t - s)) / sinh(lam t) and the edge values from up and dn of the two levels: the linear interpolation at
+ * lam == 0 (den == 0 needs no branch), weights in [0, 1] at any thickness.  With u = lam t, tau = t / mu, E = exp(-u),
+ * Tv = exp(-tau), x = (1 - lam mu) tau the integrals of 1, r0 + r1 and r1 against exp(-s / mu) ds / mu are
+ *   W  = -expm1(-tau)
+ *   Wp = (A1 + A2) / (1 + E),  A1 = (x >= 0 ? E : Tv) (-expm1(-|x|)) / |1 - lam mu|  (tau E at x == 0),
+ *                              A2 = -expm1(-(tau + u)) / (1 + lam mu)
+ *   W1 = (m2 (A1 / tau) - Tv) / (1 + lam mu),  m2 = min(2 u, 2000) / -expm1(-2 u)  (1 at u == 0)
+ * and a layer adds, for an up view (a down view: Bt and Bb, and the two edges, exchanged, and the Delta term negated),
+ *   pi J = Bb W + g(tau) (Bt - Bb) + (w / 2) (sigma(0) Wp + (sigma(t) - sigma(0)) W1)
+ *          + (w D g mu / 2) (2 c (W - Wp) + Delta(0) Wp + (Delta(t) - Delta(0)) W1)
+ * with g of lbl_ray_radiance_linear_dev.  A1 is smooth through lam mu == 1 - no point is left out and no mu is moved - and
+ * no exponential has a positive argument; a thin layer adds (t / mu) S.
+ * Identities.  At mu = 1 / sqrt(3), I = F+- / pi satisfies the transfer equation, so pi Iu_L == up_L and pi Id_0 == dn_0 to
+ * rounding.  Without scatterers S = B and the result is lbl_ray_radiance_surface_dev's (_linear_dev's) for the same cosine
+ * to rounding.  With one temperature everywhere, the sky included, I = B(T0) for every view.
+ * Known limit of the two-term phase function: 1 - D g mu is negative for g mu > 1 / sqrt(3), which delta scaling
+ * (g -> g / (1 + g)) avoids; nothing is clamped.
+ * radiance is n_views x n.  up_top and down_surface (may be NULL; n points each) receive lbl_column_flux_scatter_dev's
+ * spectra bit for bit.  A point where some layer's t is not finite is NaN in every output; every other point keeps its bits.
+ * The workspace is lbl_column_flux_scatter_dev's (4 numbers per level and point; the second kernel recomputes the layer
+ * from the coefficients); the grid runs in passes of whole 256-point tiles and the bits do not depend on the workspace's
+ * size, nor a view's on the other views of the call.  No atomics.
+ * LBL_ERR_BAD_ARG, all before anything is enqueued: what lbl_column_flux_scatter_dev refuses of the shared arguments (n == 0
+ * among them); n_views outside 1 .. lbl_limit("scatter_views"); NULL view_mu or view_down; a mu outside (0, 1] or NaN; a
+ * view_down not 0 or 1; a radiance buffer shorter than n_views * n; a short workspace; "sweep_ieee_divisions" 1.
+ * Stream-ordered; nothing is synchronised. */
+int lbl_column_radiance_scatter_workspace(int n_layers, int64_t points, int64_t* doubles);
+int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
+                                    const double* T /* n_layers, or 2 n_layers: bottom, top of layer l */, int planck_linear,
+                                    const double* depth, double range_min, double range_max, int64_t n,
+                                    lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                                    int n_scat, const double* scat_amount /* n_scat x n_layers */,
+                                    lbl_buffer* const* scat_ext /* may be NULL, and every entry */, const double* scat_ext_all,
+                                    lbl_buffer* const* scat_ssa, const double* scat_ssa_all,
+                                    lbl_buffer* const* scat_asym, const double* scat_asym_all, int delta_scaling,
+                                    lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                    int n_views, const double* view_mu, const int32_t* view_down /* 0 up at the top, 1 down at the surface */,
+                                    lbl_buffer* workspace, lbl_buffer* radiance /* n_views x n */,
+                                    lbl_buffer* up_top, lbl_buffer* down_surface /* may be NULL */);
+
 /* ---- ray-path Jacobians (beyond the reference; ABI 5, backward compatible) --------------------------------------------
  * pyrad_amd.model.Atmosphere.pathJacobians: the weighting functions of the radiance lbl_ray_radiance_dev computes - its
  * analytic derivatives to every crossed layer's optical depth and (Planck) temperature, to the source temperature and to any

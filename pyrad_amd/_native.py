@@ -137,6 +137,11 @@ SIGNATURES = {
                                               C.c_double, _P, C.c_int, _D, C.POINTER(_P), _D, C.POINTER(_P), _D, C.POINTER(_P),
                                               _D, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, C.c_double,
                                               _P, _P, _P, _P, _P]),
+    "lbl_column_radiance_scatter_workspace": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int64)]),
+    "lbl_column_radiance_scatter_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_int, _D, C.c_double, C.c_double,
+                                                  C.c_int64, _P, C.c_double, _P, C.c_int, _D, C.POINTER(_P), _D,
+                                                  C.POINTER(_P), _D, C.POINTER(_P), _D, C.c_int, _P, C.c_double, C.c_int, _D,
+                                                  C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "lbl_ray_jacobian_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lbl_ray_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
@@ -807,6 +812,41 @@ class Context:
             _arr(C.c_int64, [int(f) for f in band_first]), _arr(C.c_int64, [int(c) for c in band_count]),
             *self._emissivity_args(emissivity), _hb(workspace), _hb(level_flux), _hb(up_top), _hb(down_surface),
             _hb(up_surface)))
+
+    def column_radiance_scatter_workspace(self, n_layers, points):
+        """The doubles of a workspace with which column_radiance_scatter_dev does ``points`` points in one pass
+        (lbl_column_radiance_scatter_workspace: column_flux_scatter_workspace's)."""
+        out = C.c_int64()
+        self.check(self.lib.lbl_column_radiance_scatter_workspace(int(n_layers), int(points), C.byref(out)))
+        return out.value
+
+    def column_radiance_scatter_dev(self, abs_coef, T, planck_linear, depth, range_min, range_max, n, scat_amount, scat_ext,
+                                    scat_ssa, scat_asym, delta_scaling, view_mu, view_down, workspace, radiance,
+                                    emissivity=1.0, I_surface=None, surface_T=0.0, I_top=None, up_top=None, down_surface=None):
+        """Radiances through scattering layers (lbl_column_radiance_scatter_dev): the column, the scatterers, the surface,
+        ``I_top`` and ``workspace`` as column_flux_scatter_dev takes them, over the whole grid; ``view_mu`` the viewing
+        cosines and ``view_down`` per view 0 (upward at the top) or 1 (downward at the surface).  ``radiance`` receives
+        len(view_mu) x n values; ``up_top`` / ``down_surface`` (optional, n points) column_flux_scatter_dev's spectra."""
+        nl, nc = len(abs_coef), len(scat_ext)
+        T = _as_f64(T).reshape(-1)
+        if len(T) != (2 if planck_linear else 1) * nl:
+            raise ValueError("column_radiance_scatter_dev: one temperature per layer, or two with planck_linear")
+        amount = _as_f64(scat_amount).reshape(-1)
+        if len(amount) != nc * nl or len(scat_ssa) != nc or len(scat_asym) != nc:
+            raise ValueError("column_radiance_scatter_dev: one amount per scatterer and layer, one of each number per scatterer")
+        if len(view_down) != len(view_mu):
+            raise ValueError("column_radiance_scatter_dev: one direction per view")
+
+        def numbers(vals):
+            return (_arr(_P, [v.h if isinstance(v, Buffer) else None for v in vals]),
+                    _arr(C.c_double, [0.0 if isinstance(v, Buffer) else float(v) for v in vals]))
+        self.check(self.lib.lbl_column_radiance_scatter_dev(
+            self.h, nl, _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in T]), int(planck_linear),
+            _arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), _hb(I_surface),
+            float(surface_T), _hb(I_top), nc, _arr(C.c_double, [float(v) for v in amount]), *numbers(scat_ext),
+            *numbers(scat_ssa), *numbers(scat_asym), int(delta_scaling), *self._emissivity_args(emissivity),
+            len(view_mu), _arr(C.c_double, [float(m) for m in view_mu]), _arr(C.c_int32, [int(d) for d in view_down]),
+            _hb(workspace), _hb(radiance), _hb(up_top), _hb(down_surface)))
 
     def column_jacobian_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                             jac, I_surface=None, surface_T=0.0, term_abs_coef=(), term_layer=(), ln_tau_spectra=None,

@@ -3,9 +3,9 @@
 // variants over a reflecting surface, lbl_column_flux_surface_dev, lbl_ray_radiance_surface_dev, lbl_column_jacobian_surface_dev
 // and lbl_ray_jacobian_surface_dev, of the linear-source variants lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev, and
 // of their Jacobians lbl_column_jacobian_linear_dev and lbl_ray_jacobian_linear_dev, of the direct solar beam,
-// lbl_column_solar_dev, of its two-stream multiple scattering, lbl_column_twostream_dev, and of the thermal fluxes through
-// scattering layers, lbl_column_flux_scatter_dev.
-// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j, K5k, K5l and K5m of lbl_kernels.hip; the context's internals
+// lbl_column_solar_dev, of its two-stream multiple scattering, lbl_column_twostream_dev, of the thermal fluxes through
+// scattering layers, lbl_column_flux_scatter_dev, and of the radiances through them, lbl_column_radiance_scatter_dev.
+// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j, K5k, K5l, K5m and K5n of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -579,6 +579,83 @@ extern "C" int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffe
                                      std::min<int64_t>(ws_points, band_count[b] - done), slots, (double*)partial, s);
         launch_scatter_flux_final(n_layers, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
     }
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+} LBL_GUARD_END(ctx)
+
+// K5n: the doubles of a workspace that holds `points` points in one pass: K5m's (the layer quantities are recomputed)
+extern "C" int lbl_column_radiance_scatter_workspace(int n_layers, int64_t points, int64_t* doubles) {
+    return lbl_column_flux_scatter_workspace(n_layers, points, doubles);
+}
+
+// K5n: lbl_column_flux_scatter_dev's checks in its order over one band, the whole grid, then the views and the radiance
+// buffer; the passes are K5m's, without partial sums.
+extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                               int planck_linear, const double* depth, double range_min, double range_max,
+                                               int64_t n, lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                                               int n_scat, const double* scat_amount, lbl_buffer* const* scat_ext,
+                                               const double* scat_ext_all, lbl_buffer* const* scat_ssa,
+                                               const double* scat_ssa_all, lbl_buffer* const* scat_asym,
+                                               const double* scat_asym_all, int delta_scaling, lbl_buffer* emissivity,
+                                               double emissivity_all, int n_views, const double* view_mu,
+                                               const int32_t* view_down, lbl_buffer* workspace, lbl_buffer* radiance,
+                                               lbl_buffer* up_top, lbl_buffer* down_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(ScatterRadianceArgs), 0);
+    ScatterRadianceArgs* a = (ScatterRadianceArgs*)blk.data();
+    if (planck_linear != 0 && planck_linear != 1)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "planck_linear must be 0 (layer temperatures) or 1 (edge temperatures)");
+    const double mu = 0.5773502691896258, weight = kPi;      // (K5m's angle set: not used by the kernels)
+    const int64_t band_first = 0, band_count = n;
+    int rc;
+    if ((rc = check_column(ctx, "scattering radiances", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
+                           surface_T, 1, &mu, &weight, 1, &band_first, &band_count, planck_linear ? a->pbkT_top : nullptr)))
+        return rc;
+    for (int l = 0; l < n_layers && !planck_linear; ++l)
+        if (!std::isfinite(T[l])) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be finite and > 0", l);
+    if (n_scat < 0 || n_scat > kMaxScatterers) return column_fail(ctx, LBL_ERR_BAD_ARG, "0..%d scatterers", kMaxScatterers);
+    if (n_scat > 0 && n_layers > 0 && !scat_amount) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL scatterer amounts");
+    if (delta_scaling != 0 && delta_scaling != 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "delta_scaling must be 0 or 1");
+    if (n_views < 1 || n_views > kMaxScatterViews) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d views", kMaxScatterViews);
+    if (!view_mu || !view_down) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL view list");
+    for (int v = 0; v < kMaxScatterViews; ++v) {
+        if (v < n_views && !(view_mu[v] > 0 && view_mu[v] <= 1))
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "view %d: mu must lie in (0, 1]", v);
+        if (v < n_views && view_down[v] != 0 && view_down[v] != 1)
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "view %d: the direction must be 0 (up) or 1 (down)", v);
+        a->view_mu[v] = v < n_views ? view_mu[v] : 1.0;
+        a->view_rmu[v] = 1.0 / a->view_mu[v];
+        a->view_down[v] = v < n_views ? view_down[v] : 0;
+    }
+    if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_views * n, "radiance", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    if ((rc = check_scatterers(ctx, a, n_layers, n, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa, scat_ssa_all,
+                               scat_asym, scat_asym_all)))
+        return rc;
+    int64_t ws_points = 0;
+    if ((rc = check_workspace(ctx, workspace, kScatterFluxQuantities, n_layers, &ws_points))) return rc;
+    a->I_top = I_top ? buffer_data(I_top) : nullptr;
+    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a->emissivity_all = emissivity_all;
+    a->workspace = buffer_data(workspace);
+    a->ws_points = ws_points;
+    a->up_top = up_top ? buffer_data(up_top) : nullptr;
+    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
+    a->up_surface = nullptr;
+    a->delta_scaling = delta_scaling;
+    a->radiance = buffer_data(radiance);
+    a->n_views = n_views;
+
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, a, sizeof(ScatterRadianceArgs), &d_args))) return rc;
+    const hipStream_t s = ctx_stream(ctx);
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    for (int64_t done = 0; done < n; done += ws_points)
+        launch_scatter_radiance_pass((const ScatterRadianceArgs*)d_args, planck_linear != 0, n_views, done,
+                                     std::min<int64_t>(ws_points, n - done), s);
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
 } LBL_GUARD_END(ctx)

@@ -434,6 +434,22 @@ void launch_scatter_flux_pass(const ScatterFluxArgs* d_args, bool linear, long l
                               int slots, double* partial, hipStream_t s);
 void launch_scatter_flux_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s);
 
+// Radiances through scattering layers (K5n, lbl_column_transport.hip: lbl_column_radiance_scatter_dev): K5m's column, whose
+// first kernel runs as it stands on the ScatterFluxArgs part of this block (the workspace is K5m's, four numbers per level),
+// then one upward walk that integrates the two-stream source function along every view.  No band sums: up_surface stays
+// nullptr, and the band fields of ColumnRT are not used.
+constexpr int kMaxScatterViews = 16;
+struct ScatterRadianceArgs : ScatterFluxArgs {
+    double view_mu[kMaxScatterViews];   // the viewing cosines, in (0, 1]; 1 beyond n_views
+    double view_rmu[kMaxScatterViews];  // 1 / mu_v, from the host
+    int32_t view_down[kMaxScatterViews];        // 0: upward at the top of the column; 1: downward at the surface
+    double* radiance;                   // n_views x n
+    int32_t n_views, pad_views;
+};
+// one pass over the points [first, first + count): first is a multiple of the tile and count <= ws_points
+void launch_scatter_radiance_pass(const ScatterRadianceArgs* d_args, bool linear, int n_views, long long first, long long count,
+                                  hipStream_t s);
+
 // Ray-path Jacobians (K5f, lbl_column_transport.hip: lbl_ray_jacobian_dev): K5e's walk, then the segments last to first
 // with K5d's transmittance-and-emission recurrence, one output row per ray, kind and crossed layer.  RayArgs' block with
 // more tables behind it; `radiance` may be nullptr here and `transmittance` is not used.  A ray's rows start at row_first[r]:

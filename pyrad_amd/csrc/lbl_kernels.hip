@@ -35,6 +35,8 @@
 //                              layer, joined by adding through a workspace (Atmosphere.solarFluxesTwoStream; beyond the reference)
 //   K5m scatter_flux_down_kernel, scatter_flux_up_kernel   K5l with the layers' thermal emission as the source and an emitting
 //                              surface (Atmosphere.fluxesTwoStream; beyond the reference)
+//   K5n scatter_radiance_up_kernel   K5m's column seen along up to 16 views: the two-stream source function integrated in
+//                              closed form per layer and view (Atmosphere.radianceTwoStream; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -4743,6 +4745,140 @@ __global__ __launch_bounds__(256) void scatter_flux_up_kernel(const ScatterFluxA
 }
 
 // ----------------------------------------------------------------------------------------
+// K5n: radiances through scattering layers (lbl_column_radiance_scatter_dev; the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// The two-stream source function technique on K5m's column.  The first pass is scatter_flux_down_kernel<LINEAR> as it
+// stands (ScatterRadianceArgs begins with ScatterFluxArgs); scatter_radiance_up_kernel<LINEAR, NV> is K5m's upward walk
+// without the sums, and per layer and view one closed-form integral of the source function
+//     pi S+-(s) = Bs(s) + (w / 2) sigma(s) +- kap Delta(s),   sigma = F+ + F- - 2 Bs,  Delta = F+ - F-,  kap = w D g mu / 2
+// (a + w = 1).  sigma and Delta - 2 c, c = d / (D (t - tsg)), solve y'' = lam^2 y, so each is fixed by its values at the two
+// edges of the layer, which the walk has at hand (up and dn at the level below and above):
+//     y(s) = y(0) sinh(lam (t - s)) / sinh(lam t) + y(t) sinh(lam s) / sinh(lam t).
+// This basis is the linear interpolation at lam = 0 (K5m's den == 0 branch: no switch-over here) and has weights in [0, 1]
+// however thick the layer: nothing grows, and no edge value is extrapolated from the other edge.  With u = lam t,
+// tau = t / mu, E = exp(-u), Tv = exp(-tau), x = (1 - lam mu) tau the weights against exp(-s / mu) ds / mu are
+//     W  = -expm1(-tau)                                                        of 1
+//     Wp = (A1 + A2) / (1 + E)                                                 of both sinh ratios together
+//          A1 = tau (E - Tv) / x = (x >= 0 ? E : Tv) (-expm1(-|x|)) / |1 - lam mu|   (tau E at x == 0)
+//          A2 = -expm1(-(tau + u)) / (1 + lam mu)
+//     W1 = ((2 u / -expm1(-2 u)) (A1 / tau) - Tv) / (1 + lam mu)                of sinh(lam s) / sinh(lam t)
+// Wp is a sum of positive terms (relative accuracy, also of a thin layer); A1 is smooth through lam mu = 1, no argument of an
+// exponential is positive, and W1 - the second divided difference of exp over the nodes 0, -(tau - u), -(tau + u), divided by
+// the largest node distance - is good to an absolute rounding error everywhere: it multiplies the difference of the edge
+// values, so y(0) Wp + (y(t) - y(0)) W1 tends to (t / mu) y for a thin layer.  The Planck part is the ray kernels'
+// (1 - Tv) B_in + g(tau) (B_out - B_in) (linear_source_g), so a column without scatterers (w = 0) gives their expression.
+// Both directions run in the one walk: an up view carries I <- Tv I + J, a down view I <- I + C J, C <- Tv C from the surface.
+// The layer quantities are recomputed (twostream_layer: the coefficient and the scatterers' numbers read again, 8 bytes and
+// about 80 fp64 operations, one sqrt, one exp and two expm1 per point and layer) and not stored: t, lam, w, g, tsg and the two
+// Planck values would add 7 numbers per level, 56 bytes written and 56 read per point and layer, about 14 ps of HBM time at
+// 8 TB/s against 2 ps of fp64 at the vector rate - and a workspace 2.75 times K5m's.  So the workspace is K5m's.
+// One point per thread as K5l/K5m; NV in {1, 2, 4, 8, 16} is the view count rounded up (the views beyond n_views are
+// computed with mu = 1 and not stored), so a view's arithmetic does not depend on its neighbours.
+template <bool LINEAR, int NV>
+__global__ __launch_bounds__(256) void scatter_radiance_up_kernel(const ScatterRadianceArgs* __restrict__ Ap, long long first,
+                                                                  long long count) {
+#pragma clang fp contract(off)
+    const ScatterRadianceArgs& A = *Ap;
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= count) return;
+    const long long j = first + q;
+    const int L = A.n_layers;
+    const int levels = L + 1;
+    const long long row = A.ws_points;
+    const double* const W = A.workspace + q;
+    auto ws = [&](int v, int i) { return W[((long long)v * levels + i) * row]; };
+    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+    double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
+    scatterer_numbers(A, j, al, si, et);
+    const double nu = linspace_at(j, A.n, A.start, A.stop, A.step);
+    double Rs = ws(0, 0), Ds = ws(1, 0);
+    const bool bad = isnan(Rs) || isnan(Ds);
+    const double nan = __builtin_nan("");
+    const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
+    const double Is = A.I_surface ? A.I_surface[j] : planck_budget(nu, A.pa, A.pbk_surface);
+    const double albedo = 1.0 - e;
+    double up = (e * (kPi * Is) + albedo * Ds) / (1.0 - albedo * Rs);
+    double dn = Rs * up + Ds;
+    if (A.down_surface) A.down_surface[j] = bad ? nan : dn;
+    double I[NV], C[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        I[v] = A.view_down[v] ? 0.0 : up / kPi;
+        C[v] = 1.0;
+    }
+    double k = L > 0 ? load_global_f64(A.abs_coef[0], j) : 0.0;
+    double B_below = 0.0;                           // LINEAR: pi B at the top edge of the layer below
+    for (int l = 0; l < L; ++l) {
+        const double k_next = l + 1 < L ? load_global_f64(A.abs_coef[l + 1], j) : k;
+        const TwoStreamLayer lay = twostream_layer(A, l, k, al, si, et);
+        const double upB = up, dnB = dn;
+        up = ws(2, l + 1) * up + ws(3, l + 1);
+        Rs = ws(0, l + 1); Ds = ws(1, l + 1);
+        dn = Rs * up + Ds;
+        double Bb, Bt;
+        if (LINEAR) {
+            const bool shared_edge = l > 0 && A.pbkT[l] == A.pbkT_top[l - 1];
+            Bb = shared_edge ? B_below : kPi * planck_budget(nu, A.pa, A.pbkT[l]);
+            Bt = kPi * planck_budget(nu, A.pa, A.pbkT_top[l]);
+            B_below = Bt;
+        } else {
+            Bb = Bt = kPi * planck_budget(nu, A.pa, A.pbkT[l]);
+        }
+        if (!lay.empty) {
+            const double t = lay.t, lam = lay.lam;
+            const double u = lam * t;
+            const double E = exp_neg_budget(u);
+            const double m2 = u == 0.0 ? 1.0 : fmin(2.0 * u, 2000.0) / -expm1(-2.0 * u);     // (E == 0 beyond 800)
+            const double c2 = LINEAR && lay.ta != 0.0 ? (2.0 * (Bb - Bt)) / (D * (t - lay.tsg)) : 0.0;
+            const double sig0 = (up + dn) - 2.0 * Bt, sigt = (upB + dnB) - 2.0 * Bb;      // top edge, bottom edge
+            const double del0 = up - dn, delt = upB - dnB;
+            const double hw = 0.5 * lay.w;
+            const double Dg = D * lay.g;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const double mu = A.view_mu[v];
+                const double tau = t * A.view_rmu[v];
+                const double Tv = exp_neg_budget(tau);
+                const double Wt = -expm1(-tau);
+                const double lm = lam * mu;
+                const double q1 = 1.0 - lm, p1 = 1.0 + lm;
+                const double x = q1 * tau, ax = fabs(x);
+                const double sel = x >= 0.0 ? E : Tv;
+                const double em = -expm1(-ax);
+                const double A1 = sel * (ax == 0.0 ? tau : em / fabs(q1));
+                const double A1t = sel * (ax == 0.0 ? 1.0 : em / ax);
+                const double A2 = -expm1(-(tau + u)) / p1;
+                const double Wp = (A1 + A2) / (1.0 + E);
+                const double W1 = (m2 * A1t - Tv) / p1;
+                const double gl = lbl::linear_source_g(tau, Tv);
+                const double kap = hw * (Dg * mu);
+                const double part = c2 * (Wt - Wp);
+                if (A.view_down[v]) {
+                    const double J = (Bt * Wt + gl * (Bb - Bt)) + hw * (sigt * Wp + (sig0 - sigt) * W1)
+                                     - kap * (part + (delt * Wp + (del0 - delt) * W1));
+                    I[v] = I[v] + C[v] * (J / kPi);
+                    C[v] = C[v] * Tv;
+                } else {
+                    const double J = (Bb * Wt + gl * (Bt - Bb)) + hw * (sig0 * Wp + (sigt - sig0) * W1)
+                                     + kap * (part + (del0 * Wp + (delt - del0) * W1));
+                    I[v] = I[v] * Tv + J / kPi;
+                }
+            }
+        }
+        k = k_next;
+    }
+    if (A.up_top) A.up_top[j] = bad ? nan : up;
+    const double Itop = A.I_top ? load_global_f64(A.I_top, j) : 0.0;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        if (v < A.n_views) {
+            const double r = A.view_down[v] ? I[v] + C[v] * Itop : I[v];
+            A.radiance[(long long)v * A.n + j] = bad ? nan : r;
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------------
 // K5i: linear-in-optical-depth Planck source (lbl_column_flux_linear_dev, lbl_ray_radiance_linear_dev; the semantics are in
 // include/pyrad_hip.h)
 // ----------------------------------------------------------------------------------------
@@ -6331,6 +6467,32 @@ void launch_scatter_flux_pass(const ScatterFluxArgs* d_args, bool linear, long l
 void launch_scatter_flux_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s) {
     const int nv = 2 * (n_layers + 1);
     hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, slots, nv, level_flux);
+}
+
+template <bool LINEAR, int NV>
+static void launch_scatter_radiance_up(const ScatterRadianceArgs* d_args, unsigned tiles, long long first, long long count,
+                                       hipStream_t s) {
+    hipLaunchKernelGGL((scatter_radiance_up_kernel<LINEAR, NV>), dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+}
+
+void launch_scatter_radiance_pass(const ScatterRadianceArgs* d_args, bool linear, int n_views, long long first, long long count,
+                                  hipStream_t s) {
+    if (count <= 0) return;
+    const unsigned tiles = (unsigned)((count + kTwoStreamTile - 1) / kTwoStreamTile);
+    const ScatterFluxArgs* const flux_args = d_args;      // (the block begins with K5m's)
+    if (linear)
+        hipLaunchKernelGGL(scatter_flux_down_kernel<true>, dim3(tiles), dim3(kTwoStreamTile), 0, s, flux_args, first, count);
+    else
+        hipLaunchKernelGGL(scatter_flux_down_kernel<false>, dim3(tiles), dim3(kTwoStreamTile), 0, s, flux_args, first, count);
+#define LBL_RADIANCE_UP(NV)                                                                          \
+    (linear ? launch_scatter_radiance_up<true, NV>(d_args, tiles, first, count, s)                   \
+            : launch_scatter_radiance_up<false, NV>(d_args, tiles, first, count, s))
+    if (n_views <= 1) LBL_RADIANCE_UP(1);
+    else if (n_views <= 2) LBL_RADIANCE_UP(2);
+    else if (n_views <= 4) LBL_RADIANCE_UP(4);
+    else if (n_views <= 8) LBL_RADIANCE_UP(8);
+    else LBL_RADIANCE_UP(16);
+#undef LBL_RADIANCE_UP
 }
 
 // K5d's points per thread, chosen per angle count so that no instantiation spills (DESIGN.md "K5d")

@@ -2299,6 +2299,46 @@ class PathRadiance:
             len(self.paths), self.wavenumber.size, self.transmittance is not None)
 
 
+class ScatterRadiance:
+    """What Atmosphere.radianceTwoStream returns, for V views.  Without an instrument ``wavenumber`` is the grid (n,) and
+    ``radiance`` (V, n) the spectrum along every view, in the units of transmission(); with one they are the channel centres
+    (C,) and the channel radiances (V, C).  ``mu``: (V,) the viewing cosines; ``direction``: V times "up" (leaving the top of
+    the column) or "down" (arriving at the surface).  brightnessTemperature(wavenumber, radiance) applies."""
+
+    def __init__(self, wavenumber, radiance, mu, direction):
+        self.wavenumber = wavenumber
+        self.radiance = radiance
+        self.mu = mu
+        self.direction = direction
+
+    def __repr__(self):
+        return "ScatterRadiance(views=%d, points=%d)" % (len(self.mu), self.wavenumber.size)
+
+
+def _scatter_views(views):
+    """``views`` of radianceTwoStream as (mu (V,), down (V,) of 0 / 1, the directions' names)"""
+    if isinstance(views, (str, bytes)) or not hasattr(views, "__len__") or len(views) == 0:
+        raise ValueError("views: a sequence of mu or (mu, \"up\" | \"down\"), at least one, not %r" % (views,))
+    mu, down = [], []
+    for v in views:
+        direction = "up"
+        if isinstance(v, (tuple, list)):
+            if len(v) != 2:
+                raise ValueError("views: (mu, \"up\" | \"down\"), not %r" % (v,))
+            v, direction = v
+        if direction not in ("up", "down"):
+            raise ValueError("views: the direction is \"up\" or \"down\", not %r" % (direction,))
+        try:
+            m = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("views: mu must be a number in (0, 1], not %r" % (v,))
+        if not (m > 0 and m <= 1):
+            raise ValueError("views: mu must lie in (0, 1], not %r" % (v,))
+        mu.append(m)
+        down.append(1 if direction == "down" else 0)
+    return np.array(mu), down, ["down" if d else "up" for d in down]
+
+
 class PathJacobians:
     """What Atmosphere.pathJacobians returns, for R paths through L layers.  X is the grid (n points) or, with an instrument,
     its channels (C).  ``wavenumber``: (X,) the grid or the channel centres; ``radiance``: (R, X), Atmosphere.radiance's;
@@ -2894,6 +2934,91 @@ class Atmosphere(list):
                       upSpectrum=spec["up_top"].download(n) if spectra else None,
                       downSpectrum=spec["down_surface"].download(n) if spectra else None,
                       upSurfaceSpectrum=spec["up_surface"].download(n) if spectra else None)
+
+    def radianceTwoStream(self, views, scatterers=(), deltaScaling=True, surfaceTemperature=None, surfaceSpectrum=None,
+                          topSpectrum=None, emissivity=1.0, planck="layer", levelTemperatures=None, instrument=None):
+        """What an instrument sees of fluxesTwoStream()'s column: the spectrum leaving the top of a cloudy column, or
+        arriving under it at the surface, at any viewing cosine (beyond the reference).  The two-stream source function
+        technique (Toon et al. 1989): fluxesTwoStream()'s solution gives the hemispheric fluxes F+ and F- inside every
+        layer, they give the source function in the viewing direction
+            S+-(s, mu) = (a B(s) + (w / 2) [(1 +- sqrt(3) g mu) F+(s) + (1 -+ sqrt(3) g mu) F-(s)]) / pi
+        (w the layer's scaled single-scattering albedo, g its asymmetry, a = 1 - w), and the radiance is the formal
+        solution along the view - in closed form per layer, smooth through lam mu = 1 (lbl_column_radiance_scatter_dev,
+        include/pyrad_hip.h).
+
+        ``views``: a sequence of mu (upward at the top) or (mu, "up" | "down"), mu in (0, 1]: "up" is the radiance leaving
+        the top of the column, from the Lambertian surface's up_0 / pi; "down" the radiance arriving at the surface, from
+        ``topSpectrum`` (or 0).  More than 16 views run in chunks of 16; a view's values do not depend on the others.
+        Every other argument as fluxesTwoStream() takes it.  ``instrument``: an Instrument - the rows are convolved onto
+        its channels on the device, as radiance() does.
+        At mu = 1 / sqrt(3) pi times the radiance is fluxesTwoStream()'s flux, without scatterers the result is
+        radiance()'s along the same slant to rounding, and a column at one temperature under a sky of the same shows
+        B(T) in every view.  The two-term phase function's 1 - sqrt(3) g mu is negative for g mu > 1 / sqrt(3), which
+        ``deltaScaling`` (g -> g / (1 + g)) avoids; nothing is clamped.
+        Returns a ScatterRadiance.  The absorption coefficients are the resident ones; the workspace (four numbers per
+        level and point) stays with the atmosphere, at most 256 MiB - a longer grid is done in several passes, with the same
+        bits.  Everything is validated (ValueError) before the device is touched."""
+        layers, n, _, _, _, _, surfaceSpectrum = self._column_checks(
+            surfaceSpectrum, surfaceTemperature, [(1.0 / math.sqrt(3.0), pi)], None)
+        view_mu, view_down, direction = _scatter_views(views)
+        topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
+        first = layers[0]
+        nl = len(layers)
+        scat = _scatterers(scatterers, nl)
+        numbers = [sc._on_grid(first.xAxis) for sc in scat]
+        if not isinstance(deltaScaling, (bool, np.bool_)):
+            raise ValueError("deltaScaling: True or False, not %r" % (deltaScaling,))
+        linear = _planck_source(planck, levelTemperatures)
+        if linear:
+            lev = self._level_temperatures(levelTemperatures)
+            T = np.column_stack([lev[:-1], lev[1:]])
+        else:
+            T = [L.T for L in layers]
+        emissivity = _surface_emissivity(emissivity, first.xAxis)
+        depth = [L.depth for L in layers]
+        support = None
+        if instrument is not None:
+            if not isinstance(instrument, Instrument):
+                raise ValueError("instrument: an Instrument, not %r" % (instrument,))
+            support = instrument.support(first.rangeMin, first.rangeMax, n)
+        chunk = nat.limit("scatter_views")
+        V = len(view_mu)
+        ctx = _ctx()
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        st = _kept_state(self, "_scatter_radiance_state")
+        st.reserve(ctx, n)
+        I_surface = st.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
+        I_top = st.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
+        emissivity = self._device_emissivity(ctx, st, emissivity)
+        columns = []
+        for c, triple in enumerate(numbers):
+            columns.append([v if isinstance(v, float) else st.buf(ctx, "scat%d_%d" % (c, q)).upload(v)
+                            for q, v in enumerate(triple)])
+        # the workspace: the grid in one pass where 256 MiB hold it, else as many whole tiles as they hold
+        tile = ctx.column_radiance_scatter_workspace(nl, 1)
+        want = ctx.column_radiance_scatter_workspace(nl, n)
+        wst = _kept_state(self, "_scatter_radiance_workspace")
+        wst.reserve(ctx, min(want, max(TWOSTREAM_WORKSPACE_BYTES // 8 // tile, 1) * tile))
+        rad = _kept_state(self, "_scatter_radiance_rows").reserve(ctx, min(V, chunk) * n).buf(ctx, "radiance")
+        X = n if instrument is None else len(instrument)
+        out = None
+        if instrument is not None:
+            out = _kept_state(self, "_scatter_radiance_out").reserve(ctx, min(V, chunk) * X).buf(ctx, "out")
+        values = np.empty((V, X))
+        for lo in range(0, V, chunk):
+            hi = min(lo + chunk, V)
+            ctx.column_radiance_scatter_dev(kbufs, T, int(linear), depth, first.rangeMin, first.rangeMax, n,
+                                            [sc.amounts for sc in scat], [t[0] for t in columns], [t[1] for t in columns],
+                                            [t[2] for t in columns], int(bool(deltaScaling)), view_mu[lo:hi],
+                                            view_down[lo:hi], wst.buf(ctx, "workspace"), rad, emissivity=emissivity,
+                                            I_surface=I_surface, surface_T=float(surfaceTemperature or 0.0), I_top=I_top)
+            if instrument is None:
+                values[lo:hi] = rad.download((hi - lo) * n).reshape(hi - lo, n)
+            else:
+                _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, [(rad, r * n) for r in range(hi - lo)],
+                              out)
+                values[lo:hi] = out.download((hi - lo) * X).reshape(hi - lo, X)
+        return ScatterRadiance(first.xAxis if instrument is None else instrument.centres.copy(), values, view_mu, direction)
 
     def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False,
                   temperature="planck", emissivity=None, reflection="lambertian", topSpectrum=None):
