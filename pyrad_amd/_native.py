@@ -740,12 +740,38 @@ class Context:
             _arr(C.c_int64, [int(c) for c in band_count]), *self._emissivity_args(emissivity), int(reflection),
             _hb(level_flux), _hb(up_top), _hb(down_surface), _hb(up_surface)))
 
+    def _scatter_workspace(self, entry, n_layers, points):
+        """The doubles the lbl_column_*_workspace function ``entry`` gives for ``points`` points in one pass"""
+        out = C.c_int64()
+        self.check(entry(int(n_layers), int(points), C.byref(out)))
+        return out.value
+
+    @staticmethod
+    def _scatter_args(name, abs_coef, scat_amount, scat_ext, scat_ssa, scat_asym):
+        """The scatterer arguments of the two-stream entry points, from n_scat to scat_asym_all, behind the length check
+        of the wrapper ``name``: each number a Buffer of n points or a number"""
+        nl, nc = len(abs_coef), len(scat_ext)
+        amount = _as_f64(scat_amount).reshape(-1)
+        if len(amount) != nc * nl or len(scat_ssa) != nc or len(scat_asym) != nc:
+            raise ValueError("%s: one amount per scatterer and layer, one of each number per scatterer" % name)
+
+        def numbers(vals):
+            return (_arr(_P, [v.h if isinstance(v, Buffer) else None for v in vals]),
+                    _arr(C.c_double, [0.0 if isinstance(v, Buffer) else float(v) for v in vals]))
+        return (nc, _arr(C.c_double, [float(v) for v in amount]), *numbers(scat_ext), *numbers(scat_ssa), *numbers(scat_asym))
+
+    @staticmethod
+    def _scatter_T(name, T, planck_linear, abs_coef):
+        """``T`` of the column_*_scatter_dev wrapper ``name`` as L numbers, or 2 L with ``planck_linear``"""
+        T = _as_f64(T).reshape(-1)
+        if len(T) != (2 if planck_linear else 1) * len(abs_coef):
+            raise ValueError("%s: one temperature per layer, or two with planck_linear" % name)
+        return _arr(C.c_double, [float(t) for t in T])
+
     def column_twostream_workspace(self, n_layers, points):
         """The doubles of a workspace with which column_twostream_dev does ``points`` points in one pass
         (lbl_column_twostream_workspace: whole tiles, at least one)."""
-        out = C.c_int64()
-        self.check(self.lib.lbl_column_twostream_workspace(int(n_layers), int(points), C.byref(out)))
-        return out.value
+        return self._scatter_workspace(self.lib.lbl_column_twostream_workspace, n_layers, points)
 
     def column_twostream_dev(self, abs_coef, depth, range_min, range_max, n, S0, beam_weight, slant, scat_amount, scat_ext,
                              scat_ssa, scat_asym, delta_scaling, band_first, band_count, workspace, level_flux, emissivity=1.0,
@@ -756,22 +782,15 @@ class Context:
         column_twostream_workspace(layers, 1) doubles.  ``level_flux`` receives len(band_first) x 3 x (layers + 1) band sums
         [band][up, diffuse down, direct][level]; ``up_top`` / ``down_surface`` (diffuse) / ``direct_surface`` / ``up_surface``
         (optional, n points) the spectral fluxes."""
-        nl, ns, nc = len(abs_coef), len(beam_weight), len(scat_ext)
+        nl, ns = len(abs_coef), len(beam_weight)
         slant = _as_f64(slant).reshape(-1)
         if len(slant) != ns * nl:
             raise ValueError("column_twostream_dev: one slant per beam and layer")
-        amount = _as_f64(scat_amount).reshape(-1)
-        if len(amount) != nc * nl or len(scat_ssa) != nc or len(scat_asym) != nc:
-            raise ValueError("column_twostream_dev: one amount per scatterer and layer, one of each number per scatterer")
-
-        def numbers(vals):
-            return (_arr(_P, [v.h if isinstance(v, Buffer) else None for v in vals]),
-                    _arr(C.c_double, [0.0 if isinstance(v, Buffer) else float(v) for v in vals]))
+        scat = self._scatter_args("column_twostream_dev", abs_coef, scat_amount, scat_ext, scat_ssa, scat_asym)
         self.check(self.lib.lbl_column_twostream_dev(
             self.h, nl, _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(d) for d in depth]), float(range_min),
             float(range_max), int(n), _hb(S0), ns, _arr(C.c_double, [float(w) for w in beam_weight]),
-            _arr(C.c_double, [float(v) for v in slant]), nc, _arr(C.c_double, [float(v) for v in amount]),
-            *numbers(scat_ext), *numbers(scat_ssa), *numbers(scat_asym), int(delta_scaling), len(band_first),
+            _arr(C.c_double, [float(v) for v in slant]), *scat, int(delta_scaling), len(band_first),
             _arr(C.c_int64, [int(f) for f in band_first]), _arr(C.c_int64, [int(c) for c in band_count]),
             *self._emissivity_args(emissivity), _hb(workspace), _hb(level_flux), _hb(up_top), _hb(down_surface),
             _hb(direct_surface), _hb(up_surface)))
@@ -779,9 +798,7 @@ class Context:
     def column_flux_scatter_workspace(self, n_layers, points):
         """The doubles of a workspace with which column_flux_scatter_dev does ``points`` points in one pass
         (lbl_column_flux_scatter_workspace: four numbers per level and point, whole tiles, at least one)."""
-        out = C.c_int64()
-        self.check(self.lib.lbl_column_flux_scatter_workspace(int(n_layers), int(points), C.byref(out)))
-        return out.value
+        return self._scatter_workspace(self.lib.lbl_column_flux_scatter_workspace, n_layers, points)
 
     def column_flux_scatter_dev(self, abs_coef, T, planck_linear, depth, range_min, range_max, n, scat_amount, scat_ext,
                                 scat_ssa, scat_asym, delta_scaling, band_first, band_count, workspace, level_flux,
@@ -793,22 +810,12 @@ class Context:
         column_flux_scatter_workspace(layers, 1) doubles) as column_twostream_dev takes them.  ``level_flux`` receives
         len(band_first) x 2 x (layers + 1) band sums [band][up, down][level]; ``up_top`` / ``down_surface`` / ``up_surface``
         (optional, n points) the spectral fluxes."""
-        nl, nc = len(abs_coef), len(scat_ext)
-        T = _as_f64(T).reshape(-1)
-        if len(T) != (2 if planck_linear else 1) * nl:
-            raise ValueError("column_flux_scatter_dev: one temperature per layer, or two with planck_linear")
-        amount = _as_f64(scat_amount).reshape(-1)
-        if len(amount) != nc * nl or len(scat_ssa) != nc or len(scat_asym) != nc:
-            raise ValueError("column_flux_scatter_dev: one amount per scatterer and layer, one of each number per scatterer")
-
-        def numbers(vals):
-            return (_arr(_P, [v.h if isinstance(v, Buffer) else None for v in vals]),
-                    _arr(C.c_double, [0.0 if isinstance(v, Buffer) else float(v) for v in vals]))
+        T = self._scatter_T("column_flux_scatter_dev", T, planck_linear, abs_coef)
+        scat = self._scatter_args("column_flux_scatter_dev", abs_coef, scat_amount, scat_ext, scat_ssa, scat_asym)
         self.check(self.lib.lbl_column_flux_scatter_dev(
-            self.h, nl, _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in T]), int(planck_linear),
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), T, int(planck_linear),
             _arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), _hb(I_surface),
-            float(surface_T), _hb(I_top), nc, _arr(C.c_double, [float(v) for v in amount]), *numbers(scat_ext),
-            *numbers(scat_ssa), *numbers(scat_asym), int(delta_scaling), len(band_first),
+            float(surface_T), _hb(I_top), *scat, int(delta_scaling), len(band_first),
             _arr(C.c_int64, [int(f) for f in band_first]), _arr(C.c_int64, [int(c) for c in band_count]),
             *self._emissivity_args(emissivity), _hb(workspace), _hb(level_flux), _hb(up_top), _hb(down_surface),
             _hb(up_surface)))
@@ -816,9 +823,7 @@ class Context:
     def column_radiance_scatter_workspace(self, n_layers, points):
         """The doubles of a workspace with which column_radiance_scatter_dev does ``points`` points in one pass
         (lbl_column_radiance_scatter_workspace: column_flux_scatter_workspace's)."""
-        out = C.c_int64()
-        self.check(self.lib.lbl_column_radiance_scatter_workspace(int(n_layers), int(points), C.byref(out)))
-        return out.value
+        return self._scatter_workspace(self.lib.lbl_column_radiance_scatter_workspace, n_layers, points)
 
     def column_radiance_scatter_dev(self, abs_coef, T, planck_linear, depth, range_min, range_max, n, scat_amount, scat_ext,
                                     scat_ssa, scat_asym, delta_scaling, view_mu, view_down, workspace, radiance,
@@ -827,24 +832,14 @@ class Context:
         ``I_top`` and ``workspace`` as column_flux_scatter_dev takes them, over the whole grid; ``view_mu`` the viewing
         cosines and ``view_down`` per view 0 (upward at the top) or 1 (downward at the surface).  ``radiance`` receives
         len(view_mu) x n values; ``up_top`` / ``down_surface`` (optional, n points) column_flux_scatter_dev's spectra."""
-        nl, nc = len(abs_coef), len(scat_ext)
-        T = _as_f64(T).reshape(-1)
-        if len(T) != (2 if planck_linear else 1) * nl:
-            raise ValueError("column_radiance_scatter_dev: one temperature per layer, or two with planck_linear")
-        amount = _as_f64(scat_amount).reshape(-1)
-        if len(amount) != nc * nl or len(scat_ssa) != nc or len(scat_asym) != nc:
-            raise ValueError("column_radiance_scatter_dev: one amount per scatterer and layer, one of each number per scatterer")
+        T = self._scatter_T("column_radiance_scatter_dev", T, planck_linear, abs_coef)
+        scat = self._scatter_args("column_radiance_scatter_dev", abs_coef, scat_amount, scat_ext, scat_ssa, scat_asym)
         if len(view_down) != len(view_mu):
             raise ValueError("column_radiance_scatter_dev: one direction per view")
-
-        def numbers(vals):
-            return (_arr(_P, [v.h if isinstance(v, Buffer) else None for v in vals]),
-                    _arr(C.c_double, [0.0 if isinstance(v, Buffer) else float(v) for v in vals]))
         self.check(self.lib.lbl_column_radiance_scatter_dev(
-            self.h, nl, _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(t) for t in T]), int(planck_linear),
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), T, int(planck_linear),
             _arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), _hb(I_surface),
-            float(surface_T), _hb(I_top), nc, _arr(C.c_double, [float(v) for v in amount]), *numbers(scat_ext),
-            *numbers(scat_ssa), *numbers(scat_asym), int(delta_scaling), *self._emissivity_args(emissivity),
+            float(surface_T), _hb(I_top), *scat, int(delta_scaling), *self._emissivity_args(emissivity),
             len(view_mu), _arr(C.c_double, [float(m) for m in view_mu]), _arr(C.c_int32, [int(d) for d in view_down]),
             _hb(workspace), _hb(radiance), _hb(up_top), _hb(down_surface)))
 

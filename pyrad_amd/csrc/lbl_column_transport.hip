@@ -348,12 +348,22 @@ extern "C" int lbl_column_solar_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
     return LBL_OK;
 } LBL_GUARD_END(ctx)
 
-// K5l: the doubles of a workspace that holds `points` points (rounded up to whole tiles, at least one) in one pass
-extern "C" int lbl_column_twostream_workspace(int n_layers, int64_t points, int64_t* doubles) {
+// K5l, K5m, K5n: the doubles of a workspace that holds `points` points (rounded up to whole tiles, at least one) in one
+// pass, `quantities` numbers per level and point; K5n's is K5m's (the layer quantities are recomputed)
+static int scatter_workspace(int quantities, int n_layers, int64_t points, int64_t* doubles) {
     if (!doubles || n_layers < 0 || n_layers > kMaxLayers || points < 0 || points > (int64_t)1 << 40) return LBL_ERR_BAD_ARG;
     const int64_t tiles = std::max<int64_t>((points + kTwoStreamTile - 1) / kTwoStreamTile, 1);
-    *doubles = (int64_t)kTwoStreamQuantities * (n_layers + 1) * tiles * kTwoStreamTile;
+    *doubles = (int64_t)quantities * (n_layers + 1) * tiles * kTwoStreamTile;
     return LBL_OK;
+}
+extern "C" int lbl_column_twostream_workspace(int n_layers, int64_t points, int64_t* doubles) {
+    return scatter_workspace(kTwoStreamQuantities, n_layers, points, doubles);
+}
+extern "C" int lbl_column_flux_scatter_workspace(int n_layers, int64_t points, int64_t* doubles) {
+    return scatter_workspace(kScatterFluxQuantities, n_layers, points, doubles);
+}
+extern "C" int lbl_column_radiance_scatter_workspace(int n_layers, int64_t points, int64_t* doubles) {
+    return scatter_workspace(kScatterFluxQuantities, n_layers, points, doubles);
 }
 
 // one of the three spectral numbers of the scatterers: a buffer of n points per scatterer, or the number beside it within
@@ -374,10 +384,8 @@ static int check_scat_numbers(lbl_ctx* ctx, const char* what, int n_scat, int64_
     return LBL_OK;
 }
 
-// the scatterers of K5l and K5m (n_scat within its limit, scat_amount there): every amount, then the three numbers of each,
-// into the fields both argument blocks name alike
-template <class Args>
-static int check_scatterers(lbl_ctx* ctx, Args* a, int n_layers, int64_t n, int n_scat, const double* scat_amount,
+// the scatterers of K5l, K5m and K5n (n_scat within its limit, scat_amount there): every amount, then the three numbers of each
+static int check_scatterers(lbl_ctx* ctx, ScatterPart* a, int n_layers, int64_t n, int n_scat, const double* scat_amount,
                             lbl_buffer* const* scat_ext, const double* scat_ext_all, lbl_buffer* const* scat_ssa,
                             const double* scat_ssa_all, lbl_buffer* const* scat_asym, const double* scat_asym_all) {
     int rc;
@@ -407,8 +415,52 @@ static int check_workspace(lbl_ctx* ctx, lbl_buffer* workspace, int quantities, 
     return LBL_OK;
 }
 
-// K5l: lbl_column_solar_dev's checks in its order, the scatterers' and the workspace's behind them; then every band in passes
-// of as many points as the workspace holds, the band's partial slots zeroed first and reduced after its last pass.
+// the scatter part's fields that are not the scatterers' (those: check_scatterers), from checked arguments
+static void fill_scatter_part(ScatterPart* a, lbl_buffer* emissivity, double emissivity_all, lbl_buffer* workspace,
+                              int64_t ws_points, lbl_buffer* up_top, lbl_buffer* down_surface, lbl_buffer* up_surface,
+                              int delta_scaling) {
+    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
+    a->emissivity_all = emissivity_all;
+    a->workspace = buffer_data(workspace);
+    a->ws_points = ws_points;
+    a->up_top = up_top ? buffer_data(up_top) : nullptr;
+    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
+    a->up_surface = up_surface ? buffer_data(up_surface) : nullptr;
+    a->delta_scaling = delta_scaling;
+}
+
+// The launch sequence of K5l and K5m on a checked argument block: the partial scratch, the block uploaded, the spectra zeroed,
+// then every band in passes of as many points as the workspace holds, the band's partial slots zeroed first and reduced after
+// its last pass.  `rows` level sums per band; `variant` picks the downward kernel (K5l: n_beams; K5m: bool linear).
+template <class Args, class Variant>
+static int run_scatter_bands(lbl_ctx* ctx, const Args* a, Variant variant, int rows, int64_t n, int n_bands,
+                             const int64_t* band_first, const int64_t* band_count, std::initializer_list<double*> spectra,
+                             lbl_buffer* level_flux) {
+    const int nv = rows * (a->n_layers + 1);
+    const int64_t max_count = *std::max_element(band_count, band_count + n_bands);
+    int rc;
+    void* partial = nullptr;
+    if ((rc = ctx_reduction_scratch(ctx, (size_t)twostream_partials(max_count) * nv * sizeof(double), &partial))) return rc;
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, a, sizeof(Args), &d_args))) return rc;
+    const hipStream_t s = ctx_stream(ctx);
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    // (points outside every band keep 0 in the spectra)
+    for (double* p : spectra)
+        if (p && n > 0) COLUMN_HIP_TRY(ctx, hipMemsetAsync(p, 0, (size_t)n * sizeof(double), s));
+    for (int b = 0; b < n_bands; ++b) {
+        const int slots = twostream_partials(band_count[b]);
+        COLUMN_HIP_TRY(ctx, hipMemsetAsync(partial, 0, (size_t)slots * nv * sizeof(double), s));
+        for (int64_t done = 0; done < band_count[b]; done += a->ws_points)
+            launch_scatter_pass((const Args*)d_args, variant, band_first[b], band_first[b] + done,
+                                std::min<int64_t>(a->ws_points, band_count[b] - done), slots, (double*)partial, s);
+        launch_scatter_final(rows, a->n_layers, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
+    }
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+}
+
+// K5l: lbl_column_solar_dev's checks in its order, the scatterers' and the workspace's behind them; then run_scatter_bands.
 extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
                                         double range_min, double range_max, int64_t n, lbl_buffer* S0, int n_beams,
                                         const double* beam_weight, const double* slant, int n_scat, const double* scat_amount,
@@ -443,12 +495,9 @@ extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* 
     if ((rc = ctx_check_buffer(ctx, direct_surface, n, "direct_surface", false))) return rc;
     if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
     if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
-    int64_t max_count = 0;
-    for (int b = 0; b < n_bands; ++b) {
+    for (int b = 0; b < n_bands; ++b)
         if (band_first[b] < 0 || band_count[b] < 1 || band_count[b] > n - band_first[b])
             return column_fail(ctx, LBL_ERR_BAD_ARG, "band %d: empty or outside [0, n)", b);
-        max_count = std::max(max_count, band_count[b]);
-    }
     for (int l = 0; l < n_layers; ++l) {
         if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
         if (!(depth[l] >= 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: depth must be >= 0", l);
@@ -471,48 +520,62 @@ extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* 
         return rc;
     int64_t ws_points = 0;
     if ((rc = check_workspace(ctx, workspace, kTwoStreamQuantities, n_layers, &ws_points))) return rc;
+    fill_scatter_part(a, emissivity, emissivity_all, workspace, ws_points, up_top, down_surface, up_surface, delta_scaling);
     a->S0 = buffer_data(S0);
-    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
-    a->emissivity_all = emissivity_all;
-    a->workspace = buffer_data(workspace);
-    a->ws_points = ws_points;
-    a->up_top = up_top ? buffer_data(up_top) : nullptr;
-    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
     a->direct_surface = direct_surface ? buffer_data(direct_surface) : nullptr;
-    a->up_surface = up_surface ? buffer_data(up_surface) : nullptr;
-    a->n_layers = n_layers; a->delta_scaling = delta_scaling;
-
-    void* partial = nullptr;
-    if ((rc = ctx_reduction_scratch(ctx, (size_t)twostream_partials(max_count) * nv * sizeof(double), &partial))) return rc;
-    void* d_args = nullptr;
-    if ((rc = ctx_device_args(ctx, a, sizeof(TwoStreamArgs), &d_args))) return rc;
-    const hipStream_t s = ctx_stream(ctx);
-    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
-    // (points outside every band keep 0 in the spectra)
-    for (double* p : {a->up_top, a->down_surface, a->direct_surface, a->up_surface})
-        if (p && n > 0) COLUMN_HIP_TRY(ctx, hipMemsetAsync(p, 0, (size_t)n * sizeof(double), s));
-    for (int b = 0; b < n_bands; ++b) {
-        const int slots = twostream_partials(band_count[b]);
-        COLUMN_HIP_TRY(ctx, hipMemsetAsync(partial, 0, (size_t)slots * nv * sizeof(double), s));
-        for (int64_t done = 0; done < band_count[b]; done += ws_points)
-            launch_twostream_pass((const TwoStreamArgs*)d_args, n_beams, band_first[b], band_first[b] + done,
-                                  std::min<int64_t>(ws_points, band_count[b] - done), slots, (double*)partial, s);
-        launch_twostream_final(n_layers, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
-    }
-    COLUMN_HIP_TRY(ctx, hipGetLastError());
-    return LBL_OK;
+    a->n_layers = n_layers;
+    return run_scatter_bands(ctx, a, n_beams, 3, n, n_bands, band_first, band_count,
+                             {a->up_top, a->down_surface, a->direct_surface, a->up_surface}, level_flux);
 } LBL_GUARD_END(ctx)
 
-// K5m: the doubles of a workspace that holds `points` points (rounded up to whole tiles, at least one) in one pass
-extern "C" int lbl_column_flux_scatter_workspace(int n_layers, int64_t points, int64_t* doubles) {
-    if (!doubles || n_layers < 0 || n_layers > kMaxLayers || points < 0 || points > (int64_t)1 << 40) return LBL_ERR_BAD_ARG;
-    const int64_t tiles = std::max<int64_t>((points + kTwoStreamTile - 1) / kTwoStreamTile, 1);
-    *doubles = (int64_t)kScatterFluxQuantities * (n_layers + 1) * tiles * kTwoStreamTile;
+// The thermal scattering column of K5m and K5n, checked in two halves around each call's own checks (its output buffer; K5n's
+// views).  Head: check_column with the two-stream angle in place of an angle set (column, temperatures, surface source,
+// bands), finite layer temperatures, and the scatterer count and switches.
+static int check_scatter_column_head(lbl_ctx* ctx, const char* what, ScatterFluxArgs* a, int n_layers, lbl_buffer* const* abs_coef,
+                                     const double* T, int planck_linear, const double* depth, double range_min,
+                                     double range_max, int64_t n, lbl_buffer* I_surface, double surface_T, int n_scat,
+                                     const double* scat_amount, int delta_scaling, int n_bands, const int64_t* band_first,
+                                     const int64_t* band_count) {
+    if (planck_linear != 0 && planck_linear != 1)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "planck_linear must be 0 (layer temperatures) or 1 (edge temperatures)");
+    const double mu = 0.5773502691896258, weight = kPi;      // 1 / sqrt(3) and pi: what the result corresponds to
+    int rc;
+    if ((rc = check_column(ctx, what, a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface, surface_T, 1, &mu,
+                           &weight, n_bands, band_first, band_count, planck_linear ? a->pbkT_top : nullptr)))
+        return rc;
+    for (int l = 0; l < n_layers && !planck_linear; ++l)
+        if (!std::isfinite(T[l])) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be finite and > 0", l);
+    if (n_scat < 0 || n_scat > kMaxScatterers) return column_fail(ctx, LBL_ERR_BAD_ARG, "0..%d scatterers", kMaxScatterers);
+    if (n_scat > 0 && n_layers > 0 && !scat_amount) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL scatterer amounts");
+    if (delta_scaling != 0 && delta_scaling != 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "delta_scaling must be 0 or 1");
     return LBL_OK;
 }
 
-// K5m: check_column with the two-stream angle in place of an angle set (column, temperatures, surface source, bands), what
-// lbl_column_flux_surface_dev checks behind it, then K5l's scatterers and workspace; the launch sequence is K5l's.
+// Tail: the optional buffers (up_surface: nullptr for K5n), the emissivity, K5l's scatterers and workspace; then I_top and the
+// scatter part filled.
+static int check_scatter_column_tail(lbl_ctx* ctx, ScatterFluxArgs* a, int n_layers, int64_t n, lbl_buffer* I_top, int n_scat,
+                                     const double* scat_amount, lbl_buffer* const* scat_ext, const double* scat_ext_all,
+                                     lbl_buffer* const* scat_ssa, const double* scat_ssa_all, lbl_buffer* const* scat_asym,
+                                     const double* scat_asym_all, int delta_scaling, lbl_buffer* emissivity,
+                                     double emissivity_all, lbl_buffer* workspace, lbl_buffer* up_top,
+                                     lbl_buffer* down_surface, lbl_buffer* up_surface) {
+    int rc;
+    if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    if ((rc = check_scatterers(ctx, a, n_layers, n, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa, scat_ssa_all,
+                               scat_asym, scat_asym_all)))
+        return rc;
+    int64_t ws_points = 0;
+    if ((rc = check_workspace(ctx, workspace, kScatterFluxQuantities, n_layers, &ws_points))) return rc;
+    a->I_top = I_top ? buffer_data(I_top) : nullptr;
+    fill_scatter_part(a, emissivity, emissivity_all, workspace, ws_points, up_top, down_surface, up_surface, delta_scaling);
+    return LBL_OK;
+}
+
+// K5m: the thermal scattering column's checks around the level sums' buffer; the launch sequence is K5l's.
 extern "C" int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
                                            int planck_linear, const double* depth, double range_min, double range_max,
                                            int64_t n, lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top, int n_scat,
@@ -526,70 +589,22 @@ extern "C" int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffe
     if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     std::vector<char> blk(sizeof(ScatterFluxArgs), 0);
     ScatterFluxArgs* a = (ScatterFluxArgs*)blk.data();
-    if (planck_linear != 0 && planck_linear != 1)
-        return column_fail(ctx, LBL_ERR_BAD_ARG, "planck_linear must be 0 (layer temperatures) or 1 (edge temperatures)");
-    const double mu = 0.5773502691896258, weight = kPi;      // 1 / sqrt(3) and pi: what the result corresponds to
     int rc;
-    if ((rc = check_column(ctx, "scattering level fluxes", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
-                           surface_T, 1, &mu, &weight, n_bands, band_first, band_count, planck_linear ? a->pbkT_top : nullptr)))
+    if ((rc = check_scatter_column_head(ctx, "scattering level fluxes", a, n_layers, abs_coef, T, planck_linear, depth, range_min,
+                                        range_max, n, I_surface, surface_T, n_scat, scat_amount, delta_scaling, n_bands,
+                                        band_first, band_count)))
         return rc;
-    for (int l = 0; l < n_layers && !planck_linear; ++l)
-        if (!std::isfinite(T[l])) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be finite and > 0", l);
-    if (n_scat < 0 || n_scat > kMaxScatterers) return column_fail(ctx, LBL_ERR_BAD_ARG, "0..%d scatterers", kMaxScatterers);
-    if (n_scat > 0 && n_layers > 0 && !scat_amount) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL scatterer amounts");
-    if (delta_scaling != 0 && delta_scaling != 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "delta_scaling must be 0 or 1");
-    const int nv = 2 * (n_layers + 1);
-    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
-    if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
-    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
-    if ((rc = check_scatterers(ctx, a, n_layers, n, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa, scat_ssa_all,
-                               scat_asym, scat_asym_all)))
+    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * 2 * (n_layers + 1), "level_flux", true))) return rc;
+    if ((rc = check_scatter_column_tail(ctx, a, n_layers, n, I_top, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa,
+                                        scat_ssa_all, scat_asym, scat_asym_all, delta_scaling, emissivity, emissivity_all,
+                                        workspace, up_top, down_surface, up_surface)))
         return rc;
-    int64_t ws_points = 0;
-    if ((rc = check_workspace(ctx, workspace, kScatterFluxQuantities, n_layers, &ws_points))) return rc;
-    int64_t max_count = 0;
-    for (int b = 0; b < n_bands; ++b) max_count = std::max(max_count, band_count[b]);
-    a->I_top = I_top ? buffer_data(I_top) : nullptr;
-    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
-    a->emissivity_all = emissivity_all;
-    a->workspace = buffer_data(workspace);
-    a->ws_points = ws_points;
-    a->up_top = up_top ? buffer_data(up_top) : nullptr;
-    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
-    a->up_surface = up_surface ? buffer_data(up_surface) : nullptr;
-    a->delta_scaling = delta_scaling;
-
-    void* partial = nullptr;
-    if ((rc = ctx_reduction_scratch(ctx, (size_t)twostream_partials(max_count) * nv * sizeof(double), &partial))) return rc;
-    void* d_args = nullptr;
-    if ((rc = ctx_device_args(ctx, a, sizeof(ScatterFluxArgs), &d_args))) return rc;
-    const hipStream_t s = ctx_stream(ctx);
-    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
-    // (points outside every band keep 0 in the spectra)
-    for (double* p : {a->up_top, a->down_surface, a->up_surface})
-        if (p && n > 0) COLUMN_HIP_TRY(ctx, hipMemsetAsync(p, 0, (size_t)n * sizeof(double), s));
-    for (int b = 0; b < n_bands; ++b) {
-        const int slots = twostream_partials(band_count[b]);
-        COLUMN_HIP_TRY(ctx, hipMemsetAsync(partial, 0, (size_t)slots * nv * sizeof(double), s));
-        for (int64_t done = 0; done < band_count[b]; done += ws_points)
-            launch_scatter_flux_pass((const ScatterFluxArgs*)d_args, planck_linear != 0, band_first[b], band_first[b] + done,
-                                     std::min<int64_t>(ws_points, band_count[b] - done), slots, (double*)partial, s);
-        launch_scatter_flux_final(n_layers, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
-    }
-    COLUMN_HIP_TRY(ctx, hipGetLastError());
-    return LBL_OK;
+    return run_scatter_bands(ctx, a, planck_linear != 0, 2, n, n_bands, band_first, band_count,
+                             {a->up_top, a->down_surface, a->up_surface}, level_flux);
 } LBL_GUARD_END(ctx)
 
-// K5n: the doubles of a workspace that holds `points` points in one pass: K5m's (the layer quantities are recomputed)
-extern "C" int lbl_column_radiance_scatter_workspace(int n_layers, int64_t points, int64_t* doubles) {
-    return lbl_column_flux_scatter_workspace(n_layers, points, doubles);
-}
-
-// K5n: lbl_column_flux_scatter_dev's checks in its order over one band, the whole grid, then the views and the radiance
-// buffer; the passes are K5m's, without partial sums.
+// K5n: the thermal scattering column's checks over one band, the whole grid, around the views' and the radiance buffer's;
+// the passes are K5m's, without partial sums.
 extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
                                                int planck_linear, const double* depth, double range_min, double range_max,
                                                int64_t n, lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
@@ -603,19 +618,12 @@ extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_b
     if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     std::vector<char> blk(sizeof(ScatterRadianceArgs), 0);
     ScatterRadianceArgs* a = (ScatterRadianceArgs*)blk.data();
-    if (planck_linear != 0 && planck_linear != 1)
-        return column_fail(ctx, LBL_ERR_BAD_ARG, "planck_linear must be 0 (layer temperatures) or 1 (edge temperatures)");
-    const double mu = 0.5773502691896258, weight = kPi;      // (K5m's angle set: not used by the kernels)
     const int64_t band_first = 0, band_count = n;
     int rc;
-    if ((rc = check_column(ctx, "scattering radiances", a, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
-                           surface_T, 1, &mu, &weight, 1, &band_first, &band_count, planck_linear ? a->pbkT_top : nullptr)))
+    if ((rc = check_scatter_column_head(ctx, "scattering radiances", a, n_layers, abs_coef, T, planck_linear, depth, range_min,
+                                        range_max, n, I_surface, surface_T, n_scat, scat_amount, delta_scaling, 1, &band_first,
+                                        &band_count)))
         return rc;
-    for (int l = 0; l < n_layers && !planck_linear; ++l)
-        if (!std::isfinite(T[l])) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: T must be finite and > 0", l);
-    if (n_scat < 0 || n_scat > kMaxScatterers) return column_fail(ctx, LBL_ERR_BAD_ARG, "0..%d scatterers", kMaxScatterers);
-    if (n_scat > 0 && n_layers > 0 && !scat_amount) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL scatterer amounts");
-    if (delta_scaling != 0 && delta_scaling != 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "delta_scaling must be 0 or 1");
     if (n_views < 1 || n_views > kMaxScatterViews) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d views", kMaxScatterViews);
     if (!view_mu || !view_down) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL view list");
     for (int v = 0; v < kMaxScatterViews; ++v) {
@@ -628,24 +636,10 @@ extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_b
         a->view_down[v] = v < n_views ? view_down[v] : 0;
     }
     if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_views * n, "radiance", true))) return rc;
-    if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
-    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
-    if ((rc = check_scatterers(ctx, a, n_layers, n, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa, scat_ssa_all,
-                               scat_asym, scat_asym_all)))
+    if ((rc = check_scatter_column_tail(ctx, a, n_layers, n, I_top, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa,
+                                        scat_ssa_all, scat_asym, scat_asym_all, delta_scaling, emissivity, emissivity_all,
+                                        workspace, up_top, down_surface, nullptr)))
         return rc;
-    int64_t ws_points = 0;
-    if ((rc = check_workspace(ctx, workspace, kScatterFluxQuantities, n_layers, &ws_points))) return rc;
-    a->I_top = I_top ? buffer_data(I_top) : nullptr;
-    a->emissivity = emissivity ? buffer_data(emissivity) : nullptr;
-    a->emissivity_all = emissivity_all;
-    a->workspace = buffer_data(workspace);
-    a->ws_points = ws_points;
-    a->up_top = up_top ? buffer_data(up_top) : nullptr;
-    a->down_surface = down_surface ? buffer_data(down_surface) : nullptr;
-    a->up_surface = nullptr;
-    a->delta_scaling = delta_scaling;
     a->radiance = buffer_data(radiance);
     a->n_views = n_views;
 
@@ -653,9 +647,9 @@ extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_b
     if ((rc = ctx_device_args(ctx, a, sizeof(ScatterRadianceArgs), &d_args))) return rc;
     const hipStream_t s = ctx_stream(ctx);
     COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
-    for (int64_t done = 0; done < n; done += ws_points)
+    for (int64_t done = 0; done < n; done += a->ws_points)
         launch_scatter_radiance_pass((const ScatterRadianceArgs*)d_args, planck_linear != 0, n_views, done,
-                                     std::min<int64_t>(ws_points, n - done), s);
+                                     std::min<int64_t>(a->ws_points, n - done), s);
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
 } LBL_GUARD_END(ctx)

@@ -373,66 +373,56 @@ void launch_solar(const SolarArgs* d_args, int n_layers, int n_beams, int n_angl
 // kTwoStreamTile points of one workgroup.
 constexpr int kMaxScatterers = 4;
 constexpr int kTwoStreamTile = 256;
-constexpr int kTwoStreamQuantities = 5;    // workspace[q][level][point]: R*, D*, U1, U0 (levels 1 .. L), direct flux
-struct TwoStreamArgs {
-    const double* abs_coef[kMaxLayers];
-    double depth[kMaxLayers];
-    double slant[kMaxFluxAngles][kMaxLayers];   // beam s, layer l: path length through the layer per unit depth, > 0
-    double m[kMaxFluxAngles][kMaxLayers];       // 1 / slant, from the host
+// What the family's argument blocks (K5l here, K5m and K5n below) hold alike: the scatterers, the reflecting surface, the
+// workspace and the optional spectra.  The device functions and the host's checks of these fields take this part.
+struct ScatterPart {
     double amount[kMaxScatterers][kMaxLayers];  // scatterer c, layer l; 0 for c >= n_scat
-    double beam_w[kMaxFluxAngles];
     const double* ext[kMaxScatterers];          // n points each, or nullptr: the number beside it (0 for c >= n_scat)
     const double* ssa[kMaxScatterers];
     const double* asym[kMaxScatterers];
     double ext_all[kMaxScatterers], ssa_all[kMaxScatterers], asym_all[kMaxScatterers];
-    const double* S0;                   // the beams' irradiance at the top, n points
     const double* emissivity;           // n points, or nullptr: emissivity_all
     double emissivity_all;
-    double* workspace;                  // kTwoStreamQuantities x (n_layers + 1) x ws_points
+    double* workspace;                  // quantities x (n_layers + 1) x ws_points
     long long ws_points;                // points of one pass: a whole number of tiles
     double* up_top;                     // optional spectra
     double* down_surface;
-    double* direct_surface;
     double* up_surface;
-    int32_t n_layers, delta_scaling;
+    int32_t delta_scaling, pad_scatter;
+};
+constexpr int kTwoStreamQuantities = 5;    // workspace[q][level][point]: R*, D*, U1, U0 (levels 1 .. L), direct flux
+struct TwoStreamArgs : ScatterPart {
+    const double* abs_coef[kMaxLayers];
+    double depth[kMaxLayers];
+    double slant[kMaxFluxAngles][kMaxLayers];   // beam s, layer l: path length through the layer per unit depth, > 0
+    double m[kMaxFluxAngles][kMaxLayers];       // 1 / slant, from the host
+    double beam_w[kMaxFluxAngles];
+    const double* S0;                   // the beams' irradiance at the top, n points
+    double* direct_surface;             // optional spectrum, beside ScatterPart's
+    int32_t n_layers, pad;
 };
 // partial-sum slots of a band of `count` points: one per tile up to kFluxMaxBlocks, tile t adds into slot t % slots
 int twostream_partials(long long count);
 // one pass over the points [first, first + count) of the band that starts at band_first: first - band_first is a multiple of
 // the tile and count <= ws_points; the second kernel adds the pass's tiles into their slots of `partial` (zeroed by the
 // caller before the band's first pass)
-void launch_twostream_pass(const TwoStreamArgs* d_args, int n_beams, long long band_first, long long first, long long count,
-                           int slots, double* partial, hipStream_t s);
-// the fixed-order reduction of a band's slots into level_flux[0 .. 3 (n_layers + 1))
-void launch_twostream_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s);
+void launch_scatter_pass(const TwoStreamArgs* d_args, int n_beams, long long band_first, long long first, long long count,
+                         int slots, double* partial, hipStream_t s);
+// the fixed-order reduction of a band's slots into level_flux[0 .. rows (n_layers + 1)): 3 rows for K5l, 2 for K5m
+void launch_scatter_final(int rows, int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s);
 
 // Thermal fluxes through scattering layers (K5m, lbl_column_transport.hip: lbl_column_flux_scatter_dev): K5l's layer solution,
 // adding, workspace, tiles and partial slots, with the layers' Planck emission as the source, an emitting Lambertian surface
-// and a downward flux at the top.  Of ColumnRT the angle set is not used (the two-stream angle is built in); the scatterer
-// fields carry TwoStreamArgs' names, so that the kernels share K5l's device functions.  Values per band as K5c's.
+// and a downward flux at the top.  Of ColumnRT the angle set is not used (the two-stream angle is built in).  Values per band
+// as K5c's.
 constexpr int kScatterFluxQuantities = 4;  // workspace[q][level][point]: R*, D*, U1, U0 (levels 1 .. L)
-struct ScatterFluxArgs : ColumnRT {
+struct ScatterFluxArgs : ColumnRT, ScatterPart {
     double pbkT_top[kMaxLayers];        // planck_linear: 100 h c / k / T at the top edge of layer l; pbkT holds the bottom edge
-    double amount[kMaxScatterers][kMaxLayers];  // scatterer c, layer l; 0 for c >= n_scat
-    const double* ext[kMaxScatterers];          // n points each, or nullptr: the number beside it (0 for c >= n_scat)
-    const double* ssa[kMaxScatterers];
-    const double* asym[kMaxScatterers];
-    double ext_all[kMaxScatterers], ssa_all[kMaxScatterers], asym_all[kMaxScatterers];
     const double* I_top;                // downward radiance entering at the top, or nullptr: 0
-    const double* emissivity;           // n points, or nullptr: emissivity_all
-    double emissivity_all;
-    double* workspace;                  // kScatterFluxQuantities x (n_layers + 1) x ws_points
-    long long ws_points;                // points of one pass: a whole number of tiles
-    double* up_top;                     // optional spectra
-    double* down_surface;
-    double* up_surface;
-    int32_t delta_scaling, pad;
 };
-// launch_twostream_pass and launch_twostream_final for K5m (`linear`: two edge temperatures per layer); the slots are
-// twostream_partials'
-void launch_scatter_flux_pass(const ScatterFluxArgs* d_args, bool linear, long long band_first, long long first, long long count,
-                              int slots, double* partial, hipStream_t s);
-void launch_scatter_flux_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s);
+// K5m's pass (`linear`: two edge temperatures per layer); the slots are twostream_partials', the final is launch_scatter_final
+void launch_scatter_pass(const ScatterFluxArgs* d_args, bool linear, long long band_first, long long first, long long count,
+                         int slots, double* partial, hipStream_t s);
 
 // Radiances through scattering layers (K5n, lbl_column_transport.hip: lbl_column_radiance_scatter_dev): K5m's column, whose
 // first kernel runs as it stands on the ScatterFluxArgs part of this block (the workspace is K5m's, four numbers per level),

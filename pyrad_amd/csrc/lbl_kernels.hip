@@ -4432,10 +4432,9 @@ __global__ __launch_bounds__(256) void solar_diffuse_kernel(const SolarArgs* __r
 // slot (tile of the band) % slots of the partials by the one workgroup that owns the slot, tiles ascending; the passes of a
 // band follow each other in stream order, so a slot's additions are the same whatever the pass size; column_flux_final_kernel
 // finishes.  No float atomics.
-// What the two downward kernels (K5l here, K5m below) share.  Args: TwoStreamArgs or ScatterFluxArgs.
+// What the family's kernels (K5l here, K5m and K5n below) share.
 // a point's scatterers, per unit amount: what each adds to a layer's absorption, scattering and asymmetry-weighted depths
-template <class Args>
-__device__ __forceinline__ void scatterer_numbers(const Args& A, long long j, double (&al)[kMaxScatterers],
+__device__ __forceinline__ void scatterer_numbers(const ScatterPart& A, long long j, double (&al)[kMaxScatterers],
                                                   double (&si)[kMaxScatterers], double (&et)[kMaxScatterers]) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -4450,20 +4449,20 @@ __device__ __forceinline__ void scatterer_numbers(const Args& A, long long j, do
     }
 }
 
-// layer l at a point with absorption coefficient k: its depths and the two-stream solution for diffuse light.  At t == 0
+// layer l (of depth `depth`) at a point with absorption coefficient k: its depths and the two-stream solution for diffuse light.  At t == 0
 // (`empty`) R = 0 and T = 1, and nothing else is to be used; `conservative` is den == 0, where Ab = 0.
 struct TwoStreamLayer {
     double ta, ts, tsg, t, w, g, Da, g1, g2, lam, R, T, Ab;
     bool empty, conservative;
 };
-template <class Args>
-__device__ __forceinline__ TwoStreamLayer twostream_layer(const Args& A, int l, double k, const double (&al)[kMaxScatterers],
+__device__ __forceinline__ TwoStreamLayer twostream_layer(const ScatterPart& A, int l, double depth, double k,
+                                                          const double (&al)[kMaxScatterers],
                                                           const double (&si)[kMaxScatterers],
                                                           const double (&et)[kMaxScatterers]) {
 #pragma clang fp contract(off)
     constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
     TwoStreamLayer Y;
-    double ta = k * A.depth[l], ts = 0.0, tsg = 0.0;
+    double ta = k * depth, ts = 0.0, tsg = 0.0;
 #pragma unroll
     for (int c = 0; c < kMaxScatterers; ++c) {
         const double am = A.amount[c][l];
@@ -4510,81 +4509,53 @@ __device__ __forceinline__ void twostream_add(double R, double T, double P, doub
     if (bad) Rs = Ds = __builtin_nan("");
 }
 
-template <int NB>
-__global__ __launch_bounds__(256) void twostream_down_kernel(const TwoStreamArgs* __restrict__ Ap, long long first,
-                                                             long long count) {
+// The downward walk of K5l and K5m: the point of this thread, its scatterers, then top to bottom the layer solution, the
+// stack above each level and the workspace's four numbers per level.  What a kernel adds: top(j) sets up its own state and
+// gives Ds at the top of the column; sources(l, lay, P, Q) gives the layer's sources; level(i, ws) stores what else the
+// kernel keeps per level.  (threads: blockDim.x, read by the __global__ kernel itself - see band_frame)
+template <class Args, class Top, class Sources, class Level>
+__device__ __forceinline__ void twostream_down_frame(const Args& A, unsigned threads, long long first, long long count, Top top,
+                                                     Sources sources, Level level) {
 #pragma clang fp contract(off)
-    const TwoStreamArgs& A = *Ap;
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long q = (long long)blockIdx.x * threads + threadIdx.x;
     if (q >= count) return;
     const long long j = first + q;
     const int L = A.n_layers;
     const long long row = A.ws_points;
     double* const W = A.workspace + q;
     auto ws = [&](int v, int i) -> double& { return W[((long long)v * (L + 1) + i) * row]; };
-    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
     double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
     scatterer_numbers(A, j, al, si, et);
-    double S[NB];
-    const double top = load_global_f64(A.S0, j);
-#pragma unroll
-    for (int s = 0; s < NB; ++s) S[s] = top;
-    auto direct = [&]() {
-        double f = A.beam_w[0] * S[0];
-#pragma unroll
-        for (int s = 1; s < NB; ++s) f = fma(A.beam_w[s], S[s], f);
-        return f;
-    };
-    double Rs = 0.0, Ds = 0.0;
+    double Rs = 0.0, Ds = top(j);
     bool bad = false;
-    ws(0, L) = Rs; ws(1, L) = Ds; ws(4, L) = direct();
+    ws(0, L) = Rs; ws(1, L) = Ds; level(L, ws);
     double k = L > 0 ? load_global_f64(A.abs_coef[L - 1], j) : 0.0;
     for (int l = L - 1; l >= 0; --l) {
         const double k_next = l > 0 ? load_global_f64(A.abs_coef[l - 1], j) : k;
-        const TwoStreamLayer lay = twostream_layer(A, l, k, al, si, et);
-        const double t = lay.t, w = lay.w, g = lay.g, Da = lay.Da, g1 = lay.g1, g2 = lay.g2, lam = lay.lam;
-        const double R = lay.R, T = lay.T, Ab = lay.Ab;
-        const bool empty = lay.empty;
-        bad = bad || !isfinite(t);
-        double P = 0.0, Q = 0.0;
-#pragma unroll
-        for (int s = 0; s < NB; ++s) {
-            const double Td = exp_neg_budget(t * A.slant[s][l]);       // (exactly 1 at t = 0)
-            double m = A.m[s][l];
-            const double g3 = 0.5 * (1.0 - (D * g) * m), g4 = 1.0 - g3;
-            const double a2 = g1 * g3 + g2 * g4;
-            double Tdm = Td;
-            if (fabs(1.0 - lam * m) < 1e-6) {
-                m = (1.0 - 1e-6) / lam;
-                Tdm = exp_neg_budget(t / m);
-            }
-            const double pole = (1.0 - lam * m) * (1.0 + lam * m);
-            const double Cp = (w * (g3 - a2 * m)) / pole;
-            const double u = (w * (1.0 + (Da * (g4 - g3)) * m)) / pole;
-            const double Y = (Cp * T) * (1.0 - Tdm);
-            const double Rb = empty ? 0.0 : Y + (R * u + Cp * Ab);
-            const double Tb = empty ? 0.0 : (u * (T - Tdm) + (Cp * Tdm) * Ab) - Y;
-            const double Fd = A.beam_w[s] * S[s];
-            P = s == 0 ? Rb * Fd : fma(Rb, Fd, P);
-            Q = s == 0 ? Tb * Fd : fma(Tb, Fd, Q);
-            S[s] = Td * S[s];
-        }
+        const TwoStreamLayer lay = twostream_layer(A, l, A.depth[l], k, al, si, et);
+        bad = bad || !isfinite(lay.t);
+        double P, Q;
+        sources(l, lay, P, Q);
         double U1, U0;
-        twostream_add(R, T, P, Q, bad, Rs, Ds, U1, U0);
+        twostream_add(lay.R, lay.T, P, Q, bad, Rs, Ds, U1, U0);
         ws(2, l + 1) = U1; ws(3, l + 1) = U0;
-        ws(0, l) = Rs; ws(1, l) = Ds; ws(4, l) = direct();
+        ws(0, l) = Rs; ws(1, l) = Ds; level(l, ws);
         k = k_next;
     }
 }
 
-__global__ __launch_bounds__(256) void twostream_up_kernel(const TwoStreamArgs* __restrict__ Ap, long long tile0, long long first,
-                                                           long long count, int slots, double* __restrict__ partial) {
+// The upward walk of K5l and K5m over ROWS rows of level sums (up, diffuse down and, with 3, the direct flux of workspace
+// quantity 4): the tiles of this workgroup's slot in ascending order; per tile the surface - surface(active, j, Rs, Ds, F)
+// gives `up` there - then up and dn per level from the workspace alone, the spectra, the wave sums, and the tile's value
+// added to its slot.  acc: 4 x ROWS x (kMaxLayers + 1) doubles of LDS, [wave][row][level].
+template <int ROWS, class Args, class Surface>
+__device__ __forceinline__ void twostream_up_frame(const Args& A, unsigned threads, long long tile0, long long first,
+                                                   long long count, int slots, double* __restrict__ partial, double* acc,
+                                                   Surface surface) {
 #pragma clang fp contract(off)
-    constexpr int kSlot = 3 * (kMaxLayers + 1);
-    __shared__ double acc[4 * kSlot];                // [wave][up levels 0..L, diffuse down levels 0..L, direct levels 0..L]
-    const TwoStreamArgs& A = *Ap;
+    constexpr int kSlot = ROWS * (kMaxLayers + 1);
     const int L = A.n_layers;
-    const int levels = L + 1, nv = 3 * levels;
+    const int levels = L + 1, nv = ROWS * levels;
     const long long row = A.ws_points;
     double* const my = acc + (threadIdx.x >> 6) * kSlot;
     const bool lane0 = (threadIdx.x & 63) == 0;
@@ -4596,16 +4567,16 @@ __global__ __launch_bounds__(256) void twostream_up_kernel(const TwoStreamArgs* 
         const long long j = first + q;
         const double* const W = A.workspace + q;
         auto ws = [&](int v, int i) { return active ? W[((long long)v * levels + i) * row] : 0.0; };
-        double Rs = ws(0, 0), Ds = ws(1, 0), F = ws(4, 0);
+        double Rs = ws(0, 0), Ds = ws(1, 0), F = 0.0;
+        if constexpr (ROWS == 3) F = ws(4, 0);
         const bool bad = isnan(Rs) || isnan(Ds);
         const double nan = __builtin_nan("");
-        const double e = !active ? 1.0 : A.emissivity ? A.emissivity[j] : A.emissivity_all;
-        const double albedo = 1.0 - e;
-        double up = (albedo * (Ds + F)) / (1.0 - albedo * Rs);
+        double up = surface(active, j, Rs, Ds, F);
         for (int i = 0; i <= L; ++i) {
             if (i > 0) {
                 up = ws(2, i) * up + ws(3, i);
-                Rs = ws(0, i); Ds = ws(1, i); F = ws(4, i);
+                Rs = ws(0, i); Ds = ws(1, i);
+                if constexpr (ROWS == 3) F = ws(4, i);
             }
             double dn = Rs * up + Ds;
             if (bad) up = dn = F = nan;
@@ -4613,21 +4584,90 @@ __global__ __launch_bounds__(256) void twostream_up_kernel(const TwoStreamArgs* 
                 if (i == 0) {
                     if (A.up_surface) A.up_surface[j] = up;
                     if (A.down_surface) A.down_surface[j] = dn;
-                    if (A.direct_surface) A.direct_surface[j] = F;
+                    if constexpr (ROWS == 3)
+                        if (A.direct_surface) A.direct_surface[j] = F;
                 }
                 if (i == L && A.up_top) A.up_top[j] = up;
             }
             const double s_up = wave_sum(active ? nan_to_num(up) : 0.0);
             const double s_dn = wave_sum(active ? nan_to_num(dn) : 0.0);
-            const double s_F = wave_sum(active ? nan_to_num(F) : 0.0);
-            if (lane0) { my[i] = s_up; my[levels + i] = s_dn; my[2 * levels + i] = s_F; }
+            if (lane0) { my[i] = s_up; my[levels + i] = s_dn; }
+            if constexpr (ROWS == 3) {
+                const double s_F = wave_sum(active ? nan_to_num(F) : 0.0);
+                if (lane0) my[2 * levels + i] = s_F;
+            }
         }
         __syncthreads();
         double* const slot = partial + ((tile0 + tile) % slots) * nv;
-        for (int t = threadIdx.x; t < nv; t += blockDim.x)
+        for (int t = threadIdx.x; t < nv; t += threads)
             slot[t] = slot[t] + ((acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]));
         __syncthreads();
     }
+}
+
+template <int NB>
+__global__ __launch_bounds__(256) void twostream_down_kernel(const TwoStreamArgs* __restrict__ Ap, long long first,
+                                                             long long count) {
+#pragma clang fp contract(off)
+    const TwoStreamArgs& A = *Ap;
+    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+    double S[NB];
+    auto direct = [&]() {
+        double f = A.beam_w[0] * S[0];
+#pragma unroll
+        for (int s = 1; s < NB; ++s) f = fma(A.beam_w[s], S[s], f);
+        return f;
+    };
+    twostream_down_frame(A, blockDim.x, first, count,
+        [&](long long j) {
+            const double top = load_global_f64(A.S0, j);
+#pragma unroll
+            for (int s = 0; s < NB; ++s) S[s] = top;
+            return 0.0;
+        },
+        [&](int l, const TwoStreamLayer& lay, double& P, double& Q) {
+            const double t = lay.t, w = lay.w, g = lay.g, Da = lay.Da, g1 = lay.g1, g2 = lay.g2, lam = lay.lam;
+            const double R = lay.R, T = lay.T, Ab = lay.Ab;
+            const bool empty = lay.empty;
+            P = 0.0; Q = 0.0;
+#pragma unroll
+            for (int s = 0; s < NB; ++s) {
+                const double Td = exp_neg_budget(t * A.slant[s][l]);       // (exactly 1 at t = 0)
+                double m = A.m[s][l];
+                const double g3 = 0.5 * (1.0 - (D * g) * m), g4 = 1.0 - g3;
+                const double a2 = g1 * g3 + g2 * g4;
+                double Tdm = Td;
+                if (fabs(1.0 - lam * m) < 1e-6) {
+                    m = (1.0 - 1e-6) / lam;
+                    Tdm = exp_neg_budget(t / m);
+                }
+                const double pole = (1.0 - lam * m) * (1.0 + lam * m);
+                const double Cp = (w * (g3 - a2 * m)) / pole;
+                const double u = (w * (1.0 + (Da * (g4 - g3)) * m)) / pole;
+                const double Y = (Cp * T) * (1.0 - Tdm);
+                const double Rb = empty ? 0.0 : Y + (R * u + Cp * Ab);
+                const double Tb = empty ? 0.0 : (u * (T - Tdm) + (Cp * Tdm) * Ab) - Y;
+                const double Fd = A.beam_w[s] * S[s];
+                P = s == 0 ? Rb * Fd : fma(Rb, Fd, P);
+                Q = s == 0 ? Tb * Fd : fma(Tb, Fd, Q);
+                S[s] = Td * S[s];
+            }
+        },
+        [&](int i, auto& ws) { ws(4, i) = direct(); });
+}
+
+__global__ __launch_bounds__(256) void twostream_up_kernel(const TwoStreamArgs* __restrict__ Ap, long long tile0, long long first,
+                                                           long long count, int slots, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    __shared__ double acc[4 * 3 * (kMaxLayers + 1)];     // [wave][up levels 0..L, diffuse down levels 0..L, direct levels 0..L]
+    const TwoStreamArgs& A = *Ap;
+    // the reflecting surface under the diffuse and the direct light
+    twostream_up_frame<3>(A, blockDim.x, tile0, first, count, slots, partial, acc,
+        [&](bool active, long long j, double Rs, double Ds, double F) {
+            const double e = !active ? 1.0 : A.emissivity ? A.emissivity[j] : A.emissivity_all;
+            const double albedo = 1.0 - e;
+            return (albedo * (Ds + F)) / (1.0 - albedo * Rs);
+        });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -4645,103 +4685,74 @@ __global__ __launch_bounds__(256) void twostream_up_kernel(const TwoStreamArgs* 
 // A thread holds one point, so the fold's one-exp-per-thread Planck path (successive points of a thread) has nothing to run
 // along: every Planck value is the fold's general expression (planck_budget; the calls exist in the default arithmetic only).
 // Workspace layout, tiles, scalar loads, the partial slots by tile of the band and the absence of atomics are K5l's.
+// pi B at the bottom and the top edge of layer l (K5m's downward walk, K5n's upward one).  LINEAR: the edge that the walk
+// reaches first is the far edge of the layer before it where the two temperatures are equal (a workgroup-uniform test), and
+// then comes from `carried`, which receives this layer's far edge; otherwise one Planck value per layer.
+template <bool LINEAR>
+__device__ __forceinline__ void planck_edge_pair(const ScatterFluxArgs& A, double nu, int l, bool down, bool first_layer,
+                                                 double& carried, double& Bb, double& Bt) {
+#pragma clang fp contract(off)
+    if (!LINEAR) {
+        Bb = Bt = kPi * planck_budget(nu, A.pa, A.pbkT[l]);
+        return;
+    }
+    const double near = down ? A.pbkT_top[l] : A.pbkT[l], far = down ? A.pbkT[l] : A.pbkT_top[l];
+    const bool shared_edge = !first_layer && near == (down ? A.pbkT[l + 1] : A.pbkT_top[l - 1]);
+    const double Bn = shared_edge ? carried : kPi * planck_budget(nu, A.pa, near);
+    const double Bf = kPi * planck_budget(nu, A.pa, far);
+    carried = Bf;
+    Bb = down ? Bf : Bn;
+    Bt = down ? Bn : Bf;
+}
+
+// the emitting Lambertian surface of K5m and K5n at point j: `up` there, under the stack dn = Rs up + Ds
+__device__ __forceinline__ double emitting_surface_up(const ScatterFluxArgs& A, long long j, double nu, double Rs, double Ds) {
+#pragma clang fp contract(off)
+    const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
+    const double Is = A.I_surface ? A.I_surface[j] : planck_budget(nu, A.pa, A.pbk_surface);
+    const double albedo = 1.0 - e;
+    return (e * (kPi * Is) + albedo * Ds) / (1.0 - albedo * Rs);
+}
+
 template <bool LINEAR>
 __global__ __launch_bounds__(256) void scatter_flux_down_kernel(const ScatterFluxArgs* __restrict__ Ap, long long first,
                                                                 long long count) {
 #pragma clang fp contract(off)
     const ScatterFluxArgs& A = *Ap;
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= count) return;
-    const long long j = first + q;
-    const int L = A.n_layers;
-    const long long row = A.ws_points;
-    double* const W = A.workspace + q;
-    auto ws = [&](int v, int i) -> double& { return W[((long long)v * (L + 1) + i) * row]; };
     constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
-    double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
-    scatterer_numbers(A, j, al, si, et);
-    const double nu = linspace_at(j, A.n, A.start, A.stop, A.step);
-    double Rs = 0.0, Ds = A.I_top ? kPi * load_global_f64(A.I_top, j) : 0.0;
-    bool bad = false;
-    ws(0, L) = Rs; ws(1, L) = Ds;
-    double k = L > 0 ? load_global_f64(A.abs_coef[L - 1], j) : 0.0;
+    const int L = A.n_layers;
+    double nu = 0.0;
     double B_above = 0.0;                           // LINEAR: pi B at the bottom edge of the layer above
-    for (int l = L - 1; l >= 0; --l) {
-        const double k_next = l > 0 ? load_global_f64(A.abs_coef[l - 1], j) : k;
-        const TwoStreamLayer lay = twostream_layer(A, l, k, al, si, et);
-        bad = bad || !isfinite(lay.t);
-        const double Bb = kPi * planck_budget(nu, A.pa, A.pbkT[l]);
-        double P = Bb * lay.Ab, Q = P;
-        if (LINEAR) {
-            const bool shared_edge = l < L - 1 && A.pbkT_top[l] == A.pbkT[l + 1];
-            const double Bt = shared_edge ? B_above : kPi * planck_budget(nu, A.pa, A.pbkT_top[l]);
-            const double d = Bb - Bt;
-            const double h = (lay.Ab + 2.0 * lay.R) / (D * (lay.t - lay.tsg)) - lay.T;
-            P = Bt * lay.Ab + d * h;
-            Q = Bb * lay.Ab - d * h;
-            B_above = Bb;
-        }
-        if (lay.empty || lay.conservative || lay.ta == 0.0) P = Q = 0.0;       // (nothing absorbs: nothing emits)
-        double U1, U0;
-        twostream_add(lay.R, lay.T, P, Q, bad, Rs, Ds, U1, U0);
-        ws(2, l + 1) = U1; ws(3, l + 1) = U0;
-        ws(0, l) = Rs; ws(1, l) = Ds;
-        k = k_next;
-    }
+    twostream_down_frame(A, blockDim.x, first, count,
+        [&](long long j) {
+            nu = linspace_at(j, A.n, A.start, A.stop, A.step);
+            return A.I_top ? kPi * load_global_f64(A.I_top, j) : 0.0;
+        },
+        [&](int l, const TwoStreamLayer& lay, double& P, double& Q) {
+            double Bb, Bt;
+            planck_edge_pair<LINEAR>(A, nu, l, true, l == L - 1, B_above, Bb, Bt);
+            P = Bb * lay.Ab; Q = P;
+            if (LINEAR) {
+                const double d = Bb - Bt;
+                const double h = (lay.Ab + 2.0 * lay.R) / (D * (lay.t - lay.tsg)) - lay.T;
+                P = Bt * lay.Ab + d * h;
+                Q = Bb * lay.Ab - d * h;
+            }
+            if (lay.empty || lay.conservative || lay.ta == 0.0) P = Q = 0.0;       // (nothing absorbs: nothing emits)
+        },
+        [](int, auto&) {});
 }
 
 __global__ __launch_bounds__(256) void scatter_flux_up_kernel(const ScatterFluxArgs* __restrict__ Ap, long long tile0,
                                                               long long first, long long count, int slots,
                                                               double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    constexpr int kSlot = 2 * (kMaxLayers + 1);
-    __shared__ double acc[4 * kSlot];                // [wave][up levels 0..L, down levels 0..L]
+    __shared__ double acc[4 * 2 * (kMaxLayers + 1)];     // [wave][up levels 0..L, down levels 0..L]
     const ScatterFluxArgs& A = *Ap;
-    const int L = A.n_layers;
-    const int levels = L + 1, nv = 2 * levels;
-    const long long row = A.ws_points;
-    double* const my = acc + (threadIdx.x >> 6) * kSlot;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
-    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions)
-    for (long long tile = blockIdx.x; tile < tiles; tile += slots) {
-        const long long q = tile * kTwoStreamTile + threadIdx.x;
-        const bool active = q < count;
-        const long long j = first + q;
-        const double* const W = A.workspace + q;
-        auto ws = [&](int v, int i) { return active ? W[((long long)v * levels + i) * row] : 0.0; };
-        double Rs = ws(0, 0), Ds = ws(1, 0);
-        const bool bad = isnan(Rs) || isnan(Ds);
-        const double nan = __builtin_nan("");
-        const double e = !active ? 1.0 : A.emissivity ? A.emissivity[j] : A.emissivity_all;
-        const double Is = !active ? 0.0 : A.I_surface ? A.I_surface[j]
-                                        : planck_budget(linspace_at(j, A.n, A.start, A.stop, A.step), A.pa, A.pbk_surface);
-        const double albedo = 1.0 - e;
-        double up = (e * (kPi * Is) + albedo * Ds) / (1.0 - albedo * Rs);
-        for (int i = 0; i <= L; ++i) {
-            if (i > 0) {
-                up = ws(2, i) * up + ws(3, i);
-                Rs = ws(0, i); Ds = ws(1, i);
-            }
-            double dn = Rs * up + Ds;
-            if (bad) up = dn = nan;
-            if (active) {
-                if (i == 0) {
-                    if (A.up_surface) A.up_surface[j] = up;
-                    if (A.down_surface) A.down_surface[j] = dn;
-                }
-                if (i == L && A.up_top) A.up_top[j] = up;
-            }
-            const double s_up = wave_sum(active ? nan_to_num(up) : 0.0);
-            const double s_dn = wave_sum(active ? nan_to_num(dn) : 0.0);
-            if (lane0) { my[i] = s_up; my[levels + i] = s_dn; }
-        }
-        __syncthreads();
-        double* const slot = partial + ((tile0 + tile) % slots) * nv;
-        for (int t = threadIdx.x; t < nv; t += blockDim.x)
-            slot[t] = slot[t] + ((acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]));
-        __syncthreads();
-    }
+    twostream_up_frame<2>(A, blockDim.x, tile0, first, count, slots, partial, acc,
+        [&](bool active, long long j, double Rs, double Ds, double) {
+            return !active ? 0.0 : emitting_surface_up(A, j, linspace_at(j, A.n, A.start, A.stop, A.step), Rs, Ds);
+        });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -4794,10 +4805,7 @@ __global__ __launch_bounds__(256) void scatter_radiance_up_kernel(const ScatterR
     double Rs = ws(0, 0), Ds = ws(1, 0);
     const bool bad = isnan(Rs) || isnan(Ds);
     const double nan = __builtin_nan("");
-    const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
-    const double Is = A.I_surface ? A.I_surface[j] : planck_budget(nu, A.pa, A.pbk_surface);
-    const double albedo = 1.0 - e;
-    double up = (e * (kPi * Is) + albedo * Ds) / (1.0 - albedo * Rs);
+    double up = emitting_surface_up(A, j, nu, Rs, Ds);
     double dn = Rs * up + Ds;
     if (A.down_surface) A.down_surface[j] = bad ? nan : dn;
     double I[NV], C[NV];
@@ -4810,20 +4818,13 @@ __global__ __launch_bounds__(256) void scatter_radiance_up_kernel(const ScatterR
     double B_below = 0.0;                           // LINEAR: pi B at the top edge of the layer below
     for (int l = 0; l < L; ++l) {
         const double k_next = l + 1 < L ? load_global_f64(A.abs_coef[l + 1], j) : k;
-        const TwoStreamLayer lay = twostream_layer(A, l, k, al, si, et);
+        const TwoStreamLayer lay = twostream_layer(A, l, A.depth[l], k, al, si, et);
         const double upB = up, dnB = dn;
         up = ws(2, l + 1) * up + ws(3, l + 1);
         Rs = ws(0, l + 1); Ds = ws(1, l + 1);
         dn = Rs * up + Ds;
         double Bb, Bt;
-        if (LINEAR) {
-            const bool shared_edge = l > 0 && A.pbkT[l] == A.pbkT_top[l - 1];
-            Bb = shared_edge ? B_below : kPi * planck_budget(nu, A.pa, A.pbkT[l]);
-            Bt = kPi * planck_budget(nu, A.pa, A.pbkT_top[l]);
-            B_below = Bt;
-        } else {
-            Bb = Bt = kPi * planck_budget(nu, A.pa, A.pbkT[l]);
-        }
+        planck_edge_pair<LINEAR>(A, nu, l, false, l == 0, B_below, Bb, Bt);
         if (!lay.empty) {
             const double t = lay.t, lam = lay.lam;
             const double u = lam * t;
@@ -6428,71 +6429,72 @@ void launch_solar(const SolarArgs* d_args, int n_layers, int n_beams, int n_angl
     });
 }
 
-// K5l: one pass of a band - the downward kernel over the pass's points, one per thread, then the upward kernel with one
-// workgroup per partial slot that the pass's tiles reach (a workgroup takes the tiles of its slot in ascending order).
+// K5l, K5m: the partial-sum slots of a band of `count` points
 int twostream_partials(long long count) {
     return (int)std::min<long long>(std::max<long long>((count + kTwoStreamTile - 1) / kTwoStreamTile, 1), kFluxMaxBlocks);
 }
 
-void launch_twostream_pass(const TwoStreamArgs* d_args, int n_beams, long long band_first, long long first, long long count,
-                           int slots, double* partial, hipStream_t s) {
+// One pass of a band for K5l and K5m - the downward kernel over the pass's points, one per thread (launch_down(tiles) launches
+// the family's), then its upward kernel with one workgroup per partial slot that the pass's tiles reach (a workgroup takes the
+// tiles of its slot in ascending order).
+template <class Args, class LaunchDown, class UpKernel>
+static void scatter_pass(const Args* d_args, LaunchDown launch_down, UpKernel up_kernel, long long band_first, long long first,
+                         long long count, int slots, double* partial, hipStream_t s) {
     if (count <= 0) return;
     const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
-    with_angles(n_beams, [&](auto nb) {
-        constexpr int NB = decltype(nb)::value;
-        hipLaunchKernelGGL(twostream_down_kernel<NB>, dim3((unsigned)tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
-    });
-    hipLaunchKernelGGL(twostream_up_kernel, dim3((unsigned)std::min<long long>(tiles, slots)), dim3(kTwoStreamTile), 0, s, d_args,
+    launch_down((unsigned)tiles);
+    hipLaunchKernelGGL(up_kernel, dim3((unsigned)std::min<long long>(tiles, slots)), dim3(kTwoStreamTile), 0, s, d_args,
                        (first - band_first) / kTwoStreamTile, first, count, slots, partial);
 }
 
-void launch_twostream_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s) {
-    const int nv = 3 * (n_layers + 1);
+// scatter_flux_down_kernel<linear> over the pass's points (K5m's and K5n's first kernel)
+static void launch_scatter_flux_down(const ScatterFluxArgs* d_args, bool linear, unsigned tiles, long long first, long long count,
+                                     hipStream_t s) {
+    const auto kernel = linear ? scatter_flux_down_kernel<true> : scatter_flux_down_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+}
+
+void launch_scatter_pass(const TwoStreamArgs* d_args, int n_beams, long long band_first, long long first, long long count,
+                         int slots, double* partial, hipStream_t s) {
+    scatter_pass(d_args, [&](unsigned tiles) {
+        with_angles(n_beams, [&](auto nb) {
+            hipLaunchKernelGGL(twostream_down_kernel<decltype(nb)::value>, dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first,
+                               count);
+        });
+    }, twostream_up_kernel, band_first, first, count, slots, partial, s);
+}
+
+void launch_scatter_pass(const ScatterFluxArgs* d_args, bool linear, long long band_first, long long first, long long count,
+                         int slots, double* partial, hipStream_t s) {
+    scatter_pass(d_args, [&](unsigned tiles) { launch_scatter_flux_down(d_args, linear, tiles, first, count, s); },
+                 scatter_flux_up_kernel, band_first, first, count, slots, partial, s);
+}
+
+void launch_scatter_final(int rows, int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s) {
+    const int nv = rows * (n_layers + 1);
     hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, slots, nv, level_flux);
 }
 
-// K5m: K5l's pass and final reduction with the thermal kernels and two rows of level sums
-void launch_scatter_flux_pass(const ScatterFluxArgs* d_args, bool linear, long long band_first, long long first, long long count,
-                              int slots, double* partial, hipStream_t s) {
-    if (count <= 0) return;
-    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
-    if (linear)
-        hipLaunchKernelGGL(scatter_flux_down_kernel<true>, dim3((unsigned)tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
-    else
-        hipLaunchKernelGGL(scatter_flux_down_kernel<false>, dim3((unsigned)tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
-    hipLaunchKernelGGL(scatter_flux_up_kernel, dim3((unsigned)std::min<long long>(tiles, slots)), dim3(kTwoStreamTile), 0, s, d_args,
-                       (first - band_first) / kTwoStreamTile, first, count, slots, partial);
-}
-
-void launch_scatter_flux_final(int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s) {
-    const int nv = 2 * (n_layers + 1);
-    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, slots, nv, level_flux);
-}
-
-template <bool LINEAR, int NV>
-static void launch_scatter_radiance_up(const ScatterRadianceArgs* d_args, unsigned tiles, long long first, long long count,
-                                       hipStream_t s) {
-    hipLaunchKernelGGL((scatter_radiance_up_kernel<LINEAR, NV>), dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+// f(std::integral_constant<int, NV>) for the view count rounded up to NV in {1, 2, 4, 8, 16}
+template <class F>
+static void with_views(int n_views, F f) {
+    if (n_views <= 1) f(std::integral_constant<int, 1>{});
+    else if (n_views <= 2) f(std::integral_constant<int, 2>{});
+    else if (n_views <= 4) f(std::integral_constant<int, 4>{});
+    else if (n_views <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
 }
 
 void launch_scatter_radiance_pass(const ScatterRadianceArgs* d_args, bool linear, int n_views, long long first, long long count,
                                   hipStream_t s) {
     if (count <= 0) return;
     const unsigned tiles = (unsigned)((count + kTwoStreamTile - 1) / kTwoStreamTile);
-    const ScatterFluxArgs* const flux_args = d_args;      // (the block begins with K5m's)
-    if (linear)
-        hipLaunchKernelGGL(scatter_flux_down_kernel<true>, dim3(tiles), dim3(kTwoStreamTile), 0, s, flux_args, first, count);
-    else
-        hipLaunchKernelGGL(scatter_flux_down_kernel<false>, dim3(tiles), dim3(kTwoStreamTile), 0, s, flux_args, first, count);
-#define LBL_RADIANCE_UP(NV)                                                                          \
-    (linear ? launch_scatter_radiance_up<true, NV>(d_args, tiles, first, count, s)                   \
-            : launch_scatter_radiance_up<false, NV>(d_args, tiles, first, count, s))
-    if (n_views <= 1) LBL_RADIANCE_UP(1);
-    else if (n_views <= 2) LBL_RADIANCE_UP(2);
-    else if (n_views <= 4) LBL_RADIANCE_UP(4);
-    else if (n_views <= 8) LBL_RADIANCE_UP(8);
-    else LBL_RADIANCE_UP(16);
-#undef LBL_RADIANCE_UP
+    launch_scatter_flux_down(d_args, linear, tiles, first, count, s);       // (the block begins with K5m's)
+    with_views(n_views, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        const auto kernel = linear ? scatter_radiance_up_kernel<true, NV> : scatter_radiance_up_kernel<false, NV>;
+        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+    });
 }
 
 // K5d's points per thread, chosen per angle count so that no instantiation spills (DESIGN.md "K5d")

@@ -17,6 +17,7 @@ interactive menu.
 from __future__ import annotations
 
 import math
+import types
 import weakref
 
 import numpy as np
@@ -2339,6 +2340,9 @@ def _scatter_views(views):
     return np.array(mu), down, ["down" if d else "up" for d in down]
 
 
+_NO_VIEWS = object()         # _thermal_scatter_checks: the call has no views (None is a caller's mistake, and reported)
+
+
 class PathJacobians:
     """What Atmosphere.pathJacobians returns, for R paths through L layers.  X is the grid (n points) or, with an instrument,
     its channels (C).  ``wavenumber``: (X,) the grid or the channel centres; ``radiance``: (R, X), Atmosphere.radiance's;
@@ -2791,6 +2795,71 @@ class Atmosphere(list):
                            downSpectrum=down_surface.download(n) if spectra else None,
                            upSurfaceSpectrum=up_surface.download(n) if spectra else None)
 
+    # What the three two-stream methods below share.  A new member of the family names these instead of copying a sibling.
+    @staticmethod
+    def _scatter_checks(scatterers, deltaScaling, x, n_layers):
+        """(the Scatterers, each one's (extinction, albedo, asymmetry) on the grid x) behind the checks of ``scatterers``
+        and ``deltaScaling``"""
+        scat = _scatterers(scatterers, n_layers)
+        numbers = [sc._on_grid(x) for sc in scat]
+        if not isinstance(deltaScaling, (bool, np.bool_)):
+            raise ValueError("deltaScaling: True or False, not %r" % (deltaScaling,))
+        return scat, numbers
+
+    @staticmethod
+    def _scatter_columns(ctx, st, scat, numbers):
+        """scat_amount, scat_ext, scat_ssa, scat_asym of the column_*_dev call: a number stays one, n values go into the
+        kept state ``st``"""
+        columns = []
+        for c, triple in enumerate(numbers):
+            columns.append([v if isinstance(v, float) else st.buf(ctx, "scat%d_%d" % (c, q)).upload(v)
+                            for q, v in enumerate(triple)])
+        return [sc.amounts for sc in scat], [t[0] for t in columns], [t[1] for t in columns], [t[2] for t in columns]
+
+    def _scatter_workspace(self, ctx, sizing, key, n_layers, points):
+        """The workspace buffer kept under ``key``: ``points`` points in one pass where 256 MiB hold them, else as many whole
+        tiles as they hold (``sizing``: the entry point's column_*_workspace)"""
+        tile = sizing(n_layers, 1)
+        want = sizing(n_layers, points)
+        wst = _kept_state(self, key)
+        wst.reserve(ctx, min(want, max(TWOSTREAM_WORKSPACE_BYTES // 8 // tile, 1) * tile))
+        return wst.buf(ctx, "workspace")
+
+    def _thermal_scatter_checks(self, surfaceTemperature, surfaceSpectrum, topSpectrum, bands, scatterers, deltaScaling,
+                                emissivity, planck, levelTemperatures, views=_NO_VIEWS):
+        """What fluxesTwoStream() and radianceTwoStream() check and form before the device is touched, as a namespace:
+        layers, n, mu, weight, band_first, band_count, surfaceSpectrum, topSpectrum, views (_scatter_views' triple, with
+        ``views``), scat, numbers, linear, T (the layers' temperatures, or with ``linear`` their edge pairs), emissivity,
+        depth, surface_T"""
+        c = types.SimpleNamespace()
+        c.layers, c.n, c.mu, c.weight, c.band_first, c.band_count, c.surfaceSpectrum = self._column_checks(
+            surfaceSpectrum, surfaceTemperature, [(1.0 / math.sqrt(3.0), pi)], bands)
+        c.views = _scatter_views(views) if views is not _NO_VIEWS else None
+        c.topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, c.n)
+        x = c.layers[0].xAxis
+        c.scat, c.numbers = self._scatter_checks(scatterers, deltaScaling, x, len(c.layers))
+        c.linear = _planck_source(planck, levelTemperatures)
+        if c.linear:
+            lev = self._level_temperatures(levelTemperatures)
+            c.T = np.column_stack([lev[:-1], lev[1:]])
+        else:
+            c.T = [L.T for L in c.layers]
+        c.emissivity = _surface_emissivity(emissivity, x)
+        c.depth = [L.depth for L in c.layers]
+        c.surface_T = float(surfaceTemperature or 0.0)
+        return c
+
+    def _thermal_scatter_uploads(self, ctx, st, c, sizing, workspace_key, points):
+        """The uploads of a checked column ``c`` into the kept state ``st`` and the workspace for ``points`` points: the
+        arguments of column_flux_scatter_dev and column_radiance_scatter_dev that they share - positional from scat_amount
+        to delta_scaling, then the workspace, and the keywords emissivity, I_surface, surface_T, I_top"""
+        I_surface = st.buf(ctx, "I_surface").upload(c.surfaceSpectrum) if c.surfaceSpectrum is not None else None
+        I_top = st.buf(ctx, "I_top").upload(c.topSpectrum) if c.topSpectrum is not None else None
+        emissivity = self._device_emissivity(ctx, st, c.emissivity)
+        columns = self._scatter_columns(ctx, st, c.scat, c.numbers)
+        workspace = self._scatter_workspace(ctx, sizing, workspace_key, len(c.layers), points)
+        return columns, workspace, dict(emissivity=emissivity, I_surface=I_surface, surface_T=c.surface_T, I_top=I_top)
+
     def solarFluxesTwoStream(self, scatterers=(), deltaScaling=True, solarSpectrum=None, solarTemperature=None, distanceAU=1.0,
                              mu0=1.0, geometry="plane", planetRadius=6.371e8, emissivity=1.0, bands=None, spectra=False):
         """solarFluxes() through a column that also scatters: Rayleigh air, clouds, aerosol (beyond the reference).  A
@@ -2817,10 +2886,7 @@ class Atmosphere(list):
         first = layers[0]
         x = first.xAxis
         nl = len(layers)
-        scat = _scatterers(scatterers, nl)
-        numbers = [sc._on_grid(x) for sc in scat]
-        if not isinstance(deltaScaling, (bool, np.bool_)):
-            raise ValueError("deltaScaling: True or False, not %r" % (deltaScaling,))
+        scat, numbers = self._scatter_checks(scatterers, deltaScaling, x, nl)
         S0 = _solar_spectrum(solarSpectrum, solarTemperature, distanceAU, x)
         mu_s, weight_s = _solar_beams(mu0)
         depth = [L.depth for L in layers]
@@ -2837,22 +2903,15 @@ class Atmosphere(list):
         source = st.buf(ctx, "S0").upload(S0)
         if not isinstance(emissivity, float):
             emissivity = st.buf(ctx, "emissivity").upload(emissivity)
-        columns = []
-        for c, triple in enumerate(numbers):
-            columns.append([v if isinstance(v, float) else st.buf(ctx, "scat%d_%d" % (c, q)).upload(v)
-                            for q, v in enumerate(triple)])
-        # the workspace: the widest band in one pass where 256 MiB hold it, else as many whole tiles as they hold
-        tile = ctx.column_twostream_workspace(nl, 1)
-        want = ctx.column_twostream_workspace(nl, max(band_count))
-        wst = _kept_state(self, "_twostream_workspace")
-        wst.reserve(ctx, min(want, max(TWOSTREAM_WORKSPACE_BYTES // 8 // tile, 1) * tile))
+        columns = self._scatter_columns(ctx, st, scat, numbers)
+        # (the widest band in one pass)
+        workspace = self._scatter_workspace(ctx, ctx.column_twostream_workspace, "_twostream_workspace", nl, max(band_count))
         level = st.buf(ctx, "level")
         names = ("up_top", "down_surface", "direct_surface", "up_surface")
         spec = {name: st.buf(ctx, name) if spectra else None for name in names}
-        ctx.column_twostream_dev(kbufs, depth, first.rangeMin, first.rangeMax, n, source, beam_weight, slant,
-                                 [sc.amounts for sc in scat], [t[0] for t in columns], [t[1] for t in columns],
-                                 [t[2] for t in columns], int(bool(deltaScaling)), band_first, band_count,
-                                 wst.buf(ctx, "workspace"), level, emissivity=emissivity, **spec)
+        ctx.column_twostream_dev(kbufs, depth, first.rangeMin, first.rangeMax, n, source, beam_weight, slant, *columns,
+                                 int(bool(deltaScaling)), band_first, band_count, workspace, level, emissivity=emissivity,
+                                 **spec)
         sums = level.download(nb * 3 * (nl + 1)).reshape(nb, 3, nl + 1) * res
         up, direct = sums[:, 0, :], sums[:, 2, :]
         down = sums[:, 1, :] + direct
@@ -2884,53 +2943,27 @@ class Atmosphere(list):
         Returns a Fluxes with mu = [1 / sqrt(3)] and weight = [pi].  The absorption coefficients are the resident ones;
         the workspace (four numbers per level and point) stays with the atmosphere, at most 256 MiB - a longer band is
         done in several passes, with the same bits.  Everything is validated (ValueError) before the device is touched."""
-        layers, n, mu, weight, band_first, band_count, surfaceSpectrum = self._column_checks(
-            surfaceSpectrum, surfaceTemperature, [(1.0 / math.sqrt(3.0), pi)], bands)
-        topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
-        first = layers[0]
-        nl, nb = len(layers), len(band_first)
-        scat = _scatterers(scatterers, nl)
-        numbers = [sc._on_grid(first.xAxis) for sc in scat]
-        if not isinstance(deltaScaling, (bool, np.bool_)):
-            raise ValueError("deltaScaling: True or False, not %r" % (deltaScaling,))
-        linear = _planck_source(planck, levelTemperatures)
-        if linear:
-            lev = self._level_temperatures(levelTemperatures)
-            T = np.column_stack([lev[:-1], lev[1:]])
-        else:
-            T = [L.T for L in layers]
-        emissivity = _surface_emissivity(emissivity, first.xAxis)
-        depth = [L.depth for L in layers]
-        res = utils.BASE_RESOLUTION
+        c = self._thermal_scatter_checks(surfaceTemperature, surfaceSpectrum, topSpectrum, bands, scatterers, deltaScaling,
+                                         emissivity, planck, levelTemperatures)
+        layers, n, first = c.layers, c.n, c.layers[0]
+        nl, nb = len(layers), len(c.band_first)
         ctx = _ctx()
         kbufs, _ = self._column_abs_coef(ctx, layers, n)
         st = _kept_state(self, "_scatter_flux_state")
         st.reserve(ctx, max(n, nb * 2 * (nl + 1)))
-        I_surface = st.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
-        I_top = st.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
-        emissivity = self._device_emissivity(ctx, st, emissivity)
-        columns = []
-        for c, triple in enumerate(numbers):
-            columns.append([v if isinstance(v, float) else st.buf(ctx, "scat%d_%d" % (c, q)).upload(v)
-                            for q, v in enumerate(triple)])
-        # the workspace: the widest band in one pass where 256 MiB hold it, else as many whole tiles as they hold
-        tile = ctx.column_flux_scatter_workspace(nl, 1)
-        want = ctx.column_flux_scatter_workspace(nl, max(band_count))
-        wst = _kept_state(self, "_scatter_flux_workspace")
-        wst.reserve(ctx, min(want, max(TWOSTREAM_WORKSPACE_BYTES // 8 // tile, 1) * tile))
+        # (the widest band in one pass)
+        columns, workspace, kw = self._thermal_scatter_uploads(ctx, st, c, ctx.column_flux_scatter_workspace,
+                                                               "_scatter_flux_workspace", max(c.band_count))
         level = st.buf(ctx, "level")
         names = ("up_top", "down_surface", "up_surface")
         spec = {name: st.buf(ctx, name) if spectra else None for name in names}
-        ctx.column_flux_scatter_dev(kbufs, T, int(linear), depth, first.rangeMin, first.rangeMax, n,
-                                    [sc.amounts for sc in scat], [t[0] for t in columns], [t[1] for t in columns],
-                                    [t[2] for t in columns], int(bool(deltaScaling)), band_first, band_count,
-                                    wst.buf(ctx, "workspace"), level, emissivity=emissivity, I_surface=I_surface,
-                                    surface_T=float(surfaceTemperature or 0.0), I_top=I_top, **spec)
-        sums = level.download(nb * 2 * (nl + 1)).reshape(nb, 2, nl + 1) * res
+        ctx.column_flux_scatter_dev(kbufs, c.T, int(c.linear), c.depth, first.rangeMin, first.rangeMax, n, *columns,
+                                    int(bool(deltaScaling)), c.band_first, c.band_count, workspace, level, **kw, **spec)
+        sums = level.download(nb * 2 * (nl + 1)).reshape(nb, 2, nl + 1) * utils.BASE_RESOLUTION
         up, down = sums[:, 0, :], sums[:, 1, :]
-        heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], depth)
+        heat = heatingRates(up - down, [L.P for L in layers], [L.T for L in layers], c.depth)
         up, down, heat = _band_values(bands, [up, down, heat])
-        return Fluxes(up, down, heat, mu, weight,
+        return Fluxes(up, down, heat, c.mu, c.weight,
                       upSpectrum=spec["up_top"].download(n) if spectra else None,
                       downSpectrum=spec["down_surface"].download(n) if spectra else None,
                       upSurfaceSpectrum=spec["up_surface"].download(n) if spectra else None)
@@ -2958,24 +2991,10 @@ class Atmosphere(list):
         Returns a ScatterRadiance.  The absorption coefficients are the resident ones; the workspace (four numbers per
         level and point) stays with the atmosphere, at most 256 MiB - a longer grid is done in several passes, with the same
         bits.  Everything is validated (ValueError) before the device is touched."""
-        layers, n, _, _, _, _, surfaceSpectrum = self._column_checks(
-            surfaceSpectrum, surfaceTemperature, [(1.0 / math.sqrt(3.0), pi)], None)
-        view_mu, view_down, direction = _scatter_views(views)
-        topSpectrum = _grid_spectrum("topSpectrum", topSpectrum, n)
-        first = layers[0]
-        nl = len(layers)
-        scat = _scatterers(scatterers, nl)
-        numbers = [sc._on_grid(first.xAxis) for sc in scat]
-        if not isinstance(deltaScaling, (bool, np.bool_)):
-            raise ValueError("deltaScaling: True or False, not %r" % (deltaScaling,))
-        linear = _planck_source(planck, levelTemperatures)
-        if linear:
-            lev = self._level_temperatures(levelTemperatures)
-            T = np.column_stack([lev[:-1], lev[1:]])
-        else:
-            T = [L.T for L in layers]
-        emissivity = _surface_emissivity(emissivity, first.xAxis)
-        depth = [L.depth for L in layers]
+        c = self._thermal_scatter_checks(surfaceTemperature, surfaceSpectrum, topSpectrum, None, scatterers, deltaScaling,
+                                         emissivity, planck, levelTemperatures, views=views)
+        layers, n, first = c.layers, c.n, c.layers[0]
+        view_mu, view_down, direction = c.views
         support = None
         if instrument is not None:
             if not isinstance(instrument, Instrument):
@@ -2987,18 +3006,9 @@ class Atmosphere(list):
         kbufs, _ = self._column_abs_coef(ctx, layers, n)
         st = _kept_state(self, "_scatter_radiance_state")
         st.reserve(ctx, n)
-        I_surface = st.buf(ctx, "I_surface").upload(surfaceSpectrum) if surfaceSpectrum is not None else None
-        I_top = st.buf(ctx, "I_top").upload(topSpectrum) if topSpectrum is not None else None
-        emissivity = self._device_emissivity(ctx, st, emissivity)
-        columns = []
-        for c, triple in enumerate(numbers):
-            columns.append([v if isinstance(v, float) else st.buf(ctx, "scat%d_%d" % (c, q)).upload(v)
-                            for q, v in enumerate(triple)])
-        # the workspace: the grid in one pass where 256 MiB hold it, else as many whole tiles as they hold
-        tile = ctx.column_radiance_scatter_workspace(nl, 1)
-        want = ctx.column_radiance_scatter_workspace(nl, n)
-        wst = _kept_state(self, "_scatter_radiance_workspace")
-        wst.reserve(ctx, min(want, max(TWOSTREAM_WORKSPACE_BYTES // 8 // tile, 1) * tile))
+        # (the grid in one pass)
+        columns, workspace, kw = self._thermal_scatter_uploads(ctx, st, c, ctx.column_radiance_scatter_workspace,
+                                                               "_scatter_radiance_workspace", n)
         rad = _kept_state(self, "_scatter_radiance_rows").reserve(ctx, min(V, chunk) * n).buf(ctx, "radiance")
         X = n if instrument is None else len(instrument)
         out = None
@@ -3007,11 +3017,8 @@ class Atmosphere(list):
         values = np.empty((V, X))
         for lo in range(0, V, chunk):
             hi = min(lo + chunk, V)
-            ctx.column_radiance_scatter_dev(kbufs, T, int(linear), depth, first.rangeMin, first.rangeMax, n,
-                                            [sc.amounts for sc in scat], [t[0] for t in columns], [t[1] for t in columns],
-                                            [t[2] for t in columns], int(bool(deltaScaling)), view_mu[lo:hi],
-                                            view_down[lo:hi], wst.buf(ctx, "workspace"), rad, emissivity=emissivity,
-                                            I_surface=I_surface, surface_T=float(surfaceTemperature or 0.0), I_top=I_top)
+            ctx.column_radiance_scatter_dev(kbufs, c.T, int(c.linear), c.depth, first.rangeMin, first.rangeMax, n, *columns,
+                                            int(bool(deltaScaling)), view_mu[lo:hi], view_down[lo:hi], workspace, rad, **kw)
             if instrument is None:
                 values[lo:hi] = rad.download((hi - lo) * n).reshape(hi - lo, n)
             else:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The model-level sibling of dump_transport.py: every Atmosphere method over the column transport entry points (fluxes,
-jacobians, jacobiansLinear, observe, observeLinear, radiance, pathJacobians, pathJacobiansLinear) over its option matrix on
+jacobians, jacobiansLinear, observe, observeLinear, radiance, pathJacobians, pathJacobiansLinear, solarFluxesTwoStream,
+fluxesTwoStream, radianceTwoStream) over its option matrix on
 a seeded synthetic column, every array of every result saved as .npy (one file per call, the arrays concatenated in the
 order of their attribute names), and beside them calls.txt: every Context.column_* / ray_* / ils_convolve_dev call and every
 Buffer upload, download and device copy, with its arguments by value (arrays of more than 32 values as length and SHA-1 of
@@ -204,6 +205,51 @@ def transport_calls(save):
                                                                          reflection="specular", instrument=ins))
 
 
+def scatter_calls(save):
+    """solarFluxesTwoStream, fluxesTwoStream and radianceTwoStream: no scatterers and two (numbers, n values and a table,
+    mixed), deltaScaling, the emissivity forms, planck, bands, spectra, more views than one chunk, with and without instrument"""
+    atm = column(RNG, LAYERS)
+    x = atm[0].xAxis
+    n = len(x)
+    rng = np.random.default_rng(20241021)
+    e_arr = rng.uniform(0.55, 0.98, n)
+    surface = np.array(model.planckWavenumber(x, 300.0)) * rng.uniform(0.9, 1.0, n)
+    top = 0.1 * np.array(model.planckWavenumber(x, 250.0))
+    bands = [(600.0, 604.0), (604.0, 610.07)]
+    ins = model.Instrument(np.linspace(601.5, 608.5, 5), width=0.5)
+    cloud = model.Scatterer([0.0, 3.0, 0.5, 0.0], extinction=1.0, singleScatteringAlbedo=rng.uniform(0.6, 0.99, n),
+                            asymmetry=0.8, name="cloud")
+    haze = model.Scatterer([0.2, 0.1, 0.05, 0.02], extinction=rng.uniform(0.5, 1.5, n), singleScatteringAlbedo=0.9,
+                           asymmetry=(np.array([590.0, 620.0]), np.array([0.3, 0.5])), name="haze")
+    few = [1.0, (0.6, "down"), (0.35, "up")]
+    many = few + [(0.2 + 0.04 * i, "down" if i % 3 == 0 else "up") for i in range(18)]
+    for scat in ((), (cloud, haze)):
+        for delta in (False, True):
+            for e in (1.0, 0.8, e_arr):
+                t = tag(scat=len(scat), delta=delta, e=e)
+                for spectra in (False, True):
+                    for b in (None, bands):
+                        u = t + "_" + tag(spectra=spectra, bands=b is not None)
+                        save("solarFluxesTwoStream_" + u,
+                             atm.solarFluxesTwoStream(scat, delta, solarTemperature=5772.0, mu0=[(0.5, 0.7), (0.9, 0.3)],
+                                                      emissivity=e, bands=b, spectra=spectra))
+                        for planck in ("layer", "linear"):
+                            save("fluxesTwoStream_" + u + "_" + tag(planck=planck),
+                                 atm.fluxesTwoStream(scat, delta, surfaceTemperature=290.0, topSpectrum=top, emissivity=e,
+                                                     planck=planck, bands=b, spectra=spectra))
+                for planck in ("layer", "linear"):
+                    for views in (few, many):
+                        for instrument in (None, ins):
+                            save("radianceTwoStream_" + t + "_" + tag(planck=planck, views=len(views), ins=instrument is not None),
+                                 atm.radianceTwoStream(views, scat, delta, surfaceTemperature=290.0, topSpectrum=top,
+                                                       emissivity=e, planck=planck, instrument=instrument))
+    kw = dict(surfaceSpectrum=surface, emissivity=e_arr, planck="linear", levelTemperatures=LEVELS)
+    save("fluxesTwoStream_surfaceSpectrum", atm.fluxesTwoStream((cloud, haze), bands=bands, spectra=True, **kw))
+    save("radianceTwoStream_surfaceSpectrum", atm.radianceTwoStream(many, (cloud, haze), instrument=ins, **kw))
+    save("solarFluxesTwoStream_spectrum", atm.solarFluxesTwoStream(cloud, solarSpectrum=surface, mu0=0.4, geometry="spherical",
+                                                                   spectra=True))
+
+
 def voigt_calls(save):
     """temperature="full": dk/dT as terms, which exists under the Voigt line shape only"""
     settings.set_line_shape("voigt")
@@ -224,6 +270,7 @@ def run(out):
     rec = Recorder().install()
     save = Dump(out)
     transport_calls(save)
+    scatter_calls(save)
     voigt_calls(save)
     with open(os.path.join(out, "calls.txt"), "w") as f:
         f.write("\n".join(rec.lines) + "\n")

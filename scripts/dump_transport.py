@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Every column transport entry point (K5c - K5k: fluxes, Jacobians, ray paths, reflecting surface, linear source, solar
-beam) through _native.Context on synthetic, seeded absorption coefficients, every output saved as .npy (one file per call,
+"""Every column transport entry point (K5c - K5n: fluxes, Jacobians, ray paths, reflecting surface, linear source, solar
+beam, the two-stream family) through _native.Context on synthetic, seeded absorption coefficients, every output saved as .npy (one file per call,
 its outputs concatenated): run once per library build (PYRAD_HIP_LIB) and compare the files bit for bit
 (scripts/bitcmp_libs.sh <lib a> <lib b> dump_transport.py).  No line lists are needed.  The shapes are the smallest at
 which the kernels' frames can go wrong: bands with head, aligned and tail points, a band of three points, a grid-stride
 second round in some workgroups only, every angle count on each side of the points-per-thread switch, both Planck paths,
-bundled and single rays with a surface marker, a tail launch.  usage: dump_transport.py <out dir>"""
-import os, sys
+bundled and single rays with a surface marker, a tail launch; for the two-stream family (K5l, K5m, K5n) see
+scatter_calls.  Per entry point of that family refusals_<name>.npy holds, as bytes, the return code and lbl_last_error of
+calls with one defect and with two: which of two defects is reported is part of what two builds must agree on.
+usage: dump_transport.py <out dir>"""
+import ctypes as C
+import itertools, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pyrad_amd import _native as nat
@@ -204,6 +208,189 @@ def ray_calls(tag, c):
         save(t + "_spectrum_ray_jacobian_linear", jac, rad)
 
 
+# ---- K5l, K5m, K5n: solar and thermal fluxes and radiances through scattering layers ------------------------------------------
+class ScatterColumn:
+    """L layers (optical depths 1e-3 .. tau_hi each) on n points from 600 cm^-1 in steps of 0.01, with four scatterers whose
+    numbers come as buffers and as plain numbers, mixed.  `special`: layer 1 empty (t = 0), layer 2 conservative (no gas, the
+    one scatterer in it with albedo 1) and one point of layer 0 with an infinite coefficient (the NaN rule)."""
+    def __init__(self, L, n, tau_hi=5.0, special=False):
+        self.L, self.n, self.lo, self.hi = L, n, 600.0, 600.0 + (n - 1) * 0.01
+        self.depth = [1.0e5 * (l % 7 + 1) for l in range(L)]
+        k = [np.exp(rng.uniform(np.log(1e-3), np.log(tau_hi), n)) / d for d in self.depth]
+        self.amount = [[0.05 * (c + 1) * (1 + (l + c) % 3) for l in range(L)] for c in range(4)]
+        if special:
+            k[1][:], k[2][:] = 0.0, 0.0
+            k[0][min(7, n - 1)] = np.inf
+            for c in range(4):
+                self.amount[c][1] = 0.0
+                self.amount[c][2] = 0.8 if c == 1 else 0.0
+        self.k = [dev(v) for v in k]
+        self.T = [288.0 - 0.5 * l for l in range(L)]
+        # (bottom edge, top edge): two of three top edges are the next layer's bottom edge, the third is 0.3 K off it
+        bottom = [292.0 - 0.5 * l for l in range(L + 1)]
+        self.edge_T = [(bottom[l], bottom[l + 1] - (0.3 if l % 3 == 2 else 0.0)) for l in range(L)]
+        self.S0 = dev(rng.uniform(0.5, 1.5, n))
+        self.I_surface = dev(rng.uniform(0.05, 0.2, n))
+        self.I_top = dev(rng.uniform(0.001, 0.02, n))
+        self.emissivity = dev(rng.uniform(0.5, 0.98, n))
+        ext, ssa, asym = (dev(rng.uniform(*r, n)) for r in ((0.2, 2.0), (0.3, 0.999), (-0.3, 0.85)))
+        self.ext = [ext, 1.3, dev(rng.uniform(0.1, 1.0, n)), 0.4]
+        self.ssa = [0.92, 1.0 if special else 0.97, 0.6, ssa]
+        self.asym = [asym, 0.1, -0.25, dev(rng.uniform(0.0, 0.9, n))]
+
+    def scat(self, count):
+        return [a[:count] for a in (self.amount, self.ext, self.ssa, self.asym)]
+
+
+SCATTER_WORKSPACE = dict(twostream=ctx.column_twostream_workspace, flux_scatter=ctx.column_flux_scatter_workspace,
+                         radiance_scatter=ctx.column_radiance_scatter_workspace)
+
+
+def mixed_views(count):
+    return [1.0 / (1.0 + 0.37 * v) for v in range(count)], [(v % 3 == 1) * 1 for v in range(count)]
+
+
+def scatter_calls(tag, c, bands=None, n_scat=4, delta=1, e="arr", surface="spectrum", top=True, spectra=True, ws="wide",
+                  linear=(1,), beams=(2,), views=(3,)):
+    """K5l for every beam count in `beams`, K5m and K5n for both or one Planck setting in `linear`, K5n for every view
+    count in `views`; ws: a workspace of one tile ("tile") or one that holds the widest band ("wide")"""
+    L, n = c.L, c.n
+    first, count = bands if bands else ([0], [n])
+    nb = len(first)
+    e = c.emissivity if e == "arr" else e
+    src = dict(I_surface=c.I_surface) if surface == "spectrum" else dict(surface_T=291.5)
+    src["I_top"] = c.I_top if top else None
+    spec = [empty(n) if spectra else None for _ in range(4)]
+    kept = [b for b in spec if b is not None]
+
+    def work(family, points):
+        return empty(SCATTER_WORKSPACE[family](L, 1 if ws == "tile" else points))
+    for ns in beams:
+        bw = [1.0 / (s + 1) for s in range(ns)]
+        slant = [[1.0 + 0.5 * s + 0.1 * (l % 5) for l in range(L)] for s in range(ns)]
+        levels = empty(nb * 3 * (L + 1))
+        ctx.column_twostream_dev(c.k, c.depth, c.lo, c.hi, n, c.S0, bw, slant, *c.scat(n_scat), delta, first, count,
+                                 work("twostream", max(count)), levels, emissivity=e, up_top=spec[0], down_surface=spec[1],
+                                 direct_surface=spec[2], up_surface=spec[3])
+        save("%s_b%d_twostream" % (tag, ns), levels, *kept)
+    for lin in linear:
+        T = c.edge_T if lin else c.T
+        levels = empty(nb * 2 * (L + 1))
+        ctx.column_flux_scatter_dev(c.k, T, lin, c.depth, c.lo, c.hi, n, *c.scat(n_scat), delta, first, count,
+                                    work("flux_scatter", max(count)), levels, emissivity=e, up_top=spec[0],
+                                    down_surface=spec[1], up_surface=spec[3], **src)
+        save("%s_p%d_flux_scatter" % (tag, lin), levels, *kept[:2], *kept[3:])
+        for nv in views:
+            mu, down = mixed_views(nv)
+            rad = empty(nv * n)
+            ctx.column_radiance_scatter_dev(c.k, T, lin, c.depth, c.lo, c.hi, n, *c.scat(n_scat), delta, mu, down,
+                                            work("radiance_scatter", n), rad, emissivity=e, up_top=spec[0],
+                                            down_surface=spec[1], **src)
+            save("%s_p%d_v%d_radiance_scatter" % (tag, lin, nv), rad, *kept[:2])
+    release()
+
+
+def scatter_family():
+    n = 515
+    c = lambda **kw: ScatterColumn(3, n, **kw)
+    scatter_calls("base", c(), bands=bands_of(n), linear=(0, 1), beams=range(1, 9), views=(1, 2, 3, 4, 5, 8, 9, 16))
+    scatter_calls("onetile", c(), bands=bands_of(n), ws="tile", linear=(0, 1))
+    scatter_calls("scat0", c(), bands=bands_of(n), n_scat=0)
+    scatter_calls("scat1", c(), bands=bands_of(n), n_scat=1, delta=0)
+    scatter_calls("delta0", c(), delta=0, linear=(0, 1))
+    scatter_calls("plain", c(), e=0.7, surface="T", top=False, spectra=False, linear=(0, 1))
+    scatter_calls("e0.7", c(), e=0.7)
+    scatter_calls("surfaceT", c(), surface="T")
+    scatter_calls("notop", c(), top=False)
+    scatter_calls("nospectra", c(), spectra=False)
+    for delta in (0, 1):
+        scatter_calls("special_d%d" % delta, c(special=True), bands=bands_of(n), delta=delta, linear=(0, 1), views=(2,))
+        scatter_calls("special_onetile_d%d" % delta, c(special=True), ws="tile", delta=delta, linear=(0, 1), views=(5,))
+    scatter_calls("empty", ScatterColumn(0, 1), linear=(0, 1), views=(1, 3))
+    scatter_calls("deep", ScatterColumn(nat.limit("layers_per_column"), 259, tau_hi=0.3), linear=(0, 1), beams=(1, 8),
+                  views=(1, 16))
+    scatter_calls("deep_onetile", ScatterColumn(nat.limit("layers_per_column"), 259, tau_hi=0.3), ws="tile", n_scat=2)
+    scatter_calls("wrap", ScatterColumn(1, 256 * 1025 + 7), linear=(0, 1), views=(2,))
+
+
+def refusal_calls():
+    """Per entry point of the family: calls with one defect and with two (every pair of defects that touch different
+    arguments, so each is paired with those checked behind it), the return code and the error text of each."""
+    L, n, V = 3, 515, 3
+    c = ScatterColumn(L, n)
+    i64, f64 = lambda v: (C.c_int64 * max(len(v), 1))(*v), lambda v: (C.c_double * max(len(v), 1))(*v)
+    i32 = lambda v: (C.c_int32 * max(len(v), 1))(*v)
+    ptrs = lambda v: (C.c_void_p * max(len(v), 1))(*v)
+    inf, nan = float("inf"), float("nan")
+    n_short, spec = empty(n - 1), [empty(n) for _ in range(4)]
+    ext, ssa, asym = c.ext[0], c.ssa[3], c.asym[0]
+    scat = dict(n_scat=2, scat_amount=f64([0.1, 0.0, 2.0, 1.0, 1.0, 1.0]), scat_ext=ptrs([ext.h, None]),
+                scat_ext_all=f64([0.0, 2.0]), scat_ssa=ptrs([ssa.h, None]), scat_ssa_all=f64([0.0, 1.0]),
+                scat_asym=ptrs([asym.h, None]), scat_asym_all=f64([0.0, -0.2]), delta_scaling=1)
+    head = dict(ctx=ctx.h, n_layers=L, abs_coef=ptrs([b.h for b in c.k]))
+    grid = dict(depth=f64([1e4, 2e4, 1e4]), lo=c.lo, hi=c.hi, n=n)
+    thermal = dict(I_surface=c.I_surface.h, surface_T=0.0, I_top=c.I_top.h)
+    bands = dict(n_bands=1, band_first=i64([0]), band_count=i64([n]))
+    surface = dict(emissivity=c.emissivity.h, emissivity_all=0.5)
+    edges = dict(T=f64([290.0, 280.0, 280.0, 260.0, 255.0, 240.0]), planck_linear=1)
+    tiles = {f: SCATTER_WORKSPACE[f](L, 1) for f in SCATTER_WORKSPACE}
+    good = dict(
+        twostream=dict(**head, **grid, S0=c.S0.h, n_beams=2, beam_weight=f64([0.5, 0.1]),
+                       slant=f64([2.0, 1.9, 1.8, 1.0, 1.0, 1.0]), **scat, **bands, **surface,
+                       workspace=empty(2 * tiles["twostream"]).h, level_flux=empty(3 * (L + 1)).h, up_top=spec[0].h,
+                       down_surface=spec[1].h, direct_surface=spec[2].h, up_surface=spec[3].h),
+        flux_scatter=dict(**head, **edges, **grid, **thermal, **scat, **bands, **surface,
+                          workspace=empty(2 * tiles["flux_scatter"]).h, level_flux=empty(2 * (L + 1)).h, up_top=spec[0].h,
+                          down_surface=spec[1].h, up_surface=spec[3].h),
+        radiance_scatter=dict(**head, **edges, **grid, **thermal, **scat, **surface, n_views=V, view_mu=f64([1.0, 0.5, 0.2]),
+                              view_down=i32([0, 1, 0]), workspace=empty(2 * tiles["radiance_scatter"]).h,
+                              radiance=empty(V * n).h, up_top=spec[0].h, down_surface=spec[1].h))
+    # the defect kinds of the three test_refusals, by the argument they spoil
+    shared = [dict(abs_coef=None), dict(depth=None), dict(scat_amount=None), dict(workspace=None), dict(n_layers=-1),
+              dict(n_layers=nat.limit("layers_per_column") + 1), dict(n=-5), dict(n_scat=-1),
+              dict(n_scat=nat.limit("scatterers") + 1), dict(up_top=n_short.h), dict(down_surface=n_short.h),
+              dict(emissivity=n_short.h), dict(abs_coef=ptrs([c.k[0].h, n_short.h, c.k[2].h])),
+              dict(scat_ext=ptrs([n_short.h, None])), dict(scat_ssa=ptrs([ssa.h, n_short.h])),
+              dict(scat_asym=ptrs([n_short.h, None])), dict(depth=f64([1e4, -1.0, 1e4])), dict(depth=f64([1e4, nan, 1e4])),
+              dict(scat_amount=f64([0.1, -1e-9, 2.0, 1.0, 1.0, 1.0])), dict(scat_amount=f64([inf, 0.0, 2.0, 1.0, 1.0, 1.0])),
+              dict(scat_ext_all=f64([0.0, -1.0])), dict(scat_ext_all=None), dict(scat_ssa_all=f64([0.0, 1.01])),
+              dict(scat_asym_all=f64([0.0, 1.0])), dict(scat_asym_all=f64([0.0, nan])), dict(delta_scaling=2),
+              dict(emissivity=None, emissivity_all=1.01), dict(emissivity=None, emissivity_all=nan)]
+    banded = [dict(band_first=None), dict(band_count=None), dict(level_flux=None), dict(n_bands=0),
+              dict(n_bands=nat.limit("flux_bands") + 1), dict(level_flux=n_short.h), dict(up_surface=n_short.h),
+              dict(band_count=i64([n + 1])), dict(band_first=i64([-1])), dict(band_count=i64([0]))]
+    heated = [dict(T=None), dict(I_surface=n_short.h), dict(I_top=n_short.h), dict(I_surface=None, surface_T=0.0),
+              dict(I_surface=None, surface_T=nan), dict(T=f64([290.0, 280.0, 280.0, 0.0, 255.0, 240.0])),
+              dict(T=f64([nan, 280.0, 280.0, 260.0, 255.0, 240.0])), dict(planck_linear=0, T=f64([290.0, nan, 250.0])),
+              dict(planck_linear=0, T=f64([290.0, 270.0, inf])), dict(planck_linear=2)]
+    own = dict(
+        twostream=banded + [dict(S0=None), dict(beam_weight=None), dict(slant=None), dict(n_beams=0), dict(S0=n_short.h),
+                            dict(n_beams=nat.limit("flux_angles") + 1), dict(direct_surface=n_short.h),
+                            dict(workspace=empty(tiles["twostream"] - 1).h),
+                            dict(slant=f64([2.0, 1.9, 1.8, 1.0, 0.0, 1.0])), dict(slant=f64([2.0, inf, 1.8, 1.0, 1.0, 1.0])),
+                            dict(beam_weight=f64([0.5, inf]))],
+        flux_scatter=banded + heated + [dict(workspace=empty(tiles["flux_scatter"] - 1).h)],
+        radiance_scatter=heated + [dict(radiance=None), dict(view_mu=None), dict(view_down=None), dict(n=0), dict(n_views=0),
+                                   dict(n_views=nat.limit("scatter_views") + 1), dict(view_mu=f64([1.0, 0.0, 0.2])),
+                                   dict(view_mu=f64([1.0, nan, 0.2])), dict(view_down=i32([0, 2, 0])),
+                                   dict(radiance=n_short.h), dict(workspace=empty(tiles["radiance_scatter"] - 1).h)])
+    for name, base in good.items():
+        entry = getattr(ctx.lib, "lbl_column_%s_dev" % name)
+        defects = shared + own[name]
+        calls = [{}] + defects + [dict(a, **b) for a, b in itertools.combinations(defects, 2) if not set(a) & set(b)]
+        record = bytearray()
+        for kw in calls:
+            rc = entry(*[dict(base, **kw)[key] for key in base])
+            record += b"%d %s\n" % (rc, (ctx.lib.lbl_last_error(ctx.h) or b"") if rc else b"")
+        assert entry(*base.values()) == 0 and len(calls) > 500, name
+        ctx.sync()
+        np.save(os.path.join(out, "refusals_%s.npy" % name), np.frombuffer(bytes(record), dtype=np.uint8))
+        tally[0] += 1
+        tally[1] += len(record)
+        tally[2] += len(record)
+    release()
+
+
 def release():
     ctx.sync()
     while held:
@@ -237,5 +424,7 @@ jac, ln_tau = empty(2 + 2 * 2), empty(2 * n)
 ctx.column_jacobian_dev(col.k, col.T, col.depth, *col.args(), mu, w, [0], [n], jac, ln_tau_spectra=ln_tau, surface_T=288.0)
 save("stride_jacobian", jac, ln_tau)
 release()
+scatter_family()
+refusal_calls()
 ctx.close()
-print("dumped to %s: %d files, %d values, %d of them finite and not zero" % (out, *tally))
+print("dumped to %s: %d files, %d values, %d of them finite and not zero (%.2f %%)" % (out, *tally, 100.0 * tally[2] / tally[1]))

@@ -223,7 +223,7 @@ def test_scatter_flux_kernels_in_the_resource_report():
     for n, f in mine.items():
         print(n, f["VGPRs"], f["Occupancy [waves/SIMD]"])
         assert f.get("ScratchSize [bytes/lane]") == 0 and f.get("VGPRs Spill") == 0 and f.get("SGPRs Spill") == 0, (n, f)
-    # what launch_scatter_flux_pass uses: the downward kernel for the layer and the linear source, one upward kernel
+    # what launch_scatter_pass uses (K5m): the downward kernel for the layer and the linear source, one upward kernel
     down = sorted(re.search(r"scatter_flux_down_kernelILb(\d)EE", n).group(1) for n in mine if "down" in n)
     assert down == ["0", "1"] and len(mine) == 3 and sum("scatter_flux_up_kernel" in n for n in mine) == 1, sorted(mine)
 

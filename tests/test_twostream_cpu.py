@@ -193,7 +193,7 @@ def test_twostream_kernels_in_the_resource_report():
         m = re.search(r"twostream_down_kernelILi(\d+)EE", n)
         if m:
             down[int(m.group(1))] = f
-    # what launch_twostream_pass uses: one downward instantiation per beam count 1 .. 8, one upward kernel
+    # what launch_scatter_pass uses (K5l): one downward instantiation per beam count 1 .. 8, one upward kernel
     assert sorted(down) == list(range(1, 9)) and len(mine) == 9, sorted(mine)
 
 
