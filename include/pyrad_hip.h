@@ -128,8 +128,8 @@ int lbl_device_info(lbl_ctx* ctx, char* name, int name_len, int* n_cu, int64_t* 
  *                            records, every pair evaluated directly |
  *                            5 (default) = 3 with the fp64-exact far-field series for Lorentz lines
  *                            more than 4 half-spans away from a span of 64*R points.
- *                            (1, 2 and 4 - superseded comparison kernels - exist in diagnostic builds of the
- *                            library only, make EXTRA=-DLBL_DIAG; the production library answers LBL_ERR_BAD_ARG)
+ *                            (1, 2 and 4 - superseded comparison kernels - were measured and removed from every
+ *                            build, docs/history/: LBL_ERR_BAD_ARG)
  *   "accum_points_per_lane"  0 (auto) | 1 | 2 | 4 | 8
  *   "accum_line_split"       0 (auto) | 1 | 2 | 4 | 8 waves of a workgroup share one span of points
  *                            and split its lines (variants 3 and 5)
@@ -144,7 +144,8 @@ int lbl_device_info(lbl_ctx* ctx, char* name, int name_len, int* n_cu, int64_t* 
  *                            100-2500 cm^-1 cell at the same kernel time
  *   "accum_tile_order"       positional order only: 1 (default) natural | 0 one contiguous run of
  *                            tiles per XCD | 2 golden-ratio stride
- *   "accum_blocks_per_cu"    variant 4 (diagnostic builds) only: resident workgroups per CU, 0 = ask the runtime
+ *   "accum_blocks_per_cu"    0 .. 8, checked and without effect: it sized the launch of the retired variant 4, and the
+ *                            key stays for callers that still set it (bench.py --blocks-per-cu)
  *   "accum_skew"             1 (default) line lists whose window has no far line (narrower than 640 points) go
  *                            through the skewed-range kernel when they fill the chip | 0 the span kernel
  *                            (all-direct instantiation) | 2 EVERY job through the skewed-range kernel (parity tests)

@@ -48,9 +48,7 @@ struct lbl_ctx {
     DeviceArena cold;       // ColdRec per line
     DeviceArena cidx;       // int32 per line
     DeviceArena work;       // work grids that need a regrid
-    DeviceArena jobs;       // PrepJob[] + AccumJob[] + regime counters (3 x u64 per job)
     DeviceArena counts;     // per-block regime counts of the last batch
-    DeviceArena bal;        // balanced variant: span table, counts, prefix, slab
     DeviceArena red;        // band-integral partials + result; lbl_column_flux_dev's partials
     DeviceArena zeros;      // an array of zeros: the cross section of a column layer without line lists
     size_t zeros_set = 0;
@@ -68,17 +66,14 @@ struct lbl_ctx {
     int last_blocks_per_job = 0;
     std::vector<int> last_list_blocks;   // blocks of 256 (lines, or merged positions of its job) each list of the last batch was counted in
     // tuning knobs (lbl_set_option)
-    int accum_variant = 5;   // 0: IEEE divide + exp per pair; 1: running fraction; 2: + Gaussian recurrence
-                             // (0-2 fetch records through the scalar cache); 3: 2 with wave-private LDS
-                             // staging (every pair evaluated directly); 4: 3 with the balanced single-round
-                             // partition of (span, line) pairs (measured: same main-kernel time as 3 plus
-                             // ~20 us of helper kernels); 5 (default): 3 with the far-field series for
-                             // Lorentz lines more than 4 half-spans from a span
+    int accum_variant = 5;   // 0: IEEE divide + exp per pair, records through the scalar cache (the literal form, for
+                             // cross-checks); 3: records through wave-private LDS staging, every pair evaluated
+                             // directly; 5 (default): 3 with the far-field series for Lorentz lines more than 4
+                             // half-spans from a span.  (1, 2 and 4 were measured, superseded and removed: docs/history/)
     int accum_R = 0;         // points per lane, 0 = choose per launch
     int accum_LS = 0;        // waves sharing one span of points (line split), 0 = choose per launch
     int gauss_run = 0;       // points per lane of a Gaussian run in the far-field kernel's production shape: 0 = by the launch's wave count, 16, 32
     int reach_skip = 1;      // the far loop skips the Gaussian-reach test of chunks beyond the largest cut-off of the span's record blocks (0: never, for A/B)
-    int bal_workers[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // resident wavefronts of the balanced kernel per R (cached)
     // schedule cache: (job, tile) lists sorted longest first, per launch group
     struct Schedule {
         std::vector<uint64_t> key; int2* d_list; int total; int32_t* d_tabs; std::vector<size_t> tab_off;
@@ -374,6 +369,22 @@ static void shard_range(const lbl_grid& g, long long* first, long long* count) {
     else { *first = 0; *count = g.n_work; }
 }
 
+// a job's shard as the accumulate launches see it: workgroup tiles of tile_pts points, spans of 64 R points
+struct ShardShape { long long first, count, tiles, spans; };
+static ShardShape shard_shape(const lbl_grid& g, long long tile_pts, int R) {
+    ShardShape s;
+    shard_range(g, &s.first, &s.count);
+    s.tiles = (s.count + tile_pts - 1) / tile_pts;
+    s.spans = (s.count + 64LL * R - 1) / (64LL * R);
+    return s;
+}
+static long long shard_points(const lbl_grid& g) { long long f, c; shard_range(g, &f, &c); return c; }
+
+// H: a line's wing support in points (AccumJob.H)
+static long long half_window(const lbl_grid& g) { return std::max<long long>(g.window - 2, 0); }
+
+static int cu_count(const lbl_ctx* ctx) { return ctx->n_cu > 0 ? ctx->n_cu : 256; }   // (256: the device did not say)
+
 static bool needs_regrid(const lbl_grid& g) {
     return !(g.resolution == g.base_resolution && g.n_work == g.n_base);
 }
@@ -455,7 +466,7 @@ extern "C" int lbl_ctx_destroy(lbl_ctx* ctx) try {
     for (auto& sc : ctx->schedules) if (sc->d_block) (void)hipFree(sc->d_block);
     for (auto& e : ctx->desc_cache) if (e.dptr) (void)hipFree(e.dptr);
     for (auto& e : ctx->arg_cache) if (e.dptr) (void)hipFree(e.dptr);
-    DeviceArena* arenas[] = {&ctx->recs, &ctx->cold, &ctx->cidx, &ctx->work, &ctx->jobs, &ctx->counts, &ctx->bal, &ctx->red, &ctx->zeros, &ctx->sched, &ctx->merge_tmp, &ctx->ktmp, &ctx->voigt};
+    DeviceArena* arenas[] = {&ctx->recs, &ctx->cold, &ctx->cidx, &ctx->work, &ctx->counts, &ctx->red, &ctx->zeros, &ctx->sched, &ctx->merge_tmp, &ctx->ktmp, &ctx->voigt};
     for (DeviceArena* a : arenas) if (a->ptr) (void)hipFree(a->ptr);
     if (ctx->host_stage) (void)hipHostFree(ctx->host_stage);
     for (int h = 0; h < 2; ++h) if (ctx->stage_ev[h]) (void)hipEventDestroy(ctx->stage_ev[h]);
@@ -552,14 +563,13 @@ void comm_prof_end(lbl_ctx* ctx, void* start) { prof_end(ctx, PROF_GATHER, (hipE
 }  // namespace lbl
 
 // Tuning knobs for benchmarking and A/B parity runs (not part of the reference surface):
-//   "accum_variant" 0 | 1 | 2,  "accum_points_per_lane" 0 (auto) | 1 | 2 | 4 | 8
+//   "accum_variant" 0 | 3 | 5,  "accum_points_per_lane" 0 (auto) | 1 | 2 | 4 | 8,  ... (the list is in include/pyrad_hip.h)
 // Every option decides which kernels, launch shapes or arithmetic the batches enqueued afterwards use; a graph captured
 // before (lbl_capture_end) would go on replaying the old ones.  A change of any option therefore bumps the context's epoch:
 // lbl_graph_launch reports the graph stale (LBL_ERR_STATE) and the caller captures again (engine.StepGraph does by itself).
 static uint64_t option_state(const lbl_ctx* c) {
     const long long v[] = {c->accum_variant, c->accum_R, c->accum_LS, c->gauss_run, c->reach_skip, c->lpt, c->tile_order, c->skew, c->skew_R, c->skew_LS, c->xcd_chunks, c->xcd_pack, c->xcd_tol, c->far_min_H,
-                           c->ablate, c->accuracy, c->sweep_ieee, c->sched_build, c->no_fuse ? 1 : 0,
-                           c->bal_workers[1], c->bal_workers[2], c->bal_workers[4], c->bal_workers[8]};
+                           c->ablate, c->accuracy, c->sweep_ieee, c->sched_build, c->no_fuse ? 1 : 0};
     uint64_t h = 1469598103934665603ull;
     for (long long x : v) { h ^= (uint64_t)x; h *= 1099511628211ull; }
     return h;
@@ -576,12 +586,8 @@ extern "C" int lbl_set_option(lbl_ctx* ctx, const char* key, int value) try {
 
 static int set_option_value(lbl_ctx* ctx, const char* key, int value) {
     if (!strcmp(key, "accum_variant")) {
-#ifdef LBL_DIAG
-        if (value < 0 || value > 5) return fail(ctx, LBL_ERR_BAD_ARG, "accum_variant must be 0..5");
-#else
         if (!(value == 0 || value == 3 || value == 5))
-            return fail(ctx, LBL_ERR_BAD_ARG, "accum_variant must be 0, 3 or 5 (1, 2 and 4 are superseded comparison kernels: diagnostic builds only)");
-#endif
+            return fail(ctx, LBL_ERR_BAD_ARG, "accum_variant must be 0, 3 or 5 (1, 2 and 4 are retired: superseded comparison kernels, removed from every build)");
         ctx->accum_variant = value;
     } else if (!strcmp(key, "accum_points_per_lane")) {
         if (!(value == 0 || value == 1 || value == 2 || value == 4 || value == 8))
@@ -591,8 +597,8 @@ static int set_option_value(lbl_ctx* ctx, const char* key, int value) {
         if (value < 0 || value > 4) return fail(ctx, LBL_ERR_BAD_ARG, "accum_longest_first must be 0..4");
         ctx->lpt = value;
     } else if (!strcmp(key, "accum_blocks_per_cu")) {
+        // (sized the retired variant 4's launch; the key stays, checked and without effect, for callers that still set it)
         if (value < 0 || value > 8) return fail(ctx, LBL_ERR_BAD_ARG, "accum_blocks_per_cu must be 0 (auto) .. 8");
-        for (int r = 0; r < 9; ++r) ctx->bal_workers[r] = value ? (ctx->n_cu > 0 ? ctx->n_cu : 256) * value * 4 : 0;
     } else if (!strcmp(key, "accum_tile_order")) {
         if (value < 0 || value > 2) return fail(ctx, LBL_ERR_BAD_ARG, "accum_tile_order must be 0, 1 or 2");
         ctx->tile_order = value;
@@ -874,10 +880,10 @@ extern "C" int lbl_lines_count(const lbl_lines* lines, int64_t* n) try {
 //   LS waves sharing one span and splitting its lines: 4 when a span sees >= 1024 lines,
 //      2 from 256 (the four waves of a workgroup then finish together and workgroups are
 //      short, which balances the clustered line density), else 1.
-// The scalar-cache variants (0-2) keep their original rule: about 3 waves per SIMD.
+// The scalar-cache variant (0) keeps its original rule: about 3 waves per SIMD.
 static void choose_shape(const lbl_ctx* ctx, int variant, long long total_points, long long total_lines, long long min_H,
                          int* R_out, int* LS_out) {
-    const long long cus = ctx->n_cu > 0 ? ctx->n_cu : 256;
+    const long long cus = cu_count(ctx);
     const bool lds = variant >= 3;
     int R = ctx->accum_R, LS = lds ? ctx->accum_LS : 1;
     auto lines_per_span = [&](int r) {
@@ -925,9 +931,7 @@ static void choose_shape(const lbl_ctx* ctx, int variant, long long total_points
         return;
     }
     if (!R) {
-        if (variant == 4) {
-            R = 4;                       // work is split by lines, not spans: no reason to shrink R on small grids
-        } else if (lds) {
+        if (lds) {
             R = 4;
             // positional order only: finer spans shorten the tail on small grids; the longest-first
             // schedule removes that tail and then the lower instruction count of R = 4 wins
@@ -965,42 +969,60 @@ static void choose_shape(const lbl_ctx* ctx, int variant, long long total_points
 #ifndef LBL_COST_GAUSS
 #define LBL_COST_GAUSS 15.0      // wave-instructions a near line's Gaussian passes add per span (0.6 passes of ~25; 29 before the 16-point runs)
 #endif
-// list_first (merged layer jobs, else NULL): job j accumulates the line lists [list_first[j], list_first[j + 1]) of `lines`
-// as ONE record array; without it job j is line list j.
-static lbl_ctx::Schedule* group_schedule(lbl_ctx* ctx, int variant, const std::vector<int>& jobs_in_group,
-                                         lbl_lines* const* lines, const lbl_grid* grid, int R, int LS, long long tile_pts,
-                                         const int* list_first = nullptr) {
-    std::vector<uint64_t> key;
-    const bool far_field = variant == 5;
+// Which line lists of `lines` / `iso` a job accumulates.  first == NULL: job j is line list j.  Else (merged layer jobs:
+// lbl_layer_merged_step_dev, lbl_layers_merged_accumulate_dev) job j takes the lists [first[j], first[j + 1]) as ONE record array.
+struct JobLists {
+    const int* first = nullptr;          // n_jobs + 1 offsets into lines / iso, or NULL
+    int begin(int j) const { return first ? first[j] : j; }
+    int end(int j) const { return first ? first[j + 1] : j + 1; }
+    int count(int j) const { return end(j) - begin(j); }
+};
+
+// What a launch group asks of the schedule cache, and what its key and both builds derive from that
+struct ScheduleQuery {
+    int variant;                         // 3 or 5 (the skewed-range kernel asks as 3)
+    const std::vector<int>& jobs;        // the group's jobs in launch order
+    lbl_lines* const* lines; const lbl_grid* grid; JobLists lists;
+    int R, LS;
+    long long tile_pts;
+    // filled by schedule_lookup
+    bool far_field = false, merged = false;      // merged: any job of the group with several line lists
     int far_half_spans = 0;
     double far_cost = 1.0;
-    if (far_field) accumulate_far_field_params(R, &far_half_spans, &far_cost, ctx->accuracy);      // (the span tables hold the far bounds)
-    auto l0 = [&](int j) { return list_first ? list_first[j] : j; };
-    auto l1 = [&](int j) { return list_first ? list_first[j + 1] : j + 1; };
-    bool merged = false;                       // any job of the group with several line lists
-    for (int j : jobs_in_group) merged = merged || l1(j) - l0(j) > 1;
+    int build_bits = 0, lpt_bits = 0, xcd_chunks = 0, sr_chunks = 0;
+    std::vector<uint64_t> key;
+};
+
+// The cache key of the query, and the cached schedule that carries it (NULL: none)
+static lbl_ctx::Schedule* schedule_lookup(lbl_ctx* ctx, ScheduleQuery& q) {
+    q.far_field = q.variant == 5;
+    if (q.far_field) accumulate_far_field_params(q.R, &q.far_half_spans, &q.far_cost, ctx->accuracy);      // (the span tables hold the far bounds)
+    for (int j : q.jobs) q.merged = q.merged || q.lists.count(j) > 1;
     // (a merged group's tables and merged positions only come from the device build, whatever the options say)
-    const int build_bits = merged ? 1 : ctx->sched_build, lpt_bits = merged ? 4 : ctx->lpt;
+    q.build_bits = q.merged ? 1 : ctx->sched_build;
+    q.lpt_bits = q.merged ? 4 : ctx->lpt;
     // XCD-partitioned order: contiguous chunks of the tile sequence per XCD.  Every chunk drags the line halo of its ends into
     // its XCD's L2, so few chunks mean little traffic, and many chunks even out what the cost model misjudges by spectral
     // region: about 29 workgroups per chunk, between 10 and 32 chunks per XCD (round 2 measured 32 against 8 and 1 on the
     // per-list 100-2500 cm^-1 cell, 7,031 workgroups; round 5 on its merged job, 2,344 workgroups: 10 chunks fetch 34 MB
     // where 32 fetch 55, same kernel time; a merged shard of 8, 1,172 workgroups: 10.7 MB against 16.5, same time; 6: +8 %)
     long long n_wg = 0;
-    for (int j : jobs_in_group) { long long sf, sc; shard_range(grid[j], &sf, &sc); n_wg += (sc + tile_pts - 1) / tile_pts; }
-    const int xcd_chunks = ctx->xcd_chunks > 0 ? ctx->xcd_chunks : (int)std::min<long long>(32, std::max<long long>(10, (n_wg + 116) / 232));
+    for (int j : q.jobs) n_wg += shard_shape(q.grid[j], q.tile_pts, q.R).tiles;
+    q.xcd_chunks = ctx->xcd_chunks > 0 ? ctx->xcd_chunks : (int)std::min<long long>(32, std::max<long long>(10, (n_wg + 116) / 232));
     // (a launch of one round: 1..16 runs per XCD, default 1 - see launch_schedule_build)
-    const int sr_chunks = ctx->xcd_chunks > 0 ? std::min(ctx->xcd_chunks, 16) : 1;
-    key.push_back((uint64_t)(ctx->xcd_tol + 1) << 59 | (uint64_t)sr_chunks << 52 | (uint64_t)ctx->xcd_pack << 48 | (uint64_t)xcd_chunks << 40 | (uint64_t)R << 32 | (uint64_t)far_half_spans << 16 | (uint64_t)LS << 8 | (uint64_t)build_bits << 4 | (uint64_t)lpt_bits << 1 | (uint64_t)far_field);
-    for (int j : jobs_in_group) {
+    q.sr_chunks = ctx->xcd_chunks > 0 ? std::min(ctx->xcd_chunks, 16) : 1;
+    std::vector<uint64_t>& key = q.key;
+    key.push_back((uint64_t)(ctx->xcd_tol + 1) << 59 | (uint64_t)q.sr_chunks << 52 | (uint64_t)ctx->xcd_pack << 48 | (uint64_t)q.xcd_chunks << 40 | (uint64_t)q.R << 32 | (uint64_t)q.far_half_spans << 16 | (uint64_t)q.LS << 8 | (uint64_t)q.build_bits << 4 | (uint64_t)q.lpt_bits << 1 | (uint64_t)q.far_field);
+    for (int j : q.jobs) {
+        const lbl_grid& g = q.grid[j];
         long long sf, sc;
-        shard_range(grid[j], &sf, &sc);
+        shard_range(g, &sf, &sc);
         uint64_t bits_a, bits_b;
-        memcpy(&bits_a, &grid[j].range_min, 8); memcpy(&bits_b, &grid[j].resolution, 8);
-        if (list_first) key.push_back(0xFFFFFFFF00000000ull | (uint64_t)(l1(j) - l0(j)));      // (a job of k lists is not k jobs)
-        for (int l = l0(j); l < l1(j); ++l) { key.push_back(lines[l]->serial); key.push_back((uint64_t)lines[l]->n); }
+        memcpy(&bits_a, &g.range_min, 8); memcpy(&bits_b, &g.resolution, 8);
+        if (q.lists.first) key.push_back(0xFFFFFFFF00000000ull | (uint64_t)q.lists.count(j));      // (a job of k lists is not k jobs)
+        for (int l = q.lists.begin(j); l < q.lists.end(j); ++l) { key.push_back(q.lines[l]->serial); key.push_back((uint64_t)q.lines[l]->n); }
         key.push_back(bits_a); key.push_back(bits_b);
-        key.push_back((uint64_t)sf); key.push_back((uint64_t)sc); key.push_back((uint64_t)grid[j].window);
+        key.push_back((uint64_t)sf); key.push_back((uint64_t)sc); key.push_back((uint64_t)g.window);
     }
     for (size_t i = 0; i < ctx->schedules.size(); ++i)
         if (ctx->schedules[i]->key == key) {
@@ -1008,96 +1030,106 @@ static lbl_ctx::Schedule* group_schedule(lbl_ctx* ctx, int variant, const std::v
             std::rotate(ctx->schedules.begin() + i, ctx->schedules.begin() + i + 1, ctx->schedules.end());
             return ctx->schedules.back().get();
         }
-    if (ctx->capturing) { (void)capture_refuses(ctx, "building a dispatch schedule"); return nullptr; }
-    TraceScope tr("group_schedule", (long long)jobs_in_group.size());
-    auto evict_oldest = [&]() {
-        // (64 entries: a 30-layer atmosphere used through per-layer getters holds one schedule per layer, and every eviction is a
-        // stream sync, a hipFree and a stale graph - advisor, round 5; an entry is a few MB: dispatch list, span table, merged order)
-        if (ctx->schedules.size() >= 64) {                    // drop the least recently used entry
-            ctx->epoch++;
-            (void)hipStreamSynchronize(ctx->stream);
-            if (ctx->schedules.front()->d_block) (void)hipFree(ctx->schedules.front()->d_block);
-            ctx->schedules.erase(ctx->schedules.begin());
-        }
-    };
-    auto one_block = [&](size_t n_items, size_t n_tab_ints, int2** d_list, int32_t** d_tabs, size_t n_src = 0,
-                         int32_t** d_src = nullptr) -> void* {
-        const size_t list_bytes = (std::max<size_t>(n_items, 1) * sizeof(int2) + 255) & ~(size_t)255;
-        const size_t tab_bytes = (std::max<size_t>(n_tab_ints, 8) * sizeof(int32_t) + 255) & ~(size_t)255;
-        void* blk = nullptr;
-        TraceScope tr("schedule block alloc", (long long)(list_bytes + tab_bytes + n_src * sizeof(int32_t)));
-        if (hipMalloc(&blk, list_bytes + tab_bytes + n_src * sizeof(int32_t)) != hipSuccess) return nullptr;
-        *d_list = (int2*)blk;
-        *d_tabs = (int32_t*)((char*)blk + list_bytes);
-        if (d_src) *d_src = n_src ? (int32_t*)((char*)blk + list_bytes + tab_bytes) : nullptr;
-        return blk;
-    };
-    {
-        // Device build: only the sizes are worked out here; the tables and the order are produced in stream by the first
-        // batch that uses the schedule (enqueue_accumulate, after its line prep has written the centre indices).
-        long long n_items = 0, n_spans_all = 0;
-        for (int j : jobs_in_group) {
-            long long sf, sc;
-            shard_range(grid[j], &sf, &sc);
-            n_items += (sc + tile_pts - 1) / tile_pts;
-            n_spans_all += (sc + 64LL * R - 1) / (64LL * R);
-        }
-        const int n_cu_i = ctx->n_cu > 0 ? ctx->n_cu : 256;
-        const bool device_ok = n_items > 0 && n_spans_all < (1LL << 27) && sched_device_supported((int)n_items, n_cu_i);
-        if (merged && !device_ok) { ctx->sched_refused = true; return nullptr; }
-        if (build_bits == 1 && lpt_bits == 4 && device_ok) {
-            std::unique_ptr<lbl_ctx::Schedule> S(new lbl_ctx::Schedule());
-            S->key = key;
-            S->R = R; S->spans_per_tile = (int)(tile_pts / (64LL * R));
-            S->far_reach = far_field ? (long long)far_half_spans * 32 * R : 0;
-            S->xcd_chunks = xcd_chunks;
-            S->cost_near = 5.0 * R + LBL_COST_GAUSS; S->cost_edge = 8.0 * R; S->cost_far = far_cost * 5.0 * R; S->cost_fixed = 600.0;
-            int32_t span_run = 0, tile_run = 0;
-            for (int j : jobs_in_group) {
-                long long sf, sc;
-                shard_range(grid[j], &sf, &sc);
-                S->tab_off.push_back((size_t)span_run * 8);
-                S->span_first.push_back(span_run); S->tile_first.push_back(tile_run);
-                span_run += (int32_t)((sc + 64LL * R - 1) / (64LL * R));
-                tile_run += (int32_t)((sc + tile_pts - 1) / tile_pts);
-            }
-            S->total_spans = span_run; S->total = tile_run;
-            S->xcd_pack = ctx->xcd_pack; S->sr_chunks = sr_chunks; S->xcd_tol = ctx->xcd_tol;
-            S->launch_total = sched_launch_items(tile_run, n_cu_i, S->xcd_pack != 0);
-            size_t n_src = 0;
-            for (int j : jobs_in_group) {
-                size_t n = 0;
-                for (int l = l0(j); l < l1(j); ++l) n += (size_t)lines[l]->n;
-                S->src_off.push_back(l1(j) - l0(j) > 1 ? n_src : SIZE_MAX);
-                if (l1(j) - l0(j) > 1) n_src += n;
-            }
-            S->d_block = one_block((size_t)S->launch_total, (size_t)span_run * 8, &S->d_list, &S->d_tabs, n_src, &S->d_src);
-            if (!S->d_block) return nullptr;
-            S->pending = true;
-            S->merge_pending = n_src > 0;
-            evict_oldest();
-            ctx->schedules.push_back(std::move(S));
-            return ctx->schedules.back().get();
-        }
+    return nullptr;
+}
+
+// Room for one more entry in the schedule cache
+static void evict_oldest(lbl_ctx* ctx) {
+    // (64 entries: a 30-layer atmosphere used through per-layer getters holds one schedule per layer, and every eviction is a
+    // stream sync, a hipFree and a stale graph - advisor, round 5; an entry is a few MB: dispatch list, span table, merged order)
+    if (ctx->schedules.size() >= 64) {                    // drop the least recently used entry
+        ctx->epoch++;
+        (void)hipStreamSynchronize(ctx->stream);
+        if (ctx->schedules.front()->d_block) (void)hipFree(ctx->schedules.front()->d_block);
+        ctx->schedules.erase(ctx->schedules.begin());
     }
+}
+
+// The one allocation a schedule's dispatch list, span table and merged-order map live in (NULL: out of memory)
+static void* one_block(size_t n_items, size_t n_tab_ints, int2** d_list, int32_t** d_tabs, size_t n_src = 0, int32_t** d_src = nullptr) {
+    const size_t list_bytes = (std::max<size_t>(n_items, 1) * sizeof(int2) + 255) & ~(size_t)255;
+    const size_t tab_bytes = (std::max<size_t>(n_tab_ints, 8) * sizeof(int32_t) + 255) & ~(size_t)255;
+    void* blk = nullptr;
+    TraceScope tr("schedule block alloc", (long long)(list_bytes + tab_bytes + n_src * sizeof(int32_t)));
+    if (hipMalloc(&blk, list_bytes + tab_bytes + n_src * sizeof(int32_t)) != hipSuccess) return nullptr;
+    *d_list = (int2*)blk;
+    *d_tabs = (int32_t*)((char*)blk + list_bytes);
+    if (d_src) *d_src = n_src ? (int32_t*)((char*)blk + list_bytes + tab_bytes) : nullptr;
+    return blk;
+}
+
+// Device build: only the sizes are worked out here; the tables and the order are produced in stream by the first
+// batch that uses the schedule (enqueue_accumulate, after its line prep has written the centre indices).
+// *host_build: the device build does not serve this query (options, or a launch it does not cover) and nothing was done.
+static lbl_ctx::Schedule* schedule_plan_device(lbl_ctx* ctx, const ScheduleQuery& q, bool* host_build) {
+    *host_build = false;
+    long long n_items = 0, n_spans_all = 0;
+    for (int j : q.jobs) {
+        const ShardShape s = shard_shape(q.grid[j], q.tile_pts, q.R);
+        n_items += s.tiles;
+        n_spans_all += s.spans;
+    }
+    const int n_cu = cu_count(ctx);
+    const bool device_ok = n_items > 0 && n_spans_all < (1LL << 27) && sched_device_supported((int)n_items, n_cu);
+    if (q.merged && !device_ok) { ctx->sched_refused = true; return nullptr; }
+    if (!(q.build_bits == 1 && q.lpt_bits == 4 && device_ok)) { *host_build = true; return nullptr; }
+    const int R = q.R;
+    std::unique_ptr<lbl_ctx::Schedule> S(new lbl_ctx::Schedule());
+    S->key = q.key;
+    S->R = R; S->spans_per_tile = (int)(q.tile_pts / (64LL * R));
+    S->far_reach = q.far_field ? (long long)q.far_half_spans * 32 * R : 0;
+    S->xcd_chunks = q.xcd_chunks;
+    S->cost_near = 5.0 * R + LBL_COST_GAUSS; S->cost_edge = 8.0 * R; S->cost_far = q.far_cost * 5.0 * R; S->cost_fixed = 600.0;
+    int32_t span_run = 0, tile_run = 0;
+    for (int j : q.jobs) {
+        const ShardShape s = shard_shape(q.grid[j], q.tile_pts, R);
+        S->tab_off.push_back((size_t)span_run * 8);
+        S->span_first.push_back(span_run); S->tile_first.push_back(tile_run);
+        span_run += (int32_t)s.spans; tile_run += (int32_t)s.tiles;
+    }
+    S->total_spans = span_run; S->total = tile_run;
+    S->xcd_pack = ctx->xcd_pack; S->sr_chunks = q.sr_chunks; S->xcd_tol = ctx->xcd_tol;
+    S->launch_total = sched_launch_items(tile_run, n_cu, S->xcd_pack != 0);
+    size_t n_src = 0;
+    for (int j : q.jobs) {
+        size_t n = 0;
+        for (int l = q.lists.begin(j); l < q.lists.end(j); ++l) n += (size_t)q.lines[l]->n;
+        S->src_off.push_back(q.lists.count(j) > 1 ? n_src : SIZE_MAX);
+        if (q.lists.count(j) > 1) n_src += n;
+    }
+    S->d_block = one_block((size_t)S->launch_total, (size_t)span_run * 8, &S->d_list, &S->d_tabs, n_src, &S->d_src);
+    if (!S->d_block) return nullptr;
+    S->pending = true;
+    S->merge_pending = n_src > 0;
+    evict_oldest(ctx);
+    ctx->schedules.push_back(std::move(S));
+    return ctx->schedules.back().get();
+}
+
+// Host build: span tables, tile costs and the dispatch order from the host's own evaluation of the centre indices, uploaded
+// at once (one list per job on this path: merged groups took the device build)
+static lbl_ctx::Schedule* schedule_build_host(lbl_ctx* ctx, const ScheduleQuery& q) {
     struct Item { int count, job, tile; };
     std::vector<Item> items;
     std::vector<long long> idx;
     std::vector<int32_t> tabs;
     std::vector<size_t> tab_off;
+    const int R = q.R;
+    const bool far_field = q.far_field;
     const long long span = 64LL * R;
-    const long long reach = (long long)far_half_spans * 32 * R;
-    for (size_t k = 0; k < jobs_in_group.size(); ++k) {
-        const int j = jobs_in_group[k];
-        const lbl_lines* L = lines[l0(j)];           // (one list per job on this path: merged groups took the device build)
+    const long long reach = (long long)q.far_half_spans * 32 * R;
+    for (size_t k = 0; k < q.jobs.size(); ++k) {
+        const int j = q.jobs[k];
+        const lbl_grid& grid = q.grid[j];
+        const lbl_lines* L = q.lines[q.lists.begin(j)];
         idx.resize((size_t)L->n);
-        for (int64_t i = 0; i < L->n; ++i) idx[i] = (long long)((L->host_nu[i] - grid[j].range_min) / grid[j].resolution);
-        long long sf, sc;
-        shard_range(grid[j], &sf, &sc);
-        const long long H = std::max<long long>(grid[j].window - 2, 0);
+        for (int64_t i = 0; i < L->n; ++i) idx[i] = (long long)((L->host_nu[i] - grid.range_min) / grid.resolution);
+        const ShardShape sh = shard_shape(grid, q.tile_pts, R);
+        const long long sf = sh.first, sc = sh.count;
+        const long long H = half_window(grid);
         auto below = [&](long long v) { return (int32_t)(std::lower_bound(idx.begin(), idx.end(), v) - idx.begin()); };
         // span table (same arithmetic as wave_line_ranges_far)
-        const long long n_spans = (sc + span - 1) / span;
+        const long long n_spans = sh.spans;
         tab_off.push_back(tabs.size());
         tabs.resize(tabs.size() + (size_t)n_spans * 8, 0);
         int32_t* T = tabs.data() + tab_off.back();
@@ -1119,23 +1151,23 @@ static lbl_ctx::Schedule* group_schedule(lbl_ctx* ctx, int variant, const std::v
             e[0] = iA; e[1] = iB; e[2] = iC; e[3] = iD; e[4] = iF1; e[5] = iF2; e[6] = iN1; e[7] = iN2;
         }
         // cost of every tile (a workgroup's points): lines it walks, far lines at their series price
-        const long long n_tiles = (sc + tile_pts - 1) / tile_pts;
-        const long long spans_per_tile = tile_pts / span;
+        const long long n_tiles = sh.tiles;
+        const long long spans_per_tile = q.tile_pts / span;
         for (long long t = 0; t < n_tiles; ++t) {
             double cost = 0.0;
-            for (long long q = t * spans_per_tile; q < std::min((t + 1) * spans_per_tile, n_spans); ++q) {
+            for (long long s = t * spans_per_tile; s < std::min((t + 1) * spans_per_tile, n_spans); ++s) {
                 // wave-instructions of one span: near line 5R + ~0.6 Gaussian passes (LBL_COST_GAUSS), masked edge
                 // line 8R, series line ~1.6, fixed part ~600 (variants without the series: all direct)
-                const int32_t* e = T + q * 8;
+                const int32_t* e = T + s * 8;
                 const double n_far = (double)((e[4] - e[1]) + (e[2] - e[5]));
                 const double n_edge = (double)((e[1] - e[0]) + (e[3] - e[2]));
                 const double n_near = (double)(e[5] - e[4]);
-                cost += n_near * (5.0 * R + LBL_COST_GAUSS) + n_edge * 8.0 * R + n_far * far_cost * 5.0 * R + 600.0;
+                cost += n_near * (5.0 * R + LBL_COST_GAUSS) + n_edge * 8.0 * R + n_far * q.far_cost * 5.0 * R + 600.0;
             }
             items.push_back({(int)(cost + 0.5), (int)k, (int)t});
         }
     }
-    const size_t n_cu = (size_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
+    const size_t n_cu = (size_t)cu_count(ctx);
     bool xcd_done = false;
     if (ctx->lpt == 4 && items.size() > 4 * n_cu) {
         // XCD-partitioned longest-first (launches of several rounds): workgroup i is dispatched to XCD
@@ -1148,7 +1180,7 @@ static lbl_ctx::Schedule* group_schedule(lbl_ctx* ctx, int variant, const std::v
         // the whole spectrum - a bias of the cost estimate in one spectral region, e.g. the cheaper
         // pure-Lorentz lines at low wavenumbers, then loads all XCDs alike.  Measured on the 100-2500 cm^-1
         // cell: 1 chunk per XCD +6 % kernel time, 8 chunks +3 %, 32 chunks +-0 with 33 MB fetched instead of 110)
-        const int chunks = X * xcd_chunks;
+        const int chunks = X * q.xcd_chunks;
         double total = 0.0;
         for (const Item& it : items) total += it.count;
         std::vector<std::vector<Item>> part(X);
@@ -1222,12 +1254,26 @@ static lbl_ctx::Schedule* group_schedule(lbl_ctx* ctx, int variant, const std::v
         (void)hipFree(blk);
         return nullptr;
     }
-    evict_oldest();
+    evict_oldest(ctx);
     std::unique_ptr<lbl_ctx::Schedule> S(new lbl_ctx::Schedule());
-    S->key = key; S->d_list = d_list; S->total = (int)host.size(); S->launch_total = S->total; S->d_tabs = d_tabs; S->tab_off = tab_off; S->d_block = blk;
+    S->key = q.key; S->d_list = d_list; S->total = (int)host.size(); S->launch_total = S->total; S->d_tabs = d_tabs; S->tab_off = tab_off; S->d_block = blk;
     S->total_spans = -(int)(tabs.size() / 8);          // (negative: built on the host; lbl_schedule_export)
     ctx->schedules.push_back(std::move(S));
     return ctx->schedules.back().get();
+}
+
+// The cached schedule of a launch group, planned or built if the cache does not hold it.  NULL: refused while capturing
+// (the error is set), refused for a merged group the device build does not cover (ctx->sched_refused), or out of memory.
+static lbl_ctx::Schedule* group_schedule(lbl_ctx* ctx, int variant, const std::vector<int>& jobs_in_group,
+                                         lbl_lines* const* lines, const lbl_grid* grid, int R, int LS, long long tile_pts,
+                                         const JobLists& lists) {
+    ScheduleQuery q{variant, jobs_in_group, lines, grid, lists, R, LS, tile_pts};
+    if (lbl_ctx::Schedule* hit = schedule_lookup(ctx, q)) return hit;
+    if (ctx->capturing) { (void)capture_refuses(ctx, "building a dispatch schedule"); return nullptr; }
+    TraceScope tr("group_schedule", (long long)jobs_in_group.size());
+    bool host_build = false;
+    lbl_ctx::Schedule* S = schedule_plan_device(ctx, q, &host_build);
+    return host_build ? schedule_build_host(ctx, q) : S;
 }
 
 // Merged layer jobs (lbl_layer_merged_step_dev, lbl_layers_merged_accumulate_dev): accumulate job j takes the line lists
@@ -1247,99 +1293,129 @@ static void prep_job_physics(PrepJob& p, const lbl_iso_params& iso, const lbl_gr
 }
 
 struct MergeSpec {
-    const int* first;          // n_jobs + 1 offsets into lines / iso
+    JobLists lists;            // n_jobs + 1 offsets into lines / iso
     const double* weight;      // per line list
     const double* out_scale;   // per job
 };
 
-static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines, const lbl_iso_params* iso,
-                              const lbl_grid* grid, double* const* out_dev, bool prep_only,
-                              const FusedSweep* fuse = nullptr, double fuse_conc = 0.0, const MergeSpec* merge = nullptr) {
-    // fuse != NULL (n_jobs == 1): the layer sweep runs in the output stage of the one job
-    // merge == NULL: job j is line list j; lines / iso hold n_jobs entries.  grid and out_dev are per JOB either way.
-    if (n_jobs <= 0) return LBL_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto l0 = [&](int j) { return merge ? merge->first[j] : j; };
-    auto l1 = [&](int j) { return merge ? merge->first[j + 1] : j + 1; };
-    const int n_lists = l1(n_jobs - 1);
-    if (merge && !(ctx->accum_variant == 3 || ctx->accum_variant == 5))
-        return fail(ctx, LBL_ERR_BAD_ARG, "merged layer jobs run on the LDS accumulate kernels only (accum_variant 3 or 5)");
+// One launch of the accumulate kernels: jobs order[first .. first + count) of the batch, which share a launch shape
+struct AccumGroup {
+    int first, count, R, LS, max_tiles, variant;      // variant 6: the skewed-range kernel
+    int grun;
+    lbl_ctx::Schedule* sched;                         // dispatch order + the line ranges of every span (NULL: positional order, waves search)
+};
+
+// One call of enqueue_accumulate: its arguments, and what its stages (below, in the order they run) hand to each other
+struct AccumBatch {
+    int n_jobs; lbl_lines* const* lines; const lbl_iso_params* iso; const lbl_grid* grid; double* const* out_dev;
+    const FusedSweep* fuse; double fuse_conc; const MergeSpec* merge;
+    JobLists lists;
+    int n_lists = 0;
     // layout of the scratch arenas: the lists of a job are neighbours, so a job's merged record array is one range
-    std::vector<size_t> line_off(n_lists), work_off(n_jobs), job_lines(n_jobs, 0);
-    size_t tot_lines = 0, tot_work = 0;
-    long long min_H = 1LL << 40;
-    int max_lines = 0;
+    std::vector<size_t> line_off, work_off, job_lines;     // per list: first record; per job: first work-grid point, lines
+    size_t tot_lines = 0, tot_work = 0, max_job_lines = 0;
+    int max_lines = 0, n_merged_jobs = 0;
+    int blocks_per_job = 0;
+    size_t prep_bytes = 0;                   // PrepJob[n_lists] | MergedPrep[n_merged_jobs], then AccumJob[n_jobs]
+    unsigned int* d_counts = nullptr;
+    int32_t* d_reach = nullptr;
+    int32_t* job_reach(int j) const { return d_reach + (size_t)lists.begin(j) * std::max(blocks_per_job, 1); }
+    // launch groups
+    int far_half_spans = 0;
+    std::vector<int> job_key;                // per job: 0 the skewed-range kernel, else r_cap * 2 + has_far
+    std::vector<int> order;                  // the jobs, group after group
+    std::vector<AccumGroup> groups;
+    std::vector<const int32_t*> job_src;     // where the group's schedule keeps the merged-order map of a job (NULL: a job of one list)
+    // descriptors: host copies (in ctx->desc_build) and the device block
+    PrepJob* hp = nullptr; MergedPrep* hm = nullptr;
+    AccumJob* ha = nullptr;                  // in launch order: ha[k] is job order[k]
+    char* d_desc = nullptr;
+};
+
+// 1. Check the batch and lay out the scratch arenas and the descriptor block
+static int batch_layout(lbl_ctx* ctx, AccumBatch& B) {
+    const int n_jobs = B.n_jobs;
+    const JobLists& lists = B.lists;
+    B.n_lists = lists.end(n_jobs - 1);
+    if (B.merge && !(ctx->accum_variant == 3 || ctx->accum_variant == 5))
+        return fail(ctx, LBL_ERR_BAD_ARG, "merged layer jobs run on the LDS accumulate kernels only (accum_variant 3 or 5)");
+    B.line_off.resize(B.n_lists); B.work_off.resize(n_jobs); B.job_lines.assign(n_jobs, 0);
     for (int j = 0; j < n_jobs; ++j) {
-        int rc = check_grid(ctx, &grid[j]);
+        int rc = check_grid(ctx, &B.grid[j]);
         if (rc) return rc;
-        for (int l = l0(j); l < l1(j); ++l) {
-            if (!lines[l] || lines[l]->ctx != ctx) return fail(ctx, LBL_ERR_STATE, "line list %d: missing or from another context", l);
-            if (!(iso[l].T > 0) || !(iso[l].P > 0) || !(iso[l].molmass > 0) || !(iso[l].Q_T > 0))
+        for (int l = lists.begin(j); l < lists.end(j); ++l) {
+            const lbl_lines* L = B.lines[l];
+            if (!L || L->ctx != ctx) return fail(ctx, LBL_ERR_STATE, "line list %d: missing or from another context", l);
+            if (!(B.iso[l].T > 0) || !(B.iso[l].P > 0) || !(B.iso[l].molmass > 0) || !(B.iso[l].Q_T > 0))
                 return fail(ctx, LBL_ERR_BAD_ARG, "line list %d: T, P, molmass and Q_T must be > 0", l);
-            line_off[l] = tot_lines;
-            tot_lines += (size_t)lines[l]->n;
-            job_lines[j] += (size_t)lines[l]->n;
-            max_lines = std::max<int>(max_lines, (int)lines[l]->n);
+            B.line_off[l] = B.tot_lines;
+            B.tot_lines += (size_t)L->n;
+            B.job_lines[j] += (size_t)L->n;
+            B.max_lines = std::max<int>(B.max_lines, (int)L->n);
         }
-        if (job_lines[j] > 2000000000ull) return fail(ctx, LBL_ERR_BAD_ARG, "job %d: too many lines for int32 indexing", j);
-        if (l1(j) - l0(j) > 1) {                 // merged-order map: list within the job in 6 bits, line within the list in 26
-            if (l1(j) - l0(j) > kMaxIso) return fail(ctx, LBL_ERR_BAD_ARG, "job %d: at most %d line lists per merged job", j, kMaxIso);
-            for (int l = l0(j); l < l1(j); ++l)
-                if (lines[l]->n >= (1LL << 26)) return fail(ctx, LBL_ERR_BAD_ARG, "line list %d: at most 2^26 - 1 lines per list of a merged job", l);
+        if (B.job_lines[j] > 2000000000ull) return fail(ctx, LBL_ERR_BAD_ARG, "job %d: too many lines for int32 indexing", j);
+        if (lists.count(j) > 1) {                 // merged-order map: list within the job in 6 bits, line within the list in 26
+            if (lists.count(j) > kMaxIso) return fail(ctx, LBL_ERR_BAD_ARG, "job %d: at most %d line lists per merged job", j, kMaxIso);
+            for (int l = lists.begin(j); l < lists.end(j); ++l)
+                if (B.lines[l]->n >= (1LL << 26)) return fail(ctx, LBL_ERR_BAD_ARG, "line list %d: at most 2^26 - 1 lines per list of a merged job", l);
         }
-        work_off[j] = tot_work;
-        if (needs_regrid(grid[j])) tot_work += (size_t)grid[j].n_work;
-        min_H = std::min<long long>(min_H, std::max<long long>(grid[j].window - 2, 0));
+        B.work_off[j] = B.tot_work;
+        if (needs_regrid(B.grid[j])) B.tot_work += (size_t)B.grid[j].n_work;
     }
     int rc;
-    if ((rc = arena_reserve(ctx, ctx->recs, std::max<size_t>(tot_lines, 1) * sizeof(HotRec)))) return rc;
-    if ((rc = arena_reserve(ctx, ctx->cold, std::max<size_t>(tot_lines, 1) * sizeof(ColdRec)))) return rc;
-    if ((rc = arena_reserve(ctx, ctx->cidx, std::max<size_t>(tot_lines, 1) * sizeof(int32_t)))) return rc;
-    if ((rc = arena_reserve(ctx, ctx->work, std::max<size_t>(tot_work, 1) * sizeof(double)))) return rc;
+    if ((rc = arena_reserve(ctx, ctx->recs, std::max<size_t>(B.tot_lines, 1) * sizeof(HotRec)))) return rc;
+    if ((rc = arena_reserve(ctx, ctx->cold, std::max<size_t>(B.tot_lines, 1) * sizeof(ColdRec)))) return rc;
+    if ((rc = arena_reserve(ctx, ctx->cidx, std::max<size_t>(B.tot_lines, 1) * sizeof(int32_t)))) return rc;
+    if ((rc = arena_reserve(ctx, ctx->work, std::max<size_t>(B.tot_work, 1) * sizeof(double)))) return rc;
     // per-block regime counts (3 x u32 per block of 256 lines), summed on the host on demand
     // (a list of a merged job is counted per block of 256 MERGED positions of its job)
-    int n_merged_jobs = 0;
-    size_t max_job_lines = 0;
     for (int j = 0; j < n_jobs; ++j)
-        if (l1(j) - l0(j) > 1) { ++n_merged_jobs; max_job_lines = std::max(max_job_lines, job_lines[j]); }
-    const int blocks_per_job = (int)((std::max<size_t>((size_t)max_lines, max_job_lines) + 255) / 256);
-    const size_t prep_bytes = (((size_t)n_lists * sizeof(PrepJob) + (size_t)n_merged_jobs * sizeof(MergedPrep)) + 15) & ~(size_t)15;
+        if (lists.count(j) > 1) { ++B.n_merged_jobs; B.max_job_lines = std::max(B.max_job_lines, B.job_lines[j]); }
+    B.blocks_per_job = (int)((std::max<size_t>((size_t)B.max_lines, B.max_job_lines) + 255) / 256);
+    B.prep_bytes = (((size_t)B.n_lists * sizeof(PrepJob) + (size_t)B.n_merged_jobs * sizeof(MergedPrep)) + 15) & ~(size_t)15;
     const size_t acc_bytes = (size_t)n_jobs * sizeof(AccumJob);
-    const size_t cnt_bytes = (size_t)n_lists * std::max(blocks_per_job, 1) * 3 * sizeof(unsigned int);
+    const size_t cnt_bytes = (size_t)B.n_lists * std::max(B.blocks_per_job, 1) * 3 * sizeof(unsigned int);
     // behind them: the largest Gaussian cut-off per block of 256 records (one int32 per block; a merged job's array, in
     // merged order, takes the slot of its first list)
-    const size_t reach_bytes = (size_t)n_lists * std::max(blocks_per_job, 1) * sizeof(int32_t);
+    const size_t reach_bytes = (size_t)B.n_lists * std::max(B.blocks_per_job, 1) * sizeof(int32_t);
     if ((rc = arena_reserve(ctx, ctx->counts, cnt_bytes + reach_bytes))) return rc;
+    B.d_counts = (unsigned int*)ctx->counts.ptr;
+    B.d_reach = (int32_t*)((char*)ctx->counts.ptr + cnt_bytes);
     // descriptors are built in pageable host memory first: a batch that repeats (the usual case:
     // same layer, step after step) finds its descriptor block already on the device and skips the copy
-    ctx->desc_build.assign(prep_bytes + acc_bytes, 0);
-    void* stage = ctx->desc_build.data();
-    unsigned int* d_counts = (unsigned int*)ctx->counts.ptr;
-    int32_t* d_reach = (int32_t*)((char*)ctx->counts.ptr + cnt_bytes);
-    auto job_reach = [&](int j) { return d_reach + (size_t)l0(j) * std::max(blocks_per_job, 1); };
+    ctx->desc_build.assign(B.prep_bytes + acc_bytes, 0);
+    char* stage = ctx->desc_build.data();
+    B.hp = (PrepJob*)stage;
+    B.hm = (MergedPrep*)(stage + (size_t)B.n_lists * sizeof(PrepJob));
+    B.ha = (AccumJob*)(stage + B.prep_bytes);
+    return LBL_OK;
+}
 
-    // Jobs of one batch can have very different windows (a column: W = 5000 at the surface,
-    // 50 at 10 mbar).  A wave must not own more points than a line's support is wide, so jobs are
-    // grouped by the largest R their window allows and every group gets its own launch shape.
-    const int r_default = ctx->accum_variant >= 3 ? 4 : 8;       // what choose_shape starts from
-    auto r_cap = [&](int j) {
-        const long long H = std::max<long long>(grid[j].window - 2, 0);
-        int r = r_default;                        // windows that allow more than the default share its group
-        while (r > 1 && 64LL * r > 2 * H + 1) r >>= 1;
-        return ctx->accum_R ? 8 : r;              // a forced R keeps one group
-    };
-    // Far-field kernel: a window narrower than (threshold + 1) half-spans has no far line on any span;
-    // such jobs run the all-direct kernel (same arithmetic there, 60-90 instead of 105-123 VGPRs, so
-    // 5-8 instead of 4 waves per SIMD: narrow-window spans are latency bound).
-    int far_half_spans = 0;
-    { double fc; accumulate_far_field_params(4, &far_half_spans, &fc); }
-    auto has_far = [&](int j) {
-        if (ctx->accum_variant != 5) return 0;
-        const long long H = std::max<long long>(grid[j].window - 2, 0);
-        const long long r = ctx->accum_R ? ctx->accum_R : r_cap(j);
-        if (ctx->skew && H < ctx->far_min_H) return 0;
-        return H >= 32 * r * (far_half_spans + 1) ? 1 : 0;
-    };
+// Jobs of one batch can have very different windows (a column: W = 5000 at the surface,
+// 50 at 10 mbar).  A wave must not own more points than a line's support is wide, so jobs are
+// grouped by the largest R their window allows and every group gets its own launch shape.
+static int r_cap(const lbl_ctx* ctx, const lbl_grid& g) {
+    const long long H = half_window(g);
+    int r = ctx->accum_variant >= 3 ? 4 : 8;  // what choose_shape starts from; windows that allow more than the default share its group
+    while (r > 1 && 64LL * r > 2 * H + 1) r >>= 1;
+    return ctx->accum_R ? 8 : r;              // a forced R keeps one group
+}
+// Far-field kernel: a window narrower than (threshold + 1) half-spans has no far line on any span;
+// such jobs run the all-direct kernel (same arithmetic there, 60-90 instead of 105-123 VGPRs, so
+// 5-8 instead of 4 waves per SIMD: narrow-window spans are latency bound).
+static int has_far(const lbl_ctx* ctx, const lbl_grid& g, int far_half_spans) {
+    if (ctx->accum_variant != 5) return 0;
+    const long long H = half_window(g);
+    const long long r = ctx->accum_R ? ctx->accum_R : r_cap(ctx, g);
+    if (ctx->skew && H < ctx->far_min_H) return 0;
+    return H >= 32 * r * (far_half_spans + 1) ? 1 : 0;
+}
+
+// 2. Launch groups: the jobs sorted by group key, and per group the launch shape and the cached schedule
+static int batch_group(lbl_ctx* ctx, AccumBatch& B) {
+    const int n_jobs = B.n_jobs;
+    const lbl_grid* grid = B.grid;
+    { double fc; accumulate_far_field_params(4, &B.far_half_spans, &fc); }
     // Narrow windows (no far line on any span) go to the skewed-range kernel, all in ONE group whatever their
     // width (its lanes walk per-lane line ranges, so a span may be wider than a line's support), provided the
     // group fills the chip: at least 8 wavefronts per CU, else the span kernel's line split serves small grids better.
@@ -1347,30 +1423,31 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
     if (ctx->accum_variant == 5 && ctx->skew && !ctx->accum_R && !ctx->accum_LS) {
         long long pts = 0;
         for (int j = 0; j < n_jobs; ++j)
-            if (ctx->skew == 2 || !has_far(j)) { long long f, c; shard_range(grid[j], &f, &c); pts += c; }
-        const long long cus = ctx->n_cu > 0 ? ctx->n_cu : 256;
-        skew_on = ctx->skew == 2 || pts / (64LL * ctx->skew_R) >= 8 * cus;
+            if (ctx->skew == 2 || !has_far(ctx, grid[j], B.far_half_spans)) pts += shard_points(grid[j]);
+        skew_on = ctx->skew == 2 || pts / (64LL * ctx->skew_R) >= 8LL * cu_count(ctx);
     }
-    auto is_skew = [&](int j) { return skew_on && (ctx->skew == 2 || !has_far(j)); };
-    auto group_key = [&](int j) { return is_skew(j) ? 0 : r_cap(j) * 2 + has_far(j); };
-    std::vector<int> order(n_jobs);
+    B.job_key.resize(n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        const int far = has_far(ctx, grid[j], B.far_half_spans);
+        const bool skewed = skew_on && (ctx->skew == 2 || !far);
+        B.job_key[j] = skewed ? 0 : r_cap(ctx, grid[j]) * 2 + far;
+    }
+    const std::vector<int>& key = B.job_key;
+    std::vector<int>& order = B.order;
+    order.resize(n_jobs);
     for (int j = 0; j < n_jobs; ++j) order[j] = j;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return group_key(a) > group_key(b); });
-    struct Group { int first, count, R, LS, max_tiles, variant; int grun; const int2* worklist; int total_tiles; const int32_t* tabs; std::vector<size_t> tab_off; lbl_ctx::Schedule* sched; };
-    std::vector<Group> groups;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] > key[b]; });
     for (int k = 0; k < n_jobs;) {
         int e = k;
         long long pts = 0, lns = 0, mh = 1LL << 40, mxh = 0;
-        while (e < n_jobs && group_key(order[e]) == group_key(order[k])) {
-            long long f, c;
-            shard_range(grid[order[e]], &f, &c);
-            pts += c; lns += (long long)job_lines[order[e]];
-            const long long H = std::max<long long>(grid[order[e]].window - 2, 0);
+        while (e < n_jobs && key[order[e]] == key[order[k]]) {
+            pts += shard_points(grid[order[e]]); lns += (long long)B.job_lines[order[e]];
+            const long long H = half_window(grid[order[e]]);
             mh = std::min(mh, H); mxh = std::max(mxh, H);
             ++e;
         }
-        Group g{k, e - k, 0, 0, 0, ctx->accum_variant, 16, nullptr, 0, nullptr, {}, nullptr};
-        if (is_skew(order[k])) {
+        AccumGroup g{k, e - k, 0, 0, 0, ctx->accum_variant, 16, nullptr};
+        if (key[order[k]] == 0) {
             g.R = ctx->skew_R; g.LS = 1; g.variant = 6;
             // dense (merged) line lists: a chunk of 80 records must cover about the span's 64 R points, else only part of
             // the lanes has lines in it - the waves of a workgroup then share a span and deal its records (R = 8 only)
@@ -1379,134 +1456,122 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
         } else {
             choose_shape(ctx, g.variant, pts, lns, mh, &g.R, &g.LS);
             // with the R actually chosen (a small grid may have shrunk it): does any job of the group have far lines?
-            if (ctx->accum_variant == 5 && mxh < 32LL * g.R * (far_half_spans + 1)) g.variant = 3;
+            if (ctx->accum_variant == 5 && mxh < 32LL * g.R * (B.far_half_spans + 1)) g.variant = 3;
             // Gaussian runs of 32 points (the far-field kernel's three-waves-per-SIMD build, lbl_kernels.hip).  Budget mode: for
             // launches of more than one round of the chip's wave slots at four per SIMD, a launch that fits one round keeps the
             // 16-point build.  Exact mode: the 32-point build is also the one whose series starts at 3 half-spans (fewer
             // instructions per span), so it takes every launch except those that fit one round at four waves per SIMD but not
             // at three (column of 50 layers, forced 16 / this rule / forced 32, same box: 3.797 / 3.623 -> 3.60 / 3.604 ms).
             if (g.variant == 5 && g.R == 4 && g.LS == 1) {
-                const long long waves = (pts + 255) / 256, n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+                const long long waves = (pts + 255) / 256, n_cu = cu_count(ctx);
                 const bool run32 = ctx->accuracy ? waves > 16 * n_cu : !(waves > 12 * n_cu && waves <= 16 * n_cu);
                 g.grun = ctx->gauss_run ? ctx->gauss_run : (run32 ? 32 : 16);
             }
         }
-        if ((g.variant == 3 || g.variant == 5 || g.variant == 6) && (ctx->lpt || merge)) {
+        if ((g.variant == 3 || g.variant == 5 || g.variant == 6) && (ctx->lpt || B.merge)) {
             // cached schedule of this group: dispatch order + the line ranges of every span (+ merged positions)
             std::vector<int> members(order.begin() + k, order.begin() + e);
             ctx->sched_refused = false;
-            lbl_ctx::Schedule* sc = group_schedule(ctx, g.variant == 6 ? 3 : g.variant, members, lines, grid, g.R, g.LS,
-                                                   accumulate_tile_points(g.R, g.LS, g.variant), merge ? merge->first : nullptr);
+            lbl_ctx::Schedule* sc = group_schedule(ctx, g.variant == 6 ? 3 : g.variant, members, B.lines, grid, g.R, g.LS,
+                                                   accumulate_tile_points(g.R, g.LS, g.variant), B.lists);
             if (!sc && ctx->sched_refused)
                 return fail(ctx, LBL_ERR_BAD_ARG, "merged layer jobs need the device schedule build, which does not cover a launch of this size: use the per-line-list step");
             if (!sc) return ctx->capturing ? LBL_ERR_STATE : fail(ctx, LBL_ERR_OOM, "schedule allocation failed");
             if ((sc->pending || sc->merge_pending) && ctx->capturing) return capture_refuses(ctx, "building a dispatch schedule");
-            g.worklist = sc->d_list; g.total_tiles = sc->launch_total; g.tabs = sc->d_tabs; g.tab_off = sc->tab_off; g.sched = sc;
+            g.sched = sc;
         }
-        groups.push_back(g);
+        B.groups.push_back(g);
         k = e;
     }
-    // where the group's schedule keeps the merged-order map of job order[k] (NULL: a job of one list)
-    std::vector<const int32_t*> job_src(n_jobs, nullptr);
-    for (const Group& g : groups)
+    B.job_src.assign(n_jobs, nullptr);
+    for (const AccumGroup& g : B.groups)
         for (int k = g.first; k < g.first + g.count; ++k)
             if (g.sched && g.sched->d_src && g.sched->src_off[(size_t)(k - g.first)] != SIZE_MAX)
-                job_src[order[k]] = g.sched->d_src + g.sched->src_off[(size_t)(k - g.first)];
-    PrepJob* hp = (PrepJob*)stage;
-    MergedPrep* hm = (MergedPrep*)((char*)stage + (size_t)n_lists * sizeof(PrepJob));
-    AccumJob* ha = (AccumJob*)((char*)stage + prep_bytes);
-    ctx->last_list_blocks.assign(n_lists, 0);
+                B.job_src[order[k]] = g.sched->d_src + g.sched->src_off[(size_t)(k - g.first)];
+    return LBL_OK;
+}
+
+// 3. PrepJob per line list, MergedPrep per job of several lists
+static void batch_fill_prep(lbl_ctx* ctx, AccumBatch& B) {
+    const JobLists& lists = B.lists;
+    ctx->last_list_blocks.assign(B.n_lists, 0);
     int mj = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const size_t base = line_off[l0(j)];                          // the job's record array
-        if (job_src[j]) {
-            MergedPrep& m = hm[mj++];
+    for (int j = 0; j < B.n_jobs; ++j) {
+        const size_t base = B.line_off[lists.begin(j)];                 // the job's record array
+        if (B.job_src[j]) {
+            MergedPrep& m = B.hm[mj++];
             memset(&m, 0, sizeof m);
-            m.src = job_src[j];
+            m.src = B.job_src[j];
             m.hot = (HotRec*)ctx->recs.ptr + base; m.cold = (ColdRec*)ctx->cold.ptr + base; m.cidx = (int32_t*)ctx->cidx.ptr + base;
-            m.first_list = l0(j); m.n_lists = l1(j) - l0(j);
-            m.n_total = (int32_t)job_lines[j]; m.blocks = (int32_t)((job_lines[j] + 255) / 256);
-            m.block_reach = job_reach(j);
+            m.first_list = lists.begin(j); m.n_lists = lists.count(j);
+            m.n_total = (int32_t)B.job_lines[j]; m.blocks = (int32_t)((B.job_lines[j] + 255) / 256);
+            m.block_reach = B.job_reach(j);
         }
-        for (int l = l0(j); l < l1(j); ++l) {
-            ctx->last_list_blocks[l] = job_src[j] ? (int)((job_lines[j] + 255) / 256) : (int)((lines[l]->n + 255) / 256);
-            const lbl_lines* L = lines[l];
-            PrepJob& p = hp[l];
+        for (int l = lists.begin(j); l < lists.end(j); ++l) {
+            const lbl_lines* L = B.lines[l];
+            ctx->last_list_blocks[l] = B.job_src[j] ? (int)((B.job_lines[j] + 255) / 256) : (int)((L->n + 255) / 256);
+            PrepJob& p = B.hp[l];
             memset(&p, 0, sizeof p);
             p.nu = L->field(0); p.sw = L->field(1); p.elower = L->field(2); p.gamma_air = L->field(3);
             p.gamma_self = L->field(4); p.n_air = L->field(5); p.delta_air = L->field(6);
-            const bool scattered = job_src[j] != nullptr;            // several lists: prepared in merged order into the job's arrays
-            const size_t off = scattered ? base : line_off[l];
+            const bool scattered = B.job_src[j] != nullptr;            // several lists: prepared in merged order into the job's arrays
+            const size_t off = scattered ? base : B.line_off[l];
             p.hot = (HotRec*)ctx->recs.ptr + off;
             p.cold = (ColdRec*)ctx->cold.ptr + off;
             p.cidx = (int32_t*)ctx->cidx.ptr + off;
             p.merged = scattered ? 1 : 0;
-            p.weight = merge ? merge->weight[l] : 1.0;
-            p.block_counts = d_counts + (size_t)l * blocks_per_job * 3;
-            p.block_reach = scattered ? nullptr : d_reach + (size_t)l * std::max(blocks_per_job, 1);
-            prep_job_physics(p, iso[l], grid[j]);
+            p.weight = B.merge ? B.merge->weight[l] : 1.0;
+            p.block_counts = B.d_counts + (size_t)l * B.blocks_per_job * 3;
+            p.block_reach = scattered ? nullptr : B.d_reach + (size_t)l * std::max(B.blocks_per_job, 1);
+            prep_job_physics(p, B.iso[l], B.grid[j]);
             p.gauss_cut = ctx->accuracy ? 17179869184.0 : 18014398509481984.0;          // 2^34 : 2^54
             p.n_lines = (int32_t)L->n;
             p.pad = ctx->ablate;                 // (LBL_DIAG builds: debug_ablate 1024 drops every Gaussian part; else 0, never read)
         }
     }
-    const bool balanced = ctx->accum_variant == 4;
-    // balanced variant scratch, per group: SpanRec[S] | counts u32[S] | prefix u64[S+1] | slab
-    std::vector<size_t> bal_off(groups.size() + 1, 0);
-    std::vector<int> group_spans(groups.size(), 0), group_workers(groups.size(), 0);
-    for (Group& g : groups) {
+}
+
+// 4. AccumJob per job, in launch order
+static void batch_fill_accum(lbl_ctx* ctx, AccumBatch& B) {
+    for (AccumGroup& g : B.groups) {
         const long long tile_pts = accumulate_tile_points(g.R, g.LS, g.variant);
         for (int k = g.first; k < g.first + g.count; ++k) {
-            const int j = order[k];
-            AccumJob& a = ha[k];
+            const int j = B.order[k];
+            const lbl_grid& grid = B.grid[j];
+            const size_t base = B.line_off[B.lists.begin(j)];
+            AccumJob& a = B.ha[k];
             memset(&a, 0, sizeof a);
-            a.hot = (const HotRec*)ctx->recs.ptr + line_off[l0(j)];
-            a.cold = (const ColdRec*)ctx->cold.ptr + line_off[l0(j)];
-            a.cidx = (const int32_t*)ctx->cidx.ptr + line_off[l0(j)];
-            a.out = needs_regrid(grid[j]) ? (double*)ctx->work.ptr + work_off[j] : out_dev[j];
-            a.n_lines = (int32_t)job_lines[j];
-            a.n_work = (int32_t)grid[j].n_work;
-            a.H = (int32_t)std::max<long long>(grid[j].window - 2, 0);
-            long long sf, sc;
-            shard_range(grid[j], &sf, &sc);
-            a.p_begin = (int32_t)sf;
-            a.p_end = (int32_t)(sf + sc);
-            a.n_tiles = (int32_t)((sc + tile_pts - 1) / tile_pts);
+            a.hot = (const HotRec*)ctx->recs.ptr + base;
+            a.cold = (const ColdRec*)ctx->cold.ptr + base;
+            a.cidx = (const int32_t*)ctx->cidx.ptr + base;
+            a.out = needs_regrid(grid) ? (double*)ctx->work.ptr + B.work_off[j] : B.out_dev[j];
+            a.n_lines = (int32_t)B.job_lines[j];
+            a.n_work = (int32_t)grid.n_work;
+            a.H = (int32_t)half_window(grid);
+            const ShardShape sh = shard_shape(grid, tile_pts, g.R);
+            a.p_begin = (int32_t)sh.first;
+            a.p_end = (int32_t)(sh.first + sh.count);
+            a.n_tiles = (int32_t)sh.tiles;
             a.flush_every = (a.H + 64 * g.R + 1 <= 40000) ? 32 : 16;
             a.pad = ctx->tile_order;
             a.ablate = ctx->ablate;
-            a.span_tab = g.tabs ? g.tabs + g.tab_off[(size_t)(k - g.first)] : nullptr;
-            a.out_scale = merge ? merge->out_scale[j] : 1.0;
+            a.span_tab = g.sched ? g.sched->d_tabs + g.sched->tab_off[(size_t)(k - g.first)] : nullptr;
+            a.out_scale = B.merge ? B.merge->out_scale[j] : 1.0;
             // (one list, or several prepared in merged order: the blocks of the line prep are the blocks of this job's records)
-            if (ctx->reach_skip && (l1(j) - l0(j) == 1 || job_src[j])) a.block_reach = job_reach(j);
-            if (fuse && n_jobs == 1) {
+            if (ctx->reach_skip && (B.lists.count(j) == 1 || B.job_src[j])) a.block_reach = B.job_reach(j);
+            if (B.fuse && B.n_jobs == 1) {
                 a.chain_flags = CHAIN_MOL_FIRST | CHAIN_MOL_LAST;
-                a.conc = fuse_conc;
-                a.fuse = *fuse;
+                a.conc = B.fuse_conc;
+                a.fuse = *B.fuse;
             }
             g.max_tiles = std::max(g.max_tiles, a.n_tiles);
-            if (balanced) {
-                const size_t gi = (size_t)(&g - &groups[0]);
-                a.span_first = group_spans[gi];
-                a.n_spans = (int32_t)((sc + 64LL * g.R - 1) / (64LL * g.R));
-                group_spans[gi] += a.n_spans;
-            }
         }
     }
-    if (balanced) {
-        size_t tot = 0;
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            const size_t S = (size_t)group_spans[gi];
-            group_workers[gi] = ctx->bal_workers[groups[gi].R] ? ctx->bal_workers[groups[gi].R]
-                                                                 : (ctx->bal_workers[groups[gi].R] = balanced_workers(groups[gi].R, ctx->n_cu));
-            bal_off[gi] = tot;
-            tot += ((S * sizeof(SpanRec) + S * sizeof(unsigned int) + (S + 1) * sizeof(unsigned long long) + 255) & ~(size_t)255)
-                   + (size_t)group_workers[gi] * 2 * 64 * groups[gi].R * sizeof(double) + 256;
-        }
-        bal_off[groups.size()] = tot;
-        if ((rc = arena_reserve(ctx, ctx->bal, std::max<size_t>(tot, 256)))) return rc;
-    }
-    // device copy of the descriptors: reuse an identical block if one is cached (4 slots, round robin)
+}
+
+// 5. Device copy of the descriptors: reuse an identical block if one is cached (4 slots, round robin)
+static int batch_upload_descriptors(lbl_ctx* ctx, AccumBatch& B) {
+    int rc;
     char* d_desc = nullptr;
     for (auto& e : ctx->desc_cache)
         if (e.dptr && e.bytes == ctx->desc_build) { d_desc = (char*)e.dptr; break; }
@@ -1531,13 +1596,17 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
         e.bytes = ctx->desc_build;
         d_desc = (char*)e.dptr;
     }
-    PrepJob* dp = (PrepJob*)d_desc;
-    AccumJob* da = (AccumJob*)(d_desc + prep_bytes);
-    ctx->last_blocks_per_job = blocks_per_job;
-    // Merged layer jobs whose schedule is new: the merged-order map, ahead of the line prep that runs in that order - each
-    // list's centre indices (K1's expression) into scratch, then one rank search per line and other list of its job.
-    // Once per (line lists, grid); kept in the schedule's block.
-    for (Group& g : groups) {
+    B.d_desc = d_desc;
+    ctx->last_blocks_per_job = B.blocks_per_job;
+    return LBL_OK;
+}
+
+// 6. Merged layer jobs whose schedule is new: the merged-order map, ahead of the line prep that runs in that order - each
+// list's centre indices (K1's expression) into scratch, then one rank search per line and other list of its job.
+// Once per (line lists, grid); kept in the schedule's block.
+static int batch_merge_ranks(lbl_ctx* ctx, AccumBatch& B) {
+    int rc;
+    for (AccumGroup& g : B.groups) {
         lbl_ctx::Schedule* sc = g.sched;
         if (!sc || !sc->merge_pending) continue;
         TraceScope tr("merge ranks (enqueue)", (long long)g.count);
@@ -1546,19 +1615,19 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
         size_t tmp_lines = 0;
         int ml_max = 0;
         for (int k = g.first; k < g.first + g.count; ++k) {
-            const int j = order[k];
-            if (!job_src[j]) continue;
+            const int j = B.order[k];
+            if (!B.job_src[j]) continue;
             const int jf = (int)ml.size();
-            for (int l = l0(j); l < l1(j); ++l) {
+            for (int l = B.lists.begin(j); l < B.lists.end(j); ++l) {
                 MergeList m;
                 memset(&m, 0, sizeof m);
-                m.nu = lines[l]->field(0);
+                m.nu = B.lines[l]->field(0);
                 tmp_off.push_back(tmp_lines);                             // (tmp_cidx is set once the scratch exists)
-                m.src_of_job = const_cast<int32_t*>(job_src[j]);
-                m.range_min = grid[j].range_min; m.resolution = grid[j].resolution;
-                m.n_lines = (int32_t)lines[l]->n;
-                m.job_first = jf; m.job_count = l1(j) - l0(j);
-                tmp_lines += (size_t)lines[l]->n;
+                m.src_of_job = const_cast<int32_t*>(B.job_src[j]);
+                m.range_min = B.grid[j].range_min; m.resolution = B.grid[j].resolution;
+                m.n_lines = (int32_t)B.lines[l]->n;
+                m.job_first = jf; m.job_count = B.lists.count(j);
+                tmp_lines += (size_t)B.lines[l]->n;
                 ml_max = std::max(ml_max, m.n_lines);
                 ml.push_back(m);
             }
@@ -1575,18 +1644,28 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
         HIP_TRY(ctx, hipGetLastError());
         sc->merge_pending = false;
     }
+    return LBL_OK;
+}
+
+// 7. Line prep (K1): records, centre indices and regime counts of every list
+static int batch_line_prep(lbl_ctx* ctx, AccumBatch& B) {
+    const PrepJob* dp = (const PrepJob*)B.d_desc;
     hipEvent_t ev = prof_begin(ctx, PROF_PREP);
-    if (n_merged_jobs < n_jobs) launch_line_prep(dp, n_lists, max_lines, ctx->stream);      // (lists of merged jobs return at once)
-    if (n_merged_jobs > 0)
-        launch_line_prep_merged(dp, (const MergedPrep*)(d_desc + (size_t)n_lists * sizeof(PrepJob)), n_merged_jobs, (int)max_job_lines, ctx->stream);
+    if (B.n_merged_jobs < B.n_jobs) launch_line_prep(dp, B.n_lists, B.max_lines, ctx->stream);      // (lists of merged jobs return at once)
+    if (B.n_merged_jobs > 0)
+        launch_line_prep_merged(dp, (const MergedPrep*)(B.d_desc + (size_t)B.n_lists * sizeof(PrepJob)), B.n_merged_jobs, (int)B.max_job_lines, ctx->stream);
     prof_end(ctx, PROF_PREP, ev);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->last_jobs = n_lists;
+    ctx->last_jobs = B.n_lists;
     ctx->last_prep_desc = dp;
-    if (prep_only) return LBL_OK;
-    // schedules that have not been built yet: span tables from the centre indices K1 has just written, tile costs and
-    // the dispatch order, all in stream ahead of the accumulate launches that read them (nothing comes back to the host)
-    for (Group& g : groups) {
+    return LBL_OK;
+}
+
+// 8. Schedules that have not been built yet: span tables from the centre indices K1 has just written, tile costs and
+// the dispatch order, all in stream ahead of the accumulate launches that read them (nothing comes back to the host)
+static int batch_build_schedules(lbl_ctx* ctx, AccumBatch& B) {
+    int rc;
+    for (AccumGroup& g : B.groups) {
         lbl_ctx::Schedule* sc = g.sched;
         if (!sc || !sc->pending) continue;
         TraceScope tr("schedule build (enqueue)", (long long)sc->total);
@@ -1596,7 +1675,7 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
         if ((rc = stage_alloc(ctx, jobs_bytes, &pinned))) return rc;
         SchedJob* hj = (SchedJob*)pinned;
         for (int k = g.first; k < g.first + g.count; ++k) {
-            const AccumJob& a = ha[k];
+            const AccumJob& a = B.ha[k];
             SchedJob& sj = hj[k - g.first];
             sj.cidx = a.cidx; sj.n_lines = a.n_lines; sj.H = a.H; sj.p_begin = a.p_begin; sj.p_end = a.p_end;
             sj.span_first = sc->span_first[(size_t)(k - g.first)]; sj.tile_first = sc->tile_first[(size_t)(k - g.first)];
@@ -1604,45 +1683,69 @@ static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines,
         HIP_TRY(ctx, hipMemcpyAsync(ctx->sched.ptr, pinned, (size_t)g.count * sizeof(SchedJob), hipMemcpyHostToDevice, ctx->stream));
         launch_schedule_build((const SchedJob*)ctx->sched.ptr, g.count, sc->total_spans, sc->total, sc->R, sc->spans_per_tile,
                               sc->far_reach, sc->cost_near, sc->cost_edge, sc->cost_far, sc->cost_fixed,
-                              ctx->n_cu > 0 ? ctx->n_cu : 256, sc->d_tabs, (char*)ctx->sched.ptr + jobs_bytes, sc->d_list, ctx->stream,
+                              cu_count(ctx), sc->d_tabs, (char*)ctx->sched.ptr + jobs_bytes, sc->d_list, ctx->stream,
                               sc->xcd_chunks, sc->xcd_pack != 0, sc->sr_chunks, sc->xcd_tol, sc->xcd_pack == 2 ? 1 : sc->xcd_pack == 3 ? 0 : -1);
         HIP_TRY(ctx, hipGetLastError());
         sc->pending = false;
     }
+    return LBL_OK;
+}
+
+// 9. The accumulate launches (K2), one per group
+static int batch_launch_groups(lbl_ctx* ctx, AccumBatch& B) {
     // software pipeline of two contexts (lbl_ctx_chain_accumulate): this step's accumulate kernels start after the
-    // predecessor's; its line prep (above) did not wait
+    // predecessor's; its line prep did not wait
     if (ctx->chain_pred && !ctx->capturing) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->chain_pred->accum_done, 0));
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group& g = groups[gi];
-        ev = prof_begin(ctx, PROF_ACCUM);
-        if (balanced) {
-            const size_t S = (size_t)group_spans[gi];
-            char* base = (char*)ctx->bal.ptr + bal_off[gi];
-            SpanRec* spans = (SpanRec*)base;
-            unsigned long long* prefix = (unsigned long long*)(base + S * sizeof(SpanRec));       // 8-byte aligned: 16 B * S
-            unsigned int* cnts = (unsigned int*)(base + S * sizeof(SpanRec) + (S + 1) * sizeof(unsigned long long));
-            double* slab = (double*)(base + ((S * sizeof(SpanRec) + S * sizeof(unsigned int) + (S + 1) * sizeof(unsigned long long) + 255) & ~(size_t)255));
-            launch_accumulate_balanced(da + g.first, g.count, (int)S, g.R, group_workers[gi], spans, cnts, prefix, slab,
-                                       ctx->stream);
-        } else if (g.variant == 6) {
-            launch_accumulate_skew(da + g.first, g.count, g.max_tiles, g.R, g.worklist, g.total_tiles, ctx->stream, g.LS);
-        } else {
-            launch_accumulate(da + g.first, g.count, g.max_tiles, g.R, g.LS, g.variant, g.worklist, g.total_tiles,
+    const AccumJob* da = (const AccumJob*)(B.d_desc + B.prep_bytes);
+    for (const AccumGroup& g : B.groups) {
+        const int2* worklist = g.sched ? g.sched->d_list : nullptr;
+        const int total_tiles = g.sched ? g.sched->launch_total : 0;
+        hipEvent_t ev = prof_begin(ctx, PROF_ACCUM);
+        if (g.variant == 6)
+            launch_accumulate_skew(da + g.first, g.count, g.max_tiles, g.R, worklist, total_tiles, ctx->stream, g.LS);
+        else
+            launch_accumulate(da + g.first, g.count, g.max_tiles, g.R, g.LS, g.variant, worklist, total_tiles,
                               ctx->stream, ctx->accuracy, g.grun);
-        }
         prof_end(ctx, PROF_ACCUM, ev);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (ctx->accum_done && !ctx->capturing) HIP_TRY(ctx, hipEventRecord(ctx->accum_done, ctx->stream));
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!needs_regrid(grid[j])) continue;
-        ev = prof_begin(ctx, PROF_REGRID);
-        launch_regrid((const double*)ctx->work.ptr + work_off[j], grid[j].n_work, out_dev[j], grid[j].n_base,
-                      grid[j].range_min, grid[j].range_max, ctx->stream);
+    return LBL_OK;
+}
+
+// 10. Work grids coarser than the base grid: interpolate onto the caller's array
+static int batch_regrid(lbl_ctx* ctx, AccumBatch& B) {
+    for (int j = 0; j < B.n_jobs; ++j) {
+        const lbl_grid& g = B.grid[j];
+        if (!needs_regrid(g)) continue;
+        hipEvent_t ev = prof_begin(ctx, PROF_REGRID);
+        launch_regrid((const double*)ctx->work.ptr + B.work_off[j], g.n_work, B.out_dev[j], g.n_base, g.range_min, g.range_max, ctx->stream);
         prof_end(ctx, PROF_REGRID, ev);
         HIP_TRY(ctx, hipGetLastError());
     }
     return LBL_OK;
+}
+
+static int enqueue_accumulate(lbl_ctx* ctx, int n_jobs, lbl_lines* const* lines, const lbl_iso_params* iso,
+                              const lbl_grid* grid, double* const* out_dev, bool prep_only,
+                              const FusedSweep* fuse = nullptr, double fuse_conc = 0.0, const MergeSpec* merge = nullptr) {
+    // fuse != NULL (n_jobs == 1): the layer sweep runs in the output stage of the one job
+    // merge == NULL: job j is line list j; lines / iso hold n_jobs entries.  grid and out_dev are per JOB either way.
+    if (n_jobs <= 0) return LBL_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    AccumBatch B{n_jobs, lines, iso, grid, out_dev, fuse, fuse_conc, merge, merge ? merge->lists : JobLists()};
+    int rc;
+    if ((rc = batch_layout(ctx, B))) return rc;
+    if ((rc = batch_group(ctx, B))) return rc;
+    batch_fill_prep(ctx, B);
+    batch_fill_accum(ctx, B);
+    if ((rc = batch_upload_descriptors(ctx, B))) return rc;
+    if ((rc = batch_merge_ranks(ctx, B))) return rc;
+    if ((rc = batch_line_prep(ctx, B))) return rc;
+    if (prep_only) return LBL_OK;
+    if ((rc = batch_build_schedules(ctx, B))) return rc;
+    if ((rc = batch_launch_groups(ctx, B))) return rc;
+    return batch_regrid(ctx, B);
 }
 
 // Introspection for tests: the k-th most recently used schedule of the context (0 = the last one handed out):
@@ -2088,7 +2191,7 @@ extern "C" int lbl_layer_merged_step_dev(lbl_ctx* ctx, int n_iso, lbl_lines* con
     double out_scale = 1.0;
     merged_weights(n_iso, iso_mol, conc, iso[0].P, iso[0].T, weight.data(), &out_scale);
     const int first[2] = {0, n_iso};
-    MergeSpec ms{first, weight.data(), &out_scale};
+    MergeSpec ms{JobLists{first}, weight.data(), &out_scale};
     if (!needs_regrid(*grid)) {
         double* out = nullptr;
         if (!trans && !I_out) {
@@ -2148,7 +2251,7 @@ extern "C" int lbl_layers_merged_accumulate_dev(lbl_ctx* ctx, int n_layers, cons
         outs[(size_t)l] = abs_coef[l]->d;
         mol0 += n_mol[l];
     }
-    MergeSpec ms{first.data(), weight.data(), out_scale.data()};
+    MergeSpec ms{JobLists{first.data()}, weight.data(), out_scale.data()};
     return enqueue_accumulate(ctx, n_layers, lines, iso, grid, outs.data(), false, nullptr, 0.0, &ms);
 } LBL_GUARD_END(ctx)
 

@@ -79,8 +79,7 @@ struct AccumJob {
     int32_t p_end;
     int32_t flush_every;   // lines per running-fraction block: 32, or 16 for very wide windows
     int32_t pad;           // LS variant: tile order (0 XCD-chunked, 1 natural)
-    int32_t span_first;    // balanced variant: first global span id of this job
-    int32_t n_spans;
+    int32_t reserved[2];   // always 0 (the span numbering of the retired variant 4): keeps the offsets of what follows, and so the kernels' code
     // LDS variants with a host schedule: line ranges of every span of 64*R points of this job's
     // shard, 8 ints per span {iA, iB, iC, iD, iF1, iF2, 0, 0} (see wave_line_ranges[_far]); NULL:
     // the wave searches the centre indices itself
@@ -101,9 +100,9 @@ struct AccumJob {
 };
 enum : int32_t { CHAIN_MOL_FIRST = 1, CHAIN_MOL_LAST = 2 };
 
-// Balanced variant: spans (64*R consecutive grid points) of all jobs of a launch group are
-// numbered job-major; job j owns spans [span_first, span_first + n_spans).
-struct SpanRec { int32_t iA, iB, iC, iD; };
+// (the span record of the retired variant 4: the name alone, no definition and no user in the library, so that a host-shim
+// mock written against the earlier header - it stubbed variant 4's launcher by pointer - still compiles against this one)
+struct SpanRec;
 
 struct PrepJob {
     const double* nu; const double* sw; const double* elower; const double* gamma_air;
@@ -641,11 +640,6 @@ void launch_accumulate(const AccumJob* d_jobs, int n_jobs, int max_tiles, int R,
 void launch_accumulate_skew(const AccumJob* d_jobs, int n_jobs, int max_tiles, int R, const int2* worklist, int total_tiles,
                             hipStream_t s, int LS = 1);      // LS 2 | 4: R = 8 only (waves of a workgroup share a span and deal its records)
 void accumulate_far_field_params(int R, int* far_half_spans, double* far_cost, int budget = 0);
-// balanced variant (4): span ranges -> prefix sum -> equal shares of (span, line) pairs per wave -> slab reduce
-int balanced_workers(int R, int n_cu);
-void launch_accumulate_balanced(const AccumJob* d_jobs, int n_jobs, int total_spans, int R, int n_workers,
-                                SpanRec* spans, unsigned int* counts, unsigned long long* prefix, double* slab,
-                                hipStream_t s);
 void launch_regrid(const double* work, long long n_work, double* out, long long n_base, double start, double stop,
                    hipStream_t s);
 void launch_layer_sweep(const SweepArgs& a, hipStream_t s);

@@ -47,11 +47,10 @@
 // with a plain coalesced store.  No atomics, and a fixed summation order per grid point, so two
 // runs are bit-identical.
 //
-// K2 variants (lbl_set_option "accum_variant"; 1, 2 and 4 exist in diagnostic builds only, -DLBL_DIAG):
+// K2 variants (lbl_set_option "accum_variant"; 1, 2 and 4 - the scalar-cache running fraction / recurrence kernels and the
+// balanced single-round partition - were measured, superseded and removed: docs/history/):
 //   0    xsec_accumulate_kernel      the literal form: IEEE divide + exp per pair, records through the scalar cache (on-device cross-check)
-//   1-2  xsec_accumulate_kernel      running fraction / + Gaussian recurrence through the scalar cache (superseded)
 //   3    xsec_accumulate_lds_kernel  records streamed through wave-private LDS, every pair direct
-//   4    ..._balanced_kernel         3 with an exactly balanced partition of (span, line) pairs (superseded)
 //   5    xsec_accumulate_lds_kernel<.., FF = true>  (default) 3 + far-field series for distant
 //        Lorentz lines; optionally the layer sweep of a single-line-list layer in the output stage;
 //        round 3: its edge lines (support ends inside the span) take the skewed walk (skew_edges), and
@@ -635,44 +634,30 @@ struct WaveAcc {
     }
 };
 
-// One line against a lane's R points.  DIV == 0: IEEE divide per pair; DIV == 2: running fraction.
-template <int R, bool MASKED, int DIV>
-__device__ __forceinline__ void lorentz_term(double a2, double KL, int flags, double d0, double Hf, WaveAcc<R>& S) {
-    if (DIV == 0 || (flags & REC_DIRECT_DIV)) {
+// One line against a lane's R points: an IEEE divide per pair.
+template <int R, bool MASKED>
+__device__ __forceinline__ void lorentz_term(double a2, double KL, double d0, double Hf, WaveAcc<R>& S) {
 #pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const double d = d0 + (double)k;
-            double t = KL / fma(d, d, a2);
-            if (MASKED) t = (fabs(d) <= Hf) ? t : 0.0;
-            S.acc[k] += t;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const double d = d0 + (double)k;
-            const double den = fma(d, d, a2);
-            double K = KL;
-            if (MASKED) K = (fabs(d) <= Hf) ? K : 0.0;
-            const double t = K * S.D[k];
-            S.N[k] = fma(S.N[k], den, t);
-            S.D[k] *= den;
-        }
-        if (++S.cnt == S.every) S.flush();
+    for (int k = 0; k < R; ++k) {
+        const double d = d0 + (double)k;
+        double t = KL / fma(d, d, a2);
+        if (MASKED) t = (fabs(d) <= Hf) ? t : 0.0;
+        S.acc[k] += t;
     }
 }
 
-// ---- variants 0-2: line records through the scalar cache (one s_load per wave and line) ----
-template <int R, bool MASKED, int DIV, int GM>
+// ---- variant 0: line records through the scalar cache (one s_load per wave and line) ----
+template <int R, bool MASKED>
 __device__ __forceinline__ void process_lines_scalar(const HotRec* hot, const ColdRec* cold, int i0, int i1, double x0,
                                                      int wlo, int whi, double Hf, WaveAcc<R>& S) {
     for (int i = i0; i < i1; ++i) {
         Rec r = load_rec_scalar(hot, cold, i, false);
         const double d0 = x0 - r.cf;
-        lorentz_term<R, MASKED, DIV>(r.a2, r.KL, r.flags, d0, Hf, S);
+        lorentz_term<R, MASKED>(r.a2, r.KL, d0, Hf, S);
         const int dist = max(0, max(r.ci - whi, wlo - r.ci));
         if (dist < r.dgi) {
             r = load_rec_scalar(hot, cold, i, true);
-            gauss_term<R, GM>(r.KG, r.b, r.q2 >= 0.0, d0, Hf, r.q2, S.acc);
+            gauss_term<R, 0>(r.KG, r.b, r.q2 >= 0.0, d0, Hf, r.q2, S.acc);
         }
     }
 }
@@ -791,7 +776,7 @@ __device__ __forceinline__ void store_points(double* __restrict__ out, int p0, i
     }
 }
 
-template <int R, int DIV, int GM>
+template <int R>
 __global__ __launch_bounds__(256) void xsec_accumulate_kernel(const AccumJob* __restrict__ jobs) {
     const AccumJob& J = jobs[blockIdx.y];
     const int tile = xcd_tile(blockIdx.x, J.n_tiles);
@@ -812,9 +797,9 @@ __global__ __launch_bounds__(256) void xsec_accumulate_kernel(const AccumJob* __
     const double Hf = (double)H;
     WaveAcc<R> S;
     S.init(J.flush_every);
-    process_lines_scalar<R, true, DIV, GM>(J.hot, J.cold, iA, iB, x0, wlo, whi, Hf, S);
-    process_lines_scalar<R, false, DIV, GM>(J.hot, J.cold, iB, iC, x0, wlo, whi, Hf, S);
-    process_lines_scalar<R, true, DIV, GM>(J.hot, J.cold, iC, iD, x0, wlo, whi, Hf, S);
+    process_lines_scalar<R, true>(J.hot, J.cold, iA, iB, x0, wlo, whi, Hf, S);
+    process_lines_scalar<R, false>(J.hot, J.cold, iB, iC, x0, wlo, whi, Hf, S);
+    process_lines_scalar<R, true>(J.hot, J.cold, iC, iD, x0, wlo, whi, Hf, S);
     S.flush();
     store_points<R>(J.out, p0, n_end, S.acc);
 }
@@ -2186,42 +2171,6 @@ __global__ __launch_bounds__(256, 4) void xsec_accumulate_skew_kernel(const Accu
     }
 }
 
-#ifdef LBL_DIAG      // variant 4 (measured: no faster than 3): diagnostic builds only (make EXTRA=-DLBL_DIAG)
-// ---- variant 4: balanced single-round partition -----------------------------------------------
-// Small grids do not fill the chip evenly with one workgroup per span: C2 has 1.5-3 rounds of
-// workgroups of very different length (line density varies 7x) and ran with the VALU only 55-69 %
-// busy.  Here the unit of work is a (span, line) pair.  P1 finds every span's line range, P2
-// prefix-sums the counts, and K2b gives each of the W resident wavefronts exactly ceil(P/W)
-// consecutive pairs: every wave does the same number of line iterations and they all finish
-// together.  A wave's share may start and end inside a span; such partial sums go to a slab
-// (at most two per wave) and P3 adds the slabs of a split span in wave order, so the result is
-// still deterministic.  Spans covered by one wave are stored directly.
-__device__ __forceinline__ int find_job(const AccumJob* __restrict__ jobs, int n_jobs, int g, int j0 = 0) {
-    int j = j0;
-    while (j + 1 < n_jobs && g >= jobs[j].span_first + jobs[j].n_spans) ++j;
-    return j;
-}
-
-template <int R>
-__global__ __launch_bounds__(256) void span_ranges_kernel(const AccumJob* __restrict__ jobs, int n_jobs, int total_spans,
-                                                          SpanRec* __restrict__ spans, unsigned int* __restrict__ counts) {
-    const int lane = threadIdx.x & 63;
-    const int g = uniform_i32(blockIdx.x * 4 + (threadIdx.x >> 6));
-    if (g >= total_spans) return;
-    const AccumJob& J = jobs[find_job(jobs, n_jobs, g)];
-    const int wlo = J.p_begin + (g - J.span_first) * (64 * R);
-    const int whi = min(wlo + 64 * R - 1, J.p_end - 1);
-    int iA, iB, iC, iD;
-    wave_line_ranges(J.cidx, J.n_lines, wlo, whi, J.H, lane, iA, iB, iC, iD);
-    if (lane == 0) {
-        SpanRec r; r.iA = iA; r.iB = iB; r.iC = iC; r.iD = iD;
-        spans[g] = r;
-        counts[g] = (unsigned int)(iD - iA);
-    }
-}
-
-#endif
-
 // exclusive prefix sum of n counts into prefix[0..n] (single workgroup of 1024 threads)
 static int scan_blocks(int n) { const int tiles = (n + 1023) / 1024; return tiles < 1 ? 1 : (tiles > 64 ? 64 : tiles); }
 
@@ -2275,182 +2224,6 @@ __global__ __launch_bounds__(1024) void scan_counts_kernel(const unsigned int* _
     }
     if (hi == n && t == 0) prefix[n] = base;
 }
-
-#ifdef LBL_DIAG
-// first index i in [0, n] with prefix[i] > key (prefix non-decreasing): 16-ary search by the
-// first 16 lanes' worth of probes replicated over the wave
-__device__ __forceinline__ int upper_bound_u64(const unsigned long long* __restrict__ a, int n, unsigned long long key,
-                                               int lane) {
-    const int jj = lane & 15;
-    int lo = 0, hi = n;                                   // answer in [lo, hi]; a[n] treated as > key if none
-    while (hi > lo) {
-        const long long len = (long long)hi - lo;
-        const int pos = lo + (int)(((long long)(jj + 1) * len) / 17);
-        const bool le = a[pos] <= key;                    // pos < hi <= n: always a valid slot of prefix[0..n]
-        const int k = __popcll(__ballot(le) & 0xFFFFull);
-        const int p_k = lo + (int)(((long long)(k + 1) * len) / 17);
-        const int p_km1 = lo + (int)(((long long)k * len) / 17);
-        const int new_lo = k > 0 ? p_km1 + 1 : lo;
-        const int new_hi = k < 16 ? p_k : hi;
-        lo = new_lo; hi = new_hi;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ unsigned long long pairs_per_worker(unsigned long long P, int W) {
-    unsigned long long q = (P + (unsigned long long)W - 1) / (unsigned long long)W;
-    return q < 64ull ? 64ull : q;                         // at least one chunk of lines per wave
-}
-
-template <int R>
-__global__ __launch_bounds__(256, (R >= 8 ? 4 : 1)) void xsec_accumulate_balanced_kernel(
-        const AccumJob* __restrict__ jobs, int n_jobs, int total_spans, const SpanRec* __restrict__ spans,
-        const unsigned long long* __restrict__ prefix, int W, double* __restrict__ slab) {
-    constexpr int STAGE = (68 * R > 512) ? 68 * R : 512;
-    __shared__ double s_stage[4][STAGE];
-    const int lane = threadIdx.x & 63;
-    const int wave = uniform_i32(threadIdx.x >> 6);
-    const int w = uniform_i32(blockIdx.x * 4 + wave);
-    if (w >= W) return;
-    const unsigned long long P = prefix[total_spans];
-    const unsigned long long Q = pairs_per_worker(P, W);
-    const unsigned long long start = (unsigned long long)w * Q;
-    if (start >= P) return;
-    const unsigned long long end = (start + Q < P) ? start + Q : P;
-    double* lh = s_stage[wave];
-    double* lc = s_stage[wave] + 256;
-
-    int s = uniform_i32(upper_bound_u64(prefix, total_spans, start, lane)) - 1;      // prefix[s] <= start < prefix[s+1]
-    int j = 0;
-    unsigned long long pos = start;
-    while (pos < end) {
-        const unsigned long long p_lo = prefix[s], p_hi = prefix[s + 1];
-        if (p_hi <= pos) { ++s; continue; }               // empty span, or the previous one was just finished
-        const int n_s = (int)(p_hi - p_lo);
-        const int off = (int)(pos - p_lo);
-        const int piece = (int)((end - pos < (unsigned long long)(n_s - off)) ? (end - pos) : (unsigned long long)(n_s - off));
-        j = find_job(jobs, n_jobs, s, j);
-        const AccumJob& J = jobs[j];
-        const SpanRec r = spans[s];
-        const int wlo = J.p_begin + (s - J.span_first) * (64 * R);
-        const int n_end = J.p_end;
-        const int whi = min(wlo + 64 * R - 1, n_end - 1);
-        const double x0 = (double)(wlo + lane * R);
-        const double Hf = (double)J.H;
-        WaveAcc<R> S;
-        S.init(J.flush_every);
-        double unused[16];
-        accumulate_lines<R, 0>(J.hot, J.cold, r.iA + off, r.iA + off + piece, r.iB, r.iC, wlo, whi, x0, Hf, lh, lc, lane, S, unused);
-        S.flush();
-        // coalesced store through LDS: whole spans straight to the output, partial ones to the slab
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k = 0; k < R; ++k) lh[span_slot(lane * R + k)] = S.acc[k];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const bool whole = (off == 0) && (piece == n_s);
-        double* __restrict__ dst = whole ? (J.out + wlo)
-                                         : (slab + ((size_t)w * 2 + (pos == start ? 0 : 1)) * (size_t)(64 * R));
-        const int limit = whole ? (n_end - wlo) : 64 * R;
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            const int o = i * 64 + lane;
-            if (o < limit) dst[o] = lh[span_slot(o)];
-        }
-        __builtin_amdgcn_wave_barrier();
-        pos += (unsigned long long)piece;
-    }
-}
-
-// P3: one wave per span: zeros for spans no line reaches, slab sums (in wave order) for split spans
-template <int R>
-__global__ __launch_bounds__(256) void span_finalize_kernel(const AccumJob* __restrict__ jobs, int n_jobs, int total_spans,
-                                                            const unsigned long long* __restrict__ prefix, int W,
-                                                            const double* __restrict__ slab) {
-    const int lane = threadIdx.x & 63;
-    const int g = uniform_i32(blockIdx.x * 4 + (threadIdx.x >> 6));
-    if (g >= total_spans) return;
-    const AccumJob& J = jobs[find_job(jobs, n_jobs, g)];
-    const int wlo = J.p_begin + (g - J.span_first) * (64 * R);
-    const int n_end = J.p_end;
-    double* __restrict__ out = J.out;
-    const unsigned long long p_lo = prefix[g], p_hi = prefix[g + 1];
-    if (p_hi == p_lo) {
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            const int o = i * 64 + lane;
-            if (wlo + o < n_end) out[wlo + o] = 0.0;
-        }
-        return;
-    }
-    const unsigned long long Q = pairs_per_worker(prefix[total_spans], W);
-    const int w0 = (int)(p_lo / Q), w1 = (int)((p_hi - 1) / Q);
-    if (w0 == w1) return;                                  // stored directly by its only wave
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int o = i * 64 + lane;
-        double t = 0.0;
-        for (int w = w0; w <= w1; ++w) {
-            // a wave that started before this span contributes its LAST piece (slot 1); a wave that
-            // starts inside (or at) the span contributes its FIRST piece (slot 0)
-            const int slot = (w == w0 && (unsigned long long)w0 * Q < p_lo) ? 1 : 0;
-            t += slab[((size_t)w * 2 + slot) * (size_t)(64 * R) + o];
-        }
-        if (wlo + o < n_end) out[wlo + o] = t;
-    }
-}
-
-// Number of wavefronts that are resident at once: the partition must fit in ONE round, so ask the
-// runtime how many 256-thread workgroups of the kernel a CU holds (registers, LDS) and stay one
-// workgroup per CU below the answer when it is at the 8-block edge (the API over-reports there for
-// SGPR-heavy kernels, MI355X_MICROARCH.md "Residency and cooperative launch").
-template <int R>
-static int balanced_workers_r(int n_cu) {
-    int blocks = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, xsec_accumulate_balanced_kernel<R>, 256, 0) != hipSuccess || blocks < 1)
-        blocks = 2;
-    if (blocks >= 8) blocks = 7;
-    return (n_cu > 0 ? n_cu : 256) * blocks * 4;
-}
-
-int balanced_workers(int R, int n_cu) {
-    switch (R) {
-        case 1: return balanced_workers_r<1>(n_cu);
-        case 2: return balanced_workers_r<2>(n_cu);
-        case 4: return balanced_workers_r<4>(n_cu);
-        default: return balanced_workers_r<8>(n_cu);
-    }
-}
-
-template <int R>
-static void launch_balanced_r(const AccumJob* d_jobs, int n_jobs, int total_spans, int n_workers, SpanRec* spans,
-                              unsigned int* counts, unsigned long long* prefix, double* slab, hipStream_t s) {
-    const int span_blocks = (total_spans + 3) / 4;
-    hipLaunchKernelGGL((span_ranges_kernel<R>), dim3(span_blocks), dim3(256), 0, s, d_jobs, n_jobs, total_spans, spans, counts);
-    hipLaunchKernelGGL(scan_counts_kernel, dim3(scan_blocks(total_spans)), dim3(1024), 0, s, counts, total_spans, prefix);
-    hipLaunchKernelGGL((xsec_accumulate_balanced_kernel<R>), dim3((n_workers + 3) / 4), dim3(256), 0, s, d_jobs, n_jobs,
-                       total_spans, spans, prefix, n_workers, slab);
-    hipLaunchKernelGGL((span_finalize_kernel<R>), dim3(span_blocks), dim3(256), 0, s, d_jobs, n_jobs, total_spans, prefix,
-                       n_workers, slab);
-}
-
-void launch_accumulate_balanced(const AccumJob* d_jobs, int n_jobs, int total_spans, int R, int n_workers,
-                                SpanRec* spans, unsigned int* counts, unsigned long long* prefix, double* slab,
-                                hipStream_t s) {
-    if (n_jobs <= 0 || total_spans <= 0) return;
-    switch (R) {
-        case 1: launch_balanced_r<1>(d_jobs, n_jobs, total_spans, n_workers, spans, counts, prefix, slab, s); break;
-        case 2: launch_balanced_r<2>(d_jobs, n_jobs, total_spans, n_workers, spans, counts, prefix, slab, s); break;
-        case 4: launch_balanced_r<4>(d_jobs, n_jobs, total_spans, n_workers, spans, counts, prefix, slab, s); break;
-        default: launch_balanced_r<8>(d_jobs, n_jobs, total_spans, n_workers, spans, counts, prefix, slab, s); break;
-    }
-}
-
-#else
-// (the production library carries no balanced kernel: lbl_set_option refuses accum_variant 4)
-int balanced_workers(int, int) { return 0; }
-void launch_accumulate_balanced(const AccumJob*, int, int, int, int, SpanRec*, unsigned int*, unsigned long long*, double*, hipStream_t) {}
-#endif
 
 // ----------------------------------------------------------------------------------------
 // Schedule of a launch group, built on the device (time to first spectrum: a pressure or range change
@@ -6038,15 +5811,9 @@ void launch_line_quantities(const PrepJob* d_job, int n_lines, long long* index,
 }
 
 template <int R>
-static void launch_accum_scalar(const AccumJob* d_jobs, int n_jobs, int max_tiles, int variant, hipStream_t s) {
+static void launch_accum_scalar(const AccumJob* d_jobs, int n_jobs, int max_tiles, hipStream_t s) {
     dim3 grid(((max_tiles + 7) / 8) * 8, n_jobs);
-    switch (variant) {
-#ifdef LBL_DIAG      // (1: running fraction, 2: + Gaussian recurrence, both through the scalar cache: superseded comparison kernels)
-        case 1: hipLaunchKernelGGL((xsec_accumulate_kernel<R, 2, 0>), grid, dim3(256), 0, s, d_jobs); break;
-        case 2: hipLaunchKernelGGL((xsec_accumulate_kernel<R, 2, 1>), grid, dim3(256), 0, s, d_jobs); break;
-#endif
-        default: hipLaunchKernelGGL((xsec_accumulate_kernel<R, 0, 0>), grid, dim3(256), 0, s, d_jobs); break;   // 0: IEEE divide + exp per pair
-    }
+    hipLaunchKernelGGL((xsec_accumulate_kernel<R>), grid, dim3(256), 0, s, d_jobs);   // 0: IEEE divide + exp per pair
 }
 
 template <int R, int NT>
@@ -6103,42 +5870,29 @@ void accumulate_far_field_params(int R, int* far_half_spans, double* far_cost, i
 }
 
 
+// f(std::integral_constant<int, R>) for the points per lane of a launch: 1, 2, 4, and 8 for everything else
+template <class F>
+static void with_points_per_lane(int R, F&& f) {
+    switch (R) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        default: f(std::integral_constant<int, 8>()); break;
+    }
+}
+
 void launch_accumulate(const AccumJob* d_jobs, int n_jobs, int max_tiles, int R, int LS, int variant,
                        const int2* worklist, int total_tiles, hipStream_t s, int budget, int gauss_run) {
     if (n_jobs <= 0 || max_tiles <= 0) return;
-    if (variant >= 5 && budget) {
-        switch (R) {
-            case 1: launch_accum_lds<1, FF_NT_BUDGET>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-            case 2: launch_accum_lds<2, FF_NT_BUDGET>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-            case 4: launch_accum_lds<4, FF_NT_BUDGET>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s, gauss_run); break;
-            default: launch_accum_lds<8, FF_NT_BUDGET>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-        }
-        return;
-    }
-    if (variant >= 5) {
-        switch (R) {
-            case 1: launch_accum_lds<1, FF_NT>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-            case 2: launch_accum_lds<2, FF_NT>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-            case 4: launch_accum_lds<4, FF_NT>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s, gauss_run); break;
-            default: launch_accum_lds<8, FF_NT>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-        }
-        return;
-    }
-    if (variant >= 3) {
-        switch (R) {
-            case 1: launch_accum_lds<1, 0>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-            case 2: launch_accum_lds<2, 0>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-            case 4: launch_accum_lds<4, 0>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-            default: launch_accum_lds<8, 0>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); break;
-        }
-        return;
-    }
-    switch (R) {
-        case 1: launch_accum_scalar<1>(d_jobs, n_jobs, max_tiles, variant, s); break;
-        case 2: launch_accum_scalar<2>(d_jobs, n_jobs, max_tiles, variant, s); break;
-        case 4: launch_accum_scalar<4>(d_jobs, n_jobs, max_tiles, variant, s); break;
-        default: launch_accum_scalar<8>(d_jobs, n_jobs, max_tiles, variant, s); break;
-    }
+    // (gauss_run: launch_accum_lds reads it for R == 4 with the far-field series only)
+    if (variant >= 5 && budget)
+        with_points_per_lane(R, [&](auto r) { launch_accum_lds<decltype(r)::value, FF_NT_BUDGET>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s, gauss_run); });
+    else if (variant >= 5)
+        with_points_per_lane(R, [&](auto r) { launch_accum_lds<decltype(r)::value, FF_NT>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s, gauss_run); });
+    else if (variant >= 3)
+        with_points_per_lane(R, [&](auto r) { launch_accum_lds<decltype(r)::value, 0>(d_jobs, n_jobs, max_tiles, LS, worklist, total_tiles, s); });
+    else
+        with_points_per_lane(R, [&](auto r) { launch_accum_scalar<decltype(r)::value>(d_jobs, n_jobs, max_tiles, s); });
 }
 
 void launch_voigt_prep(const PrepJob* d_prep, const VoigtJob* d_jobs, int n_jobs, int max_lines, hipStream_t s) {

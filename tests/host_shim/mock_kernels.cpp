@@ -257,8 +257,6 @@ void launch_accumulate_skew(const AccumJob* d_jobs, int n_jobs, int max_tiles, i
     accumulate_common(d_jobs, n_jobs, max_tiles, accumulate_tile_points(R, LS, 3), 64 * R, worklist, total_tiles);
 }
 
-int balanced_workers(int, int) { return 0; }
-void launch_accumulate_balanced(const AccumJob*, int, int, int, int, SpanRec*, unsigned int*, unsigned long long*, double*, hipStream_t) { ++mockhip::launches; }
 
 void accumulate_far_field_params(int R, int* far_half_spans, double* far_cost, int) {
     *far_half_spans = 4;

@@ -427,13 +427,40 @@ def test_production_library_has_no_ablation_option(ctx):
     with pytest.raises(nat.LblError) as e:
         ctx.set_option("debug_ablate", 1)
     assert e.value.code == -1 and "unknown option" in str(e.value)
-    # round 5: the superseded comparison kernels (variants 1, 2, 4) ship in diagnostic builds only
+    # the superseded comparison kernels (variants 1, 2, 4) are retired: no build carries them
     for v in (1, 2, 4):
         with pytest.raises(nat.LblError) as e:
             ctx.set_option("accum_variant", v)
-        assert e.value.code == -1 and "diagnostic builds only" in str(e.value)
+        assert e.value.code == -1 and "1, 2 and 4 are retired" in str(e.value)
     for v in (0, 3, 5):
         ctx.set_option("accum_variant", v)
+    # "accum_blocks_per_cu" sized variant 4's launch: the key stays (bench.py --blocks-per-cu sets it), range-checked and
+    # without effect - same bits, and a graph captured before it was set is not stale
+    from pyrad_amd import engine
+    g = engine.layer_grid(1013.25, 600, 700, .01, True)
+    L = ctx.lines(synthetic.make_lines(7, 300, 595, 705))
+    out = ctx.buffer(g["n_base"])
+    job = [(L, nat.IsoParams(296.0, 1013.25, 4e-4, 44.0, 286.0, 286.0), engine.native_grid(g), out)]
+    try:
+        ctx.set_option("accum_blocks_per_cu", 0)
+        ctx.xsec_accumulate_dev(job)
+        first = out.download()
+        assert first.size >= 10000 and np.all(np.isfinite(first)) and np.count_nonzero(first) > 0
+        graph = ctx.capture(lambda: ctx.xsec_accumulate_dev(job))
+        ctx.set_option("accum_blocks_per_cu", 8)
+        out.fill(0.0)
+        ctx.xsec_accumulate_dev(job)
+        assert np.array_equal(out.download(), first)
+        out.fill(0.0)
+        graph.launch()
+        assert np.array_equal(out.download(), first)
+        graph.free()
+        with pytest.raises(nat.LblError) as e:
+            ctx.set_option("accum_blocks_per_cu", 9)
+        assert e.value.code == -1 and "accum_blocks_per_cu" in str(e.value)
+    finally:
+        ctx.set_option("accum_blocks_per_cu", 0)
+        L.free(); out.free()
 
 
 def test_line_view_bounds_cannot_overflow(ctx):
