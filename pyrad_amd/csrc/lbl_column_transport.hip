@@ -666,7 +666,7 @@ static int check_jacobian(lbl_ctx* ctx, JacArgs* a, int head, int n_layers, cons
     if (n_terms < 0 || n_terms > kMaxJacobianTerms)
         return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d molecule terms", kMaxJacobianTerms);
     if (n_terms > 0 && (!term_abs_coef || !term_layer)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
-    const int nv = head + (1 + edges) * n_layers + n_terms;
+    const int nv = jacobian_slots(head, edges, n_layers, n_terms);
     if ((rc = ctx_check_buffer(ctx, jac, (int64_t)n_bands * nv, "jac", true))) return rc;
     if ((rc = ctx_check_buffer(ctx, jac_ln_tau_spectra, (int64_t)n_layers * n, "jac_ln_tau_spectra", false))) return rc;
     if ((rc = ctx_check_buffer(ctx, jac_T_spectra, (int64_t)edges * n_layers * n, edges == 1 ? "jac_T_spectra" : "jac_T_edge_spectra", false)))
@@ -713,7 +713,7 @@ extern "C" int lbl_column_jacobian_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* c
     if ((rc = check_jacobian(ctx, a, 2, n_layers, T, n, surface_T, n_angles, weight, n_bands, n_terms, term_abs_coef,
                              term_layer, jac, jac_ln_tau_spectra, jac_T_spectra)))
         return rc;
-    const int nv = 2 + 2 * n_layers + n_terms;
+    const int nv = jacobian_slots(2, 1, n_layers, n_terms);
     return run_column(ctx, a, 2, nv, n_bands, band_count, {a->ln_tau_spec, a->T_spec}, (size_t)n_layers * (size_t)n * sizeof(double),
                       [&](const JacArgs* d, double* partial, int b, hipStream_t s) {
         launch_column_jacobian(d, n_layers, n_angles, n_terms, band_first[b], band_count[b], partial, buffer_data(jac) + (size_t)b * nv, s);
@@ -761,7 +761,7 @@ static int surface_jacobian_call(lbl_ctx* ctx, Args* a, LinearJacArgs* linear, i
         linear->T_edge_spec = a->T_spec;
         T_spec_hi = a->T_spec ? a->T_spec + (size_t)n_layers * (size_t)n : nullptr;
     }
-    const int nv = 3 + (1 + edges) * n_layers + n_terms;
+    const int nv = jacobian_slots(3, edges, n_layers, n_terms);
     return run_column(ctx, a, np, nv, n_bands, band_count, {a->ln_tau_spec, a->T_spec, T_spec_hi},
                       (size_t)n_layers * (size_t)n * sizeof(double),
                       [&](const Args* d, double* partial, int b, hipStream_t s) {
@@ -780,7 +780,7 @@ extern "C" int lbl_column_jacobian_surface_dev(lbl_ctx* ctx, int n_layers, lbl_b
                                                lbl_buffer* jac_e_spectrum) try {
     if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     std::vector<char> blk(sizeof(SurfaceJacArgs), 0);
-    return surface_jacobian_call(ctx, (SurfaceJacArgs*)blk.data(), nullptr, surface_jacobian_points(n_angles),
+    return surface_jacobian_call(ctx, (SurfaceJacArgs*)blk.data(), nullptr, jacobian_points(n_angles),
                                  launch_surface_jacobian, n_layers, abs_coef, T, depth, range_min, range_max, n, I_surface,
                                  surface_T, I_top, n_angles, mu, weight, n_bands, band_first, band_count, emissivity,
                                  emissivity_all, reflection, n_terms, term_abs_coef, term_layer, jac, jac_ln_tau_spectra,
@@ -799,7 +799,7 @@ extern "C" int lbl_column_jacobian_linear_dev(lbl_ctx* ctx, int n_layers, lbl_bu
     if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
     std::vector<char> blk(sizeof(LinearJacArgs), 0);
     LinearJacArgs* a = (LinearJacArgs*)blk.data();
-    return surface_jacobian_call(ctx, a, a, linear_jacobian_points(n_angles), launch_linear_jacobian, n_layers, abs_coef,
+    return surface_jacobian_call(ctx, a, a, jacobian_points(n_angles), launch_linear_jacobian, n_layers, abs_coef,
                                  T_edge, depth, range_min, range_max, n, I_surface, surface_T, I_top, n_angles, mu, weight,
                                  n_bands, band_first, band_count, emissivity, emissivity_all, reflection, n_terms,
                                  term_abs_coef, term_layer, jac, jac_ln_tau_spectra, jac_T_edge_spectra, jac_e_spectrum);
@@ -1257,7 +1257,7 @@ static int ray_jacobian_call(lbl_ctx* ctx, bool surface, bool linear, int n_laye
     void* d_args = nullptr;
     if ((rc = ctx_device_args(ctx, blk.data(), blk.size(), &d_args))) return rc;
     COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
-    if (linear) launch_linear_ray_jacobian((const LinearRayJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
+    if (linear) launch_linear_ray_jacobian((const LinearRayJacArgs*)d_args, n, n_rays, a->n_bundles, ctx_stream(ctx));
     else if (surface) launch_ray_surface_jacobian((const RaySurfaceJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
     else launch_ray_jacobian((const RayJacArgs*)d_args, n, n_rays, a->n_bundles, n_terms, ctx_stream(ctx));
     COLUMN_HIP_TRY(ctx, hipGetLastError());

@@ -260,6 +260,10 @@ struct FluxArgs : ColumnRT {
 // top A and D = E - I_top (E: emission of the layers above that reaches the top), so that A_l t_l (B_l - I_l) = A_l B_l + D_l
 // needs no stored radiance.  Values per band: [F_top, dF/dT_s, L x d ln tau, L x dT (Planck part), n_terms x d ln n].
 constexpr int kMaxJacobianTerms = kMaxColumnIso;
+// Values per band of a column Jacobian call: `head` leading values (K5d: F_top, dT_s; K5h and K5j: and de), per layer one
+// d ln tau and `edges` temperature values (1; K5j, the layer's two edges: 2), then the terms.  The kernels' slots in LDS and
+// their partials, the launchers' final reductions and the checks of `jac` are all sized by it.
+constexpr int jacobian_slots(int head, int edges, int n_layers, int n_terms) { return head + (1 + edges) * n_layers + n_terms; }
 struct JacArgs : ColumnRT {
     double rT[kMaxLayers];              // 1 / T_l (dB/dT = B b e^b / ((e^b - 1) T), b = nu pbkT)
     double r_surface_T;                 // 1 / surface_T (used when I_surface == nullptr)
@@ -474,8 +478,8 @@ struct SurfaceJacArgs : JacArgs {
     double* e_spec;                     // optional: n spectral dF/de
     int32_t reflection, pad2;           // 0 Lambertian, 1 specular (SurfaceFluxArgs)
 };
-// the points per thread of surface_jacobian_kernel for n_angles (its partials are sized by it)
-int surface_jacobian_points(int n_angles);
+// the points per thread of surface_jacobian_kernel and linear_jacobian_kernel for n_angles (their partials are sized by it)
+int jacobian_points(int n_angles);
 void launch_surface_jacobian(const SurfaceJacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first,
                              long long count, double* partial, double* jac, hipStream_t s);
 struct RaySurfaceJacArgs : RayJacArgs {
@@ -495,8 +499,6 @@ struct LinearJacArgs : SurfaceJacArgs {
     double rT_top[kMaxLayers];          // 1 / T at the top edge
     double* T_edge_spec;                // optional: 2 L x n spectral dF/dT_edge
 };
-// the points per thread of linear_jacobian_kernel for n_angles (its partials are sized by it)
-int linear_jacobian_points(int n_angles);
 void launch_linear_jacobian(const LinearJacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first,
                             long long count, double* partial, double* jac, hipStream_t s);
 struct LinearRayJacArgs : RaySurfaceJacArgs {
@@ -504,8 +506,7 @@ struct LinearRayJacArgs : RaySurfaceJacArgs {
     long long off_seg_rT;               // 2 n_segments doubles: 1 / T likewise (a marker's pairs are 0 and never read)
     long long off_seg_Trow;             // n_segments x int32: the row of the segment's dTa relative to the ray's first row
 };
-void launch_linear_ray_jacobian(const LinearRayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
-                                hipStream_t s);
+void launch_linear_ray_jacobian(const LinearRayJacArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s);
 
 // Instrument channels (K8, lbl_instrument.hip: lbl_ils_convolve_dev): n_rows spectra on the base grid convolved with an
 // instrument line shape onto n_channels channels.  One argument block per call: this header, then the arrays it names by

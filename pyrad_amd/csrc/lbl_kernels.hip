@@ -3601,6 +3601,31 @@ __device__ __forceinline__ void band_frame(const Args& A, unsigned threads, long
         partial[(long long)blockIdx.x * nv + t] = (acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]);
 }
 
+// The layer walks of the column kernels: step(l, k) for the layers bottom to top (column_up) or top to bottom (column_down),
+// k the thread's NP absorption coefficients of layer l, loaded one layer ahead of their use.  For the column Jacobian
+// kernels (K5d, K5h, K5j); the flux and solar kernels write the same loop out: on these two their code changes, and
+// surface_flux_kernel<4, 7> goes to scratch ("One step body ...").
+template <int NP, class Args, class Step>
+__device__ __forceinline__ void column_up(const Args& A, long long j, int L, Step step) {
+    typedef f64v<NP> vec;
+    vec cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
+    for (int l = 0; l < L; ++l) {
+        const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
+        step(l, cur);
+        cur = nxt;
+    }
+}
+template <int NP, class Args, class Step>
+__device__ __forceinline__ void column_down(const Args& A, long long j, int L, Step step) {
+    typedef f64v<NP> vec;
+    vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
+    for (int l = L - 1; l >= 0; --l) {
+        const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
+        step(l, cur);
+        cur = nxt;
+    }
+}
+
 // K5c: walks the layers bottom to top for the upward radiances I_up[k] and then top to bottom for the downward ones,
 // re-reading k_l and recomputing B_l on the way down (the registers cannot hold 128 layers' worth).  With the angle set
 // {(1, pi)} the upward radiance at the top is the fold's I_out bit for bit wherever both take the same Planck path (every
@@ -4777,8 +4802,13 @@ __global__ __launch_bounds__(256) void linear_ray_kernel(const LinearRayArgs* __
     ray_surface_walks<NP, RB, true>(Ap, blockDim.x, lo0, n0, lo1, n1, order_first);
 }
 
-// A layer's terms for the column Jacobians (K5d, K5h, K5j): term_k Gd per point, Gd = depth G, summed into the terms' slots,
-// which begin at slot0 (in K5h and K5j walks 2 and 3 each add their leg)
+// ----------------------------------------------------------------------------------------
+// What the column Jacobian kernels (K5d, K5h, K5j) share.  K5h with a black surface returns K5d's bits and K5j with equal
+// edge temperatures K5h's because the operations in question are the same code, not copies of it.  Every body sets
+// fp contract(off) itself: the pragma ends with a function's body.
+// ----------------------------------------------------------------------------------------
+// A layer's terms: term_k Gd per point, Gd = depth G, summed into the terms' slots, which begin at slot0 (in K5h and K5j
+// walks 2 and 3 each add their leg)
 template <int NP, class Add>
 __device__ __forceinline__ void jacobian_terms(const JacArgs& A, int l, long long j, bool active, const double (&Gd)[NP],
                                                int slot0, Add add) {
@@ -4792,6 +4822,134 @@ __device__ __forceinline__ void jacobian_terms(const JacArgs& A, int l, long lon
     }
 }
 
+// One point's values of layer l into the spectra and into the thread's sums: d ln tau and NT temperature values (the
+// layer's: 1; K5j, its bottom and top edge: 2; T_spec holds NT rows per layer).  `store`: this walk stores (K5d's only walk,
+// walk 2 of K5h and K5j); otherwise it adds to what the same thread stored (their walk 3).  T_spec names the temperature
+// spectra's member of the argument block: the pointers are read here, behind `active`, as a kernel's own body would read
+// them - handed over as values they are loaded ahead of every step and cost up to 33 registers (K5j) and a wave (K5d, K5j).
+template <int NT, class Args, class Owner>
+__device__ __forceinline__ void jacobian_emit(bool store, bool active, const Args& A, double* Owner::*T_spec, int l, long long j,
+                                              int p, double dtau, const double (&gT)[NT], double& s_tau, double (&s_T)[NT]) {
+#pragma clang fp contract(off)
+    if (active && A.ln_tau_spec) {
+        double* o = A.ln_tau_spec + (long long)l * A.n + j + p;
+        *o = store ? dtau : *o + dtau;
+    }
+    if (active && A.*T_spec) {
+        double* o = A.*T_spec + (long long)(NT * l) * A.n + j + p;
+#pragma unroll
+        for (int r = 0; r < NT; ++r) {
+            *o = store ? gT[r] : *o + gT[r];
+            o += A.n;
+        }
+    }
+    s_tau += active ? nan_to_num(dtau) : 0.0;
+#pragma unroll
+    for (int r = 0; r < NT; ++r) s_T[r] += active ? nan_to_num(gT[r]) : 0.0;
+}
+
+// K5d's downward step through layer l (the derivation is at column_jacobian_kernel): I holds D, Ak the transmittance A to
+// the top.  HEAD: the band values ahead of the layers' (K5d: 2, K5h: 3); STORE: jacobian_emit's `store`.
+template <bool FAST, int HEAD, bool STORE, int NP, int NA, class Add>
+__device__ __forceinline__ void jacobian_down_step(const JacArgs& A, int L, int l, f64v<NP> v, long long j, bool active,
+                                                   const double (&nu)[NP], const double (&pa_n)[NP], double (&I)[NA][NP],
+                                                   const double (&Imax)[NA][NP], double (&Ak)[NA][NP], Add add) {
+#pragma clang fp contract(off)
+    const double pbkT = A.pbkT[l], depth = A.depth[l], rT = A.rT[l];
+    double E0 = 0.0;
+    if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+    double s_tau = 0.0, s_T[1] = {0.0}, Gd[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const double tau = v[p] * depth;
+        double dB;
+        const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
+        double G = 0.0, gT[1] = {0.0};
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const double tr = exp_neg_budget(tau * A.rmu[k]);
+            const double At = Ak[k][p] * tr;
+            const double g = fmin(fmax(Ak[k][p] * B + I[k][p], -(At * Imax[k][p])), At * B);
+            G = fma(A.wrmu[k], g, G);
+            const double a1 = Ak[k][p] * (1.0 - tr);
+            gT[0] = fma(A.w[k], a1 * dB, gT[0]);
+            I[k][p] = I[k][p] + a1 * B;              // D_(l-1) = D_l + A_l (1 - t_l) B_l
+            Ak[k][p] = At;                           // A_(l-1) = A_l t_l
+        }
+        Gd[p] = depth * G;
+        jacobian_emit<1>(STORE, active, A, &JacArgs::T_spec, l, j, p, tau * G, gT, s_tau, s_T);
+    }
+    add(HEAD + l, s_tau);
+    add(HEAD + L + l, s_T[0]);
+    jacobian_terms<NP>(A, l, j, active, Gd, HEAD + 2 * L, add);
+}
+
+// F_top into slot 0; then I becomes D = -I_top and A = 1: the state the downward derivative walk starts from
+template <int NP, int NA, class Add>
+__device__ __forceinline__ void flux_top_turn(const ColumnRT& A, bool active, double (&I)[NA][NP], double (&Ak)[NA][NP],
+                                              Add add) {
+#pragma clang fp contract(off)
+    double s = 0.0;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
+#pragma unroll
+        for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
+    }
+    add(0, s);
+}
+
+// The reflecting surface of K5h and K5j between walk 1 (downward from the top, which `start` sets up: I_L = I_top or 0,
+// Dmax the same, Ttot = 1) and walk 2.  `turn`: dF/dT_s = e sum_k W_k Ttot_k dBs/dT and dF/de = sum_k W_k Ttot_k (Is - R_k)
+// are complete here (slots 1 and 2, e_spec); then the state becomes walk 2's: I_up[0] = e Is + (1 - e) R, Imax, the weight
+// Qf of what is seen through the surface in Ak, C = 1 and D' = -D.
+template <int NP, int NA>
+struct ReflectingSurfaceTurn {
+    static __device__ __forceinline__ void start(const SurfaceJacArgs& A, long long j, double (&I)[NA][NP], double (&Dm)[NA][NP],
+                                                 double (&Ak)[NA][NP]) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const double It = A.I_top ? A.I_top[j + p] : 0.0;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
+        }
+    }
+    template <class Add>
+    static __device__ __forceinline__ void turn(const SurfaceJacArgs& A, long long j, bool active, const double (&nu)[NP],
+                                                const double (&pa_n)[NP], double (&I)[NA][NP], double (&Imax)[NA][NP],
+                                                double (&Ak)[NA][NP], double (&Ck)[NA][NP], double (&Dp)[NA][NP], Add add) {
+#pragma clang fp contract(off)
+        double s_Ts = 0.0, s_e = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
+            double dBs = 0.0;
+            const double Is = A.I_surface ? A.I_surface[j + p]
+                                          : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
+                                                                     A.r_surface_T, &dBs);
+            const double edBs = e * dBs;
+            const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
+            const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
+            const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
+            const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
+            if (active && A.e_spec) A.e_spec[j + p] = de;
+            s_Ts += active ? nan_to_num(dTs) : 0.0;
+            s_e += active ? nan_to_num(de) : 0.0;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) {
+                const double D = I[k][p];
+                I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
+                Imax[k][p] = I[k][p];
+                Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
+                Ck[k][p] = 1.0;
+                Dp[k][p] = -D;
+            }
+        }
+        add(1, s_Ts);
+        add(2, s_e);
+    }
+};
+
 // K5d: K5c's upward fold, keeping per angle only the radiance I and its running maximum Imax over the levels; then a
 // downward pass that re-reads k_l and recomputes B_l as K5c's does, and keeps per angle the transmittance A to the top and
 // D = E - I_top, E the emission of the layers above that reaches the top.  Then
@@ -4799,21 +4957,32 @@ __device__ __forceinline__ void jacobian_terms(const JacArgs& A, int l, long lon
 // clamped to [-A_l t_l Imax, A_l t_l B_l] (both bounds exact for non-negative sources): where the path above is opaque the
 // true value underflows to ~0 while E - I_top is rounding noise that tau / mu would amplify.  Per point and layer:
 // G = sum_k (W_k / mu_k) g_k; d ln tau_l = tau_l G, molecule term m of the layer = k_(m,l) depth_l G, dT_l = sum_k W_k A (1 - t) dB_l/dT.
+// The downward pass is jacobian_down_step, storing; the turn at the top flux_top_turn; the layer loops column_up / column_down.
 template <int NP, int NA>
 __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __restrict__ Ap, long long lo0, long long n0,
                                                               long long lo1, long long n1, double* __restrict__ partial) {
 #pragma clang fp contract(off)
     typedef f64v<NP> vec;
-    constexpr int kSlot = 2 + 2 * kMaxLayers + kMaxJacobianTerms;
+    constexpr int kSlot = jacobian_slots(2, 1, kMaxLayers, kMaxJacobianTerms);
     __shared__ double acc[4 * kSlot];            // [wave][F_top, dT_s, L x ln tau, L x T, terms]
     const JacArgs& A = *Ap;
     const int L = A.n_layers;
-    const int nv = 2 + 2 * L + A.n_terms;
+    const int nv = jacobian_slots(2, 1, L, A.n_terms);
     band_frame<NP, kSlot>(A, blockDim.x, lo0, n0, lo1, n1, partial, acc, nv, [&](auto fast_tag, long long j, bool active,
                           const double (&nu)[NP], const double (&pa_n)[NP], auto add) {
+        constexpr bool FAST = decltype(fast_tag)::value;
         double dBs[NP], I[NA][NP], Imax[NA][NP], Ak[NA][NP];
-        auto up = [&](auto fast_tag, int l, vec v) {
-            constexpr bool FAST = decltype(fast_tag)::value;
+        // upward: I_0 = I_surface or B(nu, surface_T), as K5c
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            dBs[p] = 0.0;
+            const double Is = A.I_surface ? A.I_surface[j + p]
+                                          : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
+                                                                     A.r_surface_T, &dBs[p]);
+#pragma unroll
+            for (int k = 0; k < NA; ++k) { I[k][p] = Is; Imax[k][p] = Is; }
+        }
+        column_up<NP>(A, j, L, [&](int l, vec v) {
             const double pbkT = A.pbkT[l], depth = A.depth[l];
             double E0 = 0.0;
             if (FAST) E0 = exp_clamped(nu[0] * pbkT);
@@ -4828,74 +4997,13 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
                     Imax[k][p] = fmax(Imax[k][p], I[k][p]);
                 }
             }
-        };
-        auto down = [&](auto fast_tag, int l, vec v) {
-            constexpr bool FAST = decltype(fast_tag)::value;
-            const double pbkT = A.pbkT[l], depth = A.depth[l], rT = A.rT[l];
-            double E0 = 0.0;
-            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
-            double s_tau = 0.0, s_T = 0.0, Gd[NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double tau = v[p] * depth;
-                double dB;
-                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
-                double G = 0.0, gT = 0.0;
-#pragma unroll
-                for (int k = 0; k < NA; ++k) {
-                    const double tr = exp_neg_budget(tau * A.rmu[k]);
-                    const double At = Ak[k][p] * tr;
-                    const double g = fmin(fmax(Ak[k][p] * B + I[k][p], -(At * Imax[k][p])), At * B);
-                    G = fma(A.wrmu[k], g, G);
-                    const double a1 = Ak[k][p] * (1.0 - tr);
-                    gT = fma(A.w[k], a1 * dB, gT);
-                    I[k][p] = I[k][p] + a1 * B;              // D_(l-1) = D_l + A_l (1 - t_l) B_l
-                    Ak[k][p] = At;                           // A_(l-1) = A_l t_l
-                }
-                const double dtau = tau * G;
-                Gd[p] = depth * G;
-                if (active && A.ln_tau_spec) A.ln_tau_spec[(long long)l * A.n + j + p] = dtau;
-                if (active && A.T_spec) A.T_spec[(long long)l * A.n + j + p] = gT;
-                s_tau += active ? nan_to_num(dtau) : 0.0;
-                s_T += active ? nan_to_num(gT) : 0.0;
-            }
-            add(2 + l, s_tau);
-            add(2 + L + l, s_T);
-            jacobian_terms<NP>(A, l, j, active, Gd, 2 + 2 * L, add);
-        };
-        // upward: I_0 = I_surface or B(nu, surface_T), as K5c
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            dBs[p] = 0.0;
-            const double Is = A.I_surface ? A.I_surface[j + p]
-                                          : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
-                                                                     A.r_surface_T, &dBs[p]);
-#pragma unroll
-            for (int k = 0; k < NA; ++k) { I[k][p] = Is; Imax[k][p] = Is; }
-        }
-        vec cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
-        for (int l = 0; l < L; ++l) {
-            const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
-            up(fast_tag, l, cur);
-            cur = nxt;
-        }
-        // F_top; then I becomes D = -I_top and A = 1
-        double s = 0.0;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
-        }
-        add(0, s);
-        cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-        for (int l = L - 1; l >= 0; --l) {
-            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-            down(fast_tag, l, cur);
-            cur = nxt;
-        }
+        });
+        flux_top_turn<NP, NA>(A, active, I, Ak, add);
+        column_down<NP>(A, j, L, [&](int l, vec v) {
+            jacobian_down_step<FAST, 2, true, NP, NA>(A, L, l, v, j, active, nu, pa_n, I, Imax, Ak, add);
+        });
         // dF/dT_s = sum_k W_k A_(-1)k dB(nu, T_s)/dT (0 when the surface is a given spectrum)
-        s = 0.0;
+        double s = 0.0;
 #pragma unroll
         for (int p = 0; p < NP; ++p)
             s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return Ak[k][p] * dBs[p]; })) : 0.0;
@@ -4903,16 +5011,199 @@ __global__ __launch_bounds__(256) void column_jacobian_kernel(const JacArgs* __r
     });
 }
 
+// ----------------------------------------------------------------------------------------
+// What the ray Jacobian kernels (K5f, K5h, K5j) share
+// ----------------------------------------------------------------------------------------
+// The rows of a bundle's rays in `jac`.  One row per ray, kind and crossed layer: the layer's first segment in backward
+// order stores, every later one adds to what the same thread stored (the host marks the first, kRayRowStore, in seg_slot).
+// The segments' slots, the term rows and the count of crossed layers are the same for every ray of the bundle.
+template <int NP, int RB>
+struct RayRows {
+    const RayJacArgs& A;
+    long long j;                        // the thread's first grid point
+    long long row0[RB];                 // each ray's first row
+    const int32_t* slot;                // per segment of the bundle: the rank of its layer among the crossed ones | kRayRowStore
+    const int32_t* term_row;            // per sorted term: its row
+    int crossed;                        // distinct layers crossed
+
+    __device__ __forceinline__ RayRows(const RayJacArgs& A_, const char* blk, const int (&rid)[RB], int s0, long long j_)
+        : A(A_), j(j_) {
+        const long long* row_first = (const long long*)(blk + A.off_row_first);
+#pragma unroll
+        for (int i = 0; i < RB; ++i) row0[i] = row_first[rid[i]];
+        slot = (const int32_t*)(blk + A.off_seg_slot) + s0;
+        term_row = (const int32_t*)(blk + A.off_term_row) + ((const int32_t*)(blk + A.off_ray_terms))[rid[0]];
+        crossed = ((const int32_t*)(blk + A.off_ray_crossed))[rid[0]];
+    }
+    // whether segment s stores its layer's rows, and the layer's rank (both uniform over the workgroup)
+    __device__ __forceinline__ bool stores(int s) const { return (slot[s] & kRayRowStore) != 0; }
+    __device__ __forceinline__ long long rank(int s) const { return slot[s] & (kRayRowStore - 1); }
+    // row `row` of ray i at point p
+    __device__ __forceinline__ void put(int i, long long row, int p, double v, bool store) const {
+#pragma clang fp contract(off)
+        double* o = A.jac + (row0[i] + row) * A.n + (j + p);
+        *o = store ? v : *o + v;
+    }
+};
+
+// K5d's downward step along real segment s (layer l), last to first (the derivation is at ray_jacobian_kernel): I holds D,
+// Ak the transmittance A from the segment's end to the observer; g is kept for the segment's terms.  HEAD: the ray's rows
+// ahead of the layers' (K5f: 1, K5h: 2).
+template <bool FAST, int HEAD, int NP, int RB>
+__device__ __forceinline__ void ray_backward_step(const RayJacArgs& A, const RayRows<NP, RB>& R, int s, int l, f64v<NP> cur,
+                                                  const double (&len)[RB], bool active, const double (&nu)[NP],
+                                                  const double (&pa_n)[NP], double (&I)[RB][NP], const double (&Imax)[RB][NP],
+                                                  double (&Ak)[RB][NP], double (&g)[RB][NP]) {
+#pragma clang fp contract(off)
+    const bool store = R.stores(s);
+    const long long row_tau = HEAD + R.rank(s);
+    const long long row_T = row_tau + R.crossed;
+    const double pbkT = A.pbkT[l], rT = A.rT[l];
+    double E0 = 0.0;
+    if (FAST) E0 = exp_clamped(nu[0] * pbkT);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        double dB;
+        const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+            const double tau = cur[p] * len[i];
+            const double tr = exp_neg_budget(tau);
+            const double At = Ak[i][p] * tr;
+            g[i][p] = fmin(fmax(Ak[i][p] * B + I[i][p], -(At * Imax[i][p])), At * B);
+            const double a1 = Ak[i][p] * (1.0 - tr);
+            if (active) {
+                R.put(i, row_tau, p, tau * g[i][p], store);
+                R.put(i, row_T, p, a1 * dB, store);
+            }
+            I[i][p] = I[i][p] + a1 * B;              // D_(s-1) = D_s + A_s (1 - t_s) B_s
+            Ak[i][p] = At;                           // A_(s-1) = A_s t_s
+        }
+    }
+}
+
+// The terms of segment s (layer l): k_m len g per ray and point into the term's row, stored or added to as the layer's rows
+template <int NP, int RB>
+__device__ __forceinline__ void ray_terms(const RayJacArgs& A, const RayRows<NP, RB>& R, int s, int l, const double (&len)[RB],
+                                          bool active, const double (&g)[RB][NP]) {
+#pragma clang fp contract(off)
+    const bool store = R.stores(s);
+    for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
+        const f64v<NP> km = load_points<NP>(A.term_k[t], R.j);
+        const long long row = R.term_row[t];
+        if (active) {
+#pragma unroll
+            for (int i = 0; i < RB; ++i) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p) R.put(i, row, p, (km[p] * len[i]) * g[i][p], store);
+            }
+        }
+    }
+}
+
+// The state of the ray Jacobian kernels that know surface markers (K5h, K5j) and everything they do outside a real segment.
+// Forward: I <- e Is + (1 - e) I at a marker, as ray_surface_kernel, Imax takes the result, and dI/de is carried along in Ak:
+// S <- t S per segment (the kernel's step), S <- (Is - I) + (1 - e) S at a marker (the backward identity would divide by
+// 1 - e); a ray from the surface starts with I = e Is and S = Is.  Backward: a marker emits, D += A e Is, adds A e dBs/dT to
+// the ray's row 0 (the first marker met stores, as a layer's rows are stored, the source at the very end adds or stores)
+// and then dims what lies before it, A <- A (1 - e).  Rows: [dT_source, de, ...].
+template <int NP, int RB, class Args>
+struct RaySurfaceWalk {
+    const RayFrame<NP, RB, true, Args>& F;
+    const RayRows<NP, RB> R;
+    double I[RB][NP], Imax[RB][NP], Ak[RB][NP];          // (Ak: S = dI/de on the forward walk)
+    bool row0_stored;                                     // backward: a marker has stored row 0
+
+    __device__ __forceinline__ RaySurfaceWalk(const RayFrame<NP, RB, true, Args>& F_)
+        : F(F_), R(F_.A, F_.blk, F_.rid, F_.s0[0], F_.j), row0_stored(false) {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                I[i][p] = F.surface[i] ? surface_leaving(F.em[p], F.Is[p], 0.0) : 0.0;
+                Imax[i][p] = I[i][p];
+                Ak[i][p] = F.surface[i] ? F.Is[p] : 0.0;
+            }
+        }
+    }
+    // e dB(nu, source_T)/dT at point p (0 when the source is a given spectrum)
+    __device__ __forceinline__ double source_dT(int p) const {
+#pragma clang fp contract(off)
+        double dBs = 0.0;
+        if (!F.A.I_surface)
+            fold_planck<false, true>(false, F.nu[p], F.nu[p], F.pa_n[p], F.A.pbk_surface, 0.0, F.A.r_source_T, &dBs);
+        return F.em[p] * dBs;
+    }
+    __device__ __forceinline__ void forward_marker() {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                Ak[i][p] = (F.Is[p] - I[i][p]) + (1.0 - F.em[p]) * Ak[i][p];
+                I[i][p] = surface_leaving(F.em[p], F.Is[p], I[i][p]);
+                Imax[i][p] = fmax(Imax[i][p], I[i][p]);
+            }
+        }
+    }
+    // after the forward walk: the radiance and dI/de; then I becomes D = -I_final and A = 1
+    __device__ __forceinline__ void turn() {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int i = 0; i < RB; ++i) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                if (F.active && F.A.radiance) F.A.radiance[(long long)F.rid[i] * F.A.n + F.j + p] = I[i][p];
+                if (F.active) R.put(i, 1, p, Ak[i][p], true);
+                I[i][p] = -I[i][p];
+                Ak[i][p] = 1.0;
+            }
+        }
+    }
+    __device__ __forceinline__ void backward_marker() {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const double edBs = F.A.I_surface ? 0.0 : source_dT(p);
+            const double eIs = F.em[p] * F.Is[p];
+#pragma unroll
+            for (int i = 0; i < RB; ++i) {
+                if (F.active && !F.A.I_surface) R.put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
+                I[i][p] = I[i][p] + Ak[i][p] * eIs;
+                Ak[i][p] = Ak[i][p] * (1.0 - F.em[p]);
+            }
+        }
+        if (!F.A.I_surface) row0_stored = true;
+    }
+    // after the backward walk, the source's part of dI/dT_source: A_0 e dBs/dT for a ray from the surface at source_T
+    __device__ __forceinline__ void source_row() const {
+#pragma clang fp contract(off)
+        if (F.active) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const double edBs = source_dT(p);
+#pragma unroll
+                for (int i = 0; i < RB; ++i) {
+                    const double v = F.surface[i] && !F.A.I_surface ? Ak[i][p] * edBs : 0.0;
+                    if (!row0_stored || F.surface[i]) R.put(i, 0, p, v, !row0_stored);
+                }
+            }
+        }
+    }
+};
+
 // K5f: ray-path Jacobians (lbl_ray_jacobian_dev; the semantics are in include/pyrad_hip.h).  K5e's walk over the bundle's
 // segments (the same transport_step, exp and update, so the radiance is K5e's bit for bit), keeping per ray and point the
 // running maximum Imax of I; then K5d's downward pass along the segments last to first: k_l re-read a segment ahead, B_l
 // and dB_l/dT recomputed, and per ray the transmittance A from the segment's end to the observer and D = E - I_final.
 //     A t (B - I_s) = A B + D, clamped to [-A t Imax, A t B]            (I_s: the radiance entering the segment)
-// One row per ray, kind and crossed layer: the layer's first segment in this backward order stores, every later one adds to
-// what the same thread stored (the host marks the first, kRayRowStore).  No atomics, no memset, no LDS, nothing shared between
-// threads: the same inputs give the same bits, and a ray's rows do not depend on the rays it travels with.
+// Rows as RayRows keeps them.  No atomics, no memset, no LDS, nothing shared between threads: the same inputs give the
+// same bits, and a ray's rows do not depend on the rays it travels with.
 // TERMS = false leaves the term loop out (a call without terms): the bundle then need not keep g for it and fits two waves
 // per SIMD; the arithmetic of every other row is the same.
+// The frame (set-up and segment loops) is the kernel's own, not RayFrame (it measures slower on it: DESIGN.md, "Two frames
+// carry ..."); the backward step, the term loop and the rows are the shared ray_backward_step, ray_terms and RayRows.
 template <int NP, int RB, bool TERMS>
 __global__ __launch_bounds__(256) void ray_jacobian_kernel(const RayJacArgs* __restrict__ Ap, long long lo0, long long n0,
                                                            long long lo1, long long n1, int order_first) {
@@ -4925,7 +5216,6 @@ __global__ __launch_bounds__(256) void ray_jacobian_kernel(const RayJacArgs* __r
     const double* __restrict__ seg_length = (const double*)(blk + A.off_seg_length);
     const int32_t* __restrict__ source_kind = (const int32_t*)(blk + A.off_source_kind);
     const int32_t* __restrict__ order = (const int32_t*)(blk + A.off_order);
-    const long long* __restrict__ row_first = (const long long*)(blk + A.off_row_first);
     // (idle lanes of the last workgroup work on a valid point and store nothing)
     const long long q = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * NP;
     const bool active = q < n0 + n1;
@@ -4937,26 +5227,17 @@ __global__ __launch_bounds__(256) void ray_jacobian_kernel(const RayJacArgs* __r
     for (int p = 0; p < NP; ++p) Is[p] = A.I_surface ? A.I_surface[j + p] : planck_budget(nu[p], A.pa, A.pbk_surface);
     int rid[RB], s0[RB];
     bool surface[RB];
-    long long row0[RB];                                   // the ray's first row
 #pragma unroll
     for (int i = 0; i < RB; ++i) {
         rid[i] = order[order_first + (int)blockIdx.y * RB + i];
         s0[i] = ray_first[rid[i]];
         surface[i] = source_kind[rid[i]] == 1;
-        row0[i] = row_first[rid[i]];
 #pragma unroll
         for (int p = 0; p < NP; ++p) { I[i][p] = surface[i] ? Is[p] : 0.0; Imax[i][p] = I[i][p]; }
     }
     const int ns = ray_first[rid[0] + 1] - s0[0];        // (the same for every ray of the bundle, as are its layers and rows)
     const int32_t* lay = seg_layer + s0[0];
-    const int32_t* slot = (const int32_t*)(blk + A.off_seg_slot) + s0[0];
-    const int32_t* term_row = (const int32_t*)(blk + A.off_term_row) + ((const int32_t*)(blk + A.off_ray_terms))[rid[0]];
-    const int crossed = ((const int32_t*)(blk + A.off_ray_crossed))[rid[0]];
-    // row `row` of ray i: stored by the layer's first segment, added to afterwards (`store` is uniform over the workgroup)
-    auto put = [&](int i, long long row, int p, double v, bool store) {
-        double* o = A.jac + (row0[i] + row) * A.n + (j + p);
-        *o = store ? v : *o + v;
-    };
+    const RayRows<NP, RB> R(A, blk, rid, s0[0], j);
     auto walk = [&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
         // forward: K5e's walk, and the running maximum
@@ -4989,46 +5270,11 @@ __global__ __launch_bounds__(256) void ray_jacobian_kernel(const RayJacArgs* __r
         cur = ns > 0 ? load_points<NP>(A.abs_coef[lay[ns - 1]], j) : (vec)(0.0);
         for (int s = ns - 1; s >= 0; --s) {
             const vec nxt = s > 0 ? load_points<NP>(A.abs_coef[lay[s - 1]], j) : cur;
-            const int l = lay[s];
-            const bool store = (slot[s] & kRayRowStore) != 0;
-            const long long row_tau = 1 + (slot[s] & (kRayRowStore - 1));
-            const long long row_T = row_tau + crossed;
-            const double pbkT = A.pbkT[l], rT = A.rT[l];
             double len[RB], g[RB][NP];
 #pragma unroll
             for (int i = 0; i < RB; ++i) len[i] = seg_length[s0[i] + s];
-            double E0 = 0.0;
-            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                double dB;
-                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
-#pragma unroll
-                for (int i = 0; i < RB; ++i) {
-                    const double tau = cur[p] * len[i];
-                    const double tr = exp_neg_budget(tau);
-                    const double At = Ak[i][p] * tr;
-                    g[i][p] = fmin(fmax(Ak[i][p] * B + I[i][p], -(At * Imax[i][p])), At * B);
-                    const double a1 = Ak[i][p] * (1.0 - tr);
-                    if (active) {
-                        put(i, row_tau, p, tau * g[i][p], store);
-                        put(i, row_T, p, a1 * dB, store);
-                    }
-                    I[i][p] = I[i][p] + a1 * B;              // D_(s-1) = D_s + A_s (1 - t_s) B_s
-                    Ak[i][p] = At;                           // A_(s-1) = A_s t_s
-                }
-            }
-            if constexpr (TERMS) for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load_points<NP>(A.term_k[t], j);
-                const long long row = term_row[t];
-                if (active) {
-#pragma unroll
-                    for (int i = 0; i < RB; ++i) {
-#pragma unroll
-                        for (int p = 0; p < NP; ++p) put(i, row, p, (km[p] * len[i]) * g[i][p], store);
-                    }
-                }
-            }
+            ray_backward_step<FAST, 1, NP, RB>(A, R, s, lay[s], cur, len, active, nu, pa_n, I, Imax, Ak, g);
+            if constexpr (TERMS) ray_terms<NP, RB>(A, R, s, lay[s], len, active, g);
             cur = nxt;
         }
         // dI/dT_source = A dB(nu, source_T)/dT for a ray from the surface at source_T, else 0
@@ -5038,7 +5284,7 @@ __global__ __launch_bounds__(256) void ray_jacobian_kernel(const RayJacArgs* __r
                 double dBs = 0.0;
                 if (!A.I_surface) fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
 #pragma unroll
-                for (int i = 0; i < RB; ++i) put(i, 0, p, surface[i] && !A.I_surface ? Ak[i][p] * dBs : 0.0, true);
+                for (int i = 0; i < RB; ++i) R.put(i, 0, p, surface[i] && !A.I_surface ? Ak[i][p] * dBs : 0.0, true);
             }
         }
     };
@@ -5065,22 +5311,26 @@ __global__ __launch_bounds__(256) void ray_jacobian_kernel(const RayJacArgs* __r
 // and adds its sums to the band slots.  (3) K5d's downward pass, which ADDS its part to what the same thread stored.
 // With e == 1: Qf = 0, walk (2) contributes +-0 everywhere, I_up[0] = Is, and walks (2) and (3) are K5d's operations in
 // K5d's order - K5d's bits on its own groups of points (the one-exp Planck path starts from a thread's first point).
+// Walk 1's start and the surface are ReflectingSurfaceTurn, the turn at the top flux_top_turn, walk 3 K5d's own
+// jacobian_down_step, adding; walks 1 and 2 are this kernel's.
 template <int NP, int NA>
 __global__ __launch_bounds__(256) void surface_jacobian_kernel(const SurfaceJacArgs* __restrict__ Ap, long long lo0, long long n0,
                                                                long long lo1, long long n1, double* __restrict__ partial) {
 #pragma clang fp contract(off)
     typedef f64v<NP> vec;
-    constexpr int kSlot = 3 + 2 * kMaxLayers + kMaxJacobianTerms;
+    constexpr int kSlot = jacobian_slots(3, 1, kMaxLayers, kMaxJacobianTerms);
     __shared__ double acc[4 * kSlot];            // [wave][F_top, dT_s, de, L x ln tau, L x T, terms]
     const SurfaceJacArgs& A = *Ap;
     const int L = A.n_layers;
-    const int nv = 3 + 2 * L + A.n_terms;
+    const int nv = jacobian_slots(3, 1, L, A.n_terms);
     band_frame<NP, kSlot>(A, blockDim.x, lo0, n0, lo1, n1, partial, acc, nv, [&](auto fast_tag, long long j, bool active,
                           const double (&nu)[NP], const double (&pa_n)[NP], auto add) {
+        constexpr bool FAST = decltype(fast_tag)::value;
         // walk 1: I = Id, Dm = Dmax, Ak = Ttot;  walk 2: I = Iu, Imax, Ck = C, Dp = D', Dm, Ak = Qf;  walk 3: I = D, Imax, Ak = A
         double I[NA][NP], Imax[NA][NP], Ak[NA][NP], Ck[NA][NP], Dp[NA][NP], Dm[NA][NP];
-        auto first_down = [&](auto fast_tag, int l, vec v) {
-            constexpr bool FAST = decltype(fast_tag)::value;
+        // walk 1, downward
+        ReflectingSurfaceTurn<NP, NA>::start(A, j, I, Dm, Ak);
+        column_down<NP>(A, j, L, [&](int l, vec v) {
             const double pbkT = A.pbkT[l], depth = A.depth[l];
             double E0 = 0.0;
             if (FAST) E0 = exp_clamped(nu[0] * pbkT);
@@ -5097,19 +5347,20 @@ __global__ __launch_bounds__(256) void surface_jacobian_kernel(const SurfaceJacA
                     Ak[k][p] = Ak[k][p] * tr;
                 }
             }
-        };
-        auto up = [&](auto fast_tag, int l, vec v) {
-            constexpr bool FAST = decltype(fast_tag)::value;
+        });
+        ReflectingSurfaceTurn<NP, NA>::turn(A, j, active, nu, pa_n, I, Imax, Ak, Ck, Dp, add);
+        // walk 2, upward
+        column_up<NP>(A, j, L, [&](int l, vec v) {
             const double pbkT = A.pbkT[l], depth = A.depth[l], rT = A.rT[l];
             double E0 = 0.0;
             if (FAST) E0 = exp_clamped(nu[0] * pbkT);
-            double s_tau = 0.0, s_T = 0.0, Gd[NP];
+            double s_tau = 0.0, s_T[1] = {0.0}, Gd[NP];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const double tau = v[p] * depth;
                 double dB;
                 const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
-                double G = 0.0, gT = 0.0;
+                double G = 0.0, gT[1] = {0.0};
 #pragma unroll
                 for (int k = 0; k < NA; ++k) {
                     const double tr = exp_neg_budget(tau * A.rmu[k]);
@@ -5118,140 +5369,32 @@ __global__ __launch_bounds__(256) void surface_jacobian_kernel(const SurfaceJacA
                     const double g = fmin(fmax(Ck[k][p] * B + Dp[k][p], -(Ct * Dm[k][p])), Ct * B);
                     G = fma(A.wrmu[k], Ak[k][p] * g, G);
                     const double c1 = Ck[k][p] * (1.0 - tr);
-                    gT = fma(A.w[k], Ak[k][p] * (c1 * dB), gT);
+                    gT[0] = fma(A.w[k], Ak[k][p] * (c1 * dB), gT[0]);
                     Dp[k][p] = Dp[k][p] + c1 * B;            // D'_(l+1) = D'_l + C_l (1 - t_l) B_l
                     Ck[k][p] = Ct;                           // C_(l+1) = C_l t_l
                     // the upward leg: K5d's walk
                     I[k][p] = fold_update<FAST>(tr, I[k][p], B);
                     Imax[k][p] = fmax(Imax[k][p], I[k][p]);
                 }
-                const double dtau = tau * G;
                 Gd[p] = depth * G;
-                if (active && A.ln_tau_spec) A.ln_tau_spec[(long long)l * A.n + j + p] = dtau;
-                if (active && A.T_spec) A.T_spec[(long long)l * A.n + j + p] = gT;
-                s_tau += active ? nan_to_num(dtau) : 0.0;
-                s_T += active ? nan_to_num(gT) : 0.0;
+                jacobian_emit<1>(true, active, A, &JacArgs::T_spec, l, j, p, tau * G, gT, s_tau, s_T);
             }
             add(3 + l, s_tau);
-            add(3 + L + l, s_T);
+            add(3 + L + l, s_T[0]);
             jacobian_terms<NP>(A, l, j, active, Gd, 3 + 2 * L, add);
-        };
-        auto down = [&](auto fast_tag, int l, vec v) {
-            constexpr bool FAST = decltype(fast_tag)::value;
-            const double pbkT = A.pbkT[l], depth = A.depth[l], rT = A.rT[l];
-            double E0 = 0.0;
-            if (FAST) E0 = exp_clamped(nu[0] * pbkT);
-            double s_tau = 0.0, s_T = 0.0, Gd[NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double tau = v[p] * depth;
-                double dB;
-                const double B = fold_planck<FAST, true>(p == 0, nu[p], nu[0], pa_n[p], pbkT, E0, rT, &dB);
-                double G = 0.0, gT = 0.0;
-#pragma unroll
-                for (int k = 0; k < NA; ++k) {
-                    const double tr = exp_neg_budget(tau * A.rmu[k]);
-                    const double At = Ak[k][p] * tr;
-                    const double g = fmin(fmax(Ak[k][p] * B + I[k][p], -(At * Imax[k][p])), At * B);
-                    G = fma(A.wrmu[k], g, G);
-                    const double a1 = Ak[k][p] * (1.0 - tr);
-                    gT = fma(A.w[k], a1 * dB, gT);
-                    I[k][p] = I[k][p] + a1 * B;              // D_(l-1) = D_l + A_l (1 - t_l) B_l
-                    Ak[k][p] = At;                           // A_(l-1) = A_l t_l
-                }
-                const double dtau = tau * G;
-                Gd[p] = depth * G;
-                // (what walk 2 stored here, this thread stored)
-                if (active && A.ln_tau_spec) {
-                    double* o = A.ln_tau_spec + (long long)l * A.n + j + p;
-                    *o = *o + dtau;
-                }
-                if (active && A.T_spec) {
-                    double* o = A.T_spec + (long long)l * A.n + j + p;
-                    *o = *o + gT;
-                }
-                s_tau += active ? nan_to_num(dtau) : 0.0;
-                s_T += active ? nan_to_num(gT) : 0.0;
-            }
-            add(3 + l, s_tau);
-            add(3 + L + l, s_T);
-            jacobian_terms<NP>(A, l, j, active, Gd, 3 + 2 * L, add);
-        };
-        // walk 1, downward: I_L = I_top or 0
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const double It = A.I_top ? A.I_top[j + p] : 0.0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
-        }
-        vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-        for (int l = L - 1; l >= 0; --l) {
-            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-            first_down(fast_tag, l, cur);
-            cur = nxt;
-        }
-        // the surface: dF/dT_s = e sum_k W_k Ttot_k dBs/dT, dF/de = sum_k W_k Ttot_k (Is - R_k); then the state of walk 2
-        double s_Ts = 0.0, s_e = 0.0;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
-            double dBs = 0.0;
-            const double Is = A.I_surface ? A.I_surface[j + p]
-                                          : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
-                                                                     A.r_surface_T, &dBs);
-            const double edBs = e * dBs;
-            const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
-            const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
-            const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
-            const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
-            if (active && A.e_spec) A.e_spec[j + p] = de;
-            s_Ts += active ? nan_to_num(dTs) : 0.0;
-            s_e += active ? nan_to_num(de) : 0.0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) {
-                const double D = I[k][p];
-                I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
-                Imax[k][p] = I[k][p];
-                Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
-                Ck[k][p] = 1.0;
-                Dp[k][p] = -D;
-            }
-        }
-        add(1, s_Ts);
-        add(2, s_e);
-        // walk 2, upward
-        cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
-        for (int l = 0; l < L; ++l) {
-            const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
-            up(fast_tag, l, cur);
-            cur = nxt;
-        }
-        // F_top; then I becomes D = -I_top and A = 1
-        double s = 0.0;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
-        }
-        add(0, s);
+        });
+        flux_top_turn<NP, NA>(A, active, I, Ak, add);
         // walk 3, downward: K5d's
-        cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-        for (int l = L - 1; l >= 0; --l) {
-            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-            down(fast_tag, l, cur);
-            cur = nxt;
-        }
+        column_down<NP>(A, j, L, [&](int l, vec v) {
+            jacobian_down_step<FAST, 3, false, NP, NA>(A, L, l, v, j, active, nu, pa_n, I, Imax, Ak, add);
+        });
     });
 }
 
 // Rays: K5f's kernel with K5g's surface in the path.  A marker (layer kRaySurfaceMarker) is part of the bundle's common
-// sequence, so the branch on it is uniform over the workgroup.  Forward: I <- e Is + (1 - e) I at a marker, as
-// ray_surface_kernel, Imax takes the result, and dI/de is carried along: S <- t S per segment, S <- (Is - I) + (1 - e) S at a
-// marker (the backward identity would divide by 1 - e); a ray from the surface starts with I = e Is and S = Is.  Backward: a
-// marker emits, D += A e Is, adds A e dBs/dT to the ray's row 0 (the first marker met stores, as a layer's rows are stored,
-// the source at the very end adds or stores) and then dims what lies before it, A <- A (1 - e).  Rows: [dT_source, de, K5f's].
-// With e == 1 and no marker every operation on I, Imax, D and A is K5f's.
+// sequence, so the branch on it is uniform over the workgroup.  What happens at a marker, at the start and between and
+// after the walks is RaySurfaceWalk's; the backward step through a real segment is K5f's own ray_backward_step and
+// ray_terms.  Rows: [dT_source, de, K5f's].  With e == 1 and no marker every operation on I, Imax, D and A is K5f's.
 template <int NP, int RB, bool TERMS>
 __global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurfaceJacArgs* __restrict__ Ap, long long lo0,
                                                                    long long n0, long long lo1, long long n1, int order_first) {
@@ -5259,134 +5402,28 @@ __global__ __launch_bounds__(256) void ray_surface_jacobian_kernel(const RaySurf
     typedef f64v<NP> vec;
     const RaySurfaceJacArgs& A = *Ap;
     const RayFrame<NP, RB, true, RaySurfaceJacArgs> F(Ap, blockDim.x, lo0, n0, lo1, n1, order_first);
-    const long long* row_first = (const long long*)(F.blk + A.off_row_first);
-    double I[RB][NP], Imax[RB][NP], Ak[RB][NP];          // (Ak: S = dI/de on the forward walk)
-    long long row0[RB];                                   // the ray's first row
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        row0[i] = row_first[F.rid[i]];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            I[i][p] = F.surface[i] ? surface_leaving(F.em[p], F.Is[p], 0.0) : 0.0;
-            Imax[i][p] = I[i][p];
-            Ak[i][p] = F.surface[i] ? F.Is[p] : 0.0;
-        }
-    }
-    const int32_t* slot = (const int32_t*)(F.blk + A.off_seg_slot) + F.s0[0];
-    const int32_t* term_row = (const int32_t*)(F.blk + A.off_term_row) + ((const int32_t*)(F.blk + A.off_ray_terms))[F.rid[0]];
-    const int crossed = ((const int32_t*)(F.blk + A.off_ray_crossed))[F.rid[0]];
-    auto put = [&](int i, long long row, int p, double v, bool store) {
-        double* o = A.jac + (row0[i] + row) * A.n + (F.j + p);
-        *o = store ? v : *o + v;
-    };
-    // e dB(nu, source_T)/dT at point p (0 when the source is a given spectrum)
-    auto source_dT = [&](int p) {
-        double dBs = 0.0;
-        if (!A.I_surface) fold_planck<false, true>(false, F.nu[p], F.nu[p], F.pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
-        return F.em[p] * dBs;
-    };
+    RaySurfaceWalk<NP, RB, RaySurfaceJacArgs> W(F);
     F.dispatch([&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
         // forward: ray_surface_kernel's walk, the running maximum and dI/de
-        F.forward([&] {
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-#pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    Ak[i][p] = (F.Is[p] - I[i][p]) + (1.0 - F.em[p]) * Ak[i][p];
-                    I[i][p] = surface_leaving(F.em[p], F.Is[p], I[i][p]);
-                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
-                }
-            }
-        }, [&](int s, vec cur, const double (&len)[RB]) {
+        F.forward([&] { W.forward_marker(); }, [&](int s, vec cur, const double (&len)[RB]) {
             transport_step<FAST, NP>(F.nu, F.pa_n, A.pbkT[F.lay[s]], cur, [&](int p, double kp, double B) {
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
                     const double tr = exp_neg_budget(kp * len[i]);
-                    I[i][p] = fold_update<FAST>(tr, I[i][p], B);
-                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
-                    Ak[i][p] = tr * Ak[i][p];
+                    W.I[i][p] = fold_update<FAST>(tr, W.I[i][p], B);
+                    W.Imax[i][p] = fmax(W.Imax[i][p], W.I[i][p]);
+                    W.Ak[i][p] = tr * W.Ak[i][p];
                 }
             });
         });
-        // the radiance and dI/de; then I becomes D = -I_final and A = 1
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                if (F.active && A.radiance) A.radiance[(long long)F.rid[i] * A.n + F.j + p] = I[i][p];
-                if (F.active) put(i, 1, p, Ak[i][p], true);
-                I[i][p] = -I[i][p];
-                Ak[i][p] = 1.0;
-            }
-        }
-        // backward
-        bool row0_stored = false;
-        F.backward([&] {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double edBs = A.I_surface ? 0.0 : source_dT(p);
-                const double eIs = F.em[p] * F.Is[p];
-#pragma unroll
-                for (int i = 0; i < RB; ++i) {
-                    if (F.active && !A.I_surface) put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
-                    I[i][p] = I[i][p] + Ak[i][p] * eIs;
-                    Ak[i][p] = Ak[i][p] * (1.0 - F.em[p]);
-                }
-            }
-            if (!A.I_surface) row0_stored = true;
-        }, [&](int s, vec cur, const double (&len)[RB]) {
-            const int l = F.lay[s];
-            const bool store = (slot[s] & kRayRowStore) != 0;
-            const long long row_tau = 2 + (slot[s] & (kRayRowStore - 1));
-            const long long row_T = row_tau + crossed;
-            const double pbkT = A.pbkT[l], rT = A.rT[l];
+        W.turn();
+        F.backward([&] { W.backward_marker(); }, [&](int s, vec cur, const double (&len)[RB]) {
             double g[RB][NP];
-            double E0 = 0.0;
-            if (FAST) E0 = exp_clamped(F.nu[0] * pbkT);
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                double dB;
-                const double B = fold_planck<FAST, true>(p == 0, F.nu[p], F.nu[0], F.pa_n[p], pbkT, E0, rT, &dB);
-#pragma unroll
-                for (int i = 0; i < RB; ++i) {
-                    const double tau = cur[p] * len[i];
-                    const double tr = exp_neg_budget(tau);
-                    const double At = Ak[i][p] * tr;
-                    g[i][p] = fmin(fmax(Ak[i][p] * B + I[i][p], -(At * Imax[i][p])), At * B);
-                    const double a1 = Ak[i][p] * (1.0 - tr);
-                    if (F.active) {
-                        put(i, row_tau, p, tau * g[i][p], store);
-                        put(i, row_T, p, a1 * dB, store);
-                    }
-                    I[i][p] = I[i][p] + a1 * B;              // D_(s-1) = D_s + A_s (1 - t_s) B_s
-                    Ak[i][p] = At;                           // A_(s-1) = A_s t_s
-                }
-            }
-            if constexpr (TERMS) for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load_points<NP>(A.term_k[t], F.j);
-                const long long row = term_row[t];
-                if (F.active) {
-#pragma unroll
-                    for (int i = 0; i < RB; ++i) {
-#pragma unroll
-                        for (int p = 0; p < NP; ++p) put(i, row, p, (km[p] * len[i]) * g[i][p], store);
-                    }
-                }
-            }
+            ray_backward_step<FAST, 2, NP, RB>(A, W.R, s, F.lay[s], cur, len, F.active, F.nu, F.pa_n, W.I, W.Imax, W.Ak, g);
+            if constexpr (TERMS) ray_terms<NP, RB>(A, W.R, s, F.lay[s], len, F.active, g);
         });
-        // the source's part of dI/dT_source: A_0 e dBs/dT for a ray from the surface at source_T
-        if (F.active) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double edBs = source_dT(p);
-#pragma unroll
-                for (int i = 0; i < RB; ++i) {
-                    const double v = F.surface[i] && !A.I_surface ? Ak[i][p] * edBs : 0.0;
-                    if (!row0_stored || F.surface[i]) put(i, 0, p, v, !row0_stored);
-                }
-            }
-        }
+        W.source_row();
     });
 }
 
@@ -5412,48 +5449,58 @@ __device__ __forceinline__ void linear_planck_pair(bool first, double nu, double
     Bb = fold_planck<FAST, true>(first, nu, nu0, pa_n, pbkT_b, Eb0, rT_b, &dBb);
 }
 
+// What walks 2 and 3 of linear_jacobian_kernel need of layer l before its points: the layer's scalars, bottom and top edge,
+// and on the fast path the thread's two exps; then per point the two Planck values with their temperature derivatives
+template <bool FAST>
+struct LinearLayer {
+    double pbkT, pbkT_top, depth, rT, rT_top, E0, E0_top;
+    __device__ __forceinline__ LinearLayer(const LinearJacArgs& A, int l, double nu0)
+        : pbkT(A.pbkT[l]), pbkT_top(A.pbkT_top[l]), depth(A.depth[l]), rT(A.rT[l]), rT_top(A.rT_top[l]), E0(0.0), E0_top(0.0) {
+#pragma clang fp contract(off)
+        if (FAST) {
+            E0 = exp_clamped(nu0 * pbkT);
+            E0_top = exp_clamped(nu0 * pbkT_top);
+        }
+    }
+    __device__ __forceinline__ void planck(bool first, double nu, double nu0, double pa_n, double& Bbot, double& Btop,
+                                           double& dBbot, double& dBtop) const {
+        linear_planck_pair<FAST>(first, nu, nu0, pa_n, pbkT, pbkT_top, E0, E0_top, rT, rT_top, Bbot, Btop, dBbot, dBtop);
+    }
+};
+
 // Column: surface_jacobian_kernel's three walks.  Walk 1 is linear_flux_kernel's downward walk (entered at the top edge,
-// left at the bottom edge) with Dmax and Ttot; the surface is K5h's; walk 2 carries the upward leg (entered at the bottom
-// edge) and the mirrored downward leg, walk 3 the upward leg's derivatives.  Both later walks add to the band slots; of the
-// spectra walk 2 stores and walk 3 adds to what the same thread stored.  Band slots: [F, dT_s, de, L x ln tau, 2 L x T_edge
-// (bottom, top), terms].
+// left at the bottom edge) with Dmax and Ttot; the surface is K5h's (ReflectingSurfaceTurn, as is walk 1's start); walk 2
+// carries the upward leg (entered at the bottom edge) and the mirrored downward leg, walk 3 the upward leg's derivatives.
+// Both later walks add to the band slots; of the spectra walk 2 stores and walk 3 adds to what the same thread stored
+// (jacobian_emit with two temperature rows).  Band slots: [F, dT_s, de, L x ln tau, 2 L x T_edge (bottom, top), terms].
 // Points per thread: K5h's - 4 with one and two angles, 2 beyond.  The state is its six values per angle and point, and a
 // step keeps four Planck values, g, g' and h beside them: 256 VGPRs and up to 202 AGPRs at one wave per SIMD, no scratch
 // (DESIGN.md "K5j").
-template <int NA> constexpr int linear_jacobian_np() { return NA <= 2 ? 4 : 2; }
 template <int NP, int NA>
 __global__ __launch_bounds__(256) void linear_jacobian_kernel(const LinearJacArgs* __restrict__ Ap, long long lo0, long long n0,
                                                               long long lo1, long long n1, double* __restrict__ partial) {
 #pragma clang fp contract(off)
     typedef f64v<NP> vec;
-    constexpr int kSlot = 3 + 3 * kMaxLayers + kMaxJacobianTerms;
+    constexpr int kSlot = jacobian_slots(3, 2, kMaxLayers, kMaxJacobianTerms);
     __shared__ double acc[4 * kSlot];            // [wave][F_top, dT_s, de, L x ln tau, 2 L x T_edge, terms]
     const LinearJacArgs& A = *Ap;
     const int L = A.n_layers;
-    const int nv = 3 + 3 * L + A.n_terms;
+    const int nv = jacobian_slots(3, 2, L, A.n_terms);
     band_frame<NP, kSlot>(A, blockDim.x, lo0, n0, lo1, n1, partial, acc, nv, [&](auto fast_tag, long long j, bool active,
                           const double (&nu)[NP], const double (&pa_n)[NP], auto add) __attribute__((always_inline)) {
+        constexpr bool FAST = decltype(fast_tag)::value;
         // walk 1: I = Id, Dm = Dmax, Ak = Ttot;  walk 2: I = Iu, Imax, Ck = C, Dp = D', Dm, Ak = Qf;  walk 3: I = D, Imax, Ak = A
         double I[NA][NP], Imax[NA][NP], Ak[NA][NP], Ck[NA][NP], Dp[NA][NP], Dm[NA][NP];
-        // one point's values of a layer into the spectra (walk 2 stores, walk 3 adds) and the thread's sums
-        auto emit = [&](bool store, int l, int p, double dtau, double gbot, double gtop, double& s_tau, double& s_bot,
-                        double& s_top) __attribute__((always_inline)) {
-            if (active && A.ln_tau_spec) {
-                double* o = A.ln_tau_spec + (long long)l * A.n + j + p;
-                *o = store ? dtau : *o + dtau;
-            }
-            if (active && A.T_edge_spec) {
-                double* o = A.T_edge_spec + (long long)(2 * l) * A.n + j + p;
-                *o = store ? gbot : *o + gbot;
-                o += A.n;
-                *o = store ? gtop : *o + gtop;
-            }
-            s_tau += active ? nan_to_num(dtau) : 0.0;
-            s_bot += active ? nan_to_num(gbot) : 0.0;
-            s_top += active ? nan_to_num(gtop) : 0.0;
+        // a layer's sums into its band slots, and its terms
+        auto sums = [&](int l, double s_tau, const double (&s_T)[2], const double (&Gd)[NP]) __attribute__((always_inline)) {
+            add(3 + l, s_tau);
+            add(3 + L + 2 * l, s_T[0]);
+            add(3 + L + 2 * l + 1, s_T[1]);
+            jacobian_terms<NP>(A, l, j, active, Gd, 3 + 3 * L, add);
         };
-        auto first_down = [&](auto fast_tag, int l, vec v) __attribute__((always_inline)) {
-            constexpr bool FAST = decltype(fast_tag)::value;
+        // walk 1, downward
+        ReflectingSurfaceTurn<NP, NA>::start(A, j, I, Dm, Ak);
+        column_down<NP>(A, j, L, [&](int l, vec v) __attribute__((always_inline)) {
             const double depth = A.depth[l];
             linear_step<FAST, NP>(nu, pa_n, A.pbkT_top[l], A.pbkT[l], v, [&](int p, double kp, double Ba, double dB) __attribute__((always_inline)) {
                 const double tau = kp * depth;
@@ -5466,23 +5513,19 @@ __global__ __launch_bounds__(256) void linear_jacobian_kernel(const LinearJacArg
                     Ak[k][p] = Ak[k][p] * tr;
                 }
             });
-        };
-        auto up = [&](auto fast_tag, int l, vec v) __attribute__((always_inline)) {
-            constexpr bool FAST = decltype(fast_tag)::value;
-            const double pbkT = A.pbkT[l], pbkT_top = A.pbkT_top[l], depth = A.depth[l], rT = A.rT[l], rT_top = A.rT_top[l];
-            double E0 = 0.0, E0_top = 0.0;
-            if (FAST) {
-                E0 = exp_clamped(nu[0] * pbkT);
-                E0_top = exp_clamped(nu[0] * pbkT_top);
-            }
-            double s_tau = 0.0, s_bot = 0.0, s_top = 0.0, Gd[NP];
+        });
+        ReflectingSurfaceTurn<NP, NA>::turn(A, j, active, nu, pa_n, I, Imax, Ak, Ck, Dp, add);
+        // walk 2, upward; (gT, s_T: bottom edge, top edge)
+        column_up<NP>(A, j, L, [&](int l, vec v) __attribute__((always_inline)) {
+            const LinearLayer<FAST> Y(A, l, nu[0]);
+            double s_tau = 0.0, s_T[2] = {0.0, 0.0}, Gd[NP];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                const double tau = v[p] * depth;
+                const double tau = v[p] * Y.depth;
                 double Bbot, Btop, dBbot, dBtop;
-                linear_planck_pair<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT, pbkT_top, E0, E0_top, rT, rT_top, Bbot, Btop, dBbot, dBtop);
+                Y.planck(p == 0, nu[p], nu[0], pa_n[p], Bbot, Btop, dBbot, dBtop);
                 const double dBu = Btop - Bbot, dBd = Bbot - Btop;
-                double G = 0.0, gbot = 0.0, gtop = 0.0;
+                double G = 0.0, gT[2] = {0.0, 0.0};
 #pragma unroll
                 for (int k = 0; k < NA; ++k) {
                     const double x = tau * A.rmu[k];
@@ -5494,38 +5537,31 @@ __global__ __launch_bounds__(256) void linear_jacobian_kernel(const LinearJacArg
                     const double Ct = Ck[k][p] * tr;
                     const double gd = fmin(fmax(Ck[k][p] * (Btop + g * dBd) + Dp[k][p], -(Ct * Dm[k][p])), Ct * Btop);
                     G = fma(A.wrmu[k], Ak[k][p] * (gd + Ck[k][p] * (dg * dBd)), G);
-                    gtop = fma(A.w[k], Ak[k][p] * ((Ck[k][p] * h) * dBtop), gtop);
-                    gbot = fma(A.w[k], Ak[k][p] * ((Ck[k][p] * g) * dBbot), gbot);
+                    gT[1] = fma(A.w[k], Ak[k][p] * ((Ck[k][p] * h) * dBtop), gT[1]);
+                    gT[0] = fma(A.w[k], Ak[k][p] * ((Ck[k][p] * g) * dBbot), gT[0]);
                     Dp[k][p] = Dp[k][p] + Ck[k][p] * ((1.0 - tr) * Btop + g * dBd);      // D' <- D' + C (the step's emission)
                     Ck[k][p] = Ct;
                     // the upward leg: linear_flux_kernel's step
                     I[k][p] = linear_update<FAST>(x, tr, I[k][p], Bbot, dBu);
                     Imax[k][p] = fmax(Imax[k][p], I[k][p]);
                 }
-                Gd[p] = depth * G;
-                emit(true, l, p, tau * G, gbot, gtop, s_tau, s_bot, s_top);
+                Gd[p] = Y.depth * G;
+                jacobian_emit<2>(true, active, A, &LinearJacArgs::T_edge_spec, l, j, p, tau * G, gT, s_tau, s_T);
             }
-            add(3 + l, s_tau);
-            add(3 + L + 2 * l, s_bot);
-            add(3 + L + 2 * l + 1, s_top);
-            jacobian_terms<NP>(A, l, j, active, Gd, 3 + 3 * L, add);
-        };
-        auto down = [&](auto fast_tag, int l, vec v) __attribute__((always_inline)) {
-            constexpr bool FAST = decltype(fast_tag)::value;
-            const double pbkT = A.pbkT[l], pbkT_top = A.pbkT_top[l], depth = A.depth[l], rT = A.rT[l], rT_top = A.rT_top[l];
-            double E0 = 0.0, E0_top = 0.0;
-            if (FAST) {
-                E0 = exp_clamped(nu[0] * pbkT);
-                E0_top = exp_clamped(nu[0] * pbkT_top);
-            }
-            double s_tau = 0.0, s_bot = 0.0, s_top = 0.0, Gd[NP];
+            sums(l, s_tau, s_T, Gd);
+        });
+        flux_top_turn<NP, NA>(A, active, I, Ak, add);
+        // walk 3, downward
+        column_down<NP>(A, j, L, [&](int l, vec v) __attribute__((always_inline)) {
+            const LinearLayer<FAST> Y(A, l, nu[0]);
+            double s_tau = 0.0, s_T[2] = {0.0, 0.0}, Gd[NP];
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                const double tau = v[p] * depth;
+                const double tau = v[p] * Y.depth;
                 double Bbot, Btop, dBbot, dBtop;
-                linear_planck_pair<FAST>(p == 0, nu[p], nu[0], pa_n[p], pbkT, pbkT_top, E0, E0_top, rT, rT_top, Bbot, Btop, dBbot, dBtop);
+                Y.planck(p == 0, nu[p], nu[0], pa_n[p], Bbot, Btop, dBbot, dBtop);
                 const double dBu = Btop - Bbot;
-                double G = 0.0, gbot = 0.0, gtop = 0.0;
+                double G = 0.0, gT[2] = {0.0, 0.0};
 #pragma unroll
                 for (int k = 0; k < NA; ++k) {
                     const double x = tau * A.rmu[k];
@@ -5536,91 +5572,23 @@ __global__ __launch_bounds__(256) void linear_jacobian_kernel(const LinearJacArg
                     const double At = Ak[k][p] * tr;
                     const double gu = fmin(fmax(Ak[k][p] * (Bbot + g * dBu) + I[k][p], -(At * Imax[k][p])), At * Bbot);
                     G = fma(A.wrmu[k], gu + Ak[k][p] * (dg * dBu), G);
-                    gbot = fma(A.w[k], (Ak[k][p] * h) * dBbot, gbot);
-                    gtop = fma(A.w[k], (Ak[k][p] * g) * dBtop, gtop);
+                    gT[0] = fma(A.w[k], (Ak[k][p] * h) * dBbot, gT[0]);
+                    gT[1] = fma(A.w[k], (Ak[k][p] * g) * dBtop, gT[1]);
                     I[k][p] = I[k][p] + Ak[k][p] * ((1.0 - tr) * Bbot + g * dBu);        // D <- D + A (the step's emission)
                     Ak[k][p] = At;
                 }
-                Gd[p] = depth * G;
-                emit(false, l, p, tau * G, gbot, gtop, s_tau, s_bot, s_top);
+                Gd[p] = Y.depth * G;
+                jacobian_emit<2>(false, active, A, &LinearJacArgs::T_edge_spec, l, j, p, tau * G, gT, s_tau, s_T);
             }
-            add(3 + l, s_tau);
-            add(3 + L + 2 * l, s_bot);
-            add(3 + L + 2 * l + 1, s_top);
-            jacobian_terms<NP>(A, l, j, active, Gd, 3 + 3 * L, add);
-        };
-        // walk 1, downward: I_L = I_top or 0
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const double It = A.I_top ? A.I_top[j + p] : 0.0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) { I[k][p] = It; Dm[k][p] = It; Ak[k][p] = 1.0; }
-        }
-        vec cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-        for (int l = L - 1; l >= 0; --l) {
-            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-            first_down(fast_tag, l, cur);
-            cur = nxt;
-        }
-        // the surface: K5h's
-        double s_Ts = 0.0, s_e = 0.0;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const double e = A.emissivity ? A.emissivity[j + p] : A.emissivity_all;
-            double dBs = 0.0;
-            const double Is = A.I_surface ? A.I_surface[j + p]
-                                          : fold_planck<false, true>(false, nu[p], nu[p], pa_n[p], A.pbk_surface, 0.0,
-                                                                     A.r_surface_T, &dBs);
-            const double edBs = e * dBs;
-            const double diffuse = angle_sum<NA>(A, [&](int k) { return I[k][p]; }) / A.w_sum;
-            const double Tdiffuse = angle_sum<NA>(A, [&](int k) { return Ak[k][p]; }) / A.w_sum;
-            const double dTs = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * edBs; });
-            const double de = angle_sum<NA>(A, [&](int k) { return Ak[k][p] * (Is - (A.reflection == 0 ? diffuse : I[k][p])); });
-            if (active && A.e_spec) A.e_spec[j + p] = de;
-            s_Ts += active ? nan_to_num(dTs) : 0.0;
-            s_e += active ? nan_to_num(de) : 0.0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) {
-                const double D = I[k][p];
-                I[k][p] = surface_leaving(e, Is, A.reflection == 0 ? diffuse : D);
-                Imax[k][p] = I[k][p];
-                Ak[k][p] = (1.0 - e) * (A.reflection == 0 ? Tdiffuse : Ak[k][p]);
-                Ck[k][p] = 1.0;
-                Dp[k][p] = -D;
-            }
-        }
-        add(1, s_Ts);
-        add(2, s_e);
-        // walk 2, upward
-        cur = L > 0 ? load_points<NP>(A.abs_coef[0], j) : (vec)(0.0);
-        for (int l = 0; l < L; ++l) {
-            const vec nxt = l + 1 < L ? load_points<NP>(A.abs_coef[l + 1], j) : cur;
-            up(fast_tag, l, cur);
-            cur = nxt;
-        }
-        // F_top; then I becomes D = -I_top and A = 1
-        double s = 0.0;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            s += active ? nan_to_num(angle_sum<NA>(A, [&](int k) { return I[k][p]; })) : 0.0;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) { I[k][p] = -I[k][p]; Ak[k][p] = 1.0; }
-        }
-        add(0, s);
-        // walk 3, downward
-        cur = L > 0 ? load_points<NP>(A.abs_coef[L - 1], j) : (vec)(0.0);
-        for (int l = L - 1; l >= 0; --l) {
-            const vec nxt = l > 0 ? load_points<NP>(A.abs_coef[l - 1], j) : cur;
-            down(fast_tag, l, cur);
-            cur = nxt;
-        }
+            sums(l, s_tau, s_T, Gd);
+        });
     });
 }
 
-// Rays: ray_surface_jacobian_kernel's walks with linear_ray_kernel's step.  Forward every operation on I is
+// Rays: ray_surface_jacobian_kernel's walks (RaySurfaceWalk) with linear_ray_kernel's step.  Forward every operation on I is
 // linear_ray_kernel's, on the same groups of points, so `radiance` is lbl_ray_radiance_linear_dev's bit for bit; Imax and
 // dI/de are carried as K5h carries them.  Backward a real segment stores its own two temperature rows (once, never added
-// to: seg_Trow names them) and stores or adds to its layer's ln tau row and term rows as K5f's do.
+// to: seg_Trow names them) and stores or adds to its layer's ln tau row and term rows (ray_terms) as K5f's do.
 // Rows: [dT_source, de, c x d ln tau, (dTa, dTb) per real segment in order of travel, terms].
 template <int NP, int RB>
 __global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRayJacArgs* __restrict__ Ap, long long lo0,
@@ -5629,89 +5597,29 @@ __global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRa
     typedef f64v<NP> vec;
     const LinearRayJacArgs& A = *Ap;
     const RayFrame<NP, RB, true, LinearRayJacArgs> F(Ap, blockDim.x, lo0, n0, lo1, n1, order_first);
-    const long long* row_first = (const long long*)(F.blk + A.off_row_first);
-    double I[RB][NP], Imax[RB][NP], Ak[RB][NP];          // (Ak: S = dI/de on the forward walk)
-    long long row0[RB];                                   // the ray's first row
-#pragma unroll
-    for (int i = 0; i < RB; ++i) {
-        row0[i] = row_first[F.rid[i]];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            I[i][p] = F.surface[i] ? surface_leaving(F.em[p], F.Is[p], 0.0) : 0.0;
-            Imax[i][p] = I[i][p];
-            Ak[i][p] = F.surface[i] ? F.Is[p] : 0.0;
-        }
-    }
+    RaySurfaceWalk<NP, RB, LinearRayJacArgs> W(F);
     const double* pbk = (const double*)(F.blk + A.off_seg_pbkT) + 2 * (long long)F.s0[0];
     const double* srT = (const double*)(F.blk + A.off_seg_rT) + 2 * (long long)F.s0[0];
-    const int32_t* slot = (const int32_t*)(F.blk + A.off_seg_slot) + F.s0[0];
     const int32_t* Trow = (const int32_t*)(F.blk + A.off_seg_Trow) + F.s0[0];
-    const int32_t* term_row = (const int32_t*)(F.blk + A.off_term_row) + ((const int32_t*)(F.blk + A.off_ray_terms))[F.rid[0]];
-    auto put = [&](int i, long long row, int p, double v, bool store) {
-        double* o = A.jac + (row0[i] + row) * A.n + (F.j + p);
-        *o = store ? v : *o + v;
-    };
-    // e dB(nu, source_T)/dT at point p (0 when the source is a given spectrum)
-    auto source_dT = [&](int p) {
-        double dBs = 0.0;
-        if (!A.I_surface) fold_planck<false, true>(false, F.nu[p], F.nu[p], F.pa_n[p], A.pbk_surface, 0.0, A.r_source_T, &dBs);
-        return F.em[p] * dBs;
-    };
     F.dispatch([&](auto fast_tag) {
         constexpr bool FAST = decltype(fast_tag)::value;
         // forward: linear_ray_kernel's walk, the running maximum and dI/de
-        F.forward([&] {
-#pragma unroll
-            for (int i = 0; i < RB; ++i) {
-#pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    Ak[i][p] = (F.Is[p] - I[i][p]) + (1.0 - F.em[p]) * Ak[i][p];
-                    I[i][p] = surface_leaving(F.em[p], F.Is[p], I[i][p]);
-                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
-                }
-            }
-        }, [&](int s, vec cur, const double (&len)[RB]) {
+        F.forward([&] { W.forward_marker(); }, [&](int s, vec cur, const double (&len)[RB]) {
             linear_step<FAST, NP>(F.nu, F.pa_n, pbk[2 * s], pbk[2 * s + 1], cur, [&](int p, double kp, double Ba, double dB) {
 #pragma unroll
                 for (int i = 0; i < RB; ++i) {
                     const double tau = kp * len[i];
                     const double tr = exp_neg_budget(tau);
-                    I[i][p] = linear_update<FAST>(tau, tr, I[i][p], Ba, dB);
-                    Imax[i][p] = fmax(Imax[i][p], I[i][p]);
-                    Ak[i][p] = tr * Ak[i][p];
+                    W.I[i][p] = linear_update<FAST>(tau, tr, W.I[i][p], Ba, dB);
+                    W.Imax[i][p] = fmax(W.Imax[i][p], W.I[i][p]);
+                    W.Ak[i][p] = tr * W.Ak[i][p];
                 }
             });
         });
-        // the radiance and dI/de; then I becomes D = -I_final and A = 1
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                if (F.active && A.radiance) A.radiance[(long long)F.rid[i] * A.n + F.j + p] = I[i][p];
-                if (F.active) put(i, 1, p, Ak[i][p], true);
-                I[i][p] = -I[i][p];
-                Ak[i][p] = 1.0;
-            }
-        }
-        // backward
-        bool row0_stored = false;
-        F.backward([&] {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double edBs = A.I_surface ? 0.0 : source_dT(p);
-                const double eIs = F.em[p] * F.Is[p];
-#pragma unroll
-                for (int i = 0; i < RB; ++i) {
-                    if (F.active && !A.I_surface) put(i, 0, p, Ak[i][p] * edBs, !row0_stored);
-                    I[i][p] = I[i][p] + Ak[i][p] * eIs;
-                    Ak[i][p] = Ak[i][p] * (1.0 - F.em[p]);
-                }
-            }
-            if (!A.I_surface) row0_stored = true;
-        }, [&](int s, vec cur, const double (&len)[RB]) {
-            const int l = F.lay[s];
-            const bool store = (slot[s] & kRayRowStore) != 0;
-            const long long row_tau = 2 + (slot[s] & (kRayRowStore - 1));
+        W.turn();
+        F.backward([&] { W.backward_marker(); }, [&](int s, vec cur, const double (&len)[RB]) {
+            const bool store = W.R.stores(s);
+            const long long row_tau = 2 + W.R.rank(s);
             const long long row_Ta = Trow[s];
             const double pbkT_a = pbk[2 * s], pbkT_b = pbk[2 * s + 1], rT_a = srT[2 * s], rT_b = srT[2 * s + 1];
             double G[RB][NP];
@@ -5731,42 +5639,21 @@ __global__ __launch_bounds__(256) void ray_linear_jacobian_kernel(const LinearRa
                     const double tr = exp_neg_budget(tau);
                     const double g = linear_source_g(tau, tr);
                     const double dg = linear_source_dg(tau, tr);
-                    const double At = Ak[i][p] * tr;
-                    const double gc = fmin(fmax(Ak[i][p] * (Ba + g * dB) + I[i][p], -(At * Imax[i][p])), At * Ba);
-                    G[i][p] = gc + Ak[i][p] * (dg * dB);
+                    const double At = W.Ak[i][p] * tr;
+                    const double gc = fmin(fmax(W.Ak[i][p] * (Ba + g * dB) + W.I[i][p], -(At * W.Imax[i][p])), At * Ba);
+                    G[i][p] = gc + W.Ak[i][p] * (dg * dB);
                     if (F.active) {
-                        put(i, row_tau, p, tau * G[i][p], store);
-                        put(i, row_Ta, p, (Ak[i][p] * (tau * dg)) * dBa, true);
-                        put(i, row_Ta + 1, p, (Ak[i][p] * g) * dBb, true);
+                        W.R.put(i, row_tau, p, tau * G[i][p], store);
+                        W.R.put(i, row_Ta, p, (W.Ak[i][p] * (tau * dg)) * dBa, true);
+                        W.R.put(i, row_Ta + 1, p, (W.Ak[i][p] * g) * dBb, true);
                     }
-                    I[i][p] = I[i][p] + Ak[i][p] * ((1.0 - tr) * Ba + g * dB);           // D <- D + A (the step's emission)
-                    Ak[i][p] = At;
+                    W.I[i][p] = W.I[i][p] + W.Ak[i][p] * ((1.0 - tr) * Ba + g * dB);     // D <- D + A (the step's emission)
+                    W.Ak[i][p] = At;
                 }
             }
-            for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
-                const vec km = load_points<NP>(A.term_k[t], F.j);
-                const long long row = term_row[t];
-                if (F.active) {
-#pragma unroll
-                    for (int i = 0; i < RB; ++i) {
-#pragma unroll
-                        for (int p = 0; p < NP; ++p) put(i, row, p, (km[p] * len[i]) * G[i][p], store);
-                    }
-                }
-            }
+            ray_terms<NP, RB>(A, W.R, s, F.lay[s], len, F.active, G);
         });
-        // the source's part of dI/dT_source: A_0 e dBs/dT for a ray from the surface at source_T
-        if (F.active) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const double edBs = source_dT(p);
-#pragma unroll
-                for (int i = 0; i < RB; ++i) {
-                    const double v = F.surface[i] && !A.I_surface ? Ak[i][p] * edBs : 0.0;
-                    if (!row0_stored || F.surface[i]) put(i, 0, p, v, !row0_stored);
-                }
-            }
-        }
+        W.source_row();
     });
 }
 
@@ -6251,16 +6138,26 @@ void launch_scatter_radiance_pass(const ScatterRadianceArgs* d_args, bool linear
     });
 }
 
-// K5d's points per thread, chosen per angle count so that no instantiation spills (DESIGN.md "K5d")
+// The points per thread of the three column Jacobian kernels: 4 with one and two angles, 2 beyond.  One rule, three reasons:
+// K5d keeps three values per angle and point and no instantiation may spill (DESIGN.md "K5d"); K5h takes K5d's groups of
+// points, so that a black surface gives K5d's bits, and its walk 2 keeps six values per angle and point alive (DESIGN.md
+// "K5h"); K5j takes K5h's groups, so that equal edge temperatures give K5h's bits, and a step of it keeps four Planck values,
+// g, g' and h beside the six (DESIGN.md "K5j").
 template <int NA> constexpr int jacobian_np() { return NA <= 2 ? 4 : 2; }
+
+int jacobian_points(int n_angles) {
+    int np = 1;
+    with_angles(n_angles, [&](auto na) { np = jacobian_np<decltype(na)::value>(); });
+    return np;
+}
 
 void launch_column_jacobian(const JacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first, long long count,
                             double* partial, double* jac, hipStream_t s) {
     with_angles(n_angles, [&](auto na) {
         constexpr int NA = decltype(na)::value;
         constexpr int NP = jacobian_np<NA>();
-        launch_column_band<NP>(column_jacobian_kernel<NP, NA>, column_jacobian_kernel<1, NA>, d_args, 2 + 2 * n_layers + n_terms,
-                               first, count, partial, jac, s);
+        launch_column_band<NP>(column_jacobian_kernel<NP, NA>, column_jacobian_kernel<1, NA>, d_args,
+                               jacobian_slots(2, 1, n_layers, n_terms), first, count, partial, jac, s);
     });
 }
 
@@ -6325,23 +6222,14 @@ void launch_ray_jacobian(const RayJacArgs* d_args, long long n, int n_rays, int 
                                  ray_jacobian_kernel<4, 1, true>, ray_jacobian_kernel<1, 1, true>, d_args, n, n_rays, n_bundles, s);
 }
 
-// K5h: K5d's launch.  Points per thread: K5d's 4 for one and two angles (its groups of points, so that a black surface
-// gives K5d's bits), 2 beyond - walk 2 keeps six values per angle and point alive (DESIGN.md "K5h")
-template <int NA> constexpr int surface_jacobian_np() { return NA <= 2 ? 4 : 2; }
-
-int surface_jacobian_points(int n_angles) {
-    int np = 1;
-    with_angles(n_angles, [&](auto na) { np = surface_jacobian_np<decltype(na)::value>(); });
-    return np;
-}
-
+// K5h: K5d's launch at K5d's points per thread (jacobian_np)
 void launch_surface_jacobian(const SurfaceJacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first,
                              long long count, double* partial, double* jac, hipStream_t s) {
     with_angles(n_angles, [&](auto na) {
         constexpr int NA = decltype(na)::value;
-        constexpr int NP = surface_jacobian_np<NA>();
+        constexpr int NP = jacobian_np<NA>();
         launch_column_band<NP>(surface_jacobian_kernel<NP, NA>, surface_jacobian_kernel<1, NA>, d_args,
-                               3 + 2 * n_layers + n_terms, first, count, partial, jac, s);
+                               jacobian_slots(3, 1, n_layers, n_terms), first, count, partial, jac, s);
     });
 }
 
@@ -6354,27 +6242,20 @@ void launch_ray_surface_jacobian(const RaySurfaceJacArgs* d_args, long long n, i
                                         n_rays, n_bundles, s);
 }
 
-// K5j: K5h's launches.  The column's points per thread are linear_jacobian_np's; the rays keep K5i's groups of 4 points,
+// K5j: K5h's launches.  The column's points per thread are jacobian_np's; the rays keep K5i's groups of 4 points,
 // which is what makes `radiance` lbl_ray_radiance_linear_dev's bit for bit.  (One bundle kernel: without the term loop it
 // spills two registers, and it runs at one wave per SIMD either way.)
-int linear_jacobian_points(int n_angles) {
-    int np = 1;
-    with_angles(n_angles, [&](auto na) { np = linear_jacobian_np<decltype(na)::value>(); });
-    return np;
-}
-
 void launch_linear_jacobian(const LinearJacArgs* d_args, int n_layers, int n_angles, int n_terms, long long first,
                             long long count, double* partial, double* jac, hipStream_t s) {
     with_angles(n_angles, [&](auto na) {
         constexpr int NA = decltype(na)::value;
-        constexpr int NP = linear_jacobian_np<NA>();
+        constexpr int NP = jacobian_np<NA>();
         launch_column_band<NP>(linear_jacobian_kernel<NP, NA>, linear_jacobian_kernel<1, NA>, d_args,
-                               3 + 3 * n_layers + n_terms, first, count, partial, jac, s);
+                               jacobian_slots(3, 2, n_layers, n_terms), first, count, partial, jac, s);
     });
 }
 
-void launch_linear_ray_jacobian(const LinearRayJacArgs* d_args, long long n, int n_rays, int n_bundles, int n_terms,
-                                hipStream_t s) {
+void launch_linear_ray_jacobian(const LinearRayJacArgs* d_args, long long n, int n_rays, int n_bundles, hipStream_t s) {
     launch_ray_split<LinearRayJacArgs>(ray_linear_jacobian_kernel<4, kRayBundle>, ray_linear_jacobian_kernel<4, 1>,
                                        ray_linear_jacobian_kernel<1, 1>, d_args, n, n_rays, n_bundles, s);
 }

@@ -1,7 +1,8 @@
 # bit-for-bit comparison of two library builds: usage bitcmp_libs.sh <lib a> <lib b> [dump script]
 # (libraries: names under scripts/bin without the libpyrad_hip_ prefix, or 'prod'; dump script: a script under scripts/ that
 # takes an output directory - dump_spectra.py, the default: C1, C2, C3 (merged and per-list) and the column;
-# dump_transport.py: every column transport entry point on synthetic absorption coefficients).  Each dump runs under a time
+# dump_transport.py: every column transport entry point on synthetic absorption coefficients; dump_model_transport.py: every
+# Atmosphere method over them, with its call log, which is compared byte for byte).  Each dump runs under a time
 # limit of its own (DUMP_TIMEOUT seconds, default 300), and nothing more is started after one that fails.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 D=${3:-dump_spectra.py}
@@ -17,6 +18,13 @@ bad = 0
 if sorted(os.listdir(a)) != sorted(os.listdir(b)):
     sys.exit("the two dumps hold different files")
 for f in sorted(os.listdir(a)):
+    if not f.endswith(".npy"):          # (dump_model_transport.py's calls.txt: compared as bytes)
+        with open(os.path.join(a, f), "rb") as fa, open(os.path.join(b, f), "rb") as fb:
+            same = fa.read() == fb.read()
+        bad += 0 if same else 1
+        if not same:
+            print(f, "DIFFERENT")
+        continue
     x, y = np.load(os.path.join(a, f)), np.load(os.path.join(b, f))
     same = x.shape == y.shape and np.array_equal(x, y, equal_nan=True)
     bad += 0 if same else 1

@@ -4,7 +4,7 @@ beam, the two-stream family) through _native.Context on synthetic, seeded absorp
 its outputs concatenated): run once per library build (PYRAD_HIP_LIB) and compare the files bit for bit
 (scripts/bitcmp_libs.sh <lib a> <lib b> dump_transport.py).  No line lists are needed.  The shapes are the smallest at
 which the kernels' frames can go wrong: bands with head, aligned and tail points, a band of three points, a grid-stride
-second round in some workgroups only, every angle count on each side of the points-per-thread switch, both Planck paths,
+second round in some workgroups only, every angle count (1 to 8: each is an instantiation of its own), both Planck paths,
 bundled and single rays with a surface marker, a tail launch; for the two-stream family (K5l, K5m, K5n) see
 scatter_calls.  Per entry point of that family refusals_<name>.npy holds, as bytes, the return code and lbl_last_error of
 calls with one defect and with two: which of two defects is reported is part of what two builds must agree on.
@@ -178,6 +178,9 @@ def ray_calls(tag, c):
         jac = empty(rows * n)
         ctx.ray_jacobian_dev(c.k, c.T, *c.args(), f, lay, length, kind, jac, radiance=rad, source_T=290.0, **tk)
         save("%s_t%d_ray_jacobian" % (tag, terms), jac, rad)
+    # the source given as a spectrum (with its NaN and infinity), two terms
+    ctx.ray_jacobian_dev(c.k, c.T, *c.args(), f, lay, length, kind, jac, radiance=rad, **tk, **src)
+    save(tag + "_spectrum_ray_jacobian", jac, rad)
     f, lay, length, kind, seg_T = pack(True)
     for e_name, e in (("e0.7", 0.7), ("earr", c.emissivity)):
         t = "%s_%s" % (tag, e_name)
@@ -403,7 +406,7 @@ n_points = 4 * 256 * 2 + 7
 for grid, lo, res in GRIDS:
     for L in (1, 3):
         col = Column(L, n_points, lo, res)
-        for na in (1, 2, 3, 5, 8):
+        for na in range(1, 9):            # every angle count has kernels of its own
             for surface in ("T", "spectrum"):
                 column_calls(grid, col, na, surface)
         solar_calls(grid, col)
