@@ -1206,24 +1206,57 @@ __device__ __forceinline__ void wave_sum_rows(double (&C)[NT], double* scratch, 
 }
 
 // Terms a chunk of far lines needs, by the distance d (in half-spans) of its NEAREST line from the span centre:
-// rho <= 1/d, and the remainder bound above falls fast with d.  Exact mode (NT = 30, remainder below half an ulp of
-// the line's own smallest term on the span): d >= 8: 20 terms (2.7e-17), d >= 16: 15 (1.7e-17), d >= 32: 12 (1.2e-17).
-// Budget mode (NT = 18, 5.9e-10): d >= 8: 12 (2.8e-10), d >= 16: 9 (1.8e-10), d >= 32: 7 (2.6e-10).  With a window of
-// +-39 half-spans two thirds of the far lines are beyond 16 half-spans: 17 terms on average instead of 30.
-// The classes as {d, terms} pairs, nearest first (tests/test_far_terms_cpu.py reads these two lines and holds every pair
-// to the remainder bound of its mode):
-constexpr int kFarClassExact[5][2] = {{3, 38}, {4, 30}, {8, 20}, {16, 15}, {32, 12}};
+// rho <= 1/d, and the remainder bound above falls fast with d.  Exact mode (remainder below 7.8e-17, half an ulp of the
+// line's own smallest term on the span, which the 38 terms from 3 half-spans on meet): one class per distinct count, each
+// starting at the first whole d whose bound admits that count - the staircase 38 / 30 / 26 / 23 / 21 / 20 / 19 / 18 from
+// d = 3 .. 10, then 17 from 11, 16 from 13, 15 from 15, 14 from 18, 13 from 22, 12 from 28 and 11 from 37 on (the window of a
+// one-atmosphere cell ends at 39).  Budget mode (NT = 18, 5.9e-10) keeps four classes: d >= 8: 12 (2.8e-10), d >= 16: 9
+// (1.8e-10), d >= 32: 7 (2.6e-10).
+// The classes as {d, terms} pairs, nearest first: the only place a count lives (far_chunk's descent and the edge series'
+// count take theirs from the table of the build's mode).  tests/test_far_terms_cpu.py reads these two lines and holds
+// every pair to the remainder bound of its mode; tests/test_far_classes_cpu.py holds the exact table to the minimal count
+// at every whole d:
+constexpr int kFarClassExact[15][2] = {{3, 38}, {4, 30}, {5, 26}, {6, 23}, {7, 21}, {8, 20}, {9, 19}, {10, 18}, {11, 17}, {13, 16}, {15, 15}, {18, 14}, {22, 13}, {28, 12}, {37, 11}};
 constexpr int kFarClassBudget[4][2] = {{4, 18}, {8, 12}, {16, 9}, {32, 7}};
 static_assert(kFarClassExact[0][0] == FF_MID && kFarClassExact[0][1] == FF_NT_MID && kFarClassExact[1][0] == FF_FAR && kFarClassExact[1][1] == FF_NT &&
               kFarClassBudget[0][0] == FF_FAR_BUDGET && kFarClassBudget[0][1] == FF_NT_BUDGET, "the nearest classes are the builds' own thresholds and term counts");
-static_assert(kFarClassExact[2][0] == 8 && kFarClassExact[3][0] == 16 && kFarClassExact[4][0] == 32 && kFarClassBudget[1][0] == 8 &&
-              kFarClassBudget[2][0] == 16 && kFarClassBudget[3][0] == 32, "far_chunk and the edge series branch at 8, 16 and 32 half-spans");
+constexpr int FF_EDGE_MIN = 8;       // the edge series is entered from this many half-spans on (series_edges)
+// Where far_chunk's descent stops, exact mode: the distances (half-spans, nearest first) at which a chunk may leave the
+// chain; a chunk takes the count of the table class of the last stop at or below its distance, so a chunk between two
+// stops runs up to three terms more than its own class needs (never fewer: the bound holds).  Not every class is a stop,
+// because a stop is not free: one scalar compare and one branch for every chunk that comes by, measured at about
+// what ONE term costs (three dependent fp64 instructions) - with all 15 classes as stops a merged 100-2500 cm^-1 launch ran
+// 1.8e6 fewer vector and 0.7e6 more scalar instructions in the same time as with the five stops 3 / 4 / 8 / 16 / 32 before.
+// A stop pays where (the share of the passing chunks that leave) x (the terms they shed) exceeds that.  With a chunk's
+// distance spread evenly over 3 .. 38 half-spans: five stops 18.0 terms and 2.3 compares per chunk, all fifteen 16.0 and
+// 5.3, these eight (38 / 30 / 26 / 23 / 20 / 17 / 15 / 13 terms) 16.6 and 2.4 - the least cost for a compare worth 0.8 of
+// a term, and within 1 % of it from 0.5 to 1.1.  The edge series pays its compares once per span and takes the count of
+// its own class.  (LBL_FAR_STOPS: A/B builds, scripts/make_variant_lib.sh.)
+#ifndef LBL_FAR_STOPS
+#define LBL_FAR_STOPS {3, 4, 5, 6, 8, 11, 15, 22}
+#endif
+constexpr int kFarStopsExact[] = LBL_FAR_STOPS;
+static_assert(kFarStopsExact[0] == FF_MID && kFarStopsExact[1] == FF_FAR, "the nearest stops are the builds' own thresholds");
+// The classes and stops of one build: NT == FF_NT_MID walks the exact mode's stops from the first (3 half-spans), NT == FF_NT
+// from the second (that build's series starts at FF_FAR and never enters the d = 3 segment); NT == FF_NT_BUDGET stops at
+// every class of the budget table; any other NT (diagnostic builds) is one class of NT terms.
 template <int NT> struct FarTerms {
     static constexpr bool exact = NT == FF_NT || NT == FF_NT_MID, budget = NT == FF_NT_BUDGET;
-    static constexpr int t4 = budget ? kFarClassBudget[0][1] : (NT == FF_NT_MID ? kFarClassExact[1][1] : NT);     // (from 4 half-spans on: 30 terms; nearer, NT = 38: the build whose series starts at 3)
-    static constexpr int t8 = exact ? kFarClassExact[2][1] : (budget ? kFarClassBudget[1][1] : NT);
-    static constexpr int t16 = exact ? kFarClassExact[3][1] : (budget ? kFarClassBudget[2][1] : NT);
-    static constexpr int t32 = exact ? kFarClassExact[4][1] : (budget ? kFarClassBudget[3][1] : NT);
+    static constexpr int first = exact && NT != FF_NT_MID ? 1 : 0;
+    static constexpr int count = exact ? (int)(sizeof(kFarClassExact) / sizeof(kFarClassExact[0])) : (budget ? (int)(sizeof(kFarClassBudget) / sizeof(kFarClassBudget[0])) : 1);
+    static constexpr int dist(int i) { return exact ? kFarClassExact[i][0] : (budget ? kFarClassBudget[i][0] : 0); }
+    static constexpr int terms(int i) { return exact ? kFarClassExact[i][1] : (budget ? kFarClassBudget[i][1] : NT); }
+    static constexpr int edge_first() { int i = first; while (i + 1 < count && dist(i) < FF_EDGE_MIN) ++i; return i; }
+    static constexpr int terms_at(int d) { int i = 0; while (i + 1 < count && dist(i + 1) <= d) ++i; return terms(i); }
+    static constexpr int stops = exact ? (int)(sizeof(kFarStopsExact) / sizeof(kFarStopsExact[0])) : count;
+    static constexpr int stop_dist(int s) { return exact ? kFarStopsExact[s] : dist(s); }
+    static constexpr int stop_terms(int s) { return exact ? terms_at(kFarStopsExact[s]) : terms(s); }
+    // terms of the class that a distance of dmin points falls into, among the classes from FF_EDGE_MIN half-spans on (the
+    // edge series: once per span, scalar compares against compile-time limits, farthest class first)
+    template <int R, int I = count - 1> static __device__ __forceinline__ int edge_terms(int dmin) {
+        if constexpr (I > edge_first()) return dmin >= dist(I) * 32 * R ? terms(I) : edge_terms<R, I - 1>(dmin);
+        else return terms(I);
+    }
 };
 
 // q_N0 .. q_{N1-1} of one line per lane added to the per-lane sums (qa, qb: q_{N0-2}, q_{N0-1}; carried on)
@@ -1235,8 +1268,24 @@ __device__ __forceinline__ void series_terms(double al, double bp, double& qa, d
         C[n] += qn;
         // (an empty statement the scheduler may not move code across: without it the compiler runs the whole chain of
         // q_n first and sinks the additions behind the term-count branches - 20 more live values, spilled in the loop)
-        if ((n & 1) == 1) asm volatile("" : "+v"(C[n]));
+        // (also after a segment's last term: the one-term segments of the distance classes would otherwise have none)
+        if ((n & 1) == 1 || n == N1 - 1) asm volatile("" : "+v"(C[n]));
         qa = qb; qb = qn;
+    }
+}
+
+// The terms beyond those of stop I (already added), for a chunk whose nearest line is dmin2 / 2 points from the span
+// centre: while the chunk lies nearer than stop I, the segment up to the next nearer stop's count, farthest stop first -
+// a distant chunk (most of them) leaves after one or two scalar compares, only a span's two or three nearest walk the whole
+// chain.  Integer compares against compile-time limits (stop I lies at stop_dist(I) half-spans = 32 R stop_dist(I) points).
+template <int R, int NT, int I>
+__device__ __forceinline__ void far_descent(int dmin2, double al, double bp, double& qa, double& qb, double (&C)[NT]) {
+    typedef FarTerms<NT> FT;
+    if constexpr (I > FT::first) {
+        if (dmin2 < 2 * FT::stop_dist(I) * 32 * R) {
+            series_terms<FT::stop_terms(I), FT::stop_terms(I - 1), NT>(al, bp, qa, qb, C);
+            far_descent<R, NT, I - 1>(dmin2, al, bp, qa, qb, C);
+        }
     }
 }
 
@@ -1324,17 +1373,10 @@ __device__ __forceinline__ void far_chunk(const double __attribute__((ext_vector
     double qb = al * qa;
     C[1] += qb;
     typedef FarTerms<NT> FT;
-    series_terms<2, FT::t32, NT>(al, bp, qa, qb, C);
-    if (dmin2 < 2 * 32 * 32 * R) {
-        series_terms<FT::t32, FT::t16, NT>(al, bp, qa, qb, C);
-        if (dmin2 < 2 * 16 * 32 * R) {
-            series_terms<FT::t16, FT::t8, NT>(al, bp, qa, qb, C);
-            if (dmin2 < 2 * 8 * 32 * R) {
-                series_terms<FT::t8, FT::t4, NT>(al, bp, qa, qb, C);
-                if (FT::t4 < NT && dmin2 < 2 * 4 * 32 * R) series_terms<FT::t4, NT, NT>(al, bp, qa, qb, C);
-            }
-        }
-    }
+    static_assert(FT::stop_terms(FT::first) == NT && FT::stop_terms(FT::stops - 1) >= 2, "a build's nearest class takes the build's own term count");
+    static_assert(FT::count == 1 || FT::dist(FT::edge_first()) == FF_EDGE_MIN, "a class starts where the edge series is entered");
+    series_terms<2, FT::stop_terms(FT::stops - 1), NT>(al, bp, qa, qb, C);
+    far_descent<R, NT, FT::stops - 1>(dmin2, al, bp, qa, qb, C);
 }
 
 // Series coefficients of the far lines m0, m0+stride*k.. (chunks of 64, one line per lane) below m1.  stride: 64 LS, LS a
@@ -1563,8 +1605,8 @@ __device__ __forceinline__ void skew_edges(const HotRec* hot, const ColdRec* col
 // that cover only some of its points keep the masked walk; rounds with a Gaussian part that reaches the span or a
 // denominator outside the running-fraction range keep the masked span path, as before.  Like the skewed walk it runs BEFORE
 // the far lines' series phase, so that its NTE coefficients and that phase's NT are never live together.
-// NTE terms: by the distance of the job's nearest edge line, H - 32 R points (FarTerms classes: 20 / 15 / 12 from 8 / 16 / 32
-// half-spans on, exact to half an ulp); nearer than 8 half-spans 30 terms would cost what the walk costs: the walk stays.
+// NTE terms: by the distance of the job's nearest edge line, H - 32 R points (FarTerms classes from FF_EDGE_MIN = 8 half-spans
+// on: 20 terms there, 11 from 37 on, exact to half an ulp); nearer than 8 half-spans 30 terms would cost what the walk costs: the walk stays.
 // inclusive prefix sum over the 64 lanes (lanes without a source add 0); fixed summation tree.  The two steps across rows
 // fetch with full masks and are switched on per row by a factor (m15: 1.0 in rows 1 and 3, m31: 1.0 in rows 2 and 3, else
 // 0.0; x * 1.0 is exact and the values are finite, so the sums are those of masked moves) - a DPP move under a partial row
@@ -1863,11 +1905,11 @@ void xsec_accumulate_lds_kernel(const AccumJob* __restrict__ jobs, const int2* _
             const int dmin = H - 32 * R;
             unsigned long long odd = 0ull;
             // a round of the series costs ~52 wave-instructions per term + ~250 whatever it holds, the walk ~21 per line: the
-            // series from 42 / 49 / 62 edge lines per span on (a merged 100-2500 cm^-1 span has 84, one of its line lists 28:
+            // series from 40 (11 terms, windows of 37 half-spans and more) to 62 (20 terms, 8 half-spans) edge lines per span on (a merged 100-2500 cm^-1 span has 84, one of its line lists 28:
             // measured on the per-list step, series for everything: K2 +4.5 %)
             const int n_edge = (iB - iA) + (iD - iC);
-            const int nte = dmin >= 32 * 32 * R ? FT::t32 : dmin >= 16 * 32 * R ? FT::t16 : FT::t8;
-            if (EDGE_SERIES && dmin >= 8 * 32 * R && n_edge * 21 >= 52 * nte + 250)
+            const int nte = FT::template edge_terms<R>(dmin);
+            if (EDGE_SERIES && dmin >= FF_EDGE_MIN * 32 * R && n_edge * 21 >= 52 * nte + 250)
                 series_edges<R>(J.hot, J.cold, iA, iB, iC, iD, wlo, whi, H, x0, Hf, xc, nte, lh, lc, eL, eR, lane, S, odd);
             else
                 skew_edges<R>(J.hot, J.cold, iA, iB, iC, iD, wlo, whi, H, x0, Hf, lh, lc, eL, eR, lane, S, odd);
