@@ -852,6 +852,83 @@ int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* cons
                                     lbl_buffer* workspace, lbl_buffer* radiance /* n_views x n */,
                                     lbl_buffer* up_top, lbl_buffer* down_surface /* may be NULL */);
 
+/* ---- scattered sunlight along a view (beyond the reference; ABI 5, backward compatible) -----------------------------------
+ * pyrad_amd.model.Atmosphere.solarRadianceTwoStream: what an instrument sees of lbl_column_twostream_dev's column in
+ * sunlight, by lbl_column_radiance_scatter_dev's source function technique with the beam's single scattering in the source.
+ * Everything about the column is lbl_column_twostream_dev's, unchanged: layers, scatterers and delta scaling, ta, ts, tsg, t,
+ * w, g, Da, g1, g2, lam, R, T, Ab, the t == 0 and den == 0 branches, the beam's m = 1 / slant_l, g3, g4, a2, Cp, u (Cm = Cp - u)
+ * and Td, the move of m to (1 - 1e-6) / lam with Tdm where |1 - lam m| < 1e-6, the sources Rb and Tb, the adding recurrences
+ * and the Lambertian surface; they define the hemispheric fluxes up_i, dn_i (diffuse) and the beam's flux through the
+ * horizontal Fd_i = beam_weight S_i at every level over the whole grid [0, n) (there are no bands).  One sun per call
+ * (n_beams is 1: an instrument sees one sun, and a mean over suns of radiances along a fixed view means nothing): one
+ * beam_weight and one slant per layer.  Nothing emits.  Up to lbl_limit("beam_views") = 16 views, view_mu and view_down as
+ * lbl_column_radiance_scatter_dev takes them.
+ * Within layer l let s in [0, t] be the scaled optical depth from the layer's top, D = sqrt(3), Fd = Fd_(l+1).  F+(s), F-(s)
+ * are the two-stream fluxes inside the layer, the system that Cp and Cm are the particular solution of:
+ *   dF+/ds =  g1 F+ - g2 F- - w g3 (Fd / m) exp(-s / m)        F-(0) = dn_(l+1)
+ *   dF-/ds =  g2 F+ - g1 F- + w g4 (Fd / m) exp(-s / m)        F+(t) = up_l       (so F+(0) = up_(l+1), F-(t) = dn_l)
+ * The source function in direction +-mu is
+ *   pi S+-(s, mu) = (w / 2) [ (1 +- D g mu) F+(s) + (1 -+ D g mu) F-(s) ]
+ *                 + (w / (2 D m)) (1 -+ 3 g mu m) Fd exp(-s / m)
+ * The first line is lbl_column_radiance_scatter_dev's scattering term.  The second is the singly scattered beam: the two-term
+ * phase function 1 + 3 g cos(Theta) averaged over azimuth, cos(Theta) -> -+ mu m (a plane-parallel beam of cosine m in the
+ * layer; the radiance is the azimuthal mean, there is no azimuth argument).  Its normalisation w / (2 D m) per unit Fd is
+ * that of the quadrature scheme, not of an exact single-scattering calculation (w / (4 m) per unit Fd, i.e. 2 / sqrt(3)
+ * times smaller): it is the one with which I = F+- / pi satisfies the transfer equation at mu = 1 / sqrt(3), a known property
+ * of the two-stream source function technique, and what makes the first identity below hold.
+ *   up view:    Iu_0 = up_0 / pi   (the Lambertian surface reflects diffuse and direct light alike)
+ *               Iu_(l+1) = Iu_l exp(-t / mu) + integral_0^t S+(s, mu) exp(-s / mu) ds / mu            result Iu_L
+ *   down view:  Id_L = 0   (the diffuse sky: the solar disc itself is not in it)
+ *               Id_l = Id_(l+1) exp(-t / mu) + integral_0^t S-(s, mu) exp(-(t - s) / mu) ds / mu      result Id_0
+ *   t == 0:     the layer changes nothing.
+ * Where m is moved (the pole lam m = 1), every in-layer beam term - Cp, u, exp(-s / m), the 1 / m and m of the second line -
+ * uses the moved m, and the beam's value at the layer's bottom is Fd Tdm: F+-(s) is the solution whose edge values the
+ * adding used.  g3, g4 and a2 keep the unmoved m, as in lbl_column_twostream_dev.
+ * Evaluation (every operation rounded on its own, exp the flux kernels').  sigma = F+ + F- - (2 Cp - u) Fd exp(-s / m) and
+ * Delta = F+ - F- - u Fd exp(-s / m) solve y'' = lam^2 y, so each is y(0) r0(s) + y(t) r1(s) with
+ * lbl_column_radiance_scatter_dev's r0, r1 and the edge values
+ *   sigma(0) = (up_(l+1) + dn_(l+1)) - (2 Cp - u) Fd          sigma(t) = (up_l + dn_l) - (2 Cp - u) (Fd Tdm)
+ *   Delta(0) = (up_(l+1) - dn_(l+1)) - u Fd                   Delta(t) = (up_l - dn_l) - u (Fd Tdm)
+ * integrated by that call's Wp and W1 (u there is lam t), unchanged.  With tau = t / mu, Tv = exp(-tau), the beam
+ * exponential integrates against exp(-s / mu) ds / mu and exp(-(t - s) / mu) ds / mu to
+ *   Xu = -expm1(-(tau + t / m)) / (1 + mu / m)
+ *   Xd = (x >= 0 ? Tdm : Tv) (-expm1(-|x|)) / |1 - mu / m|,  x = (1 - mu / m) tau   (tau Tv at x == 0)
+ * (1 / m is slant_l, or 1 / (the moved m)), and a layer adds, for an up view,
+ *   pi J = (w / 2) (sigma(0) Wp + (sigma(t) - sigma(0)) W1) + (w D g mu / 2) (Delta(0) Wp + (Delta(t) - Delta(0)) W1)
+ *        + (Fd Xu) [ (w / 2) (2 Cp - u) + (w D g mu / 2) u + ((w / 2) / D) (1 / m - 3 g mu) ]
+ * and for a down view the same with the two edges exchanged, the two w D g mu / 2 terms negated, Xd for Xu and 1 / m + 3 g mu.
+ * Xd is smooth through mu == m, Wp and W1 through lam mu == 1: no point is left out and no mu is moved; no exponential has a
+ * positive argument and no branch fires at lam == 0 or den == 0; a thin layer adds (t / mu) S.  Near the pole Cp and u reach
+ * 1e6 and cancel against sigma and Delta: there the result loses digits (measured within 1.4e-12 of S0 / pi of a float64
+ * restatement that is itself within 7.4e-13 of 50 digits; DESIGN.md "K5o"), elsewhere it is good to rounding.
+ * Identities.  At mu = 1 / sqrt(3), pi Iu_L == up_L and pi Id_0 == dn_0 to rounding, lbl_column_twostream_dev's own spectra.
+ * Without scatterers w = 0 and every J is exactly 0: an up view is lbl_column_solar_dev's Lambertian up_top / pi with the
+ * single angle (mu, pi), a down view exactly 0.  A layer split into two of half the amounts and depth gives the same radiances.
+ * Known limit of the two-term phase function: 1 - 3 g mu m is negative for g mu m > 1 / 3 (the forward peak seen against the
+ * sun), which delta scaling (g -> g / (1 + g)) eases but does not exclude; nothing is clamped.
+ * radiance is n_views x n.  up_top, down_surface (diffuse) and direct_surface (may be NULL; n points each) receive
+ * lbl_column_twostream_dev's spectra bit for bit.  A point where some layer's t is not finite is NaN in every output; every
+ * other point keeps its bits.  The workspace is lbl_column_twostream_dev's (5 numbers per level and point; the second kernel
+ * recomputes the layer from the coefficients): lbl_column_beam_radiance_workspace is lbl_column_twostream_workspace.  The
+ * grid runs in passes of whole 256-point tiles and the bits do not depend on the workspace's size, nor a view's on the other
+ * views of the call.  No atomics.
+ * LBL_ERR_BAD_ARG, all before anything is enqueued: what lbl_column_twostream_dev refuses of the shared arguments (one beam:
+ * a beam_weight that is not finite, a slant that is not finite and > 0); n < 1; what lbl_column_radiance_scatter_dev refuses
+ * of the views (the limit is lbl_limit("beam_views")), the radiance buffer and the workspace; "sweep_ieee_divisions" 1.
+ * The host arrays are copied and not retained.  Stream-ordered; nothing is synchronised. */
+int lbl_column_beam_radiance_workspace(int n_layers, int64_t points, int64_t* doubles);
+int lbl_column_beam_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                                 double range_min, double range_max, int64_t n,
+                                 lbl_buffer* S0, double beam_weight, const double* slant /* n_layers */,
+                                 int n_scat, const double* scat_amount /* n_scat x n_layers */,
+                                 lbl_buffer* const* scat_ext /* may be NULL, and every entry */, const double* scat_ext_all,
+                                 lbl_buffer* const* scat_ssa, const double* scat_ssa_all,
+                                 lbl_buffer* const* scat_asym, const double* scat_asym_all, int delta_scaling,
+                                 lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                 int n_views, const double* view_mu, const int32_t* view_down /* 0 up at the top, 1 down at the surface */,
+                                 lbl_buffer* workspace, lbl_buffer* radiance /* n_views x n */,
+                                 lbl_buffer* up_top, lbl_buffer* down_surface, lbl_buffer* direct_surface /* may be NULL */);
+
 /* ---- ray-path Jacobians (beyond the reference; ABI 5, backward compatible) --------------------------------------------
  * pyrad_amd.model.Atmosphere.pathJacobians: the weighting functions of the radiance lbl_ray_radiance_dev computes - its
  * analytic derivatives to every crossed layer's optical depth and (Planck) temperature, to the source temperature and to any

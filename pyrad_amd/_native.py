@@ -142,6 +142,11 @@ SIGNATURES = {
                                                   C.c_int64, _P, C.c_double, _P, C.c_int, _D, C.POINTER(_P), _D,
                                                   C.POINTER(_P), _D, C.POINTER(_P), _D, C.c_int, _P, C.c_double, C.c_int, _D,
                                                   C.POINTER(C.c_int32), _P, _P, _P, _P]),
+    "lbl_column_beam_radiance_workspace": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int64)]),
+    "lbl_column_beam_radiance_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, _P,
+                                               C.c_double, _D, C.c_int, _D, C.POINTER(_P), _D, C.POINTER(_P), _D,
+                                               C.POINTER(_P), _D, C.c_int, _P, C.c_double, C.c_int, _D,
+                                               C.POINTER(C.c_int32), _P, _P, _P, _P, _P]),
     "lbl_ray_jacobian_rows": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "lbl_ray_jacobian_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_double, C.c_double, C.c_int64, C.c_int,
@@ -842,6 +847,32 @@ class Context:
             float(surface_T), _hb(I_top), *scat, int(delta_scaling), *self._emissivity_args(emissivity),
             len(view_mu), _arr(C.c_double, [float(m) for m in view_mu]), _arr(C.c_int32, [int(d) for d in view_down]),
             _hb(workspace), _hb(radiance), _hb(up_top), _hb(down_surface)))
+
+    def column_beam_radiance_workspace(self, n_layers, points):
+        """The doubles of a workspace with which column_beam_radiance_dev does ``points`` points in one pass
+        (lbl_column_beam_radiance_workspace: column_twostream_workspace's)."""
+        return self._scatter_workspace(self.lib.lbl_column_beam_radiance_workspace, n_layers, points)
+
+    def column_beam_radiance_dev(self, abs_coef, depth, range_min, range_max, n, S0, beam_weight, slant, scat_amount, scat_ext,
+                                 scat_ssa, scat_asym, delta_scaling, view_mu, view_down, workspace, radiance, emissivity=1.0,
+                                 up_top=None, down_surface=None, direct_surface=None):
+        """Scattered sunlight along views (lbl_column_beam_radiance_dev): one sun - ``S0``, one ``beam_weight`` and one
+        ``slant`` per layer - through the column, the scatterers, the surface and the ``workspace`` that
+        column_twostream_dev takes, over the whole grid; ``view_mu`` and ``view_down`` as column_radiance_scatter_dev takes
+        them.  ``radiance`` receives len(view_mu) x n values; ``up_top`` / ``down_surface`` (diffuse) / ``direct_surface``
+        (optional, n points) column_twostream_dev's spectra."""
+        slant = _as_f64(slant).reshape(-1)
+        if len(slant) != len(abs_coef):
+            raise ValueError("column_beam_radiance_dev: one slant per layer")
+        scat = self._scatter_args("column_beam_radiance_dev", abs_coef, scat_amount, scat_ext, scat_ssa, scat_asym)
+        if len(view_down) != len(view_mu):
+            raise ValueError("column_beam_radiance_dev: one direction per view")
+        self.check(self.lib.lbl_column_beam_radiance_dev(
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), _arr(C.c_double, [float(d) for d in depth]),
+            float(range_min), float(range_max), int(n), _hb(S0), float(beam_weight),
+            _arr(C.c_double, [float(v) for v in slant]), *scat, int(delta_scaling), *self._emissivity_args(emissivity),
+            len(view_mu), _arr(C.c_double, [float(m) for m in view_mu]), _arr(C.c_int32, [int(d) for d in view_down]),
+            _hb(workspace), _hb(radiance), _hb(up_top), _hb(down_surface), _hb(direct_surface)))
 
     def column_jacobian_dev(self, abs_coef, layer_T, depth, range_min, range_max, n, mu, weight, band_first, band_count,
                             jac, I_surface=None, surface_T=0.0, term_abs_coef=(), term_layer=(), ln_tau_spectra=None,

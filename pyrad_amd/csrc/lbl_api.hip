@@ -407,6 +407,7 @@ extern "C" int lbl_limit(const char* name, int64_t* value) {
     else if (!strcmp(name, "flux_bands")) *value = kMaxFluxBands;             // bands of lbl_column_flux_dev
     else if (!strcmp(name, "scatterers")) *value = kMaxScatterers;            // scatterers of lbl_column_twostream_dev
     else if (!strcmp(name, "scatter_views")) *value = kMaxScatterViews;       // views of lbl_column_radiance_scatter_dev
+    else if (!strcmp(name, "beam_views")) *value = kMaxBeamViews;             // views of lbl_column_beam_radiance_dev
     else if (!strcmp(name, "jacobian_terms")) *value = kMaxJacobianTerms;    // molecule terms of lbl_column_jacobian_dev
     else if (!strcmp(name, "ils_rows")) *value = kMaxIlsRows;                  // rows of lbl_ils_convolve_dev
     else if (!strcmp(name, "ils_channels")) *value = kMaxIlsChannels;          // ... its channels

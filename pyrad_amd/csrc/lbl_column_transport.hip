@@ -365,6 +365,9 @@ extern "C" int lbl_column_flux_scatter_workspace(int n_layers, int64_t points, i
 extern "C" int lbl_column_radiance_scatter_workspace(int n_layers, int64_t points, int64_t* doubles) {
     return scatter_workspace(kScatterFluxQuantities, n_layers, points, doubles);
 }
+extern "C" int lbl_column_beam_radiance_workspace(int n_layers, int64_t points, int64_t* doubles) {
+    return scatter_workspace(kTwoStreamQuantities, n_layers, points, doubles);      // (K5o's is K5l's)
+}
 
 // one of the three spectral numbers of the scatterers: a buffer of n points per scatterer, or the number beside it within
 // [lo, hi] (the ends excluded where `open`)
@@ -460,44 +463,35 @@ static int run_scatter_bands(lbl_ctx* ctx, const Args* a, Variant variant, int r
     return LBL_OK;
 }
 
-// K5l: lbl_column_solar_dev's checks in its order, the scatterers' and the workspace's behind them; then run_scatter_bands.
-extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
-                                        double range_min, double range_max, int64_t n, lbl_buffer* S0, int n_beams,
-                                        const double* beam_weight, const double* slant, int n_scat, const double* scat_amount,
-                                        lbl_buffer* const* scat_ext, const double* scat_ext_all, lbl_buffer* const* scat_ssa,
-                                        const double* scat_ssa_all, lbl_buffer* const* scat_asym, const double* scat_asym_all,
-                                        int delta_scaling, int n_bands, const int64_t* band_first, const int64_t* band_count,
-                                        lbl_buffer* emissivity, double emissivity_all, lbl_buffer* workspace,
-                                        lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface,
-                                        lbl_buffer* direct_surface, lbl_buffer* up_surface) try {
-    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
-    (void)range_min; (void)range_max;       // (the grid of the other column calls: nothing here depends on a wavenumber)
-    std::vector<char> blk(sizeof(TwoStreamArgs), 0);
-    TwoStreamArgs* a = (TwoStreamArgs*)blk.data();
+// The beam column of K5l and K5o, checked in two halves around each call's own checks (K5l's bands and level sums, K5o's
+// views and radiances; the optional spectra and the emissivity in between).  Head: the column's extent, the sweeps'
+// arithmetic, the beam and scatterer counts and the switch.
+static int check_beam_column_head(lbl_ctx* ctx, const char* what, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                                  int64_t n, int n_beams, const double* beam_weight, const double* slant, int n_scat,
+                                  const double* scat_amount, int delta_scaling) {
     if (n_layers < 0 || n_layers > kMaxLayers) return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d layers", kMaxLayers);
     if (n < 0) return column_fail(ctx, LBL_ERR_BAD_ARG, "negative n");
     if (n_layers > 0 && (!abs_coef || !depth || !slant)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL argument");
     if (ctx_sweep_ieee(ctx))
-        return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", "two-stream fluxes");
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "%s exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)", what);
     if (n_beams < 1 || n_beams > kMaxFluxAngles) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d beams", kMaxFluxAngles);
     if (!beam_weight) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL beam set");
     if (n_scat < 0 || n_scat > kMaxScatterers) return column_fail(ctx, LBL_ERR_BAD_ARG, "0..%d scatterers", kMaxScatterers);
     if (n_scat > 0 && n_layers > 0 && !scat_amount) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL scatterer amounts");
     if (delta_scaling != 0 && delta_scaling != 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "delta_scaling must be 0 or 1");
-    if (n_bands < 1 || n_bands > kMaxFluxBands) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d bands", kMaxFluxBands);
-    if (!band_first || !band_count) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL band list");
-    const int nv = 3 * (n_layers + 1);
+    return LBL_OK;
+}
+
+// Tail: the layers, the beams, the scatterers and the workspace; then the block (zeroed by the caller) filled from the
+// buffers that the call checked itself.
+static int check_beam_column_tail(lbl_ctx* ctx, TwoStreamArgs* a, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                                  int64_t n, lbl_buffer* S0, int n_beams, const double* beam_weight, const double* slant,
+                                  int n_scat, const double* scat_amount, lbl_buffer* const* scat_ext,
+                                  const double* scat_ext_all, lbl_buffer* const* scat_ssa, const double* scat_ssa_all,
+                                  lbl_buffer* const* scat_asym, const double* scat_asym_all, int delta_scaling,
+                                  lbl_buffer* emissivity, double emissivity_all, lbl_buffer* workspace, lbl_buffer* up_top,
+                                  lbl_buffer* down_surface, lbl_buffer* direct_surface, lbl_buffer* up_surface) {
     int rc;
-    if ((rc = ctx_check_buffer(ctx, S0, n, "S0", true))) return rc;
-    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
-    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, direct_surface, n, "direct_surface", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
-    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
-    for (int b = 0; b < n_bands; ++b)
-        if (band_first[b] < 0 || band_count[b] < 1 || band_count[b] > n - band_first[b])
-            return column_fail(ctx, LBL_ERR_BAD_ARG, "band %d: empty or outside [0, n)", b);
     for (int l = 0; l < n_layers; ++l) {
         if ((rc = ctx_check_buffer(ctx, abs_coef[l], n, "abs_coef", true))) return rc;
         if (!(depth[l] >= 0)) return column_fail(ctx, LBL_ERR_BAD_ARG, "layer %d: depth must be >= 0", l);
@@ -524,6 +518,44 @@ extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* 
     a->S0 = buffer_data(S0);
     a->direct_surface = direct_surface ? buffer_data(direct_surface) : nullptr;
     a->n_layers = n_layers;
+    return LBL_OK;
+}
+
+// K5l: lbl_column_solar_dev's checks in its order, the scatterers' and the workspace's behind them; then run_scatter_bands.
+extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                                        double range_min, double range_max, int64_t n, lbl_buffer* S0, int n_beams,
+                                        const double* beam_weight, const double* slant, int n_scat, const double* scat_amount,
+                                        lbl_buffer* const* scat_ext, const double* scat_ext_all, lbl_buffer* const* scat_ssa,
+                                        const double* scat_ssa_all, lbl_buffer* const* scat_asym, const double* scat_asym_all,
+                                        int delta_scaling, int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                        lbl_buffer* emissivity, double emissivity_all, lbl_buffer* workspace,
+                                        lbl_buffer* level_flux, lbl_buffer* up_top, lbl_buffer* down_surface,
+                                        lbl_buffer* direct_surface, lbl_buffer* up_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    (void)range_min; (void)range_max;       // (the grid of the other column calls: nothing here depends on a wavenumber)
+    std::vector<char> blk(sizeof(TwoStreamArgs), 0);
+    TwoStreamArgs* a = (TwoStreamArgs*)blk.data();
+    int rc;
+    if ((rc = check_beam_column_head(ctx, "two-stream fluxes", n_layers, abs_coef, depth, n, n_beams, beam_weight, slant, n_scat,
+                                     scat_amount, delta_scaling)))
+        return rc;
+    if (n_bands < 1 || n_bands > kMaxFluxBands) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d bands", kMaxFluxBands);
+    if (!band_first || !band_count) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL band list");
+    const int nv = 3 * (n_layers + 1);
+    if ((rc = ctx_check_buffer(ctx, S0, n, "S0", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, level_flux, (int64_t)n_bands * nv, "level_flux", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, direct_surface, n, "direct_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_surface, n, "up_surface", false))) return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    for (int b = 0; b < n_bands; ++b)
+        if (band_first[b] < 0 || band_count[b] < 1 || band_count[b] > n - band_first[b])
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "band %d: empty or outside [0, n)", b);
+    if ((rc = check_beam_column_tail(ctx, a, n_layers, abs_coef, depth, n, S0, n_beams, beam_weight, slant, n_scat, scat_amount,
+                                     scat_ext, scat_ext_all, scat_ssa, scat_ssa_all, scat_asym, scat_asym_all, delta_scaling,
+                                     emissivity, emissivity_all, workspace, up_top, down_surface, direct_surface, up_surface)))
+        return rc;
     return run_scatter_bands(ctx, a, n_beams, 3, n, n_bands, band_first, band_count,
                              {a->up_top, a->down_surface, a->direct_surface, a->up_surface}, level_flux);
 } LBL_GUARD_END(ctx)
@@ -603,6 +635,24 @@ extern "C" int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffe
                              {a->up_top, a->down_surface, a->up_surface}, level_flux);
 } LBL_GUARD_END(ctx)
 
+// the views of K5n and K5o (Args: ScatterRadianceArgs or BeamViewArgs): 1 .. limit cosines in (0, 1] with a direction each;
+// the block's entries beyond n_views get mu = 1, up
+template <class Args>
+static int check_views(lbl_ctx* ctx, Args* a, int limit, int n_views, const double* view_mu, const int32_t* view_down) {
+    if (n_views < 1 || n_views > limit) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d views", limit);
+    if (!view_mu || !view_down) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL view list");
+    for (int v = 0; v < limit; ++v) {
+        if (v < n_views && !(view_mu[v] > 0 && view_mu[v] <= 1))
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "view %d: mu must lie in (0, 1]", v);
+        if (v < n_views && view_down[v] != 0 && view_down[v] != 1)
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "view %d: the direction must be 0 (up) or 1 (down)", v);
+        a->view_mu[v] = v < n_views ? view_mu[v] : 1.0;
+        a->view_rmu[v] = 1.0 / a->view_mu[v];
+        a->view_down[v] = v < n_views ? view_down[v] : 0;
+    }
+    return LBL_OK;
+}
+
 // K5n: the thermal scattering column's checks over one band, the whole grid, around the views' and the radiance buffer's;
 // the passes are K5m's, without partial sums.
 extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
@@ -624,17 +674,7 @@ extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_b
                                         range_max, n, I_surface, surface_T, n_scat, scat_amount, delta_scaling, 1, &band_first,
                                         &band_count)))
         return rc;
-    if (n_views < 1 || n_views > kMaxScatterViews) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d views", kMaxScatterViews);
-    if (!view_mu || !view_down) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL view list");
-    for (int v = 0; v < kMaxScatterViews; ++v) {
-        if (v < n_views && !(view_mu[v] > 0 && view_mu[v] <= 1))
-            return column_fail(ctx, LBL_ERR_BAD_ARG, "view %d: mu must lie in (0, 1]", v);
-        if (v < n_views && view_down[v] != 0 && view_down[v] != 1)
-            return column_fail(ctx, LBL_ERR_BAD_ARG, "view %d: the direction must be 0 (up) or 1 (down)", v);
-        a->view_mu[v] = v < n_views ? view_mu[v] : 1.0;
-        a->view_rmu[v] = 1.0 / a->view_mu[v];
-        a->view_down[v] = v < n_views ? view_down[v] : 0;
-    }
+    if ((rc = check_views(ctx, a, kMaxScatterViews, n_views, view_mu, view_down))) return rc;
     if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_views * n, "radiance", true))) return rc;
     if ((rc = check_scatter_column_tail(ctx, a, n_layers, n, I_top, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa,
                                         scat_ssa_all, scat_asym, scat_asym_all, delta_scaling, emissivity, emissivity_all,
@@ -650,6 +690,50 @@ extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_b
     for (int64_t done = 0; done < n; done += a->ws_points)
         launch_scatter_radiance_pass((const ScatterRadianceArgs*)d_args, planck_linear != 0, n_views, done,
                                      std::min<int64_t>(a->ws_points, n - done), s);
+    COLUMN_HIP_TRY(ctx, hipGetLastError());
+    return LBL_OK;
+} LBL_GUARD_END(ctx)
+
+// K5o: K5l's checks of one beam over the whole grid around the views' and the radiance buffer's; the passes are K5n's.
+extern "C" int lbl_column_beam_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* depth,
+                                            double range_min, double range_max, int64_t n, lbl_buffer* S0, double beam_weight,
+                                            const double* slant, int n_scat, const double* scat_amount,
+                                            lbl_buffer* const* scat_ext, const double* scat_ext_all,
+                                            lbl_buffer* const* scat_ssa, const double* scat_ssa_all,
+                                            lbl_buffer* const* scat_asym, const double* scat_asym_all, int delta_scaling,
+                                            lbl_buffer* emissivity, double emissivity_all, int n_views, const double* view_mu,
+                                            const int32_t* view_down, lbl_buffer* workspace, lbl_buffer* radiance,
+                                            lbl_buffer* up_top, lbl_buffer* down_surface, lbl_buffer* direct_surface) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    (void)range_min; (void)range_max;       // (as lbl_column_twostream_dev: nothing here depends on a wavenumber)
+    std::vector<char> blk(sizeof(BeamViewArgs), 0);
+    BeamViewArgs* a = (BeamViewArgs*)blk.data();
+    int rc;
+    if ((rc = check_beam_column_head(ctx, "scattered solar radiances", n_layers, abs_coef, depth, n, 1, &beam_weight, slant,
+                                     n_scat, scat_amount, delta_scaling)))
+        return rc;
+    if (n < 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "the grid is empty");
+    if ((rc = check_views(ctx, a, kMaxBeamViews, n_views, view_mu, view_down))) return rc;
+    if ((rc = ctx_check_buffer(ctx, S0, n, "S0", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_views * n, "radiance", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, down_surface, n, "down_surface", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, direct_surface, n, "direct_surface", false))) return rc;
+    if ((rc = check_emissivity(ctx, emissivity, emissivity_all, n))) return rc;
+    if ((rc = check_beam_column_tail(ctx, a, n_layers, abs_coef, depth, n, S0, 1, &beam_weight, slant, n_scat, scat_amount,
+                                     scat_ext, scat_ext_all, scat_ssa, scat_ssa_all, scat_asym, scat_asym_all, delta_scaling,
+                                     emissivity, emissivity_all, workspace, up_top, down_surface, direct_surface, nullptr)))
+        return rc;
+    a->radiance = buffer_data(radiance);
+    a->n = n;
+    a->n_views = n_views;
+
+    void* d_args = nullptr;
+    if ((rc = ctx_device_args(ctx, a, sizeof(BeamViewArgs), &d_args))) return rc;
+    const hipStream_t s = ctx_stream(ctx);
+    COLUMN_HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+    for (int64_t done = 0; done < n; done += a->ws_points)
+        launch_beam_view_pass((const BeamViewArgs*)d_args, n_views, done, std::min<int64_t>(a->ws_points, n - done), s);
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
 } LBL_GUARD_END(ctx)

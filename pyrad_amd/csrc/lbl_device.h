@@ -443,6 +443,22 @@ struct ScatterRadianceArgs : ScatterFluxArgs {
 void launch_scatter_radiance_pass(const ScatterRadianceArgs* d_args, bool linear, int n_views, long long first, long long count,
                                   hipStream_t s);
 
+// Scattered sunlight along a view (K5o, lbl_column_transport.hip: lbl_column_beam_radiance_dev): K5l's column with one beam,
+// whose first kernel runs as it stands on the TwoStreamArgs part of this block (the workspace is K5l's, five numbers per
+// level), then one upward walk that integrates the two-stream source function with the beam's single scattering along every
+// view.  No band sums: up_surface stays nullptr.
+constexpr int kMaxBeamViews = 16;
+struct BeamViewArgs : TwoStreamArgs {
+    double view_mu[kMaxBeamViews];      // the viewing cosines, in (0, 1]; 1 beyond n_views
+    double view_rmu[kMaxBeamViews];     // 1 / mu_v, from the host
+    int32_t view_down[kMaxBeamViews];   // 0: upward at the top of the column; 1: downward at the surface
+    double* radiance;                   // n_views x n
+    long long n;                        // points of the grid: a view's row of `radiance`
+    int32_t n_views, pad_views;
+};
+// one pass over the points [first, first + count): first is a multiple of the tile and count <= ws_points
+void launch_beam_view_pass(const BeamViewArgs* d_args, int n_views, long long first, long long count, hipStream_t s);
+
 // Ray-path Jacobians (K5f, lbl_column_transport.hip: lbl_ray_jacobian_dev): K5e's walk, then the segments last to first
 // with K5d's transmittance-and-emission recurrence, one output row per ray, kind and crossed layer.  RayArgs' block with
 // more tables behind it; `radiance` may be nullptr here and `transmittance` is not used.  A ray's rows start at row_first[r]:

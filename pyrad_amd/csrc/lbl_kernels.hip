@@ -37,6 +37,8 @@
 //                              surface (Atmosphere.fluxesTwoStream; beyond the reference)
 //   K5n scatter_radiance_up_kernel   K5m's column seen along up to 16 views: the two-stream source function integrated in
 //                              closed form per layer and view (Atmosphere.radianceTwoStream; beyond the reference)
+//   K5o beam_view_kernel      K5l's column with one sun seen along up to 16 views: K5n's integrals with the beam's single
+//                              scattering in the source function (Atmosphere.solarRadianceTwoStream; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -4625,6 +4627,30 @@ __global__ __launch_bounds__(256) void scatter_flux_up_kernel(const ScatterFluxA
 // 8 TB/s against 2 ps of fp64 at the vector rate - and a workspace 2.75 times K5m's.  So the workspace is K5m's.
 // One point per thread as K5l/K5m; NV in {1, 2, 4, 8, 16} is the view count rounded up (the views beyond n_views are
 // computed with mu = 1 and not stored), so a view's arithmetic does not depend on its neighbours.
+// The weights of one view in one layer (K5n, K5o), as above: tau = t / mu, Tv = exp(-tau), Wp and W1, from the layer's
+// t, lam, u = lam t, E = exp(-u) and m2 = 2 u / -expm1(-2 u) (1 at u == 0), which do not depend on the view.
+struct ViewWeights {
+    double tau, Tv, Wp, W1;
+};
+__device__ __forceinline__ ViewWeights view_weights(double t, double lam, double u, double E, double m2, double mu, double rmu) {
+#pragma clang fp contract(off)
+    ViewWeights Y;
+    const double tau = t * rmu;
+    const double Tv = exp_neg_budget(tau);
+    const double lm = lam * mu;
+    const double q1 = 1.0 - lm, p1 = 1.0 + lm;
+    const double x = q1 * tau, ax = fabs(x);
+    const double sel = x >= 0.0 ? E : Tv;
+    const double em = -expm1(-ax);
+    const double A1 = sel * (ax == 0.0 ? tau : em / fabs(q1));
+    const double A1t = sel * (ax == 0.0 ? 1.0 : em / ax);
+    const double A2 = -expm1(-(tau + u)) / p1;
+    Y.tau = tau; Y.Tv = Tv;
+    Y.Wp = (A1 + A2) / (1.0 + E);
+    Y.W1 = (m2 * A1t - Tv) / p1;
+    return Y;
+}
+
 template <bool LINEAR, int NV>
 __global__ __launch_bounds__(256) void scatter_radiance_up_kernel(const ScatterRadianceArgs* __restrict__ Ap, long long first,
                                                                   long long count) {
@@ -4678,19 +4704,9 @@ __global__ __launch_bounds__(256) void scatter_radiance_up_kernel(const ScatterR
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
                 const double mu = A.view_mu[v];
-                const double tau = t * A.view_rmu[v];
-                const double Tv = exp_neg_budget(tau);
+                const ViewWeights vw = view_weights(t, lam, u, E, m2, mu, A.view_rmu[v]);
+                const double tau = vw.tau, Tv = vw.Tv, Wp = vw.Wp, W1 = vw.W1;
                 const double Wt = -expm1(-tau);
-                const double lm = lam * mu;
-                const double q1 = 1.0 - lm, p1 = 1.0 + lm;
-                const double x = q1 * tau, ax = fabs(x);
-                const double sel = x >= 0.0 ? E : Tv;
-                const double em = -expm1(-ax);
-                const double A1 = sel * (ax == 0.0 ? tau : em / fabs(q1));
-                const double A1t = sel * (ax == 0.0 ? 1.0 : em / ax);
-                const double A2 = -expm1(-(tau + u)) / p1;
-                const double Wp = (A1 + A2) / (1.0 + E);
-                const double W1 = (m2 * A1t - Tv) / p1;
                 const double gl = lbl::linear_source_g(tau, Tv);
                 const double kap = hw * (Dg * mu);
                 const double part = c2 * (Wt - Wp);
@@ -4717,6 +4733,124 @@ __global__ __launch_bounds__(256) void scatter_radiance_up_kernel(const ScatterR
             A.radiance[(long long)v * A.n + j] = bad ? nan : r;
         }
     }
+}
+
+// ----------------------------------------------------------------------------------------
+// K5o: scattered sunlight along a view (lbl_column_beam_radiance_dev; the semantics are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// K5n's technique on K5l's column with one beam.  The first pass is twostream_down_kernel<1> as it stands (BeamViewArgs
+// begins with TwoStreamArgs; the workspace is K5l's, quantity 4 the beam's flux Fd_i through the horizontal);
+// beam_view_kernel<NV> is K5l's upward walk without the sums - its surface, up and dn per level, the three spectra - and per
+// layer and view the closed-form integral of
+//     pi S+-(s) = (w / 2) sigma(s) +- kap Delta(s) + (w / (2 D m)) (1 -+ 3 g mu m) Fd exp(-s / m),   kap = w D g mu / 2,
+// Fd = Fd_(l+1) at the layer's top.  sigma = F+ + F- and Delta = F+ - F- less their particular parts (2 Cp - u) Fd exp(-s / m)
+// and u Fd exp(-s / m) (K5l's Cp and u = Cp - Cm, restated here: with the moved m and Tdm at the pole lam m = 1, so that the
+// edge values are those the adding used) solve y'' = lam^2 y: K5n's sinh-ratio basis between the edge values and its weights
+// Wp and W1 (view_weights).  What multiplies Fd exp(-s / m) is gathered in one bracket per view and integrates to
+//     Xu = -expm1(-(tau + t / m)) / (1 + mu / m)                                       (up view,   against exp(-s / mu))
+//     Xd = (x >= 0 ? Tdm : Tv) (-expm1(-|x|)) / |1 - mu / m|,  x = (1 - mu / m) tau    (down view, against exp(-(t - s) / mu);
+//                                                                                       tau Tv at x == 0: smooth through mu == m)
+// No exponential has a positive argument and no branch fires at lam == 0 or den == 0.  The layer is recomputed for K5n's
+// reason (the workspace would grow from 5 to 11 numbers per level).  One point per thread; NV as K5n.
+template <int NV>
+__global__ __launch_bounds__(256) void beam_view_kernel(const BeamViewArgs* __restrict__ Ap, long long first, long long count) {
+#pragma clang fp contract(off)
+    const BeamViewArgs& A = *Ap;
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= count) return;
+    const long long j = first + q;
+    const int L = A.n_layers;
+    const int levels = L + 1;
+    const long long row = A.ws_points;
+    const double* const W = A.workspace + q;
+    auto ws = [&](int v, int i) { return W[((long long)v * levels + i) * row]; };
+    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+    double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
+    scatterer_numbers(A, j, al, si, et);
+    double Rs = ws(0, 0), Ds = ws(1, 0);
+    const double F0 = ws(4, 0);
+    const bool bad = isnan(Rs) || isnan(Ds);
+    const double nan = __builtin_nan("");
+    // K5l's surface (twostream_up_kernel)
+    const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
+    const double albedo = 1.0 - e;
+    double up = (albedo * (Ds + F0)) / (1.0 - albedo * Rs);
+    double dn = Rs * up + Ds;
+    if (A.down_surface) A.down_surface[j] = bad ? nan : dn;
+    if (A.direct_surface) A.direct_surface[j] = bad ? nan : F0;
+    double I[NV], C[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        I[v] = A.view_down[v] ? 0.0 : up / kPi;
+        C[v] = 1.0;
+    }
+    double k = L > 0 ? load_global_f64(A.abs_coef[0], j) : 0.0;
+    for (int l = 0; l < L; ++l) {
+        const double k_next = l + 1 < L ? load_global_f64(A.abs_coef[l + 1], j) : k;
+        const TwoStreamLayer lay = twostream_layer(A, l, A.depth[l], k, al, si, et);
+        const double upB = up, dnB = dn;
+        up = ws(2, l + 1) * up + ws(3, l + 1);
+        Rs = ws(0, l + 1); Ds = ws(1, l + 1);
+        dn = Rs * up + Ds;
+        const double Fd = ws(4, l + 1);
+        if (!lay.empty) {
+            const double t = lay.t, lam = lay.lam, w = lay.w, g = lay.g;
+            // the beam's terms, K5l's (twostream_down_kernel)
+            double tm = t * A.slant[0][l];
+            double m = A.m[0][l], rm = A.slant[0][l];
+            const double g3 = 0.5 * (1.0 - (D * g) * m), g4 = 1.0 - g3;
+            const double a2 = lay.g1 * g3 + lay.g2 * g4;
+            if (fabs(1.0 - lam * m) < 1e-6) {
+                m = (1.0 - 1e-6) / lam;
+                tm = t / m;
+                rm = 1.0 / m;
+            }
+            const double Tdm = exp_neg_budget(tm);
+            const double pole = (1.0 - lam * m) * (1.0 + lam * m);
+            const double Cp = (w * (g3 - a2 * m)) / pole;
+            const double cu = (w * (1.0 + (lay.Da * (g4 - g3)) * m)) / pole;
+            const double cs = Cp + (Cp - cu);               // Cp + Cm
+            const double Fb = Fd * Tdm;                     // the in-layer beam term at the bottom edge
+            const double sig0 = (up + dn) - cs * Fd, sigt = (upB + dnB) - cs * Fb;      // top edge, bottom edge
+            const double del0 = (up - dn) - cu * Fd, delt = (upB - dnB) - cu * Fb;
+            const double u = lam * t;
+            const double E = exp_neg_budget(u);
+            const double m2 = u == 0.0 ? 1.0 : fmin(2.0 * u, 2000.0) / -expm1(-2.0 * u);     // (E == 0 beyond 800)
+            const double hw = 0.5 * w;
+            const double Dg = D * g;
+            const double g3x = 3.0 * g;
+            const double hs = hw / D;
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const double mu = A.view_mu[v];
+                const ViewWeights vw = view_weights(t, lam, u, E, m2, mu, A.view_rmu[v]);
+                const double tau = vw.tau, Tv = vw.Tv, Wp = vw.Wp, W1 = vw.W1;
+                const double kap = hw * (Dg * mu);
+                const double mr = mu * rm;
+                if (A.view_down[v]) {
+                    const double qb = 1.0 - mr;
+                    const double xb = qb * tau, axb = fabs(xb);
+                    const double Xd = (xb >= 0.0 ? Tdm : Tv) * (axb == 0.0 ? tau : -expm1(-axb) / fabs(qb));
+                    const double beam = (hw * cs - kap * cu) + hs * (rm + g3x * mu);
+                    const double J = (hw * (sigt * Wp + (sig0 - sigt) * W1) - kap * (delt * Wp + (del0 - delt) * W1))
+                                     + (Fd * Xd) * beam;
+                    I[v] = I[v] + C[v] * (J / kPi);
+                    C[v] = C[v] * Tv;
+                } else {
+                    const double Xu = -expm1(-(tau + tm)) / (1.0 + mr);
+                    const double beam = (hw * cs + kap * cu) + hs * (rm - g3x * mu);
+                    const double J = (hw * (sig0 * Wp + (sigt - sig0) * W1) + kap * (del0 * Wp + (delt - del0) * W1))
+                                     + (Fd * Xu) * beam;
+                    I[v] = I[v] * Tv + J / kPi;
+                }
+            }
+        }
+        k = k_next;
+    }
+    if (A.up_top) A.up_top[j] = bad ? nan : up;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+        if (v < A.n_views) A.radiance[(long long)v * A.n + j] = bad ? nan : I[v];
 }
 
 // ----------------------------------------------------------------------------------------
@@ -6177,6 +6311,16 @@ void launch_scatter_radiance_pass(const ScatterRadianceArgs* d_args, bool linear
         constexpr int NV = decltype(nv)::value;
         const auto kernel = linear ? scatter_radiance_up_kernel<true, NV> : scatter_radiance_up_kernel<false, NV>;
         hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+    });
+}
+
+void launch_beam_view_pass(const BeamViewArgs* d_args, int n_views, long long first, long long count, hipStream_t s) {
+    if (count <= 0) return;
+    const unsigned tiles = (unsigned)((count + kTwoStreamTile - 1) / kTwoStreamTile);
+    hipLaunchKernelGGL(twostream_down_kernel<1>, dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first,
+                       count);                                              // (the block begins with K5l's)
+    with_views(n_views, [&](auto nv) {
+        hipLaunchKernelGGL(beam_view_kernel<decltype(nv)::value>, dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
     });
 }
 

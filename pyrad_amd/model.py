@@ -3027,6 +3027,86 @@ class Atmosphere(list):
                 values[lo:hi] = out.download((hi - lo) * X).reshape(hi - lo, X)
         return ScatterRadiance(first.xAxis if instrument is None else instrument.centres.copy(), values, view_mu, direction)
 
+    def solarRadianceTwoStream(self, views, scatterers=(), deltaScaling=True, solarSpectrum=None, solarTemperature=None,
+                               distanceAU=1.0, mu0=1.0, geometry="plane", planetRadius=6.371e8, emissivity=1.0,
+                               instrument=None):
+        """What an instrument sees of solarFluxesTwoStream()'s column in sunlight: the reflected spectrum leaving the top,
+        or the diffuse sky arriving at the surface, at any viewing cosine (beyond the reference).  radianceTwoStream()'s
+        source function technique with the beam in the source: solarFluxesTwoStream()'s solution gives the hemispheric
+        fluxes F+ and F- inside every layer and the beam's flux Fd through the horizontal at its top, and
+            pi S+-(s, mu) = (w / 2) [(1 +- sqrt(3) g mu) F+(s) + (1 -+ sqrt(3) g mu) F-(s)]
+                            + (w / (2 sqrt(3) m)) (1 -+ 3 g mu m) Fd exp(-s / m)
+        (w the layer's scaled single-scattering albedo, g its asymmetry, m = 1 / slant the beam's cosine in the layer) is
+        integrated along the view in closed form per layer, smooth through mu = m and lam mu = 1
+        (lbl_column_beam_radiance_dev, include/pyrad_hip.h).  The second line is the singly scattered beam.  The radiance
+        is the AZIMUTHAL MEAN: the two-term phase function 1 + 3 g cos(Theta) is averaged over the azimuth between sun and
+        view, which leaves 1 -+ 3 g mu m, and there is no azimuth argument.  Its normalisation w / (2 sqrt(3) m) is the
+        quadrature scheme's, 2 / sqrt(3) times the w / (4 m) of an exact single-scattering calculation - a known property
+        of the two-stream source function technique: with it pi times the radiance at mu = 1 / sqrt(3) is
+        solarFluxesTwoStream()'s flux.
+
+        ``views`` and ``instrument`` as radianceTwoStream() takes them: "up" starts from the Lambertian surface's
+        up_0 / pi (diffuse and direct light reflected alike), "down" from 0 - the diffuse sky; the solar disc itself is
+        not in it.  More than 16 views run in chunks of 16; a view's values do not depend on the others.  ``mu0``: ONE
+        cosine in (0, 1] - an instrument sees one sun, and a day's mean of radiances along a fixed view means nothing, so
+        a list of (mu0, weight) pairs is refused.  Every other argument as solarFluxesTwoStream() takes it.
+        A daytime spectrum is this plus radianceTwoStream(...) for the same views and scatterers, view by view: the
+        thermal and the solar radiances superpose.
+        Without scatterers an "up" view is solarFluxes(angles=[(mu, pi)], spectra=True).upSpectrum / pi over the same
+        Lambertian surface and a "down" view is exactly 0; a layer split in two gives the same radiances.  The two-term
+        phase function's 1 - 3 g mu m is negative for g mu m > 1 / 3, which ``deltaScaling`` (g -> g / (1 + g)) eases;
+        nothing is clamped, as in radianceTwoStream().
+        Returns a ScatterRadiance.  The absorption coefficients are the resident ones; the workspace (five numbers per
+        level and point) stays with the atmosphere, at most 256 MiB - a longer grid is done in several passes, with the same
+        bits.  Everything is validated (ValueError) before the device is touched."""
+        layers, n = self._column_layers()
+        first = layers[0]
+        x = first.xAxis
+        nl = len(layers)
+        view_mu, view_down, direction = _scatter_views(views)
+        scat, numbers = self._scatter_checks(scatterers, deltaScaling, x, nl)
+        S0 = _solar_spectrum(solarSpectrum, solarTemperature, distanceAU, x)
+        if isinstance(mu0, (bool, str)) or not isinstance(mu0, (int, float, np.integer, np.floating)):
+            raise ValueError("mu0: one cosine in (0, 1] - one sun per call - not %r" % (mu0,))
+        mu_s, _ = _solar_beams(mu0)
+        depth = [L.depth for L in layers]
+        slant = solarSlants(depth, float(mu0), geometry, planetRadius)
+        emissivity = _surface_emissivity(emissivity, x)
+        support = None
+        if instrument is not None:
+            if not isinstance(instrument, Instrument):
+                raise ValueError("instrument: an Instrument, not %r" % (instrument,))
+            support = instrument.support(first.rangeMin, first.rangeMax, n)
+        chunk = nat.limit("beam_views")
+        V = len(view_mu)
+        ctx = _ctx()
+        kbufs, _ = self._column_abs_coef(ctx, layers, n)
+        st = _kept_state(self, "_beam_view_state")
+        st.reserve(ctx, n)
+        source = st.buf(ctx, "S0").upload(S0)
+        emissivity = self._device_emissivity(ctx, st, emissivity)
+        columns = self._scatter_columns(ctx, st, scat, numbers)
+        # (the grid in one pass)
+        workspace = self._scatter_workspace(ctx, ctx.column_beam_radiance_workspace, "_beam_view_workspace", nl, n)
+        rad = _kept_state(self, "_beam_view_rows").reserve(ctx, min(V, chunk) * n).buf(ctx, "radiance")
+        X = n if instrument is None else len(instrument)
+        out = None
+        if instrument is not None:
+            out = _kept_state(self, "_beam_view_out").reserve(ctx, min(V, chunk) * X).buf(ctx, "out")
+        values = np.empty((V, X))
+        for lo in range(0, V, chunk):
+            hi = min(lo + chunk, V)
+            ctx.column_beam_radiance_dev(kbufs, depth, first.rangeMin, first.rangeMax, n, source, float(mu_s[0]), slant,
+                                         *columns, int(bool(deltaScaling)), view_mu[lo:hi], view_down[lo:hi], workspace, rad,
+                                         emissivity=emissivity)
+            if instrument is None:
+                values[lo:hi] = rad.download((hi - lo) * n).reshape(hi - lo, n)
+            else:
+                _ils_convolve(ctx, instrument, first.rangeMin, first.rangeMax, n, support, [(rad, r * n) for r in range(hi - lo)],
+                              out)
+                values[lo:hi] = out.download((hi - lo) * X).reshape(hi - lo, X)
+        return ScatterRadiance(first.xAxis if instrument is None else instrument.centres.copy(), values, view_mu, direction)
+
     def jacobians(self, surfaceTemperature=None, surfaceSpectrum=None, angles=3, bands=None, molecules=True, spectra=False,
                   temperature="planck", emissivity=None, reflection="lambertian", topSpectrum=None):
         """Analytic sensitivities of the upward flux at the top (beyond the reference), in one pass over the resident
