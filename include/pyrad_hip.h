@@ -788,6 +788,68 @@ int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* a
                                 lbl_buffer* workspace, lbl_buffer* level_flux, lbl_buffer* up_top,
                                 lbl_buffer* down_surface, lbl_buffer* up_surface /* may be NULL */);
 
+/* ---- Jacobians of the outgoing flux through scattering layers (beyond the reference; ABI 5, backward compatible) -----------
+ * pyrad_amd.model.Atmosphere.jacobiansTwoStream: the analytic derivatives of F = up_L, lbl_column_flux_scatter_dev's upward
+ * flux at the top, per grid point.  The forward model is that call's, unchanged: scatterers, delta scaling, ta, ts, tsg, t, the
+ * layer's R, T, Ab, the sources P, Q of planck_linear 0 and 1, the t == 0, den == 0 and ta == 0 branches, Rs, Ds, U1, U0, the
+ * emitting Lambertian surface and I_top.  The level relations are linear in the fluxes, so one adjoint pass gives every row:
+ *   above level i:   up_L = Tu_i up_i + ...,   Tu_L = 1,  Tu_i = Tu_(i+1) U1_(i+1)          (the downward walk, with U1)
+ *   below level l:   the surface and layers 0 .. l-1 reflect A_l:  A_0 = 1 - e,  A_(l+1) = R_l + T_l^2 A_l / (1 - A_l R_l)
+ *   layer l alone changed, with up = up_l, dn' = dn_(l+1), Rs' = Rs_(l+1), Tu' = Tu_(l+1):
+ *     w1 = Tu' / ((1 - R Rs') - T^2 A_l Rs' / (1 - R A_l))        w2 = w1 T A_l / (1 - R A_l)
+ *     dF = w1 (dT up + dR dn' + dP) + w2 (dT dn' + dR up + dQ)
+ *   surface, c0 = 1 - (1 - e) Rs_0:   dF/dEs = Tu_0 e / c0  (times pi dB/dT at surface_T: dF/dT_s; 0 with I_surface),
+ *                                     dF/de = Tu_0 (Es - dn_0) / c0
+ * The layer depends on its three depths through p = D ta and q = D (t - tsg) alone (D = sqrt(3)): with r = sqrt(p), s = sqrt(q),
+ * x = r s, E = exp(-x), Gam = (s - r) / (s + r), G = r s / (s + r)^2 = (1 - Gam^2) / 4, oE = 1 - E^2, N = 4 G + Gam^2 oE
+ *   R = Gam oE / N      T = 4 G E / N      Ab = 1 - R - T      h = (Ab + 2 R) / q - T
+ *   p R_p  = G (4 x Gam E^2 - oE (1 + Gam^2 E^2)) / N^2        q R_q  = G (4 x Gam E^2 + oE (1 + Gam^2 E^2)) / N^2
+ *   p T_p  = 2 G E (Gam oE - x (1 + Gam^2 E^2)) / N^2          q T_q  = -2 G E (Gam oE + x (1 + Gam^2 E^2)) / N^2
+ *   p Ab_p = G (oE + 2 x E) / (1 + Gam E)^2                    q Ab_q = -G (oE - 2 x E) / (1 + Gam E)^2
+ *   p h_p  = (p Ab_p + 2 p R_p) / q - p T_p                    q h_q  = (q Ab_q + 2 q R_q - (Ab + 2 R)) / q - q T_q
+ * R and T are even in r, so they are smooth in p; the products p X_p and q X_q are formed directly and nothing is divided by
+ * sqrt(ta) or sqrt(q) (G / N <= 1 / 4).  den == 0: the branch's R = y / (1 + y), T = 1 / (1 + y), y = (p + q) / 2, Ab = 0;
+ * t == 0: every derivative is 0.  Sources: planck_linear 0, P = Q = B Ab: dP = dQ = B dAb, dP/dB = dQ/dB = Ab;
+ * planck_linear 1: dP = Bt dAb + d dh, dQ = Bb dAb - d dh, dP/dBt = dQ/dBb = Ab - h, dP/dBb = dQ/dBt = h; where P = Q = 0
+ * by a branch (t == 0, den == 0, ta == 0) their derivatives are 0.  With p F_p and q F_q the two sums dF above,
+ *   fa = p F_p / ta  (0 at ta == 0),   fq = q F_q / (t - tsg)  (0 at t == tsg):   dF/dta = fa + fq,  dF/dts = fq,  dF/dtsg = -fq
+ * so the logarithmic derivative of an amount that is 0 is exactly 0, and a term of a layer whose ta is 0 at a point sees fq alone.
+ * jac is n_bands x (3 + (1 + NT + n_scat) n_layers + n_terms), band sums of nan_to_num, NT = 1 (planck_linear 0) or 2:
+ *   F, dF/dT_s, dF/de,
+ *   dF/d ln tau_l        l = 0 .. L-1                 the gas of layer l:  k_l depth_l dF/dta_l
+ *   dF/dT                NT per layer, layer by layer  NT = 1: the layer's temperature, (w1 + w2) Ab pi dB/dT; NT = 2: bottom
+ *                                                      edge (w1 h + w2 (Ab - h)) pi dB/dT_b, then top edge (w1 (Ab - h) + w2 h)
+ *                                                      pi dB/dT_t  (lbl_column_jacobian_linear_dev's order)
+ *   dF/d ln amount_cl    c = 0 .. n_scat-1, l = 0 .. L-1:  amount_cl (al_c dF/dta + si_c dF/dts + et_c dF/dtsg) of layer l
+ *   dF/d ln n_m          m = 0 .. n_terms-1, lbl_column_jacobian_dev's terms:  term_abs_coef[m] depth_l dF/dta_l, l = term_layer[m]
+ * The temperature rows are the Planck part; the absorption part is a term (dk/dT), as for lbl_column_jacobian_dev.
+ * jac_ln_tau_spectra (L x n) and jac_T_spectra (NT L x n; both may be NULL) receive the spectral rows, 0 outside every band.
+ * up_top (may be NULL) receives lbl_column_flux_scatter_dev's spectrum bit for bit, and the band's F is that call's up at
+ * level L bit for bit.  A point where some layer's t is not finite is NaN in the spectra and counts as 0 in every sum.
+ * Not differentiated: the scatterers' albedo and asymmetry, and the downward flux at the surface.
+ * The first of two kernels writes 5 numbers per level and point into `workspace` ([number][level][point]: that call's four
+ * and Tu), the second recomputes each layer; passes, tiles and the partial sums by tile of the band are
+ * lbl_column_twostream_dev's: the bits do not depend on the workspace's size, and there are no atomics.
+ * lbl_column_jacobian_scatter_workspace gives the doubles that hold `points` points in one pass.
+ * LBL_ERR_BAD_ARG, all before anything is enqueued: what lbl_column_flux_scatter_dev refuses of the shared arguments; what
+ * lbl_column_jacobian_dev refuses of the terms, jac and the spectra (more than lbl_limit("jacobian_terms") terms, a term
+ * layer out of range, a short buffer); a workspace of fewer than lbl_column_jacobian_scatter_workspace(n_layers, 1) doubles;
+ * "sweep_ieee_divisions" 1.  The host arrays are copied and not retained.  Stream-ordered; nothing is synchronised. */
+int lbl_column_jacobian_scatter_workspace(int n_layers, int64_t points, int64_t* doubles);
+int lbl_column_jacobian_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef,
+                                    const double* T /* n_layers, or 2 n_layers: bottom, top of layer l */, int planck_linear,
+                                    const double* depth, double range_min, double range_max, int64_t n,
+                                    lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                                    int n_scat, const double* scat_amount /* n_scat x n_layers */,
+                                    lbl_buffer* const* scat_ext /* may be NULL, and every entry */, const double* scat_ext_all,
+                                    lbl_buffer* const* scat_ssa, const double* scat_ssa_all,
+                                    lbl_buffer* const* scat_asym, const double* scat_asym_all, int delta_scaling,
+                                    int n_bands, const int64_t* band_first, const int64_t* band_count,
+                                    lbl_buffer* emissivity /* may be NULL */, double emissivity_all,
+                                    int n_terms, lbl_buffer* const* term_abs_coef, const int32_t* term_layer,
+                                    lbl_buffer* workspace, lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra /* may be NULL */,
+                                    lbl_buffer* jac_T_spectra /* may be NULL */, lbl_buffer* up_top /* may be NULL */);
+
 /* ---- radiances through scattering layers (beyond the reference; ABI 5, backward compatible) -------------------------------
  * pyrad_amd.model.Atmosphere.radianceTwoStream: what an instrument sees of lbl_column_flux_scatter_dev's column, by the
  * two-stream source function technique (Toon et al. 1989).  Everything about the column is that call's, unchanged: layers,

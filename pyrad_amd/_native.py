@@ -137,6 +137,12 @@ SIGNATURES = {
                                               C.c_double, _P, C.c_int, _D, C.POINTER(_P), _D, C.POINTER(_P), _D, C.POINTER(_P),
                                               _D, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, C.c_double,
                                               _P, _P, _P, _P, _P]),
+    "lbl_column_jacobian_scatter_workspace": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int64)]),
+    "lbl_column_jacobian_scatter_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_int, _D, C.c_double, C.c_double,
+                                                  C.c_int64, _P, C.c_double, _P, C.c_int, _D, C.POINTER(_P), _D,
+                                                  C.POINTER(_P), _D, C.POINTER(_P), _D, C.c_int, C.c_int,
+                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, C.c_double, C.c_int,
+                                                  C.POINTER(_P), C.POINTER(C.c_int32), _P, _P, _P, _P, _P]),
     "lbl_column_radiance_scatter_workspace": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int64)]),
     "lbl_column_radiance_scatter_dev": (C.c_int, [_P, C.c_int, C.POINTER(_P), _D, C.c_int, _D, C.c_double, C.c_double,
                                                   C.c_int64, _P, C.c_double, _P, C.c_int, _D, C.POINTER(_P), _D,
@@ -824,6 +830,33 @@ class Context:
             _arr(C.c_int64, [int(f) for f in band_first]), _arr(C.c_int64, [int(c) for c in band_count]),
             *self._emissivity_args(emissivity), _hb(workspace), _hb(level_flux), _hb(up_top), _hb(down_surface),
             _hb(up_surface)))
+
+    def column_jacobian_scatter_workspace(self, n_layers, points):
+        """The doubles of a workspace with which column_jacobian_scatter_dev does ``points`` points in one pass
+        (lbl_column_jacobian_scatter_workspace: five numbers per level and point, whole tiles, at least one)."""
+        return self._scatter_workspace(self.lib.lbl_column_jacobian_scatter_workspace, n_layers, points)
+
+    def column_jacobian_scatter_dev(self, abs_coef, T, planck_linear, depth, range_min, range_max, n, scat_amount, scat_ext,
+                                    scat_ssa, scat_asym, delta_scaling, band_first, band_count, workspace, jac,
+                                    emissivity=1.0, I_surface=None, surface_T=0.0, I_top=None, term_abs_coef=(), term_layer=(),
+                                    ln_tau_spectra=None, T_spectra=None, up_top=None):
+        """Jacobians of the upward flux at the top through scattering layers (lbl_column_jacobian_scatter_dev):
+        column_flux_scatter_dev's column, scatterers, surface, ``I_top`` and bands, the terms as column_jacobian_dev takes
+        them and ``workspace`` of at least column_jacobian_scatter_workspace(layers, 1) doubles.  With NT = 2 for
+        ``planck_linear`` 1 and 1 otherwise, ``jac`` receives len(band_first) x (3 + (1 + NT + scatterers) L + terms) band
+        sums [band][F, dF/dT_s, dF/de, L x dF/d ln tau, NT L x dF/dT (per layer; NT = 2: bottom, top edge), scatterers x L
+        dF/d ln amount, terms]; ``ln_tau_spectra`` (L x n), ``T_spectra`` (NT L x n) and ``up_top`` (n) are optional."""
+        T = self._scatter_T("column_jacobian_scatter_dev", T, planck_linear, abs_coef)
+        scat = self._scatter_args("column_jacobian_scatter_dev", abs_coef, scat_amount, scat_ext, scat_ssa, scat_asym)
+        if len(term_abs_coef) != len(term_layer):
+            raise ValueError("column_jacobian_scatter_dev: one layer per term")
+        self.check(self.lib.lbl_column_jacobian_scatter_dev(
+            self.h, len(abs_coef), _arr(_P, [b.h for b in abs_coef]), T, int(planck_linear),
+            _arr(C.c_double, [float(d) for d in depth]), float(range_min), float(range_max), int(n), _hb(I_surface),
+            float(surface_T), _hb(I_top), *scat, int(delta_scaling), len(band_first),
+            _arr(C.c_int64, [int(f) for f in band_first]), _arr(C.c_int64, [int(c) for c in band_count]),
+            *self._emissivity_args(emissivity), *self._term_args(term_abs_coef, term_layer), _hb(workspace), _hb(jac),
+            _hb(ln_tau_spectra), _hb(T_spectra), _hb(up_top)))
 
     def column_radiance_scatter_workspace(self, n_layers, points):
         """The doubles of a workspace with which column_radiance_scatter_dev does ``points`` points in one pass

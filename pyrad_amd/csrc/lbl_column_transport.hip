@@ -4,8 +4,9 @@
 // and lbl_ray_jacobian_surface_dev, of the linear-source variants lbl_column_flux_linear_dev and lbl_ray_radiance_linear_dev, and
 // of their Jacobians lbl_column_jacobian_linear_dev and lbl_ray_jacobian_linear_dev, of the direct solar beam,
 // lbl_column_solar_dev, of its two-stream multiple scattering, lbl_column_twostream_dev, of the thermal fluxes through
-// scattering layers, lbl_column_flux_scatter_dev, and of the radiances through them, lbl_column_radiance_scatter_dev.
-// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j, K5k, K5l, K5m and K5n of lbl_kernels.hip; the context's internals
+// scattering layers, lbl_column_flux_scatter_dev, of its Jacobians, lbl_column_jacobian_scatter_dev, and of the radiances
+// through them, lbl_column_radiance_scatter_dev.
+// The kernels are K5c, K5d, K5e, K5f, K5g, K5h, K5i, K5j, K5k, K5l, K5m, K5n, K5o and K5p of lbl_kernels.hip; the context's internals
 // are reached through the hooks at the end of lbl_api.hip, so that lbl_api.hip builds on its own (tests/host_shim) without
 // this file's launchers.
 #include "../../include/pyrad_hip.h"
@@ -434,12 +435,12 @@ static void fill_scatter_part(ScatterPart* a, lbl_buffer* emissivity, double emi
 
 // The launch sequence of K5l and K5m on a checked argument block: the partial scratch, the block uploaded, the spectra zeroed,
 // then every band in passes of as many points as the workspace holds, the band's partial slots zeroed first and reduced after
-// its last pass.  `rows` level sums per band; `variant` picks the downward kernel (K5l: n_beams; K5m: bool linear).
+// its last pass.  `nv` values per band (K5l, K5m: the level sums; K5p: jac's rows); `variant` picks the downward kernel (K5l:
+// n_beams; K5m, K5p: bool linear).
 template <class Args, class Variant>
-static int run_scatter_bands(lbl_ctx* ctx, const Args* a, Variant variant, int rows, int64_t n, int n_bands,
-                             const int64_t* band_first, const int64_t* band_count, std::initializer_list<double*> spectra,
+static int run_scatter_bands(lbl_ctx* ctx, const Args* a, Variant variant, int nv, int64_t n, int n_bands,
+                             const int64_t* band_first, const int64_t* band_count, const std::vector<double*>& spectra,
                              lbl_buffer* level_flux) {
-    const int nv = rows * (a->n_layers + 1);
     const int64_t max_count = *std::max_element(band_count, band_count + n_bands);
     int rc;
     void* partial = nullptr;
@@ -457,7 +458,7 @@ static int run_scatter_bands(lbl_ctx* ctx, const Args* a, Variant variant, int r
         for (int64_t done = 0; done < band_count[b]; done += a->ws_points)
             launch_scatter_pass((const Args*)d_args, variant, band_first[b], band_first[b] + done,
                                 std::min<int64_t>(a->ws_points, band_count[b] - done), slots, (double*)partial, s);
-        launch_scatter_final(rows, a->n_layers, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
+        launch_scatter_final_values(nv, slots, (const double*)partial, buffer_data(level_flux) + (size_t)b * nv, s);
     }
     COLUMN_HIP_TRY(ctx, hipGetLastError());
     return LBL_OK;
@@ -556,7 +557,7 @@ extern "C" int lbl_column_twostream_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* 
                                      scat_ext, scat_ext_all, scat_ssa, scat_ssa_all, scat_asym, scat_asym_all, delta_scaling,
                                      emissivity, emissivity_all, workspace, up_top, down_surface, direct_surface, up_surface)))
         return rc;
-    return run_scatter_bands(ctx, a, n_beams, 3, n, n_bands, band_first, band_count,
+    return run_scatter_bands(ctx, a, n_beams, nv, n, n_bands, band_first, band_count,
                              {a->up_top, a->down_surface, a->direct_surface, a->up_surface}, level_flux);
 } LBL_GUARD_END(ctx)
 
@@ -583,14 +584,15 @@ static int check_scatter_column_head(lbl_ctx* ctx, const char* what, ScatterFlux
     return LBL_OK;
 }
 
-// Tail: the optional buffers (up_surface: nullptr for K5n), the emissivity, K5l's scatterers and workspace; then I_top and the
-// scatter part filled.
+// Tail: the optional buffers (up_surface: nullptr for K5n), the emissivity, K5l's scatterers and workspace (`quantities`
+// numbers per level and point: K5p's has five); then I_top and the scatter part filled.
 static int check_scatter_column_tail(lbl_ctx* ctx, ScatterFluxArgs* a, int n_layers, int64_t n, lbl_buffer* I_top, int n_scat,
                                      const double* scat_amount, lbl_buffer* const* scat_ext, const double* scat_ext_all,
                                      lbl_buffer* const* scat_ssa, const double* scat_ssa_all, lbl_buffer* const* scat_asym,
                                      const double* scat_asym_all, int delta_scaling, lbl_buffer* emissivity,
                                      double emissivity_all, lbl_buffer* workspace, lbl_buffer* up_top,
-                                     lbl_buffer* down_surface, lbl_buffer* up_surface) {
+                                     lbl_buffer* down_surface, lbl_buffer* up_surface,
+                                     int quantities = kScatterFluxQuantities) {
     int rc;
     if ((rc = ctx_check_buffer(ctx, I_top, n, "I_top", false))) return rc;
     if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
@@ -601,7 +603,7 @@ static int check_scatter_column_tail(lbl_ctx* ctx, ScatterFluxArgs* a, int n_lay
                                scat_asym, scat_asym_all)))
         return rc;
     int64_t ws_points = 0;
-    if ((rc = check_workspace(ctx, workspace, kScatterFluxQuantities, n_layers, &ws_points))) return rc;
+    if ((rc = check_workspace(ctx, workspace, quantities, n_layers, &ws_points))) return rc;
     a->I_top = I_top ? buffer_data(I_top) : nullptr;
     fill_scatter_part(a, emissivity, emissivity_all, workspace, ws_points, up_top, down_surface, up_surface, delta_scaling);
     return LBL_OK;
@@ -631,7 +633,7 @@ extern "C" int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffe
                                         scat_ssa_all, scat_asym, scat_asym_all, delta_scaling, emissivity, emissivity_all,
                                         workspace, up_top, down_surface, up_surface)))
         return rc;
-    return run_scatter_bands(ctx, a, planck_linear != 0, 2, n, n_bands, band_first, band_count,
+    return run_scatter_bands(ctx, a, planck_linear != 0, 2 * (n_layers + 1), n, n_bands, band_first, band_count,
                              {a->up_top, a->down_surface, a->up_surface}, level_flux);
 } LBL_GUARD_END(ctx)
 
@@ -742,35 +744,46 @@ extern "C" int lbl_column_beam_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buff
 // argument block filled; `head` values per band come before the layers' (2, or 3 with dF/de).  `edges` temperatures per
 // layer in T, as many temperature values per layer and band and rows per layer in jac_T_spectra: 1, or 2 with the linear
 // source (lbl_column_jacobian_linear_dev), where rT receives the bottom edges'.
+// The terms and the outputs of every column Jacobian call (K5d, K5h, K5j, K5p), `nv0` values per band ahead of the terms': the
+// term count, jac and the two optional spectra (`edges` temperature rows per layer), then every term; the terms sorted by layer (stable) into
+// term_k, term_slot and layer_term (zeroed by the caller): layer l reads [layer_term[l], layer_term[l + 1]).
+static int check_jacobian_terms(lbl_ctx* ctx, int nv0, int edges, int n_layers, int64_t n, int n_bands, int n_terms,
+                                lbl_buffer* const* term_abs_coef, const int32_t* term_layer, lbl_buffer* jac,
+                                lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra, const double** term_k,
+                                int32_t* term_slot, int32_t* layer_term) {
+    int rc;
+    if (n_terms < 0 || n_terms > kMaxJacobianTerms)
+        return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d molecule terms", kMaxJacobianTerms);
+    if (n_terms > 0 && (!term_abs_coef || !term_layer)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
+    if ((rc = ctx_check_buffer(ctx, jac, (int64_t)n_bands * (nv0 + n_terms), "jac", true))) return rc;
+    if ((rc = ctx_check_buffer(ctx, jac_ln_tau_spectra, (int64_t)n_layers * n, "jac_ln_tau_spectra", false))) return rc;
+    if ((rc = ctx_check_buffer(ctx, jac_T_spectra, (int64_t)edges * n_layers * n, edges == 1 ? "jac_T_spectra" : "jac_T_edge_spectra", false)))
+        return rc;
+    for (int t = 0; t < n_terms; ++t) {
+        if (term_layer[t] < 0 || term_layer[t] >= n_layers)
+            return column_fail(ctx, LBL_ERR_BAD_ARG, "term %d: layer %d outside [0, %d)", t, (int)term_layer[t], n_layers);
+        if ((rc = ctx_check_buffer(ctx, term_abs_coef[t], n, "term_abs_coef", true))) return rc;
+        ++layer_term[term_layer[t] + 1];
+    }
+    for (int l = 0; l < n_layers; ++l) layer_term[l + 1] += layer_term[l];
+    std::vector<int32_t> fill(layer_term, layer_term + std::max(n_layers, 1));
+    for (int t = 0; t < n_terms; ++t) {
+        const int pos = fill[term_layer[t]]++;
+        term_k[pos] = buffer_data(term_abs_coef[t]);
+        term_slot[pos] = t;
+    }
+    return LBL_OK;
+}
+
 static int check_jacobian(lbl_ctx* ctx, JacArgs* a, int head, int n_layers, const double* T, int64_t n, double surface_T,
                           int n_angles, const double* weight, int n_bands, int n_terms, lbl_buffer* const* term_abs_coef,
                           const int32_t* term_layer, lbl_buffer* jac, lbl_buffer* jac_ln_tau_spectra,
                           lbl_buffer* jac_T_spectra, int edges = 1) {
     int rc;
-    if (n_terms < 0 || n_terms > kMaxJacobianTerms)
-        return column_fail(ctx, LBL_ERR_BAD_ARG, "at most %d molecule terms", kMaxJacobianTerms);
-    if (n_terms > 0 && (!term_abs_coef || !term_layer)) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL term list");
-    const int nv = jacobian_slots(head, edges, n_layers, n_terms);
-    if ((rc = ctx_check_buffer(ctx, jac, (int64_t)n_bands * nv, "jac", true))) return rc;
-    if ((rc = ctx_check_buffer(ctx, jac_ln_tau_spectra, (int64_t)n_layers * n, "jac_ln_tau_spectra", false))) return rc;
-    if ((rc = ctx_check_buffer(ctx, jac_T_spectra, (int64_t)edges * n_layers * n, edges == 1 ? "jac_T_spectra" : "jac_T_edge_spectra", false)))
+    if ((rc = check_jacobian_terms(ctx, jacobian_slots(head, edges, n_layers, 0), edges, n_layers, n, n_bands, n_terms,
+                                   term_abs_coef, term_layer, jac, jac_ln_tau_spectra, jac_T_spectra, a->term_k, a->term_slot,
+                                   a->layer_term)))
         return rc;
-    // the molecule terms, sorted by layer (stable): layer l reads [layer_term[l], layer_term[l + 1])
-    for (int t = 0; t < n_terms; ++t) {
-        if (term_layer[t] < 0 || term_layer[t] >= n_layers)
-            return column_fail(ctx, LBL_ERR_BAD_ARG, "term %d: layer %d outside [0, %d)", t, (int)term_layer[t], n_layers);
-        if ((rc = ctx_check_buffer(ctx, term_abs_coef[t], n, "term_abs_coef", true))) return rc;
-        ++a->layer_term[term_layer[t] + 1];
-    }
-    for (int l = 0; l < n_layers; ++l) a->layer_term[l + 1] += a->layer_term[l];
-    {
-        std::vector<int32_t> fill(a->layer_term, a->layer_term + std::max(n_layers, 1));
-        for (int t = 0; t < n_terms; ++t) {
-            const int pos = fill[term_layer[t]]++;
-            a->term_k[pos] = buffer_data(term_abs_coef[t]);
-            a->term_slot[pos] = t;
-        }
-    }
     for (int l = 0; l < n_layers; ++l) a->rT[l] = 1.0 / T[edges * l];
     for (int k = 0; k < n_angles; ++k) a->wrmu[k] = weight[k] * a->rmu[k];
     a->r_surface_T = surface_T > 0 ? 1.0 / surface_T : 0.0;
@@ -887,6 +900,59 @@ extern "C" int lbl_column_jacobian_linear_dev(lbl_ctx* ctx, int n_layers, lbl_bu
                                  T_edge, depth, range_min, range_max, n, I_surface, surface_T, I_top, n_angles, mu, weight,
                                  n_bands, band_first, band_count, emissivity, emissivity_all, reflection, n_terms,
                                  term_abs_coef, term_layer, jac, jac_ln_tau_spectra, jac_T_edge_spectra, jac_e_spectrum);
+} LBL_GUARD_END(ctx)
+
+extern "C" int lbl_column_jacobian_scatter_workspace(int n_layers, int64_t points, int64_t* doubles) {
+    return scatter_workspace(kScatterJacQuantities, n_layers, points, doubles);
+}
+
+// K5p: K5m's checks of the shared arguments around the terms' and the outputs' (check_jacobian_terms); the launch sequence
+// is K5l's over jac's rows.  The spectra are zeroed row by row (n points each), as run_scatter_bands zeroes K5m's.
+extern "C" int lbl_column_jacobian_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffer* const* abs_coef, const double* T,
+                                               int planck_linear, const double* depth, double range_min, double range_max,
+                                               int64_t n, lbl_buffer* I_surface, double surface_T, lbl_buffer* I_top,
+                                               int n_scat, const double* scat_amount, lbl_buffer* const* scat_ext,
+                                               const double* scat_ext_all, lbl_buffer* const* scat_ssa,
+                                               const double* scat_ssa_all, lbl_buffer* const* scat_asym,
+                                               const double* scat_asym_all, int delta_scaling, int n_bands,
+                                               const int64_t* band_first, const int64_t* band_count, lbl_buffer* emissivity,
+                                               double emissivity_all, int n_terms, lbl_buffer* const* term_abs_coef,
+                                               const int32_t* term_layer, lbl_buffer* workspace, lbl_buffer* jac,
+                                               lbl_buffer* jac_ln_tau_spectra, lbl_buffer* jac_T_spectra,
+                                               lbl_buffer* up_top) try {
+    if (!ctx) return comm_fail(nullptr, LBL_ERR_BAD_ARG, "ctx is NULL");
+    std::vector<char> blk(sizeof(ScatterJacArgs), 0);
+    ScatterJacArgs* a = (ScatterJacArgs*)blk.data();
+    int rc;
+    if ((rc = check_scatter_column_head(ctx, "scattering Jacobians", a, n_layers, abs_coef, T, planck_linear, depth, range_min,
+                                        range_max, n, I_surface, surface_T, n_scat, scat_amount, delta_scaling, n_bands,
+                                        band_first, band_count)))
+        return rc;
+    const int edges = planck_linear ? 2 : 1;
+    if ((rc = check_jacobian_terms(ctx, scatter_jacobian_slots(edges, n_layers, n_scat, 0), edges, n_layers, n, n_bands, n_terms,
+                                   term_abs_coef, term_layer, jac, jac_ln_tau_spectra, jac_T_spectra, a->term_k, a->term_slot,
+                                   a->layer_term)))
+        return rc;
+    if ((rc = check_scatter_column_tail(ctx, a, n_layers, n, I_top, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa,
+                                        scat_ssa_all, scat_asym, scat_asym_all, delta_scaling, emissivity, emissivity_all,
+                                        workspace, up_top, nullptr, nullptr, kScatterJacQuantities)))
+        return rc;
+    for (int l = 0; l < n_layers; ++l) {
+        a->rT[l] = 1.0 / T[edges * l];
+        a->rT_top[l] = 1.0 / T[edges * l + edges - 1];
+    }
+    a->r_surface_T = surface_T > 0 ? 1.0 / surface_T : 0.0;
+    a->ln_tau_spec = jac_ln_tau_spectra ? buffer_data(jac_ln_tau_spectra) : nullptr;
+    a->T_spec = jac_T_spectra ? buffer_data(jac_T_spectra) : nullptr;
+    a->n_terms = n_terms;
+    a->n_scat = n_scat;
+    std::vector<double*> spectra{a->up_top};
+    for (int l = 0; l < n_layers; ++l) {
+        if (a->ln_tau_spec) spectra.push_back(a->ln_tau_spec + (size_t)l * (size_t)n);
+        for (int r = 0; r < edges && a->T_spec; ++r) spectra.push_back(a->T_spec + ((size_t)edges * l + r) * (size_t)n);
+    }
+    return run_scatter_bands(ctx, a, planck_linear != 0, scatter_jacobian_slots(edges, n_layers, n_scat, n_terms), n, n_bands,
+                             band_first, band_count, spectra, jac);
 } LBL_GUARD_END(ctx)
 
 static size_t round8(size_t b) { return (b + 7) & ~(size_t)7; }

@@ -427,6 +427,31 @@ struct ScatterFluxArgs : ColumnRT, ScatterPart {
 void launch_scatter_pass(const ScatterFluxArgs* d_args, bool linear, long long band_first, long long first, long long count,
                          int slots, double* partial, hipStream_t s);
 
+// Jacobians of the outgoing flux through scattering layers (K5p, lbl_column_transport.hip: lbl_column_jacobian_scatter_dev):
+// K5m's downward walk, which also writes Tu (up_L = Tu_i up_i + ...) as a fifth number per level, then one upward walk that
+// recomputes each layer, differentiates it and forms every row.  Values per band: [F, dF/dT_s, dF/de, L x d ln tau,
+// edges L x dT (layer by layer), n_scat x L d ln amount, n_terms x d ln n].
+constexpr int kScatterJacQuantities = 5;   // workspace[q][level][point]: K5m's four, Tu
+constexpr int scatter_jacobian_slots(int edges, int n_layers, int n_scat, int n_terms) {
+    return 3 + (1 + edges + n_scat) * n_layers + n_terms;
+}
+constexpr int kScatterJacMaxSlots = scatter_jacobian_slots(2, kMaxLayers, kMaxScatterers, kMaxJacobianTerms);
+struct ScatterJacArgs : ScatterFluxArgs {
+    double rT[kMaxLayers];              // 1 / T_l (planck_linear: at the bottom edge)
+    double rT_top[kMaxLayers];          // planck_linear: 1 / T at the top edge
+    double r_surface_T;                 // 1 / surface_T (used when I_surface == nullptr)
+    double* ln_tau_spec;                // optional: L x n spectral dF/d ln tau_l
+    double* T_spec;                     // optional: edges L x n spectral dF/dT
+    const double* term_k[kMaxJacobianTerms];   // the molecule terms sorted by layer (stable), as JacArgs'
+    int32_t term_slot[kMaxJacobianTerms];
+    int32_t layer_term[kMaxLayers + 1];
+    int32_t n_terms, n_scat;
+};
+// K5p's pass and final reduction: the slots are twostream_partials', nv = scatter_jacobian_slots(...)
+void launch_scatter_pass(const ScatterJacArgs* d_args, bool linear, long long band_first, long long first, long long count,
+                         int slots, double* partial, hipStream_t s);
+void launch_scatter_final_values(int nv, int slots, const double* partial, double* values, hipStream_t s);
+
 // Radiances through scattering layers (K5n, lbl_column_transport.hip: lbl_column_radiance_scatter_dev): K5m's column, whose
 // first kernel runs as it stands on the ScatterFluxArgs part of this block (the workspace is K5m's, four numbers per level),
 // then one upward walk that integrates the two-stream source function along every view.  No band sums: up_surface stays

@@ -39,6 +39,9 @@
 //                              closed form per layer and view (Atmosphere.radianceTwoStream; beyond the reference)
 //   K5o beam_view_kernel      K5l's column with one sun seen along up to 16 views: K5n's integrals with the beam's single
 //                              scattering in the source function (Atmosphere.solarRadianceTwoStream; beyond the reference)
+//   K5p scatter_jacobian_down_kernel, scatter_jacobian_up_kernel   the derivatives of K5m's upward flux at the top: its
+//                              downward walk with one more number per level, then one adjoint walk that recomputes and
+//                              differentiates every layer (Atmosphere.jacobiansTwoStream; beyond the reference)
 //   K7 line_survey_kernel     pyradClasses.py:409-428
 //
 // Design notes (DESIGN.md has the long form).  The reference snaps every line centre to a
@@ -4556,16 +4559,16 @@ __device__ __forceinline__ double emitting_surface_up(const ScatterFluxArgs& A, 
     return (e * (kPi * Is) + albedo * Ds) / (1.0 - albedo * Rs);
 }
 
-template <bool LINEAR>
-__global__ __launch_bounds__(256) void scatter_flux_down_kernel(const ScatterFluxArgs* __restrict__ Ap, long long first,
-                                                                long long count) {
+// K5m's downward walk; `level` is twostream_down_frame's hook (K5m: nothing; K5p: Tu per level)
+template <bool LINEAR, class Level>
+__device__ __forceinline__ void scatter_flux_down_walk(const ScatterFluxArgs& A, unsigned threads, long long first, long long count,
+                                                       Level level) {
 #pragma clang fp contract(off)
-    const ScatterFluxArgs& A = *Ap;
     constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
     const int L = A.n_layers;
     double nu = 0.0;
     double B_above = 0.0;                           // LINEAR: pi B at the bottom edge of the layer above
-    twostream_down_frame(A, blockDim.x, first, count,
+    twostream_down_frame(A, threads, first, count,
         [&](long long j) {
             nu = linspace_at(j, A.n, A.start, A.stop, A.step);
             return A.I_top ? kPi * load_global_f64(A.I_top, j) : 0.0;
@@ -4582,7 +4585,13 @@ __global__ __launch_bounds__(256) void scatter_flux_down_kernel(const ScatterFlu
             }
             if (lay.empty || lay.conservative || lay.ta == 0.0) P = Q = 0.0;       // (nothing absorbs: nothing emits)
         },
-        [](int, auto&) {});
+        level);
+}
+
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void scatter_flux_down_kernel(const ScatterFluxArgs* __restrict__ Ap, long long first,
+                                                                long long count) {
+    scatter_flux_down_walk<LINEAR>(*Ap, blockDim.x, first, count, [](int, auto&) {});
 }
 
 __global__ __launch_bounds__(256) void scatter_flux_up_kernel(const ScatterFluxArgs* __restrict__ Ap, long long tile0,
@@ -4985,8 +4994,8 @@ __global__ __launch_bounds__(256) void linear_ray_kernel(const LinearRayArgs* __
 // ----------------------------------------------------------------------------------------
 // A layer's terms: term_k Gd per point, Gd = depth G, summed into the terms' slots, which begin at slot0 (in K5h and K5j
 // walks 2 and 3 each add their leg)
-template <int NP, class Add>
-__device__ __forceinline__ void jacobian_terms(const JacArgs& A, int l, long long j, bool active, const double (&Gd)[NP],
+template <int NP, class Args, class Add>
+__device__ __forceinline__ void jacobian_terms(const Args& A, int l, long long j, bool active, const double (&Gd)[NP],
                                                int slot0, Add add) {
 #pragma clang fp contract(off)
     for (int t = A.layer_term[l]; t < A.layer_term[l + 1]; ++t) {
@@ -6246,6 +6255,238 @@ void launch_solar(const SolarArgs* d_args, int n_layers, int n_beams, int n_angl
     });
 }
 
+// ----------------------------------------------------------------------------------------
+// K5p: Jacobians of the outgoing flux through scattering layers (lbl_column_jacobian_scatter_dev; the semantics and the
+// derivation are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// The layer relations are linear in the fluxes, so F = up_L answers a change of one layer through two weights: with the stack
+// above level l + 1 (Rs', Tu' from the downward walk) and the stack below level l (A_l, built here going up)
+//     w1 = Tu' / ((1 - R Rs') - T^2 A_l Rs' / (1 - R A_l)),   w2 = w1 T A_l / (1 - R A_l)
+//     dF = w1 (dT up_l + dR dn_(l+1) + dP) + w2 (dT dn_(l+1) + dR up_l + dQ).
+//   scatter_jacobian_down_kernel<LINEAR>  K5m's downward walk (scatter_flux_down_walk: the same code, the same bits) with
+//                                         Tu_L = 1, Tu_i = Tu_(i+1) U1_(i+1) as a fifth number per level.
+//   scatter_jacobian_up_kernel<LINEAR>    the surface and its two rows, then bottom to top per layer: the layer recomputed as
+//                                         K5n does (twostream_layer), p dX/dp and q dX/dq of X = R, T, Ab and h in closed form
+//                                         (p = D ta, q = D (t - tsg); nothing is divided by sqrt(ta) or sqrt(q)), the two
+//                                         weights, the layer's rows and its terms (jacobian_terms).
+// One point per thread.  A workgroup takes the tiles of its partial slot in ascending order, as K5l's upward kernel does; per
+// tile every row is one wave_sum whose result lane 0 of each wave stores at acc[wave][row], the row order being jac's: F,
+// dF/dT_s, dF/de, L d ln tau, NT L temperatures (NT per layer), n_scat x L amounts, the terms.  Every row is stored once per
+// tile; then the four waves are added in a fixed order into the tile's slot.  4 x kScatterJacMaxSlots doubles of LDS
+// (45,152 bytes).  A lane beyond the pass's points computes the tile's first point again and adds zeros.
+// pi B and pi dB/dT at the bottom and top edge of layer l on the way up; LINEAR: the bottom edge is the top edge of the layer
+// below where the two temperatures are equal (a workgroup-uniform test), and then comes from cB, cdB
+template <bool LINEAR>
+__device__ __forceinline__ void planck_edge_pair_dT(const ScatterJacArgs& A, double nu, double pa_n, int l, double& cB,
+                                                    double& cdB, double& Bb, double& Bt, double& dBb, double& dBt) {
+#pragma clang fp contract(off)
+    double d;
+    if (!LINEAR) {
+        Bb = Bt = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT[l], 0.0, A.rT[l], &d);
+        dBb = dBt = kPi * d;
+        return;
+    }
+    if (l > 0 && A.pbkT[l] == A.pbkT_top[l - 1]) {
+        Bb = cB; dBb = cdB;
+    } else {
+        Bb = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT[l], 0.0, A.rT[l], &d);
+        dBb = kPi * d;
+    }
+    Bt = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT_top[l], 0.0, A.rT_top[l], &d);
+    dBt = kPi * d;
+    cB = Bt; cdB = dBt;
+}
+
+// p dX/dp and q dX/dq of a layer's R, T and Ab, p = D ta = r^2, q = D (t - tsg) = s^2: with x = r s, E = exp(-x),
+// Gam = (s - r) / (s + r), G = r s / (s + r)^2 = (1 - Gam^2) / 4, oE = 1 - E^2 and N = 1 - Gam^2 E^2 = 4 G + Gam^2 oE
+//     p R_p = G (-oE (1 + Gam^2 E^2) + 4 x Gam E^2) / N^2      q R_q = G (oE (1 + Gam^2 E^2) + 4 x Gam E^2) / N^2
+//     p T_p = 2 G E (Gam oE - x (1 + Gam^2 E^2)) / N^2         q T_q = -2 G E (Gam oE + x (1 + Gam^2 E^2)) / N^2
+//     p Ab_p = G (oE + 2 x E) / (1 + Gam E)^2                  q Ab_q = -G (oE - 2 x E) / (1 + Gam E)^2
+// (G / N <= 1 / 4: no quotient grows in a thin layer).  den == 0 (and N == 0): the branch's R = y / (1 + y), T = 1 / (1 + y),
+// y = (p + q) / 2, Ab = 0.
+struct TwoStreamLayerD {
+    double pR, qR, pT, qT, pAb, qAb;
+};
+__device__ __forceinline__ TwoStreamLayerD twostream_layer_partials(const TwoStreamLayer& lay, double p, double q) {
+#pragma clang fp contract(off)
+    TwoStreamLayerD Y;
+    const double r = sqrt(p), s = sqrt(q);
+    const double sr = s + r;
+    const double Gam = (s - r) / sr;
+    const double G = (r / sr) * (s / sr);
+    const double x = r * s;
+    const double E = exp_neg_budget(x);
+    const double oE = -expm1(-2.0 * x);
+    const double GE = Gam * E;
+    const double N = 4.0 * G + (Gam * Gam) * oE;
+    if (lay.conservative || !(N > 0.0)) {
+        const double i1 = 1.0 / (1.0 + 0.5 * (p + q));
+        Y.pR = (0.5 * p) * (i1 * i1); Y.qR = (0.5 * q) * (i1 * i1);
+        Y.pT = -Y.pR; Y.qT = -Y.qR;
+        Y.pAb = 0.0; Y.qAb = 0.0;
+        return Y;
+    }
+    const double gN = (G / N) / N;
+    const double m = 1.0 + GE * GE;
+    const double xE = x * E;
+    Y.pR = gN * (4.0 * (xE * GE) - oE * m);
+    Y.qR = gN * (4.0 * (xE * GE) + oE * m);
+    Y.pT = (2.0 * gN) * (GE * oE - xE * m);
+    Y.qT = -(2.0 * gN) * (GE * oE + xE * m);
+    const double S = G / ((1.0 + GE) * (1.0 + GE));
+    Y.pAb = S * (oE + 2.0 * xE);
+    Y.qAb = -(S * (oE - 2.0 * xE));
+    return Y;
+}
+
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void scatter_jacobian_down_kernel(const ScatterJacArgs* __restrict__ Ap, long long first,
+                                                                    long long count) {
+#pragma clang fp contract(off)
+    const int L = Ap->n_layers;
+    double Tu = 1.0;
+    scatter_flux_down_walk<LINEAR>(*Ap, blockDim.x, first, count, [&](int i, auto& ws) {
+        if (i < L) Tu = Tu * ws(2, i + 1);
+        ws(4, i) = Tu;
+    });
+}
+
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void scatter_jacobian_up_kernel(const ScatterJacArgs* __restrict__ Ap, long long tile0,
+                                                                  long long first, long long count, int slots,
+                                                                  double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    constexpr int NT = LINEAR ? 2 : 1;
+    constexpr int kSlot = kScatterJacMaxSlots;
+    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+    __shared__ double acc[4 * kSlot];               // [wave][row of jac]
+    const ScatterJacArgs& A = *Ap;
+    const int L = A.n_layers, levels = L + 1, C = A.n_scat;
+    const int nv = scatter_jacobian_slots(NT, L, C, A.n_terms);
+    const int row_T = 3 + L, row_scat = row_T + NT * L, row_term = row_scat + C * L;
+    const long long row = A.ws_points;
+    double* const my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const double nan = __builtin_nan("");
+    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions)
+    for (long long tile = blockIdx.x; tile < tiles; tile += slots) {
+        const long long q0 = tile * kTwoStreamTile;
+        const bool active = q0 + threadIdx.x < count;
+        const long long qq = active ? q0 + threadIdx.x : q0;
+        const long long j = first + qq;
+        const double* const W = A.workspace + qq;
+        auto ws = [&](int v, int i) { return W[((long long)v * levels + i) * row]; };
+        auto add = [&](int slot, double v) {
+            const double s = wave_sum(active ? nan_to_num(v) : 0.0);
+            if (lane0) my[slot] = s;
+        };
+        // (jacobian_terms hands over a value that is masked and nan_to_num'ed already)
+        auto add_term = [&](int slot, double v) {
+            const double s = wave_sum(v);
+            if (lane0) my[slot] = s;
+        };
+        double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
+        scatterer_numbers(A, j, al, si, et);
+        const double nu = linspace_at(j, A.n, A.start, A.stop, A.step);
+        const double pa_n = A.pa * (nu * nu * nu);
+        double Rs = ws(0, 0), Ds = ws(1, 0);
+        const bool bad = isnan(Rs) || isnan(Ds);
+        // the surface: up_0 = (e Es + (1 - e) Ds_0) / c0, c0 = 1 - (1 - e) Rs_0
+        const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
+        double up = emitting_surface_up(A, j, nu, Rs, Ds);
+        double dn = Rs * up + Ds;
+        {
+            double dBs = 0.0;
+            const double Is = A.I_surface ? A.I_surface[j]
+                                          : fold_planck<false, true>(false, nu, nu, pa_n, A.pbk_surface, 0.0, A.r_surface_T, &dBs);
+            const double gs = ws(4, 0) / (1.0 - (1.0 - e) * Rs);
+            add(1, bad ? nan : (gs * e) * (kPi * dBs));
+            add(2, bad ? nan : gs * (kPi * Is - dn));
+        }
+        double Al = 1.0 - e;                            // what the stack below level l reflects
+        double k = L > 0 ? load_global_f64(A.abs_coef[0], j) : 0.0;
+        double cB = 0.0, cdB = 0.0;                     // LINEAR: pi B and pi dB/dT at the top edge of the layer below
+        for (int l = 0; l < L; ++l) {
+            const double k_next = l + 1 < L ? load_global_f64(A.abs_coef[l + 1], j) : k;
+            const double depth = A.depth[l];
+            const TwoStreamLayer lay = twostream_layer(A, l, depth, k, al, si, et);
+            const double upB = up;
+            up = ws(2, l + 1) * up + ws(3, l + 1);
+            Rs = ws(0, l + 1); Ds = ws(1, l + 1);
+            dn = Rs * up + Ds;
+            const double R = lay.R, T = lay.T, Ab = lay.Ab;
+            const double TA = (T * Al) / (1.0 - R * Al);
+            const double w1 = ws(4, l + 1) / ((1.0 - R * Rs) - (T * TA) * Rs);
+            const double w2 = w1 * TA;
+            Al = R + T * TA;
+            double Bb, Bt, dBb, dBt;
+            planck_edge_pair_dT<LINEAR>(A, nu, pa_n, l, cB, cdB, Bb, Bt, dBb, dBt);
+            const double tq = lay.t - lay.tsg;
+            double pF = 0.0, qF = 0.0, gT[NT];
+#pragma unroll
+            for (int i = 0; i < NT; ++i) gT[i] = 0.0;
+            if (!lay.empty) {
+                const TwoStreamLayerD d = twostream_layer_partials(lay, D * lay.ta, D * tq);
+                double pP = 0.0, qP = 0.0, pQ = 0.0, qQ = 0.0;
+                if (!(lay.conservative || lay.ta == 0.0)) {        // (else nothing absorbs: P = Q = 0)
+                    if (LINEAR) {
+                        const double dq = D * tq;
+                        const double h = (Ab + 2.0 * R) / dq - T;
+                        const double ph = (d.pAb + 2.0 * d.pR) / dq - d.pT;
+                        const double qh = ((d.qAb + 2.0 * d.qR) - (Ab + 2.0 * R)) / dq - d.qT;
+                        const double dB = Bb - Bt;
+                        pP = Bt * d.pAb + dB * ph; pQ = Bb * d.pAb - dB * ph;
+                        qP = Bt * d.qAb + dB * qh; qQ = Bb * d.qAb - dB * qh;
+                        gT[0] = (w1 * h + w2 * (Ab - h)) * dBb;
+                        gT[NT - 1] = (w1 * (Ab - h) + w2 * h) * dBt;
+                    } else {
+                        pP = pQ = Bb * d.pAb;
+                        qP = qQ = Bb * d.qAb;
+                        gT[0] = ((w1 + w2) * Ab) * dBb;
+                    }
+                }
+                pF = w1 * ((d.pT * upB + d.pR * dn) + pP) + w2 * ((d.pT * dn + d.pR * upB) + pQ);
+                qF = w1 * ((d.qT * upB + d.qR * dn) + qP) + w2 * ((d.qT * dn + d.qR * upB) + qQ);
+            }
+            // per unit of ta and of t - tsg: dF/dta = fa + fq, dF/dts = fq, dF/dtsg = -fq
+            const double fa = lay.ta > 0.0 ? pF / lay.ta : 0.0;
+            const double fq = tq > 0.0 ? qF / tq : 0.0;
+            double Gd[1] = {depth * (fa + fq)};
+            double dtau = k * Gd[0];
+            if (bad) {
+                Gd[0] = dtau = nan;
+#pragma unroll
+                for (int i = 0; i < NT; ++i) gT[i] = nan;
+            }
+            if (active && A.ln_tau_spec) A.ln_tau_spec[(long long)l * A.n + j] = dtau;
+            add(3 + l, dtau);
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                if (active && A.T_spec) A.T_spec[(long long)(NT * l + i) * A.n + j] = gT[i];
+                add(row_T + NT * l + i, gT[i]);
+            }
+#pragma unroll
+            for (int c = 0; c < kMaxScatterers; ++c) {          // (n_scat is uniform over the workgroup)
+                if (c < C) {
+                    const double v = A.amount[c][l] * (al[c] * (fa + fq) + (si[c] - et[c]) * fq);
+                    add(row_scat + c * L + l, bad ? nan : v);
+                }
+            }
+            jacobian_terms<1>(A, l, j, active, Gd, row_term, add_term);
+            k = k_next;
+        }
+        if (bad) up = nan;
+        if (active && A.up_top) A.up_top[j] = up;
+        add(0, up);
+        __syncthreads();
+        double* const slot = partial + ((tile0 + tile) % slots) * nv;
+        for (int t = threadIdx.x; t < nv; t += blockDim.x)
+            slot[t] = slot[t] + ((acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]));
+        __syncthreads();
+    }
+}
+
 // K5l, K5m: the partial-sum slots of a band of `count` points
 int twostream_partials(long long count) {
     return (int)std::min<long long>(std::max<long long>((count + kTwoStreamTile - 1) / kTwoStreamTile, 1), kFluxMaxBlocks);
@@ -6287,9 +6528,22 @@ void launch_scatter_pass(const ScatterFluxArgs* d_args, bool linear, long long b
                  scatter_flux_up_kernel, band_first, first, count, slots, partial, s);
 }
 
+void launch_scatter_final_values(int nv, int slots, const double* partial, double* values, hipStream_t s) {
+    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, slots, nv, values);
+}
+
 void launch_scatter_final(int rows, int n_layers, int slots, const double* partial, double* level_flux, hipStream_t s) {
-    const int nv = rows * (n_layers + 1);
-    hipLaunchKernelGGL(column_flux_final_kernel, dim3(nv), dim3(256), 0, s, partial, slots, nv, level_flux);
+    launch_scatter_final_values(rows * (n_layers + 1), slots, partial, level_flux, s);
+}
+
+// K5p's pass: its downward kernel, then its upward kernel over the partial slots that the pass's tiles reach
+void launch_scatter_pass(const ScatterJacArgs* d_args, bool linear, long long band_first, long long first, long long count,
+                         int slots, double* partial, hipStream_t s) {
+    const auto down = linear ? scatter_jacobian_down_kernel<true> : scatter_jacobian_down_kernel<false>;
+    const auto up = linear ? scatter_jacobian_up_kernel<true> : scatter_jacobian_up_kernel<false>;
+    scatter_pass(d_args, [&](unsigned tiles) {
+        hipLaunchKernelGGL(down, dim3(tiles), dim3(kTwoStreamTile), 0, s, d_args, first, count);
+    }, up, band_first, first, count, slots, partial, s);
 }
 
 // f(std::integral_constant<int, NV>) for the view count rounded up to NV in {1, 2, 4, 8, 16}

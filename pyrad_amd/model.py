@@ -1815,11 +1815,13 @@ class Jacobians:
     From Atmosphere.jacobiansLinear only (else None): ``edgeTemperature``: (L, 2) dF/dT of the bottom and the top edge of
     every layer; ``levelTemperature``: (L + 1,) dF/d(level temperature), level i the top edge of layer i - 1 plus the bottom
     edge of layer i; ``levelTemperatureSpectrum``: (L + 1, n) with spectra.  ``temperature`` is then the chain through the
-    default level temperatures, or None when level temperatures were given, and temperatureSpectrum is None."""
+    default level temperatures, or None when level temperatures were given, and temperatureSpectrum is None.
+    From Atmosphere.jacobiansTwoStream only (else None): ``scatterers``: (C, L) dF/d ln amount of scatterer c in layer l."""
 
     def __init__(self, olr, surfaceTemperature, temperature, opticalDepth, molecules, moleculeNames, mu, weight,
                  temperatureSpectrum=None, opticalDepthSpectrum=None, temperatureAbsorption=None, emissivity=None,
-                 emissivitySpectrum=None, edgeTemperature=None, levelTemperature=None, levelTemperatureSpectrum=None):
+                 emissivitySpectrum=None, edgeTemperature=None, levelTemperature=None, levelTemperatureSpectrum=None,
+                 scatterers=None):
         self.olr = olr
         self.surfaceTemperature = surfaceTemperature
         self.temperature = temperature
@@ -1838,6 +1840,7 @@ class Jacobians:
         self.edgeTemperature = edgeTemperature
         self.levelTemperature = levelTemperature
         self.levelTemperatureSpectrum = levelTemperatureSpectrum
+        self.scatterers = scatterers
 
     def __repr__(self):
         return "Jacobians(layers=%d, angles=%d, olr=%s)" % (self.opticalDepth.shape[-1], len(self.mu), self.olr)
@@ -3302,6 +3305,91 @@ class Atmosphere(list):
         return Jacobians(olr, dTs, own[2] if chain is not None else None, dtau, mol, names, mu, weight,
                          opticalDepthSpectrum=tau_rows, temperatureAbsorption=dT_abs, emissivity=de, emissivitySpectrum=e_row,
                          edgeTemperature=own[0], levelTemperature=own[1], levelTemperatureSpectrum=lev_spec)
+
+    def jacobiansTwoStream(self, scatterers=(), deltaScaling=True, surfaceTemperature=None, surfaceSpectrum=None,
+                           topSpectrum=None, emissivity=1.0, planck="layer", levelTemperatures=None, bands=None, molecules=True,
+                           spectra=False, temperature="planck"):
+        """Analytic sensitivities of fluxesTwoStream()'s upward flux at the top: jacobians() / jacobiansLinear() through a
+        column that also scatters, and the sensitivity to every scatterer's amount (beyond the reference).  One adjoint pass
+        over the stacks that the forward solution builds (lbl_column_jacobian_scatter_dev, include/pyrad_hip.h): with the
+        stack above level l + 1 reflecting Rs' and passing Tu' of an upward flux to the top, and the surface with the layers
+        below level l reflecting A_l, a change of layer l alone moves the flux at the top by
+            dF = w1 (dT up_l + dR dn_(l+1) + dP) + w2 (dT dn_(l+1) + dR up_l + dQ)
+            w1 = Tu' / ((1 - R Rs') - T^2 A_l Rs' / (1 - R A_l))        w2 = w1 T A_l / (1 - R A_l)
+        where R, T, P, Q are the layer's reflectance, transmittance and sources as fluxesTwoStream() defines them, and
+        their derivatives to the layer's three depths are closed forms.
+
+        Arguments as fluxesTwoStream() takes them; ``molecules``, ``spectra`` and ``temperature`` as jacobians() takes
+        them.  Returns a Jacobians with mu = [1 / sqrt(3)] and weight = [pi]: ``olr`` (fluxesTwoStream()'s up at the top, bit
+        for bit), ``surfaceTemperature`` (None with a surface spectrum), ``emissivity``, ``opticalDepth`` (the gas of a layer
+        scaled), ``molecules``, and ``scatterers``, (C, L): dF/d ln amount of scatterer c in layer l, 0 where the amount is
+        0.  planck="layer": ``temperature`` (L,), the Planck part; planck="linear": ``edgeTemperature``,
+        ``levelTemperature`` and, over the default level temperatures, ``temperature`` as jacobiansLinear() gives them.
+        temperature="full" adds temperatureAbsorption through dk_l/dT.  With ``spectra`` also opticalDepthSpectrum and
+        temperatureSpectrum (planck="layer") or levelTemperatureSpectrum (planck="linear").  Without scatterers the result
+        is jacobians(angles=[(1 / sqrt(3), pi)], emissivity=..., reflection="lambertian") (jacobiansLinear()) to rounding.
+        Not differentiated: the scatterers' albedo and asymmetry, and the downward flux at the surface.  The workspace (five
+        numbers per level and point) stays with the atmosphere, at most 256 MiB.  Everything is validated (ValueError)
+        before the device is touched."""
+        if temperature not in ("planck", "full"):
+            raise ValueError("temperature: \"planck\" or \"full\", not %r" % (temperature,))
+        c = self._thermal_scatter_checks(surfaceTemperature, surfaceSpectrum, topSpectrum, bands, scatterers, deltaScaling,
+                                         emissivity, planck, levelTemperatures)
+        layers, n, first, linear = c.layers, c.n, c.layers[0], c.linear
+        chain = self._level_chain() if linear and (levelTemperatures is None or levelTemperatures is True) else None
+        names = [[m.name for m in L] for L in layers]
+        full = temperature == "full"
+        self._term_count(layers, molecules, full, full)
+        nl, nb, nc = len(layers), len(c.band_first), len(c.scat)
+        ctx = _ctx()
+        if ctx.option("sweep_ieee_divisions"):
+            raise ValueError("Jacobians exist in the sweeps' default arithmetic only (\"sweep_ieee_divisions\" 0)")
+        kbufs, plan = self._column_abs_coef(ctx, layers, n)
+        term_bufs, term_layer, n_mol_terms = self._term_buffers(ctx, layers, n, plan, molecules, full)
+        nt = 2 if linear else 1
+        o = 3 + (1 + nt + nc) * nl                   # (where the terms begin)
+        nv = o + len(term_bufs)
+        st = _kept_state(self, "_scatter_jacobian_state")
+        st.reserve(ctx, max(n, nb * nv))
+        # (the widest band in one pass)
+        columns, workspace, kw = self._thermal_scatter_uploads(ctx, st, c, ctx.column_jacobian_scatter_workspace,
+                                                               "_scatter_jacobian_workspace", max(c.band_count))
+        jac = st.buf(ctx, "jac")
+        ln_tau_spec, T_spec = self._jacobian_spectra(ctx, linear, nl, n) if spectra else (None, None)
+        ctx.column_jacobian_scatter_dev(kbufs, c.T, int(linear), c.depth, first.rangeMin, first.rangeMax, n, *columns,
+                                        int(bool(deltaScaling)), c.band_first, c.band_count, workspace, jac,
+                                        term_abs_coef=term_bufs, term_layer=term_layer, ln_tau_spectra=ln_tau_spec,
+                                        T_spectra=T_spec, **kw)
+        v = jac.download(nb * nv).reshape(nb, nv) * utils.BASE_RESOLUTION
+        mol = None
+        if molecules:
+            mol, at = [], o
+            for L in layers:
+                mol.append(v[:, at:at + len(L)])
+                at += len(L)
+            mol = _band_values(bands, mol)
+        at = 3 + (1 + nt) * nl
+        rows = [v[:, 0], v[:, 1], v[:, 2], v[:, 3:3 + nl], v[:, at:at + nc * nl].reshape(nb, nc, nl)]
+        if linear:
+            edge = v[:, 3 + nl:at].reshape(nb, nl, 2)
+            dlev = self._levels_of_edges(edge)
+            rows += [edge, dlev] + ([dlev @ chain] if chain is not None else [])
+        else:
+            rows.append(v[:, 3 + nl:at])
+        olr, dTs, de, dtau, dscat, *own = _band_values(bands, rows)
+        if c.surfaceSpectrum is not None:
+            dTs = None
+        T_rows = T_spec.download(nt * nl * n) if spectra else None
+        tau_rows = ln_tau_spec.download(nl * n).reshape(nl, n) if spectra else None
+        dT_abs = _band_values(bands, [v[:, o + n_mol_terms:]])[0] if full else None
+        if not linear:
+            return Jacobians(olr, dTs, own[0], dtau, mol, names, c.mu, c.weight,
+                             temperatureSpectrum=T_rows.reshape(nl, n) if spectra else None, opticalDepthSpectrum=tau_rows,
+                             temperatureAbsorption=dT_abs, emissivity=de, scatterers=dscat)
+        lev_spec = self._levels_of_edges(T_rows.reshape(nl, 2, n).transpose(2, 0, 1)).T.copy() if spectra else None
+        return Jacobians(olr, dTs, own[2] if chain is not None else None, dtau, mol, names, c.mu, c.weight,
+                         opticalDepthSpectrum=tau_rows, temperatureAbsorption=dT_abs, emissivity=de,
+                         edgeTemperature=own[0], levelTemperature=own[1], levelTemperatureSpectrum=lev_spec, scatterers=dscat)
 
     @staticmethod
     def _levels_of_edges(edge):
