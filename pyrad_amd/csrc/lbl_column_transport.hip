@@ -637,13 +637,12 @@ extern "C" int lbl_column_flux_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_buffe
                              {a->up_top, a->down_surface, a->up_surface}, level_flux);
 } LBL_GUARD_END(ctx)
 
-// the views of K5n and K5o (Args: ScatterRadianceArgs or BeamViewArgs): 1 .. limit cosines in (0, 1] with a direction each;
-// the block's entries beyond n_views get mu = 1, up
-template <class Args>
-static int check_views(lbl_ctx* ctx, Args* a, int limit, int n_views, const double* view_mu, const int32_t* view_down) {
-    if (n_views < 1 || n_views > limit) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d views", limit);
+// the views of K5n and K5o: 1 .. kMaxViews cosines in (0, 1] with a direction each; the block's entries beyond n_views get
+// mu = 1, up
+static int check_views(lbl_ctx* ctx, ViewPart* a, int n_views, const double* view_mu, const int32_t* view_down) {
+    if (n_views < 1 || n_views > kMaxViews) return column_fail(ctx, LBL_ERR_BAD_ARG, "1..%d views", kMaxViews);
     if (!view_mu || !view_down) return column_fail(ctx, LBL_ERR_BAD_ARG, "NULL view list");
-    for (int v = 0; v < limit; ++v) {
+    for (int v = 0; v < kMaxViews; ++v) {
         if (v < n_views && !(view_mu[v] > 0 && view_mu[v] <= 1))
             return column_fail(ctx, LBL_ERR_BAD_ARG, "view %d: mu must lie in (0, 1]", v);
         if (v < n_views && view_down[v] != 0 && view_down[v] != 1)
@@ -676,14 +675,14 @@ extern "C" int lbl_column_radiance_scatter_dev(lbl_ctx* ctx, int n_layers, lbl_b
                                         range_max, n, I_surface, surface_T, n_scat, scat_amount, delta_scaling, 1, &band_first,
                                         &band_count)))
         return rc;
-    if ((rc = check_views(ctx, a, kMaxScatterViews, n_views, view_mu, view_down))) return rc;
+    if ((rc = check_views(ctx, &a->views, n_views, view_mu, view_down))) return rc;
     if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_views * n, "radiance", true))) return rc;
     if ((rc = check_scatter_column_tail(ctx, a, n_layers, n, I_top, n_scat, scat_amount, scat_ext, scat_ext_all, scat_ssa,
                                         scat_ssa_all, scat_asym, scat_asym_all, delta_scaling, emissivity, emissivity_all,
                                         workspace, up_top, down_surface, nullptr)))
         return rc;
-    a->radiance = buffer_data(radiance);
-    a->n_views = n_views;
+    a->views.radiance = buffer_data(radiance);
+    a->views.n_views = n_views;
 
     void* d_args = nullptr;
     if ((rc = ctx_device_args(ctx, a, sizeof(ScatterRadianceArgs), &d_args))) return rc;
@@ -715,7 +714,7 @@ extern "C" int lbl_column_beam_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buff
                                      n_scat, scat_amount, delta_scaling)))
         return rc;
     if (n < 1) return column_fail(ctx, LBL_ERR_BAD_ARG, "the grid is empty");
-    if ((rc = check_views(ctx, a, kMaxBeamViews, n_views, view_mu, view_down))) return rc;
+    if ((rc = check_views(ctx, &a->views, n_views, view_mu, view_down))) return rc;
     if ((rc = ctx_check_buffer(ctx, S0, n, "S0", true))) return rc;
     if ((rc = ctx_check_buffer(ctx, radiance, (int64_t)n_views * n, "radiance", true))) return rc;
     if ((rc = ctx_check_buffer(ctx, up_top, n, "up_top", false))) return rc;
@@ -726,9 +725,9 @@ extern "C" int lbl_column_beam_radiance_dev(lbl_ctx* ctx, int n_layers, lbl_buff
                                      scat_ext, scat_ext_all, scat_ssa, scat_ssa_all, scat_asym, scat_asym_all, delta_scaling,
                                      emissivity, emissivity_all, workspace, up_top, down_surface, direct_surface, nullptr)))
         return rc;
-    a->radiance = buffer_data(radiance);
+    a->views.radiance = buffer_data(radiance);
     a->n = n;
-    a->n_views = n_views;
+    a->views.n_views = n_views;
 
     void* d_args = nullptr;
     if ((rc = ctx_device_args(ctx, a, sizeof(BeamViewArgs), &d_args))) return rc;

@@ -456,14 +456,16 @@ void launch_scatter_final_values(int nv, int slots, const double* partial, doubl
 // first kernel runs as it stands on the ScatterFluxArgs part of this block (the workspace is K5m's, four numbers per level),
 // then one upward walk that integrates the two-stream source function along every view.  No band sums: up_surface stays
 // nullptr, and the band fields of ColumnRT are not used.
-constexpr int kMaxScatterViews = 16;
-struct ScatterRadianceArgs : ScatterFluxArgs {
-    double view_mu[kMaxScatterViews];   // the viewing cosines, in (0, 1]; 1 beyond n_views
-    double view_rmu[kMaxScatterViews];  // 1 / mu_v, from the host
-    int32_t view_down[kMaxScatterViews];        // 0: upward at the top of the column; 1: downward at the surface
+constexpr int kMaxViews = 16;
+constexpr int kMaxScatterViews = kMaxViews, kMaxBeamViews = kMaxViews;     // (lbl_limit's scatter_views and beam_views)
+struct ViewPart {                       // the views of K5n and K5o
+    double view_mu[kMaxViews];          // the viewing cosines, in (0, 1]; 1 beyond n_views
+    double view_rmu[kMaxViews];         // 1 / mu_v, from the host
+    int32_t view_down[kMaxViews];       // 0: upward at the top of the column; 1: downward at the surface
     double* radiance;                   // n_views x n
     int32_t n_views, pad_views;
 };
+struct ScatterRadianceArgs : ScatterFluxArgs { ViewPart views; };
 // one pass over the points [first, first + count): first is a multiple of the tile and count <= ws_points
 void launch_scatter_radiance_pass(const ScatterRadianceArgs* d_args, bool linear, int n_views, long long first, long long count,
                                   hipStream_t s);
@@ -472,14 +474,9 @@ void launch_scatter_radiance_pass(const ScatterRadianceArgs* d_args, bool linear
 // whose first kernel runs as it stands on the TwoStreamArgs part of this block (the workspace is K5l's, five numbers per
 // level), then one upward walk that integrates the two-stream source function with the beam's single scattering along every
 // view.  No band sums: up_surface stays nullptr.
-constexpr int kMaxBeamViews = 16;
 struct BeamViewArgs : TwoStreamArgs {
-    double view_mu[kMaxBeamViews];      // the viewing cosines, in (0, 1]; 1 beyond n_views
-    double view_rmu[kMaxBeamViews];     // 1 / mu_v, from the host
-    int32_t view_down[kMaxBeamViews];   // 0: upward at the top of the column; 1: downward at the surface
-    double* radiance;                   // n_views x n
+    ViewPart views;
     long long n;                        // points of the grid: a view's row of `radiance`
-    int32_t n_views, pad_views;
 };
 // one pass over the points [first, first + count): first is a multiple of the tile and count <= ws_points
 void launch_beam_view_pass(const BeamViewArgs* d_args, int n_views, long long first, long long count, hipStream_t s);

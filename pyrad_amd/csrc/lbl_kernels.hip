@@ -4277,7 +4277,7 @@ __global__ __launch_bounds__(256) void solar_diffuse_kernel(const SolarArgs* __r
 // slot (tile of the band) % slots of the partials by the one workgroup that owns the slot, tiles ascending; the passes of a
 // band follow each other in stream order, so a slot's additions are the same whatever the pass size; column_flux_final_kernel
 // finishes.  No float atomics.
-// What the family's kernels (K5l here, K5m and K5n below) share.
+// What the family's kernels (K5l here; K5m, K5n, K5o and K5p below) share.
 // a point's scatterers, per unit amount: what each adds to a layer's absorption, scattering and asymmetry-weighted depths
 __device__ __forceinline__ void scatterer_numbers(const ScatterPart& A, long long j, double (&al)[kMaxScatterers],
                                                   double (&si)[kMaxScatterers], double (&et)[kMaxScatterers]) {
@@ -4389,6 +4389,17 @@ __device__ __forceinline__ void twostream_down_frame(const Args& A, unsigned thr
     }
 }
 
+// the end of a tile in the upward kernels (K5l, K5m, K5p): the four waves' rows acc[wave][0 .. nv), kSlot doubles apart, added
+// in a fixed order into the tile's slot of the partials
+template <int kSlot>
+__device__ __forceinline__ void tile_slot_add(double* slot, const double* acc, int nv, unsigned threads) {
+#pragma clang fp contract(off)
+    __syncthreads();
+    for (int t = threadIdx.x; t < nv; t += threads)
+        slot[t] = slot[t] + ((acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]));
+    __syncthreads();
+}
+
 // The upward walk of K5l and K5m over ROWS rows of level sums (up, diffuse down and, with 3, the direct flux of workspace
 // quantity 4): the tiles of this workgroup's slot in ascending order; per tile the surface - surface(active, j, Rs, Ds, F)
 // gives `up` there - then up and dn per level from the workspace alone, the spectra, the wave sums, and the tile's value
@@ -4442,12 +4453,49 @@ __device__ __forceinline__ void twostream_up_frame(const Args& A, unsigned threa
                 if (lane0) my[2 * levels + i] = s_F;
             }
         }
-        __syncthreads();
-        double* const slot = partial + ((tile0 + tile) % slots) * nv;
-        for (int t = threadIdx.x; t < nv; t += threads)
-            slot[t] = slot[t] + ((acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]));
-        __syncthreads();
+        tile_slot_add<kSlot>(partial + ((tile0 + tile) % slots) * nv, acc, nv, threads);
     }
+}
+
+// The upward walk that recomputes the layers (K5n, K5o, K5p): the point's scatterer numbers and the stack above the surface
+// from the downward kernel's workspace, then per layer twostream_layer, up <- U1 up + U0, Rs and Ds of the level above and
+// dn = Rs up + Ds, with up and dn of the level below kept.  Two calls, the kernel's level-0 work between them: surface(w)
+// gives `up` at the surface from w.Rs and w.Ds; layer(l, lay, k) sees the walk at the top of layer l; the NaN rule on w.up
+// ends it.  q: the point's place in the pass (K5p: the tile's first point in a lane beyond the pass).
+struct UpWalk {
+    const double* W; long long row; int levels;     // the point's workspace: quantity v at level i is W[(v levels + i) row]
+    double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
+    double Rs, Ds, up, dn;              // at the level the walk has reached
+    double upB, dnB;                    // up and dn at the level below it
+    bool bad;                           // some layer's t was not finite: every result of the point is NaN
+    __device__ __forceinline__ double ws(int v, int i) const { return W[((long long)v * levels + i) * row]; }
+};
+template <class Args, class Surface>
+__device__ __forceinline__ void twostream_up_start(const Args& A, long long q, long long j, UpWalk& w, Surface surface) {
+#pragma clang fp contract(off)
+    w.W = A.workspace + q; w.row = A.ws_points; w.levels = A.n_layers + 1;
+    scatterer_numbers(A, j, w.al, w.si, w.et);
+    w.Rs = w.ws(0, 0); w.Ds = w.ws(1, 0);
+    w.bad = isnan(w.Rs) || isnan(w.Ds);
+    w.up = surface(w);
+    w.dn = w.Rs * w.up + w.Ds;
+}
+template <class Args, class Layer>
+__device__ __forceinline__ void twostream_up_layers(const Args& A, long long j, UpWalk& w, Layer layer) {
+#pragma clang fp contract(off)
+    const int L = A.n_layers;
+    double k = L > 0 ? load_global_f64(A.abs_coef[0], j) : 0.0;
+    for (int l = 0; l < L; ++l) {
+        const double k_next = l + 1 < L ? load_global_f64(A.abs_coef[l + 1], j) : k;
+        const TwoStreamLayer lay = twostream_layer(A, l, A.depth[l], k, w.al, w.si, w.et);
+        w.upB = w.up; w.dnB = w.dn;
+        w.up = w.ws(2, l + 1) * w.up + w.ws(3, l + 1);
+        w.Rs = w.ws(0, l + 1); w.Ds = w.ws(1, l + 1);
+        w.dn = w.Rs * w.up + w.Ds;
+        layer(l, lay, k);
+        k = k_next;
+    }
+    if (w.bad) w.up = __builtin_nan("");
 }
 
 template <int NB>
@@ -4660,6 +4708,59 @@ __device__ __forceinline__ ViewWeights view_weights(double t, double lam, double
     return Y;
 }
 
+// The views of K5n and K5o over the upward walk: I and C per view, per layer what the weights take that does not depend on
+// the view, per view its weights and kap = w D g mu / 2, the source integral J from the kernel - source(down, mu, vw, hw, kap),
+// grouped as the kernel groups it - and the carry: an up view I <- Tv I + J, a down view I <- I + C J, C <- Tv C.
+template <int NV>
+struct ViewWalk {
+    double I[NV], C[NV];
+    template <class Args>
+    __device__ __forceinline__ void start(const Args& A, const ViewPart& V, long long j, const UpWalk& w) {
+#pragma clang fp contract(off)
+        if (A.down_surface) A.down_surface[j] = w.bad ? __builtin_nan("") : w.dn;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            I[v] = V.view_down[v] ? 0.0 : w.up / kPi;
+            C[v] = 1.0;
+        }
+    }
+    template <class Source>
+    __device__ __forceinline__ void layer(const ViewPart& V, const TwoStreamLayer& lay, Source source) {
+#pragma clang fp contract(off)
+        constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+        const double t = lay.t, lam = lay.lam, u = lam * t;
+        const double E = exp_neg_budget(u);
+        const double m2 = u == 0.0 ? 1.0 : fmin(2.0 * u, 2000.0) / -expm1(-2.0 * u);     // (E == 0 beyond 800)
+        const double hw = 0.5 * lay.w, Dg = D * lay.g;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const double mu = V.view_mu[v];
+            const ViewWeights vw = view_weights(t, lam, u, E, m2, mu, V.view_rmu[v]);
+            const double kap = hw * (Dg * mu);
+            const double J = source(V.view_down[v] != 0, mu, vw, hw, kap);
+            if (V.view_down[v]) {
+                I[v] = I[v] + C[v] * (J / kPi);
+                C[v] = C[v] * vw.Tv;
+            } else
+                I[v] = I[v] * vw.Tv + J / kPi;
+        }
+    }
+    // after the walk: the flux up at the top and the views' rows; arrive(I, C) gives a down view's radiance at the surface
+    template <class Args, class Arrive>
+    __device__ __forceinline__ void finish(const Args& A, const ViewPart& V, long long n, long long j, const UpWalk& w,
+                                           Arrive arrive) {
+#pragma clang fp contract(off)
+        if (A.up_top) A.up_top[j] = w.up;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            if (v < V.n_views) {
+                const double r = V.view_down[v] ? arrive(I[v], C[v]) : I[v];
+                V.radiance[(long long)v * n + j] = w.bad ? __builtin_nan("") : r;
+            }
+        }
+    }
+};
+
 template <bool LINEAR, int NV>
 __global__ __launch_bounds__(256) void scatter_radiance_up_kernel(const ScatterRadianceArgs* __restrict__ Ap, long long first,
                                                                   long long count) {
@@ -4668,80 +4769,34 @@ __global__ __launch_bounds__(256) void scatter_radiance_up_kernel(const ScatterR
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= count) return;
     const long long j = first + q;
-    const int L = A.n_layers;
-    const int levels = L + 1;
-    const long long row = A.ws_points;
-    const double* const W = A.workspace + q;
-    auto ws = [&](int v, int i) { return W[((long long)v * levels + i) * row]; };
     constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
-    double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
-    scatterer_numbers(A, j, al, si, et);
     const double nu = linspace_at(j, A.n, A.start, A.stop, A.step);
-    double Rs = ws(0, 0), Ds = ws(1, 0);
-    const bool bad = isnan(Rs) || isnan(Ds);
-    const double nan = __builtin_nan("");
-    double up = emitting_surface_up(A, j, nu, Rs, Ds);
-    double dn = Rs * up + Ds;
-    if (A.down_surface) A.down_surface[j] = bad ? nan : dn;
-    double I[NV], C[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        I[v] = A.view_down[v] ? 0.0 : up / kPi;
-        C[v] = 1.0;
-    }
-    double k = L > 0 ? load_global_f64(A.abs_coef[0], j) : 0.0;
+    UpWalk w;
+    twostream_up_start(A, q, j, w, [&](const UpWalk& s) { return emitting_surface_up(A, j, nu, s.Rs, s.Ds); });
+    ViewWalk<NV> views;
+    views.start(A, A.views, j, w);
     double B_below = 0.0;                           // LINEAR: pi B at the top edge of the layer below
-    for (int l = 0; l < L; ++l) {
-        const double k_next = l + 1 < L ? load_global_f64(A.abs_coef[l + 1], j) : k;
-        const TwoStreamLayer lay = twostream_layer(A, l, A.depth[l], k, al, si, et);
-        const double upB = up, dnB = dn;
-        up = ws(2, l + 1) * up + ws(3, l + 1);
-        Rs = ws(0, l + 1); Ds = ws(1, l + 1);
-        dn = Rs * up + Ds;
+    twostream_up_layers(A, j, w, [&](int l, const TwoStreamLayer& lay, double) {
         double Bb, Bt;
         planck_edge_pair<LINEAR>(A, nu, l, false, l == 0, B_below, Bb, Bt);
-        if (!lay.empty) {
-            const double t = lay.t, lam = lay.lam;
-            const double u = lam * t;
-            const double E = exp_neg_budget(u);
-            const double m2 = u == 0.0 ? 1.0 : fmin(2.0 * u, 2000.0) / -expm1(-2.0 * u);     // (E == 0 beyond 800)
-            const double c2 = LINEAR && lay.ta != 0.0 ? (2.0 * (Bb - Bt)) / (D * (t - lay.tsg)) : 0.0;
-            const double sig0 = (up + dn) - 2.0 * Bt, sigt = (upB + dnB) - 2.0 * Bb;      // top edge, bottom edge
-            const double del0 = up - dn, delt = upB - dnB;
-            const double hw = 0.5 * lay.w;
-            const double Dg = D * lay.g;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const double mu = A.view_mu[v];
-                const ViewWeights vw = view_weights(t, lam, u, E, m2, mu, A.view_rmu[v]);
-                const double tau = vw.tau, Tv = vw.Tv, Wp = vw.Wp, W1 = vw.W1;
-                const double Wt = -expm1(-tau);
-                const double gl = lbl::linear_source_g(tau, Tv);
-                const double kap = hw * (Dg * mu);
-                const double part = c2 * (Wt - Wp);
-                if (A.view_down[v]) {
-                    const double J = (Bt * Wt + gl * (Bb - Bt)) + hw * (sigt * Wp + (sig0 - sigt) * W1)
-                                     - kap * (part + (delt * Wp + (del0 - delt) * W1));
-                    I[v] = I[v] + C[v] * (J / kPi);
-                    C[v] = C[v] * Tv;
-                } else {
-                    const double J = (Bb * Wt + gl * (Bt - Bb)) + hw * (sig0 * Wp + (sigt - sig0) * W1)
-                                     + kap * (part + (del0 * Wp + (delt - del0) * W1));
-                    I[v] = I[v] * Tv + J / kPi;
-                }
-            }
-        }
-        k = k_next;
-    }
-    if (A.up_top) A.up_top[j] = bad ? nan : up;
+        if (lay.empty) return;
+        const double c2 = LINEAR && lay.ta != 0.0 ? (2.0 * (Bb - Bt)) / (D * (lay.t - lay.tsg)) : 0.0;
+        const double sig0 = (w.up + w.dn) - 2.0 * Bt, sigt = (w.upB + w.dnB) - 2.0 * Bb;      // top edge, bottom edge
+        const double del0 = w.up - w.dn, delt = w.upB - w.dnB;
+        views.layer(A.views, lay, [&](bool down, double, const ViewWeights& vw, double hw, double kap) {
+            const double Wp = vw.Wp, W1 = vw.W1;
+            const double Wt = -expm1(-vw.tau);
+            const double gl = lbl::linear_source_g(vw.tau, vw.Tv);
+            const double part = c2 * (Wt - Wp);
+            if (down)
+                return (Bt * Wt + gl * (Bb - Bt)) + hw * (sigt * Wp + (sig0 - sigt) * W1)
+                       - kap * (part + (delt * Wp + (del0 - delt) * W1));
+            return (Bb * Wt + gl * (Bt - Bb)) + hw * (sig0 * Wp + (sigt - sig0) * W1)
+                   + kap * (part + (del0 * Wp + (delt - del0) * W1));
+        });
+    });
     const double Itop = A.I_top ? load_global_f64(A.I_top, j) : 0.0;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        if (v < A.n_views) {
-            const double r = A.view_down[v] ? I[v] + C[v] * Itop : I[v];
-            A.radiance[(long long)v * A.n + j] = bad ? nan : r;
-        }
-    }
+    views.finish(A, A.views, A.n, j, w, [&](double I, double C) { return I + C * Itop; });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -4768,98 +4823,278 @@ __global__ __launch_bounds__(256) void beam_view_kernel(const BeamViewArgs* __re
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= count) return;
     const long long j = first + q;
-    const int L = A.n_layers;
-    const int levels = L + 1;
-    const long long row = A.ws_points;
-    const double* const W = A.workspace + q;
-    auto ws = [&](int v, int i) { return W[((long long)v * levels + i) * row]; };
     constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
-    double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
-    scatterer_numbers(A, j, al, si, et);
-    double Rs = ws(0, 0), Ds = ws(1, 0);
-    const double F0 = ws(4, 0);
-    const bool bad = isnan(Rs) || isnan(Ds);
-    const double nan = __builtin_nan("");
+    UpWalk w;
+    double F0 = 0.0;
     // K5l's surface (twostream_up_kernel)
-    const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
-    const double albedo = 1.0 - e;
-    double up = (albedo * (Ds + F0)) / (1.0 - albedo * Rs);
-    double dn = Rs * up + Ds;
-    if (A.down_surface) A.down_surface[j] = bad ? nan : dn;
-    if (A.direct_surface) A.direct_surface[j] = bad ? nan : F0;
-    double I[NV], C[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        I[v] = A.view_down[v] ? 0.0 : up / kPi;
-        C[v] = 1.0;
-    }
-    double k = L > 0 ? load_global_f64(A.abs_coef[0], j) : 0.0;
-    for (int l = 0; l < L; ++l) {
-        const double k_next = l + 1 < L ? load_global_f64(A.abs_coef[l + 1], j) : k;
-        const TwoStreamLayer lay = twostream_layer(A, l, A.depth[l], k, al, si, et);
-        const double upB = up, dnB = dn;
-        up = ws(2, l + 1) * up + ws(3, l + 1);
-        Rs = ws(0, l + 1); Ds = ws(1, l + 1);
-        dn = Rs * up + Ds;
-        const double Fd = ws(4, l + 1);
-        if (!lay.empty) {
-            const double t = lay.t, lam = lay.lam, w = lay.w, g = lay.g;
-            // the beam's terms, K5l's (twostream_down_kernel)
-            double tm = t * A.slant[0][l];
-            double m = A.m[0][l], rm = A.slant[0][l];
-            const double g3 = 0.5 * (1.0 - (D * g) * m), g4 = 1.0 - g3;
-            const double a2 = lay.g1 * g3 + lay.g2 * g4;
-            if (fabs(1.0 - lam * m) < 1e-6) {
-                m = (1.0 - 1e-6) / lam;
-                tm = t / m;
-                rm = 1.0 / m;
+    twostream_up_start(A, q, j, w, [&](const UpWalk& s) {
+        F0 = s.ws(4, 0);
+        const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
+        const double albedo = 1.0 - e;
+        return (albedo * (s.Ds + F0)) / (1.0 - albedo * s.Rs);
+    });
+    if (A.direct_surface) A.direct_surface[j] = w.bad ? __builtin_nan("") : F0;
+    ViewWalk<NV> views;
+    views.start(A, A.views, j, w);
+    twostream_up_layers(A, j, w, [&](int l, const TwoStreamLayer& lay, double) {
+        const double Fd = w.ws(4, l + 1);
+        if (lay.empty) return;
+        const double t = lay.t, lam = lay.lam;
+        // the beam's terms, K5l's (twostream_down_kernel)
+        double tm = t * A.slant[0][l];
+        double m = A.m[0][l], rm = A.slant[0][l];
+        const double g3 = 0.5 * (1.0 - (D * lay.g) * m), g4 = 1.0 - g3;
+        const double a2 = lay.g1 * g3 + lay.g2 * g4;
+        if (fabs(1.0 - lam * m) < 1e-6) {
+            m = (1.0 - 1e-6) / lam;
+            tm = t / m;
+            rm = 1.0 / m;
+        }
+        const double Tdm = exp_neg_budget(tm);
+        const double pole = (1.0 - lam * m) * (1.0 + lam * m);
+        const double Cp = (lay.w * (g3 - a2 * m)) / pole;
+        const double cu = (lay.w * (1.0 + (lay.Da * (g4 - g3)) * m)) / pole;
+        const double cs = Cp + (Cp - cu);               // Cp + Cm
+        const double Fb = Fd * Tdm;                     // the in-layer beam term at the bottom edge
+        const double sig0 = (w.up + w.dn) - cs * Fd, sigt = (w.upB + w.dnB) - cs * Fb;      // top edge, bottom edge
+        const double del0 = (w.up - w.dn) - cu * Fd, delt = (w.upB - w.dnB) - cu * Fb;
+        const double g3x = 3.0 * lay.g;
+        const double hs = (0.5 * lay.w) / D;
+        views.layer(A.views, lay, [&](bool down, double mu, const ViewWeights& vw, double hw, double kap) {
+            const double tau = vw.tau, Tv = vw.Tv, Wp = vw.Wp, W1 = vw.W1;
+            const double mr = mu * rm;
+            if (down) {
+                const double qb = 1.0 - mr;
+                const double xb = qb * tau, axb = fabs(xb);
+                const double Xd = (xb >= 0.0 ? Tdm : Tv) * (axb == 0.0 ? tau : -expm1(-axb) / fabs(qb));
+                const double beam = (hw * cs - kap * cu) + hs * (rm + g3x * mu);
+                return (hw * (sigt * Wp + (sig0 - sigt) * W1) - kap * (delt * Wp + (del0 - delt) * W1)) + (Fd * Xd) * beam;
             }
-            const double Tdm = exp_neg_budget(tm);
-            const double pole = (1.0 - lam * m) * (1.0 + lam * m);
-            const double Cp = (w * (g3 - a2 * m)) / pole;
-            const double cu = (w * (1.0 + (lay.Da * (g4 - g3)) * m)) / pole;
-            const double cs = Cp + (Cp - cu);               // Cp + Cm
-            const double Fb = Fd * Tdm;                     // the in-layer beam term at the bottom edge
-            const double sig0 = (up + dn) - cs * Fd, sigt = (upB + dnB) - cs * Fb;      // top edge, bottom edge
-            const double del0 = (up - dn) - cu * Fd, delt = (upB - dnB) - cu * Fb;
-            const double u = lam * t;
-            const double E = exp_neg_budget(u);
-            const double m2 = u == 0.0 ? 1.0 : fmin(2.0 * u, 2000.0) / -expm1(-2.0 * u);     // (E == 0 beyond 800)
-            const double hw = 0.5 * w;
-            const double Dg = D * g;
-            const double g3x = 3.0 * g;
-            const double hs = hw / D;
+            const double Xu = -expm1(-(tau + tm)) / (1.0 + mr);
+            const double beam = (hw * cs + kap * cu) + hs * (rm - g3x * mu);
+            return (hw * (sig0 * Wp + (sigt - sig0) * W1) + kap * (del0 * Wp + (delt - del0) * W1)) + (Fd * Xu) * beam;
+        });
+    });
+    views.finish(A, A.views, A.n, j, w, [](double I, double) { return I; });
+}
+
+// ----------------------------------------------------------------------------------------
+// K5p: Jacobians of the outgoing flux through scattering layers (lbl_column_jacobian_scatter_dev; the semantics and the
+// derivation are in include/pyrad_hip.h)
+// ----------------------------------------------------------------------------------------
+// The layer relations are linear in the fluxes, so F = up_L answers a change of one layer through two weights: with the stack
+// above level l + 1 (Rs', Tu' from the downward walk) and the stack below level l (A_l, built here going up)
+//     w1 = Tu' / ((1 - R Rs') - T^2 A_l Rs' / (1 - R A_l)),   w2 = w1 T A_l / (1 - R A_l)
+//     dF = w1 (dT up_l + dR dn_(l+1) + dP) + w2 (dT dn_(l+1) + dR up_l + dQ).
+//   scatter_jacobian_down_kernel<LINEAR>  K5m's downward walk (scatter_flux_down_walk: the same code, the same bits) with
+//                                         Tu_L = 1, Tu_i = Tu_(i+1) U1_(i+1) as a fifth number per level.
+//   scatter_jacobian_up_kernel<LINEAR>    the surface and its two rows, then bottom to top per layer: the layer recomputed as
+//                                         K5n does (twostream_layer), p dX/dp and q dX/dq of X = R, T, Ab and h in closed form
+//                                         (p = D ta, q = D (t - tsg); nothing is divided by sqrt(ta) or sqrt(q)), the two
+//                                         weights, the layer's rows and its terms (jacobian_terms).
+// One point per thread.  A workgroup takes the tiles of its partial slot in ascending order, as K5l's upward kernel does; per
+// tile every row is one wave_sum whose result lane 0 of each wave stores at acc[wave][row], the row order being jac's: F,
+// dF/dT_s, dF/de, L d ln tau, NT L temperatures (NT per layer), n_scat x L amounts, the terms.  Every row is stored once per
+// tile; then the four waves are added in a fixed order into the tile's slot.  4 x kScatterJacMaxSlots doubles of LDS
+// (45,152 bytes).  A lane beyond the pass's points computes the tile's first point again and adds zeros.
+// pi B and pi dB/dT at the bottom and top edge of layer l on the way up; LINEAR: the bottom edge is the top edge of the layer
+// below where the two temperatures are equal (a workgroup-uniform test), and then comes from cB, cdB
+template <bool LINEAR>
+__device__ __forceinline__ void planck_edge_pair_dT(const ScatterJacArgs& A, double nu, double pa_n, int l, double& cB,
+                                                    double& cdB, double& Bb, double& Bt, double& dBb, double& dBt) {
+#pragma clang fp contract(off)
+    double d;
+    if (!LINEAR) {
+        Bb = Bt = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT[l], 0.0, A.rT[l], &d);
+        dBb = dBt = kPi * d;
+        return;
+    }
+    if (l > 0 && A.pbkT[l] == A.pbkT_top[l - 1]) {
+        Bb = cB; dBb = cdB;
+    } else {
+        Bb = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT[l], 0.0, A.rT[l], &d);
+        dBb = kPi * d;
+    }
+    Bt = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT_top[l], 0.0, A.rT_top[l], &d);
+    dBt = kPi * d;
+    cB = Bt; cdB = dBt;
+}
+
+// p dX/dp and q dX/dq of a layer's R, T and Ab, p = D ta = r^2, q = D (t - tsg) = s^2: with x = r s, E = exp(-x),
+// Gam = (s - r) / (s + r), G = r s / (s + r)^2 = (1 - Gam^2) / 4, oE = 1 - E^2 and N = 1 - Gam^2 E^2 = 4 G + Gam^2 oE
+//     p R_p = G (-oE (1 + Gam^2 E^2) + 4 x Gam E^2) / N^2      q R_q = G (oE (1 + Gam^2 E^2) + 4 x Gam E^2) / N^2
+//     p T_p = 2 G E (Gam oE - x (1 + Gam^2 E^2)) / N^2         q T_q = -2 G E (Gam oE + x (1 + Gam^2 E^2)) / N^2
+//     p Ab_p = G (oE + 2 x E) / (1 + Gam E)^2                  q Ab_q = -G (oE - 2 x E) / (1 + Gam E)^2
+// (G / N <= 1 / 4: no quotient grows in a thin layer).  den == 0 (and N == 0): the branch's R = y / (1 + y), T = 1 / (1 + y),
+// y = (p + q) / 2, Ab = 0.
+struct TwoStreamLayerD {
+    double pR, qR, pT, qT, pAb, qAb;
+};
+__device__ __forceinline__ TwoStreamLayerD twostream_layer_partials(const TwoStreamLayer& lay, double p, double q) {
+#pragma clang fp contract(off)
+    TwoStreamLayerD Y;
+    const double r = sqrt(p), s = sqrt(q);
+    const double sr = s + r;
+    const double Gam = (s - r) / sr;
+    const double G = (r / sr) * (s / sr);
+    const double x = r * s;
+    const double E = exp_neg_budget(x);
+    const double oE = -expm1(-2.0 * x);
+    const double GE = Gam * E;
+    const double N = 4.0 * G + (Gam * Gam) * oE;
+    if (lay.conservative || !(N > 0.0)) {
+        const double i1 = 1.0 / (1.0 + 0.5 * (p + q));
+        Y.pR = (0.5 * p) * (i1 * i1); Y.qR = (0.5 * q) * (i1 * i1);
+        Y.pT = -Y.pR; Y.qT = -Y.qR;
+        Y.pAb = 0.0; Y.qAb = 0.0;
+        return Y;
+    }
+    const double gN = (G / N) / N;
+    const double m = 1.0 + GE * GE;
+    const double xE = x * E;
+    Y.pR = gN * (4.0 * (xE * GE) - oE * m);
+    Y.qR = gN * (4.0 * (xE * GE) + oE * m);
+    Y.pT = (2.0 * gN) * (GE * oE - xE * m);
+    Y.qT = -(2.0 * gN) * (GE * oE + xE * m);
+    const double S = G / ((1.0 + GE) * (1.0 + GE));
+    Y.pAb = S * (oE + 2.0 * xE);
+    Y.qAb = -(S * (oE - 2.0 * xE));
+    return Y;
+}
+
+// (K5d's, defined with the Jacobian kernels below)
+template <int NP, class Args, class Add>
+__device__ __forceinline__ void jacobian_terms(const Args& A, int l, long long j, bool active, const double (&Gd)[NP],
+                                               int slot0, Add add);
+
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void scatter_jacobian_down_kernel(const ScatterJacArgs* __restrict__ Ap, long long first,
+                                                                    long long count) {
+#pragma clang fp contract(off)
+    const int L = Ap->n_layers;
+    double Tu = 1.0;
+    scatter_flux_down_walk<LINEAR>(*Ap, blockDim.x, first, count, [&](int i, auto& ws) {
+        if (i < L) Tu = Tu * ws(2, i + 1);
+        ws(4, i) = Tu;
+    });
+}
+
+template <bool LINEAR>
+__global__ __launch_bounds__(256) void scatter_jacobian_up_kernel(const ScatterJacArgs* __restrict__ Ap, long long tile0,
+                                                                  long long first, long long count, int slots,
+                                                                  double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    constexpr int NT = LINEAR ? 2 : 1;
+    constexpr int kSlot = kScatterJacMaxSlots;
+    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
+    __shared__ double acc[4 * kSlot];               // [wave][row of jac]
+    const ScatterJacArgs& A = *Ap;
+    const int L = A.n_layers, C = A.n_scat;
+    const int nv = scatter_jacobian_slots(NT, L, C, A.n_terms);
+    const int row_T = 3 + L, row_scat = row_T + NT * L, row_term = row_scat + C * L;
+    double* const my = acc + (threadIdx.x >> 6) * kSlot;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const double nan = __builtin_nan("");
+    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
+    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions)
+    for (long long tile = blockIdx.x; tile < tiles; tile += slots) {
+        const long long q0 = tile * kTwoStreamTile;
+        const bool active = q0 + threadIdx.x < count;
+        const long long qq = active ? q0 + threadIdx.x : q0;
+        const long long j = first + qq;
+        auto add = [&](int slot, double v) {
+            const double s = wave_sum(active ? nan_to_num(v) : 0.0);
+            if (lane0) my[slot] = s;
+        };
+        // (jacobian_terms hands over a value that is masked and nan_to_num'ed already)
+        auto add_term = [&](int slot, double v) {
+            const double s = wave_sum(v);
+            if (lane0) my[slot] = s;
+        };
+        const double nu = linspace_at(j, A.n, A.start, A.stop, A.step);
+        const double pa_n = A.pa * (nu * nu * nu);
+        // the surface: up_0 = (e Es + (1 - e) Ds_0) / c0, c0 = 1 - (1 - e) Rs_0
+        UpWalk w;
+        twostream_up_start(A, qq, j, w, [&](const UpWalk& s) { return emitting_surface_up(A, j, nu, s.Rs, s.Ds); });
+        const bool bad = w.bad;
+        const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
+        {
+            double dBs = 0.0;
+            const double Is = A.I_surface ? A.I_surface[j]
+                                          : fold_planck<false, true>(false, nu, nu, pa_n, A.pbk_surface, 0.0, A.r_surface_T, &dBs);
+            const double gs = w.ws(4, 0) / (1.0 - (1.0 - e) * w.Rs);
+            add(1, bad ? nan : (gs * e) * (kPi * dBs));
+            add(2, bad ? nan : gs * (kPi * Is - w.dn));
+        }
+        double Al = 1.0 - e;                            // what the stack below level l reflects
+        double cB = 0.0, cdB = 0.0;                     // LINEAR: pi B and pi dB/dT at the top edge of the layer below
+        twostream_up_layers(A, j, w, [&](int l, const TwoStreamLayer& lay, double k) {
+            const double depth = A.depth[l];
+            const double upB = w.upB, dn = w.dn, Rs = w.Rs;
+            const double R = lay.R, T = lay.T, Ab = lay.Ab;
+            const double TA = (T * Al) / (1.0 - R * Al);
+            const double w1 = w.ws(4, l + 1) / ((1.0 - R * Rs) - (T * TA) * Rs);
+            const double w2 = w1 * TA;
+            Al = R + T * TA;
+            double Bb, Bt, dBb, dBt;
+            planck_edge_pair_dT<LINEAR>(A, nu, pa_n, l, cB, cdB, Bb, Bt, dBb, dBt);
+            const double tq = lay.t - lay.tsg;
+            double pF = 0.0, qF = 0.0, gT[NT];
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const double mu = A.view_mu[v];
-                const ViewWeights vw = view_weights(t, lam, u, E, m2, mu, A.view_rmu[v]);
-                const double tau = vw.tau, Tv = vw.Tv, Wp = vw.Wp, W1 = vw.W1;
-                const double kap = hw * (Dg * mu);
-                const double mr = mu * rm;
-                if (A.view_down[v]) {
-                    const double qb = 1.0 - mr;
-                    const double xb = qb * tau, axb = fabs(xb);
-                    const double Xd = (xb >= 0.0 ? Tdm : Tv) * (axb == 0.0 ? tau : -expm1(-axb) / fabs(qb));
-                    const double beam = (hw * cs - kap * cu) + hs * (rm + g3x * mu);
-                    const double J = (hw * (sigt * Wp + (sig0 - sigt) * W1) - kap * (delt * Wp + (del0 - delt) * W1))
-                                     + (Fd * Xd) * beam;
-                    I[v] = I[v] + C[v] * (J / kPi);
-                    C[v] = C[v] * Tv;
-                } else {
-                    const double Xu = -expm1(-(tau + tm)) / (1.0 + mr);
-                    const double beam = (hw * cs + kap * cu) + hs * (rm - g3x * mu);
-                    const double J = (hw * (sig0 * Wp + (sigt - sig0) * W1) + kap * (del0 * Wp + (delt - del0) * W1))
-                                     + (Fd * Xu) * beam;
-                    I[v] = I[v] * Tv + J / kPi;
+            for (int i = 0; i < NT; ++i) gT[i] = 0.0;
+            if (!lay.empty) {
+                const TwoStreamLayerD d = twostream_layer_partials(lay, D * lay.ta, D * tq);
+                double pP = 0.0, qP = 0.0, pQ = 0.0, qQ = 0.0;
+                if (!(lay.conservative || lay.ta == 0.0)) {        // (else nothing absorbs: P = Q = 0)
+                    if (LINEAR) {
+                        const double dq = D * tq;
+                        const double h = (Ab + 2.0 * R) / dq - T;
+                        const double ph = (d.pAb + 2.0 * d.pR) / dq - d.pT;
+                        const double qh = ((d.qAb + 2.0 * d.qR) - (Ab + 2.0 * R)) / dq - d.qT;
+                        const double dB = Bb - Bt;
+                        pP = Bt * d.pAb + dB * ph; pQ = Bb * d.pAb - dB * ph;
+                        qP = Bt * d.qAb + dB * qh; qQ = Bb * d.qAb - dB * qh;
+                        gT[0] = (w1 * h + w2 * (Ab - h)) * dBb;
+                        gT[NT - 1] = (w1 * (Ab - h) + w2 * h) * dBt;
+                    } else {
+                        pP = pQ = Bb * d.pAb;
+                        qP = qQ = Bb * d.qAb;
+                        gT[0] = ((w1 + w2) * Ab) * dBb;
+                    }
+                }
+                pF = w1 * ((d.pT * upB + d.pR * dn) + pP) + w2 * ((d.pT * dn + d.pR * upB) + pQ);
+                qF = w1 * ((d.qT * upB + d.qR * dn) + qP) + w2 * ((d.qT * dn + d.qR * upB) + qQ);
+            }
+            // per unit of ta and of t - tsg: dF/dta = fa + fq, dF/dts = fq, dF/dtsg = -fq
+            const double fa = lay.ta > 0.0 ? pF / lay.ta : 0.0;
+            const double fq = tq > 0.0 ? qF / tq : 0.0;
+            double Gd[1] = {depth * (fa + fq)};
+            double dtau = k * Gd[0];
+            if (bad) {
+                Gd[0] = dtau = nan;
+#pragma unroll
+                for (int i = 0; i < NT; ++i) gT[i] = nan;
+            }
+            if (active && A.ln_tau_spec) A.ln_tau_spec[(long long)l * A.n + j] = dtau;
+            add(3 + l, dtau);
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                if (active && A.T_spec) A.T_spec[(long long)(NT * l + i) * A.n + j] = gT[i];
+                add(row_T + NT * l + i, gT[i]);
+            }
+#pragma unroll
+            for (int c = 0; c < kMaxScatterers; ++c) {          // (n_scat is uniform over the workgroup)
+                if (c < C) {
+                    const double v = A.amount[c][l] * (w.al[c] * (fa + fq) + (w.si[c] - w.et[c]) * fq);
+                    add(row_scat + c * L + l, bad ? nan : v);
                 }
             }
-        }
-        k = k_next;
+            jacobian_terms<1>(A, l, j, active, Gd, row_term, add_term);
+        });
+        if (active && A.up_top) A.up_top[j] = w.up;
+        add(0, w.up);
+        tile_slot_add<kSlot>(partial + ((tile0 + tile) % slots) * nv, acc, nv, blockDim.x);
     }
-    if (A.up_top) A.up_top[j] = bad ? nan : up;
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-        if (v < A.n_views) A.radiance[(long long)v * A.n + j] = bad ? nan : I[v];
 }
 
 // ----------------------------------------------------------------------------------------
@@ -6253,238 +6488,6 @@ void launch_solar(const SolarArgs* d_args, int n_layers, int n_beams, int n_angl
         launch_column_band<4>(solar_diffuse_kernel<4, NA>, solar_diffuse_kernel<1, NA>, d_args, levels, first, count, partial,
                               level_flux, s);
     });
-}
-
-// ----------------------------------------------------------------------------------------
-// K5p: Jacobians of the outgoing flux through scattering layers (lbl_column_jacobian_scatter_dev; the semantics and the
-// derivation are in include/pyrad_hip.h)
-// ----------------------------------------------------------------------------------------
-// The layer relations are linear in the fluxes, so F = up_L answers a change of one layer through two weights: with the stack
-// above level l + 1 (Rs', Tu' from the downward walk) and the stack below level l (A_l, built here going up)
-//     w1 = Tu' / ((1 - R Rs') - T^2 A_l Rs' / (1 - R A_l)),   w2 = w1 T A_l / (1 - R A_l)
-//     dF = w1 (dT up_l + dR dn_(l+1) + dP) + w2 (dT dn_(l+1) + dR up_l + dQ).
-//   scatter_jacobian_down_kernel<LINEAR>  K5m's downward walk (scatter_flux_down_walk: the same code, the same bits) with
-//                                         Tu_L = 1, Tu_i = Tu_(i+1) U1_(i+1) as a fifth number per level.
-//   scatter_jacobian_up_kernel<LINEAR>    the surface and its two rows, then bottom to top per layer: the layer recomputed as
-//                                         K5n does (twostream_layer), p dX/dp and q dX/dq of X = R, T, Ab and h in closed form
-//                                         (p = D ta, q = D (t - tsg); nothing is divided by sqrt(ta) or sqrt(q)), the two
-//                                         weights, the layer's rows and its terms (jacobian_terms).
-// One point per thread.  A workgroup takes the tiles of its partial slot in ascending order, as K5l's upward kernel does; per
-// tile every row is one wave_sum whose result lane 0 of each wave stores at acc[wave][row], the row order being jac's: F,
-// dF/dT_s, dF/de, L d ln tau, NT L temperatures (NT per layer), n_scat x L amounts, the terms.  Every row is stored once per
-// tile; then the four waves are added in a fixed order into the tile's slot.  4 x kScatterJacMaxSlots doubles of LDS
-// (45,152 bytes).  A lane beyond the pass's points computes the tile's first point again and adds zeros.
-// pi B and pi dB/dT at the bottom and top edge of layer l on the way up; LINEAR: the bottom edge is the top edge of the layer
-// below where the two temperatures are equal (a workgroup-uniform test), and then comes from cB, cdB
-template <bool LINEAR>
-__device__ __forceinline__ void planck_edge_pair_dT(const ScatterJacArgs& A, double nu, double pa_n, int l, double& cB,
-                                                    double& cdB, double& Bb, double& Bt, double& dBb, double& dBt) {
-#pragma clang fp contract(off)
-    double d;
-    if (!LINEAR) {
-        Bb = Bt = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT[l], 0.0, A.rT[l], &d);
-        dBb = dBt = kPi * d;
-        return;
-    }
-    if (l > 0 && A.pbkT[l] == A.pbkT_top[l - 1]) {
-        Bb = cB; dBb = cdB;
-    } else {
-        Bb = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT[l], 0.0, A.rT[l], &d);
-        dBb = kPi * d;
-    }
-    Bt = kPi * fold_planck<false, true>(false, nu, nu, pa_n, A.pbkT_top[l], 0.0, A.rT_top[l], &d);
-    dBt = kPi * d;
-    cB = Bt; cdB = dBt;
-}
-
-// p dX/dp and q dX/dq of a layer's R, T and Ab, p = D ta = r^2, q = D (t - tsg) = s^2: with x = r s, E = exp(-x),
-// Gam = (s - r) / (s + r), G = r s / (s + r)^2 = (1 - Gam^2) / 4, oE = 1 - E^2 and N = 1 - Gam^2 E^2 = 4 G + Gam^2 oE
-//     p R_p = G (-oE (1 + Gam^2 E^2) + 4 x Gam E^2) / N^2      q R_q = G (oE (1 + Gam^2 E^2) + 4 x Gam E^2) / N^2
-//     p T_p = 2 G E (Gam oE - x (1 + Gam^2 E^2)) / N^2         q T_q = -2 G E (Gam oE + x (1 + Gam^2 E^2)) / N^2
-//     p Ab_p = G (oE + 2 x E) / (1 + Gam E)^2                  q Ab_q = -G (oE - 2 x E) / (1 + Gam E)^2
-// (G / N <= 1 / 4: no quotient grows in a thin layer).  den == 0 (and N == 0): the branch's R = y / (1 + y), T = 1 / (1 + y),
-// y = (p + q) / 2, Ab = 0.
-struct TwoStreamLayerD {
-    double pR, qR, pT, qT, pAb, qAb;
-};
-__device__ __forceinline__ TwoStreamLayerD twostream_layer_partials(const TwoStreamLayer& lay, double p, double q) {
-#pragma clang fp contract(off)
-    TwoStreamLayerD Y;
-    const double r = sqrt(p), s = sqrt(q);
-    const double sr = s + r;
-    const double Gam = (s - r) / sr;
-    const double G = (r / sr) * (s / sr);
-    const double x = r * s;
-    const double E = exp_neg_budget(x);
-    const double oE = -expm1(-2.0 * x);
-    const double GE = Gam * E;
-    const double N = 4.0 * G + (Gam * Gam) * oE;
-    if (lay.conservative || !(N > 0.0)) {
-        const double i1 = 1.0 / (1.0 + 0.5 * (p + q));
-        Y.pR = (0.5 * p) * (i1 * i1); Y.qR = (0.5 * q) * (i1 * i1);
-        Y.pT = -Y.pR; Y.qT = -Y.qR;
-        Y.pAb = 0.0; Y.qAb = 0.0;
-        return Y;
-    }
-    const double gN = (G / N) / N;
-    const double m = 1.0 + GE * GE;
-    const double xE = x * E;
-    Y.pR = gN * (4.0 * (xE * GE) - oE * m);
-    Y.qR = gN * (4.0 * (xE * GE) + oE * m);
-    Y.pT = (2.0 * gN) * (GE * oE - xE * m);
-    Y.qT = -(2.0 * gN) * (GE * oE + xE * m);
-    const double S = G / ((1.0 + GE) * (1.0 + GE));
-    Y.pAb = S * (oE + 2.0 * xE);
-    Y.qAb = -(S * (oE - 2.0 * xE));
-    return Y;
-}
-
-template <bool LINEAR>
-__global__ __launch_bounds__(256) void scatter_jacobian_down_kernel(const ScatterJacArgs* __restrict__ Ap, long long first,
-                                                                    long long count) {
-#pragma clang fp contract(off)
-    const int L = Ap->n_layers;
-    double Tu = 1.0;
-    scatter_flux_down_walk<LINEAR>(*Ap, blockDim.x, first, count, [&](int i, auto& ws) {
-        if (i < L) Tu = Tu * ws(2, i + 1);
-        ws(4, i) = Tu;
-    });
-}
-
-template <bool LINEAR>
-__global__ __launch_bounds__(256) void scatter_jacobian_up_kernel(const ScatterJacArgs* __restrict__ Ap, long long tile0,
-                                                                  long long first, long long count, int slots,
-                                                                  double* __restrict__ partial) {
-#pragma clang fp contract(off)
-    constexpr int NT = LINEAR ? 2 : 1;
-    constexpr int kSlot = kScatterJacMaxSlots;
-    constexpr double D = 1.7320508075688772;        // sqrt(3), rounded
-    __shared__ double acc[4 * kSlot];               // [wave][row of jac]
-    const ScatterJacArgs& A = *Ap;
-    const int L = A.n_layers, levels = L + 1, C = A.n_scat;
-    const int nv = scatter_jacobian_slots(NT, L, C, A.n_terms);
-    const int row_T = 3 + L, row_scat = row_T + NT * L, row_term = row_scat + C * L;
-    const long long row = A.ws_points;
-    double* const my = acc + (threadIdx.x >> 6) * kSlot;
-    const bool lane0 = (threadIdx.x & 63) == 0;
-    const double nan = __builtin_nan("");
-    const long long tiles = (count + kTwoStreamTile - 1) / kTwoStreamTile;
-    // (the loop bound is uniform over the workgroup: every lane takes part in the wave reductions)
-    for (long long tile = blockIdx.x; tile < tiles; tile += slots) {
-        const long long q0 = tile * kTwoStreamTile;
-        const bool active = q0 + threadIdx.x < count;
-        const long long qq = active ? q0 + threadIdx.x : q0;
-        const long long j = first + qq;
-        const double* const W = A.workspace + qq;
-        auto ws = [&](int v, int i) { return W[((long long)v * levels + i) * row]; };
-        auto add = [&](int slot, double v) {
-            const double s = wave_sum(active ? nan_to_num(v) : 0.0);
-            if (lane0) my[slot] = s;
-        };
-        // (jacobian_terms hands over a value that is masked and nan_to_num'ed already)
-        auto add_term = [&](int slot, double v) {
-            const double s = wave_sum(v);
-            if (lane0) my[slot] = s;
-        };
-        double al[kMaxScatterers], si[kMaxScatterers], et[kMaxScatterers];
-        scatterer_numbers(A, j, al, si, et);
-        const double nu = linspace_at(j, A.n, A.start, A.stop, A.step);
-        const double pa_n = A.pa * (nu * nu * nu);
-        double Rs = ws(0, 0), Ds = ws(1, 0);
-        const bool bad = isnan(Rs) || isnan(Ds);
-        // the surface: up_0 = (e Es + (1 - e) Ds_0) / c0, c0 = 1 - (1 - e) Rs_0
-        const double e = A.emissivity ? A.emissivity[j] : A.emissivity_all;
-        double up = emitting_surface_up(A, j, nu, Rs, Ds);
-        double dn = Rs * up + Ds;
-        {
-            double dBs = 0.0;
-            const double Is = A.I_surface ? A.I_surface[j]
-                                          : fold_planck<false, true>(false, nu, nu, pa_n, A.pbk_surface, 0.0, A.r_surface_T, &dBs);
-            const double gs = ws(4, 0) / (1.0 - (1.0 - e) * Rs);
-            add(1, bad ? nan : (gs * e) * (kPi * dBs));
-            add(2, bad ? nan : gs * (kPi * Is - dn));
-        }
-        double Al = 1.0 - e;                            // what the stack below level l reflects
-        double k = L > 0 ? load_global_f64(A.abs_coef[0], j) : 0.0;
-        double cB = 0.0, cdB = 0.0;                     // LINEAR: pi B and pi dB/dT at the top edge of the layer below
-        for (int l = 0; l < L; ++l) {
-            const double k_next = l + 1 < L ? load_global_f64(A.abs_coef[l + 1], j) : k;
-            const double depth = A.depth[l];
-            const TwoStreamLayer lay = twostream_layer(A, l, depth, k, al, si, et);
-            const double upB = up;
-            up = ws(2, l + 1) * up + ws(3, l + 1);
-            Rs = ws(0, l + 1); Ds = ws(1, l + 1);
-            dn = Rs * up + Ds;
-            const double R = lay.R, T = lay.T, Ab = lay.Ab;
-            const double TA = (T * Al) / (1.0 - R * Al);
-            const double w1 = ws(4, l + 1) / ((1.0 - R * Rs) - (T * TA) * Rs);
-            const double w2 = w1 * TA;
-            Al = R + T * TA;
-            double Bb, Bt, dBb, dBt;
-            planck_edge_pair_dT<LINEAR>(A, nu, pa_n, l, cB, cdB, Bb, Bt, dBb, dBt);
-            const double tq = lay.t - lay.tsg;
-            double pF = 0.0, qF = 0.0, gT[NT];
-#pragma unroll
-            for (int i = 0; i < NT; ++i) gT[i] = 0.0;
-            if (!lay.empty) {
-                const TwoStreamLayerD d = twostream_layer_partials(lay, D * lay.ta, D * tq);
-                double pP = 0.0, qP = 0.0, pQ = 0.0, qQ = 0.0;
-                if (!(lay.conservative || lay.ta == 0.0)) {        // (else nothing absorbs: P = Q = 0)
-                    if (LINEAR) {
-                        const double dq = D * tq;
-                        const double h = (Ab + 2.0 * R) / dq - T;
-                        const double ph = (d.pAb + 2.0 * d.pR) / dq - d.pT;
-                        const double qh = ((d.qAb + 2.0 * d.qR) - (Ab + 2.0 * R)) / dq - d.qT;
-                        const double dB = Bb - Bt;
-                        pP = Bt * d.pAb + dB * ph; pQ = Bb * d.pAb - dB * ph;
-                        qP = Bt * d.qAb + dB * qh; qQ = Bb * d.qAb - dB * qh;
-                        gT[0] = (w1 * h + w2 * (Ab - h)) * dBb;
-                        gT[NT - 1] = (w1 * (Ab - h) + w2 * h) * dBt;
-                    } else {
-                        pP = pQ = Bb * d.pAb;
-                        qP = qQ = Bb * d.qAb;
-                        gT[0] = ((w1 + w2) * Ab) * dBb;
-                    }
-                }
-                pF = w1 * ((d.pT * upB + d.pR * dn) + pP) + w2 * ((d.pT * dn + d.pR * upB) + pQ);
-                qF = w1 * ((d.qT * upB + d.qR * dn) + qP) + w2 * ((d.qT * dn + d.qR * upB) + qQ);
-            }
-            // per unit of ta and of t - tsg: dF/dta = fa + fq, dF/dts = fq, dF/dtsg = -fq
-            const double fa = lay.ta > 0.0 ? pF / lay.ta : 0.0;
-            const double fq = tq > 0.0 ? qF / tq : 0.0;
-            double Gd[1] = {depth * (fa + fq)};
-            double dtau = k * Gd[0];
-            if (bad) {
-                Gd[0] = dtau = nan;
-#pragma unroll
-                for (int i = 0; i < NT; ++i) gT[i] = nan;
-            }
-            if (active && A.ln_tau_spec) A.ln_tau_spec[(long long)l * A.n + j] = dtau;
-            add(3 + l, dtau);
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                if (active && A.T_spec) A.T_spec[(long long)(NT * l + i) * A.n + j] = gT[i];
-                add(row_T + NT * l + i, gT[i]);
-            }
-#pragma unroll
-            for (int c = 0; c < kMaxScatterers; ++c) {          // (n_scat is uniform over the workgroup)
-                if (c < C) {
-                    const double v = A.amount[c][l] * (al[c] * (fa + fq) + (si[c] - et[c]) * fq);
-                    add(row_scat + c * L + l, bad ? nan : v);
-                }
-            }
-            jacobian_terms<1>(A, l, j, active, Gd, row_term, add_term);
-            k = k_next;
-        }
-        if (bad) up = nan;
-        if (active && A.up_top) A.up_top[j] = up;
-        add(0, up);
-        __syncthreads();
-        double* const slot = partial + ((tile0 + tile) % slots) * nv;
-        for (int t = threadIdx.x; t < nv; t += blockDim.x)
-            slot[t] = slot[t] + ((acc[t] + acc[kSlot + t]) + (acc[2 * kSlot + t] + acc[3 * kSlot + t]));
-        __syncthreads();
-    }
 }
 
 // K5l, K5m: the partial-sum slots of a band of `count` points

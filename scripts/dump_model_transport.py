@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The model-level sibling of dump_transport.py: every Atmosphere method over the column transport entry points (fluxes,
 jacobians, jacobiansLinear, observe, observeLinear, radiance, pathJacobians, pathJacobiansLinear, solarFluxesTwoStream,
-fluxesTwoStream, radianceTwoStream) over its option matrix on
+fluxesTwoStream, radianceTwoStream, solarRadianceTwoStream, jacobiansTwoStream) over its option matrix on
 a seeded synthetic column, every array of every result saved as .npy (one file per call, the arrays concatenated in the
 order of their attribute names), and beside them calls.txt: every Context.column_* / ray_* / ils_convolve_dev call and every
 Buffer upload, download and device copy, with its arguments by value (arrays of more than 32 values as length and SHA-1 of
@@ -206,7 +206,7 @@ def transport_calls(save):
 
 
 def scatter_calls(save):
-    """solarFluxesTwoStream, fluxesTwoStream and radianceTwoStream: no scatterers and two (numbers, n values and a table,
+    """solarFluxesTwoStream, fluxesTwoStream, jacobiansTwoStream, radianceTwoStream and solarRadianceTwoStream: no scatterers and two (numbers, n values and a table,
     mixed), deltaScaling, the emissivity forms, planck, bands, spectra, more views than one chunk, with and without instrument"""
     atm = column(RNG, LAYERS)
     x = atm[0].xAxis
@@ -237,15 +237,26 @@ def scatter_calls(save):
                             save("fluxesTwoStream_" + u + "_" + tag(planck=planck),
                                  atm.fluxesTwoStream(scat, delta, surfaceTemperature=290.0, topSpectrum=top, emissivity=e,
                                                      planck=planck, bands=b, spectra=spectra))
+                            save("jacobiansTwoStream_" + u + "_" + tag(planck=planck),
+                                 atm.jacobiansTwoStream(scat, delta, surfaceTemperature=290.0, topSpectrum=top, emissivity=e,
+                                                        planck=planck, bands=b, molecules=b is None, spectra=spectra))
                 for planck in ("layer", "linear"):
                     for views in (few, many):
                         for instrument in (None, ins):
                             save("radianceTwoStream_" + t + "_" + tag(planck=planck, views=len(views), ins=instrument is not None),
                                  atm.radianceTwoStream(views, scat, delta, surfaceTemperature=290.0, topSpectrum=top,
                                                        emissivity=e, planck=planck, instrument=instrument))
+                for views in (few, many) if scat else (few,):       # (without scatterers a down view is 0 throughout)
+                    for instrument in (None, ins):
+                        save("solarRadianceTwoStream_" + t + "_" + tag(views=len(views), ins=instrument is not None),
+                             atm.solarRadianceTwoStream(views, scat, delta, solarTemperature=5772.0, mu0=0.5, emissivity=e,
+                                                        instrument=instrument))
     kw = dict(surfaceSpectrum=surface, emissivity=e_arr, planck="linear", levelTemperatures=LEVELS)
     save("fluxesTwoStream_surfaceSpectrum", atm.fluxesTwoStream((cloud, haze), bands=bands, spectra=True, **kw))
     save("radianceTwoStream_surfaceSpectrum", atm.radianceTwoStream(many, (cloud, haze), instrument=ins, **kw))
+    save("jacobiansTwoStream_surfaceSpectrum", atm.jacobiansTwoStream((cloud, haze), bands=bands, spectra=True, **kw))
+    save("solarRadianceTwoStream_spectrum", atm.solarRadianceTwoStream(many, cloud, solarSpectrum=surface, mu0=0.4,
+                                                                       geometry="spherical", instrument=ins))
     save("solarFluxesTwoStream_spectrum", atm.solarFluxesTwoStream(cloud, solarSpectrum=surface, mu0=0.4, geometry="spherical",
                                                                    spectra=True))
 
@@ -258,6 +269,9 @@ def voigt_calls(save):
     atm = column(VOIGT_RNG, VOIGT_LAYERS)
     for name in ("jacobians", "jacobiansLinear"):
         save(name + "_full", getattr(atm, name)(surfaceTemperature=288.0, temperature="full", emissivity=0.8, spectra=True))
+    for planck in ("layer", "linear"):
+        save("jacobiansTwoStream_full_" + planck, atm.jacobiansTwoStream(surfaceTemperature=288.0, temperature="full",
+                                                                         emissivity=0.8, planck=planck, spectra=True))
 
 
 def run(out):

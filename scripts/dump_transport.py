@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Every column transport entry point (K5c - K5n: fluxes, Jacobians, ray paths, reflecting surface, linear source, solar
+"""Every column transport entry point (K5c - K5p: fluxes, Jacobians, ray paths, reflecting surface, linear source, solar
 beam, the two-stream family) through _native.Context on synthetic, seeded absorption coefficients, every output saved as .npy (one file per call,
 its outputs concatenated): run once per library build (PYRAD_HIP_LIB) and compare the files bit for bit
 (scripts/bitcmp_libs.sh <lib a> <lib b> dump_transport.py).  No line lists are needed.  The shapes are the smallest at
 which the kernels' frames can go wrong: bands with head, aligned and tail points, a band of three points, a grid-stride
 second round in some workgroups only, every angle count (1 to 8: each is an instantiation of its own), both Planck paths,
-bundled and single rays with a surface marker, a tail launch; for the two-stream family (K5l, K5m, K5n) see
-scatter_calls.  Per entry point of that family refusals_<name>.npy holds, as bytes, the return code and lbl_last_error of
+bundled and single rays with a surface marker, a tail launch; for the two-stream family (K5l - K5p) see
+scatter_calls and pole_column.  Every output buffer of the family's two youngest (K5o, K5p) must hold a finite value that is
+not zero, or the script fails: a dump of zeros compares equal and says nothing.  Per entry point of that family refusals_<name>.npy holds, as bytes, the return code and lbl_last_error of
 calls with one defect and with two: which of two defects is reported is part of what two builds must agree on.
 usage: dump_transport.py <out dir>"""
 import ctypes as C
@@ -38,10 +39,15 @@ def empty(n):
     return b
 
 
-def save(name, *bufs):
-    """one file per call: the call's output buffers, concatenated"""
+def save(name, *bufs, live=False, zero=()):
+    """one file per call: the call's output buffers, concatenated.  live: every buffer must hold a finite value that is not
+    zero, but for those in `zero`, which the call's arguments make zero throughout"""
     ctx.sync()
-    values = np.concatenate([b.download(b.n) for b in bufs])
+    parts = [b.download(b.n) for b in bufs]
+    for i, (b, v) in enumerate(zip(bufs, parts)):
+        if live and not any(b is z for z in zero) and not np.any(np.isfinite(v) & (v != 0.0)):
+            sys.exit("%s: output buffer %d holds no finite value that is not zero" % (name, i))
+    values = np.concatenate(parts)
     np.save(os.path.join(out, name + ".npy"), values)
     tally[0] += 1
     tally[1] += values.size
@@ -211,7 +217,7 @@ def ray_calls(tag, c):
         save(t + "_spectrum_ray_jacobian_linear", jac, rad)
 
 
-# ---- K5l, K5m, K5n: solar and thermal fluxes and radiances through scattering layers ------------------------------------------
+# ---- K5l - K5p: solar and thermal fluxes and radiances through scattering layers ------------------------------------------
 class ScatterColumn:
     """L layers (optical depths 1e-3 .. tau_hi each) on n points from 600 cm^-1 in steps of 0.01, with four scatterers whose
     numbers come as buffers and as plain numbers, mixed.  `special`: layer 1 empty (t = 0), layer 2 conservative (no gas, the
@@ -228,6 +234,9 @@ class ScatterColumn:
                 self.amount[c][1] = 0.0
                 self.amount[c][2] = 0.8 if c == 1 else 0.0
         self.k = [dev(v) for v in k]
+        # two molecule terms, as Column's (K5p)
+        self.term_layer = [0, L - 1] if L else []
+        self.term_k = [dev(np.exp(rng.uniform(np.log(1e-4), np.log(1.0), n)) / self.depth[l]) for l in self.term_layer]
         self.T = [288.0 - 0.5 * l for l in range(L)]
         # (bottom edge, top edge): two of three top edges are the next layer's bottom edge, the third is 0.3 K off it
         bottom = [292.0 - 0.5 * l for l in range(L + 1)]
@@ -245,8 +254,36 @@ class ScatterColumn:
         return [a[:count] for a in (self.amount, self.ext, self.ssa, self.asym)]
 
 
+class PoleColumn(ScatterColumn):
+    """The column of pole_case (tests/test_beam_view_cpu.py) at L = 2 and n = 259: one scatterer of plain numbers, and the
+    first beam's slant in layer 1 is lam of point 2 there, so that lam m = 1 to rounding at that point - and at every fourth
+    point, which has its coefficient: K5l and K5o move m there (|1 - lam m| < 1e-6) and keep it at the other points."""
+    def __init__(self):
+        L, n, j = 2, 259, 2
+        super().__init__(L, n)
+        k = 10.0 ** rng.uniform(-2, 1, (L, n)) / np.array(self.depth)[:, None]
+        k[1, j % 4::4] = k[1, j]
+        self.k = [dev(v) for v in k]
+        self.amount = [[0.5, 2.0]]
+        self.ext, self.ssa, self.asym = [1.0], [0.6], [0.5]
+        # lam as twostream_layer forms it (delta scaling on)
+        ext, ssa, g = self.ext[0], self.ssa[0], self.asym[0]
+        f = g * g
+        al, si, et = ext * (1.0 - ssa), (ext * ssa) * (1.0 - f), (ext * ssa) * (g - f)
+        am = self.amount[0][1]
+        ta, ts, tsg = k[1] * self.depth[1] + am * al, am * si, am * et
+        t = ta + ts
+        D = 1.7320508075688772
+        lam = np.sqrt((D * (ta / t)) * (D * ((t - tsg) / t)))
+        assert 1.0 < lam[j] < D, lam[j]                  # (so that m = 1 / lam is a sun's cosine)
+        self.slant0 = [1.3, float(lam[j])]
+        self.in_window = int(np.count_nonzero(np.abs(1.0 - lam * (1.0 / self.slant0[1])) < 1e-6))
+
+
 SCATTER_WORKSPACE = dict(twostream=ctx.column_twostream_workspace, flux_scatter=ctx.column_flux_scatter_workspace,
-                         radiance_scatter=ctx.column_radiance_scatter_workspace)
+                         radiance_scatter=ctx.column_radiance_scatter_workspace,
+                         beam_radiance=ctx.column_beam_radiance_workspace,
+                         jacobian_scatter=ctx.column_jacobian_scatter_workspace)
 
 
 def mixed_views(count):
@@ -255,8 +292,9 @@ def mixed_views(count):
 
 def scatter_calls(tag, c, bands=None, n_scat=4, delta=1, e="arr", surface="spectrum", top=True, spectra=True, ws="wide",
                   linear=(1,), beams=(2,), views=(3,)):
-    """K5l for every beam count in `beams`, K5m and K5n for both or one Planck setting in `linear`, K5n for every view
-    count in `views`; ws: a workspace of one tile ("tile") or one that holds the widest band ("wide")"""
+    """K5l for every beam count in `beams`, K5o with one beam for every view count in `views`, K5m, K5p and K5n for both
+    or one Planck setting in `linear`, K5n for every view count in `views`; ws: a workspace of one tile ("tile") or one that
+    holds the widest band ("wide").  A column's `slant0` is the first beam's slants."""
     L, n = c.L, c.n
     first, count = bands if bands else ([0], [n])
     nb = len(first)
@@ -268,14 +306,27 @@ def scatter_calls(tag, c, bands=None, n_scat=4, delta=1, e="arr", surface="spect
 
     def work(family, points):
         return empty(SCATTER_WORKSPACE[family](L, 1 if ws == "tile" else points))
+    def slants(ns):
+        slant = [[1.0 + 0.5 * s + 0.1 * (l % 5) for l in range(L)] for s in range(ns)]
+        return [getattr(c, "slant0", slant[0])] + slant[1:]
     for ns in beams:
         bw = [1.0 / (s + 1) for s in range(ns)]
-        slant = [[1.0 + 0.5 * s + 0.1 * (l % 5) for l in range(L)] for s in range(ns)]
+        slant = slants(ns)
         levels = empty(nb * 3 * (L + 1))
         ctx.column_twostream_dev(c.k, c.depth, c.lo, c.hi, n, c.S0, bw, slant, *c.scat(n_scat), delta, first, count,
                                  work("twostream", max(count)), levels, emissivity=e, up_top=spec[0], down_surface=spec[1],
                                  direct_surface=spec[2], up_surface=spec[3])
         save("%s_b%d_twostream" % (tag, ns), levels, *kept)
+    for nv in views:
+        mu, down = mixed_views(nv)
+        rad = empty(nv * n)
+        for b in kept:                  # (what an earlier call left there must not pass for this call's)
+            b.fill(0.0)
+        ctx.column_beam_radiance_dev(c.k, c.depth, c.lo, c.hi, n, c.S0, 0.8, slants(1)[0], *c.scat(n_scat), delta, mu, down,
+                                     work("beam_radiance", n), rad, emissivity=e, up_top=spec[0], down_surface=spec[1],
+                                     direct_surface=spec[2])
+        # (no layer or no scatterer: nothing is scattered down to the surface)
+        save("%s_v%d_beam_radiance" % (tag, nv), rad, *kept[:3], live=True, zero=kept[1:2] if L == 0 or n_scat == 0 else ())
     for lin in linear:
         T = c.edge_T if lin else c.T
         levels = empty(nb * 2 * (L + 1))
@@ -283,6 +334,18 @@ def scatter_calls(tag, c, bands=None, n_scat=4, delta=1, e="arr", surface="spect
                                     work("flux_scatter", max(count)), levels, emissivity=e, up_top=spec[0],
                                     down_surface=spec[1], up_surface=spec[3], **src)
         save("%s_p%d_flux_scatter" % (tag, lin), levels, *kept[:2], *kept[3:])
+        nt = 2 if lin else 1
+        jac = empty(nb * (3 + (1 + nt + n_scat) * L + len(c.term_k)))
+        # (no layer: no rows of spectra)
+        ln_tau, T_spec = (empty(L * n), empty(nt * L * n)) if spectra and L else (None, None)
+        for b in kept[:1]:
+            b.fill(0.0)
+        ctx.column_jacobian_scatter_dev(c.k, T, lin, c.depth, c.lo, c.hi, n, *c.scat(n_scat), delta, first, count,
+                                        work("jacobian_scatter", max(count)), jac, emissivity=e, term_abs_coef=c.term_k,
+                                        term_layer=c.term_layer, ln_tau_spectra=ln_tau, T_spectra=T_spec, up_top=spec[0],
+                                        **src)
+        save("%s_p%d_jacobian_scatter" % (tag, lin), jac, *[b for b in (ln_tau, T_spec) if b is not None], *kept[:1],
+             live=True)
         for nv in views:
             mu, down = mixed_views(nv)
             rad = empty(nv * n)
@@ -314,6 +377,11 @@ def scatter_family():
                   views=(1, 16))
     scatter_calls("deep_onetile", ScatterColumn(nat.limit("layers_per_column"), 259, tau_hi=0.3), ws="tile", n_scat=2)
     scatter_calls("wrap", ScatterColumn(1, 256 * 1025 + 7), linear=(0, 1), views=(2,))
+    pole = PoleColumn()
+    print("pole column: lam m within 1e-6 of 1 at %d of %d points of layer 1" % (pole.in_window, pole.n))
+    if pole.in_window == 0:
+        sys.exit("the pole column has no point inside |1 - lam m| < 1e-6")
+    scatter_calls("pole", pole, n_scat=1, linear=(), beams=(1, 2), views=(1, 3))
 
 
 def refusal_calls():
@@ -347,7 +415,15 @@ def refusal_calls():
                           down_surface=spec[1].h, up_surface=spec[3].h),
         radiance_scatter=dict(**head, **edges, **grid, **thermal, **scat, **surface, n_views=V, view_mu=f64([1.0, 0.5, 0.2]),
                               view_down=i32([0, 1, 0]), workspace=empty(2 * tiles["radiance_scatter"]).h,
-                              radiance=empty(V * n).h, up_top=spec[0].h, down_surface=spec[1].h))
+                              radiance=empty(V * n).h, up_top=spec[0].h, down_surface=spec[1].h),
+        beam_radiance=dict(**head, **grid, S0=c.S0.h, beam_weight=0.5, slant=f64([2.0, 1.9, 1.8]), **scat, **surface,
+                           n_views=V, view_mu=f64([1.0, 0.5, 0.2]), view_down=i32([0, 1, 0]),
+                           workspace=empty(2 * tiles["beam_radiance"]).h, radiance=empty(V * n).h, up_top=spec[0].h,
+                           down_surface=spec[1].h, direct_surface=spec[2].h),
+        jacobian_scatter=dict(**head, **edges, **grid, **thermal, **scat, **bands, **surface, n_terms=2,
+                              term_abs_coef=ptrs([b.h for b in c.term_k]), term_layer=i32(c.term_layer),
+                              workspace=empty(2 * tiles["jacobian_scatter"]).h, jac=empty(3 + 5 * L + 2).h,
+                              ln_tau_spectra=empty(L * n).h, T_spectra=empty(2 * L * n).h, up_top=spec[0].h))
     # the defect kinds of the three test_refusals, by the argument they spoil
     shared = [dict(abs_coef=None), dict(depth=None), dict(scat_amount=None), dict(workspace=None), dict(n_layers=-1),
               dict(n_layers=nat.limit("layers_per_column") + 1), dict(n=-5), dict(n_scat=-1),
@@ -366,6 +442,9 @@ def refusal_calls():
               dict(I_surface=None, surface_T=nan), dict(T=f64([290.0, 280.0, 280.0, 0.0, 255.0, 240.0])),
               dict(T=f64([nan, 280.0, 280.0, 260.0, 255.0, 240.0])), dict(planck_linear=0, T=f64([290.0, nan, 250.0])),
               dict(planck_linear=0, T=f64([290.0, 270.0, inf])), dict(planck_linear=2)]
+    viewed = [dict(radiance=None), dict(view_mu=None), dict(view_down=None), dict(n=0), dict(n_views=0),
+              dict(view_mu=f64([1.0, 0.0, 0.2])), dict(view_mu=f64([1.0, nan, 0.2])), dict(view_down=i32([0, 2, 0])),
+              dict(radiance=n_short.h)]
     own = dict(
         twostream=banded + [dict(S0=None), dict(beam_weight=None), dict(slant=None), dict(n_beams=0), dict(S0=n_short.h),
                             dict(n_beams=nat.limit("flux_angles") + 1), dict(direct_surface=n_short.h),
@@ -373,13 +452,23 @@ def refusal_calls():
                             dict(slant=f64([2.0, 1.9, 1.8, 1.0, 0.0, 1.0])), dict(slant=f64([2.0, inf, 1.8, 1.0, 1.0, 1.0])),
                             dict(beam_weight=f64([0.5, inf]))],
         flux_scatter=banded + heated + [dict(workspace=empty(tiles["flux_scatter"] - 1).h)],
-        radiance_scatter=heated + [dict(radiance=None), dict(view_mu=None), dict(view_down=None), dict(n=0), dict(n_views=0),
-                                   dict(n_views=nat.limit("scatter_views") + 1), dict(view_mu=f64([1.0, 0.0, 0.2])),
-                                   dict(view_mu=f64([1.0, nan, 0.2])), dict(view_down=i32([0, 2, 0])),
-                                   dict(radiance=n_short.h), dict(workspace=empty(tiles["radiance_scatter"] - 1).h)])
+        radiance_scatter=heated + viewed + [dict(n_views=nat.limit("scatter_views") + 1),
+                                            dict(workspace=empty(tiles["radiance_scatter"] - 1).h)],
+        beam_radiance=viewed + [dict(n_views=nat.limit("beam_views") + 1), dict(S0=None), dict(slant=None), dict(S0=n_short.h),
+                                dict(direct_surface=n_short.h), dict(workspace=empty(tiles["beam_radiance"] - 1).h),
+                                dict(slant=f64([2.0, 0.0, 1.8])), dict(slant=f64([2.0, inf, 1.8])), dict(beam_weight=inf),
+                                dict(beam_weight=-0.5)],
+        jacobian_scatter=banded + heated + [dict(workspace=empty(tiles["jacobian_scatter"] - 1).h), dict(jac=None),
+                                            dict(jac=empty(3 + 5 * L + 1).h), dict(n_terms=-1),
+                                            dict(n_terms=nat.limit("jacobian_terms") + 1), dict(term_abs_coef=None),
+                                            dict(term_layer=None), dict(term_layer=i32([0, L])), dict(term_layer=i32([-1, 0])),
+                                            dict(term_abs_coef=ptrs([n_short.h, c.term_k[1].h])),
+                                            dict(ln_tau_spectra=n_short.h), dict(T_spectra=n_short.h)])
     for name, base in good.items():
         entry = getattr(ctx.lib, "lbl_column_%s_dev" % name)
-        defects = shared + own[name]
+        absent = {"level_flux", "down_surface", "up_surface"} if name == "jacobian_scatter" else set()   # (K5p: jac, up_top)
+        defects = [d for d in shared + own[name] if not set(d) & absent]
+        assert all(set(d) <= set(base) for d in defects), name
         calls = [{}] + defects + [dict(a, **b) for a, b in itertools.combinations(defects, 2) if not set(a) & set(b)]
         record = bytearray()
         for kw in calls:
